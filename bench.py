@@ -2,6 +2,7 @@
 """bench.py -- line-triangulation hot path on N MI355X GPUs (one process per GPU).
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR   # + the last timed step's results as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -466,6 +467,44 @@ _REAL_STDOUT = None
 ONE_GPU = os.environ.get("LT_BENCH_ONE_GPU") == "1"
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(ctx, out_dir, suffix=""):
+    """`--dump-outputs DIR`: what the timed step hands its caller -- the per-node results of the last device run (best
+    candidate per node, its support score and source, candidate counts, the valid edges) -- as DIR/<name>.npy in float64,
+    so that two builds can be compared output for output.  Valid edges are sorted inside every node (their order there has
+    no observable effect: it feeds a std::set).  Above 64 MB in all, a fixed seeded sample of the nodes is written (the
+    sampled node indices are in `node_index`).  Returns {name: shape}."""
+    best = ctx.get_best()
+    n_tris = ctx.get_num_tris()
+    off, edges = ctx.get_valid_edges()
+    G = len(n_tris)
+    node = np.repeat(np.arange(G, dtype=np.int64), np.diff(off))
+    order = np.lexsort((edges[:, 1], edges[:, 0], node)) if len(edges) else np.zeros(0, np.int64)
+    edges = edges[order]
+    per_node = 10 + 1 + 2 + 1 + 1 + 1 + 1   # best_line, best_score, best_src, has_best, num_tris, node_index, edge count
+    take = G
+    while take > 0 and 8 * (per_node * take + 2 * len(edges) * take / max(G, 1)) > 0.9 * DUMP_LIMIT_BYTES:
+        take //= 2
+    idx = np.arange(G, dtype=np.int64) if take == G else np.sort(np.random.default_rng(0).choice(G, take, replace=False))
+    cnt = np.diff(off)[idx]
+    keep = np.zeros(G, bool)
+    keep[idx] = True
+    sel = np.nonzero(keep[node])[0]   # (node is ascending: the sampled nodes' edges stay in node order)
+    arrays = {"node_index": idx, "best_line": best["line"][idx], "best_score": best["score"][idx],
+              "best_src": best["src"][idx], "has_best": best["has_best"][idx], "num_tris": n_tris[idx],
+              "valid_edge_count": cnt, "valid_edges": edges[sel].reshape(-1, 2)}
+    arrays = {k: np.ascontiguousarray(v, np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + suffix + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
+
+
 def _comm_dev(dev):
     """device of the small tensors that go through collectives"""
     import torch
@@ -592,7 +631,14 @@ def main():
                          "outside observer -- rocm-smi -- sees the device busy); 0 = off")
     ap.add_argument("--e2e-child", nargs=5, type=int, metavar=("VIEWS", "SEGS", "NEIGHBORS", "SEED", "TOPK"),
                     help="internal: the end-to-end call sequence in this (torch-free) process, see e2e_child")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: write the per-node results of the last timed step as DIR/<name>.npy "
+                         "(float64, at most 64 MB; see dump_outputs)")
     args = ap.parse_args()
+    if args.dump_outputs and args.stream:
+        ap.error("--dump-outputs is not available with --stream")
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs --steps >= 1")
     if args.e2e_child:
         return e2e_child(*args.e2e_child)
     if args.config3:
@@ -760,6 +806,9 @@ def main():
     if acc.get("survivors", 0.0) == 0.0:  # counted on demand when the run did not have it on the host
         acc["survivors"] = last["survivors"] * max(args.steps, 1)
     kt = {k: v / max(args.steps, 1) for k, v in acc.items()}  # average HIP-event ms per launch
+    dumped = None
+    if args.dump_outputs:  # the results of the last timed step, read back after the clock has stopped
+        dumped = dump_outputs(ctx, args.dump_outputs, suffix=f"_rank{rank}" if world > 1 else "")
     # The timed region carries the events around the dominant stage only (scoring = k_score_q: roofline).  The generation
     # kernels are priced in a few extra steps with their own events on (LT_FINE_TIMERS=2 costs ~5 us per step).
     if args.mode == "matched":
@@ -953,6 +1002,8 @@ def main():
                       "images_per_rank": per_rank_imgs, "allgather_alone_us": allgather_us},
             "device_source_hash": device_source_hash(),
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
 
     # ---- the same step, sustained: the timed region above is a few milliseconds of a process that runs for tens of
     # seconds; this loop keeps the device on the step for --sustain-s so that an observer outside the process (the driver's

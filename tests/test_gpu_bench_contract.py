@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -107,3 +108,34 @@ def test_bench_two_ranks_on_one_gpu(gpu_lib):
     assert "error" not in t2 and t2["note"] is None and "error" not in t1 and t1["note"] is None, (t2, t1)
     assert t2["n_gpus"] == 2 and t2["chunks"] == t1["chunks"] == 5
     assert t2["candidates"] == t1["candidates"] > 0 and t2["connections"] == t1["connections"] and t2["tracks"] == t1["tracks"] > 0
+
+
+def test_bench_dump_outputs_are_the_timed_steps_results(gpu_lib, oracle, tmp_path):
+    """--dump-outputs DIR: the per-node results of the last timed step as float64 .npy files, --steps timed steps in the
+    line; the arrays are the CPU oracle's for the same seeded scene (best candidate, its geometry, candidate counts, the
+    valid edges sorted inside every node)."""
+    from limap_amd import synthetic as syn
+    from helpers import run_oracle
+    out = tmp_path / "dump"
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+                          "--views", "12", "--segs", "60", "--neighbors", "5", "--no-cpu-baseline", "--no-extras",
+                          "--sustain-s", "0", "--dump-outputs", str(out)],
+                         stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=ROOT)
+    assert res.returncode == 0, res.stderr[-2000:]
+    d = json.loads(res.stdout.strip().splitlines()[-1])
+    assert d["steps"] == 4 and d["ms_per_step"] > 0 and d["dumped_outputs"]["dir"] == str(out)
+    got = {f[:-4]: np.load(str(out / f)) for f in os.listdir(str(out))}
+    assert set(got) == set(d["dumped_outputs"]["arrays"])
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    sc = syn.make_scene(n_views=12, n_segs=60, n_neighbors=5, n_rooms=1, n_gt=None, seed=0, topk=10)
+    O = run_oracle(oracle, sc, syn.default_triangulation_cfg(), topk=10)
+    ob, (ooff, oe) = O.get_best(), O.get_valid_edges()
+    assert np.array_equal(got["node_index"], np.arange(O.num_nodes()))
+    assert np.array_equal(got["has_best"], ob["has_best"]) and np.array_equal(got["best_src"], ob["src"])
+    assert np.array_equal(got["best_line"], ob["line"])
+    np.testing.assert_allclose(got["best_score"], ob["score"], rtol=1e-12, atol=0)
+    assert np.array_equal(got["num_tris"], O.get_num_tris())
+    assert np.array_equal(got["valid_edge_count"], np.diff(ooff))
+    node = np.repeat(np.arange(len(ooff) - 1), np.diff(ooff))
+    assert len(oe) > 0 and np.array_equal(got["valid_edges"], oe[np.lexsort((oe[:, 1], oe[:, 0], node))])
