@@ -280,6 +280,28 @@ int lt_ts_filter_by_overlap(lt_ctx *ctx, lt_trackset *ts, double th_overlap, int
  * l3_* fields of linker_cfg; the all-pairs connection test runs on the GPU */
 int lt_ts_remerge_once(lt_ctx *ctx, lt_trackset *ts, const lt_config *linker_cfg, int num_outliers);
 
+/* ---- limap.merging.merging / MergeToLineTracks (merging/merging.py:6-21, merging/merging.cc:347-511): the merge of
+ * one fitted 3D segment per 2D segment (runners/line_fitnmerge.py) into line tracks.  The context is initialised
+ * (lt_init) with the cameras and the 2D segments; seg3d = per image in ascending id order, per line, start3 end3
+ * (seg3d_off[n_img+1] offsets in segments: each image needs as many 3D as 2D segments, else LT_ERR_ARGUMENT); a
+ * zero-length segment is not a node.  Neighbours as CSR over the images in ascending id order: nb_ids[nb_off[i] ..
+ * nb_off[i+1]) in list order (an id that is not an image: LT_ERR_ARGUMENT).  The 2D linker is read from the l2_* fields
+ * of linker_cfg, the 3D linker from the l3_* fields, switched to set_to_spatial_merging().  Every line gets
+ * uncertainty = computeUncertainty(view, var2d).  The pair tests run on the GPU.  *out: a new track set (members in node
+ * order, score = length, line3d10 with depths 0 and score -1, track line = aggregate with num_outliers 0); free it with
+ * lt_ts_destroy.  The graph stays in the context until the next call. ---- */
+int lt_merge_to_tracks(lt_ctx *ctx, const int64_t *seg3d_off, const double *seg3d, const int64_t *nb_off,
+                       const int32_t *nb_ids, const lt_config *linker_cfg, double var2d, lt_trackset **out);
+/* the graph of the last lt_merge_to_tracks: node count, edge count */
+int lt_merge_graph_size(lt_ctx *ctx, int64_t *n_nodes, int64_t *n_edges);
+/* nodes (image id, line id) in node order; edges (node_idx1, node_idx2, sim) in the reference's insertion order
+ * (Graph::undirected_edges); any pointer may be NULL */
+int lt_merge_graph_get(lt_ctx *ctx, int32_t *node_img, int32_t *node_line, int32_t *edge_n1, int32_t *edge_n2,
+                       double *edge_sim);
+/* of the last lt_merge_to_tracks: [0] device ms of the pair kernels (HIP events, last attempt), [1] host ms of the
+ * whole call, [2] kernel attempts (more than 1 after an edge-buffer overflow), [3] edges */
+int lt_merge_get_timers(lt_ctx *ctx, double out[4]);
+
 /* Counters of the last device run: [0] connections tested, [1] candidates, [2] ordered candidate
  * pairs swept by the scoring kernel (sum n_tris^2), [3] valid edges, [4] graph nodes,
  * [5] graph edges, [6] tracks, [7] nodes. */

@@ -389,6 +389,12 @@ struct lt_ctx {
   long long pend_C = 0;
   int pend_ev_gen_end = 3, pend_ev_place_end = 4;
   long long C_last = 0;  // candidates of the last lt_run_device (known on the host once the scoring grid is sized)
+  // ---- MergeToLineTracks (lt_merge.cpp): the graph of the last lt_merge_to_tracks ----
+  std::vector<int> mg_node_img, mg_node_line;  // node -> image id, line id (node order)
+  std::vector<int> mg_e1, mg_e2;               // edges in the reference's insertion order
+  std::vector<double> mg_sim;
+  double mg_timers[4] = {0, 0, 0, 0};          // lt_merge_get_timers
+  DevBuf d_mg_lines, d_mg_blks, d_mg_edges;
 };
 
 #define HIPCHK(ctx, call)                                                                  \

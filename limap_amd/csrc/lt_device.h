@@ -105,6 +105,27 @@ void launch_tail_compact(hipStream_t st, long long E, const unsigned long long *
 void launch_tail_gather(hipStream_t st, long long G, const unsigned *mark, const long long *pos, const Cand *best_c,
                         const double *best_score, const int *best_src2, void *recs, int *nodes, long long *n_out);
 
+// MergeToLineTracks (merging/merging.cc:347-511), lt_kernels_merge.hip / lt_merge.cpp
+struct MLine {  // 128 B: one 3D segment of the merge with its image's 2D segment
+  double s[3], e[3];
+  double dir[3];  // Line3d::direction() = unit(e - s), exactly what angle_between computes
+  double unc;     // computeUncertainty(camview(img), var2d)
+  double len;     // Line3d::length(); 0: not a node
+  double seg[4];  // the 2D segment x1 y1 x2 y2
+  double pad_;
+};
+static_assert(sizeof(MLine) == 128, "MLine layout");
+struct MBlock {  // one workgroup: rows [row0, row0 + 256) of image `img` against neighbour image `nb` (slot -1: self)
+  int img, nb, slot, row0;
+  int img_id, nb_id, pad_[2];
+};
+struct MEdge {  // an accepted pair: (image index, line) of the emitting image, neighbour slot (-1: self pass), line
+  int img, line, slot, ng_line;
+};
+void launch_merge_pairs(hipStream_t st, bool self, int n_blk, const MBlock *blks, const long long *seg_off,
+                        const MLine *lines, const Cam *cams, const LinkCfg2 &l2, const LinkCfg3 &l3, double cos_guard,
+                        int parity_fast, MEdge *edges, unsigned long long capacity, unsigned long long *n_edges);
+
 void launch_track_connect(hipStream_t st, int T, const double *line7, const unsigned char *active, int all_active,
                           const LinkCfg3 &cfg, double cos_guard, unsigned long long *edges,
                           unsigned long long capacity, unsigned long long *n_edges);

@@ -432,6 +432,41 @@ LT_HD double score2d(const LinkCfg2 &c, const L2 &l1, const L2 &l2) {
   return score;
 }
 
+// LineLinker2d::check_connection, line_linker.cc:120-137 (+ its check_connection_* at :67-118): angle <= th_angle
+// directly, overlap > th_overlap, the other gates through their scores (MergeToLineTracks, merging/merging.cc:347-511)
+LT_HD bool check2d(const LinkCfg2 &c, const L2 &l1, const L2 &l2) {
+  double ang = 0.0;
+  bool have_ang = false;
+  if (c.use_angle) {  // :67-71
+    ang = angle_between(l1, l2);
+    have_ang = true;
+    if (!(ang <= c.th_angle)) return false;
+  }
+  double ov = 0.0;
+  bool have_ov = false;
+  if (c.use_overlap) {  // :79-91
+    ov = bioverlap(l1, l2);
+    have_ov = true;
+    if (!(ov > c.th_overlap)) return false;
+  }
+  if (c.use_angle && c.use_overlap && c.use_smartangle) {  // :73-77, :49-65
+    if (!have_ang) ang = angle_between(l1, l2);
+    if (!have_ov) ov = bioverlap(l1, l2);
+    double th = c.th_angle;
+    if (ov < c.th_smartoverlap) {
+      double ratio = (c.th_smartoverlap - ov) / (c.th_smartoverlap - c.th_overlap);
+      ratio = dmin(ratio, 1.0);
+      th = c.th_angle - ratio * (c.th_angle - c.th_smartangle);
+    }
+    if (!(gate(expscore(ang, th * c.mult), c.score_th) >= c.score_th)) return false;
+  }
+  if (c.use_perp)  // :93-104
+    if (!(gate(expscore(perp_dist(l1, l2), c.th_perp * c.mult), c.score_th) >= c.score_th)) return false;
+  if (c.use_innerseg)  // :106-118
+    if (!(gate(expscore(innerseg_dist(l1, l2), c.th_innerseg * c.mult), c.score_th) >= c.score_th)) return false;
+  return true;
+}
+
 // LineLinker3d::compute_score, line_linker.cc:306-331 (general form; unc = line uncertainties,
 // dep1 = depths of l1 for the one-way scale-invariant endpoint distance, line_dists.cc:55-60)
 LT_HD double score3d(const LinkCfg3 &c, const L3 &l1, const L3 &l2, double unc1, double unc2,

@@ -32,6 +32,47 @@ inline int uf_root(int i, std::vector<int> &parent) {  // base/graph.cc:156-165 
   return r;
 }
 
+// Track labels of ComputeLineTrackLabelsGreedy (merging/merging.cc:18-103) over a graph whose edges are already in the
+// reference's union order (descending (sim, idx1, idx2)): the root whose image set is smaller joins the other (equal
+// sizes: the second joins the first), then labels from the parent array as it stands after the unions -- a node that
+// never joined anything keeps -1.  Used by MergeToLineTracks (lt_merge.cpp); the triangulation tail (lt_api_tail.cpp)
+// keeps its own arena-based form of the same loop.  Returns the number of tracks.
+struct UnionEdge {
+  double sim;
+  int n1, n2;
+};
+inline int greedy_track_labels(int n_nodes, const int *node_img, const std::vector<UnionEdge> &edges,
+                               std::vector<int> &labels) {
+  std::vector<int> parent((size_t)n_nodes, -1);
+  std::vector<std::vector<int>> images((size_t)n_nodes);  // images_in_track: sorted, distinct
+  for (int i = 0; i < n_nodes; ++i) images[(size_t)i].assign(1, node_img[i]);
+  std::vector<int> merged;
+  for (const UnionEdge &e : edges) {
+    int r1 = uf_root(e.n1, parent), r2 = uf_root(e.n2, parent);
+    if (r1 == r2) continue;
+    int dst = r1, src = r2;
+    if (images[(size_t)r1].size() < images[(size_t)r2].size()) { dst = r2; src = r1; }
+    parent[(size_t)src] = dst;
+    std::vector<int> &a = images[(size_t)dst], &b = images[(size_t)src];
+    merged.resize(a.size() + b.size());
+    merged.resize((size_t)(std::set_union(a.begin(), a.end(), b.begin(), b.end(), merged.begin()) - merged.begin()));
+    a.swap(merged);
+    std::vector<int>().swap(b);
+  }
+  labels.assign((size_t)n_nodes, -1);
+  int n_tracks = 0;
+  for (int i = 0; i < n_nodes; ++i) {
+    if (parent[(size_t)i] == -1) continue;
+    const int p = parent[(size_t)i];
+    if (parent[(size_t)p] == -1 && labels[(size_t)p] == -1) labels[(size_t)p] = n_tracks++;
+  }
+  for (int i = 0; i < n_nodes; ++i) {
+    if (parent[(size_t)i] == -1) continue;
+    labels[(size_t)i] = labels[(size_t)uf_root(i, parent)];
+  }
+  return n_tracks;
+}
+
 // Principal axis of a centred point set = Eigen::JacobiSVD(points, ComputeThinV).matrixV().col(0) of
 // merging/aggregator.cc:76-78, computed by Eigen 3.4's own procedure (lt_svd.h: column-pivoted Householder QR, two-sided
 // Jacobi sweeps, descending sort) so that the SIGN of the direction -- it decides which end of the aggregated line is

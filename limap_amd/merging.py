@@ -1,5 +1,6 @@
-"""Host-side mirror of the `limap.merging` functions that follow ComputeLineTracks inside
-`limap.runners.line_triangulation` (runners/line_triangulation.py:171-200; python wrappers
+"""Mirror of `limap.merging`: `merging` (MergeToLineTracks, merging/merging.py:6-21, merging/merging.cc:347-511), the
+merge of `limap.runners.line_fitnmerge`, with its pair tests on the GPU; and the functions that follow
+ComputeLineTracks inside `limap.runners.line_triangulation` (runners/line_triangulation.py:171-200; python wrappers
 merging/merging.py:24-100, C++ merging/merging_utils.cc:27-155 and merging/merging.cc:513-644):
 
     filter_tracks_by_reprojection, remerge, filter_tracks_by_sensitivity, filter_tracks_by_overlap
@@ -24,6 +25,111 @@ def _linker_cfg(linker3d):
         conf = getattr(linker3d, "config", linker3d)
         d = {k: getattr(conf, k) for k in _capi.L3_KEYS if hasattr(conf, k)}
     return _capi.config_from_dict({"linker3d_config": d})
+
+
+def _conf_dict(obj, keys):
+    """a linker config as a dict: a dict itself, a LineLinker2d/3d (`.config`) or a config object"""
+    if isinstance(obj, dict):
+        return dict(obj)
+    conf = getattr(obj, "config", obj)
+    if isinstance(conf, dict):
+        return dict(conf)
+    return {k: getattr(conf, k) for k in keys if hasattr(conf, k)}
+
+
+def _merge_linker_cfg(linker):
+    """LineLinker-like (`.linker_2d` / `.linker_3d`) or {"linker2d": ..., "linker3d": ...} (cfg["merging"])."""
+    if isinstance(linker, dict):
+        d2 = linker.get("linker2d", linker.get("linker2d_config")) or {}
+        d3 = linker.get("linker3d", linker.get("linker3d_config")) or {}
+    else:
+        d2 = getattr(linker, "linker_2d", None)
+        d3 = getattr(linker, "linker_3d", None)
+        if d2 is None and hasattr(linker, "GetLinker2d"):
+            d2, d3 = linker.GetLinker2d(), linker.GetLinker3d()
+        d2, d3 = d2 if d2 is not None else {}, d3 if d3 is not None else {}
+    return _capi.config_from_dict({"linker2d_config": _conf_dict(d2, _capi.L2_KEYS),
+                                   "linker3d_config": _conf_dict(d3, _capi.L3_KEYS)})
+
+
+def _seg3d_array(x):
+    """_GetLine3dVectorFromArray input: (M, 2, 3), (M, 6) or a list of (2, 3) -> (M, 6)"""
+    if isinstance(x, (list, tuple)) and len(x) == 0:
+        return np.zeros((0, 6))
+    a = np.asarray(x, dtype=np.float64)
+    if a.size == 0:
+        return np.zeros((0, 6))
+    if (a.ndim == 3 and a.shape[1:] == (2, 3)) or (a.ndim == 2 and a.shape[1] == 6):
+        return np.ascontiguousarray(a.reshape(-1, 6))
+    raise ValueError(f"3D segments must be (M, 2, 3) or (M, 6), got shape {a.shape}")
+
+
+def _merge_inputs(all_2d_segs, imagecols, seg3d_list, neighbors):
+    """Arrays of the merge, with the checks of merging/merging.cc:353-368 and the std::map::at lookups made before
+    any device work: the image counts of the three inputs, 2D against 3D segments per image, neighbour ids."""
+    from .triangulation import _view_arrays
+    ids = sorted(int(i) for i in imagecols.get_img_ids())
+    if len(all_2d_segs) != len(seg3d_list) or len(all_2d_segs) != len(neighbors):
+        raise ValueError(f"merging: {len(all_2d_segs)} images of 2D segments, {len(seg3d_list)} of 3D segments, "
+                         f"{len(neighbors)} of neighbours")
+    idset = set(ids)
+    k = np.zeros((len(ids), 4)); q = np.zeros((len(ids), 4)); t = np.zeros((len(ids), 3))
+    seg_off = np.zeros(len(ids) + 1, np.int64)
+    segs2, segs3, nb_off, nb = [], [], np.zeros(len(ids) + 1, np.int64), []
+    for n, i in enumerate(ids):
+        k[n], q[n], t[n] = _view_arrays(imagecols.camview(i))
+        s2 = np.asarray(all_2d_segs[i], dtype=np.float64)
+        s2 = s2.reshape(0, 4) if s2.size == 0 else s2[:, :4]
+        s3 = _seg3d_array(seg3d_list[i])
+        if len(s2) != len(s3):
+            raise ValueError(f"merging: image {i} has {len(s2)} 2D segments but {len(s3)} 3D segments")
+        if i not in neighbors:
+            raise IndexError(f"merging: no neighbour list for image {i}")
+        ng = [int(j) for j in neighbors[i]]
+        for j in ng:
+            if j not in idset:
+                raise IndexError(f"merging: neighbour {j} of image {i} is not an image")
+        segs2.append(s2); segs3.append(s3); nb += ng
+        seg_off[n + 1] = seg_off[n] + len(s2)
+        nb_off[n + 1] = len(nb)
+    cat = lambda L, w: np.ascontiguousarray(np.concatenate(L, 0)) if L else np.zeros((0, w))  # noqa: E731
+    return dict(ids=ids, k=k, q=q, t=t, seg_off=seg_off, segs2=cat(segs2, 4), segs3=cat(segs3, 6), nb_off=nb_off,
+                nb=np.asarray(nb, np.int32).reshape(-1))
+
+
+class MergeGraph:
+    """The graph MergeToLineTracks builds (base/graph.h): nodes in node order as (image id, line id), undirected
+    edges (node_idx1, node_idx2, sim) in insertion order."""
+
+    def __init__(self, node_image_ids, node_line_ids, edge_idx1, edge_idx2, edge_sim):
+        self.node_image_ids, self.node_line_ids = node_image_ids, node_line_ids
+        self.edge_idx1, self.edge_idx2, self.edge_sim = edge_idx1, edge_idx2, edge_sim
+
+    @classmethod
+    def from_ctx(cls, ctx):
+        n, e = C.c_int64(), C.c_int64()
+        ctx.chk(ctx.L.lt_merge_graph_size(ctx.h, C.byref(n), C.byref(e)))
+        N, E = n.value, e.value
+        ni, nl = np.zeros(max(N, 1), np.int32), np.zeros(max(N, 1), np.int32)
+        e1, e2, sim = np.zeros(max(E, 1), np.int32), np.zeros(max(E, 1), np.int32), np.zeros(max(E, 1))
+        p = _capi.ptr
+        ctx.chk(ctx.L.lt_merge_graph_get(ctx.h, p(ni, C.c_int32), p(nl, C.c_int32), p(e1, C.c_int32),
+                                         p(e2, C.c_int32), p(sim, C.c_double)))
+        return cls(ni[:N], nl[:N], e1[:E], e2[:E], sim[:E])
+
+    @property
+    def nodes(self):
+        return np.stack([self.node_image_ids, self.node_line_ids], 1)
+
+    @property
+    def edges(self):
+        return np.stack([self.edge_idx1, self.edge_idx2], 1)
+
+    def num_nodes(self):
+        return len(self.node_image_ids)
+
+    def num_edges(self):
+        return len(self.edge_idx1)
 
 
 class TrackSet:
@@ -68,6 +174,28 @@ class TrackSet:
                                p(lid, C.c_int32), p(nid, C.c_int32), p(sc, C.c_double), p(l2, C.c_double),
                                p(l3, C.c_double))
         return cls(ctx, h)
+
+    @classmethod
+    def from_merge(cls, linker, all_2d_segs, imagecols, seg3d_list, neighbors, var2d=5.0, device=0):
+        """limap.merging.merging into a track set bound to a context with the cameras of `imagecols` (the later
+        filter_by_reprojection / remerge run on it without a copy); the graph is in `.graph`, the merge's timers
+        (lt_merge_get_timers) in `.merge_timers`."""
+        a = _merge_inputs(all_2d_segs, imagecols, seg3d_list, neighbors)
+        cfg = _merge_linker_cfg(linker)
+        ctx = _capi.Context(device=device)
+        ctx.init(a["ids"], a["k"], a["q"], a["t"], a["seg_off"], a["segs2"])
+        seg3d_off = a["seg_off"].copy()
+        out = C.c_void_p()
+        p = _capi.ptr
+        ctx.chk(ctx.L.lt_merge_to_tracks(ctx.h, p(seg3d_off, C.c_int64), p(a["segs3"], C.c_double),
+                                         p(a["nb_off"], C.c_int64), p(a["nb"], C.c_int32), C.byref(cfg),
+                                         float(var2d), C.byref(out)))
+        ts = cls(ctx, out.value)
+        ts.graph = MergeGraph.from_ctx(ctx)
+        tm = np.zeros(4)
+        ctx.chk(ctx.L.lt_merge_get_timers(ctx.h, p(tm, C.c_double)))
+        ts.merge_timers = dict(device_ms=float(tm[0]), host_ms=float(tm[1]), attempts=int(tm[2]), edges=int(tm[3]))
+        return ts
 
     def __del__(self):
         try:
@@ -136,6 +264,12 @@ class TrackSet:
 
 
 # ---- module-level functions with the reference's signatures ------------------------------------
+def merging(linker, all_2d_segs, imagecols, seg3d_list, neighbors, var2d=5.0):
+    """limap.merging.merging (merging/merging.py:6-21): -> (graph, linetracks)."""
+    ts = TrackSet.from_merge(linker, all_2d_segs, imagecols, seg3d_list, neighbors, var2d)
+    return ts.graph, ts.tracks()
+
+
 def _ctx_for(imagecols):
     from .triangulation import _view_arrays
     ids = [int(i) for i in imagecols.get_img_ids()]

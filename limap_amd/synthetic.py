@@ -376,6 +376,59 @@ def gen_matches(scene, img_id, topk=10):
     return out
 
 
+def make_fit_segs(scene, seed=0, depth_noise=0.002, fail_frac=0.1):
+    """seg3d_list of a depth fitter (runners/line_fitnmerge.py, `load_fit` form) for a scene: img_id -> (M, 2, 3).
+    Each endpoint of a 2D segment is back-projected onto the segment's GT 3D line (scene.gt_ids) -- the point of the
+    line closest to the endpoint's ray -- and moved along its viewing ray by a relative depth error
+    N(0, depth_noise).  Clutter segments (gt id -1) and a random `fail_frac` of the others are zeros: a fitter writes
+    zeros where a fit fails."""
+    out = {}
+    for n, img_id in enumerate(scene.img_ids):
+        rng = np.random.default_rng([seed, 4242, int(img_id)])
+        segs = scene.segs_of(n)
+        gids = scene.gt_ids[scene.seg_off[n]:scene.seg_off[n + 1]]
+        M = len(segs)
+        res = np.zeros((M, 2, 3))
+        R = quat_to_rot(scene.qvec[n])
+        C = -R.T @ scene.tvec[n]
+        fx, fy, cx, cy = scene.kvec[n]
+        noise = rng.normal(size=(M, 2)) * depth_noise
+        failed = rng.uniform(size=M) < fail_frac
+        for m in range(M):
+            if gids[m] < 0 or failed[m]:
+                continue
+            p0 = scene.gt_lines[gids[m], :3]
+            u = scene.gt_lines[gids[m], 3:] - p0
+            for e in range(2):
+                x, y = segs[m, 2 * e], segs[m, 2 * e + 1]
+                d = R.T @ np.array([(x - cx) / fx, (y - cy) / fy, 1.0])
+                # closest point of the GT line p0 + t u to the ray C + s d
+                A = np.array([[d @ d, -(d @ u)], [d @ u, -(u @ u)]])
+                b = np.array([(p0 - C) @ d, (p0 - C) @ u])
+                try:
+                    _, t = np.linalg.solve(A, b)
+                except np.linalg.LinAlgError:
+                    t = 0.0
+                X = p0 + t * u
+                res[m, e] = C + (X - C) * (1.0 + noise[m, e])
+        out[int(img_id)] = res
+    return out
+
+
+def imagecols_of(scene):
+    """limap_amd.base.ImageCollection of a scene's cameras."""
+    from .base import ImageCollection
+    return ImageCollection.from_arrays(scene.img_ids, scene.kvec, scene.qvec, scene.tvec)
+
+
+def default_merging_cfg(var2d=5.0):
+    """cfg["merging"] of cfgs/fitnmerge/default.yaml:62-76 with var2d resolved."""
+    return dict(var2d=var2d,
+                linker3d=dict(score_th=0.5, th_angle=8.0, th_overlap=0.01, th_smartoverlap=0.1, th_smartangle=1.0,
+                              th_perp=0.75, th_innerseg=0.75),
+                linker2d=dict(score_th=0.5, th_angle=5.0, th_perp=2.0, th_overlap=0.05))
+
+
 def default_triangulation_cfg(var2d=2.0, **over):
     """cfg["triangulation"] of cfgs/triangulation/default.yaml:70-100 with var2d resolved for LSD
     (line_triangulation.py:39-40)."""
