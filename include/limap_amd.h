@@ -282,7 +282,10 @@ int lt_ts_remerge_once(lt_ctx *ctx, lt_trackset *ts, const lt_config *linker_cfg
 
 /* ---- limap.merging.merging / MergeToLineTracks (merging/merging.py:6-21, merging/merging.cc:347-511): the merge of
  * one fitted 3D segment per 2D segment (runners/line_fitnmerge.py) into line tracks.  The context is initialised
- * (lt_init) with the cameras and the 2D segments; seg3d = per image in ascending id order, per line, start3 end3
+ * (lt_init / lt_init_device, the images in any order) with the cameras and the 2D segments.  The merge reads the 2D
+ * segments as given: a context created with add_halfpix = 1 does not shift them by half a pixel here, like the
+ * reference's MergeToLineTracks (the triangulation on the same context still does).  seg3d = per image in ascending
+ * id order, per line, start3 end3
  * (seg3d_off[n_img+1] offsets in segments: each image needs as many 3D as 2D segments, else LT_ERR_ARGUMENT); a
  * zero-length segment is not a node.  Neighbours as CSR over the images in ascending id order: nb_ids[nb_off[i] ..
  * nb_off[i+1]) in list order (an id that is not an image: LT_ERR_ARGUMENT).  The 2D linker is read from the l2_* fields

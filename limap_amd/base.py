@@ -124,6 +124,9 @@ class CameraView:
         q = np.asarray(qvec, float).reshape(4)
         n = np.linalg.norm(q)
         self.qvec = q / n if n > 0 else q
+        # the native code receives the quaternion as given: it normalises it like CameraPose's constructor and R() do
+        # (camera.h:95, pose.cc:12-28); a third normalisation here would change the last bits of R
+        self._qvec_given = q
         self.tvec = np.asarray(tvec, float).reshape(3)
         self._name = image_name
 

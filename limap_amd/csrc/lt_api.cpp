@@ -477,11 +477,9 @@ int build_invariants(lt_ctx *ctx, const double *hk = nullptr, const double *hq =
       if (ctx->G > 0)
         HIPCHK(ctx, hipMemcpy(ctx->h_segs.data(), ctx->d_segs_raw.p, 32 * (size_t)ctx->G, hipMemcpyDeviceToHost));
     }
-    if (!(hk && hq && ht && hs)) {
-      if (ctx->cfg.add_halfpix)
-        for (double &v : ctx->h_segs) v = v + 0.5;
+    if (!(hk && hq && ht && hs)) {  // (the segments as given on both paths: a reader adds h_segs_add itself)
       ctx->h_segs_ptr = ctx->h_segs.data();
-      ctx->h_segs_add = 0.0;
+      ctx->h_segs_add = ctx->cfg.add_halfpix ? 0.5 : 0.0;
     }
     ctx->h_cams.resize(n);
     for (int i = 0; i < n; ++i) cam_build(&k[4 * i], &q[4 * i], &t[3 * i], &ctx->h_cams[i]);

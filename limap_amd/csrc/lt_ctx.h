@@ -195,7 +195,7 @@ struct lt_ctx {
   long long G = 0;
   std::vector<int> h_node_img;  // node -> image index
   std::vector<lt::Cam> h_cams;     // host copy of the camera table (post-triangulation filters)
-  std::vector<double> h_segs;     // host copy of the 2D segments, x1 y1 x2 y2 (after add_halfpix) -- only where Init got device buffers
+  std::vector<double> h_segs;     // host copy of the 2D segments, x1 y1 x2 y2 (as given) -- only where Init got device buffers
   const double *h_segs_ptr = nullptr;  // the 2D segments on the host: h_segs, or the scene block of lt_init (init_blk: no 32 B per
   double h_segs_add = 0.0;             // segment copied at Init -- 3 ms at 10^6 segments); a reader adds h_segs_add (add_halfpix)
   DevBuf d_kvec, d_qvec, d_tvec, d_segs_raw, d_cams, d_segs, d_seg_off, d_node_img;

@@ -50,7 +50,8 @@ int lt_merge_to_tracks(lt_ctx *ctx, const int64_t *seg3d_off, const double *seg3
   LinkCfg3 l3 = make_l3(*linker_cfg);
   l3.use_angle = 1; l3.use_overlap = 1; l3.use_perp = 0; l3.use_innerseg = 1; l3.use_scaleinv = 0;
   const double th = l3.th_angle * (1.0 + 1e-6) + 1e-6;
-  const double cos_guard = (th < 90.0) ? std::cos(th * kPi / 180.0) : -1.0;
+  double cos_guard = (th < 90.0) ? std::cos(th * kPi / 180.0) : -1.0;
+  if (test_switch("LT_TEST_MERGE_NO_GUARD")) cos_guard = -1.0;  // every pair through the exact 3D test
 
   // per-line records, nodes in (ascending image id, line) order (merging.cc:360-374)
   const long long G = ctx->G;
@@ -71,8 +72,9 @@ int lt_merge_to_tracks(lt_ctx *ctx, const int64_t *seg3d_off, const double *seg3
       const double d = (cam_depth(cam, ln.s) + cam_depth(cam, ln.e)) / 2.0;
       r.unc = var2d * d / cam.f;
       r.len = len(ln);
+      // the segments as given: MergeToLineTracks never shifts them by half a pixel, whatever the context's add_halfpix
       const double *s2 = ctx->h_segs_ptr + 4 * (g0 + l);
-      for (int k = 0; k < 4; ++k) r.seg[k] = s2[k] + ctx->h_segs_add;
+      for (int k = 0; k < 4; ++k) r.seg[k] = s2[k];
       r.pad_ = 0.0;
       if (r.len == 0) continue;  // merging.cc:370-371: exact test
       node_of[(size_t)(g0 + l)] = (int)ctx->mg_node_img.size();
@@ -100,7 +102,8 @@ int lt_merge_to_tracks(lt_ctx *ctx, const int64_t *seg3d_off, const double *seg3
         cross_blks.push_back(MBlock{n, nb, (int)(k - nb_off[n]), r0, id, ctx->img_ids[(size_t)nb], {0, 0}});
     }
   }
-  const int parity_fast = (ids_nonneg && 2 * max_id + 2 * max_lines < (1ll << 30)) ? 1 : 0;
+  int parity_fast = (ids_nonneg && 2 * max_id + 2 * max_lines < (1ll << 30)) ? 1 : 0;
+  if (test_switch("LT_TEST_MERGE_PARITY_SLOW")) parity_fast = 0;  // the reference's int key on every pair
 
   // device: both passes into one edge buffer; an overflow is counted, never truncated, and runs again
   hipStream_t st = ctx->stream;

@@ -276,7 +276,8 @@ class GlobalLineTriangulatorConfig:
 def _view_arrays(view):
     """(kvec4, qvec4, tvec3) of a limap CameraView or of limap_amd.base.CameraView."""
     if hasattr(view, "kvec"):
-        return np.asarray(view.kvec, float), np.asarray(view.qvec, float), np.asarray(view.tvec, float)
+        q = getattr(view, "_qvec_given", view.qvec)
+        return np.asarray(view.kvec, float), np.asarray(q, float), np.asarray(view.tvec, float)
     K = np.asarray(view.K(), float)
     pose = getattr(view, "pose", view)
     q = np.asarray(getattr(pose, "qvec"), float).reshape(4)

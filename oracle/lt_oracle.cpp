@@ -408,6 +408,19 @@ struct Linker2d {
     if (config.use_innerseg) score = std::min(score, score_innerseg(l1, l2));
     return score;
   }
+  bool check_connection(const Line2d &l1, const Line2d &l2) const {  // line_linker.cc:120-137
+    if (config.use_angle)  // check_connection_angle, :67-71: plain angle <= th_angle
+      if (!(compute_angle(l1, l2) <= config.th_angle)) return false;
+    if (config.use_overlap)  // :87-90
+      if (!(score_overlap(l1, l2) == 1.0)) return false;
+    if (config.use_angle && config.use_overlap && config.use_smartangle)  // :73-76
+      if (!(score_smartangle(l1, l2) >= config.score_th)) return false;
+    if (config.use_perp)  // :101-104
+      if (!(score_perp(l1, l2) >= config.score_th)) return false;
+    if (config.use_innerseg)  // :115-118
+      if (!(score_innerseg(l1, l2) >= config.score_th)) return false;
+    return true;
+  }
 };
 
 struct Linker3d {
@@ -1366,6 +1379,104 @@ static std::vector<LineTrack> RemergeLineTracks(const std::vector<LineTrack> &tr
   return out;
 }
 
+// MergeToLineTracks (merging/merging.cc:347-511) as the plain double loop, one image after the other: no guard, no
+// parity shortcut.  `lines3d` already carry the uncertainty of SetUncertaintySegs3d (merging_utils.cc:15-25).
+static void MergeToLineTracks(Graph &graph, std::vector<LineTrack> &tracks, const std::vector<int> &img_ids,
+                              const std::map<int, CameraView> &views, const std::map<int, std::vector<Line2d>> &lines2d,
+                              const std::map<int, std::vector<Line3d>> &lines3d,
+                              const std::map<int, std::vector<int>> &neighbors, const Linker2d &linker2d,
+                              Linker3d linker3d) {
+  linker3d.config.set_to_spatial_merging();  // :353
+  // nodes: every line of non-zero 3D length, images ascending, lines ascending (:364-374)
+  std::map<int, std::vector<double>> lengths;
+  for (int img : img_ids) {
+    const std::vector<Line3d> &ls = lines3d.at(img);
+    if (ls.size() != lines2d.at(img).size())
+      throw std::runtime_error("image " + std::to_string(img) + ": 2D and 3D segment counts differ");
+    std::vector<double> &len = lengths[img];
+    for (size_t l = 0; l < ls.size(); ++l) {
+      len.push_back(ls[l].length());
+      if (len.back() == 0) continue;
+      graph.FindOrCreateNode(img, int(l));
+    }
+  }
+  // candidate pairs per image: the self pass first (:388-414), then the cross pass (:416-456)
+  std::map<int, std::vector<std::pair<std::pair<int, size_t>, std::pair<int, size_t>>>> pairs;
+  for (int img : img_ids) {
+    auto &out = pairs[img];
+    const std::vector<Line3d> &ls = lines3d.at(img);
+    const std::vector<Line2d> &segs = lines2d.at(img);
+    const std::vector<double> &len = lengths.at(img);
+    for (size_t a = 0; a < ls.size(); ++a) {
+      if (len[a] == 0) continue;
+      for (size_t b = a + 1; b < ls.size(); ++b) {
+        if (len[b] == 0) continue;
+        if (!linker3d.check_connection(ls[a], ls[b])) continue;
+        if (!linker2d.check_connection(segs[a], segs[b])) continue;
+        out.push_back({{img, a}, {img, b}});
+      }
+    }
+  }
+  for (int img : img_ids) {
+    auto &out = pairs[img];
+    const std::vector<Line3d> &ls = lines3d.at(img);
+    const std::vector<Line2d> &segs = lines2d.at(img);
+    const std::vector<double> &len = lengths.at(img);
+    const std::vector<int> &nbs = neighbors.at(img);
+    for (size_t a = 0; a < ls.size(); ++a) {
+      if (len[a] == 0) continue;
+      for (size_t k = 0; k < nbs.size(); ++k) {
+        // the neighbour id is held as size_t there (:422): a negative id becomes 2^64 + id in the comparisons below,
+        // and the sum of the four indices is done in size_t, then narrowed to the int `key`
+        const size_t nb_u = size_t(nbs[k]);
+        const int nb = nbs[k];
+        const std::vector<Line3d> &ns = lines3d.at(nb);
+        const std::vector<Line2d> &nsegs = lines2d.at(nb);
+        const std::vector<double> &nlen = lengths.at(nb);
+        for (size_t b = 0; b < nsegs.size(); ++b) {
+          const size_t img_u = size_t(img);
+          const int key = int(img_u + a + nb_u + b);  // :431
+          if (key % 2 == 0 && img_u < nb_u) continue;  // :432-435: int img compared with size_t ng_image_id
+          if (key % 2 == 1 && img_u > nb_u) continue;
+          if (nlen[b] == 0) continue;
+          if (!linker3d.check_connection(ls[a], ns[b])) continue;
+          if (!linker2d.check_connection(ls[a].projection(views.at(nb)), nsegs[b])) continue;
+          if (!linker2d.check_connection(ns[b].projection(views.at(img)), segs[a])) continue;
+          out.push_back({{img, a}, {nb, b}});
+        }
+      }
+    }
+  }
+  // edges in insertion order, sim = sum of the two 3D lengths (:458-469)
+  for (int img : img_ids)
+    for (const auto &p : pairs[img]) {
+      const int n1 = graph.FindOrCreateNode(p.first.first, int(p.first.second));
+      const int n2 = graph.FindOrCreateNode(p.second.first, int(p.second.second));
+      graph.AddEdge(n1, n2, lengths.at(p.first.first)[p.first.second] + lengths.at(p.second.first)[p.second.second]);
+    }
+  // greedy labels, then one track per label with its members in node order (:471-504)
+  std::vector<int> node_img(graph.nodes.size());
+  for (size_t i = 0; i < graph.nodes.size(); ++i) node_img[i] = graph.nodes[i].first;
+  const std::vector<int> labels = ComputeLineTrackLabelsGreedy(node_img, graph.edges);
+  int n_tracks = 0;  // (the reference reads *max_element of an empty vector when there is no node)
+  for (int l : labels) n_tracks = std::max(n_tracks, l + 1);
+  tracks.assign(size_t(n_tracks), LineTrack());
+  for (size_t i = 0; i < graph.nodes.size(); ++i) {
+    if (labels[i] < 0) continue;
+    const int img = graph.nodes[i].first, l = graph.nodes[i].second;
+    LineTrack &tr = tracks[size_t(labels[i])];
+    const Line3d &l3 = lines3d.at(img)[size_t(l)];
+    tr.node_id_list.push_back(int(i));
+    tr.image_id_list.push_back(img);
+    tr.line_id_list.push_back(l);
+    tr.line2d_list.push_back(lines2d.at(img)[size_t(l)]);
+    tr.line3d_list.push_back(l3);
+    tr.score_list.push_back(l3.length());
+  }
+  // the track line: the aggregator with no outliers dropped (:506-510)
+  for (LineTrack &tr : tracks) tr.line = aggregate_line3d_list(tr.line3d_list, tr.score_list, 0);
+}
+
 // ---------------------------------------------------------------------------------------------
 // triangulation/base_line_triangulator.{h,cc} + global_line_triangulator.{h,cc}
 // ---------------------------------------------------------------------------------------------
@@ -1389,6 +1500,7 @@ struct Triangulator {
   std::vector<int> img_ids;         // ascending
 
   std::map<int, std::vector<Line2d>> all_lines_2d_;
+  std::map<int, std::vector<Line2d>> given_lines_2d_;  // as given to Init, before offsetHalfPixel (the merge's)
   std::map<int, std::vector<int>> neighbors_;
   std::map<int, std::vector<std::vector<std::pair<int, int>>>> edges_;
   std::map<int, std::vector<std::vector<TriTuple>>> tris_;
@@ -2001,6 +2113,7 @@ int ora_init(ora_ctx *ctx, int n_img, const int32_t *img_ids, const double *kvec
       std::vector<ora::Line2d> lines;
       for (int64_t s = seg_off[i]; s < seg_off[i + 1]; ++s) lines.push_back(ora::seg_to_line(segs + 4 * s));
       t.all_lines_2d_[img_ids[i]] = lines;
+      t.given_lines_2d_[img_ids[i]] = lines;
     }
     t.img_ids.clear();
     for (auto &kv : t.views) t.img_ids.push_back(kv.first);
@@ -2207,6 +2320,7 @@ int ora_get_timers(ora_ctx *ctx, double out[4]) {
 // ---- track sets: post-triangulation filters and remerge on flat arrays ----
 struct ora_trackset {
   std::vector<ora::LineTrack> tracks;
+  ora::Graph graph;  // the graph of ora_merge_to_tracks (empty otherwise)
 };
 
 ora_trackset *ora_ts_from_ctx(ora_ctx *ctx) {
@@ -2260,6 +2374,58 @@ int ora_ts_remerge_once(ora_ctx *ctx, ora_trackset *ts, const ora_config *linker
     ora::set_linkers(*linker_cfg, l2, l3);
     ts->tracks = ora::RemergeLineTracks(ts->tracks, l3, num_outliers);
   })
+}
+
+// ---- MergeToLineTracks (limap.merging.merging) on the cameras and 2D segments of ora_init ----
+ora_trackset *ora_merge_to_tracks(ora_ctx *ctx, const int64_t *seg3d_off, const double *seg3d, const int64_t *nb_off,
+                                  const int32_t *nb_ids, const ora_config *linker_cfg, double var2d) {
+  auto *ts = new ora_trackset();
+  try {
+    const ora::Triangulator &t = ctx->t;
+    std::map<int, std::vector<ora::Line3d>> lines3d;
+    std::map<int, std::vector<int>> neighbors;
+    for (size_t n = 0; n < t.img_ids.size(); ++n) {
+      const int img = t.img_ids[n];
+      const ora::CameraView &view = t.views.at(img);
+      std::vector<ora::Line3d> &ls = lines3d[img];
+      for (int64_t k = seg3d_off[n]; k < seg3d_off[n + 1]; ++k) {
+        const double *p = seg3d + 6 * k;
+        // Line3d(MatrixXd) (linebase.cc:60-65) leaves score -1 and depths unset (0 here), merging.py:14-16 sets the
+        // uncertainty (merging_utils.cc:15-25)
+        ora::Line3d l(ora::V3{p[0], p[1], p[2]}, ora::V3{p[3], p[4], p[5]}, -1.0, 0.0, 0.0);
+        l.uncertainty = l.computeUncertainty(view, var2d);
+        ls.push_back(l);
+      }
+      neighbors[img] = std::vector<int>(nb_ids + nb_off[n], nb_ids + nb_off[n + 1]);
+    }
+    ora::Linker2d l2;
+    ora::Linker3d l3;
+    ora::set_linkers(*linker_cfg, l2, l3);
+    ora::MergeToLineTracks(ts->graph, ts->tracks, t.img_ids, t.views, t.given_lines_2d_, lines3d, neighbors, l2, l3);
+  } catch (const std::exception &e) {
+    ctx->t.err = e.what();
+    delete ts;
+    return nullptr;
+  }
+  return ts;
+}
+int ora_merge_graph_size(ora_trackset *ts, int64_t *n_nodes, int64_t *n_edges) {
+  if (n_nodes) *n_nodes = int64_t(ts->graph.nodes.size());
+  if (n_edges) *n_edges = int64_t(ts->graph.edges.size());
+  return 0;
+}
+int ora_merge_graph_get(ora_trackset *ts, int32_t *node_img, int32_t *node_line, int32_t *edge_n1, int32_t *edge_n2,
+                        double *edge_sim) {
+  for (size_t i = 0; i < ts->graph.nodes.size(); ++i) {
+    if (node_img) node_img[i] = ts->graph.nodes[i].first;
+    if (node_line) node_line[i] = ts->graph.nodes[i].second;
+  }
+  for (size_t k = 0; k < ts->graph.edges.size(); ++k) {
+    if (edge_n1) edge_n1[k] = std::get<1>(ts->graph.edges[k]);
+    if (edge_n2) edge_n2[k] = std::get<2>(ts->graph.edges[k]);
+    if (edge_sim) edge_sim[k] = std::get<0>(ts->graph.edges[k]);
+  }
+  return 0;
 }
 
 // ---- free functions ----

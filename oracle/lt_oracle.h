@@ -147,6 +147,19 @@ int ora_ts_filter_by_sensitivity(ora_ctx *ctx, ora_trackset *ts, double th_angul
 int ora_ts_filter_by_overlap(ora_ctx *ctx, ora_trackset *ts, double th_overlap, int min_supports);
 int ora_ts_remerge_once(ora_ctx *ctx, ora_trackset *ts, const ora_config *linker_cfg, int num_outliers);
 
+/* MergeToLineTracks (merging/merging.cc:347-511, merging/merging.py:6-21) on the cameras and the 2D segments given to
+ * ora_init (never shifted by add_halfpix).  seg3d (x1,y1,z1,x2,y2,z2) and nb_ids are CSR over the images in ascending
+ * id order (seg3d_off, nb_off: n_img+1 entries); the linkers come from linker_cfg's l2_* / l3_* fields, the 3D one
+ * switched to spatial merging.  Returns a track set (the filters and remerge above apply to it) that also holds the
+ * graph, or NULL on error (ora_last_error). */
+ora_trackset *ora_merge_to_tracks(ora_ctx *ctx, const int64_t *seg3d_off, const double *seg3d, const int64_t *nb_off,
+                                  const int32_t *nb_ids, const ora_config *linker_cfg, double var2d);
+/* the graph of a merge's track set: nodes as (image id, line id), then the edges in insertion order with their sim;
+ * 0 nodes / edges for any other track set */
+int ora_merge_graph_size(ora_trackset *ts, int64_t *n_nodes, int64_t *n_edges);
+int ora_merge_graph_get(ora_trackset *ts, int32_t *node_img, int32_t *node_line, int32_t *edge_n1, int32_t *edge_n2,
+                        double *edge_sim);
+
 /* ---- free functions (mirror triangulation/bindings.cc:22-31) on raw arrays ----
  * cam = kvec[4] | qvec[4] | tvec[3]  (11 doubles), seg = x1,y1,x2,y2 */
 void ora_get_normal_direction(const double seg[4], const double cam[11], double out[3]);

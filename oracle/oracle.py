@@ -107,6 +107,9 @@ def _prototype(L):
     for name in ("ora_compute_epipolar_IoU", "ora_cam_projdepth", "ora_line3d_sensitivity",
                  "ora_line3d_uncertainty", "ora_linker2d_score", "ora_linker3d_score"):
         getattr(L, name).restype = C.c_double
+    L.ora_merge_to_tracks.restype = C.c_void_p
+    L.ora_merge_to_tracks.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_int64),
+                                      C.POINTER(C.c_int32), C.POINTER(OraConfig), C.c_double]
     return L
 
 
@@ -299,6 +302,22 @@ class OracleTriangulator:
         self._chk(self.L.ora_compute_tracks(self.ctx))
         return self.get_tracks()
 
+    def MergeToLineTracks(self, seg3d_off, seg3d, nb_off, nb_ids, linker=None, var2d=5.0):
+        """limap.merging.merging (MergeToLineTracks) on the cameras and the 2D segments given to Init: 3D segments
+        (M, 6) and neighbour ids as CSR over the images in ascending id order; `linker` = {"linker2d": {...},
+        "linker3d": {...}} (missing keys keep the C++ defaults).  Returns an OracleTrackSet whose graph() is the
+        merge's graph."""
+        linker = linker or {}
+        cfg = config_from_dict({"linker2d_config": dict(linker.get("linker2d", {})),
+                                "linker3d_config": dict(linker.get("linker3d", {}))})
+        seg3d_off, seg3d = _i64(seg3d_off), _f64(np.asarray(seg3d, float).reshape(-1, 6))
+        nb_off, nb_ids = _i64(nb_off), _i32(np.asarray(nb_ids).reshape(-1) if len(nb_ids) else np.zeros(1))
+        h = self.L.ora_merge_to_tracks(self.ctx, _p(seg3d_off, C.c_int64), _p(seg3d, C.c_double),
+                                       _p(nb_off, C.c_int64), _p(nb_ids, C.c_int32), C.byref(cfg), float(var2d))
+        if not h:
+            raise RuntimeError(self.L.ora_last_error(self.ctx).decode())
+        return OracleTrackSet(self, handle=h)
+
     # ---- getters ----
     def num_nodes(self):
         return int(self.L.ora_num_nodes(self.ctx))
@@ -471,7 +490,7 @@ class OracleTrackSet:
     (limap.merging.filter_tracks_by_reprojection / remerge / filter_tracks_by_sensitivity /
     filter_tracks_by_overlap; runners/line_triangulation.py:171-200)."""
 
-    def __init__(self, tri):
+    def __init__(self, tri, handle=None):
         self.L = lib()
         self.tri = tri
         self.L.ora_ts_from_ctx.restype = C.c_void_p
@@ -481,7 +500,7 @@ class OracleTrackSet:
         self.L.ora_ts_filter_by_sensitivity.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_int]
         self.L.ora_ts_filter_by_overlap.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_int]
         self.L.ora_ts_remerge_once.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(OraConfig), C.c_int]
-        self.h = C.c_void_p(self.L.ora_ts_from_ctx(tri.ctx))
+        self.h = C.c_void_p(handle if handle is not None else self.L.ora_ts_from_ctx(tri.ctx))
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -490,6 +509,18 @@ class OracleTrackSet:
 
     def num_tracks(self):
         return int(self.L.ora_ts_num_tracks(self.h))
+
+    def graph(self):
+        """The graph of a merge (MergeToLineTracks): nodes (image id, line id) in node order, edges in insertion
+        order with their sim; empty for the tracks of a triangulator."""
+        n, e = C.c_int64(), C.c_int64()
+        self.L.ora_merge_graph_size(self.h, C.byref(n), C.byref(e))
+        N, E = n.value, e.value
+        ni, nl = np.zeros(max(N, 1), np.int32), np.zeros(max(N, 1), np.int32)
+        e1, e2, sim = np.zeros(max(E, 1), np.int32), np.zeros(max(E, 1), np.int32), np.zeros(max(E, 1))
+        self.L.ora_merge_graph_get(self.h, _p(ni, C.c_int32), _p(nl, C.c_int32), _p(e1, C.c_int32), _p(e2, C.c_int32),
+                                   _p(sim, C.c_double))
+        return dict(node_img=ni[:N], node_line=nl[:N], edge_n1=e1[:E], edge_n2=e2[:E], edge_sim=sim[:E])
 
     def filter_by_reprojection(self, th_angular2d, th_perp2d, num_outliers=2):
         self.tri._chk(self.L.ora_ts_filter_by_reprojection(self.tri.ctx, self.h, th_angular2d, th_perp2d, num_outliers))

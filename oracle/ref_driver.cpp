@@ -125,6 +125,8 @@ struct ora_ctx {  // (the type name of lt_oracle.h; this is the reference-backed
 };
 struct ora_trackset {
   std::vector<LineTrack> tracks;
+  std::vector<int> node_img, node_line, e1, e2;  // the graph of ref_merge_to_tracks (empty otherwise)
+  std::vector<double> sim;
 };
 
 #define REF_TRY(ctx, ...)                      \
@@ -492,6 +494,63 @@ int ref_ts_remerge_once(ora_ctx *ctx, ora_trackset *ts, const ora_config *linker
     LineLinker3d l3(linker3d_dict(*linker_cfg));
     ts->tracks = merging::RemergeLineTracks(ts->tracks, l3, num_outliers);
   })
+}
+
+// ---- MergeToLineTracks: what limap.merging.merging does (merging/merging.py:6-21) with the reference's functions ----
+ora_trackset *ref_merge_to_tracks(ora_ctx *ctx, const int64_t *seg3d_off, const double *seg3d, const int64_t *nb_off,
+                                  const int32_t *nb_ids, const ora_config *linker_cfg, double var2d) {
+  auto *ts = new ora_trackset();
+  try {
+    std::map<int, std::vector<Line3d>> all_lines_3d;
+    std::map<int, std::vector<int>> neighbors;
+    for (size_t n = 0; n < ctx->ids.size(); ++n) {
+      const int id = ctx->ids[n];
+      std::vector<Eigen::MatrixXd> arr;
+      for (int64_t k = seg3d_off[n]; k < seg3d_off[n + 1]; ++k) {
+        Eigen::MatrixXd m(2, 3);
+        for (int r = 0; r < 2; ++r)
+          for (int c = 0; c < 3; ++c) m(r, c) = seg3d[6 * k + 3 * r + c];
+        arr.push_back(m);
+      }
+      all_lines_3d[id] = merging::SetUncertaintySegs3d(GetLine3dVectorFromArray(arr), ctx->imagecols->camview(id), var2d);
+      neighbors[id] = std::vector<int>(nb_ids + nb_off[n], nb_ids + nb_off[n + 1]);
+    }
+    LineLinker linker(linker2d_dict(*linker_cfg), linker3d_dict(*linker_cfg));
+    Graph graph;
+    merging::MergeToLineTracks(graph, ts->tracks, ctx->segs, *ctx->imagecols, all_lines_3d, neighbors, linker);
+    for (PatchNode *node : graph.nodes) {
+      ts->node_img.push_back(node->image_idx);
+      ts->node_line.push_back(int(node->line_idx));
+    }
+    for (Edge *e : graph.undirected_edges) {
+      ts->e1.push_back(int(e->node_idx1));
+      ts->e2.push_back(int(e->node_idx2));
+      ts->sim.push_back(e->sim);
+    }
+  } catch (const std::exception &e) {
+    ctx->err = e.what();
+    delete ts;
+    return nullptr;
+  }
+  return ts;
+}
+int ref_merge_graph_size(ora_trackset *ts, int64_t *n_nodes, int64_t *n_edges) {
+  if (n_nodes) *n_nodes = int64_t(ts->node_img.size());
+  if (n_edges) *n_edges = int64_t(ts->e1.size());
+  return 0;
+}
+int ref_merge_graph_get(ora_trackset *ts, int32_t *node_img, int32_t *node_line, int32_t *edge_n1, int32_t *edge_n2,
+                        double *edge_sim) {
+  for (size_t i = 0; i < ts->node_img.size(); ++i) {
+    if (node_img) node_img[i] = ts->node_img[i];
+    if (node_line) node_line[i] = ts->node_line[i];
+  }
+  for (size_t k = 0; k < ts->e1.size(); ++k) {
+    if (edge_n1) edge_n1[k] = ts->e1[k];
+    if (edge_n2) edge_n2[k] = ts->e2[k];
+    if (edge_sim) edge_sim[k] = ts->sim[k];
+  }
+  return 0;
 }
 
 // ---- free functions ----

@@ -1,12 +1,15 @@
-"""MergeToLineTracks without a GPU: the C ABI surface, synthetic.make_fit_segs, the golden files' own consistency, and
-the argument errors of limap_amd.merging.merging (raised before any device work)."""
+"""MergeToLineTracks without a GPU: the C ABI surface, synthetic.make_fit_segs, the golden files' own consistency, the
+CPU oracle's merge (oracle/lt_oracle.cpp ora_merge_to_tracks, the checker of tests/test_gpu_merge_oracle.py) against
+the golden files, and the argument errors of limap_amd.merging.merging (raised before any device work)."""
+import json
 import os
 import re
 
 import numpy as np
 import pytest
 
-from merge_fixtures import SCENES, call_args, load
+from merge_fixtures import (ANGLES, STAGES, SCENES, angle_scene, assert_stage, bits, call_args, generator, load,
+                            oracle_chain, pair_angles)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MERGE_ABI = ("lt_merge_to_tracks", "lt_merge_graph_size", "lt_merge_graph_get", "lt_merge_get_timers")
@@ -114,6 +117,52 @@ def test_golden_self_consistent(name):
     for t in range(len(off) - 1):
         m = nid[off[t]:off[t + 1]]
         assert np.all(np.diff(m) > 0) and np.all(g["labels"][m] == t)
+
+
+def _stage_arrays(o, stage):
+    p = stage + "_"
+    return dict(off=o[p + "off"], image_ids=o[p + "img"], line_ids=o[p + "lid"], node_ids=o[p + "nid"],
+                scores=o[p + "score"], line2d=o[p + "line2d"], line3d=o[p + "line3d"], line=o[p + "line"])
+
+
+@pytest.mark.parametrize("name", SCENES)
+def test_oracle_merge_reproduces_golden(oracle, name):
+    """the oracle's MergeToLineTracks and the fit-and-merge chain after it are what the reference's own code wrote"""
+    g = load(name)
+    o = oracle_chain(oracle, g)
+    for k in ("node_img", "node_line", "edge_n1", "edge_n2", "labels"):
+        assert np.array_equal(o[k], g[k]), k
+    assert np.array_equal(bits(o["edge_sim"]), bits(g["edge_sim"]))
+    for stage in STAGES:
+        assert_stage(_stage_arrays(o, stage), g, stage)
+
+
+def test_oracle_merge_reproduces_scene_e_digests(oracle):
+    gen = generator()
+    with open(os.path.join(ROOT, "tests", "golden", "merge", "merge_e_digests.json")) as f:
+        d = json.load(f)
+    o = oracle_chain(oracle, gen.scene_e_inputs())
+    assert len(o["node_img"]) == d["n_nodes"] and len(o["edge_n1"]) == d["n_edges"]
+    assert gen.digest(o["node_img"], o["node_line"]) == d["nodes"]
+    assert gen.digest(o["edge_n1"], o["edge_n2"], o["edge_sim"]) == d["edges"]
+    assert gen.digest(o["labels"]) == d["labels"]
+    for s in STAGES:
+        assert len(o[s + "_off"]) - 1 == d[f"{s}_tracks"], s
+        assert gen.digest(o[s + "_off"], o[s + "_img"], o[s + "_lid"], o[s + "_nid"]) == d[f"{s}_members"], s
+        assert gen.digest(o[s + "_line"]) == d[f"{s}_line"], s
+
+
+@pytest.mark.parametrize("th", [a for a in ANGLES if 0 < a < 90])
+def test_angle_scenes_decide_at_the_threshold(oracle, th):
+    """the pairs of merge_fixtures.angle_scene sit on both sides of th_angle, and the exact test decides them there:
+    a pair is linked in the self pass iff its angle is at most th_angle"""
+    o = oracle_chain(oracle, angle_scene(th))
+    linked = {(int(o["node_line"][i]), int(o["node_line"][j])) for i, j in zip(o["edge_n1"], o["edge_n2"])
+              if o["node_img"][i] == o["node_img"][j] == 0}
+    angles = pair_angles(th)
+    want = [n for n, a in enumerate(angles) if a <= th]
+    assert 0 < len(want) < len(angles)
+    assert sorted(n for n in range(len(angles)) if (2 * n, 2 * n + 1) in linked) == want
 
 
 def test_golden_covers_the_quirks():

@@ -21,6 +21,7 @@ import pytest
 
 from limap_amd import synthetic as syn
 
+import merge_fixtures
 from helpers import compare_best, compare_candidates, compare_tracks, run_oracle, small_scene
 from test_golden import _check, _feed, _load
 
@@ -371,3 +372,30 @@ def test_reference_error_conventions(ref):
         R.TriangulateImage(i0, {i1: np.array([[1000, 0]], np.int32)})  # line_id of the image itself (:87)
     with pytest.raises(RuntimeError):
         R.TriangulateImage(12345, {i1: np.array([[0, 0]], np.int32)})
+
+
+def _same_arrays(a, b, where):
+    assert sorted(a) == sorted(b), where
+    for k in a:
+        x, y = np.asarray(a[k]), np.asarray(b[k])
+        assert x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes(), f"{where}: {k}"
+
+
+_MERGE_EDGE = sorted(merge_fixtures.edge_scenes(ref_defined=True))
+
+
+@pytest.mark.parametrize("name", _MERGE_EDGE)
+def test_merge_edge_scenes(ref, oracle, name):
+    """MergeToLineTracks (merging.cc:347-511) and the fit-and-merge chain after it, bit for bit, on the edge-case scenes
+    of tests/test_gpu_merge_oracle.py: angles at and around th_angle and the device's guard cut, parallel and identical
+    lines, depth 0 and negative depth in the neighbour view, tied sims, row-tile sizes, a self-listed neighbour"""
+    g = merge_fixtures.edge_scenes(ref_defined=True)[name]()
+    _same_arrays(merge_fixtures.oracle_chain(ref, g), merge_fixtures.oracle_chain(oracle, g), name)
+
+
+@pytest.mark.parametrize("k", range(10))
+def test_merge_random_scenes(ref, oracle, k):
+    """random sizes, neighbour counts, failed fits, depth noise and every threshold / use_* flag of the linkers"""
+    g = merge_fixtures.random_scene(5100 + k)
+    o = merge_fixtures.oracle_chain(oracle, g)
+    _same_arrays(merge_fixtures.oracle_chain(ref, g), o, f"seed {5100 + k}")
