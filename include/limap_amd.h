@@ -305,6 +305,63 @@ int lt_merge_graph_get(lt_ctx *ctx, int32_t *node_img, int32_t *node_line, int32
  * whole call, [2] kernel attempts (more than 1 after an edge-buffer overflow), [3] edges */
 int lt_merge_get_timers(lt_ctx *ctx, double out[4]);
 
+/* ---- limap.fitting on the GPU (fitting/fitting.py:8-53, fitting/line3d_estimator.cc:7-109) ----
+ * LO-MSAC options (LORansacOptions as estimators/bindings.cc:50-75 exposes them) plus the parameters of
+ * estimate_seg3d_from_depth.  random_seed_ is honoured (`seed`): the reference reseeds from std::random_device. */
+typedef struct lt_fit_config {
+  double ransac_th;                /* 0.75: threshold = ransac_th * var2d * median(depth) / ((fx + fy) / 2) */
+  double min_percentage_inliers;   /* 0.6: a fit with inlier ratio below it fails */
+  double var2d;                    /* 5.0 */
+  double squared_inlier_threshold; /* 1.0: lt_fit_points only (squared_inlier_threshold_) */
+  double success_probability;      /* 0.9999, in [0, 1] */
+  double threshold_multiplier;     /* sqrt(2) */
+  int32_t min_num_iterations;      /* 100 */
+  int32_t max_num_iterations;      /* 10000 */
+  int32_t num_lo_steps;            /* 10 */
+  int32_t num_lsq_iterations;      /* 4 */
+  int32_t min_sample_multiplicator;  /* 7 */
+  int32_t non_min_sample_multiplier; /* 3 */
+  int32_t lo_starting_iterations;  /* 50 */
+  int32_t final_least_squares;     /* 0 or 1 */
+  uint64_t seed;                   /* 0 */
+} lt_fit_config;
+
+#define LT_DEPTH_F32 0
+#define LT_DEPTH_F64 1
+/* one depth map: h rows of w values, row r at ptr + r * row_stride elements; on_device = 1: a device pointer of the
+ * context's device (read in place), 0: host memory (uploaded by the call) */
+typedef struct lt_depth_map {
+  const void *ptr;
+  int64_t h, w, row_stride;
+  int32_t dtype; /* LT_DEPTH_F32 or LT_DEPTH_F64 */
+  int32_t on_device;
+} lt_depth_map;
+
+#define LT_FIT_OK 0
+#define LT_FIT_TOO_FEW_POINTS 1  /* 6 or fewer pixels with a non-inf depth (fitting.py:46-47) */
+#define LT_FIT_LOW_INLIER_RATIO 2 /* inlier ratio below min_percentage_inliers, no model counting as 0 (fitting.py:13) */
+
+void lt_fit_config_default(lt_fit_config *cfg);
+/* estimate_seg3d_from_depth (fitting/fitting.py:20-53) for every 2D segment of the images [img_begin, img_begin +
+ * n_maps) of an initialised context (ascending id order; the segments as given, never shifted by add_halfpix), maps[k]
+ * being the depth map of image img_begin + k.  Per segment, in the context's order from the first segment of img_begin:
+ * seg3d = start3 end3 (zeros when the fit fails, like runners/line_fitnmerge.py:38-39), status = LT_FIT_*, stats (may be
+ * NULL) = 5 int32: points kept, inliers, num_iterations, number_lo_iterations, 1 if the final model came from the
+ * least-squares solver.  Validation (sizes, pointers, dtype, option ranges, segment coordinates finite and below 2^29 in
+ * magnitude) happens before any device work: LT_ERR_ARGUMENT. */
+int lt_fit_segs(lt_ctx *ctx, int img_begin, int n_maps, const lt_depth_map *maps, const lt_fit_config *cfg,
+                double *seg3d, int32_t *status, int32_t *stats);
+/* Fit3DPoints + estimate_seg3d (fitting/line3d_estimator.cc:7-44, fitting/fitting.py:8-18) over a CSR of point sets:
+ * set s = xyz[3 off[s] .. 3 off[s+1]) (host memory, off[0] = 0), squared threshold cfg->squared_inlier_threshold.  Same
+ * outputs as lt_fit_segs (status LT_FIT_OK or LT_FIT_LOW_INLIER_RATIO); inlier_mask (may be NULL): off[n_sets] bytes, 1
+ * for the final inliers (stats.inlier_indices).  Needs no lt_init. */
+int lt_fit_points(lt_ctx *ctx, int64_t n_sets, const int64_t *off, const double *xyz, const lt_fit_config *cfg,
+                  double *seg3d, int32_t *status, int32_t *stats, uint8_t *inlier_mask);
+/* of the last lt_fit_segs / lt_fit_points: [0] device ms of the fit kernel (HIP events, last attempt), [1] device ms of
+ * the depth-map upload, [2] host ms of the call, [3] kernel attempts (more than 1 when the scratch of long segments
+ * overflowed) */
+int lt_fit_get_timers(lt_ctx *ctx, double out[4]);
+
 /* Counters of the last device run: [0] connections tested, [1] candidates, [2] ordered candidate
  * pairs swept by the scoring kernel (sum n_tris^2), [3] valid edges, [4] graph nodes,
  * [5] graph edges, [6] tracks, [7] nodes. */

@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = [
     "lt_fn_triangulate_line_with_direction", "lt_fn_triangulate_line_with_one_point", "lt_fn_compute_fundamental_matrix", "lt_fn_compute_epipolar_IoU",
     "lt_fn_triangulate_line", "lt_fn_aggregate_line3d_list", "lt_fn_pack_match_rows",
     "lt_fn_compressed_block_words", "lt_fn_pack_match_rows_compressed",
+    "lt_fit_config_default", "lt_fit_segs", "lt_fit_points", "lt_fit_get_timers",
 ]
 
 
@@ -95,6 +96,22 @@ def _preload_torch_hip_runtime():
             C.CDLL(cand, mode=C.RTLD_GLOBAL)
     except Exception:
         pass  # fall back to the system runtime
+
+
+class LtFitConfig(C.Structure):
+    """lt_fit_config of include/limap_amd.h"""
+    _fields_ = [("ransac_th", C.c_double), ("min_percentage_inliers", C.c_double), ("var2d", C.c_double),
+                ("squared_inlier_threshold", C.c_double), ("success_probability", C.c_double),
+                ("threshold_multiplier", C.c_double), ("min_num_iterations", C.c_int32),
+                ("max_num_iterations", C.c_int32), ("num_lo_steps", C.c_int32), ("num_lsq_iterations", C.c_int32),
+                ("min_sample_multiplicator", C.c_int32), ("non_min_sample_multiplier", C.c_int32),
+                ("lo_starting_iterations", C.c_int32), ("final_least_squares", C.c_int32), ("seed", C.c_uint64)]
+
+
+class LtDepthMap(C.Structure):
+    """lt_depth_map of include/limap_amd.h"""
+    _fields_ = [("ptr", C.c_void_p), ("h", C.c_int64), ("w", C.c_int64), ("row_stride", C.c_int64),
+                ("dtype", C.c_int32), ("on_device", C.c_int32)]
 
 
 def load_library():
@@ -201,6 +218,11 @@ def load_library():
     L.lt_fn_compressed_block_words.restype = C.c_int64
     L.lt_fn_pack_match_rows_compressed.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]
     L.lt_fn_triangulate_line.argtypes = [vp, dp, dp, dp, dp, C.c_int, dp]
+    L.lt_fit_config_default.argtypes = [C.POINTER(LtFitConfig)]
+    L.lt_fit_config_default.restype = None
+    L.lt_fit_segs.argtypes = [vp, C.c_int, C.c_int, C.POINTER(LtDepthMap), C.POINTER(LtFitConfig), dp, i32p, i32p]
+    L.lt_fit_points.argtypes = [vp, C.c_int64, i64p, dp, C.POINTER(LtFitConfig), dp, i32p, i32p, u8p]
+    L.lt_fit_get_timers.argtypes = [vp, dp]
     _lib = L
     return L
 

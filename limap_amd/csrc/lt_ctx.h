@@ -395,6 +395,9 @@ struct lt_ctx {
   std::vector<double> mg_sim;
   double mg_timers[4] = {0, 0, 0, 0};          // lt_merge_get_timers
   DevBuf d_mg_lines, d_mg_blks, d_mg_edges;
+  // ---- line fitting (lt_fit.cpp) ----
+  double ft_timers[4] = {0, 0, 0, 0};  // lt_fit_get_timers
+  DevBuf d_ft_maps, d_ft_imgs, d_ft_in, d_ft_out, d_ft_scr;
 };
 
 #define HIPCHK(ctx, call)                                                                  \

@@ -1,0 +1,259 @@
+// lt_fit.cpp -- limap.fitting on the GPU (fitting/fitting.py:8-53, fitting/line3d_estimator.cc): one 3D segment per 2D
+// segment of the context from a depth map per image (lt_fit_segs), and Fit3DPoints over a CSR of point sets
+// (lt_fit_points).  The host validates, uploads and launches once per batch; every segment's work runs on the device
+// (lt_kernels_fit.hip).  DESIGN §12.
+
+#include "lt_host.h"
+#include "lt_fit.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+using namespace lt;
+using lt_impl::now_ms;
+using lt_impl::test_switch;
+
+namespace {
+
+int check_cfg(lt_ctx *ctx, const lt_fit_config &c) {
+  auto bad = [&](const char *what) { return fail(ctx, LT_ERR_ARGUMENT, std::string("lt_fit: ") + what); };
+  if (!std::isfinite(c.ransac_th) || !std::isfinite(c.var2d) || !std::isfinite(c.min_percentage_inliers))
+    return bad("ransac_th, var2d and min_percentage_inliers must be finite");
+  if (!std::isfinite(c.squared_inlier_threshold) || c.squared_inlier_threshold < 0.0)
+    return bad("squared_inlier_threshold must be finite and >= 0");
+  if (!(c.success_probability >= 0.0 && c.success_probability <= 1.0)) return bad("success_probability outside [0, 1]");
+  if (!std::isfinite(c.threshold_multiplier)) return bad("threshold_multiplier must be finite");
+  if (c.min_num_iterations < 0 || c.max_num_iterations < 0 || c.min_num_iterations > 10000000 ||
+      c.max_num_iterations > 10000000)
+    return bad("iteration counts outside [0, 1e7]");
+  if (c.num_lo_steps < 0 || c.num_lo_steps > 100000 || c.num_lsq_iterations < 0 || c.num_lsq_iterations > 100000)
+    return bad("num_lo_steps / num_lsq_iterations outside [0, 1e5]");
+  if (c.min_sample_multiplicator < 0 || c.min_sample_multiplicator > 1000000 || c.non_min_sample_multiplier < 0 ||
+      c.non_min_sample_multiplier > 1000000 || c.lo_starting_iterations < 0)
+    return bad("sample multipliers outside [0, 1e6] or lo_starting_iterations < 0");
+  if (c.final_least_squares != 0 && c.final_least_squares != 1) return bad("final_least_squares must be 0 or 1");
+  return LT_OK;
+}
+
+FitCfg dev_cfg(const lt_fit_config &c) {
+  FitCfg f;
+  f.t2_points = c.squared_inlier_threshold;
+  f.ransac_th = c.ransac_th; f.min_pct = c.min_percentage_inliers; f.var2d = c.var2d;
+  f.pmiss = 1.0 - c.success_probability;
+  f.mult = c.threshold_multiplier;
+  f.min_it = c.min_num_iterations; f.max_it = c.max_num_iterations;
+  f.num_lo = c.num_lo_steps; f.num_lsq = c.num_lsq_iterations;
+  f.min_smp_mult = c.min_sample_multiplicator; f.nonmin_mult = c.non_min_sample_multiplier;
+  f.lo_start = c.lo_starting_iterations; f.final_ls = c.final_least_squares;
+  f.seed = c.seed;
+  return f;
+}
+
+// [seg3d 6 doubles | status int | stats 5 ints] per problem, 8-byte aligned blocks
+struct OutLayout {
+  size_t seg, status, stats, mask, bytes;
+  OutLayout(long long n, long long n_mask) {
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    seg = 0;
+    status = up(seg + 48 * (size_t)n);
+    stats = up(status + 4 * (size_t)n);
+    mask = up(stats + 20 * (size_t)n);
+    bytes = up(mask + (size_t)n_mask) + 256;
+  }
+};
+
+// the launch, run again with the counted scratch size when a long problem found no room; results do not depend on it
+template <class Launch>
+int run_with_scratch(lt_ctx *ctx, hipStream_t st, Launch launch, int *attempts) {
+  // points (32 B each): what the buffer already holds, at least 2^18; LT_TEST_FIT_SCRATCH_CAP forces a small first try
+  unsigned long long cap = ctx->d_ft_scr.cap > 256 ? (ctx->d_ft_scr.cap - 256) / 32 : 0;
+  if (cap < (1ull << 18)) cap = 1ull << 18;
+  if (const char *e = test_switch("LT_TEST_FIT_SCRATCH_CAP")) cap = std::max(1ull, std::strtoull(e, nullptr, 10));
+  for (*attempts = 1;; ++*attempts) {
+    ENSURE(ctx, ctx->d_ft_scr, 256 + 32 * (size_t)cap);
+    unsigned long long *d_cnt = ctx->d_ft_scr.as<unsigned long long>();
+    double *scr = reinterpret_cast<double *>(ctx->d_ft_scr.as<char>() + 256);
+    HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, 8, st));
+    launch(scr, cap, d_cnt);
+    HIPCHK(ctx, hipGetLastError());
+    unsigned long long used = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&used, d_cnt, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    if (used <= cap) return LT_OK;
+    cap = used;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+void lt_fit_config_default(lt_fit_config *c) {
+  c->ransac_th = 0.75;
+  c->min_percentage_inliers = 0.6;
+  c->var2d = 5.0;
+  c->squared_inlier_threshold = 1.0;
+  c->success_probability = 0.9999;
+  c->threshold_multiplier = std::sqrt(2.0);
+  c->min_num_iterations = 100;
+  c->max_num_iterations = 10000;
+  c->num_lo_steps = 10;
+  c->num_lsq_iterations = 4;
+  c->min_sample_multiplicator = 7;
+  c->non_min_sample_multiplier = 3;
+  c->lo_starting_iterations = 50;
+  c->final_least_squares = 0;
+  c->seed = 0;
+}
+
+int lt_fit_segs(lt_ctx *ctx, int img_begin, int n_maps, const lt_depth_map *maps, const lt_fit_config *cfg,
+                double *seg3d, int32_t *status, int32_t *stats) {
+  if (!ctx->inited) return fail(ctx, LT_ERR_STATE, "lt_fit_segs before lt_init");
+  if (!cfg || !seg3d || !status || (n_maps > 0 && !maps)) return fail(ctx, LT_ERR_ARGUMENT, "lt_fit_segs: null argument");
+  if (img_begin < 0 || n_maps < 0 || img_begin + (long long)n_maps > ctx->n_img)
+    return fail(ctx, LT_ERR_ARGUMENT, "lt_fit_segs: images outside the context");
+  if (int rc = check_cfg(ctx, *cfg)) return rc;
+  const double t_start = now_ms();
+  const long long g0 = ctx->seg_off[(size_t)img_begin], g1 = ctx->seg_off[(size_t)(img_begin + n_maps)];
+  const long long G = g1 - g0;
+  std::vector<FitImg> imgs((size_t)n_maps);
+  size_t host_bytes = 0;
+  for (int k = 0; k < n_maps; ++k) {
+    const lt_depth_map &m = maps[k];
+    const std::string who = "lt_fit_segs: map of image " + std::to_string(ctx->img_ids[(size_t)(img_begin + k)]) + ": ";
+    if (m.h < 0 || m.w < 0 || m.h >= (1ll << 31) || m.w >= (1ll << 31)) return fail(ctx, LT_ERR_ARGUMENT, who + "bad size");
+    if (m.dtype != LT_DEPTH_F32 && m.dtype != LT_DEPTH_F64) return fail(ctx, LT_ERR_ARGUMENT, who + "dtype");
+    if (m.on_device != 0 && m.on_device != 1) return fail(ctx, LT_ERR_ARGUMENT, who + "on_device must be 0 or 1");
+    if (m.h > 0 && m.w > 0) {
+      if (!m.ptr) return fail(ctx, LT_ERR_ARGUMENT, who + "null pointer");
+      if (m.row_stride < m.w) return fail(ctx, LT_ERR_ARGUMENT, who + "row stride below the width");
+    }
+    FitImg &f = imgs[(size_t)k];
+    f.map = m.ptr; f.h = m.h; f.w = m.w; f.stride = m.row_stride; f.dtype = m.dtype;
+    f.img_id = ctx->img_ids[(size_t)(img_begin + k)];
+    f.cam = img_begin + k;
+    f.seg_begin = ctx->seg_off[(size_t)(img_begin + k)] - g0;
+    f.seg_end = ctx->seg_off[(size_t)(img_begin + k) + 1] - g0;
+    f.pad_ = 0;
+    if (!m.on_device && m.h > 0 && m.w > 0)
+      host_bytes += (((size_t)(m.h - 1) * (size_t)m.row_stride + (size_t)m.w) * (m.dtype ? 8 : 4) + 255) & ~(size_t)255;
+  }
+  // segs.astype(int) and Bresenham stay in int64 for coordinates below 2^29 (the reference would enumerate every pixel)
+  const double *segs = ctx->h_segs_ptr + 4 * g0;
+  for (long long g = 0; g < 4 * G; ++g)
+    if (!(std::fabs(segs[g]) < 536870912.0))
+      return fail(ctx, LT_ERR_ARGUMENT, "lt_fit_segs: 2D segment coordinate not finite or beyond 2^29");
+  hipStream_t st = ctx->stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // start, maps uploaded, kernel start, kernel end
+  for (auto &e : ev) HIPCHK(ctx, hipEventCreate(&e));
+  HIPCHK(ctx, hipEventRecord(ev[0], st));
+  if (host_bytes) {
+    ENSURE(ctx, ctx->d_ft_maps, host_bytes);
+    size_t at = 0;
+    for (int k = 0; k < n_maps; ++k) {
+      const lt_depth_map &m = maps[k];
+      if (m.on_device || m.h == 0 || m.w == 0) continue;
+      const size_t b = ((size_t)(m.h - 1) * (size_t)m.row_stride + (size_t)m.w) * (m.dtype ? 8 : 4);
+      char *dst = ctx->d_ft_maps.as<char>() + at;
+      HIPCHK(ctx, hipMemcpyAsync(dst, m.ptr, b, hipMemcpyHostToDevice, st));
+      imgs[(size_t)k].map = dst;
+      at += (b + 255) & ~(size_t)255;
+    }
+  }
+  HIPCHK(ctx, hipEventRecord(ev[1], st));
+  const OutLayout L(G, 0);
+  ENSURE(ctx, ctx->d_ft_imgs, sizeof(FitImg) * (size_t)std::max(n_maps, 1));
+  ENSURE(ctx, ctx->d_ft_in, 32 * (size_t)std::max<long long>(G, 1));
+  ENSURE(ctx, ctx->d_ft_out, L.bytes);
+  if (n_maps) HIPCHK(ctx, hipMemcpyAsync(ctx->d_ft_imgs.p, imgs.data(), sizeof(FitImg) * (size_t)n_maps, hipMemcpyHostToDevice, st));
+  if (G) HIPCHK(ctx, hipMemcpyAsync(ctx->d_ft_in.p, segs, 32 * (size_t)G, hipMemcpyHostToDevice, st));
+  const FitCfg fc = dev_cfg(*cfg);
+  char *out = ctx->d_ft_out.as<char>();
+  int attempts = 0;
+  if (int rc = run_with_scratch(ctx, st, [&](double *scr, unsigned long long cap, unsigned long long *cnt) {
+        (void)hipEventRecord(ev[2], st);
+        launch_fit_depth(st, G, n_maps, ctx->d_ft_imgs.as<FitImg>(), ctx->d_ft_in.as<double>(), ctx->d_cams.as<Cam>(),
+                         fc, scr, cap, cnt, reinterpret_cast<double *>(out + L.seg),
+                         reinterpret_cast<int *>(out + L.status), reinterpret_cast<int *>(out + L.stats));
+        (void)hipEventRecord(ev[3], st);
+      }, &attempts))
+    return rc;
+  if (G) {
+    HIPCHK(ctx, hipMemcpyAsync(seg3d, out + L.seg, 48 * (size_t)G, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(status, out + L.status, 4 * (size_t)G, hipMemcpyDeviceToHost, st));
+    if (stats) HIPCHK(ctx, hipMemcpyAsync(stats, out + L.stats, 20 * (size_t)G, hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  float up_ms = 0.f, k_ms = 0.f;
+  (void)hipEventElapsedTime(&up_ms, ev[0], ev[1]);
+  (void)hipEventElapsedTime(&k_ms, ev[2], ev[3]);
+  for (auto &e : ev) (void)hipEventDestroy(e);
+  ctx->ft_timers[0] = k_ms;
+  ctx->ft_timers[1] = up_ms;
+  ctx->ft_timers[2] = now_ms() - t_start;
+  ctx->ft_timers[3] = attempts;
+  return LT_OK;
+}
+
+int lt_fit_points(lt_ctx *ctx, int64_t n_sets, const int64_t *off, const double *xyz, const lt_fit_config *cfg,
+                  double *seg3d, int32_t *status, int32_t *stats, uint8_t *inlier_mask) {
+  if (!off || !cfg || !seg3d || !status || n_sets < 0) return fail(ctx, LT_ERR_ARGUMENT, "lt_fit_points: null argument");
+  if (off[0] != 0) return fail(ctx, LT_ERR_ARGUMENT, "lt_fit_points: off[0] must be 0");
+  for (int64_t s = 0; s < n_sets; ++s)
+    if (off[s + 1] < off[s] || off[s + 1] - off[s] >= (1ll << 30))
+      return fail(ctx, LT_ERR_ARGUMENT, "lt_fit_points: offsets must be non-decreasing, sets below 2^30 points");
+  const int64_t N = off[n_sets];
+  if (N > 0 && !xyz) return fail(ctx, LT_ERR_ARGUMENT, "lt_fit_points: null points");
+  if (int rc = check_cfg(ctx, *cfg)) return rc;
+  const double t_start = now_ms();
+  hipStream_t st = ctx->stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const OutLayout L(n_sets, inlier_mask ? N : 0);
+  const size_t off_bytes = ((size_t)(n_sets + 1) * 8 + 255) & ~(size_t)255;
+  ENSURE(ctx, ctx->d_ft_in, off_bytes + 24 * (size_t)std::max<int64_t>(N, 1));
+  ENSURE(ctx, ctx->d_ft_out, L.bytes);
+  char *in = ctx->d_ft_in.as<char>(), *out = ctx->d_ft_out.as<char>();
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  for (auto &e : ev) HIPCHK(ctx, hipEventCreate(&e));
+  HIPCHK(ctx, hipMemcpyAsync(in, off, (size_t)(n_sets + 1) * 8, hipMemcpyHostToDevice, st));
+  if (N) HIPCHK(ctx, hipMemcpyAsync(in + off_bytes, xyz, 24 * (size_t)N, hipMemcpyHostToDevice, st));
+  if (inlier_mask && N) HIPCHK(ctx, hipMemsetAsync(out + L.mask, 0, (size_t)N, st));
+  const FitCfg fc = dev_cfg(*cfg);
+  int attempts = 0;
+  if (int rc = run_with_scratch(ctx, st, [&](double *scr, unsigned long long cap, unsigned long long *cnt) {
+        (void)hipEventRecord(ev[0], st);
+        launch_fit_points(st, n_sets, reinterpret_cast<const long long *>(in),
+                          reinterpret_cast<const double *>(in + off_bytes), fc, scr, cap, cnt,
+                          reinterpret_cast<double *>(out + L.seg), reinterpret_cast<int *>(out + L.status),
+                          reinterpret_cast<int *>(out + L.stats),
+                          inlier_mask ? reinterpret_cast<unsigned char *>(out + L.mask) : nullptr);
+        (void)hipEventRecord(ev[1], st);
+      }, &attempts))
+    return rc;
+  if (n_sets) {
+    HIPCHK(ctx, hipMemcpyAsync(seg3d, out + L.seg, 48 * (size_t)n_sets, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(status, out + L.status, 4 * (size_t)n_sets, hipMemcpyDeviceToHost, st));
+    if (stats) HIPCHK(ctx, hipMemcpyAsync(stats, out + L.stats, 20 * (size_t)n_sets, hipMemcpyDeviceToHost, st));
+  }
+  if (inlier_mask && N) HIPCHK(ctx, hipMemcpyAsync(inlier_mask, out + L.mask, (size_t)N, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  float k_ms = 0.f;
+  (void)hipEventElapsedTime(&k_ms, ev[0], ev[1]);
+  for (auto &e : ev) (void)hipEventDestroy(e);
+  ctx->ft_timers[0] = k_ms;
+  ctx->ft_timers[1] = 0.0;
+  ctx->ft_timers[2] = now_ms() - t_start;
+  ctx->ft_timers[3] = attempts;
+  return LT_OK;
+}
+
+int lt_fit_get_timers(lt_ctx *ctx, double out[4]) {
+  for (int k = 0; k < 4; ++k) out[k] = ctx->ft_timers[k];
+  return LT_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,321 @@
+"""Mirror of `limap.fitting` and of the fit step of `limap.runners.line_fitnmerge` with the fitter on the GPU:
+
+    Fit3DPoints, estimate_seg3d, estimate_seg3d_from_depth   (fitting/fitting.py:8-53, fitting/line3d_estimator.cc)
+    fit_3d_segs                                              (runners/line_fitnmerge.py:17-70)
+    fit_3d_segs_arrays                                       the fast form: (M, 2, 3) per image plus stats
+
+Same names, arguments and results.  LO-MSAC runs with the project's counter-based generator: `random_seed_` (or `seed`)
+decides the draws and a segment's result depends on (seed, image id, line index) alone -- not on the batch, the image
+order, the chunking or the device.  The reference reseeds from std::random_device on every call.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import _capi
+from .base import Line3d
+
+STATUS_OK, STATUS_TOO_FEW_POINTS, STATUS_LOW_INLIER_RATIO = 0, 1, 2
+STATS_FIELDS = ("num_points", "num_inliers", "num_iterations", "number_lo_iterations", "from_lo")  # columns of stats
+
+
+class LORansacOptions:
+    """ransac_lib::LORansacOptions as estimators/bindings.cc:50-75 exposes it, with RansacLib's defaults."""
+
+    def __init__(self):
+        self.min_num_iterations_ = 100
+        self.max_num_iterations_ = 10000
+        self.success_probability_ = 0.9999
+        self.squared_inlier_threshold_ = 1.0
+        self.random_seed_ = 0
+        self.num_lo_steps_ = 10
+        self.threshold_multiplier_ = math.sqrt(2.0)
+        self.num_lsq_iterations_ = 4
+        self.min_sample_multiplicator_ = 7
+        self.non_min_sample_multiplier_ = 3
+        self.lo_starting_iterations_ = 50
+        self.final_least_squares_ = False
+
+
+class RansacStatistics:
+    """ransac_lib::RansacStatistics of Fit3DPoints"""
+
+    def __init__(self, num_iterations, best_num_inliers, inlier_ratio, inlier_indices, number_lo_iterations, from_lo):
+        self.num_iterations = num_iterations
+        self.best_num_inliers = best_num_inliers
+        self.inlier_ratio = inlier_ratio
+        self.inlier_indices = inlier_indices
+        self.number_lo_iterations = number_lo_iterations
+        self.from_lo = from_lo
+
+
+def _check_int(name, v, lo, hi):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+        raise ValueError(f"fitting: {name} must be an integer in [{lo}, {hi}], got {v!r}")
+    return int(v)
+
+
+def _check_float(name, v, nonneg=False):
+    try:
+        f = float(v)
+    except (TypeError, ValueError):
+        raise ValueError(f"fitting: {name} must be a number, got {v!r}") from None
+    if not math.isfinite(f) or (nonneg and f < 0.0):
+        raise ValueError(f"fitting: {name} must be finite{' and >= 0' if nonneg else ''}, got {v!r}")
+    return f
+
+
+def _config(options=None, ransac_th=0.75, min_percentage_inliers=0.6, var2d=5.0, seed=None):
+    """lt_fit_config from LORansacOptions (or None: defaults), checked here before any device work"""
+    o = options if options is not None else LORansacOptions()
+    c = _capi.LtFitConfig()
+    c.ransac_th = _check_float("ransac_th", ransac_th)
+    c.min_percentage_inliers = _check_float("min_percentage_inliers", min_percentage_inliers)
+    c.var2d = _check_float("var2d", var2d)
+    c.squared_inlier_threshold = _check_float("squared_inlier_threshold_", o.squared_inlier_threshold_, nonneg=True)
+    p = _check_float("success_probability_", o.success_probability_)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"fitting: success_probability_ must lie in [0, 1], got {p}")
+    c.success_probability = p
+    c.threshold_multiplier = _check_float("threshold_multiplier_", o.threshold_multiplier_)
+    c.min_num_iterations = _check_int("min_num_iterations_", o.min_num_iterations_, 0, 10_000_000)
+    c.max_num_iterations = _check_int("max_num_iterations_", o.max_num_iterations_, 0, 10_000_000)
+    c.num_lo_steps = _check_int("num_lo_steps_", o.num_lo_steps_, 0, 100_000)
+    c.num_lsq_iterations = _check_int("num_lsq_iterations_", o.num_lsq_iterations_, 0, 100_000)
+    c.min_sample_multiplicator = _check_int("min_sample_multiplicator_", o.min_sample_multiplicator_, 0, 1_000_000)
+    c.non_min_sample_multiplier = _check_int("non_min_sample_multiplier_", o.non_min_sample_multiplier_, 0, 1_000_000)
+    c.lo_starting_iterations = _check_int("lo_starting_iterations_", o.lo_starting_iterations_, 0, 2**31 - 1)
+    c.final_least_squares = 1 if bool(o.final_least_squares_) else 0
+    s = o.random_seed_ if seed is None else seed
+    c.seed = _check_int("seed", s, -(2**63), 2**64 - 1) & (2**64 - 1)
+    return c
+
+
+_contexts = {}
+
+
+def _context(device=0):
+    """one context per device for the calls that bring no scene (lt_fit_points)"""
+    ctx = _contexts.get(device)
+    if ctx is None:
+        ctx = _contexts[device] = _capi.Context(device=device)
+    return ctx
+
+
+# ---- point sets -----------------------------------------------------------------------------------------------------
+def fit_points_arrays(point_sets, options=None, min_percentage_inliers=0.0, device=0):
+    """lt_fit_points over a list of (N_i, 3) point sets: -> dict(seg (S, 2, 3), status (S,), stats (S, 5),
+    inlier_mask (sum N_i,), off (S + 1,))"""
+    sets = [np.ascontiguousarray(np.asarray(p, np.float64).reshape(-1, 3)) for p in point_sets]
+    off = np.zeros(len(sets) + 1, np.int64)
+    off[1:] = np.cumsum([len(p) for p in sets])
+    cfg = _config(options, min_percentage_inliers=min_percentage_inliers)
+    xyz = np.ascontiguousarray(np.concatenate(sets, 0) if sets else np.zeros((0, 3)))
+    S, N = len(sets), int(off[-1])
+    seg = np.zeros((max(S, 1), 6)); status = np.zeros(max(S, 1), np.int32); stats = np.zeros((max(S, 1), 5), np.int32)
+    mask = np.zeros(max(N, 1), np.uint8)
+    ctx = _context(device)
+    p = _capi.ptr
+    ctx.chk(ctx.L.lt_fit_points(ctx.h, S, p(off, C.c_int64), p(xyz.reshape(-1) if N else np.zeros(3), C.c_double),
+                                C.byref(cfg), p(seg, C.c_double), p(status, C.c_int32), p(stats, C.c_int32),
+                                p(mask, C.c_uint8)))
+    return dict(seg=seg[:S].reshape(S, 2, 3), status=status[:S], stats=stats[:S], inlier_mask=mask[:N].astype(bool),
+                off=off)
+
+
+def Fit3DPoints(points, options):
+    """fitting::Fit3DPoints (line3d_estimator.cc:7-44): points (3, N) -> (Line3d, RansacStatistics)"""
+    P = np.asarray(points, np.float64)
+    if P.ndim != 2 or P.shape[0] != 3:
+        raise ValueError(f"Fit3DPoints: points must be (3, N), got shape {P.shape}")
+    r = fit_points_arrays([P.T], options, min_percentage_inliers=0.0)
+    st = r["stats"][0]
+    inl = np.nonzero(r["inlier_mask"])[0].tolist()
+    n = P.shape[1]
+    ratio = len(inl) / n if n >= 2 else 0.0
+    stats = RansacStatistics(int(st[2]), int(st[1]), ratio, inl, int(st[3]), bool(st[4]))
+    seg = r["seg"][0]
+    return Line3d(seg[0], seg[1]), stats
+
+
+def estimate_seg3d(points, ransac_th=0.75, min_percentage_inliers=0.6):
+    """fitting.py:8-18: None or (start, end)"""
+    options = LORansacOptions()
+    options.squared_inlier_threshold_ = ransac_th * ransac_th
+    line, stats = Fit3DPoints(points, options)
+    if stats.inlier_ratio < min_percentage_inliers:
+        return None
+    return line.start, line.end
+
+
+# ---- depth maps -----------------------------------------------------------------------------------------------------
+def _is_torch(x):
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+def _map_of(depth, device=0):
+    """(LtDepthMap, keep-alive) of a NumPy array or a torch tensor; integer maps become float64 (exact), like NumPy's
+    promotion in the reference; float16 is refused.  A GPU tensor must live on `device`, the context's device; it is
+    read in place on the context's stream, so the caller orders that read after torch's work (_sync_torch)."""
+    if _is_torch(depth):
+        import torch
+        if depth.dim() != 2:
+            raise ValueError(f"fitting: a depth map must be 2-D, got shape {tuple(depth.shape)}")
+        if depth.dtype == torch.float16 or depth.dtype == torch.bfloat16:
+            raise ValueError("fitting: float16 depth maps are not supported")
+        if depth.is_cuda and depth.device.index != device:
+            raise ValueError(f"fitting: a depth map on {depth.device} for a fit on cuda:{device}")
+        if depth.dtype not in (torch.float32, torch.float64):
+            depth = depth.to(torch.float64)
+        if depth.stride(1) != 1 or depth.stride(0) < depth.shape[1]:
+            depth = depth.contiguous()
+        on_dev = 1 if depth.is_cuda else 0
+        if not on_dev:
+            return _map_of(depth.numpy())
+        dm = _capi.LtDepthMap(C.c_void_p(depth.data_ptr()), depth.shape[0], depth.shape[1], depth.stride(0),
+                              0 if depth.dtype == torch.float32 else 1, 1)
+        return dm, depth
+    a = np.asarray(depth)
+    if a.ndim != 2:
+        raise ValueError(f"fitting: a depth map must be 2-D, got shape {a.shape}")
+    if a.dtype == np.float16:
+        raise ValueError("fitting: float16 depth maps are not supported")
+    if a.dtype not in (np.float32, np.float64):
+        if a.dtype.kind not in "iub":
+            raise ValueError(f"fitting: unsupported depth dtype {a.dtype}")
+        a = a.astype(np.float64)
+    if a.strides[1] != a.itemsize or a.strides[0] % a.itemsize:
+        a = np.ascontiguousarray(a)
+    dm = _capi.LtDepthMap(C.c_void_p(a.ctypes.data), a.shape[0], a.shape[1], a.strides[0] // a.itemsize,
+                          0 if a.dtype == np.float32 else 1, 0)
+    return dm, a
+
+
+def _sync_torch(device):
+    """the context's stream does not wait for torch's streams: a map a network has just written, and the conversions of
+    _map_of, must be finished before lt_fit_segs reads them"""
+    import torch
+    torch.cuda.synchronize(device)
+
+
+def _shape_of(depth):
+    return tuple(int(v) for v in depth.shape)
+
+
+def _read_depth(reader, camview):
+    """a reader's map (read_depth(img_hw=[h, w]) when the view knows its size), an array or a tensor"""
+    if hasattr(reader, "read_depth"):
+        hw = None
+        if hasattr(camview, "h") and hasattr(camview, "w"):
+            hw = [int(camview.h()), int(camview.w())]
+        d = reader.read_depth(img_hw=hw) if hw is not None else reader.read_depth()
+    else:
+        d = reader
+    if hasattr(camview, "h") and hasattr(camview, "w"):
+        if _shape_of(d)[:2] != (int(camview.h()), int(camview.w())):
+            raise ValueError(f"fitting: depth map of shape {_shape_of(d)} for a view of {camview.h()} x {camview.w()}")
+    return d
+
+
+def _segs4(segs):
+    s = np.asarray(segs, np.float64)
+    if s.size == 0:
+        return np.zeros((0, 4))
+    s = s.reshape(len(s), -1)
+    if s.shape[1] < 4:
+        raise ValueError(f"fitting: 2D segments need 4 columns, got {s.shape}")
+    s = np.ascontiguousarray(s[:, :4])
+    if not (np.abs(s) < 2.0**29).all():
+        raise ValueError("fitting: 2D segment coordinates must be finite and below 2^29 in magnitude")
+    return s
+
+
+def _fitting_args(fitting_config):
+    fc = dict(fitting_config or {})
+    return (fc.get("ransac_th", 0.75), fc.get("min_percentage_inliers", 0.6), fc.get("var2d", 5.0))
+
+
+def fit_3d_segs_arrays(all_2d_segs, imagecols, depths, fitting_config=None, seed=0, max_chunk_bytes=1 << 30,
+                       options=None, device=0):
+    """fit_3d_segs in array form: -> (dict img_id -> (M, 2, 3) float64, dict img_id -> dict(status (M,), stats (M, 5)),
+    timers).  Images go through the device in ascending id order in chunks whose depth maps stay under
+    max_chunk_bytes; the results do not depend on the chunking."""
+    from .triangulation import _view_arrays
+    ransac_th, min_pct, var2d = _fitting_args(fitting_config)
+    cfg = _config(options, ransac_th, min_pct, var2d, seed)
+    ids = sorted(int(i) for i in imagecols.get_img_ids())
+    segs = {}
+    k = np.zeros((len(ids), 4)); q = np.zeros((len(ids), 4)); t = np.zeros((len(ids), 3))
+    seg_off = np.zeros(len(ids) + 1, np.int64)
+    for n, i in enumerate(ids):
+        k[n], q[n], t[n] = _view_arrays(imagecols.camview(i))
+        segs[i] = _segs4(all_2d_segs[i]) if i in all_2d_segs else np.zeros((0, 4))
+        seg_off[n + 1] = seg_off[n] + len(segs[i])
+    G = int(seg_off[-1])
+    allsegs = np.ascontiguousarray(np.concatenate([segs[i] for i in ids], 0)) if ids else np.zeros((0, 4))
+    for i in ids:
+        if i not in depths:
+            raise KeyError(f"fitting: no depth map for image {i}")
+    seg = np.zeros((max(G, 1), 6)); status = np.zeros(max(G, 1), np.int32); stats = np.zeros((max(G, 1), 5), np.int32)
+    timers = dict(device_ms=0.0, upload_ms=0.0, host_ms=0.0, attempts=0, chunks=0)
+    p = _capi.ptr
+    ctx = None
+    n = 0
+    carry = None  # the map that did not fit into the last chunk: it opens the next one (a reader is not read twice)
+    while n < len(ids):
+        # the maps of one chunk are read and checked before its device work (the context comes after the first chunk)
+        maps, keep, used, on_dev = [], [], 0, False
+        m = n
+        while m < len(ids):
+            if carry is not None:
+                (dm, ka), carry = carry, None
+            else:
+                i = ids[m]
+                dm, ka = _map_of(_read_depth(depths[i], imagecols.camview(i)), device)
+            nbytes = int(dm.h) * int(dm.row_stride) * (4 if dm.dtype == 0 else 8)
+            if m > n and used + nbytes > max_chunk_bytes:
+                carry = (dm, ka)
+                break
+            maps.append(dm); keep.append(ka); used += nbytes; on_dev = on_dev or bool(dm.on_device)
+            m += 1
+        if ctx is None:
+            ctx = _capi.Context(device=device)
+            ctx.init(ids, k, q, t, seg_off, allsegs)
+        if on_dev:
+            _sync_torch(device)
+        arr = (_capi.LtDepthMap * len(maps))(*maps)
+        g0 = int(seg_off[n])
+        ctx.chk(ctx.L.lt_fit_segs(ctx.h, n, len(maps), arr, C.byref(cfg), p(seg[g0:], C.c_double),
+                                  p(status[g0:], C.c_int32), p(stats[g0:], C.c_int32)))
+        tm = np.zeros(4)
+        ctx.chk(ctx.L.lt_fit_get_timers(ctx.h, p(tm, C.c_double)))
+        timers["device_ms"] += tm[0]; timers["upload_ms"] += tm[1]; timers["host_ms"] += tm[2]
+        timers["attempts"] = max(timers["attempts"], int(tm[3])); timers["chunks"] += 1
+        del keep
+        n = m
+    out, info = {}, {}
+    for j, i in enumerate(ids):
+        a, b = int(seg_off[j]), int(seg_off[j + 1])
+        out[i] = seg[a:b].reshape(b - a, 2, 3).copy()
+        info[i] = dict(status=status[a:b].copy(), stats=stats[a:b].copy())
+    return out, info, timers
+
+
+def fit_3d_segs(all_2d_segs, imagecols, depths, fitting_config, seed=0, max_chunk_bytes=1 << 30):
+    """runners/line_fitnmerge.py:17-70: dict img_id -> list of (start, end) float64 (3,) arrays, zeros where the fit
+    fails.  fitting_config["n_jobs"] is accepted and ignored."""
+    arrs, _, _ = fit_3d_segs_arrays(all_2d_segs, imagecols, depths, fitting_config, seed, max_chunk_bytes)
+    return {i: [(a[0].copy(), a[1].copy()) for a in arrs[i]] for i in arrs}
+
+
+def estimate_seg3d_from_depth(seg2d, depth, camview, ransac_th=0.75, min_percentage_inliers=0.6, var2d=5.0, seed=0):
+    """fitting.py:20-53 for one segment: None or (start, end)"""
+    from .base import ImageCollection
+    ic = ImageCollection({0: camview})
+    arrs, info, _ = fit_3d_segs_arrays({0: np.asarray(seg2d, np.float64).reshape(1, -1)}, ic, {0: depth},
+                                       dict(ransac_th=ransac_th, min_percentage_inliers=min_percentage_inliers,
+                                            var2d=var2d), seed=seed)
+    if info[0]["status"][0] != STATUS_OK:
+        return None
+    return arrs[0][0, 0].copy(), arrs[0][0, 1].copy()
