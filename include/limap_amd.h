@@ -357,8 +357,33 @@ int lt_fit_segs(lt_ctx *ctx, int img_begin, int n_maps, const lt_depth_map *maps
  * for the final inliers (stats.inlier_indices).  Needs no lt_init. */
 int lt_fit_points(lt_ctx *ctx, int64_t n_sets, const int64_t *off, const double *xyz, const lt_fit_config *cfg,
                   double *seg3d, int32_t *status, int32_t *stats, uint8_t *inlier_mask);
-/* of the last lt_fit_segs / lt_fit_points: [0] device ms of the fit kernel (HIP events, last attempt), [1] device ms of
- * the depth-map upload, [2] host ms of the call, [3] kernel attempts (more than 1 when the scratch of long segments
+/* one 3D point scan (estimate_seg3d_from_points3d, fitting/fitting.py:56-102): h rows of w pixels
+ * of 3 channels (x, y, z in the camera frame, NaN where the scan has no point), channel c of pixel (r, x) at ptr + r *
+ * row_stride + x * pix_stride + c * chan_stride elements (strides >= 0); img_h, img_w: the camera's image size (the
+ * reference's camview.h(), camview.w()), which need not be the scan's.  dtype LT_DEPTH_F32 / LT_DEPTH_F64: float32 is
+ * widened to double exactly (an extension: the reference's grid_sample refuses float32 scans).  on_device as
+ * lt_depth_map. */
+typedef struct lt_scan_map {
+  const void *ptr;
+  int64_t h, w, row_stride, pix_stride, chan_stride;
+  int64_t img_h, img_w;
+  int32_t dtype;
+  int32_t on_device;
+} lt_scan_map;
+
+#define LT_FIT_SCAN_OUT_OF_RANGE 3 /* a kept sample normalises outside (-1, 1) of the scan (hloc's interpolate_scan assert) */
+
+/* estimate_seg3d_from_points3d for every 2D segment of the images [img_begin, img_begin + n_maps), maps[k] being the
+ * scan of image img_begin + k: linspace samples of the segment (int(2 |seg|) of them) strictly inside the camera's
+ * image, bilinear scan interpolation with a per-channel nearest fallback, the samples without a NaN channel kept; the
+ * threshold from the median ray depth; points R^T p - R^T t, or Tr[:3, :3] p + Tr[:3, 3] with Tr = scan_poses[12 k ..
+ * 12 k + 12) (row-major 3 x 4; NULL: the camera transform for every image).  Outputs, timers and validation as
+ * lt_fit_segs (h, w, img_h, img_w >= 2, the camera's below 2^24, poses finite); status LT_FIT_SCAN_OUT_OF_RANGE skips
+ * the fit of that segment. */
+int lt_fit_scans(lt_ctx *ctx, int img_begin, int n_maps, const lt_scan_map *maps, const double *scan_poses,
+                 const lt_fit_config *cfg, double *seg3d, int32_t *status, int32_t *stats);
+/* of the last lt_fit_segs / lt_fit_scans / lt_fit_points: [0] device ms of the fit kernel (HIP events, last attempt),
+ * [1] device ms of the depth-map / scan upload, [2] host ms of the call, [3] kernel attempts (more than 1 when the scratch of long segments
  * overflowed) */
 int lt_fit_get_timers(lt_ctx *ctx, double out[4]);
 

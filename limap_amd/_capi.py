@@ -30,7 +30,7 @@ EXPORTED_SYMBOLS = [
     "lt_fn_triangulate_line_with_direction", "lt_fn_triangulate_line_with_one_point", "lt_fn_compute_fundamental_matrix", "lt_fn_compute_epipolar_IoU",
     "lt_fn_triangulate_line", "lt_fn_aggregate_line3d_list", "lt_fn_pack_match_rows",
     "lt_fn_compressed_block_words", "lt_fn_pack_match_rows_compressed",
-    "lt_fit_config_default", "lt_fit_segs", "lt_fit_points", "lt_fit_get_timers",
+    "lt_fit_config_default", "lt_fit_segs", "lt_fit_scans", "lt_fit_points", "lt_fit_get_timers",
 ]
 
 
@@ -111,6 +111,13 @@ class LtFitConfig(C.Structure):
 class LtDepthMap(C.Structure):
     """lt_depth_map of include/limap_amd.h"""
     _fields_ = [("ptr", C.c_void_p), ("h", C.c_int64), ("w", C.c_int64), ("row_stride", C.c_int64),
+                ("dtype", C.c_int32), ("on_device", C.c_int32)]
+
+
+class LtScanMap(C.Structure):
+    """lt_scan_map of include/limap_amd.h"""
+    _fields_ = [("ptr", C.c_void_p), ("h", C.c_int64), ("w", C.c_int64), ("row_stride", C.c_int64),
+                ("pix_stride", C.c_int64), ("chan_stride", C.c_int64), ("img_h", C.c_int64), ("img_w", C.c_int64),
                 ("dtype", C.c_int32), ("on_device", C.c_int32)]
 
 
@@ -221,6 +228,7 @@ def load_library():
     L.lt_fit_config_default.argtypes = [C.POINTER(LtFitConfig)]
     L.lt_fit_config_default.restype = None
     L.lt_fit_segs.argtypes = [vp, C.c_int, C.c_int, C.POINTER(LtDepthMap), C.POINTER(LtFitConfig), dp, i32p, i32p]
+    L.lt_fit_scans.argtypes = [vp, C.c_int, C.c_int, C.POINTER(LtScanMap), dp, C.POINTER(LtFitConfig), dp, i32p, i32p]
     L.lt_fit_points.argtypes = [vp, C.c_int64, i64p, dp, C.POINTER(LtFitConfig), dp, i32p, i32p, u8p]
     L.lt_fit_get_timers.argtypes = [vp, dp]
     _lib = L

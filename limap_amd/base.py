@@ -119,8 +119,10 @@ class CameraView:
     """camera_view.h:56-88 reduced to the undistorted pinhole the hot path requires
     (base_line_triangulator.cc:49)."""
 
-    def __init__(self, kvec, qvec, tvec, image_name="none"):
+    def __init__(self, kvec, qvec, tvec, image_name="none", hw=None):
         self.kvec = np.asarray(kvec, float).reshape(4)
+        # hw = (h, w): the image size (camera.h / camera.w); None when unknown -- h() and w() then return None
+        self._hw = None if hw is None else (int(hw[0]), int(hw[1]))
         q = np.asarray(qvec, float).reshape(4)
         n = np.linalg.norm(q)
         self.qvec = q / n if n > 0 else q
@@ -132,6 +134,12 @@ class CameraView:
 
     def image_name(self):
         return self._name
+
+    def h(self):
+        return None if self._hw is None else self._hw[0]
+
+    def w(self):
+        return None if self._hw is None else self._hw[1]
 
     def K(self):
         fx, fy, cx, cy = self.kvec
@@ -157,8 +165,8 @@ class ImageCollection:
         self._views = dict(views or {})
 
     @classmethod
-    def from_arrays(cls, img_ids, kvec, qvec, tvec):
-        return cls({int(i): CameraView(kvec[k], qvec[k], tvec[k]) for k, i in enumerate(img_ids)})
+    def from_arrays(cls, img_ids, kvec, qvec, tvec, hw=None):
+        return cls({int(i): CameraView(kvec[k], qvec[k], tvec[k], hw=hw) for k, i in enumerate(img_ids)})
 
     def get_img_ids(self):
         return sorted(self._views.keys())
@@ -174,6 +182,9 @@ class ImageCollection:
 
     def IsUndistorted(self):
         return True
+
+    def image_name(self, img_id):
+        return self._views[img_id].image_name()
 
     def get_image_name_dict(self):  # image_collection.cc: img_id -> image name
         return {i: self._views[i].image_name() for i in self.get_img_ids()}

@@ -1,7 +1,7 @@
-// lt_fit.cpp -- limap.fitting on the GPU (fitting/fitting.py:8-53, fitting/line3d_estimator.cc): one 3D segment per 2D
-// segment of the context from a depth map per image (lt_fit_segs), and Fit3DPoints over a CSR of point sets
-// (lt_fit_points).  The host validates, uploads and launches once per batch; every segment's work runs on the device
-// (lt_kernels_fit.hip).  DESIGN §12.
+// lt_fit.cpp -- limap.fitting on the GPU (fitting/fitting.py:8-102, fitting/line3d_estimator.cc): one 3D segment per 2D
+// segment of the context from a depth map (lt_fit_segs) or a 3D point scan (lt_fit_scans) per image, and Fit3DPoints
+// over a CSR of point sets (lt_fit_points).  The host validates, uploads and launches once per batch; every segment's
+// work runs on the device (lt_kernels_fit.hip).  DESIGN §12, §13.
 
 #include "lt_host.h"
 #include "lt_fit.h"
@@ -87,6 +87,53 @@ int run_with_scratch(lt_ctx *ctx, hipStream_t st, Launch launch, int *attempts) 
   }
 }
 
+// segs.astype(int) / linspace stay exact for coordinates below 2^29 (the reference would enumerate every pixel)
+int check_segs(lt_ctx *ctx, const char *who, const double *segs, long long G) {
+  for (long long g = 0; g < 4 * G; ++g)
+    if (!(std::fabs(segs[g]) < 536870912.0))
+      return fail(ctx, LT_ERR_ARGUMENT, std::string(who) + ": 2D segment coordinate not finite or beyond 2^29");
+  return LT_OK;
+}
+
+// the host maps of a batch into one device buffer, 256-B aligned: bytes_of(k) (0: nothing to upload), set_dev(k, p)
+template <class Bytes, class Ptr, class SetDev>
+int upload_maps(lt_ctx *ctx, hipStream_t st, int n_maps, Bytes bytes_of, Ptr ptr_of, SetDev set_dev) {
+  size_t total = 0;
+  for (int k = 0; k < n_maps; ++k) total += (bytes_of(k) + 255) & ~(size_t)255;
+  if (!total) return LT_OK;
+  ENSURE(ctx, ctx->d_ft_maps, total);
+  size_t at = 0;
+  for (int k = 0; k < n_maps; ++k) {
+    const size_t b = bytes_of(k);
+    if (!b) continue;
+    char *dst = ctx->d_ft_maps.as<char>() + at;
+    HIPCHK(ctx, hipMemcpyAsync(dst, ptr_of(k), b, hipMemcpyHostToDevice, st));
+    set_dev(k, dst);
+    at += (b + 255) & ~(size_t)255;
+  }
+  return LT_OK;
+}
+
+// the outputs of G segments to the host, then the timers (ev: start, maps uploaded, kernel start, kernel end)
+int finish_segs(lt_ctx *ctx, hipStream_t st, const char *out, const OutLayout &L, long long G, double *seg3d,
+                int32_t *status, int32_t *stats, hipEvent_t ev[4], double t_start, int attempts) {
+  if (G) {
+    HIPCHK(ctx, hipMemcpyAsync(seg3d, out + L.seg, 48 * (size_t)G, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(status, out + L.status, 4 * (size_t)G, hipMemcpyDeviceToHost, st));
+    if (stats) HIPCHK(ctx, hipMemcpyAsync(stats, out + L.stats, 20 * (size_t)G, hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  float up_ms = 0.f, k_ms = 0.f;
+  (void)hipEventElapsedTime(&up_ms, ev[0], ev[1]);
+  (void)hipEventElapsedTime(&k_ms, ev[2], ev[3]);
+  for (int k = 0; k < 4; ++k) (void)hipEventDestroy(ev[k]);
+  ctx->ft_timers[0] = k_ms;
+  ctx->ft_timers[1] = up_ms;
+  ctx->ft_timers[2] = now_ms() - t_start;
+  ctx->ft_timers[3] = attempts;
+  return LT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -120,7 +167,6 @@ int lt_fit_segs(lt_ctx *ctx, int img_begin, int n_maps, const lt_depth_map *maps
   const long long g0 = ctx->seg_off[(size_t)img_begin], g1 = ctx->seg_off[(size_t)(img_begin + n_maps)];
   const long long G = g1 - g0;
   std::vector<FitImg> imgs((size_t)n_maps);
-  size_t host_bytes = 0;
   for (int k = 0; k < n_maps; ++k) {
     const lt_depth_map &m = maps[k];
     const std::string who = "lt_fit_segs: map of image " + std::to_string(ctx->img_ids[(size_t)(img_begin + k)]) + ": ";
@@ -138,32 +184,20 @@ int lt_fit_segs(lt_ctx *ctx, int img_begin, int n_maps, const lt_depth_map *maps
     f.seg_begin = ctx->seg_off[(size_t)(img_begin + k)] - g0;
     f.seg_end = ctx->seg_off[(size_t)(img_begin + k) + 1] - g0;
     f.pad_ = 0;
-    if (!m.on_device && m.h > 0 && m.w > 0)
-      host_bytes += (((size_t)(m.h - 1) * (size_t)m.row_stride + (size_t)m.w) * (m.dtype ? 8 : 4) + 255) & ~(size_t)255;
   }
-  // segs.astype(int) and Bresenham stay in int64 for coordinates below 2^29 (the reference would enumerate every pixel)
   const double *segs = ctx->h_segs_ptr + 4 * g0;
-  for (long long g = 0; g < 4 * G; ++g)
-    if (!(std::fabs(segs[g]) < 536870912.0))
-      return fail(ctx, LT_ERR_ARGUMENT, "lt_fit_segs: 2D segment coordinate not finite or beyond 2^29");
+  if (int rc = check_segs(ctx, "lt_fit_segs", segs, G)) return rc;
   hipStream_t st = ctx->stream;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // start, maps uploaded, kernel start, kernel end
   for (auto &e : ev) HIPCHK(ctx, hipEventCreate(&e));
   HIPCHK(ctx, hipEventRecord(ev[0], st));
-  if (host_bytes) {
-    ENSURE(ctx, ctx->d_ft_maps, host_bytes);
-    size_t at = 0;
-    for (int k = 0; k < n_maps; ++k) {
-      const lt_depth_map &m = maps[k];
-      if (m.on_device || m.h == 0 || m.w == 0) continue;
-      const size_t b = ((size_t)(m.h - 1) * (size_t)m.row_stride + (size_t)m.w) * (m.dtype ? 8 : 4);
-      char *dst = ctx->d_ft_maps.as<char>() + at;
-      HIPCHK(ctx, hipMemcpyAsync(dst, m.ptr, b, hipMemcpyHostToDevice, st));
-      imgs[(size_t)k].map = dst;
-      at += (b + 255) & ~(size_t)255;
-    }
-  }
+  if (int rc = upload_maps(ctx, st, n_maps, [&](int k) -> size_t {
+        const lt_depth_map &m = maps[k];
+        if (m.on_device || m.h == 0 || m.w == 0) return 0;
+        return ((size_t)(m.h - 1) * (size_t)m.row_stride + (size_t)m.w) * (m.dtype ? 8 : 4);
+      }, [&](int k) { return maps[k].ptr; }, [&](int k, char *p) { imgs[(size_t)k].map = p; }))
+    return rc;
   HIPCHK(ctx, hipEventRecord(ev[1], st));
   const OutLayout L(G, 0);
   ENSURE(ctx, ctx->d_ft_imgs, sizeof(FitImg) * (size_t)std::max(n_maps, 1));
@@ -182,21 +216,82 @@ int lt_fit_segs(lt_ctx *ctx, int img_begin, int n_maps, const lt_depth_map *maps
         (void)hipEventRecord(ev[3], st);
       }, &attempts))
     return rc;
-  if (G) {
-    HIPCHK(ctx, hipMemcpyAsync(seg3d, out + L.seg, 48 * (size_t)G, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(status, out + L.status, 4 * (size_t)G, hipMemcpyDeviceToHost, st));
-    if (stats) HIPCHK(ctx, hipMemcpyAsync(stats, out + L.stats, 20 * (size_t)G, hipMemcpyDeviceToHost, st));
+  return finish_segs(ctx, st, out, L, G, seg3d, status, stats, ev, t_start, attempts);
+}
+
+int lt_fit_scans(lt_ctx *ctx, int img_begin, int n_maps, const lt_scan_map *maps, const double *scan_poses,
+                 const lt_fit_config *cfg, double *seg3d, int32_t *status, int32_t *stats) {
+  if (!ctx->inited) return fail(ctx, LT_ERR_STATE, "lt_fit_scans before lt_init");
+  if (!cfg || !seg3d || !status || (n_maps > 0 && !maps)) return fail(ctx, LT_ERR_ARGUMENT, "lt_fit_scans: null argument");
+  if (img_begin < 0 || n_maps < 0 || img_begin + (long long)n_maps > ctx->n_img)
+    return fail(ctx, LT_ERR_ARGUMENT, "lt_fit_scans: images outside the context");
+  if (int rc = check_cfg(ctx, *cfg)) return rc;
+  const double t_start = now_ms();
+  const long long g0 = ctx->seg_off[(size_t)img_begin], g1 = ctx->seg_off[(size_t)(img_begin + n_maps)];
+  const long long G = g1 - g0;
+  std::vector<ScanImg> imgs((size_t)n_maps);
+  std::vector<size_t> host_bytes((size_t)n_maps, 0);
+  for (int k = 0; k < n_maps; ++k) {
+    const lt_scan_map &m = maps[k];
+    const std::string who = "lt_fit_scans: scan of image " + std::to_string(ctx->img_ids[(size_t)(img_begin + k)]) + ": ";
+    if (m.h < 2 || m.w < 2 || m.h >= (1ll << 31) || m.w >= (1ll << 31)) return fail(ctx, LT_ERR_ARGUMENT, who + "bad size");
+    // the camera's size bounds the samples a segment visits (about 2 sqrt(h^2 + w^2)): int32 counts stay exact
+    if (m.img_h < 2 || m.img_w < 2 || m.img_h > (1ll << 24) || m.img_w > (1ll << 24))
+      return fail(ctx, LT_ERR_ARGUMENT, who + "image size outside [2, 2^24]");
+    if (m.dtype != LT_DEPTH_F32 && m.dtype != LT_DEPTH_F64) return fail(ctx, LT_ERR_ARGUMENT, who + "dtype");
+    if (m.on_device != 0 && m.on_device != 1) return fail(ctx, LT_ERR_ARGUMENT, who + "on_device must be 0 or 1");
+    if (!m.ptr) return fail(ctx, LT_ERR_ARGUMENT, who + "null pointer");
+    if (m.row_stride < 0 || m.pix_stride < 0 || m.chan_stride < 0 || m.row_stride >= (1ll << 40) ||
+        m.pix_stride >= (1ll << 40) || m.chan_stride >= (1ll << 40))
+      return fail(ctx, LT_ERR_ARGUMENT, who + "strides outside [0, 2^40)");
+    const double *P = scan_poses ? scan_poses + 12 * (size_t)k : nullptr;
+    if (P)
+      for (int e = 0; e < 12; ++e)
+        if (!std::isfinite(P[e])) return fail(ctx, LT_ERR_ARGUMENT, who + "scan pose not finite");
+    ScanImg &f = imgs[(size_t)k];
+    f.map = m.ptr; f.h = m.h; f.w = m.w;
+    f.rs = m.row_stride; f.ps = m.pix_stride; f.cs = m.chan_stride;
+    f.img_h = m.img_h; f.img_w = m.img_w;
+    f.seg_begin = ctx->seg_off[(size_t)(img_begin + k)] - g0;
+    f.seg_end = ctx->seg_off[(size_t)(img_begin + k) + 1] - g0;
+    for (int e = 0; e < 12; ++e) f.pose[e] = P ? P[e] : 0.0;
+    f.dtype = m.dtype;
+    f.img_id = ctx->img_ids[(size_t)(img_begin + k)];
+    f.cam = img_begin + k;
+    f.use_pose = P ? 1 : 0;
+    if (!m.on_device)  // one past the last element read
+      host_bytes[(size_t)k] = (size_t)((m.h - 1) * m.row_stride + (m.w - 1) * m.pix_stride + 2 * m.chan_stride + 1) *
+                              (m.dtype ? 8 : 4);
   }
-  HIPCHK(ctx, hipStreamSynchronize(st));
-  float up_ms = 0.f, k_ms = 0.f;
-  (void)hipEventElapsedTime(&up_ms, ev[0], ev[1]);
-  (void)hipEventElapsedTime(&k_ms, ev[2], ev[3]);
-  for (auto &e : ev) (void)hipEventDestroy(e);
-  ctx->ft_timers[0] = k_ms;
-  ctx->ft_timers[1] = up_ms;
-  ctx->ft_timers[2] = now_ms() - t_start;
-  ctx->ft_timers[3] = attempts;
-  return LT_OK;
+  const double *segs = ctx->h_segs_ptr + 4 * g0;
+  if (int rc = check_segs(ctx, "lt_fit_scans", segs, G)) return rc;
+  hipStream_t st = ctx->stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  for (auto &e : ev) HIPCHK(ctx, hipEventCreate(&e));
+  HIPCHK(ctx, hipEventRecord(ev[0], st));
+  if (int rc = upload_maps(ctx, st, n_maps, [&](int k) { return host_bytes[(size_t)k]; },
+                           [&](int k) { return maps[k].ptr; }, [&](int k, char *p) { imgs[(size_t)k].map = p; }))
+    return rc;
+  HIPCHK(ctx, hipEventRecord(ev[1], st));
+  const OutLayout L(G, 0);
+  ENSURE(ctx, ctx->d_ft_imgs, sizeof(ScanImg) * (size_t)std::max(n_maps, 1));
+  ENSURE(ctx, ctx->d_ft_in, 32 * (size_t)std::max<long long>(G, 1));
+  ENSURE(ctx, ctx->d_ft_out, L.bytes);
+  if (n_maps) HIPCHK(ctx, hipMemcpyAsync(ctx->d_ft_imgs.p, imgs.data(), sizeof(ScanImg) * (size_t)n_maps, hipMemcpyHostToDevice, st));
+  if (G) HIPCHK(ctx, hipMemcpyAsync(ctx->d_ft_in.p, segs, 32 * (size_t)G, hipMemcpyHostToDevice, st));
+  const FitCfg fc = dev_cfg(*cfg);
+  char *out = ctx->d_ft_out.as<char>();
+  int attempts = 0;
+  if (int rc = run_with_scratch(ctx, st, [&](double *scr, unsigned long long cap, unsigned long long *cnt) {
+        (void)hipEventRecord(ev[2], st);
+        launch_fit_scan(st, G, n_maps, ctx->d_ft_imgs.as<ScanImg>(), ctx->d_ft_in.as<double>(), ctx->d_cams.as<Cam>(),
+                        fc, scr, cap, cnt, reinterpret_cast<double *>(out + L.seg),
+                        reinterpret_cast<int *>(out + L.status), reinterpret_cast<int *>(out + L.stats));
+        (void)hipEventRecord(ev[3], st);
+      }, &attempts))
+    return rc;
+  return finish_segs(ctx, st, out, L, G, seg3d, status, stats, ev, t_start, attempts);
 }
 
 int lt_fit_points(lt_ctx *ctx, int64_t n_sets, const int64_t *off, const double *xyz, const lt_fit_config *cfg,

@@ -29,9 +29,25 @@ struct FitImg {  // one image of a depth batch
   int pad_;
 };
 
+struct ScanImg {  // one image of a scan batch (estimate_seg3d_from_points3d)
+  const void *map;
+  long long h, w;          // the scan's rows and columns
+  long long rs, ps, cs;    // row, pixel and channel strides in elements
+  long long img_h, img_w;  // the camera's image size (the keep filter, the uncertainty)
+  long long seg_begin, seg_end;
+  double pose[12];  // Tr[:3, :4] row-major when use_pose
+  int dtype;        // 0 float32, 1 float64
+  int img_id;
+  int cam;
+  int use_pose;
+};
+
 void launch_fit_depth(hipStream_t st, long long n_segs, int n_img, const FitImg *imgs, const double *segs,
                       const Cam *cams, const FitCfg &cfg, double *scratch, unsigned long long scratch_cap,
                       unsigned long long *scratch_cnt, double *seg3d, int *status, int *stats);
+void launch_fit_scan(hipStream_t st, long long n_segs, int n_img, const ScanImg *imgs, const double *segs,
+                     const Cam *cams, const FitCfg &cfg, double *scratch, unsigned long long scratch_cap,
+                     unsigned long long *scratch_cnt, double *seg3d, int *status, int *stats);
 void launch_fit_points(hipStream_t st, long long n_sets, const long long *off, const double *xyz, const FitCfg &cfg,
                        double *scratch, unsigned long long scratch_cap, unsigned long long *scratch_cnt, double *seg3d,
                        int *status, int *stats, unsigned char *mask);

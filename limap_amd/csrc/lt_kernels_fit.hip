@@ -573,6 +573,215 @@ __global__ __launch_bounds__(64) void k_fit_points(const long long *__restrict__
     for (int k = lane_id(); k < cnt; k += 64) mask[p0 + S.la[k]] = 1;
 }
 
+
+// ---- estimate_seg3d_from_points3d (fitting/fitting.py:56-102) -------------------------------------------------------
+// the store of a scan problem: the points, the two index lists and the ray depths (40 B a point; the scratch counts
+// 32-B units, so a slice takes need + ceil(need / 4) of them)
+__device__ bool take_scan_store(int need, double *s_x, double *s_y, double *s_z, int *s_a, int *s_b, double *s_r,
+                                double *scratch, unsigned long long cap, unsigned long long *cnt, Store &S, double *&rd) {
+  if (need <= kFitLds) {
+    S.x = s_x; S.y = s_y; S.z = s_z; S.la = s_a; S.lb = s_b;
+    rd = s_r;
+    return true;
+  }
+  const unsigned long long units = (unsigned long long)need + (unsigned long long)((need + 3) / 4);
+  unsigned long long base = 0;
+  if (lane_id() == 0) base = atomicAdd(cnt, units);
+  base = __shfl(base, 0, 64);
+  if (base + units > cap) return false;
+  double *p = scratch + 4ull * base;
+  S.x = p; S.y = p + need; S.z = p + 2 * (size_t)need;
+  rd = p + 3 * (size_t)need;
+  S.la = reinterpret_cast<int *>(p + 4 * (size_t)need);
+  S.lb = S.la + need;
+  return true;
+}
+
+// one corner of the scan: the three channels widened to double, 0 outside (grid_sample's zero padding)
+__device__ __forceinline__ void scan_px(const ScanImg &im, long long ix, long long iy, double v[3]) {
+  if (ix < 0 || iy < 0 || ix >= im.w || iy >= im.h) {
+    v[0] = 0.0; v[1] = 0.0; v[2] = 0.0;
+    return;
+  }
+  const long long at = iy * im.rs + ix * im.ps;
+  if (im.dtype == 0) {
+    const float *b = reinterpret_cast<const float *>(im.map) + at;
+    v[0] = (double)b[0]; v[1] = (double)b[im.cs]; v[2] = (double)b[2 * im.cs];
+  } else {
+    const double *b = reinterpret_cast<const double *>(im.map) + at;
+    v[0] = b[0]; v[1] = b[im.cs]; v[2] = b[2 * im.cs];
+  }
+}
+
+// the index range [lo, hi] of np.linspace(start, stop, num) samples that can lie inside 0 < c < lim for both
+// coordinates: the exact per-sample filter follows, so the range only has to be conservative (the sample error, a few
+// ulps of |start| + |delta|, is covered 1000 times over by the margin in index units)
+__device__ void scan_walk(const double s[4], long long num, double lim_x, double lim_y, long long &lo, long long &hi) {
+  lo = 0; hi = num - 1;
+  if (num <= 1) return;
+  const double div = (double)(num - 1);
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const double s0 = s[c], d = s[2 + c] - s[c], lim = c == 0 ? lim_x : lim_y;
+    const double step = d / div;
+    if (d == 0.0) {
+      if (!(0.0 < s0 && s0 < lim)) { lo = 1; hi = 0; }
+      continue;
+    }
+    if (step == 0.0) continue;
+    const double ta = (0.0 - s0) / step, tb = (lim - s0) / step;
+    const double m = 2.0 + 1e-12 * ((fabs(s0) + fabs(d)) + lim) / fabs(step);
+    const double a = (ta < tb ? ta : tb) - m, b = (ta < tb ? tb : ta) + m;
+    if (a > (double)lo) lo = (long long)ceil(a);
+    if (b < (double)hi) hi = (long long)floor(b);
+  }
+}
+
+__global__ __launch_bounds__(64) void k_fit_scan(int n_img, const ScanImg *__restrict__ imgs,
+                                                 const double *__restrict__ segs, const Cam *__restrict__ cams,
+                                                 FitCfg cfg, double *scratch, unsigned long long scratch_cap,
+                                                 unsigned long long *scratch_cnt, double *seg3d, int *status,
+                                                 int *stats) {
+  __shared__ double s_x[kFitLds], s_y[kFitLds], s_z[kFitLds], s_r[kFitLds];
+  __shared__ int s_a[kFitLds], s_b[kFitLds];
+  __shared__ double s_med[2];
+  const long long g = blockIdx.x;
+  int lo = 0, hi = n_img - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (imgs[mid].seg_begin <= g) lo = mid; else hi = mid - 1;
+  }
+  const ScanImg im = imgs[lo];
+  const long long line = g - im.seg_begin;
+  const Cam &cam = cams[im.cam];
+  // num = int(norm(stop - start) * 2), the norm as sqrt(fma(dy, dy, dx * dx)); linspace as NumPy 2.2 evaluates it
+  const double s[4] = {segs[4 * g], segs[4 * g + 1], segs[4 * g + 2], segs[4 * g + 3]};
+  const double dx = s[2] - s[0], dy = s[3] - s[1];
+  const long long num = (long long)(sqrt(fma(dy, dy, dx * dx)) * 2.0);
+  const double div = (double)(num - 1);
+  const double stx = dx / div, sty = dy / div;
+  const bool step0 = stx == 0.0 || sty == 0.0;
+  const double lim_x = (double)(im.img_w - 1), lim_y = (double)(im.img_h - 1);
+  const double sw1 = (double)(im.w - 1), sh1 = (double)(im.h - 1);
+  long long ilo, ihi;
+  scan_walk(s, num, lim_x, lim_y, ilo, ihi);
+  const int need = ihi >= ilo ? (int)(ihi - ilo + 1) : 0;
+  Store S;
+  double *rd;
+  if (!take_scan_store(need, s_x, s_y, s_z, s_a, s_b, s_r, scratch, scratch_cap, scratch_cnt, S, rd)) {
+    if (lane_id() == 0) status[g] = -1;
+    return;
+  }
+  int n = 0;
+  bool oor = false;
+  for (long long b = ilo; b <= ihi; b += 64) {
+    const long long i = b + lane_id();
+    bool keep = false, bad = false;
+    double v[3] = {0.0, 0.0, 0.0};
+    if (i <= ihi) {
+      double px, py;
+      if (num == 1) { px = 0.0 * dx + s[0]; py = 0.0 * dy + s[1]; }
+      else if (i == num - 1) { px = s[2]; py = s[3]; }
+      else if (step0) { px = ((double)i / div) * dx + s[0]; py = ((double)i / div) * dy + s[1]; }
+      else { px = (double)i * stx + s[0]; py = (double)i * sty + s[1]; }
+      if (0.0 < px && 0.0 < py && px < lim_x && py < lim_y) {
+        // interpolate_scan: kp / [W-1, H-1] * 2 - 1 (the scan's W, H), its (-1, 1) assert, then grid_sample with
+        // align_corners: the coordinate goes through the normalise / unnormalise round trip
+        const double gx = (px / sw1) * 2.0 - 1.0, gy = (py / sh1) * 2.0 - 1.0;
+        if (gx > -1.0 && gx < 1.0 && gy > -1.0 && gy < 1.0) {
+          const double ux = ((gx + 1.0) / 2.0) * sw1, uy = ((gy + 1.0) / 2.0) * sh1;
+          const double fx0 = floor(ux), fy0 = floor(uy);
+          const double wx = ux - fx0, wy = uy - fy0;
+          const double ex = 1.0 - wx, ey = 1.0 - wy;
+          const double nw = ey * ex, ne = ey * wx, sw = wy * ex, se = wy * wx;
+          const long long x0 = (long long)fx0, y0 = (long long)fy0;
+          double a[3], bb[3], c[3], d[3];
+          scan_px(im, x0, y0, a); scan_px(im, x0 + 1, y0, bb);
+          scan_px(im, x0, y0 + 1, c); scan_px(im, x0 + 1, y0 + 1, d);
+          bool any = false;
+#pragma unroll
+          for (int k = 0; k < 3; ++k) {
+            v[k] = fma(d[k], se, fma(c[k], sw, fma(bb[k], ne, a[k] * nw)));
+            any = any || isnan(v[k]);
+          }
+          if (any) {  // mode="nearest" (round half to even) for the channels bilinear left NaN
+            double nn[3];
+            scan_px(im, (long long)rint(ux), (long long)rint(uy), nn);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) v[k] = isnan(v[k]) ? nn[k] : v[k];
+          }
+          keep = !isnan(v[0]) && !isnan(v[1]) && !isnan(v[2]);
+        } else {
+          bad = true;
+        }
+      }
+    }
+    oor = oor || __ballot(bad) != 0ull;
+    const unsigned long long mk = __ballot(keep);
+    if (keep) {
+      const int pos = n + __popcll(mk & lanemask_lt());
+      S.x[pos] = v[0]; S.y[pos] = v[1]; S.z[pos] = v[2];
+      rd[pos] = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+    }
+    n += __popcll(mk);
+  }
+  __syncthreads();
+  S.n = n;
+  if (oor || n <= 6) {
+    if (lane_id() == 0) {
+      for (int k = 0; k < 6; ++k) seg3d[6 * g + k] = 0.0;
+      status[g] = oor ? 3 : 1;
+      int *o = stats + 5 * g;
+      o[0] = oor ? 0 : n; o[1] = 0; o[2] = 0; o[3] = 0; o[4] = 0;
+    }
+    return;
+  }
+  // the exact median of the ray depths (no NaN: a kept sample has three non-NaN channels)
+  const int k1 = (n - 1) / 2, k2 = n / 2;
+  for (int i = lane_id(); i < n; i += 64) {
+    const double v = rd[i];
+    int rank = 0;
+    for (int j = 0; j < n; ++j) {
+      const double w = rd[j];
+      rank += (w < v || (w == v && j < i)) ? 1 : 0;
+    }
+    if (rank == k1) s_med[0] = v;
+    if (rank == k2) s_med[1] = v;
+  }
+  __syncthreads();
+  const double med = (n % 2) == 0 ? (s_med[0] + s_med[1]) / 2.0 : s_med[0];
+  const double unc = (cfg.var2d * med) / (0.7 * (double)(im.img_h > im.img_w ? im.img_h : im.img_w));
+  const double th = cfg.ransac_th * unc;
+  if (im.use_pose) {  // Tr[:3, :3] @ p + Tr[:3, 3]
+    const double *T = im.pose;
+    for (int k = lane_id(); k < n; k += 64) {
+      const double X = S.x[k], Y = S.y[k], Z = S.z[k];
+      S.x[k] = ((T[0] * X + T[1] * Y) + T[2] * Z) + T[3];
+      S.y[k] = ((T[4] * X + T[5] * Y) + T[6] * Z) + T[7];
+      S.z[k] = ((T[8] * X + T[9] * Y) + T[10] * Z) + T[11];
+    }
+  } else {  // R^T p - R^T t
+    const double *R = cam.R;
+    const double ct0 = (R[0] * cam.t[0] + R[3] * cam.t[1]) + R[6] * cam.t[2];
+    const double ct1 = (R[1] * cam.t[0] + R[4] * cam.t[1]) + R[7] * cam.t[2];
+    const double ct2 = (R[2] * cam.t[0] + R[5] * cam.t[1]) + R[8] * cam.t[2];
+    for (int k = lane_id(); k < n; k += 64) {
+      const double X = S.x[k], Y = S.y[k], Z = S.z[k];
+      S.x[k] = ((R[0] * X + R[3] * Y) + R[6] * Z) - ct0;
+      S.y[k] = ((R[1] * X + R[4] * Y) + R[7] * Z) - ct1;
+      S.z[k] = ((R[2] * X + R[5] * Y) + R[8] * Z) - ct2;
+    }
+  }
+  __syncthreads();
+  Fit F;
+  F.S = S;
+  F.cfg = cfg;
+  F.t2 = th * th;
+  F.smp.init(cfg.seed, im.img_id, line, 0);
+  F.shf.init(cfg.seed, im.img_id, line, 1);
+  finish(F, seg3d, status, stats, g, n);
+}
+
 }  // namespace
 
 namespace lt {
@@ -589,5 +798,12 @@ void launch_fit_points(hipStream_t st, long long n_sets, const long long *off, c
   if (n_sets <= 0) return;
   hipLaunchKernelGGL(k_fit_points, dim3((unsigned)n_sets), dim3(64), 0, st, off, xyz, cfg, scratch, scratch_cap,
                      scratch_cnt, seg3d, status, stats, mask);
+}
+void launch_fit_scan(hipStream_t st, long long n_segs, int n_img, const ScanImg *imgs, const double *segs,
+                     const Cam *cams, const FitCfg &cfg, double *scratch, unsigned long long scratch_cap,
+                     unsigned long long *scratch_cnt, double *seg3d, int *status, int *stats) {
+  if (n_segs <= 0) return;
+  hipLaunchKernelGGL(k_fit_scan, dim3((unsigned)n_segs), dim3(64), 0, st, n_img, imgs, segs, cams, cfg, scratch,
+                     scratch_cap, scratch_cnt, seg3d, status, stats);
 }
 }  // namespace lt

@@ -3,6 +3,10 @@
     Fit3DPoints, estimate_seg3d, estimate_seg3d_from_depth   (fitting/fitting.py:8-53, fitting/line3d_estimator.cc)
     fit_3d_segs                                              (runners/line_fitnmerge.py:17-70)
     fit_3d_segs_arrays                                       the fast form: (M, 2, 3) per image plus stats
+    estimate_seg3d_from_points3d                             (fitting/fitting.py:56-102), 3D point scans
+    fit_3d_segs_with_points3d                                (runners/line_fitnmerge.py:73-130)
+    fit_3d_segs_with_points3d_arrays                         its fast form
+    tracks_from_fit                                          one track per fitted segment (line_fitnmerge.py:210-221)
 
 Same names, arguments and results.  LO-MSAC runs with the project's counter-based generator: `random_seed_` (or `seed`)
 decides the draws and a segment's result depends on (seed, image id, line index) alone -- not on the batch, the image
@@ -16,7 +20,7 @@ import numpy as np
 from . import _capi
 from .base import Line3d
 
-STATUS_OK, STATUS_TOO_FEW_POINTS, STATUS_LOW_INLIER_RATIO = 0, 1, 2
+STATUS_OK, STATUS_TOO_FEW_POINTS, STATUS_LOW_INLIER_RATIO, STATUS_SCAN_OUT_OF_RANGE = 0, 1, 2, 3
 STATS_FIELDS = ("num_points", "num_inliers", "num_iterations", "number_lo_iterations", "from_lo")  # columns of stats
 
 
@@ -203,18 +207,26 @@ def _shape_of(depth):
     return tuple(int(v) for v in depth.shape)
 
 
+def _view_hw(camview):
+    """(h, w) of a view that knows its image size (limap's CameraView, base.CameraView(..., hw=...)), else None"""
+    if not (hasattr(camview, "h") and hasattr(camview, "w")):
+        return None
+    h, w = camview.h(), camview.w()
+    if h is None or w is None:
+        return None
+    return int(h), int(w)
+
+
 def _read_depth(reader, camview):
     """a reader's map (read_depth(img_hw=[h, w]) when the view knows its size), an array or a tensor"""
+    hw = _view_hw(camview)
     if hasattr(reader, "read_depth"):
-        hw = None
-        if hasattr(camview, "h") and hasattr(camview, "w"):
-            hw = [int(camview.h()), int(camview.w())]
-        d = reader.read_depth(img_hw=hw) if hw is not None else reader.read_depth()
+        d = reader.read_depth(img_hw=list(hw)) if hw is not None else reader.read_depth()
     else:
         d = reader
-    if hasattr(camview, "h") and hasattr(camview, "w"):
-        if _shape_of(d)[:2] != (int(camview.h()), int(camview.w())):
-            raise ValueError(f"fitting: depth map of shape {_shape_of(d)} for a view of {camview.h()} x {camview.w()}")
+    if hw is not None:
+        if _shape_of(d)[:2] != hw:
+            raise ValueError(f"fitting: depth map of shape {_shape_of(d)} for a view of {hw[0]} x {hw[1]}")
     return d
 
 
@@ -236,14 +248,9 @@ def _fitting_args(fitting_config):
     return (fc.get("ransac_th", 0.75), fc.get("min_percentage_inliers", 0.6), fc.get("var2d", 5.0))
 
 
-def fit_3d_segs_arrays(all_2d_segs, imagecols, depths, fitting_config=None, seed=0, max_chunk_bytes=1 << 30,
-                       options=None, device=0):
-    """fit_3d_segs in array form: -> (dict img_id -> (M, 2, 3) float64, dict img_id -> dict(status (M,), stats (M, 5)),
-    timers).  Images go through the device in ascending id order in chunks whose depth maps stay under
-    max_chunk_bytes; the results do not depend on the chunking."""
+def _scene_of(all_2d_segs, imagecols):
+    """the images in ascending id order: ids, (kvec, qvec, tvec) arrays, segment offsets, all segments (G, 4)"""
     from .triangulation import _view_arrays
-    ransac_th, min_pct, var2d = _fitting_args(fitting_config)
-    cfg = _config(options, ransac_th, min_pct, var2d, seed)
     ids = sorted(int(i) for i in imagecols.get_img_ids())
     segs = {}
     k = np.zeros((len(ids), 4)); q = np.zeros((len(ids), 4)); t = np.zeros((len(ids), 3))
@@ -252,11 +259,16 @@ def fit_3d_segs_arrays(all_2d_segs, imagecols, depths, fitting_config=None, seed
         k[n], q[n], t[n] = _view_arrays(imagecols.camview(i))
         segs[i] = _segs4(all_2d_segs[i]) if i in all_2d_segs else np.zeros((0, 4))
         seg_off[n + 1] = seg_off[n] + len(segs[i])
-    G = int(seg_off[-1])
     allsegs = np.ascontiguousarray(np.concatenate([segs[i] for i in ids], 0)) if ids else np.zeros((0, 4))
-    for i in ids:
-        if i not in depths:
-            raise KeyError(f"fitting: no depth map for image {i}")
+    return ids, (k, q, t), seg_off, allsegs
+
+
+def _fit_chunks(ids, cams, seg_off, allsegs, map_of, nbytes_of, launch, max_chunk_bytes, device):
+    """the chunk loop of the per-image fits: map_of(m) -> (map record, keep-alive) for the m-th image, read once;
+    launch(ctx, n, maps, seg, status, stats) fits the images [n, n + len(maps)).  Chunks keep their maps' bytes under
+    max_chunk_bytes (at least one map each); the results do not depend on the chunking.
+    -> (seg (G, 6), status (G,), stats (G, 5), timers)"""
+    G = int(seg_off[-1])
     seg = np.zeros((max(G, 1), 6)); status = np.zeros(max(G, 1), np.int32); stats = np.zeros((max(G, 1), 5), np.int32)
     timers = dict(device_ms=0.0, upload_ms=0.0, host_ms=0.0, attempts=0, chunks=0)
     p = _capi.ptr
@@ -271,9 +283,8 @@ def fit_3d_segs_arrays(all_2d_segs, imagecols, depths, fitting_config=None, seed
             if carry is not None:
                 (dm, ka), carry = carry, None
             else:
-                i = ids[m]
-                dm, ka = _map_of(_read_depth(depths[i], imagecols.camview(i)), device)
-            nbytes = int(dm.h) * int(dm.row_stride) * (4 if dm.dtype == 0 else 8)
+                dm, ka = map_of(m)
+            nbytes = nbytes_of(dm)
             if m > n and used + nbytes > max_chunk_bytes:
                 carry = (dm, ka)
                 break
@@ -281,24 +292,51 @@ def fit_3d_segs_arrays(all_2d_segs, imagecols, depths, fitting_config=None, seed
             m += 1
         if ctx is None:
             ctx = _capi.Context(device=device)
-            ctx.init(ids, k, q, t, seg_off, allsegs)
+            ctx.init(ids, *cams, seg_off, allsegs)
         if on_dev:
             _sync_torch(device)
-        arr = (_capi.LtDepthMap * len(maps))(*maps)
         g0 = int(seg_off[n])
-        ctx.chk(ctx.L.lt_fit_segs(ctx.h, n, len(maps), arr, C.byref(cfg), p(seg[g0:], C.c_double),
-                                  p(status[g0:], C.c_int32), p(stats[g0:], C.c_int32)))
+        launch(ctx, n, maps, seg[g0:], status[g0:], stats[g0:])
         tm = np.zeros(4)
         ctx.chk(ctx.L.lt_fit_get_timers(ctx.h, p(tm, C.c_double)))
         timers["device_ms"] += tm[0]; timers["upload_ms"] += tm[1]; timers["host_ms"] += tm[2]
         timers["attempts"] = max(timers["attempts"], int(tm[3])); timers["chunks"] += 1
         del keep
         n = m
+    return seg, status, stats, timers
+
+
+def _per_image(ids, seg_off, seg, status, stats):
     out, info = {}, {}
     for j, i in enumerate(ids):
         a, b = int(seg_off[j]), int(seg_off[j + 1])
         out[i] = seg[a:b].reshape(b - a, 2, 3).copy()
         info[i] = dict(status=status[a:b].copy(), stats=stats[a:b].copy())
+    return out, info
+
+
+def fit_3d_segs_arrays(all_2d_segs, imagecols, depths, fitting_config=None, seed=0, max_chunk_bytes=1 << 30,
+                       options=None, device=0):
+    """fit_3d_segs in array form: -> (dict img_id -> (M, 2, 3) float64, dict img_id -> dict(status (M,), stats (M, 5)),
+    timers).  Images go through the device in ascending id order in chunks whose depth maps stay under
+    max_chunk_bytes; the results do not depend on the chunking."""
+    ransac_th, min_pct, var2d = _fitting_args(fitting_config)
+    cfg = _config(options, ransac_th, min_pct, var2d, seed)
+    ids, cams, seg_off, allsegs = _scene_of(all_2d_segs, imagecols)
+    for i in ids:
+        if i not in depths:
+            raise KeyError(f"fitting: no depth map for image {i}")
+    p = _capi.ptr
+
+    def launch(ctx, n, maps, seg, status, stats):
+        arr = (_capi.LtDepthMap * len(maps))(*maps)
+        ctx.chk(ctx.L.lt_fit_segs(ctx.h, n, len(maps), arr, C.byref(cfg), p(seg, C.c_double), p(status, C.c_int32),
+                                  p(stats, C.c_int32)))
+
+    seg, status, stats, timers = _fit_chunks(
+        ids, cams, seg_off, allsegs, lambda m: _map_of(_read_depth(depths[ids[m]], imagecols.camview(ids[m])), device),
+        lambda dm: int(dm.h) * int(dm.row_stride) * (4 if dm.dtype == 0 else 8), launch, max_chunk_bytes, device)
+    out, info = _per_image(ids, seg_off, seg, status, stats)
     return out, info, timers
 
 
@@ -319,3 +357,156 @@ def estimate_seg3d_from_depth(seg2d, depth, camview, ransac_th=0.75, min_percent
     if info[0]["status"][0] != STATUS_OK:
         return None
     return arrs[0][0, 0].copy(), arrs[0][0, 1].copy()
+
+
+# ---- 3D point scans -------------------------------------------------------------------------------------------------
+def _scan_of(p3ds, img_hw, device=0):
+    """(LtScanMap, keep-alive) of an (H, W, 3) NumPy array or torch tensor (a reader's read_p3ds()), img_hw the camera's
+    (h, w).  float32 and float64 only (the reference's grid_sample takes float64; float32 is widened exactly); any
+    non-negative strides are read in place.  A GPU tensor must live on `device` (see _map_of)."""
+    if _is_torch(p3ds):
+        import torch
+        if p3ds.dim() != 3 or p3ds.shape[2] != 3:
+            raise ValueError(f"fitting: a scan must be (H, W, 3), got shape {tuple(p3ds.shape)}")
+        if p3ds.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"fitting: scans must be float32 or float64, got {p3ds.dtype}")
+        if p3ds.is_cuda and p3ds.device.index != device:
+            raise ValueError(f"fitting: a scan on {p3ds.device} for a fit on cuda:{device}")
+        if not p3ds.is_cuda:
+            return _scan_of(p3ds.numpy(), img_hw, device)
+        if p3ds.shape[0] < 2 or p3ds.shape[1] < 2:
+            raise ValueError(f"fitting: a scan needs at least 2 x 2 pixels, got shape {tuple(p3ds.shape)}")
+        st = p3ds.stride()
+        sm = _capi.LtScanMap(C.c_void_p(p3ds.data_ptr()), p3ds.shape[0], p3ds.shape[1], st[0], st[1], st[2],
+                             img_hw[0], img_hw[1], 0 if p3ds.dtype == torch.float32 else 1, 1)
+        return sm, p3ds
+    a = np.asarray(p3ds)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"fitting: a scan must be (H, W, 3), got shape {a.shape}")
+    if a.dtype not in (np.float32, np.float64):
+        raise ValueError(f"fitting: scans must be float32 or float64, got {a.dtype}")
+    if a.shape[0] < 2 or a.shape[1] < 2:
+        raise ValueError(f"fitting: a scan needs at least 2 x 2 pixels, got shape {a.shape}")
+    if any(s < 0 or s % a.itemsize for s in a.strides):
+        a = np.ascontiguousarray(a)
+    rs, ps, cs = (s // a.itemsize for s in a.strides)
+    sm = _capi.LtScanMap(C.c_void_p(a.ctypes.data), a.shape[0], a.shape[1], rs, ps, cs, img_hw[0], img_hw[1],
+                         0 if a.dtype == np.float32 else 1, 0)
+    return sm, a
+
+
+def _scan_nbytes(sm):
+    return int(sm.h) * int(sm.w) * 3 * (4 if sm.dtype == 0 else 8)
+
+
+def _view_size(camview, img_id):
+    hw = _view_hw(camview)
+    if hw is None:
+        raise ValueError(f"fitting: the view of image {img_id} has no image size (camview.h(), camview.w()); "
+                         "base.CameraView takes it as hw=(h, w)")
+    if hw[0] < 2 or hw[1] < 2 or hw[0] > 2**24 or hw[1] > 2**24:
+        raise ValueError(f"fitting: image {img_id} of {hw[0]} x {hw[1]}: sizes must lie in [2, 2^24]")
+    return hw
+
+
+def _read_p3ds(reader):
+    return reader.read_p3ds() if hasattr(reader, "read_p3ds") else reader
+
+
+def _pose_rows(T, img_id):
+    """Tr[:3, :4] of a 4 x 4 (or 3 x 4) scan pose, row-major, finite"""
+    a = np.asarray(T, np.float64)
+    if a.shape not in ((4, 4), (3, 4)):
+        raise ValueError(f"fitting: the scan pose of image {img_id} must be 4 x 4 or 3 x 4, got {a.shape}")
+    a = np.ascontiguousarray(a[:3, :4]).reshape(12)
+    if not np.isfinite(a).all():
+        raise ValueError(f"fitting: the scan pose of image {img_id} is not finite")
+    return a
+
+
+def fit_3d_segs_with_points3d_arrays(all_2d_segs, imagecols, p3d_reader, fitting_config=None, inloc_dataset=None,
+                                     seed=0, max_chunk_bytes=1 << 30, scan_poses=None, options=None, device=0):
+    """fit_3d_segs_with_points3d in array form: -> (dict img_id -> (M, 2, 3) float64, dict img_id -> dict(status (M,),
+    stats (M, 5)), timers), like fit_3d_segs_arrays.  p3d_reader: img_id -> reader with read_p3ds(), or the (H, W, 3)
+    scan itself (NumPy array or torch tensor).  inloc_dataset: the points go through hloc's
+    get_scan_pose(inloc_dataset, image_name) instead of the camera (ImportError without hloc, as in the reference);
+    scan_poses (img_id -> 4 x 4) gives the same transforms without hloc.  A sample outside hloc's (-1, 1) range (a scan
+    smaller than the image) raises ValueError naming the image and the line."""
+    if inloc_dataset is not None and scan_poses is not None:
+        raise ValueError("fitting: give inloc_dataset or scan_poses, not both")
+    ransac_th, min_pct, var2d = _fitting_args(fitting_config)
+    cfg = _config(options, ransac_th, min_pct, var2d, seed)
+    ids, cams, seg_off, allsegs = _scene_of(all_2d_segs, imagecols)
+    sizes = [_view_size(imagecols.camview(i), i) for i in ids]
+    for i in ids:
+        if i not in p3d_reader:
+            raise KeyError(f"fitting: no 3D points for image {i}")
+    if inloc_dataset is not None:
+        from hloc.localize_inloc import get_scan_pose
+        scan_poses = {i: get_scan_pose(inloc_dataset, imagecols.image_name(i)) for i in ids}
+    poses = None
+    if scan_poses is not None:
+        for i in ids:
+            if i not in scan_poses:
+                raise KeyError(f"fitting: no scan pose for image {i}")
+        poses = np.ascontiguousarray(np.stack([_pose_rows(scan_poses[i], i) for i in ids])) if ids else None
+    p = _capi.ptr
+
+    def launch(ctx, n, maps, seg, status, stats):
+        arr = (_capi.LtScanMap * len(maps))(*maps)
+        pp = p(poses[n:], C.c_double) if poses is not None else None
+        ctx.chk(ctx.L.lt_fit_scans(ctx.h, n, len(maps), arr, pp, C.byref(cfg), p(seg, C.c_double),
+                                   p(status, C.c_int32), p(stats, C.c_int32)))
+
+    seg, status, stats, timers = _fit_chunks(
+        ids, cams, seg_off, allsegs, lambda m: _scan_of(_read_p3ds(p3d_reader[ids[m]]), sizes[m], device),
+        _scan_nbytes, launch, max_chunk_bytes, device)
+    bad = np.nonzero(status[:int(seg_off[-1])] == STATUS_SCAN_OUT_OF_RANGE)[0]
+    if len(bad):
+        j = int(np.searchsorted(seg_off, bad[0], side="right")) - 1
+        raise ValueError(f"fitting: image {ids[j]} line {int(bad[0] - seg_off[j])}: a sample falls outside the scan "
+                         "(interpolate_scan's -1 < kp < 1 assertion)")
+    out, info = _per_image(ids, seg_off, seg, status, stats)
+    return out, info, timers
+
+
+def fit_3d_segs_with_points3d(all_2d_segs, imagecols, p3d_reader, fitting_config, inloc_dataset=None, seed=0,
+                              max_chunk_bytes=1 << 30, scan_poses=None):
+    """runners/line_fitnmerge.py:73-130: dict img_id -> list of (start, end) float64 (3,) arrays, zeros where the fit
+    fails.  fitting_config["n_jobs"] is accepted and ignored."""
+    arrs, _, _ = fit_3d_segs_with_points3d_arrays(all_2d_segs, imagecols, p3d_reader, fitting_config, inloc_dataset,
+                                                  seed, max_chunk_bytes, scan_poses)
+    return {i: [(a[0].copy(), a[1].copy()) for a in arrs[i]] for i in arrs}
+
+
+def estimate_seg3d_from_points3d(seg2d, p3ds, camview, image_name, inloc_dataset=None, ransac_th=0.75,
+                                 min_percentage_inliers=0.6, var2d=5.0, seed=0):
+    """fitting.py:56-102 for one segment: None or (start, end).  camview must know its image size."""
+    from .base import ImageCollection
+    poses = None
+    if inloc_dataset is not None:
+        from hloc.localize_inloc import get_scan_pose
+        poses = {0: get_scan_pose(inloc_dataset, image_name)}
+    arrs, info, _ = fit_3d_segs_with_points3d_arrays(
+        {0: np.asarray(seg2d, np.float64).reshape(1, -1)}, ImageCollection({0: camview}), {0: p3ds},
+        dict(ransac_th=ransac_th, min_percentage_inliers=min_percentage_inliers, var2d=var2d), seed=seed,
+        scan_poses=poses)
+    if info[0]["status"][0] != STATUS_OK:
+        return None
+    return arrs[0][0, 0].copy(), arrs[0][0, 1].copy()
+
+
+def tracks_from_fit(all_2d_segs, seg3d_list):
+    """one LineTrack per 2D segment whose fitted 3D segment has a length > 0, in all_2d_segs' image order and line
+    order (runners/line_fitnmerge.py:210-221 and :392-402); seg3d_list[img_id][line_id] is (start, end) or (2, 3)"""
+    from .base import Line2d, Line3d, LineTrack
+    tracks = []
+    for img_id in all_2d_segs:
+        for line_id, seg2d in enumerate(all_2d_segs[img_id]):
+            seg3d = seg3d_list[img_id][line_id]
+            l3d = Line3d(seg3d[0], seg3d[1])
+            l2d = Line2d(seg2d[0:2], seg2d[2:4])
+            if l3d.length() == 0:
+                continue
+            tracks.append(LineTrack(l3d, [img_id], [line_id], [l2d]))
+    return tracks

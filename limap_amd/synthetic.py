@@ -459,10 +459,30 @@ def render_depths(scene, h=H_IMG, w=W_IMG, noise=0.0, hole_frac=0.0, outlier_fra
     return out
 
 
-def imagecols_of(scene):
-    """limap_amd.base.ImageCollection of a scene's cameras."""
+def render_scans(scene, h=H_IMG, w=W_IMG, noise=0.0, hole_frac=0.0, dtype=np.float64, seed=0):
+    """3D point scans of the box rooms for h x w images (the cameras of resize_scene(scene, h, w)): img_id -> (h, w, 3)
+    array of `dtype`, the camera-frame XYZ ((x - cx) / fx * z, (y - cy) / fy * z, z) of render_depths' z-depths at the
+    integer pixel (x, y).  noise: relative N(0, noise) depth error; hole_frac: pixels whose three channels are NaN, like
+    the holes of InLoc's XYZcut scans."""
+    sc = resize_scene(scene, h, w)
+    depths = render_depths(scene, h, w, noise=noise, dtype=np.float64, seed=seed)
+    xs, ys = np.meshgrid(np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64))
+    out = {}
+    for n, img_id in enumerate(sc.img_ids):
+        rng = np.random.default_rng([seed, 778, int(img_id)])
+        fx, fy, cx, cy = sc.kvec[n]
+        z = depths[int(img_id)]
+        xyz = np.stack([(xs - cx) / fx * z, (ys - cy) / fy * z, z], -1)
+        if hole_frac > 0:
+            xyz[rng.uniform(size=z.shape) < hole_frac] = np.nan
+        out[int(img_id)] = xyz.astype(dtype)
+    return out
+
+
+def imagecols_of(scene, hw=None):
+    """limap_amd.base.ImageCollection of a scene's cameras; hw = (h, w): the image size every view carries."""
     from .base import ImageCollection
-    return ImageCollection.from_arrays(scene.img_ids, scene.kvec, scene.qvec, scene.tvec)
+    return ImageCollection.from_arrays(scene.img_ids, scene.kvec, scene.qvec, scene.tvec, hw=hw)
 
 
 def default_merging_cfg(var2d=5.0):
