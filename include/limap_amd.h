@@ -387,6 +387,42 @@ int lt_fit_scans(lt_ctx *ctx, int img_begin, int n_maps, const lt_scan_map *maps
  * overflowed) */
 int lt_fit_get_timers(lt_ctx *ctx, double out[4]);
 
+/* ---- limap.evaluation (evaluation/point_cloud_evaluator.cc, base_evaluator.cc, refline_evaluator.cc) on the GPU.
+ * Lines are 6 doubles (start, end).  Distances are the reference's expressions bit for bit.
+ * Inputs must be finite (LT_ERR_ARGUMENT otherwise).  chunk: queries (or cloud points) per launch, 0 = default.
+ *
+ * A point index on the context's device: the cloud in Morton order, buckets of 32 points, an implicit hierarchy of
+ * bounding boxes.  xyz: n x 3 points, dtype 0 float32 (widened exactly) or 1 float64, on the host or (on_device) a
+ * device pointer of the context's device.  perm (may be NULL): the order of a saved index (lt_pcd_get_perm), which
+ * skips the sort; the points must be the ones it was saved with. */
+typedef struct lt_pcd lt_pcd;
+int lt_pcd_build(lt_ctx *ctx, const void *xyz, int64_t n, int dtype, int on_device, const uint32_t *perm,
+                 lt_pcd **out);
+void lt_pcd_free(lt_pcd *pcd);
+/* the index order: perm[k] = input index of the k-th point in Morton order */
+int lt_pcd_get_perm(lt_ctx *ctx, const lt_pcd *pcd, uint32_t *perm);
+/* ComputeDistPoint over n query points (n x 3): the exact distance to the nearest cloud point */
+int lt_pcd_nearest_dists(lt_ctx *ctx, const lt_pcd *pcd, const double *query, int64_t n, int64_t chunk,
+                         double *dist);
+#define LT_SAMPLE_CENTER 0 /* start + ((i + 0.5) / n) (end - start): ComputeInlierRatio, Compute*Segs */
+#define LT_SAMPLE_ENDS 1   /* start + (i / (n - 1)) (end - start): ComputeDistLine (n >= 2) */
+/* n_samples samples of each line against the cloud: dists (may be NULL) n_lines x n_samples nearest distances;
+ * counts (may be NULL) n_lines x n_th samples with distance <= thresholds[t] (n_th <= 64) */
+int lt_pcd_line_samples(lt_ctx *ctx, const lt_pcd *pcd, const double *lines, int64_t n_lines, int mode,
+                        int n_samples, const double *thresholds, int n_th, int64_t chunk, double *dists,
+                        int32_t *counts);
+/* ComputeDistsforEachPoint: per cloud point (input order) the minimum of Line3d::point_distance over the lines,
+ * DBL_MAX when there are none */
+int lt_lines_point_dists(lt_ctx *ctx, const lt_pcd *pcd, const double *lines, int64_t n_lines, int64_t chunk,
+                         double *dist);
+/* RefLineEvaluator::ComputeRecallLength's counters: counts[r * n_th + t] = samples i < n_samples of query line r
+ * (start + (length / (n - 1) * i) * direction) whose DistPointLines to `lines` is < thresholds[t] */
+int lt_refline_counts(lt_ctx *ctx, const double *query_lines, int64_t n_query, const double *lines, int64_t n_lines,
+                      int n_samples, const double *thresholds, int n_th, int64_t chunk, int32_t *counts);
+/* of the last evaluation call: [0] device ms of its kernels (HIP events), [1] host ms of the call, [2] launches,
+ * [3] index levels (lt_pcd_build) */
+int lt_eval_get_timers(lt_ctx *ctx, double out[4]);
+
 /* Counters of the last device run: [0] connections tested, [1] candidates, [2] ordered candidate
  * pairs swept by the scoring kernel (sum n_tris^2), [3] valid edges, [4] graph nodes,
  * [5] graph edges, [6] tracks, [7] nodes. */

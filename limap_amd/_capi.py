@@ -31,6 +31,8 @@ EXPORTED_SYMBOLS = [
     "lt_fn_triangulate_line", "lt_fn_aggregate_line3d_list", "lt_fn_pack_match_rows",
     "lt_fn_compressed_block_words", "lt_fn_pack_match_rows_compressed",
     "lt_fit_config_default", "lt_fit_segs", "lt_fit_scans", "lt_fit_points", "lt_fit_get_timers",
+    "lt_pcd_build", "lt_pcd_free", "lt_pcd_get_perm", "lt_pcd_nearest_dists", "lt_pcd_line_samples",
+    "lt_lines_point_dists", "lt_refline_counts", "lt_eval_get_timers",
 ]
 
 
@@ -231,6 +233,15 @@ def load_library():
     L.lt_fit_scans.argtypes = [vp, C.c_int, C.c_int, C.POINTER(LtScanMap), dp, C.POINTER(LtFitConfig), dp, i32p, i32p]
     L.lt_fit_points.argtypes = [vp, C.c_int64, i64p, dp, C.POINTER(LtFitConfig), dp, i32p, i32p, u8p]
     L.lt_fit_get_timers.argtypes = [vp, dp]
+    L.lt_pcd_build.argtypes = [vp, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.POINTER(vp)]
+    L.lt_pcd_free.argtypes = [vp]
+    L.lt_pcd_free.restype = None
+    L.lt_pcd_get_perm.argtypes = [vp, vp, C.c_void_p]
+    L.lt_pcd_nearest_dists.argtypes = [vp, vp, dp, C.c_int64, C.c_int64, dp]
+    L.lt_pcd_line_samples.argtypes = [vp, vp, dp, C.c_int64, C.c_int, C.c_int, dp, C.c_int, C.c_int64, dp, i32p]
+    L.lt_lines_point_dists.argtypes = [vp, vp, dp, C.c_int64, C.c_int64, dp]
+    L.lt_refline_counts.argtypes = [vp, dp, C.c_int64, dp, C.c_int64, C.c_int, dp, C.c_int, C.c_int64, i32p]
+    L.lt_eval_get_timers.argtypes = [vp, dp]
     _lib = L
     return L
 

@@ -398,6 +398,9 @@ struct lt_ctx {
   // ---- line fitting (lt_fit.cpp) ----
   double ft_timers[4] = {0, 0, 0, 0};  // lt_fit_get_timers
   DevBuf d_ft_maps, d_ft_imgs, d_ft_in, d_ft_out, d_ft_scr;
+  // ---- line-map evaluation (lt_eval.cpp) ----
+  double ev_timers[4] = {0, 0, 0, 0};  // lt_eval_get_timers
+  DevBuf d_ev_in, d_ev_lines, d_ev_th, d_ev_out, d_ev_cnt;
 };
 
 #define HIPCHK(ctx, call)                                                                  \

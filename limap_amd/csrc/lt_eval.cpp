@@ -1,0 +1,390 @@
+// lt_eval.cpp -- limap.evaluation on the GPU (evaluation/point_cloud_evaluator.cc, base_evaluator.cc,
+// refline_evaluator.cc): the point index (lt_pcd_build), nearest-point distances of free points and of line samples
+// (lt_pcd_nearest_dists, lt_pcd_line_samples), the point-to-segment minima of ComputeDistsforEachPoint
+// (lt_lines_point_dists) and the counters of RefLineEvaluator (lt_refline_counts).  The host validates, prepares the
+// per-line constants (direction, length: the sqrt and divisions of Line3d, once per line) and launches in chunks; every
+// distance is computed on the device (lt_kernels_eval.hip).  DESIGN §14.
+
+#include "lt_host.h"
+#include "lt_eval.h"
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+using namespace lt;
+using lt_impl::now_ms;
+
+struct lt_pcd {
+  int device = 0;
+  long long n = 0;
+  DevBuf x, y, z, box, perm;
+  EvalTree tree{};
+};
+
+namespace {
+
+constexpr long long kDefaultChunk = 1ll << 22;
+
+long long chunk_of(int64_t chunk) { return chunk > 0 ? (long long)chunk : kDefaultChunk; }
+
+int check_finite(lt_ctx *ctx, const char *who, const double *v, long long n, const char *what) {
+  for (long long k = 0; k < n; ++k)
+    if (!std::isfinite(v[k])) return fail(ctx, LT_ERR_ARGUMENT, std::string(who) + ": non-finite " + what);
+  return LT_OK;
+}
+
+// Line3d's direction() (Eigen normalized(): unchanged unless the squared norm is > 0) and length() ((start - end).norm())
+std::vector<EvalLine> prep_lines(const double *l6, long long n, int rint_n) {
+  std::vector<EvalLine> out((size_t)std::max<long long>(n, 1));
+  for (long long k = 0; k < n; ++k) {
+    const double *a = l6 + 6 * k;
+    EvalLine &L = out[(size_t)k];
+    double v[3], w[3];
+    for (int c = 0; c < 3; ++c) {
+      L.s[c] = a[c];
+      L.e[c] = a[3 + c];
+      v[c] = a[3 + c] - a[c];
+      w[c] = a[c] - a[3 + c];
+    }
+    const double z = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
+    if (z > 0.0) {
+      const double nv = std::sqrt(z);
+      for (int c = 0; c < 3; ++c) L.d[c] = v[c] / nv;
+    } else {
+      for (int c = 0; c < 3; ++c) L.d[c] = v[c];
+    }
+    L.len = std::sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]);
+    L.rint = rint_n > 0 ? L.len / (double)(rint_n - 1) : 0.0;  // ComputeRecallLength: length() / (num_samples - 1)
+    L.pad_ = 0.0;
+  }
+  return out;
+}
+
+int upload_lines(lt_ctx *ctx, DevBuf &buf, const std::vector<EvalLine> &v) {
+  ENSURE(ctx, buf, sizeof(EvalLine) * v.size());
+  HIPCHK(ctx, hipMemcpyAsync(buf.p, v.data(), sizeof(EvalLine) * v.size(), hipMemcpyHostToDevice, ctx->stream));
+  return LT_OK;
+}
+
+int check_pcd(lt_ctx *ctx, const char *who, const lt_pcd *pcd) {
+  if (!pcd) return fail(ctx, LT_ERR_ARGUMENT, std::string(who) + ": null index");
+  if (pcd->device != ctx->device)
+    return fail(ctx, LT_ERR_ARGUMENT, std::string(who) + ": the index lives on another device than the context");
+  return LT_OK;
+}
+
+struct Timer {  // HIP events around the kernels of one call
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  double t0 = now_ms();
+  int launches = 0;
+  ~Timer() {
+    for (auto &e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  int start(lt_ctx *ctx) {
+    for (auto &e : ev) HIPCHK(ctx, hipEventCreate(&e));
+    HIPCHK(ctx, hipEventRecord(ev[0], ctx->stream));
+    return LT_OK;
+  }
+  int finish(lt_ctx *ctx, double levels) {
+    HIPCHK(ctx, hipEventRecord(ev[1], ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipGetLastError());
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
+    ctx->ev_timers[0] = ms;
+    ctx->ev_timers[1] = now_ms() - t0;
+    ctx->ev_timers[2] = launches;
+    ctx->ev_timers[3] = levels;
+    return LT_OK;
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+int lt_pcd_build(lt_ctx *ctx, const void *xyz, int64_t n, int dtype, int on_device, const uint32_t *perm,
+                 lt_pcd **out) {
+  if (!ctx || !out) return LT_ERR_ARGUMENT;
+  *out = nullptr;
+  if (n <= 0) return fail(ctx, LT_ERR_ARGUMENT, "lt_pcd_build: empty point cloud");
+  if (n >= (1ll << 32)) return fail(ctx, LT_ERR_ARGUMENT, "lt_pcd_build: more than 2^32 - 1 points");
+  if (!xyz) return fail(ctx, LT_ERR_ARGUMENT, "lt_pcd_build: null points");
+  if (dtype != 0 && dtype != 1) return fail(ctx, LT_ERR_ARGUMENT, "lt_pcd_build: dtype must be 0 (float32) or 1 (float64)");
+  if (!on_device) {
+    for (long long k = 0; k < 3 * n; ++k) {
+      const double v = dtype ? static_cast<const double *>(xyz)[k] : (double)static_cast<const float *>(xyz)[k];
+      if (!std::isfinite(v)) return fail(ctx, LT_ERR_ARGUMENT, "lt_pcd_build: non-finite point coordinate");
+    }
+  }
+  if (perm) {  // a saved order: any permutation gives exact answers, anything else would read out of bounds
+    std::vector<unsigned char> seen((size_t)n, 0);
+    for (long long k = 0; k < n; ++k) {
+      if ((long long)perm[k] >= n || seen[perm[k]])
+        return fail(ctx, LT_ERR_ARGUMENT, "lt_pcd_build: the saved order is not a permutation of the points");
+      seen[perm[k]] = 1;
+    }
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  Timer tm;
+  if (int rc = tm.start(ctx)) return rc;
+  lt_pcd *p = new lt_pcd();
+  p->device = ctx->device;
+  p->n = n;
+  auto bail = [&](int rc) {
+    (void)hipStreamSynchronize(st);
+    delete p;
+    return rc;
+  };
+  const size_t in_bytes = (size_t)n * 3 * (dtype ? 8 : 4);
+  const void *src = xyz;
+  if (!on_device) {
+    if (!ctx->d_ev_in.ensure(in_bytes)) return bail(fail(ctx, LT_ERR_HIP, "hipMalloc failed for the point upload"));
+    if (hipMemcpyAsync(ctx->d_ev_in.p, xyz, in_bytes, hipMemcpyHostToDevice, st) != hipSuccess)
+      return bail(fail(ctx, LT_ERR_HIP, "lt_pcd_build: upload failed"));
+    src = ctx->d_ev_in.p;
+  }
+  // the levels: buckets of 32 points, then fanout 8 up to one root
+  EvalTree &T = p->tree;
+  T.n = n;
+  long long cnt = (n + kEvalBucket - 1) / kEvalBucket, off = 0;
+  int l = 0;
+  for (;; ++l) {
+    T.lvl_off[l] = off;
+    T.lvl_n[l] = cnt;
+    off += cnt;
+    if (cnt == 1) break;
+    cnt = (cnt + kEvalFanout - 1) / kEvalFanout;
+  }
+  T.top = l;
+  T.total = off;
+  for (int k = l + 1; k < kEvalMaxLevels; ++k) T.lvl_off[k] = T.lvl_n[k] = 0;
+  if (!p->x.ensure(8 * (size_t)n) || !p->y.ensure(8 * (size_t)n) || !p->z.ensure(8 * (size_t)n) ||
+      !p->box.ensure(48 * (size_t)T.total) || !p->perm.ensure(4 * (size_t)n))
+    return bail(fail(ctx, LT_ERR_HIP, "hipMalloc failed for the point index"));
+  if (perm) {
+    if (hipMemcpyAsync(p->perm.p, perm, 4 * (size_t)n, hipMemcpyHostToDevice, st) != hipSuccess)
+      return bail(fail(ctx, LT_ERR_HIP, "lt_pcd_build: upload of the order failed"));
+  } else {
+    // bounding box -> 21-bit quantisation per axis -> 63-bit Morton keys -> rocprim radix sort
+    DevBuf keys;
+    const size_t tmp = eval_sort_temp_bytes(n);
+    const size_t kb = ((size_t)n * 8 + 255) & ~(size_t)255, ib = ((size_t)n * 4 + 255) & ~(size_t)255;
+    if (!keys.ensure(256 + 2 * kb + ib + std::max<size_t>(tmp, 16)))
+      return bail(fail(ctx, LT_ERR_HIP, "hipMalloc failed for the sort of the point index"));
+    char *kp = keys.as<char>();
+    unsigned long long *box6 = reinterpret_cast<unsigned long long *>(kp);
+    unsigned long long *k_in = reinterpret_cast<unsigned long long *>(kp + 256);
+    unsigned long long *k_out = reinterpret_cast<unsigned long long *>(kp + 256 + kb);
+    unsigned *i_in = reinterpret_cast<unsigned *>(kp + 256 + 2 * kb);
+    const unsigned long long init[6] = {~0ull, ~0ull, ~0ull, 0, 0, 0};
+    if (hipMemcpyAsync(box6, init, 48, hipMemcpyHostToDevice, st) != hipSuccess)
+      return bail(fail(ctx, LT_ERR_HIP, "lt_pcd_build: memcpy failed"));
+    launch_eval_bbox(st, src, dtype, n, box6);
+    unsigned long long got[6];
+    if (hipMemcpyAsync(got, box6, 48, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+      return bail(fail(ctx, LT_ERR_HIP, "lt_pcd_build: bounding box failed"));
+    double lo[3], scale[3];
+    for (int k = 0; k < 3; ++k) {
+      auto dec = [](unsigned long long u) {
+        u = (u >> 63) ? (u & 0x7fffffffffffffffull) : ~u;
+        double v;
+        std::memcpy(&v, &u, 8);
+        return v;
+      };
+      lo[k] = dec(got[k]);
+      const double ext = dec(got[3 + k]) - lo[k];
+      scale[k] = (ext > 0.0 && std::isfinite(ext)) ? 2097151.0 / ext : 0.0;
+    }
+    launch_eval_morton(st, src, dtype, n, lo, scale, k_in, i_in);
+    if (launch_eval_sort(st, kp + 256 + 2 * kb + ib, tmp, n, k_in, k_out, i_in, p->perm.as<unsigned>()) != 0)
+      return bail(fail(ctx, LT_ERR_HIP, "rocprim radix sort failed"));
+    tm.launches += 3;
+    if (hipStreamSynchronize(st) != hipSuccess) return bail(fail(ctx, LT_ERR_HIP, "lt_pcd_build: sort failed"));
+  }
+  T.x = p->x.as<double>();
+  T.y = p->y.as<double>();
+  T.z = p->z.as<double>();
+  T.box = p->box.as<double>();
+  launch_eval_gather(st, src, dtype, n, p->perm.as<unsigned>(), p->x.as<double>(), p->y.as<double>(),
+                     p->z.as<double>());
+  launch_eval_boxes(st, T, p->box.as<double>());
+  tm.launches += 2 + T.top;
+  if (int rc = tm.finish(ctx, T.top + 1)) return bail(rc);
+  *out = p;
+  return LT_OK;
+}
+
+void lt_pcd_free(lt_pcd *pcd) {
+  if (!pcd) return;
+  (void)hipSetDevice(pcd->device);
+  (void)hipDeviceSynchronize();  // no work of any stream may still read the index
+  delete pcd;
+}
+
+int lt_pcd_get_perm(lt_ctx *ctx, const lt_pcd *pcd, uint32_t *perm) {
+  if (int rc = check_pcd(ctx, "lt_pcd_get_perm", pcd)) return rc;
+  if (!perm) return fail(ctx, LT_ERR_ARGUMENT, "lt_pcd_get_perm: null output");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipMemcpyAsync(perm, pcd->perm.p, 4 * (size_t)pcd->n, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return LT_OK;
+}
+
+int lt_pcd_nearest_dists(lt_ctx *ctx, const lt_pcd *pcd, const double *query, int64_t n, int64_t chunk,
+                         double *dist) {
+  if (!ctx) return LT_ERR_ARGUMENT;
+  if (int rc = check_pcd(ctx, "lt_pcd_nearest_dists", pcd)) return rc;
+  if (n < 0 || (n > 0 && (!query || !dist))) return fail(ctx, LT_ERR_ARGUMENT, "lt_pcd_nearest_dists: bad arguments");
+  if (int rc = check_finite(ctx, "lt_pcd_nearest_dists", query, 3 * n, "query coordinate")) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  Timer tm;
+  if (int rc = tm.start(ctx)) return rc;
+  const long long C = chunk_of(chunk);
+  ENSURE(ctx, ctx->d_ev_in, 24 * (size_t)std::min<long long>(std::max<long long>(n, 1), C));
+  ENSURE(ctx, ctx->d_ev_out, 8 * (size_t)std::min<long long>(std::max<long long>(n, 1), C));
+  for (long long q0 = 0; q0 < n; q0 += C) {
+    const long long m = std::min<long long>(C, n - q0);
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_ev_in.p, query + 3 * q0, 24 * (size_t)m, hipMemcpyHostToDevice, st));
+    EvalQuery Q{};
+    const double *d = ctx->d_ev_in.as<double>();
+    Q.x = d; Q.y = d + 1; Q.z = d + 2; Q.stride = 3; Q.mode = EV_Q_POINTS; Q.n = 1;
+    launch_eval_nearest(st, pcd->tree, Q, m, ctx->d_ev_out.as<double>());
+    ++tm.launches;
+    HIPCHK(ctx, hipMemcpyAsync(dist + q0, ctx->d_ev_out.p, 8 * (size_t)m, hipMemcpyDeviceToHost, st));
+  }
+  return tm.finish(ctx, 0);
+}
+
+int lt_pcd_line_samples(lt_ctx *ctx, const lt_pcd *pcd, const double *lines, int64_t n_lines, int mode,
+                        int n_samples, const double *thresholds, int n_th, int64_t chunk, double *dists,
+                        int32_t *counts) {
+  if (!ctx) return LT_ERR_ARGUMENT;
+  const char *who = "lt_pcd_line_samples";
+  if (int rc = check_pcd(ctx, who, pcd)) return rc;
+  if (mode != LT_SAMPLE_CENTER && mode != LT_SAMPLE_ENDS) return fail(ctx, LT_ERR_ARGUMENT, "lt_pcd_line_samples: bad mode");
+  if (n_samples < (mode == LT_SAMPLE_ENDS ? 2 : 1))
+    return fail(ctx, LT_ERR_ARGUMENT, "lt_pcd_line_samples: n_samples must be >= 1 (>= 2 for end-point sampling)");
+  if (n_th < 0 || n_th > kEvalMaxTh || (n_th > 0 && !thresholds))
+    return fail(ctx, LT_ERR_ARGUMENT, "lt_pcd_line_samples: between 0 and 64 thresholds");
+  if (n_lines < 0 || (n_lines > 0 && !lines)) return fail(ctx, LT_ERR_ARGUMENT, "lt_pcd_line_samples: bad lines");
+  if (counts && n_th == 0) counts = nullptr;
+  if (int rc = check_finite(ctx, who, lines, 6 * n_lines, "line coordinate")) return rc;
+  if (n_lines == 0 || (!dists && !counts)) return LT_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  Timer tm;
+  if (int rc = tm.start(ctx)) return rc;
+  const auto L = prep_lines(lines, n_lines, 0);
+  if (int rc = upload_lines(ctx, ctx->d_ev_lines, L)) return rc;
+  ENSURE(ctx, ctx->d_ev_th, 8 * (size_t)std::max(n_th, 1));
+  if (n_th) HIPCHK(ctx, hipMemcpyAsync(ctx->d_ev_th.p, thresholds, 8 * (size_t)n_th, hipMemcpyHostToDevice, st));
+  const long long per = std::max<long long>(1, chunk_of(chunk) / n_samples);  // whole lines per launch
+  const long long lc = std::min<long long>(per, n_lines);
+  ENSURE(ctx, ctx->d_ev_out, 8 * (size_t)(lc * n_samples));
+  if (counts) ENSURE(ctx, ctx->d_ev_cnt, 4 * (size_t)(n_lines * n_th));
+  EvalQuery Q{};
+  Q.mode = mode == LT_SAMPLE_CENTER ? EV_Q_CENTER : EV_Q_ENDS;
+  Q.n = n_samples;
+  Q.interval = mode == LT_SAMPLE_CENTER ? 1.0 / n_samples : 1.0 / (n_samples - 1);
+  for (long long l0 = 0; l0 < n_lines; l0 += per) {
+    const long long m = std::min<long long>(per, n_lines - l0);
+    Q.lines = ctx->d_ev_lines.as<EvalLine>() + l0;
+    launch_eval_nearest(st, pcd->tree, Q, m * n_samples, ctx->d_ev_out.as<double>());
+    ++tm.launches;
+    if (counts) {
+      launch_eval_count(st, ctx->d_ev_out.as<double>(), m, n_samples, ctx->d_ev_th.as<double>(), n_th, 1,
+                        ctx->d_ev_cnt.as<int>() + l0 * n_th);
+      ++tm.launches;
+    }
+    if (dists)
+      HIPCHK(ctx, hipMemcpyAsync(dists + l0 * n_samples, ctx->d_ev_out.p, 8 * (size_t)(m * n_samples),
+                                 hipMemcpyDeviceToHost, st));
+  }
+  if (counts)
+    HIPCHK(ctx, hipMemcpyAsync(counts, ctx->d_ev_cnt.p, 4 * (size_t)(n_lines * n_th), hipMemcpyDeviceToHost, st));
+  return tm.finish(ctx, 0);
+}
+
+int lt_lines_point_dists(lt_ctx *ctx, const lt_pcd *pcd, const double *lines, int64_t n_lines, int64_t chunk,
+                         double *dist) {
+  if (!ctx) return LT_ERR_ARGUMENT;
+  const char *who = "lt_lines_point_dists";
+  if (int rc = check_pcd(ctx, who, pcd)) return rc;
+  if (!dist || n_lines < 0 || (n_lines > 0 && !lines)) return fail(ctx, LT_ERR_ARGUMENT, "lt_lines_point_dists: bad arguments");
+  if (int rc = check_finite(ctx, who, lines, 6 * n_lines, "line coordinate")) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  Timer tm;
+  if (int rc = tm.start(ctx)) return rc;
+  const auto L = prep_lines(lines, n_lines, 0);
+  if (int rc = upload_lines(ctx, ctx->d_ev_lines, L)) return rc;
+  const long long N = pcd->n, C = chunk_of(chunk);
+  ENSURE(ctx, ctx->d_ev_out, 8 * (size_t)N);
+  for (long long p0 = 0; p0 < N; p0 += C) {  // the cloud in Morton order, written back in the input order
+    const long long m = std::min<long long>(C, N - p0);
+    EvalQuery Q{};
+    Q.x = pcd->x.as<double>() + p0; Q.y = pcd->y.as<double>() + p0; Q.z = pcd->z.as<double>() + p0;
+    Q.stride = 1; Q.mode = EV_Q_POINTS; Q.n = 1;
+    launch_eval_lines_min(st, 0, Q, m, ctx->d_ev_lines.as<EvalLine>(), n_lines, ctx->d_ev_out.as<double>(),
+                          pcd->perm.as<unsigned>() + p0);
+    ++tm.launches;
+  }
+  HIPCHK(ctx, hipMemcpyAsync(dist, ctx->d_ev_out.p, 8 * (size_t)N, hipMemcpyDeviceToHost, st));
+  return tm.finish(ctx, 0);
+}
+
+int lt_refline_counts(lt_ctx *ctx, const double *query_lines, int64_t n_query, const double *lines, int64_t n_lines,
+                      int n_samples, const double *thresholds, int n_th, int64_t chunk, int32_t *counts) {
+  if (!ctx) return LT_ERR_ARGUMENT;
+  const char *who = "lt_refline_counts";
+  if (n_samples < 1) return fail(ctx, LT_ERR_ARGUMENT, "lt_refline_counts: n_samples must be >= 1");
+  if (n_th < 0 || n_th > kEvalMaxTh || (n_th > 0 && !thresholds))
+    return fail(ctx, LT_ERR_ARGUMENT, "lt_refline_counts: between 0 and 64 thresholds");
+  if (n_query < 0 || n_lines < 0 || (n_query > 0 && !query_lines) || (n_lines > 0 && !lines) ||
+      (n_query > 0 && n_th > 0 && !counts))
+    return fail(ctx, LT_ERR_ARGUMENT, "lt_refline_counts: bad arguments");
+  if (int rc = check_finite(ctx, who, query_lines, 6 * n_query, "line coordinate")) return rc;
+  if (int rc = check_finite(ctx, who, lines, 6 * n_lines, "line coordinate")) return rc;
+  if (n_query == 0 || n_th == 0) return LT_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  Timer tm;
+  if (int rc = tm.start(ctx)) return rc;
+  const auto QL = prep_lines(query_lines, n_query, n_samples);
+  const auto L = prep_lines(lines, n_lines, 0);
+  if (int rc = upload_lines(ctx, ctx->d_ev_in, QL)) return rc;
+  if (int rc = upload_lines(ctx, ctx->d_ev_lines, L)) return rc;
+  ENSURE(ctx, ctx->d_ev_th, 8 * (size_t)n_th);
+  HIPCHK(ctx, hipMemcpyAsync(ctx->d_ev_th.p, thresholds, 8 * (size_t)n_th, hipMemcpyHostToDevice, st));
+  const long long per = std::max<long long>(1, chunk_of(chunk) / n_samples);
+  ENSURE(ctx, ctx->d_ev_out, 8 * (size_t)(std::min<long long>(per, n_query) * n_samples));
+  ENSURE(ctx, ctx->d_ev_cnt, 4 * (size_t)(n_query * n_th));
+  EvalQuery Q{};
+  Q.mode = EV_Q_REFLINE;
+  Q.n = n_samples;
+  for (long long r0 = 0; r0 < n_query; r0 += per) {
+    const long long m = std::min<long long>(per, n_query - r0);
+    Q.lines = ctx->d_ev_in.as<EvalLine>() + r0;
+    launch_eval_lines_min(st, 1, Q, m * n_samples, ctx->d_ev_lines.as<EvalLine>(), n_lines,
+                          ctx->d_ev_out.as<double>(), nullptr);
+    launch_eval_count(st, ctx->d_ev_out.as<double>(), m, n_samples, ctx->d_ev_th.as<double>(), n_th, 0,
+                      ctx->d_ev_cnt.as<int>() + r0 * n_th);
+    tm.launches += 2;
+  }
+  HIPCHK(ctx, hipMemcpyAsync(counts, ctx->d_ev_cnt.p, 4 * (size_t)(n_query * n_th), hipMemcpyDeviceToHost, st));
+  return tm.finish(ctx, 0);
+}
+
+int lt_eval_get_timers(lt_ctx *ctx, double out[4]) {
+  if (!ctx || !out) return LT_ERR_ARGUMENT;
+  for (int k = 0; k < 4; ++k) out[k] = ctx->ev_timers[k];
+  return LT_OK;
+}
+
+}  // extern "C"

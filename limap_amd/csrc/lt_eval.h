@@ -1,0 +1,63 @@
+// lt_eval.h -- records shared by the host side (lt_eval.cpp) and the device side (lt_kernels_eval.hip) of the line-map
+// evaluation (limap.evaluation: PointCloudEvaluator, RefLineEvaluator).  DESIGN §14.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+namespace lt {
+
+constexpr int kEvalBucket = 32;     // cloud points per leaf bucket (consecutive in Morton order)
+constexpr int kEvalFanout = 8;      // children per node of the implicit AABB hierarchy
+constexpr int kEvalMaxLevels = 16;  // 32 * 8^15 points: far beyond any cloud that fits a device
+constexpr int kEvalMaxTh = 64;      // thresholds per call
+constexpr double kEvalEps = 1e-12;  // util/types.h EPS (RefLineEvaluator::DistPointLines' early exit)
+
+// one line, prepared on the host once: direction and length as Line3d::direction() / length() compute them, and the
+// sample spacing of RefLineEvaluator (length / (n - 1))
+struct EvalLine {
+  double s[3], e[3], d[3];
+  double len, rint, pad_;
+};
+
+// the point index: the cloud in Morton order (SoA), leaf buckets of kEvalBucket points and an implicit fanout-8
+// hierarchy of AABBs over them, levels bottom (0: the buckets) to top (one root).  box: 6 doubles per node (lo, hi).
+struct EvalTree {
+  const double *x, *y, *z;
+  const double *box;
+  long long n;
+  long long total;  // nodes of all levels
+  long long lvl_off[kEvalMaxLevels], lvl_n[kEvalMaxLevels];
+  int top;
+};
+
+enum EvalQueryMode { EV_Q_POINTS = 0, EV_Q_CENTER = 1, EV_Q_ENDS = 2, EV_Q_REFLINE = 3 };
+
+// where the query points come from: free points (x, y, z with a stride) or the samples of lines, generated in the
+// kernel from (line, i) -- query q is sample q % n of line q / n
+struct EvalQuery {
+  const double *x, *y, *z;
+  long long stride;
+  const EvalLine *lines;
+  double interval;  // 1 / n (EV_Q_CENTER), 1 / (n - 1) (EV_Q_ENDS)
+  int mode, n;
+};
+
+void launch_eval_bbox(hipStream_t st, const void *xyz, int dtype, long long n, unsigned long long *keys6);
+void launch_eval_morton(hipStream_t st, const void *xyz, int dtype, long long n, const double lo[3],
+                        const double scale[3], unsigned long long *keys, unsigned *idx);
+size_t eval_sort_temp_bytes(long long n);
+int launch_eval_sort(hipStream_t st, void *temp, size_t temp_bytes, long long n, const unsigned long long *keys_in,
+                     unsigned long long *keys_out, const unsigned *idx_in, unsigned *idx_out);
+void launch_eval_gather(hipStream_t st, const void *xyz, int dtype, long long n, const unsigned *perm, double *x,
+                        double *y, double *z);
+void launch_eval_boxes(hipStream_t st, const EvalTree &T, double *box);
+void launch_eval_nearest(hipStream_t st, const EvalTree &T, const EvalQuery &Q, long long nq, double *dist);
+// form 0: Line3d::point_distance, minimum DBL_MAX; form 1: RefLineEvaluator::DistPointLine with the EPS rule.
+// scatter (may be null): out[scatter[q]] instead of out[q]
+void launch_eval_lines_min(hipStream_t st, int form, const EvalQuery &Q, long long nq, const EvalLine *lines,
+                           long long n_lines, double *out, const unsigned *scatter);
+// counts[l * n_th + t] = #{i < n : dist[l * n + i] <= th[t]} (le) or < th[t] (!le), one block per line
+void launch_eval_count(hipStream_t st, const double *dist, long long n_lines, int n, const double *th, int n_th, int le,
+                       int *counts);
+
+}  // namespace lt
