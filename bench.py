@@ -3,6 +3,7 @@
 
     python bench.py --gpus 1 --steps 20 --warmup 3
     python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR   # + the last timed step's results as DIR/*.npy
+    python bench.py --gpus 1 --full                                      # + every extra figure and check (below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -16,11 +17,16 @@ configs[2]: 1000 views x 1000 segs over 4 rooms, sharded by image with connectio
 One step = [all-gather of the per-image payload (N > 1)] + rebuild of the per-camera / per-segment invariants +
 the whole device pipeline (pair invariants, candidate generation, placement, multi-view scoring, per-node
 arg-max + valid edges) with the match lists already resident in HBM.  metric value = 3D line candidates scored
-per second, whole job.  The JSON line also carries the end-to-end wall-clock of the reference's API sequence
-(ctor + Init + TriangulateImage x views + ComputeLineTracks, incl. PCIe and the host tail), the roofline of the
-dominant kernel (HIP-event timed on the kernels' stream) with the FP64-VALU / LDS view next to the HBM one, the
-same measurements for exhaustive matching (CI config 1's mode), and the CPU oracle timed on the host cores with
-a stage-by-stage comparison of its results with the product's (rank 0, N = 1 only; a mismatch fails the run).
+per second, whole job.
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line, which carries the
+roofline of the scoring stage (HIP-event timed on the kernels' stream inside the timed region) with the FP64-VALU /
+LDS view next to the HBM one.  `--full` adds everything that takes runs of its own: the generation kernels priced by
+their own events, the merge of the shards and ComputeLineTracks with and without a step, the sustained loop, the
+strong-scaling and streamed legs, batches in flight, the same measurements for exhaustive matching (CI config 1's
+mode), the end-to-end wall-clock of the reference's API sequence (ctor + Init + TriangulateImage x views +
+ComputeLineTracks, incl. PCIe and the host tail), and the CPU oracle timed on the host cores with a stage-by-stage
+comparison of its results with the product's (rank 0, N = 1 only; a mismatch fails the run).
 """
 import argparse
 import hashlib
@@ -614,21 +620,24 @@ def main():
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"])
     ap.add_argument("--config3", action="store_true",
                     help="BASELINE.json configs[2]: strong scaling, 1000 views x 1000 segs over 4 rooms, 3000 GT segments, seed 1")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps: every extra figure and check -- per-kernel events, merge and tail, the "
+                         "sustained loop, the legs, e2e wall-clock, CPU baselines and parity (the options below shape it)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines and parity")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extras (batches in flight, exhaustive leg): profiling runs want the main kernels only")
+                    help="--full without the extras (batches in flight, exhaustive leg): profiling runs want the main kernels only")
     ap.add_argument("--strong-leg", default="auto", choices=["auto", "on", "off"],
-                    help="BASELINE config 3 as a strong-scaling leg of the same run (`strong_config3` in the line); auto = "
+                    help="BASELINE config 3 as a strong-scaling leg of a --full run (`strong_config3` in the line); auto = "
                          "with the default workload")
     ap.add_argument("--stream-leg", default="auto", choices=["auto", "on", "off"],
                     help="BASELINE config 5's stand-in (5000 x 600, streamed in chunks with neighbour closure, chunks round-robin "
-                         "over the ranks) as a leg of the same run (`streamed_config5` in the line); auto = with the default workload")
+                         "over the ranks) as a leg of a --full run (`streamed_config5` in the line); auto = with the default workload")
     ap.add_argument("--stream", action="store_true",
                     help="the streamed leg only: the line's value is the streamed job's candidates/s (5000 x 600)")
     ap.add_argument("--sustain-s", type=float, default=2.0,
-                    help="after the timed region: the same step looped for about this long (sustained_ms_per_step; an "
-                         "outside observer -- rocm-smi -- sees the device busy); 0 = off")
+                    help="--full, after the timed region: the same step looped for about this long (sustained_ms_per_step; "
+                         "an outside observer of the device sees it busy); 0 = off")
     ap.add_argument("--e2e-child", nargs=5, type=int, metavar=("VIEWS", "SEGS", "NEIGHBORS", "SEED", "TOPK"),
                     help="internal: the end-to-end call sequence in this (torch-free) process, see e2e_child")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -639,6 +648,9 @@ def main():
         ap.error("--dump-outputs is not available with --stream")
     if args.dump_outputs and args.steps < 1:
         ap.error("--dump-outputs needs --steps >= 1")
+    for leg in ("strong_leg", "stream_leg"):
+        if getattr(args, leg) == "on" and not args.full:
+            ap.error(f"--{leg.replace('_', '-')} on needs --full")
     if args.e2e_child:
         return e2e_child(*args.e2e_child)
     if args.config3:
@@ -810,8 +822,8 @@ def main():
     if args.dump_outputs:  # the results of the last timed step, read back after the clock has stopped
         dumped = dump_outputs(ctx, args.dump_outputs, suffix=f"_rank{rank}" if world > 1 else "")
     # The timed region carries the events around the dominant stage only (scoring = k_score_q: roofline).  The generation
-    # kernels are priced in a few extra steps with their own events on (LT_FINE_TIMERS=2 costs ~5 us per step).
-    if args.mode == "matched":
+    # kernels are priced in a few extra steps with their own events on (LT_FINE_TIMERS=2 costs ~5 us per step), --full only.
+    if args.mode == "matched" and args.full:
         prev_fine = os.environ.get("LT_FINE_TIMERS")
         os.environ["LT_FINE_TIMERS"] = "2"
         os.environ["LT_TIMER_SAMPLE"] = "1"
@@ -828,13 +840,16 @@ def main():
         # (generation and placement stages too: the timed region records no event between them)
         for k in ("k_gates", "k_tri_rows", "gen", "compact"):
             kt[k] = acc2[k] / max(n2, 1)
+    elif args.mode == "matched":  # (not measured: a plain run leaves them out of kernel_ms)
+        for k in ("k_gates", "k_tri_rows", "gen", "compact"):
+            kt.pop(k, None)
     if pending[0] is not None:  # the collective launched by the last step
         pending[0].wait()
         torch.cuda.synchronize(dev)
 
     # the collective alone (what the overlap hides): 10 all-gathers back to back
     allgather_us = None
-    if use_dist:
+    if use_dist and args.full:
         torch.cuda.synchronize(dev)
         dist.barrier()
         ta = time.perf_counter()
@@ -843,60 +858,61 @@ def main():
         torch.cuda.synchronize(dev)
         allgather_us = 1e6 * (time.perf_counter() - ta) / 10
 
-    # the tail (not part of the timed step).  N > 1: the other shards' per-node results and valid-edge keys travel to
-    # rank 0 device to device (ltdist.merge_shards_device: one gather of two flat buffers, no host copy, no per-image
-    # export), and rank 0's tail runs on its device over the whole scene.  This rank's nodes are one range of the
-    # global node index (images are sharded in id order).
+    # the tail (not part of the timed step), --full only.  N > 1: the other shards' per-node results and valid-edge keys
+    # travel to rank 0 device to device (ltdist.merge_shards_device: one gather of two flat buffers, no host copy, no
+    # per-image export), and rank 0's tail runs on its device over the whole scene.  This rank's nodes are one range of
+    # the global node index (images are sharded in id order).
     my_idx = np.searchsorted(scene.img_ids, my_imgs)
     node_range = (int(scene.seg_off[my_idx[0]]), int(scene.seg_off[my_idx[-1] + 1])) if len(my_idx) else (0, 0)
-    all_ranges, key_cap = shard_node_ranges(scene, world, weights)  # -> ONE collective per merge
-    merge_note, t_merge = None, None
-    if world > 1:
-        try:
-            tm0 = time.perf_counter()
-            ltdist.merge_shards_device(ctx, node_range, rank, world, merge_dev, all_ranges=all_ranges, key_cap=key_cap)
-            t_merge = time.perf_counter() - tm0
-        except Exception as e:  # never lose the throughput line over the (untimed) merge
-            merge_note = f"merge failed: {type(e).__name__}: {e}"
-    t_tail0 = time.perf_counter()
-    ctx.compute_tracks()
-    t_tail = time.perf_counter() - t_tail0
+    merge_note, t_merge, t_tail = None, None, None
+    if args.full:
+        all_ranges, key_cap = shard_node_ranges(scene, world, weights)  # -> ONE collective per merge
+        if world > 1:
+            try:
+                tm0 = time.perf_counter()
+                ltdist.merge_shards_device(ctx, node_range, rank, world, merge_dev, all_ranges=all_ranges, key_cap=key_cap)
+                t_merge = time.perf_counter() - tm0
+            except Exception as e:  # never lose the throughput line over the (untimed) merge
+                merge_note = f"merge failed: {type(e).__name__}: {e}"
+        t_tail0 = time.perf_counter()
+        ctx.compute_tracks()
+        t_tail = time.perf_counter() - t_tail0
     st = ctx.stats()   # (reads this rank's per-node results back: the pair statistic is summed on the host)
     st["active_nodes"] = int(sum(scene.seg_off[j + 1] - scene.seg_off[j] for j in my_idx))
-    st_after = ctx.stats()
-    # ---- second figure (not `value`): the step INCLUDING what `value` leaves out -- the per-node results' way to the
-    # host, rank 0's import of the other shards (one tensor gather) and the serial tail ComputeLineTracks on rank 0
-    # (global_line_triangulator.cc:234-351: the Amdahl part of an N-GPU run).  Strictly sequential per step; max
-    # over ranks; reported beside ms_per_step so that a scaling curve shows both.
-    n_full = max(1, min(args.steps, 5))
-    full_note = None
-    sync()
-    tf0 = time.perf_counter()
-    try:
-        for _ in range(n_full):
-            step()
-            ctx.sync()
-            if world > 1:  # (nothing is downloaded: the tail works from device-resident results, merged on the device)
-                ltdist.merge_shards_device(ctx, node_range, rank, world, merge_dev, all_ranges=all_ranges, key_cap=key_cap)
-            if rank == 0 or world == 1:
-                ctx.compute_tracks()
+    step_full_ms, full_note, track_report_gpu = None, None, None
+    if args.full:
+        st_after = ctx.stats()
+        # ---- second figure (not `value`): the step INCLUDING what `value` leaves out -- the per-node results' way to the
+        # host, rank 0's import of the other shards (one tensor gather) and the serial tail ComputeLineTracks on rank 0
+        # (global_line_triangulator.cc:234-351: the Amdahl part of an N-GPU run).  Strictly sequential per step; max
+        # over ranks; reported beside ms_per_step so that a scaling curve shows both.
+        n_full = max(1, min(args.steps, 5))
         sync()
-    except Exception as e:
-        full_note = f"{type(e).__name__}: {e}"
-    full_elapsed = time.perf_counter() - tf0
-    if pending[0] is not None:
-        pending[0].wait()
-        torch.cuda.synchronize(dev)
-    if use_dist:
-        t_f = torch.tensor([full_elapsed], dtype=torch.float64, device=_comm_dev(dev))
-        dist.all_reduce(t_f, op=dist.ReduceOp.MAX)
-        full_elapsed = float(t_f.item())
-    step_full_ms = None if full_note else 1e3 * full_elapsed / n_full
-    track_report_gpu = None
-    if rank == 0:  # limap's track report (visualize/trackvis/base.py:25-50): a secondary parity signal
-        from limap_amd.base import track_report
-        trk = ctx.get_tracks()
-        track_report_gpu = track_report(trk["off"], trk["image_ids"])
+        tf0 = time.perf_counter()
+        try:
+            for _ in range(n_full):
+                step()
+                ctx.sync()
+                if world > 1:  # (nothing is downloaded: the tail works from device-resident results, merged on the device)
+                    ltdist.merge_shards_device(ctx, node_range, rank, world, merge_dev, all_ranges=all_ranges, key_cap=key_cap)
+                if rank == 0 or world == 1:
+                    ctx.compute_tracks()
+            sync()
+        except Exception as e:
+            full_note = f"{type(e).__name__}: {e}"
+        full_elapsed = time.perf_counter() - tf0
+        if pending[0] is not None:
+            pending[0].wait()
+            torch.cuda.synchronize(dev)
+        if use_dist:
+            t_f = torch.tensor([full_elapsed], dtype=torch.float64, device=_comm_dev(dev))
+            dist.all_reduce(t_f, op=dist.ReduceOp.MAX)
+            full_elapsed = float(t_f.item())
+        step_full_ms = None if full_note else 1e3 * full_elapsed / n_full
+        if rank == 0:  # limap's track report (visualize/trackvis/base.py:25-50): a secondary parity signal
+            from limap_amd.base import track_report
+            trk = ctx.get_tracks()
+            track_report_gpu = track_report(trk["off"], trk["image_ids"])
 
     per_rank_ms = [1e3 * elapsed_local / max(args.steps, 1)]
     if use_dist:
@@ -946,15 +962,16 @@ def main():
                                    and isinstance(b_[k], (int, float)) and k not in ("valu_busy_frac", "lds_active_frac")}
                 pmc["k_score3"]["per_kernel"] = {n_: {k: v for k, v in e_.items() if k != "raw"}
                                                  for n_, e_ in (("k_score3(sweep)", a_), ("k_dense8", b_))}
-            kernels = {"k_score3": (ab["score"], kt.get("k_score3", 0.0)), "k_gates": (ab["gates"], kt.get("k_gates", 0.0)),
-                       "k_tri_rows": (ab["tri"], kt.get("k_tri_rows", 0.0))}
+            kernels = {"k_score3": (ab["score"], kt.get("k_score3", 0.0))}
+            if args.full:  # (priced in the extra steps with their own events)
+                kernels.update(k_gates=(ab["gates"], kt.get("k_gates", 0.0)), k_tri_rows=(ab["tri"], kt.get("k_tri_rows", 0.0)))
         else:
             pmc = exhaustive_stage_pmc(pmc)
             kernels = {"k_score3": (ab["score"], kt.get("k_score3", 0.0)), "k_gen_exhaustive": (ab["gen"], kt.get("gen", 0.0))}
         dom = max(kernels, key=lambda k: kernels[k][1])
         roof = {name: roofline_entry(name, nbytes, ms, pmc) for name, (nbytes, ms) in kernels.items()}
         kt["line_slots"] = last.get("line_slots", 0.0)
-        if args.mode == "matched" and last.get("line_slots", 0.0):  # the stage names stay, the kernels are round 5's
+        if args.mode == "matched" and args.full and last.get("line_slots", 0.0):  # the stage names stay, the kernels are round 5's
             roof["k_gates"]["kernel"] = "k_gates_ln (stage A, line-slot form: one lane per line)"
             roof["k_tri_rows"]["kernel"] = "k_tri_rounds (stage B in rounds of 64 survivors)"
         if args.mode == "matched" and kt.get("gen", 0.0) > 0:
@@ -967,17 +984,14 @@ def main():
             "metric": ("3D line candidates scored/sec (" + ("100 views x 500 segs per GPU" if default_wl else wl.split(",")[0])
                        + (", matched topk=%d)" % args.topk if args.mode == "matched" else ", exhaustive)")),
             "value": value, "unit": "candidates/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "step_with_merge_and_tail_ms": step_full_ms,
-            "step_with_merge_and_tail_note": full_note or (
-                f"{n_full} steps of: all-gather + kernels + per-node results to the host + rank 0's import of the other "
-                "shards + ComputeLineTracks on rank 0, sequential, max over ranks (not part of `value`)"),
+            "ms_per_step": ms_per_step,
             "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
             "dtype": "f64", "data": "synthetic",
             "config": {"workload": wl, "views_total": n_total, "segs_per_view": args.segs, "n_neighbors": args.neighbors,
                        "mode": args.mode, "topk": args.topk, "parallelism": f"shard-by-image x{world}",
                        "scene_seed": args.seed, "rooms": n_rooms},
             "counts": {"connections": conn_total, "candidates": cand_total, "scoring_pairs": pairs_total,
-                       "valid_edges_rank0": st["valid_edges"], "tracks_rank0": st_after["tracks"]},
+                       "valid_edges_rank0": st["valid_edges"]},
             "kernel_ms": kt, "preroll": preroll,
             "connections_per_s": conn_total * args.steps / elapsed,
             "roofline": dict(roof[dom], kernel=(dom if not (dom == "k_score3" and args.mode == "matched" and not os.environ.get("LT_SCORE_FUSED"))
@@ -990,18 +1004,25 @@ def main():
             "roofline_all": roof,
             "roofline_note": pmc_note or ("traffic / valu_f64 / lds: rocprofv3 --pmc passes over this exact device code "
                                           "(profiles/r06_pmc.json, tools/prof_pmc_json.sh); FP64 VALU peak 78.6 TF"),
-            "host_ms": {"upload_matches": 1e3 * t_upload, "tail_compute_tracks": 1e3 * t_tail,
-                        "merge_shards_device": None if t_merge is None else 1e3 * t_merge},
-            "tracks_whole_scene": st_after["tracks"], "merge_note": merge_note,
-            "track_report": track_report_gpu,
+            "host_ms": {"upload_matches": 1e3 * t_upload},
             "ranks": {"world_size": dist.get_world_size() if use_dist else 1,
                       "n_ranks_rccl": dist.get_world_size() if (use_dist and dist.get_backend() == "nccl") else 0,
                       "backend": (dist.get_backend() + (" (RCCL)" if dist.get_backend() == "nccl" else "")) if use_dist else None,
                       "ms_per_step_per_rank": per_rank_ms, "candidates_per_rank": per_rank_cand,
                       "load_imbalance_max_over_mean": (max(per_rank_ms) / (sum(per_rank_ms) / len(per_rank_ms))) if per_rank_ms else None,
-                      "images_per_rank": per_rank_imgs, "allgather_alone_us": allgather_us},
+                      "images_per_rank": per_rank_imgs},
             "device_source_hash": device_source_hash(),
         }
+        if args.full:
+            out["step_with_merge_and_tail_ms"] = step_full_ms
+            out["step_with_merge_and_tail_note"] = full_note or (
+                f"{n_full} steps of: all-gather + kernels + per-node results to the host + rank 0's import of the other "
+                "shards + ComputeLineTracks on rank 0, sequential, max over ranks (not part of `value`)")
+            out["counts"]["tracks_rank0"] = st_after["tracks"]
+            out["host_ms"].update(tail_compute_tracks=1e3 * t_tail,
+                                  merge_shards_device=None if t_merge is None else 1e3 * t_merge)
+            out.update(tracks_whole_scene=st_after["tracks"], merge_note=merge_note, track_report=track_report_gpu)
+            out["ranks"]["allgather_alone_us"] = allgather_us
         if dumped is not None:
             out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
 
@@ -1009,7 +1030,7 @@ def main():
     # seconds; this loop keeps the device on the step for --sustain-s so that an observer outside the process (the driver's
     # SMI sampler) sees it busy, and reports what the step costs when it is not a burst ----
     sustained = None
-    if args.sustain_s > 0 and not args.no_extras:
+    if args.full and args.sustain_s > 0 and not args.no_extras:
         # (steps for about sustain_s seconds: from the faster of the two per-step figures at hand -- the timed region's and the
         # pre-roll's -- so that a short timed region's burst figure does not cut the loop short)
         per_step_ms = ms_per_step
@@ -1039,7 +1060,7 @@ def main():
         out["sustained"] = sustained
 
     # ---- the strong-scaling leg: BASELINE config 3 over the same ranks (every rank takes part) ----
-    if args.mode == "matched" and (args.strong_leg == "on" or (args.strong_leg == "auto" and default_wl and not args.no_extras)):
+    if args.full and args.mode == "matched" and (args.strong_leg == "on" or (args.strong_leg == "auto" and default_wl and not args.no_extras)):
         try:
             sc3 = strong_config3_leg(cfg, rank, world, local_rank, dev, use_dist)
         except Exception as e:  # an extra: never lose the main line over it
@@ -1048,7 +1069,7 @@ def main():
             out["strong_config3"] = sc3
 
     # ---- the streamed leg: BASELINE config 5's stand-in over the same ranks (every rank takes part) ----
-    if args.mode == "matched" and (args.stream_leg == "on" or (args.stream_leg == "auto" and default_wl and not args.no_extras)):
+    if args.full and args.mode == "matched" and (args.stream_leg == "on" or (args.stream_leg == "auto" and default_wl and not args.no_extras)):
         try:
             s5 = streamed_config5_leg(cfg, rank, world, local_rank, dev, use_dist, pmc_path=stream_pmc)
         except Exception as e:  # an extra: never lose the main line over it
@@ -1061,7 +1082,7 @@ def main():
     # with its own stream and buffers, the same workload) overlap one batch's kernel tails and launch gaps
     # with the other's kernels.  `value` above stays the one-batch-at-a-time figure the per-kernel roofline
     # numbers belong to (HIP-event kernel durations are not meaningful while two streams interleave).
-    if rank == 0 and world == 1 and args.mode == "matched" and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and args.mode == "matched" and not args.no_extras:
         def make_ctx():
             c = _capi.Context(cfg_dict=cfg, device=local_rank)
             c.set_ranges(*scene.ranges)
@@ -1094,7 +1115,7 @@ def main():
             out["batches_in_flight"] = {"error": f"{type(e).__name__}: {e}"}
 
     # ---- extra: the same scene with exhaustive matching (CI config 1's mode), N = 1 ----
-    if rank == 0 and world == 1 and args.mode == "matched" and default_wl and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and args.mode == "matched" and default_wl and not args.no_extras:
         try:
             cx = _capi.Context(cfg_dict=cfg, device=local_rank)
             cx.set_ranges(*scene.ranges)
@@ -1128,7 +1149,7 @@ def main():
             out["exhaustive"] = {"error": f"{type(e).__name__}: {e}"}
 
     # ---- end-to-end wall-clock through the reference's API sequence, rank 0 / N = 1 ----
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         from limap_amd import triangulation as tri
         matches = {int(i): scene.matches_of(int(i), args.topk) for i in scene.img_ids} if args.mode == "matched" else None
         segs_list = [scene.segs_of(j) for j in range(scene.n_images)]

@@ -1,4 +1,5 @@
-"""-m gpu: bench.py prints ONE JSON line as its last stdout line with the fields the driver reads."""
+"""-m gpu: bench.py prints ONE JSON line as its last stdout line with the fields the driver reads; a plain run stops
+after the timed steps, --full adds every extra figure and check."""
 import json
 import os
 import subprocess
@@ -14,8 +15,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_line_has_the_contract_fields(gpu_lib):
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                          "--views", "12", "--segs", "60", "--neighbors", "5", "--strong-leg", "on", "--sustain-s", "0.2",
-                          "--stream-leg", "on"],
+                          "--views", "12", "--segs", "60", "--neighbors", "5", "--full", "--strong-leg", "on",
+                          "--sustain-s", "0.2", "--stream-leg", "on"],
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=ROOT,
                          env=dict(os.environ, LT_BENCH_STRONG_SCENE="30,80,6", LT_BENCH_STREAM_SCENE="40,60,6,9"))
     assert res.returncode == 0, res.stderr[-2000:]
@@ -56,6 +57,30 @@ def test_bench_line_has_the_contract_fields(gpu_lib):
     assert d["cpu_parity"]["candidates_cpu"] == d["cpu_parity"]["candidates_gpu"]
 
 
+def test_plain_bench_run_stops_after_the_timed_steps(gpu_lib, oracle):
+    """Without --full: the headline fields and the timed region's roofline, counted on the same job as the CPU oracle,
+    and none of the figures that take runs of their own (tail, sustained loop, legs, e2e, CPU baselines)."""
+    from limap_amd import synthetic as syn
+    from helpers import run_oracle
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--views", "12", "--segs", "60", "--neighbors", "5"],
+                         stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=ROOT)
+    assert res.returncode == 0, res.stderr[-2000:]
+    d = json.loads(res.stdout.strip().splitlines()[-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "roofline"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["unit"] == "candidates/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert set(d["roofline_all"]) == {"k_score3"} and d["roofline"]["kernel_ms"] > 0
+    for k in ("step_with_merge_and_tail_ms", "tracks_whole_scene", "sustained", "strong_config3", "streamed_config5",
+              "batches_in_flight", "exhaustive", "e2e_wall_ms", "cpu_baseline", "cpu_parity"):
+        assert k not in d, k
+    assert "k_gates" not in d["kernel_ms"] and "tracks_rank0" not in d["counts"]
+    sc = syn.make_scene(n_views=12, n_segs=60, n_neighbors=5, n_rooms=1, n_gt=None, seed=0, topk=10)
+    so = run_oracle(oracle, sc, syn.default_triangulation_cfg(), topk=10).stats()
+    assert d["counts"]["candidates"] == so["candidates"] > 0 and d["counts"]["connections"] == so["connections"]
+
+
 def test_bench_collective_path_one_rank(gpu_lib):
     """The N > 1 code path of bench.py (RCCL all-gather per step, overlapped with the kernels, max over ranks) on
     the one GPU a test box has: LT_BENCH_FORCE_DIST=1 under torch.distributed.run with one rank."""
@@ -63,7 +88,7 @@ def test_bench_collective_path_one_rank(gpu_lib):
     res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                           "--master-addr", "127.0.0.1", "--master-port", "29533", os.path.join(ROOT, "bench.py"),
                           "--gpus", "1", "--steps", "3", "--warmup", "1", "--views", "12", "--segs", "60",
-                          "--neighbors", "5", "--no-cpu-baseline", "--strong-leg", "on", "--sustain-s", "0.2"],
+                          "--neighbors", "5", "--full", "--no-cpu-baseline", "--strong-leg", "on", "--sustain-s", "0.2"],
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=ROOT,
                          env=dict(env, LT_BENCH_STRONG_SCENE="30,80,6"))
     assert res.returncode == 0, res.stderr[-2000:]
@@ -80,8 +105,9 @@ def test_bench_two_ranks_on_one_gpu(gpu_lib):
     control flow of the file -- connection-weighted shards, the merge of the shards on rank 0 in its one-collective form,
     the reductions over ranks, the strong-scaling leg with its sequential and its overlapped tail -- runs to the JSON
     line, and the whole-scene track count is that of a one-rank run of the same scene."""
-    common = ["--steps", "3", "--warmup", "1", "--views", "12", "--segs", "60", "--neighbors", "5", "--no-cpu-baseline",
-              "--no-extras", "--strong-leg", "on", "--sustain-s", "0.2", "--scaling", "strong", "--stream-leg", "on"]
+    common = ["--steps", "3", "--warmup", "1", "--views", "12", "--segs", "60", "--neighbors", "5", "--full",
+              "--no-cpu-baseline", "--no-extras", "--strong-leg", "on", "--sustain-s", "0.2", "--scaling", "strong",
+              "--stream-leg", "on"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", LT_BENCH_STRONG_SCENE="30,80,6", LT_BENCH_STREAM_SCENE="40,60,6,9")
     res2 = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                            "--master-addr", "127.0.0.1", "--master-port", "29537", os.path.join(ROOT, "bench.py"),

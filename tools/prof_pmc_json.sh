@@ -1,5 +1,6 @@
 #!/bin/bash
-# Counter-derived per-launch numbers for bench.py's roofline block -> gpurun_out/${TAG:-r06}_pmc.json (copy to profiles/).
+# Counter-derived per-launch numbers for bench.py's roofline block -> $PROF_OUT/${TAG:-r06}_pmc.json (default prof_out/;
+# copy to profiles/).
 #   HBM bytes     : reads  = 32 x TCC_EA0_RDREQ_32B + 64 x TCC_EA0_RDREQ_64B + 128 x TCC_EA0_RDREQ_128B (the L2's memory-side
 #                   requests by size; calibrated on known byte counts in this code's access patterns --
 #                   profiles/r03_traffic_calib.txt: every pattern, streams and record gathers alike, is served by 128-byte
@@ -13,8 +14,9 @@
 # the device sources; bench.py quotes the numbers only while that hash matches.
 # usage (on the GPU box, repo root): bash tools/prof_pmc_json.sh
 repo=$(pwd)
+export PROF_OUT=${PROF_OUT:-$repo/prof_out}
 export TMPDIR=/tmp
-mkdir -p $repo/gpurun_out
+mkdir -p $PROF_OUT
 groups=(
 "FETCH_SIZE"
 "WRITE_SIZE"
@@ -25,18 +27,18 @@ groups=(
 )
 for mode in matched exhaustive; do
   i=0
-  : > $repo/gpurun_out/pmcj_$mode.csv
+  : > $PROF_OUT/pmcj_$mode.csv
   for g in "${groups[@]}"; do
     i=$((i+1))
     cd /tmp && rm -rf /tmp/pmcj_${mode}_$i
     steps=3; [ $mode = exhaustive ] && steps=2
-    timeout 150 rocprofv3 --pmc $g -d /tmp/pmcj_${mode}_$i -- python $repo/bench.py --steps $steps --warmup 1 --mode $mode --no-cpu-baseline --no-extras > /dev/null 2> /tmp/pmcj_${mode}_$i.err || { echo "# group $i failed: $g"; tail -3 /tmp/pmcj_${mode}_$i.err; continue; }
+    timeout 150 rocprofv3 --pmc $g -d /tmp/pmcj_${mode}_$i -- python $repo/bench.py --steps $steps --warmup 1 --mode $mode --full --no-cpu-baseline --no-extras > /dev/null 2> /tmp/pmcj_${mode}_$i.err || { echo "# group $i failed: $g"; tail -3 /tmp/pmcj_${mode}_$i.err; continue; }
     db=$(find /tmp/pmcj_${mode}_$i -name "*.db" | head -1)
-    python $repo/tools/rocpd_pmc.py $db 2>/dev/null >> $repo/gpurun_out/pmcj_$mode.csv
+    python $repo/tools/rocpd_pmc.py $db 2>/dev/null >> $PROF_OUT/pmcj_$mode.csv
   done
 done
 cd $repo && python - <<'PY'
-import csv, json, re, sys
+import csv, json, os, re, sys
 sys.path.insert(0, ".")
 import bench
 out = {"device_source_hash": bench.device_source_hash(),
@@ -54,7 +56,7 @@ alias = {"k_gen_ex_block": "k_gen_exhaustive", "k_gates_ln": "k_gates", "k_tri_r
 for mode in ("matched", "exhaustive"):
     vals = {}
     try:
-        rows = list(csv.reader(open(f"gpurun_out/pmcj_{mode}.csv")))
+        rows = list(csv.reader(open(os.path.join(os.environ["PROF_OUT"], f"pmcj_{mode}.csv"))))
     except FileNotFoundError:
         continue
     for row in rows:
@@ -89,8 +91,7 @@ for mode in ("matched", "exhaustive"):
         a, b = kern["k_gates_ex"], kern["k_tri_ex"]
         kern["k_gen_exhaustive"] = {f: a[f] + b[f] for f in ("hbm_bytes", "valu_flops_f64", "valu_insts") if f in a and f in b}
     out["kernels"][mode] = kern
-import os
-json.dump(out, open("gpurun_out/%s_pmc.json" % os.environ.get("TAG", "r06"), "w"), indent=1)
+json.dump(out, open(os.path.join(os.environ["PROF_OUT"], "%s_pmc.json" % os.environ.get("TAG", "r06")), "w"), indent=1)
 for mode, kern in out["kernels"].items():
     for n in ("k_score_q", "k_score3", "k_dense8", "k_gates", "k_tri_rows", "k_place", "k_gen_exhaustive"):
         if n in kern:
