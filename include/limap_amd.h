@@ -419,8 +419,26 @@ int lt_lines_point_dists(lt_ctx *ctx, const lt_pcd *pcd, const double *lines, in
  * (start + (length / (n - 1) * i) * direction) whose DistPointLines to `lines` is < thresholds[t] */
 int lt_refline_counts(lt_ctx *ctx, const double *query_lines, int64_t n_query, const double *lines, int64_t n_lines,
                       int n_samples, const double *thresholds, int n_th, int64_t chunk, int32_t *counts);
+/* MeshEvaluator (evaluation/mesh_evaluator.cc): distances to a triangle mesh (Ericson's
+ * closest point on a triangle in a stated FP64 operation order, a project rule for faces whose interior denominator is
+ * not > 0).  A triangle index on the context's device: faces in the Morton order of their centroids, buckets of
+ * consecutive faces, the implicit hierarchy of lt_pcd.  V: nv x 3 vertices, dtype 0 float32 (widened exactly) or 1
+ * float64, on the host or (on_device) a device pointer of the context's device; each coordinate is multiplied by scale
+ * once (the reference's V_ *= mpau).  F: nf x 3 vertex indices (0-based, host memory).  LT_ERR_ARGUMENT for nf == 0,
+ * a face index outside [0, nv), a non-finite scale or scaled coordinate. */
+typedef struct lt_mesh lt_mesh;
+int lt_mesh_build(lt_ctx *ctx, const void *V, int64_t nv, int dtype, int on_device, const int64_t *F, int64_t nf,
+                  double scale, lt_mesh **out);
+void lt_mesh_free(lt_mesh *mesh);
+/* ComputeDistPoint over n query points (n x 3): the exact distance to the nearest face */
+int lt_mesh_nearest_dists(lt_ctx *ctx, const lt_mesh *mesh, const double *query, int64_t n, int64_t chunk,
+                          double *dist);
+/* as lt_pcd_line_samples, against the mesh */
+int lt_mesh_line_samples(lt_ctx *ctx, const lt_mesh *mesh, const double *lines, int64_t n_lines, int mode,
+                         int n_samples, const double *thresholds, int n_th, int64_t chunk, double *dists,
+                         int32_t *counts);
 /* of the last evaluation call: [0] device ms of its kernels (HIP events), [1] host ms of the call, [2] launches,
- * [3] index levels (lt_pcd_build) */
+ * [3] index levels (lt_pcd_build, lt_mesh_build) */
 int lt_eval_get_timers(lt_ctx *ctx, double out[4]);
 
 /* Counters of the last device run: [0] connections tested, [1] candidates, [2] ordered candidate

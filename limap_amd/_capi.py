@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = [
     "lt_fit_config_default", "lt_fit_segs", "lt_fit_scans", "lt_fit_points", "lt_fit_get_timers",
     "lt_pcd_build", "lt_pcd_free", "lt_pcd_get_perm", "lt_pcd_nearest_dists", "lt_pcd_line_samples",
     "lt_lines_point_dists", "lt_refline_counts", "lt_eval_get_timers",
+    "lt_mesh_build", "lt_mesh_free", "lt_mesh_nearest_dists", "lt_mesh_line_samples",
 ]
 
 
@@ -242,6 +243,12 @@ def load_library():
     L.lt_lines_point_dists.argtypes = [vp, vp, dp, C.c_int64, C.c_int64, dp]
     L.lt_refline_counts.argtypes = [vp, dp, C.c_int64, dp, C.c_int64, C.c_int, dp, C.c_int, C.c_int64, i32p]
     L.lt_eval_get_timers.argtypes = [vp, dp]
+    L.lt_mesh_build.argtypes = [vp, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_double,
+                                C.POINTER(vp)]
+    L.lt_mesh_free.argtypes = [vp]
+    L.lt_mesh_free.restype = None
+    L.lt_mesh_nearest_dists.argtypes = [vp, vp, dp, C.c_int64, C.c_int64, dp]
+    L.lt_mesh_line_samples.argtypes = [vp, vp, dp, C.c_int64, C.c_int, C.c_int, dp, C.c_int, C.c_int64, dp, i32p]
     _lib = L
     return L
 

@@ -1,9 +1,10 @@
 // lt_eval.cpp -- limap.evaluation on the GPU (evaluation/point_cloud_evaluator.cc, base_evaluator.cc,
-// refline_evaluator.cc): the point index (lt_pcd_build), nearest-point distances of free points and of line samples
-// (lt_pcd_nearest_dists, lt_pcd_line_samples), the point-to-segment minima of ComputeDistsforEachPoint
-// (lt_lines_point_dists) and the counters of RefLineEvaluator (lt_refline_counts).  The host validates, prepares the
-// per-line constants (direction, length: the sqrt and divisions of Line3d, once per line) and launches in chunks; every
-// distance is computed on the device (lt_kernels_eval.hip).  DESIGN §14.
+// refline_evaluator.cc, mesh_evaluator.cc): the point index (lt_pcd_build), nearest-point distances of free points and
+// of line samples (lt_pcd_nearest_dists, lt_pcd_line_samples), the point-to-segment minima of ComputeDistsforEachPoint
+// (lt_lines_point_dists), the counters of RefLineEvaluator (lt_refline_counts), and the triangle index of
+// MeshEvaluator with its point-to-mesh distances (lt_mesh_build, lt_mesh_nearest_dists, lt_mesh_line_samples).  The
+// host validates, prepares the per-line constants (direction, length: the sqrt and divisions of Line3d, once per line)
+// and launches in chunks; every distance is computed on the device (lt_kernels_eval.hip).  DESIGN §14, §15.
 
 #include "lt_host.h"
 #include "lt_eval.h"
@@ -21,6 +22,13 @@ struct lt_pcd {
   long long n = 0;
   DevBuf x, y, z, box, perm;
   EvalTree tree{};
+};
+
+struct lt_mesh {
+  int device = 0;
+  long long n = 0;  // faces
+  DevBuf faces, box, eta, perm;
+  MeshTree tree{};
 };
 
 namespace {
@@ -73,6 +81,19 @@ int check_pcd(lt_ctx *ctx, const char *who, const lt_pcd *pcd) {
   if (pcd->device != ctx->device)
     return fail(ctx, LT_ERR_ARGUMENT, std::string(who) + ": the index lives on another device than the context");
   return LT_OK;
+}
+
+int check_mesh(lt_ctx *ctx, const char *who, const lt_mesh *mesh) {
+  if (!mesh) return fail(ctx, LT_ERR_ARGUMENT, std::string(who) + ": null mesh");
+  if (mesh->device != ctx->device)
+    return fail(ctx, LT_ERR_ARGUMENT, std::string(who) + ": the mesh lives on another device than the context");
+  return LT_OK;
+}
+
+// LT_TEST_MESH_BRUTE=1: every face for every query (k_mesh_brute), the yardstick of the hierarchy walk
+int mesh_brute() {
+  const char *e = lt_impl::test_switch("LT_TEST_MESH_BRUTE");
+  return e && e[0] == '1';
 }
 
 struct Timer {  // HIP events around the kernels of one call
@@ -378,6 +399,208 @@ int lt_refline_counts(lt_ctx *ctx, const double *query_lines, int64_t n_query, c
     tm.launches += 2;
   }
   HIPCHK(ctx, hipMemcpyAsync(counts, ctx->d_ev_cnt.p, 4 * (size_t)(n_query * n_th), hipMemcpyDeviceToHost, st));
+  return tm.finish(ctx, 0);
+}
+
+int lt_mesh_build(lt_ctx *ctx, const void *V, int64_t nv, int dtype, int on_device, const int64_t *F, int64_t nf,
+                  double scale, lt_mesh **out) {
+  if (!ctx || !out) return LT_ERR_ARGUMENT;
+  *out = nullptr;
+  const char *who = "lt_mesh_build";
+  if (nf <= 0) return fail(ctx, LT_ERR_ARGUMENT, "lt_mesh_build: a mesh without faces");
+  if (nf >= (1ll << 32)) return fail(ctx, LT_ERR_ARGUMENT, "lt_mesh_build: more than 2^32 - 1 faces");
+  if (nv <= 0 || !V || !F) return fail(ctx, LT_ERR_ARGUMENT, "lt_mesh_build: null or empty vertices or faces");
+  if (dtype != 0 && dtype != 1) return fail(ctx, LT_ERR_ARGUMENT, "lt_mesh_build: dtype must be 0 (float32) or 1 (float64)");
+  if (!std::isfinite(scale)) return fail(ctx, LT_ERR_ARGUMENT, "lt_mesh_build: non-finite scale");
+  for (long long k = 0; k < 3 * nf; ++k)
+    if (F[k] < 0 || F[k] >= nv) return fail(ctx, LT_ERR_ARGUMENT, "lt_mesh_build: face index out of range");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  // the vertices as the reference scales them (V_ *= mpau): one multiplication per coordinate, here on the host
+  const size_t in_bytes = (size_t)nv * 3 * (dtype ? 8 : 4);
+  std::vector<unsigned char> staged;
+  const void *src = V;
+  if (on_device) {
+    staged.resize(in_bytes);
+    HIPCHK(ctx, hipMemcpy(staged.data(), V, in_bytes, hipMemcpyDeviceToHost));
+    src = staged.data();
+  }
+  std::vector<double> Vs((size_t)nv * 3);
+  for (long long k = 0; k < 3 * nv; ++k) {
+    const double v = dtype ? static_cast<const double *>(src)[k] : (double)static_cast<const float *>(src)[k];
+    Vs[(size_t)k] = v * scale;
+    if (!std::isfinite(Vs[(size_t)k])) return fail(ctx, LT_ERR_ARGUMENT, std::string(who) + ": non-finite vertex coordinate");
+  }
+  int bucket = kMeshBucket;
+  if (const char *e = lt_impl::test_switch("LT_TEST_MESH_BUCKET")) {  // bucket sizes for the measurement
+    bucket = atoi(e);
+    if (bucket < 1 || bucket > kMeshMaxBucket) return fail(ctx, LT_ERR_ARGUMENT, "LT_TEST_MESH_BUCKET: 1 .. 64");
+  }
+  Timer tm;
+  if (int rc = tm.start(ctx)) return rc;
+  lt_mesh *m = new lt_mesh();
+  m->device = ctx->device;
+  m->n = nf;
+  auto bail = [&](int rc) {
+    (void)hipStreamSynchronize(st);
+    delete m;
+    return rc;
+  };
+  MeshTree &T = m->tree;
+  T.n = nf;
+  T.bucket = bucket;
+  long long cnt = (nf + bucket - 1) / bucket, off = 0;
+  int l = 0;
+  for (;; ++l) {
+    T.lvl_off[l] = off;
+    T.lvl_n[l] = cnt;
+    off += cnt;
+    if (cnt == 1) break;
+    cnt = (cnt + kEvalFanout - 1) / kEvalFanout;
+  }
+  T.top = l;
+  T.total = off;
+  for (int k = l + 1; k < kEvalMaxLevels; ++k) T.lvl_off[k] = T.lvl_n[k] = 0;
+  // scratch: vertices, faces, centroids, Morton keys and the sort
+  const size_t vb = ((size_t)nv * 24 + 255) & ~(size_t)255, fb = ((size_t)nf * 24 + 255) & ~(size_t)255;
+  const size_t kb = ((size_t)nf * 8 + 255) & ~(size_t)255, ib = ((size_t)nf * 4 + 255) & ~(size_t)255;
+  const size_t tmp = eval_sort_temp_bytes(nf);
+  DevBuf scr;
+  if (!scr.ensure(256 + vb + 2 * fb + 2 * kb + ib + std::max<size_t>(tmp, 16)) || !m->faces.ensure(72 * (size_t)nf) ||
+      !m->box.ensure(48 * (size_t)T.total) || !m->eta.ensure(8 * (size_t)T.total) || !m->perm.ensure(4 * (size_t)nf))
+    return bail(fail(ctx, LT_ERR_HIP, "hipMalloc failed for the mesh index"));
+  char *sp = scr.as<char>();
+  unsigned long long *box6 = reinterpret_cast<unsigned long long *>(sp);
+  double *dV = reinterpret_cast<double *>(sp + 256);
+  long long *dF = reinterpret_cast<long long *>(sp + 256 + vb);
+  double *cen = reinterpret_cast<double *>(sp + 256 + vb + fb);
+  unsigned long long *k_in = reinterpret_cast<unsigned long long *>(sp + 256 + vb + 2 * fb);
+  unsigned long long *k_out = reinterpret_cast<unsigned long long *>(sp + 256 + vb + 2 * fb + kb);
+  unsigned *i_in = reinterpret_cast<unsigned *>(sp + 256 + vb + 2 * fb + 2 * kb);
+  void *sort_tmp = sp + 256 + vb + 2 * fb + 2 * kb + ib;
+  const unsigned long long init[6] = {~0ull, ~0ull, ~0ull, 0, 0, 0};
+  if (hipMemcpyAsync(dV, Vs.data(), 24 * (size_t)nv, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(dF, F, 24 * (size_t)nf, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(box6, init, 48, hipMemcpyHostToDevice, st) != hipSuccess)
+    return bail(fail(ctx, LT_ERR_HIP, "lt_mesh_build: upload failed"));
+  // the order: the point index's bounding box, Morton keys and radix sort, over the face centroids
+  launch_mesh_centroids(st, dV, dF, nf, cen);
+  launch_eval_bbox(st, cen, 1, nf, box6);
+  unsigned long long got[6];
+  if (hipMemcpyAsync(got, box6, 48, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return bail(fail(ctx, LT_ERR_HIP, "lt_mesh_build: bounding box failed"));
+  double lo[3], sc[3];
+  for (int k = 0; k < 3; ++k) {
+    auto dec = [](unsigned long long u) {
+      u = (u >> 63) ? (u & 0x7fffffffffffffffull) : ~u;
+      double v;
+      std::memcpy(&v, &u, 8);
+      return v;
+    };
+    lo[k] = dec(got[k]);
+    const double ext = dec(got[3 + k]) - lo[k];
+    sc[k] = (ext > 0.0 && std::isfinite(ext)) ? 2097151.0 / ext : 0.0;
+  }
+  launch_eval_morton(st, cen, 1, nf, lo, sc, k_in, i_in);
+  if (launch_eval_sort(st, sort_tmp, tmp, nf, k_in, k_out, i_in, m->perm.as<unsigned>()) != 0)
+    return bail(fail(ctx, LT_ERR_HIP, "rocprim radix sort failed"));
+  double *fa[9];
+  for (int k = 0; k < 9; ++k) {
+    fa[k] = m->faces.as<double>() + (size_t)k * nf;
+    T.v[k] = fa[k];
+  }
+  T.box = m->box.as<double>();
+  T.eta = m->eta.as<double>();
+  launch_mesh_gather(st, dV, dF, nf, m->perm.as<unsigned>(), fa);
+  launch_mesh_boxes(st, T, m->box.as<double>(), m->eta.as<double>());
+  tm.launches += 6 + 2 * T.top;
+  if (int rc = tm.finish(ctx, T.top + 1)) return bail(rc);  // (the scratch returns to the cache after the sync)
+  *out = m;
+  return LT_OK;
+}
+
+void lt_mesh_free(lt_mesh *mesh) {
+  if (!mesh) return;
+  (void)hipSetDevice(mesh->device);
+  (void)hipDeviceSynchronize();
+  delete mesh;
+}
+
+int lt_mesh_nearest_dists(lt_ctx *ctx, const lt_mesh *mesh, const double *query, int64_t n, int64_t chunk,
+                          double *dist) {
+  if (!ctx) return LT_ERR_ARGUMENT;
+  if (int rc = check_mesh(ctx, "lt_mesh_nearest_dists", mesh)) return rc;
+  if (n < 0 || (n > 0 && (!query || !dist))) return fail(ctx, LT_ERR_ARGUMENT, "lt_mesh_nearest_dists: bad arguments");
+  if (int rc = check_finite(ctx, "lt_mesh_nearest_dists", query, 3 * n, "query coordinate")) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int brute = mesh_brute();
+  Timer tm;
+  if (int rc = tm.start(ctx)) return rc;
+  const long long C = chunk_of(chunk);
+  ENSURE(ctx, ctx->d_ev_in, 24 * (size_t)std::min<long long>(std::max<long long>(n, 1), C));
+  ENSURE(ctx, ctx->d_ev_out, 8 * (size_t)std::min<long long>(std::max<long long>(n, 1), C));
+  for (long long q0 = 0; q0 < n; q0 += C) {
+    const long long m = std::min<long long>(C, n - q0);
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_ev_in.p, query + 3 * q0, 24 * (size_t)m, hipMemcpyHostToDevice, st));
+    EvalQuery Q{};
+    const double *d = ctx->d_ev_in.as<double>();
+    Q.x = d; Q.y = d + 1; Q.z = d + 2; Q.stride = 3; Q.mode = EV_Q_POINTS; Q.n = 1;
+    launch_mesh_nearest(st, mesh->tree, Q, m, brute, ctx->d_ev_out.as<double>());
+    ++tm.launches;
+    HIPCHK(ctx, hipMemcpyAsync(dist + q0, ctx->d_ev_out.p, 8 * (size_t)m, hipMemcpyDeviceToHost, st));
+  }
+  return tm.finish(ctx, 0);
+}
+
+int lt_mesh_line_samples(lt_ctx *ctx, const lt_mesh *mesh, const double *lines, int64_t n_lines, int mode,
+                         int n_samples, const double *thresholds, int n_th, int64_t chunk, double *dists,
+                         int32_t *counts) {
+  if (!ctx) return LT_ERR_ARGUMENT;
+  const char *who = "lt_mesh_line_samples";
+  if (int rc = check_mesh(ctx, who, mesh)) return rc;
+  if (mode != LT_SAMPLE_CENTER && mode != LT_SAMPLE_ENDS) return fail(ctx, LT_ERR_ARGUMENT, "lt_mesh_line_samples: bad mode");
+  if (n_samples < (mode == LT_SAMPLE_ENDS ? 2 : 1))
+    return fail(ctx, LT_ERR_ARGUMENT, "lt_mesh_line_samples: n_samples must be >= 1 (>= 2 for end-point sampling)");
+  if (n_th < 0 || n_th > kEvalMaxTh || (n_th > 0 && !thresholds))
+    return fail(ctx, LT_ERR_ARGUMENT, "lt_mesh_line_samples: between 0 and 64 thresholds");
+  if (n_lines < 0 || (n_lines > 0 && !lines)) return fail(ctx, LT_ERR_ARGUMENT, "lt_mesh_line_samples: bad lines");
+  if (counts && n_th == 0) counts = nullptr;
+  if (int rc = check_finite(ctx, who, lines, 6 * n_lines, "line coordinate")) return rc;
+  if (n_lines == 0 || (!dists && !counts)) return LT_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int brute = mesh_brute();
+  Timer tm;
+  if (int rc = tm.start(ctx)) return rc;
+  const auto L = prep_lines(lines, n_lines, 0);
+  if (int rc = upload_lines(ctx, ctx->d_ev_lines, L)) return rc;
+  ENSURE(ctx, ctx->d_ev_th, 8 * (size_t)std::max(n_th, 1));
+  if (n_th) HIPCHK(ctx, hipMemcpyAsync(ctx->d_ev_th.p, thresholds, 8 * (size_t)n_th, hipMemcpyHostToDevice, st));
+  const long long per = std::max<long long>(1, chunk_of(chunk) / n_samples);  // whole lines per launch
+  const long long lc = std::min<long long>(per, n_lines);
+  ENSURE(ctx, ctx->d_ev_out, 8 * (size_t)(lc * n_samples));
+  if (counts) ENSURE(ctx, ctx->d_ev_cnt, 4 * (size_t)(n_lines * n_th));
+  EvalQuery Q{};
+  Q.mode = mode == LT_SAMPLE_CENTER ? EV_Q_CENTER : EV_Q_ENDS;
+  Q.n = n_samples;
+  Q.interval = mode == LT_SAMPLE_CENTER ? 1.0 / n_samples : 1.0 / (n_samples - 1);
+  for (long long l0 = 0; l0 < n_lines; l0 += per) {
+    const long long m = std::min<long long>(per, n_lines - l0);
+    Q.lines = ctx->d_ev_lines.as<EvalLine>() + l0;
+    launch_mesh_nearest(st, mesh->tree, Q, m * n_samples, brute, ctx->d_ev_out.as<double>());
+    ++tm.launches;
+    if (counts) {
+      launch_eval_count(st, ctx->d_ev_out.as<double>(), m, n_samples, ctx->d_ev_th.as<double>(), n_th, 1,
+                        ctx->d_ev_cnt.as<int>() + l0 * n_th);
+      ++tm.launches;
+    }
+    if (dists)
+      HIPCHK(ctx, hipMemcpyAsync(dists + l0 * n_samples, ctx->d_ev_out.p, 8 * (size_t)(m * n_samples),
+                                 hipMemcpyDeviceToHost, st));
+  }
+  if (counts)
+    HIPCHK(ctx, hipMemcpyAsync(counts, ctx->d_ev_cnt.p, 4 * (size_t)(n_lines * n_th), hipMemcpyDeviceToHost, st));
   return tm.finish(ctx, 0);
 }
 

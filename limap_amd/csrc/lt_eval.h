@@ -1,5 +1,5 @@
-// lt_eval.h -- records shared by the host side (lt_eval.cpp) and the device side (lt_kernels_eval.hip) of the line-map
-// evaluation (limap.evaluation: PointCloudEvaluator, RefLineEvaluator).  DESIGN §14.
+// lt_eval.h -- records shared by the host side (lt_eval.cpp, lt_mesh.cpp) and the device side (lt_kernels_eval.hip) of
+// the line-map evaluation (limap.evaluation: PointCloudEvaluator, RefLineEvaluator, MeshEvaluator).  DESIGN §14, §15.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -42,6 +42,22 @@ struct EvalQuery {
   int mode, n;
 };
 
+constexpr int kMeshBucket = 4;      // faces per leaf bucket (consecutive in the Morton order of the centroids), DESIGN §15
+constexpr int kMeshMaxBucket = 64;  // LT_TEST_MESH_BUCKET: the bucket sizes a measurement may try
+
+// the triangle index: the faces in the Morton order of their centroids, as nine SoA vertex arrays (a, b, c: x, y, z),
+// leaf buckets of `bucket` faces and the implicit fanout-8 hierarchy of EvalTree over them.  box: 6 doubles per node,
+// the leaf boxes widened by a few ulps of their coordinates; eta: per node the largest region-7 slack
+// factor of the faces below it (+inf: a near-degenerate face, the node is never pruned).
+struct MeshTree {
+  const double *v[9];
+  const double *box, *eta;
+  long long n;
+  long long total;
+  long long lvl_off[kEvalMaxLevels], lvl_n[kEvalMaxLevels];
+  int top, bucket;
+};
+
 void launch_eval_bbox(hipStream_t st, const void *xyz, int dtype, long long n, unsigned long long *keys6);
 void launch_eval_morton(hipStream_t st, const void *xyz, int dtype, long long n, const double lo[3],
                         const double scale[3], unsigned long long *keys, unsigned *idx);
@@ -59,5 +75,15 @@ void launch_eval_lines_min(hipStream_t st, int form, const EvalQuery &Q, long lo
 // counts[l * n_th + t] = #{i < n : dist[l * n + i] <= th[t]} (le) or < th[t] (!le), one block per line
 void launch_eval_count(hipStream_t st, const double *dist, long long n_lines, int n, const double *th, int n_th, int le,
                        int *counts);
+
+// the mesh index (lt_mesh.cpp): centroids (nf x 3) of faces F (int64, validated) over vertices V (nv x 3, scaled)
+void launch_mesh_centroids(hipStream_t st, const double *V, const long long *F, long long nf, double *cen);
+// faces in the order perm into the nine SoA arrays of T
+void launch_mesh_gather(hipStream_t st, const double *V, const long long *F, long long nf, const unsigned *perm,
+                        double *const out[9]);
+// leaf boxes and slack factors, then the levels above (k_eval_level_boxes and the maximum of eta)
+void launch_mesh_boxes(hipStream_t st, const MeshTree &T, double *box, double *eta);
+// squared-distance minimum over the faces, sqrt at the end: the hierarchy walk, or (brute) every face, staged in LDS
+void launch_mesh_nearest(hipStream_t st, const MeshTree &T, const EvalQuery &Q, long long nq, int brute, double *dist);
 
 }  // namespace lt

@@ -1,6 +1,7 @@
 // lt_kernels_eval.hip -- device side of limap.evaluation (evaluation/point_cloud_evaluator.cc, base_evaluator.cc,
 // refline_evaluator.cc of the reference): the point index (Morton order, buckets, an implicit AABB hierarchy), exact
-// nearest-point queries on it, and the brute-force minima of point-to-segment distances.  DESIGN §14.
+// nearest-point queries on it, and the brute-force minima of point-to-segment distances.  DESIGN §14.  The same
+// machinery over triangle faces for MeshEvaluator (mesh_evaluator.cc): DESIGN §15.
 //
 // Exactness: every distance is the reference's expression in its operation order (-ffp-contract=off); the minimum is
 // kept over SQUARED distances and the one correctly rounded sqrt taken at the end, which gives the same double because
@@ -309,6 +310,286 @@ __global__ __launch_bounds__(kBlock) void k_eval_count(const double *dist, int n
   for (int t = threadIdx.x; t < n_th; t += kBlock) counts[(long long)blockIdx.x * n_th + t] = c[t];
 }
 
+// ---- MeshEvaluator: point-to-triangle distances ----------------------------------------------------------
+
+constexpr int kFaceTile = 256;  // brute force: faces staged in LDS per pass (72 B each)
+
+__device__ inline double dot3(const double u[3], const double v[3]) { return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2]; }
+
+__device__ inline double sqn_diff(const double p[3], const double q[3]) {
+  const double r[3] = {p[0] - q[0], p[1] - q[1], p[2] - q[2]};
+  return dot3(r, r);
+}
+
+// the project rule of a face whose region-7 denominator is not > 0: the closest of the clamped projections onto
+// AB, BC, CA, in that order, kept with <
+__device__ inline double degenerate_dist2(const double a[3], const double b[3], const double c[3], const double p[3]) {
+  const double *U[3] = {a, b, c}, *W[3] = {b, c, a};
+  double m = INFINITY;
+  for (int k = 0; k < 3; ++k) {
+    double e[3], up[3], q[3];
+    for (int i = 0; i < 3; ++i) {
+      e[i] = W[k][i] - U[k][i];
+      up[i] = p[i] - U[k][i];
+    }
+    const double ee = dot3(e, e);
+    double t = ee > 0.0 ? dot3(up, e) / ee : 0.0;
+    t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
+    for (int i = 0; i < 3; ++i) q[i] = U[k][i] + t * e[i];
+    const double d = sqn_diff(p, q);
+    m = d < m ? d : m;
+  }
+  return m;
+}
+
+// Ericson's ClosestPtPointTriangle (Real-Time Collision Detection §5.1.5), squared distance, in the operation order of
+// the first region that matches decides q
+__device__ inline double tri_dist2(const double a[3], const double b[3], const double c[3], const double p[3]) {
+  double ab[3], ac[3], ap[3], bp[3], cp[3], q[3];
+  for (int i = 0; i < 3; ++i) {
+    ab[i] = b[i] - a[i];
+    ac[i] = c[i] - a[i];
+    ap[i] = p[i] - a[i];
+  }
+  const double d1 = dot3(ab, ap), d2 = dot3(ac, ap);
+  if (d1 <= 0.0 && d2 <= 0.0) return sqn_diff(p, a);  // 1: vertex a
+  for (int i = 0; i < 3; ++i) bp[i] = p[i] - b[i];
+  const double d3 = dot3(ab, bp), d4 = dot3(ac, bp);
+  if (d3 >= 0.0 && d4 <= d3) return sqn_diff(p, b);  // 2: vertex b
+  const double vc = d1 * d4 - d3 * d2;
+  if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {  // 3: edge ab
+    const double v = d1 / (d1 - d3);
+    for (int i = 0; i < 3; ++i) q[i] = a[i] + v * ab[i];
+    return sqn_diff(p, q);
+  }
+  for (int i = 0; i < 3; ++i) cp[i] = p[i] - c[i];
+  const double d5 = dot3(ab, cp), d6 = dot3(ac, cp);
+  if (d6 >= 0.0 && d5 <= d6) return sqn_diff(p, c);  // 4: vertex c
+  const double vb = d5 * d2 - d1 * d6;
+  if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) {  // 5: edge ac
+    const double w = d2 / (d2 - d6);
+    for (int i = 0; i < 3; ++i) q[i] = a[i] + w * ac[i];
+    return sqn_diff(p, q);
+  }
+  const double va = d3 * d6 - d5 * d4;
+  const double e43 = d4 - d3, e56 = d5 - d6;
+  if (va <= 0.0 && e43 >= 0.0 && e56 >= 0.0) {  // 6: edge bc
+    const double w = e43 / (e43 + e56);
+    for (int i = 0; i < 3; ++i) q[i] = b[i] + w * (c[i] - b[i]);
+    return sqn_diff(p, q);
+  }
+  const double s = (va + vb) + vc;
+  if (!(s > 0.0)) return degenerate_dist2(a, b, c, p);
+  const double denom = 1.0 / s;  // 7: the interior
+  const double v = vb * denom, w = vc * denom;
+  for (int i = 0; i < 3; ++i) q[i] = (a[i] + ab[i] * v) + ac[i] * w;
+  return sqn_diff(p, q);
+}
+
+__device__ inline void load_face(const MeshTree &T, long long f, double a[3], double b[3], double c[3]) {
+  for (int i = 0; i < 3; ++i) {
+    a[i] = T.v[i][f];
+    b[i] = T.v[3 + i][f];
+    c[i] = T.v[6 + i][f];
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_mesh_centroids(const double *V, const long long *F, long long nf,
+                                                           double *cen) {
+  const long long f = blockIdx.x * (long long)kBlock + threadIdx.x;
+  if (f >= nf) return;
+  const long long i0 = F[3 * f], i1 = F[3 * f + 1], i2 = F[3 * f + 2];
+  for (int k = 0; k < 3; ++k) cen[3 * f + k] = ((V[3 * i0 + k] + V[3 * i1 + k]) + V[3 * i2 + k]) / 3.0;
+}
+
+struct FaceOut {
+  double *p[9];
+};
+
+__global__ __launch_bounds__(kBlock) void k_mesh_gather(const double *V, const long long *F, long long nf,
+                                                        const unsigned *perm, FaceOut out) {
+  const long long f = blockIdx.x * (long long)kBlock + threadIdx.x;
+  if (f >= nf) return;
+  const long long g = perm[f];
+  for (int j = 0; j < 3; ++j) {
+    const long long vi = F[3 * g + j];
+    for (int k = 0; k < 3; ++k) out.p[3 * j + k][f] = V[3 * vi + k];
+  }
+}
+
+// a bucket's box over all its vertices, widened per axis by 2 * 2^-48 * max(|lo|, |hi|) (+ a subnormal floor): the few
+// roundings of regions 1-6 and of the degenerate rule keep q inside it.  eta: the largest region-7 factor of its faces,
+// 2^-40 E^3 / S (E^2 the longest squared edge, S = |ab|^2 |ac|^2 - (ab.ac)^2), +inf when S <= 2^-30 E^4
+__global__ __launch_bounds__(kBlock) void k_mesh_leaf_boxes(MeshTree T, double *box, double *eta) {
+  const long long b = blockIdx.x * (long long)kBlock + threadIdx.x;
+  if (b >= T.lvl_n[0]) return;
+  const long long f0 = b * T.bucket;
+  const long long f1 = f0 + T.bucket < T.n ? f0 + T.bucket : T.n;
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, et = 0.0;
+  for (long long f = f0; f < f1; ++f) {
+    double v[3][3];
+    load_face(T, f, v[0], v[1], v[2]);
+    for (int j = 0; j < 3; ++j)
+      for (int k = 0; k < 3; ++k) {
+        lo[k] = v[j][k] < lo[k] ? v[j][k] : lo[k];
+        hi[k] = v[j][k] > hi[k] ? v[j][k] : hi[k];
+      }
+    double ab[3], ac[3], bc[3];
+    for (int k = 0; k < 3; ++k) {
+      ab[k] = v[1][k] - v[0][k];
+      ac[k] = v[2][k] - v[0][k];
+      bc[k] = v[2][k] - v[1][k];
+    }
+    const double l1 = dot3(ab, ab), l2 = dot3(ac, ac), l3 = dot3(bc, bc), x = dot3(ab, ac);
+    double e2 = l1 > l2 ? l1 : l2;
+    e2 = l3 > e2 ? l3 : e2;
+    if (e2 > 0.0) {  // (three equal vertices: region 1 always, q = a)
+      const double S = l1 * l2 - x * x;
+      const double h = S > 0x1p-30 * (e2 * e2) ? 0x1p-40 * (e2 * sqrt(e2)) / S : INFINITY;
+      et = h > et ? h : et;
+    }
+  }
+  double *o = box + 6 * (T.lvl_off[0] + b);
+  for (int k = 0; k < 3; ++k) {
+    const double m = 0x1p-48 * fmax(fabs(lo[k]), fabs(hi[k])) + 0x1p-1060;
+    o[k] = lo[k] - 2.0 * m;
+    o[3 + k] = hi[k] + 2.0 * m;
+  }
+  eta[T.lvl_off[0] + b] = et;
+}
+
+__global__ __launch_bounds__(kBlock) void k_mesh_level_eta(MeshTree T, int l, double *eta) {
+  const long long j = blockIdx.x * (long long)kBlock + threadIdx.x;
+  if (j >= T.lvl_n[l]) return;
+  const long long c0 = j * kEvalFanout;
+  const long long c1 = c0 + kEvalFanout < T.lvl_n[l - 1] ? c0 + kEvalFanout : T.lvl_n[l - 1];
+  double m = 0.0;
+  for (long long c = c0; c < c1; ++c) {
+    const double e = eta[T.lvl_off[l - 1] + c];
+    m = e > m ? e : m;
+  }
+  eta[T.lvl_off[l] + j] = m;
+}
+
+// a lower bound of the computed squared distance of p to every face below a node: the per-axis gap to the (widened)
+// box, reduced by the region-7 slack X = eta * Rfar^2 (Rfar: the farthest point of the box) and by 2^-50 of itself,
+// squared and summed in the distance's order.  A NaN slack (inf * 0) leaves no gap.
+__device__ inline double mesh_bound2(const double *b, double eta, const double p[3]) {
+  double g[3], r[3];
+  for (int k = 0; k < 3; ++k) {
+    const double lo = b[k] - p[k], hi = p[k] - b[3 + k];
+    g[k] = lo > 0.0 ? lo : (hi > 0.0 ? hi : 0.0);
+    const double al = fabs(lo), ah = fabs(hi);
+    r[k] = al > ah ? al : ah;
+  }
+  const double X = (eta * ((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2])) * (1.0 + 0x1p-40);
+  for (int k = 0; k < 3; ++k) {
+    const double h = g[k] - (X + g[k] * 0x1p-50);
+    g[k] = h > 0.0 ? h : 0.0;
+  }
+  return (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];
+}
+
+__device__ inline double scan_faces(const MeshTree &T, long long b, const double p[3], double best) {
+  const long long f0 = b * T.bucket;
+  const long long f1 = f0 + T.bucket < T.n ? f0 + T.bucket : T.n;
+  for (long long f = f0; f < f1; ++f) {
+    double a[3], bb[3], c[3];
+    load_face(T, f, a, bb, c);
+    const double d2 = tri_dist2(a, bb, c, p);
+    best = d2 < best ? d2 : best;
+  }
+  return best;
+}
+
+// as nearest2 of the point index: a greedy descent to one bucket, then the stackless walk bounded by T.total
+__device__ double mesh_nearest2(const MeshTree &T, const double p[3]) {
+  long long j = 0;
+  for (int l = T.top; l > 0; --l) {
+    const long long c0 = j * kEvalFanout;
+    const long long c1 = c0 + kEvalFanout < T.lvl_n[l - 1] ? c0 + kEvalFanout : T.lvl_n[l - 1];
+    long long bj = c0;
+    double bb = INFINITY;
+    for (long long c = c0; c < c1; ++c) {
+      const long long node = T.lvl_off[l - 1] + c;
+      const double v = mesh_bound2(T.box + 6 * node, T.eta[node], p);
+      if (v < bb) { bb = v; bj = c; }
+    }
+    j = bj;
+  }
+  const long long first = j;
+  double best = scan_faces(T, first, p, INFINITY);
+  int l = T.top;
+  j = 0;
+  for (long long it = 0; it < T.total; ++it) {
+    const long long node = T.lvl_off[l] + j;
+    const double lb = mesh_bound2(T.box + 6 * node, T.eta[node], p);
+    if (!(lb > best)) {
+      if (l > 0) {
+        --l;
+        j *= kEvalFanout;
+        continue;
+      }
+      if (j != first) best = scan_faces(T, j, p, best);
+    }
+    bool done = true;
+    for (int u = 0; u < kEvalMaxLevels && l < T.top; ++u) {
+      if ((j + 1) % kEvalFanout != 0 && j + 1 < T.lvl_n[l]) {
+        ++j;
+        done = false;
+        break;
+      }
+      ++l;
+      j /= kEvalFanout;
+    }
+    if (done) break;
+  }
+  return best;
+}
+
+__global__ __launch_bounds__(kBlock) void k_mesh_nearest(MeshTree T, EvalQuery Q, long long nq, double *dist) {
+  const long long q = blockIdx.x * (long long)kBlock + threadIdx.x;
+  if (q >= nq) return;
+  double p[3];
+  query_point(Q, q, p);
+  dist[q] = sqrt(mesh_nearest2(T, p));
+}
+
+// the walk's yardstick: every face, tiles of kFaceTile faces staged in LDS (SoA), kPerLane queries per lane
+__global__ __launch_bounds__(kBlock) void k_mesh_brute(MeshTree T, EvalQuery Q, long long nq, double *dist) {
+  __shared__ double tile[9][kFaceTile];
+  const long long base = blockIdx.x * (long long)(kBlock * kPerLane) + threadIdx.x;
+  double p[kPerLane][3], m2[kPerLane];
+  for (int r = 0; r < kPerLane; ++r) {
+    const long long q = base + r * kBlock;
+    if (q < nq) query_point(Q, q, p[r]);
+    else p[r][0] = p[r][1] = p[r][2] = 0.0;
+    m2[r] = INFINITY;
+  }
+  for (long long t0 = 0; t0 < T.n; t0 += kFaceTile) {
+    const int cnt = (int)(T.n - t0 < kFaceTile ? T.n - t0 : kFaceTile);
+    __syncthreads();
+    for (int k = threadIdx.x; k < 9 * kFaceTile; k += kBlock) {
+      const int a = k / kFaceTile, f = k - a * kFaceTile;
+      if (f < cnt) tile[a][f] = T.v[a][t0 + f];
+    }
+    __syncthreads();
+    for (int j = 0; j < cnt; ++j) {
+      const double a[3] = {tile[0][j], tile[1][j], tile[2][j]};
+      const double b[3] = {tile[3][j], tile[4][j], tile[5][j]};
+      const double c[3] = {tile[6][j], tile[7][j], tile[8][j]};
+      for (int r = 0; r < kPerLane; ++r) {
+        const double d2 = tri_dist2(a, b, c, p[r]);
+        m2[r] = d2 < m2[r] ? d2 : m2[r];
+      }
+    }
+  }
+  for (int r = 0; r < kPerLane; ++r) {
+    const long long q = base + r * kBlock;
+    if (q < nq) dist[q] = sqrt(m2[r]);
+  }
+}
+
 }  // namespace
 
 void launch_eval_bbox(hipStream_t st, const void *xyz, int dtype, long long n, unsigned long long *keys6) {
@@ -365,6 +646,40 @@ void launch_eval_count(hipStream_t st, const double *dist, long long n_lines, in
                        int *counts) {
   if (n_lines <= 0) return;
   hipLaunchKernelGGL(k_eval_count, dim3((unsigned)n_lines), dim3(kBlock), 0, st, dist, n, th, n_th, le, counts);
+}
+
+void launch_mesh_centroids(hipStream_t st, const double *V, const long long *F, long long nf, double *cen) {
+  hipLaunchKernelGGL(k_mesh_centroids, dim3(nblk(nf, kBlock)), dim3(kBlock), 0, st, V, F, nf, cen);
+}
+
+void launch_mesh_gather(hipStream_t st, const double *V, const long long *F, long long nf, const unsigned *perm,
+                        double *const out[9]) {
+  FaceOut o;
+  for (int k = 0; k < 9; ++k) o.p[k] = out[k];
+  hipLaunchKernelGGL(k_mesh_gather, dim3(nblk(nf, kBlock)), dim3(kBlock), 0, st, V, F, nf, perm, o);
+}
+
+void launch_mesh_boxes(hipStream_t st, const MeshTree &T, double *box, double *eta) {
+  hipLaunchKernelGGL(k_mesh_leaf_boxes, dim3(nblk(T.lvl_n[0], kBlock)), dim3(kBlock), 0, st, T, box, eta);
+  EvalTree E{};  // the levels above the buckets: the point index's box kernel reads only the level table
+  E.total = T.total;
+  E.top = T.top;
+  for (int l = 0; l < kEvalMaxLevels; ++l) {
+    E.lvl_off[l] = T.lvl_off[l];
+    E.lvl_n[l] = T.lvl_n[l];
+  }
+  for (int l = 1; l <= T.top; ++l) {
+    hipLaunchKernelGGL(k_eval_level_boxes, dim3(nblk(T.lvl_n[l], kBlock)), dim3(kBlock), 0, st, E, l, box);
+    hipLaunchKernelGGL(k_mesh_level_eta, dim3(nblk(T.lvl_n[l], kBlock)), dim3(kBlock), 0, st, T, l, eta);
+  }
+}
+
+void launch_mesh_nearest(hipStream_t st, const MeshTree &T, const EvalQuery &Q, long long nq, int brute, double *dist) {
+  if (nq <= 0) return;
+  if (brute)
+    hipLaunchKernelGGL(k_mesh_brute, dim3(nblk(nq, kBlock * kPerLane)), dim3(kBlock), 0, st, T, Q, nq, dist);
+  else
+    hipLaunchKernelGGL(k_mesh_nearest, dim3(nblk(nq, kBlock)), dim3(kBlock), 0, st, T, Q, nq, dist);
 }
 
 }  // namespace lt

@@ -1,15 +1,18 @@
-"""limap.evaluation on the GPU: a drop-in for ``PointCloudEvaluator`` and ``RefLineEvaluator`` (evaluation/bindings.cc of
-limap; method and argument names, and defaults, follow the bindings), plus batched forms and the two helpers of
-scripts/eval_hypersim.py and scripts/eval_tnt.py.
+"""limap.evaluation on the GPU: a drop-in for ``PointCloudEvaluator``, ``RefLineEvaluator`` and ``MeshEvaluator``
+(evaluation/bindings.cc of limap; method and argument names, and defaults, follow the bindings), plus batched forms and
+the two helpers of scripts/eval_hypersim.py and scripts/eval_tnt.py.
 
     from limap_amd import evaluation
     ev = evaluation.PointCloudEvaluator(points)       # (N, 3) array, list of (3,) arrays, or a float32/64 GPU tensor
     ev.Build()
     ratios = ev.ComputeInlierRatios(lines, [0.001, 0.005, 0.01])   # (L, T), one distance pass
+    mesh = evaluation.MeshEvaluator("scene.obj", MPAU)    # .obj / .off, vertices scaled by mpau
+    report = evaluation.report_error_to_GT(mesh, lines, [0.001, 0.005, 0.01])
 
-Every distance is the reference's expression bit for bit; the few host-side reductions
-(ComputeDistLine's sum, the recall length, the segment endpoints) run in the reference's order.  MeshEvaluator is not
-provided.
+Every point-cloud and line distance is the reference's expression bit for bit; the few host-side
+reductions (ComputeDistLine's sum, the recall length, the segment endpoints) run in the reference's order.  The mesh
+distance is Ericson's closest point on a triangle in the FP64 operation order of DESIGN.md section 15, held bit for bit
+to a NumPy restatement in the tests; the reference computes it with libigl, against which no agreement is claimed.
 """
 import ctypes as C
 import hashlib
@@ -21,7 +24,7 @@ import numpy as np
 from . import _capi
 from .base import Line3d
 
-__all__ = ["PointCloudEvaluator", "RefLineEvaluator", "report_error_to_GT", "report_pc_recall_for_GT",
+__all__ = ["PointCloudEvaluator", "RefLineEvaluator", "MeshEvaluator", "report_error_to_GT", "report_pc_recall_for_GT",
            "lines_array", "line_lengths"]
 
 _MAGIC = b"LIMAP_AMD_PCD\x00\x01\x00"  # 16 bytes: name, format version 1
@@ -92,7 +95,57 @@ def _points3(p):
     return q
 
 
-class PointCloudEvaluator:
+class _SampledEvaluator:
+    """the methods of evaluation/base_evaluator.cc over a subclass's ComputeDistPoints and _samples (line samples
+    generated on the device, distances and per-threshold counts)"""
+
+    def ComputeDistPoint(self, point):
+        return float(self.ComputeDistPoints(np.asarray(point, np.float64).reshape(1, 3))[0])
+
+    def _chunk(self, chunk):
+        return int(self.chunk if chunk is None else chunk)
+
+    def ComputeDistLine(self, line, n_samples=1000):
+        """mean distance of n_samples points start + (i / (n - 1)) (end - start), summed in order"""
+        n = int(n_samples)
+        if n <= 2:
+            raise ValueError("n_samples should be >= 3")
+        _check_n(n, 3)
+        d, _ = self._samples(lines_array([line]), 1, n)
+        s = 0.0
+        for v in d[0].tolist():  # std::accumulate: sequential
+            s += v
+        return s / float(n)
+
+    def ComputeInlierRatios(self, lines, thresholds, n_samples=1000, chunk=None):
+        """(L, T) ratios counter / n of samples within (<=) each threshold: one distance pass for all thresholds"""
+        n = _check_n(n_samples)
+        a = lines_array(lines)
+        th = _thresholds(thresholds)
+        if a.shape[0] == 0 or th.size == 0:
+            return np.zeros((a.shape[0], th.size))
+        _, c = self._samples(a, 0, n, th, want_dists=False, chunk=chunk)
+        return c.astype(np.float64) / float(n)
+
+    def ComputeInlierRatio(self, line, threshold, n_samples=1000):
+        return float(self.ComputeInlierRatios([line], [float(threshold)], n_samples)[0, 0])
+
+    def _segs(self, lines, threshold, n_samples, inlier):
+        n = _check_n(n_samples)
+        a = lines_array(lines)
+        if a.shape[0] == 0:
+            return []
+        d, _ = self._samples(a, 0, n)
+        return _segments(a, d, float(threshold), n, inlier)
+
+    def ComputeInlierSegs(self, lines, threshold, n_samples=1000):
+        return self._segs(lines, threshold, n_samples, True)
+
+    def ComputeOutlierSegs(self, lines, threshold, n_samples=1000):
+        return self._segs(lines, threshold, n_samples, False)
+
+
+class PointCloudEvaluator(_SampledEvaluator):
     """evaluation/point_cloud_evaluator.h: nearest-point distances to a GT point cloud, on a device index."""
 
     def __init__(self, points=None, device=0, chunk=0):
@@ -221,12 +274,6 @@ class PointCloudEvaluator:
         ctx.chk(ctx.L.lt_pcd_nearest_dists(ctx.h, pcd, _p(q), q.shape[0], self._chunk(chunk), _p(out)))
         return out[:q.shape[0]]
 
-    def ComputeDistPoint(self, point):
-        return float(self.ComputeDistPoints(np.asarray(point, np.float64).reshape(1, 3))[0])
-
-    def _chunk(self, chunk):
-        return int(self.chunk if chunk is None else chunk)
-
     def _samples(self, a, mode, n, thresholds=None, want_dists=True, chunk=None):
         ctx = self._ctx()
         pcd = self._index()
@@ -239,45 +286,6 @@ class PointCloudEvaluator:
                 ctx.h, pcd, _p(a), L, mode, n, _p(th) if th.size else None, th.size, self._chunk(chunk),
                 _p(dists) if want_dists else None, _p(counts, C.c_int32) if counts is not None else None))
         return (dists[:L] if want_dists else None), (counts[:L, :th.size] if counts is not None else None)
-
-    def ComputeDistLine(self, line, n_samples=1000):
-        """mean distance of n_samples points start + (i / (n - 1)) (end - start), summed in order"""
-        n = int(n_samples)
-        if n <= 2:
-            raise ValueError("n_samples should be >= 3")
-        _check_n(n, 3)
-        d, _ = self._samples(lines_array([line]), 1, n)
-        s = 0.0
-        for v in d[0].tolist():  # std::accumulate: sequential
-            s += v
-        return s / float(n)
-
-    def ComputeInlierRatios(self, lines, thresholds, n_samples=1000, chunk=None):
-        """(L, T) ratios counter / n of samples within (<=) each threshold: one distance pass for all thresholds"""
-        n = _check_n(n_samples)
-        a = lines_array(lines)
-        th = _thresholds(thresholds)
-        if a.shape[0] == 0 or th.size == 0:
-            return np.zeros((a.shape[0], th.size))
-        _, c = self._samples(a, 0, n, th, want_dists=False, chunk=chunk)
-        return c.astype(np.float64) / float(n)
-
-    def ComputeInlierRatio(self, line, threshold, n_samples=1000):
-        return float(self.ComputeInlierRatios([line], [float(threshold)], n_samples)[0, 0])
-
-    def _segs(self, lines, threshold, n_samples, inlier):
-        n = _check_n(n_samples)
-        a = lines_array(lines)
-        if a.shape[0] == 0:
-            return []
-        d, _ = self._samples(a, 0, n)
-        return _segments(a, d, float(threshold), n, inlier)
-
-    def ComputeInlierSegs(self, lines, threshold, n_samples=1000):
-        return self._segs(lines, threshold, n_samples, True)
-
-    def ComputeOutlierSegs(self, lines, threshold, n_samples=1000):
-        return self._segs(lines, threshold, n_samples, False)
 
     def ComputeDistsforEachPoint(self, lines, chunk=None):
         """per cloud point (constructor order): min over the lines of Line3d::point_distance; DBL_MAX without lines"""
@@ -363,6 +371,102 @@ class RefLineEvaluator:
 
     def ComputeRecallTested(self, lines, threshold, num_samples=1000):
         return float(self.ComputeRecallTesteds(lines, [float(threshold)], num_samples)[0])
+
+
+class MeshEvaluator(_SampledEvaluator):
+    """evaluation/mesh_evaluator.h: distances to a GT triangle mesh, on a device triangle index.  The point-to-triangle
+    distance is Ericson's closest point in a stated FP64 operation order; agreement with
+    libigl's point_simplex_squared_distance is not claimed."""
+
+    def __init__(self, filename, mpau, device=0, chunk=0):
+        from .io import read_mesh
+        V, F = read_mesh(filename)
+        self._init(V, F, mpau, device, chunk)
+
+    @classmethod
+    def from_arrays(cls, V, F, mpau=1.0, device=0, chunk=0):
+        """a mesh in memory: V (nv, 3) vertices, F (nf, 3) 0-based vertex indices"""
+        self = cls.__new__(cls)
+        self._init(V, F, mpau, device, chunk)
+        return self
+
+    def _init(self, V, F, mpau, device, chunk):
+        self._mesh = None
+        self.device = int(device)
+        self.chunk = int(chunk)
+        V = np.ascontiguousarray(np.asarray(V, np.float64).reshape(-1, 3))
+        F = np.asarray(F)
+        if F.size and not np.issubdtype(F.dtype, np.integer):
+            raise ValueError("MeshEvaluator: face indices must be integers")
+        F = np.ascontiguousarray(F.astype(np.int64).reshape(-1, 3))
+        self.mpau = float(mpau)
+        if not math.isfinite(self.mpau):
+            raise ValueError("MeshEvaluator: non-finite mpau")
+        if F.shape[0] == 0:
+            raise ValueError("MeshEvaluator: a mesh without faces")
+        if F.min() < 0 or F.max() >= V.shape[0]:
+            raise ValueError(f"MeshEvaluator: face index out of range (vertices: {V.shape[0]})")
+        with np.errstate(over="ignore", invalid="ignore"):
+            if not np.isfinite(V * self.mpau).all():
+                raise ValueError("MeshEvaluator: non-finite vertex coordinate (after scaling by mpau)")
+        self.V, self.F = V, F
+        self.n_vertices, self.n_faces = V.shape[0], F.shape[0]
+
+    def _ctx(self):
+        return _context(self.device)
+
+    def _index(self):
+        if self._mesh is None:
+            ctx = self._ctx()
+            out = C.c_void_p()
+            ctx.chk(ctx.L.lt_mesh_build(ctx.h, self.V.ctypes.data, self.n_vertices, 1, 0, self.F.ctypes.data,
+                                        self.n_faces, self.mpau, C.byref(out)))
+            self._mesh = out
+        return self._mesh
+
+    def Build(self):
+        """(re)builds the device index; the queries build it on first use"""
+        self._free()
+        self._index()
+
+    def _free(self):
+        if getattr(self, "_mesh", None) is not None and self._mesh.value:
+            _capi.load_library().lt_mesh_free(self._mesh)
+        self._mesh = None
+
+    def __del__(self):
+        try:
+            self._free()
+        except Exception:
+            pass
+
+    def ComputeDistPoints(self, points, chunk=None):
+        """ComputeDistPoint for each row of an (M, 3) array"""
+        q = _points3(points)
+        out = np.zeros(max(q.shape[0], 1))
+        ctx = self._ctx()
+        mesh = self._index()
+        ctx.chk(ctx.L.lt_mesh_nearest_dists(ctx.h, mesh, _p(q), q.shape[0], self._chunk(chunk), _p(out)))
+        return out[:q.shape[0]]
+
+    def _samples(self, a, mode, n, thresholds=None, want_dists=True, chunk=None):
+        ctx = self._ctx()
+        mesh = self._index()
+        L = a.shape[0]
+        th = _thresholds(thresholds) if thresholds is not None else np.zeros(0)
+        dists = np.zeros((max(L, 1), n)) if want_dists else None
+        counts = np.zeros((max(L, 1), max(th.size, 1)), np.int32) if th.size else None
+        if L:
+            ctx.chk(ctx.L.lt_mesh_line_samples(
+                ctx.h, mesh, _p(a), L, mode, n, _p(th) if th.size else None, th.size, self._chunk(chunk),
+                _p(dists) if want_dists else None, _p(counts, C.c_int32) if counts is not None else None))
+        return (dists[:L] if want_dists else None), (counts[:L, :th.size] if counts is not None else None)
+
+    def timers(self):
+        out = np.zeros(4)
+        ctx = self._ctx()
+        ctx.chk(ctx.L.lt_eval_get_timers(ctx.h, _p(out)))
+        return out
 
 
 # ---- scripts/eval_hypersim.py:47-68, scripts/eval_tnt.py:22-59 ----------------------------------------------------------

@@ -308,3 +308,82 @@ def triangulate_scene_folder(imagecols_npy, metainfos_txt, segments_folder, matc
     else:  # the whole loop of runners/line_triangulation.py:160-167 in one native call
         T.TriangulateAll({i: read_matches(matches_folder, i) for i in imagecols.get_img_ids()})
     return T, T.ComputeLineTracks()
+
+
+# ---- GT meshes (evaluation/mesh_evaluator.cc reads them with libigl's readOBJ / readOFF) --------------------------------
+def _fan(corners, where):
+    if len(corners) < 3:
+        raise ValueError(f"{where}: a face needs at least 3 corners, got {len(corners)}")
+    # a polygon of k > 3 corners becomes the fan (c0, c[j], c[j + 1]) of its first corner (this project's choice)
+    return [(corners[0], corners[j], corners[j + 1]) for j in range(1, len(corners) - 1)]
+
+
+def _read_obj(fname):
+    V, F = [], []
+    with open(fname) as f:
+        for ln, line in enumerate(f, 1):
+            tok = line.split("#", 1)[0].split()
+            if not tok:
+                continue
+            if tok[0] == "v":
+                if len(tok) < 4:
+                    raise ValueError(f"{fname}:{ln}: a vertex needs x y z")
+                V.append([float(t) for t in tok[1:4]])  # an optional w is ignored
+            elif tok[0] == "f":
+                corners = []
+                for t in tok[1:]:
+                    i = int(t.split("/", 1)[0])  # i, i/t, i//n, i/t/n
+                    if i == 0:
+                        raise ValueError(f"{fname}:{ln}: face index 0 (indices start at 1)")
+                    corners.append(i - 1 if i > 0 else len(V) + i)  # negative: counted back from the vertices so far
+                F.extend(_fan(corners, f"{fname}:{ln}"))
+            # vt, vn, l, o, g, s, usemtl, mtllib and anything else: not part of the triangle mesh
+    return V, F
+
+
+def _read_off(fname):
+    with open(fname) as f:
+        lines = [t for t in (line.split("#", 1)[0].split() for line in f) if t]
+    if not lines or not lines[0][0].endswith("OFF"):
+        raise ValueError(f"{fname}: not an OFF file (no OFF header)")
+    if lines[0][0] != "OFF":
+        raise ValueError(f"{fname}: only the plain OFF variant is read, got {lines[0][0]}")
+    head, k = (lines[0][1:], 1) if len(lines[0]) > 1 else (lines[1] if len(lines) > 1 else [], 2)
+    if len(head) < 2:
+        raise ValueError(f"{fname}: missing the vertex and face counts")
+    nv, nf = int(head[0]), int(head[1])
+    if nv < 0 or nf < 0 or len(lines) < k + nv + nf:
+        raise ValueError(f"{fname}: fewer vertex or face lines than the counts promise")
+    V = [[float(t) for t in lines[k + i][:3]] for i in range(nv)]
+    if any(len(v) != 3 for v in V):
+        raise ValueError(f"{fname}: a vertex needs x y z")
+    F = []
+    for i in range(nf):
+        row = lines[k + nv + i]
+        c = int(row[0])
+        if len(row) < 1 + c:
+            raise ValueError(f"{fname}: face {i} lists fewer than its {c} corners")
+        F.extend(_fan([int(t) for t in row[1:1 + c]], f"{fname}: face {i}"))  # 0-based; trailing colours ignored
+    return V, F
+
+
+def read_mesh(fname):
+    """A triangle mesh from .obj or .off -> (V float64 (nv, 3), F int64 (nf, 3), 0-based).  Polygons are fanned from
+    their first corner.  Raises for another extension (the reference throws "Not Implemented!!"), a file without faces
+    (e.g. a line map written by save_obj), a face index out of range and a non-finite coordinate."""
+    ext = str(fname).rsplit(".", 1)[-1]
+    if ext == "obj":
+        V, F = _read_obj(fname)
+    elif ext == "off":
+        V, F = _read_off(fname)
+    else:
+        raise NotImplementedError(f"{fname}: only .obj and .off meshes are read (the reference: Not Implemented!!)")
+    V = np.array(V, np.float64).reshape(-1, 3)
+    F = np.array(F, np.int64).reshape(-1, 3)
+    if F.shape[0] == 0:
+        raise ValueError(f"{fname}: the file holds no faces")
+    if F.min() < 0 or F.max() >= V.shape[0]:
+        raise ValueError(f"{fname}: face index out of range (vertices: {V.shape[0]})")
+    if not np.isfinite(V).all():
+        raise ValueError(f"{fname}: non-finite vertex coordinate")
+    return V, F
