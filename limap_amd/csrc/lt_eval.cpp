@@ -18,6 +18,7 @@ using namespace lt;
 using lt_impl::now_ms;
 
 struct lt_pcd {
+  static constexpr const char *noun = "index";  // of the messages about the handle
   int device = 0;
   long long n = 0;
   DevBuf x, y, z, box, perm;
@@ -25,6 +26,7 @@ struct lt_pcd {
 };
 
 struct lt_mesh {
+  static constexpr const char *noun = "mesh";
   int device = 0;
   long long n = 0;  // faces
   DevBuf faces, box, eta, perm;
@@ -76,17 +78,12 @@ int upload_lines(lt_ctx *ctx, DevBuf &buf, const std::vector<EvalLine> &v) {
   return LT_OK;
 }
 
-int check_pcd(lt_ctx *ctx, const char *who, const lt_pcd *pcd) {
-  if (!pcd) return fail(ctx, LT_ERR_ARGUMENT, std::string(who) + ": null index");
-  if (pcd->device != ctx->device)
-    return fail(ctx, LT_ERR_ARGUMENT, std::string(who) + ": the index lives on another device than the context");
-  return LT_OK;
-}
-
-int check_mesh(lt_ctx *ctx, const char *who, const lt_mesh *mesh) {
-  if (!mesh) return fail(ctx, LT_ERR_ARGUMENT, std::string(who) + ": null mesh");
-  if (mesh->device != ctx->device)
-    return fail(ctx, LT_ERR_ARGUMENT, std::string(who) + ": the mesh lives on another device than the context");
+template <class Handle>
+int check_handle(lt_ctx *ctx, const char *who, const Handle *h) {
+  if (!h) return fail(ctx, LT_ERR_ARGUMENT, std::string(who) + ": null " + Handle::noun);
+  if (h->device != ctx->device)
+    return fail(ctx, LT_ERR_ARGUMENT,
+                std::string(who) + ": the " + Handle::noun + " lives on another device than the context");
   return LT_OK;
 }
 
@@ -122,6 +119,142 @@ struct Timer {  // HIP events around the kernels of one call
     return LT_OK;
   }
 };
+
+// the nearest-distance launch of an index: (stream, queries, their number, distances out)
+auto pcd_launch(const lt_pcd *pcd) {
+  return [pcd](hipStream_t st, const EvalQuery &Q, long long nq, double *dist) {
+    launch_eval_nearest(st, pcd->tree, Q, nq, dist);
+  };
+}
+
+auto mesh_launch(const lt_mesh *mesh) {
+  const int brute = mesh_brute();
+  return [mesh, brute](hipStream_t st, const EvalQuery &Q, long long nq, double *dist) {
+    launch_mesh_nearest(st, mesh->tree, Q, nq, brute, dist);
+  };
+}
+
+// the Morton order of n device points: bounding box -> 21-bit quantisation per axis -> 63-bit Morton keys -> rocprim
+// radix sort.  Scratch, carved at 256 bytes: six ordered keys of the box, Morton keys in and out, indices in, the sort's.
+struct MortonOrder {
+  long long n;
+  size_t kb, ib, tmp;
+  char *scr = nullptr;
+  explicit MortonOrder(long long n_)
+      : n(n_), kb(((size_t)n_ * 8 + 255) & ~(size_t)255), ib(((size_t)n_ * 4 + 255) & ~(size_t)255),
+        tmp(eval_sort_temp_bytes(n_)) {}
+  size_t bytes() const { return 256 + 2 * kb + ib + std::max<size_t>(tmp, 16); }
+  // takes the scratch and uploads the box's initial keys: the last of a build's uploads, before its first kernel
+  hipError_t prime(hipStream_t st, char *scratch) {
+    static const unsigned long long init[6] = {~0ull, ~0ull, ~0ull, 0, 0, 0};
+    scr = scratch;
+    return hipMemcpyAsync(scr, init, 48, hipMemcpyHostToDevice, st);
+  }
+  // the order into perm.  Synchronises the stream once (the box comes to the host); the sort is left in flight.
+  int run(lt_ctx *ctx, const char *who, const void *xyz, int dtype, unsigned *perm, int *launches) const {
+    hipStream_t st = ctx->stream;
+    unsigned long long *box6 = reinterpret_cast<unsigned long long *>(scr);
+    unsigned long long *k_in = reinterpret_cast<unsigned long long *>(scr + 256);
+    unsigned long long *k_out = reinterpret_cast<unsigned long long *>(scr + 256 + kb);
+    unsigned *i_in = reinterpret_cast<unsigned *>(scr + 256 + 2 * kb);
+    launch_eval_bbox(st, xyz, dtype, n, box6);
+    unsigned long long got[6];
+    if (hipMemcpyAsync(got, box6, 48, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+      return fail(ctx, LT_ERR_HIP, std::string(who) + ": bounding box failed");
+    double lo[3], scale[3];
+    for (int k = 0; k < 3; ++k) {
+      auto dec = [](unsigned long long u) {
+        u = (u >> 63) ? (u & 0x7fffffffffffffffull) : ~u;
+        double v;
+        std::memcpy(&v, &u, 8);
+        return v;
+      };
+      lo[k] = dec(got[k]);
+      const double ext = dec(got[3 + k]) - lo[k];
+      scale[k] = (ext > 0.0 && std::isfinite(ext)) ? 2097151.0 / ext : 0.0;
+    }
+    launch_eval_morton(st, xyz, dtype, n, lo, scale, k_in, i_in);
+    if (launch_eval_sort(st, scr + 256 + 2 * kb + ib, tmp, n, k_in, k_out, i_in, perm) != 0)
+      return fail(ctx, LT_ERR_HIP, "rocprim radix sort failed");
+    *launches += 3;
+    return LT_OK;
+  }
+};
+
+// nearest distances of free points, in chunks
+template <class Launch>
+int nearest_dists(lt_ctx *ctx, const char *who, const double *query, int64_t n, int64_t chunk, double *dist,
+                  Launch launch) {
+  if (n < 0 || (n > 0 && (!query || !dist))) return fail(ctx, LT_ERR_ARGUMENT, std::string(who) + ": bad arguments");
+  if (int rc = check_finite(ctx, who, query, 3 * n, "query coordinate")) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  Timer tm;
+  if (int rc = tm.start(ctx)) return rc;
+  const long long C = chunk_of(chunk);
+  ENSURE(ctx, ctx->d_ev_in, 24 * (size_t)std::min<long long>(std::max<long long>(n, 1), C));
+  ENSURE(ctx, ctx->d_ev_out, 8 * (size_t)std::min<long long>(std::max<long long>(n, 1), C));
+  for (long long q0 = 0; q0 < n; q0 += C) {
+    const long long m = std::min<long long>(C, n - q0);
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_ev_in.p, query + 3 * q0, 24 * (size_t)m, hipMemcpyHostToDevice, st));
+    EvalQuery Q{};
+    const double *d = ctx->d_ev_in.as<double>();
+    Q.x = d; Q.y = d + 1; Q.z = d + 2; Q.stride = 3; Q.mode = EV_Q_POINTS; Q.n = 1;
+    launch(st, Q, m, ctx->d_ev_out.as<double>());
+    ++tm.launches;
+    HIPCHK(ctx, hipMemcpyAsync(dist + q0, ctx->d_ev_out.p, 8 * (size_t)m, hipMemcpyDeviceToHost, st));
+  }
+  return tm.finish(ctx, 0);
+}
+
+// nearest distances of the samples of lines, whole lines per launch, with optional per-threshold counts
+template <class Launch>
+int line_samples(lt_ctx *ctx, const char *who, const double *lines, int64_t n_lines, int mode, int n_samples,
+                 const double *thresholds, int n_th, int64_t chunk, double *dists, int32_t *counts, Launch launch) {
+  const std::string w(who);
+  if (mode != LT_SAMPLE_CENTER && mode != LT_SAMPLE_ENDS) return fail(ctx, LT_ERR_ARGUMENT, w + ": bad mode");
+  if (n_samples < (mode == LT_SAMPLE_ENDS ? 2 : 1))
+    return fail(ctx, LT_ERR_ARGUMENT, w + ": n_samples must be >= 1 (>= 2 for end-point sampling)");
+  if (n_th < 0 || n_th > kEvalMaxTh || (n_th > 0 && !thresholds))
+    return fail(ctx, LT_ERR_ARGUMENT, w + ": between 0 and 64 thresholds");
+  if (n_lines < 0 || (n_lines > 0 && !lines)) return fail(ctx, LT_ERR_ARGUMENT, w + ": bad lines");
+  if (counts && n_th == 0) counts = nullptr;
+  if (int rc = check_finite(ctx, who, lines, 6 * n_lines, "line coordinate")) return rc;
+  if (n_lines == 0 || (!dists && !counts)) return LT_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  Timer tm;
+  if (int rc = tm.start(ctx)) return rc;
+  const auto L = prep_lines(lines, n_lines, 0);
+  if (int rc = upload_lines(ctx, ctx->d_ev_lines, L)) return rc;
+  ENSURE(ctx, ctx->d_ev_th, 8 * (size_t)std::max(n_th, 1));
+  if (n_th) HIPCHK(ctx, hipMemcpyAsync(ctx->d_ev_th.p, thresholds, 8 * (size_t)n_th, hipMemcpyHostToDevice, st));
+  const long long per = std::max<long long>(1, chunk_of(chunk) / n_samples);  // whole lines per launch
+  const long long lc = std::min<long long>(per, n_lines);
+  ENSURE(ctx, ctx->d_ev_out, 8 * (size_t)(lc * n_samples));
+  if (counts) ENSURE(ctx, ctx->d_ev_cnt, 4 * (size_t)(n_lines * n_th));
+  EvalQuery Q{};
+  Q.mode = mode == LT_SAMPLE_CENTER ? EV_Q_CENTER : EV_Q_ENDS;
+  Q.n = n_samples;
+  Q.interval = mode == LT_SAMPLE_CENTER ? 1.0 / n_samples : 1.0 / (n_samples - 1);
+  for (long long l0 = 0; l0 < n_lines; l0 += per) {
+    const long long m = std::min<long long>(per, n_lines - l0);
+    Q.lines = ctx->d_ev_lines.as<EvalLine>() + l0;
+    launch(st, Q, m * n_samples, ctx->d_ev_out.as<double>());
+    ++tm.launches;
+    if (counts) {
+      launch_eval_count(st, ctx->d_ev_out.as<double>(), m, n_samples, ctx->d_ev_th.as<double>(), n_th, 1,
+                        ctx->d_ev_cnt.as<int>() + l0 * n_th);
+      ++tm.launches;
+    }
+    if (dists)
+      HIPCHK(ctx, hipMemcpyAsync(dists + l0 * n_samples, ctx->d_ev_out.p, 8 * (size_t)(m * n_samples),
+                                 hipMemcpyDeviceToHost, st));
+  }
+  if (counts)
+    HIPCHK(ctx, hipMemcpyAsync(counts, ctx->d_ev_cnt.p, 4 * (size_t)(n_lines * n_th), hipMemcpyDeviceToHost, st));
+  return tm.finish(ctx, 0);
+}
 
 }  // namespace
 
@@ -169,62 +302,22 @@ int lt_pcd_build(lt_ctx *ctx, const void *xyz, int64_t n, int dtype, int on_devi
       return bail(fail(ctx, LT_ERR_HIP, "lt_pcd_build: upload failed"));
     src = ctx->d_ev_in.p;
   }
-  // the levels: buckets of 32 points, then fanout 8 up to one root
   EvalTree &T = p->tree;
-  T.n = n;
-  long long cnt = (n + kEvalBucket - 1) / kEvalBucket, off = 0;
-  int l = 0;
-  for (;; ++l) {
-    T.lvl_off[l] = off;
-    T.lvl_n[l] = cnt;
-    off += cnt;
-    if (cnt == 1) break;
-    cnt = (cnt + kEvalFanout - 1) / kEvalFanout;
-  }
-  T.top = l;
-  T.total = off;
-  for (int k = l + 1; k < kEvalMaxLevels; ++k) T.lvl_off[k] = T.lvl_n[k] = 0;
+  T.L = eval_levels(n, kEvalBucket);
   if (!p->x.ensure(8 * (size_t)n) || !p->y.ensure(8 * (size_t)n) || !p->z.ensure(8 * (size_t)n) ||
-      !p->box.ensure(48 * (size_t)T.total) || !p->perm.ensure(4 * (size_t)n))
+      !p->box.ensure(48 * (size_t)T.L.total) || !p->perm.ensure(4 * (size_t)n))
     return bail(fail(ctx, LT_ERR_HIP, "hipMalloc failed for the point index"));
   if (perm) {
     if (hipMemcpyAsync(p->perm.p, perm, 4 * (size_t)n, hipMemcpyHostToDevice, st) != hipSuccess)
       return bail(fail(ctx, LT_ERR_HIP, "lt_pcd_build: upload of the order failed"));
   } else {
-    // bounding box -> 21-bit quantisation per axis -> 63-bit Morton keys -> rocprim radix sort
     DevBuf keys;
-    const size_t tmp = eval_sort_temp_bytes(n);
-    const size_t kb = ((size_t)n * 8 + 255) & ~(size_t)255, ib = ((size_t)n * 4 + 255) & ~(size_t)255;
-    if (!keys.ensure(256 + 2 * kb + ib + std::max<size_t>(tmp, 16)))
+    MortonOrder order(n);
+    if (!keys.ensure(order.bytes()))
       return bail(fail(ctx, LT_ERR_HIP, "hipMalloc failed for the sort of the point index"));
-    char *kp = keys.as<char>();
-    unsigned long long *box6 = reinterpret_cast<unsigned long long *>(kp);
-    unsigned long long *k_in = reinterpret_cast<unsigned long long *>(kp + 256);
-    unsigned long long *k_out = reinterpret_cast<unsigned long long *>(kp + 256 + kb);
-    unsigned *i_in = reinterpret_cast<unsigned *>(kp + 256 + 2 * kb);
-    const unsigned long long init[6] = {~0ull, ~0ull, ~0ull, 0, 0, 0};
-    if (hipMemcpyAsync(box6, init, 48, hipMemcpyHostToDevice, st) != hipSuccess)
+    if (order.prime(st, keys.as<char>()) != hipSuccess)
       return bail(fail(ctx, LT_ERR_HIP, "lt_pcd_build: memcpy failed"));
-    launch_eval_bbox(st, src, dtype, n, box6);
-    unsigned long long got[6];
-    if (hipMemcpyAsync(got, box6, 48, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-      return bail(fail(ctx, LT_ERR_HIP, "lt_pcd_build: bounding box failed"));
-    double lo[3], scale[3];
-    for (int k = 0; k < 3; ++k) {
-      auto dec = [](unsigned long long u) {
-        u = (u >> 63) ? (u & 0x7fffffffffffffffull) : ~u;
-        double v;
-        std::memcpy(&v, &u, 8);
-        return v;
-      };
-      lo[k] = dec(got[k]);
-      const double ext = dec(got[3 + k]) - lo[k];
-      scale[k] = (ext > 0.0 && std::isfinite(ext)) ? 2097151.0 / ext : 0.0;
-    }
-    launch_eval_morton(st, src, dtype, n, lo, scale, k_in, i_in);
-    if (launch_eval_sort(st, kp + 256 + 2 * kb + ib, tmp, n, k_in, k_out, i_in, p->perm.as<unsigned>()) != 0)
-      return bail(fail(ctx, LT_ERR_HIP, "rocprim radix sort failed"));
-    tm.launches += 3;
+    if (int rc = order.run(ctx, "lt_pcd_build", src, dtype, p->perm.as<unsigned>(), &tm.launches)) return bail(rc);
     if (hipStreamSynchronize(st) != hipSuccess) return bail(fail(ctx, LT_ERR_HIP, "lt_pcd_build: sort failed"));
   }
   T.x = p->x.as<double>();
@@ -234,8 +327,8 @@ int lt_pcd_build(lt_ctx *ctx, const void *xyz, int64_t n, int dtype, int on_devi
   launch_eval_gather(st, src, dtype, n, p->perm.as<unsigned>(), p->x.as<double>(), p->y.as<double>(),
                      p->z.as<double>());
   launch_eval_boxes(st, T, p->box.as<double>());
-  tm.launches += 2 + T.top;
-  if (int rc = tm.finish(ctx, T.top + 1)) return bail(rc);
+  tm.launches += 2 + T.L.top;
+  if (int rc = tm.finish(ctx, T.L.top + 1)) return bail(rc);
   *out = p;
   return LT_OK;
 }
@@ -248,7 +341,7 @@ void lt_pcd_free(lt_pcd *pcd) {
 }
 
 int lt_pcd_get_perm(lt_ctx *ctx, const lt_pcd *pcd, uint32_t *perm) {
-  if (int rc = check_pcd(ctx, "lt_pcd_get_perm", pcd)) return rc;
+  if (int rc = check_handle(ctx, "lt_pcd_get_perm", pcd)) return rc;
   if (!perm) return fail(ctx, LT_ERR_ARGUMENT, "lt_pcd_get_perm: null output");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   HIPCHK(ctx, hipMemcpyAsync(perm, pcd->perm.p, 4 * (size_t)pcd->n, hipMemcpyDeviceToHost, ctx->stream));
@@ -259,27 +352,9 @@ int lt_pcd_get_perm(lt_ctx *ctx, const lt_pcd *pcd, uint32_t *perm) {
 int lt_pcd_nearest_dists(lt_ctx *ctx, const lt_pcd *pcd, const double *query, int64_t n, int64_t chunk,
                          double *dist) {
   if (!ctx) return LT_ERR_ARGUMENT;
-  if (int rc = check_pcd(ctx, "lt_pcd_nearest_dists", pcd)) return rc;
-  if (n < 0 || (n > 0 && (!query || !dist))) return fail(ctx, LT_ERR_ARGUMENT, "lt_pcd_nearest_dists: bad arguments");
-  if (int rc = check_finite(ctx, "lt_pcd_nearest_dists", query, 3 * n, "query coordinate")) return rc;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  Timer tm;
-  if (int rc = tm.start(ctx)) return rc;
-  const long long C = chunk_of(chunk);
-  ENSURE(ctx, ctx->d_ev_in, 24 * (size_t)std::min<long long>(std::max<long long>(n, 1), C));
-  ENSURE(ctx, ctx->d_ev_out, 8 * (size_t)std::min<long long>(std::max<long long>(n, 1), C));
-  for (long long q0 = 0; q0 < n; q0 += C) {
-    const long long m = std::min<long long>(C, n - q0);
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_ev_in.p, query + 3 * q0, 24 * (size_t)m, hipMemcpyHostToDevice, st));
-    EvalQuery Q{};
-    const double *d = ctx->d_ev_in.as<double>();
-    Q.x = d; Q.y = d + 1; Q.z = d + 2; Q.stride = 3; Q.mode = EV_Q_POINTS; Q.n = 1;
-    launch_eval_nearest(st, pcd->tree, Q, m, ctx->d_ev_out.as<double>());
-    ++tm.launches;
-    HIPCHK(ctx, hipMemcpyAsync(dist + q0, ctx->d_ev_out.p, 8 * (size_t)m, hipMemcpyDeviceToHost, st));
-  }
-  return tm.finish(ctx, 0);
+  const char *who = "lt_pcd_nearest_dists";
+  if (int rc = check_handle(ctx, who, pcd)) return rc;
+  return nearest_dists(ctx, who, query, n, chunk, dist, pcd_launch(pcd));
 }
 
 int lt_pcd_line_samples(lt_ctx *ctx, const lt_pcd *pcd, const double *lines, int64_t n_lines, int mode,
@@ -287,56 +362,16 @@ int lt_pcd_line_samples(lt_ctx *ctx, const lt_pcd *pcd, const double *lines, int
                         int32_t *counts) {
   if (!ctx) return LT_ERR_ARGUMENT;
   const char *who = "lt_pcd_line_samples";
-  if (int rc = check_pcd(ctx, who, pcd)) return rc;
-  if (mode != LT_SAMPLE_CENTER && mode != LT_SAMPLE_ENDS) return fail(ctx, LT_ERR_ARGUMENT, "lt_pcd_line_samples: bad mode");
-  if (n_samples < (mode == LT_SAMPLE_ENDS ? 2 : 1))
-    return fail(ctx, LT_ERR_ARGUMENT, "lt_pcd_line_samples: n_samples must be >= 1 (>= 2 for end-point sampling)");
-  if (n_th < 0 || n_th > kEvalMaxTh || (n_th > 0 && !thresholds))
-    return fail(ctx, LT_ERR_ARGUMENT, "lt_pcd_line_samples: between 0 and 64 thresholds");
-  if (n_lines < 0 || (n_lines > 0 && !lines)) return fail(ctx, LT_ERR_ARGUMENT, "lt_pcd_line_samples: bad lines");
-  if (counts && n_th == 0) counts = nullptr;
-  if (int rc = check_finite(ctx, who, lines, 6 * n_lines, "line coordinate")) return rc;
-  if (n_lines == 0 || (!dists && !counts)) return LT_OK;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  Timer tm;
-  if (int rc = tm.start(ctx)) return rc;
-  const auto L = prep_lines(lines, n_lines, 0);
-  if (int rc = upload_lines(ctx, ctx->d_ev_lines, L)) return rc;
-  ENSURE(ctx, ctx->d_ev_th, 8 * (size_t)std::max(n_th, 1));
-  if (n_th) HIPCHK(ctx, hipMemcpyAsync(ctx->d_ev_th.p, thresholds, 8 * (size_t)n_th, hipMemcpyHostToDevice, st));
-  const long long per = std::max<long long>(1, chunk_of(chunk) / n_samples);  // whole lines per launch
-  const long long lc = std::min<long long>(per, n_lines);
-  ENSURE(ctx, ctx->d_ev_out, 8 * (size_t)(lc * n_samples));
-  if (counts) ENSURE(ctx, ctx->d_ev_cnt, 4 * (size_t)(n_lines * n_th));
-  EvalQuery Q{};
-  Q.mode = mode == LT_SAMPLE_CENTER ? EV_Q_CENTER : EV_Q_ENDS;
-  Q.n = n_samples;
-  Q.interval = mode == LT_SAMPLE_CENTER ? 1.0 / n_samples : 1.0 / (n_samples - 1);
-  for (long long l0 = 0; l0 < n_lines; l0 += per) {
-    const long long m = std::min<long long>(per, n_lines - l0);
-    Q.lines = ctx->d_ev_lines.as<EvalLine>() + l0;
-    launch_eval_nearest(st, pcd->tree, Q, m * n_samples, ctx->d_ev_out.as<double>());
-    ++tm.launches;
-    if (counts) {
-      launch_eval_count(st, ctx->d_ev_out.as<double>(), m, n_samples, ctx->d_ev_th.as<double>(), n_th, 1,
-                        ctx->d_ev_cnt.as<int>() + l0 * n_th);
-      ++tm.launches;
-    }
-    if (dists)
-      HIPCHK(ctx, hipMemcpyAsync(dists + l0 * n_samples, ctx->d_ev_out.p, 8 * (size_t)(m * n_samples),
-                                 hipMemcpyDeviceToHost, st));
-  }
-  if (counts)
-    HIPCHK(ctx, hipMemcpyAsync(counts, ctx->d_ev_cnt.p, 4 * (size_t)(n_lines * n_th), hipMemcpyDeviceToHost, st));
-  return tm.finish(ctx, 0);
+  if (int rc = check_handle(ctx, who, pcd)) return rc;
+  return line_samples(ctx, who, lines, n_lines, mode, n_samples, thresholds, n_th, chunk, dists, counts,
+                      pcd_launch(pcd));
 }
 
 int lt_lines_point_dists(lt_ctx *ctx, const lt_pcd *pcd, const double *lines, int64_t n_lines, int64_t chunk,
                          double *dist) {
   if (!ctx) return LT_ERR_ARGUMENT;
   const char *who = "lt_lines_point_dists";
-  if (int rc = check_pcd(ctx, who, pcd)) return rc;
+  if (int rc = check_handle(ctx, who, pcd)) return rc;
   if (!dist || n_lines < 0 || (n_lines > 0 && !lines)) return fail(ctx, LT_ERR_ARGUMENT, "lt_lines_point_dists: bad arguments");
   if (int rc = check_finite(ctx, who, lines, 6 * n_lines, "line coordinate")) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -447,63 +482,27 @@ int lt_mesh_build(lt_ctx *ctx, const void *V, int64_t nv, int dtype, int on_devi
     return rc;
   };
   MeshTree &T = m->tree;
-  T.n = nf;
+  T.L = eval_levels(nf, bucket);
   T.bucket = bucket;
-  long long cnt = (nf + bucket - 1) / bucket, off = 0;
-  int l = 0;
-  for (;; ++l) {
-    T.lvl_off[l] = off;
-    T.lvl_n[l] = cnt;
-    off += cnt;
-    if (cnt == 1) break;
-    cnt = (cnt + kEvalFanout - 1) / kEvalFanout;
-  }
-  T.top = l;
-  T.total = off;
-  for (int k = l + 1; k < kEvalMaxLevels; ++k) T.lvl_off[k] = T.lvl_n[k] = 0;
-  // scratch: vertices, faces, centroids, Morton keys and the sort
+  // scratch: vertices, faces and centroids, then the order's
+  MortonOrder order(nf);
   const size_t vb = ((size_t)nv * 24 + 255) & ~(size_t)255, fb = ((size_t)nf * 24 + 255) & ~(size_t)255;
-  const size_t kb = ((size_t)nf * 8 + 255) & ~(size_t)255, ib = ((size_t)nf * 4 + 255) & ~(size_t)255;
-  const size_t tmp = eval_sort_temp_bytes(nf);
   DevBuf scr;
-  if (!scr.ensure(256 + vb + 2 * fb + 2 * kb + ib + std::max<size_t>(tmp, 16)) || !m->faces.ensure(72 * (size_t)nf) ||
-      !m->box.ensure(48 * (size_t)T.total) || !m->eta.ensure(8 * (size_t)T.total) || !m->perm.ensure(4 * (size_t)nf))
+  if (!scr.ensure(vb + 2 * fb + order.bytes()) || !m->faces.ensure(72 * (size_t)nf) ||
+      !m->box.ensure(48 * (size_t)T.L.total) || !m->eta.ensure(8 * (size_t)T.L.total) ||
+      !m->perm.ensure(4 * (size_t)nf))
     return bail(fail(ctx, LT_ERR_HIP, "hipMalloc failed for the mesh index"));
   char *sp = scr.as<char>();
-  unsigned long long *box6 = reinterpret_cast<unsigned long long *>(sp);
-  double *dV = reinterpret_cast<double *>(sp + 256);
-  long long *dF = reinterpret_cast<long long *>(sp + 256 + vb);
-  double *cen = reinterpret_cast<double *>(sp + 256 + vb + fb);
-  unsigned long long *k_in = reinterpret_cast<unsigned long long *>(sp + 256 + vb + 2 * fb);
-  unsigned long long *k_out = reinterpret_cast<unsigned long long *>(sp + 256 + vb + 2 * fb + kb);
-  unsigned *i_in = reinterpret_cast<unsigned *>(sp + 256 + vb + 2 * fb + 2 * kb);
-  void *sort_tmp = sp + 256 + vb + 2 * fb + 2 * kb + ib;
-  const unsigned long long init[6] = {~0ull, ~0ull, ~0ull, 0, 0, 0};
+  double *dV = reinterpret_cast<double *>(sp);
+  long long *dF = reinterpret_cast<long long *>(sp + vb);
+  double *cen = reinterpret_cast<double *>(sp + vb + fb);
   if (hipMemcpyAsync(dV, Vs.data(), 24 * (size_t)nv, hipMemcpyHostToDevice, st) != hipSuccess ||
       hipMemcpyAsync(dF, F, 24 * (size_t)nf, hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemcpyAsync(box6, init, 48, hipMemcpyHostToDevice, st) != hipSuccess)
+      order.prime(st, sp + vb + 2 * fb) != hipSuccess)
     return bail(fail(ctx, LT_ERR_HIP, "lt_mesh_build: upload failed"));
-  // the order: the point index's bounding box, Morton keys and radix sort, over the face centroids
+  // the order: the point index's, over the face centroids
   launch_mesh_centroids(st, dV, dF, nf, cen);
-  launch_eval_bbox(st, cen, 1, nf, box6);
-  unsigned long long got[6];
-  if (hipMemcpyAsync(got, box6, 48, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-    return bail(fail(ctx, LT_ERR_HIP, "lt_mesh_build: bounding box failed"));
-  double lo[3], sc[3];
-  for (int k = 0; k < 3; ++k) {
-    auto dec = [](unsigned long long u) {
-      u = (u >> 63) ? (u & 0x7fffffffffffffffull) : ~u;
-      double v;
-      std::memcpy(&v, &u, 8);
-      return v;
-    };
-    lo[k] = dec(got[k]);
-    const double ext = dec(got[3 + k]) - lo[k];
-    sc[k] = (ext > 0.0 && std::isfinite(ext)) ? 2097151.0 / ext : 0.0;
-  }
-  launch_eval_morton(st, cen, 1, nf, lo, sc, k_in, i_in);
-  if (launch_eval_sort(st, sort_tmp, tmp, nf, k_in, k_out, i_in, m->perm.as<unsigned>()) != 0)
-    return bail(fail(ctx, LT_ERR_HIP, "rocprim radix sort failed"));
+  if (int rc = order.run(ctx, who, cen, 1, m->perm.as<unsigned>(), &tm.launches)) return bail(rc);
   double *fa[9];
   for (int k = 0; k < 9; ++k) {
     fa[k] = m->faces.as<double>() + (size_t)k * nf;
@@ -513,8 +512,8 @@ int lt_mesh_build(lt_ctx *ctx, const void *V, int64_t nv, int dtype, int on_devi
   T.eta = m->eta.as<double>();
   launch_mesh_gather(st, dV, dF, nf, m->perm.as<unsigned>(), fa);
   launch_mesh_boxes(st, T, m->box.as<double>(), m->eta.as<double>());
-  tm.launches += 6 + 2 * T.top;
-  if (int rc = tm.finish(ctx, T.top + 1)) return bail(rc);  // (the scratch returns to the cache after the sync)
+  tm.launches += 3 + 2 * T.L.top;
+  if (int rc = tm.finish(ctx, T.L.top + 1)) return bail(rc);  // (the scratch returns to the cache after the sync)
   *out = m;
   return LT_OK;
 }
@@ -529,28 +528,9 @@ void lt_mesh_free(lt_mesh *mesh) {
 int lt_mesh_nearest_dists(lt_ctx *ctx, const lt_mesh *mesh, const double *query, int64_t n, int64_t chunk,
                           double *dist) {
   if (!ctx) return LT_ERR_ARGUMENT;
-  if (int rc = check_mesh(ctx, "lt_mesh_nearest_dists", mesh)) return rc;
-  if (n < 0 || (n > 0 && (!query || !dist))) return fail(ctx, LT_ERR_ARGUMENT, "lt_mesh_nearest_dists: bad arguments");
-  if (int rc = check_finite(ctx, "lt_mesh_nearest_dists", query, 3 * n, "query coordinate")) return rc;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const int brute = mesh_brute();
-  Timer tm;
-  if (int rc = tm.start(ctx)) return rc;
-  const long long C = chunk_of(chunk);
-  ENSURE(ctx, ctx->d_ev_in, 24 * (size_t)std::min<long long>(std::max<long long>(n, 1), C));
-  ENSURE(ctx, ctx->d_ev_out, 8 * (size_t)std::min<long long>(std::max<long long>(n, 1), C));
-  for (long long q0 = 0; q0 < n; q0 += C) {
-    const long long m = std::min<long long>(C, n - q0);
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_ev_in.p, query + 3 * q0, 24 * (size_t)m, hipMemcpyHostToDevice, st));
-    EvalQuery Q{};
-    const double *d = ctx->d_ev_in.as<double>();
-    Q.x = d; Q.y = d + 1; Q.z = d + 2; Q.stride = 3; Q.mode = EV_Q_POINTS; Q.n = 1;
-    launch_mesh_nearest(st, mesh->tree, Q, m, brute, ctx->d_ev_out.as<double>());
-    ++tm.launches;
-    HIPCHK(ctx, hipMemcpyAsync(dist + q0, ctx->d_ev_out.p, 8 * (size_t)m, hipMemcpyDeviceToHost, st));
-  }
-  return tm.finish(ctx, 0);
+  const char *who = "lt_mesh_nearest_dists";
+  if (int rc = check_handle(ctx, who, mesh)) return rc;
+  return nearest_dists(ctx, who, query, n, chunk, dist, mesh_launch(mesh));
 }
 
 int lt_mesh_line_samples(lt_ctx *ctx, const lt_mesh *mesh, const double *lines, int64_t n_lines, int mode,
@@ -558,50 +538,9 @@ int lt_mesh_line_samples(lt_ctx *ctx, const lt_mesh *mesh, const double *lines, 
                          int32_t *counts) {
   if (!ctx) return LT_ERR_ARGUMENT;
   const char *who = "lt_mesh_line_samples";
-  if (int rc = check_mesh(ctx, who, mesh)) return rc;
-  if (mode != LT_SAMPLE_CENTER && mode != LT_SAMPLE_ENDS) return fail(ctx, LT_ERR_ARGUMENT, "lt_mesh_line_samples: bad mode");
-  if (n_samples < (mode == LT_SAMPLE_ENDS ? 2 : 1))
-    return fail(ctx, LT_ERR_ARGUMENT, "lt_mesh_line_samples: n_samples must be >= 1 (>= 2 for end-point sampling)");
-  if (n_th < 0 || n_th > kEvalMaxTh || (n_th > 0 && !thresholds))
-    return fail(ctx, LT_ERR_ARGUMENT, "lt_mesh_line_samples: between 0 and 64 thresholds");
-  if (n_lines < 0 || (n_lines > 0 && !lines)) return fail(ctx, LT_ERR_ARGUMENT, "lt_mesh_line_samples: bad lines");
-  if (counts && n_th == 0) counts = nullptr;
-  if (int rc = check_finite(ctx, who, lines, 6 * n_lines, "line coordinate")) return rc;
-  if (n_lines == 0 || (!dists && !counts)) return LT_OK;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const int brute = mesh_brute();
-  Timer tm;
-  if (int rc = tm.start(ctx)) return rc;
-  const auto L = prep_lines(lines, n_lines, 0);
-  if (int rc = upload_lines(ctx, ctx->d_ev_lines, L)) return rc;
-  ENSURE(ctx, ctx->d_ev_th, 8 * (size_t)std::max(n_th, 1));
-  if (n_th) HIPCHK(ctx, hipMemcpyAsync(ctx->d_ev_th.p, thresholds, 8 * (size_t)n_th, hipMemcpyHostToDevice, st));
-  const long long per = std::max<long long>(1, chunk_of(chunk) / n_samples);  // whole lines per launch
-  const long long lc = std::min<long long>(per, n_lines);
-  ENSURE(ctx, ctx->d_ev_out, 8 * (size_t)(lc * n_samples));
-  if (counts) ENSURE(ctx, ctx->d_ev_cnt, 4 * (size_t)(n_lines * n_th));
-  EvalQuery Q{};
-  Q.mode = mode == LT_SAMPLE_CENTER ? EV_Q_CENTER : EV_Q_ENDS;
-  Q.n = n_samples;
-  Q.interval = mode == LT_SAMPLE_CENTER ? 1.0 / n_samples : 1.0 / (n_samples - 1);
-  for (long long l0 = 0; l0 < n_lines; l0 += per) {
-    const long long m = std::min<long long>(per, n_lines - l0);
-    Q.lines = ctx->d_ev_lines.as<EvalLine>() + l0;
-    launch_mesh_nearest(st, mesh->tree, Q, m * n_samples, brute, ctx->d_ev_out.as<double>());
-    ++tm.launches;
-    if (counts) {
-      launch_eval_count(st, ctx->d_ev_out.as<double>(), m, n_samples, ctx->d_ev_th.as<double>(), n_th, 1,
-                        ctx->d_ev_cnt.as<int>() + l0 * n_th);
-      ++tm.launches;
-    }
-    if (dists)
-      HIPCHK(ctx, hipMemcpyAsync(dists + l0 * n_samples, ctx->d_ev_out.p, 8 * (size_t)(m * n_samples),
-                                 hipMemcpyDeviceToHost, st));
-  }
-  if (counts)
-    HIPCHK(ctx, hipMemcpyAsync(counts, ctx->d_ev_cnt.p, 4 * (size_t)(n_lines * n_th), hipMemcpyDeviceToHost, st));
-  return tm.finish(ctx, 0);
+  if (int rc = check_handle(ctx, who, mesh)) return rc;
+  return line_samples(ctx, who, lines, n_lines, mode, n_samples, thresholds, n_th, chunk, dists, counts,
+                      mesh_launch(mesh));
 }
 
 int lt_eval_get_timers(lt_ctx *ctx, double out[4]) {

@@ -1,4 +1,4 @@
-// lt_eval.h -- records shared by the host side (lt_eval.cpp, lt_mesh.cpp) and the device side (lt_kernels_eval.hip) of
+// lt_eval.h -- records shared by the host side (lt_eval.cpp) and the device side (lt_kernels_eval.hip) of
 // the line-map evaluation (limap.evaluation: PointCloudEvaluator, RefLineEvaluator, MeshEvaluator).  DESIGN §14, §15.
 #pragma once
 
@@ -19,15 +19,41 @@ struct EvalLine {
   double len, rint, pad_;
 };
 
-// the point index: the cloud in Morton order (SoA), leaf buckets of kEvalBucket points and an implicit fanout-8
-// hierarchy of AABBs over them, levels bottom (0: the buckets) to top (one root).  box: 6 doubles per node (lo, hi).
-struct EvalTree {
-  const double *x, *y, *z;
-  const double *box;
+// the level table of an index: leaf buckets over n members in Morton order and an implicit fanout-8 hierarchy of AABBs
+// over them, levels bottom (0: the buckets) to top (one root)
+struct EvalLevels {
   long long n;
   long long total;  // nodes of all levels
   long long lvl_off[kEvalMaxLevels], lvl_n[kEvalMaxLevels];
   int top;
+};
+
+// the levels of n members in buckets of `bucket`, then fanout 8 up to one root
+inline EvalLevels eval_levels(long long n, int bucket) {
+  EvalLevels L{};
+  L.n = n;
+  long long cnt = (n + bucket - 1) / bucket;
+  int l = 0;
+  for (;; ++l) {
+    L.lvl_off[l] = L.total;
+    L.lvl_n[l] = cnt;
+    L.total += cnt;
+    if (cnt == 1) break;
+    cnt = (cnt + kEvalFanout - 1) / kEvalFanout;
+  }
+  L.top = l;
+  return L;
+}
+
+// the point index: the cloud in Morton order (SoA), leaf buckets of kEvalBucket points.  box: 6 doubles per node (lo, hi).
+struct EvalTree {
+  const double *x, *y, *z;
+  const double *box;
+  EvalLevels L;
+  // what the hierarchy walk asks of an index (lt_kernels_eval.hip): a lower bound of the computed squared distance of p
+  // to everything below a node, and the scan of leaf bucket b, which returns the new best
+  __device__ double bound2(long long node, const double p[3]) const;
+  __device__ double scan(long long b, const double p[3], double best) const;
 };
 
 enum EvalQueryMode { EV_Q_POINTS = 0, EV_Q_CENTER = 1, EV_Q_ENDS = 2, EV_Q_REFLINE = 3 };
@@ -46,16 +72,16 @@ constexpr int kMeshBucket = 4;      // faces per leaf bucket (consecutive in the
 constexpr int kMeshMaxBucket = 64;  // LT_TEST_MESH_BUCKET: the bucket sizes a measurement may try
 
 // the triangle index: the faces in the Morton order of their centroids, as nine SoA vertex arrays (a, b, c: x, y, z),
-// leaf buckets of `bucket` faces and the implicit fanout-8 hierarchy of EvalTree over them.  box: 6 doubles per node,
-// the leaf boxes widened by a few ulps of their coordinates; eta: per node the largest region-7 slack
-// factor of the faces below it (+inf: a near-degenerate face, the node is never pruned).
+// leaf buckets of `bucket` faces.  box: 6 doubles per node, the leaf boxes widened by a few ulps of their coordinates
+// (DESIGN §15); eta: per node the largest region-7 slack factor of the faces below it (+inf: a near-degenerate face,
+// the node is never pruned).
 struct MeshTree {
   const double *v[9];
   const double *box, *eta;
-  long long n;
-  long long total;
-  long long lvl_off[kEvalMaxLevels], lvl_n[kEvalMaxLevels];
-  int top, bucket;
+  EvalLevels L;
+  int bucket;
+  __device__ double bound2(long long node, const double p[3]) const;  // as EvalTree's
+  __device__ double scan(long long b, const double p[3], double best) const;
 };
 
 void launch_eval_bbox(hipStream_t st, const void *xyz, int dtype, long long n, unsigned long long *keys6);
@@ -76,7 +102,7 @@ void launch_eval_lines_min(hipStream_t st, int form, const EvalQuery &Q, long lo
 void launch_eval_count(hipStream_t st, const double *dist, long long n_lines, int n, const double *th, int n_th, int le,
                        int *counts);
 
-// the mesh index (lt_mesh.cpp): centroids (nf x 3) of faces F (int64, validated) over vertices V (nv x 3, scaled)
+// the mesh index: centroids (nf x 3) of faces F (int64, validated) over vertices V (nv x 3, scaled)
 void launch_mesh_centroids(hipStream_t st, const double *V, const long long *F, long long nf, double *cen);
 // faces in the order perm into the nine SoA arrays of T
 void launch_mesh_gather(hipStream_t st, const double *V, const long long *F, long long nf, const unsigned *perm,

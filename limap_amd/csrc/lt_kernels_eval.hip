@@ -100,9 +100,9 @@ __global__ __launch_bounds__(kBlock) void k_eval_gather(const void *xyz, int dty
 
 __global__ __launch_bounds__(kBlock) void k_eval_leaf_boxes(EvalTree T, double *box) {
   const long long b = blockIdx.x * (long long)kBlock + threadIdx.x;
-  if (b >= T.lvl_n[0]) return;
+  if (b >= T.L.lvl_n[0]) return;
   const long long p0 = b * kEvalBucket;
-  const long long p1 = p0 + kEvalBucket < T.n ? p0 + kEvalBucket : T.n;
+  const long long p1 = p0 + kEvalBucket < T.L.n ? p0 + kEvalBucket : T.L.n;
   double lo[3] = {T.x[p0], T.y[p0], T.z[p0]}, hi[3] = {lo[0], lo[1], lo[2]};
   for (long long p = p0 + 1; p < p1; ++p) {
     const double v[3] = {T.x[p], T.y[p], T.z[p]};
@@ -111,26 +111,26 @@ __global__ __launch_bounds__(kBlock) void k_eval_leaf_boxes(EvalTree T, double *
       hi[k] = v[k] > hi[k] ? v[k] : hi[k];
     }
   }
-  double *o = box + 6 * (T.lvl_off[0] + b);
+  double *o = box + 6 * (T.L.lvl_off[0] + b);
   for (int k = 0; k < 3; ++k) {
     o[k] = lo[k];
     o[3 + k] = hi[k];
   }
 }
 
-__global__ __launch_bounds__(kBlock) void k_eval_level_boxes(EvalTree T, int l, double *box) {
+__global__ __launch_bounds__(kBlock) void k_eval_level_boxes(EvalLevels L, int l, double *box) {
   const long long j = blockIdx.x * (long long)kBlock + threadIdx.x;
-  if (j >= T.lvl_n[l]) return;
+  if (j >= L.lvl_n[l]) return;
   const long long c0 = j * kEvalFanout;
-  const long long c1 = c0 + kEvalFanout < T.lvl_n[l - 1] ? c0 + kEvalFanout : T.lvl_n[l - 1];
-  const double *c = box + 6 * (T.lvl_off[l - 1] + c0);
+  const long long c1 = c0 + kEvalFanout < L.lvl_n[l - 1] ? c0 + kEvalFanout : L.lvl_n[l - 1];
+  const double *c = box + 6 * (L.lvl_off[l - 1] + c0);
   double b[6] = {c[0], c[1], c[2], c[3], c[4], c[5]};
   for (long long i = 1; i < c1 - c0; ++i)
     for (int k = 0; k < 3; ++k) {
       b[k] = c[6 * i + k] < b[k] ? c[6 * i + k] : b[k];
       b[3 + k] = c[6 * i + 3 + k] > b[3 + k] ? c[6 * i + 3 + k] : b[3 + k];
     }
-  double *o = box + 6 * (T.lvl_off[l] + j);
+  double *o = box + 6 * (L.lvl_off[l] + j);
   for (int k = 0; k < 6; ++k) o[k] = b[k];
 }
 
@@ -168,67 +168,13 @@ __device__ inline double box_bound2(const double *b, const double p[3]) {
 
 __device__ inline double scan_bucket(const EvalTree &T, long long b, const double p[3], double best) {
   const long long p0 = b * kEvalBucket;
-  const long long p1 = p0 + kEvalBucket < T.n ? p0 + kEvalBucket : T.n;
+  const long long p1 = p0 + kEvalBucket < T.L.n ? p0 + kEvalBucket : T.L.n;
   for (long long j = p0; j < p1; ++j) {
     const double dx = p[0] - T.x[j], dy = p[1] - T.y[j], dz = p[2] - T.z[j];
     const double d2 = (dx * dx + dy * dy) + dz * dz;
     best = d2 < best ? d2 : best;
   }
   return best;
-}
-
-// exact minimum squared distance of p to the cloud: a greedy descent to one bucket for a first bound, then a
-// depth-first walk of the implicit hierarchy (no stack: the next node follows from (level, index) alone) that skips
-// subtrees whose bound exceeds the best.  Each node is visited at most once: the walk is bounded by T.total.
-__device__ double nearest2(const EvalTree &T, const double p[3]) {
-  long long j = 0;
-  for (int l = T.top; l > 0; --l) {
-    const long long c0 = j * kEvalFanout;
-    const long long c1 = c0 + kEvalFanout < T.lvl_n[l - 1] ? c0 + kEvalFanout : T.lvl_n[l - 1];
-    long long bj = c0;
-    double bb = INFINITY;
-    for (long long c = c0; c < c1; ++c) {
-      const double v = box_bound2(T.box + 6 * (T.lvl_off[l - 1] + c), p);
-      if (v < bb) { bb = v; bj = c; }
-    }
-    j = bj;
-  }
-  const long long first = j;
-  double best = scan_bucket(T, first, p, INFINITY);
-  int l = T.top;
-  j = 0;
-  for (long long it = 0; it < T.total; ++it) {
-    const double lb = box_bound2(T.box + 6 * (T.lvl_off[l] + j), p);
-    if (!(lb > best)) {
-      if (l > 0) {  // descend to the first child
-        --l;
-        j *= kEvalFanout;
-        continue;
-      }
-      if (j != first) best = scan_bucket(T, j, p, best);
-    }
-    // next: the following sibling, else up to the parent's following sibling
-    bool done = true;
-    for (int u = 0; u < kEvalMaxLevels && l < T.top; ++u) {
-      if ((j + 1) % kEvalFanout != 0 && j + 1 < T.lvl_n[l]) {
-        ++j;
-        done = false;
-        break;
-      }
-      ++l;
-      j /= kEvalFanout;
-    }
-    if (done) break;
-  }
-  return best;
-}
-
-__global__ __launch_bounds__(kBlock) void k_eval_nearest(EvalTree T, EvalQuery Q, long long nq, double *dist) {
-  const long long q = blockIdx.x * (long long)kBlock + threadIdx.x;
-  if (q >= nq) return;
-  double p[3];
-  query_point(Q, q, p);
-  dist[q] = sqrt(nearest2(T, p));
 }
 
 // Line3d::point_distance (base/linebase.cc:67-80), squared: the projection onto the segment, clamped at its ends
@@ -422,9 +368,9 @@ __global__ __launch_bounds__(kBlock) void k_mesh_gather(const double *V, const l
 // 2^-40 E^3 / S (E^2 the longest squared edge, S = |ab|^2 |ac|^2 - (ab.ac)^2), +inf when S <= 2^-30 E^4
 __global__ __launch_bounds__(kBlock) void k_mesh_leaf_boxes(MeshTree T, double *box, double *eta) {
   const long long b = blockIdx.x * (long long)kBlock + threadIdx.x;
-  if (b >= T.lvl_n[0]) return;
+  if (b >= T.L.lvl_n[0]) return;
   const long long f0 = b * T.bucket;
-  const long long f1 = f0 + T.bucket < T.n ? f0 + T.bucket : T.n;
+  const long long f1 = f0 + T.bucket < T.L.n ? f0 + T.bucket : T.L.n;
   double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, et = 0.0;
   for (long long f = f0; f < f1; ++f) {
     double v[3][3];
@@ -449,26 +395,26 @@ __global__ __launch_bounds__(kBlock) void k_mesh_leaf_boxes(MeshTree T, double *
       et = h > et ? h : et;
     }
   }
-  double *o = box + 6 * (T.lvl_off[0] + b);
+  double *o = box + 6 * (T.L.lvl_off[0] + b);
   for (int k = 0; k < 3; ++k) {
     const double m = 0x1p-48 * fmax(fabs(lo[k]), fabs(hi[k])) + 0x1p-1060;
     o[k] = lo[k] - 2.0 * m;
     o[3 + k] = hi[k] + 2.0 * m;
   }
-  eta[T.lvl_off[0] + b] = et;
+  eta[T.L.lvl_off[0] + b] = et;
 }
 
 __global__ __launch_bounds__(kBlock) void k_mesh_level_eta(MeshTree T, int l, double *eta) {
   const long long j = blockIdx.x * (long long)kBlock + threadIdx.x;
-  if (j >= T.lvl_n[l]) return;
+  if (j >= T.L.lvl_n[l]) return;
   const long long c0 = j * kEvalFanout;
-  const long long c1 = c0 + kEvalFanout < T.lvl_n[l - 1] ? c0 + kEvalFanout : T.lvl_n[l - 1];
+  const long long c1 = c0 + kEvalFanout < T.L.lvl_n[l - 1] ? c0 + kEvalFanout : T.L.lvl_n[l - 1];
   double m = 0.0;
   for (long long c = c0; c < c1; ++c) {
-    const double e = eta[T.lvl_off[l - 1] + c];
+    const double e = eta[T.L.lvl_off[l - 1] + c];
     m = e > m ? e : m;
   }
-  eta[T.lvl_off[l] + j] = m;
+  eta[T.L.lvl_off[l] + j] = m;
 }
 
 // a lower bound of the computed squared distance of p to every face below a node: the per-axis gap to the (widened)
@@ -492,7 +438,7 @@ __device__ inline double mesh_bound2(const double *b, double eta, const double p
 
 __device__ inline double scan_faces(const MeshTree &T, long long b, const double p[3], double best) {
   const long long f0 = b * T.bucket;
-  const long long f1 = f0 + T.bucket < T.n ? f0 + T.bucket : T.n;
+  const long long f1 = f0 + T.bucket < T.L.n ? f0 + T.bucket : T.L.n;
   for (long long f = f0; f < f1; ++f) {
     double a[3], bb[3], c[3];
     load_face(T, f, a, bb, c);
@@ -502,39 +448,60 @@ __device__ inline double scan_faces(const MeshTree &T, long long b, const double
   return best;
 }
 
-// as nearest2 of the point index: a greedy descent to one bucket, then the stackless walk bounded by T.total
-__device__ double mesh_nearest2(const MeshTree &T, const double p[3]) {
+}  // namespace
+
+// what the walk asks of the two indexes (lt_eval.h)
+__device__ inline double EvalTree::bound2(long long node, const double p[3]) const {
+  return box_bound2(box + 6 * node, p);
+}
+__device__ inline double EvalTree::scan(long long b, const double p[3], double best) const {
+  return scan_bucket(*this, b, p, best);
+}
+__device__ inline double MeshTree::bound2(long long node, const double p[3]) const {
+  return mesh_bound2(box + 6 * node, eta[node], p);
+}
+__device__ inline double MeshTree::scan(long long b, const double p[3], double best) const {
+  return scan_faces(*this, b, p, best);
+}
+
+namespace {
+
+// exact minimum squared distance of p to the members of an index: a greedy descent to one bucket for a first bound,
+// then a depth-first walk of the implicit hierarchy (no stack: the next node follows from (level, index) alone) that
+// skips subtrees whose bound exceeds the best.  Each node is visited at most once: the walk is bounded by L.total.
+template <class Index>
+__device__ inline double nearest2(const Index &T, const double p[3]) {
+  const EvalLevels &L = T.L;
   long long j = 0;
-  for (int l = T.top; l > 0; --l) {
+  for (int l = L.top; l > 0; --l) {
     const long long c0 = j * kEvalFanout;
-    const long long c1 = c0 + kEvalFanout < T.lvl_n[l - 1] ? c0 + kEvalFanout : T.lvl_n[l - 1];
+    const long long c1 = c0 + kEvalFanout < L.lvl_n[l - 1] ? c0 + kEvalFanout : L.lvl_n[l - 1];
     long long bj = c0;
     double bb = INFINITY;
     for (long long c = c0; c < c1; ++c) {
-      const long long node = T.lvl_off[l - 1] + c;
-      const double v = mesh_bound2(T.box + 6 * node, T.eta[node], p);
+      const double v = T.bound2(L.lvl_off[l - 1] + c, p);
       if (v < bb) { bb = v; bj = c; }
     }
     j = bj;
   }
   const long long first = j;
-  double best = scan_faces(T, first, p, INFINITY);
-  int l = T.top;
+  double best = T.scan(first, p, INFINITY);
+  int l = L.top;
   j = 0;
-  for (long long it = 0; it < T.total; ++it) {
-    const long long node = T.lvl_off[l] + j;
-    const double lb = mesh_bound2(T.box + 6 * node, T.eta[node], p);
+  for (long long it = 0; it < L.total; ++it) {
+    const double lb = T.bound2(L.lvl_off[l] + j, p);
     if (!(lb > best)) {
-      if (l > 0) {
+      if (l > 0) {  // descend to the first child
         --l;
         j *= kEvalFanout;
         continue;
       }
-      if (j != first) best = scan_faces(T, j, p, best);
+      if (j != first) best = T.scan(j, p, best);
     }
+    // next: the following sibling, else up to the parent's following sibling
     bool done = true;
-    for (int u = 0; u < kEvalMaxLevels && l < T.top; ++u) {
-      if ((j + 1) % kEvalFanout != 0 && j + 1 < T.lvl_n[l]) {
+    for (int u = 0; u < kEvalMaxLevels && l < L.top; ++u) {
+      if ((j + 1) % kEvalFanout != 0 && j + 1 < L.lvl_n[l]) {
         ++j;
         done = false;
         break;
@@ -547,12 +514,20 @@ __device__ double mesh_nearest2(const MeshTree &T, const double p[3]) {
   return best;
 }
 
+__global__ __launch_bounds__(kBlock) void k_eval_nearest(EvalTree T, EvalQuery Q, long long nq, double *dist) {
+  const long long q = blockIdx.x * (long long)kBlock + threadIdx.x;
+  if (q >= nq) return;
+  double p[3];
+  query_point(Q, q, p);
+  dist[q] = sqrt(nearest2(T, p));
+}
+
 __global__ __launch_bounds__(kBlock) void k_mesh_nearest(MeshTree T, EvalQuery Q, long long nq, double *dist) {
   const long long q = blockIdx.x * (long long)kBlock + threadIdx.x;
   if (q >= nq) return;
   double p[3];
   query_point(Q, q, p);
-  dist[q] = sqrt(mesh_nearest2(T, p));
+  dist[q] = sqrt(nearest2(T, p));
 }
 
 // the walk's yardstick: every face, tiles of kFaceTile faces staged in LDS (SoA), kPerLane queries per lane
@@ -566,8 +541,8 @@ __global__ __launch_bounds__(kBlock) void k_mesh_brute(MeshTree T, EvalQuery Q, 
     else p[r][0] = p[r][1] = p[r][2] = 0.0;
     m2[r] = INFINITY;
   }
-  for (long long t0 = 0; t0 < T.n; t0 += kFaceTile) {
-    const int cnt = (int)(T.n - t0 < kFaceTile ? T.n - t0 : kFaceTile);
+  for (long long t0 = 0; t0 < T.L.n; t0 += kFaceTile) {
+    const int cnt = (int)(T.L.n - t0 < kFaceTile ? T.L.n - t0 : kFaceTile);
     __syncthreads();
     for (int k = threadIdx.x; k < 9 * kFaceTile; k += kBlock) {
       const int a = k / kFaceTile, f = k - a * kFaceTile;
@@ -622,9 +597,9 @@ void launch_eval_gather(hipStream_t st, const void *xyz, int dtype, long long n,
 }
 
 void launch_eval_boxes(hipStream_t st, const EvalTree &T, double *box) {
-  hipLaunchKernelGGL(k_eval_leaf_boxes, dim3(nblk(T.lvl_n[0], kBlock)), dim3(kBlock), 0, st, T, box);
-  for (int l = 1; l <= T.top; ++l)
-    hipLaunchKernelGGL(k_eval_level_boxes, dim3(nblk(T.lvl_n[l], kBlock)), dim3(kBlock), 0, st, T, l, box);
+  hipLaunchKernelGGL(k_eval_leaf_boxes, dim3(nblk(T.L.lvl_n[0], kBlock)), dim3(kBlock), 0, st, T, box);
+  for (int l = 1; l <= T.L.top; ++l)
+    hipLaunchKernelGGL(k_eval_level_boxes, dim3(nblk(T.L.lvl_n[l], kBlock)), dim3(kBlock), 0, st, T.L, l, box);
 }
 
 void launch_eval_nearest(hipStream_t st, const EvalTree &T, const EvalQuery &Q, long long nq, double *dist) {
@@ -660,17 +635,10 @@ void launch_mesh_gather(hipStream_t st, const double *V, const long long *F, lon
 }
 
 void launch_mesh_boxes(hipStream_t st, const MeshTree &T, double *box, double *eta) {
-  hipLaunchKernelGGL(k_mesh_leaf_boxes, dim3(nblk(T.lvl_n[0], kBlock)), dim3(kBlock), 0, st, T, box, eta);
-  EvalTree E{};  // the levels above the buckets: the point index's box kernel reads only the level table
-  E.total = T.total;
-  E.top = T.top;
-  for (int l = 0; l < kEvalMaxLevels; ++l) {
-    E.lvl_off[l] = T.lvl_off[l];
-    E.lvl_n[l] = T.lvl_n[l];
-  }
-  for (int l = 1; l <= T.top; ++l) {
-    hipLaunchKernelGGL(k_eval_level_boxes, dim3(nblk(T.lvl_n[l], kBlock)), dim3(kBlock), 0, st, E, l, box);
-    hipLaunchKernelGGL(k_mesh_level_eta, dim3(nblk(T.lvl_n[l], kBlock)), dim3(kBlock), 0, st, T, l, eta);
+  hipLaunchKernelGGL(k_mesh_leaf_boxes, dim3(nblk(T.L.lvl_n[0], kBlock)), dim3(kBlock), 0, st, T, box, eta);
+  for (int l = 1; l <= T.L.top; ++l) {
+    hipLaunchKernelGGL(k_eval_level_boxes, dim3(nblk(T.L.lvl_n[l], kBlock)), dim3(kBlock), 0, st, T.L, l, box);
+    hipLaunchKernelGGL(k_mesh_level_eta, dim3(nblk(T.L.lvl_n[l], kBlock)), dim3(kBlock), 0, st, T, l, eta);
   }
 }
 

@@ -96,8 +96,54 @@ def _points3(p):
 
 
 class _SampledEvaluator:
-    """the methods of evaluation/base_evaluator.cc over a subclass's ComputeDistPoints and _samples (line samples
-    generated on the device, distances and per-threshold counts)"""
+    """the methods of evaluation/base_evaluator.cc over a device index: nearest distances of free points and of line
+    samples generated on the device (distances and per-threshold counts).  A subclass names its two query entry points
+    and the free function of the C ABI, and implements _index(), which returns the handle (built on first use) that it
+    keeps in _handle."""
+
+    _handle = None
+
+    def _ctx(self):
+        return _context(self.device)
+
+    def _free(self):
+        if self._handle is not None and self._handle.value:
+            getattr(_capi.load_library(), self._free_fn)(self._handle)
+        self._handle = None
+
+    def __del__(self):
+        try:
+            self._free()
+        except Exception:
+            pass
+
+    def timers(self):
+        out = np.zeros(4)
+        ctx = self._ctx()
+        ctx.chk(ctx.L.lt_eval_get_timers(ctx.h, _p(out)))
+        return out
+
+    def ComputeDistPoints(self, points, chunk=None):
+        """ComputeDistPoint for each row of an (M, 3) array"""
+        q = _points3(points)
+        out = np.zeros(max(q.shape[0], 1))
+        ctx = self._ctx()
+        index = self._index()
+        ctx.chk(getattr(ctx.L, self._nearest_fn)(ctx.h, index, _p(q), q.shape[0], self._chunk(chunk), _p(out)))
+        return out[:q.shape[0]]
+
+    def _samples(self, a, mode, n, thresholds=None, want_dists=True, chunk=None):
+        ctx = self._ctx()
+        index = self._index()
+        L = a.shape[0]
+        th = _thresholds(thresholds) if thresholds is not None else np.zeros(0)
+        dists = np.zeros((max(L, 1), n)) if want_dists else None
+        counts = np.zeros((max(L, 1), max(th.size, 1)), np.int32) if th.size else None
+        if L:
+            ctx.chk(getattr(ctx.L, self._samples_fn)(
+                ctx.h, index, _p(a), L, mode, n, _p(th) if th.size else None, th.size, self._chunk(chunk),
+                _p(dists) if want_dists else None, _p(counts, C.c_int32) if counts is not None else None))
+        return (dists[:L] if want_dists else None), (counts[:L, :th.size] if counts is not None else None)
 
     def ComputeDistPoint(self, point):
         return float(self.ComputeDistPoints(np.asarray(point, np.float64).reshape(1, 3))[0])
@@ -148,10 +194,11 @@ class _SampledEvaluator:
 class PointCloudEvaluator(_SampledEvaluator):
     """evaluation/point_cloud_evaluator.h: nearest-point distances to a GT point cloud, on a device index."""
 
+    _nearest_fn, _samples_fn, _free_fn = "lt_pcd_nearest_dists", "lt_pcd_line_samples", "lt_pcd_free"
+
     def __init__(self, points=None, device=0, chunk=0):
         self.device = int(device)
         self.chunk = int(chunk)
-        self._pcd = None
         self._torch = None
         if points is None:
             raise ValueError("PointCloudEvaluator: an empty point cloud cannot be evaluated against")
@@ -191,9 +238,6 @@ class PointCloudEvaluator(_SampledEvaluator):
         self.n_points = int(self._torch.shape[0] if self._torch is not None else self.points.shape[0])
 
     # ---- index -------------------------------------------------------------------------------------------------------
-    def _ctx(self):
-        return _context(self.device)
-
     def _build(self, perm=None):
         ctx = self._ctx()
         self._free()
@@ -209,23 +253,12 @@ class PointCloudEvaluator(_SampledEvaluator):
         else:
             ctx.chk(ctx.L.lt_pcd_build(ctx.h, self.points.ctypes.data, self.points.shape[0], 1, 0,
                                        None if pp is None else pp.ctypes.data, C.byref(out)))
-        self._pcd = out
-
-    def _free(self):
-        if self._pcd is not None and self._pcd.value:
-            _capi.load_library().lt_pcd_free(self._pcd)
-        self._pcd = None
-
-    def __del__(self):
-        try:
-            self._free()
-        except Exception:
-            pass
+        self._handle = out
 
     def _index(self):
-        if self._pcd is None:
+        if self._handle is None:
             self._build()
-        return self._pcd
+        return self._handle
 
     def Build(self):
         self._build()
@@ -265,28 +298,6 @@ class PointCloudEvaluator(_SampledEvaluator):
         self._build(perm.astype(np.uint32))
 
     # ---- queries -----------------------------------------------------------------------------------------------------
-    def ComputeDistPoints(self, points, chunk=None):
-        """ComputeDistPoint for each row of an (M, 3) array"""
-        q = _points3(points)
-        out = np.zeros(max(q.shape[0], 1))
-        ctx = self._ctx()
-        pcd = self._index()
-        ctx.chk(ctx.L.lt_pcd_nearest_dists(ctx.h, pcd, _p(q), q.shape[0], self._chunk(chunk), _p(out)))
-        return out[:q.shape[0]]
-
-    def _samples(self, a, mode, n, thresholds=None, want_dists=True, chunk=None):
-        ctx = self._ctx()
-        pcd = self._index()
-        L = a.shape[0]
-        th = _thresholds(thresholds) if thresholds is not None else np.zeros(0)
-        dists = np.zeros((max(L, 1), n)) if want_dists else None
-        counts = np.zeros((max(L, 1), max(th.size, 1)), np.int32) if th.size else None
-        if L:
-            ctx.chk(ctx.L.lt_pcd_line_samples(
-                ctx.h, pcd, _p(a), L, mode, n, _p(th) if th.size else None, th.size, self._chunk(chunk),
-                _p(dists) if want_dists else None, _p(counts, C.c_int32) if counts is not None else None))
-        return (dists[:L] if want_dists else None), (counts[:L, :th.size] if counts is not None else None)
-
     def ComputeDistsforEachPoint(self, lines, chunk=None):
         """per cloud point (constructor order): min over the lines of Line3d::point_distance; DBL_MAX without lines"""
         a = lines_array(lines)
@@ -302,12 +313,6 @@ class PointCloudEvaluator(_SampledEvaluator):
             "ComputeDistsforEachPoint_KDTree is an approximation whose line sampling is wrong in limap "
             "(interval = length / (n - 1) scales an unnormalised direction) and whose ties depend on the kd-tree; "
             "use ComputeDistsforEachPoint, which is exact and runs on the GPU")
-
-    def timers(self):
-        out = np.zeros(4)
-        ctx = self._ctx()
-        ctx.chk(ctx.L.lt_eval_get_timers(ctx.h, _p(out)))
-        return out
 
 
 def _segments(a, d, threshold, n, inlier):
@@ -378,6 +383,8 @@ class MeshEvaluator(_SampledEvaluator):
     distance is Ericson's closest point in a stated FP64 operation order; agreement with
     libigl's point_simplex_squared_distance is not claimed."""
 
+    _nearest_fn, _samples_fn, _free_fn = "lt_mesh_nearest_dists", "lt_mesh_line_samples", "lt_mesh_free"
+
     def __init__(self, filename, mpau, device=0, chunk=0):
         from .io import read_mesh
         V, F = read_mesh(filename)
@@ -391,7 +398,6 @@ class MeshEvaluator(_SampledEvaluator):
         return self
 
     def _init(self, V, F, mpau, device, chunk):
-        self._mesh = None
         self.device = int(device)
         self.chunk = int(chunk)
         V = np.ascontiguousarray(np.asarray(V, np.float64).reshape(-1, 3))
@@ -412,61 +418,19 @@ class MeshEvaluator(_SampledEvaluator):
         self.V, self.F = V, F
         self.n_vertices, self.n_faces = V.shape[0], F.shape[0]
 
-    def _ctx(self):
-        return _context(self.device)
-
     def _index(self):
-        if self._mesh is None:
+        if self._handle is None:
             ctx = self._ctx()
             out = C.c_void_p()
             ctx.chk(ctx.L.lt_mesh_build(ctx.h, self.V.ctypes.data, self.n_vertices, 1, 0, self.F.ctypes.data,
                                         self.n_faces, self.mpau, C.byref(out)))
-            self._mesh = out
-        return self._mesh
+            self._handle = out
+        return self._handle
 
     def Build(self):
         """(re)builds the device index; the queries build it on first use"""
         self._free()
         self._index()
-
-    def _free(self):
-        if getattr(self, "_mesh", None) is not None and self._mesh.value:
-            _capi.load_library().lt_mesh_free(self._mesh)
-        self._mesh = None
-
-    def __del__(self):
-        try:
-            self._free()
-        except Exception:
-            pass
-
-    def ComputeDistPoints(self, points, chunk=None):
-        """ComputeDistPoint for each row of an (M, 3) array"""
-        q = _points3(points)
-        out = np.zeros(max(q.shape[0], 1))
-        ctx = self._ctx()
-        mesh = self._index()
-        ctx.chk(ctx.L.lt_mesh_nearest_dists(ctx.h, mesh, _p(q), q.shape[0], self._chunk(chunk), _p(out)))
-        return out[:q.shape[0]]
-
-    def _samples(self, a, mode, n, thresholds=None, want_dists=True, chunk=None):
-        ctx = self._ctx()
-        mesh = self._index()
-        L = a.shape[0]
-        th = _thresholds(thresholds) if thresholds is not None else np.zeros(0)
-        dists = np.zeros((max(L, 1), n)) if want_dists else None
-        counts = np.zeros((max(L, 1), max(th.size, 1)), np.int32) if th.size else None
-        if L:
-            ctx.chk(ctx.L.lt_mesh_line_samples(
-                ctx.h, mesh, _p(a), L, mode, n, _p(th) if th.size else None, th.size, self._chunk(chunk),
-                _p(dists) if want_dists else None, _p(counts, C.c_int32) if counts is not None else None))
-        return (dists[:L] if want_dists else None), (counts[:L, :th.size] if counts is not None else None)
-
-    def timers(self):
-        out = np.zeros(4)
-        ctx = self._ctx()
-        ctx.chk(ctx.L.lt_eval_get_timers(ctx.h, _p(out)))
-        return out
 
 
 # ---- scripts/eval_hypersim.py:47-68, scripts/eval_tnt.py:22-59 ----------------------------------------------------------
