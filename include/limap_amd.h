@@ -441,6 +441,50 @@ int lt_mesh_line_samples(lt_ctx *ctx, const lt_mesh *mesh, const double *lines, 
  * [3] index levels (lt_pcd_build, lt_mesh_build) */
 int lt_eval_get_timers(lt_ctx *ctx, double out[4]);
 
+/* ---- limap.structures.PL_Bipartite2d (structures/pl_bipartite.cc) on the GPU, for a batch of images per call
+ * (DESIGN.md section 16).  Images are given as CSR: the lines of image m are lines[4 line_off[m] .. 4 line_off[m+1])
+ * (x1, y1, x2, y2; in ascending line-id order, which is the order of the reference's std::map), its points
+ * pts[2 pt_off[m] .. 2 pt_off[m+1]); offsets start at 0.  Lines are named by their index within the image.  Needs no
+ * lt_init.  Coordinates must be finite and no threshold NaN: LT_ERR_ARGUMENT before any launch otherwise (the reference
+ * has no defined behaviour there).  An image without lines yields no edge and no junction (the reference's loop bounds
+ * `count_lines() - 1` and `n_inters - 1` wrap around in size_t, pl_bipartite.cc:112,129).
+ * PL_Bipartite2dConfig (structures/pl_bipartite.h:22-33), in pixels. */
+typedef struct lt_bpt_config {
+  double threshold_keypoints;
+  double threshold_intersection;
+  double threshold_merge_junctions;
+} lt_bpt_config;
+void lt_bpt_config_default(lt_bpt_config *cfg); /* 2.0 each */
+/* PL_Bipartite2d::add_keypoint for every point (pl_bipartite.cc:56-67 under :69-82): point p is connected to line l
+ * iff !(Line2d::point_distance(p) > threshold_keypoints) (base/linebase.cc:20-33, bit for bit).  The result stays in
+ * the context: n_edges (may be NULL) receives its size, lt_bpt_associate_get copies it out -- edge_off[pt_off[n_img]
+ * + 1] (may be NULL), and per point its line indices in ascending order, edge_line[n_edges] (may be NULL). */
+int lt_bpt_associate(lt_ctx *ctx, int n_img, const int64_t *line_off, const double *lines, const int64_t *pt_off,
+                     const double *pts, const lt_bpt_config *cfg, int64_t *n_edges);
+int lt_bpt_associate_get(lt_ctx *ctx, int64_t *edge_off, int32_t *edge_line);
+/* PL_Bipartite2d::compute_intersection_with_points(kps) on a bipartite that holds the lines only (pl_bipartite.cc:91-164):
+ * the junction candidates -- both endpoints of every line, then intersect() (:166-204) of every line pair i < j in the
+ * order of :112-124 -- merged by the union-find of :128-143 (union_find_get_root, base/graph.cc:157-166) over the pairs
+ * within threshold_merge_junctions, each cluster replaced by merge_junctions (:206-223), and a merged junction dropped
+ * iff the image has keypoints and KDTree::point_distance (util/kd_tree.h:96-98, taken as the exact minimum) is <
+ * threshold_merge_junctions (:155-161).  The surviving junctions come in the order add_junction sees them, which is
+ * the order of their point ids.  LT_ERR_ARGUMENT when an accepted intersection or a merged junction is not finite, for
+ * more than 2^32 - 1 candidates or 2^31 close candidate pairs.  The result stays in the context; sizes (may be NULL)
+ * receives {junctions, line indices of all junctions, candidates, close candidate pairs}.  lt_bpt_junctions_get copies
+ * out (any pointer may be NULL) junc_off[n_img + 1], junc_xy[2 sizes[0]], id_off[sizes[0] + 1] and the ascending line
+ * indices of every junction, line_idx[sizes[1]].  lt_bpt_junctions_get_candidates (for tests) copies out
+ * cand_off[n_img + 1], cand_xy[2 sizes[2]], cand_lines[2 sizes[2]] (the candidate's one or two lines, -1 for none) and
+ * parents[sizes[2]]: the union-find's array after the last root look-ups of :145-146, indices within the image. */
+int lt_bpt_junctions(lt_ctx *ctx, int n_img, const int64_t *line_off, const double *lines, const int64_t *kp_off,
+                     const double *kps, const lt_bpt_config *cfg, int64_t sizes[4]);
+int lt_bpt_junctions_get(lt_ctx *ctx, int64_t *junc_off, double *junc_xy, int64_t *id_off, int32_t *line_idx);
+int lt_bpt_junctions_get_candidates(lt_ctx *ctx, int64_t *cand_off, double *cand_xy, int32_t *cand_lines,
+                                    int32_t *parents);
+/* host ms of the stages of the last lt_bpt_associate / lt_bpt_junctions, each ended by a stream synchronisation:
+ * [0] upload, [1] kernels (with the counts and prefix sums that size their outputs), [2] sorts, [3] download and host
+ * replay */
+int lt_bpt_get_timers(lt_ctx *ctx, double out[4]);
+
 /* Counters of the last device run: [0] connections tested, [1] candidates, [2] ordered candidate
  * pairs swept by the scoring kernel (sum n_tris^2), [3] valid edges, [4] graph nodes,
  * [5] graph edges, [6] tracks, [7] nodes. */

@@ -34,6 +34,8 @@ EXPORTED_SYMBOLS = [
     "lt_pcd_build", "lt_pcd_free", "lt_pcd_get_perm", "lt_pcd_nearest_dists", "lt_pcd_line_samples",
     "lt_lines_point_dists", "lt_refline_counts", "lt_eval_get_timers",
     "lt_mesh_build", "lt_mesh_free", "lt_mesh_nearest_dists", "lt_mesh_line_samples",
+    "lt_bpt_config_default", "lt_bpt_associate", "lt_bpt_associate_get", "lt_bpt_junctions", "lt_bpt_junctions_get",
+    "lt_bpt_junctions_get_candidates", "lt_bpt_get_timers",
 ]
 
 
@@ -122,6 +124,12 @@ class LtScanMap(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("h", C.c_int64), ("w", C.c_int64), ("row_stride", C.c_int64),
                 ("pix_stride", C.c_int64), ("chan_stride", C.c_int64), ("img_h", C.c_int64), ("img_w", C.c_int64),
                 ("dtype", C.c_int32), ("on_device", C.c_int32)]
+
+
+class LtBptConfig(C.Structure):
+    """lt_bpt_config of include/limap_amd.h"""
+    _fields_ = [("threshold_keypoints", C.c_double), ("threshold_intersection", C.c_double),
+                ("threshold_merge_junctions", C.c_double)]
 
 
 def load_library():
@@ -249,6 +257,14 @@ def load_library():
     L.lt_mesh_free.restype = None
     L.lt_mesh_nearest_dists.argtypes = [vp, vp, dp, C.c_int64, C.c_int64, dp]
     L.lt_mesh_line_samples.argtypes = [vp, vp, dp, C.c_int64, C.c_int, C.c_int, dp, C.c_int, C.c_int64, dp, i32p]
+    L.lt_bpt_config_default.argtypes = [C.POINTER(LtBptConfig)]
+    L.lt_bpt_config_default.restype = None
+    L.lt_bpt_associate.argtypes = [vp, C.c_int, i64p, dp, i64p, dp, C.POINTER(LtBptConfig), i64p]
+    L.lt_bpt_associate_get.argtypes = [vp, i64p, i32p]
+    L.lt_bpt_junctions.argtypes = [vp, C.c_int, i64p, dp, i64p, dp, C.POINTER(LtBptConfig), i64p]
+    L.lt_bpt_junctions_get.argtypes = [vp, i64p, dp, i64p, i32p]
+    L.lt_bpt_junctions_get_candidates.argtypes = [vp, i64p, dp, i32p, i32p]
+    L.lt_bpt_get_timers.argtypes = [vp, dp]
     _lib = L
     return L
 

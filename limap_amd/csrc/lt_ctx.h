@@ -401,6 +401,18 @@ struct lt_ctx {
   // ---- line-map evaluation (lt_eval.cpp) ----
   double ev_timers[4] = {0, 0, 0, 0};  // lt_eval_get_timers
   DevBuf d_ev_in, d_ev_lines, d_ev_th, d_ev_out, d_ev_cnt;
+  // ---- 2D point-line bipartites (lt_bpt.cpp): the results of the last lt_bpt_associate / lt_bpt_junctions ----
+  double bp_timers[4] = {0, 0, 0, 0};  // lt_bpt_get_timers
+  std::vector<long long> bp_edge_off;  // per point, CSR of line indices
+  std::vector<int> bp_edge;
+  std::vector<long long> bp_junc_off, bp_jid_off;  // per image the junctions, per junction its line indices
+  std::vector<double> bp_junc_xy;
+  std::vector<int> bp_jid;
+  std::vector<long long> bp_cand_off;  // per image the junction candidates (endpoints, then intersections)
+  std::vector<double> bp_cand_xy;
+  std::vector<int> bp_cand_lines, bp_parents;
+  DevBuf d_bp_raw, d_bp_lines, d_bp_pts, d_bp_off, d_bp_off2, d_bp_off3, d_bp_blk, d_bp_cnt, d_bp_scan, d_bp_out,
+      d_bp_inter, d_bp_cand, d_bp_keys, d_bp_keys2, d_bp_idx, d_bp_idx2, d_bp_tmp, d_bp_misc;
 };
 
 #define HIPCHK(ctx, call)                                                                  \
