@@ -485,6 +485,43 @@ int lt_bpt_junctions_get_candidates(lt_ctx *ctx, int64_t *cand_off, double *cand
  * replay */
 int lt_bpt_get_timers(lt_ctx *ctx, double out[4]);
 
+/* ---- limap.line2d matchers that are pure linear algebra: L2D2Matcher (line2d/L2D2/matcher.py) and the top-k form of
+ * NNEndpointsMatcher (line2d/endpoints/matcher.py:71-111), a whole scene in one call.
+ * score(i, j) of two descriptors is the FP32 fmaf chain over the dimension in ascending order from +0.0f; the endpoints
+ * line score is 0.5f * max(S[2i,2j] + S[2i+1,2j+1], S[2i,2j+1] + S[2i+1,2j]) in FP32 (the first sum when both are equal).
+ * Columns rank by score descending, equal scores by ascending column.  topk > 0: min(topk, lines of the neighbour) rows
+ * per line; topk == 0 (L2D2 only): mutual nearest neighbours, arg-max = first maximum. */
+#define LT_MATCH_L2D2 0
+#define LT_MATCH_ENDPOINTS 1
+#define LT_MATCH_MAX_TOPK 64
+#define LT_MATCH_MAX_DIM 256
+typedef struct lt_match_config {
+  int32_t kind;           /* LT_MATCH_L2D2: a descriptor row per line; LT_MATCH_ENDPOINTS: two rows (endpoints) per line */
+  int32_t topk;           /* 0 .. LT_MATCH_MAX_TOPK; limap's default is 10 */
+  int32_t desc_on_device; /* desc is device memory of the context's device, read in place on the context's stream */
+  int32_t want_scores;    /* also download the FP32 scores of the returned rows (lt_match_get_scores) */
+} lt_match_config;
+/* Images as CSR over descriptor rows: image m owns rows desc_off[m] .. desc_off[m+1] of desc (row-major, dim floats per
+ * row, FP32; for the endpoints kind rows 2 l and 2 l + 1 are the endpoints of line l -- the transpose of limap's
+ * (256, 2 M) array).  Pairs as CSR over images: image m is matched against images pair_nb[pair_off[m] .. pair_off[m+1])
+ * (indices into this call's images).  Rejected with LT_ERR_ARGUMENT before any matching launch: a value that is not
+ * finite or above 2^57 in magnitude (no score can then overflow), dim not a multiple of 8 in [8, LT_MATCH_MAX_DIM],
+ * topk outside [0, LT_MATCH_MAX_TOPK], topk == 0 with the endpoints kind, more than 65 535 lines in an image, an odd
+ * endpoint count, a neighbour that is not an image.  The rows stay in the context: n_rows (may be NULL) receives their
+ * number; lt_match_get copies out row_off[pairs + 1] and rows2[2 * n_rows] = (line, neighbour line) per row, pairs in
+ * call order, within a pair by line, within a line best first; lt_match_get_scores the score of every row. */
+int lt_match_scene(lt_ctx *ctx, int n_img, const int64_t *desc_off, const float *desc, int dim, const int64_t *pair_off,
+                   const int32_t *pair_nb, const lt_match_config *cfg, int64_t *n_rows);
+int lt_match_get(lt_ctx *ctx, int64_t *row_off, int32_t *rows2);
+int lt_match_get_scores(lt_ctx *ctx, float *scores);
+/* host ms of the last lt_match_scene: [0] validation and upload, [1] kernels, [2] download, [3] host row bookkeeping */
+int lt_match_get_timers(lt_ctx *ctx, double out[4]);
+/* The same semantics on the host, no context and no device (std::fmaf in a plain loop): exposed for tests.  desc1: n1
+ * rows, desc2: n2 rows.  rows2 / scores (either may be NULL) need room for (lines of 1) * max(1, min(topk, lines of 2))
+ * rows; n_rows receives the count. */
+int lt_fn_match_pair_host(const float *desc1, int64_t n1, const float *desc2, int64_t n2, int dim,
+                          const lt_match_config *cfg, int32_t *rows2, float *scores, int64_t *n_rows);
+
 /* Counters of the last device run: [0] connections tested, [1] candidates, [2] ordered candidate
  * pairs swept by the scoring kernel (sum n_tris^2), [3] valid edges, [4] graph nodes,
  * [5] graph edges, [6] tracks, [7] nodes. */

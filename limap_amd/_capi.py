@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = [
     "lt_mesh_build", "lt_mesh_free", "lt_mesh_nearest_dists", "lt_mesh_line_samples",
     "lt_bpt_config_default", "lt_bpt_associate", "lt_bpt_associate_get", "lt_bpt_junctions", "lt_bpt_junctions_get",
     "lt_bpt_junctions_get_candidates", "lt_bpt_get_timers",
+    "lt_match_scene", "lt_match_get", "lt_match_get_scores", "lt_match_get_timers", "lt_fn_match_pair_host",
 ]
 
 
@@ -130,6 +131,11 @@ class LtBptConfig(C.Structure):
     """lt_bpt_config of include/limap_amd.h"""
     _fields_ = [("threshold_keypoints", C.c_double), ("threshold_intersection", C.c_double),
                 ("threshold_merge_junctions", C.c_double)]
+
+
+class LtMatchConfig(C.Structure):
+    """lt_match_config of include/limap_amd.h"""
+    _fields_ = [("kind", C.c_int32), ("topk", C.c_int32), ("desc_on_device", C.c_int32), ("want_scores", C.c_int32)]
 
 
 def load_library():
@@ -265,6 +271,12 @@ def load_library():
     L.lt_bpt_junctions_get.argtypes = [vp, i64p, dp, i64p, i32p]
     L.lt_bpt_junctions_get_candidates.argtypes = [vp, i64p, dp, i32p, i32p]
     L.lt_bpt_get_timers.argtypes = [vp, dp]
+    fp = C.POINTER(C.c_float)
+    L.lt_match_scene.argtypes = [vp, C.c_int, i64p, vp, C.c_int, i64p, i32p, C.POINTER(LtMatchConfig), i64p]
+    L.lt_match_get.argtypes = [vp, i64p, i32p]
+    L.lt_match_get_scores.argtypes = [vp, fp]
+    L.lt_match_get_timers.argtypes = [vp, dp]
+    L.lt_fn_match_pair_host.argtypes = [fp, C.c_int64, fp, C.c_int64, C.c_int, C.POINTER(LtMatchConfig), i32p, fp, i64p]
     _lib = L
     return L
 

@@ -413,6 +413,14 @@ struct lt_ctx {
   std::vector<int> bp_cand_lines, bp_parents;
   DevBuf d_bp_raw, d_bp_lines, d_bp_pts, d_bp_off, d_bp_off2, d_bp_off3, d_bp_blk, d_bp_cnt, d_bp_scan, d_bp_out,
       d_bp_inter, d_bp_cand, d_bp_keys, d_bp_keys2, d_bp_idx, d_bp_idx2, d_bp_tmp, d_bp_misc;
+  // ---- line-descriptor matching (lt_match.cpp): the result of the last lt_match_scene ----
+  double mt_timers[4] = {0, 0, 0, 0};             // lt_match_get_timers
+  std::vector<long long> mt_row_off, mt_slot_off; // per pair: its rows / its output slots (lines x kept columns)
+  std::vector<int> mt_kk;                         // per pair: columns kept per line
+  std::vector<unsigned short> mt_col;             // per slot: neighbour line (0xffff: dropped by the mutual test)
+  std::vector<float> mt_score;                    // per slot, only with want_scores
+  bool mt_mutual = false;
+  DevBuf d_mt_desc, d_mt_tasks, d_mt_units, d_mt_col, d_mt_score, d_mt_flag;
 };
 
 #define HIPCHK(ctx, call)                                                                  \

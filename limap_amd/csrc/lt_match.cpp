@@ -1,0 +1,283 @@
+// lt_match.cpp -- line-descriptor matching (limap.line2d: L2D2Matcher, NNEndpointsMatcher top-k) for a whole scene in
+// one call: validation, one upload of the descriptors, the launches of lt_kernels_match.hip on the context's stream,
+// context-owned rows with getters, timers; and the host restatement lt_fn_match_pair_host of the same semantics
+// (std::fmaf in a plain loop).  DESIGN §17.
+
+#include "lt_host.h"
+#include "lt_match.h"
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+using namespace lt;
+using lt_impl::now_ms;
+using lt_impl::upload_vec;
+
+namespace {
+
+int check_config(const lt_match_config *cfg, int dim, std::string &msg) {
+  if (!cfg) { msg = "null configuration"; return 1; }
+  if (cfg->kind != LT_MATCH_L2D2 && cfg->kind != LT_MATCH_ENDPOINTS) { msg = "unknown matcher kind"; return 1; }
+  if (cfg->topk < 0) { msg = "topk is negative"; return 1; }
+  if (cfg->topk > LT_MATCH_MAX_TOPK) { msg = "topk above LT_MATCH_MAX_TOPK (64)"; return 1; }
+  if (cfg->kind == LT_MATCH_ENDPOINTS && cfg->topk == 0) {
+    msg = "the endpoints matcher has no mutual nearest-neighbour form here (topk == 0 is Sinkhorn in limap)";
+    return 1;
+  }
+  if (dim < 8 || dim > LT_MATCH_MAX_DIM || (dim & 7)) {
+    msg = "descriptor width must be a multiple of 8 in [8, 256]";
+    return 1;
+  }
+  return 0;
+}
+
+bool values_ok(const float *v, long long n) {
+  int bad = 0;
+#pragma omp parallel for reduction(| : bad) schedule(static)
+  for (long long k = 0; k < n; ++k) bad |= !(std::fabs(v[k]) <= kMatchMaxAbs);
+  return !bad;
+}
+
+int sync(lt_ctx *ctx) {
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipGetLastError());
+  return LT_OK;
+}
+
+// score(i, j): the fmaf chain in ascending k from +0.0f
+inline float dot_chain(const float *a, const float *b, int dim) {
+  float acc = 0.0f;
+  for (int k = 0; k < dim; ++k) acc = std::fmaf(a[k], b[k], acc);
+  return acc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lt_match_scene(lt_ctx *ctx, int n_img, const int64_t *desc_off, const float *desc, int dim, const int64_t *pair_off,
+                   const int32_t *pair_nb, const lt_match_config *cfg, int64_t *n_rows) {
+  if (!ctx) return LT_ERR_ARGUMENT;
+  const std::string who = "lt_match_scene: ";
+  std::string msg;
+  if (check_config(cfg, dim, msg)) return fail(ctx, LT_ERR_ARGUMENT, who + msg);
+  if (n_img < 0 || !desc_off || !pair_off) return fail(ctx, LT_ERR_ARGUMENT, who + "bad image count or null offsets");
+  if (desc_off[0] != 0 || pair_off[0] != 0) return fail(ctx, LT_ERR_ARGUMENT, who + "offsets must start at 0");
+  const int rpl = cfg->kind == LT_MATCH_ENDPOINTS ? 2 : 1;  // descriptor rows per line
+  for (int m = 0; m < n_img; ++m) {
+    const int64_t n = desc_off[m + 1] - desc_off[m];
+    if (n < 0 || pair_off[m + 1] < pair_off[m]) return fail(ctx, LT_ERR_ARGUMENT, who + "offsets decrease");
+    if (n % rpl) return fail(ctx, LT_ERR_ARGUMENT, who + "an image has an odd number of endpoints");
+    if (n / rpl > kMatchMaxLines) return fail(ctx, LT_ERR_ARGUMENT, who + "more than 65535 lines in an image");
+  }
+  const long long n_desc = desc_off[n_img], n_pairs = pair_off[n_img];
+  if (n_pairs > (1 << 30)) return fail(ctx, LT_ERR_ARGUMENT, who + "too many pairs");
+  if ((n_desc > 0 && !desc) || (n_pairs > 0 && !pair_nb)) return fail(ctx, LT_ERR_ARGUMENT, who + "null input");
+  for (long long p = 0; p < n_pairs; ++p)
+    if (pair_nb[p] < 0 || pair_nb[p] >= n_img) return fail(ctx, LT_ERR_ARGUMENT, who + "a neighbour is not an image");
+  const bool on_dev = cfg->desc_on_device != 0;
+  double t0 = now_ms();
+  if (!on_dev && !values_ok(desc, n_desc * dim))
+    return fail(ctx, LT_ERR_ARGUMENT, who + "a descriptor value is not finite or above 2^57 in magnitude");
+
+  // ---- tasks (a pair each; mutual: the swapped pairs behind them), units, output slots ----
+  const bool mutual = cfg->topk == 0;
+  const int topk = mutual ? 1 : cfg->topk;
+  std::vector<MatchTask> tasks((size_t)n_pairs * (mutual ? 2 : 1));
+  std::vector<long long> &row_off = ctx->mt_row_off;
+  row_off.assign((size_t)n_pairs + 1, 0);
+  long long slots = 0;
+  int kcap = 0;
+  {
+    long long p = 0;
+    for (int m = 0; m < n_img; ++m)
+      for (; p < pair_off[m + 1]; ++p) {
+        const int nb = pair_nb[p];
+        MatchTask &T = tasks[(size_t)p];
+        T.a0 = desc_off[m];
+        T.na = (int)(desc_off[m + 1] - desc_off[m]);
+        T.b0 = desc_off[nb];
+        T.nb = (int)(desc_off[nb + 1] - desc_off[nb]);
+        T.kk = T.na > 0 ? std::min(topk, T.nb / rpl) : 0;
+        T.out0 = slots;
+        T.pad_ = 0;
+        slots += (long long)(T.na / rpl) * T.kk;
+        row_off[(size_t)p + 1] = slots;  // (mutual: an upper bound, replaced below)
+        kcap = std::max(kcap, T.kk);
+      }
+  }
+  const long long fwd_slots = slots;
+  if (mutual)
+    for (long long p = 0; p < n_pairs; ++p) {
+      const MatchTask &F = tasks[(size_t)p];
+      MatchTask &B = tasks[(size_t)(n_pairs + p)];
+      B = MatchTask{F.b0, F.a0, slots, F.nb, F.na, F.kk, 0};
+      slots += (long long)(B.na / rpl) * B.kk;
+    }
+  if (slots >= (1ll << 40)) return fail(ctx, LT_ERR_ARGUMENT, who + "too many result rows");
+  const int waves = kcap ? match_waves(dim, kcap) : 1;
+  std::vector<MatchUnit> units;
+  for (size_t t = 0; t < tasks.size(); ++t)
+    if (tasks[t].kk > 0)
+      for (int r0 = 0; r0 < tasks[t].na; r0 += kMatchTile * waves) units.push_back(MatchUnit{(int)t, r0});
+  if (units.size() > 0x7fffffffull) return fail(ctx, LT_ERR_ARGUMENT, who + "too many row tiles");
+
+  // ---- upload ----
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const float *d_desc = desc;
+  if (!on_dev) {
+    ENSURE(ctx, ctx->d_mt_desc, sizeof(float) * (size_t)std::max<long long>(n_desc * dim, 1));
+    if (n_desc)
+      HIPCHK(ctx, hipMemcpyAsync(ctx->d_mt_desc.p, desc, sizeof(float) * (size_t)(n_desc * dim), hipMemcpyHostToDevice, st));
+    d_desc = ctx->d_mt_desc.as<float>();
+  }
+  if (int rc = upload_vec(ctx, ctx->d_mt_tasks, tasks)) return rc;
+  if (int rc = upload_vec(ctx, ctx->d_mt_units, units)) return rc;
+  ENSURE(ctx, ctx->d_mt_col, 2 * (size_t)std::max<long long>(slots, 1) + 16);
+  ENSURE(ctx, ctx->d_mt_score, 4 * (size_t)std::max<long long>(slots, 1));
+  if (on_dev && n_desc) {  // the same rejection as on the host, by a kernel of its own, before the matching launches
+    ENSURE(ctx, ctx->d_mt_flag, 16);
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_mt_flag.p, 0, 4, st));
+    launch_match_check(st, d_desc, n_desc * dim, ctx->d_mt_flag.as<int>());
+    int flag = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&flag, ctx->d_mt_flag.p, 4, hipMemcpyDeviceToHost, st));
+    if (int rc = sync(ctx)) return rc;
+    if (flag) return fail(ctx, LT_ERR_ARGUMENT, who + "a descriptor value is not finite or above 2^57 in magnitude");
+  }
+  if (int rc = sync(ctx)) return rc;
+  double t1 = now_ms();
+  ctx->mt_timers[0] = t1 - t0;
+
+  // ---- kernels ----
+  launch_match_topk(st, cfg->kind, dim, kcap, waves, ctx->d_mt_tasks.as<MatchTask>(), ctx->d_mt_units.as<MatchUnit>(),
+                    (int)units.size(), d_desc, ctx->d_mt_col.as<unsigned short>(), ctx->d_mt_score.as<float>());
+  if (mutual)
+    launch_match_mutual(st, ctx->d_mt_tasks.as<MatchTask>(), (int)n_pairs, rpl, ctx->d_mt_col.as<unsigned short>());
+  if (int rc = sync(ctx)) return rc;
+  double t2 = now_ms();
+  ctx->mt_timers[1] = t2 - t1;
+
+  // ---- download: 2 bytes per row, the scores only when asked for ----
+  ctx->mt_col.resize((size_t)fwd_slots);
+  ctx->mt_score.clear();
+  if (fwd_slots)
+    HIPCHK(ctx, hipMemcpyAsync(ctx->mt_col.data(), ctx->d_mt_col.p, 2 * (size_t)fwd_slots, hipMemcpyDeviceToHost, st));
+  if (cfg->want_scores && fwd_slots) {
+    ctx->mt_score.resize((size_t)fwd_slots);
+    HIPCHK(ctx, hipMemcpyAsync(ctx->mt_score.data(), ctx->d_mt_score.p, 4 * (size_t)fwd_slots, hipMemcpyDeviceToHost, st));
+  }
+  if (int rc = sync(ctx)) return rc;
+  double t3 = now_ms();
+  ctx->mt_timers[2] = t3 - t2;
+
+  // ---- rows: (line, neighbour line) per slot; mutual keeps the slots that survived ----
+  ctx->mt_kk.resize((size_t)n_pairs);
+  for (long long p = 0; p < n_pairs; ++p) ctx->mt_kk[(size_t)p] = tasks[(size_t)p].kk;
+  ctx->mt_slot_off.assign(row_off.begin(), row_off.end());
+  if (mutual) {
+    for (long long p = 0; p < n_pairs; ++p) {
+      long long n = 0;
+      for (long long s = ctx->mt_slot_off[(size_t)p]; s < ctx->mt_slot_off[(size_t)p + 1]; ++s)
+        n += ctx->mt_col[(size_t)s] != 0xffff;
+      row_off[(size_t)p + 1] = row_off[(size_t)p] + n;
+    }
+  }
+  ctx->mt_mutual = mutual;
+  ctx->mt_timers[3] = now_ms() - t3;
+  if (n_rows) *n_rows = (int64_t)row_off.back();
+  return LT_OK;
+}
+
+int lt_match_get(lt_ctx *ctx, int64_t *row_off, int32_t *rows2) {
+  if (!ctx) return LT_ERR_ARGUMENT;
+  const std::vector<long long> &off = ctx->mt_row_off, &soff = ctx->mt_slot_off;
+  if (row_off) std::copy(off.begin(), off.end(), row_off);
+  if (!rows2 || off.empty()) return LT_OK;
+  const long long n_pairs = (long long)off.size() - 1;
+#pragma omp parallel for schedule(dynamic, 8)
+  for (long long p = 0; p < n_pairs; ++p) {
+    const int kk = ctx->mt_kk[(size_t)p];
+    int32_t *out = rows2 + 2 * off[(size_t)p];
+    for (long long s = soff[(size_t)p]; s < soff[(size_t)p + 1]; ++s) {
+      const unsigned short c = ctx->mt_col[(size_t)s];
+      if (ctx->mt_mutual && c == 0xffff) continue;
+      *out++ = (int32_t)((s - soff[(size_t)p]) / kk);
+      *out++ = (int32_t)c;
+    }
+  }
+  return LT_OK;
+}
+
+int lt_match_get_scores(lt_ctx *ctx, float *scores) {
+  if (!ctx) return LT_ERR_ARGUMENT;
+  if (!scores) return LT_OK;
+  const long long slots = ctx->mt_slot_off.empty() ? 0 : ctx->mt_slot_off.back();
+  if ((long long)ctx->mt_score.size() != slots)
+    return fail(ctx, LT_ERR_STATE, "lt_match_get_scores: the last lt_match_scene did not ask for scores (want_scores)");
+  for (long long s = 0; s < slots; ++s)
+    if (!(ctx->mt_mutual && ctx->mt_col[(size_t)s] == 0xffff)) *scores++ = ctx->mt_score[(size_t)s];
+  return LT_OK;
+}
+
+int lt_match_get_timers(lt_ctx *ctx, double out[4]) {
+  if (!ctx || !out) return LT_ERR_ARGUMENT;
+  for (int k = 0; k < 4; ++k) out[k] = ctx->mt_timers[k];
+  return LT_OK;
+}
+
+int lt_fn_match_pair_host(const float *desc1, int64_t n1, const float *desc2, int64_t n2, int dim,
+                          const lt_match_config *cfg, int32_t *rows2, float *scores, int64_t *n_rows) {
+  std::string msg;
+  if (check_config(cfg, dim, msg) || n1 < 0 || n2 < 0 || !n_rows) return LT_ERR_ARGUMENT;
+  const int rpl = cfg->kind == LT_MATCH_ENDPOINTS ? 2 : 1;
+  if (n1 % rpl || n2 % rpl || n1 / rpl > kMatchMaxLines || n2 / rpl > kMatchMaxLines) return LT_ERR_ARGUMENT;
+  if ((n1 && !desc1) || (n2 && !desc2)) return LT_ERR_ARGUMENT;
+  if (!values_ok(desc1, n1 * dim) || !values_ok(desc2, n2 * dim)) return LT_ERR_ARGUMENT;
+  const long long m1 = n1 / rpl, m2 = n2 / rpl;
+  const bool mutual = cfg->topk == 0;
+  const int kk = (int)std::min<long long>(mutual ? 1 : cfg->topk, m2);
+  *n_rows = 0;
+  if (m1 == 0 || m2 == 0) return LT_OK;
+  auto line_score = [&](long long i, long long j) {
+    if (rpl == 1) return dot_chain(desc1 + i * dim, desc2 + j * dim, dim);
+    const float *a0 = desc1 + 2 * i * dim, *a1 = a0 + dim, *b0 = desc2 + 2 * j * dim, *b1 = b0 + dim;
+    return match_endpoint_score(dot_chain(a0, b0, dim), dot_chain(a1, b1, dim), dot_chain(a0, b1, dim),
+                                dot_chain(a1, b0, dim));
+  };
+  std::vector<unsigned long long> best((size_t)m1 * kk), col_best(mutual ? (size_t)m2 : 0, 0ull);
+#pragma omp parallel
+  {
+    std::vector<unsigned long long> keys((size_t)m2);
+#pragma omp for schedule(static)
+    for (long long i = 0; i < m1; ++i) {
+      for (long long j = 0; j < m2; ++j) keys[(size_t)j] = match_key(line_score(i, j), (unsigned)j);
+      std::partial_sort(keys.begin(), keys.begin() + kk, keys.end(), std::greater<unsigned long long>());
+      std::copy(keys.begin(), keys.begin() + kk, best.begin() + i * kk);
+    }
+    if (mutual) {
+#pragma omp for schedule(static)
+      for (long long j = 0; j < m2; ++j) {
+        unsigned long long b = 0ull;
+        for (long long i = 0; i < m1; ++i) b = std::max(b, match_key(line_score(i, j), (unsigned)i));
+        col_best[(size_t)j] = b;
+      }
+    }
+  }
+  long long n = 0;
+  for (long long i = 0; i < m1; ++i)
+    for (int t = 0; t < kk; ++t) {
+      const unsigned long long key = best[(size_t)(i * kk + t)];
+      const unsigned j = match_key_col(key);
+      if (mutual && match_key_col(col_best[j]) != (unsigned)i) continue;
+      if (rows2) { rows2[2 * n] = (int32_t)i; rows2[2 * n + 1] = (int32_t)j; }
+      if (scores) scores[n] = match_key_score(key);
+      ++n;
+    }
+  *n_rows = n;
+  return LT_OK;
+}
+
+}  // extern "C"

@@ -376,6 +376,37 @@ def gen_matches(scene, img_id, topk=10):
     return out
 
 
+def make_descriptors(scene, kind="l2d2", dim=None, noise=0.05, seed=0):
+    """descinfos of a line-descriptor extractor for a scene: img_id -> {"line_descriptors": (M, dim) float32} (kind
+    "l2d2", dim 128) or {"endpoints_desc": (dim, 2 M) float32} (kind "endpoints", dim 256).  Every observed segment gets
+    the unit descriptor of its GT segment plus Gaussian noise of standard deviation `noise` per component (clutter: a
+    random unit descriptor of its own), normalised again.  Endpoints: one descriptor per GT endpoint, and the endpoint
+    order of an observation is flipped at random, so the larger of the two pairings is the one that matches."""
+    if kind not in ("l2d2", "endpoints"):
+        raise ValueError(f"make_descriptors: unknown kind {kind!r}")
+    per = 1 if kind == "l2d2" else 2
+    dim = (128 if per == 1 else 256) if dim is None else int(dim)
+    rng = np.random.default_rng([int(seed), 4242, per])
+    gt = rng.standard_normal((len(scene.gt_lines), per, dim))
+    gt /= np.linalg.norm(gt, axis=2, keepdims=True)
+    out = {}
+    for idx, img_id in enumerate(scene.img_ids):
+        g = scene.gt_ids[scene.seg_off[idx]:scene.seg_off[idx + 1]]
+        r = np.random.default_rng([int(seed), 4243, int(img_id)])
+        d = r.standard_normal((len(g), per, dim))
+        d /= np.maximum(np.linalg.norm(d, axis=2, keepdims=True), 1e-30)
+        has = g >= 0
+        d[has] = gt[g[has]] + noise * r.standard_normal((int(has.sum()), per, dim))
+        d /= np.maximum(np.linalg.norm(d, axis=2, keepdims=True), 1e-30)
+        if per == 1:
+            out[int(img_id)] = {"line_descriptors": np.ascontiguousarray(d[:, 0], np.float32)}
+        else:
+            flip = r.random(len(g)) < 0.5
+            d[flip] = d[flip][:, ::-1]
+            out[int(img_id)] = {"endpoints_desc": np.ascontiguousarray(d.reshape(-1, dim).T, np.float32)}
+    return out
+
+
 def make_fit_segs(scene, seed=0, depth_noise=0.002, fail_frac=0.1):
     """seg3d_list of a depth fitter (runners/line_fitnmerge.py, `load_fit` form) for a scene: img_id -> (M, 2, 3).
     Each endpoint of a 2D segment is back-projected onto the segment's GT 3D line (scene.gt_ids) -- the point of the
