@@ -522,6 +522,49 @@ int lt_match_get_timers(lt_ctx *ctx, double out[4]);
 int lt_fn_match_pair_host(const float *desc1, int64_t n1, const float *desc2, int64_t n2, int dim,
                           const lt_match_config *cfg, int32_t *rows2, float *scores, int64_t *n_rows);
 
+/* ---- limap.vplib: the JLinkage vanishing-point detector (vplib/JLinkage/JLinkage.cc, vplib/base_vp_detector.cc) for a
+ * batch of images per call.  Images as CSR over lines, as for lt_bpt_*.  limap's own code around
+ * the two calls into its J-Linkage third party is reproduced bit for bit: the `length() < min_length` filter, endpoints
+ * rounded to FP32, the guard `valid lines < 2 * max(min_num_supports, 10)` (all labels -1), per cluster the size test and
+ * count_valid_supports_2d, the compaction of the surviving clusters in label order, fitVP (the third right singular
+ * vector of the rows Line2d::coords(), normalised) and AssociateVPs.  The two calls themselves -- upstream samples
+ * 5000 hypotheses at random -- are this project's deterministic definition: hypothesis m is the cross product of the
+ * lines (a, b) a counter-based generator draws from (seed, m) and the number of valid lines; a line prefers the
+ * hypotheses within inlier_threshold by Tardif's measure; clusters merge by the greatest Jaccard ratio of their
+ * preference sets, ties to the smallest (i, j), until no two sets intersect.  Labels therefore do not equal those of a
+ * particular upstream run.  th_perp_supports is carried for as_dict only: upstream's count_valid_supports_2d reads the
+ * base class's default-constructed configuration, so 3.0 is used whatever the value (section 18).
+ * LT_ERR_ARGUMENT before any launch: non-finite coordinates, a NaN threshold, min_num_supports outside [3, 2^20] (fitVP
+ * is undefined below three lines), num_hypotheses outside [1, 2^20]; after the clustering: a support line on which a
+ * check of InfiniteLine2d throws upstream. */
+typedef struct lt_vp_config {
+  double min_length;        /* 40, pixels */
+  double inlier_threshold;  /* 1.0, pixels */
+  double th_perp_supports;  /* 3.0, pixels (see above) */
+  int32_t min_num_supports; /* 5 */
+  int32_t num_hypotheses;   /* 5000 (JLinkage.cc:44); not a key of upstream's configuration */
+  uint64_t seed;            /* 0; not a key of upstream's configuration */
+} lt_vp_config;
+void lt_vp_config_default(lt_vp_config *cfg);
+/* The result stays in the context: n_vps (may be NULL) receives the number of vanishing points of all images; lt_vp_get
+ * copies out (any pointer may be NULL) labels[line_off[n_img]] (VPResult::labels, -1: none), vp_off[n_img + 1],
+ * vps[3 n_vps] and clusters[line_off[n_img]]: the cluster of every line before the filters (the third party's Labels;
+ * -1 for a line the length filter or the guard dropped). */
+int lt_vp_detect(lt_ctx *ctx, int n_img, const int64_t *line_off, const double *lines, const lt_vp_config *cfg,
+                 int64_t *n_vps);
+int lt_vp_get(lt_ctx *ctx, int32_t *labels, int64_t *vp_off, double *vps, int32_t *clusters);
+/* of the last lt_vp_detect: host ms of [0] upload, length filter and tables, [1] kernels, [2] download, [3] host tail;
+ * device ms (HIP events) of [4] the preference kernel, [5] the clustering kernel */
+int lt_vp_get_timers(lt_ctx *ctx, double out[6]);
+/* The whole detector on the host, no context and no device: the same expressions and the same order, images spread
+ * over n_threads OpenMP threads (0: the default).  vps has room for vps_cap vanishing points (sum over the images of
+ * lines / 3 always suffices); LT_ERR_ARGUMENT when it does not. */
+int lt_fn_vp_detect_host(int n_img, const int64_t *line_off, const double *lines, const lt_vp_config *cfg, int n_threads,
+                         int32_t *labels, int64_t *vp_off, double *vps, int64_t vps_cap, int32_t *clusters);
+/* The clustering alone on the host, for tests: pref is n rows of n_words 64-bit words (the preference sets), roots[n]
+ * receives the id of the cluster every row ends in (the smallest row index of the cluster). */
+int lt_fn_vp_cluster_host(int64_t n, int64_t n_words, const uint64_t *pref, int32_t *roots);
+
 /* Counters of the last device run: [0] connections tested, [1] candidates, [2] ordered candidate
  * pairs swept by the scoring kernel (sum n_tris^2), [3] valid edges, [4] graph nodes,
  * [5] graph edges, [6] tracks, [7] nodes. */

@@ -37,6 +37,8 @@ EXPORTED_SYMBOLS = [
     "lt_bpt_config_default", "lt_bpt_associate", "lt_bpt_associate_get", "lt_bpt_junctions", "lt_bpt_junctions_get",
     "lt_bpt_junctions_get_candidates", "lt_bpt_get_timers",
     "lt_match_scene", "lt_match_get", "lt_match_get_scores", "lt_match_get_timers", "lt_fn_match_pair_host",
+    "lt_vp_config_default", "lt_vp_detect", "lt_vp_get", "lt_vp_get_timers", "lt_fn_vp_detect_host",
+    "lt_fn_vp_cluster_host",
 ]
 
 
@@ -136,6 +138,12 @@ class LtBptConfig(C.Structure):
 class LtMatchConfig(C.Structure):
     """lt_match_config of include/limap_amd.h"""
     _fields_ = [("kind", C.c_int32), ("topk", C.c_int32), ("desc_on_device", C.c_int32), ("want_scores", C.c_int32)]
+
+
+class LtVpConfig(C.Structure):
+    """lt_vp_config of include/limap_amd.h"""
+    _fields_ = [("min_length", C.c_double), ("inlier_threshold", C.c_double), ("th_perp_supports", C.c_double),
+                ("min_num_supports", C.c_int32), ("num_hypotheses", C.c_int32), ("seed", C.c_uint64)]
 
 
 def load_library():
@@ -277,6 +285,13 @@ def load_library():
     L.lt_match_get_scores.argtypes = [vp, fp]
     L.lt_match_get_timers.argtypes = [vp, dp]
     L.lt_fn_match_pair_host.argtypes = [fp, C.c_int64, fp, C.c_int64, C.c_int, C.POINTER(LtMatchConfig), i32p, fp, i64p]
+    L.lt_vp_config_default.argtypes = [C.POINTER(LtVpConfig)]
+    L.lt_vp_config_default.restype = None
+    L.lt_vp_detect.argtypes = [vp, C.c_int, i64p, dp, C.POINTER(LtVpConfig), i64p]
+    L.lt_vp_get.argtypes = [vp, i32p, i64p, dp, i32p]
+    L.lt_vp_get_timers.argtypes = [vp, dp]
+    L.lt_fn_vp_detect_host.argtypes = [C.c_int, i64p, dp, C.POINTER(LtVpConfig), C.c_int, i32p, i64p, dp, C.c_int64, i32p]
+    L.lt_fn_vp_cluster_host.argtypes = [C.c_int64, C.c_int64, C.POINTER(C.c_uint64), i32p]
     _lib = L
     return L
 

@@ -421,6 +421,12 @@ struct lt_ctx {
   std::vector<float> mt_score;                    // per slot, only with want_scores
   bool mt_mutual = false;
   DevBuf d_mt_desc, d_mt_tasks, d_mt_units, d_mt_col, d_mt_score, d_mt_flag;
+  // ---- vanishing-point detection (lt_vp.cpp): the result of the last lt_vp_detect ----
+  double vp_timers[6] = {0, 0, 0, 0, 0, 0};  // lt_vp_get_timers
+  std::vector<int> vp_labels, vp_clusters;   // per line: VPResult::labels, the cluster before the filters
+  std::vector<long long> vp_vp_off;          // per image its vanishing points
+  std::vector<double> vp_vps;
+  DevBuf d_vp_raw, d_vp_flag, d_vp_src, d_vp_lines, d_vp_imgs, d_vp_blk, d_vp_hyp, d_vp_pref, d_vp_state, d_vp_roots;
 };
 
 #define HIPCHK(ctx, call)                                                                  \

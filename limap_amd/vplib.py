@@ -1,0 +1,251 @@
+"""limap.vplib on the GPU: the JLinkage vanishing-point detector with ``VPResult``, its config and
+``get_vp_detector`` (vplib/bindings.cc, vpbase.h, base_vp_detector.{h,cc,py}, JLinkage/JLinkage.{h,cc,py},
+register_vp_detector.py of limap; names and defaults follow them), plus a whole-scene call -- one set of launches for all
+images instead of one serial pass per image spread over joblib processes:
+
+    from limap_amd import vplib
+    vpdetector = vplib.get_vp_detector(cfg["vpdet_config"], n_jobs=cfg["n_jobs"])
+    vpresults = vpdetector.detect_vp_all_images(all_2d_lines, camviews)        # img_id -> VPResult
+    triangulator.InitVPResults(vpresults)                                      # use_vp without limap
+
+limap's own code around its J-Linkage third party (length filter, FP32 endpoints, the guard, the cluster filters,
+``count_valid_supports_2d``, ``fitVP``, ``AssociateVPs``) is reproduced bit for bit.  The third party itself samples
+its hypotheses at random, so no fixed output exists to equal: hypotheses, consistency test and clustering order are
+this project's deterministic definition, computed by the HIP kernels of lt_kernels_vp.hip and,
+identically, by a host path (``detect_vps_host``).  Two configuration keys are new: ``num_hypotheses`` (5000) and
+``seed`` (0); upstream ignores both, as it ignores every unknown key.  ``GlobalVPTrackConstructor``, the VP-line
+bipartites and Progressive-X are out of scope.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _capi
+from .structures import lines2d_array
+
+__all__ = ["VPResult", "BaseVPDetectorConfig", "BaseVPDetectorOptions", "DefaultVPDetectorOptions", "JLinkageConfig",
+           "JLinkage", "get_vp_detector", "detect_vps", "detect_vps_host", "timers"]
+
+_contexts = {}
+
+
+def _context(device=0):
+    ctx = _contexts.get(device)
+    if ctx is None:
+        ctx = _contexts[device] = _capi.Context(device=device)
+    return ctx
+
+
+def _p(a, t=C.c_double):
+    return a.ctypes.data_as(C.POINTER(t))
+
+
+class VPResult:
+    """vplib/vpbase.h:18-47: ``labels`` (one per line, -1: no vanishing point) and ``vps`` (homogeneous, unit norm)"""
+
+    def __init__(self, labels=None, vps=None):
+        if isinstance(labels, VPResult):
+            labels, vps = labels.labels, labels.vps
+        elif isinstance(labels, dict):  # ASSIGN_PYDICT_ITEM: a missing key keeps the empty default
+            labels, vps = labels.get("labels"), labels.get("vps")
+        self.labels = [] if labels is None else [int(x) for x in labels]
+        self.vps = [] if vps is None else [np.array(v, np.float64).reshape(3) for v in vps]
+
+    def as_dict(self):
+        return {"labels": list(self.labels), "vps": [v.copy() for v in self.vps]}
+
+    def count_lines(self):
+        return len(self.labels)
+
+    def count_vps(self):
+        return len(self.vps)
+
+    def GetVPLabel(self, line_id):
+        return self.labels[line_id]
+
+    def GetVPbyCluster(self, vp_id):
+        return self.vps[vp_id]
+
+    def HasVP(self, line_id):
+        return self.GetVPLabel(line_id) >= 0
+
+    def GetVP(self, line_id):
+        if not self.HasVP(line_id):
+            raise ValueError("Check failed: HasVP(line_id) == true")
+        return self.GetVPbyCluster(self.GetVPLabel(line_id))
+
+
+class BaseVPDetectorConfig:
+    """vplib/base_vp_detector.h:20-35: keys that are present overwrite the defaults, unknown keys are ignored.
+    ``num_hypotheses`` and ``seed`` are this backend's own keys; ``as_dict`` lists upstream's four."""
+
+    KEYS = (("min_length", float), ("inlier_threshold", float), ("min_num_supports", int), ("th_perp_supports", float))
+    OWN_KEYS = (("num_hypotheses", int), ("seed", int))
+
+    def __init__(self, d=None):
+        self.min_length = 40.0
+        self.inlier_threshold = 1.0
+        self.min_num_supports = 5
+        self.th_perp_supports = 3.0
+        self.num_hypotheses = 5000
+        self.seed = 0
+        if isinstance(d, BaseVPDetectorConfig):
+            d = dict(d.as_dict(), num_hypotheses=d.num_hypotheses, seed=d.seed)
+        for k, t in self.KEYS + self.OWN_KEYS:
+            if d and k in d:
+                setattr(self, k, t(d[k]))
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self.KEYS}
+
+    def _struct(self):
+        return _capi.LtVpConfig(self.min_length, self.inlier_threshold, self.th_perp_supports, self.min_num_supports,
+                                self.num_hypotheses, self.seed & 0xFFFFFFFFFFFFFFFF)
+
+
+class JLinkageConfig(BaseVPDetectorConfig):
+    """vplib/JLinkage/JLinkage.h:18-23"""
+
+
+class BaseVPDetectorOptions:
+    """vplib/base_vp_detector.py:7-15 (a NamedTuple there): ``n_jobs`` is kept for the signature; the whole scene is one
+    native call here"""
+
+    def __init__(self, n_jobs=1):
+        self.n_jobs = n_jobs
+
+    def _replace(self, **kw):
+        return BaseVPDetectorOptions(**{"n_jobs": self.n_jobs, **kw})
+
+
+DefaultVPDetectorOptions = BaseVPDetectorOptions()
+
+
+def _cfg(cfg):
+    return cfg if isinstance(cfg, BaseVPDetectorConfig) else BaseVPDetectorConfig(cfg)
+
+
+def _csr(parts):
+    off = np.zeros(len(parts) + 1, np.int64)
+    for k, a in enumerate(parts):
+        off[k + 1] = off[k] + a.shape[0]
+    flat = np.ascontiguousarray(np.concatenate(parts, 0), np.float64) if off[-1] else np.zeros((1, 4))
+    return off, flat
+
+
+def _split(off, labels, vp_off, vps, clusters, want_clusters):
+    out = []
+    for m in range(len(off) - 1):
+        r = VPResult(labels[off[m]:off[m + 1]].tolist(), vps[vp_off[m]:vp_off[m + 1]])
+        out.append((r, clusters[off[m]:off[m + 1]].copy()) if want_clusters else r)
+    return out
+
+
+def _detect(lines_list, cfg, device=0, clusters=False):
+    """one native call for the batch -> list of VPResult (with clusters: of (VPResult, cluster of every line))"""
+    if not lines_list:
+        return []
+    ctx = _context(device)
+    off, flat = _csr(lines_list)
+    st = cfg._struct()
+    n_vps = C.c_int64(0)
+    ctx.chk(ctx.L.lt_vp_detect(ctx.h, len(lines_list), _p(off, C.c_int64), _p(flat), C.byref(st), C.byref(n_vps)))
+    labels = np.zeros(max(int(off[-1]), 1), np.int32)
+    clu = np.zeros(max(int(off[-1]), 1), np.int32)
+    vp_off = np.zeros(len(lines_list) + 1, np.int64)
+    vps = np.zeros((max(n_vps.value, 1), 3))
+    ctx.chk(ctx.L.lt_vp_get(ctx.h, _p(labels, C.c_int32), _p(vp_off, C.c_int64), _p(vps), _p(clu, C.c_int32)))
+    return _split(off, labels, vp_off, vps, clu, clusters)
+
+
+def _detect_host(lines_list, cfg, n_threads=0, clusters=False):
+    if not lines_list:
+        return []
+    L = _capi.load_library()
+    off, flat = _csr(lines_list)
+    st = cfg._struct()
+    cap = int(sum(a.shape[0] // 3 for a in lines_list)) + 1
+    labels = np.zeros(max(int(off[-1]), 1), np.int32)
+    clu = np.zeros(max(int(off[-1]), 1), np.int32)
+    vp_off = np.zeros(len(lines_list) + 1, np.int64)
+    vps = np.zeros((cap, 3))
+    rc = L.lt_fn_vp_detect_host(len(lines_list), _p(off, C.c_int64), _p(flat), C.byref(st), int(n_threads),
+                                _p(labels, C.c_int32), _p(vp_off, C.c_int64), _p(vps), cap, _p(clu, C.c_int32))
+    if rc != 0:
+        raise ValueError("lt_fn_vp_detect_host: bad configuration or lines (see lt_vp_config in include/limap_amd.h), "
+                         "or a check of InfiniteLine2d fails on a support line")
+    return _split(off, labels, vp_off, vps, clu, clusters)
+
+
+def detect_vps(all_2d_lines, cfg=None, device=0):
+    """AssociateVPs for every image of ``all_2d_lines`` (dict img_id -> lines in any form structures.lines2d_array
+    accepts) in one native call.  Returns dict img_id -> VPResult in the key order of ``all_2d_lines``.  The result of an
+    image does not depend on the other images of the call."""
+    cfg = _cfg(cfg)
+    keys = list(all_2d_lines.keys())
+    res = _detect([lines2d_array(all_2d_lines[k]) for k in keys], cfg, device)
+    return dict(zip(keys, res))
+
+
+def detect_vps_host(all_2d_lines, cfg=None, n_threads=0):
+    """``detect_vps`` by the host path of the library (no device): the same results bit for bit, for tests and timing"""
+    cfg = _cfg(cfg)
+    keys = list(all_2d_lines.keys())
+    res = _detect_host([lines2d_array(all_2d_lines[k]) for k in keys], cfg, n_threads)
+    return dict(zip(keys, res))
+
+
+def timers(device=0):
+    """lt_vp_get_timers of the last device call: host ms of upload + length filter, kernels, download, host tail; device
+    ms of the preference kernel and of the clustering kernel"""
+    out = np.zeros(6)
+    ctx = _context(device)
+    ctx.chk(ctx.L.lt_vp_get_timers(ctx.h, _p(out)))
+    return out
+
+
+class BaseVPDetector:
+    """vplib/base_vp_detector.py:21-78"""
+
+    def __init__(self, options=DefaultVPDetectorOptions):
+        self.n_jobs = options.n_jobs
+
+    def get_module_name(self):
+        raise NotImplementedError
+
+    def detect_vp(self, lines, camview=None):
+        raise NotImplementedError
+
+    def detect_vp_all_images(self, all_lines, camviews=None):
+        return {img_id: self.detect_vp(lines, None if camviews is None else camviews[img_id])
+                for img_id, lines in all_lines.items()}
+
+
+class JLinkage(BaseVPDetector):
+    """vplib/JLinkage/JLinkage.py: ``cfg_jlinkage`` is the ``vpdet_config`` dict (or a config object)"""
+
+    def __init__(self, cfg_jlinkage=None, options=DefaultVPDetectorOptions, device=0):
+        super().__init__(options)
+        self.config_ = JLinkageConfig(cfg_jlinkage)
+        self.device = int(device)
+
+    def as_dict(self):
+        return self.config_.as_dict()
+
+    def get_module_name(self):
+        return "JLinkage"
+
+    def detect_vp(self, lines, camview=None):
+        return _detect([lines2d_array(lines)], self.config_, self.device)[0]
+
+    def detect_vp_all_images(self, all_lines, camviews=None):
+        return detect_vps(all_lines, self.config_, self.device)
+
+
+def get_vp_detector(cfg_vp_detector, n_jobs=1):
+    """vplib/register_vp_detector.py: the detector named by cfg_vp_detector["method"]"""
+    options = BaseVPDetectorOptions()._replace(n_jobs=n_jobs)
+    method = cfg_vp_detector["method"]
+    if method == "jlinkage":
+        return JLinkage(cfg_vp_detector, options)
+    raise NotImplementedError  # "progressivex" (a learned third party) and anything else
