@@ -564,6 +564,13 @@ int lt_fn_vp_detect_host(int n_img, const int64_t *line_off, const double *lines
 /* The clustering alone on the host, for tests: pref is n rows of n_words 64-bit words (the preference sets), roots[n]
  * receives the id of the cluster every row ends in (the smallest row index of the cluster). */
 int lt_fn_vp_cluster_host(int64_t n, int64_t n_words, const uint64_t *pref, int32_t *roots);
+/* Its device twin, for tests: the clustering kernel of lt_vp_detect alone (same launch, same buffers of the context) on
+ * preference sets the caller supplies, a batch of images per call.  pref is row_off[n_img] rows of n_words words in the
+ * layout above, image m owning the rows [row_off[m], row_off[m + 1]); roots[k] is the cluster row k ends in, as an index
+ * within its own image.  Images of 0 or 1 rows are legal.  LT_ERR_ARGUMENT before any launch: null pointers where rows
+ * exist, offsets that do not start at 0 or decrease, n_words outside [1, 2^14], more than 2^32 words in the call. */
+int lt_vp_cluster_sets(lt_ctx *ctx, int n_img, const int64_t *row_off, int64_t n_words, const uint64_t *pref,
+                       int32_t *roots);
 
 /* Counters of the last device run: [0] connections tested, [1] candidates, [2] ordered candidate
  * pairs swept by the scoring kernel (sum n_tris^2), [3] valid edges, [4] graph nodes,

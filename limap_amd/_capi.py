@@ -38,7 +38,7 @@ EXPORTED_SYMBOLS = [
     "lt_bpt_junctions_get_candidates", "lt_bpt_get_timers",
     "lt_match_scene", "lt_match_get", "lt_match_get_scores", "lt_match_get_timers", "lt_fn_match_pair_host",
     "lt_vp_config_default", "lt_vp_detect", "lt_vp_get", "lt_vp_get_timers", "lt_fn_vp_detect_host",
-    "lt_fn_vp_cluster_host",
+    "lt_fn_vp_cluster_host", "lt_vp_cluster_sets",
 ]
 
 
@@ -292,6 +292,7 @@ def load_library():
     L.lt_vp_get_timers.argtypes = [vp, dp]
     L.lt_fn_vp_detect_host.argtypes = [C.c_int, i64p, dp, C.POINTER(LtVpConfig), C.c_int, i32p, i64p, dp, C.c_int64, i32p]
     L.lt_fn_vp_cluster_host.argtypes = [C.c_int64, C.c_int64, C.POINTER(C.c_uint64), i32p]
+    L.lt_vp_cluster_sets.argtypes = [vp, C.c_int, i64p, C.c_int64, C.POINTER(C.c_uint64), i32p]
     _lib = L
     return L
 

@@ -33,11 +33,12 @@ __global__ void __launch_bounds__(kVpBlock) k_vp_lines(const double *__restrict_
   out[s] = vp_line(lines4[4 * k], lines4[4 * k + 1], lines4[4 * k + 2], lines4[4 * k + 3]);
 }
 
-// grid: (ceil(n_hyp / kVpBlock), images)
-__global__ void __launch_bounds__(kVpBlock) k_vp_hyp(const VpImg *__restrict__ imgs, int n_hyp, unsigned long long seed,
-                                                     const VpLine *__restrict__ lines, VpHyp *__restrict__ hyp) {
-  const VpImg im = imgs[blockIdx.y];
-  const int m = (int)blockIdx.x * kVpBlock + (int)threadIdx.x;
+// grid: images x ceil(n_hyp / kVpBlock) workgroups in x, an image's workgroups next to each other
+__global__ void __launch_bounds__(kVpBlock) k_vp_hyp(const VpImg *__restrict__ imgs, int n_hyp, int blocks_per_img,
+                                                     unsigned long long seed, const VpLine *__restrict__ lines,
+                                                     VpHyp *__restrict__ hyp) {
+  const VpImg im = imgs[blockIdx.x / (unsigned)blocks_per_img];
+  const int m = (int)(blockIdx.x % (unsigned)blocks_per_img) * kVpBlock + (int)threadIdx.x;
   if (m >= n_hyp || im.n < 2) return;
   unsigned a, b;
   vp_sample(seed, (unsigned long long)m, (unsigned)im.n, &a, &b);
@@ -223,7 +224,9 @@ void launch_vp_lines(hipStream_t st, const double *lines4, const long long *src,
 void launch_vp_hyp(hipStream_t st, const VpImg *imgs, int n_act, int n_hyp, unsigned long long seed, const VpLine *lines,
                    VpHyp *hyp) {
   if (n_act <= 0 || n_hyp <= 0) return;
-  hipLaunchKernelGGL(k_vp_hyp, dim3(grid_of(n_hyp), n_act), dim3(kVpBlock), 0, st, imgs, n_hyp, seed, lines, hyp);
+  const int per_img = grid_of(n_hyp);  // the caller keeps n_act * per_img within a launch (vp_launch_fits)
+  hipLaunchKernelGGL(k_vp_hyp, dim3((unsigned)((long long)n_act * per_img)), dim3(kVpBlock), 0, st, imgs, n_hyp, per_img,
+                     seed, lines, hyp);
 }
 
 void launch_vp_pref(hipStream_t st, const VpBlock *blk, int n_blk, const VpImg *imgs, int n_hyp, int n_words, double th,

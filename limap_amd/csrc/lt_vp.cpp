@@ -349,6 +349,8 @@ int lt_vp_detect(lt_ctx *ctx, int n_img, const int64_t *line_off, const double *
   ctx->vp_vps.clear();
   if (n_vps) *n_vps = 0;
   if (nl == 0) return LT_OK;
+  const char *too_large = ": the scene is too large for one call (split the images)";
+  if (!vp_launch_fits((nl + kVpBlock - 1) / kVpBlock, kVpBlock)) return fail(ctx, LT_ERR_ARGUMENT, who + too_large);
 
   // ---- upload, length filter ----
   double t0 = now_ms();
@@ -386,8 +388,10 @@ int lt_vp_detect(lt_ctx *ctx, int n_img, const int64_t *line_off, const double *
   const int n_act = (int)imgs.size();
   std::vector<int> roots((size_t)nv);
   if (n_act > 0) {
-    if (imgs.size() * (size_t)M > (size_t)1 << 31 || (size_t)nv * (size_t)W > (size_t)1 << 32 || blocks.size() > (size_t)INT_MAX)
-      return fail(ctx, LT_ERR_ARGUMENT, who + ": the scene is too large for one call (split the images)");
+    if (imgs.size() * (size_t)M > (size_t)1 << 31 || (size_t)nv * (size_t)W > (size_t)1 << 32 ||
+        !vp_launch_fits((long long)blocks.size(), kVpBlock) || !vp_launch_fits(n_act, kVpClBlock) ||
+        !vp_launch_fits((long long)n_act * ((M + kVpBlock - 1) / kVpBlock), kVpBlock))
+      return fail(ctx, LT_ERR_ARGUMENT, who + too_large);
     if (int rc = upload_vec(ctx, ctx->d_vp_src, src)) return rc;
     if (int rc = upload_vec(ctx, ctx->d_vp_imgs, imgs)) return rc;
     if (int rc = upload_vec(ctx, ctx->d_vp_blk, blocks)) return rc;
@@ -510,6 +514,56 @@ int lt_fn_vp_detect_host(int n_img, const int64_t *line_off, const double *lines
   if (clusters) std::copy(clu.begin(), clu.end(), clusters);
   std::copy(off.begin(), off.end(), vp_off);
   if (vps) std::copy(v.begin(), v.end(), vps);
+  return LT_OK;
+}
+
+int lt_vp_cluster_sets(lt_ctx *ctx, int n_img, const int64_t *row_off, int64_t n_words, const uint64_t *pref,
+                       int32_t *roots) {
+  if (!ctx) return LT_ERR_ARGUMENT;
+  const std::string who = "lt_vp_cluster_sets";
+  if (n_img < 0) return fail(ctx, LT_ERR_ARGUMENT, who + ": bad image count");
+  if (!row_off) return fail(ctx, LT_ERR_ARGUMENT, who + ": null row offsets");
+  if (row_off[0] != 0) return fail(ctx, LT_ERR_ARGUMENT, who + ": row offsets must start at 0");
+  for (int m = 0; m < n_img; ++m) {
+    if (row_off[m + 1] < row_off[m]) return fail(ctx, LT_ERR_ARGUMENT, who + ": row offsets decrease");
+    if (row_off[m + 1] - row_off[m] > INT_MAX / 2) return fail(ctx, LT_ERR_ARGUMENT, who + ": too many rows in an image");
+  }
+  if (n_words < 1 || n_words > kVpMaxHypotheses / 64)
+    return fail(ctx, LT_ERR_ARGUMENT, who + ": n_words outside [1, 2^14]");
+  const long long nv = row_off[n_img];
+  if (nv == 0) return LT_OK;
+  if (!pref || !roots) return fail(ctx, LT_ERR_ARGUMENT, who + ": null preference sets or roots");
+  const int W = (int)n_words;
+  if ((size_t)nv * (size_t)W > (size_t)1 << 32 || !vp_launch_fits(n_img, kVpClBlock))
+    return fail(ctx, LT_ERR_ARGUMENT, who + ": the scene is too large for one call (split the images)");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  // the VpImg table and the kernel's word-major layout (lt_vp.h), as lt_vp_detect leaves them for k_vp_cluster
+  std::vector<VpImg> imgs((size_t)n_img);
+  std::vector<unsigned long long> P((size_t)nv * (size_t)W);
+  for (int m = 0; m < n_img; ++m) {
+    VpImg &im = imgs[(size_t)m];
+    im.v0 = row_off[m];
+    im.p0 = im.v0 * W;
+    im.h0 = 0;
+    im.n = (int)(row_off[m + 1] - row_off[m]);
+    im.pad_ = 0;
+    for (int k = 0; k < im.n; ++k)
+      for (int w = 0; w < W; ++w)
+        P[(size_t)(im.p0 + (long long)w * im.n + k)] = pref[(size_t)(im.v0 + k) * (size_t)W + (size_t)w];
+  }
+  if (int rc = upload_vec(ctx, ctx->d_vp_imgs, imgs)) return rc;
+  if (int rc = upload_vec(ctx, ctx->d_vp_pref, P)) return rc;
+  ENSURE(ctx, ctx->d_vp_state, 4 * (size_t)kVpStateInts * (size_t)nv);
+  ENSURE(ctx, ctx->d_vp_roots, 4 * (size_t)nv);
+  launch_vp_cluster(st, ctx->d_vp_imgs.as<VpImg>(), n_img, W, ctx->d_vp_pref.as<unsigned long long>(),
+                    ctx->d_vp_state.as<int>(), ctx->d_vp_roots.as<int>());
+  HIPCHK(ctx, hipMemcpyAsync(roots, ctx->d_vp_roots.p, 4 * (size_t)nv, hipMemcpyDeviceToHost, st));
+  if (int rc = sync(ctx)) return rc;
+  for (int m = 0; m < n_img; ++m)
+    for (long long k = row_off[m]; k < row_off[m + 1]; ++k)
+      if (roots[k] < 0 || roots[k] >= imgs[(size_t)m].n)
+        return fail(ctx, LT_ERR_RUNTIME, who + ": the clustering kernel returned a cluster out of range");
   return LT_OK;
 }
 

@@ -6,6 +6,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <climits>
+
 namespace lt {
 
 constexpr int kVpBlock = 256;          // lanes per workgroup of k_vp_prep / k_vp_lines / k_vp_hyp / k_vp_pref
@@ -101,6 +103,9 @@ LT_VP_HD bool vp_better(int c1, int u1, int i1, int j1, int c2, int u2, int i2, 
   if (i1 != i2) return i1 < i2;
   return j1 < j2;
 }
+
+// a launch carries its size per dimension (workgroups x lanes) in 32 bits: the callers keep every launch below 2^31
+inline bool vp_launch_fits(long long workgroups, int lanes) { return workgroups <= (long long)INT_MAX / lanes; }
 
 // flag[k] = !(length(line k) < min_length)
 void launch_vp_prep(hipStream_t st, const double *lines4, long long n_lines, double min_length, unsigned char *flag);

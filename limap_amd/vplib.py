@@ -177,6 +177,23 @@ def _detect_host(lines_list, cfg, n_threads=0, clusters=False):
     return _split(off, labels, vp_off, vps, clu, clusters)
 
 
+def _cluster_sets(words_list, device=0):
+    """lt_vp_cluster_sets: the clustering kernel alone on caller-supplied preference sets, one (rows, words) uint64 array
+    per image (the same width in all) -> list of the int32 roots of every image.  For tests."""
+    if not words_list:
+        return []
+    ctx = _context(device)
+    off = np.zeros(len(words_list) + 1, np.int64)
+    off[1:] = np.cumsum([a.shape[0] for a in words_list])
+    n_words = words_list[0].shape[1]
+    assert all(a.ndim == 2 and a.shape[1] == n_words for a in words_list)
+    flat = np.ascontiguousarray(np.concatenate(words_list, 0), np.uint64) if off[-1] else np.zeros((1, n_words), np.uint64)
+    roots = np.zeros(max(int(off[-1]), 1), np.int32)
+    ctx.chk(ctx.L.lt_vp_cluster_sets(ctx.h, len(words_list), _p(off, C.c_int64), n_words, _p(flat, C.c_uint64),
+                                     _p(roots, C.c_int32)))
+    return [roots[off[m]:off[m + 1]].copy() for m in range(len(words_list))]
+
+
 def detect_vps(all_2d_lines, cfg=None, device=0):
     """AssociateVPs for every image of ``all_2d_lines`` (dict img_id -> lines in any form structures.lines2d_array
     accepts) in one native call.  Returns dict img_id -> VPResult in the key order of ``all_2d_lines``.  The result of an

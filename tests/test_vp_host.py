@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import vp_cluster_cases as vcc
 import vp_oracle as vo
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "vp")
@@ -169,6 +170,57 @@ def test_clustering_random_sets_host_equals_oracle(gpu_lib):
     for n, m, p in ((40, 70, 0.2), (25, 130, 0.5), (60, 64, 0.05)):
         pref = rng.random((n, m)) < p
         assert _lib_cluster(gpu_lib, pref).tolist() == vo.cluster(pref).tolist()
+
+
+def host_cluster(gpu_lib, pref):
+    """lt_fn_vp_cluster_host on an (n, M) bool matrix"""
+    words = vcc.pack(pref)
+    n, w = words.shape
+    roots = np.zeros(max(n, 1), np.int32)
+    rc = gpu_lib.lt_fn_vp_cluster_host(n, w, words.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                       roots.ctypes.data_as(C.POINTER(C.c_int32)))
+    assert rc == 0
+    return roots[:n]
+
+
+def test_pack_is_the_layout_of_the_known_answers(gpu_lib):
+    rng = np.random.default_rng(12)
+    pref = rng.random((9, 130)) < 0.3
+    words = vcc.pack(pref)
+    assert words.shape == (9, 3) and words.dtype == np.uint64
+    for k in range(9):
+        for b in range(130):
+            assert bool((int(words[k, b // 64]) >> (b % 64)) & 1) == bool(pref[k, b])
+    assert np.array_equal(host_cluster(gpu_lib, pref), _lib_cluster(gpu_lib, pref))
+
+
+# the members of 2047 rows and more take the oracle 2.5 - 8 s each, 62 s together: they run in tests/test_gpu_vp_cluster.py, where the host
+# twin is compared with the oracle on them as well
+HOST_CASES = vcc.all_cases(large=False)
+
+
+@pytest.mark.parametrize("name,pref", HOST_CASES, ids=[c[0] for c in HOST_CASES])
+def test_clustering_case_families_host_equals_oracle(gpu_lib, name, pref):
+    assert np.array_equal(host_cluster(gpu_lib, pref), vo.cluster(pref))
+
+
+def test_case_families_are_what_they_claim():
+    cases = dict(vcc.all_cases())
+    assert {n for n in vcc.RANDOM_N if n > vcc.LDS_CLUSTERS} == {2049, 2600}
+    for n in vcc.RANDOM_N:
+        for p in vcc.RANDOM_P:
+            assert cases[f"random_n{n}_p{p}"].shape[0] == n
+    assert all(cases[f"ties_n{n}"].all(0).sum() == 3 for n in (2, 3, 64, 65, 130))
+    assert {m for m in (1, 63, 64, 65, 128, 5000)} == {cases[f"edge_bits_m{m}"].shape[1] for m in (1, 63, 64, 65, 128, 5000)}
+    e = cases["empty_n50_m40"]
+    assert not e[0].any() and not e[-1].any() and not e[10:20].any() and e.any(1).sum() > 20
+    d = vo.cluster(cases["disjoint_40_groups"])
+    assert 40 <= len(set(d.tolist())) and cases["disjoint_40_groups"].shape[0] > 400
+    # the re-scan constructions do what their docstring says: L hub merges, then the leaves' next partners
+    r = vo.cluster(cases["rescan_hub_high_a30_L4"])
+    assert [int(r[30 + l]) for l in range(4)] == [0, 1, 2, 3]
+    r = vo.cluster(cases["rescan_hub_low_a30_L4"])
+    assert [int(r[30 + 2 * l + 1]) for l in range(4)] == [30, 32, 34, 36] and int(r[38]) == 0
 
 
 # ---- the Python surface -----------------------------------------------------------------------------------------------------
