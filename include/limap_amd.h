@@ -572,6 +572,67 @@ int lt_fn_vp_cluster_host(int64_t n, int64_t n_words, const uint64_t *pref, int3
 int lt_vp_cluster_sets(lt_ctx *ctx, int n_img, const int64_t *row_off, int64_t n_words, const uint64_t *pref,
                        int32_t *roots);
 
+/* ---- limap.optimize: the geometric refinement of line tracks with constant cameras -- step [E] of
+ * limap.runners.line_triangulation (:208-219, optimize/hybrid_bundle_adjustment/hybrid_bundle_adjustment.cc) and the
+ * geometric terms of limap.optimize.line_refinement.  With constant intrinsics and poses every
+ * track is its own problem: a Pluecker line in the orthonormal form (uvec in S^3, wvec in S^1), two residuals per
+ * supporting 2D segment (optimize/line_refinement/cost_functions.h:106-127), ScaledLoss(CauchyLoss(0.25), length / 30)
+ * per support.  limap's own code -- MinimalInfiniteLine3d, GetInfiniteLine, ComputeLineWeights, the residual, the
+ * residual order (sorted image ids, list order within an image), GetLineSegmentFromInfiniteLine3d over the track's
+ * line3d_list, applied to every track, constant ones included -- is restated; the minimiser (a Levenberg-Marquardt
+ * iteration per track on the device) is this project's definition: refined lines are minimisers of upstream's cost, not
+ * the iterates of a particular Ceres run.
+ * LT_ERR_ARGUMENT before any launch, where upstream CHECK-fails or indexes out of range: a track line of zero length, a
+ * track without supports, num_outliers_aggregator outside [0, 2 K - 1] for a track of K supports, an image id that is
+ * not in the collection; also non-finite input, geometric_alpha outside [0, 700], max_num_iterations < 0. */
+typedef struct lt_refine_config {
+  double geometric_alpha;          /* 10.0 */
+  int32_t min_num_images;          /* 4: a track seen in fewer images is held constant */
+  int32_t num_outliers_aggregator; /* 2: the num_outliers of GetOutputLineTracks; the entry points below cut with it */
+  int32_t num_outliers_aggregate;  /* 2: RefinementConfig's key (GetLine3d); carried, the Python layer selects */
+  int32_t max_num_iterations;      /* 100 */
+  int32_t constant_line;           /* 0 */
+  int32_t pad_;
+} lt_refine_config;
+void lt_refine_config_default(lt_refine_config *cfg);
+/* Termination codes: 0 max_num_iterations, 1 radius below 1e-32, 2 zero gradient, 3 non-positive or non-finite pivot,
+ * 4 non-positive or non-finite model decrease, 5 held constant.
+ * Tracks as CSR: track n owns the supports [off[n], off[n + 1]) in the order of its lists; line6 = start, end of
+ * track.line; img = image_id_list; line2d4 = line2d_list; line3d6 = start, end of line3d_list.  Cameras: n_img ids (any
+ * order, distinct) with kvec4 (fx, fy, cx, cy), qvec4 (w, x, y, z), tvec3.  The result stays in the context. */
+int lt_refine_arrays(lt_ctx *ctx, int n_img, const int32_t *img_ids, const double *kvec4, const double *qvec4,
+                     const double *tvec3, int64_t n_tracks, const double *line6, const int64_t *off, const int32_t *img,
+                     const double *line2d4, const double *line3d6, const lt_refine_config *cfg);
+/* The same on a track set, with the cameras the context holds on the device since lt_init: every track's line becomes
+ * the re-cut segment of its refined line (uncertainty -1, like a fresh Line3d). */
+int lt_refine_tracks(lt_ctx *ctx, lt_trackset *ts, const lt_refine_config *cfg);
+/* of the last lt_refine_arrays / lt_refine_tracks (any pointer may be NULL): per track params6 = uvec (w, x, y, z),
+ * wvec; seg6 = start, end; cost2 = initial, final cost (1/2 sum rho); iterations; termination code */
+int64_t lt_refine_num(lt_ctx *ctx);
+int lt_refine_get(lt_ctx *ctx, double *params6, double *seg6, double *cost2, int32_t *iters, int32_t *codes);
+/* host ms of [0] validation, tables and upload, [1] the kernels, [2] download; device ms (HIP events) of [3] k_refine_lm */
+int lt_refine_get_timers(lt_ctx *ctx, double out[4]);
+/* The whole step on the host, no context and no device: the same inline functions and the same reduction order, tracks
+ * spread over n_threads OpenMP threads (0: the default).  Outputs as lt_refine_get. */
+int lt_fn_refine_host(int n_img, const int32_t *img_ids, const double *kvec4, const double *qvec4, const double *tvec3,
+                      int64_t n_tracks, const double *line6, const int64_t *off, const int32_t *img,
+                      const double *line2d4, const double *line3d6, const lt_refine_config *cfg, int n_threads,
+                      double *params6, double *seg6, double *cost2, int32_t *iters, int32_t *codes);
+/* the message of the calling thread's last lt_fn_refine_host that returned LT_ERR_ARGUMENT ("" after a success) */
+const char *lt_fn_refine_host_error(void);
+/* GetLineSegmentFromInfiniteLine3d alone (host): the segment of the line params6 over the K 3D supports line3d6 with
+ * num_outliers in [0, 2 K - 1]; what a second num_outliers on solved tracks needs, without a new solve */
+int lt_fn_refine_cut(int64_t K, const double *line3d6, const double params6[6], int num_outliers, double seg6[6]);
+/* For tests: one track of K supports (cam11 = kvec | qvec | tvec per support, in residual order) at the given minimal
+ * parameters: residuals[2 K], cost, g[4] and H[16] of the linearisation (any pointer may be NULL). */
+int lt_fn_refine_eval(int64_t K, const double *cam11, const double *line2d4, const double params6[6], double alpha,
+                      double *residuals, double *cost, double g[4], double H[16]);
+/* For tests: out[k] = lt_exp(x[k]) (which = 0, x in [0, 700]) or lt_log(x[k]) (which = 1, x >= 1), the module's own
+ * exponential and logarithm; MinimalInfiniteLine3d of a segment; GetInfiniteLine (d, m) of minimal parameters. */
+int lt_fn_refine_explog(int which, int64_t n, const double *x, double *out);
+int lt_fn_refine_minimal(const double line6[6], double params6[6]);
+int lt_fn_refine_infinite(const double params6[6], double dm6[6]);
+
 /* Counters of the last device run: [0] connections tested, [1] candidates, [2] ordered candidate
  * pairs swept by the scoring kernel (sum n_tris^2), [3] valid edges, [4] graph nodes,
  * [5] graph edges, [6] tracks, [7] nodes. */

@@ -39,6 +39,9 @@ EXPORTED_SYMBOLS = [
     "lt_match_scene", "lt_match_get", "lt_match_get_scores", "lt_match_get_timers", "lt_fn_match_pair_host",
     "lt_vp_config_default", "lt_vp_detect", "lt_vp_get", "lt_vp_get_timers", "lt_fn_vp_detect_host",
     "lt_fn_vp_cluster_host", "lt_vp_cluster_sets",
+    "lt_refine_config_default", "lt_refine_arrays", "lt_refine_tracks", "lt_refine_num", "lt_refine_get",
+    "lt_refine_get_timers", "lt_fn_refine_host", "lt_fn_refine_eval", "lt_fn_refine_explog", "lt_fn_refine_minimal",
+    "lt_fn_refine_infinite", "lt_fn_refine_host_error", "lt_fn_refine_cut",
 ]
 
 
@@ -144,6 +147,13 @@ class LtVpConfig(C.Structure):
     """lt_vp_config of include/limap_amd.h"""
     _fields_ = [("min_length", C.c_double), ("inlier_threshold", C.c_double), ("th_perp_supports", C.c_double),
                 ("min_num_supports", C.c_int32), ("num_hypotheses", C.c_int32), ("seed", C.c_uint64)]
+
+
+class LtRefineConfig(C.Structure):
+    """lt_refine_config of include/limap_amd.h"""
+    _fields_ = [("geometric_alpha", C.c_double), ("min_num_images", C.c_int32), ("num_outliers_aggregator", C.c_int32),
+                ("num_outliers_aggregate", C.c_int32), ("max_num_iterations", C.c_int32), ("constant_line", C.c_int32),
+                ("pad_", C.c_int32)]
 
 
 def load_library():
@@ -293,6 +303,24 @@ def load_library():
     L.lt_fn_vp_detect_host.argtypes = [C.c_int, i64p, dp, C.POINTER(LtVpConfig), C.c_int, i32p, i64p, dp, C.c_int64, i32p]
     L.lt_fn_vp_cluster_host.argtypes = [C.c_int64, C.c_int64, C.POINTER(C.c_uint64), i32p]
     L.lt_vp_cluster_sets.argtypes = [vp, C.c_int, i64p, C.c_int64, C.POINTER(C.c_uint64), i32p]
+    rcp = C.POINTER(LtRefineConfig)
+    L.lt_refine_config_default.argtypes = [rcp]
+    L.lt_refine_config_default.restype = None
+    L.lt_refine_arrays.argtypes = [vp, C.c_int, i32p, dp, dp, dp, C.c_int64, dp, i64p, i32p, dp, dp, rcp]
+    L.lt_refine_tracks.argtypes = [vp, vp, rcp]
+    L.lt_refine_num.argtypes = [vp]
+    L.lt_refine_num.restype = C.c_int64
+    L.lt_refine_get.argtypes = [vp, dp, dp, dp, i32p, i32p]
+    L.lt_refine_get_timers.argtypes = [vp, dp]
+    L.lt_fn_refine_host.argtypes = [C.c_int, i32p, dp, dp, dp, C.c_int64, dp, i64p, i32p, dp, dp, rcp, C.c_int,
+                                    dp, dp, dp, i32p, i32p]
+    L.lt_fn_refine_eval.argtypes = [C.c_int64, dp, dp, dp, C.c_double, dp, dp, dp, dp]
+    L.lt_fn_refine_explog.argtypes = [C.c_int, C.c_int64, dp, dp]
+    L.lt_fn_refine_minimal.argtypes = [dp, dp]
+    L.lt_fn_refine_infinite.argtypes = [dp, dp]
+    L.lt_fn_refine_host_error.argtypes = []
+    L.lt_fn_refine_host_error.restype = C.c_char_p
+    L.lt_fn_refine_cut.argtypes = [C.c_int64, dp, dp, C.c_int, dp]
     _lib = L
     return L
 

@@ -427,6 +427,11 @@ struct lt_ctx {
   std::vector<long long> vp_vp_off;          // per image its vanishing points
   std::vector<double> vp_vps;
   DevBuf d_vp_raw, d_vp_flag, d_vp_src, d_vp_lines, d_vp_imgs, d_vp_blk, d_vp_hyp, d_vp_pref, d_vp_state, d_vp_roots;
+
+  // ---- line refinement (lt_refine.cpp): the result of the last lt_refine_arrays / lt_refine_tracks ----
+  double rf_timers[4] = {0, 0, 0, 0};  // lt_refine_get_timers
+  std::vector<double> rf_out;          // 15 doubles (one lt::RfOut) per track
+  DevBuf d_rf_k, d_rf_q, d_rf_t, d_rf_cam, d_rf_l2d, d_rf_l3d, d_rf_tab, d_rf_line, d_rf_tracks, d_rf_out;
 };
 
 #define HIPCHK(ctx, call)                                                                  \
@@ -450,3 +455,9 @@ static inline int fail(lt_ctx *ctx, int code, const std::string &msg) {
   ctx->err = msg;
   return code;
 }
+
+namespace lt_impl {
+// lt_refine.cpp: the refinement of tracks given as CSR arrays with the cameras the context holds on the device
+int refine_with_ctx_cams(lt_ctx *ctx, int64_t n_tracks, const double *line6, const int64_t *off, const int32_t *img,
+                         const double *line2d4, const double *line3d6, const lt_refine_config *cfg);
+}  // namespace lt_impl

@@ -1,0 +1,151 @@
+// lt_kernels_refine.hip -- the geometric line refinement on the device: every expression comes from
+// lt_refine.h, which lt_refine.cpp compiles for the host path too.
+//   k_refine_prep  per support: the 3x6 projection matrix of its view, the 2D endpoints and the weight into the SoA
+//                  table; per track: MinimalInfiniteLine3d of its line
+//   k_refine_lm    the whole Levenberg-Marquardt loop of a track: kRfWidth lanes of a wave64 per track, lanes over the
+//                  supports, the 14 sums of a linearisation reduced by a fixed xor tree of shuffles, the 4x4 solve done
+//                  by every lane of the group on the same bits
+//   k_refine_cut   GetLineSegmentFromInfiniteLine3d: the two order statistics by rank counting, no sort
+// All stores are ordinary vector stores of the lanes.
+
+#include "lt_refine.h"
+
+namespace lt {
+
+namespace {
+
+__global__ void __launch_bounds__(256) k_refine_prep(const double *__restrict__ kvec, const double *__restrict__ qvec,
+                                                     const double *__restrict__ tvec, const int *__restrict__ sup_cam,
+                                                     const double *__restrict__ l2d4, long long n_sup,
+                                                     double *__restrict__ tab, long long stride,
+                                                     const double *__restrict__ line6, long long n_tracks,
+                                                     RfOut *__restrict__ out) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_sup) {
+    const int cam = sup_cam[i];
+    rf_view_matrix(kvec + 4 * (long long)cam, qvec + 4 * (long long)cam, tvec + 3 * (long long)cam, tab + i, stride);
+    const double x1 = l2d4[4 * i], y1 = l2d4[4 * i + 1], x2 = l2d4[4 * i + 2], y2 = l2d4[4 * i + 3];
+    tab[18 * stride + i] = x1; tab[19 * stride + i] = y1;
+    tab[20 * stride + i] = x2; tab[21 * stride + i] = y2;
+    const double dx = x2 - x1, dy = y2 - y1;
+    tab[22 * stride + i] = sqrt(dx * dx + dy * dy) / 30.0;  // ComputeLineWeights (linetrack.cc:315-322)
+  }
+  if (i < n_tracks) {
+    double p[6];
+    rf_minimal(line6 + 6 * i, p);
+    for (int c = 0; c < 6; ++c) out[i].p[c] = p[c];
+  }
+}
+
+// the sum over the group's kRfWidth lanes, the same bits in every lane (a + b == b + a)
+__device__ __forceinline__ double group_sum(double v) {
+#pragma unroll
+  for (int m = kRfWidth / 2; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, kRfWidth);
+  return v;
+}
+
+// the reductions of rf_lm over the group's lanes: lane l takes supports l, l + kRfWidth, ... in ascending order
+struct DevGroup {
+  const RfDev &dev;
+  const RfTrack &t;
+  int lane;
+  __device__ __forceinline__ double cost(const double p[6]) const {
+    double dm[6];
+    rf_plucker<double>(p, p + 4, dm);
+    double part = 0.0;
+    for (int k = lane; k < t.n; k += kRfWidth) part = part + rf_cost_term(rf_load(dev.sup, dev.stride, t.s0 + k), dm, dev.alpha);
+    return 0.5 * group_sum(part);
+  }
+  __device__ __forceinline__ void linearise(const double p[6], double acc[kRfSums]) const {
+    Rf4 u[4], w[2], dm[6];
+    rf_seed(p, u, w);
+    rf_plucker<Rf4>(u, w, dm);
+    for (int c = 0; c < kRfSums; ++c) acc[c] = 0.0;
+    for (int k = lane; k < t.n; k += kRfWidth) rf_accumulate(rf_load(dev.sup, dev.stride, t.s0 + k), dm, dev.alpha, acc);
+    for (int c = 0; c < kRfSums; ++c) acc[c] = group_sum(acc[c]);
+  }
+};
+
+// a group whose track ends leaves rf_lm's loop while the other groups of its wave go on; the wave retires with its
+// last track
+__global__ void __launch_bounds__(kRfBlock) k_refine_lm(RfDev dev, RfOut *__restrict__ out) {
+  const long long ti = ((long long)blockIdx.x * kRfBlock + threadIdx.x) / kRfWidth;
+  const int lane = threadIdx.x % kRfWidth;
+  if (ti >= dev.n_tracks) return;  // a whole group leaves together
+  const RfTrack t = dev.tracks[ti];
+  double p[6], F0, F1;
+  int it, code;
+  for (int c = 0; c < 6; ++c) p[c] = out[ti].p[c];
+  DevGroup grp{dev, t, lane};
+  rf_lm(grp, t.constant != 0, dev.max_iter, p, &F0, &F1, &it, &code);
+  if (lane == 0) {
+    for (int c = 0; c < 6; ++c) out[ti].p[c] = p[c];
+    out[ti].cost0 = F0;
+    out[ti].cost1 = F1;
+    out[ti].iters = it;
+    out[ti].code = code;
+  }
+}
+
+__global__ void __launch_bounds__(kRfBlock) k_refine_cut(RfDev dev, RfOut *__restrict__ out) {
+  const long long ti = ((long long)blockIdx.x * kRfBlock + threadIdx.x) / kRfWidth;
+  const int lane = threadIdx.x % kRfWidth;
+  if (ti >= dev.n_tracks) return;
+  const RfTrack t = dev.tracks[ti];
+  double p[6];
+  for (int c = 0; c < 6; ++c) p[c] = out[ti].p[c];
+  d3 dir, m;
+  rf_infinite(p, &dir, &m);
+  const double *l3 = dev.l3d + 6 * t.s0;
+  const d3 pref = rf_pref(dir, m, mk3(l3[0], l3[1], l3[2]));
+  const long long n = 2 * (long long)t.n, lo = dev.num_outliers, hi = n - 1 - dev.num_outliers;
+  // every endpoint has at most one writer (rf_rank_test); where no value takes a rank -- a NaN among them -- lane 0
+  // writes NaN, as the host does
+  bool any_lo = false, any_hi = false;
+  for (long long i = lane; i < n; i += kRfWidth) {
+    double v;
+    bool is_lo, is_hi;
+    rf_rank_test(l3, n, i, pref, dir, lo, hi, &v, &is_lo, &is_hi);
+    if (is_lo) {
+      out[ti].seg[0] = pref.x + dir.x * v; out[ti].seg[1] = pref.y + dir.y * v; out[ti].seg[2] = pref.z + dir.z * v;
+    }
+    if (is_hi) {
+      out[ti].seg[3] = pref.x + dir.x * v; out[ti].seg[4] = pref.y + dir.y * v; out[ti].seg[5] = pref.z + dir.z * v;
+    }
+    any_lo |= is_lo;
+    any_hi |= is_hi;
+  }
+  int found = (any_lo ? 1 : 0) | (any_hi ? 2 : 0);
+#pragma unroll
+  for (int m = kRfWidth / 2; m >= 1; m >>= 1) found |= __shfl_xor(found, m, kRfWidth);
+  if (lane == 0) {
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    if (!(found & 1)) { out[ti].seg[0] = nan; out[ti].seg[1] = nan; out[ti].seg[2] = nan; }
+    if (!(found & 2)) { out[ti].seg[3] = nan; out[ti].seg[4] = nan; out[ti].seg[5] = nan; }
+  }
+}
+
+inline unsigned grid_of(long long n, int block) { return (unsigned)((n + block - 1) / block); }
+
+}  // namespace
+
+void launch_refine_prep(hipStream_t st, const double *kvec, const double *qvec, const double *tvec, const int *sup_cam,
+                        const double *l2d4, long long n_sup, double *sup_tab, long long stride, const double *line6,
+                        long long n_tracks, RfOut *out) {
+  const long long n = n_sup > n_tracks ? n_sup : n_tracks;
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_refine_prep, dim3(grid_of(n, 256)), dim3(256), 0, st, kvec, qvec, tvec, sup_cam, l2d4, n_sup,
+                     sup_tab, stride, line6, n_tracks, out);
+}
+
+void launch_refine_lm(hipStream_t st, const RfDev &dev, RfOut *out) {
+  if (dev.n_tracks <= 0) return;
+  hipLaunchKernelGGL(k_refine_lm, dim3(grid_of(dev.n_tracks * kRfWidth, kRfBlock)), dim3(kRfBlock), 0, st, dev, out);
+}
+
+void launch_refine_cut(hipStream_t st, const RfDev &dev, RfOut *out) {
+  if (dev.n_tracks <= 0) return;
+  hipLaunchKernelGGL(k_refine_cut, dim3(grid_of(dev.n_tracks * kRfWidth, kRfBlock)), dim3(kRfBlock), 0, st, dev, out);
+}
+
+}  // namespace lt

@@ -1,0 +1,543 @@
+// lt_refine.h -- records and the FP64 expressions shared by the host side (lt_refine.cpp) and the device side
+// (lt_kernels_refine.hip) of the geometric line refinement: step [E] of limap.runners.line_triangulation
+// (runners/line_triangulation.py:208-219) with constant cameras, where every track is its own 4-degree-of-freedom robust
+// least-squares problem.  Both sides compile the same inline functions with -ffp-contract=off, so the
+// device and lt_fn_refine_host agree bit for bit.
+//
+// limap's own part is restated in its operation order where the order decides a branch (the conversions), and as one
+// 3x6 matrix per support where it is linear in the Pluecker line (the projection): paths relative to src/limap,
+//   base/infinite_line.cc:67-71,180-231,265-287   InfiniteLine3d(Line3d), MinimalInfiniteLine3d, GetInfiniteLine,
+//                                                 GetLineSegmentFromInfiniteLine3d
+//   base/pose.cc:7-28                             RotationMatrixToQuaternion / QuaternionToRotationMatrix
+//   base/linetrack.cc:315-322                     ComputeLineWeights
+//   ceresbase/line_transforms.h:8-29              MinimalPluckerToPlucker
+//   ceresbase/line_projection.h:14-80             Line_ImgFromCam, Line_WorldToPixel
+//   ceresbase/line_dists.h:19-28                  CeresComputeDist2D_cosine
+//   optimize/line_refinement/cost_functions.h:96-127  Ceres_PerpendicularDist2D, Ceres_CosineWeightedPerpendicularDist2D_1D
+// ASSUMPTIONS of the same kind as lt_svd.h (the libraries are not part of limap; their published procedures are
+// followed): Eigen's Quaternion(Matrix3) and Quaternion::toRotationMatrix, Ceres' QuaternionToRotation
+// (QuaternionToScaledRotation, then the division by the squared norm), CauchyLoss, ScaledLoss and the Jet rule
+// d|x|/dx = +1 at x = 0.  The minimiser is this project's own definition, not Ceres' iterates.
+#pragma once
+
+#include "lt_geom.h"
+
+namespace lt {
+
+constexpr int kRfWidth = 16;            // lanes of a wave64 that work on one track (k_refine_lm, k_refine_cut)
+constexpr int kRfBlock = 64;            // lanes per workgroup: one wave, four tracks
+constexpr int kRfFields = 23;           // doubles per support (SoA over the scene's supports): A[18], x1 y1 x2 y2, weight
+constexpr double kRfCauchyB = 0.0625;   // CauchyLoss(0.25): b = a^2 (refinement_config.h:21)
+constexpr double kRfMu0 = 1e4;          // initial trust-region radius (Ceres' default)
+constexpr double kRfMuMax = 1e16, kRfMuMin = 1e-32;
+constexpr double kRfMinRatio = 1e-3;    // min_relative_decrease
+constexpr double kRfDMin = 1e-6, kRfDMax = 1e32;  // min / max_lm_diagonal
+
+// termination codes of a track (lt_refine_get)
+enum RfCode : int {
+  kRfMaxIter = 0,    // max_num_iterations reached
+  kRfRadius = 1,     // the radius fell below 1e-32
+  kRfZeroGrad = 2,   // g == 0
+  kRfBadPivot = 3,   // a Cholesky pivot is not positive or not finite
+  kRfBadModel = 4,   // the model decrease is not positive or not finite
+  kRfConstant = 5,   // constant_line, or fewer than min_num_images images: not optimised, segment re-cut
+};
+
+// a track as the kernels see it: supports [s0, s0 + n) of the scene's supports (residual order), line, flags
+struct RfTrack {
+  long long s0;
+  int n, constant;
+};
+static_assert(sizeof(RfTrack) == 16, "RfTrack layout");
+
+// per track result
+struct RfOut {
+  double p[6];      // uvec (w, x, y, z), wvec
+  double seg[6];    // start, end
+  double cost0, cost1;
+  int iters, code;
+};
+static_assert(sizeof(RfOut) == 120, "RfOut layout");
+
+// ---- exp on [0, 700] and log on [1, inf): plain FP64 arithmetic in a fixed order, the same bits on both sides ----
+// exp(x) = 2^k exp(r), k = floor(x / ln 2 + 1/2), r = (x - k ln2_hi) - k ln2_lo, |r| <= 0.3466; exp(r) by its Taylor
+// polynomial of degree 14 (Horner); 2^k by ten exact multiplications
+LT_HD double lt_exp(double x) {
+  const double kd = floor(x * 1.4426950408889634074 + 0.5);
+  const double r = (x - kd * 6.93147180369123816490e-01) - kd * 1.90821492927058770002e-10;
+  double p = 1.0 / 87178291200.0;
+  p = p * r + 1.0 / 6227020800.0;
+  p = p * r + 1.0 / 479001600.0;
+  p = p * r + 1.0 / 39916800.0;
+  p = p * r + 1.0 / 3628800.0;
+  p = p * r + 1.0 / 362880.0;
+  p = p * r + 1.0 / 40320.0;
+  p = p * r + 1.0 / 5040.0;
+  p = p * r + 1.0 / 720.0;
+  p = p * r + 1.0 / 120.0;
+  p = p * r + 1.0 / 24.0;
+  p = p * r + 1.0 / 6.0;
+  p = p * r + 0.5;
+  p = p * r + 1.0;
+  p = p * r + 1.0;
+  int k = (int)kd;
+  double s = 1.0, b = 2.0;
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    s = (k & 1) ? s * b : s;
+    b = b * b;
+    k >>= 1;
+  }
+  return p * s;
+}
+
+// log(y), y >= 1 finite: y = 2^e f with f in [1/sqrt 2, sqrt 2) by ten exact scalings, log f = 2 atanh(s),
+// s = (f - 1) / (f + 1), |s| <= 0.1716, odd series to s^23
+LT_HD double lt_log(double y) {
+  int e = 0;
+  if (y >= 0x1p512) { y = y * 0x1p-512; e += 512; }
+  if (y >= 0x1p256) { y = y * 0x1p-256; e += 256; }
+  if (y >= 0x1p128) { y = y * 0x1p-128; e += 128; }
+  if (y >= 0x1p64) { y = y * 0x1p-64; e += 64; }
+  if (y >= 0x1p32) { y = y * 0x1p-32; e += 32; }
+  if (y >= 0x1p16) { y = y * 0x1p-16; e += 16; }
+  if (y >= 0x1p8) { y = y * 0x1p-8; e += 8; }
+  if (y >= 0x1p4) { y = y * 0x1p-4; e += 4; }
+  if (y >= 0x1p2) { y = y * 0x1p-2; e += 2; }
+  if (y >= 0x1p1) { y = y * 0x1p-1; e += 1; }
+  if (y > 1.41421356237309514547) { y = y * 0.5; e += 1; }
+  const double s = (y - 1.0) / (y + 1.0), z = s * s;
+  double p = 1.0 / 23.0;
+  p = p * z + 1.0 / 21.0;
+  p = p * z + 1.0 / 19.0;
+  p = p * z + 1.0 / 17.0;
+  p = p * z + 1.0 / 15.0;
+  p = p * z + 1.0 / 13.0;
+  p = p * z + 1.0 / 11.0;
+  p = p * z + 1.0 / 9.0;
+  p = p * z + 1.0 / 7.0;
+  p = p * z + 1.0 / 5.0;
+  p = p * z + 1.0 / 3.0;
+  p = p * z;                       // the series without its leading 1
+  const double lf = 2.0 * s + 2.0 * s * p;
+  const double ed = (double)e;
+  return ed * 6.93147180369123816490e-01 + (lf + ed * 1.90821492927058770002e-10);
+}
+
+// ---- forward-mode scalar: a value and its derivatives along the four local directions (du1, du2, du3, dw) ----
+struct Rf4 {
+  double v, d[4];
+};
+LT_HD Rf4 rf_const(double v) { return Rf4{v, {0.0, 0.0, 0.0, 0.0}}; }
+LT_HD double rf_val(double a) { return a; }
+LT_HD double rf_val(const Rf4 &a) { return a.v; }
+LT_HD Rf4 operator+(const Rf4 &a, const Rf4 &b) {
+  return Rf4{a.v + b.v, {a.d[0] + b.d[0], a.d[1] + b.d[1], a.d[2] + b.d[2], a.d[3] + b.d[3]}};
+}
+LT_HD Rf4 operator-(const Rf4 &a, const Rf4 &b) {
+  return Rf4{a.v - b.v, {a.d[0] - b.d[0], a.d[1] - b.d[1], a.d[2] - b.d[2], a.d[3] - b.d[3]}};
+}
+LT_HD Rf4 operator-(const Rf4 &a) { return Rf4{-a.v, {-a.d[0], -a.d[1], -a.d[2], -a.d[3]}}; }
+LT_HD Rf4 operator*(const Rf4 &a, const Rf4 &b) {
+  return Rf4{a.v * b.v,
+             {a.v * b.d[0] + a.d[0] * b.v, a.v * b.d[1] + a.d[1] * b.v, a.v * b.d[2] + a.d[2] * b.v,
+              a.v * b.d[3] + a.d[3] * b.v}};
+}
+LT_HD Rf4 operator/(const Rf4 &a, const Rf4 &b) {
+  const double q = a.v / b.v;
+  return Rf4{q, {(a.d[0] - q * b.d[0]) / b.v, (a.d[1] - q * b.d[1]) / b.v, (a.d[2] - q * b.d[2]) / b.v,
+                 (a.d[3] - q * b.d[3]) / b.v}};
+}
+LT_HD Rf4 operator+(const Rf4 &a, double b) { return Rf4{a.v + b, {a.d[0], a.d[1], a.d[2], a.d[3]}}; }
+LT_HD Rf4 operator*(const Rf4 &a, double b) { return Rf4{a.v * b, {a.d[0] * b, a.d[1] * b, a.d[2] * b, a.d[3] * b}}; }
+LT_HD Rf4 operator*(double b, const Rf4 &a) { return a * b; }
+LT_HD Rf4 operator-(double b, const Rf4 &a) { return Rf4{b - a.v, {-a.d[0], -a.d[1], -a.d[2], -a.d[3]}}; }
+LT_HD Rf4 rf_sqrt(const Rf4 &a) {
+  const double s = sqrt(a.v), h = 0.5 / s;
+  return Rf4{s, {a.d[0] * h, a.d[1] * h, a.d[2] * h, a.d[3] * h}};
+}
+LT_HD double rf_sqrt(double a) { return sqrt(a); }
+LT_HD Rf4 rf_abs(const Rf4 &a) { return a.v < 0.0 ? -a : a; }  // the Jet rule: +1 at 0
+LT_HD double rf_abs(double a) { return a < 0.0 ? -a : a; }
+LT_HD Rf4 rf_exp(const Rf4 &a) {
+  const double e = lt_exp(a.v);
+  return Rf4{e, {e * a.d[0], e * a.d[1], e * a.d[2], e * a.d[3]}};
+}
+LT_HD double rf_exp(double a) { return lt_exp(a); }
+LT_HD void rf_set(double &a, double v) { a = v; }
+LT_HD void rf_set(Rf4 &a, double v) { a = rf_const(v); }
+
+// MinimalPluckerToPlucker (line_transforms.h:8-29): dm = (d, m) from uvec (w, x, y, z) and wvec
+template <class T>
+LT_HD void rf_plucker(const T u[4], const T w[2], T dm[6]) {
+  const T a = u[0], b = u[1], c = u[2], d = u[3];
+  const T aa = a * a, ab = a * b, ac = a * c, ad = a * d, bb = b * b, bc = b * c, bd = b * d, cc = c * c, cd = c * d,
+          dd = d * d;
+  const T n = ((aa + bb) + cc) + dd;
+  const T r0 = (((aa + bb) - cc) - dd) / n, r1 = ((bc - ad) * 2.0) / n;
+  const T r3 = ((ad + bc) * 2.0) / n, r4 = (((aa - bb) + cc) - dd) / n;
+  const T r6 = ((bd - ac) * 2.0) / n, r7 = ((ab + cd) * 2.0) / n;
+  const T w1 = rf_abs(w[0]), w2 = rf_abs(w[1]);
+  const T bn = w2 / (w1 + kEps);
+  dm[0] = r0; dm[1] = r3; dm[2] = r6;
+  dm[3] = r1 * bn; dm[4] = r4 * bn; dm[5] = r7 * bn;
+}
+
+// the 3x6 matrix of a view: Line_WorldToPixel (line_projection.h:51-80) before its normalisation is
+// A (d, m) with A = cof(K) [ [t]x R | R ] -- R [m]x R^T - t (R d)^T + (R d) t^T = [R m + t x R d]x and
+// K [v]x K^T = [cof(K) v]x.  q: CameraPose's quaternion, normalised once like its constructor (camera.h:94-95), then
+// Ceres' QuaternionToRotation
+// A[f] goes to out[f * stride] (the SoA table directly: no private array of the lane)
+LT_HD void rf_view_matrix(const double *k4, const double *q4, const double *t3, double *out, long long stride) {
+  double q[4];
+  const double n0 = sqrt((q4[0] * q4[0] + q4[2] * q4[2]) + (q4[1] * q4[1] + q4[3] * q4[3]));
+#pragma unroll
+  for (int i = 0; i < 4; ++i) q[i] = n0 > 0.0 ? q4[i] / n0 : q4[i];
+  const double a = q[0], b = q[1], c = q[2], d = q[3];
+  const double aa = a * a, ab = a * b, ac = a * c, ad = a * d, bb = b * b, bc = b * c, bd = b * d, cc = c * c,
+               cd = c * d, dd = d * d;
+  const double n = ((aa + bb) + cc) + dd;
+  double R[9] = {((aa + bb) - cc) - dd, 2.0 * (bc - ad), 2.0 * (ac + bd), 2.0 * (ad + bc), ((aa - bb) + cc) - dd,
+                 2.0 * (cd - ab), 2.0 * (bd - ac), 2.0 * (ab + cd), ((aa - bb) - cc) + dd};
+#pragma unroll
+  for (int i = 0; i < 9; ++i) R[i] = R[i] / n;
+  // B = [ [t]x R | R ]  (3 x 6, row-major)
+  double B[18];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const double r0 = R[j], r1 = R[3 + j], r2 = R[6 + j];
+    B[j] = t3[1] * r2 - t3[2] * r1;
+    B[6 + j] = t3[2] * r0 - t3[0] * r2;
+    B[12 + j] = t3[0] * r1 - t3[1] * r0;
+    B[3 + j] = r0; B[9 + j] = r1; B[15 + j] = r2;
+  }
+  // cof(K) = [[fy, 0, 0], [0, fx, 0], [-fy cx, -fx cy, fx fy]]
+  const double fx = k4[0], fy = k4[1], cx = k4[2], cy = k4[3];
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    out[(long long)j * stride] = fy * B[j];
+    out[(long long)(6 + j) * stride] = fx * B[6 + j];
+    out[(long long)(12 + j) * stride] = ((-(fy * cx)) * B[j] - (fx * cy) * B[6 + j]) + (fx * fy) * B[12 + j];
+  }
+}
+
+// one support as the residual reads it (strided by `stride` doubles in the scene's SoA table)
+struct RfSup {
+  double A[18];
+  double x1, y1, x2, y2, weight;
+};
+LT_HD RfSup rf_load(const double *tab, long long stride, long long s) {
+  RfSup r;
+  for (int i = 0; i < 18; ++i) r.A[i] = tab[(long long)i * stride + s];
+  r.x1 = tab[18 * stride + s]; r.y1 = tab[19 * stride + s];
+  r.x2 = tab[20 * stride + s]; r.y2 = tab[21 * stride + s];
+  r.weight = tab[22 * stride + s];
+  return r;
+}
+
+// the two residuals of a support (cost_functions.h:106-127 after Line_WorldToPixel); T = double or Rf4
+template <class T>
+LT_HD void rf_residual(const RfSup &s, const T dm[6], double alpha, T res[2]) {
+  T c[3];
+  for (int i = 0; i < 3; ++i) {
+    const double *a = s.A + 6 * i;
+    c[i] = ((((dm[0] * a[0] + dm[1] * a[1]) + dm[2] * a[2]) + dm[3] * a[3]) + dm[4] * a[4]) + dm[5] * a[5];
+  }
+  const T cn = rf_sqrt(((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]) + kEps);  // Line_ImgFromCam :43-47
+  const T c0 = c[0] / cn, c1 = c[1] / cn, c2 = c[2] / cn;
+  const T dn = rf_sqrt((c0 * c0 + c1 * c1) + kEps);  // direc_norm
+  const T e0 = -(c1 / dn), e1 = c0 / dn;             // dir2d
+  const double f0 = s.x2 - s.x1, f1 = s.y2 - s.y1;   // direc
+  const T n1 = rf_sqrt((e0 * e0 + e1 * e1) + kEps);
+  const double n2 = sqrt((f0 * f0 + f1 * f1) + kEps);
+  T cosine = rf_abs((e0 * f0 + e1 * f1) / (n1 * n2));
+  if (rf_val(cosine) > 1.0) rf_set(cosine, 1.0);
+  const T wgt = rf_exp((1.0 - cosine) * alpha);
+  res[0] = (((c0 * s.x1 + c1 * s.y1) + c2) / dn) * wgt;
+  res[1] = (((c0 * s.x2 + c1 * s.y2) + c2) / dn) * wgt;
+}
+
+// rho_k(s) = w b log(1 + s / b): ScaledLoss(CauchyLoss(0.25), w) over the squared norm of a residual block
+LT_HD double rf_rho(double weight, double s) { return (weight * kRfCauchyB) * lt_log(1.0 + s / kRfCauchyB); }
+LT_HD double rf_rho1(double weight, double s) { return weight / (1.0 + s / kRfCauchyB); }
+
+// the sums of a linearisation, in the order every reduction uses: H upper triangle (00 01 02 03 11 12 13 22 23 33), g
+constexpr int kRfSums = 14;
+LT_HD void rf_accumulate(const RfSup &s, const Rf4 dm[6], double alpha, double acc[kRfSums], double *r2 = nullptr) {
+  Rf4 r[2];
+  rf_residual<Rf4>(s, dm, alpha, r);
+  if (r2) { r2[0] = r[0].v; r2[1] = r[1].v; }
+  const double sq = r[0].v * r[0].v + r[1].v * r[1].v;
+  const double rho1 = rf_rho1(s.weight, sq);
+  int o = 0;
+  for (int i = 0; i < 4; ++i)
+    for (int j = i; j < 4; ++j, ++o) acc[o] = acc[o] + rho1 * (r[0].d[i] * r[0].d[j] + r[1].d[i] * r[1].d[j]);
+  for (int i = 0; i < 4; ++i) acc[10 + i] = acc[10 + i] + rho1 * (r[0].d[i] * r[0].v + r[1].d[i] * r[1].v);
+}
+LT_HD double rf_cost_term(const RfSup &s, const double dm[6], double alpha) {
+  double r[2];
+  rf_residual<double>(s, dm, alpha, r);
+  return rf_rho(s.weight, r[0] * r[0] + r[1] * r[1]);
+}
+
+// the point and its four local directions: u + du_i (0, e_i) (x) u, w + dw (-w1, w0)
+LT_HD void rf_seed(const double p[6], Rf4 u[4], Rf4 w[2]) {
+  u[0] = Rf4{p[0], {-p[1], -p[2], -p[3], 0.0}};
+  u[1] = Rf4{p[1], {p[0], p[3], -p[2], 0.0}};
+  u[2] = Rf4{p[2], {-p[3], p[0], p[1], 0.0}};
+  u[3] = Rf4{p[3], {p[2], -p[1], p[0], 0.0}};
+  w[0] = Rf4{p[4], {0.0, 0.0, 0.0, -p[5]}};
+  w[1] = Rf4{p[5], {0.0, 0.0, 0.0, p[4]}};
+}
+
+// the retraction: u+ = normalize((1, du) (x) u), w+ = normalize(w + dw (-w1, w0))
+LT_HD void rf_retract(const double p[6], const double dl[4], double out[6]) {
+  const double q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
+  const double r0 = ((q0 - dl[0] * q1) - dl[1] * q2) - dl[2] * q3;
+  const double r1 = ((q1 + dl[0] * q0) + dl[1] * q3) - dl[2] * q2;
+  const double r2 = ((q2 - dl[0] * q3) + dl[1] * q0) + dl[2] * q1;
+  const double r3 = ((q3 + dl[0] * q2) - dl[1] * q1) + dl[2] * q0;
+  const double nu = sqrt(((r0 * r0 + r1 * r1) + r2 * r2) + r3 * r3);
+  out[0] = r0 / nu; out[1] = r1 / nu; out[2] = r2 / nu; out[3] = r3 / nu;
+  const double w0 = p[4] - dl[3] * p[5], w1 = p[5] + dl[3] * p[4];
+  const double nw = sqrt(w0 * w0 + w1 * w1);
+  out[4] = w0 / nw; out[5] = w1 / nw;
+}
+
+// the Levenberg-Marquardt step from the reduced sums: (H + D^2 / mu) dl = -g by a 4x4 Cholesky factorisation.
+// Returns 0, or the termination code; md = the model decrease -(g' dl + dl' H dl / 2)
+LT_HD int rf_step(const double acc[kRfSums], double mu, double dl[4], double *md) {
+  double H[4][4], L[4][4], g[4];
+  int o = 0;
+  for (int i = 0; i < 4; ++i)
+    for (int j = i; j < 4; ++j, ++o) H[i][j] = H[j][i] = acc[o];
+  for (int i = 0; i < 4; ++i) g[i] = acc[10 + i];
+  for (int i = 0; i < 4; ++i) {
+    double dg = sqrt(H[i][i]);
+    dg = dg < kRfDMin ? kRfDMin : (dg > kRfDMax ? kRfDMax : dg);
+    for (int j = 0; j <= i; ++j) {
+      double sum = i == j ? H[i][i] + (dg * dg) / mu : H[i][j];
+      for (int k = 0; k < j; ++k) sum = sum - L[i][k] * L[j][k];
+      if (i == j) {
+        if (!(sum > 0.0) || !(sum < kMaxDist)) return kRfBadPivot;
+        L[i][i] = sqrt(sum);
+      } else {
+        L[i][j] = sum / L[j][j];
+      }
+    }
+  }
+  double y[4];
+  for (int i = 0; i < 4; ++i) {
+    double sum = -g[i];
+    for (int k = 0; k < i; ++k) sum = sum - L[i][k] * y[k];
+    y[i] = sum / L[i][i];
+  }
+  for (int i = 3; i >= 0; --i) {
+    double sum = y[i];
+    for (int k = i + 1; k < 4; ++k) sum = sum - L[k][i] * dl[k];
+    dl[i] = sum / L[i][i];
+  }
+  double gd = 0.0, dhd = 0.0;
+  for (int i = 0; i < 4; ++i) {
+    gd = gd + g[i] * dl[i];
+    double hd = 0.0;
+    for (int j = 0; j < 4; ++j) hd = hd + H[i][j] * dl[j];
+    dhd = dhd + dl[i] * hd;
+  }
+  *md = -(gd + 0.5 * dhd);
+  if (!(*md > 0.0) || !(*md < kMaxDist)) return kRfBadModel;
+  return 0;
+}
+
+// the radius after an accepted step
+LT_HD double rf_grow(double mu, double ratio) {
+  const double t = 2.0 * ratio - 1.0;
+  double f = 1.0 - (t * t) * t;
+  f = f < 1.0 / 3.0 ? 1.0 / 3.0 : f;
+  const double m = mu / f;
+  return m < kRfMuMax ? m : kRfMuMax;
+}
+
+// the minimiser of one track.  G supplies the two reductions over the track's supports -- cost(p) and
+// linearise(p, acc) -- as values every lane of a group holds bit for bit (device: shuffles; host: rf_tree_host), so
+// every branch below is uniform over the group.  An iteration counts whether its step was accepted or not
+template <class G>
+LT_HD void rf_lm(G &grp, bool constant, int max_iter, double p[6], double *cost0, double *cost1, int *iters, int *code_out) {
+  double F = grp.cost(p);
+  *cost0 = F;
+  int it = 0, code = kRfMaxIter;
+  if (constant) {
+    code = kRfConstant;
+  } else {
+    double mu = kRfMu0, nu = 2.0;
+    double acc[kRfSums];
+    bool fresh = true;
+    for (; it < max_iter; ++it) {
+      if (fresh) {
+        grp.linearise(p, acc);
+        if (acc[10] == 0.0 && acc[11] == 0.0 && acc[12] == 0.0 && acc[13] == 0.0) { code = kRfZeroGrad; break; }
+        fresh = false;
+      }
+      double dl[4], md;
+      const int rc = rf_step(acc, mu, dl, &md);
+      if (rc) { code = rc; break; }
+      double pn[6];
+      rf_retract(p, dl, pn);
+      const double Fn = grp.cost(pn);
+      const double ratio = (F - Fn) / md;
+      if (ratio > kRfMinRatio) {
+        for (int c = 0; c < 6; ++c) p[c] = pn[c];
+        F = Fn;
+        mu = rf_grow(mu, ratio);
+        nu = 2.0;
+        fresh = true;
+      } else {
+        mu = mu / nu;
+        nu = 2.0 * nu;
+        if (mu < kRfMuMin) { code = kRfRadius; ++it; break; }
+      }
+    }
+  }
+  *cost1 = F;
+  *iters = it;
+  *code_out = code;
+}
+
+// MinimalInfiniteLine3d(InfiniteLine3d(line)) (infinite_line.cc:67-71,180-223); the caller has checked length > 0
+LT_HD void rf_minimal(const double l6[6], double p[6]) {
+  const d3 s = mk3(l6[0], l6[1], l6[2]);
+  const d3 a = unit(sub(mk3(l6[3], l6[4], l6[5]), s));  // Line3d::direction()
+  const d3 b = cross(s, a);
+  const double bn = sqrt(sqn(b));
+  const double den = sqrt(1.0 * 1.0 + bn * bn);
+  p[4] = 1.0 / den;
+  p[5] = bn / den;
+  const double an = sqrt(sqn(a));
+  const d3 c0 = mk3(a.x / an, a.y / an, a.z / an);
+  d3 c1, c2;
+  if (bn > kEps) {
+    c1 = mk3(b.x / bn, b.y / bn, b.z / bn);
+    const d3 axb = cross(a, b);
+    const double n = sqrt(sqn(axb));
+    c2 = mk3(axb.x / n, axb.y / n, axb.z / n);
+  } else {
+    const double av[3] = {a.x, a.y, a.z};
+    int best = 0;
+    if (fabs(av[1]) > fabs(av[0])) best = 1;
+    if (fabs(av[2]) > fabs(av[best])) best = 2;
+    const int i1 = (best + 1) % 3, i2 = (best + 2) % 3;
+    double bp[3];
+    bp[i1] = 1.0;
+    bp[i2] = 1.0;
+    bp[best] = -(av[i1] * bp[i1] + av[i2] * bp[i2]) / av[best];
+    const d3 bv = mk3(bp[0], bp[1], bp[2]);
+    const double n1 = sqrt(sqn(bv));
+    c1 = mk3(bv.x / n1, bv.y / n1, bv.z / n1);
+    const d3 axb = cross(a, bv);
+    const double n = sqrt(sqn(axb));
+    c2 = mk3(axb.x / n, axb.y / n, axb.z / n);
+  }
+  // Eigen::Quaterniond(Q), Q = [c0 c1 c2] by columns: m(i, j) = column j, row i
+  const double m[3][3] = {{c0.x, c1.x, c2.x}, {c0.y, c1.y, c2.y}, {c0.z, c1.z, c2.z}};
+  double t = (m[0][0] + m[1][1]) + m[2][2];
+  double q[4];  // x, y, z, w
+  if (t > 0.0) {
+    t = sqrt(t + 1.0);
+    q[3] = 0.5 * t;
+    t = 0.5 / t;
+    q[0] = (m[2][1] - m[1][2]) * t;
+    q[1] = (m[0][2] - m[2][0]) * t;
+    q[2] = (m[1][0] - m[0][1]) * t;
+  } else {
+    int i = 0;
+    if (m[1][1] > m[0][0]) i = 1;
+    if (m[2][2] > m[i][i]) i = 2;
+    const int j = (i + 1) % 3, k = (j + 1) % 3;
+    t = sqrt(((m[i][i] - m[j][j]) - m[k][k]) + 1.0);
+    q[i] = 0.5 * t;
+    t = 0.5 / t;
+    q[3] = (m[k][j] - m[j][k]) * t;
+    q[j] = (m[j][i] + m[i][j]) * t;
+    q[k] = (m[k][i] + m[i][k]) * t;
+  }
+  p[0] = q[3]; p[1] = q[0]; p[2] = q[1]; p[3] = q[2];
+}
+
+// GetInfiniteLine() (infinite_line.cc:225-231): d, m from the minimal parameters
+LT_HD void rf_infinite(const double p[6], d3 *d, d3 *m) {
+  const double n = sqrt((p[0] * p[0] + p[2] * p[2]) + (p[1] * p[1] + p[3] * p[3]));  // NormalizeQuaternion (pose.cc:19-28)
+  double w, x, y, z;
+  if (n == 0.0) {
+    w = 1.0; x = p[1]; y = p[2]; z = p[3];
+  } else {
+    w = p[0] / n; x = p[1] / n; y = p[2] / n; z = p[3] / n;
+  }
+  const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
+  const double twx = tx * w, twy = ty * w, twz = tz * w;
+  const double txx = tx * x, txy = ty * x, txz = tz * x;
+  const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
+  *d = mk3(1.0 - (tyy + tzz), txy + twz, txz - twy);  // Q.col(0)
+  const double f = fabs(p[5]) / fabs(p[4]);
+  *m = mk3(f * (txy - twz), f * (1.0 - (txx + tzz)), f * (tyz + twx));  // f * Q.col(1)
+}
+
+// GetLineSegmentFromInfiniteLine3d (infinite_line.cc:265-287), the projection of its values: value 2 k + e of a
+// track is (endpoint e of line3d k - p_ref) . dir
+LT_HD d3 rf_pref(d3 d, d3 m, d3 q) {  // point_projection (:73-78)
+  const d3 mq = add(m, cross(d, q));
+  return add(q, cross(d, mq));
+}
+LT_HD double rf_value(const double *l3d6, long long j, d3 pref, d3 dir) {
+  const double *e = l3d6 + 3 * j;  // 6 doubles per line: value j reads point j of the flat list
+  return dot(sub(mk3(e[0], e[1], e[2]), pref), dir);
+}
+
+// does value i hold rank r of the n values?  #(< v_i) <= r < #(< v_i) + #(== v_i), and i is the first index with its
+// value (-0.0 == +0.0: the lowest index speaks for both, so one lane writes and the host picks the same element).  A NaN
+// among the values satisfies no rank; the caller then returns NaN
+LT_HD void rf_rank_test(const double *l3d6, long long n, long long i, d3 pref, d3 dir, long long lo, long long hi,
+                        double *v_out, bool *is_lo, bool *is_hi) {
+  const double v = rf_value(l3d6, i, pref, dir);
+  long long lt = 0, eq = 0;
+  bool first = true;
+  for (long long j = 0; j < n; ++j) {
+    const double o = rf_value(l3d6, j, pref, dir);
+    lt += o < v;
+    eq += o == v;
+    if (j < i && o == v) first = false;
+  }
+  *v_out = v;
+  *is_lo = first && lt <= lo && lo < lt + eq;
+  *is_hi = first && lt <= hi && hi < lt + eq;
+}
+
+// the fixed xor tree over kRfWidth partial sums (host twin of the shuffles of k_refine_lm)
+inline void rf_tree_host(double part[kRfWidth][kRfSums], int n_sums, double out[kRfSums]) {
+  for (int m = kRfWidth / 2; m >= 1; m >>= 1) {
+    double nxt[kRfWidth][kRfSums];
+    for (int l = 0; l < kRfWidth; ++l)
+      for (int c = 0; c < n_sums; ++c) nxt[l][c] = part[l][c] + part[l ^ m][c];
+    for (int l = 0; l < kRfWidth; ++l)
+      for (int c = 0; c < n_sums; ++c) part[l][c] = nxt[l][c];
+  }
+  for (int c = 0; c < n_sums; ++c) out[c] = part[0][c];
+}
+
+// the scene's tables on the device
+struct RfDev {
+  const RfTrack *tracks;
+  long long n_tracks;
+  const double *sup;        // kRfFields x stride
+  long long stride;
+  const double *l3d;        // 6 doubles per support, member order
+  double alpha;
+  int max_iter, num_outliers;
+};
+
+void launch_refine_prep(hipStream_t st, const double *kvec, const double *qvec, const double *tvec, const int *sup_cam,
+                        const double *l2d4, long long n_sup, double *sup_tab, long long stride, const double *line6,
+                        long long n_tracks, RfOut *out);
+void launch_refine_lm(hipStream_t st, const RfDev &dev, RfOut *out);
+void launch_refine_cut(hipStream_t st, const RfDev &dev, RfOut *out);
+
+}  // namespace lt

@@ -409,4 +409,37 @@ int lt_ts_remerge_once(lt_ctx *ctx, lt_trackset *ts, const lt_config *linker_cfg
   return LT_OK;
 }
 
+// step [E] of the runner on a track set (lt_refine.cpp): the tracks as CSR arrays through the kernels with
+// the cameras the context holds on the device; every track's line becomes the re-cut segment of its refined line
+int lt_refine_tracks(lt_ctx *ctx, lt_trackset *ts, const lt_refine_config *cfg) {
+  if (!ctx || !ts) return LT_ERR_ARGUMENT;
+  const size_t T = ts->tracks.size();
+  std::vector<int64_t> off(T + 1, 0);
+  for (size_t t = 0; t < T; ++t) off[t + 1] = off[t] + (int64_t)ts->tracks[t].m.size();
+  const size_t M = (size_t)off[T];
+  std::vector<double> line6(6 * T), l2(4 * M), l3(6 * M);
+  std::vector<int32_t> img(M);
+  for (size_t t = 0; t < T; ++t) {
+    std::memcpy(line6.data() + 6 * t, ts->tracks[t].line, 48);
+    size_t e = (size_t)off[t];
+    for (const Member &mm : ts->tracks[t].m) {
+      img[e] = mm.img_id;
+      std::memcpy(l2.data() + 4 * e, mm.l2d, 32);
+      for (int k = 0; k < 3; ++k) { l3[6 * e + k] = mm.l3d.s[k]; l3[6 * e + 3 + k] = mm.l3d.e[k]; }
+      ++e;
+    }
+  }
+  int rc = lt_impl::refine_with_ctx_cams(ctx, (int64_t)T, line6.data(), off.data(), img.data(), l2.data(), l3.data(), cfg);
+  if (rc) return rc;
+  std::vector<double> seg(6 * T);
+  rc = lt_refine_get(ctx, nullptr, seg.data(), nullptr, nullptr, nullptr);
+  if (rc) return rc;
+  for (size_t t = 0; t < T; ++t) {
+    std::memcpy(ts->tracks[t].line, seg.data() + 6 * t, 48);
+    ts->tracks[t].line[6] = -1.0;  // a fresh Line3d
+    ts->tracks[t].agg_k = -1;      // no longer the aggregate of the members
+  }
+  return LT_OK;
+}
+
 }  // extern "C"

@@ -235,6 +235,33 @@ class TrackSet:
             n = n_new
         return self
 
+    def refine(self, cfg, max_num_iterations=200):
+        """Step [E] of the runner (runners/line_triangulation.py:208-219) on the native container, cameras constant:
+        every track's line becomes the re-cut segment of its refined infinite line (limap_amd.optimize, DESIGN.md
+        section 19).  cfg: cfg["refinement"] or an optimize.HybridBAConfig.  The per-track results (parameters, costs,
+        iterations, termination codes) are in `.refine_result` afterwards."""
+        import copy
+        from . import optimize
+        ba = optimize.HybridBAConfig(cfg) if isinstance(cfg, dict) or cfg is None else copy.copy(cfg)
+        if not isinstance(ba, optimize.HybridBAConfig):
+            raise TypeError("TrackSet.refine: cfg must be a dict or an optimize.HybridBAConfig")
+        ba._check()
+        ba.max_num_iterations = int(max_num_iterations)
+        T = len(self)
+        if T == 0:
+            self.refine_result = dict(params=np.zeros((0, 6)), segments=np.zeros((0, 6)), cost=np.zeros((0, 2)),
+                                      iterations=np.zeros(0, np.int32), codes=np.zeros(0, np.int32))
+            return self
+        c = ba._struct(ba.num_outliers_aggregator, ba.constant_line)
+        self.ctx.chk(self.L.lt_refine_tracks(self.ctx.h, self.h, C.byref(c)))
+        P = np.zeros((T, 6)); seg = np.zeros((T, 6)); cost = np.zeros((T, 2))
+        it = np.zeros(T, np.int32); code = np.zeros(T, np.int32)
+        p = _capi.ptr
+        self.ctx.chk(self.L.lt_refine_get(self.ctx.h, p(P, C.c_double), p(seg, C.c_double), p(cost, C.c_double),
+                                          p(it, C.c_int32), p(code, C.c_int32)))
+        self.refine_result = dict(params=P, segments=seg, cost=cost, iterations=it, codes=code)
+        return self
+
     def arrays(self):
         T = len(self); M = int(self.L.lt_ts_num_members(self.h))
         line = np.zeros((max(T, 1), 7)); active = np.zeros(max(T, 1), np.uint8); off = np.zeros(T + 1, np.int64)
