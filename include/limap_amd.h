@@ -484,6 +484,17 @@ int lt_bpt_junctions_get_candidates(lt_ctx *ctx, int64_t *cand_off, double *cand
  * [0] upload, [1] kernels (with the counts and prefix sums that size their outputs), [2] sorts, [3] download and host
  * replay */
 int lt_bpt_get_timers(lt_ctx *ctx, double out[4]);
+/* The grid prefilter of lt_bpt_junctions on the host, for tests (no context, no device; the expressions are the ones
+ * the device compiles, limap_amd/csrc/lt_bpt.h).  lt_fn_bpt_grid_keys: the grid of one image from its lines
+ * (grid_out, may be NULL: lo x, lo y, cell size) and the sort key of every point xy[2 n_pts] as a candidate of image
+ * img: img << 40 | cell y << 20 | cell x.  lt_fn_bpt_close_pairs_host: what k_bpt_close_pairs finds over n candidates
+ * with these keys (candidates into cell order, the 3 x 3 cell scan, the reference's distance test): n_pairs receives
+ * the number of pairs, pairs_out the first min(cap, n_pairs) of them in ascending order as i << 32 | j, i < j.
+ * LT_ERR_ARGUMENT for null pointers, non-finite coordinates or a NaN threshold. */
+int lt_fn_bpt_grid_keys(int img, int64_t n_lines, const double *lines4, double th_merge, int64_t n_pts, const double *xy,
+                        double grid_out[3], uint64_t *keys_out);
+int lt_fn_bpt_close_pairs_host(int64_t n, const uint64_t *keys, const double *xy, double th_merge, int64_t cap,
+                               uint64_t *pairs_out, int64_t *n_pairs);
 
 /* ---- limap.line2d matchers that are pure linear algebra: L2D2Matcher (line2d/L2D2/matcher.py) and the top-k form of
  * NNEndpointsMatcher (line2d/endpoints/matcher.py:71-111), a whole scene in one call.

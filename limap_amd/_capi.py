@@ -35,7 +35,7 @@ EXPORTED_SYMBOLS = [
     "lt_lines_point_dists", "lt_refline_counts", "lt_eval_get_timers",
     "lt_mesh_build", "lt_mesh_free", "lt_mesh_nearest_dists", "lt_mesh_line_samples",
     "lt_bpt_config_default", "lt_bpt_associate", "lt_bpt_associate_get", "lt_bpt_junctions", "lt_bpt_junctions_get",
-    "lt_bpt_junctions_get_candidates", "lt_bpt_get_timers",
+    "lt_bpt_junctions_get_candidates", "lt_bpt_get_timers", "lt_fn_bpt_grid_keys", "lt_fn_bpt_close_pairs_host",
     "lt_match_scene", "lt_match_get", "lt_match_get_scores", "lt_match_get_timers", "lt_fn_match_pair_host",
     "lt_vp_config_default", "lt_vp_detect", "lt_vp_get", "lt_vp_get_timers", "lt_fn_vp_detect_host",
     "lt_fn_vp_cluster_host", "lt_vp_cluster_sets",
@@ -289,6 +289,9 @@ def load_library():
     L.lt_bpt_junctions_get.argtypes = [vp, i64p, dp, i64p, i32p]
     L.lt_bpt_junctions_get_candidates.argtypes = [vp, i64p, dp, i32p, i32p]
     L.lt_bpt_get_timers.argtypes = [vp, dp]
+    L.lt_fn_bpt_grid_keys.argtypes = [C.c_int, C.c_int64, dp, C.c_double, C.c_int64, dp, dp, C.POINTER(C.c_uint64)]
+    L.lt_fn_bpt_close_pairs_host.argtypes = [C.c_int64, C.POINTER(C.c_uint64), dp, C.c_double, C.c_int64,
+                                             C.POINTER(C.c_uint64), i64p]
     fp = C.POINTER(C.c_float)
     L.lt_match_scene.argtypes = [vp, C.c_int, i64p, vp, C.c_int, i64p, i32p, C.POINTER(LtMatchConfig), i64p]
     L.lt_match_get.argtypes = [vp, i64p, i32p]

@@ -207,22 +207,8 @@ int lt_bpt_junctions(lt_ctx *ctx, int n_img, const int64_t *line_off, const doub
   std::vector<int> row_img((size_t)nl);
   std::vector<BptGrid> grid((size_t)n_img);
   for (int m = 0; m < n_img; ++m) {
-    double lo[2] = {DBL_MAX, DBL_MAX}, hi[2] = {-DBL_MAX, -DBL_MAX};
-    for (long long k = line_off[m]; k < line_off[m + 1]; ++k) {
-      row_img[(size_t)k] = m;
-      for (int c = 0; c < 4; ++c) {
-        lo[c & 1] = std::min(lo[c & 1], lines[4 * k + c]);
-        hi[c & 1] = std::max(hi[c & 1], lines[4 * k + c]);
-      }
-    }
-    BptGrid g{0.0, 0.0, 1.0};
-    if (line_off[m + 1] > line_off[m]) {
-      const double ext = std::max(hi[0] - lo[0], hi[1] - lo[1]);
-      double cell = std::max(kBptCellSlack * th_m, ext / (double)((1 << kBptCellBits) - 2));
-      if (!(cell > 0.0)) cell = 1.0;
-      g = BptGrid{lo[0], lo[1], cell};
-    }
-    grid[(size_t)m] = g;
+    for (long long k = line_off[m]; k < line_off[m + 1]; ++k) row_img[(size_t)k] = m;
+    grid[(size_t)m] = bpt_grid_of(lines + 4 * line_off[m], line_off[m + 1] - line_off[m], th_m);
   }
   if (int rc = upload_vec(ctx, ctx->d_bp_idx2, row_img)) return rc;
   if (int rc = upload_vec(ctx, ctx->d_bp_misc, grid)) return rc;
@@ -464,6 +450,48 @@ int lt_bpt_junctions_get_candidates(lt_ctx *ctx, int64_t *cand_off, double *cand
   if (cand_xy) std::copy(ctx->bp_cand_xy.begin(), ctx->bp_cand_xy.end(), cand_xy);
   if (cand_lines) std::copy(ctx->bp_cand_lines.begin(), ctx->bp_cand_lines.end(), cand_lines);
   if (parents) std::copy(ctx->bp_parents.begin(), ctx->bp_parents.end(), parents);
+  return LT_OK;
+}
+
+int lt_fn_bpt_grid_keys(int img, int64_t n_lines, const double *lines4, double th_merge, int64_t n_pts, const double *xy,
+                        double grid_out[3], uint64_t *keys_out) {
+  if (img < 0 || img >= kMaxImages || n_lines < 0 || n_pts < 0 || (n_lines > 0 && !lines4) || (n_pts > 0 && !xy) ||
+      (n_pts > 0 && !keys_out) || std::isnan(th_merge))
+    return LT_ERR_ARGUMENT;
+  for (int64_t k = 0; k < 4 * n_lines; ++k)
+    if (!std::isfinite(lines4[k])) return LT_ERR_ARGUMENT;
+  for (int64_t k = 0; k < 2 * n_pts; ++k)
+    if (!std::isfinite(xy[k])) return LT_ERR_ARGUMENT;
+  const BptGrid g = bpt_grid_of(lines4, n_lines, th_merge);
+  if (grid_out) {
+    grid_out[0] = g.lox;
+    grid_out[1] = g.loy;
+    grid_out[2] = g.cell;
+  }
+  for (int64_t k = 0; k < n_pts; ++k) keys_out[k] = bpt_key_of(img, xy[2 * k], xy[2 * k + 1], g);
+  return LT_OK;
+}
+
+int lt_fn_bpt_close_pairs_host(int64_t n, const uint64_t *keys, const double *xy, double th_merge, int64_t cap,
+                               uint64_t *pairs_out, int64_t *n_pairs) {
+  if (n < 0 || n > kMaxCandidates || cap < 0 || (n > 0 && (!keys || !xy)) || (cap > 0 && !pairs_out) || !n_pairs ||
+      std::isnan(th_merge))
+    return LT_ERR_ARGUMENT;
+  std::vector<unsigned> idx((size_t)n);
+  for (int64_t k = 0; k < n; ++k) idx[(size_t)k] = (unsigned)k;
+  std::stable_sort(idx.begin(), idx.end(), [&](unsigned a, unsigned b) { return keys[a] < keys[b]; });
+  std::vector<unsigned long long> skeys((size_t)n);
+  for (int64_t k = 0; k < n; ++k) skeys[(size_t)k] = keys[idx[(size_t)k]];
+  std::vector<int> cnt((size_t)n, 0);  // two passes, as on the device: count, prefix sums, fill
+  for (int64_t s = 0; s < n; ++s)
+    cnt[idx[(size_t)s]] = bpt_close_pairs_of(n, skeys.data(), idx.data(), xy, th_merge, s, nullptr);
+  const std::vector<long long> off = scan(cnt);
+  std::vector<unsigned long long> pairs((size_t)off.back());
+  for (int64_t s = 0; s < n; ++s)
+    bpt_close_pairs_of(n, skeys.data(), idx.data(), xy, th_merge, s, pairs.data() + off[idx[(size_t)s]]);
+  std::sort(pairs.begin(), pairs.end());
+  *n_pairs = (int64_t)pairs.size();
+  std::copy(pairs.begin(), pairs.begin() + std::min<int64_t>(cap, (int64_t)pairs.size()), pairs_out);
   return LT_OK;
 }
 

@@ -5,6 +5,11 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cfloat>
+
+#include "lt_geom.h"
+
 namespace lt {
 
 constexpr int kBptBlock = 256;         // lanes per workgroup: one point / junction / line pair / candidate each
@@ -13,6 +18,8 @@ constexpr int kBptPointTile = 1024;    // keypoints staged in LDS at a time by k
 constexpr int kBptCellBits = 20;       // grid cells per axis of k_bpt_close_pairs: 2^20
 constexpr double kBptCellSlack = 1.25; // cell >= slack * threshold_merge_junctions: a pair within the threshold lies
                                        // in adjacent cells whatever the rounding of the cell coordinate
+constexpr double kBptCellMin = 0x1p-500;  // no smaller cell: below 2^-511 the square of a coordinate difference
+                                          // underflows, and the reference's norm accepts pairs many thresholds apart
 
 // one 2D line, prepared on the device once (k_bpt_prep): direction, length and homogeneous coordinates as
 // Line2d::direction() / length() / coords() compute them (base/linebase.h:24-26, linebase.cc:35-39)
@@ -34,6 +41,81 @@ static_assert(sizeof(BptBlock) == 24, "BptBlock layout");
 struct BptGrid {
   double lox, loy, cell;
 };
+
+// ---- the grid of k_bpt_close_pairs, shared by the device, lt_bpt_junctions and the host twins of lt_bpt.cpp
+// (lt_fn_bpt_grid_keys, lt_fn_bpt_close_pairs_host), so that tests reach it without a GPU ----
+
+// the grid of an image with the lines lines4[0 .. 4 n_lines): lo = the smallest endpoint coordinates
+inline BptGrid bpt_grid_of(const double *lines4, long long n_lines, double th_m) {
+  double lo[2] = {DBL_MAX, DBL_MAX}, hi[2] = {-DBL_MAX, -DBL_MAX};
+  for (long long k = 0; k < n_lines; ++k)
+    for (int c = 0; c < 4; ++c) {
+      lo[c & 1] = std::min(lo[c & 1], lines4[4 * k + c]);
+      hi[c & 1] = std::max(hi[c & 1], lines4[4 * k + c]);
+    }
+  BptGrid g{0.0, 0.0, 1.0};
+  if (n_lines > 0) {
+    const double ext = std::max(hi[0] - lo[0], hi[1] - lo[1]);
+    double cell = std::max(kBptCellSlack * th_m, ext / (double)((1 << kBptCellBits) - 2));
+    if (!(cell > 0.0)) cell = 1.0;
+    if (cell < kBptCellMin) cell = kBptCellMin;
+    g = BptGrid{lo[0], lo[1], cell};
+  }
+  return g;
+}
+
+LT_HD unsigned bpt_cell_of(double v, double lo, double cell) {
+  const double u = floor((v - lo) / cell);
+  const double hi = (double)((1u << kBptCellBits) - 1u);
+  return (unsigned)(u < 0.0 ? 0.0 : (u > hi ? hi : u));  // (a NaN never gets here: the host stops at the flag)
+}
+
+// the sort key of a candidate: image << 40 | cell y << 20 | cell x
+LT_HD unsigned long long bpt_key_of(int img, double x, double y, const BptGrid &g) {
+  return ((unsigned long long)img << (2 * kBptCellBits)) |
+         ((unsigned long long)bpt_cell_of(y, g.loy, g.cell) << kBptCellBits) | bpt_cell_of(x, g.lox, g.cell);
+}
+
+LT_HD double bpt_norm2(double x, double y) { return sqrt(x * x + y * y); }
+
+LT_HD long long bpt_lower_bound(const unsigned long long *a, long long n, unsigned long long v) {
+  long long lo = 0, hi = n;
+  while (lo < hi) {
+    const long long mid = (lo + hi) >> 1;
+    if (a[mid] < v) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// the close pairs (c, j > c) of the candidate at position s of the cell order (keys, idx sorted): the 3 x 3 cells
+// around c, one binary search per cell row.  Returns their number; dst (may be null) receives c << 32 | j
+LT_HD int bpt_close_pairs_of(long long n_cand, const unsigned long long *keys, const unsigned *idx,
+                             const double *cand_xy, double th, long long s, unsigned long long *dst) {
+  const unsigned long long key = keys[s];
+  const unsigned c = idx[s];
+  const double x = cand_xy[2 * (long long)c], y = cand_xy[2 * (long long)c + 1];
+  const unsigned mask = (1u << kBptCellBits) - 1u;
+  const unsigned cx = (unsigned)key & mask, cy = (unsigned)(key >> kBptCellBits) & mask;
+  const unsigned long long img_bits = key >> (2 * kBptCellBits) << (2 * kBptCellBits);
+  const unsigned x0 = cx > 0 ? cx - 1 : 0, x1 = cx < mask ? cx + 1 : mask;
+  int n = 0;
+  for (int dy = -1; dy <= 1; ++dy) {
+    if ((dy < 0 && cy == 0) || (dy > 0 && cy == mask)) continue;
+    const unsigned long long rowk = img_bits | ((unsigned long long)(cy + dy) << kBptCellBits);
+    long long q = bpt_lower_bound(keys, n_cand, rowk | x0);
+    const unsigned long long last = rowk | x1;
+    for (; q < n_cand && keys[q] <= last; ++q) {
+      const unsigned j = idx[q];
+      if (j <= c) continue;
+      // (intersections[i].p - intersections[j].p).norm() > threshold_merge_junctions, i < j  (:135-137)
+      const double dist = bpt_norm2(x - cand_xy[2 * (long long)j], y - cand_xy[2 * (long long)j + 1]);
+      if (dist > th) continue;
+      if (dst) dst[n] = ((unsigned long long)c << 32) | j;
+      ++n;
+    }
+  }
+  return n;
+}
 
 // a junction candidate that came from a line pair (the endpoints need no record)
 struct BptInter {

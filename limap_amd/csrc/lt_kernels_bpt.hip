@@ -92,14 +92,12 @@ __global__ void __launch_bounds__(kBptBlock) k_bpt_assoc(const BptBlock *__restr
   if (!FILL && live) cnt[p] = n;
 }
 
-__device__ __forceinline__ double norm2(double x, double y) { return sqrt(x * x + y * y); }
-
 // PL_Bipartite2d::intersect (pl_bipartite.cc:166-204)
 __device__ __forceinline__ bool intersect(const BptLine &a, const BptLine &b, double th, double *ox, double *oy) {
-  if (norm2(a.sx - b.sx, a.sy - b.sy) <= th) { *ox = (a.sx + b.sx) / 2.0; *oy = (a.sy + b.sy) / 2.0; return true; }
-  if (norm2(a.ex - b.sx, a.ey - b.sy) <= th) { *ox = (a.ex + b.sx) / 2.0; *oy = (a.ey + b.sy) / 2.0; return true; }
-  if (norm2(a.sx - b.ex, a.sy - b.ey) <= th) { *ox = (a.sx + b.ex) / 2.0; *oy = (a.sy + b.ey) / 2.0; return true; }
-  if (norm2(a.ex - b.ex, a.ey - b.ey) <= th) { *ox = (a.ex + b.ex) / 2.0; *oy = (a.ey + b.ey) / 2.0; return true; }
+  if (bpt_norm2(a.sx - b.sx, a.sy - b.sy) <= th) { *ox = (a.sx + b.sx) / 2.0; *oy = (a.sy + b.sy) / 2.0; return true; }
+  if (bpt_norm2(a.ex - b.sx, a.ey - b.sy) <= th) { *ox = (a.ex + b.sx) / 2.0; *oy = (a.ey + b.sy) / 2.0; return true; }
+  if (bpt_norm2(a.sx - b.ex, a.sy - b.ey) <= th) { *ox = (a.sx + b.ex) / 2.0; *oy = (a.sy + b.ey) / 2.0; return true; }
+  if (bpt_norm2(a.ex - b.ex, a.ey - b.ey) <= th) { *ox = (a.ex + b.ex) / 2.0; *oy = (a.ey + b.ey) / 2.0; return true; }
   const d3 h = unit(cross(mk3(a.c0, a.c1, a.c2), mk3(b.c0, b.c1, b.c2)));
   const double px = h.x / (h.z + kEps), py = h.y / (h.z + kEps);
   const double proj1 = (px - a.sx) * a.dx + (py - a.sy) * a.dy;
@@ -163,12 +161,6 @@ __global__ void __launch_bounds__(kBptBlock) k_bpt_intersect(const int *__restri
   if (!FILL && threadIdx.x == 0) cnt[row] = n;
 }
 
-__device__ __forceinline__ unsigned cell_of(double v, double lo, double cell) {
-  const double u = floor((v - lo) / cell);
-  const double hi = (double)((1u << kBptCellBits) - 1u);
-  return (unsigned)(u < 0.0 ? 0.0 : (u > hi ? hi : u));  // (a NaN never gets here: the host stops at the flag)
-}
-
 __device__ __forceinline__ int image_of(const long long *off, int n, long long k) {  // off[img] <= k < off[img + 1]
   int lo = 0, hi = n;
   while (hi - lo > 1) {
@@ -205,18 +197,8 @@ __global__ void __launch_bounds__(kBptBlock) k_bpt_candidates(int n_img, long lo
   cand_xy[2 * c] = x;
   cand_xy[2 * c + 1] = y;
   const BptGrid g = grid[img];
-  keys[c] = ((unsigned long long)img << (2 * kBptCellBits)) |
-            ((unsigned long long)cell_of(y, g.loy, g.cell) << kBptCellBits) | cell_of(x, g.lox, g.cell);
+  keys[c] = bpt_key_of(img, x, y, g);
   idx[c] = (unsigned)c;
-}
-
-__device__ __forceinline__ long long lower_bound(const unsigned long long *a, long long n, unsigned long long v) {
-  long long lo = 0, hi = n;
-  while (lo < hi) {
-    const long long mid = (lo + hi) >> 1;
-    if (a[mid] < v) lo = mid + 1; else hi = mid;
-  }
-  return lo;
 }
 
 // one lane per candidate (in cell order, so that the lanes of a wave read the same neighbourhood)
@@ -230,30 +212,8 @@ __global__ void __launch_bounds__(kBptBlock) k_bpt_close_pairs(long long n_cand,
                                                                unsigned long long *__restrict__ out) {
   const long long s = (long long)blockIdx.x * kBptBlock + threadIdx.x;
   if (s >= n_cand) return;
-  const unsigned long long key = keys[s];
   const unsigned c = idx[s];
-  const double x = cand_xy[2 * (long long)c], y = cand_xy[2 * (long long)c + 1];
-  const unsigned mask = (1u << kBptCellBits) - 1u;
-  const unsigned cx = (unsigned)key & mask, cy = (unsigned)(key >> kBptCellBits) & mask;
-  const unsigned long long img_bits = key >> (2 * kBptCellBits) << (2 * kBptCellBits);
-  const unsigned x0 = cx > 0 ? cx - 1 : 0, x1 = cx < mask ? cx + 1 : mask;
-  int n = 0;
-  unsigned long long *dst = FILL ? out + off[c] : nullptr;
-  for (int dy = -1; dy <= 1; ++dy) {
-    if ((dy < 0 && cy == 0) || (dy > 0 && cy == mask)) continue;
-    const unsigned long long rowk = img_bits | ((unsigned long long)(cy + dy) << kBptCellBits);
-    long long q = lower_bound(keys, n_cand, rowk | x0);
-    const unsigned long long last = rowk | x1;
-    for (; q < n_cand && keys[q] <= last; ++q) {
-      const unsigned j = idx[q];
-      if (j <= c) continue;
-      // (intersections[i].p - intersections[j].p).norm() > threshold_merge_junctions, i < j  (:135-137)
-      const double dist = norm2(x - cand_xy[2 * (long long)j], y - cand_xy[2 * (long long)j + 1]);
-      if (dist > th) continue;
-      if (FILL) dst[n] = ((unsigned long long)c << 32) | j;
-      ++n;
-    }
-  }
+  const int n = bpt_close_pairs_of(n_cand, keys, idx, cand_xy, th, s, FILL ? out + off[c] : nullptr);
   if (!FILL) cnt[c] = n;
 }
 

@@ -150,13 +150,15 @@ def _associate(lines_list, points_list, cfg, device=0):
     return out
 
 
-def _junctions(lines_list, kps_list, cfg, device=0, candidates=False):
-    """per image (xy (J, 2), id_off (J + 1), line indices): one native call for the batch"""
+def _junctions(lines_list, kps_list, cfg, device=0, candidates=False, sizes=False):
+    """per image (xy (J, 2), id_off (J + 1), line indices): one native call for the batch.  candidates: also the
+    per-image candidate lists; sizes: also lt_bpt_junctions' sizes[4] (junctions, line indices, candidates, close
+    pairs of the whole call)"""
     ctx = _context(device)
     loff, lflat = _csr(lines_list, 4)
     koff, kflat = _csr(kps_list, 2)
     st = cfg._struct()
-    sizes = np.zeros(4, np.int64)
+    want_sizes, sizes = sizes, np.zeros(4, np.int64)
     n = len(lines_list)
     ctx.chk(ctx.L.lt_bpt_junctions(ctx.h, n, _p(loff, C.c_int64), _p(lflat), _p(koff, C.c_int64), _p(kflat),
                                    C.byref(st), _p(sizes, C.c_int64)))
@@ -170,7 +172,7 @@ def _junctions(lines_list, kps_list, cfg, device=0, candidates=False):
         o = ioff[joff[m]:joff[m + 1] + 1]
         out.append((xy[joff[m]:joff[m + 1]].copy(), o - o[0], idx[o[0]:o[-1]].copy()))
     if not candidates:
-        return out
+        return (out, sizes) if want_sizes else out
     coff = np.zeros(n + 1, np.int64)
     cxy = np.zeros((max(int(sizes[2]), 1), 2))
     cl = np.zeros((max(int(sizes[2]), 1), 2), np.int32)
@@ -179,7 +181,7 @@ def _junctions(lines_list, kps_list, cfg, device=0, candidates=False):
                                                   _p(par, C.c_int32)))
     cands = [dict(xy=cxy[coff[m]:coff[m + 1]].copy(), lines=cl[coff[m]:coff[m + 1]].copy(),
                   parents=par[coff[m]:coff[m + 1]].copy()) for m in range(n)]
-    return out, cands
+    return (out, cands, sizes) if want_sizes else (out, cands)
 
 
 class PL_Bipartite2d:

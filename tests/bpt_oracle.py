@@ -183,16 +183,18 @@ def nearest_dists(kps, q):
 
 def junctions(lines, kps, cfg=None, full=False):
     """compute_intersection_with_points on a bipartite of the lines alone: dict(xy (J, 2), line_ids list of lists,
-    cand_xy, cand_lines, parents (after the last root look-ups), roots, merged_xy)"""
+    cand_xy, cand_lines, parents (after the last root look-ups), roots, merged_xy, pairs (the close pairs; None with
+    full=True))"""
     c = config(cfg)
     a = np.asarray(lines, np.float64).reshape(-1, 4)
     kps = np.asarray(kps, np.float64).reshape(-1, 2)
     if a.shape[0] == 0:  # the reference's loop bounds wrap around: defined here as no junction
         return dict(xy=np.zeros((0, 2)), line_ids=[], cand_xy=np.zeros((0, 2)), cand_lines=np.zeros((0, 2), np.int64),
-                    parents=[], roots=[], merged_xy=np.zeros((0, 2)))
+                    parents=[], roots=[], merged_xy=np.zeros((0, 2)), pairs=np.zeros((0, 2), np.int64))
     xy, ln = candidates(a, c["threshold_intersection"])
     th = c["threshold_merge_junctions"]
-    parents = merge_full(xy, th) if full else merge_sparse(xy, th)
+    pairs = None if full else close_pairs(xy, th)
+    parents = merge_full(xy, th) if full else merge_sparse(xy, th, pairs)
     rt = [find_root(parents, k) for k in range(len(parents))]  # pl_bipartite.cc:145-146
     groups = {}
     for k, r in enumerate(rt):
@@ -213,7 +215,7 @@ def junctions(lines, kps, cfg=None, full=False):
     if kps.shape[0]:  # `if (!tree.empty())`
         keep = ~(nearest_dists(kps, mxy) < th)
     return dict(xy=mxy[keep], line_ids=[m for m, k in zip(mids, keep) if k], cand_xy=xy, cand_lines=ln,
-                parents=parents, roots=rt, merged_xy=mxy)
+                parents=parents, roots=rt, merged_xy=mxy, pairs=pairs)
 
 
 def bipartite_dict(lines, xy, point3D_ids, ids, cfg=None, line_ids=None):

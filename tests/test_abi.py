@@ -19,7 +19,8 @@ def test_header_declares_expected_surface():
     syms = declared_symbols()
     for must in ("lt_create", "lt_init", "lt_triangulate_image", "lt_triangulate_image_exhaustive",
                  "lt_compute_tracks", "lt_get_tracks", "lt_set_ranges", "lt_get_best", "lt_vp_detect",
-                 "lt_fn_vp_cluster_host", "lt_vp_cluster_sets"):
+                 "lt_fn_vp_cluster_host", "lt_vp_cluster_sets", "lt_bpt_junctions", "lt_fn_bpt_grid_keys",
+                 "lt_fn_bpt_close_pairs_host"):
         assert must in syms
 
 

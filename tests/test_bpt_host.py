@@ -188,3 +188,157 @@ def test_error_cases():
         b.add_keypoints_with_point3D_ids(np.array([[np.inf, 0.0]]), [1])
     with pytest.raises(RuntimeError):
         st.PL_Bipartite2d({"points_": {}})
+
+
+# ---- the grid prefilter of k_bpt_close_pairs through its host twins (lt_bpt.h, compiled for the host) ------------------
+import ctypes as C  # noqa: E402
+
+import bpt_cases as bc  # noqa: E402
+
+MASK = (1 << 20) - 1
+
+
+def grid_keys(lib, lines, th, xy, img=0):
+    """lt_fn_bpt_grid_keys: (lo x, lo y, cell), keys (n,) uint64"""
+    lines = np.ascontiguousarray(lines, np.float64).reshape(-1, 4)
+    xy = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+    grid, keys = np.zeros(3), np.zeros(max(xy.shape[0], 1), np.uint64)
+    dp = C.POINTER(C.c_double)
+    rc = lib.lt_fn_bpt_grid_keys(img, lines.shape[0], lines.ctypes.data_as(dp), float(th), xy.shape[0],
+                                 xy.ctypes.data_as(dp), grid.ctypes.data_as(dp), keys.ctypes.data_as(C.POINTER(C.c_uint64)))
+    assert rc == 0
+    return grid, keys[:xy.shape[0]]
+
+
+def host_pairs(lib, keys, xy, th):
+    """lt_fn_bpt_close_pairs_host: (P, 2) int64, lexicographic"""
+    xy = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+    keys = np.ascontiguousarray(keys, np.uint64)
+    n, u64p = C.c_int64(0), C.POINTER(C.c_uint64)
+    out = np.zeros(1, np.uint64)
+    for _ in range(2):  # the count, then the pairs
+        rc = lib.lt_fn_bpt_close_pairs_host(xy.shape[0], keys.ctypes.data_as(u64p), xy.ctypes.data_as(C.POINTER(C.c_double)),
+                                            float(th), out.shape[0], out.ctypes.data_as(u64p), C.byref(n))
+        assert rc == 0
+        if n.value <= out.shape[0]:
+            break
+        out = np.zeros(n.value, np.uint64)
+    out = out[:n.value]
+    return np.stack([out >> np.uint64(32), out & np.uint64(0xffffffff)], 1).astype(np.int64)
+
+
+def check_prefilter(lib, lines, th, xy, pairs=None, img=0):
+    """every close pair of the restatement lies in the same or adjacent cells, every key inside the image's bit
+    field, and the scan over the 3 x 3 cells finds exactly the restatement's pairs.  Returns the cells."""
+    xy = np.asarray(xy, np.float64).reshape(-1, 2)
+    grid, keys = grid_keys(lib, lines, th, xy, img)
+    assert grid[2] > 0.0 and np.isfinite(grid[:2]).all()
+    assert (keys >> np.uint64(40) == np.uint64(img)).all()
+    cx, cy = (keys & np.uint64(MASK)).astype(np.int64), ((keys >> np.uint64(20)) & np.uint64(MASK)).astype(np.int64)
+    pairs = bo.close_pairs(xy, th) if pairs is None else pairs
+    i, j = pairs[:, 0], pairs[:, 1]
+    assert (np.abs(cx[i] - cx[j]) <= 1).all() and (np.abs(cy[i] - cy[j]) <= 1).all()
+    assert np.array_equal(host_pairs(lib, keys, xy, th), pairs.reshape(-1, 2))
+    return grid, cx, cy
+
+
+@pytest.mark.parametrize("name", list(bc.FAMILIES))
+def test_case_generators_hold_their_properties(name):
+    cases = bc.family(name)  # the generators assert
+    assert cases and all(bc.reference(c)["cand_xy"].shape[0] <= bc.MAX_CANDIDATES for c in cases)
+
+
+def test_batch_generators():
+    lines, kps = bc.many_images()
+    assert len(lines) == len(kps) == 3000 and all(lines[m].size == kps[m].size == 0 for m in (0, 1, 2, -3, -2, -1))
+    assert [c[1].shape[0] for c in bc.sandwich()] == [1, 769, 1, 40, 1]
+
+
+@pytest.mark.parametrize("name", list(bc.FAMILIES))
+def test_close_pairs_share_adjacent_cells_on_case_families(gpu_lib, name):
+    for k, c in enumerate(bc.family(name)):
+        o = bc.reference(c)
+        th = bo.config(c[3])["threshold_merge_junctions"]
+        grid, cx, cy = check_prefilter(gpu_lib, c[1], th, o["cand_xy"], o["pairs"], img=(1 << 23) - 1 - k)
+        a = c[1].reshape(-1, 2)
+        assert grid[:2].tolist() == a.min(0).tolist()
+        assert cx.min() == 0 and cy.min() == 0  # the endpoints at lo
+        if bc.extent_branch(c[1], th):          # the whole grid is in use
+            assert max(cx.max(), cy.max()) >= (1 << 20) - 3
+
+
+def _adversarial():
+    """(tag, lines, th, points): pairs exactly th apart astride cell boundaries, points at and beyond the box, a huge
+    lo, no extent at all, and the thresholds 0, negative, +inf, subnormal"""
+    out = []
+    frame = np.array([[0.0, 0.0, 640.0, 480.0]])
+    for th in (2.0, 0.7, 1e-4, 500.0):
+        grid = max(1.25 * th, 640.0 / ((1 << 20) - 2))
+        k = np.arange(1, 40, dtype=np.float64)
+        b = k * grid  # cell boundaries
+        pts = [np.stack([b - th / 2, 7 + 0 * k], 1), np.stack([b + th / 2, 7 + 0 * k], 1),
+               np.stack([9 + 0 * k, b - th / 2], 1), np.stack([9 + 0 * k, b + th / 2], 1),
+               np.stack([b, b], 1), np.stack([b + th, b], 1), np.stack([b, b - th], 1),
+               np.stack([np.nextafter(b, 0), b], 1), np.stack([np.nextafter(b, 0) + th, b], 1)]
+        out.append((f"boundary_th{th}", frame, th, np.concatenate(pts, 0)))
+    for th, thi in ((2.0, 40.0), (0.5, 40.0), (1e-4, 2.0)):
+        xs = [0.0, -th, th, -thi, -thi + th, -thi - th, 640.0, 640.0 + th, 640.0 - th, 640.0 + thi, 640.0 + thi - th,
+              640.0 + thi + th, 1e7, 1e7 + th, -1e7, -1e7 - th, 1e150, -1e150]
+        ys = [0.0, -th, 480.0, 480.0 + th, 480.0 + thi, -thi]
+        pts = np.array([[x, y] for x in xs for y in ys])
+        out.append((f"box_th{th}", frame, th, np.concatenate([pts, pts[:, ::-1]], 0)))
+    for lo in (1e15, -1e15):
+        k = np.arange(0, 60, dtype=np.float64)
+        x = lo + 0.5 * k
+        pts = np.concatenate([np.stack([x, -lo + 0 * k], 1), np.stack([x + 2.0, -lo + 0 * k], 1),
+                              np.stack([lo + 0 * k, -lo + 0.5 * k + 2.0], 1)], 0)
+        out.append((f"lo_{lo}", frame + np.array([lo, -lo, lo, -lo]), 2.0, pts))
+    dot = np.array([[5.0, 5.0, 5.0, 5.0]] * 3)
+    k = np.arange(-20, 21, dtype=np.float64)
+    ring = np.concatenate([np.stack([5 + 2.0 * k, 5 + 0 * k], 1), np.stack([5 + 0 * k, 5 + 2.0 * k], 1),
+                           np.stack([5 + 2.0 * k, 5 + 2.0 * k], 1)], 0)
+    out.append(("extent0", dot, 2.0, ring))
+    rng = np.random.default_rng(8)
+    cloud = rng.uniform(0, 30, (150, 2))
+    cloud[100:] = cloud[:50]  # coincident points, for the threshold 0
+    tiny = 5e-324
+    for th in (0.0, -1.0, float("inf"), tiny, 1e-310, 1e-160):
+        out.append((f"frame_th{th}", frame, th, cloud))
+        out.append((f"extent0_th{th}", dot, th, np.concatenate([ring, ring[:9]], 0)))
+        # everything within a few thousand thresholds of the origin: the squares of the differences underflow, and the
+        # reference's norm is 0 for all of them
+        step = th if 0 < th < 1 else tiny
+        m = np.arange(0, 3000, 7, dtype=np.float64)[:, None] * step
+        out.append((f"origin_th{th}", np.zeros((2, 4)), th, np.concatenate([m * [1, 0], m * [0, 1], m * [1, 1]], 0)))
+        out.append((f"small_extent_th{th}", np.array([[0.0, 0.0, 3000 * step, 0.0]]), th,
+                    np.concatenate([m * [1, 0], m * [1, 0] + [0, step]], 0)))
+    return out
+
+
+@pytest.mark.parametrize("case", _adversarial(), ids=lambda c: c[0])
+def test_close_pairs_share_adjacent_cells_on_adversarial_points(gpu_lib, case):
+    _, lines, th, pts = case
+    check_prefilter(gpu_lib, lines, th, pts, img=5)
+
+
+def test_grid_keys_reject_what_the_device_call_rejects(gpu_lib):
+    dp, u64p = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
+    lines, xy, keys = np.zeros((1, 4)), np.zeros((1, 2)), np.zeros(1, np.uint64)
+
+    def call(lines=lines, xy=xy, th=2.0, img=0):
+        return gpu_lib.lt_fn_bpt_grid_keys(img, 1, lines.ctypes.data_as(dp), th, 1, xy.ctypes.data_as(dp), None,
+                                           keys.ctypes.data_as(u64p))
+    assert call() == 0
+    assert call(th=float("nan")) == -2 and call(img=1 << 23) == -2 and call(img=-1) == -2
+    assert call(lines=np.array([[0.0, np.inf, 0.0, 0.0]])) == -2 and call(xy=np.array([[np.nan, 0.0]])) == -2
+
+
+def test_sparse_replay_equals_full_loop_on_case_families():
+    """DESIGN section 16's claim on structured clusters: stars, chains, polygons with shared vertices"""
+    moved = 0
+    for c in bc.reduced_cases():
+        o = bc.reference(c)
+        th = bo.config(c[3])["threshold_merge_junctions"]
+        assert o["roots"] == bo.roots(bo.merge_full(o["cand_xy"], th)), c[0]
+        moved += bc.count_reparents(o["cand_xy"], th, o["pairs"])
+    assert moved >= 10
