@@ -279,6 +279,16 @@ int lt_ts_filter_by_overlap(lt_ctx *ctx, lt_trackset *ts, double th_overlap, int
 /* one pass of _RemergeLineTracks (merging/merging.cc:513-644); the LineLinker3d is read from the
  * l3_* fields of linker_cfg; the all-pairs connection test runs on the GPU */
 int lt_ts_remerge_once(lt_ctx *ctx, lt_trackset *ts, const lt_config *linker_cfg, int num_outliers);
+/* The device part of lt_ts_remerge_once alone, for tests: the all-pairs LineLinker3d::check_connection of
+ * merging/merging.cc:519-556 (k_track_connect) over n_tracks lines (line7 = start3 end3 uncertainty) with their active
+ * flags; the linker as above.  edges_out: the connected pairs as (min << 32 | max), sorted and unique; *n_unique their
+ * number -- set also when edges_out (edges_cap entries) is too small, which returns LT_ERR_ARGUMENT.  capacity0: edge
+ * slots of the first launch, 0 = the default max(65536, 32 n_tracks); a launch that finds more is repeated once with
+ * room for all.  *n_raw: the device's edge counter of the launch that fitted (a pair of two active tracks counts from
+ * both sides, unless every track is active: then each pair is tested once), *attempts: launches. */
+int lt_fn_track_connect(lt_ctx *ctx, int64_t n_tracks, const double *line7, const uint8_t *active, const lt_config *linker_cfg,
+                        int64_t capacity0, uint64_t *edges_out, int64_t edges_cap, int64_t *n_unique, int64_t *n_raw,
+                        int32_t *attempts);
 
 /* ---- limap.merging.merging / MergeToLineTracks (merging/merging.py:6-21, merging/merging.cc:347-511): the merge of
  * one fitted 3D segment per 2D segment (runners/line_fitnmerge.py) into line tracks.  The context is initialised

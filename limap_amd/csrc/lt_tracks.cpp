@@ -288,11 +288,18 @@ int lt_ts_filter_by_overlap(lt_ctx *ctx, lt_trackset *ts, double th_overlap, int
   return LT_OK;
 }
 
-// One pass of RemergeLineTracks (merging/merging.cc:513-644).  linker = l3_* fields of `linker_cfg`.
-int lt_ts_remerge_once(lt_ctx *ctx, lt_trackset *ts, const lt_config *linker_cfg, int num_outliers) {
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  const int T = (int)ts->tracks.size();
-  if (T == 0) return LT_OK;
+}  // extern "C"
+
+namespace {
+
+// The device part of a remerge pass (merging/merging.cc:519-556): `pack(t, dst7)` writes track t's line (start, end,
+// uncertainty) and returns its active flag; the sorted, unique edges (min << 32 | max) of k_track_connect are left in
+// ctx->h_rm_edges.  capacity0: edge slots of the first launch, 0 = max(65536, 32 T); a launch that finds more edges than
+// it has slots for is repeated once with room for all of them.  *n_raw: the device counter of the launch that fitted (a
+// pair of two active tracks is counted from both sides unless every track is active), *attempts: launches.
+template <class Pack>
+int track_connect_edges(lt_ctx *ctx, int T, Pack pack, const lt_config *linker_cfg, unsigned long long capacity0,
+                        unsigned long long *n_raw, int *attempts) {
   LinkCfg3 l3;
   l3.score_th = linker_cfg->l3_score_th; l3.th_angle = linker_cfg->l3_th_angle; l3.th_overlap = linker_cfg->l3_th_overlap;
   l3.th_smartoverlap = linker_cfg->l3_th_smartoverlap; l3.th_smartangle = linker_cfg->l3_th_smartangle;
@@ -311,8 +318,7 @@ int lt_ts_remerge_once(lt_ctx *ctx, lt_trackset *ts, const lt_config *linker_cfg
   unsigned char *active = reinterpret_cast<unsigned char *>(inbuf.data() + 7 * (size_t)T);
   int n_active = 0;
   for (int t = 0; t < T; ++t) {
-    std::memcpy(&inbuf[7 * (size_t)t], ts->tracks[t].line, 56);
-    active[t] = ts->tracks[t].active ? 1 : 0;
+    active[t] = pack(t, &inbuf[7 * (size_t)t]) ? 1 : 0;
     n_active += active[t];
   }
   // the device buffers and the edge list live in the context: a remerge to its fixed point calls this several times
@@ -322,12 +328,16 @@ int lt_ts_remerge_once(lt_ctx *ctx, lt_trackset *ts, const lt_config *linker_cfg
   edges.clear();
   // d_edges = [edge count | edges ...]: count and the first kFirst edges come back in ONE copy behind the kernel
   constexpr unsigned long long kFirst = 4095;
-  unsigned long long capacity = std::max<unsigned long long>(1ull << 16, 32ull * (unsigned long long)T);
+  unsigned long long capacity = capacity0 ? capacity0 : std::max<unsigned long long>(1ull << 16, 32ull * (unsigned long long)T);
   int rc = LT_OK;
+  bool fitted = false;
+  *n_raw = 0;
+  *attempts = 0;
   std::vector<unsigned long long> &back = ctx->h_rm_back;
   back.resize((size_t)kFirst + 1);
   for (int attempt = 0; attempt < 8; ++attempt) {
-    if (!d_in.ensure(inbuf.size() * 8) || !d_edges.ensure((capacity + 1) * 8)) {
+    // (the copy behind the kernel reads kFirst + 1 words whatever the capacity is: the buffer is never smaller)
+    if (!d_in.ensure(inbuf.size() * 8) || !d_edges.ensure((std::max(capacity, kFirst) + 1) * 8)) {
       rc = fail(ctx, LT_ERR_HIP, "hipMalloc failed in remerge");
       break;
     }
@@ -339,6 +349,7 @@ int lt_ts_remerge_once(lt_ctx *ctx, lt_trackset *ts, const lt_config *linker_cfg
     launch_track_connect(st, T, d_in.as<double>(), reinterpret_cast<const unsigned char *>(d_in.as<double>() + 7 * (size_t)T),
                          n_active == T ? 1 : 0, l3, cos_guard, d_edges.as<unsigned long long>() + 1, capacity,
                          d_edges.as<unsigned long long>());
+    ++*attempts;
     if (hipMemcpyAsync(back.data(), d_edges.p, (kFirst + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess) {
       rc = fail(ctx, LT_ERR_HIP, "HIP failure in k_track_connect");
@@ -356,12 +367,65 @@ int lt_ts_remerge_once(lt_ctx *ctx, lt_trackset *ts, const lt_config *linker_cfg
                     hipMemcpyDeviceToHost) != hipSuccess)
         rc = fail(ctx, LT_ERR_HIP, "HIP copy failed in remerge");
     }
+    *n_raw = n;
+    fitted = true;
     break;
   }
   if (rc) return rc;
+  if (!fitted) return fail(ctx, LT_ERR_STATE, "k_track_connect: the edge count kept growing between launches");
   // std::set<pair<size_t,size_t>> order + dedupe
   std::sort(edges.begin(), edges.end());
   edges.erase(std::unique(edges.begin(), edges.end()), edges.end());
+  return LT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// The edge set of k_track_connect on plain arrays (include/limap_amd.h): the device part of lt_ts_remerge_once alone.
+int lt_fn_track_connect(lt_ctx *ctx, int64_t n_tracks, const double *line7, const uint8_t *active, const lt_config *linker_cfg,
+                        int64_t capacity0, uint64_t *edges_out, int64_t edges_cap, int64_t *n_unique, int64_t *n_raw,
+                        int32_t *attempts) {
+  if (!ctx) return LT_ERR_ARGUMENT;
+  if (n_tracks < 0 || n_tracks > 0x7FFFFFFF || capacity0 < 0 || edges_cap < 0 || !linker_cfg || !n_unique ||
+      (n_tracks > 0 && (!line7 || !active)))
+    return fail(ctx, LT_ERR_ARGUMENT, "lt_fn_track_connect: bad argument");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  unsigned long long raw = 0;
+  int launches = 0;
+  ctx->h_rm_edges.clear();
+  if (n_tracks > 0) {
+    int rc = track_connect_edges(ctx, (int)n_tracks, [&](int t, double *dst) {
+      std::memcpy(dst, line7 + 7 * (size_t)t, 56);
+      return active[t] != 0;
+    }, linker_cfg, (unsigned long long)capacity0, &raw, &launches);
+    if (rc) return rc;
+  }
+  const std::vector<unsigned long long> &edges = ctx->h_rm_edges;
+  *n_unique = (int64_t)edges.size();
+  if (n_raw) *n_raw = (int64_t)raw;
+  if (attempts) *attempts = launches;
+  if ((int64_t)edges.size() > edges_cap || (!edges.empty() && !edges_out))
+    return fail(ctx, LT_ERR_ARGUMENT, "lt_fn_track_connect: edges_out holds " + std::to_string(edges_cap) + " edges, " +
+                                          std::to_string(edges.size()) + " found");
+  if (!edges.empty()) std::memcpy(edges_out, edges.data(), edges.size() * 8);
+  return LT_OK;
+}
+
+// One pass of RemergeLineTracks (merging/merging.cc:513-644).  linker = l3_* fields of `linker_cfg`.
+int lt_ts_remerge_once(lt_ctx *ctx, lt_trackset *ts, const lt_config *linker_cfg, int num_outliers) {
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const int T = (int)ts->tracks.size();
+  if (T == 0) return LT_OK;
+  unsigned long long n_raw = 0;
+  int attempts = 0;
+  int rc = track_connect_edges(ctx, T, [&](int t, double *dst) {
+    std::memcpy(dst, ts->tracks[t].line, 56);
+    return ts->tracks[t].active;
+  }, linker_cfg, 0, &n_raw, &attempts);
+  if (rc) return rc;
+  const std::vector<unsigned long long> &edges = ctx->h_rm_edges;
   std::vector<int> parent((size_t)T, -1);
   std::vector<size_t> gsize((size_t)T, 1);
   for (unsigned long long e : edges) {

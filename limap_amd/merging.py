@@ -290,6 +290,31 @@ class TrackSet:
         return out
 
 
+def track_connect_edges(ctx, line7, active, linker3d, capacity0=0):
+    """The edge set of one remerge pass's device part (lt_fn_track_connect, k_track_connect) on plain arrays, for tests:
+    line7 (T, 7) = start, end, uncertainty; active (T,).  -> dict(edges (E, 2) int64 as (min, max), sorted and unique;
+    n_raw: the device's edge counter; attempts: launches).  capacity0: edge slots of the first launch (0 = default)."""
+    line7 = np.ascontiguousarray(np.asarray(line7, np.float64).reshape(-1, 7))
+    active = np.ascontiguousarray(np.asarray(active).reshape(-1) != 0, np.uint8)
+    if len(active) != len(line7):
+        raise ValueError(f"track_connect_edges: {len(line7)} lines, {len(active)} active flags")
+    cfg = _linker_cfg(linker3d)
+    T = len(line7)
+    p = _capi.ptr
+    n_unique, n_raw, attempts = C.c_int64(), C.c_int64(), C.c_int32()
+    out = np.zeros(max(4 * T, 1), np.uint64)
+    for _ in range(2):
+        rc = ctx.L.lt_fn_track_connect(ctx.h, T, p(line7, C.c_double), p(active, C.c_uint8), C.byref(cfg), int(capacity0),
+                                       p(out, C.c_uint64), len(out), C.byref(n_unique), C.byref(n_raw), C.byref(attempts))
+        if rc == 0 or n_unique.value <= len(out):
+            break
+        out = np.zeros(n_unique.value, np.uint64)  # too small: the call said how many there are
+    ctx.chk(rc)
+    e = out[:n_unique.value]
+    edges = np.stack([(e >> np.uint64(32)).astype(np.int64), (e & np.uint64(0xFFFFFFFF)).astype(np.int64)], 1)
+    return dict(edges=edges, n_raw=int(n_raw.value), attempts=int(attempts.value))
+
+
 # ---- module-level functions with the reference's signatures ------------------------------------
 def merging(linker, all_2d_segs, imagecols, seg3d_list, neighbors, var2d=5.0):
     """limap.merging.merging (merging/merging.py:6-21): -> (graph, linetracks)."""

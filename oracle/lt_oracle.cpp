@@ -2526,6 +2526,24 @@ double ora_linker3d_score(const ora_config *cfg, int mode3d, const double a[10],
   if (mode3d == 3) l3.config.set_to_avgtest_merging();
   return l3.compute_score(ora::line_from10(a), ora::line_from10(b));
 }
+/* The predicate of RemergeLineTracks' pair loop (merging/merging.cc:516, :534 -- above: RemergeLineTracks), batched:
+ * out[k] = check_connection(a[k], b[k]) in that order, the linker of cfg's l3_* fields switched to spatial merging,
+ * each line as start3 end3 uncertainty.  Test infrastructure of the oracle alone: oracle/_ref has no counterpart, so it is
+ * declared here and in oracle/oracle.py, not in lt_oracle.h (whose bytes are part of what the recorded answers of the
+ * reference are keyed by). */
+int ora_linker3d_check_pairs(const ora_config *cfg, int64_t n, const double *line7_a, const double *line7_b,
+                             uint8_t *out) {
+  ora::Linker2d l2;
+  ora::Linker3d l3;
+  ora::set_linkers(*cfg, l2, l3);
+  l3.config.set_to_spatial_merging();
+  auto line = [](const double *p) {
+    return ora::Line3d(ora::V3{p[0], p[1], p[2]}, ora::V3{p[3], p[4], p[5]}, -1.0, -1.0, -1.0, p[6]);
+  };
+#pragma omp parallel for schedule(static)
+  for (int64_t k = 0; k < n; ++k) out[k] = l3.check_connection(line(line7_a + 7 * k), line(line7_b + 7 * k)) ? 1 : 0;
+  return 0;
+}
 int ora_track_labels_greedy(int n_nodes, const int32_t *node_img, int64_t n_edges,
                             const double *edge_sim, const int32_t *edge_nodes2,
                             int32_t *out_labels) {

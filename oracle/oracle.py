@@ -470,6 +470,20 @@ def linker3d_score(cfg_dict, mode3d, line1, line2):
     return float(lib().ora_linker3d_score(C.byref(cfg), int(mode3d), _d(_f64(line1)), _d(_f64(line2))))
 
 
+def linker3d_check_pairs(linker3d_dict, line7_a, line7_b):
+    """LineLinker3d::check_connection(a[k], b[k]) in spatial-merging mode for n pairs of track lines (start, end,
+    uncertainty) in ONE call: the predicate of RemergeLineTracks' pair loop (merging/merging.cc:534), which is what
+    ora_ts_remerge_once evaluates.  -> (n,) bool.  The oracle's own code only (oracle/_ref has no such entry)."""
+    cfg = config_from_dict({"linker3d_config": dict(linker3d_dict)})
+    a, b = _f64(line7_a).reshape(-1, 7), _f64(line7_b).reshape(-1, 7)
+    assert a.shape == b.shape
+    out = np.zeros(max(len(a), 1), np.uint8)
+    fn = lib().ora_linker3d_check_pairs
+    fn.argtypes = [C.POINTER(OraConfig), C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint8)]
+    fn(C.byref(cfg), len(a), _d(a), _d(b), _p(out, C.c_uint8))
+    return out[:len(a)].astype(bool)
+
+
 def track_labels_greedy(node_img, edge_sim, edge_nodes):
     node_img = _i32(node_img); edge_sim = _f64(edge_sim); edge_nodes = _i32(edge_nodes).reshape(-1, 2)
     out = np.zeros(len(node_img), np.int32)
@@ -543,6 +557,12 @@ class OracleTrackSet:
             if n_new == n:
                 break
             n = n_new
+
+    def remerge_once(self, linker3d_dict, num_outliers=2):
+        """one pass of RemergeLineTracks (merging/merging.cc:513-644)"""
+        cfg = config_from_dict({"linker3d_config": dict(linker3d_dict)})
+        if self.num_tracks():
+            self.tri._chk(self.L.ora_ts_remerge_once(self.tri.ctx, self.h, C.byref(cfg), num_outliers))
 
     def get(self):
         T = self.num_tracks(); M = int(self.L.ora_ts_num_members(self.h))
