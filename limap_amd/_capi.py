@@ -362,7 +362,7 @@ def i64(a):
     return np.ascontiguousarray(a, dtype=np.int64)
 
 
-def ptr(a, t):
+def ptr(a, t=C.c_double):
     return a.ctypes.data_as(C.POINTER(t))
 
 
@@ -731,3 +731,17 @@ class Context:
                                                ptr(f64(seg2), C.c_double), ptr(f64(cam2), C.c_double),
                                                int(bool(by_endpoints)), ptr(out, C.c_double)))
         return out
+
+
+def per_device_contexts():
+    """-> ``_context(device=0)``: one Context per device, created on first use and kept by the closure.  Every module
+    around the triangulation core takes its own (its calls then see their own error string, stream and buffers)."""
+    contexts = {}
+
+    def _context(device=0):
+        ctx = contexts.get(device)
+        if ctx is None:
+            ctx = contexts[device] = Context(device=device)
+        return ctx
+
+    return _context

@@ -1,5 +1,6 @@
-// lt_ctx.h -- context of the C ABI, shared by lt_api.cpp (pipeline, tail) and lt_tracks.cpp
-// (post-triangulation filters and remerge).
+// lt_ctx.h -- the context of the C ABI, shared by every host translation unit: the triangulation core's state (scene,
+// buffered job, device tables, results, tail) as flat members of lt_ctx, then one plain struct per module around the
+// core with what its last call left behind (results, timers) and its device buffers.
 #pragma once
 
 #include "../../include/limap_amd.h"
@@ -170,6 +171,72 @@ struct TrackStore {
   }
 };
 
+// ---- the modules' state: results and timers of the module's last call, and its device buffers ----
+// (declared here and not in the modules' headers: those are compiled into kernels)
+
+struct RemergeState {  // lt_ts_remerge_once (lt_tracks.cpp): kept across the passes of a remerge
+  DevBuf d_line, d_act, d_edges, d_cnt;
+  std::vector<unsigned long long> h_edges;
+  std::vector<unsigned long long> h_back;  // count + first edges of a remerge pass (one copy)
+  std::vector<double> h_in;                // host image of a pass's input (lines | active flags)
+};
+
+struct MergeState {  // MergeToLineTracks (lt_merge.cpp): the graph of the last lt_merge_to_tracks
+  std::vector<int> node_img, node_line;  // node -> image id, line id (node order)
+  std::vector<int> e1, e2;               // edges in the reference's insertion order
+  std::vector<double> sim;
+  double timers[4] = {0, 0, 0, 0};       // lt_merge_get_timers
+  DevBuf d_lines, d_blks, d_edges;
+};
+
+struct FitState {  // line fitting (lt_fit.cpp)
+  double timers[4] = {0, 0, 0, 0};  // lt_fit_get_timers
+  DevBuf d_maps, d_imgs, d_in, d_out, d_scr;
+};
+
+struct EvalState {  // line-map evaluation (lt_eval.cpp)
+  double timers[4] = {0, 0, 0, 0};  // lt_eval_get_timers
+  DevBuf d_in, d_lines, d_th, d_out, d_cnt;
+};
+
+struct BptState {  // 2D point-line bipartites (lt_bpt.cpp): the results of the last lt_bpt_associate / lt_bpt_junctions
+  double timers[4] = {0, 0, 0, 0};  // lt_bpt_get_timers
+  std::vector<long long> edge_off;  // per point, CSR of line indices
+  std::vector<int> edge;
+  std::vector<long long> junc_off, jid_off;  // per image the junctions, per junction its line indices
+  std::vector<double> junc_xy;
+  std::vector<int> jid;
+  std::vector<long long> cand_off;  // per image the junction candidates (endpoints, then intersections)
+  std::vector<double> cand_xy;
+  std::vector<int> cand_lines, parents;
+  DevBuf d_raw, d_lines, d_pts, d_off, d_off2, d_off3, d_blk, d_cnt, d_scan, d_out, d_inter, d_cand, d_keys, d_keys2,
+      d_idx, d_idx2, d_tmp, d_misc;
+};
+
+struct MatchState {  // line-descriptor matching (lt_match.cpp): the result of the last lt_match_scene
+  double timers[4] = {0, 0, 0, 0};          // lt_match_get_timers
+  std::vector<long long> row_off, slot_off; // per pair: its rows / its output slots (lines x kept columns)
+  std::vector<int> kk;                      // per pair: columns kept per line
+  std::vector<unsigned short> col;          // per slot: neighbour line (0xffff: dropped by the mutual test)
+  std::vector<float> score;                 // per slot, only with want_scores
+  bool mutual = false;
+  DevBuf d_desc, d_tasks, d_units, d_col, d_score, d_flag;
+};
+
+struct VpState {  // vanishing-point detection (lt_vp.cpp): the result of the last lt_vp_detect
+  double timers[6] = {0, 0, 0, 0, 0, 0};  // lt_vp_get_timers
+  std::vector<int> labels, clusters;      // per line: VPResult::labels, the cluster before the filters
+  std::vector<long long> vp_off;          // per image its vanishing points
+  std::vector<double> vps;
+  DevBuf d_raw, d_flag, d_src, d_lines, d_imgs, d_blk, d_hyp, d_pref, d_state, d_roots;
+};
+
+struct RefineState {  // line refinement (lt_refine.cpp): the result of the last lt_refine_arrays / lt_refine_tracks
+  double timers[4] = {0, 0, 0, 0};  // lt_refine_get_timers
+  std::vector<double> out;          // 15 doubles (one lt::RfOut) per track
+  DevBuf d_k, d_q, d_t, d_cam, d_l2d, d_l3d, d_tab, d_line, d_tracks, d_out;
+};
+
 }  // namespace lt_host
 
 using lt_host::DevBuf;
@@ -235,10 +302,6 @@ struct lt_ctx {
   DevBuf d_keys, d_rows, d_row_blk, d_skeys, d_srows, d_sort_tmp, d_conn_off;
   DevBuf d_st_c, d_st_l, d_flags, d_pos, d_scan_tmp;
   DevBuf d_item_off, d_masks, d_mask_cnt, d_mask_pos;
-  DevBuf d_rm_line, d_rm_act, d_rm_edges, d_rm_cnt;  // lt_ts_remerge_once: kept across the passes of a remerge
-  std::vector<unsigned long long> h_rm_edges;
-  std::vector<unsigned long long> h_rm_back;  // count + first edges of a remerge pass (one copy)
-  std::vector<double> h_rm_in;                // host image of a pass's input (lines | active flags)
   DevBuf d_hcand, d_hlite;  // split host-side view of the candidates (debug read-outs), see materialize_compact
   DevBuf d_cand, d_lite, d_tri_off, d_score, d_best_idx, d_edge_flag, d_nvalid, d_edge_off, d_edges;
   DevBuf d_best_c, d_best_score, d_best_src, d_ntris, d_err;
@@ -389,49 +452,14 @@ struct lt_ctx {
   long long pend_C = 0;
   int pend_ev_gen_end = 3, pend_ev_place_end = 4;
   long long C_last = 0;  // candidates of the last lt_run_device (known on the host once the scoring grid is sized)
-  // ---- MergeToLineTracks (lt_merge.cpp): the graph of the last lt_merge_to_tracks ----
-  std::vector<int> mg_node_img, mg_node_line;  // node -> image id, line id (node order)
-  std::vector<int> mg_e1, mg_e2;               // edges in the reference's insertion order
-  std::vector<double> mg_sim;
-  double mg_timers[4] = {0, 0, 0, 0};          // lt_merge_get_timers
-  DevBuf d_mg_lines, d_mg_blks, d_mg_edges;
-  // ---- line fitting (lt_fit.cpp) ----
-  double ft_timers[4] = {0, 0, 0, 0};  // lt_fit_get_timers
-  DevBuf d_ft_maps, d_ft_imgs, d_ft_in, d_ft_out, d_ft_scr;
-  // ---- line-map evaluation (lt_eval.cpp) ----
-  double ev_timers[4] = {0, 0, 0, 0};  // lt_eval_get_timers
-  DevBuf d_ev_in, d_ev_lines, d_ev_th, d_ev_out, d_ev_cnt;
-  // ---- 2D point-line bipartites (lt_bpt.cpp): the results of the last lt_bpt_associate / lt_bpt_junctions ----
-  double bp_timers[4] = {0, 0, 0, 0};  // lt_bpt_get_timers
-  std::vector<long long> bp_edge_off;  // per point, CSR of line indices
-  std::vector<int> bp_edge;
-  std::vector<long long> bp_junc_off, bp_jid_off;  // per image the junctions, per junction its line indices
-  std::vector<double> bp_junc_xy;
-  std::vector<int> bp_jid;
-  std::vector<long long> bp_cand_off;  // per image the junction candidates (endpoints, then intersections)
-  std::vector<double> bp_cand_xy;
-  std::vector<int> bp_cand_lines, bp_parents;
-  DevBuf d_bp_raw, d_bp_lines, d_bp_pts, d_bp_off, d_bp_off2, d_bp_off3, d_bp_blk, d_bp_cnt, d_bp_scan, d_bp_out,
-      d_bp_inter, d_bp_cand, d_bp_keys, d_bp_keys2, d_bp_idx, d_bp_idx2, d_bp_tmp, d_bp_misc;
-  // ---- line-descriptor matching (lt_match.cpp): the result of the last lt_match_scene ----
-  double mt_timers[4] = {0, 0, 0, 0};             // lt_match_get_timers
-  std::vector<long long> mt_row_off, mt_slot_off; // per pair: its rows / its output slots (lines x kept columns)
-  std::vector<int> mt_kk;                         // per pair: columns kept per line
-  std::vector<unsigned short> mt_col;             // per slot: neighbour line (0xffff: dropped by the mutual test)
-  std::vector<float> mt_score;                    // per slot, only with want_scores
-  bool mt_mutual = false;
-  DevBuf d_mt_desc, d_mt_tasks, d_mt_units, d_mt_col, d_mt_score, d_mt_flag;
-  // ---- vanishing-point detection (lt_vp.cpp): the result of the last lt_vp_detect ----
-  double vp_timers[6] = {0, 0, 0, 0, 0, 0};  // lt_vp_get_timers
-  std::vector<int> vp_labels, vp_clusters;   // per line: VPResult::labels, the cluster before the filters
-  std::vector<long long> vp_vp_off;          // per image its vanishing points
-  std::vector<double> vp_vps;
-  DevBuf d_vp_raw, d_vp_flag, d_vp_src, d_vp_lines, d_vp_imgs, d_vp_blk, d_vp_hyp, d_vp_pref, d_vp_state, d_vp_roots;
-
-  // ---- line refinement (lt_refine.cpp): the result of the last lt_refine_arrays / lt_refine_tracks ----
-  double rf_timers[4] = {0, 0, 0, 0};  // lt_refine_get_timers
-  std::vector<double> rf_out;          // 15 doubles (one lt::RfOut) per track
-  DevBuf d_rf_k, d_rf_q, d_rf_t, d_rf_cam, d_rf_l2d, d_rf_l3d, d_rf_tab, d_rf_line, d_rf_tracks, d_rf_out;
+  lt_host::RemergeState rm;
+  lt_host::MergeState mg;
+  lt_host::FitState ft;
+  lt_host::EvalState evl;
+  lt_host::BptState bp;
+  lt_host::MatchState mt;
+  lt_host::VpState vp;
+  lt_host::RefineState rf;
 };
 
 #define HIPCHK(ctx, call)                                                                  \
@@ -455,9 +483,3 @@ static inline int fail(lt_ctx *ctx, int code, const std::string &msg) {
   ctx->err = msg;
   return code;
 }
-
-namespace lt_impl {
-// lt_refine.cpp: the refinement of tracks given as CSR arrays with the cameras the context holds on the device
-int refine_with_ctx_cams(lt_ctx *ctx, int64_t n_tracks, const double *line6, const int64_t *off, const int32_t *img,
-                         const double *line2d4, const double *line3d6, const lt_refine_config *cfg);
-}  // namespace lt_impl

@@ -15,7 +15,7 @@
 #include <vector>
 
 using namespace lt;
-using lt_impl::now_ms;
+using namespace lt_impl;
 
 struct lt_pcd {
   static constexpr const char *noun = "index";  // of the messages about the handle
@@ -38,12 +38,6 @@ namespace {
 constexpr long long kDefaultChunk = 1ll << 22;
 
 long long chunk_of(int64_t chunk) { return chunk > 0 ? (long long)chunk : kDefaultChunk; }
-
-int check_finite(lt_ctx *ctx, const char *who, const double *v, long long n, const char *what) {
-  for (long long k = 0; k < n; ++k)
-    if (!std::isfinite(v[k])) return fail(ctx, LT_ERR_ARGUMENT, std::string(who) + ": non-finite " + what);
-  return LT_OK;
-}
 
 // Line3d's direction() (Eigen normalized(): unchanged unless the squared norm is > 0) and length() ((start - end).norm())
 std::vector<EvalLine> prep_lines(const double *l6, long long n, int rint_n) {
@@ -72,12 +66,6 @@ std::vector<EvalLine> prep_lines(const double *l6, long long n, int rint_n) {
   return out;
 }
 
-int upload_lines(lt_ctx *ctx, DevBuf &buf, const std::vector<EvalLine> &v) {
-  ENSURE(ctx, buf, sizeof(EvalLine) * v.size());
-  HIPCHK(ctx, hipMemcpyAsync(buf.p, v.data(), sizeof(EvalLine) * v.size(), hipMemcpyHostToDevice, ctx->stream));
-  return LT_OK;
-}
-
 template <class Handle>
 int check_handle(lt_ctx *ctx, const char *who, const Handle *h) {
   if (!h) return fail(ctx, LT_ERR_ARGUMENT, std::string(who) + ": null " + Handle::noun);
@@ -89,33 +77,25 @@ int check_handle(lt_ctx *ctx, const char *who, const Handle *h) {
 
 // LT_TEST_MESH_BRUTE=1: every face for every query (k_mesh_brute), the yardstick of the hierarchy walk
 int mesh_brute() {
-  const char *e = lt_impl::test_switch("LT_TEST_MESH_BRUTE");
+  const char *e = test_switch("LT_TEST_MESH_BRUTE");
   return e && e[0] == '1';
 }
 
 struct Timer {  // HIP events around the kernels of one call
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  Events<2> ev;
   double t0 = now_ms();
   int launches = 0;
-  ~Timer() {
-    for (auto &e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
   int start(lt_ctx *ctx) {
-    for (auto &e : ev) HIPCHK(ctx, hipEventCreate(&e));
-    HIPCHK(ctx, hipEventRecord(ev[0], ctx->stream));
-    return LT_OK;
+    if (int rc = ev.create(ctx)) return rc;
+    return ev.record(ctx, 0);
   }
   int finish(lt_ctx *ctx, double levels) {
-    HIPCHK(ctx, hipEventRecord(ev[1], ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    HIPCHK(ctx, hipGetLastError());
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
-    ctx->ev_timers[0] = ms;
-    ctx->ev_timers[1] = now_ms() - t0;
-    ctx->ev_timers[2] = launches;
-    ctx->ev_timers[3] = levels;
+    if (int rc = ev.record(ctx, 1)) return rc;
+    if (int rc = stream_sync(ctx)) return rc;
+    ctx->evl.timers[0] = ev.ms(0, 1);
+    ctx->evl.timers[1] = now_ms() - t0;
+    ctx->evl.timers[2] = launches;
+    ctx->evl.timers[3] = levels;
     return LT_OK;
   }
 };
@@ -192,17 +172,17 @@ int nearest_dists(lt_ctx *ctx, const char *who, const double *query, int64_t n, 
   Timer tm;
   if (int rc = tm.start(ctx)) return rc;
   const long long C = chunk_of(chunk);
-  ENSURE(ctx, ctx->d_ev_in, 24 * (size_t)std::min<long long>(std::max<long long>(n, 1), C));
-  ENSURE(ctx, ctx->d_ev_out, 8 * (size_t)std::min<long long>(std::max<long long>(n, 1), C));
+  ENSURE(ctx, ctx->evl.d_in, 24 * (size_t)std::min<long long>(std::max<long long>(n, 1), C));
+  ENSURE(ctx, ctx->evl.d_out, 8 * (size_t)std::min<long long>(std::max<long long>(n, 1), C));
   for (long long q0 = 0; q0 < n; q0 += C) {
     const long long m = std::min<long long>(C, n - q0);
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_ev_in.p, query + 3 * q0, 24 * (size_t)m, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->evl.d_in.p, query + 3 * q0, 24 * (size_t)m, hipMemcpyHostToDevice, st));
     EvalQuery Q{};
-    const double *d = ctx->d_ev_in.as<double>();
+    const double *d = ctx->evl.d_in.as<double>();
     Q.x = d; Q.y = d + 1; Q.z = d + 2; Q.stride = 3; Q.mode = EV_Q_POINTS; Q.n = 1;
-    launch(st, Q, m, ctx->d_ev_out.as<double>());
+    launch(st, Q, m, ctx->evl.d_out.as<double>());
     ++tm.launches;
-    HIPCHK(ctx, hipMemcpyAsync(dist + q0, ctx->d_ev_out.p, 8 * (size_t)m, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(dist + q0, ctx->evl.d_out.p, 8 * (size_t)m, hipMemcpyDeviceToHost, st));
   }
   return tm.finish(ctx, 0);
 }
@@ -226,33 +206,33 @@ int line_samples(lt_ctx *ctx, const char *who, const double *lines, int64_t n_li
   Timer tm;
   if (int rc = tm.start(ctx)) return rc;
   const auto L = prep_lines(lines, n_lines, 0);
-  if (int rc = upload_lines(ctx, ctx->d_ev_lines, L)) return rc;
-  ENSURE(ctx, ctx->d_ev_th, 8 * (size_t)std::max(n_th, 1));
-  if (n_th) HIPCHK(ctx, hipMemcpyAsync(ctx->d_ev_th.p, thresholds, 8 * (size_t)n_th, hipMemcpyHostToDevice, st));
+  if (int rc = upload_vec(ctx, ctx->evl.d_lines, L)) return rc;
+  ENSURE(ctx, ctx->evl.d_th, 8 * (size_t)std::max(n_th, 1));
+  if (n_th) HIPCHK(ctx, hipMemcpyAsync(ctx->evl.d_th.p, thresholds, 8 * (size_t)n_th, hipMemcpyHostToDevice, st));
   const long long per = std::max<long long>(1, chunk_of(chunk) / n_samples);  // whole lines per launch
   const long long lc = std::min<long long>(per, n_lines);
-  ENSURE(ctx, ctx->d_ev_out, 8 * (size_t)(lc * n_samples));
-  if (counts) ENSURE(ctx, ctx->d_ev_cnt, 4 * (size_t)(n_lines * n_th));
+  ENSURE(ctx, ctx->evl.d_out, 8 * (size_t)(lc * n_samples));
+  if (counts) ENSURE(ctx, ctx->evl.d_cnt, 4 * (size_t)(n_lines * n_th));
   EvalQuery Q{};
   Q.mode = mode == LT_SAMPLE_CENTER ? EV_Q_CENTER : EV_Q_ENDS;
   Q.n = n_samples;
   Q.interval = mode == LT_SAMPLE_CENTER ? 1.0 / n_samples : 1.0 / (n_samples - 1);
   for (long long l0 = 0; l0 < n_lines; l0 += per) {
     const long long m = std::min<long long>(per, n_lines - l0);
-    Q.lines = ctx->d_ev_lines.as<EvalLine>() + l0;
-    launch(st, Q, m * n_samples, ctx->d_ev_out.as<double>());
+    Q.lines = ctx->evl.d_lines.as<EvalLine>() + l0;
+    launch(st, Q, m * n_samples, ctx->evl.d_out.as<double>());
     ++tm.launches;
     if (counts) {
-      launch_eval_count(st, ctx->d_ev_out.as<double>(), m, n_samples, ctx->d_ev_th.as<double>(), n_th, 1,
-                        ctx->d_ev_cnt.as<int>() + l0 * n_th);
+      launch_eval_count(st, ctx->evl.d_out.as<double>(), m, n_samples, ctx->evl.d_th.as<double>(), n_th, 1,
+                        ctx->evl.d_cnt.as<int>() + l0 * n_th);
       ++tm.launches;
     }
     if (dists)
-      HIPCHK(ctx, hipMemcpyAsync(dists + l0 * n_samples, ctx->d_ev_out.p, 8 * (size_t)(m * n_samples),
+      HIPCHK(ctx, hipMemcpyAsync(dists + l0 * n_samples, ctx->evl.d_out.p, 8 * (size_t)(m * n_samples),
                                  hipMemcpyDeviceToHost, st));
   }
   if (counts)
-    HIPCHK(ctx, hipMemcpyAsync(counts, ctx->d_ev_cnt.p, 4 * (size_t)(n_lines * n_th), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(counts, ctx->evl.d_cnt.p, 4 * (size_t)(n_lines * n_th), hipMemcpyDeviceToHost, st));
   return tm.finish(ctx, 0);
 }
 
@@ -297,10 +277,10 @@ int lt_pcd_build(lt_ctx *ctx, const void *xyz, int64_t n, int dtype, int on_devi
   const size_t in_bytes = (size_t)n * 3 * (dtype ? 8 : 4);
   const void *src = xyz;
   if (!on_device) {
-    if (!ctx->d_ev_in.ensure(in_bytes)) return bail(fail(ctx, LT_ERR_HIP, "hipMalloc failed for the point upload"));
-    if (hipMemcpyAsync(ctx->d_ev_in.p, xyz, in_bytes, hipMemcpyHostToDevice, st) != hipSuccess)
+    if (!ctx->evl.d_in.ensure(in_bytes)) return bail(fail(ctx, LT_ERR_HIP, "hipMalloc failed for the point upload"));
+    if (hipMemcpyAsync(ctx->evl.d_in.p, xyz, in_bytes, hipMemcpyHostToDevice, st) != hipSuccess)
       return bail(fail(ctx, LT_ERR_HIP, "lt_pcd_build: upload failed"));
-    src = ctx->d_ev_in.p;
+    src = ctx->evl.d_in.p;
   }
   EvalTree &T = p->tree;
   T.L = eval_levels(n, kEvalBucket);
@@ -379,19 +359,19 @@ int lt_lines_point_dists(lt_ctx *ctx, const lt_pcd *pcd, const double *lines, in
   Timer tm;
   if (int rc = tm.start(ctx)) return rc;
   const auto L = prep_lines(lines, n_lines, 0);
-  if (int rc = upload_lines(ctx, ctx->d_ev_lines, L)) return rc;
+  if (int rc = upload_vec(ctx, ctx->evl.d_lines, L)) return rc;
   const long long N = pcd->n, C = chunk_of(chunk);
-  ENSURE(ctx, ctx->d_ev_out, 8 * (size_t)N);
+  ENSURE(ctx, ctx->evl.d_out, 8 * (size_t)N);
   for (long long p0 = 0; p0 < N; p0 += C) {  // the cloud in Morton order, written back in the input order
     const long long m = std::min<long long>(C, N - p0);
     EvalQuery Q{};
     Q.x = pcd->x.as<double>() + p0; Q.y = pcd->y.as<double>() + p0; Q.z = pcd->z.as<double>() + p0;
     Q.stride = 1; Q.mode = EV_Q_POINTS; Q.n = 1;
-    launch_eval_lines_min(st, 0, Q, m, ctx->d_ev_lines.as<EvalLine>(), n_lines, ctx->d_ev_out.as<double>(),
+    launch_eval_lines_min(st, 0, Q, m, ctx->evl.d_lines.as<EvalLine>(), n_lines, ctx->evl.d_out.as<double>(),
                           pcd->perm.as<unsigned>() + p0);
     ++tm.launches;
   }
-  HIPCHK(ctx, hipMemcpyAsync(dist, ctx->d_ev_out.p, 8 * (size_t)N, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipMemcpyAsync(dist, ctx->evl.d_out.p, 8 * (size_t)N, hipMemcpyDeviceToHost, st));
   return tm.finish(ctx, 0);
 }
 
@@ -414,26 +394,26 @@ int lt_refline_counts(lt_ctx *ctx, const double *query_lines, int64_t n_query, c
   if (int rc = tm.start(ctx)) return rc;
   const auto QL = prep_lines(query_lines, n_query, n_samples);
   const auto L = prep_lines(lines, n_lines, 0);
-  if (int rc = upload_lines(ctx, ctx->d_ev_in, QL)) return rc;
-  if (int rc = upload_lines(ctx, ctx->d_ev_lines, L)) return rc;
-  ENSURE(ctx, ctx->d_ev_th, 8 * (size_t)n_th);
-  HIPCHK(ctx, hipMemcpyAsync(ctx->d_ev_th.p, thresholds, 8 * (size_t)n_th, hipMemcpyHostToDevice, st));
+  if (int rc = upload_vec(ctx, ctx->evl.d_in, QL)) return rc;
+  if (int rc = upload_vec(ctx, ctx->evl.d_lines, L)) return rc;
+  ENSURE(ctx, ctx->evl.d_th, 8 * (size_t)n_th);
+  HIPCHK(ctx, hipMemcpyAsync(ctx->evl.d_th.p, thresholds, 8 * (size_t)n_th, hipMemcpyHostToDevice, st));
   const long long per = std::max<long long>(1, chunk_of(chunk) / n_samples);
-  ENSURE(ctx, ctx->d_ev_out, 8 * (size_t)(std::min<long long>(per, n_query) * n_samples));
-  ENSURE(ctx, ctx->d_ev_cnt, 4 * (size_t)(n_query * n_th));
+  ENSURE(ctx, ctx->evl.d_out, 8 * (size_t)(std::min<long long>(per, n_query) * n_samples));
+  ENSURE(ctx, ctx->evl.d_cnt, 4 * (size_t)(n_query * n_th));
   EvalQuery Q{};
   Q.mode = EV_Q_REFLINE;
   Q.n = n_samples;
   for (long long r0 = 0; r0 < n_query; r0 += per) {
     const long long m = std::min<long long>(per, n_query - r0);
-    Q.lines = ctx->d_ev_in.as<EvalLine>() + r0;
-    launch_eval_lines_min(st, 1, Q, m * n_samples, ctx->d_ev_lines.as<EvalLine>(), n_lines,
-                          ctx->d_ev_out.as<double>(), nullptr);
-    launch_eval_count(st, ctx->d_ev_out.as<double>(), m, n_samples, ctx->d_ev_th.as<double>(), n_th, 0,
-                      ctx->d_ev_cnt.as<int>() + r0 * n_th);
+    Q.lines = ctx->evl.d_in.as<EvalLine>() + r0;
+    launch_eval_lines_min(st, 1, Q, m * n_samples, ctx->evl.d_lines.as<EvalLine>(), n_lines,
+                          ctx->evl.d_out.as<double>(), nullptr);
+    launch_eval_count(st, ctx->evl.d_out.as<double>(), m, n_samples, ctx->evl.d_th.as<double>(), n_th, 0,
+                      ctx->evl.d_cnt.as<int>() + r0 * n_th);
     tm.launches += 2;
   }
-  HIPCHK(ctx, hipMemcpyAsync(counts, ctx->d_ev_cnt.p, 4 * (size_t)(n_query * n_th), hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipMemcpyAsync(counts, ctx->evl.d_cnt.p, 4 * (size_t)(n_query * n_th), hipMemcpyDeviceToHost, st));
   return tm.finish(ctx, 0);
 }
 
@@ -467,7 +447,7 @@ int lt_mesh_build(lt_ctx *ctx, const void *V, int64_t nv, int dtype, int on_devi
     if (!std::isfinite(Vs[(size_t)k])) return fail(ctx, LT_ERR_ARGUMENT, std::string(who) + ": non-finite vertex coordinate");
   }
   int bucket = kMeshBucket;
-  if (const char *e = lt_impl::test_switch("LT_TEST_MESH_BUCKET")) {  // bucket sizes for the measurement
+  if (const char *e = test_switch("LT_TEST_MESH_BUCKET")) {  // bucket sizes for the measurement
     bucket = atoi(e);
     if (bucket < 1 || bucket > kMeshMaxBucket) return fail(ctx, LT_ERR_ARGUMENT, "LT_TEST_MESH_BUCKET: 1 .. 64");
   }
@@ -545,7 +525,7 @@ int lt_mesh_line_samples(lt_ctx *ctx, const lt_mesh *mesh, const double *lines, 
 
 int lt_eval_get_timers(lt_ctx *ctx, double out[4]) {
   if (!ctx || !out) return LT_ERR_ARGUMENT;
-  for (int k = 0; k < 4; ++k) out[k] = ctx->ev_timers[k];
+  for (int k = 0; k < 4; ++k) out[k] = ctx->evl.timers[k];
   return LT_OK;
 }
 

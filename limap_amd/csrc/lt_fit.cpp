@@ -13,8 +13,7 @@
 #include <vector>
 
 using namespace lt;
-using lt_impl::now_ms;
-using lt_impl::test_switch;
+using namespace lt_impl;
 
 namespace {
 
@@ -65,26 +64,17 @@ struct OutLayout {
   }
 };
 
-// the launch, run again with the counted scratch size when a long problem found no room; results do not depend on it
+// the launch over a counted scratch of points (32 B each, behind a 256-B header), run again with the counted size when a
+// long problem found no room; results do not depend on it
 template <class Launch>
-int run_with_scratch(lt_ctx *ctx, hipStream_t st, Launch launch, int *attempts) {
-  // points (32 B each): what the buffer already holds, at least 2^18; LT_TEST_FIT_SCRATCH_CAP forces a small first try
-  unsigned long long cap = ctx->d_ft_scr.cap > 256 ? (ctx->d_ft_scr.cap - 256) / 32 : 0;
+int run_with_scratch(lt_ctx *ctx, Launch launch, int *attempts) {
+  // first try: what the buffer already holds, at least 2^18; LT_TEST_FIT_SCRATCH_CAP forces a small one
+  unsigned long long cap = ctx->ft.d_scr.cap > 256 ? (ctx->ft.d_scr.cap - 256) / 32 : 0, used = 0;
   if (cap < (1ull << 18)) cap = 1ull << 18;
   if (const char *e = test_switch("LT_TEST_FIT_SCRATCH_CAP")) cap = std::max(1ull, std::strtoull(e, nullptr, 10));
-  for (*attempts = 1;; ++*attempts) {
-    ENSURE(ctx, ctx->d_ft_scr, 256 + 32 * (size_t)cap);
-    unsigned long long *d_cnt = ctx->d_ft_scr.as<unsigned long long>();
-    double *scr = reinterpret_cast<double *>(ctx->d_ft_scr.as<char>() + 256);
-    HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, 8, st));
-    launch(scr, cap, d_cnt);
-    HIPCHK(ctx, hipGetLastError());
-    unsigned long long used = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&used, d_cnt, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    if (used <= cap) return LT_OK;
-    cap = used;
-  }
+  return run_counted(ctx, ctx->ft.d_scr, 256, 32, cap, [&](void *scr, unsigned long long room, unsigned long long *cnt) {
+    return launch(static_cast<double *>(scr), room, cnt);
+  }, &used, attempts);
 }
 
 // segs.astype(int) / linspace stay exact for coordinates below 2^29 (the reference would enumerate every pixel)
@@ -101,12 +91,12 @@ int upload_maps(lt_ctx *ctx, hipStream_t st, int n_maps, Bytes bytes_of, Ptr ptr
   size_t total = 0;
   for (int k = 0; k < n_maps; ++k) total += (bytes_of(k) + 255) & ~(size_t)255;
   if (!total) return LT_OK;
-  ENSURE(ctx, ctx->d_ft_maps, total);
+  ENSURE(ctx, ctx->ft.d_maps, total);
   size_t at = 0;
   for (int k = 0; k < n_maps; ++k) {
     const size_t b = bytes_of(k);
     if (!b) continue;
-    char *dst = ctx->d_ft_maps.as<char>() + at;
+    char *dst = ctx->ft.d_maps.as<char>() + at;
     HIPCHK(ctx, hipMemcpyAsync(dst, ptr_of(k), b, hipMemcpyHostToDevice, st));
     set_dev(k, dst);
     at += (b + 255) & ~(size_t)255;
@@ -116,21 +106,17 @@ int upload_maps(lt_ctx *ctx, hipStream_t st, int n_maps, Bytes bytes_of, Ptr ptr
 
 // the outputs of G segments to the host, then the timers (ev: start, maps uploaded, kernel start, kernel end)
 int finish_segs(lt_ctx *ctx, hipStream_t st, const char *out, const OutLayout &L, long long G, double *seg3d,
-                int32_t *status, int32_t *stats, hipEvent_t ev[4], double t_start, int attempts) {
+                int32_t *status, int32_t *stats, const Events<4> &ev, double t_start, int attempts) {
   if (G) {
     HIPCHK(ctx, hipMemcpyAsync(seg3d, out + L.seg, 48 * (size_t)G, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipMemcpyAsync(status, out + L.status, 4 * (size_t)G, hipMemcpyDeviceToHost, st));
     if (stats) HIPCHK(ctx, hipMemcpyAsync(stats, out + L.stats, 20 * (size_t)G, hipMemcpyDeviceToHost, st));
   }
   HIPCHK(ctx, hipStreamSynchronize(st));
-  float up_ms = 0.f, k_ms = 0.f;
-  (void)hipEventElapsedTime(&up_ms, ev[0], ev[1]);
-  (void)hipEventElapsedTime(&k_ms, ev[2], ev[3]);
-  for (int k = 0; k < 4; ++k) (void)hipEventDestroy(ev[k]);
-  ctx->ft_timers[0] = k_ms;
-  ctx->ft_timers[1] = up_ms;
-  ctx->ft_timers[2] = now_ms() - t_start;
-  ctx->ft_timers[3] = attempts;
+  ctx->ft.timers[0] = ev.ms(2, 3);
+  ctx->ft.timers[1] = ev.ms(0, 1);
+  ctx->ft.timers[2] = now_ms() - t_start;
+  ctx->ft.timers[3] = attempts;
   return LT_OK;
 }
 
@@ -189,31 +175,31 @@ int lt_fit_segs(lt_ctx *ctx, int img_begin, int n_maps, const lt_depth_map *maps
   if (int rc = check_segs(ctx, "lt_fit_segs", segs, G)) return rc;
   hipStream_t st = ctx->stream;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // start, maps uploaded, kernel start, kernel end
-  for (auto &e : ev) HIPCHK(ctx, hipEventCreate(&e));
-  HIPCHK(ctx, hipEventRecord(ev[0], st));
+  Events<4> ev;  // start, maps uploaded, kernel start, kernel end
+  if (int rc = ev.create(ctx)) return rc;
+  if (int rc = ev.record(ctx, 0)) return rc;
   if (int rc = upload_maps(ctx, st, n_maps, [&](int k) -> size_t {
         const lt_depth_map &m = maps[k];
         if (m.on_device || m.h == 0 || m.w == 0) return 0;
         return ((size_t)(m.h - 1) * (size_t)m.row_stride + (size_t)m.w) * (m.dtype ? 8 : 4);
       }, [&](int k) { return maps[k].ptr; }, [&](int k, char *p) { imgs[(size_t)k].map = p; }))
     return rc;
-  HIPCHK(ctx, hipEventRecord(ev[1], st));
+  if (int rc = ev.record(ctx, 1)) return rc;
   const OutLayout L(G, 0);
-  ENSURE(ctx, ctx->d_ft_imgs, sizeof(FitImg) * (size_t)std::max(n_maps, 1));
-  ENSURE(ctx, ctx->d_ft_in, 32 * (size_t)std::max<long long>(G, 1));
-  ENSURE(ctx, ctx->d_ft_out, L.bytes);
-  if (n_maps) HIPCHK(ctx, hipMemcpyAsync(ctx->d_ft_imgs.p, imgs.data(), sizeof(FitImg) * (size_t)n_maps, hipMemcpyHostToDevice, st));
-  if (G) HIPCHK(ctx, hipMemcpyAsync(ctx->d_ft_in.p, segs, 32 * (size_t)G, hipMemcpyHostToDevice, st));
+  ENSURE(ctx, ctx->ft.d_imgs, sizeof(FitImg) * (size_t)std::max(n_maps, 1));
+  ENSURE(ctx, ctx->ft.d_in, 32 * (size_t)std::max<long long>(G, 1));
+  ENSURE(ctx, ctx->ft.d_out, L.bytes);
+  if (n_maps) HIPCHK(ctx, hipMemcpyAsync(ctx->ft.d_imgs.p, imgs.data(), sizeof(FitImg) * (size_t)n_maps, hipMemcpyHostToDevice, st));
+  if (G) HIPCHK(ctx, hipMemcpyAsync(ctx->ft.d_in.p, segs, 32 * (size_t)G, hipMemcpyHostToDevice, st));
   const FitCfg fc = dev_cfg(*cfg);
-  char *out = ctx->d_ft_out.as<char>();
+  char *out = ctx->ft.d_out.as<char>();
   int attempts = 0;
-  if (int rc = run_with_scratch(ctx, st, [&](double *scr, unsigned long long cap, unsigned long long *cnt) {
-        (void)hipEventRecord(ev[2], st);
-        launch_fit_depth(st, G, n_maps, ctx->d_ft_imgs.as<FitImg>(), ctx->d_ft_in.as<double>(), ctx->d_cams.as<Cam>(),
+  if (int rc = run_with_scratch(ctx, [&](double *scr, unsigned long long cap, unsigned long long *cnt) {
+        if (int rc = ev.record(ctx, 2)) return rc;
+        launch_fit_depth(st, G, n_maps, ctx->ft.d_imgs.as<FitImg>(), ctx->ft.d_in.as<double>(), ctx->d_cams.as<Cam>(),
                          fc, scr, cap, cnt, reinterpret_cast<double *>(out + L.seg),
                          reinterpret_cast<int *>(out + L.status), reinterpret_cast<int *>(out + L.stats));
-        (void)hipEventRecord(ev[3], st);
+        return ev.record(ctx, 3);
       }, &attempts))
     return rc;
   return finish_segs(ctx, st, out, L, G, seg3d, status, stats, ev, t_start, attempts);
@@ -267,28 +253,28 @@ int lt_fit_scans(lt_ctx *ctx, int img_begin, int n_maps, const lt_scan_map *maps
   if (int rc = check_segs(ctx, "lt_fit_scans", segs, G)) return rc;
   hipStream_t st = ctx->stream;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  for (auto &e : ev) HIPCHK(ctx, hipEventCreate(&e));
-  HIPCHK(ctx, hipEventRecord(ev[0], st));
+  Events<4> ev;
+  if (int rc = ev.create(ctx)) return rc;
+  if (int rc = ev.record(ctx, 0)) return rc;
   if (int rc = upload_maps(ctx, st, n_maps, [&](int k) { return host_bytes[(size_t)k]; },
                            [&](int k) { return maps[k].ptr; }, [&](int k, char *p) { imgs[(size_t)k].map = p; }))
     return rc;
-  HIPCHK(ctx, hipEventRecord(ev[1], st));
+  if (int rc = ev.record(ctx, 1)) return rc;
   const OutLayout L(G, 0);
-  ENSURE(ctx, ctx->d_ft_imgs, sizeof(ScanImg) * (size_t)std::max(n_maps, 1));
-  ENSURE(ctx, ctx->d_ft_in, 32 * (size_t)std::max<long long>(G, 1));
-  ENSURE(ctx, ctx->d_ft_out, L.bytes);
-  if (n_maps) HIPCHK(ctx, hipMemcpyAsync(ctx->d_ft_imgs.p, imgs.data(), sizeof(ScanImg) * (size_t)n_maps, hipMemcpyHostToDevice, st));
-  if (G) HIPCHK(ctx, hipMemcpyAsync(ctx->d_ft_in.p, segs, 32 * (size_t)G, hipMemcpyHostToDevice, st));
+  ENSURE(ctx, ctx->ft.d_imgs, sizeof(ScanImg) * (size_t)std::max(n_maps, 1));
+  ENSURE(ctx, ctx->ft.d_in, 32 * (size_t)std::max<long long>(G, 1));
+  ENSURE(ctx, ctx->ft.d_out, L.bytes);
+  if (n_maps) HIPCHK(ctx, hipMemcpyAsync(ctx->ft.d_imgs.p, imgs.data(), sizeof(ScanImg) * (size_t)n_maps, hipMemcpyHostToDevice, st));
+  if (G) HIPCHK(ctx, hipMemcpyAsync(ctx->ft.d_in.p, segs, 32 * (size_t)G, hipMemcpyHostToDevice, st));
   const FitCfg fc = dev_cfg(*cfg);
-  char *out = ctx->d_ft_out.as<char>();
+  char *out = ctx->ft.d_out.as<char>();
   int attempts = 0;
-  if (int rc = run_with_scratch(ctx, st, [&](double *scr, unsigned long long cap, unsigned long long *cnt) {
-        (void)hipEventRecord(ev[2], st);
-        launch_fit_scan(st, G, n_maps, ctx->d_ft_imgs.as<ScanImg>(), ctx->d_ft_in.as<double>(), ctx->d_cams.as<Cam>(),
+  if (int rc = run_with_scratch(ctx, [&](double *scr, unsigned long long cap, unsigned long long *cnt) {
+        if (int rc = ev.record(ctx, 2)) return rc;
+        launch_fit_scan(st, G, n_maps, ctx->ft.d_imgs.as<ScanImg>(), ctx->ft.d_in.as<double>(), ctx->d_cams.as<Cam>(),
                         fc, scr, cap, cnt, reinterpret_cast<double *>(out + L.seg),
                         reinterpret_cast<int *>(out + L.status), reinterpret_cast<int *>(out + L.stats));
-        (void)hipEventRecord(ev[3], st);
+        return ev.record(ctx, 3);
       }, &attempts))
     return rc;
   return finish_segs(ctx, st, out, L, G, seg3d, status, stats, ev, t_start, attempts);
@@ -309,24 +295,24 @@ int lt_fit_points(lt_ctx *ctx, int64_t n_sets, const int64_t *off, const double 
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const OutLayout L(n_sets, inlier_mask ? N : 0);
   const size_t off_bytes = ((size_t)(n_sets + 1) * 8 + 255) & ~(size_t)255;
-  ENSURE(ctx, ctx->d_ft_in, off_bytes + 24 * (size_t)std::max<int64_t>(N, 1));
-  ENSURE(ctx, ctx->d_ft_out, L.bytes);
-  char *in = ctx->d_ft_in.as<char>(), *out = ctx->d_ft_out.as<char>();
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  for (auto &e : ev) HIPCHK(ctx, hipEventCreate(&e));
+  ENSURE(ctx, ctx->ft.d_in, off_bytes + 24 * (size_t)std::max<int64_t>(N, 1));
+  ENSURE(ctx, ctx->ft.d_out, L.bytes);
+  char *in = ctx->ft.d_in.as<char>(), *out = ctx->ft.d_out.as<char>();
+  Events<2> ev;
+  if (int rc = ev.create(ctx)) return rc;
   HIPCHK(ctx, hipMemcpyAsync(in, off, (size_t)(n_sets + 1) * 8, hipMemcpyHostToDevice, st));
   if (N) HIPCHK(ctx, hipMemcpyAsync(in + off_bytes, xyz, 24 * (size_t)N, hipMemcpyHostToDevice, st));
   if (inlier_mask && N) HIPCHK(ctx, hipMemsetAsync(out + L.mask, 0, (size_t)N, st));
   const FitCfg fc = dev_cfg(*cfg);
   int attempts = 0;
-  if (int rc = run_with_scratch(ctx, st, [&](double *scr, unsigned long long cap, unsigned long long *cnt) {
-        (void)hipEventRecord(ev[0], st);
+  if (int rc = run_with_scratch(ctx, [&](double *scr, unsigned long long cap, unsigned long long *cnt) {
+        if (int rc = ev.record(ctx, 0)) return rc;
         launch_fit_points(st, n_sets, reinterpret_cast<const long long *>(in),
                           reinterpret_cast<const double *>(in + off_bytes), fc, scr, cap, cnt,
                           reinterpret_cast<double *>(out + L.seg), reinterpret_cast<int *>(out + L.status),
                           reinterpret_cast<int *>(out + L.stats),
                           inlier_mask ? reinterpret_cast<unsigned char *>(out + L.mask) : nullptr);
-        (void)hipEventRecord(ev[1], st);
+        return ev.record(ctx, 1);
       }, &attempts))
     return rc;
   if (n_sets) {
@@ -336,18 +322,15 @@ int lt_fit_points(lt_ctx *ctx, int64_t n_sets, const int64_t *off, const double 
   }
   if (inlier_mask && N) HIPCHK(ctx, hipMemcpyAsync(inlier_mask, out + L.mask, (size_t)N, hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
-  float k_ms = 0.f;
-  (void)hipEventElapsedTime(&k_ms, ev[0], ev[1]);
-  for (auto &e : ev) (void)hipEventDestroy(e);
-  ctx->ft_timers[0] = k_ms;
-  ctx->ft_timers[1] = 0.0;
-  ctx->ft_timers[2] = now_ms() - t_start;
-  ctx->ft_timers[3] = attempts;
+  ctx->ft.timers[0] = ev.ms(0, 1);
+  ctx->ft.timers[1] = 0.0;
+  ctx->ft.timers[2] = now_ms() - t_start;
+  ctx->ft.timers[3] = attempts;
   return LT_OK;
 }
 
 int lt_fit_get_timers(lt_ctx *ctx, double out[4]) {
-  for (int k = 0; k < 4; ++k) out[k] = ctx->ft_timers[k];
+  for (int k = 0; k < 4; ++k) out[k] = ctx->ft.timers[k];
   return LT_OK;
 }
 

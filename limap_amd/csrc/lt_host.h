@@ -1,8 +1,10 @@
-// lt_host.h -- declarations shared by the host-side translation units of the C ABI (lt_api*.cpp): launch wrappers of
-// lt_kernels_v2.hip, tracing ranges, configuration records, and the helpers one unit defines and another uses.
+// lt_host.h -- declarations shared by the host-side translation units of the C ABI: launch wrappers of
+// lt_kernels_v2.hip, tracing ranges, configuration records, the helpers one unit defines and another uses, and the
+// modules' toolkit (lt_hostutil.h).
 #pragma once
 
 #include "lt_ctx.h"
+#include "lt_hostutil.h"
 #include "lt_tail.h"
 #include "lt_rows.h"
 #include "lt_pool.h"
@@ -119,14 +121,9 @@ int upload_points(lt_ctx *ctx);
 int finish_run(lt_ctx *ctx);  // completes a run lt_run_device_async left in flight
 void define_best_of_other_images(lt_ctx *ctx);
 int materialize_compact(lt_ctx *ctx);
-
-template <class T>
-int upload_vec(lt_ctx *ctx, DevBuf &buf, const std::vector<T> &v) {
-  ENSURE(ctx, buf, sizeof(T) * std::max<size_t>(v.size(), 1));
-  if (!v.empty())
-    HIPCHK(ctx, hipMemcpyAsync(buf.p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, ctx->stream));
-  return LT_OK;
-}
+// lt_refine.cpp: the refinement of tracks given as CSR arrays with the cameras the context holds on the device
+int refine_with_ctx_cams(lt_ctx *ctx, int64_t n_tracks, const double *line6, const int64_t *off, const int32_t *img,
+                         const double *line2d4, const double *line3d6, const lt_refine_config *cfg);
 }  // namespace lt_impl
 
 #define LT_FINISH(ctx)                       \

@@ -12,8 +12,7 @@
 #include <vector>
 
 using namespace lt;
-using lt_impl::now_ms;
-using lt_impl::upload_vec;
+using namespace lt_impl;
 
 namespace {
 
@@ -40,12 +39,6 @@ bool values_ok(const float *v, long long n) {
   return !bad;
 }
 
-int sync(lt_ctx *ctx) {
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  HIPCHK(ctx, hipGetLastError());
-  return LT_OK;
-}
-
 // score(i, j): the fmaf chain in ascending k from +0.0f
 inline float dot_chain(const float *a, const float *b, int dim) {
   float acc = 0.0f;
@@ -64,11 +57,11 @@ int lt_match_scene(lt_ctx *ctx, int n_img, const int64_t *desc_off, const float 
   std::string msg;
   if (check_config(cfg, dim, msg)) return fail(ctx, LT_ERR_ARGUMENT, who + msg);
   if (n_img < 0 || !desc_off || !pair_off) return fail(ctx, LT_ERR_ARGUMENT, who + "bad image count or null offsets");
-  if (desc_off[0] != 0 || pair_off[0] != 0) return fail(ctx, LT_ERR_ARGUMENT, who + "offsets must start at 0");
+  if (int rc = check_offsets(ctx, "lt_match_scene", "descriptor", n_img, desc_off)) return rc;
+  if (int rc = check_offsets(ctx, "lt_match_scene", "pair", n_img, pair_off)) return rc;
   const int rpl = cfg->kind == LT_MATCH_ENDPOINTS ? 2 : 1;  // descriptor rows per line
   for (int m = 0; m < n_img; ++m) {
     const int64_t n = desc_off[m + 1] - desc_off[m];
-    if (n < 0 || pair_off[m + 1] < pair_off[m]) return fail(ctx, LT_ERR_ARGUMENT, who + "offsets decrease");
     if (n % rpl) return fail(ctx, LT_ERR_ARGUMENT, who + "an image has an odd number of endpoints");
     if (n / rpl > kMatchMaxLines) return fail(ctx, LT_ERR_ARGUMENT, who + "more than 65535 lines in an image");
   }
@@ -86,7 +79,7 @@ int lt_match_scene(lt_ctx *ctx, int n_img, const int64_t *desc_off, const float 
   const bool mutual = cfg->topk == 0;
   const int topk = mutual ? 1 : cfg->topk;
   std::vector<MatchTask> tasks((size_t)n_pairs * (mutual ? 2 : 1));
-  std::vector<long long> &row_off = ctx->mt_row_off;
+  std::vector<long long> &row_off = ctx->mt.row_off;
   row_off.assign((size_t)n_pairs + 1, 0);
   long long slots = 0;
   int kcap = 0;
@@ -129,81 +122,81 @@ int lt_match_scene(lt_ctx *ctx, int n_img, const int64_t *desc_off, const float 
   hipStream_t st = ctx->stream;
   const float *d_desc = desc;
   if (!on_dev) {
-    ENSURE(ctx, ctx->d_mt_desc, sizeof(float) * (size_t)std::max<long long>(n_desc * dim, 1));
+    ENSURE(ctx, ctx->mt.d_desc, sizeof(float) * (size_t)std::max<long long>(n_desc * dim, 1));
     if (n_desc)
-      HIPCHK(ctx, hipMemcpyAsync(ctx->d_mt_desc.p, desc, sizeof(float) * (size_t)(n_desc * dim), hipMemcpyHostToDevice, st));
-    d_desc = ctx->d_mt_desc.as<float>();
+      HIPCHK(ctx, hipMemcpyAsync(ctx->mt.d_desc.p, desc, sizeof(float) * (size_t)(n_desc * dim), hipMemcpyHostToDevice, st));
+    d_desc = ctx->mt.d_desc.as<float>();
   }
-  if (int rc = upload_vec(ctx, ctx->d_mt_tasks, tasks)) return rc;
-  if (int rc = upload_vec(ctx, ctx->d_mt_units, units)) return rc;
-  ENSURE(ctx, ctx->d_mt_col, 2 * (size_t)std::max<long long>(slots, 1) + 16);
-  ENSURE(ctx, ctx->d_mt_score, 4 * (size_t)std::max<long long>(slots, 1));
+  if (int rc = upload_vec(ctx, ctx->mt.d_tasks, tasks)) return rc;
+  if (int rc = upload_vec(ctx, ctx->mt.d_units, units)) return rc;
+  ENSURE(ctx, ctx->mt.d_col, 2 * (size_t)std::max<long long>(slots, 1) + 16);
+  ENSURE(ctx, ctx->mt.d_score, 4 * (size_t)std::max<long long>(slots, 1));
   if (on_dev && n_desc) {  // the same rejection as on the host, by a kernel of its own, before the matching launches
-    ENSURE(ctx, ctx->d_mt_flag, 16);
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_mt_flag.p, 0, 4, st));
-    launch_match_check(st, d_desc, n_desc * dim, ctx->d_mt_flag.as<int>());
+    ENSURE(ctx, ctx->mt.d_flag, 16);
+    HIPCHK(ctx, hipMemsetAsync(ctx->mt.d_flag.p, 0, 4, st));
+    launch_match_check(st, d_desc, n_desc * dim, ctx->mt.d_flag.as<int>());
     int flag = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&flag, ctx->d_mt_flag.p, 4, hipMemcpyDeviceToHost, st));
-    if (int rc = sync(ctx)) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(&flag, ctx->mt.d_flag.p, 4, hipMemcpyDeviceToHost, st));
+    if (int rc = stream_sync(ctx)) return rc;
     if (flag) return fail(ctx, LT_ERR_ARGUMENT, who + "a descriptor value is not finite or above 2^57 in magnitude");
   }
-  if (int rc = sync(ctx)) return rc;
+  if (int rc = stream_sync(ctx)) return rc;
   double t1 = now_ms();
-  ctx->mt_timers[0] = t1 - t0;
+  ctx->mt.timers[0] = t1 - t0;
 
   // ---- kernels ----
-  launch_match_topk(st, cfg->kind, dim, kcap, waves, ctx->d_mt_tasks.as<MatchTask>(), ctx->d_mt_units.as<MatchUnit>(),
-                    (int)units.size(), d_desc, ctx->d_mt_col.as<unsigned short>(), ctx->d_mt_score.as<float>());
+  launch_match_topk(st, cfg->kind, dim, kcap, waves, ctx->mt.d_tasks.as<MatchTask>(), ctx->mt.d_units.as<MatchUnit>(),
+                    (int)units.size(), d_desc, ctx->mt.d_col.as<unsigned short>(), ctx->mt.d_score.as<float>());
   if (mutual)
-    launch_match_mutual(st, ctx->d_mt_tasks.as<MatchTask>(), (int)n_pairs, rpl, ctx->d_mt_col.as<unsigned short>());
-  if (int rc = sync(ctx)) return rc;
+    launch_match_mutual(st, ctx->mt.d_tasks.as<MatchTask>(), (int)n_pairs, rpl, ctx->mt.d_col.as<unsigned short>());
+  if (int rc = stream_sync(ctx)) return rc;
   double t2 = now_ms();
-  ctx->mt_timers[1] = t2 - t1;
+  ctx->mt.timers[1] = t2 - t1;
 
   // ---- download: 2 bytes per row, the scores only when asked for ----
-  ctx->mt_col.resize((size_t)fwd_slots);
-  ctx->mt_score.clear();
+  ctx->mt.col.resize((size_t)fwd_slots);
+  ctx->mt.score.clear();
   if (fwd_slots)
-    HIPCHK(ctx, hipMemcpyAsync(ctx->mt_col.data(), ctx->d_mt_col.p, 2 * (size_t)fwd_slots, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->mt.col.data(), ctx->mt.d_col.p, 2 * (size_t)fwd_slots, hipMemcpyDeviceToHost, st));
   if (cfg->want_scores && fwd_slots) {
-    ctx->mt_score.resize((size_t)fwd_slots);
-    HIPCHK(ctx, hipMemcpyAsync(ctx->mt_score.data(), ctx->d_mt_score.p, 4 * (size_t)fwd_slots, hipMemcpyDeviceToHost, st));
+    ctx->mt.score.resize((size_t)fwd_slots);
+    HIPCHK(ctx, hipMemcpyAsync(ctx->mt.score.data(), ctx->mt.d_score.p, 4 * (size_t)fwd_slots, hipMemcpyDeviceToHost, st));
   }
-  if (int rc = sync(ctx)) return rc;
+  if (int rc = stream_sync(ctx)) return rc;
   double t3 = now_ms();
-  ctx->mt_timers[2] = t3 - t2;
+  ctx->mt.timers[2] = t3 - t2;
 
   // ---- rows: (line, neighbour line) per slot; mutual keeps the slots that survived ----
-  ctx->mt_kk.resize((size_t)n_pairs);
-  for (long long p = 0; p < n_pairs; ++p) ctx->mt_kk[(size_t)p] = tasks[(size_t)p].kk;
-  ctx->mt_slot_off.assign(row_off.begin(), row_off.end());
+  ctx->mt.kk.resize((size_t)n_pairs);
+  for (long long p = 0; p < n_pairs; ++p) ctx->mt.kk[(size_t)p] = tasks[(size_t)p].kk;
+  ctx->mt.slot_off.assign(row_off.begin(), row_off.end());
   if (mutual) {
     for (long long p = 0; p < n_pairs; ++p) {
       long long n = 0;
-      for (long long s = ctx->mt_slot_off[(size_t)p]; s < ctx->mt_slot_off[(size_t)p + 1]; ++s)
-        n += ctx->mt_col[(size_t)s] != 0xffff;
+      for (long long s = ctx->mt.slot_off[(size_t)p]; s < ctx->mt.slot_off[(size_t)p + 1]; ++s)
+        n += ctx->mt.col[(size_t)s] != 0xffff;
       row_off[(size_t)p + 1] = row_off[(size_t)p] + n;
     }
   }
-  ctx->mt_mutual = mutual;
-  ctx->mt_timers[3] = now_ms() - t3;
+  ctx->mt.mutual = mutual;
+  ctx->mt.timers[3] = now_ms() - t3;
   if (n_rows) *n_rows = (int64_t)row_off.back();
   return LT_OK;
 }
 
 int lt_match_get(lt_ctx *ctx, int64_t *row_off, int32_t *rows2) {
   if (!ctx) return LT_ERR_ARGUMENT;
-  const std::vector<long long> &off = ctx->mt_row_off, &soff = ctx->mt_slot_off;
+  const std::vector<long long> &off = ctx->mt.row_off, &soff = ctx->mt.slot_off;
   if (row_off) std::copy(off.begin(), off.end(), row_off);
   if (!rows2 || off.empty()) return LT_OK;
   const long long n_pairs = (long long)off.size() - 1;
 #pragma omp parallel for schedule(dynamic, 8)
   for (long long p = 0; p < n_pairs; ++p) {
-    const int kk = ctx->mt_kk[(size_t)p];
+    const int kk = ctx->mt.kk[(size_t)p];
     int32_t *out = rows2 + 2 * off[(size_t)p];
     for (long long s = soff[(size_t)p]; s < soff[(size_t)p + 1]; ++s) {
-      const unsigned short c = ctx->mt_col[(size_t)s];
-      if (ctx->mt_mutual && c == 0xffff) continue;
+      const unsigned short c = ctx->mt.col[(size_t)s];
+      if (ctx->mt.mutual && c == 0xffff) continue;
       *out++ = (int32_t)((s - soff[(size_t)p]) / kk);
       *out++ = (int32_t)c;
     }
@@ -214,17 +207,17 @@ int lt_match_get(lt_ctx *ctx, int64_t *row_off, int32_t *rows2) {
 int lt_match_get_scores(lt_ctx *ctx, float *scores) {
   if (!ctx) return LT_ERR_ARGUMENT;
   if (!scores) return LT_OK;
-  const long long slots = ctx->mt_slot_off.empty() ? 0 : ctx->mt_slot_off.back();
-  if ((long long)ctx->mt_score.size() != slots)
+  const long long slots = ctx->mt.slot_off.empty() ? 0 : ctx->mt.slot_off.back();
+  if ((long long)ctx->mt.score.size() != slots)
     return fail(ctx, LT_ERR_STATE, "lt_match_get_scores: the last lt_match_scene did not ask for scores (want_scores)");
   for (long long s = 0; s < slots; ++s)
-    if (!(ctx->mt_mutual && ctx->mt_col[(size_t)s] == 0xffff)) *scores++ = ctx->mt_score[(size_t)s];
+    if (!(ctx->mt.mutual && ctx->mt.col[(size_t)s] == 0xffff)) *scores++ = ctx->mt.score[(size_t)s];
   return LT_OK;
 }
 
 int lt_match_get_timers(lt_ctx *ctx, double out[4]) {
   if (!ctx || !out) return LT_ERR_ARGUMENT;
-  for (int k = 0; k < 4; ++k) out[k] = ctx->mt_timers[k];
+  for (int k = 0; k < 4; ++k) out[k] = ctx->mt.timers[k];
   return LT_OK;
 }
 

@@ -57,7 +57,7 @@ int lt_merge_to_tracks(lt_ctx *ctx, const int64_t *seg3d_off, const double *seg3
   const long long G = ctx->G;
   std::vector<MLine> lines((size_t)std::max<long long>(G, 1));
   std::vector<int> node_of((size_t)std::max<long long>(G, 1), -1);
-  ctx->mg_node_img.clear(); ctx->mg_node_line.clear();
+  ctx->mg.node_img.clear(); ctx->mg.node_line.clear();
   for (int n = 0; n < n_img; ++n) {
     const Cam &cam = ctx->h_cams[(size_t)n];
     const long long g0 = ctx->seg_off[(size_t)n], m = ctx->seg_off[(size_t)n + 1] - g0;
@@ -77,12 +77,12 @@ int lt_merge_to_tracks(lt_ctx *ctx, const int64_t *seg3d_off, const double *seg3
       for (int k = 0; k < 4; ++k) r.seg[k] = s2[k];
       r.pad_ = 0.0;
       if (r.len == 0) continue;  // merging.cc:370-371: exact test
-      node_of[(size_t)(g0 + l)] = (int)ctx->mg_node_img.size();
-      ctx->mg_node_img.push_back(ctx->img_ids[(size_t)n]);
-      ctx->mg_node_line.push_back((int)l);
+      node_of[(size_t)(g0 + l)] = (int)ctx->mg.node_img.size();
+      ctx->mg.node_img.push_back(ctx->img_ids[(size_t)n]);
+      ctx->mg.node_line.push_back((int)l);
     }
   }
-  const int n_nodes = (int)ctx->mg_node_img.size();
+  const int n_nodes = (int)ctx->mg.node_img.size();
 
   // workgroups: self pass of every image, then one per (image, neighbour slot), each in tiles of 256 rows
   std::vector<MBlock> self_blks, cross_blks;
@@ -115,54 +115,28 @@ int lt_merge_to_tracks(lt_ctx *ctx, const int64_t *seg3d_off, const double *seg3
   std::vector<MEdge> h_edges;
   unsigned long long n_found = 0;
   int attempts = 0;
-  float dev_ms = 0.0f;
+  Events<2> ev;  // around the two launches of the attempt that fitted
   if (!blks.empty()) {
-    ENSURE(ctx, ctx->d_mg_lines, sizeof(MLine) * lines.size());
-    ENSURE(ctx, ctx->d_mg_blks, sizeof(MBlock) * blks.size());
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_mg_lines.p, lines.data(), sizeof(MLine) * lines.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_mg_blks.p, blks.data(), sizeof(MBlock) * blks.size(), hipMemcpyHostToDevice, st));
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    HIPCHK(ctx, hipEventCreate(&ev0));
-    HIPCHK(ctx, hipEventCreate(&ev1));
-    int rc = LT_OK;
-    for (;;) {
-      ++attempts;
-      // [counter (8 B, padded to 16) | capacity edges of 16 B]
-      if (!ctx->d_mg_edges.ensure(16 + sizeof(MEdge) * (size_t)capacity)) {
-        rc = fail(ctx, LT_ERR_HIP, "hipMalloc failed for the merge edge buffer");
-        break;
-      }
-      unsigned long long *d_cnt = ctx->d_mg_edges.as<unsigned long long>();
-      MEdge *d_edges = reinterpret_cast<MEdge *>(ctx->d_mg_edges.as<char>() + 16);
-      if (hipMemsetAsync(d_cnt, 0, 8, st) != hipSuccess || hipEventRecord(ev0, st) != hipSuccess) {
-        rc = fail(ctx, LT_ERR_HIP, "HIP failure before the merge kernels");
-        break;
-      }
-      const MBlock *d_blks = ctx->d_mg_blks.as<MBlock>();
-      launch_merge_pairs(st, true, (int)self_blks.size(), d_blks, ctx->d_seg_off.as<long long>(), ctx->d_mg_lines.as<MLine>(),
-                         ctx->d_cams.as<Cam>(), l2, l3, cos_guard, parity_fast, d_edges, capacity, d_cnt);
-      launch_merge_pairs(st, false, (int)cross_blks.size(), d_blks + self_blks.size(), ctx->d_seg_off.as<long long>(),
-                         ctx->d_mg_lines.as<MLine>(), ctx->d_cams.as<Cam>(), l2, l3, cos_guard, parity_fast, d_edges,
-                         capacity, d_cnt);
-      if (hipGetLastError() != hipSuccess || hipEventRecord(ev1, st) != hipSuccess ||
-          hipMemcpyAsync(&n_found, d_cnt, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-          hipStreamSynchronize(st) != hipSuccess) {
-        rc = fail(ctx, LT_ERR_HIP, "HIP failure in k_merge_pairs");
-        break;
-      }
-      (void)hipEventElapsedTime(&dev_ms, ev0, ev1);
-      if (n_found > capacity) {  // every accepted pair was counted: the next run has room for all of them
-        capacity = n_found;
-        continue;
-      }
-      h_edges.resize((size_t)n_found);
-      if (n_found && hipMemcpy(h_edges.data(), d_edges, sizeof(MEdge) * (size_t)n_found, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(ctx, LT_ERR_HIP, "HIP copy failed for the merge edges");
-      break;
-    }
-    (void)hipEventDestroy(ev0);
-    (void)hipEventDestroy(ev1);
-    if (rc) return rc;
+    if (int rc = upload_vec(ctx, ctx->mg.d_lines, lines)) return rc;
+    if (int rc = upload_vec(ctx, ctx->mg.d_blks, blks)) return rc;
+    if (int rc = ev.create(ctx)) return rc;
+    const MBlock *d_blks = ctx->mg.d_blks.as<MBlock>();
+    // [counter (8 B, padded to 16) | capacity edges of 16 B]
+    if (int rc = run_counted(ctx, ctx->mg.d_edges, 16, sizeof(MEdge), capacity,
+                             [&](void *items, unsigned long long cap, unsigned long long *d_cnt) {
+          MEdge *d_edges = static_cast<MEdge *>(items);
+          if (int rc = ev.record(ctx, 0)) return rc;
+          launch_merge_pairs(st, true, (int)self_blks.size(), d_blks, ctx->d_seg_off.as<long long>(),
+                             ctx->mg.d_lines.as<MLine>(), ctx->d_cams.as<Cam>(), l2, l3, cos_guard, parity_fast, d_edges,
+                             cap, d_cnt);
+          launch_merge_pairs(st, false, (int)cross_blks.size(), d_blks + self_blks.size(),
+                             ctx->d_seg_off.as<long long>(), ctx->mg.d_lines.as<MLine>(), ctx->d_cams.as<Cam>(), l2, l3,
+                             cos_guard, parity_fast, d_edges, cap, d_cnt);
+          return ev.record(ctx, 1);
+        }, &n_found, &attempts))
+      return rc;
+    if (int rc = download(ctx, h_edges, ctx->mg.d_edges.as<char>() + 16, (size_t)n_found)) return rc;
+    if (int rc = stream_sync(ctx)) return rc;
   }
 
   // the reference's insertion order (merging.cc:458-469): image, self pass before cross pass, then the loop indices
@@ -171,13 +145,13 @@ int lt_merge_to_tracks(lt_ctx *ctx, const int64_t *seg3d_off, const double *seg3
            std::make_tuple(b.img, b.slot >= 0, b.line, b.slot, b.ng_line);
   });
   std::vector<UnionEdge> ue(h_edges.size());
-  ctx->mg_e1.resize(h_edges.size()); ctx->mg_e2.resize(h_edges.size()); ctx->mg_sim.resize(h_edges.size());
+  ctx->mg.e1.resize(h_edges.size()); ctx->mg.e2.resize(h_edges.size()); ctx->mg.sim.resize(h_edges.size());
   for (size_t k = 0; k < h_edges.size(); ++k) {
     const MEdge &e = h_edges[k];
     const int nb = e.slot < 0 ? e.img : nb_idx[(size_t)(nb_off[e.img] - nb_off[0] + e.slot)];
     const long long g1 = ctx->seg_off[(size_t)e.img] + e.line, g2 = ctx->seg_off[(size_t)nb] + e.ng_line;
     ue[k] = UnionEdge{lines[(size_t)g1].len + lines[(size_t)g2].len, node_of[(size_t)g1], node_of[(size_t)g2]};
-    ctx->mg_e1[k] = ue[k].n1; ctx->mg_e2[k] = ue[k].n2; ctx->mg_sim[k] = ue[k].sim;
+    ctx->mg.e1[k] = ue[k].n1; ctx->mg.e2[k] = ue[k].n2; ctx->mg.sim[k] = ue[k].sim;
   }
   // ComputeLineTrackLabelsGreedy: std::sort of (sim, idx1, idx2) tuples, then reversed (merging.cc:33-34)
   std::sort(ue.begin(), ue.end(), [](const UnionEdge &a, const UnionEdge &b) {
@@ -187,7 +161,7 @@ int lt_merge_to_tracks(lt_ctx *ctx, const int64_t *seg3d_off, const double *seg3
   std::vector<long long> node_g((size_t)n_nodes);
   for (long long g = 0; g < G; ++g)
     if (node_of[(size_t)g] >= 0) node_g[(size_t)node_of[(size_t)g]] = g;
-  for (int i = 0; i < n_nodes; ++i) node_imgidx[(size_t)i] = ctx->mg_node_img[(size_t)i];
+  for (int i = 0; i < n_nodes; ++i) node_imgidx[(size_t)i] = ctx->mg.node_img[(size_t)i];
   std::vector<int> labels;
   const int n_tracks = n_nodes > 0 ? greedy_track_labels(n_nodes, node_imgidx.data(), ue, labels) : 0;
 
@@ -206,7 +180,7 @@ int lt_merge_to_tracks(lt_ctx *ctx, const int64_t *seg3d_off, const double *seg3
     if (t < 0) continue;
     const size_t w = (size_t)wr[(size_t)t]++;
     const MLine &r = lines[(size_t)node_g[(size_t)i]];
-    m_img[w] = ctx->mg_node_img[(size_t)i]; m_lid[w] = ctx->mg_node_line[(size_t)i]; m_nid[w] = i;
+    m_img[w] = ctx->mg.node_img[(size_t)i]; m_lid[w] = ctx->mg.node_line[(size_t)i]; m_nid[w] = i;
     m_sc[w] = r.len;
     for (int k = 0; k < 4; ++k) m_l2[4 * w + k] = r.seg[k];
     // Line3d(MatrixXd) (linebase.cc:60-65): score -1; its depths are not set there (0 here, as value-initialised)
@@ -230,31 +204,31 @@ int lt_merge_to_tracks(lt_ctx *ctx, const int64_t *seg3d_off, const double *seg3
   }
   *out = lt_ts_create(n_tracks, line7.data(), active.data(), off.data(), m_img.data(), m_lid.data(), m_nid.data(),
                       m_sc.data(), m_l2.data(), m_l3.data());
-  ctx->mg_timers[0] = dev_ms;
-  ctx->mg_timers[1] = now_ms() - t_start;
-  ctx->mg_timers[2] = attempts;
-  ctx->mg_timers[3] = (double)n_found;
+  ctx->mg.timers[0] = ev.ms(0, 1);
+  ctx->mg.timers[1] = now_ms() - t_start;
+  ctx->mg.timers[2] = attempts;
+  ctx->mg.timers[3] = (double)n_found;
   return LT_OK;
 }
 
 int lt_merge_graph_size(lt_ctx *ctx, int64_t *n_nodes, int64_t *n_edges) {
-  if (n_nodes) *n_nodes = (int64_t)ctx->mg_node_img.size();
-  if (n_edges) *n_edges = (int64_t)ctx->mg_e1.size();
+  if (n_nodes) *n_nodes = (int64_t)ctx->mg.node_img.size();
+  if (n_edges) *n_edges = (int64_t)ctx->mg.e1.size();
   return LT_OK;
 }
 
 int lt_merge_graph_get(lt_ctx *ctx, int32_t *node_img, int32_t *node_line, int32_t *edge_n1, int32_t *edge_n2,
                        double *edge_sim) {
-  if (node_img) std::copy(ctx->mg_node_img.begin(), ctx->mg_node_img.end(), node_img);
-  if (node_line) std::copy(ctx->mg_node_line.begin(), ctx->mg_node_line.end(), node_line);
-  if (edge_n1) std::copy(ctx->mg_e1.begin(), ctx->mg_e1.end(), edge_n1);
-  if (edge_n2) std::copy(ctx->mg_e2.begin(), ctx->mg_e2.end(), edge_n2);
-  if (edge_sim) std::copy(ctx->mg_sim.begin(), ctx->mg_sim.end(), edge_sim);
+  if (node_img) std::copy(ctx->mg.node_img.begin(), ctx->mg.node_img.end(), node_img);
+  if (node_line) std::copy(ctx->mg.node_line.begin(), ctx->mg.node_line.end(), node_line);
+  if (edge_n1) std::copy(ctx->mg.e1.begin(), ctx->mg.e1.end(), edge_n1);
+  if (edge_n2) std::copy(ctx->mg.e2.begin(), ctx->mg.e2.end(), edge_n2);
+  if (edge_sim) std::copy(ctx->mg.sim.begin(), ctx->mg.sim.end(), edge_sim);
   return LT_OK;
 }
 
 int lt_merge_get_timers(lt_ctx *ctx, double out[4]) {
-  for (int k = 0; k < 4; ++k) out[k] = ctx->mg_timers[k];
+  for (int k = 0; k < 4; ++k) out[k] = ctx->mg.timers[k];
   return LT_OK;
 }
 

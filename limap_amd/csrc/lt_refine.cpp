@@ -21,8 +21,7 @@
 #include <omp.h>
 
 using namespace lt;
-using lt_impl::now_ms;
-using lt_impl::upload_vec;
+using namespace lt_impl;
 
 namespace {
 
@@ -35,12 +34,6 @@ struct Plan {
   long long n_sup = 0;
 };
 
-bool finite_all(const double *v, size_t n) {
-  for (size_t k = 0; k < n; ++k)
-    if (!std::isfinite(v[k])) return false;
-  return true;
-}
-
 int check_config(const lt_refine_config *cfg, std::string &msg) {
   if (!cfg) { msg = "null configuration"; return 1; }
   if (!(cfg->geometric_alpha >= 0.0) || !(cfg->geometric_alpha <= 700.0)) { msg = "geometric_alpha outside [0, 700]"; return 1; }
@@ -51,7 +44,7 @@ int check_config(const lt_refine_config *cfg, std::string &msg) {
 int check_cams(int n_img, const int32_t *ids, const double *k, const double *q, const double *t,
                std::unordered_map<int, int> &id2idx, std::string &msg) {
   if (n_img < 0 || (n_img > 0 && (!ids || !k || !q || !t))) { msg = "bad camera arrays"; return 1; }
-  if (!finite_all(k, 4 * (size_t)n_img) || !finite_all(q, 4 * (size_t)n_img) || !finite_all(t, 3 * (size_t)n_img)) {
+  if (!all_finite(k, 4 * (size_t)n_img) || !all_finite(q, 4 * (size_t)n_img) || !all_finite(t, 3 * (size_t)n_img)) {
     msg = "non-finite camera";
     return 1;
   }
@@ -65,14 +58,15 @@ int make_plan(const std::unordered_map<int, int> &id2idx, int64_t T, const doubl
               const int32_t *img, const double *l2d4, const double *l3d6, const lt_refine_config &cfg, Plan &pl,
               std::string &msg) {
   if (T < 0 || !off || (T > 0 && !line6)) { msg = "bad track arrays"; return 1; }
-  if (off[0] != 0) { msg = "offsets must start at 0"; return 1; }
+  msg = offsets_msg("track", T, off);
+  if (!msg.empty()) return 1;
   for (int64_t n = 0; n < T; ++n) {
     if (off[n + 1] <= off[n]) { msg = "track " + std::to_string(n) + " has no supports"; return 1; }  // THROW_CHECK_GT(line3ds.size(), 0)
     if (off[n + 1] - off[n] > (1 << 28)) { msg = "too many supports in a track"; return 1; }
   }
   const long long S = T > 0 ? off[T] : 0;
   if (S > 0 && (!img || !l2d4 || !l3d6)) { msg = "null support arrays"; return 1; }
-  if (!finite_all(line6, 6 * (size_t)T) || !finite_all(l2d4, 4 * (size_t)S) || !finite_all(l3d6, 6 * (size_t)S)) {
+  if (!all_finite(line6, 6 * (size_t)T) || !all_finite(l2d4, 4 * (size_t)S) || !all_finite(l3d6, 6 * (size_t)S)) {
     msg = "non-finite coordinate";
     return 1;
   }
@@ -207,70 +201,54 @@ void copy_out(const RfOut *o, long long T, double *params6, double *seg6, double
   }
 }
 
-int sync(lt_ctx *ctx) {
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  HIPCHK(ctx, hipGetLastError());
-  return LT_OK;
-}
-
-// upload of the plan, the three kernels, download into ctx->rf_out; d_k / d_q / d_t: the cameras on the device
+// upload of the plan, the three kernels, download into ctx->rf.out; d_k / d_q / d_t: the cameras on the device
 int run_device(lt_ctx *ctx, const Plan &pl, const double *d_k, const double *d_q, const double *d_t,
                const lt_refine_config &cfg, double t0) {
   const long long S = pl.n_sup, T = (long long)pl.tracks.size();
   static_assert(sizeof(RfOut) == 15 * sizeof(double), "RfOut is 15 doubles");
-  ctx->rf_out.assign(15 * (size_t)T, 0.0);
-  for (int k = 0; k < 4; ++k) ctx->rf_timers[k] = 0.0;
+  ctx->rf.out.assign(15 * (size_t)T, 0.0);
+  for (int k = 0; k < 4; ++k) ctx->rf.timers[k] = 0.0;
   if (T == 0) return LT_OK;
   if (T * kRfWidth / kRfBlock + 1 > (long long)INT_MAX / kRfBlock || S > ((long long)1 << 31))
     return fail(ctx, LT_ERR_ARGUMENT, "lt_refine: too many tracks for one call (split them)");
   hipStream_t st = ctx->stream;
   const long long stride = S;
-  if (int rc = upload_vec(ctx, ctx->d_rf_cam, pl.sup_cam)) return rc;
-  if (int rc = upload_vec(ctx, ctx->d_rf_l2d, pl.l2d)) return rc;
-  if (int rc = upload_vec(ctx, ctx->d_rf_l3d, pl.l3d)) return rc;
-  if (int rc = upload_vec(ctx, ctx->d_rf_line, pl.line6)) return rc;
-  if (int rc = upload_vec(ctx, ctx->d_rf_tracks, pl.tracks)) return rc;
-  ENSURE(ctx, ctx->d_rf_tab, 8 * (size_t)kRfFields * (size_t)stride);
-  ENSURE(ctx, ctx->d_rf_out, sizeof(RfOut) * (size_t)T);
-  if (int rc = sync(ctx)) return rc;
+  if (int rc = upload_vec(ctx, ctx->rf.d_cam, pl.sup_cam)) return rc;
+  if (int rc = upload_vec(ctx, ctx->rf.d_l2d, pl.l2d)) return rc;
+  if (int rc = upload_vec(ctx, ctx->rf.d_l3d, pl.l3d)) return rc;
+  if (int rc = upload_vec(ctx, ctx->rf.d_line, pl.line6)) return rc;
+  if (int rc = upload_vec(ctx, ctx->rf.d_tracks, pl.tracks)) return rc;
+  ENSURE(ctx, ctx->rf.d_tab, 8 * (size_t)kRfFields * (size_t)stride);
+  ENSURE(ctx, ctx->rf.d_out, sizeof(RfOut) * (size_t)T);
+  if (int rc = stream_sync(ctx)) return rc;
   const double t1 = now_ms();
-  ctx->rf_timers[0] = t1 - t0;
+  ctx->rf.timers[0] = t1 - t0;
 
   RfDev dev;
-  dev.tracks = ctx->d_rf_tracks.as<RfTrack>();
+  dev.tracks = ctx->rf.d_tracks.as<RfTrack>();
   dev.n_tracks = T;
-  dev.sup = ctx->d_rf_tab.as<double>();
+  dev.sup = ctx->rf.d_tab.as<double>();
   dev.stride = stride;
-  dev.l3d = ctx->d_rf_l3d.as<double>();
+  dev.l3d = ctx->rf.d_l3d.as<double>();
   dev.alpha = cfg.geometric_alpha;
   dev.max_iter = cfg.max_num_iterations;
   dev.num_outliers = cfg.num_outliers_aggregator;
-  RfOut *d_out = ctx->d_rf_out.as<RfOut>();
-  struct Events {  // destroyed on every return path
-    hipEvent_t e[2] = {nullptr, nullptr};
-    ~Events() {
-      for (auto &x : e)
-        if (x) (void)hipEventDestroy(x);
-    }
-  } evs;
-  hipEvent_t *ev = evs.e;
-  for (int k = 0; k < 2; ++k) HIPCHK(ctx, hipEventCreate(&ev[k]));
-  launch_refine_prep(st, d_k, d_q, d_t, ctx->d_rf_cam.as<int>(), ctx->d_rf_l2d.as<double>(), S, ctx->d_rf_tab.as<double>(),
-                     stride, ctx->d_rf_line.as<double>(), T, d_out);
-  HIPCHK(ctx, hipEventRecord(ev[0], st));
+  RfOut *d_out = ctx->rf.d_out.as<RfOut>();
+  Events<2> ev;  // around k_refine_lm
+  if (int rc = ev.create(ctx)) return rc;
+  launch_refine_prep(st, d_k, d_q, d_t, ctx->rf.d_cam.as<int>(), ctx->rf.d_l2d.as<double>(), S, ctx->rf.d_tab.as<double>(),
+                     stride, ctx->rf.d_line.as<double>(), T, d_out);
+  if (int rc = ev.record(ctx, 0)) return rc;
   launch_refine_lm(st, dev, d_out);
-  HIPCHK(ctx, hipEventRecord(ev[1], st));
+  if (int rc = ev.record(ctx, 1)) return rc;
   launch_refine_cut(st, dev, d_out);
-  int rc = sync(ctx);
-  float ms_lm = 0.f;
-  if (!rc) (void)hipEventElapsedTime(&ms_lm, ev[0], ev[1]);
-  if (rc) return rc;
+  if (int rc = stream_sync(ctx)) return rc;
   const double t2 = now_ms();
-  ctx->rf_timers[1] = t2 - t1;
-  ctx->rf_timers[3] = ms_lm;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->rf_out.data(), d_out, sizeof(RfOut) * (size_t)T, hipMemcpyDeviceToHost, st));
-  if (int rc2 = sync(ctx)) return rc2;
-  ctx->rf_timers[2] = now_ms() - t2;
+  ctx->rf.timers[1] = t2 - t1;
+  ctx->rf.timers[3] = ev.ms(0, 1);
+  HIPCHK(ctx, hipMemcpyAsync(ctx->rf.out.data(), d_out, sizeof(RfOut) * (size_t)T, hipMemcpyDeviceToHost, st));
+  if (int rc = stream_sync(ctx)) return rc;
+  ctx->rf.timers[2] = now_ms() - t2;
   return LT_OK;
 }
 
@@ -322,29 +300,29 @@ int lt_refine_arrays(lt_ctx *ctx, int n_img, const int32_t *img_ids, const doubl
     return fail(ctx, LT_ERR_ARGUMENT, who + ": " + msg);
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const size_t nI = (size_t)std::max(n_img, 1);
-  ENSURE(ctx, ctx->d_rf_k, 32 * nI);
-  ENSURE(ctx, ctx->d_rf_q, 32 * nI);
-  ENSURE(ctx, ctx->d_rf_t, 24 * nI);
+  ENSURE(ctx, ctx->rf.d_k, 32 * nI);
+  ENSURE(ctx, ctx->rf.d_q, 32 * nI);
+  ENSURE(ctx, ctx->rf.d_t, 24 * nI);
   if (n_img > 0) {
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_rf_k.p, kvec4, 32 * (size_t)n_img, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_rf_q.p, qvec4, 32 * (size_t)n_img, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_rf_t.p, tvec3, 24 * (size_t)n_img, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->rf.d_k.p, kvec4, 32 * (size_t)n_img, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->rf.d_q.p, qvec4, 32 * (size_t)n_img, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->rf.d_t.p, tvec3, 24 * (size_t)n_img, hipMemcpyHostToDevice, ctx->stream));
   }
-  return run_device(ctx, pl, ctx->d_rf_k.as<double>(), ctx->d_rf_q.as<double>(), ctx->d_rf_t.as<double>(), *cfg, t0);
+  return run_device(ctx, pl, ctx->rf.d_k.as<double>(), ctx->rf.d_q.as<double>(), ctx->rf.d_t.as<double>(), *cfg, t0);
 }
 
-int64_t lt_refine_num(lt_ctx *ctx) { return ctx ? (int64_t)(ctx->rf_out.size() / 15) : 0; }
+int64_t lt_refine_num(lt_ctx *ctx) { return ctx ? (int64_t)(ctx->rf.out.size() / 15) : 0; }
 
 int lt_refine_get(lt_ctx *ctx, double *params6, double *seg6, double *cost2, int32_t *iters, int32_t *codes) {
   if (!ctx) return LT_ERR_ARGUMENT;
-  copy_out(reinterpret_cast<const RfOut *>(ctx->rf_out.data()), (long long)(ctx->rf_out.size() / 15), params6, seg6, cost2,
+  copy_out(reinterpret_cast<const RfOut *>(ctx->rf.out.data()), (long long)(ctx->rf.out.size() / 15), params6, seg6, cost2,
            iters, codes);
   return LT_OK;
 }
 
 int lt_refine_get_timers(lt_ctx *ctx, double out[4]) {
   if (!ctx || !out) return LT_ERR_ARGUMENT;
-  for (int k = 0; k < 4; ++k) out[k] = ctx->rf_timers[k];
+  for (int k = 0; k < 4; ++k) out[k] = ctx->rf.timers[k];
   return LT_OK;
 }
 
@@ -404,7 +382,7 @@ int lt_fn_refine_eval(int64_t K, const double *cam11, const double *line2d4, con
 
 int lt_fn_refine_cut(int64_t K, const double *line3d6, const double params6[6], int num_outliers, double seg6[6]) {
   if (K < 1 || K > (1 << 28) || !line3d6 || !params6 || !seg6 || num_outliers < 0 || num_outliers > 2 * K - 1 ||
-      !finite_all(line3d6, 6 * (size_t)K))
+      !all_finite(line3d6, 6 * (size_t)K))
     return LT_ERR_ARGUMENT;
   RfOut o;
   std::copy(params6, params6 + 6, o.p);
@@ -423,7 +401,7 @@ int lt_fn_refine_explog(int which, int64_t n, const double *x, double *out) {
 }
 
 int lt_fn_refine_minimal(const double line6[6], double params6[6]) {
-  if (!line6 || !params6 || !finite_all(line6, 6)) return LT_ERR_ARGUMENT;
+  if (!line6 || !params6 || !all_finite(line6, 6)) return LT_ERR_ARGUMENT;
   const double dx = line6[0] - line6[3], dy = line6[1] - line6[4], dz = line6[2] - line6[5];
   if (!(std::sqrt((dx * dx + dy * dy) + dz * dz) > 0.0)) return LT_ERR_ARGUMENT;
   rf_minimal(line6, params6);

@@ -11,9 +11,7 @@
 // remerge (O(T^2), the next hotspot on big scenes) runs on the GPU (k_track_connect); the union-find
 // over its edges and the aggregation stay on the host like the rest of the tail.
 
-#include "lt_ctx.h"
-#include "lt_pool.h"
-#include "lt_tail.h"
+#include "lt_host.h"
 
 #include <atomic>
 
@@ -294,7 +292,7 @@ namespace {
 
 // The device part of a remerge pass (merging/merging.cc:519-556): `pack(t, dst7)` writes track t's line (start, end,
 // uncertainty) and returns its active flag; the sorted, unique edges (min << 32 | max) of k_track_connect are left in
-// ctx->h_rm_edges.  capacity0: edge slots of the first launch, 0 = max(65536, 32 T); a launch that finds more edges than
+// ctx->rm.h_edges.  capacity0: edge slots of the first launch, 0 = max(65536, 32 T); a launch that finds more edges than
 // it has slots for is repeated once with room for all of them.  *n_raw: the device counter of the launch that fitted (a
 // pair of two active tracks is counted from both sides unless every track is active), *attempts: launches.
 template <class Pack>
@@ -312,7 +310,7 @@ int track_connect_edges(lt_ctx *ctx, int T, Pack pack, const lt_config *linker_c
   double cos_guard = (th < 90.0) ? std::cos(th * kPi / 180.0) : -1.0;
 
   // host image of the device input: [7 T doubles: the track lines | T bytes: active flags], one copy
-  std::vector<double> &inbuf = ctx->h_rm_in;
+  std::vector<double> &inbuf = ctx->rm.h_in;
   const size_t in_bytes = 56 * (size_t)T + (size_t)T;
   inbuf.resize((in_bytes + 7) / 8);
   unsigned char *active = reinterpret_cast<unsigned char *>(inbuf.data() + 7 * (size_t)T);
@@ -322,57 +320,34 @@ int track_connect_edges(lt_ctx *ctx, int T, Pack pack, const lt_config *linker_c
     n_active += active[t];
   }
   // the device buffers and the edge list live in the context: a remerge to its fixed point calls this several times
-  DevBuf &d_in = ctx->d_rm_line, &d_edges = ctx->d_rm_edges;
+  DevBuf &d_in = ctx->rm.d_line, &d_edges = ctx->rm.d_edges;
   hipStream_t st = ctx->stream;
-  std::vector<unsigned long long> &edges = ctx->h_rm_edges;
-  edges.clear();
+  ENSURE(ctx, d_in, inbuf.size() * 8);
+  HIPCHK(ctx, hipMemcpyAsync(d_in.p, inbuf.data(), inbuf.size() * 8, hipMemcpyHostToDevice, st));
   // d_edges = [edge count | edges ...]: count and the first kFirst edges come back in ONE copy behind the kernel
   constexpr unsigned long long kFirst = 4095;
-  unsigned long long capacity = capacity0 ? capacity0 : std::max<unsigned long long>(1ull << 16, 32ull * (unsigned long long)T);
-  int rc = LT_OK;
-  bool fitted = false;
+  std::vector<unsigned long long> &back = ctx->rm.h_back, &edges = ctx->rm.h_edges;
+  back.resize((size_t)kFirst + 1);
+  edges.clear();
   *n_raw = 0;
   *attempts = 0;
-  std::vector<unsigned long long> &back = ctx->h_rm_back;
-  back.resize((size_t)kFirst + 1);
-  for (int attempt = 0; attempt < 8; ++attempt) {
-    // (the copy behind the kernel reads kFirst + 1 words whatever the capacity is: the buffer is never smaller)
-    if (!d_in.ensure(inbuf.size() * 8) || !d_edges.ensure((std::max(capacity, kFirst) + 1) * 8)) {
-      rc = fail(ctx, LT_ERR_HIP, "hipMalloc failed in remerge");
-      break;
-    }
-    if (hipMemcpyAsync(d_in.p, inbuf.data(), inbuf.size() * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemsetAsync(d_edges.p, 0, 8, st) != hipSuccess) {
-      rc = fail(ctx, LT_ERR_HIP, "HIP copy failed in remerge");
-      break;
-    }
-    launch_track_connect(st, T, d_in.as<double>(), reinterpret_cast<const unsigned char *>(d_in.as<double>() + 7 * (size_t)T),
-                         n_active == T ? 1 : 0, l3, cos_guard, d_edges.as<unsigned long long>() + 1, capacity,
-                         d_edges.as<unsigned long long>());
-    ++*attempts;
-    if (hipMemcpyAsync(back.data(), d_edges.p, (kFirst + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) {
-      rc = fail(ctx, LT_ERR_HIP, "HIP failure in k_track_connect");
-      break;
-    }
-    const unsigned long long n = back[0];
-    if (n > capacity) {  // rare: more edges than reserved, run again with room for all of them
-      capacity = n + 1024;
-      continue;
-    }
-    edges.assign(back.begin() + 1, back.begin() + 1 + (size_t)std::min(n, kFirst));
-    if (n > kFirst) {
-      edges.resize((size_t)n);
-      if (hipMemcpy(edges.data() + kFirst, d_edges.as<unsigned long long>() + 1 + kFirst, (size_t)(n - kFirst) * 8,
-                    hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(ctx, LT_ERR_HIP, "HIP copy failed in remerge");
-    }
-    *n_raw = n;
-    fitted = true;
-    break;
+  const unsigned long long first = capacity0 ? capacity0 : std::max<unsigned long long>(1ull << 16, 32ull * (unsigned long long)T);
+  if (int rc = lt_impl::run_counted(ctx, d_edges, 8, 8, first,
+                                    [&](void *items, unsigned long long capacity, unsigned long long *counter) {
+        launch_track_connect(st, T, d_in.as<double>(),
+                             reinterpret_cast<const unsigned char *>(d_in.as<double>() + 7 * (size_t)T), n_active == T ? 1 : 0,
+                             l3, cos_guard, static_cast<unsigned long long *>(items), capacity, counter);
+        return LT_OK;
+      }, n_raw, attempts, back.data(), (size_t)kFirst))
+    return rc;
+  const unsigned long long n = *n_raw;
+  edges.assign(back.begin() + 1, back.begin() + 1 + (size_t)std::min(n, kFirst));
+  if (n > kFirst) {
+    edges.resize((size_t)n);
+    HIPCHK(ctx, hipMemcpyAsync(edges.data() + kFirst, d_edges.as<unsigned long long>() + 1 + kFirst, (size_t)(n - kFirst) * 8,
+                               hipMemcpyDeviceToHost, st));
+    if (int rc = lt_impl::stream_sync(ctx)) return rc;
   }
-  if (rc) return rc;
-  if (!fitted) return fail(ctx, LT_ERR_STATE, "k_track_connect: the edge count kept growing between launches");
   // std::set<pair<size_t,size_t>> order + dedupe
   std::sort(edges.begin(), edges.end());
   edges.erase(std::unique(edges.begin(), edges.end()), edges.end());
@@ -394,7 +369,7 @@ int lt_fn_track_connect(lt_ctx *ctx, int64_t n_tracks, const double *line7, cons
   HIPCHK(ctx, hipSetDevice(ctx->device));
   unsigned long long raw = 0;
   int launches = 0;
-  ctx->h_rm_edges.clear();
+  ctx->rm.h_edges.clear();
   if (n_tracks > 0) {
     int rc = track_connect_edges(ctx, (int)n_tracks, [&](int t, double *dst) {
       std::memcpy(dst, line7 + 7 * (size_t)t, 56);
@@ -402,7 +377,7 @@ int lt_fn_track_connect(lt_ctx *ctx, int64_t n_tracks, const double *line7, cons
     }, linker_cfg, (unsigned long long)capacity0, &raw, &launches);
     if (rc) return rc;
   }
-  const std::vector<unsigned long long> &edges = ctx->h_rm_edges;
+  const std::vector<unsigned long long> &edges = ctx->rm.h_edges;
   *n_unique = (int64_t)edges.size();
   if (n_raw) *n_raw = (int64_t)raw;
   if (attempts) *attempts = launches;
@@ -425,7 +400,7 @@ int lt_ts_remerge_once(lt_ctx *ctx, lt_trackset *ts, const lt_config *linker_cfg
     return ts->tracks[t].active;
   }, linker_cfg, 0, &n_raw, &attempts);
   if (rc) return rc;
-  const std::vector<unsigned long long> &edges = ctx->h_rm_edges;
+  const std::vector<unsigned long long> &edges = ctx->rm.h_edges;
   std::vector<int> parent((size_t)T, -1);
   std::vector<size_t> gsize((size_t)T, 1);
   for (unsigned long long e : edges) {

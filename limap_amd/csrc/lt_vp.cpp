@@ -21,8 +21,7 @@
 #include <omp.h>
 
 using namespace lt;
-using lt_impl::now_ms;
-using lt_impl::upload_vec;
+using namespace lt_impl;
 
 namespace {
 
@@ -50,15 +49,12 @@ int check_config(const lt_vp_config *cfg, std::string &msg) {
 
 int check_lines(int n_img, const int64_t *line_off, const double *lines, std::string &msg) {
   if (n_img < 0) { msg = "bad image count"; return 1; }
-  if (!line_off) { msg = "null line offsets"; return 1; }
-  if (line_off[0] != 0) { msg = "line offsets must start at 0"; return 1; }
-  for (int m = 0; m < n_img; ++m) {
-    if (line_off[m + 1] < line_off[m]) { msg = "line offsets decrease"; return 1; }
+  msg = offsets_msg("line", n_img, line_off);
+  if (!msg.empty()) return 1;
+  for (int m = 0; m < n_img; ++m)
     if (line_off[m + 1] - line_off[m] > INT_MAX / 2) { msg = "too many lines in an image"; return 1; }
-  }
   if (line_off[n_img] > 0 && !lines) { msg = "null coordinates"; return 1; }
-  for (long long k = 0; k < 4 * line_off[n_img]; ++k)
-    if (!std::isfinite(lines[k])) { msg = "non-finite line coordinate"; return 1; }
+  if (!all_finite(lines, 4 * line_off[n_img])) { msg = "non-finite line coordinate"; return 1; }
   return 0;
 }
 
@@ -164,17 +160,6 @@ void host_roots(const double *lines, const std::vector<int> &valid, const lt_vp_
 }
 
 // ---- limap's own tail ----
-int find_root(std::vector<int> &parents, int k) {  // union_find_get_root (base/graph.cc:157-166), without recursion
-  int r = k;
-  while (parents[(size_t)r] != -1) r = parents[(size_t)r];
-  while (parents[(size_t)k] != -1) {
-    const int up = parents[(size_t)k];
-    parents[(size_t)k] = r;
-    k = up;
-  }
-  return r;
-}
-
 inline d3 line_coords(const double *l) {  // Line2d::coords() (linebase.cc:35-39)
   return unit(cross(mk3(l[0], l[1], 1.0), mk3(l[2], l[3], 1.0)));
 }
@@ -197,16 +182,16 @@ bool inf_line_distance(const double *line, double qx, double qy, double *out) {
 // count_valid_supports_2d (base_vp_detector.cc:41-73) over the lines ids[] of an image; -1 where the reference throws
 int count_valid_supports(const double *lines, const std::vector<int> &ids, double th) {
   const size_t n = ids.size();
-  std::vector<int> parents(n, -1);
+  std::vector<int> parents(n, -1);  // union_find_get_root (base/graph.cc:157-166) is uf_root (lt_tail.h)
   std::vector<double> len(n);
   for (size_t k = 0; k < n; ++k) {
     const double *l = lines + 4 * (size_t)ids[k];
     len[k] = vp_length(l[0], l[1], l[2], l[3]);
   }
   for (size_t i = 0; i + 1 < n; ++i) {
-    const int root_i = find_root(parents, (int)i);
+    const int root_i = uf_root((int)i, parents);
     for (size_t j = i + 1; j < n; ++j) {
-      const int root_j = find_root(parents, (int)j);
+      const int root_j = uf_root((int)j, parents);
       if (root_j == root_i) continue;
       size_t k1 = i, k2 = j;  // the shorter line is projected on the longer one
       if (len[i] > len[j]) { k1 = j; k2 = i; }
@@ -310,12 +295,6 @@ void gather(int n_img, const int64_t *line_off, const std::vector<ImgResult> &re
   }
 }
 
-int sync(lt_ctx *ctx) {
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  HIPCHK(ctx, hipGetLastError());
-  return LT_OK;
-}
-
 const char *kThrowMsg =
     ": a check of InfiniteLine2d fails on a support line (zero length, or coordinates beyond its EPS tests)";
 
@@ -342,11 +321,11 @@ int lt_vp_detect(lt_ctx *ctx, int n_img, const int64_t *line_off, const double *
   const long long nl = line_off[n_img];
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  for (int k = 0; k < 6; ++k) ctx->vp_timers[k] = 0.0;
-  ctx->vp_labels.assign((size_t)nl, -1);
-  ctx->vp_clusters.assign((size_t)nl, -1);
-  ctx->vp_vp_off.assign((size_t)n_img + 1, 0);
-  ctx->vp_vps.clear();
+  for (int k = 0; k < 6; ++k) ctx->vp.timers[k] = 0.0;
+  ctx->vp.labels.assign((size_t)nl, -1);
+  ctx->vp.clusters.assign((size_t)nl, -1);
+  ctx->vp.vp_off.assign((size_t)n_img + 1, 0);
+  ctx->vp.vps.clear();
   if (n_vps) *n_vps = 0;
   if (nl == 0) return LT_OK;
   const char *too_large = ": the scene is too large for one call (split the images)";
@@ -354,13 +333,13 @@ int lt_vp_detect(lt_ctx *ctx, int n_img, const int64_t *line_off, const double *
 
   // ---- upload, length filter ----
   double t0 = now_ms();
-  ENSURE(ctx, ctx->d_vp_raw, 32 * (size_t)nl);
-  ENSURE(ctx, ctx->d_vp_flag, (size_t)nl);
-  HIPCHK(ctx, hipMemcpyAsync(ctx->d_vp_raw.p, lines, 32 * (size_t)nl, hipMemcpyHostToDevice, st));
-  launch_vp_prep(st, ctx->d_vp_raw.as<double>(), nl, cfg->min_length, ctx->d_vp_flag.as<unsigned char>());
+  ENSURE(ctx, ctx->vp.d_raw, 32 * (size_t)nl);
+  ENSURE(ctx, ctx->vp.d_flag, (size_t)nl);
+  HIPCHK(ctx, hipMemcpyAsync(ctx->vp.d_raw.p, lines, 32 * (size_t)nl, hipMemcpyHostToDevice, st));
+  launch_vp_prep(st, ctx->vp.d_raw.as<double>(), nl, cfg->min_length, ctx->vp.d_flag.as<unsigned char>());
   std::vector<unsigned char> flag((size_t)nl);
-  HIPCHK(ctx, hipMemcpyAsync(flag.data(), ctx->d_vp_flag.p, (size_t)nl, hipMemcpyDeviceToHost, st));
-  if (int rc = sync(ctx)) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(flag.data(), ctx->vp.d_flag.p, (size_t)nl, hipMemcpyDeviceToHost, st));
+  if (int rc = stream_sync(ctx)) return rc;
   std::vector<std::vector<int>> valid;
   std::vector<char> active;
   plan_images(n_img, line_off, flag.data(), *cfg, valid, active);
@@ -392,49 +371,42 @@ int lt_vp_detect(lt_ctx *ctx, int n_img, const int64_t *line_off, const double *
         !vp_launch_fits((long long)blocks.size(), kVpBlock) || !vp_launch_fits(n_act, kVpClBlock) ||
         !vp_launch_fits((long long)n_act * ((M + kVpBlock - 1) / kVpBlock), kVpBlock))
       return fail(ctx, LT_ERR_ARGUMENT, who + too_large);
-    if (int rc = upload_vec(ctx, ctx->d_vp_src, src)) return rc;
-    if (int rc = upload_vec(ctx, ctx->d_vp_imgs, imgs)) return rc;
-    if (int rc = upload_vec(ctx, ctx->d_vp_blk, blocks)) return rc;
-    ENSURE(ctx, ctx->d_vp_lines, sizeof(VpLine) * (size_t)nv);
-    ENSURE(ctx, ctx->d_vp_hyp, sizeof(VpHyp) * (size_t)n_act * (size_t)M);
-    ENSURE(ctx, ctx->d_vp_pref, 8 * (size_t)nv * (size_t)W);
-    ENSURE(ctx, ctx->d_vp_state, 4 * (size_t)kVpStateInts * (size_t)nv);
-    ENSURE(ctx, ctx->d_vp_roots, 4 * (size_t)nv);
-    if (int rc = sync(ctx)) return rc;
+    if (int rc = upload_vec(ctx, ctx->vp.d_src, src)) return rc;
+    if (int rc = upload_vec(ctx, ctx->vp.d_imgs, imgs)) return rc;
+    if (int rc = upload_vec(ctx, ctx->vp.d_blk, blocks)) return rc;
+    ENSURE(ctx, ctx->vp.d_lines, sizeof(VpLine) * (size_t)nv);
+    ENSURE(ctx, ctx->vp.d_hyp, sizeof(VpHyp) * (size_t)n_act * (size_t)M);
+    ENSURE(ctx, ctx->vp.d_pref, 8 * (size_t)nv * (size_t)W);
+    ENSURE(ctx, ctx->vp.d_state, 4 * (size_t)kVpStateInts * (size_t)nv);
+    ENSURE(ctx, ctx->vp.d_roots, 4 * (size_t)nv);
+    if (int rc = stream_sync(ctx)) return rc;
   }
   double t1 = now_ms();
-  ctx->vp_timers[0] = t1 - t0;
+  ctx->vp.timers[0] = t1 - t0;
 
   // ---- kernels ----
   if (n_act > 0) {
-    hipEvent_t ev[3];
-    for (auto &e : ev) HIPCHK(ctx, hipEventCreate(&e));
-    launch_vp_lines(st, ctx->d_vp_raw.as<double>(), ctx->d_vp_src.as<long long>(), nv, ctx->d_vp_lines.as<VpLine>());
-    launch_vp_hyp(st, ctx->d_vp_imgs.as<VpImg>(), n_act, M, cfg->seed, ctx->d_vp_lines.as<VpLine>(),
-                  ctx->d_vp_hyp.as<VpHyp>());
-    HIPCHK(ctx, hipEventRecord(ev[0], st));
-    launch_vp_pref(st, ctx->d_vp_blk.as<VpBlock>(), (int)blocks.size(), ctx->d_vp_imgs.as<VpImg>(), M, W,
-                   cfg->inlier_threshold, ctx->d_vp_lines.as<VpLine>(), ctx->d_vp_hyp.as<VpHyp>(),
-                   ctx->d_vp_pref.as<unsigned long long>());
-    HIPCHK(ctx, hipEventRecord(ev[1], st));
-    launch_vp_cluster(st, ctx->d_vp_imgs.as<VpImg>(), n_act, W, ctx->d_vp_pref.as<unsigned long long>(),
-                      ctx->d_vp_state.as<int>(), ctx->d_vp_roots.as<int>());
-    HIPCHK(ctx, hipEventRecord(ev[2], st));
-    int rc = sync(ctx);
-    float ms_pref = 0.f, ms_cl = 0.f;
-    if (!rc) {
-      (void)hipEventElapsedTime(&ms_pref, ev[0], ev[1]);
-      (void)hipEventElapsedTime(&ms_cl, ev[1], ev[2]);
-    }
-    for (auto &e : ev) (void)hipEventDestroy(e);
-    if (rc) return rc;
-    ctx->vp_timers[4] = ms_pref;
-    ctx->vp_timers[5] = ms_cl;
+    Events<3> ev;  // hypotheses done, preference sets done, clustering done
+    if (int rc = ev.create(ctx)) return rc;
+    launch_vp_lines(st, ctx->vp.d_raw.as<double>(), ctx->vp.d_src.as<long long>(), nv, ctx->vp.d_lines.as<VpLine>());
+    launch_vp_hyp(st, ctx->vp.d_imgs.as<VpImg>(), n_act, M, cfg->seed, ctx->vp.d_lines.as<VpLine>(),
+                  ctx->vp.d_hyp.as<VpHyp>());
+    if (int rc = ev.record(ctx, 0)) return rc;
+    launch_vp_pref(st, ctx->vp.d_blk.as<VpBlock>(), (int)blocks.size(), ctx->vp.d_imgs.as<VpImg>(), M, W,
+                   cfg->inlier_threshold, ctx->vp.d_lines.as<VpLine>(), ctx->vp.d_hyp.as<VpHyp>(),
+                   ctx->vp.d_pref.as<unsigned long long>());
+    if (int rc = ev.record(ctx, 1)) return rc;
+    launch_vp_cluster(st, ctx->vp.d_imgs.as<VpImg>(), n_act, W, ctx->vp.d_pref.as<unsigned long long>(),
+                      ctx->vp.d_state.as<int>(), ctx->vp.d_roots.as<int>());
+    if (int rc = ev.record(ctx, 2)) return rc;
+    if (int rc = stream_sync(ctx)) return rc;
+    ctx->vp.timers[4] = ev.ms(0, 1);
+    ctx->vp.timers[5] = ev.ms(1, 2);
     double t2 = now_ms();
-    ctx->vp_timers[1] = t2 - t1;
-    HIPCHK(ctx, hipMemcpyAsync(roots.data(), ctx->d_vp_roots.p, 4 * (size_t)nv, hipMemcpyDeviceToHost, st));
-    if (int rc2 = sync(ctx)) return rc2;
-    ctx->vp_timers[2] = now_ms() - t2;
+    ctx->vp.timers[1] = t2 - t1;
+    HIPCHK(ctx, hipMemcpyAsync(roots.data(), ctx->vp.d_roots.p, 4 * (size_t)nv, hipMemcpyDeviceToHost, st));
+    if (int rc = stream_sync(ctx)) return rc;
+    ctx->vp.timers[2] = now_ms() - t2;
     for (int a = 0; a < n_act; ++a)
       for (int k = 0; k < imgs[(size_t)a].n; ++k) {
         const int r = roots[(size_t)(imgs[(size_t)a].v0 + k)];
@@ -457,24 +429,24 @@ int lt_vp_detect(lt_ctx *ctx, int n_img, const int64_t *line_off, const double *
   }
   for (int m = 0; m < n_img; ++m)
     if (res[(size_t)m].err) return fail(ctx, LT_ERR_ARGUMENT, who + kThrowMsg);
-  gather(n_img, line_off, res, ctx->vp_labels, ctx->vp_clusters, ctx->vp_vp_off, ctx->vp_vps);
-  ctx->vp_timers[3] = now_ms() - t3;
-  if (n_vps) *n_vps = (int64_t)ctx->vp_vp_off.back();
+  gather(n_img, line_off, res, ctx->vp.labels, ctx->vp.clusters, ctx->vp.vp_off, ctx->vp.vps);
+  ctx->vp.timers[3] = now_ms() - t3;
+  if (n_vps) *n_vps = (int64_t)ctx->vp.vp_off.back();
   return LT_OK;
 }
 
 int lt_vp_get(lt_ctx *ctx, int32_t *labels, int64_t *vp_off, double *vps, int32_t *clusters) {
   if (!ctx) return LT_ERR_ARGUMENT;
-  if (labels) std::copy(ctx->vp_labels.begin(), ctx->vp_labels.end(), labels);
-  if (vp_off) std::copy(ctx->vp_vp_off.begin(), ctx->vp_vp_off.end(), vp_off);
-  if (vps) std::copy(ctx->vp_vps.begin(), ctx->vp_vps.end(), vps);
-  if (clusters) std::copy(ctx->vp_clusters.begin(), ctx->vp_clusters.end(), clusters);
+  if (labels) std::copy(ctx->vp.labels.begin(), ctx->vp.labels.end(), labels);
+  if (vp_off) std::copy(ctx->vp.vp_off.begin(), ctx->vp.vp_off.end(), vp_off);
+  if (vps) std::copy(ctx->vp.vps.begin(), ctx->vp.vps.end(), vps);
+  if (clusters) std::copy(ctx->vp.clusters.begin(), ctx->vp.clusters.end(), clusters);
   return LT_OK;
 }
 
 int lt_vp_get_timers(lt_ctx *ctx, double out[6]) {
   if (!ctx || !out) return LT_ERR_ARGUMENT;
-  for (int k = 0; k < 6; ++k) out[k] = ctx->vp_timers[k];
+  for (int k = 0; k < 6; ++k) out[k] = ctx->vp.timers[k];
   return LT_OK;
 }
 
@@ -522,12 +494,9 @@ int lt_vp_cluster_sets(lt_ctx *ctx, int n_img, const int64_t *row_off, int64_t n
   if (!ctx) return LT_ERR_ARGUMENT;
   const std::string who = "lt_vp_cluster_sets";
   if (n_img < 0) return fail(ctx, LT_ERR_ARGUMENT, who + ": bad image count");
-  if (!row_off) return fail(ctx, LT_ERR_ARGUMENT, who + ": null row offsets");
-  if (row_off[0] != 0) return fail(ctx, LT_ERR_ARGUMENT, who + ": row offsets must start at 0");
-  for (int m = 0; m < n_img; ++m) {
-    if (row_off[m + 1] < row_off[m]) return fail(ctx, LT_ERR_ARGUMENT, who + ": row offsets decrease");
+  if (int rc = check_offsets(ctx, who.c_str(), "row", n_img, row_off)) return rc;
+  for (int m = 0; m < n_img; ++m)
     if (row_off[m + 1] - row_off[m] > INT_MAX / 2) return fail(ctx, LT_ERR_ARGUMENT, who + ": too many rows in an image");
-  }
   if (n_words < 1 || n_words > kVpMaxHypotheses / 64)
     return fail(ctx, LT_ERR_ARGUMENT, who + ": n_words outside [1, 2^14]");
   const long long nv = row_off[n_img];
@@ -552,14 +521,14 @@ int lt_vp_cluster_sets(lt_ctx *ctx, int n_img, const int64_t *row_off, int64_t n
       for (int w = 0; w < W; ++w)
         P[(size_t)(im.p0 + (long long)w * im.n + k)] = pref[(size_t)(im.v0 + k) * (size_t)W + (size_t)w];
   }
-  if (int rc = upload_vec(ctx, ctx->d_vp_imgs, imgs)) return rc;
-  if (int rc = upload_vec(ctx, ctx->d_vp_pref, P)) return rc;
-  ENSURE(ctx, ctx->d_vp_state, 4 * (size_t)kVpStateInts * (size_t)nv);
-  ENSURE(ctx, ctx->d_vp_roots, 4 * (size_t)nv);
-  launch_vp_cluster(st, ctx->d_vp_imgs.as<VpImg>(), n_img, W, ctx->d_vp_pref.as<unsigned long long>(),
-                    ctx->d_vp_state.as<int>(), ctx->d_vp_roots.as<int>());
-  HIPCHK(ctx, hipMemcpyAsync(roots, ctx->d_vp_roots.p, 4 * (size_t)nv, hipMemcpyDeviceToHost, st));
-  if (int rc = sync(ctx)) return rc;
+  if (int rc = upload_vec(ctx, ctx->vp.d_imgs, imgs)) return rc;
+  if (int rc = upload_vec(ctx, ctx->vp.d_pref, P)) return rc;
+  ENSURE(ctx, ctx->vp.d_state, 4 * (size_t)kVpStateInts * (size_t)nv);
+  ENSURE(ctx, ctx->vp.d_roots, 4 * (size_t)nv);
+  launch_vp_cluster(st, ctx->vp.d_imgs.as<VpImg>(), n_img, W, ctx->vp.d_pref.as<unsigned long long>(),
+                    ctx->vp.d_state.as<int>(), ctx->vp.d_roots.as<int>());
+  HIPCHK(ctx, hipMemcpyAsync(roots, ctx->vp.d_roots.p, 4 * (size_t)nv, hipMemcpyDeviceToHost, st));
+  if (int rc = stream_sync(ctx)) return rc;
   for (int m = 0; m < n_img; ++m)
     for (long long k = row_off[m]; k < row_off[m + 1]; ++k)
       if (roots[k] < 0 || roots[k] >= imgs[(size_t)m].n)

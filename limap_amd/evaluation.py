@@ -28,18 +28,8 @@ __all__ = ["PointCloudEvaluator", "RefLineEvaluator", "MeshEvaluator", "report_e
            "lines_array", "line_lengths"]
 
 _MAGIC = b"LIMAP_AMD_PCD\x00\x01\x00"  # 16 bytes: name, format version 1
-_contexts = {}
-
-
-def _context(device=0):
-    ctx = _contexts.get(device)
-    if ctx is None:
-        ctx = _contexts[device] = _capi.Context(device=device)
-    return ctx
-
-
-def _p(a, t=C.c_double):
-    return a.ctypes.data_as(C.POINTER(t))
+_context = _capi.per_device_contexts()
+_p = _capi.ptr
 
 
 def lines_array(lines):

@@ -96,15 +96,7 @@ def _config(options=None, ransac_th=0.75, min_percentage_inliers=0.6, var2d=5.0,
     return c
 
 
-_contexts = {}
-
-
-def _context(device=0):
-    """one context per device for the calls that bring no scene (lt_fit_points)"""
-    ctx = _contexts.get(device)
-    if ctx is None:
-        ctx = _contexts[device] = _capi.Context(device=device)
-    return ctx
+_context = _capi.per_device_contexts()  # for the calls that bring no scene (lt_fit_points)
 
 
 # ---- point sets -----------------------------------------------------------------------------------------------------

@@ -28,14 +28,7 @@ MAX_DIM = 256   # LT_MATCH_MAX_DIM
 KINDS = {"l2d2": 0, "endpoints": 1, "nn_endpoints": 1}
 _KEY = {0: "line_descriptors", 1: "endpoints_desc"}
 
-_contexts = {}
-
-
-def _context(device=0):
-    ctx = _contexts.get(device)
-    if ctx is None:
-        ctx = _contexts[device] = _capi.Context(device=device)
-    return ctx
+_context = _capi.per_device_contexts()
 
 
 def _kind(kind):

@@ -125,15 +125,7 @@ def _camera_arrays(views):
     return ids, k, q, t
 
 
-_CTX = None
-
-
-def _context():
-    """one context for the module's device calls (lt_create once, buffers reused between calls)"""
-    global _CTX
-    if _CTX is None:
-        _CTX = _capi.Context()
-    return _CTX
+_context = _capi.per_device_contexts()  # lt_create once per device, buffers reused between calls
 
 
 def cut_segment(params6, line3d6, num_outliers):

@@ -20,18 +20,8 @@ from . import _capi
 __all__ = ["Point2d", "Junction", "PL_Bipartite2dConfig", "PL_Bipartite2d", "compute_2d_bipartites",
            "compute_junctions", "lines2d_array", "timers"]
 
-_contexts = {}
-
-
-def _context(device=0):
-    ctx = _contexts.get(device)
-    if ctx is None:
-        ctx = _contexts[device] = _capi.Context(device=device)
-    return ctx
-
-
-def _p(a, t=C.c_double):
-    return a.ctypes.data_as(C.POINTER(t))
+_context = _capi.per_device_contexts()
+_p = _capi.ptr
 
 
 def timers(device=0):

@@ -26,18 +26,8 @@ from .structures import lines2d_array
 __all__ = ["VPResult", "BaseVPDetectorConfig", "BaseVPDetectorOptions", "DefaultVPDetectorOptions", "JLinkageConfig",
            "JLinkage", "get_vp_detector", "detect_vps", "detect_vps_host", "timers"]
 
-_contexts = {}
-
-
-def _context(device=0):
-    ctx = _contexts.get(device)
-    if ctx is None:
-        ctx = _contexts[device] = _capi.Context(device=device)
-    return ctx
-
-
-def _p(a, t=C.c_double):
-    return a.ctypes.data_as(C.POINTER(t))
+_context = _capi.per_device_contexts()
+_p = _capi.ptr
 
 
 class VPResult:
