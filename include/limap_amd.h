@@ -654,6 +654,47 @@ int lt_fn_refine_explog(int which, int64_t n, const double *x, double *out);
 int lt_fn_refine_minimal(const double line6[6], double params6[6]);
 int lt_fn_refine_infinite(const double params6[6], double dm6[6]);
 
+/* ---- limap.pointsfm: the visual neighbours of every image and the robust ranges of the point cloud -- step [A] of
+ * limap.runners.line_triangulation, `compute_metainfos` (pointsfm/functions.py:20-55) over SfmModel
+ * (pointsfm/sfm_model.{h,cc}, colmap::mvs::Model).  DESIGN.md section 21 is the definition: shared points and the 75th
+ * percentile of the triangulation angles per image pair, the gate by min_triangulation_angle, the score of `kind`
+ * (0 overlap: GetMaxOverlapImages, 1 IoU: GetMaxIoUImages, 2 Dice: GetMaxDiceCoeffImages), the first num_images partners
+ * by (score descending, image index ascending).
+ * The model as arrays: image m (an index, 0 .. n_img - 1; n_img <= 65535) has R9 (row-major) and T3 as the float32
+ * values upstream stores; point p has xyz (float32) and the track track_img[track_off[p] .. track_off[p + 1]) of image
+ * indices (an index may repeat).  LT_ERR_ARGUMENT before any launch for: an index outside [0, n_img) (message starts
+ * with "unknown": upstream's std::out_of_range), non-finite values, offsets that do not start at 0 or decrease, kind
+ * outside 0 .. 2, num_images < 0; and for a model whose E = sum L (L - 1) / 2 pair instances (track length L) need more
+ * key memory than the budget of 32 GiB (16 E bytes and the sort's scratch): the message names E and the budget.
+ * The result stays in the context; n_neighbors / n_pairs (may be NULL) receive the sizes lt_sfm_get /
+ * lt_sfm_get_pairs need. */
+int lt_sfm_neighbors(lt_ctx *ctx, int n_img, const float *R9, const float *T3, int64_t n_pts, const float *xyz,
+                     const int64_t *track_off, const int32_t *track_img, int kind, int64_t num_images,
+                     double min_triangulation_angle, int64_t *n_neighbors, int64_t *n_pairs);
+/* of the last lt_sfm_neighbors (any pointer may be NULL): nb_off[n_img + 1], nb = neighbour image indices in order */
+int lt_sfm_get(lt_ctx *ctx, int64_t *nb_off, int32_t *nb);
+/* the image pairs that share a point, ascending in (i, j), i < j: ij[2 k], ij[2 k + 1]; shared = ComputeSharedPoints;
+ * angle = the percentile angle (radians, float32) the gate tests */
+int lt_sfm_get_pairs(lt_ctx *ctx, int32_t *ij, int32_t *shared, float *angle);
+/* of the last lt_sfm_neighbors: host ms of [0] validation, tables and upload, [1] the device stage, [2] download; device
+ * ms (HIP events) of [3] k_sfm_pairs, [4] the key sort, [5] k_sfm_segments, [6] partner lists, selection and
+ * compaction; [7] launches of k_sfm_segments (2: the first had too little room for the pair records) */
+int lt_sfm_get_timers(lt_ctx *ctx, double out[8]);
+/* The same definition on the host, no context and no device: the same inline functions, OpenMP over n_threads threads
+ * (0: the default).  The result stays with the calling thread until its next call: lt_fn_sfm_host_get copies it out
+ * (arrays as lt_sfm_get and lt_sfm_get_pairs), lt_fn_sfm_host_error is the message of the thread's last
+ * lt_fn_sfm_neighbors_host / lt_fn_sfm_ranges that returned LT_ERR_ARGUMENT ("" after a success). */
+int lt_fn_sfm_neighbors_host(int n_img, const float *R9, const float *T3, int64_t n_pts, const float *xyz,
+                             const int64_t *track_off, const int32_t *track_img, int kind, int64_t num_images,
+                             double min_triangulation_angle, int n_threads, int64_t *n_neighbors, int64_t *n_pairs);
+int lt_fn_sfm_host_get(int64_t *nb_off, int32_t *nb, int32_t *ij, int32_t *shared, float *angle);
+const char *lt_fn_sfm_host_error(void);
+/* SfmModel::ComputeRanges(range_robust, k_stretch): per axis, in float32 as get_robust_range writes it.  Host work.
+ * LT_ERR_ARGUMENT where upstream is undefined: no points, an index float(n) * float(p) outside [0, n), a non-finite
+ * coordinate. */
+int lt_fn_sfm_ranges(int64_t n_pts, const float *xyz, double range_lo, double range_hi, double k_stretch, double lo[3],
+                     double hi[3]);
+
 /* Counters of the last device run: [0] connections tested, [1] candidates, [2] ordered candidate
  * pairs swept by the scoring kernel (sum n_tris^2), [3] valid edges, [4] graph nodes,
  * [5] graph edges, [6] tracks, [7] nodes. */

@@ -42,6 +42,8 @@ EXPORTED_SYMBOLS = [
     "lt_refine_config_default", "lt_refine_arrays", "lt_refine_tracks", "lt_refine_num", "lt_refine_get",
     "lt_refine_get_timers", "lt_fn_refine_host", "lt_fn_refine_eval", "lt_fn_refine_explog", "lt_fn_refine_minimal",
     "lt_fn_refine_infinite", "lt_fn_refine_host_error", "lt_fn_refine_cut",
+    "lt_sfm_neighbors", "lt_sfm_get", "lt_sfm_get_pairs", "lt_sfm_get_timers", "lt_fn_sfm_neighbors_host",
+    "lt_fn_sfm_host_get", "lt_fn_sfm_host_error", "lt_fn_sfm_ranges",
 ]
 
 
@@ -326,6 +328,16 @@ def load_library():
     L.lt_fn_refine_host_error.argtypes = []
     L.lt_fn_refine_host_error.restype = C.c_char_p
     L.lt_fn_refine_cut.argtypes = [C.c_int64, dp, dp, C.c_int, dp]
+    L.lt_sfm_neighbors.argtypes = [vp, C.c_int, fp, fp, C.c_int64, fp, i64p, i32p, C.c_int, C.c_int64, C.c_double, i64p, i64p]
+    L.lt_sfm_get.argtypes = [vp, i64p, i32p]
+    L.lt_sfm_get_pairs.argtypes = [vp, i32p, i32p, fp]
+    L.lt_sfm_get_timers.argtypes = [vp, dp]
+    L.lt_fn_sfm_neighbors_host.argtypes = [C.c_int, fp, fp, C.c_int64, fp, i64p, i32p, C.c_int, C.c_int64, C.c_double,
+                                           C.c_int, i64p, i64p]
+    L.lt_fn_sfm_host_get.argtypes = [i64p, i32p, i32p, i32p, fp]
+    L.lt_fn_sfm_host_error.argtypes = []
+    L.lt_fn_sfm_host_error.restype = C.c_char_p
+    L.lt_fn_sfm_ranges.argtypes = [C.c_int64, fp, C.c_double, C.c_double, C.c_double, dp, dp]
     _lib = L
     return L
 

@@ -237,6 +237,15 @@ struct RefineState {  // line refinement (lt_refine.cpp): the result of the last
   DevBuf d_k, d_q, d_t, d_cam, d_l2d, d_l3d, d_tab, d_line, d_tracks, d_out;
 };
 
+struct SfmState {  // visual neighbours (lt_sfm.cpp): the result of the last lt_sfm_neighbors
+  double timers[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // lt_sfm_get_timers
+  std::vector<long long> nb_off;                // per image its neighbours (image indices)
+  std::vector<int> nb;
+  long long n_pairs = 0;                        // pair records the call left in d_pairs (behind its 16-byte head)
+  DevBuf d_pair_off, d_track_off, d_track_img, d_centres, d_xyz, d_npts, d_keys, d_keys2, d_tmp, d_pairs, d_cnt, d_off,
+      d_part, d_score, d_nb, d_nb_cnt, d_nb_off, d_dense;
+};
+
 }  // namespace lt_host
 
 using lt_host::DevBuf;
@@ -460,6 +469,7 @@ struct lt_ctx {
   lt_host::MatchState mt;
   lt_host::VpState vp;
   lt_host::RefineState rf;
+  lt_host::SfmState sf;
 };
 
 #define HIPCHK(ctx, call)                                                                  \

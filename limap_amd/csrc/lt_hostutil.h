@@ -1,5 +1,5 @@
 // lt_hostutil.h -- the host toolkit of the modules around the triangulation core (lt_merge, lt_fit, lt_eval, lt_bpt,
-// lt_match, lt_vp, lt_refine, the remerge of lt_tracks): stream synchronisation, HIP event timing, transfers of host
+// lt_match, lt_vp, lt_refine, lt_sfm, the remerge of lt_tracks): stream synchronisation, HIP event timing, transfers of host
 // vectors, input checks and the counted-output launch loop.  A new module uses these, it does not bring its own
 // (DESIGN §20).  Included from lt_host.h.
 #pragma once
@@ -66,6 +66,12 @@ int download(lt_ctx *ctx, std::vector<T> &dst, const void *src, size_t n) {
 }
 
 inline bool all_finite(const double *v, long long n) {
+  for (long long k = 0; k < n; ++k)
+    if (!std::isfinite(v[k])) return false;
+  return true;
+}
+
+inline bool all_finite(const float *v, long long n) {
   for (long long k = 0; k < n; ++k)
     if (!std::isfinite(v[k])) return false;
   return true;
