@@ -290,6 +290,25 @@ int lt_fn_track_connect(lt_ctx *ctx, int64_t n_tracks, const double *line7, cons
                         int64_t capacity0, uint64_t *edges_out, int64_t edges_cap, int64_t *n_unique, int64_t *n_raw,
                         int32_t *attempts);
 
+/* The per-connection decisions of candidate generation alone, for tests: n connections, each conn30 = seg1[4] cam1[11]
+ * seg2[4] cam2[11] (cam = fx fy cx cy, qvec[4], tvec[3]), against the thresholds, bands and ranges of this context -- the
+ * generation configuration a job of the context would run with.  One lane per connection builds the camera, segment
+ * and pair records as a job does and writes, with plain stores,
+ *   out10[10 i + 0] fast      the three-way stage-A gate (0 certainly skipped, 1 certainly passed, 2 undecided); the
+ *                             LT_TEST_NO_FAST_GATES switch is ignored for this entry alone
+ *   out10[10 i + 1] exact     the reference-exact stage-A gates
+ *   out10[10 i + 2] tri_ok    the triangulation of stage B succeeded (the endpoint form under
+ *                             use_endpoints_triangulation)
+ *   out10[10 i + 3 .. 4]      the three-way sensitivity test in view 1 / view 2 (1 greater, 0 not, 2 undecided)
+ *   out10[10 i + 5 .. 6]      the reference-exact `sensitivity > threshold` in view 1 / view 2
+ *   out10[10 i + 7]           the stage-B pre-test (false: stage B certainly fails)
+ *   out10[10 i + 8]           stage B as a whole
+ *   out10[10 i + 9]           0
+ * (entries 3 .. 6 are -1 where tri_ok is 0; under LT_TEST_NO_FAST_GATES the context's bands of the sensitivity test are
+ * open, as in a job, and entries 3 .. 4 are 2 throughout), and iou_bits[i] = the 64 bits of compute_epipolar_IoU.  n in [0, 2^24];
+ * arguments are checked before anything is launched; out10 holds 10 n and iou_bits n entries. */
+int lt_fn_gate_outcomes(lt_ctx *ctx, int64_t n, const double *conn30, int32_t *out10, uint64_t *iou_bits);
+
 /* ---- limap.merging.merging / MergeToLineTracks (merging/merging.py:6-21, merging/merging.cc:347-511): the merge of
  * one fitted 3D segment per 2D segment (runners/line_fitnmerge.py) into line tracks.  The context is initialised
  * (lt_init / lt_init_device, the images in any order) with the cameras and the 2D segments.  The merge reads the 2D

@@ -24,7 +24,7 @@ EXPORTED_SYMBOLS = [
     "lt_num_tracks", "lt_num_track_members", "lt_get_tracks", "lt_image_results_size",
     "lt_export_image_results", "lt_import_image_results", "lt_export_images_size", "lt_export_images_packed", "lt_import_images_packed", "lt_shard_node_bytes", "lt_shard_count", "lt_shard_build", "lt_shard_export", "lt_shard_import", "lt_ts_from_ctx", "lt_ts_create", "lt_ts_destroy",
     "lt_ts_num_tracks", "lt_ts_num_members", "lt_ts_get", "lt_ts_filter_by_reprojection",
-    "lt_ts_filter_by_sensitivity", "lt_ts_filter_by_overlap", "lt_ts_remerge_once", "lt_fn_track_connect", "lt_merge_to_tracks", "lt_merge_graph_size", "lt_merge_graph_get", "lt_merge_get_timers", "lt_get_stats", "lt_get_timers", "lt_get_timer_sums", "lt_run_device_async", "lt_sync",
+    "lt_ts_filter_by_sensitivity", "lt_ts_filter_by_overlap", "lt_ts_remerge_once", "lt_fn_track_connect", "lt_fn_gate_outcomes", "lt_merge_to_tracks", "lt_merge_graph_size", "lt_merge_graph_get", "lt_merge_get_timers", "lt_get_stats", "lt_get_timers", "lt_get_timer_sums", "lt_run_device_async", "lt_sync",
     "lt_release_cached_memory", "lt_reserve_host",
     "lt_fn_get_normal_direction", "lt_fn_get_direction_from_vp", "lt_fn_triangulate_point",
     "lt_fn_triangulate_line_with_direction", "lt_fn_triangulate_line_with_one_point", "lt_fn_compute_fundamental_matrix", "lt_fn_compute_epipolar_IoU",
@@ -244,6 +244,7 @@ def load_library():
     L.lt_ts_remerge_once.argtypes = [vp, vp, C.POINTER(LtConfig), C.c_int]
     L.lt_fn_track_connect.argtypes = [vp, C.c_int64, dp, u8p, C.POINTER(LtConfig), C.c_int64, C.POINTER(C.c_uint64),
                                       C.c_int64, i64p, i64p, i32p]
+    L.lt_fn_gate_outcomes.argtypes = [vp, C.c_int64, dp, i32p, C.POINTER(C.c_uint64)]
     L.lt_merge_to_tracks.argtypes = [vp, i64p, dp, i64p, i32p, C.POINTER(LtConfig), C.c_double, C.POINTER(vp)]
     L.lt_merge_graph_size.argtypes = [vp, i64p, i64p]
     L.lt_merge_graph_get.argtypes = [vp, i32p, i32p, i32p, i32p, dp]
@@ -743,6 +744,21 @@ class Context:
                                                ptr(f64(seg2), C.c_double), ptr(f64(cam2), C.c_double),
                                                int(bool(by_endpoints)), ptr(out, C.c_double)))
         return out
+
+    GATE_OUTCOME_KEYS = ["fast", "exact", "tri_ok", "sens3_1", "sens3_2", "sens_gt_1", "sens_gt_2", "pretest", "finish"]
+
+    def fn_gate_outcomes(self, conn30):
+        """The per-connection decisions of candidate generation (lt_fn_gate_outcomes) for (n, 30) connections
+        seg1[4] cam1[11] seg2[4] cam2[11], against this context's configuration and ranges: dict of (n,) int32 arrays
+        (GATE_OUTCOME_KEYS) and "iou_bits" (n,) uint64."""
+        conn = f64(conn30).reshape(-1, 30)
+        n = len(conn)
+        out = np.zeros((max(n, 1), 10), np.int32)
+        bits = np.zeros(max(n, 1), np.uint64)
+        self.chk(self.L.lt_fn_gate_outcomes(self.h, n, ptr(conn, C.c_double), ptr(out, C.c_int32), ptr(bits, C.c_uint64)))
+        res = {k: out[:n, j].copy() for j, k in enumerate(self.GATE_OUTCOME_KEYS)}
+        res["iou_bits"] = bits[:n]
+        return res
 
 
 def per_device_contexts():

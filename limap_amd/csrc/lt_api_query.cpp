@@ -504,6 +504,28 @@ int lt_fn_triangulate_line_with_one_point(lt_ctx *ctx, const double seg1[4], con
   return LT_OK;
 }
 
+// The per-connection decisions of candidate generation on plain arrays (include/limap_amd.h): k_fn_gate_outcomes with the
+// generation configuration a job of this context would run with (make_gen: its thresholds, bands and ranges).
+int lt_fn_gate_outcomes(lt_ctx *ctx, int64_t n, const double *conn30, int32_t *out10, uint64_t *iou_bits) {
+  if (!ctx) return LT_ERR_ARGUMENT;
+  if (n < 0 || n > (1ll << 24) || (n > 0 && (!conn30 || !out10 || !iou_bits)))
+    return fail(ctx, LT_ERR_ARGUMENT, "lt_fn_gate_outcomes: bad argument");
+  if (n == 0) return LT_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const GenCfg gcfg = make_gen(ctx);
+  const size_t nn = (size_t)n;
+  DevBuf din, dout, dbits;
+  ENSURE(ctx, din, nn * 30 * 8); ENSURE(ctx, dout, nn * 10 * 4); ENSURE(ctx, dbits, nn * 8);
+  HIPCHK(ctx, hipMemcpyAsync(din.p, conn30, nn * 30 * 8, hipMemcpyHostToDevice, ctx->stream));
+  launch_fn_gate_outcomes(ctx->stream, (int)n, din.as<double>(), gcfg, dout.as<int>(), dbits.as<unsigned long long>());
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipMemcpyAsync(out10, dout.p, nn * 10 * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(iou_bits, dbits.p, nn * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  din.release(); dout.release(); dbits.release();
+  return LT_OK;
+}
+
 int lt_fn_pack_match_rows(const int32_t *rows, int64_t n, uint32_t *out, uint32_t stats[3], int level) {
   if (n < 0 || (n > 0 && (!rows || !out)) || !stats) return LT_ERR_ARGUMENT;
   const lt::RowStats rs = lt::pack_rows(rows, n, out, level);

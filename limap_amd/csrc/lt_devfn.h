@@ -268,52 +268,12 @@ static __device__ __forceinline__ GateEpi gate3_epi(const double *F, double px, 
   return e;
 }
 
-// q1 = squared length of l1
-static __device__ __forceinline__ int gate3_core(const GenCfg &cfg, double q1, double rs1x, double rs1y, double rs1z,
-                                                 double re1x, double re1y, double re1z, double n2x, double n2y,
-                                                 double n2z, double lcx, double lcy, double P, double Q, double w1,
-                                                 double sv, double q2, const GateEpi &ea, const GateEpi &eb) {
-  bool rej = (q1 <= cfg.len_lo2) | (q2 <= cfg.len_lo2) | (cfg.disable_algebraic != 0);
-  bool und = !(q1 > cfg.len_hi2) | !(q2 > cfg.len_hi2);
-  const double as = fabs(__builtin_fma(n2x, rs1x, __builtin_fma(n2y, rs1y, n2z * rs1z)));
-  const double ae = fabs(__builtin_fma(n2x, re1x, __builtin_fma(n2y, re1y, n2z * re1z)));
-  rej |= (as < cfg.sin_lo) | (ae < cfg.sin_lo);
-  und |= !(as > cfg.sin_hi) | !(ae > cfg.sin_hi);
-  double cv[2], ce[2];
-  bool well = q2 > 0.0;
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const GateEpi &e = k == 0 ? ea : eb;
-    const double ax = e.ax, ay = e.ay, az = e.az, n2a = e.n2a, na = e.na;
-    const double t1 = lcx * ay, t2 = lcy * ax;
-    const double D = __builtin_fma(kEps, na, t1 - t2);
-    const double m0 = az * w1, m1 = ax * P, m2 = ay * Q, m3 = D * sv;
-    const double numer = ((m0 + m1) + m2) - m3;
-    const double Dq = D * q2;
-    const double r = fast_rcp(Dq);
-    // conditioning: no cancellation in D beyond 1e4, the float sqrt stays far below the margin, no
-    // overflow / underflow games
-    well = well & (fabs(D) > 1e-4 * (fabs(t1) + fabs(t2))) & (fabs(D) > 1e-9 * na) & (n2a > 1e-30) &
-           (n2a < 1e30) & (fabs(Dq) > 1e-280) & (fabs(Dq) < 1e280);
-    cv[k] = numer * r;
-    ce[k] = (((fabs(m0) + fabs(m1)) + fabs(m2)) + fabs(m3)) * fabs(r);
-  }
-  const double cerr = ce[0] + ce[1];
-  // v_min/v_max drop NaN operands: harmless here, a NaN can only come from an infinite term of
-  // `numer`, which makes cerr (hence the margin) infinite or NaN and the outcome "undecided"
-  const double c1v = __builtin_fmin(cv[0], cv[1]), c2v = __builtin_fmax(cv[0], cv[1]);
-  const double num = __builtin_fmin(c2v, 1.0) - __builtin_fmax(c1v, 0.0);
-  const double den = __builtin_fmax(c2v, 1.0) - __builtin_fmin(c1v, 0.0);
-  const double delta = num - cfg.iou_th * den;
-  const double margin = __builtin_fma(1e-12, cerr, 1e-7 * (1.0 + fabs(c1v) + fabs(c2v)) * (1.0 + fabs(cfg.iou_th)));
-  rej |= well & (delta < -margin);
-  und |= !(well & (delta > margin));
-  if (cfg.force_undecided) return 2;  // test switch (LT_TEST_NO_FAST_GATES)
-  return rej ? 0 : (und ? 2 : 1);
-}
-
-// The same decision with fewer instructions (k_gates_ln): the numerator and its cancellation bound as FMA chains (this is
-// not reference arithmetic -- see gate3_core -- and a fused product only tightens the roundings the margin covers).
+// q1 = squared length of l1.  The numerator and its cancellation bound are FMA chains (this is not reference arithmetic
+// -- see above -- and a fused product only tightens the roundings the margin covers).
+//   * conditioning (`well`): no cancellation in D beyond 1e4, the float sqrt stays far below the margin (|D| > 1e-9 |a|),
+//     no overflow / underflow games; a connection that is not `well` is never decided by the IoU.
+//   * v_min / v_max drop NaN operands: harmless here, a NaN can only come from an infinite term of `numer`, which makes
+//     cerr (hence the margin) infinite or NaN and the outcome "undecided".
 static __device__ __forceinline__ int gate3_core_fma(const GenCfg &cfg, double q1, double rs1x, double rs1y, double rs1z,
                                                      double re1x, double re1y, double re1z, double n2x, double n2y,
                                                      double n2z, double lcx, double lcy, double P, double Q, double w1,

@@ -27,6 +27,8 @@
 
 namespace lt {
 void launch_fn_query(hipStream_t st, const double *in30, int by_endpoints, double *out32);
+void launch_fn_gate_outcomes(hipStream_t st, int n, const double *conn30, const GenCfg &cfg, int *out10,
+                             unsigned long long *iou_bits);
 // lt_kernels_v2.hip
 int gen_slots(long long max_rows);
 int gen_groups(long long max_rows);

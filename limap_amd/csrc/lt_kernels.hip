@@ -1389,4 +1389,63 @@ void launch_fn_query(hipStream_t st, const double *in30, int by_endpoints, doubl
   hipLaunchKernelGGL(k_fn_query, dim3(1), dim3(64), 0, st, in30, by_endpoints, out32);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The per-connection decisions of candidate generation on plain arrays (lt_fn_gate_outcomes, a test entry): the batched
+// sibling of k_fn_query.  One lane per connection, conn30 = seg1[4] cam1[11] seg2[4] cam2[11]; the records are built
+// as a job builds them and every decision function of lt_devfn.h is evaluated on them.  Plain per-lane stores only.
+// ---------------------------------------------------------------------------------------------
+__global__ void k_fn_gate_outcomes(int n, const double *__restrict__ in, GenCfg cfg, int *__restrict__ out,
+                                   unsigned long long *__restrict__ iou_bits) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double *p = in + 30 * (size_t)i;
+  Cam c1, c2;
+  cam_build(p + 4, p + 8, p + 12, &c1);
+  cam_build(p + 19, p + 23, p + 27, &c2);
+  Seg s1, s2;
+  seg_build(c1, p[0], p[1], p[2], p[3], &s1);
+  seg_build(c2, p[15], p[16], p[17], p[18], &s2);
+  SegGate gg;
+  seg_gate_build(s2, &gg);
+  PairRec pr;
+  pair_build(c1, c2, &pr);
+  int *o = out + 10 * (size_t)i;
+  GenCfg fastcfg = cfg;
+  fastcfg.force_undecided = 0;
+  o[0] = gate3(fastcfg, s1.x1, s1.y1, s1.x2, s1.y2, s1.rs[0], s1.rs[1], s1.rs[2], s1.re[0], s1.re[1], s1.re[2], gg.n[0],
+               gg.n[1], gg.n[2], gg.lcx, gg.lcy, gg.P, gg.Q, gg.w1, gg.sv, gg.q2, pr.F);
+  o[1] = gen_gates(cfg, s1, s2, pr.F) ? 1 : 0;
+  iou_bits[i] = (unsigned long long)__double_as_longlong(epipolar_iou(s1, s2, pr.F));
+  d3 ps, pe;
+  bool ok;
+  if (!cfg.use_endpoints) {
+    double zs, ze, d21, d22;
+    ok = tri_line(c1, c2, s1, s2, pr.B, &ps, &pe, &zs, &ze, &d21, &d22);
+  } else {
+    d3 r1s = mk3(s1.rs[0], s1.rs[1], s1.rs[2]), r1e = mk3(s1.re[0], s1.re[1], s1.re[2]);
+    d3 c2s = mk3(s2.rs[0], s2.rs[1], s2.rs[2]), c2e = mk3(s2.re[0], s2.re[1], s2.re[2]);
+    ok = tri_point(c1, r1s, c2, c2s, &ps) && tri_point(c1, r1e, c2, c2e, &pe);
+  }
+  o[2] = ok ? 1 : 0;
+  if (ok) {
+    const d3 dir3 = unit(sub(pe, ps));
+    o[3] = sensitivity3(cfg, c1, ps, pe, dir3);
+    o[4] = sensitivity3(cfg, c2, ps, pe, dir3);
+    o[5] = sensitivity_gt(cfg, c1, ps, pe, dir3) ? 1 : 0;
+    o[6] = sensitivity_gt(cfg, c2, ps, pe, dir3) ? 1 : 0;
+  } else {
+    o[3] = o[4] = o[5] = o[6] = -1;
+  }
+  GenOut go;
+  o[7] = gen_pretest(cfg, c1, c2, s1, s2, pr.B) ? 1 : 0;
+  o[8] = gen_finish(cfg, c1, c2, s1, s2, pr.B, &go) ? 1 : 0;
+  o[9] = 0;
+}
+
+void launch_fn_gate_outcomes(hipStream_t st, int n, const double *conn30, const GenCfg &cfg, int *out10,
+                             unsigned long long *iou_bits) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_fn_gate_outcomes, dim3(nblk(n, 64)), dim3(64), 0, st, n, conn30, cfg, out10, iou_bits);
+}
+
 }  // namespace lt

@@ -87,6 +87,11 @@ def _rot_to_quat(R):
     return q / np.linalg.norm(q)
 
 
+def rot_to_quat(R):
+    """Rotation matrix (world -> cam) -> unit quaternion (w, x, y, z) with w >= 0: the inverse of quat_to_rot."""
+    return _rot_to_quat(R)
+
+
 def quat_to_rot(q):
     w, x, y, z = np.asarray(q, float) / np.linalg.norm(q)
     return np.array([

@@ -20,7 +20,7 @@ def test_header_declares_expected_surface():
     for must in ("lt_create", "lt_init", "lt_triangulate_image", "lt_triangulate_image_exhaustive",
                  "lt_compute_tracks", "lt_get_tracks", "lt_set_ranges", "lt_get_best", "lt_vp_detect",
                  "lt_fn_vp_cluster_host", "lt_vp_cluster_sets", "lt_bpt_junctions", "lt_fn_bpt_grid_keys",
-                 "lt_fn_bpt_close_pairs_host", "lt_fn_track_connect"):
+                 "lt_fn_bpt_close_pairs_host", "lt_fn_track_connect", "lt_fn_gate_outcomes"):
         assert must in syms
 
 
