@@ -714,6 +714,58 @@ const char *lt_fn_sfm_host_error(void);
 int lt_fn_sfm_ranges(int64_t n_pts, const float *xyz, double range_lo, double range_hi, double k_stretch, double lo[3],
                      double hi[3]);
 
+/* ---- limap.undistortion: images and points of distorted COLMAP cameras brought to pinhole cameras -- the step
+ * limap.runners.functions.undistort_images puts in front of line_triangulation (undistortion/undistort.{cc,py} over
+ * COLMAP's UndistortImage).  DESIGN.md section 22 is the definition: the camera models, the iterative undistortion
+ * (Newton, central differences, at most 100 updates), the warp with bilinear interpolation, the in-range test on the
+ * doubles and the rounding rule.  Everything is FP64; the device and the host path agree bit for bit. */
+typedef struct lt_undist_camera {
+  int32_t model;      /* COLMAP model id: 0 SIMPLE_PINHOLE, 1 PINHOLE, 2 SIMPLE_RADIAL, 3 RADIAL, 4 OPENCV, 6 FULL_OPENCV */
+  int32_t n_params;   /* 3, 4, 4, 5, 8, 12 */
+  double params[12];  /* in COLMAP's order */
+} lt_undist_camera;
+typedef struct lt_undist_image {
+  const void *src;    /* uint8, rows of src_w * channels bytes, src_stride bytes apart */
+  void *dst;          /* uint8, rows of dst_w * channels bytes, dst_stride bytes apart */
+  int64_t src_stride, dst_stride;
+  int32_t src_w, src_h, dst_w, dst_h;
+  int32_t channels;   /* 1, 3 or 4 */
+  int32_t src_cam, dst_cam; /* rows of the camera table: the distorted camera, the pinhole camera of the target */
+  int32_t on_device;  /* src and dst are device memory, read and written in place on the context's stream */
+} lt_undist_image;
+/* One launch set over a whole batch of images, which may differ in size, channels and camera.  Host images go through
+ * one upload and one download; a batch is either all host or all device.  Returns after the stream has finished.
+ * LT_ERR_ARGUMENT before any launch for: a model that is not built or a wrong parameter count, non-finite parameters, a
+ * focal length that is 0, a size below 1, a channel count outside {1, 3, 4}, a stride shorter than a row, a camera
+ * index outside the table, a target camera that is not a pinhole model, a mixed batch. */
+int lt_undist_warp(lt_ctx *ctx, int n_cam, const lt_undist_camera *cams, int n_img, const lt_undist_image *imgs);
+/* UndistortPoint for n points (host arrays): point i goes through CamFromImg of camera cam_src[i] and ImgFromCam of camera
+ * cam_dst[i].  out_xy[2 n]; status[n] is 0, or 1 with the point the canonical quiet NaN (a singular Jacobian, an
+ * overflow); iters[n] is the number of Newton updates (0 for a pinhole source). */
+int lt_undist_points(lt_ctx *ctx, int n_cam, const lt_undist_camera *cams, int64_t n, const double *xy,
+                     const int32_t *cam_src, const int32_t *cam_dst, double *out_xy, int32_t *status, int32_t *iters);
+/* of the last lt_undist_warp / lt_undist_points: host ms of [0] validation, packing and upload, [2] download and
+ * unpacking; [1] device ms (HIP events) of the kernel; [3] its work units (runs of 4 target pixels) or points */
+int lt_undist_get_timers(lt_ctx *ctx, double out[4]);
+/* the yardstick of the warp's measurement (tools/time_undist.py): device ms of a copy kernel that moves `bytes` bytes,
+ * 16 per lane, between two buffers of the context */
+int lt_undist_copy_yardstick(lt_ctx *ctx, int64_t bytes, double *ms);
+/* The same definition on the host, no context and no device: the same inline functions, OpenMP over n_threads threads
+ * (0: the default).  lt_fn_undist_host_error is the message of the calling thread's last lt_fn_undist_* call that
+ * returned LT_ERR_ARGUMENT ("" after a success). */
+int lt_fn_undist_warp_host(int n_cam, const lt_undist_camera *cams, int n_img, const lt_undist_image *imgs,
+                           int n_threads);
+int lt_fn_undist_points_host(int n_cam, const lt_undist_camera *cams, int64_t n, const double *xy,
+                             const int32_t *cam_src, const int32_t *cam_dst, double *out_xy, int32_t *status,
+                             int32_t *iters, int n_threads);
+const char *lt_fn_undist_host_error(void);
+/* The scale rule of UndistortCamera for a camera of size w x h with principal point (cx, cy): ext = the extremes of
+ * the undistorted border {left min x, left max x, right min x, right max x, top min y, top max y, bottom min y, bottom
+ * max y}; out = {new_w, new_h, new_cx, new_cy}.  LT_ERR_ARGUMENT for COLMAP's range checks of the options and for a
+ * border that is not finite. */
+int lt_fn_undist_scale(int32_t w, int32_t h, double cx, double cy, const double ext[8], double blank_pixels,
+                       double min_scale, double max_scale, double out[4]);
+
 /* Counters of the last device run: [0] connections tested, [1] candidates, [2] ordered candidate
  * pairs swept by the scoring kernel (sum n_tris^2), [3] valid edges, [4] graph nodes,
  * [5] graph edges, [6] tracks, [7] nodes. */

@@ -44,6 +44,8 @@ EXPORTED_SYMBOLS = [
     "lt_fn_refine_infinite", "lt_fn_refine_host_error", "lt_fn_refine_cut",
     "lt_sfm_neighbors", "lt_sfm_get", "lt_sfm_get_pairs", "lt_sfm_get_timers", "lt_fn_sfm_neighbors_host",
     "lt_fn_sfm_host_get", "lt_fn_sfm_host_error", "lt_fn_sfm_ranges",
+    "lt_undist_warp", "lt_undist_points", "lt_undist_get_timers", "lt_undist_copy_yardstick", "lt_fn_undist_warp_host",
+    "lt_fn_undist_points_host", "lt_fn_undist_host_error", "lt_fn_undist_scale",
 ]
 
 
@@ -156,6 +158,16 @@ class LtRefineConfig(C.Structure):
     _fields_ = [("geometric_alpha", C.c_double), ("min_num_images", C.c_int32), ("num_outliers_aggregator", C.c_int32),
                 ("num_outliers_aggregate", C.c_int32), ("max_num_iterations", C.c_int32), ("constant_line", C.c_int32),
                 ("pad_", C.c_int32)]
+
+
+class LtUndistCamera(C.Structure):
+    _fields_ = [("model", C.c_int32), ("n_params", C.c_int32), ("params", C.c_double * 12)]
+
+
+class LtUndistImage(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("src_stride", C.c_int64), ("dst_stride", C.c_int64),
+                ("src_w", C.c_int32), ("src_h", C.c_int32), ("dst_w", C.c_int32), ("dst_h", C.c_int32),
+                ("channels", C.c_int32), ("src_cam", C.c_int32), ("dst_cam", C.c_int32), ("on_device", C.c_int32)]
 
 
 def load_library():
@@ -339,6 +351,17 @@ def load_library():
     L.lt_fn_sfm_host_error.argtypes = []
     L.lt_fn_sfm_host_error.restype = C.c_char_p
     L.lt_fn_sfm_ranges.argtypes = [C.c_int64, fp, C.c_double, C.c_double, C.c_double, dp, dp]
+    ucp, uip = C.POINTER(LtUndistCamera), C.POINTER(LtUndistImage)
+    L.lt_undist_warp.argtypes = [vp, C.c_int, ucp, C.c_int, uip]
+    L.lt_undist_points.argtypes = [vp, C.c_int, ucp, C.c_int64, dp, i32p, i32p, dp, i32p, i32p]
+    L.lt_undist_get_timers.argtypes = [vp, dp]
+    L.lt_undist_copy_yardstick.argtypes = [vp, C.c_int64, dp]
+    L.lt_fn_undist_warp_host.argtypes = [C.c_int, ucp, C.c_int, uip, C.c_int]
+    L.lt_fn_undist_points_host.argtypes = [C.c_int, ucp, C.c_int64, dp, i32p, i32p, dp, i32p, i32p, C.c_int]
+    L.lt_fn_undist_host_error.argtypes = []
+    L.lt_fn_undist_host_error.restype = C.c_char_p
+    L.lt_fn_undist_scale.argtypes = [C.c_int32, C.c_int32, C.c_double, C.c_double, dp, C.c_double, C.c_double,
+                                     C.c_double, dp]
     _lib = L
     return L
 

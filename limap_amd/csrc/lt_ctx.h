@@ -246,6 +246,12 @@ struct SfmState {  // visual neighbours (lt_sfm.cpp): the result of the last lt_
       d_part, d_score, d_nb, d_nb_cnt, d_nb_off, d_dense;
 };
 
+struct UdState {  // undistortion (lt_undist.cpp): staging and timers of the last lt_undist_warp / lt_undist_points
+  double timers[4] = {0, 0, 0, 0};    // lt_undist_get_timers
+  std::vector<unsigned char> h_in, h_out;  // host images of a batch, packed: one upload, one download
+  DevBuf d_cams, d_imgs, d_src, d_dst, d_xy, d_idx, d_out, d_stat;
+};
+
 }  // namespace lt_host
 
 using lt_host::DevBuf;
@@ -470,6 +476,7 @@ struct lt_ctx {
   lt_host::VpState vp;
   lt_host::RefineState rf;
   lt_host::SfmState sf;
+  lt_host::UdState ud;
 };
 
 #define HIPCHK(ctx, call)                                                                  \
