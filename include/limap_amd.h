@@ -636,7 +636,8 @@ typedef struct lt_refine_config {
 } lt_refine_config;
 void lt_refine_config_default(lt_refine_config *cfg);
 /* Termination codes: 0 max_num_iterations, 1 radius below 1e-32, 2 zero gradient, 3 non-positive or non-finite pivot,
- * 4 non-positive or non-finite model decrease, 5 held constant.
+ * 4 non-positive or non-finite model decrease, 5 held constant, 6 evaluation failed at the initial point (only with
+ * the heatmap term, below).
  * Tracks as CSR: track n owns the supports [off[n], off[n + 1]) in the order of its lists; line6 = start, end of
  * track.line; img = image_id_list; line2d4 = line2d_list; line3d6 = start, end of line3d_list.  Cameras: n_img ids (any
  * order, distinct) with kvec4 (fx, fy, cx, cy), qvec4 (w, x, y, z), tvec3.  The result stays in the context. */
@@ -672,6 +673,73 @@ int lt_fn_refine_eval(int64_t K, const double *cam11, const double *line2d4, con
 int lt_fn_refine_explog(int which, int64_t n, const double *x, double *out);
 int lt_fn_refine_minimal(const double line6[6], double params6[6]);
 int lt_fn_refine_infinite(const double params6[6], double dm6[6]);
+
+/* ---- the VP and the heatmap term of limap.optimize.line_refinement (runners/refinement.py with
+ * cfgs/refinement/default.yaml; refine.cc:87-126,315-360).  Per support of a track, after its
+ * geometric block: a VP block where its VPResult labels the line -- one residual, the sine between the line's direction
+ * in the camera frame and the direction of the vanishing point, TrivialLoss scaled by (length / 30) vp_multiplier -- and a
+ * heatmap block of n_samples_heatmap residuals 1 - f(xy_j), xy_j the intersection of the projected line with sample line
+ * j of the support, f the bilinear interpolation of the image's heatmap with upstream's forward-difference derivatives,
+ * HuberLoss(0.001) scaled by (length / 30) heatmap_multiplier / (n_samples_heatmap / 10.0).
+ * Evaluation failure: a sample whose intersection has |p_homo[2]| < 1e-12 (or is not a number) fails; a cost evaluation
+ * with a failed sample is +inf, so the step is rejected and the radius shrinks; at the initial point the track ends with
+ * termination code 6, its parameters unchanged, its segment re-cut.
+ * Texels are binary16 or binary32 in memory and widen to FP64 exactly. */
+#define LT_TEXEL_F16 0
+#define LT_TEXEL_F32 1
+typedef struct lt_refine_terms {
+  int32_t use_geometric;      /* 1 */
+  int32_t use_vp;             /* 0 */
+  int32_t use_heatmap;        /* 0 */
+  int32_t n_samples_heatmap;  /* 10 */
+  double vp_multiplier;       /* 1.0 */
+  double sample_range_min;    /* 0.05 */
+  double sample_range_max;    /* 0.95 */
+  double heatmap_multiplier;  /* 1.0 */
+  int32_t texel_type;         /* LT_TEXEL_F16: the type of the heatmaps the call reads */
+  int32_t pad_;
+} lt_refine_terms;
+void lt_refine_terms_default(lt_refine_terms *terms);
+/* The scene's heatmaps, uploaded once and kept in the context until they are set again or cleared: n images with
+ * distinct ids, h[i] x w[i] texels of texel_type each, row-major without padding, at the host pointers data[i].  The
+ * call returns after the copy. */
+int lt_refine_set_heatmaps(lt_ctx *ctx, int n, const int32_t *img_ids, const int32_t *h, const int32_t *w,
+                           const void *const *data, int texel_type);
+int lt_refine_clear_heatmaps(lt_ctx *ctx);
+/* Counts the calls that changed the context's heatmaps (a set that passed its argument checks, whether its copy then
+ * succeeded or not, and every clear): a caller that remembers the value after its own lt_refine_set_heatmaps knows that
+ * its heatmaps are still the resident ones while the value stands. */
+int64_t lt_refine_heatmaps_generation(lt_ctx *ctx);
+/* lt_refine_arrays with the terms.  vp_flag[s] != 0 where support s (the caller's order, like img) has a vanishing
+ * point, vp3 its homogeneous image coordinates (read only there; both may be NULL without use_vp); view_hw: (h, w) of
+ * every camera row, or NULL, an entry <= 0 meaning that the view carries no size.  With neither use_vp nor use_heatmap
+ * the call is lt_refine_arrays: the same launches, the same bits.  The getters and timers are lt_refine_arrays'; [3] is
+ * the device time of k_refine_lm_terms.
+ * LT_ERR_ARGUMENT before any launch, besides lt_refine_arrays' cases: no term enabled; n_samples_heatmap outside
+ * [2, 1024]; a multiplier, a sample range or a flagged vanishing point that is not finite; with use_heatmap a supporting image
+ * without a heatmap in the context, heatmaps of another texel type than the terms', a heatmap whose size is not its
+ * view's, a 2D support of zero length. */
+int lt_refine_arrays_terms(lt_ctx *ctx, int n_img, const int32_t *img_ids, const double *kvec4, const double *qvec4,
+                           const double *tvec3, int64_t n_tracks, const double *line6, const int64_t *off,
+                           const int32_t *img, const double *line2d4, const double *line3d6, const lt_refine_config *cfg,
+                           const lt_refine_terms *terms, const int32_t *vp_flag, const double *vp3,
+                           const int32_t *view_hw);
+/* lt_fn_refine_host with the terms: the heatmaps are the caller's n_hm host images (as lt_refine_set_heatmaps takes
+ * them, of terms->texel_type).  Errors through lt_fn_refine_host_error. */
+int lt_fn_refine_host_terms(int n_img, const int32_t *img_ids, const double *kvec4, const double *qvec4, const double *tvec3,
+                            int64_t n_tracks, const double *line6, const int64_t *off, const int32_t *img,
+                            const double *line2d4, const double *line3d6, const lt_refine_config *cfg,
+                            const lt_refine_terms *terms, const int32_t *vp_flag, const double *vp3, const int32_t *view_hw,
+                            int n_hm, const int32_t *hm_ids, const int32_t *hm_h, const int32_t *hm_w,
+                            const void *const *hm_data, int n_threads, double *params6, double *seg6, double *cost2,
+                            int32_t *iters, int32_t *codes);
+/* For tests: lt_fn_refine_eval with the terms; support k reads the heatmap hm_data[k] of hm_h[k] x hm_w[k] texels.
+ * residuals[K (3 + n)], n = n_samples_heatmap with use_heatmap and 0 without: per support 2 geometric, 1 VP and n heatmap
+ * residuals, NaN where the block is absent; *failed = 1 where a sample fails (then the cost is +inf). */
+int lt_fn_refine_eval_terms(int64_t K, const double *cam11, const double *line2d4, const double params6[6], double alpha,
+                            const lt_refine_terms *terms, const int32_t *vp_flag, const double *vp3, const int32_t *hm_h,
+                            const int32_t *hm_w, const void *const *hm_data, double *residuals, int32_t *failed,
+                            double *cost, double g[4], double H[16]);
 
 /* ---- limap.pointsfm: the visual neighbours of every image and the robust ranges of the point cloud -- step [A] of
  * limap.runners.line_triangulation, `compute_metainfos` (pointsfm/functions.py:20-55) over SfmModel

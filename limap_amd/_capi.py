@@ -42,6 +42,9 @@ EXPORTED_SYMBOLS = [
     "lt_refine_config_default", "lt_refine_arrays", "lt_refine_tracks", "lt_refine_num", "lt_refine_get",
     "lt_refine_get_timers", "lt_fn_refine_host", "lt_fn_refine_eval", "lt_fn_refine_explog", "lt_fn_refine_minimal",
     "lt_fn_refine_infinite", "lt_fn_refine_host_error", "lt_fn_refine_cut",
+    "lt_refine_terms_default", "lt_refine_set_heatmaps", "lt_refine_clear_heatmaps", "lt_refine_heatmaps_generation",
+    "lt_refine_arrays_terms",
+    "lt_fn_refine_host_terms", "lt_fn_refine_eval_terms",
     "lt_sfm_neighbors", "lt_sfm_get", "lt_sfm_get_pairs", "lt_sfm_get_timers", "lt_fn_sfm_neighbors_host",
     "lt_fn_sfm_host_get", "lt_fn_sfm_host_error", "lt_fn_sfm_ranges",
     "lt_undist_warp", "lt_undist_points", "lt_undist_get_timers", "lt_undist_copy_yardstick", "lt_fn_undist_warp_host",
@@ -158,6 +161,17 @@ class LtRefineConfig(C.Structure):
     _fields_ = [("geometric_alpha", C.c_double), ("min_num_images", C.c_int32), ("num_outliers_aggregator", C.c_int32),
                 ("num_outliers_aggregate", C.c_int32), ("max_num_iterations", C.c_int32), ("constant_line", C.c_int32),
                 ("pad_", C.c_int32)]
+
+
+class LtRefineTerms(C.Structure):
+    """lt_refine_terms of include/limap_amd.h"""
+    _fields_ = [("use_geometric", C.c_int32), ("use_vp", C.c_int32), ("use_heatmap", C.c_int32),
+                ("n_samples_heatmap", C.c_int32), ("vp_multiplier", C.c_double), ("sample_range_min", C.c_double),
+                ("sample_range_max", C.c_double), ("heatmap_multiplier", C.c_double), ("texel_type", C.c_int32),
+                ("pad_", C.c_int32)]
+
+
+TEXEL_F16, TEXEL_F32 = 0, 1
 
 
 class LtUndistCamera(C.Structure):
@@ -341,6 +355,18 @@ def load_library():
     L.lt_fn_refine_host_error.argtypes = []
     L.lt_fn_refine_host_error.restype = C.c_char_p
     L.lt_fn_refine_cut.argtypes = [C.c_int64, dp, dp, C.c_int, dp]
+    rtp, vpp = C.POINTER(LtRefineTerms), C.POINTER(C.c_void_p)
+    L.lt_refine_terms_default.argtypes = [rtp]
+    L.lt_refine_terms_default.restype = None
+    L.lt_refine_set_heatmaps.argtypes = [vp, C.c_int, i32p, i32p, i32p, vpp, C.c_int]
+    L.lt_refine_clear_heatmaps.argtypes = [vp]
+    L.lt_refine_heatmaps_generation.argtypes = [vp]
+    L.lt_refine_heatmaps_generation.restype = C.c_int64
+    L.lt_refine_arrays_terms.argtypes = L.lt_refine_arrays.argtypes + [rtp, i32p, dp, i32p]
+    L.lt_fn_refine_host_terms.argtypes = [C.c_int, i32p, dp, dp, dp, C.c_int64, dp, i64p, i32p, dp, dp, rcp, rtp, i32p, dp,
+                                          i32p, C.c_int, i32p, i32p, i32p, vpp, C.c_int, dp, dp, dp, i32p, i32p]
+    L.lt_fn_refine_eval_terms.argtypes = [C.c_int64, dp, dp, dp, C.c_double, rtp, i32p, dp, i32p, i32p, vpp, dp, i32p, dp,
+                                          dp, dp]
     L.lt_sfm_neighbors.argtypes = [vp, C.c_int, fp, fp, C.c_int64, fp, i64p, i32p, C.c_int, C.c_int64, C.c_double, i64p, i64p]
     L.lt_sfm_get.argtypes = [vp, i64p, i32p]
     L.lt_sfm_get_pairs.argtypes = [vp, i32p, i32p, fp]

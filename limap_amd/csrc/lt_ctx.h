@@ -235,6 +235,13 @@ struct RefineState {  // line refinement (lt_refine.cpp): the result of the last
   double timers[4] = {0, 0, 0, 0};  // lt_refine_get_timers
   std::vector<double> out;          // 15 doubles (one lt::RfOut) per track
   DevBuf d_k, d_q, d_t, d_cam, d_l2d, d_l3d, d_tab, d_line, d_tracks, d_out;
+  // the scene's heatmaps (lt_refine_set_heatmaps), kept across calls: texels packed in d_hm_tex, one lt::RfHm per
+  // image in d_hm_tab; the host keeps what validation needs
+  int hm_type = 0;                  // LT_TEXEL_F16 / LT_TEXEL_F32
+  long long hm_generation = 0;      // counts the calls that set or cleared them (lt_refine_heatmaps_generation)
+  std::vector<int> hm_ids, hm_h, hm_w;
+  DevBuf d_hm_tex, d_hm_tab;
+  DevBuf d_ext, d_vp_flag, d_vp3, d_sup_hm;  // per call with terms: the supports' extra tables
 };
 
 struct SfmState {  // visual neighbours (lt_sfm.cpp): the result of the last lt_sfm_neighbors

@@ -6,6 +6,12 @@
 //                  supports, the 14 sums of a linearisation reduced by a fixed xor tree of shuffles, the 4x4 solve done
 //                  by every lane of the group on the same bits
 //   k_refine_cut   GetLineSegmentFromInfiniteLine3d: the two order statistics by rank counting, no sort
+// and for a call with the VP or the heatmap term (k_refine_lm and its tables are not involved in what they add):
+//   k_refine_prep_terms  per support: the view's unit quaternion, the direction of its vanishing point and the flag
+//   k_refine_lm_terms    k_refine_lm with the blocks of the two terms, kRfTermWidth lanes per track; instantiated
+//                        without the heatmap term and with it for binary16 and float texels.  The geometric and the VP
+//                        term are switches of the launch, the same in every lane.  A lane loads the 4 (cost) or 8
+//                        (linearisation) texels of a sample together, before the first of them is used
 // All stores are ordinary vector stores of the lanes.
 
 #include "lt_refine.h"
@@ -87,6 +93,79 @@ __global__ void __launch_bounds__(kRfBlock) k_refine_lm(RfDev dev, RfOut *__rest
   }
 }
 
+__global__ void __launch_bounds__(256) k_refine_prep_terms(const double *__restrict__ kvec, const double *__restrict__ qvec,
+                                                           const int *__restrict__ sup_cam, const int *__restrict__ vp_flag,
+                                                           const double *__restrict__ vp3, long long n_sup,
+                                                           double *__restrict__ ext, long long stride) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_sup) return;
+  const int cam = sup_cam[i];
+  rf_ext_prep(kvec + 4 * (long long)cam, qvec + 4 * (long long)cam, vp_flag[i] != 0, vp3 + 3 * i, ext + i, stride);
+}
+
+__device__ __forceinline__ double group_sum_terms(double v) {
+#pragma unroll
+  for (int m = kRfTermWidth / 2; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, kRfTermWidth);
+  return v;
+}
+
+// DevGroup with the terms' blocks
+template <bool HM, class Tx>
+struct DevGroupTerms {
+  const RfDev &dev;
+  const RfDevTerms &tr;
+  const RfTrack &t;
+  int lane;
+  __device__ __forceinline__ RfGrid<Tx> grid(long long s) const {
+    if (!HM) return RfGrid<Tx>{nullptr, 1, 1};
+    const RfHm hm = tr.hm[tr.sup_hm[s]];
+    return RfGrid<Tx>{static_cast<const Tx *>(tr.texels) + hm.off, hm.h, hm.w};
+  }
+  __device__ __forceinline__ double cost(const double p[6]) const {
+    double dm[6];
+    rf_plucker<double>(p, p + 4, dm);
+    double part = 0.0;
+    for (int k = lane; k < t.n; k += kRfTermWidth) {
+      const long long s = t.s0 + k;
+      part = part + rf_cost_terms<HM, Tx>(rf_load(dev.sup, dev.stride, s), rf_load_ext(tr.ext, dev.stride, s), grid(s),
+                                          tr.cfg, dm, dev.alpha);
+    }
+    return 0.5 * group_sum_terms(part);
+  }
+  __device__ __forceinline__ void linearise(const double p[6], double acc[kRfSums]) const {
+    Rf4 u[4], w[2], dm[6];
+    rf_seed(p, u, w);
+    rf_plucker<Rf4>(u, w, dm);
+    for (int c = 0; c < kRfSums; ++c) acc[c] = 0.0;
+    for (int k = lane; k < t.n; k += kRfTermWidth) {
+      const long long s = t.s0 + k;
+      rf_accumulate_terms<HM, Tx>(rf_load(dev.sup, dev.stride, s), rf_load_ext(tr.ext, dev.stride, s), grid(s), tr.cfg, dm,
+                                  dev.alpha, acc);
+    }
+    for (int c = 0; c < kRfSums; ++c) acc[c] = group_sum_terms(acc[c]);
+  }
+};
+
+template <bool HM, class Tx>
+__global__ void __launch_bounds__(kRfBlock) k_refine_lm_terms(RfDev dev, RfDevTerms tr, RfOut *__restrict__ out) {
+  const long long ti = ((long long)blockIdx.x * kRfBlock + threadIdx.x) / kRfTermWidth;
+  const int lane = threadIdx.x % kRfTermWidth;
+  if (ti >= dev.n_tracks) return;  // a whole group leaves together
+  const RfTrack t = dev.tracks[ti];
+  double p[6], F0, F1;
+  int it, code;
+  for (int c = 0; c < 6; ++c) p[c] = out[ti].p[c];
+  DevGroupTerms<HM, Tx> grp{dev, tr, t, lane};
+  rf_lm_terms(grp, t.constant != 0, dev.max_iter, p, &F0, &F1, &it, &code);
+  if (lane == 0) {
+    for (int c = 0; c < 6; ++c) out[ti].p[c] = p[c];
+    out[ti].cost0 = F0;
+    out[ti].cost1 = F1;
+    out[ti].iters = it;
+    out[ti].code = code;
+  }
+}
+
 __global__ void __launch_bounds__(kRfBlock) k_refine_cut(RfDev dev, RfOut *__restrict__ out) {
   const long long ti = ((long long)blockIdx.x * kRfBlock + threadIdx.x) / kRfWidth;
   const int lane = threadIdx.x % kRfWidth;
@@ -141,6 +220,24 @@ void launch_refine_prep(hipStream_t st, const double *kvec, const double *qvec, 
 void launch_refine_lm(hipStream_t st, const RfDev &dev, RfOut *out) {
   if (dev.n_tracks <= 0) return;
   hipLaunchKernelGGL(k_refine_lm, dim3(grid_of(dev.n_tracks * kRfWidth, kRfBlock)), dim3(kRfBlock), 0, st, dev, out);
+}
+
+void launch_refine_prep_terms(hipStream_t st, const double *kvec, const double *qvec, const int *sup_cam,
+                              const int *vp_flag, const double *vp3, long long n_sup, double *ext, long long stride) {
+  if (n_sup <= 0) return;
+  hipLaunchKernelGGL(k_refine_prep_terms, dim3(grid_of(n_sup, 256)), dim3(256), 0, st, kvec, qvec, sup_cam, vp_flag, vp3,
+                     n_sup, ext, stride);
+}
+
+void launch_refine_lm_terms(hipStream_t st, const RfDev &dev, const RfDevTerms &terms, bool texel_f32, RfOut *out) {
+  if (dev.n_tracks <= 0) return;
+  const dim3 grid(grid_of(dev.n_tracks * kRfTermWidth, kRfBlock)), block(kRfBlock);
+  if (!terms.cfg.use_heatmap)
+    hipLaunchKernelGGL((k_refine_lm_terms<false, float>), grid, block, 0, st, dev, terms, out);
+  else if (texel_f32)
+    hipLaunchKernelGGL((k_refine_lm_terms<true, float>), grid, block, 0, st, dev, terms, out);
+  else
+    hipLaunchKernelGGL((k_refine_lm_terms<true, unsigned short>), grid, block, 0, st, dev, terms, out);
 }
 
 void launch_refine_cut(hipStream_t st, const RfDev &dev, RfOut *out) {

@@ -31,8 +31,110 @@ struct Plan {
   std::vector<double> l2d;     // 4 per support, residual order
   std::vector<double> l3d;     // 6 per support, list order
   std::vector<double> line6;
+  std::vector<long long> src;  // residual order -> the caller's support
   long long n_sup = 0;
 };
+
+// the heatmaps a call can read: the caller's (host path) or the context's (device path)
+struct HmSet {
+  int type = LT_TEXEL_F16;
+  std::vector<int> h, w;
+  std::vector<long long> off;          // first texel in the packed buffer, n + 1
+  std::vector<const void *> data;      // host path: the caller's images
+  std::unordered_map<int, int> slot;   // image id -> row
+};
+
+// what the terms add to a plan, residual order
+struct TermsPlan {
+  std::vector<int> vp_flag, sup_hm;
+  std::vector<double> vp3;
+  RfTermCfg cfg;
+};
+
+int check_terms(const lt_refine_terms *t, std::string &msg) {
+  if (!t) { msg = "null terms"; return 1; }
+  if (!t->use_geometric && !t->use_vp && !t->use_heatmap) { msg = "no term is enabled"; return 1; }
+  if (t->use_vp && !std::isfinite(t->vp_multiplier)) { msg = "vp_multiplier is not finite"; return 1; }
+  if (t->use_heatmap) {
+    if (t->n_samples_heatmap < 2 || t->n_samples_heatmap > 1024) {  // interval = range / (n - 1)
+      msg = "n_samples_heatmap outside [2, 1024]";
+      return 1;
+    }
+    if (!std::isfinite(t->heatmap_multiplier)) { msg = "heatmap_multiplier is not finite"; return 1; }
+    if (!std::isfinite(t->sample_range_min) || !std::isfinite(t->sample_range_max)) {
+      msg = "sample_range is not finite";
+      return 1;
+    }
+    if (t->texel_type != LT_TEXEL_F16 && t->texel_type != LT_TEXEL_F32) { msg = "unknown texel type"; return 1; }
+  }
+  return 0;
+}
+
+int check_heatmaps(int n, const int32_t *ids, const int32_t *h, const int32_t *w, const void *const *data, int type,
+                   HmSet &hs, std::string &msg) {
+  if (n < 0 || (n > 0 && (!ids || !h || !w || !data))) { msg = "bad heatmap arrays"; return 1; }
+  if (type != LT_TEXEL_F16 && type != LT_TEXEL_F32) { msg = "unknown texel type"; return 1; }
+  hs.type = type;
+  hs.off.assign(1, 0);
+  for (int i = 0; i < n; ++i) {
+    if (h[i] < 1 || w[i] < 1 || !data[i]) { msg = "heatmap of image " + std::to_string(ids[i]) + " is empty"; return 1; }
+    if (!hs.slot.emplace(ids[i], i).second) { msg = "heatmap of image " + std::to_string(ids[i]) + " given twice"; return 1; }
+    hs.h.push_back(h[i]);
+    hs.w.push_back(w[i]);
+    hs.data.push_back(data[i]);
+    hs.off.push_back(hs.off.back() + (long long)h[i] * w[i]);
+  }
+  return 0;
+}
+
+// the checks of the terms' per-support input and its tables in residual order; view_hw: (h, w) per camera row, or null,
+// an entry <= 0 meaning the view carries no size
+int make_terms_plan(const Plan &pl, const int32_t *img, const lt_refine_terms &t, const int32_t *vp_flag, const double *vp3,
+                    const int32_t *view_hw, const HmSet *hs, TermsPlan &tp, std::string &msg) {
+  const size_t S = (size_t)pl.n_sup;
+  tp.vp_flag.assign(S, 0);
+  tp.vp3.assign(3 * S, 0.0);
+  tp.sup_hm.assign(S, 0);
+  if (t.use_vp && S > 0 && (!vp_flag || !vp3)) { msg = "use_vp without VP arrays"; return 1; }
+  if (t.use_heatmap && !hs) { msg = "use_heatmap without heatmaps"; return 1; }
+  if (t.use_heatmap && hs->type != t.texel_type) { msg = "the heatmaps' texel type is not the terms'"; return 1; }
+  for (size_t i = 0; i < S; ++i) {
+    const long long src = pl.src[i];
+    if (t.use_vp && vp_flag[src]) {
+      if (!all_finite(vp3 + 3 * src, 3)) { msg = "non-finite vanishing point"; return 1; }
+      tp.vp_flag[i] = 1;
+      for (int c = 0; c < 3; ++c) tp.vp3[3 * i + c] = vp3[3 * src + c];
+    }
+    if (t.use_heatmap) {
+      auto it = hs->slot.find(img[src]);
+      if (it == hs->slot.end()) { msg = "image " + std::to_string(img[src]) + " supports a track and has no heatmap"; return 1; }
+      const int cam = pl.sup_cam[i], sl = it->second;
+      // THROW_CHECK_EQ of the heatmap's size against the view's (refine.cc:283-284)
+      if (view_hw && view_hw[2 * cam] > 0 && view_hw[2 * cam + 1] > 0 &&
+          (view_hw[2 * cam] != hs->h[(size_t)sl] || view_hw[2 * cam + 1] != hs->w[(size_t)sl])) {
+        msg = "the heatmap of image " + std::to_string(img[src]) + " has not the size of its view";
+        return 1;
+      }
+      const double *l = pl.l2d.data() + 4 * i;
+      const double dx = l[2] - l[0], dy = l[3] - l[1];
+      if (!(std::sqrt(dx * dx + dy * dy) > 0.0)) {  // THROW_CHECK_LT(|direc.norm() - 1|, EPS) (infinite_line.cc:10)
+        msg = "a 2D support of zero length has no sample lines";
+        return 1;
+      }
+      tp.sup_hm[i] = sl;
+    }
+  }
+  tp.cfg.vp_multiplier = t.vp_multiplier;
+  tp.cfg.heatmap_multiplier = t.heatmap_multiplier;
+  tp.cfg.n_samples = t.use_heatmap ? t.n_samples_heatmap : 0;
+  tp.cfg.heatmap_den = t.n_samples_heatmap / 10.0;
+  tp.cfg.t0 = t.sample_range_min;
+  tp.cfg.interval = t.use_heatmap ? (t.sample_range_max - t.sample_range_min) / (t.n_samples_heatmap - 1) : 0.0;
+  tp.cfg.use_geometric = t.use_geometric != 0;
+  tp.cfg.use_vp = t.use_vp != 0;
+  tp.cfg.use_heatmap = t.use_heatmap != 0;
+  return 0;
+}
 
 int check_config(const lt_refine_config *cfg, std::string &msg) {
   if (!cfg) { msg = "null configuration"; return 1; }
@@ -74,6 +176,7 @@ int make_plan(const std::unordered_map<int, int> &id2idx, int64_t T, const doubl
   pl.tracks.resize((size_t)T);
   pl.sup_cam.resize((size_t)S);
   pl.l2d.resize(4 * (size_t)S);
+  pl.src.resize((size_t)S);
   pl.l3d.assign(l3d6, l3d6 + 6 * (size_t)S);
   pl.line6.assign(line6, line6 + 6 * (size_t)T);
   std::vector<int> order, ids;
@@ -106,6 +209,7 @@ int make_plan(const std::unordered_map<int, int> &id2idx, int64_t T, const doubl
         return 1;
       }
       pl.sup_cam[(size_t)(a + k)] = it->second;
+      pl.src[(size_t)(a + k)] = src;
       for (int c = 0; c < 4; ++c) pl.l2d[4 * (size_t)(a + k) + c] = l2d4[4 * src + c];
     }
     pl.tracks[(size_t)n] = RfTrack{a, K, (cfg.constant_line != 0 || n_images < cfg.min_num_images) ? 1 : 0};
@@ -129,7 +233,7 @@ struct HostGroup {
       part[l][0] = s;
     }
     double out[kRfSums];
-    rf_tree_host(part, 1, out);
+    rf_tree_host<kRfWidth>(part, 1, out);
     return 0.5 * out[0];
   }
   void linearise(const double p[6], double acc[kRfSums]) const {
@@ -141,9 +245,74 @@ struct HostGroup {
       for (int c = 0; c < kRfSums; ++c) part[l][c] = 0.0;
       for (int k = l; k < t.n; k += kRfWidth) rf_accumulate(rf_load(tab, stride, t.s0 + k), dm, alpha, part[l]);
     }
-    rf_tree_host(part, kRfSums, acc);
+    rf_tree_host<kRfWidth>(part, kRfSums, acc);
   }
 };
+
+// the host twin of a group of k_refine_lm_terms
+template <bool HM, class Tx>
+struct HostGroupTerms {
+  const double *tab, *ext;
+  long long stride;
+  const RfTrack &t;
+  double alpha;
+  const TermsPlan &tp;
+  const HmSet *hs;
+  RfGrid<Tx> grid(long long s) const {
+    if (!HM) return RfGrid<Tx>{nullptr, 1, 1};
+    const size_t sl = (size_t)tp.sup_hm[(size_t)s];
+    return RfGrid<Tx>{static_cast<const Tx *>(hs->data[sl]), hs->h[sl], hs->w[sl]};
+  }
+  double cost(const double p[6]) const {
+    double dm[6];
+    rf_plucker<double>(p, p + 4, dm);
+    double part[kRfTermWidth][kRfSums];
+    for (int l = 0; l < kRfTermWidth; ++l) {
+      double s = 0.0;
+      for (int k = l; k < t.n; k += kRfTermWidth)
+        s = s + rf_cost_terms<HM, Tx>(rf_load(tab, stride, t.s0 + k), rf_load_ext(ext, stride, t.s0 + k), grid(t.s0 + k),
+                                      tp.cfg, dm, alpha);
+      part[l][0] = s;
+    }
+    double out[kRfSums];
+    rf_tree_host<kRfTermWidth>(part, 1, out);
+    return 0.5 * out[0];
+  }
+  // res: the residuals of every support, 3 + n_samples each (tests)
+  bool linearise_res(const double p[6], double acc[kRfSums], double *res) const {
+    Rf4 u[4], w[2], dm[6];
+    rf_seed(p, u, w);
+    rf_plucker<Rf4>(u, w, dm);
+    double part[kRfTermWidth][kRfSums];
+    bool ok = true;
+    for (int l = 0; l < kRfTermWidth; ++l) {
+      for (int c = 0; c < kRfSums; ++c) part[l][c] = 0.0;
+      for (int k = l; k < t.n; k += kRfTermWidth)
+        ok = rf_accumulate_terms<HM, Tx>(rf_load(tab, stride, t.s0 + k), rf_load_ext(ext, stride, t.s0 + k), grid(t.s0 + k),
+                                         tp.cfg, dm, alpha, part[l],
+                                         res ? res + (size_t)k * (3 + (size_t)tp.cfg.n_samples) : nullptr) && ok;
+    }
+    rf_tree_host<kRfTermWidth>(part, kRfSums, acc);
+    return ok;
+  }
+  void linearise(const double p[6], double acc[kRfSums]) const { linearise_res(p, acc, nullptr); }
+};
+
+// f(HostGroupTerms) for the instantiation the terms select, like launch_refine_lm_terms
+template <class F>
+void with_host_group(const double *tab, const double *ext, long long stride, const RfTrack &t, double alpha,
+                     const TermsPlan &tp, const HmSet *hs, F &&f) {
+  if (!tp.cfg.use_heatmap) {
+    HostGroupTerms<false, float> g{tab, ext, stride, t, alpha, tp, hs};
+    f(g);
+  } else if (hs->type == LT_TEXEL_F32) {
+    HostGroupTerms<true, float> g{tab, ext, stride, t, alpha, tp, hs};
+    f(g);
+  } else {
+    HostGroupTerms<true, unsigned short> g{tab, ext, stride, t, alpha, tp, hs};
+    f(g);
+  }
+}
 
 // k_refine_cut on the host: the same rank rule
 void cut_host(const RfTrack &t, const double *l3d, int num_outliers, RfOut &o) {
@@ -163,21 +332,29 @@ void cut_host(const RfTrack &t, const double *l3d, int num_outliers, RfOut &o) {
   }
 }
 
+// k_refine_prep's support table
+void fill_support(const double *k4, const double *q4, const double *t3, const double *l, double *tab, long long stride) {
+  rf_view_matrix(k4, q4, t3, tab, stride);
+  tab[18 * stride] = l[0]; tab[19 * stride] = l[1];
+  tab[20 * stride] = l[2]; tab[21 * stride] = l[3];
+  const double dx = l[2] - l[0], dy = l[3] - l[1];
+  tab[22 * stride] = std::sqrt(dx * dx + dy * dy) / 30.0;
+}
+
+// tp: the terms of the call, or null (then hs is not read)
 void run_host(const Plan &pl, const double *k, const double *q, const double *t, const lt_refine_config &cfg, int n_threads,
-              std::vector<RfOut> &out) {
+              std::vector<RfOut> &out, const TermsPlan *tp = nullptr, const HmSet *hs = nullptr) {
   const long long S = pl.n_sup, T = (long long)pl.tracks.size();
   const long long stride = std::max<long long>(S, 1);
-  std::vector<double> tab((size_t)kRfFields * (size_t)stride);
+  std::vector<double> tab((size_t)kRfFields * (size_t)stride), ext(tp ? (size_t)kRfExtFields * (size_t)stride : 0);
   const int nt = n_threads > 0 ? n_threads : omp_get_max_threads();
 #pragma omp parallel for num_threads(nt) schedule(static)
   for (long long i = 0; i < S; ++i) {
     const int cam = pl.sup_cam[(size_t)i];
-    rf_view_matrix(k + 4 * (size_t)cam, q + 4 * (size_t)cam, t + 3 * (size_t)cam, tab.data() + i, stride);
-    const double *l = pl.l2d.data() + 4 * i;
-    tab[18 * stride + i] = l[0]; tab[19 * stride + i] = l[1];
-    tab[20 * stride + i] = l[2]; tab[21 * stride + i] = l[3];
-    const double dx = l[2] - l[0], dy = l[3] - l[1];
-    tab[22 * stride + i] = std::sqrt(dx * dx + dy * dy) / 30.0;
+    fill_support(k + 4 * (size_t)cam, q + 4 * (size_t)cam, t + 3 * (size_t)cam, pl.l2d.data() + 4 * i, tab.data() + i, stride);
+    if (tp)
+      rf_ext_prep(k + 4 * (size_t)cam, q + 4 * (size_t)cam, tp->vp_flag[(size_t)i] != 0, tp->vp3.data() + 3 * i,
+                  ext.data() + i, stride);
   }
   out.resize((size_t)T);
 #pragma omp parallel for num_threads(nt) schedule(dynamic, 16)
@@ -185,8 +362,14 @@ void run_host(const Plan &pl, const double *k, const double *q, const double *t,
     RfOut &o = out[(size_t)n];
     const RfTrack &tr = pl.tracks[(size_t)n];
     rf_minimal(pl.line6.data() + 6 * n, o.p);
-    HostGroup grp{tab.data(), stride, tr, cfg.geometric_alpha};
-    rf_lm(grp, tr.constant != 0, cfg.max_num_iterations, o.p, &o.cost0, &o.cost1, &o.iters, &o.code);
+    if (tp) {
+      with_host_group(tab.data(), ext.data(), stride, tr, cfg.geometric_alpha, *tp, hs, [&](auto &grp) {
+        rf_lm_terms(grp, tr.constant != 0, cfg.max_num_iterations, o.p, &o.cost0, &o.cost1, &o.iters, &o.code);
+      });
+    } else {
+      HostGroup grp{tab.data(), stride, tr, cfg.geometric_alpha};
+      rf_lm(grp, tr.constant != 0, cfg.max_num_iterations, o.p, &o.cost0, &o.cost1, &o.iters, &o.code);
+    }
     cut_host(tr, pl.l3d.data(), cfg.num_outliers_aggregator, o);
   }
 }
@@ -202,8 +385,9 @@ void copy_out(const RfOut *o, long long T, double *params6, double *seg6, double
 }
 
 // upload of the plan, the three kernels, download into ctx->rf.out; d_k / d_q / d_t: the cameras on the device
+// tp: the terms of the call, or null; with them k_refine_prep_terms runs too and k_refine_lm_terms replaces k_refine_lm
 int run_device(lt_ctx *ctx, const Plan &pl, const double *d_k, const double *d_q, const double *d_t,
-               const lt_refine_config &cfg, double t0) {
+               const lt_refine_config &cfg, double t0, const TermsPlan *tp = nullptr) {
   const long long S = pl.n_sup, T = (long long)pl.tracks.size();
   static_assert(sizeof(RfOut) == 15 * sizeof(double), "RfOut is 15 doubles");
   ctx->rf.out.assign(15 * (size_t)T, 0.0);
@@ -220,6 +404,12 @@ int run_device(lt_ctx *ctx, const Plan &pl, const double *d_k, const double *d_q
   if (int rc = upload_vec(ctx, ctx->rf.d_tracks, pl.tracks)) return rc;
   ENSURE(ctx, ctx->rf.d_tab, 8 * (size_t)kRfFields * (size_t)stride);
   ENSURE(ctx, ctx->rf.d_out, sizeof(RfOut) * (size_t)T);
+  if (tp) {
+    if (int rc = upload_vec(ctx, ctx->rf.d_vp_flag, tp->vp_flag)) return rc;
+    if (int rc = upload_vec(ctx, ctx->rf.d_vp3, tp->vp3)) return rc;
+    if (int rc = upload_vec(ctx, ctx->rf.d_sup_hm, tp->sup_hm)) return rc;
+    ENSURE(ctx, ctx->rf.d_ext, 8 * (size_t)kRfExtFields * (size_t)stride);
+  }
   if (int rc = stream_sync(ctx)) return rc;
   const double t1 = now_ms();
   ctx->rf.timers[0] = t1 - t0;
@@ -238,8 +428,17 @@ int run_device(lt_ctx *ctx, const Plan &pl, const double *d_k, const double *d_q
   if (int rc = ev.create(ctx)) return rc;
   launch_refine_prep(st, d_k, d_q, d_t, ctx->rf.d_cam.as<int>(), ctx->rf.d_l2d.as<double>(), S, ctx->rf.d_tab.as<double>(),
                      stride, ctx->rf.d_line.as<double>(), T, d_out);
+  if (tp)
+    launch_refine_prep_terms(st, d_k, d_q, ctx->rf.d_cam.as<int>(), ctx->rf.d_vp_flag.as<int>(), ctx->rf.d_vp3.as<double>(), S,
+                             ctx->rf.d_ext.as<double>(), stride);
   if (int rc = ev.record(ctx, 0)) return rc;
-  launch_refine_lm(st, dev, d_out);
+  if (tp) {
+    const RfDevTerms terms{ctx->rf.d_ext.as<double>(), ctx->rf.d_sup_hm.as<int>(), ctx->rf.d_hm_tab.as<RfHm>(),
+                           ctx->rf.d_hm_tex.p, tp->cfg};
+    launch_refine_lm_terms(st, dev, terms, ctx->rf.hm_type == LT_TEXEL_F32, d_out);
+  } else {
+    launch_refine_lm(st, dev, d_out);
+  }
   if (int rc = ev.record(ctx, 1)) return rc;
   launch_refine_cut(st, dev, d_out);
   if (int rc = stream_sync(ctx)) return rc;
@@ -249,6 +448,20 @@ int run_device(lt_ctx *ctx, const Plan &pl, const double *d_k, const double *d_q
   HIPCHK(ctx, hipMemcpyAsync(ctx->rf.out.data(), d_out, sizeof(RfOut) * (size_t)T, hipMemcpyDeviceToHost, st));
   if (int rc = stream_sync(ctx)) return rc;
   ctx->rf.timers[2] = now_ms() - t2;
+  return LT_OK;
+}
+
+// the caller's cameras into the context's buffers (lt_refine_arrays and lt_refine_arrays_terms)
+int upload_cameras(lt_ctx *ctx, int n_img, const double *kvec4, const double *qvec4, const double *tvec3) {
+  const size_t nI = (size_t)std::max(n_img, 1);
+  ENSURE(ctx, ctx->rf.d_k, 32 * nI);
+  ENSURE(ctx, ctx->rf.d_q, 32 * nI);
+  ENSURE(ctx, ctx->rf.d_t, 24 * nI);
+  if (n_img > 0) {
+    HIPCHK(ctx, hipMemcpyAsync(ctx->rf.d_k.p, kvec4, 32 * (size_t)n_img, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->rf.d_q.p, qvec4, 32 * (size_t)n_img, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->rf.d_t.p, tvec3, 24 * (size_t)n_img, hipMemcpyHostToDevice, ctx->stream));
+  }
   return LT_OK;
 }
 
@@ -299,16 +512,88 @@ int lt_refine_arrays(lt_ctx *ctx, int n_img, const int32_t *img_ids, const doubl
       make_plan(id2idx, n_tracks, line6, off, img, line2d4, line3d6, *cfg, pl, msg))
     return fail(ctx, LT_ERR_ARGUMENT, who + ": " + msg);
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  const size_t nI = (size_t)std::max(n_img, 1);
-  ENSURE(ctx, ctx->rf.d_k, 32 * nI);
-  ENSURE(ctx, ctx->rf.d_q, 32 * nI);
-  ENSURE(ctx, ctx->rf.d_t, 24 * nI);
-  if (n_img > 0) {
-    HIPCHK(ctx, hipMemcpyAsync(ctx->rf.d_k.p, kvec4, 32 * (size_t)n_img, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->rf.d_q.p, qvec4, 32 * (size_t)n_img, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->rf.d_t.p, tvec3, 24 * (size_t)n_img, hipMemcpyHostToDevice, ctx->stream));
-  }
+  if (int rc = upload_cameras(ctx, n_img, kvec4, qvec4, tvec3)) return rc;
   return run_device(ctx, pl, ctx->rf.d_k.as<double>(), ctx->rf.d_q.as<double>(), ctx->rf.d_t.as<double>(), *cfg, t0);
+}
+
+void lt_refine_terms_default(lt_refine_terms *t) {
+  if (!t) return;
+  t->use_geometric = 1;          // refinement_config.h:54-79
+  t->use_vp = 0;
+  t->use_heatmap = 0;
+  t->n_samples_heatmap = 10;
+  t->vp_multiplier = 1.0;
+  t->sample_range_min = 0.05;
+  t->sample_range_max = 0.95;
+  t->heatmap_multiplier = 1.0;
+  t->texel_type = LT_TEXEL_F16;  // interpolation's dtype "float16" (cfgs/refinement/default.yaml)
+  t->pad_ = 0;
+}
+
+int lt_refine_set_heatmaps(lt_ctx *ctx, int n, const int32_t *img_ids, const int32_t *h, const int32_t *w,
+                           const void *const *data, int texel_type) {
+  if (!ctx) return LT_ERR_ARGUMENT;
+  HmSet hs;
+  std::string msg;
+  if (check_heatmaps(n, img_ids, h, w, data, texel_type, hs, msg))
+    return fail(ctx, LT_ERR_ARGUMENT, "lt_refine_set_heatmaps: " + msg);
+  lt_refine_clear_heatmaps(ctx);  // a failure below leaves the context without heatmaps
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t px = texel_type == LT_TEXEL_F32 ? 4 : 2;
+  std::vector<RfHm> tab((size_t)n);
+  ENSURE(ctx, ctx->rf.d_hm_tex, std::max<size_t>(px * (size_t)hs.off.back(), 1));
+  for (int i = 0; i < n; ++i) {
+    tab[(size_t)i] = RfHm{hs.off[(size_t)i], h[i], w[i]};
+    HIPCHK(ctx, hipMemcpyAsync(static_cast<char *>(ctx->rf.d_hm_tex.p) + px * (size_t)hs.off[(size_t)i], data[i],
+                               px * (size_t)h[i] * (size_t)w[i], hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (int rc = upload_vec(ctx, ctx->rf.d_hm_tab, tab)) return rc;
+  if (int rc = stream_sync(ctx)) return rc;  // the caller's images may go after the call
+  ctx->rf.hm_type = texel_type;
+  ctx->rf.hm_ids.assign(img_ids, img_ids + n);
+  ctx->rf.hm_h = hs.h;
+  ctx->rf.hm_w = hs.w;
+  return LT_OK;
+}
+
+int lt_refine_clear_heatmaps(lt_ctx *ctx) {
+  if (!ctx) return LT_ERR_ARGUMENT;
+  ++ctx->rf.hm_generation;
+  ctx->rf.hm_ids.clear();
+  ctx->rf.hm_h.clear();
+  ctx->rf.hm_w.clear();
+  return LT_OK;
+}
+
+int64_t lt_refine_heatmaps_generation(lt_ctx *ctx) { return ctx ? (int64_t)ctx->rf.hm_generation : 0; }
+
+int lt_refine_arrays_terms(lt_ctx *ctx, int n_img, const int32_t *img_ids, const double *kvec4, const double *qvec4,
+                           const double *tvec3, int64_t n_tracks, const double *line6, const int64_t *off,
+                           const int32_t *img, const double *line2d4, const double *line3d6, const lt_refine_config *cfg,
+                           const lt_refine_terms *terms, const int32_t *vp_flag, const double *vp3,
+                           const int32_t *view_hw) {
+  if (!ctx) return LT_ERR_ARGUMENT;
+  const std::string who = "lt_refine_arrays_terms";
+  const double t0 = now_ms();
+  std::string msg;
+  if (check_terms(terms, msg)) return fail(ctx, LT_ERR_ARGUMENT, who + ": " + msg);
+  if (!terms->use_vp && !terms->use_heatmap)
+    return lt_refine_arrays(ctx, n_img, img_ids, kvec4, qvec4, tvec3, n_tracks, line6, off, img, line2d4, line3d6, cfg);
+  std::unordered_map<int, int> id2idx;
+  Plan pl;
+  TermsPlan tp;
+  HmSet hs;  // the context's heatmaps as the checks read them
+  hs.type = ctx->rf.hm_type;
+  hs.h = ctx->rf.hm_h;
+  hs.w = ctx->rf.hm_w;
+  for (size_t i = 0; i < ctx->rf.hm_ids.size(); ++i) hs.slot.emplace(ctx->rf.hm_ids[i], (int)i);
+  if (check_config(cfg, msg) || check_cams(n_img, img_ids, kvec4, qvec4, tvec3, id2idx, msg) ||
+      make_plan(id2idx, n_tracks, line6, off, img, line2d4, line3d6, *cfg, pl, msg) ||
+      make_terms_plan(pl, img, *terms, vp_flag, vp3, view_hw, &hs, tp, msg))
+    return fail(ctx, LT_ERR_ARGUMENT, who + ": " + msg);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (int rc = upload_cameras(ctx, n_img, kvec4, qvec4, tvec3)) return rc;
+  return run_device(ctx, pl, ctx->rf.d_k.as<double>(), ctx->rf.d_q.as<double>(), ctx->rf.d_t.as<double>(), *cfg, t0, &tp);
 }
 
 int64_t lt_refine_num(lt_ctx *ctx) { return ctx ? (int64_t)(ctx->rf.out.size() / 15) : 0; }
@@ -345,6 +630,85 @@ int lt_fn_refine_host(int n_img, const int32_t *img_ids, const double *kvec4, co
   std::vector<RfOut> out;
   run_host(pl, kvec4, qvec4, tvec3, *cfg, n_threads, out);
   copy_out(out.data(), (long long)out.size(), params6, seg6, cost2, iters, codes);
+  return LT_OK;
+}
+
+int lt_fn_refine_host_terms(int n_img, const int32_t *img_ids, const double *kvec4, const double *qvec4, const double *tvec3,
+                            int64_t n_tracks, const double *line6, const int64_t *off, const int32_t *img,
+                            const double *line2d4, const double *line3d6, const lt_refine_config *cfg,
+                            const lt_refine_terms *terms, const int32_t *vp_flag, const double *vp3, const int32_t *view_hw,
+                            int n_hm, const int32_t *hm_ids, const int32_t *hm_h, const int32_t *hm_w,
+                            const void *const *hm_data, int n_threads, double *params6, double *seg6, double *cost2,
+                            int32_t *iters, int32_t *codes) {
+  std::string msg;
+  if (check_terms(terms, msg)) {
+    g_host_error = "lt_fn_refine_host_terms: " + msg;
+    return LT_ERR_ARGUMENT;
+  }
+  if (!terms->use_vp && !terms->use_heatmap)
+    return lt_fn_refine_host(n_img, img_ids, kvec4, qvec4, tvec3, n_tracks, line6, off, img, line2d4, line3d6, cfg,
+                             n_threads, params6, seg6, cost2, iters, codes);
+  std::unordered_map<int, int> id2idx;
+  Plan pl;
+  TermsPlan tp;
+  HmSet hs;
+  if ((terms->use_heatmap && check_heatmaps(n_hm, hm_ids, hm_h, hm_w, hm_data, terms->texel_type, hs, msg)) ||
+      check_config(cfg, msg) || check_cams(n_img, img_ids, kvec4, qvec4, tvec3, id2idx, msg) ||
+      make_plan(id2idx, n_tracks, line6, off, img, line2d4, line3d6, *cfg, pl, msg) ||
+      make_terms_plan(pl, img, *terms, vp_flag, vp3, view_hw, &hs, tp, msg)) {
+    g_host_error = "lt_fn_refine_host_terms: " + msg;
+    return LT_ERR_ARGUMENT;
+  }
+  g_host_error.clear();
+  std::vector<RfOut> out;
+  run_host(pl, kvec4, qvec4, tvec3, *cfg, n_threads, out, &tp, &hs);
+  copy_out(out.data(), (long long)out.size(), params6, seg6, cost2, iters, codes);
+  return LT_OK;
+}
+
+int lt_fn_refine_eval_terms(int64_t K, const double *cam11, const double *line2d4, const double params6[6], double alpha,
+                            const lt_refine_terms *terms, const int32_t *vp_flag, const double *vp3, const int32_t *hm_h,
+                            const int32_t *hm_w, const void *const *hm_data, double *residuals, int32_t *failed,
+                            double *cost, double g[4], double H[16]) {
+  std::string msg;
+  if (K < 1 || K > (1 << 28) || !cam11 || !line2d4 || !params6 || !(alpha >= 0.0) || !(alpha <= 700.0) ||
+      check_terms(terms, msg))
+    return LT_ERR_ARGUMENT;
+  Plan pl;  // one track, the supports already in residual order, every support its own camera row
+  pl.n_sup = K;
+  pl.sup_cam.resize((size_t)K);
+  pl.src.resize((size_t)K);
+  std::iota(pl.sup_cam.begin(), pl.sup_cam.end(), 0);
+  std::iota(pl.src.begin(), pl.src.end(), 0ll);
+  pl.l2d.assign(line2d4, line2d4 + 4 * (size_t)K);
+  std::vector<int32_t> ids((size_t)K);
+  std::iota(ids.begin(), ids.end(), 0);
+  TermsPlan tp;
+  HmSet hs;
+  if ((terms->use_heatmap && check_heatmaps((int)K, ids.data(), hm_h, hm_w, hm_data, terms->texel_type, hs, msg)) ||
+      make_terms_plan(pl, ids.data(), *terms, vp_flag, vp3, nullptr, &hs, tp, msg))
+    return LT_ERR_ARGUMENT;
+  std::vector<double> tab((size_t)kRfFields * (size_t)K), ext((size_t)kRfExtFields * (size_t)K);
+  for (int64_t i = 0; i < K; ++i) {
+    const double *c = cam11 + 11 * i;
+    fill_support(c, c + 4, c + 8, line2d4 + 4 * i, tab.data() + i, (long long)K);
+    rf_ext_prep(c, c + 4, tp.vp_flag[(size_t)i] != 0, tp.vp3.data() + 3 * i, ext.data() + i, (long long)K);
+  }
+  const RfTrack tr{0, (int)K, 0};
+  const size_t per = 3 + (size_t)tp.cfg.n_samples;
+  if (residuals) std::fill(residuals, residuals + per * (size_t)K, std::nan(""));
+  with_host_group(tab.data(), ext.data(), (long long)K, tr, alpha, tp, &hs, [&](auto &grp) {
+    if (cost) *cost = grp.cost(params6);
+    double acc[kRfSums];
+    const bool ok = grp.linearise_res(params6, acc, residuals);
+    if (failed) *failed = ok ? 0 : 1;
+    if (H) {
+      int o = 0;
+      for (int i = 0; i < 4; ++i)
+        for (int j = i; j < 4; ++j, ++o) H[4 * i + j] = H[4 * j + i] = acc[o];
+    }
+    if (g) std::copy(acc + 10, acc + 14, g);
+  });
   return LT_OK;
 }
 

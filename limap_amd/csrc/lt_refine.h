@@ -14,10 +14,23 @@
 //   ceresbase/line_projection.h:14-80             Line_ImgFromCam, Line_WorldToPixel
 //   ceresbase/line_dists.h:19-28                  CeresComputeDist2D_cosine
 //   optimize/line_refinement/cost_functions.h:96-127  Ceres_PerpendicularDist2D, Ceres_CosineWeightedPerpendicularDist2D_1D
+// and the two optional terms of limap.optimize.line_refinement (runners/refinement.py), one block per support each:
+//   optimize/line_refinement/cost_functions.h:35-90, refine.cc:87-126   VPConstraintsFunctor, AddVPResiduals
+//   ceresbase/line_dists.h:40-57, ceresbase/line_projection.h:125-134   CeresComputeDist3D_sine, GetDirectionFromVP
+//   optimize/line_refinement/pixel_cost_functions.h:34-107, refine.cc:315-360   MaxHeatmapFunctor, AddHeatmapResiduals
+//   base/linetrack.cc:324-351, base/infinite_line.cc:9-16               ComputeHeatmapSamples, InfiniteLine2d(p, direc)
+//   ceresbase/line_transforms.h:55-72                                   Ceres_IntersectLineCoordinates
+//   ceresbase/interpolation.h:526-579, features/featuremap.h:71-85      BiLinearInterpolator over a Grid2D, one node
 // ASSUMPTIONS of the same kind as lt_svd.h (the libraries are not part of limap; their published procedures are
 // followed): Eigen's Quaternion(Matrix3) and Quaternion::toRotationMatrix, Ceres' QuaternionToRotation
 // (QuaternionToScaledRotation, then the division by the squared norm), CauchyLoss, ScaledLoss and the Jet rule
-// d|x|/dx = +1 at x = 0.  The minimiser is this project's own definition, not Ceres' iterates.
+// d|x|/dx = +1 at x = 0; for the two terms Ceres' QuaternionRotatePoint (the scale 1 / |q|, then
+// UnitQuaternionRotatePoint in its cross-product form, rotation.h of Ceres 2.1 and later), CrossProduct, TrivialLoss,
+// HuberLoss (rho' = max(DBL_MIN, a / sqrt s) outside a^2), Grid2D::GetValue (rows and columns clamped to the image), the
+// Jet of an interpolated value (dfdr dr + dfdc dc), and Eigen's normalized() of a 2- and a 3-vector taken as
+// v / sqrt((x^2 + y^2) + z^2).  `const int row = std::floor(r)` overflows the int for |r| >= 2^31 upstream; here the
+// floor stays a double and is clamped to [-3, h] before the conversion, which reads the same texels wherever upstream's
+// conversion is defined.  The minimiser is this project's own definition, not Ceres' iterates.
 #pragma once
 
 #include "lt_geom.h"
@@ -32,6 +45,9 @@ constexpr double kRfMu0 = 1e4;          // initial trust-region radius (Ceres' d
 constexpr double kRfMuMax = 1e16, kRfMuMin = 1e-32;
 constexpr double kRfMinRatio = 1e-3;    // min_relative_decrease
 constexpr double kRfDMin = 1e-6, kRfDMax = 1e32;  // min / max_lm_diagonal
+constexpr int kRfTermWidth = 16;        // lanes per track of k_refine_lm_terms and of its host twin (the choice: DESIGN §19)
+constexpr int kRfExtFields = 8;         // doubles per support of the terms' table: unit qvec[4], VP direction[3], VP flag
+constexpr double kRfHuberA = 0.001;     // HuberLoss(0.001) (refinement_config.h:23)
 
 // termination codes of a track (lt_refine_get)
 enum RfCode : int {
@@ -41,6 +57,7 @@ enum RfCode : int {
   kRfBadPivot = 3,   // a Cholesky pivot is not positive or not finite
   kRfBadModel = 4,   // the model decrease is not positive or not finite
   kRfConstant = 5,   // constant_line, or fewer than min_num_images images: not optimised, segment re-cut
+  kRfEvalFailed = 6, // the cost at the initial point is not finite (a heatmap sample failed): not optimised, segment re-cut
 };
 
 // a track as the kernels see it: supports [s0, s0 + n) of the scene's supports (residual order), line, flags
@@ -280,6 +297,268 @@ LT_HD double rf_cost_term(const RfSup &s, const double dm[6], double alpha) {
   return rf_rho(s.weight, r[0] * r[0] + r[1] * r[1]);
 }
 
+// ---- the VP and the heatmap term (limap.optimize.line_refinement with use_vp / use_heatmap) ----
+// the heatmap of an image in the packed texel buffer
+struct RfHm {
+  long long off;  // first texel
+  int h, w;
+};
+static_assert(sizeof(RfHm) == 16, "RfHm layout");
+template <class Tx>
+struct RfGrid {
+  const Tx *tex;
+  int h, w;
+};
+// the terms' parameters as the kernels read them
+struct RfTermCfg {
+  double vp_multiplier, heatmap_multiplier;
+  double heatmap_den;        // n_samples_heatmap / 10.0
+  double t0, interval;       // t_j = t0 + interval * j, interval = (max - min) / (n - 1) (linetrack.cc:329-335)
+  int n_samples, use_geometric, use_vp, use_heatmap;
+};
+// what a support carries for the terms besides RfSup (kRfExtFields doubles, SoA like the support table)
+struct RfExt {
+  double q[4];    // the view's quaternion times Ceres' scale 1 / |q|
+  double vp[3];   // the direction of the support's vanishing point, normalised as the sine normalises it
+  double has_vp;  // 1.0 where the VPResult labels the support's line
+};
+LT_HD RfExt rf_load_ext(const double *ext, long long stride, long long s) {
+  RfExt e;
+  for (int i = 0; i < 4; ++i) e.q[i] = ext[(long long)i * stride + s];
+  for (int i = 0; i < 3; ++i) e.vp[i] = ext[(long long)(4 + i) * stride + s];
+  e.has_vp = ext[7 * stride + s];
+  return e;
+}
+
+// the constants of a support's VP block: CameraPose's normalisation (camera.h:94-95) and the scale of Ceres'
+// QuaternionRotatePoint; GetDirectionFromVP (line_projection.h:125-134) and the normalisation CeresComputeDist3D_sine
+// applies to its second argument (line_dists.h:42-50).  F[f] goes to out[f * stride]
+LT_HD void rf_ext_prep(const double *k4, const double *q4, bool has_vp, const double *vp3, double *out, long long stride) {
+  double q[4];
+  const double n0 = sqrt((q4[0] * q4[0] + q4[2] * q4[2]) + (q4[1] * q4[1] + q4[3] * q4[3]));
+  for (int i = 0; i < 4; ++i) q[i] = n0 > 0.0 ? q4[i] / n0 : q4[i];
+  const double scale = 1.0 / sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+  for (int i = 0; i < 4; ++i) out[(long long)i * stride] = q[i] * scale;
+  double d[3] = {0.0, 0.0, 0.0};
+  if (has_vp) {
+    d[0] = vp3[0] / k4[0] - (k4[2] / k4[0]) * vp3[2];
+    d[1] = vp3[1] / k4[1] - (k4[3] / k4[1]) * vp3[2];
+    d[2] = vp3[2];
+    const double n = sqrt(((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) + kEps);
+    for (int i = 0; i < 3; ++i) d[i] = d[i] / n;
+    const double n2 = sqrt(((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) + kEps);
+    for (int i = 0; i < 3; ++i) d[i] = d[i] / n2;
+  }
+  for (int i = 0; i < 3; ++i) out[(long long)(4 + i) * stride] = d[i];
+  out[7 * stride] = has_vp ? 1.0 : 0.0;
+}
+
+// the residual of a VP block (cost_functions.h:71-84): the sine between the line's direction in the camera frame and
+// the VP's direction
+template <class T>
+LT_HD T rf_vp_residual(const RfExt &e, const T dm[6]) {
+  const double *q = e.q;
+  T uv0 = dm[2] * q[2] - dm[1] * q[3];  // UnitQuaternionRotatePoint: uv = q.xyz x pt, doubled
+  T uv1 = dm[0] * q[3] - dm[2] * q[1];
+  T uv2 = dm[1] * q[1] - dm[0] * q[2];
+  uv0 = uv0 + uv0; uv1 = uv1 + uv1; uv2 = uv2 + uv2;
+  T r0 = dm[0] + uv0 * q[0], r1 = dm[1] + uv1 * q[0], r2 = dm[2] + uv2 * q[0];
+  r0 = r0 + (uv2 * q[2] - uv1 * q[3]);
+  r1 = r1 + (uv0 * q[3] - uv2 * q[1]);
+  r2 = r2 + (uv1 * q[1] - uv0 * q[2]);
+  const T n1 = rf_sqrt(((r0 * r0 + r1 * r1) + r2 * r2) + kEps);
+  const T a0 = r0 / n1, a1 = r1 / n1, a2 = r2 / n1;
+  const T c0 = a1 * e.vp[2] - a2 * e.vp[1], c1 = a2 * e.vp[0] - a0 * e.vp[2], c2 = a0 * e.vp[1] - a1 * e.vp[0];
+  T sine = rf_sqrt(((c0 * c0 + c1 * c1) + c2 * c2) + kEps);
+  if (rf_val(sine) > 1.0) rf_set(sine, 1.0);
+  return sine;
+}
+
+// Line_WorldToPixel with the normalisation of Line_ImgFromCam (line_projection.h:43-47): the expressions rf_residual
+// starts with
+template <class T>
+LT_HD void rf_project(const RfSup &s, const T dm[6], T c[3]) {
+  for (int i = 0; i < 3; ++i) {
+    const double *a = s.A + 6 * i;
+    c[i] = ((((dm[0] * a[0] + dm[1] * a[1]) + dm[2] * a[2]) + dm[3] * a[3]) + dm[4] * a[4]) + dm[5] * a[5];
+  }
+  const T cn = rf_sqrt(((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]) + kEps);
+  c[0] = c[0] / cn; c[1] = c[1] / cn; c[2] = c[2] / cn;
+}
+
+// sample line j of a support (ComputeHeatmapSamples, linetrack.cc:338-349): InfiniteLine2d(start + t (end - start),
+// perp_direction()); the caller has checked that the support's length is positive
+LT_HD void rf_sample_line(const RfSup &s, double t, double coor[3]) {
+  const double ex = s.x2 - s.x1, ey = s.y2 - s.y1;
+  const double n = sqrt(ex * ex + ey * ey);
+  const double d0 = ex / n, d1 = ey / n;  // direction()
+  const double p0 = d1, p1 = -d0;         // perp_direction()
+  const double px = s.x1 + t * ex, py = s.y1 + t * ey;
+  const double c0 = p1, c1 = -p0, c2 = (-p1) * px + p0 * py;
+  const double cn = sqrt((c0 * c0 + c1 * c1) + c2 * c2);
+  coor[0] = c0 / cn; coor[1] = c1 / cn; coor[2] = c2 / cn;
+}
+
+// texels widen exactly: binary16 from its bits (no half type on the host side), binary32 by the conversion
+LT_HD double rf_widen(unsigned short h) {
+  const unsigned long long sign = (unsigned long long)(h >> 15) << 63;
+  const int e = (h >> 10) & 31, m = h & 1023;
+  if (e == 0) {  // zero and subnormals: m 2^-24
+    const double v = (double)m * 0x1p-24;
+    return sign ? -v : v;
+  }
+  const unsigned long long ex = (unsigned long long)(e == 31 ? 2047 : e - 15 + 1023);
+  const unsigned long long bits = sign | (ex << 52) | ((unsigned long long)m << 42);
+  union { unsigned long long u; double d; } cv;
+  cv.u = bits;
+  return cv.d;
+}
+LT_HD double rf_widen(float f) { return (double)f; }
+// Grid2D::GetValue: rows and columns clamped to the image
+template <class Tx>
+LT_HD double rf_texel(const RfGrid<Tx> &g, int r, int c) {
+  r = r < 0 ? 0 : (r > g.h - 1 ? g.h - 1 : r);
+  c = c < 0 ? 0 : (c > g.w - 1 ? g.w - 1 : c);
+  return rf_widen(g.tex[(long long)r * g.w + c]);
+}
+LT_HD double rf_bilinear(double dx, double dy, double ll, double lr, double ul, double ur) {
+  const double v0 = (1.0 - dx) * ll + dx * lr, v1 = (1.0 - dx) * ul + dx * ur;
+  return (1.0 - dy) * v0 + dy * v1;
+}
+// floor(r) and floor(c) as indices; a floor outside [-3, size] reads the texels of that bound (the clamp of rf_texel)
+LT_HD void rf_cell(double r, double c, int h, int w, int *row, int *col, double *dy, double *dx) {
+  const double fr = floor(r), fc = floor(c);
+  *dy = r - fr;
+  *dx = c - fc;
+  *row = (int)(!(fr >= -3.0) ? -3.0 : (fr > (double)h ? (double)h : fr));  // (a NaN, which no caller passes, reads row 0)
+  *col = (int)(!(fc >= -3.0) ? -3.0 : (fc > (double)w ? (double)w : fc));
+}
+// BiLinearInterpolator::Evaluate (interpolation.h:531-564) at (r, c): the value from 4 texels; as a Jet the value and
+// upstream's forward differences, 8 texels, all loaded before the first use
+template <class Tx>
+LT_HD double rf_interp(const RfGrid<Tx> &g, double r, double c) {
+  int row, col;
+  double dy, dx;
+  rf_cell(r, c, g.h, g.w, &row, &col, &dy, &dx);
+  const double ll = rf_texel(g, row, col), lr = rf_texel(g, row, col + 1);
+  const double ul = rf_texel(g, row + 1, col), ur = rf_texel(g, row + 1, col + 1);
+  return rf_bilinear(dx, dy, ll, lr, ul, ur);
+}
+template <class Tx>
+LT_HD Rf4 rf_interp(const RfGrid<Tx> &g, const Rf4 &r, const Rf4 &c) {
+  int row, col;
+  double dy, dx;
+  rf_cell(r.v, c.v, g.h, g.w, &row, &col, &dy, &dx);
+  const double ll = rf_texel(g, row, col), lr = rf_texel(g, row, col + 1);
+  const double ul = rf_texel(g, row + 1, col), ur = rf_texel(g, row + 1, col + 1);
+  const double lrx = rf_texel(g, row, col + 2), urx = rf_texel(g, row + 1, col + 2);
+  const double uly = rf_texel(g, row + 2, col), ury = rf_texel(g, row + 2, col + 1);
+  const double f = rf_bilinear(dx, dy, ll, lr, ul, ur);
+  const double dfdr = rf_bilinear(dx, dy, ul, ur, uly, ury) - f;
+  const double dfdc = rf_bilinear(dx, dy, lr, lrx, ur, urx) - f;
+  return Rf4{f, {dfdr * r.d[0] + dfdc * c.d[0], dfdr * r.d[1] + dfdc * c.d[1], dfdr * r.d[2] + dfdc * c.d[2],
+                 dfdr * r.d[3] + dfdc * c.d[3]}};
+}
+
+// one residual of a heatmap block (pixel_cost_functions.h:93-103): 1 - f at the intersection of the projected line c
+// with the sample line k (Ceres_IntersectLineCoordinates).  false: the evaluation fails -- |p_homo[2]| < EPS, or not a
+// number (a projection that coincides with the sample line), where upstream reads an unset xy
+template <class T, class Tx>
+LT_HD bool rf_heat_residual(const T c[3], const double k[3], const RfGrid<Tx> &g, T *res) {
+  T p0 = c[1] * k[2] - c[2] * k[1], p1 = c[2] * k[0] - c[0] * k[2], p2 = c[0] * k[1] - c[1] * k[0];
+  const T n = rf_sqrt((p0 * p0 + p1 * p1) + p2 * p2);
+  p0 = p0 / n; p1 = p1 / n; p2 = p2 / n;
+  if (!(rf_abs(rf_val(p2)) >= kEps)) {
+    rf_set(*res, 0.0);
+    return false;
+  }
+  const T x = p0 / p2, y = p1 / p2;
+  *res = 1.0 - rf_interp(g, y, x);
+  return true;
+}
+
+// ScaledLoss(HuberLoss(a), w) over s, the squared norm of a block, and its derivative
+LT_HD double rf_huber(double weight, double s) {
+  const double b = kRfHuberA * kRfHuberA;
+  return s > b ? weight * ((2.0 * kRfHuberA) * sqrt(s) - b) : weight * s;
+}
+LT_HD double rf_huber1(double weight, double s) {
+  const double b = kRfHuberA * kRfHuberA;
+  if (!(s > b)) return weight;
+  const double m = kRfHuberA / sqrt(s);
+  return weight * (m > 2.2250738585072014e-308 ? m : 2.2250738585072014e-308);
+}
+// the weights of a support's VP and heatmap blocks (refine.cc:104, 338-339)
+LT_HD double rf_vp_weight(const RfSup &s, const RfTermCfg &tc) { return s.weight * tc.vp_multiplier; }
+LT_HD double rf_heat_weight(const RfSup &s, const RfTermCfg &tc) { return (s.weight * tc.heatmap_multiplier) / tc.heatmap_den; }
+
+// the cost of a support: geometric + VP + heatmap, in that order; a heatmap block sums its samples in ascending order
+// before the loss.  +inf where a sample fails
+template <bool HM, class Tx>
+LT_HD double rf_cost_terms(const RfSup &s, const RfExt &e, const RfGrid<Tx> &g, const RfTermCfg &tc, const double dm[6],
+                           double alpha) {
+  double cost = 0.0;
+  if (tc.use_geometric) cost = cost + rf_cost_term(s, dm, alpha);
+  if (tc.use_vp && e.has_vp != 0.0) {
+    const double r = rf_vp_residual<double>(e, dm);
+    cost = cost + rf_vp_weight(s, tc) * (r * r);
+  }
+  if (HM) {
+    double c[3], sq = 0.0;
+    rf_project<double>(s, dm, c);
+    bool ok = true;
+    for (int j = 0; j < tc.n_samples; ++j) {
+      double k[3], r;
+      rf_sample_line(s, tc.t0 + tc.interval * (double)j, k);
+      ok = rf_heat_residual<double, Tx>(c, k, g, &r) && ok;
+      sq = sq + r * r;
+    }
+    cost = ok ? cost + rf_huber(rf_heat_weight(s, tc), sq) : __builtin_inf();
+  }
+  return cost;
+}
+
+// rf_accumulate with the terms: the blocks of a support add to acc in the order geometric, VP, heatmap; a heatmap block
+// first sums its samples' products in ascending order, then applies the loss' derivative.  res (host, tests): the
+// residuals of the support, 2 geometric, 1 VP, n_samples heatmap, NaN where a block is absent.  false where a heatmap
+// sample fails (its sample adds nothing)
+template <bool HM, class Tx>
+LT_HD bool rf_accumulate_terms(const RfSup &s, const RfExt &e, const RfGrid<Tx> &g, const RfTermCfg &tc, const Rf4 dm[6],
+                               double alpha, double acc[kRfSums], double *res = nullptr) {
+  if (tc.use_geometric) rf_accumulate(s, dm, alpha, acc, res);
+  if (tc.use_vp && e.has_vp != 0.0) {
+    const Rf4 r = rf_vp_residual<Rf4>(e, dm);
+    const double rho1 = rf_vp_weight(s, tc);
+    if (res) res[2] = r.v;
+    int o = 0;
+    for (int i = 0; i < 4; ++i)
+      for (int j = i; j < 4; ++j, ++o) acc[o] = acc[o] + rho1 * (r.d[i] * r.d[j]);
+    for (int i = 0; i < 4; ++i) acc[10 + i] = acc[10 + i] + rho1 * (r.d[i] * r.v);
+  }
+  bool ok = true;
+  if (HM) {
+    Rf4 c[3];
+    rf_project<Rf4>(s, dm, c);
+    double blk[kRfSums], sq = 0.0;
+    for (int o = 0; o < kRfSums; ++o) blk[o] = 0.0;
+    for (int n = 0; n < tc.n_samples; ++n) {
+      double k[3];
+      Rf4 r;
+      rf_sample_line(s, tc.t0 + tc.interval * (double)n, k);
+      ok = rf_heat_residual<Rf4, Tx>(c, k, g, &r) && ok;
+      if (res) res[3 + n] = r.v;
+      sq = sq + r.v * r.v;
+      int o = 0;
+      for (int i = 0; i < 4; ++i)
+        for (int j = i; j < 4; ++j, ++o) blk[o] = blk[o] + r.d[i] * r.d[j];
+      for (int i = 0; i < 4; ++i) blk[10 + i] = blk[10 + i] + r.d[i] * r.v;
+    }
+    const double rho1 = rf_huber1(rf_heat_weight(s, tc), sq);
+    for (int o = 0; o < kRfSums; ++o) acc[o] = acc[o] + rho1 * blk[o];
+  }
+  return ok;
+}
+
 // the point and its four local directions: u + du_i (0, e_i) (x) u, w + dw (-w1, w0)
 LT_HD void rf_seed(const double p[6], Rf4 u[4], Rf4 w[2]) {
   u[0] = Rf4{p[0], {-p[1], -p[2], -p[3], 0.0}};
@@ -360,11 +639,10 @@ LT_HD double rf_grow(double mu, double ratio) {
 
 // the minimiser of one track.  G supplies the two reductions over the track's supports -- cost(p) and
 // linearise(p, acc) -- as values every lane of a group holds bit for bit (device: shuffles; host: rf_tree_host), so
-// every branch below is uniform over the group.  An iteration counts whether its step was accepted or not
+// every branch below is uniform over the group.  An iteration counts whether its step was accepted or not.
+// rf_lm_from: the loop after the first cost evaluation F (the cost at p)
 template <class G>
-LT_HD void rf_lm(G &grp, bool constant, int max_iter, double p[6], double *cost0, double *cost1, int *iters, int *code_out) {
-  double F = grp.cost(p);
-  *cost0 = F;
+LT_HD void rf_lm_from(G &grp, double F, bool constant, int max_iter, double p[6], double *cost1, int *iters, int *code_out) {
   int it = 0, code = kRfMaxIter;
   if (constant) {
     code = kRfConstant;
@@ -401,6 +679,29 @@ LT_HD void rf_lm(G &grp, bool constant, int max_iter, double p[6], double *cost0
   *cost1 = F;
   *iters = it;
   *code_out = code;
+}
+template <class G>
+LT_HD void rf_lm(G &grp, bool constant, int max_iter, double p[6], double *cost0, double *cost1, int *iters, int *code_out) {
+  const double F = grp.cost(p);
+  *cost0 = F;
+  rf_lm_from(grp, F, constant, max_iter, p, cost1, iters, code_out);
+}
+
+// rf_lm with the VP and heatmap terms: a cost evaluation in which a sample fails is +inf (non-finite texels make it
+// +inf or NaN), so the ratio test rejects the step and the radius shrinks; at the initial point the track ends with
+// kRfEvalFailed, its parameters unchanged, as Ceres' FAILURE leaves the line
+template <class G>
+LT_HD void rf_lm_terms(G &grp, bool constant, int max_iter, double p[6], double *cost0, double *cost1, int *iters,
+                       int *code_out) {
+  const double F = grp.cost(p);
+  *cost0 = F;
+  if (!(F <= kMaxDist)) {
+    *cost1 = F;
+    *iters = 0;
+    *code_out = constant ? kRfConstant : kRfEvalFailed;
+    return;
+  }
+  rf_lm_from(grp, F, constant, max_iter, p, cost1, iters, code_out);
 }
 
 // MinimalInfiniteLine3d(InfiniteLine3d(line)) (infinite_line.cc:67-71,180-223); the caller has checked length > 0
@@ -511,17 +812,20 @@ LT_HD void rf_rank_test(const double *l3d6, long long n, long long i, d3 pref, d
   *is_hi = first && lt <= hi && hi < lt + eq;
 }
 
-// the fixed xor tree over kRfWidth partial sums (host twin of the shuffles of k_refine_lm)
-inline void rf_tree_host(double part[kRfWidth][kRfSums], int n_sums, double out[kRfSums]) {
-  for (int m = kRfWidth / 2; m >= 1; m >>= 1) {
-    double nxt[kRfWidth][kRfSums];
-    for (int l = 0; l < kRfWidth; ++l)
+// the fixed xor tree over W partial sums (host twin of the shuffles of k_refine_lm and k_refine_lm_terms)
+template <int W>
+inline void rf_tree_host(double part[W][kRfSums], int n_sums, double out[kRfSums]) {
+  for (int m = W / 2; m >= 1; m >>= 1) {
+    double nxt[W][kRfSums];
+    for (int l = 0; l < W; ++l)
       for (int c = 0; c < n_sums; ++c) nxt[l][c] = part[l][c] + part[l ^ m][c];
-    for (int l = 0; l < kRfWidth; ++l)
+    for (int l = 0; l < W; ++l)
       for (int c = 0; c < n_sums; ++c) part[l][c] = nxt[l][c];
   }
   for (int c = 0; c < n_sums; ++c) out[c] = part[0][c];
 }
+
+static_assert(kRfBlock % kRfTermWidth == 0 && (kRfTermWidth & (kRfTermWidth - 1)) == 0, "a group is a power-of-two part of a wave");
 
 // the scene's tables on the device
 struct RfDev {
@@ -534,10 +838,24 @@ struct RfDev {
   int max_iter, num_outliers;
 };
 
+// the terms' tables on the device: the supports' extra fields and heatmap slots, the heatmap table and the texels the
+// context holds (RefineState)
+struct RfDevTerms {
+  const double *ext;     // kRfExtFields x stride
+  const int *sup_hm;     // per support its row of hm (heatmap term only)
+  const RfHm *hm;
+  const void *texels;    // unsigned short (binary16) or float
+  RfTermCfg cfg;
+};
+
 void launch_refine_prep(hipStream_t st, const double *kvec, const double *qvec, const double *tvec, const int *sup_cam,
                         const double *l2d4, long long n_sup, double *sup_tab, long long stride, const double *line6,
                         long long n_tracks, RfOut *out);
 void launch_refine_lm(hipStream_t st, const RfDev &dev, RfOut *out);
 void launch_refine_cut(hipStream_t st, const RfDev &dev, RfOut *out);
+void launch_refine_prep_terms(hipStream_t st, const double *kvec, const double *qvec, const int *sup_cam,
+                              const int *vp_flag, const double *vp3, long long n_sup, double *ext, long long stride);
+// texel_f32: the texels are float, not binary16; only read with cfg.use_heatmap
+void launch_refine_lm_terms(hipStream_t st, const RfDev &dev, const RfDevTerms &terms, bool texel_f32, RfOut *out);
 
 }  // namespace lt

@@ -5,14 +5,23 @@
     ba_engine = optimize.solve_line_bundle_adjustment(cfg_ba, imagecols, linetracks, max_num_iterations=200)
     linetracks_map = ba_engine.GetOutputLineTracks(num_outliers=cfg["refinement"]["num_outliers_aggregator"])
 
-and, per track, `solve_line_refinement` / `line_refinement` (optimize/line_refinement) with their geometric terms.  With
-constant intrinsics and poses every track is its own 4-degree-of-freedom problem; all of them run in one launch of the
-HIP kernels of lt_kernels_refine.hip.  limap's cost, parameterisation, weights, residual order and
+and, per track, `solve_line_refinement` / `line_refinement` (optimize/line_refinement) with their geometric, VP and
+heatmap terms -- what limap.runners.refinement calls (cfgs/refinement/default.yaml):
+
+    vpresults = vplib.get_vp_detector(cfg["vpdet"]).detect_vp_all_images(all_2d_lines, camviews)
+    tracks = optimize.line_refinement(cfg["refinement"], tracks, imagecols, heatmap_dir, vpresults=vpresults)
+
+With constant intrinsics and poses every track is its own 4-degree-of-freedom problem; all of them run in one launch of
+the HIP kernels of lt_kernels_refine.hip.  The heatmaps (`heatmap_{img_id}.npy` in heatmap_dir,
+or `heatmaps={img_id: array}`) are loaded once, rounded to `dtype` ("float16", upstream's default, or "float32") by
+numpy's astype, uploaded once and sampled by the kernel.  limap's cost, parameterisation, weights, residual order and
 segment cut are restated; **the minimiser is this project's deterministic Levenberg-Marquardt definition: refined lines
 are minimisers of upstream's cost, not the iterates of a particular Ceres run.**
 
 Not built, and rejected with a ValueError that names the key: constant_intrinsics=False, constant_pose=False, point
-tracks, use_vp, use_heatmap, use_feature.
+tracks, use_feature (p_patches, p_features); use_vp and use_heatmap on the hybrid bundle adjustment, which has no such
+terms upstream either.  A track whose cost cannot be evaluated at its initial line (a heatmap sample line parallel to
+the projection) ends with TERMINATION 6 and keeps its line, re-cut.
 
 `host_threads=N` on the solve functions runs the documented host path (lt_fn_refine_host: the same inline functions in
 plain C++, bit-identical results) on N OpenMP threads instead of the device; it is a request, never a fallback -- without
@@ -26,27 +35,34 @@ import numpy as np
 from . import _capi
 from .base import Line3d, LineTrack
 
-__all__ = ["HybridBAConfig", "RefinementConfig", "HybridBAEngine", "RefinementEngine", "solve_line_bundle_adjustment",
-           "solve_line_refinement", "line_refinement", "TERMINATION"]
+__all__ = ["HybridBAConfig", "RefinementConfig", "HybridBAEngine", "RefinementEngine", "Heatmaps",
+           "solve_line_bundle_adjustment", "solve_line_refinement", "line_refinement", "TERMINATION"]
 
-TERMINATION = {0: "max_num_iterations", 1: "radius", 2: "zero_gradient", 3: "pivot", 4: "model_decrease", 5: "constant"}
-_UNSUPPORTED_TRUE = ("use_vp", "use_heatmap", "use_feature")
+TERMINATION = {0: "max_num_iterations", 1: "radius", 2: "zero_gradient", 3: "pivot", 4: "model_decrease", 5: "constant",
+               6: "evaluation_failed"}
+_TEXELS = {"float16": (np.float16, _capi.TEXEL_F16), "float32": (np.float32, _capi.TEXEL_F32)}
 
 
 class RefinementConfig:
-    """optimize/line_refinement/refinement_config.h:18-90 -- the keys the geometric terms read (ASSIGN_PYDICT_ITEM: a
-    present key overrides, unknown keys are ignored)."""
+    """optimize/line_refinement/refinement_config.h:18-90 -- the keys the geometric, VP and heatmap terms read
+    (ASSIGN_PYDICT_ITEM: a present key overrides, unknown keys are ignored)."""
     _KEYS = dict(use_geometric=bool, min_num_images=int, num_outliers_aggregate=int, geometric_alpha=float,
-                 print_summary=bool)
+                 print_summary=bool, vp_multiplier=float, sample_range_min=float, sample_range_max=float,
+                 n_samples_heatmap=int, heatmap_multiplier=float)
+    _UNSUPPORTED_TRUE = ("use_feature",)
 
     def __init__(self, cfg=None):
         self.use_geometric, self.min_num_images, self.num_outliers_aggregate = True, 4, 2
         self.geometric_alpha, self.print_summary = 10.0, True
+        self.vp_multiplier, self.heatmap_multiplier, self.n_samples_heatmap = 1.0, 1.0, 10
+        self.sample_range_min, self.sample_range_max = 0.05, 0.95
         self.max_num_iterations = 100  # solver_options.max_num_iterations
         # not keys of upstream's C++ configuration: the python callers read them from the same dict
         self.num_outliers_aggregator = 2
         self.use_vp = self.use_heatmap = self.use_feature = False
-        self._assign(cfg, dict(self._KEYS, num_outliers_aggregator=int, use_vp=bool, use_heatmap=bool, use_feature=bool))
+        self.dtype = "float16"  # the texels of the heatmaps (line_refinement.py:27: cfg["dtype"])
+        self._assign(cfg, dict(self._KEYS, num_outliers_aggregator=int, use_vp=bool, use_heatmap=bool, use_feature=bool,
+                               dtype=str))
 
     def _assign(self, cfg, keys):
         if cfg is None:
@@ -58,11 +74,26 @@ class RefinementConfig:
                 setattr(self, k, typ(cfg[k]))
 
     def _check(self):
-        for k in _UNSUPPORTED_TRUE:
+        for k in self._UNSUPPORTED_TRUE:
             if getattr(self, k):
-                raise ValueError(f"limap_amd.optimize: {k}=True is not built (geometric terms only)")
-        if not self.use_geometric:
-            raise ValueError("limap_amd.optimize: use_geometric=False leaves no residual (geometric terms only)")
+                raise ValueError(f"limap_amd.optimize: {k}=True is not built here")
+        if not (self.use_geometric or self.use_vp or self.use_heatmap):
+            raise ValueError("limap_amd.optimize: use_geometric=False leaves no residual")
+        if self.use_heatmap and self.dtype not in _TEXELS:
+            raise ValueError(f"limap_amd.optimize: dtype={self.dtype!r} is not built (float16 or float32 texels)")
+
+    def _terms(self):
+        """lt_refine_terms, or None where neither the VP nor the heatmap term is on"""
+        if not (self.use_vp or self.use_heatmap):
+            return None
+        t = _capi.LtRefineTerms()
+        _capi.load_library().lt_refine_terms_default(C.byref(t))
+        t.use_geometric, t.use_vp, t.use_heatmap = int(self.use_geometric), int(self.use_vp), int(self.use_heatmap)
+        t.n_samples_heatmap, t.vp_multiplier = int(self.n_samples_heatmap), float(self.vp_multiplier)
+        t.sample_range_min, t.sample_range_max = float(self.sample_range_min), float(self.sample_range_max)
+        t.heatmap_multiplier = float(self.heatmap_multiplier)
+        t.texel_type = _TEXELS[self.dtype][1] if self.use_heatmap else _capi.TEXEL_F16
+        return t
 
     def _struct(self, num_outliers, constant_line=False):
         c = _capi.LtRefineConfig()
@@ -75,6 +106,7 @@ class RefinementConfig:
 
 class HybridBAConfig(RefinementConfig):
     """optimize/hybrid_bundle_adjustment/hybrid_bundle_adjustment_config.h:17-49"""
+    _UNSUPPORTED_TRUE = ("use_vp", "use_heatmap", "use_feature")  # no such terms in the hybrid bundle adjustment
     _BA_KEYS = dict(constant_intrinsics=bool, constant_principal_point=bool, constant_pose=bool, constant_point=bool,
                     constant_line=bool, lw_point=float)
 
@@ -140,8 +172,45 @@ def cut_segment(params6, line3d6, num_outliers):
     return seg
 
 
-def refine_arrays(cams, tracks_csr, cfg_struct, host_threads=None, ctx=None):
-    """One call of lt_refine_arrays (device) or lt_fn_refine_host (host_threads given) -> dict of per-track results."""
+class Heatmaps:
+    """The heatmaps of a scene as the native calls take them: {img_id: (h, w) array} rounded to the texel type by
+    numpy's astype (float64 -> float16 rounds once; upstream goes through float, which can differ in the last bit of
+    a rare value: DESIGN.md section 19)."""
+
+    def __init__(self, heatmaps, dtype="float16"):
+        if dtype not in _TEXELS:
+            raise ValueError(f"limap_amd.optimize: dtype={dtype!r} is not built (float16 or float32 texels)")
+        np_type, self.texel_type = _TEXELS[dtype]
+        self.ids = np.array(sorted(int(i) for i in heatmaps), np.int32)
+        self.arrays = [np.ascontiguousarray(np.asarray(heatmaps[int(i)]).astype(np_type, copy=False)) for i in self.ids]
+        for i, a in zip(self.ids, self.arrays):
+            if a.ndim != 2 or a.size == 0:
+                raise ValueError(f"limap_amd.optimize: the heatmap of image {i} is not a non-empty 2D array")
+        self.h = np.array([a.shape[0] for a in self.arrays], np.int32)
+        self.w = np.array([a.shape[1] for a in self.arrays], np.int32)
+        self.ptrs = (C.c_void_p * max(len(self.arrays), 1))(*[a.ctypes.data for a in self.arrays])
+
+    def args(self):
+        p = _capi.ptr
+        return len(self.ids), p(self.ids, C.c_int32), p(self.h, C.c_int32), p(self.w, C.c_int32), self.ptrs
+
+    def upload(self, ctx):
+        """once per context: a second call with the same object finds them resident, which the context's generation
+        counter confirms (it moves with every set and clear, also one made through the C ABI directly or one whose
+        copy failed)"""
+        gen = ctx.L.lt_refine_heatmaps_generation(ctx.h)
+        if getattr(ctx, "_refine_heatmaps", None) != (id(self), gen):
+            ctx._refine_heatmaps = None
+            ctx.chk(ctx.L.lt_refine_set_heatmaps(ctx.h, *self.args(), self.texel_type))
+            ctx._refine_heatmaps_owner = self  # keeps id(self) from being reused
+            ctx._refine_heatmaps = (id(self), ctx.L.lt_refine_heatmaps_generation(ctx.h))
+
+
+def refine_arrays(cams, tracks_csr, cfg_struct, host_threads=None, ctx=None, terms=None, vp=None, view_hw=None,
+                  heatmaps=None):
+    """One call of lt_refine_arrays (device) or lt_fn_refine_host (host_threads given) -> dict of per-track results.
+    terms (lt_refine_terms) selects the *_terms entry points: vp = (flag (M,), vp3 (M, 3)) per support in list order,
+    view_hw (n_img, 2) or None, heatmaps a Heatmaps."""
     ids, k, q, t = cams
     line6, off, img, l2, l3 = tracks_csr
     T = len(off) - 1
@@ -153,12 +222,29 @@ def refine_arrays(cams, tracks_csr, cfg_struct, host_threads=None, ctx=None):
             p(off, C.c_int64), p(img, C.c_int32), p(l2, C.c_double), p(l3, C.c_double), C.byref(cfg_struct))
     outs = (p(P, C.c_double), p(seg, C.c_double), p(cost, C.c_double), p(it, C.c_int32), p(code, C.c_int32))
     timers = None
+    if terms is not None:
+        flag, vp3 = vp if vp is not None else (np.zeros(len(img), np.int32), np.zeros((len(img), 3)))
+        flag, vp3 = np.ascontiguousarray(flag, np.int32), np.ascontiguousarray(vp3, np.float64)
+        hw = None if view_hw is None else np.ascontiguousarray(view_hw, np.int32)
+        targs = (C.byref(terms), p(flag, C.c_int32), p(vp3, C.c_double), None if hw is None else p(hw, C.c_int32))
+        if terms.use_heatmap and heatmaps is None:
+            raise ValueError("limap_amd.optimize: use_heatmap without heatmaps")
     if host_threads is not None:
-        if L.lt_fn_refine_host(*args, int(host_threads), *outs) != 0:
+        if terms is None:
+            rc = L.lt_fn_refine_host(*args, int(host_threads), *outs)
+        else:
+            hm = heatmaps.args() if terms.use_heatmap else (0, None, None, None, None)
+            rc = L.lt_fn_refine_host_terms(*args, *targs, *hm, int(host_threads), *outs)
+        if rc != 0:
             raise ValueError("limap_amd.optimize: " + L.lt_fn_refine_host_error().decode(errors="replace"))
     else:
         ctx = ctx if ctx is not None else _context()
-        ctx.chk(L.lt_refine_arrays(ctx.h, *args))
+        if terms is None:
+            ctx.chk(L.lt_refine_arrays(ctx.h, *args))
+        else:
+            if terms.use_heatmap:
+                heatmaps.upload(ctx)
+            ctx.chk(L.lt_refine_arrays_terms(ctx.h, *args, *targs))
         ctx.chk(L.lt_refine_get(ctx.h, *outs))
         tm = np.zeros(4)
         ctx.chk(L.lt_refine_get_timers(ctx.h, p(tm, C.c_double)))
@@ -235,38 +321,103 @@ class RefinementEngine:
 
 
 def _refinement_cfg(cfg, kw):
-    for k in ("p_vpresults", "p_heatmaps", "p_patches", "p_features"):
+    for k in ("p_patches", "p_features"):
         if kw.get(k) is not None:
-            raise ValueError(f"limap_amd.optimize: {k} is not built (geometric terms only)")
+            raise ValueError(f"limap_amd.optimize: {k} is not built (use_feature)")
     rf = RefinementConfig(cfg) if isinstance(cfg, dict) or cfg is None else cfg
     rf._check()
     return rf
 
 
-def solve_line_refinement(cfg, track, p_camviews, host_threads=None, **kw):
-    """optimize/line_refinement/solve.py:4-48: p_camviews are the views of track.GetSortedImageIds(), in that order.
-    None below min_num_images."""
-    rf = _refinement_cfg(cfg, kw)
+def _vp_pair(r):
+    """a VPResult in any form InitVPResults accepts -> labels, vps (V, 3)"""
+    if isinstance(r, dict):
+        lab, vps = r["labels"], r["vps"]
+    elif hasattr(r, "labels"):
+        lab, vps = r.labels, r.vps
+    else:
+        lab, vps = r
+    return np.asarray(lab, np.int64).reshape(-1), np.asarray(vps, float).reshape(-1, 3)
+
+
+def _vp_arrays(tracks, vpresults):
+    """per support, list order: the flag (label >= 0 for line_id_list[k]: HasVP) and the vanishing point
+    (refine.cc:101-103); vpresults: {img_id: VPResult}"""
+    flat = {}
+    flag, vp3 = [], []
+    for t in tracks:
+        for img_id, line_id in zip(t.image_id_list, t.line_id_list):
+            if img_id not in flat:
+                if img_id not in vpresults:
+                    raise ValueError(f"limap_amd.optimize: use_vp and no VPResult for image {img_id}")
+                flat[img_id] = _vp_pair(vpresults[img_id])
+            lab, vps = flat[img_id]
+            label = int(lab[line_id])
+            flag.append(label >= 0)
+            vp3.append(vps[label] if label >= 0 else np.zeros(3))
+    return np.array(flag, np.int32), np.array(vp3, np.float64).reshape(-1, 3)
+
+
+def _view_hw(ids, views):
+    """(h, w) per camera row; 0 where the view carries no size"""
+    return np.array([[views[int(i)].h() or 0, views[int(i)].w() or 0] for i in ids], np.int32).reshape(-1, 2)
+
+
+def _refine(rf, tracks, views, vpresults, heatmaps, host_threads):
+    """all `tracks` in one native call; views, vpresults: {img_id: ...}; heatmaps: a Heatmaps"""
+    cams = _camera_arrays(views)
+    terms = rf._terms()
+    vp = _vp_arrays(tracks, vpresults) if rf.use_vp else None
+    return refine_arrays(cams, _track_arrays(tracks), rf._struct(rf.num_outliers_aggregate), host_threads, terms=terms, vp=vp,
+                         view_hw=_view_hw(cams[0], views) if rf.use_heatmap else None, heatmaps=heatmaps)
+
+
+def solve_line_refinement(cfg, track, p_camviews, p_vpresults=None, p_heatmaps=None, p_patches=None, p_features=None,
+                          dtype=None, host_threads=None):
+    """optimize/line_refinement/solve.py:4-48: p_camviews, p_vpresults and p_heatmaps are the views, VPResults and
+    heatmaps of track.GetSortedImageIds(), in that order.  dtype: the texels ("float16" / "float32"; the
+    configuration's by default).  None below min_num_images."""
+    for name, lst in (("p_vpresults", p_vpresults), ("p_heatmaps", p_heatmaps)):
+        if lst is not None and len(lst) != len(p_camviews):
+            raise ValueError(f"limap_amd.optimize: {name} has {len(lst)} entries for {len(p_camviews)} views")
+    rf = _refinement_cfg(cfg, dict(p_patches=p_patches, p_features=p_features))
+    if rf.use_vp and p_vpresults is None:
+        raise ValueError("limap_amd.optimize: use_vp=True needs p_vpresults")
+    if rf.use_heatmap and p_heatmaps is None:
+        raise ValueError("limap_amd.optimize: use_heatmap=True needs p_heatmaps")
     if track.count_images() < rf.min_num_images:
         return None
     ids = track.GetSortedImageIds()
     if len(p_camviews) != len(ids):
         raise ValueError(f"{len(ids)} images support the track, {len(p_camviews)} views given")
-    cams = _camera_arrays(dict(zip(ids, p_camviews)))
-    r = refine_arrays(cams, _track_arrays([track]), rf._struct(rf.num_outliers_aggregate), host_threads)
+    hm = Heatmaps(dict(zip(ids, p_heatmaps)), dtype or rf.dtype) if rf.use_heatmap else None
+    r = _refine(rf, [track], dict(zip(ids, p_camviews)), dict(zip(ids, p_vpresults)) if rf.use_vp else None, hm, host_threads)
     return RefinementEngine(r)
 
 
 def line_refinement(cfg, tracks, imagecols, heatmap_dir=None, patch_dir=None, featuremap_dir=None, vpresults=None,
-                    n_visible_views=4, host_threads=None):
-    """optimize/line_refinement/line_refinement.py:15-136 with the geometric terms: the tracks seen in at least
-    n_visible_views images and min_num_images images are refined -- all of them in one call -- the others pass through."""
+                    n_visible_views=4, host_threads=None, heatmaps=None):
+    """optimize/line_refinement/line_refinement.py:15-136 with the geometric, VP and heatmap terms: the tracks seen in at
+    least n_visible_views images and min_num_images images are refined -- all of them in one call -- the others pass
+    through.  heatmap_dir holds heatmap_{img_id}.npy; heatmaps={img_id: array} gives them directly.  Every image is
+    loaded and uploaded once."""
+    import os
     rf = _refinement_cfg(cfg, {})
+    if rf.use_vp and vpresults is None:
+        raise ValueError("limap_amd.optimize: use_vp=True needs vpresults")
+    if rf.use_heatmap and heatmap_dir is None and heatmaps is None:
+        raise ValueError("limap_amd.optimize: use_heatmap=True needs heatmap_dir or heatmaps")
     sel = [n for n, t in enumerate(tracks) if t.count_images() >= max(int(n_visible_views), rf.min_num_images)]
     out = list(tracks)
     if sel:
-        cams = _camera_arrays({int(i): imagecols.camview(int(i)) for i in imagecols.get_img_ids()})
-        r = refine_arrays(cams, _track_arrays([tracks[n] for n in sel]), rf._struct(rf.num_outliers_aggregate), host_threads)
+        views = {int(i): imagecols.camview(int(i)) for i in imagecols.get_img_ids()}
+        hm = None
+        if rf.use_heatmap:
+            if heatmaps is None:
+                files = {i: os.path.join(heatmap_dir, f"heatmap_{i}.npy") for i in views}
+                heatmaps = {i: np.load(f) for i, f in files.items() if os.path.exists(f)}
+            hm = Heatmaps(heatmaps, rf.dtype)
+        r = _refine(rf, [tracks[n] for n in sel], views, vpresults, hm, host_threads)
         for m, n in enumerate(sel):
             out[n] = _copy_track(tracks[n], Line3d(r["segments"][m, :3], r["segments"][m, 3:]))
     return out
