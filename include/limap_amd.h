@@ -562,6 +562,49 @@ int lt_match_get_timers(lt_ctx *ctx, double out[4]);
 int lt_fn_match_pair_host(const float *desc1, int64_t n1, const float *desc2, int64_t n2, int dim,
                           const lt_match_config *cfg, int32_t *rows2, float *scores, int64_t *n_rows);
 
+/* ---- the SOLD2 line matcher (line2d/SOLD2/model/line_matching.py: WunschLineMatcher; DESIGN section 17, "SOLD2").
+ * An image is n lines of num_samples (S) point descriptors each: row l * S + s of its descriptor rows is sample s of line
+ * l (the transpose of limap's (dim, S n) array), valid[l * S + s] != 0 says that the sample is real.  Point score
+ * P[i, s, j, t]: the FP32 fmaf chain of the two descriptors in ascending k from +0.0f, -1.0f where either sample is not
+ * valid.  Line score L[i, j] = ((mean over s of max_t P) + (mean over t of max_s P)) * 0.5f, every operation in FP32, the
+ * means over the maxima that differ from -1.0f, their sums in the fixed tree ((0 + 1) + (2 + 3)) + ((4 + 5) + (6 + 7))
+ * over 8 sample slots (absent terms +0.0f), a mean without any term -1.0f.  Lines rank by L descending, equal scores by
+ * ascending line.  topk > 0: min(topk, lines of the neighbour) rows per line.  topk == 0: per line the
+ * min(top_k_candidates, lines of the neighbour) best lines, ascending in that order, then the same with t reversed; the
+ * Needleman-Wunsch value (FP64, gap 0.1f subtracted in FP32) of every block; the first maximum's candidate; the same from
+ * the neighbour's side; (i, j) is a row iff each is the other's match. */
+typedef struct lt_match_wunsch_config {
+  int32_t topk;             /* 0 (mutual form) .. LT_MATCH_MAX_TOPK */
+  int32_t num_samples;      /* S in [2, 8]; limap: 5 */
+  int32_t top_k_candidates; /* 1 .. LT_MATCH_MAX_TOPK, used by the mutual form; limap: 10 */
+  int32_t desc_on_device;   /* desc is device memory of the context's device (valid is always host memory) */
+  int32_t want_scores;      /* also download L of every returned row (lt_match_get_scores) */
+  int32_t reserved;         /* 0 */
+} lt_match_wunsch_config;
+/* Images as CSR over lines (line_off) and over descriptor rows (desc_off; image m must own S times as many rows as
+ * lines), pairs as in lt_match_scene.  Rejected with LT_ERR_ARGUMENT before any matching launch: a value that is not
+ * finite or above 2^57 in magnitude, dim not a multiple of 8 in [8, LT_MATCH_MAX_DIM], num_samples outside [2, 8], topk
+ * outside [0, LT_MATCH_MAX_TOPK], top_k_candidates outside [1, LT_MATCH_MAX_TOPK], more than 65 535 lines in an image, a
+ * descriptor count that is not S times the line count, a line without a valid sample, a neighbour that is not an image.
+ * The rows are read with lt_match_get / lt_match_get_scores / lt_match_get_timers, exactly as after lt_match_scene. */
+int lt_match_wunsch_scene(lt_ctx *ctx, int n_img, const int64_t *line_off, const int64_t *desc_off, const float *desc,
+                          const uint8_t *valid, int dim, const int64_t *pair_off, const int32_t *pair_nb,
+                          const lt_match_wunsch_config *cfg, int64_t *n_rows);
+/* device ms (HIP events) of the last lt_match_wunsch_scene: [0] the line-score / top-k kernel, [1] the NW kernel (0 unless
+ * topk == 0) */
+int lt_match_wunsch_get_kernel_ms(lt_ctx *ctx, double out[2]);
+/* The same semantics on the host, no context and no device: exposed for tests.  n1, n2: lines.  rows2 / scores (either may
+ * be NULL) need room for n1 * max(1, min(topk, n2)) rows. */
+int lt_fn_match_wunsch_pair_host(const float *desc1, const uint8_t *valid1, int64_t n1, const float *desc2,
+                                 const uint8_t *valid2, int64_t n2, int dim, const lt_match_wunsch_config *cfg,
+                                 int32_t *rows2, float *scores, int64_t *n_rows);
+/* its intermediate values: point_scores (n1, n2, S, S) and line_scores (n1, n2), either may be NULL */
+int lt_fn_match_wunsch_scores_host(const float *desc1, const uint8_t *valid1, int64_t n1, const float *desc2,
+                                   const uint8_t *valid2, int64_t n2, int dim, int num_samples, float *point_scores,
+                                   float *line_scores);
+/* the Needleman-Wunsch value of one masked S x S block (row-major): out[0] as given, out[1] with its columns reversed */
+int lt_fn_match_wunsch_nw_host(const float *block, int num_samples, double out[2]);
+
 /* ---- limap.vplib: the JLinkage vanishing-point detector (vplib/JLinkage/JLinkage.cc, vplib/base_vp_detector.cc) for a
  * batch of images per call.  Images as CSR over lines, as for lt_bpt_*.  limap's own code around
  * the two calls into its J-Linkage third party is reproduced bit for bit: the `length() < min_length` filter, endpoints

@@ -37,6 +37,8 @@ EXPORTED_SYMBOLS = [
     "lt_bpt_config_default", "lt_bpt_associate", "lt_bpt_associate_get", "lt_bpt_junctions", "lt_bpt_junctions_get",
     "lt_bpt_junctions_get_candidates", "lt_bpt_get_timers", "lt_fn_bpt_grid_keys", "lt_fn_bpt_close_pairs_host",
     "lt_match_scene", "lt_match_get", "lt_match_get_scores", "lt_match_get_timers", "lt_fn_match_pair_host",
+    "lt_match_wunsch_scene", "lt_match_wunsch_get_kernel_ms", "lt_fn_match_wunsch_pair_host",
+    "lt_fn_match_wunsch_scores_host", "lt_fn_match_wunsch_nw_host",
     "lt_vp_config_default", "lt_vp_detect", "lt_vp_get", "lt_vp_get_timers", "lt_fn_vp_detect_host",
     "lt_fn_vp_cluster_host", "lt_vp_cluster_sets",
     "lt_refine_config_default", "lt_refine_arrays", "lt_refine_tracks", "lt_refine_num", "lt_refine_get",
@@ -148,6 +150,12 @@ class LtBptConfig(C.Structure):
 class LtMatchConfig(C.Structure):
     """lt_match_config of include/limap_amd.h"""
     _fields_ = [("kind", C.c_int32), ("topk", C.c_int32), ("desc_on_device", C.c_int32), ("want_scores", C.c_int32)]
+
+
+class LtMatchWunschConfig(C.Structure):
+    """lt_match_wunsch_config of include/limap_amd.h"""
+    _fields_ = [("topk", C.c_int32), ("num_samples", C.c_int32), ("top_k_candidates", C.c_int32),
+                ("desc_on_device", C.c_int32), ("want_scores", C.c_int32), ("reserved", C.c_int32)]
 
 
 class LtVpConfig(C.Structure):
@@ -329,6 +337,13 @@ def load_library():
     L.lt_match_get_scores.argtypes = [vp, fp]
     L.lt_match_get_timers.argtypes = [vp, dp]
     L.lt_fn_match_pair_host.argtypes = [fp, C.c_int64, fp, C.c_int64, C.c_int, C.POINTER(LtMatchConfig), i32p, fp, i64p]
+    u8p = C.POINTER(C.c_uint8)
+    wcfg = C.POINTER(LtMatchWunschConfig)
+    L.lt_match_wunsch_scene.argtypes = [vp, C.c_int, i64p, i64p, vp, u8p, C.c_int, i64p, i32p, wcfg, i64p]
+    L.lt_match_wunsch_get_kernel_ms.argtypes = [vp, dp]
+    L.lt_fn_match_wunsch_pair_host.argtypes = [fp, u8p, C.c_int64, fp, u8p, C.c_int64, C.c_int, wcfg, i32p, fp, i64p]
+    L.lt_fn_match_wunsch_scores_host.argtypes = [fp, u8p, C.c_int64, fp, u8p, C.c_int64, C.c_int, C.c_int, fp, fp]
+    L.lt_fn_match_wunsch_nw_host.argtypes = [fp, C.c_int, dp]
     L.lt_vp_config_default.argtypes = [C.POINTER(LtVpConfig)]
     L.lt_vp_config_default.restype = None
     L.lt_vp_detect.argtypes = [vp, C.c_int, i64p, dp, C.POINTER(LtVpConfig), i64p]

@@ -221,6 +221,9 @@ struct MatchState {  // line-descriptor matching (lt_match.cpp): the result of t
   std::vector<float> score;                 // per slot, only with want_scores
   bool mutual = false;
   DevBuf d_desc, d_tasks, d_units, d_col, d_score, d_flag;
+  // the SOLD2 kind (lt_match_wunsch.cpp): validity bytes per line, line prefix per task, the mutual form's matches
+  double kernel_ms[2] = {0, 0};  // lt_match_wunsch_get_kernel_ms: k_wunsch_topk, k_wunsch_nw (HIP events)
+  DevBuf d_vmask, d_prefix, d_mcol, d_mscore;
 };
 
 struct VpState {  // vanishing-point detection (lt_vp.cpp): the result of the last lt_vp_detect

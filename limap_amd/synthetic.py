@@ -386,11 +386,13 @@ def make_descriptors(scene, kind="l2d2", dim=None, noise=0.05, seed=0):
     "l2d2", dim 128) or {"endpoints_desc": (dim, 2 M) float32} (kind "endpoints", dim 256).  Every observed segment gets
     the unit descriptor of its GT segment plus Gaussian noise of standard deviation `noise` per component (clutter: a
     random unit descriptor of its own), normalised again.  Endpoints: one descriptor per GT endpoint, and the endpoint
-    order of an observation is flipped at random, so the larger of the two pairings is the one that matches."""
-    if kind not in ("l2d2", "endpoints"):
+    order of an observation is flipped at random, so the larger of the two pairings is the one that matches.
+    Kind "sold2": [desc (dim, 5 M), valid (M, 5)] with dim 128 -- five sample descriptors per GT segment, the sample order
+    of an observation reversed at random, and a random number (2 to 5) of leading samples valid."""
+    if kind not in ("l2d2", "endpoints", "sold2"):
         raise ValueError(f"make_descriptors: unknown kind {kind!r}")
-    per = 1 if kind == "l2d2" else 2
-    dim = (128 if per == 1 else 256) if dim is None else int(dim)
+    per = {"l2d2": 1, "endpoints": 2, "sold2": 5}[kind]
+    dim = (256 if per == 2 else 128) if dim is None else int(dim)
     rng = np.random.default_rng([int(seed), 4242, per])
     gt = rng.standard_normal((len(scene.gt_lines), per, dim))
     gt /= np.linalg.norm(gt, axis=2, keepdims=True)
@@ -405,6 +407,11 @@ def make_descriptors(scene, kind="l2d2", dim=None, noise=0.05, seed=0):
         d /= np.maximum(np.linalg.norm(d, axis=2, keepdims=True), 1e-30)
         if per == 1:
             out[int(img_id)] = {"line_descriptors": np.ascontiguousarray(d[:, 0], np.float32)}
+        elif per == 5:
+            flip = r.random(len(g)) < 0.5
+            d[flip] = d[flip][:, ::-1]
+            valid = np.arange(per)[None, :] < r.integers(2, per + 1, len(g))[:, None]
+            out[int(img_id)] = [np.ascontiguousarray(d.reshape(-1, dim).T, np.float32), valid]
         else:
             flip = r.random(len(g)) < 0.5
             d[flip] = d[flip][:, ::-1]
