@@ -605,6 +605,57 @@ int lt_fn_match_wunsch_scores_host(const float *desc1, const uint8_t *valid1, in
 /* the Needleman-Wunsch value of one masked S x S block (row-major): out[0] as given, out[1] with its columns reversed */
 int lt_fn_match_wunsch_nw_host(const float *block, int num_samples, double out[2]);
 
+/* ---- the dense-warp line matcher (line2d/dense/matcher.py: BaseDenseLineMatcher behind get_warping_symmetric; DESIGN
+ * section 17, "Dense").  A pair of images comes with a warp (hw, ww, 2) of normalised target coordinates and a certainty
+ * map (hw, ww) in either direction, FP32, row-major.  Sample k of a line is r_k start + (1 - r_k) end with
+ * r = linspace(0, 1, S); it is normalised by its image's shape, looked up bilinearly (align_corners = False, zero padding)
+ * in warp and cert and unnormalised by the target image's shape.  A sample is good for a target line iff its certainty
+ * exceeds sample_thresh and its projection on the line's unit direction lies strictly between those of the line's ends
+ * (and nothing about it is non-finite).  Per (line, target line): overlap = count / S, weighted distance = the fmaf chain
+ * over the good samples in sample order of |p . l| times 1 / count, 10000 where overlap < segment_percentage_th.  Both
+ * directions combine as dists = overlap_12 > overlap_21 ? d_12 : d_21, 10000 where the smaller overlap is below
+ * segment_percentage_th or the larger distance above pixel_th.  (i, j) is a row iff dists <= pixel_th and, unless
+ * one_to_many, dists equals its row's minimum (every tie is kept).  Rows by line, then by neighbour line.  All FP32,
+ * no contraction; the device equals lt_fn_match_dense_pair_host bit for bit. */
+typedef struct lt_match_dense_config {
+  int32_t n_samples;            /* S in [2, 64]; limap: 21 */
+  int32_t one_to_many;          /* limap: 0 */
+  float segment_percentage_th;  /* limap: 0.2 */
+  float pixel_th;               /* limap: 10 */
+  float sample_thresh;          /* the dense matcher's get_sample_thresh() */
+  int32_t on_device;            /* warp and cert pointers are device memory of the context's device, read in place */
+  int32_t want_scores;          /* also download dists of every row (lt_match_get_scores) */
+  int32_t want_dirs;            /* also keep d_12, overlap_12, d_21, overlap_21, dists of every entry (..._get_dirs) */
+} lt_match_dense_config;
+/* Images as CSR over lines (line_off; lines: 4 floats sx, sy, ex, ey per line, host memory), shapes[2 m], [2 m + 1] =
+ * height and width of image m.  Pair q matches image pair_img[2 q] (lines i) against pair_img[2 q + 1] (lines j);
+ * warp[2 q], cert[2 q] take image 1 to image 2, warp[2 q + 1], cert[2 q + 1] back; dims[4 (2 q + d) ..] = warp height,
+ * warp width, cert height, cert width of direction d.  Rejected with LT_ERR_ARGUMENT before any launch, the message
+ * naming the argument: n_samples outside [2, 64], a NaN threshold, a warp side below 1 or above 16384, cert and warp
+ * shapes that differ, a shape that is not positive, more than 65 535 lines in an image, a pair that names no image.
+ * The rows are read with lt_match_get / lt_match_get_scores / lt_match_get_timers, as after lt_match_scene. */
+int lt_match_dense_pairs(lt_ctx *ctx, int n_img, const int64_t *line_off, const float *lines, const int32_t *shapes,
+                         int64_t n_pairs, const int32_t *pair_img, const float *const *warp, const float *const *cert,
+                         const int32_t *dims, const lt_match_dense_config *cfg, int64_t *n_rows);
+/* device ms (HIP events) of the last lt_match_dense_pairs: k_dense_warp, k_dense_pairs, k_dense_select (both passes and
+ * the prefix sum between them) */
+int lt_match_dense_get_kernel_ms(lt_ctx *ctx, double out[3]);
+/* after a call with want_dirs: per entry (pairs behind each other, entry i * n2 + j of a pair) d_12, overlap_12 and, as
+ * seen from (i, j), d_21 and overlap_21, and dists; any pointer may be NULL */
+int lt_match_dense_get_dirs(lt_ctx *ctx, float *d12, float *o12, float *d21, float *o21, float *dists);
+/* The same semantics on the host, no context and no device: exposed for tests.  rows2 / scores (either may be NULL)
+ * need room for n1 * n2 rows. */
+int lt_fn_match_dense_pair_host(const float *lines1, int64_t n1, const int32_t *shape1, const float *lines2, int64_t n2,
+                                const int32_t *shape2, const float *warp12, const float *cert12, const int32_t *dims12,
+                                const float *warp21, const float *cert21, const int32_t *dims21,
+                                const lt_match_dense_config *cfg, int32_t *rows2, float *scores, int64_t *n_rows);
+/* its matrices: d12, o12 and dists are (n1, n2), d21 and o21 (n2, n1) as upstream returns them; any may be NULL */
+int lt_fn_match_dense_dists_host(const float *lines1, int64_t n1, const int32_t *shape1, const float *lines2, int64_t n2,
+                                 const int32_t *shape2, const float *warp12, const float *cert12, const int32_t *dims12,
+                                 const float *warp21, const float *cert21, const int32_t *dims21,
+                                 const lt_match_dense_config *cfg, float *d12, float *o12, float *d21, float *o21,
+                                 float *dists);
+
 /* ---- limap.vplib: the JLinkage vanishing-point detector (vplib/JLinkage/JLinkage.cc, vplib/base_vp_detector.cc) for a
  * batch of images per call.  Images as CSR over lines, as for lt_bpt_*.  limap's own code around
  * the two calls into its J-Linkage third party is reproduced bit for bit: the `length() < min_length` filter, endpoints

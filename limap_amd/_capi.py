@@ -39,6 +39,8 @@ EXPORTED_SYMBOLS = [
     "lt_match_scene", "lt_match_get", "lt_match_get_scores", "lt_match_get_timers", "lt_fn_match_pair_host",
     "lt_match_wunsch_scene", "lt_match_wunsch_get_kernel_ms", "lt_fn_match_wunsch_pair_host",
     "lt_fn_match_wunsch_scores_host", "lt_fn_match_wunsch_nw_host",
+    "lt_match_dense_pairs", "lt_match_dense_get_kernel_ms", "lt_match_dense_get_dirs", "lt_fn_match_dense_pair_host",
+    "lt_fn_match_dense_dists_host",
     "lt_vp_config_default", "lt_vp_detect", "lt_vp_get", "lt_vp_get_timers", "lt_fn_vp_detect_host",
     "lt_fn_vp_cluster_host", "lt_vp_cluster_sets",
     "lt_refine_config_default", "lt_refine_arrays", "lt_refine_tracks", "lt_refine_num", "lt_refine_get",
@@ -156,6 +158,13 @@ class LtMatchWunschConfig(C.Structure):
     """lt_match_wunsch_config of include/limap_amd.h"""
     _fields_ = [("topk", C.c_int32), ("num_samples", C.c_int32), ("top_k_candidates", C.c_int32),
                 ("desc_on_device", C.c_int32), ("want_scores", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LtMatchDenseConfig(C.Structure):
+    """lt_match_dense_config of include/limap_amd.h"""
+    _fields_ = [("n_samples", C.c_int32), ("one_to_many", C.c_int32), ("segment_percentage_th", C.c_float),
+                ("pixel_th", C.c_float), ("sample_thresh", C.c_float), ("on_device", C.c_int32),
+                ("want_scores", C.c_int32), ("want_dirs", C.c_int32)]
 
 
 class LtVpConfig(C.Structure):
@@ -344,6 +353,14 @@ def load_library():
     L.lt_fn_match_wunsch_pair_host.argtypes = [fp, u8p, C.c_int64, fp, u8p, C.c_int64, C.c_int, wcfg, i32p, fp, i64p]
     L.lt_fn_match_wunsch_scores_host.argtypes = [fp, u8p, C.c_int64, fp, u8p, C.c_int64, C.c_int, C.c_int, fp, fp]
     L.lt_fn_match_wunsch_nw_host.argtypes = [fp, C.c_int, dp]
+    dcfg = C.POINTER(LtMatchDenseConfig)
+    vpp = C.POINTER(C.c_void_p)
+    L.lt_match_dense_pairs.argtypes = [vp, C.c_int, i64p, fp, i32p, C.c_int64, i32p, vpp, vpp, i32p, dcfg, i64p]
+    L.lt_match_dense_get_kernel_ms.argtypes = [vp, dp]
+    L.lt_match_dense_get_dirs.argtypes = [vp, fp, fp, fp, fp, fp]
+    pair = [fp, C.c_int64, i32p, fp, C.c_int64, i32p, fp, fp, i32p, fp, fp, i32p, dcfg]
+    L.lt_fn_match_dense_pair_host.argtypes = pair + [i32p, fp, i64p]
+    L.lt_fn_match_dense_dists_host.argtypes = pair + [fp, fp, fp, fp, fp]
     L.lt_vp_config_default.argtypes = [C.POINTER(LtVpConfig)]
     L.lt_vp_config_default.restype = None
     L.lt_vp_detect.argtypes = [vp, C.c_int, i64p, dp, C.POINTER(LtVpConfig), i64p]

@@ -224,6 +224,15 @@ struct MatchState {  // line-descriptor matching (lt_match.cpp): the result of t
   // the SOLD2 kind (lt_match_wunsch.cpp): validity bytes per line, line prefix per task, the mutual form's matches
   double kernel_ms[2] = {0, 0};  // lt_match_wunsch_get_kernel_ms: k_wunsch_topk, k_wunsch_nw (HIP events)
   DevBuf d_vmask, d_prefix, d_mcol, d_mscore;
+  // the dense kind (lt_match_dense.cpp): rows of variable number per line, so the line of every row is kept; the five
+  // per-entry matrices of a call with want_dirs (dense_aux_n entries each; -1: not asked for)
+  bool dense = false;
+  std::vector<int> dense_line;
+  std::vector<float> dense_aux;
+  long long dense_aux_n = -1;
+  double dense_ms[3] = {0, 0, 0};  // lt_match_dense_get_kernel_ms: k_dense_warp, k_dense_pairs, k_dense_select + scan
+  DevBuf d_dn_lines, d_dn_terms, d_dn_tab, d_dn_dirs, d_dn_wx, d_dn_wy, d_dn_wok, d_dn_dist, d_dn_aux, d_dn_cnt, d_dn_off,
+      d_dn_scan, d_dn_line;
 };
 
 struct VpState {  // vanishing-point detection (lt_vp.cpp): the result of the last lt_vp_detect

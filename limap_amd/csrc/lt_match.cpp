@@ -179,6 +179,7 @@ int lt_match_scene(lt_ctx *ctx, int n_img, const int64_t *desc_off, const float 
     }
   }
   ctx->mt.mutual = mutual;
+  ctx->mt.dense = false;
   ctx->mt.timers[3] = now_ms() - t3;
   if (n_rows) *n_rows = (int64_t)row_off.back();
   return LT_OK;
@@ -190,6 +191,13 @@ int lt_match_get(lt_ctx *ctx, int64_t *row_off, int32_t *rows2) {
   if (row_off) std::copy(off.begin(), off.end(), row_off);
   if (!rows2 || off.empty()) return LT_OK;
   const long long n_pairs = (long long)off.size() - 1;
+  if (ctx->mt.dense) {  // lt_match_dense_pairs: a row per slot, its line kept beside its column
+    for (long long s = 0; s < off.back(); ++s) {
+      rows2[2 * s] = ctx->mt.dense_line[(size_t)s];
+      rows2[2 * s + 1] = (int32_t)ctx->mt.col[(size_t)s];
+    }
+    return LT_OK;
+  }
 #pragma omp parallel for schedule(dynamic, 8)
   for (long long p = 0; p < n_pairs; ++p) {
     const int kk = ctx->mt.kk[(size_t)p];

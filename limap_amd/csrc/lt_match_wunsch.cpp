@@ -294,6 +294,7 @@ int lt_match_wunsch_scene(lt_ctx *ctx, int n_img, const int64_t *line_off, const
     }
   }
   ctx->mt.mutual = mutual;
+  ctx->mt.dense = false;
   ctx->mt.timers[3] = now_ms() - t3;
   if (n_rows) *n_rows = (int64_t)row_off.back();
   return LT_OK;

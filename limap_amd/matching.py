@@ -2,18 +2,27 @@
 (line2d/L2D2/matcher.py: top-k and mutual nearest neighbour) and the top-k form of ``NNEndpointsMatcher``
 (line2d/endpoints/matcher.py:71-111) -- and SOLD2's ``WunschLineMatcher`` (line2d/SOLD2/model/line_matching.py: line
 scores pooled from the point scores of the sampled descriptors, top-k, and the mutual Needleman-Wunsch form) as
-``SOLD2Matcher``, with the reference's method names, plus one batched entry point for a scene:
+``SOLD2Matcher``, and the dense-warp matcher behind ``dense_roma`` (line2d/dense/matcher.py: everything behind
+``get_warping_symmetric``) as ``DenseLineMatcher`` / ``RoMaLineMatcher``, with the reference's method names, plus one
+batched entry point for a scene:
 
     from limap_amd import matching
     matches = matching.match_scene(descinfos, neighbors, kind="l2d2", topk=10)   # img_id -> {ng_img_id: (n, 2) int32}
     matches = matching.match_scene(descinfos, neighbors, kind="sold2", topk=0)   # descinfo = [desc (dim, 5 N), valid (N, 5)]
+    matches = matching.match_scene_dense(descinfos, neighbors, warps, sample_thresh=0.05)   # descinfo of DenseNaiveExtractor
     for img_id in image_ids:
         triangulator.TriangulateImage(img_id, matches[img_id])
+
+``warps`` is a ``BaseDenseMatcher``, a callable ``(i, j) -> (warp_12, cert_12, warp_21, cert_21)`` or a dict of those:
+RoMa's output, an optical flow, a depth-plus-pose warp, a homography.  The dense kind needs no descriptors: the samples
+of every line go through the warp and are measured against every line of the other image (lt_kernels_dense.hip).
 
 Scores are FP32 fmaf chains computed by the FP32-input MFMA, the top-k of every line is selected on chip
 (lt_kernels_match.hip, lt_kernels_wunsch.hip); equal scores rank by ascending neighbour line.
 The ``topk == 0`` form of the endpoints matcher (Sinkhorn), SuperGlue, LBD and GlueStick matchers are out of scope, and
 so is everything of SOLD2 in front of the stored descinfo (network, detector, the sampling of the dense descriptor map).
+Of the dense kind RoMa itself (``RoMaLineMatcher`` builds it from ``romatch`` where that is installed) and the image read
+of ``DenseNaiveExtractor.extract`` beyond ``camview.read_image()`` are out of scope.
 """
 import ctypes as C
 import os
@@ -26,12 +35,18 @@ from . import io as limapio
 
 __all__ = ["BaseMatcherOptions", "DefaultMatcherOptions", "BaseMatcher", "L2D2Matcher", "NNEndpointsMatcher",
            "SOLD2Matcher", "wunsch_scores_host", "wunsch_nw_host", "match_scene", "match_pair_host", "timers",
-           "kernel_ms", "MAX_TOPK", "MAX_DIM", "KINDS"]
+           "kernel_ms", "MAX_TOPK", "MAX_DIM", "KINDS", "BaseDenseLineMatcherOptions", "DefaultDenseLineMatcherOptions",
+           "BaseDenseMatcher", "DenseNaiveExtractor", "DenseLineMatcher", "RoMaLineMatcher", "match_scene_dense",
+           "match_dense_pair_host", "match_dense_dists_host", "dense_kernel_ms", "DENSE_MAX_SAMPLES",
+           "DENSE_WARP_BYTES"]
 
 MAX_TOPK = 64   # LT_MATCH_MAX_TOPK
 MAX_DIM = 256   # LT_MATCH_MAX_DIM
-KINDS = {"l2d2": 0, "endpoints": 1, "nn_endpoints": 1, "sold2": 2}
+KINDS = {"l2d2": 0, "endpoints": 1, "nn_endpoints": 1, "sold2": 2, "dense": 3, "dense_roma": 3}
 SOLD2 = 2       # descinfo = [desc (dim, S N), valid (N, S)]: lt_match_wunsch_scene
+DENSE = 3       # descinfo of DenseNaiveExtractor and a warp per pair: lt_match_dense_pairs (match_scene_dense)
+DENSE_MAX_SAMPLES = 64          # kDenseMaxSamples: a line's good flags are one 64-bit word
+DENSE_WARP_BYTES = 512 << 20    # default budget of match_scene_dense for the warps and certainties of one native call
 _KEY = {0: "line_descriptors", 1: "endpoints_desc"}
 
 _context = _capi.per_device_contexts()
@@ -42,7 +57,7 @@ def _kind(kind):
         if kind not in KINDS:
             raise ValueError(f"matching: unknown kind {kind!r}")
         return KINDS[kind]
-    if int(kind) not in (0, 1, 2):
+    if int(kind) not in (0, 1, 2, 3):
         raise ValueError(f"matching: unknown kind {kind!r}")
     return int(kind)
 
@@ -263,6 +278,9 @@ def match_scene(descinfos, neighbors, kind="l2d2", topk=10, device=0, return_sco
     [desc (dim, num_samples N), valid (N, num_samples)]; topk == 0 is the mutual Needleman-Wunsch form over the
     top_k_candidates best lines (both keywords are used by this kind only)."""
     kind = _kind(kind)
+    if kind == DENSE:
+        raise ValueError("matching: the dense kind matches through a warp per pair, which match_scene does not take: "
+                         "use match_scene_dense(descinfos, neighbors, warps, ...)")
     neighbors = {int(i): [int(j) for j in v] for i, v in neighbors.items()}
     ids = sorted(set(neighbors) | {j for v in neighbors.values() for j in v})
     index = {i: k for k, i in enumerate(ids)}
@@ -298,6 +316,8 @@ def match_pair_host(desc1, desc2, kind="l2d2", topk=10, return_scores=False, num
     """lt_fn_match_pair_host / lt_fn_match_wunsch_pair_host: the same semantics on the host (std::fmaf in a plain loop),
     for tests; no device"""
     kind = _kind(kind)
+    if kind == DENSE:
+        raise ValueError("matching: the dense kind has a host entry of its own: match_dense_pair_host")
     L = _capi.load_library()
     if kind == SOLD2:
         keep, args = _host_pair_args(desc1, desc2, num_samples)
@@ -494,3 +514,389 @@ class SOLD2Matcher(BaseMatcher):
 
     def get_pairwise_distance(self, *args, **kwargs):
         raise NotImplementedError("SOLD2Matcher: get_pairwise_distance is not built")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the dense kind (line2d/dense): DESIGN.md section 17, "Dense"
+class BaseDenseLineMatcherOptions(NamedTuple):
+    """line2d/dense/matcher.py:11-16 (device is accepted and unused: the matcher runs on its own `device` argument)"""
+    n_samples: int = 21
+    segment_percentage_th: float = 0.2
+    device: str = "cuda"
+    pixel_th: float = 10.0
+    one_to_many: bool = False
+
+
+DefaultDenseLineMatcherOptions = BaseDenseLineMatcherOptions()
+
+
+def _stack_xy(x, y):
+    if _is_torch(x):
+        import torch
+        return torch.stack([x, y], -1)
+    return np.stack([x, y], axis=-1)
+
+
+class BaseDenseMatcher:
+    """line2d/dense/dense_matcher/base.py: what a dense matcher offers the line matcher.  The helpers take NumPy arrays
+    or torch tensors."""
+
+    def __init__(self):
+        pass
+
+    def to_normalized_coordinates(self, coords, h, w):
+        """coords: (..., 2) in the order x, y"""
+        return _stack_xy(2 / w * coords[..., 0] - 1, 2 / h * coords[..., 1] - 1)
+
+    def to_unnormalized_coordinates(self, coords, h, w):
+        """inverse of to_normalized_coordinates"""
+        return _stack_xy((coords[..., 0] + 1) * w / 2, (coords[..., 1] + 1) * h / 2)
+
+    def get_sample_thresh(self):
+        raise NotImplementedError
+
+    def get_warping_symmetric(self, img1, img2):
+        """-> warp_1to2 ([-1, 1], (H, W, 2)), cert_1to2 (H, W), warp_2to1, cert_2to1"""
+        raise NotImplementedError
+
+
+class DenseNaiveExtractor:
+    """line2d/dense/extractor.py: the descinfo of the dense matchers is the image, its shape, the lines (N, 2, 2) and
+    their scores.  The image comes from ``camview.read_image()``; nothing else of the reading is built here."""
+
+    def __init__(self, options=None, device=None):
+        self.options = options
+
+    def get_module_name(self):
+        return "dense_naive"
+
+    def get_descinfo_fname(self, descinfo_folder, img_id):
+        return os.path.join(descinfo_folder, f"descinfo_{img_id}.npz")
+
+    def save_descinfo(self, descinfo_folder, img_id, descinfo):
+        os.makedirs(descinfo_folder, exist_ok=True)
+        np.savez(self.get_descinfo_fname(descinfo_folder, img_id), **{k: np.asarray(v) for k, v in descinfo.items()})
+
+    def read_descinfo(self, descinfo_folder, img_id):
+        with np.load(self.get_descinfo_fname(descinfo_folder, img_id), allow_pickle=False) as z:
+            return {k: z[k] for k in z.files}
+
+    def extract(self, camview, segs):
+        img = camview.read_image()
+        segs = np.asarray(segs)
+        lines = segs[:, :4].reshape(-1, 2, 2)
+        scores = segs[:, -1] * np.sqrt(np.linalg.norm(segs[:, :2] - segs[:, 2:4], axis=1))
+        return {"image": img, "image_shape": img.shape, "lines": lines, "scores": scores}
+
+
+def _dense_image(descinfo):
+    """lines (N, 4) float32 and (h, w) of a dense descinfo"""
+    lines = descinfo["lines"]
+    if _is_torch(lines):
+        lines = lines.detach().cpu().numpy()
+    lines = np.asarray(lines)
+    if lines.size == 0:
+        lines = np.zeros((0, 4), np.float32)
+    if lines.shape[1:] not in ((2, 2), (4,)):
+        raise ValueError(f"matching: dense lines must be (N, 2, 2), got shape {lines.shape}")
+    shape = descinfo["image_shape"]
+    return np.ascontiguousarray(lines.reshape(-1, 4), np.float32), (int(shape[0]), int(shape[1]))
+
+
+def _dense_maps(quad, device):
+    """(warp_12, cert_12, warp_21, cert_21) -> the four arrays as float32, contiguous; all torch GPU tensors or all NumPy"""
+    if len(quad) != 4:
+        raise ValueError("matching: a pair's warps are (warp_12, cert_12, warp_21, cert_21)")
+    if all(_is_torch(a) and a.is_cuda for a in quad):
+        import torch
+        if any(a.device.index != device for a in quad):
+            raise ValueError(f"matching: warps on another device than cuda:{device}")
+        out = [a.detach().to(torch.float32).contiguous() for a in quad]
+    else:
+        out = [np.ascontiguousarray(a.detach().cpu().numpy() if _is_torch(a) else a, np.float32) for a in quad]
+    for w, c in ((out[0], out[1]), (out[2], out[3])):
+        if len(w.shape) != 3 or w.shape[2] != 2 or len(c.shape) != 2:
+            raise ValueError(f"matching: a warp must be (H, W, 2) and its certainty (H, W), got {tuple(w.shape)} and "
+                             f"{tuple(c.shape)}")
+    return out
+
+
+def _dense_ptr(a):
+    return a.data_ptr() if _is_torch(a) else a.ctypes.data
+
+
+def _dense_dims(maps):
+    w12, c12, w21, c21 = maps
+    return [w12.shape[0], w12.shape[1], c12.shape[0], c12.shape[1], w21.shape[0], w21.shape[1], c21.shape[0], c21.shape[1]]
+
+
+def _dense_cfg(opts, sample_thresh, on_dev=0, want_scores=0, want_dirs=0):
+    return _capi.LtMatchDenseConfig(int(opts.n_samples), 1 if opts.one_to_many else 0, float(opts.segment_percentage_th),
+                                    float(opts.pixel_th), float(sample_thresh), on_dev, want_scores, want_dirs)
+
+
+def _match_dense_flat(images, pairs, maps, opts, sample_thresh, device=0, want_scores=False, want_dirs=False):
+    """lt_match_dense_pairs: images = [(lines (N, 4), (h, w))], pairs = [(a, b)] into them, maps = per pair the four
+    arrays of _dense_maps.  Returns row_off, rows, scores, dirs (the five matrices per pair, or None)."""
+    ctx = _context(device)
+    line_off = np.zeros(len(images) + 1, np.int64)
+    line_off[1:] = np.cumsum([im[0].shape[0] for im in images])
+    lines = np.ascontiguousarray(np.concatenate([im[0] for im in images], 0) if images else np.zeros((0, 4)), np.float32)
+    if lines.shape[0] == 0:
+        lines = np.zeros((1, 4), np.float32)
+    shapes = _capi.i32(np.array([im[1] for im in images], np.int64).reshape(-1))
+    on_dev = bool(maps) and all(_is_torch(a) for q in maps for a in q)
+    if not on_dev:
+        maps = [[a.cpu().numpy() if _is_torch(a) else a for a in q] for q in maps]
+    n = len(pairs)
+    warp_p, cert_p = (C.c_void_p * max(2 * n, 1))(), (C.c_void_p * max(2 * n, 1))()
+    dims = np.zeros(max(8 * n, 1), np.int32)
+    for q, m in enumerate(maps):
+        warp_p[2 * q], cert_p[2 * q], warp_p[2 * q + 1], cert_p[2 * q + 1] = (_dense_ptr(a) for a in m)
+        dims[8 * q:8 * q + 8] = _dense_dims(m)
+    pair_img = _capi.i32(np.array(pairs, np.int64).reshape(-1)) if n else _capi.i32([0])
+    if on_dev:
+        import torch
+        torch.cuda.synchronize(device)  # the context's stream does not wait for torch's streams
+    cfg = _dense_cfg(opts, sample_thresh, 1 if on_dev else 0, 1 if want_scores else 0, 1 if want_dirs else 0)
+    n_rows = C.c_int64(0)
+    ctx.chk(ctx.L.lt_match_dense_pairs(ctx.h, len(images), _capi.ptr(line_off, C.c_int64),
+                                       lines.ctypes.data_as(C.POINTER(C.c_float)),
+                                       _capi.ptr(shapes if len(shapes) else _capi.i32([1, 1]), C.c_int32), n,
+                                       _capi.ptr(pair_img, C.c_int32), warp_p, cert_p, _capi.ptr(dims, C.c_int32),
+                                       C.byref(cfg), C.byref(n_rows)))
+    del maps
+    nr = int(n_rows.value)
+    row_off = np.zeros(n + 1, np.int64)
+    rows = np.zeros((nr, 2), np.int32)
+    ctx.chk(ctx.L.lt_match_get(ctx.h, _capi.ptr(row_off, C.c_int64), _capi.ptr(rows, C.c_int32) if nr else None))
+    scores = None
+    if want_scores:
+        scores = np.zeros(nr, np.float32)
+        ctx.chk(ctx.L.lt_match_get_scores(ctx.h, scores.ctypes.data_as(C.POINTER(C.c_float)) if nr else None))
+    dirs = None
+    if want_dirs:
+        sizes = [images[a][0].shape[0] * images[b][0].shape[0] for a, b in pairs]
+        flat = np.zeros((5, max(sum(sizes), 1)), np.float32)
+        fp = C.POINTER(C.c_float)
+        ctx.chk(ctx.L.lt_match_dense_get_dirs(ctx.h, *(flat[k].ctypes.data_as(fp) for k in range(5))))
+        dirs, e = [], 0
+        for (a, b), sz in zip(pairs, sizes):
+            n1, n2 = images[a][0].shape[0], images[b][0].shape[0]
+            d12, o12, d21, o21, dd = (flat[k, e:e + sz].reshape(n1, n2) for k in range(5))
+            dirs.append((d12.copy(), o12.copy(), d21.T.copy(), o21.T.copy(), dd.copy()))
+            e += sz
+    return row_off, rows, scores, dirs
+
+
+def dense_kernel_ms(device=0):
+    """lt_match_dense_get_kernel_ms of the last dense call: device ms of k_dense_warp, k_dense_pairs, k_dense_select"""
+    out = np.zeros(3)
+    ctx = _context(device)
+    ctx.chk(ctx.L.lt_match_dense_get_kernel_ms(ctx.h, out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+def _dense_host_args(descinfo1, descinfo2, warps, dense_options, sample_thresh):
+    l1, s1 = _dense_image(descinfo1)
+    l2, s2 = _dense_image(descinfo2)
+    m = [np.ascontiguousarray(a.detach().cpu().numpy() if _is_torch(a) else a, np.float32) for a in warps]
+    if len(m) != 4 or m[0].ndim != 3 or m[0].shape[2] != 2 or m[2].ndim != 3 or m[2].shape[2] != 2 or m[1].ndim != 2 \
+            or m[3].ndim != 2:
+        raise ValueError("matching: a pair's warps are (warp_12 (H, W, 2), cert_12 (H, W), warp_21, cert_21)")
+    d = _dense_dims(m)
+    sh1, sh2, d12, d21 = _capi.i32(s1), _capi.i32(s2), _capi.i32(d[:4]), _capi.i32(d[4:])
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    cfg = _dense_cfg(dense_options, sample_thresh)
+    keep = (l1, l2, m, sh1, sh2, d12, d21, cfg)
+    f = lambda a: a.ctypes.data_as(fp)
+    args = (f(l1), l1.shape[0], sh1.ctypes.data_as(ip), f(l2), l2.shape[0], sh2.ctypes.data_as(ip), f(m[0]), f(m[1]),
+            d12.ctypes.data_as(ip), f(m[2]), f(m[3]), d21.ctypes.data_as(ip), C.byref(cfg))
+    return keep, args, l1.shape[0], l2.shape[0]
+
+
+def match_dense_pair_host(descinfo1, descinfo2, warps, dense_options=DefaultDenseLineMatcherOptions, sample_thresh=0.05,
+                          return_scores=False):
+    """lt_fn_match_dense_pair_host: the dense kind's semantics on the host (plain loops with std::fmaf), for tests; no
+    device.  warps = (warp_12, cert_12, warp_21, cert_21)"""
+    L = _capi.load_library()
+    keep, args, n1, n2 = _dense_host_args(descinfo1, descinfo2, warps, dense_options, sample_thresh)
+    cap = max(1, n1 * n2)
+    rows, scores, n = np.zeros((cap, 2), np.int32), np.zeros(cap, np.float32), C.c_int64(0)
+    rc = L.lt_fn_match_dense_pair_host(*args, _capi.ptr(rows, C.c_int32), scores.ctypes.data_as(C.POINTER(C.c_float)),
+                                       C.byref(n))
+    if rc != 0:
+        raise ValueError(f"lt_fn_match_dense_pair_host: rejected (code {rc})")
+    rows, scores = rows[:n.value].copy(), scores[:n.value].copy()
+    return (rows, scores) if return_scores else rows
+
+
+def match_dense_dists_host(descinfo1, descinfo2, warps, dense_options=DefaultDenseLineMatcherOptions, sample_thresh=0.05):
+    """lt_fn_match_dense_dists_host: d_12, overlap_12 (N1, N2), d_21, overlap_21 (N2, N1) as upstream's
+    compute_distance_one_direction returns them, and the combined dists (N1, N2)"""
+    L = _capi.load_library()
+    keep, args, n1, n2 = _dense_host_args(descinfo1, descinfo2, warps, dense_options, sample_thresh)
+    out = [np.zeros(s, np.float32) for s in ((n1, n2), (n1, n2), (n2, n1), (n2, n1), (n1, n2))]
+    fp = C.POINTER(C.c_float)
+    rc = L.lt_fn_match_dense_dists_host(*args, *(a.ctypes.data_as(fp) for a in out))
+    if rc != 0:
+        raise ValueError(f"lt_fn_match_dense_dists_host: rejected (code {rc})")
+    return tuple(out)
+
+
+def _warps_of(warps, descinfos, i, j):
+    if isinstance(warps, BaseDenseMatcher):
+        return warps.get_warping_symmetric(descinfos[i]["image"], descinfos[j]["image"])
+    if isinstance(warps, dict):
+        w = warps[(i, j)]
+        return w() if callable(w) else w
+    if callable(warps):
+        return warps(i, j)
+    raise ValueError("matching: warps must be a BaseDenseMatcher, a callable (i, j) -> four arrays, or a dict of those")
+
+
+def match_scene_dense(descinfos, neighbors, warps, dense_options=DefaultDenseLineMatcherOptions, sample_thresh=None,
+                      device=0, return_scores=False, warp_bytes=DENSE_WARP_BYTES):
+    """The dense kind for a scene: every image of `neighbors` (img_id -> list of neighbour ids) against its neighbours.
+    descinfos: img_id -> descinfo of DenseNaiveExtractor (needs "lines" (N, 2, 2) and "image_shape"; "image" only where
+    `warps` is a BaseDenseMatcher).  warps: a BaseDenseMatcher, a callable (i, j) -> (warp_12, cert_12, warp_21,
+    cert_21), or a dict (i, j) -> those four (or a callable without arguments that returns them); NumPy arrays or torch
+    GPU tensors, which are read in place.  sample_thresh: the certainty a sample must exceed; None asks
+    warps.get_sample_thresh().  Pairs are batched into native calls whose warps and certainties stay within warp_bytes
+    (a call takes at least one pair).  Returns what match_scene returns; the score of a row is its dists."""
+    if sample_thresh is None:
+        if not isinstance(warps, BaseDenseMatcher):
+            raise ValueError("matching: sample_thresh is needed where warps is not a BaseDenseMatcher")
+        sample_thresh = warps.get_sample_thresh()
+    neighbors = {int(i): [int(j) for j in v] for i, v in neighbors.items()}
+    ids = sorted(set(neighbors) | {j for v in neighbors.values() for j in v})
+    index = {i: k for k, i in enumerate(ids)}
+    images = [_dense_image(descinfos[i]) for i in ids]
+    out, out_s = {i: {} for i in neighbors}, {i: {} for i in neighbors}
+    todo = [(i, j) for i in sorted(neighbors) for j in neighbors[i]]
+
+    def flush(batch, maps):
+        row_off, rows, scores, _ = _match_dense_flat(images, [(index[i], index[j]) for i, j in batch], maps, dense_options,
+                                                     sample_thresh, device, return_scores)
+        for q, (i, j) in enumerate(batch):
+            out[i][j] = rows[row_off[q]:row_off[q + 1]]
+            if return_scores:
+                out_s[i][j] = scores[row_off[q]:row_off[q + 1]]
+
+    batch, maps, used, kind = [], [], 0, None
+    for i, j in todo:
+        m = _dense_maps(_warps_of(warps, descinfos, i, j), device)
+        nbytes = 4 * sum(int(np.prod(a.shape)) for a in m)
+        if batch and (used + nbytes > warp_bytes or _is_torch(m[0]) != kind):
+            flush(batch, maps)
+            batch, maps, used = [], [], 0
+        kind = _is_torch(m[0])
+        batch.append((i, j))
+        maps.append(m)
+        used += nbytes
+    if batch:
+        flush(batch, maps)
+    return (out, out_s) if return_scores else out
+
+
+class DenseLineMatcher(BaseMatcher):
+    """line2d/dense/matcher.py:22-238 (BaseDenseLineMatcher) over the native matcher: `dense_matcher` (a
+    BaseDenseMatcher) supplies the warps and the sample threshold, everything behind it runs on the device."""
+    KIND = DENSE
+
+    def __init__(self, extractor, dense_matcher, dense_options=DefaultDenseLineMatcherOptions,
+                 options=DefaultMatcherOptions, device=0):
+        super().__init__(extractor, options, device)
+        if extractor is not None and extractor.get_module_name() != "dense_naive":
+            raise ValueError("DenseLineMatcher: the extractor must be the dense_naive one")
+        if dense_options.n_samples < 2:
+            raise ValueError("DenseLineMatcher: n_samples must be at least 2")
+        if not isinstance(dense_matcher, BaseDenseMatcher):
+            raise TypeError("DenseLineMatcher: dense_matcher must be a BaseDenseMatcher")
+        self.dense_options = dense_options
+        self.dense_matcher = dense_matcher
+
+    def get_module_name(self):
+        return "dense"
+
+    def check_compatibility(self, extractor):
+        return extractor.get_module_name() == "dense_naive"
+
+    def _pair(self, descinfo1, descinfo2, opts):
+        maps = _dense_maps(self.dense_matcher.get_warping_symmetric(descinfo1["image"], descinfo2["image"]), self.device)
+        _, rows, _, _ = _match_dense_flat([_dense_image(descinfo1), _dense_image(descinfo2)], [(0, 1)], [maps], opts,
+                                          self.dense_matcher.get_sample_thresh(), self.device)
+        return rows
+
+    def match_segs_with_descinfo(self, descinfo1, descinfo2):
+        return self._pair(descinfo1, descinfo2, self.dense_options)
+
+    def match_segs_with_descinfo_topk(self, descinfo1, descinfo2, topk=10):
+        """every pair under the threshold, whatever `topk` (dense/matcher.py:200-238 never reads it)"""
+        return self._pair(descinfo1, descinfo2, self.dense_options._replace(one_to_many=True))
+
+    def compute_distance_one_direction(self, descinfo1, descinfo2, warp_1to2, cert_1to2):
+        """(weighted_dists, overlap), both (N1, N2) float32, of the restated definition, from the device"""
+        back_w, back_c = np.zeros((1, 1, 2), np.float32), np.zeros((1, 1), np.float32)
+        if _is_torch(warp_1to2) and warp_1to2.is_cuda:
+            import torch
+            back_w, back_c = (torch.from_numpy(a).to(warp_1to2.device) for a in (back_w, back_c))
+        maps = _dense_maps((warp_1to2, cert_1to2, back_w, back_c), self.device)
+        dirs = _match_dense_flat([_dense_image(descinfo1), _dense_image(descinfo2)], [(0, 1)], [maps], self.dense_options,
+                                 self.dense_matcher.get_sample_thresh(), self.device, want_dirs=True)[3]
+        return dirs[0][0], dirs[0][1]
+
+    def match_scene(self, descinfos, neighbors):
+        opts = self.dense_options if self.topk == 0 else self.dense_options._replace(one_to_many=True)
+        return match_scene_dense(descinfos, neighbors, self.dense_matcher, opts, None, self.device)
+
+
+class RoMaLineMatcher(DenseLineMatcher):
+    """line2d/dense/matcher.py:241-260.  The network is not part of this package: RoMa is built from `romatch` where
+    that is installed."""
+
+    def __init__(self, extractor, mode="outdoor", dense_options=DefaultDenseLineMatcherOptions,
+                 options=DefaultMatcherOptions, device=0):
+        super().__init__(extractor, self._roma(mode, dense_options.device), dense_options, options, device)
+
+    @staticmethod
+    def _roma(mode, device):
+        try:
+            import romatch
+        except ImportError as e:
+            raise ImportError("RoMaLineMatcher needs the `romatch` package (RoMa), which is not installed; pass warps "
+                              "from any other source to DenseLineMatcher or match_scene_dense") from e
+        return _RoMa(romatch, mode, device)
+
+    def get_module_name(self):
+        return "dense_roma"
+
+
+class _RoMa(BaseDenseMatcher):
+    """line2d/dense/dense_matcher/roma.py over an installed `romatch`"""
+
+    def __init__(self, romatch, mode="outdoor", device="cuda"):
+        super().__init__()
+        self.output_res = 864
+        self.mode = mode
+        if mode == "outdoor":
+            self.model = romatch.roma_outdoor(device=device, coarse_res=560, upsample_res=self.output_res)
+        elif mode == "indoor":
+            self.model = romatch.roma_indoor(device=device, coarse_res=560, upsample_res=self.output_res)
+        elif mode == "tiny_outdoor":
+            self.model = romatch.tiny_roma_v1_outdoor(device=device)
+        else:
+            raise ValueError(f"Unknown mode for RoMa: {mode}")
+
+    def get_sample_thresh(self):
+        return self.model.sample_thresh
+
+    def get_warping_symmetric(self, img1, img2):
+        from PIL import Image
+        im1, im2 = Image.fromarray(img1), Image.fromarray(img2)
+        warp, cert = self.model.match(im1, im2, batched=False)
+        if self.mode.startswith("tiny"):
+            back, back_cert = self.model.match(im2, im1, batched=False)
+            return warp[:, :, 2:], cert, back[:, :, 2:], back_cert
+        n = self.output_res
+        return warp[:, :n, 2:], cert[:, :n], warp[:, n:, :2], cert[:, n:]
