@@ -928,6 +928,78 @@ const char *lt_fn_undist_host_error(void);
 int lt_fn_undist_scale(int32_t w, int32_t h, double cx, double cy, const double ext[8], double blank_pixels,
                        double min_scale, double max_scale, double out[4]);
 
+/* ---- limap_amd.line2d: SOLD2 line detection from junctions and line heatmaps -- LineSegmentDetectionModule.detect of
+ * line2d/SOLD2/model/line_detection.py (heatmap refinement, candidate suppression, sampling of all junction pairs, the
+ * inlier test, junction refinement) for a whole scene in one set of launches, and the descriptor sampling of
+ * WunschLineMatcher.compute_descriptors.  DESIGN.md section 23 is the definition.  FP32 throughout; thresholds are
+ * rounded to FP32 before they are compared, as torch does. */
+typedef struct lt_sold2_config {
+  double detect_thresh, inlier_thresh, lambda_radius, nms_dist_tolerance;
+  double refine_ratio, refine_valid_thresh, refine_overlap_ratio;
+  int32_t num_samples;               /* 2 .. 64 */
+  int32_t sampling_method;           /* 0 local_max, 1 bilinear */
+  int32_t max_local_patch_radius;    /* 0 .. 4 */
+  int32_t use_candidate_suppression;
+  int32_t use_heatmap_refinement;
+  int32_t refine_mode;               /* 0 global, 1 local */
+  int32_t refine_num_blocks;         /* 1 .. 32 (local) */
+  int32_t use_junction_refinement;
+  int32_t num_perturbs;              /* odd, 1 .. 9 */
+  int32_t lds_window_floats;         /* junction refinement: largest heatmap window staged in LDS; < 0: the default */
+  const float *sampler;              /* num_samples floats: torch.linspace(0, 1, num_samples) */
+  const float *perturb_vec;          /* num_perturbs floats: the reference's torch.arange */
+} lt_sold2_config;
+/* one image: junctions (n_junc, 2) in (h, w) order and the heatmap (H, W) with heat_stride floats per row.  on_device
+ * != 0: both are device addresses, read in place.  cand_in / det_in (host form only, n_junc x n_junc bytes, the upper
+ * triangle is read): stand in for the result of the suppression / of the detection, so that a stage can be fed the
+ * output of the stage before it. */
+typedef struct lt_sold2_image {
+  const float *junctions;
+  const float *heatmap;
+  int64_t heat_stride;
+  int32_t n_junc, H, W, on_device;
+  const uint8_t *cand_in;
+  const uint8_t *det_in;
+} lt_sold2_image;
+int lt_sold2_detect_scene(lt_ctx *ctx, const lt_sold2_config *cfg, int n_img, const lt_sold2_image *imgs);
+/* the same definition on the host: no context, no device; OpenMP over n_threads threads (0: the default).  The result
+ * is kept per calling thread and read with the getters below with ctx == NULL. */
+int lt_fn_sold2_detect_host(const lt_sold2_config *cfg, int n_img, const lt_sold2_image *imgs, int n_threads);
+const char *lt_fn_sold2_host_error(void);
+/* pieces of the host form, for tests.  Samples of the given junction pairs of one image on its INPUT heatmap: pos
+ * (n_pairs, num_samples, 2) the clamped sample positions (h, w), values (n_pairs, num_samples) the local-max or
+ * bilinear sample values.  Block scales of the heatmap refinement: scales (nb, nb), negative where a block's maximum
+ * is not above valid_thresh, bounds4 (nb, 4) = row begin, row end, column begin, column end of block index a. */
+int lt_fn_sold2_samples_host(const lt_sold2_config *cfg, const lt_sold2_image *img, int64_t n_pairs,
+                             const int32_t *pairs2, float *pos, float *values);
+int lt_fn_sold2_block_scales_host(const lt_sold2_config *cfg, const lt_sold2_image *img, float *scales,
+                                  int32_t *bounds4);
+/* Getters of the last detection (ctx == NULL: of the calling thread's last host detection).  counts[n_img]: detected
+ * segments per image.  Segments of image img in candidate order: segs4 = (h1, w1, h2, w2) after junction refinement
+ * (the junctions themselves without it), pairs2 = the junction indexes i < j, perturb = index of the chosen
+ * perturbation in the reference's meshgrid order (-1 without refinement). */
+int lt_sold2_get_counts(lt_ctx *ctx, int64_t *counts);
+int lt_sold2_get_segments(lt_ctx *ctx, int img, float *segs4, int32_t *pairs2, int32_t *perturb);
+/* stages of image img, any may be NULL: heat (H, W) the refined heatmap (the input without refinement), cand / det
+ * (n_junc, n_junc) bytes: upper triangle = candidates after suppression / detected pairs */
+int lt_sold2_get_stages(lt_ctx *ctx, int img, float *heat, uint8_t *cand, uint8_t *det);
+/* device ms of the last lt_sold2_detect_scene: [0] block scales, [1] refined pixels, [2] suppression, [3] scoring,
+ * [4] compaction, [5] junction refinement, [6] all kernels, [7] whole call on the host clock */
+int lt_sold2_get_kernel_ms(lt_ctx *ctx, double out[8]);
+/* compute_descriptors, "regular" mode, after sample_line_points: per image a channel-last descriptor map (Hd, Wd, C),
+ * n_points points (h, w) in image coordinates (host memory) and the output (C, n_points): bilinear grid_sample with
+ * zero padding and align_corners = False, then L2 normalisation per point.  on_device != 0: map and out are device
+ * addresses.  out_ms (may be NULL): device ms of the kernel. */
+typedef struct lt_sold2_desc_image {
+  const float *map;
+  const float *points;
+  float *out;
+  int64_t n_points;
+  int32_t Hd, Wd, C, grid_size, on_device, pad_;
+} lt_sold2_desc_image;
+int lt_sold2_descinfo_scene(lt_ctx *ctx, int n_img, const lt_sold2_desc_image *imgs, double *out_ms);
+int lt_fn_sold2_descinfo_host(int n_img, const lt_sold2_desc_image *imgs, int n_threads);
+
 /* Counters of the last device run: [0] connections tested, [1] candidates, [2] ordered candidate
  * pairs swept by the scoring kernel (sum n_tris^2), [3] valid edges, [4] graph nodes,
  * [5] graph edges, [6] tracks, [7] nodes. */

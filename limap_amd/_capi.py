@@ -53,6 +53,9 @@ EXPORTED_SYMBOLS = [
     "lt_fn_sfm_host_get", "lt_fn_sfm_host_error", "lt_fn_sfm_ranges",
     "lt_undist_warp", "lt_undist_points", "lt_undist_get_timers", "lt_undist_copy_yardstick", "lt_fn_undist_warp_host",
     "lt_fn_undist_points_host", "lt_fn_undist_host_error", "lt_fn_undist_scale",
+    "lt_sold2_detect_scene", "lt_fn_sold2_detect_host", "lt_fn_sold2_host_error", "lt_sold2_get_counts",
+    "lt_sold2_get_segments", "lt_sold2_get_stages", "lt_sold2_get_kernel_ms", "lt_sold2_descinfo_scene",
+    "lt_fn_sold2_descinfo_host", "lt_fn_sold2_samples_host", "lt_fn_sold2_block_scales_host",
 ]
 
 
@@ -199,6 +202,29 @@ class LtUndistImage(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("src_stride", C.c_int64), ("dst_stride", C.c_int64),
                 ("src_w", C.c_int32), ("src_h", C.c_int32), ("dst_w", C.c_int32), ("dst_h", C.c_int32),
                 ("channels", C.c_int32), ("src_cam", C.c_int32), ("dst_cam", C.c_int32), ("on_device", C.c_int32)]
+
+
+class LtSold2Config(C.Structure):
+    """lt_sold2_config of include/limap_amd.h"""
+    _fields_ = [("detect_thresh", C.c_double), ("inlier_thresh", C.c_double), ("lambda_radius", C.c_double),
+                ("nms_dist_tolerance", C.c_double), ("refine_ratio", C.c_double), ("refine_valid_thresh", C.c_double),
+                ("refine_overlap_ratio", C.c_double), ("num_samples", C.c_int32), ("sampling_method", C.c_int32),
+                ("max_local_patch_radius", C.c_int32), ("use_candidate_suppression", C.c_int32),
+                ("use_heatmap_refinement", C.c_int32), ("refine_mode", C.c_int32), ("refine_num_blocks", C.c_int32),
+                ("use_junction_refinement", C.c_int32), ("num_perturbs", C.c_int32), ("lds_window_floats", C.c_int32),
+                ("sampler", C.c_void_p), ("perturb_vec", C.c_void_p)]
+
+
+class LtSold2Image(C.Structure):
+    _fields_ = [("junctions", C.c_void_p), ("heatmap", C.c_void_p), ("heat_stride", C.c_int64), ("n_junc", C.c_int32),
+                ("H", C.c_int32), ("W", C.c_int32), ("on_device", C.c_int32), ("cand_in", C.c_void_p),
+                ("det_in", C.c_void_p)]
+
+
+class LtSold2DescImage(C.Structure):
+    _fields_ = [("map", C.c_void_p), ("points", C.c_void_p), ("out", C.c_void_p), ("n_points", C.c_int64),
+                ("Hd", C.c_int32), ("Wd", C.c_int32), ("C", C.c_int32), ("grid_size", C.c_int32),
+                ("on_device", C.c_int32), ("pad_", C.c_int32)]
 
 
 def load_library():
@@ -420,6 +446,20 @@ def load_library():
     L.lt_fn_undist_host_error.restype = C.c_char_p
     L.lt_fn_undist_scale.argtypes = [C.c_int32, C.c_int32, C.c_double, C.c_double, dp, C.c_double, C.c_double,
                                      C.c_double, dp]
+    s2c, s2i, s2d = C.POINTER(LtSold2Config), C.POINTER(LtSold2Image), C.POINTER(LtSold2DescImage)
+    f32p = C.POINTER(C.c_float)
+    L.lt_sold2_detect_scene.argtypes = [vp, s2c, C.c_int, s2i]
+    L.lt_fn_sold2_detect_host.argtypes = [s2c, C.c_int, s2i, C.c_int]
+    L.lt_fn_sold2_host_error.argtypes = []
+    L.lt_fn_sold2_host_error.restype = C.c_char_p
+    L.lt_sold2_get_counts.argtypes = [vp, i64p]
+    L.lt_sold2_get_segments.argtypes = [vp, C.c_int, f32p, i32p, i32p]
+    L.lt_sold2_get_stages.argtypes = [vp, C.c_int, f32p, u8p, u8p]
+    L.lt_sold2_get_kernel_ms.argtypes = [vp, dp]
+    L.lt_sold2_descinfo_scene.argtypes = [vp, C.c_int, s2d, dp]
+    L.lt_fn_sold2_descinfo_host.argtypes = [C.c_int, s2d, C.c_int]
+    L.lt_fn_sold2_samples_host.argtypes = [s2c, s2i, C.c_int64, i32p, f32p, f32p]
+    L.lt_fn_sold2_block_scales_host.argtypes = [s2c, s2i, f32p, i32p]
     _lib = L
     return L
 

@@ -5,6 +5,7 @@
 
 #include "../../include/limap_amd.h"
 #include "lt_device.h"
+#include "lt_sold2.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -271,6 +272,33 @@ struct UdState {  // undistortion (lt_undist.cpp): staging and timers of the las
   DevBuf d_cams, d_imgs, d_src, d_dst, d_xy, d_idx, d_out, d_stat;
 };
 
+// SOLD2 line detection (lt_sold2.cpp): what the last detection left behind.  The host restatement fills the same record
+// (one per calling thread), so the getters read either.
+struct S2Result {
+  struct Meta {
+    int n, H, W;
+    long long pair0, heat0;  // first pair of the image in cand / det, first float in refined
+    const float *heat_in;    // the input heatmap where refinement is off (host result only)
+    long long heat_stride;
+  };
+  std::vector<Meta> meta;
+  std::vector<long long> seg_off;
+  std::vector<lt::S2Seg> segs;
+  std::vector<unsigned char> cand, det;  // one byte per pair
+  std::vector<float> refined;            // host result: the refined heatmaps, packed
+  bool refined_on = false;
+};
+
+struct S2State {
+  S2Result res;
+  double kernel_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  std::vector<float> h_junc, h_heat;
+  DevBuf d_cfg, d_imgs, d_junc, d_heat, d_refined, d_blk_img, d_scales, d_cand, d_det, d_list, d_seg_off, d_segs;
+  DevBuf d_pts, d_pt_off, d_maps, d_dims, d_out_off, d_map_data, d_out;
+  std::vector<const float *> dev_heat;   // device result: where image i's stage heatmap lies on the device
+  std::vector<long long> dev_stride;
+};
+
 }  // namespace lt_host
 
 using lt_host::DevBuf;
@@ -496,6 +524,7 @@ struct lt_ctx {
   lt_host::RefineState rf;
   lt_host::SfmState sf;
   lt_host::UdState ud;
+  lt_host::S2State s2;
 };
 
 #define HIPCHK(ctx, call)                                                                  \
