@@ -1000,6 +1000,70 @@ typedef struct lt_sold2_desc_image {
 int lt_sold2_descinfo_scene(lt_ctx *ctx, int n_img, const lt_sold2_desc_image *imgs, double *out_ms);
 int lt_fn_sold2_descinfo_host(int n_img, const lt_sold2_desc_image *imgs, int n_threads);
 
+/* ---- limap_amd.features: line patches resampled from dense feature maps -- limap.features' LinePatchExtractor
+ * (features/line_patch_extractor.cc, featurepatch.h, extract_line_patches.py) and the patch side of
+ * optimize/extract_track_patches_s2dnet.py.  DESIGN.md section 24 is the definition: the geometry of a patch, the
+ * global coordinate of a texel, the clamped bilinear sample, the single rounding to the output type and
+ * GetLine2DRange.  Everything is FP64; the device and the host path agree bit for bit. */
+#define LT_PATCH_F16 0
+#define LT_PATCH_F32 1
+#define LT_PATCH_F64 2
+/* a feature map of h x w texels of c channels: channel ch of texel (r, x) at ptr + r * row_stride + x * pix_stride +
+ * ch * chan_stride elements (strides of either sign); dtype LT_PATCH_F16 / _F32 / _F64, widened to double exactly.
+ * on_device != 0: ptr is device memory, read in place on the context's stream. */
+typedef struct lt_feature_map {
+  const void *ptr;
+  int64_t h, w, c, row_stride, pix_stride, chan_stride;
+  int32_t dtype;
+  int32_t on_device;
+} lt_feature_map;
+typedef struct lt_patch_config {
+  double k_stretch;   /* 1.0 */
+  int32_t t_stretch;  /* 10 */
+  int32_t range_perp; /* 20 (cfgs/refinement/default.yaml passes 16) */
+} lt_patch_config;
+void lt_patch_config_default(lt_patch_config *cfg);
+/* The patches of n lines (lines4 = x1, y1, x2, y2 each) of one feature map: patch i is an array (h_i, range_perp + 1,
+ * c) of out_dtype, and the patches lie behind one another in line order.  out in host memory (out_on_device == 0): the
+ * packed output goes there through chunks of whole patches of at most max_chunk_bytes each (at least one patch; <= 0:
+ * 2^30), one launch per chunk.  out in device memory (out_on_device != 0, on a 16-byte boundary): one launch writes it in
+ * place.  out == NULL: one launch, and the packed output stays in the context until its next patch call (the two
+ * getters below).  Returns after the stream has finished.  LT_ERR_ARGUMENT before any work for: a line
+ * coordinate that is not finite, range_perp < 0 or above 4096, t_stretch < 0, a k_stretch that is not finite, h, w or c
+ * below 1, an unknown dtype, a null map, a patch of more than 2^20 rows or whose geometry is not finite. */
+int lt_patch_extract(lt_ctx *ctx, const lt_patch_config *cfg, const lt_feature_map *map, int64_t n, const double *lines4,
+                     int32_t out_dtype, void *out, int32_t out_on_device, int64_t max_chunk_bytes);
+/* of the last lt_patch_extract, any may be NULL: R4[4 n] = perp.x, perp.y, direc.x, direc.y (PatchInfo::R, row-major),
+ * tvec2[2 n] the corner, h[n] the rows, off[n + 1] the first element of every patch in the packed output */
+int lt_patch_get_geometry(lt_ctx *ctx, double *R4, double *tvec2, int32_t *h, int64_t *off);
+/* the packed output a call with out == NULL left on the device: its address and size, or a host copy */
+int lt_patch_get_device_out(lt_ctx *ctx, void **ptr, int64_t *bytes);
+int lt_patch_get_out(lt_ctx *ctx, void *dst);
+/* of the last lt_patch_extract: host ms of [0] validation, tables and the map's upload, [2] the downloads; [1] device ms
+ * (HIP events) of the kernel over all chunks; [3] patches, [4] chunks, [5] 1 when the vector form of the kernel ran and 0
+ * for the scalar form, [6] workgroups, [7] bytes of the packed output */
+int lt_patch_get_timers(lt_ctx *ctx, double out[8]);
+/* the yardstick of the measurement (tools/time_patch.py): device ms of a copy kernel that moves `bytes` bytes, 16 per
+ * lane, between two buffers of the context */
+int lt_patch_copy_yardstick(lt_ctx *ctx, int64_t bytes, double *ms);
+/* The same definition on the host, no context and no device: the same inline functions, OpenMP over n_threads threads
+ * (0: the default); out is the whole packed output.  lt_fn_patch_geometry is the geometry alone (c: the channels the
+ * offsets count).  lt_fn_patch_host_error is the message of the calling thread's last lt_fn_patch_* call that returned
+ * LT_ERR_ARGUMENT ("" after a success). */
+int lt_fn_patch_extract_host(const lt_patch_config *cfg, const lt_feature_map *map, int64_t n, const double *lines4,
+                             int32_t out_dtype, void *out, int n_threads);
+int lt_fn_patch_geometry(const lt_patch_config *cfg, int64_t c, int64_t n, const double *lines4, double *R4,
+                         double *tvec2, int32_t *h, int64_t *off);
+const char *lt_fn_patch_host_error(void);
+/* GetLine2DRange for n_pairs (track, image) pairs.  Tracks as CSR arrays: line6[6 n_tracks] the 3D lines, sup_off[n_tracks
+ * + 1] their supports, sup_img the supports' image ids, sup_seg4 their 2D lines.  Pair i: track pair_track[i], image id
+ * pair_img[i], camera pair_cam11[11 i ..] = kvec, qvec, tvec.  range4[4 n_pairs]; status[n_pairs]: 0, 1 when the track has
+ * no support in that image, 2 when an endpoint of the 3D line is not in front of the camera or a coordinate of the
+ * range is not finite. */
+int lt_fn_patch_ranges(int64_t n_tracks, const double *line6, const int64_t *sup_off, const int32_t *sup_img,
+                       const double *sup_seg4, int64_t n_pairs, const int32_t *pair_track, const int32_t *pair_img,
+                       const double *pair_cam11, double *range4, int32_t *status);
+
 /* Counters of the last device run: [0] connections tested, [1] candidates, [2] ordered candidate
  * pairs swept by the scoring kernel (sum n_tris^2), [3] valid edges, [4] graph nodes,
  * [5] graph edges, [6] tracks, [7] nodes. */

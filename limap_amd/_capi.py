@@ -56,6 +56,9 @@ EXPORTED_SYMBOLS = [
     "lt_sold2_detect_scene", "lt_fn_sold2_detect_host", "lt_fn_sold2_host_error", "lt_sold2_get_counts",
     "lt_sold2_get_segments", "lt_sold2_get_stages", "lt_sold2_get_kernel_ms", "lt_sold2_descinfo_scene",
     "lt_fn_sold2_descinfo_host", "lt_fn_sold2_samples_host", "lt_fn_sold2_block_scales_host",
+    "lt_patch_config_default", "lt_patch_extract", "lt_patch_get_geometry", "lt_patch_get_device_out", "lt_patch_get_out",
+    "lt_patch_get_timers", "lt_patch_copy_yardstick", "lt_fn_patch_extract_host", "lt_fn_patch_geometry",
+    "lt_fn_patch_host_error", "lt_fn_patch_ranges",
 ]
 
 
@@ -225,6 +228,20 @@ class LtSold2DescImage(C.Structure):
     _fields_ = [("map", C.c_void_p), ("points", C.c_void_p), ("out", C.c_void_p), ("n_points", C.c_int64),
                 ("Hd", C.c_int32), ("Wd", C.c_int32), ("C", C.c_int32), ("grid_size", C.c_int32),
                 ("on_device", C.c_int32), ("pad_", C.c_int32)]
+
+
+class LtFeatureMap(C.Structure):
+    """lt_feature_map of include/limap_amd.h"""
+    _fields_ = [("ptr", C.c_void_p), ("h", C.c_int64), ("w", C.c_int64), ("c", C.c_int64), ("row_stride", C.c_int64),
+                ("pix_stride", C.c_int64), ("chan_stride", C.c_int64), ("dtype", C.c_int32), ("on_device", C.c_int32)]
+
+
+class LtPatchConfig(C.Structure):
+    """lt_patch_config of include/limap_amd.h"""
+    _fields_ = [("k_stretch", C.c_double), ("t_stretch", C.c_int32), ("range_perp", C.c_int32)]
+
+
+PATCH_F16, PATCH_F32, PATCH_F64 = 0, 1, 2
 
 
 def load_library():
@@ -460,6 +477,20 @@ def load_library():
     L.lt_fn_sold2_descinfo_host.argtypes = [C.c_int, s2d, C.c_int]
     L.lt_fn_sold2_samples_host.argtypes = [s2c, s2i, C.c_int64, i32p, f32p, f32p]
     L.lt_fn_sold2_block_scales_host.argtypes = [s2c, s2i, f32p, i32p]
+    pcp, fmp = C.POINTER(LtPatchConfig), C.POINTER(LtFeatureMap)
+    L.lt_patch_config_default.argtypes = [pcp]
+    L.lt_patch_config_default.restype = None
+    L.lt_patch_extract.argtypes = [vp, pcp, fmp, C.c_int64, dp, C.c_int32, vp, C.c_int32, C.c_int64]
+    L.lt_patch_get_geometry.argtypes = [vp, dp, dp, i32p, i64p]
+    L.lt_patch_get_device_out.argtypes = [vp, C.POINTER(C.c_void_p), i64p]
+    L.lt_patch_get_out.argtypes = [vp, vp]
+    L.lt_patch_get_timers.argtypes = [vp, dp]
+    L.lt_patch_copy_yardstick.argtypes = [vp, C.c_int64, dp]
+    L.lt_fn_patch_extract_host.argtypes = [pcp, fmp, C.c_int64, dp, C.c_int32, vp, C.c_int]
+    L.lt_fn_patch_geometry.argtypes = [pcp, C.c_int64, C.c_int64, dp, dp, dp, i32p, i64p]
+    L.lt_fn_patch_host_error.argtypes = []
+    L.lt_fn_patch_host_error.restype = C.c_char_p
+    L.lt_fn_patch_ranges.argtypes = [C.c_int64, dp, i64p, i32p, dp, C.c_int64, i32p, i32p, dp, dp, i32p]
     _lib = L
     return L
 

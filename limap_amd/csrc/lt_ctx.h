@@ -6,6 +6,7 @@
 #include "../../include/limap_amd.h"
 #include "lt_device.h"
 #include "lt_sold2.h"
+#include "lt_patch.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -272,6 +273,16 @@ struct UdState {  // undistortion (lt_undist.cpp): staging and timers of the las
   DevBuf d_cams, d_imgs, d_src, d_dst, d_xy, d_idx, d_out, d_stat;
 };
 
+struct PtState {  // line patch extraction (lt_patch.cpp): geometry, timers and output of the last lt_patch_extract
+  double timers[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // lt_patch_get_timers
+  std::vector<lt::PtGeom> geom;
+  std::vector<long long> off;            // n + 1: first element of every patch in the packed output
+  int out_dtype = 0;
+  long long resident_bytes = -1;         // bytes of the packed output left in d_out (-1: none, it was downloaded in chunks)
+  std::vector<unsigned char> h_map;      // a strided host map, packed for its upload
+  DevBuf d_map, d_patches, d_blocks, d_out, d_ys_src, d_ys_dst;
+};
+
 // SOLD2 line detection (lt_sold2.cpp): what the last detection left behind.  The host restatement fills the same record
 // (one per calling thread), so the getters read either.
 struct S2Result {
@@ -525,6 +536,7 @@ struct lt_ctx {
   lt_host::SfmState sf;
   lt_host::UdState ud;
   lt_host::S2State s2;
+  lt_host::PtState pt;
 };
 
 #define HIPCHK(ctx, call)                                                                  \
