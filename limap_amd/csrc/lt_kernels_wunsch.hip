@@ -2,41 +2,26 @@
 // point-score matrix P by the FP32-input MFMA, every num_samples x num_samples block pooled into a line score in the
 // accumulator's own layout, the top-k lines of every line selected on chip (k_wunsch_topk); and, for the mutual form,
 // the Needleman-Wunsch values of every line's candidates in both orientations (k_wunsch_nw) with the cross check
-// (k_wunsch_mutual).  Neither P nor the line scores reach memory.
+// (k_mutual).  Neither P nor the line scores reach memory.
 //
 // Tile layout.  Every line has 8 point slots: its S samples, then zero rows.  A 32 x 32 MFMA tile therefore holds
-// 4 x 4 whole line blocks.  As in k_match_topk the A operand is the tile of image 2 (LDS), the B operand the wave's 32
-// point slots of image 1 (registers): lane l owns slot r = l & 31 of image 1 -- line r >> 3, sample s = r & 7 -- and its
-// register q the image-2 slot (q & 3) + 8 (q >> 2) + 4 (l >> 5): line q >> 2, sample t = (q & 3) + 4 (l >> 5).  So
+// 4 x 4 whole line blocks.  The score tile and the key lists are the core of lt_match_dev.h, shared with k_match_topk:
+// the A operand is the tile of image 2 (LDS), the B operand the wave's 32 point slots of image 1 (registers); lane l
+// owns slot r = l & 31 of image 1 -- line r >> 3, sample s = r & 7 -- and its register q the image-2 slot
+// (q & 3) + 8 (q >> 2) + 4 (l >> 5): line q >> 2, sample t = (q & 3) + 4 (l >> 5).  So
 //   max over t  = four registers and the partner lane l ^ 32 (a slot pair past S is absent: -inf never wins),
 //   max over s  = three cross-lane steps inside 8 consecutive lanes,
 //   the sums    = the same two patterns: the fixed tree ((0 + 1) + (2 + 3)) + ((4 + 5) + (6 + 7)) of wunsch_pool8.
 // Every cross-lane step is a butterfly of a commutative operation, so all lanes of a line end with the same bits.
 
+#include "lt_match_dev.h"
 #include "lt_wunsch.h"
 
 namespace lt {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned long long u64;
-
 constexpr int kListStride = 2 * kWunschTileLines;  // lists per wave: (line of the wave, half)
-
-__device__ inline void wlist_insert(u64 *list, int kcap, int &cnt, u64 &thr, u64 key) {
-  int p;
-  if (cnt < kcap) p = cnt++;
-  else p = kcap - 1;
-  while (p > 0) {
-    const u64 prev = list[(p - 1) * kListStride];
-    if (prev > key) break;
-    list[p * kListStride] = prev;
-    --p;
-  }
-  list[p * kListStride] = key;
-  thr = (cnt == kcap) ? list[(kcap - 1) * kListStride] : 0ull;
-}
 
 // sum / count / maximum over the 8 lanes of a line (lanes that differ in bits 0..2)
 __device__ inline float sum8(float v) {
@@ -66,7 +51,7 @@ k_wunsch_topk(const WunschTask *__restrict__ tasks, const MatchUnit *__restrict_
               const unsigned char *__restrict__ vmask, int dim, int S, int kcap, unsigned short *__restrict__ out_col,
               float *__restrict__ out_score) {
   extern __shared__ __align__(16) unsigned char smem[];
-  const int stride = dim + kMatchPad, half = dim >> 1;
+  const int threads = (int)blockDim.x, stride = dim + kMatchPad, half = dim >> 1;
   float *sB = reinterpret_cast<float *>(smem);                                       // [32][stride], k permuted
   u64 *lists = reinterpret_cast<u64 *>(smem + sizeof(float) * kMatchTile * stride);  // [wave][slot][line, half]
 
@@ -79,55 +64,24 @@ k_wunsch_topk(const WunschTask *__restrict__ tasks, const MatchUnit *__restrict_
   const bool valid1 = (m1 >> s) & 1u;
   u64 *my = lists + (size_t)wave * kcap * kListStride + (r >> 3) * 2 + h;
 
-  // this lane's k-steps of its point row: k = 2 step + h; slots past S and lines past the image are zero rows
-  float ra[HALF];
-  {
-    const float4 *src =
-        reinterpret_cast<const float4 *>(desc + (T.a0 + (row_ok ? (long long)line * S + s : 0)) * (long long)dim);
-#pragma unroll
-    for (int t = 0; t < HALF / 2; ++t) {
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (4 * t < dim && row_ok) v = src[t];
-      ra[2 * t] = h ? v.y : v.x;
-      ra[2 * t + 1] = h ? v.w : v.z;
-    }
-  }
+  float ra[HALF];  // this lane's k-steps of its point row; slots past S and lines past the image are zero rows
+  load_row<HALF>(desc + (T.a0 + (row_ok ? (long long)line * S + s : 0)) * (long long)dim, dim, row_ok, h, ra);
 
   int cnt = 0;
   u64 thr = 0ull;
-  const int q4 = dim >> 2;  // float4 per descriptor row
   for (int col0 = 0; col0 < T.nb; col0 += kWunschTileLines) {
-    __syncthreads();  // the previous tile has been read
-    // stage 4 lines of image b as 32 slots, position of k: (k & 1) * half + (k >> 1)
-    for (int e = tid; e < kMatchTile * q4; e += (int)blockDim.x) {
-      const int c = e / q4, u = e - c * q4;
+    // 4 lines of image b as 32 slots
+    stage_tile(sB, dim, threads, [&](int c, const float *&src) {
       const int bl = col0 + (c >> 3), bt = c & 7;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (bl < T.nb && bt < S) v = reinterpret_cast<const float4 *>(desc + (T.b0 + (long long)bl * S + bt) * (long long)dim)[u];
-      float *dst = sB + c * stride;
-      *reinterpret_cast<float2 *>(dst + 2 * u) = make_float2(v.x, v.z);
-      *reinterpret_cast<float2 *>(dst + half + 2 * u) = make_float2(v.y, v.w);
-    }
-    __syncthreads();
+      src = desc + (T.b0 + (long long)bl * S + bt) * (long long)dim;
+      return bl < T.nb && bt < S;
+    });
 
     unsigned m2s[kWunschTileLines];  // validity bytes of the tile's lines (uniform), fetched under the MFMAs
 #pragma unroll
     for (int jl = 0; jl < kWunschTileLines; ++jl) m2s[jl] = col0 + jl < T.nb ? vmask[T.lb0 + col0 + jl] : 0u;
 
-    f32x16 acc;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc[q] = 0.f;
-    const float4 *bp = reinterpret_cast<const float4 *>(sB + r * stride + h * half);
-#pragma unroll
-    for (int t = 0; t < HALF / 4; ++t) {
-      if (8 * t < dim) {  // (uniform)
-        const float4 b = bp[t];
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(b.x, ra[4 * t], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(b.y, ra[4 * t + 1], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(b.z, ra[4 * t + 2], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(b.w, ra[4 * t + 3], acc, 0, 0, 0);
-      }
-    }
+    const f32x16 acc = mfma_tile<HALF>(reinterpret_cast<const float4 *>(sB + r * stride + h * half), ra, dim);
 
     // pooling: one neighbour line (4 registers) at a time
     float sc[kWunschTileLines];
@@ -168,30 +122,15 @@ k_wunsch_topk(const WunschTask *__restrict__ tasks, const MatchUnit *__restrict_
         const int col = col0 + 2 * h + e;
         if (col < T.nb) {
           const u64 key = match_key(score, (unsigned)col);
-          if (key > thr) wlist_insert(my, kcap, cnt, thr, key);
+          if (key > thr) topk_insert<kListStride>(my, kcap, cnt, thr, key);
         }
       }
     }
   }
 
-  // merge the lists of lanes r and r + 32: the kk best of the line, best first.  The partner's list was written by
-  // another lane of this wave: order its stores before the loads below explicitly.
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  const int cnt_hi = __shfl(cnt, r + 32);
-  if (h == 0 && s == 0 && line_ok) {
-    const u64 *la = my, *lb = my + 1;
-    const long long o = T.out0 + (long long)line * T.kk;
-    int ia = 0, ib = 0;
-    for (int t = 0; t < T.kk; ++t) {
-      const u64 ka = ia < cnt ? la[ia * kListStride] : 0ull, kb = ib < cnt_hi ? lb[ib * kListStride] : 0ull;
-      u64 best;
-      if (ka > kb) { best = ka; ++ia; }
-      else { best = kb; ++ib; }
-      out_col[o + t] = (unsigned short)match_key_col(best);
-      out_score[o + t] = match_key_score(best);
-    }
-  }
+  // the lists of lanes r and r + 32 hold the line's columns: its kk best, best first
+  const long long o = T.out0 + (long long)line * T.kk;
+  merge_lists<kListStride>(h == 0 && s == 0 && line_ok, my, my + 1, cnt, T.kk, out_col + o, out_score + o);
 }
 
 // One group of kWunschNwGroup lanes per (task, line): lane `sub` takes the candidates sub, sub + 16, ...; it restates
@@ -274,28 +213,13 @@ k_wunsch_nw(const WunschTask *__restrict__ tasks, const long long *__restrict__ 
   }
 }
 
-// one workgroup per pair: line i keeps its match j only if the match of j is i
-__global__ void k_wunsch_mutual(const WunschTask *__restrict__ tasks, int n_pairs, unsigned short *mcol) {
-  const WunschTask F = tasks[blockIdx.x], B = tasks[n_pairs + blockIdx.x];
-  if (F.kk == 0) return;
-  for (int i = (int)threadIdx.x; i < F.na; i += (int)blockDim.x) {
-    const unsigned j = mcol[F.mout0 + i];  // (slot i is read and written by this thread alone)
-    mcol[F.mout0 + i] = (mcol[B.mout0 + j] == (unsigned)i) ? (unsigned short)j : (unsigned short)0xffff;
-  }
-}
-
 }  // namespace
-
-size_t wunsch_lds_bytes(int dim, int kcap, int waves) {
-  return sizeof(float) * kMatchTile * (size_t)(dim + kMatchPad) +
-         sizeof(u64) * kListStride * (size_t)kcap * (size_t)waves;
-}
 
 void launch_wunsch_topk(hipStream_t st, int dim, int S, int kcap, int waves, const WunschTask *tasks,
                         const MatchUnit *units, int n_units, const float *desc, const unsigned char *vmask,
                         unsigned short *out_col, float *out_score) {
   if (n_units <= 0) return;
-  const size_t lds = wunsch_lds_bytes(dim, kcap, waves);
+  const size_t lds = topk_lds_bytes(dim, kcap, waves, kListStride);
   const dim3 grid((unsigned)n_units), block(64u * (unsigned)waves);
 #define LT_WUNSCH_LAUNCH(H)                                                                                        \
   do {                                                                                                             \
@@ -334,8 +258,7 @@ void launch_wunsch_nw(hipStream_t st, int dim, int S, const WunschTask *tasks, c
 }
 
 void launch_wunsch_mutual(hipStream_t st, const WunschTask *tasks, int n_pairs, unsigned short *mcol) {
-  if (n_pairs <= 0) return;
-  hipLaunchKernelGGL(k_wunsch_mutual, dim3((unsigned)n_pairs), dim3(256), 0, st, tasks, n_pairs, mcol);
+  launch_mutual<WunschTask, &WunschTask::mout0>(st, tasks, n_pairs, 1, mcol);
 }
 
 }  // namespace lt

@@ -1,10 +1,10 @@
 // lt_match.cpp -- line-descriptor matching (limap.line2d: L2D2Matcher, NNEndpointsMatcher top-k) for a whole scene in
 // one call: validation, one upload of the descriptors, the launches of lt_kernels_match.hip on the context's stream,
 // context-owned rows with getters, timers; and the host restatement lt_fn_match_pair_host of the same semantics
-// (std::fmaf in a plain loop).  DESIGN §17.
+// (std::fmaf in a plain loop).  The entry point is four steps: its configuration check, its tasks and units, the stage
+// of lt_match_scene.h, its launches and that header's collection of the result.  DESIGN §17.
 
-#include "lt_host.h"
-#include "lt_match.h"
+#include "lt_match_scene.h"
 
 #include <algorithm>
 #include <cmath>
@@ -32,20 +32,6 @@ int check_config(const lt_match_config *cfg, int dim, std::string &msg) {
   return 0;
 }
 
-bool values_ok(const float *v, long long n) {
-  int bad = 0;
-#pragma omp parallel for reduction(| : bad) schedule(static)
-  for (long long k = 0; k < n; ++k) bad |= !(std::fabs(v[k]) <= kMatchMaxAbs);
-  return !bad;
-}
-
-// score(i, j): the fmaf chain in ascending k from +0.0f
-inline float dot_chain(const float *a, const float *b, int dim) {
-  float acc = 0.0f;
-  for (int k = 0; k < dim; ++k) acc = std::fmaf(a[k], b[k], acc);
-  return acc;
-}
-
 }  // namespace
 
 extern "C" {
@@ -53,32 +39,25 @@ extern "C" {
 int lt_match_scene(lt_ctx *ctx, int n_img, const int64_t *desc_off, const float *desc, int dim, const int64_t *pair_off,
                    const int32_t *pair_nb, const lt_match_config *cfg, int64_t *n_rows) {
   if (!ctx) return LT_ERR_ARGUMENT;
-  const std::string who = "lt_match_scene: ";
+  const char *fn = "lt_match_scene";
+  const std::string who = std::string(fn) + ": ";
   std::string msg;
   if (check_config(cfg, dim, msg)) return fail(ctx, LT_ERR_ARGUMENT, who + msg);
-  if (n_img < 0 || !desc_off || !pair_off) return fail(ctx, LT_ERR_ARGUMENT, who + "bad image count or null offsets");
-  if (int rc = check_offsets(ctx, "lt_match_scene", "descriptor", n_img, desc_off)) return rc;
-  if (int rc = check_offsets(ctx, "lt_match_scene", "pair", n_img, pair_off)) return rc;
   const int rpl = cfg->kind == LT_MATCH_ENDPOINTS ? 2 : 1;  // descriptor rows per line
-  for (int m = 0; m < n_img; ++m) {
-    const int64_t n = desc_off[m + 1] - desc_off[m];
-    if (n % rpl) return fail(ctx, LT_ERR_ARGUMENT, who + "an image has an odd number of endpoints");
-    if (n / rpl > kMatchMaxLines) return fail(ctx, LT_ERR_ARGUMENT, who + "more than 65535 lines in an image");
-  }
+  if (int rc = check_scene(ctx, fn, n_img, {{"descriptor", desc_off}}, pair_off, pair_nb, !desc, [&](int m) -> const char * {
+        const int64_t n = desc_off[m + 1] - desc_off[m];
+        if (n % rpl) return "an image has an odd number of endpoints";
+        return n / rpl > kMatchMaxLines ? "more than 65535 lines in an image" : nullptr;
+      }))
+    return rc;
   const long long n_desc = desc_off[n_img], n_pairs = pair_off[n_img];
-  if (n_pairs > (1 << 30)) return fail(ctx, LT_ERR_ARGUMENT, who + "too many pairs");
-  if ((n_desc > 0 && !desc) || (n_pairs > 0 && !pair_nb)) return fail(ctx, LT_ERR_ARGUMENT, who + "null input");
-  for (long long p = 0; p < n_pairs; ++p)
-    if (pair_nb[p] < 0 || pair_nb[p] >= n_img) return fail(ctx, LT_ERR_ARGUMENT, who + "a neighbour is not an image");
-  const bool on_dev = cfg->desc_on_device != 0;
   double t0 = now_ms();
-  if (!on_dev && !values_ok(desc, n_desc * dim))
-    return fail(ctx, LT_ERR_ARGUMENT, who + "a descriptor value is not finite or above 2^57 in magnitude");
 
   // ---- tasks (a pair each; mutual: the swapped pairs behind them), units, output slots ----
   const bool mutual = cfg->topk == 0;
   const int topk = mutual ? 1 : cfg->topk;
   std::vector<MatchTask> tasks((size_t)n_pairs * (mutual ? 2 : 1));
+  std::vector<int> kk((size_t)n_pairs);
   std::vector<long long> &row_off = ctx->mt.row_off;
   row_off.assign((size_t)n_pairs + 1, 0);
   long long slots = 0;
@@ -93,15 +72,14 @@ int lt_match_scene(lt_ctx *ctx, int n_img, const int64_t *desc_off, const float 
         T.na = (int)(desc_off[m + 1] - desc_off[m]);
         T.b0 = desc_off[nb];
         T.nb = (int)(desc_off[nb + 1] - desc_off[nb]);
-        T.kk = T.na > 0 ? std::min(topk, T.nb / rpl) : 0;
+        T.kk = kk[(size_t)p] = T.na > 0 ? std::min(topk, T.nb / rpl) : 0;
         T.out0 = slots;
         T.pad_ = 0;
         slots += (long long)(T.na / rpl) * T.kk;
-        row_off[(size_t)p + 1] = slots;  // (mutual: an upper bound, replaced below)
+        row_off[(size_t)p + 1] = slots;  // (mutual: an upper bound, replaced by collect_rows)
         kcap = std::max(kcap, T.kk);
       }
   }
-  const long long fwd_slots = slots;
   if (mutual)
     for (long long p = 0; p < n_pairs; ++p) {
       const MatchTask &F = tasks[(size_t)p];
@@ -118,33 +96,18 @@ int lt_match_scene(lt_ctx *ctx, int n_img, const int64_t *desc_off, const float 
   if (units.size() > 0x7fffffffull) return fail(ctx, LT_ERR_ARGUMENT, who + "too many row tiles");
 
   // ---- upload ----
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const float *d_desc = desc;
-  if (!on_dev) {
-    ENSURE(ctx, ctx->mt.d_desc, sizeof(float) * (size_t)std::max<long long>(n_desc * dim, 1));
-    if (n_desc)
-      HIPCHK(ctx, hipMemcpyAsync(ctx->mt.d_desc.p, desc, sizeof(float) * (size_t)(n_desc * dim), hipMemcpyHostToDevice, st));
-    d_desc = ctx->mt.d_desc.as<float>();
-  }
+  const float *d_desc = nullptr;
+  if (int rc = stage_desc(ctx, fn, desc, n_desc * dim, cfg->desc_on_device != 0, &d_desc)) return rc;
   if (int rc = upload_vec(ctx, ctx->mt.d_tasks, tasks)) return rc;
   if (int rc = upload_vec(ctx, ctx->mt.d_units, units)) return rc;
   ENSURE(ctx, ctx->mt.d_col, 2 * (size_t)std::max<long long>(slots, 1) + 16);
   ENSURE(ctx, ctx->mt.d_score, 4 * (size_t)std::max<long long>(slots, 1));
-  if (on_dev && n_desc) {  // the same rejection as on the host, by a kernel of its own, before the matching launches
-    ENSURE(ctx, ctx->mt.d_flag, 16);
-    HIPCHK(ctx, hipMemsetAsync(ctx->mt.d_flag.p, 0, 4, st));
-    launch_match_check(st, d_desc, n_desc * dim, ctx->mt.d_flag.as<int>());
-    int flag = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&flag, ctx->mt.d_flag.p, 4, hipMemcpyDeviceToHost, st));
-    if (int rc = stream_sync(ctx)) return rc;
-    if (flag) return fail(ctx, LT_ERR_ARGUMENT, who + "a descriptor value is not finite or above 2^57 in magnitude");
-  }
   if (int rc = stream_sync(ctx)) return rc;
   double t1 = now_ms();
   ctx->mt.timers[0] = t1 - t0;
 
   // ---- kernels ----
+  hipStream_t st = ctx->stream;
   launch_match_topk(st, cfg->kind, dim, kcap, waves, ctx->mt.d_tasks.as<MatchTask>(), ctx->mt.d_units.as<MatchUnit>(),
                     (int)units.size(), d_desc, ctx->mt.d_col.as<unsigned short>(), ctx->mt.d_score.as<float>());
   if (mutual)
@@ -153,36 +116,7 @@ int lt_match_scene(lt_ctx *ctx, int n_img, const int64_t *desc_off, const float 
   double t2 = now_ms();
   ctx->mt.timers[1] = t2 - t1;
 
-  // ---- download: 2 bytes per row, the scores only when asked for ----
-  ctx->mt.col.resize((size_t)fwd_slots);
-  ctx->mt.score.clear();
-  if (fwd_slots)
-    HIPCHK(ctx, hipMemcpyAsync(ctx->mt.col.data(), ctx->mt.d_col.p, 2 * (size_t)fwd_slots, hipMemcpyDeviceToHost, st));
-  if (cfg->want_scores && fwd_slots) {
-    ctx->mt.score.resize((size_t)fwd_slots);
-    HIPCHK(ctx, hipMemcpyAsync(ctx->mt.score.data(), ctx->mt.d_score.p, 4 * (size_t)fwd_slots, hipMemcpyDeviceToHost, st));
-  }
-  if (int rc = stream_sync(ctx)) return rc;
-  double t3 = now_ms();
-  ctx->mt.timers[2] = t3 - t2;
-
-  // ---- rows: (line, neighbour line) per slot; mutual keeps the slots that survived ----
-  ctx->mt.kk.resize((size_t)n_pairs);
-  for (long long p = 0; p < n_pairs; ++p) ctx->mt.kk[(size_t)p] = tasks[(size_t)p].kk;
-  ctx->mt.slot_off.assign(row_off.begin(), row_off.end());
-  if (mutual) {
-    for (long long p = 0; p < n_pairs; ++p) {
-      long long n = 0;
-      for (long long s = ctx->mt.slot_off[(size_t)p]; s < ctx->mt.slot_off[(size_t)p + 1]; ++s)
-        n += ctx->mt.col[(size_t)s] != 0xffff;
-      row_off[(size_t)p + 1] = row_off[(size_t)p] + n;
-    }
-  }
-  ctx->mt.mutual = mutual;
-  ctx->mt.dense = false;
-  ctx->mt.timers[3] = now_ms() - t3;
-  if (n_rows) *n_rows = (int64_t)row_off.back();
-  return LT_OK;
+  return collect_rows(ctx, ctx->mt.d_col, ctx->mt.d_score, std::move(kk), cfg->want_scores != 0, mutual, t2, n_rows);
 }
 
 int lt_match_get(lt_ctx *ctx, int64_t *row_off, int32_t *rows2) {
@@ -248,25 +182,9 @@ int lt_fn_match_pair_host(const float *desc1, int64_t n1, const float *desc2, in
     return match_endpoint_score(dot_chain(a0, b0, dim), dot_chain(a1, b1, dim), dot_chain(a0, b1, dim),
                                 dot_chain(a1, b0, dim));
   };
-  std::vector<unsigned long long> best((size_t)m1 * kk), col_best(mutual ? (size_t)m2 : 0, 0ull);
-#pragma omp parallel
-  {
-    std::vector<unsigned long long> keys((size_t)m2);
-#pragma omp for schedule(static)
-    for (long long i = 0; i < m1; ++i) {
-      for (long long j = 0; j < m2; ++j) keys[(size_t)j] = match_key(line_score(i, j), (unsigned)j);
-      std::partial_sort(keys.begin(), keys.begin() + kk, keys.end(), std::greater<unsigned long long>());
-      std::copy(keys.begin(), keys.begin() + kk, best.begin() + i * kk);
-    }
-    if (mutual) {
-#pragma omp for schedule(static)
-      for (long long j = 0; j < m2; ++j) {
-        unsigned long long b = 0ull;
-        for (long long i = 0; i < m1; ++i) b = std::max(b, match_key(line_score(i, j), (unsigned)i));
-        col_best[(size_t)j] = b;
-      }
-    }
-  }
+  std::vector<unsigned long long> best, col_best;  // per line its kk best columns; mutual: per column its best line
+  best_columns(m1, m2, kk, line_score, best);
+  if (mutual) best_columns(m2, m1, 1, [&](long long j, long long i) { return line_score(i, j); }, col_best);
   long long n = 0;
   for (long long i = 0; i < m1; ++i)
     for (int t = 0; t < kk; ++t) {

@@ -2,14 +2,14 @@
 // validation, one upload of the point descriptors and the validity bytes, the launches of lt_kernels_wunsch.hip on the
 // context's stream, the rows in the state lt_match_get / lt_match_get_scores / lt_match_get_timers read; and the host
 // restatement lt_fn_match_wunsch_pair_host of the same semantics (std::fmaf in a plain loop, the pooling and the
-// Needleman-Wunsch recurrence of lt_wunsch.h).  DESIGN §17, "SOLD2".
+// Needleman-Wunsch recurrence of lt_wunsch.h).  The scene path around the tasks and the launches is the one of
+// lt_match_scene.h, shared with lt_match.cpp.  DESIGN §17, "SOLD2".
 
-#include "lt_host.h"
+#include "lt_match_scene.h"
 #include "lt_wunsch.h"
 
 #include <algorithm>
 #include <cmath>
-#include <functional>
 #include <string>
 #include <vector>
 
@@ -37,13 +37,6 @@ int check_config(const lt_match_wunsch_config *cfg, int dim, std::string &msg) {
   return 0;
 }
 
-bool values_ok(const float *v, long long n) {
-  int bad = 0;
-#pragma omp parallel for reduction(| : bad) schedule(static)
-  for (long long k = 0; k < n; ++k) bad |= !(std::fabs(v[k]) <= kMatchMaxAbs);
-  return !bad;
-}
-
 // validity byte per line (bit s = sample s); false when a line has no valid sample
 bool pack_masks(const uint8_t *valid, long long n_lines, int S, unsigned char *out) {
   bool ok = true;
@@ -54,12 +47,6 @@ bool pack_masks(const uint8_t *valid, long long n_lines, int S, unsigned char *o
     ok = ok && m != 0;
   }
   return ok;
-}
-
-inline float dot_chain(const float *a, const float *b, int dim) {
-  float acc = 0.0f;
-  for (int k = 0; k < dim; ++k) acc = std::fmaf(a[k], b[k], acc);
-  return acc;
 }
 
 // the masked S x S block of lines (i, j): P[s * S + t]
@@ -108,22 +95,6 @@ void pair_scores(const float *d1, const unsigned char *m1, long long n1, const f
   }
 }
 
-// per line of image 1 (rows of L, row stride ld_i, column stride ld_j): the kk best columns, best first
-void best_lines(const float *L, long long n1, long long n2, long long ld_i, long long ld_j, int kk,
-                std::vector<unsigned long long> &best) {
-  best.assign((size_t)n1 * kk, 0ull);
-#pragma omp parallel
-  {
-    std::vector<unsigned long long> keys((size_t)n2);
-#pragma omp for schedule(static)
-    for (long long i = 0; i < n1; ++i) {
-      for (long long j = 0; j < n2; ++j) keys[(size_t)j] = match_key(L[i * ld_i + j * ld_j], (unsigned)j);
-      std::partial_sort(keys.begin(), keys.begin() + kk, keys.end(), std::greater<unsigned long long>());
-      std::copy(keys.begin(), keys.begin() + kk, best.begin() + i * kk);
-    }
-  }
-}
-
 }  // namespace
 
 extern "C" {
@@ -132,38 +103,30 @@ int lt_match_wunsch_scene(lt_ctx *ctx, int n_img, const int64_t *line_off, const
                           const uint8_t *valid, int dim, const int64_t *pair_off, const int32_t *pair_nb,
                           const lt_match_wunsch_config *cfg, int64_t *n_rows) {
   if (!ctx) return LT_ERR_ARGUMENT;
-  const std::string who = "lt_match_wunsch_scene: ";
+  const char *fn = "lt_match_wunsch_scene";
+  const std::string who = std::string(fn) + ": ";
   std::string msg;
   if (check_config(cfg, dim, msg)) return fail(ctx, LT_ERR_ARGUMENT, who + msg);
-  if (n_img < 0 || !line_off || !desc_off || !pair_off)
-    return fail(ctx, LT_ERR_ARGUMENT, who + "bad image count or null offsets");
-  if (int rc = check_offsets(ctx, "lt_match_wunsch_scene", "line", n_img, line_off)) return rc;
-  if (int rc = check_offsets(ctx, "lt_match_wunsch_scene", "descriptor", n_img, desc_off)) return rc;
-  if (int rc = check_offsets(ctx, "lt_match_wunsch_scene", "pair", n_img, pair_off)) return rc;
   const int S = cfg->num_samples;
-  for (int m = 0; m < n_img; ++m) {
-    const int64_t n = line_off[m + 1] - line_off[m];
-    if (desc_off[m + 1] - desc_off[m] != n * S)
-      return fail(ctx, LT_ERR_ARGUMENT, who + "an image's descriptor count is not num_samples times its mask rows");
-    if (n > kMatchMaxLines) return fail(ctx, LT_ERR_ARGUMENT, who + "more than 65535 lines in an image");
-  }
+  if (int rc = check_scene(ctx, fn, n_img, {{"line", line_off}, {"descriptor", desc_off}}, pair_off, pair_nb, !desc || !valid,
+                           [&](int m) -> const char * {
+                             const int64_t n = line_off[m + 1] - line_off[m];
+                             if (desc_off[m + 1] - desc_off[m] != n * S)
+                               return "an image's descriptor count is not num_samples times its mask rows";
+                             return n > kMatchMaxLines ? "more than 65535 lines in an image" : nullptr;
+                           }))
+    return rc;
   const long long n_lines = line_off[n_img], n_desc = desc_off[n_img], n_pairs = pair_off[n_img];
-  if (n_pairs > (1 << 30)) return fail(ctx, LT_ERR_ARGUMENT, who + "too many pairs");
-  if ((n_desc > 0 && (!desc || !valid)) || (n_pairs > 0 && !pair_nb)) return fail(ctx, LT_ERR_ARGUMENT, who + "null input");
-  for (long long p = 0; p < n_pairs; ++p)
-    if (pair_nb[p] < 0 || pair_nb[p] >= n_img) return fail(ctx, LT_ERR_ARGUMENT, who + "a neighbour is not an image");
   std::vector<unsigned char> vmask((size_t)std::max<long long>(n_lines, 1), 0);
   if (!pack_masks(valid, n_lines, S, vmask.data()))
     return fail(ctx, LT_ERR_ARGUMENT, who + "a line has no valid sample");
-  const bool on_dev = cfg->desc_on_device != 0;
   double t0 = now_ms();
-  if (!on_dev && !values_ok(desc, n_desc * dim))
-    return fail(ctx, LT_ERR_ARGUMENT, who + "a descriptor value is not finite or above 2^57 in magnitude");
 
   // ---- tasks (a pair each; mutual: the swapped pairs behind them), units, output slots ----
   const bool mutual = cfg->topk == 0;
   const int topk = mutual ? cfg->top_k_candidates : cfg->topk;
   std::vector<WunschTask> tasks((size_t)n_pairs * (mutual ? 2 : 1));
+  std::vector<int> kk((size_t)n_pairs);  // columns kept per line: the mutual form keeps a line's one match
   std::vector<long long> &row_off = ctx->mt.row_off;
   row_off.assign((size_t)n_pairs + 1, 0);
   long long slots = 0, mslots = 0;
@@ -186,11 +149,11 @@ int lt_match_wunsch_scene(lt_ctx *ctx, int n_img, const int64_t *line_off, const
         T.pad_ = 0;
         slots += (long long)T.na * T.kk;
         if (T.kk) mslots += T.na;
-        row_off[(size_t)p + 1] = mutual ? mslots : slots;  // (mutual: an upper bound, replaced below)
+        row_off[(size_t)p + 1] = mutual ? mslots : slots;  // (mutual: an upper bound, replaced by collect_rows)
+        kk[(size_t)p] = mutual ? (T.kk ? 1 : 0) : T.kk;
         kcap = std::max(kcap, T.kk);
       }
   }
-  const long long fwd_slots = mutual ? mslots : slots;
   if (mutual)
     for (long long p = 0; p < n_pairs; ++p) {
       const WunschTask &F = tasks[(size_t)p];
@@ -212,15 +175,8 @@ int lt_match_wunsch_scene(lt_ctx *ctx, int n_img, const int64_t *line_off, const
   if (units.size() > 0x7fffffffull) return fail(ctx, LT_ERR_ARGUMENT, who + "too many row tiles");
 
   // ---- upload ----
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const float *d_desc = desc;
-  if (!on_dev) {
-    ENSURE(ctx, ctx->mt.d_desc, sizeof(float) * (size_t)std::max<long long>(n_desc * dim, 1));
-    if (n_desc)
-      HIPCHK(ctx, hipMemcpyAsync(ctx->mt.d_desc.p, desc, sizeof(float) * (size_t)(n_desc * dim), hipMemcpyHostToDevice, st));
-    d_desc = ctx->mt.d_desc.as<float>();
-  }
+  const float *d_desc = nullptr;
+  if (int rc = stage_desc(ctx, fn, desc, n_desc * dim, cfg->desc_on_device != 0, &d_desc)) return rc;
   if (int rc = upload_vec(ctx, ctx->mt.d_vmask, vmask)) return rc;
   if (int rc = upload_vec(ctx, ctx->mt.d_tasks, tasks)) return rc;
   if (int rc = upload_vec(ctx, ctx->mt.d_units, units)) return rc;
@@ -232,20 +188,12 @@ int lt_match_wunsch_scene(lt_ctx *ctx, int n_img, const int64_t *line_off, const
     ENSURE(ctx, ctx->mt.d_mcol, 2 * (size_t)std::max<long long>(mslots, 1) + 16);
     ENSURE(ctx, ctx->mt.d_mscore, 4 * (size_t)std::max<long long>(mslots, 1));
   }
-  if (on_dev && n_desc) {  // the same rejection as on the host, by a kernel of its own, before the matching launches
-    ENSURE(ctx, ctx->mt.d_flag, 16);
-    HIPCHK(ctx, hipMemsetAsync(ctx->mt.d_flag.p, 0, 4, st));
-    launch_match_check(st, d_desc, n_desc * dim, ctx->mt.d_flag.as<int>());
-    int flag = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&flag, ctx->mt.d_flag.p, 4, hipMemcpyDeviceToHost, st));
-    if (int rc = stream_sync(ctx)) return rc;
-    if (flag) return fail(ctx, LT_ERR_ARGUMENT, who + "a descriptor value is not finite or above 2^57 in magnitude");
-  }
   if (int rc = stream_sync(ctx)) return rc;
   double t1 = now_ms();
   ctx->mt.timers[0] = t1 - t0;
 
   // ---- kernels ----
+  hipStream_t st = ctx->stream;
   Events<3> ev;
   if (int rc = ev.create(ctx)) return rc;
   const WunschTask *d_tasks = ctx->mt.d_tasks.as<WunschTask>();
@@ -267,37 +215,9 @@ int lt_match_wunsch_scene(lt_ctx *ctx, int n_img, const int64_t *line_off, const
   ctx->mt.kernel_ms[0] = ev.ms(0, 1);
   ctx->mt.kernel_ms[1] = mutual ? ev.ms(1, 2) : 0.0;
 
-  // ---- download: 2 bytes per row, the scores only when asked for ----
-  const DevBuf &rc_col = mutual ? ctx->mt.d_mcol : ctx->mt.d_col, &rc_score = mutual ? ctx->mt.d_mscore : ctx->mt.d_score;
-  ctx->mt.col.resize((size_t)fwd_slots);
-  ctx->mt.score.clear();
-  if (fwd_slots)
-    HIPCHK(ctx, hipMemcpyAsync(ctx->mt.col.data(), rc_col.p, 2 * (size_t)fwd_slots, hipMemcpyDeviceToHost, st));
-  if (cfg->want_scores && fwd_slots) {
-    ctx->mt.score.resize((size_t)fwd_slots);
-    HIPCHK(ctx, hipMemcpyAsync(ctx->mt.score.data(), rc_score.p, 4 * (size_t)fwd_slots, hipMemcpyDeviceToHost, st));
-  }
-  if (int rc = stream_sync(ctx)) return rc;
-  double t3 = now_ms();
-  ctx->mt.timers[2] = t3 - t2;
-
-  // ---- rows: (line, neighbour line) per slot; mutual keeps the slots that survived ----
-  ctx->mt.kk.resize((size_t)n_pairs);
-  for (long long p = 0; p < n_pairs; ++p) ctx->mt.kk[(size_t)p] = mutual ? (tasks[(size_t)p].kk ? 1 : 0) : tasks[(size_t)p].kk;
-  ctx->mt.slot_off.assign(row_off.begin(), row_off.end());
-  if (mutual) {
-    for (long long p = 0; p < n_pairs; ++p) {
-      long long n = 0;
-      for (long long s = ctx->mt.slot_off[(size_t)p]; s < ctx->mt.slot_off[(size_t)p + 1]; ++s)
-        n += ctx->mt.col[(size_t)s] != 0xffff;
-      row_off[(size_t)p + 1] = row_off[(size_t)p] + n;
-    }
-  }
-  ctx->mt.mutual = mutual;
-  ctx->mt.dense = false;
-  ctx->mt.timers[3] = now_ms() - t3;
-  if (n_rows) *n_rows = (int64_t)row_off.back();
-  return LT_OK;
+  // the mutual form's rows are the matches of k_wunsch_nw that survived the cross check, a slot per line
+  return collect_rows(ctx, mutual ? ctx->mt.d_mcol : ctx->mt.d_col, mutual ? ctx->mt.d_mscore : ctx->mt.d_score,
+                      std::move(kk), cfg->want_scores != 0, mutual, t2, n_rows);
 }
 
 int lt_match_wunsch_get_kernel_ms(lt_ctx *ctx, double out[2]) {
@@ -349,7 +269,7 @@ int lt_fn_match_wunsch_pair_host(const float *desc1, const uint8_t *valid1, int6
   long long n = 0;
   if (!mutual) {
     const int kk = (int)std::min<long long>(cfg->topk, n2);
-    best_lines(L.data(), n1, n2, n2, 1, kk, best);
+    best_columns(n1, n2, kk, [&](long long i, long long j) { return L[(size_t)(i * n2 + j)]; }, best);
     for (long long i = 0; i < n1; ++i)
       for (int t = 0; t < kk; ++t, ++n) {
         const unsigned long long key = best[(size_t)(i * kk + t)];
@@ -363,7 +283,7 @@ int lt_fn_match_wunsch_pair_host(const float *desc1, const uint8_t *valid1, int6
   auto direction = [&](bool swapped, std::vector<int> &match, std::vector<float> &mscore) {
     const long long na = swapped ? n2 : n1, nb = swapped ? n1 : n2;
     const int kc = (int)std::min<long long>(cfg->top_k_candidates, nb);
-    best_lines(L.data(), na, nb, swapped ? 1 : n2, swapped ? n2 : 1, kc, best);
+    best_columns(na, nb, kc, [&](long long i, long long j) { return L[(size_t)(swapped ? j * n2 + i : i * n2 + j)]; }, best);
     match.assign((size_t)na, -1);
     mscore.assign((size_t)na, 0.0f);
 #pragma omp parallel for schedule(static)

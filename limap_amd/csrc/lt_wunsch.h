@@ -83,7 +83,6 @@ __host__ __device__ inline double wunsch_nw(const float *P, int ld, bool reverse
   return row[S];
 }
 
-size_t wunsch_lds_bytes(int dim, int kcap, int waves);
 // kernel 1: line scores by the FP32-input MFMA, pooled in the accumulator layout, top-kk lines per line
 void launch_wunsch_topk(hipStream_t st, int dim, int S, int kcap, int waves, const WunschTask *tasks,
                         const MatchUnit *units, int n_units, const float *desc, const unsigned char *vmask,

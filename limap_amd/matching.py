@@ -153,30 +153,9 @@ def _wunsch_cfg(topk, num_samples, top_k_candidates, on_dev=0, want_scores=0):
     return _capi.LtMatchWunschConfig(int(topk), int(num_samples), int(top_k_candidates), on_dev, want_scores, 0)
 
 
-def _match_flat_sold2(parts, valids, pair_off, pair_nb, topk, num_samples, top_k_candidates, device=0,
-                      want_scores=False):
-    """lt_match_wunsch_scene: parts = point-descriptor rows per image, valids = (N, S) uint8 per image"""
-    ctx = _context(device)
-    dim = _width(parts)
-    line_off = np.zeros(len(parts) + 1, np.int64)
-    line_off[1:] = np.cumsum([v.shape[0] for v in valids])
-    desc_off = np.zeros(len(parts) + 1, np.int64)
-    desc_off[1:] = np.cumsum([p.shape[0] for p in parts])
-    keep, dptr, on_dev = _gather(parts, dim, device)
-    valid = np.ascontiguousarray(np.concatenate([v.reshape(-1) for v in valids]) if valids else np.zeros(0), np.uint8)
-    if valid.size == 0:
-        valid = np.zeros(1, np.uint8)
-    pair_off, pair_nb = _capi.i64(pair_off), _capi.i32(pair_nb)
-    cfg = _wunsch_cfg(topk, num_samples, top_k_candidates, on_dev, 1 if want_scores else 0)
-    n_rows = C.c_int64(0)
-    ctx.chk(ctx.L.lt_match_wunsch_scene(ctx.h, len(parts), _capi.ptr(line_off, C.c_int64), _capi.ptr(desc_off, C.c_int64),
-                                        dptr, valid.ctypes.data_as(C.POINTER(C.c_uint8)), dim,
-                                        _capi.ptr(pair_off, C.c_int64),
-                                        _capi.ptr(pair_nb if len(pair_nb) else _capi.i32([0]), C.c_int32),
-                                        C.byref(cfg), C.byref(n_rows)))
-    del keep
-    n = int(n_rows.value)
-    row_off = np.zeros(len(pair_nb) + 1, np.int64)
+def _rows_of_last_call(ctx, n_pairs, n, want_scores):
+    """lt_match_get and, when asked for, lt_match_get_scores of a native call that left n rows: row_off, rows, scores"""
+    row_off = np.zeros(n_pairs + 1, np.int64)
     rows = np.zeros((n, 2), np.int32)
     ctx.chk(ctx.L.lt_match_get(ctx.h, _capi.ptr(row_off, C.c_int64), _capi.ptr(rows, C.c_int32) if n else None))
     scores = None
@@ -184,6 +163,37 @@ def _match_flat_sold2(parts, valids, pair_off, pair_nb, topk, num_samples, top_k
         scores = np.zeros(n, np.float32)
         ctx.chk(ctx.L.lt_match_get_scores(ctx.h, scores.ctypes.data_as(C.POINTER(C.c_float)) if n else None))
     return row_off, rows, scores
+
+
+def _match_flat(parts, pair_off, pair_nb, kind, topk, device=0, want_scores=False, valids=None, num_samples=5,
+                top_k_candidates=10):
+    """the native call: parts = descriptor rows per image (all NumPy or all torch); returns row_off, rows, scores.
+    kind SOLD2 is lt_match_wunsch_scene: parts = point-descriptor rows per image, valids = (N, S) uint8 per image"""
+    ctx = _context(device)
+    dim = _width(parts)
+    desc_off = np.zeros(len(parts) + 1, np.int64)
+    desc_off[1:] = np.cumsum([p.shape[0] for p in parts])
+    keep, dptr, on_dev = _gather(parts, dim, device)
+    pair_off, pair_nb = _capi.i64(pair_off), _capi.i32(pair_nb)
+    pairs = (_capi.ptr(pair_off, C.c_int64), _capi.ptr(pair_nb if len(pair_nb) else _capi.i32([0]), C.c_int32))
+    n_rows = C.c_int64(0)
+    if kind == SOLD2:
+        line_off = np.zeros(len(parts) + 1, np.int64)
+        line_off[1:] = np.cumsum([v.shape[0] for v in valids])
+        valid = np.ascontiguousarray(np.concatenate([v.reshape(-1) for v in valids]) if valids else np.zeros(0), np.uint8)
+        if valid.size == 0:
+            valid = np.zeros(1, np.uint8)
+        cfg = _wunsch_cfg(topk, num_samples, top_k_candidates, on_dev, 1 if want_scores else 0)
+        ctx.chk(ctx.L.lt_match_wunsch_scene(ctx.h, len(parts), _capi.ptr(line_off, C.c_int64),
+                                            _capi.ptr(desc_off, C.c_int64), dptr,
+                                            valid.ctypes.data_as(C.POINTER(C.c_uint8)), dim, *pairs, C.byref(cfg),
+                                            C.byref(n_rows)))
+    else:
+        cfg = _capi.LtMatchConfig(int(kind), int(topk), on_dev, 1 if want_scores else 0)
+        ctx.chk(ctx.L.lt_match_scene(ctx.h, len(parts), _capi.ptr(desc_off, C.c_int64), dptr, dim, *pairs, C.byref(cfg),
+                                     C.byref(n_rows)))
+    del keep
+    return _rows_of_last_call(ctx, len(pair_nb), int(n_rows.value), want_scores)
 
 
 def kernel_ms(device=0):
@@ -245,30 +255,6 @@ def timers(device=0):
     return out
 
 
-def _match_flat(parts, pair_off, pair_nb, kind, topk, device=0, want_scores=False):
-    """the native call: parts = descriptor rows per image (all NumPy or all torch); returns row_off, rows, scores"""
-    ctx = _context(device)
-    dim = _width(parts)
-    desc_off = np.zeros(len(parts) + 1, np.int64)
-    desc_off[1:] = np.cumsum([p.shape[0] for p in parts])
-    keep, dptr, on_dev = _gather(parts, dim, device)
-    pair_off, pair_nb = _capi.i64(pair_off), _capi.i32(pair_nb)
-    cfg = _capi.LtMatchConfig(int(kind), int(topk), on_dev, 1 if want_scores else 0)
-    n_rows = C.c_int64(0)
-    ctx.chk(ctx.L.lt_match_scene(ctx.h, len(parts), _capi.ptr(desc_off, C.c_int64), dptr, dim,
-                                 _capi.ptr(pair_off, C.c_int64), _capi.ptr(pair_nb if len(pair_nb) else _capi.i32([0]), C.c_int32),
-                                 C.byref(cfg), C.byref(n_rows)))
-    n = int(n_rows.value)
-    row_off = np.zeros(len(pair_nb) + 1, np.int64)
-    rows = np.zeros((n, 2), np.int32)
-    ctx.chk(ctx.L.lt_match_get(ctx.h, _capi.ptr(row_off, C.c_int64), _capi.ptr(rows, C.c_int32) if n else None))
-    scores = None
-    if want_scores:
-        scores = np.zeros(n, np.float32)
-        ctx.chk(ctx.L.lt_match_get_scores(ctx.h, scores.ctypes.data_as(C.POINTER(C.c_float)) if n else None))
-    return row_off, rows, scores
-
-
 def match_scene(descinfos, neighbors, kind="l2d2", topk=10, device=0, return_scores=False, num_samples=5,
                 top_k_candidates=10):
     """Match every image of `neighbors` (img_id -> list of neighbour ids) against its neighbours in one native call.
@@ -284,6 +270,7 @@ def match_scene(descinfos, neighbors, kind="l2d2", topk=10, device=0, return_sco
     neighbors = {int(i): [int(j) for j in v] for i, v in neighbors.items()}
     ids = sorted(set(neighbors) | {j for v in neighbors.values() for j in v})
     index = {i: k for k, i in enumerate(ids)}
+    valids = None
     if kind == SOLD2:
         both = [_sold2_parts(descinfos[i], num_samples) for i in ids]
         parts, valids = [b[0] for b in both], [b[1] for b in both]
@@ -294,11 +281,8 @@ def match_scene(descinfos, neighbors, kind="l2d2", topk=10, device=0, return_sco
     for k, i in enumerate(ids):
         pair_nb.extend(index[j] for j in neighbors.get(i, []))
         pair_off[k + 1] = len(pair_nb)
-    if kind == SOLD2:
-        row_off, rows, scores = _match_flat_sold2(parts, valids, pair_off, pair_nb, topk, num_samples, top_k_candidates,
-                                                  device, return_scores)
-    else:
-        row_off, rows, scores = _match_flat(parts, pair_off, pair_nb, kind, topk, device, return_scores)
+    row_off, rows, scores = _match_flat(parts, pair_off, pair_nb, kind, topk, device, return_scores, valids, num_samples,
+                                        top_k_candidates)
     out, out_s = {}, {}
     for k, i in enumerate(ids):
         if i not in neighbors:
@@ -498,8 +482,8 @@ class SOLD2Matcher(BaseMatcher):
 
     def _pair(self, descinfo1, descinfo2, topk):
         both = [_sold2_parts(descinfo1, self.num_samples), _sold2_parts(descinfo2, self.num_samples)]
-        _, rows, _ = _match_flat_sold2([b[0] for b in both], [b[1] for b in both], [0, 1, 1], [1], topk,
-                                       self.num_samples, self.top_k_candidates, self.device)
+        _, rows, _ = _match_flat([b[0] for b in both], [0, 1, 1], [1], SOLD2, topk, self.device, False,
+                                 [b[1] for b in both], self.num_samples, self.top_k_candidates)
         return rows
 
     def match_segs_with_descinfo(self, descinfo1, descinfo2):
@@ -666,14 +650,7 @@ def _match_dense_flat(images, pairs, maps, opts, sample_thresh, device=0, want_s
                                        _capi.ptr(pair_img, C.c_int32), warp_p, cert_p, _capi.ptr(dims, C.c_int32),
                                        C.byref(cfg), C.byref(n_rows)))
     del maps
-    nr = int(n_rows.value)
-    row_off = np.zeros(n + 1, np.int64)
-    rows = np.zeros((nr, 2), np.int32)
-    ctx.chk(ctx.L.lt_match_get(ctx.h, _capi.ptr(row_off, C.c_int64), _capi.ptr(rows, C.c_int32) if nr else None))
-    scores = None
-    if want_scores:
-        scores = np.zeros(nr, np.float32)
-        ctx.chk(ctx.L.lt_match_get_scores(ctx.h, scores.ctypes.data_as(C.POINTER(C.c_float)) if nr else None))
+    row_off, rows, scores = _rows_of_last_call(ctx, n, int(n_rows.value), want_scores)
     dirs = None
     if want_dirs:
         sizes = [images[a][0].shape[0] * images[b][0].shape[0] for a, b in pairs]

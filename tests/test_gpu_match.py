@@ -119,6 +119,42 @@ def test_batched_equals_per_pair_calls_and_torch_input():
                           matching.match_pair_host(a, b, "l2d2", 0))
 
 
+def test_every_kind_in_turn_on_one_context():
+    """The three native matchers leave their result in one state of the context, which lt_match_get* read: every kind
+    after another kind, mutual after top-k and back, with and without scores, each identical to its restatement.  17 and
+    33 lines cross the 4- and 16-line tiles of SOLD2, the 16-line tile of the dense kind and the 32-row tile of the
+    descriptor kinds."""
+    import dense_cases as dc
+    import wunsch_cases as wc
+    rng = np.random.default_rng(23)
+    ctx = matching._context(0)
+    descs = {"l2d2": [_rand(rng, "l2d2", m, 8) for m in (17, 33)], "endpoints": [_rand(rng, "endpoints", m, 8) for m in (17, 33)],
+             "sold2": [wc.rand_descinfo(rng, m, 5) for m in (17, 33)]}
+    da, db, warps = dc.overlapping_pair(rng, 17, 33, dims=(1, 1))  # a warp of one texel
+    opts = matching.BaseDenseLineMatcherOptions()
+
+    def same(rows, scores, host):
+        assert rows.dtype == np.int32 and len(rows) > 0 and rows.shape == host[0].shape and np.array_equal(rows, host[0])
+        if scores is not None:
+            assert np.array_equal(_bits(scores), _bits(host[1]))
+        else:  # the call did not ask for scores (want_scores): LT_ERR_STATE
+            buf = np.zeros(1, np.float32)
+            assert ctx.L.lt_match_get_scores(ctx.h, buf.ctypes.data_as(C.POINTER(C.c_float))) == -4
+
+    def sparse(kind, topk, scores):
+        got = matching.match_scene(dict(enumerate(descs[kind])), {0: [1]}, kind, topk, return_scores=scores)
+        host = matching.match_pair_host(descs[kind][0], descs[kind][1], kind, topk, return_scores=True)
+        same(got[0][0][1] if scores else got[0][1], got[1][0][1] if scores else None, host)
+
+    sparse("l2d2", 0, False)
+    sparse("sold2", 10, True)
+    got = matching.match_scene_dense({0: da, 1: db}, {0: [1]}, {(0, 1): warps}, opts, 0.5, return_scores=True)
+    same(got[0][0][1], got[1][0][1], matching.match_dense_pair_host(da, db, warps, opts, 0.5, return_scores=True))
+    sparse("endpoints", 10, False)
+    sparse("sold2", 0, True)
+    sparse("l2d2", 10, True)
+
+
 def test_match_all_neighbors_writes_the_files(tmp_path):
     sc = syn.make_scene(n_views=4, n_segs=30, n_neighbors=2, seed=6)
     di = syn.make_descriptors(sc, "l2d2", seed=1)

@@ -33,7 +33,7 @@ def med(f, n=7):
 def native(parts, valids, pair_off, pair_nb, topk):
     def once():
         t = time.perf_counter()
-        matching._match_flat_sold2(parts, valids, pair_off, pair_nb, topk, S, KC, 0)
+        matching._match_flat(parts, pair_off, pair_nb, matching.SOLD2, topk, 0, False, valids, S, KC)
         wall = (time.perf_counter() - t) * 1e3
         return np.concatenate([[wall], matching.timers(0), matching.kernel_ms(0)])
     once()
