@@ -1064,6 +1064,103 @@ int lt_fn_patch_ranges(int64_t n_tracks, const double *line6, const int64_t *sup
                        const double *sup_seg4, int64_t n_pairs, const int32_t *pair_track, const int32_t *pair_img,
                        const double *pair_cam11, double *range4, int32_t *status);
 
+/* ---- limap.optimize.hybrid_localization: point-line pose refinement (LineLocEngine, JointLocEngine, solve_jointloc;
+ * DESIGN.md section 25).  Every problem refines one camera pose (qvec, tvec; kvec = fx, fy, cx, cy of a PINHOLE camera
+ * is constant) from its 2D-3D line and point correspondences: residual blocks in JointLocEngine::AddResiduals' order
+ * (hybrid_localization.cc:91-134) -- per 3D line its 2D segments with ScaledLoss(loss, weight_line length / sum_lengths),
+ * then the points with ScaledLoss(loss, weight_point) -- and the cost 1/2 sum rho_k(|r_k|^2).  All problems of a call
+ * run in one launch, one wave per problem.  The minimiser is the Levenberg-Marquardt definition of section 19 with six
+ * unknowns: refined poses are minimisers of upstream's cost, not the iterates of a Ceres run. */
+#define LT_LOC_COST_MIDPOINT2 0       /* LineLocCostFunction, upstream's order */
+#define LT_LOC_COST_MIDPOINT_ANGLE3 1
+#define LT_LOC_COST_PERPENDICULAR2 2
+#define LT_LOC_COST_PERPENDICULAR4 3
+#define LT_LOC_COST_LINELINE2 4
+#define LT_LOC_COST_PLANELINE2 5
+#define LT_LOC_WEIGHT_NONE 0          /* LineLocCostFunctionWeight, upstream's order */
+#define LT_LOC_WEIGHT_COSINE 1
+#define LT_LOC_WEIGHT_LINE3DPP 2      /* rejected: it needs an arccosine */
+#define LT_LOC_WEIGHT_LENGTH 3
+#define LT_LOC_WEIGHT_INVLENGTH 4
+#define LT_LOC_LOSS_TRIVIAL 0
+#define LT_LOC_LOSS_HUBER 1
+#define LT_LOC_LOSS_SOFTLONE 2
+#define LT_LOC_LOSS_CAUCHY 3
+typedef struct lt_loc_config {
+  int32_t cost_function;       /* LT_LOC_COST_*; the 3D forms switch the points to their 3D distance too */
+  int32_t weight_function;     /* LT_LOC_WEIGHT_* */
+  int32_t loss;                /* LT_LOC_LOSS_* */
+  int32_t max_num_iterations;  /* 100 */
+  double loss_a;               /* the parameter of Huber, SoftLOne and Cauchy; > 0 */
+  double weight_line, weight_point;
+} lt_loc_config;
+void lt_loc_config_default(lt_loc_config *cfg);
+/* n_prob problems as CSR arrays.  Problem n: kvec4[4 n ..], the initial pose qvec4[4 n ..] (normalised once, as
+ * CameraPose does) and tvec3[3 n ..]; its 3D lines line_off[n] .. line_off[n + 1] of line3d6 (start, end); 3D line l is
+ * observed by the 2D segments seg_off[l] .. seg_off[l + 1] of seg4 (x1 y1 x2 y2); its points pt_off[n] .. pt_off[n + 1]
+ * of p3d3 / p2d2.  LineLocEngine is the call without points and weight_line = 1.
+ * LT_ERR_ARGUMENT before any launch: non-finite input, a zero focal length or quaternion, a 3D line of zero length
+ * (upstream divides its direction by sqrt(1e-8) and constrains against a zero direction), a 3D line whose segments have
+ * sum_lengths == 0 (0 / 0 upstream), LT_LOC_WEIGHT_LINE3DPP, a loss parameter <= 0, negative weights or iterations. */
+int lt_loc_solve(lt_ctx *ctx, int64_t n_prob, const double *kvec4, const double *qvec4, const double *tvec3,
+                 const int64_t *line_off, const double *line3d6, const int64_t *seg_off, const double *seg4,
+                 const int64_t *pt_off, const double *p3d3, const double *p2d2, const lt_loc_config *cfg);
+/* of the last lt_loc_solve (any pointer may be NULL): per problem the refined pose, cost2 = the cost at the initial and
+ * at the final pose (GetInitialCost / GetFinalCost are sqrt(cost / num_res)), the number of residuals, the iterations
+ * and the termination code: 0 max_num_iterations, 1 radius, 2 zero gradient (IsSolutionUsable for 0-2), 3 pivot,
+ * 4 model decrease, 6 the cost at the initial pose is not finite, 7 no residual block (Solve() returns false); 6 and 7
+ * keep the pose */
+int64_t lt_loc_num(lt_ctx *ctx);
+int lt_loc_get(lt_ctx *ctx, double *qvec4, double *tvec3, double *cost2, int32_t *num_res, int32_t *iters, int32_t *codes);
+/* host ms of [0] validation, tables and upload, [1] the kernel, [2] download; device ms (HIP events) of [3] k_loc_lm */
+int lt_loc_get_timers(lt_ctx *ctx, double out[4]);
+/* The same definition on the host, no context and no device: the same inline functions, the reductions in the device's
+ * order, bit-identical results; OpenMP over n_threads threads (0: the default).  Outputs as lt_loc_get. */
+int lt_fn_loc_host(int64_t n_prob, const double *kvec4, const double *qvec4, const double *tvec3, const int64_t *line_off,
+                   const double *line3d6, const int64_t *seg_off, const double *seg4, const int64_t *pt_off,
+                   const double *p3d3, const double *p2d2, const lt_loc_config *cfg, int n_threads, double *qvec4_out,
+                   double *tvec3_out, double *cost2, int32_t *num_res, int32_t *iters, int32_t *codes);
+/* the message of the calling thread's last lt_fn_loc_* call that returned LT_ERR_ARGUMENT ("" after a success) */
+const char *lt_fn_loc_host_error(void);
+/* For tests: one problem at a given pose -- residuals (4 slots per block in block order, NaN where a block has fewer),
+ * the cost, the gradient g = sum rho' J^T r and H = sum rho' J^T J over the six local directions (rotation, translation) */
+int lt_fn_loc_eval(const double kvec4[4], const double qvec4[4], const double tvec3[3], int64_t n_lines,
+                   const double *line3d6, const int64_t *seg_off, const double *seg4, int64_t n_points, const double *p3d3,
+                   const double *p2d2, const lt_loc_config *cfg, double *residuals, double *cost, double g[6], double H[36]);
+/* Pose scoring: JointPoseEstimator::EvaluateModelOnPoint (estimators/absolute_pose/joint_pose_estimator.cc:176-251) for
+ * n_poses hypotheses x N = n_pts + n_seg correspondences of one camera in one launch, the points first.  2D segment s
+ * observes 3D line l3d_ids[s].  A cell is the squared norm of the correspondence's residuals (lines with ENoneWeight),
+ * or DBL_MAX where a cheirality test fails: a NaN pose; a point below cheirality_min_depth; for a line a ray through a
+ * 2D endpoint within 1 degree of the 3D line, an unprojection below cheirality_min_depth, or less than
+ * cheirality_overlap_pixels between the projections of the 2D endpoints onto the reprojected segment.  With want_msac
+ * each pose also gets the MSAC score sum_i min(r2_i, squared_thresholds[type]) weights[type] and the counts of
+ * r2_i < squared_thresholds[type] per type (0 points, 1 lines), pl_absolute_pose_hybrid_ransac.h:338-393.
+ * LT_ERR_ARGUMENT before any launch: LT_LOC_COST_MIDPOINT_ANGLE3 (upstream throws), non-finite correspondences or
+ * intrinsics (poses may be non-finite), a 3D line of zero length that a segment refers to, an l3d_id out of range. */
+typedef struct lt_loc_score_config {
+  int32_t cost_function;  /* LT_LOC_COST_* */
+  int32_t want_msac;
+  double cheirality_min_depth, cheirality_overlap_pixels;  /* 0.0, 10.0 */
+  double squared_thresholds[2], weights[2];
+} lt_loc_score_config;
+int lt_loc_score(lt_ctx *ctx, const double kvec4[4], int64_t n_l3d, const double *line3d6, int64_t n_seg,
+                 const int32_t *l3d_ids, const double *seg4, int64_t n_pts, const double *p3d3, const double *p2d2,
+                 int64_t n_poses, const double *qvec4, const double *tvec3, const lt_loc_score_config *cfg);
+/* of the last lt_loc_score: the sizes; table[n_poses N] row-major by pose, scores[n_poses], inliers2[2 n_poses] (any
+ * may be NULL; the last two are an LT_ERR_STATE where the call did not ask for them) */
+int lt_loc_score_size(lt_ctx *ctx, int64_t *n_poses, int64_t *n_corr);
+int lt_loc_score_get(lt_ctx *ctx, double *table, double *scores, int32_t *inliers2);
+/* host ms of [0] validation, table and upload, [1] the kernel, [2] download; device ms (HIP events) of [3] k_loc_score */
+int lt_loc_score_get_timers(lt_ctx *ctx, double out[4]);
+/* The same definition on the host, bit-identical results (the score summed in the device's order); errors through
+ * lt_fn_loc_host_error */
+int lt_fn_loc_score_host(const double kvec4[4], int64_t n_l3d, const double *line3d6, int64_t n_seg, const int32_t *l3d_ids,
+                         const double *seg4, int64_t n_pts, const double *p3d3, const double *p2d2, int64_t n_poses,
+                         const double *qvec4, const double *tvec3, const lt_loc_score_config *cfg, int n_threads,
+                         double *table, double *scores, int32_t *inliers2);
+/* CameraPose(R, T)'s quaternion: Eigen's Quaternion(Matrix3) of the row-major R9, (w, x, y, z) */
+int lt_fn_loc_qvec_from_R(const double R9[9], double qvec4[4]);
+
 /* Counters of the last device run: [0] connections tested, [1] candidates, [2] ordered candidate
  * pairs swept by the scoring kernel (sum n_tris^2), [3] valid edges, [4] graph nodes,
  * [5] graph edges, [6] tracks, [7] nodes. */

@@ -59,6 +59,9 @@ EXPORTED_SYMBOLS = [
     "lt_patch_config_default", "lt_patch_extract", "lt_patch_get_geometry", "lt_patch_get_device_out", "lt_patch_get_out",
     "lt_patch_get_timers", "lt_patch_copy_yardstick", "lt_fn_patch_extract_host", "lt_fn_patch_geometry",
     "lt_fn_patch_host_error", "lt_fn_patch_ranges",
+    "lt_loc_config_default", "lt_loc_solve", "lt_loc_num", "lt_loc_get", "lt_loc_get_timers", "lt_fn_loc_host",
+    "lt_fn_loc_host_error", "lt_fn_loc_eval", "lt_fn_loc_qvec_from_R",
+    "lt_loc_score", "lt_loc_score_size", "lt_loc_score_get", "lt_loc_score_get_timers", "lt_fn_loc_score_host",
 ]
 
 
@@ -195,6 +198,20 @@ class LtRefineTerms(C.Structure):
 
 
 TEXEL_F16, TEXEL_F32 = 0, 1
+
+
+class LtLocConfig(C.Structure):
+    """lt_loc_config of include/limap_amd.h"""
+    _fields_ = [("cost_function", C.c_int32), ("weight_function", C.c_int32), ("loss", C.c_int32),
+                ("max_num_iterations", C.c_int32), ("loss_a", C.c_double), ("weight_line", C.c_double),
+                ("weight_point", C.c_double)]
+
+
+class LtLocScoreConfig(C.Structure):
+    """lt_loc_score_config of include/limap_amd.h"""
+    _fields_ = [("cost_function", C.c_int32), ("want_msac", C.c_int32), ("cheirality_min_depth", C.c_double),
+                ("cheirality_overlap_pixels", C.c_double), ("squared_thresholds", C.c_double * 2),
+                ("weights", C.c_double * 2)]
 
 
 class LtUndistCamera(C.Structure):
@@ -491,6 +508,27 @@ def load_library():
     L.lt_fn_patch_host_error.argtypes = []
     L.lt_fn_patch_host_error.restype = C.c_char_p
     L.lt_fn_patch_ranges.argtypes = [C.c_int64, dp, i64p, i32p, dp, C.c_int64, i32p, i32p, dp, dp, i32p]
+    lcp = C.POINTER(LtLocConfig)
+    loc_in = [C.c_int64, dp, dp, dp, i64p, dp, i64p, dp, i64p, dp, dp, lcp]
+    L.lt_loc_config_default.argtypes = [lcp]
+    L.lt_loc_config_default.restype = None
+    L.lt_loc_solve.argtypes = [vp] + loc_in
+    L.lt_loc_num.argtypes = [vp]
+    L.lt_loc_num.restype = C.c_int64
+    L.lt_loc_get.argtypes = [vp, dp, dp, dp, i32p, i32p, i32p]
+    L.lt_loc_get_timers.argtypes = [vp, dp]
+    L.lt_fn_loc_host.argtypes = loc_in + [C.c_int, dp, dp, dp, i32p, i32p, i32p]
+    L.lt_fn_loc_host_error.argtypes = []
+    L.lt_fn_loc_host_error.restype = C.c_char_p
+    L.lt_fn_loc_eval.argtypes = [dp, dp, dp, C.c_int64, dp, i64p, dp, C.c_int64, dp, dp, lcp, dp, dp, dp, dp]
+    L.lt_fn_loc_qvec_from_R.argtypes = [dp, dp]
+    lsp = C.POINTER(LtLocScoreConfig)
+    score_in = [dp, C.c_int64, dp, C.c_int64, i32p, dp, C.c_int64, dp, dp, C.c_int64, dp, dp, lsp]
+    L.lt_loc_score.argtypes = [vp] + score_in
+    L.lt_loc_score_size.argtypes = [vp, i64p, i64p]
+    L.lt_loc_score_get.argtypes = [vp, dp, dp, i32p]
+    L.lt_loc_score_get_timers.argtypes = [vp, dp]
+    L.lt_fn_loc_score_host.argtypes = score_in + [C.c_int, dp, dp, i32p]
     _lib = L
     return L
 

@@ -258,6 +258,20 @@ struct RefineState {  // line refinement (lt_refine.cpp): the result of the last
   DevBuf d_ext, d_vp_flag, d_vp3, d_sup_hm;  // per call with terms: the supports' extra tables
 };
 
+struct LocState {  // point-line pose refinement (lt_loc.cpp): the result of the last lt_loc_solve
+  double timers[4] = {0, 0, 0, 0};  // lt_loc_get_timers
+  std::vector<double> out;          // 10 doubles (one lt::LcOut) per problem
+  std::vector<int> n_res;           // residuals per problem
+  DevBuf d_tab, d_probs, d_k, d_out;
+  // pose scoring: the result of the last lt_loc_score
+  double score_timers[4] = {0, 0, 0, 0};  // lt_loc_score_get_timers
+  long long score_h = 0, score_n = 0;
+  bool score_msac = false;
+  std::vector<double> table, scores;      // score_h x score_n; score_h
+  std::vector<int> inliers;               // 2 per pose: points, lines
+  DevBuf d_stab, d_sq, d_st, d_table, d_scores, d_inl;
+};
+
 struct SfmState {  // visual neighbours (lt_sfm.cpp): the result of the last lt_sfm_neighbors
   double timers[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // lt_sfm_get_timers
   std::vector<long long> nb_off;                // per image its neighbours (image indices)
@@ -533,6 +547,7 @@ struct lt_ctx {
   lt_host::MatchState mt;
   lt_host::VpState vp;
   lt_host::RefineState rf;
+  lt_host::LocState lc;
   lt_host::SfmState sf;
   lt_host::UdState ud;
   lt_host::S2State s2;

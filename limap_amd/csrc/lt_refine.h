@@ -704,6 +704,8 @@ LT_HD void rf_lm_terms(G &grp, bool constant, int max_iter, double p[6], double 
   rf_lm_from(grp, F, constant, max_iter, p, cost1, iters, code_out);
 }
 
+LT_HD void rf_quat_from_matrix(const double m[3][3], double p[4]);
+
 // MinimalInfiniteLine3d(InfiniteLine3d(line)) (infinite_line.cc:67-71,180-223); the caller has checked length > 0
 LT_HD void rf_minimal(const double l6[6], double p[6]) {
   const d3 s = mk3(l6[0], l6[1], l6[2]);
@@ -740,6 +742,11 @@ LT_HD void rf_minimal(const double l6[6], double p[6]) {
   }
   // Eigen::Quaterniond(Q), Q = [c0 c1 c2] by columns: m(i, j) = column j, row i
   const double m[3][3] = {{c0.x, c1.x, c2.x}, {c0.y, c1.y, c2.y}, {c0.z, c1.z, c2.z}};
+  rf_quat_from_matrix(m, p);
+}
+
+// Eigen's Quaternion(Matrix3): (w, x, y, z) of the rotation matrix m (row, column)
+LT_HD void rf_quat_from_matrix(const double m[3][3], double p[4]) {
   double t = (m[0][0] + m[1][1]) + m[2][2];
   double q[4];  // x, y, z, w
   if (t > 0.0) {

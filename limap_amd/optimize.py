@@ -421,3 +421,11 @@ def line_refinement(cfg, tracks, imagecols, heatmap_dir=None, patch_dir=None, fe
         for m, n in enumerate(sel):
             out[n] = _copy_track(tracks[n], Line3d(r["segments"][m, :3], r["segments"][m, 3:]))
     return out
+
+
+# limap.optimize.hybrid_localization and the null-RANSAC path of limap.estimators.pl_estimate_absolute_pose: the
+# point-line pose refinement and the pose scoring
+from . import hybrid_localization as _loc  # noqa: E402
+from .hybrid_localization import *  # noqa: E402,F401,F403
+
+__all__ += _loc.__all__
