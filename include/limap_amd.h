@@ -835,6 +835,78 @@ int lt_fn_refine_eval_terms(int64_t K, const double *cam11, const double *line2d
                             const int32_t *hm_w, const void *const *hm_data, double *residuals, int32_t *failed,
                             double *cost, double g[4], double H[16]);
 
+/* ---- the feature-consistency term of limap.optimize.line_refinement (use_feature; refine.cc:363-543,
+ * pixel_cost_functions.h:198-400, linetrack.cc:353-454).  Samples are taken once per track on
+ * the host from its initial line (ComputeFConsistencySamples); every (sample, target image) is one block of 128
+ * residuals f_tgt[c](xy_tgt) - f_ref[c](xy_ref) under ScaledLoss(CauchyLoss(0.25), fconsis_multiplier /
+ * ((n_kept / 100.0) (n_targets / 5.0))), added after the track's geometric, VP and heatmap blocks, by sample, then by
+ * target.  use_ref_descriptor is not built.  The sample range is the terms' (sample_range_min / max); with use_heatmap
+ * the heatmaps and the features have one texel type.  A failed intersection follows the heatmap term's rule. */
+typedef struct lt_refine_feature {
+  int32_t use_feature;        /* 1 */
+  int32_t n_samples_feature;  /* 100 */
+  double fconsis_multiplier;  /* 1.0 */
+  int32_t channels;           /* 128, the only count built */
+  int32_t texel_type;         /* LT_TEXEL_F16 */
+} lt_refine_feature;
+void lt_refine_feature_default(lt_refine_feature *feat);
+/* The grid an image of a track is sampled on: h x w x 128 texels, row-major, channels interleaved, aligned to two
+ * texels; local_xy = R (xy - tvec) (R row-major), sampled bilinearly at (row = local y, col = local x) with rows and
+ * columns clamped.  A patch of limap_amd.features carries its R and tvec; a whole map is the identity.  on_device: data
+ * is a device address and is read in place. */
+typedef struct lt_refine_grid {
+  const void *data;
+  int32_t h, w;
+  double R[4];
+  double tvec[2];
+  int32_t on_device;
+  int32_t pad_;
+} lt_refine_grid;
+/* The scene's feature maps (the map form), kept in the context like the heatmaps: n images with distinct ids,
+ * h[i] x w[i] x 128 texels each; on_device != 0: data[i] are device addresses, kept and read in place (the caller keeps
+ * them alive), otherwise host pointers that are uploaded before the call returns.  The generation counts sets and
+ * clears like lt_refine_heatmaps_generation. */
+int lt_refine_set_feature_maps(lt_ctx *ctx, int n, const int32_t *img_ids, const int32_t *h, const int32_t *w,
+                               const void *const *data, int texel_type, int on_device);
+int lt_refine_clear_feature_maps(lt_ctx *ctx);
+int64_t lt_refine_feature_maps_generation(lt_ctx *ctx);
+/* lt_refine_arrays_terms with the feature term (any of the four terms may be the only one).  grids: one per (track,
+ * image of the track in ascending id), track after track, n_grids in all -- the patch form; NULL with n_grids 0: the
+ * map form, every image reads its map of the context.  Host grids are uploaded for the call, device grids are read in
+ * place.  Results through lt_refine_get; timer [3] is the device time of k_refine_lm_feat.
+ * LT_ERR_ARGUMENT besides lt_refine_arrays_terms' cases: channels other than 128, n_samples_feature outside [2, 4096],
+ * a grid count that is not the tracks', an empty or misaligned grid, a track of more than 64 images, an image without
+ * a map, maps of another texel type or size than the configuration's or the view's. */
+int lt_refine_arrays_feature(lt_ctx *ctx, int n_img, const int32_t *img_ids, const double *kvec4, const double *qvec4,
+                             const double *tvec3, int64_t n_tracks, const double *line6, const int64_t *off,
+                             const int32_t *img, const double *line2d4, const double *line3d6, const lt_refine_config *cfg,
+                             const lt_refine_terms *terms, const int32_t *vp_flag, const double *vp3,
+                             const int32_t *view_hw, const lt_refine_feature *feat, int64_t n_grids,
+                             const lt_refine_grid *grids);
+/* The host twin: lt_fn_refine_host_terms with the feature term; grids are host grids (a map: the identity transform).
+ * Errors through lt_fn_refine_host_error. */
+int lt_fn_refine_host_feature(int n_img, const int32_t *img_ids, const double *kvec4, const double *qvec4, const double *tvec3,
+                              int64_t n_tracks, const double *line6, const int64_t *off, const int32_t *img,
+                              const double *line2d4, const double *line3d6, const lt_refine_config *cfg,
+                              const lt_refine_terms *terms, const int32_t *vp_flag, const double *vp3, const int32_t *view_hw,
+                              int n_hm, const int32_t *hm_ids, const int32_t *hm_h, const int32_t *hm_w,
+                              const void *const *hm_data, const lt_refine_feature *feat, int64_t n_grids,
+                              const lt_refine_grid *grids, int n_threads, double *params6, double *seg6, double *cost2,
+                              int32_t *iters, int32_t *codes);
+/* For tests: one track (K supports in the caller's order) at params6 (NULL: the minimal parameters of line6), the
+ * geometric term as terms->use_geometric says, no VP or heatmap term.  The kept samples in order: *n_kept of them,
+ * sample_ref[i] the reference image id, sample_line[3 i ..] the sample line, sample_ntgt[i] its number of targets,
+ * targets the target image ids of all samples one after the other; the blocks in (sample, target) order: *n_blocks of
+ * them, residuals[128 b ..] and failed[b].  cap_samples / cap_blocks: what the outputs hold.  cost, g, H of all enabled
+ * terms (cost +inf where a block fails).  Any output may be NULL. */
+int lt_fn_refine_eval_feature(int n_img, const int32_t *img_ids, const double *kvec4, const double *qvec4, const double *tvec3,
+                              const double line6[6], int64_t K, const int32_t *img, const double *line2d4, double alpha,
+                              const lt_refine_terms *terms, const lt_refine_feature *feat, int64_t n_grids,
+                              const lt_refine_grid *grids, const double *params6, int64_t cap_samples, int64_t cap_blocks,
+                              int32_t *n_kept, int32_t *sample_ref, double *sample_line, int32_t *sample_ntgt,
+                              int32_t *targets, int32_t *n_blocks, double *residuals, int32_t *failed, double *cost,
+                              double g[4], double H[16]);
+
 /* ---- limap.pointsfm: the visual neighbours of every image and the robust ranges of the point cloud -- step [A] of
  * limap.runners.line_triangulation, `compute_metainfos` (pointsfm/functions.py:20-55) over SfmModel
  * (pointsfm/sfm_model.{h,cc}, colmap::mvs::Model).  DESIGN.md section 21 is the definition: shared points and the 75th

@@ -49,6 +49,9 @@ EXPORTED_SYMBOLS = [
     "lt_refine_terms_default", "lt_refine_set_heatmaps", "lt_refine_clear_heatmaps", "lt_refine_heatmaps_generation",
     "lt_refine_arrays_terms",
     "lt_fn_refine_host_terms", "lt_fn_refine_eval_terms",
+    "lt_refine_feature_default", "lt_refine_set_feature_maps", "lt_refine_clear_feature_maps",
+    "lt_refine_feature_maps_generation", "lt_refine_arrays_feature", "lt_fn_refine_host_feature",
+    "lt_fn_refine_eval_feature",
     "lt_sfm_neighbors", "lt_sfm_get", "lt_sfm_get_pairs", "lt_sfm_get_timers", "lt_fn_sfm_neighbors_host",
     "lt_fn_sfm_host_get", "lt_fn_sfm_host_error", "lt_fn_sfm_ranges",
     "lt_undist_warp", "lt_undist_points", "lt_undist_get_timers", "lt_undist_copy_yardstick", "lt_fn_undist_warp_host",
@@ -198,6 +201,18 @@ class LtRefineTerms(C.Structure):
 
 
 TEXEL_F16, TEXEL_F32 = 0, 1
+
+
+class LtRefineFeature(C.Structure):
+    """lt_refine_feature of include/limap_amd.h"""
+    _fields_ = [("use_feature", C.c_int32), ("n_samples_feature", C.c_int32), ("fconsis_multiplier", C.c_double),
+                ("channels", C.c_int32), ("texel_type", C.c_int32)]
+
+
+class LtRefineGrid(C.Structure):
+    """lt_refine_grid of include/limap_amd.h"""
+    _fields_ = [("data", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("R", C.c_double * 4), ("tvec", C.c_double * 2),
+                ("on_device", C.c_int32), ("pad_", C.c_int32)]
 
 
 class LtLocConfig(C.Structure):
@@ -459,6 +474,20 @@ def load_library():
                                           i32p, C.c_int, i32p, i32p, i32p, vpp, C.c_int, dp, dp, dp, i32p, i32p]
     L.lt_fn_refine_eval_terms.argtypes = [C.c_int64, dp, dp, dp, C.c_double, rtp, i32p, dp, i32p, i32p, vpp, dp, i32p, dp,
                                           dp, dp]
+    rfp, rgp = C.POINTER(LtRefineFeature), C.POINTER(LtRefineGrid)
+    L.lt_refine_feature_default.argtypes = [rfp]
+    L.lt_refine_feature_default.restype = None
+    L.lt_refine_set_feature_maps.argtypes = [vp, C.c_int, i32p, i32p, i32p, vpp, C.c_int, C.c_int]
+    L.lt_refine_clear_feature_maps.argtypes = [vp]
+    L.lt_refine_feature_maps_generation.argtypes = [vp]
+    L.lt_refine_feature_maps_generation.restype = C.c_int64
+    L.lt_refine_arrays_feature.argtypes = L.lt_refine_arrays_terms.argtypes + [rfp, C.c_int64, rgp]
+    L.lt_fn_refine_host_feature.argtypes = [C.c_int, i32p, dp, dp, dp, C.c_int64, dp, i64p, i32p, dp, dp, rcp, rtp, i32p, dp,
+                                            i32p, C.c_int, i32p, i32p, i32p, vpp, rfp, C.c_int64, rgp, C.c_int, dp, dp, dp,
+                                            i32p, i32p]
+    L.lt_fn_refine_eval_feature.argtypes = [C.c_int, i32p, dp, dp, dp, dp, C.c_int64, i32p, dp, C.c_double, rtp, rfp,
+                                            C.c_int64, rgp, dp, C.c_int64, C.c_int64, i32p, i32p, dp, i32p, i32p, i32p, dp,
+                                            i32p, dp, dp, dp]
     L.lt_sfm_neighbors.argtypes = [vp, C.c_int, fp, fp, C.c_int64, fp, i64p, i32p, C.c_int, C.c_int64, C.c_double, i64p, i64p]
     L.lt_sfm_get.argtypes = [vp, i64p, i32p]
     L.lt_sfm_get_pairs.argtypes = [vp, i32p, i32p, fp]

@@ -256,6 +256,15 @@ struct RefineState {  // line refinement (lt_refine.cpp): the result of the last
   std::vector<int> hm_ids, hm_h, hm_w;
   DevBuf d_hm_tex, d_hm_tab;
   DevBuf d_ext, d_vp_flag, d_vp3, d_sup_hm;  // per call with terms: the supports' extra tables
+  // the scene's feature maps (lt_refine_set_feature_maps), kept across calls like the heatmaps: ft_ptr[i] is the device
+  // address of image ft_ids[i] -- inside d_ft_tex where the call uploaded it, the caller's where it was on the device
+  int ft_type = 0;
+  long long ft_generation = 0;      // lt_refine_feature_maps_generation
+  std::vector<int> ft_ids, ft_h, ft_w;
+  std::vector<const void *> ft_ptr;
+  DevBuf d_ft_tex;
+  // per call with the feature term: the tables of lt::RfDevFeat and the call's host patches, packed
+  DevBuf d_f_tracks, d_f_imgs, d_f_views, d_f_smps, d_f_tgts, d_f_pairs, d_f_tex;
 };
 
 struct LocState {  // point-line pose refinement (lt_loc.cpp): the result of the last lt_loc_solve

@@ -12,6 +12,11 @@
 //                        without the heatmap term and with it for binary16 and float texels.  The geometric and the VP
 //                        term are switches of the launch, the same in every lane.  A lane loads the 4 (cost) or 8
 //                        (linearisation) texels of a sample together, before the first of them is used
+// and for a call with the feature-consistency term:
+//   k_refine_lm_feat     one wave64 per track, four tracks per workgroup: the supports' blocks on the first kRfTermWidth
+//                        lanes as above, then one block of 128 residuals per (sample, target) with two channels per
+//                        lane -- a texel's channels are one 256-byte (binary16) or 512-byte (float) load of the wave --
+//                        its 15 sums reduced by the xor tree over the wave before the loss' derivative scales them
 // All stores are ordinary vector stores of the lanes.
 
 #include "lt_refine.h"
@@ -166,6 +171,138 @@ __global__ void __launch_bounds__(kRfBlock) k_refine_lm_terms(RfDev dev, RfDevTe
   }
 }
 
+// the sum over the wave's 64 lanes by the xor tree 32, 16, .. 1, the same bits in every lane
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int m = kRfFeatLanes / 2; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, kRfFeatLanes);
+  return v;
+}
+__device__ __forceinline__ double wave_get(double v, int src) { return __shfl(v, src, kRfFeatLanes); }
+__device__ __forceinline__ Rf4 wave_get(const Rf4 &a, int src) {
+  return Rf4{wave_get(a.v, src), {wave_get(a.d[0], src), wave_get(a.d[1], src), wave_get(a.d[2], src), wave_get(a.d[3], src)}};
+}
+
+// a wave64 on one track with the feature term.  The supports' blocks go to the first kRfTermWidth lanes exactly as in
+// DevGroupTerms -- the other lanes add zeros to the tree, so a track without feature blocks gets k_refine_lm_terms'
+// bits.  Lane i < n_img projects the line into image i once per evaluation; a block reads its two projections from
+// those lanes.  The geometry of a block is the same in every lane, the texels and the sums are the lane's two channels.
+template <bool HM, class Tx>
+struct DevGroupFeat {
+  const RfDev &dev;
+  const RfDevTerms &tr;
+  const RfDevFeat &ft;
+  const RfTrack &t;
+  const RfFTrack &f;
+  int lane;
+  __device__ __forceinline__ RfGrid<Tx> grid(long long s) const {
+    if (!HM) return RfGrid<Tx>{nullptr, 1, 1};
+    const RfHm hm = tr.hm[tr.sup_hm[s]];
+    return RfGrid<Tx>{static_cast<const Tx *>(tr.texels) + hm.off, hm.h, hm.w};
+  }
+  __device__ __forceinline__ double cost(const double p[6]) const {
+    double dm[6];
+    rf_plucker<double>(p, p + 4, dm);
+    double part = 0.0;
+    if (lane < kRfTermWidth)
+      for (int k = lane; k < t.n; k += kRfTermWidth) {
+        const long long s = t.s0 + k;
+        part = part + rf_cost_terms<HM, Tx>(rf_load(dev.sup, dev.stride, s), rf_load_ext(tr.ext, dev.stride, s), grid(s),
+                                            tr.cfg, dm, dev.alpha);
+      }
+    double total = wave_sum(part);
+    if (f.n_smp == 0) return 0.5 * total;
+    double d[3], m[3], mine[3] = {0.0, 0.0, 0.0};
+    rf_plucker_c<double>(p, p + 4, d, m);
+    const RfFImg *imgs = ft.imgs + f.img0;
+    if (lane < f.n_img) rf_w2p<double>(ft.views[imgs[lane].cam], d, m, mine);
+    bool ok = true;
+    for (int si = 0; si < f.n_smp; ++si) {
+      const RfFSample s = ft.smps[f.smp0 + si];
+      const RfFImg gr = imgs[s.ref];
+      const double cr[3] = {wave_get(mine[0], s.ref), wave_get(mine[1], s.ref), wave_get(mine[2], s.ref)};
+      double x, y, lx, ly, fref[2];
+      const bool ok_ref = rf_feat_ref_xy<double>(cr, s, gr, &x, &y, &lx, &ly);
+      rf_feat_value<Tx>(gr, ly, lx, lane, fref);
+      for (int ti = 0; ti < s.n_tgt; ++ti) {
+        const int tg = ft.tgts[s.tgt0 + ti];
+        const RfFImg gt = imgs[tg];
+        const double ct[3] = {wave_get(mine[0], tg), wave_get(mine[1], tg), wave_get(mine[2], tg)};
+        double tx, ty;
+        const bool ok_tgt = rf_feat_tgt_xy<double>(ct, ft.pairs + 9 * (f.pair0 + (long long)s.ref * f.n_img + tg), x, y, gt, &tx, &ty);
+        const double sq = wave_sum(rf_feat_sq_lane<Tx>(gt, tx, ty, fref, lane));
+        if (ok_ref && ok_tgt) total = total + rf_rho(s.weight, sq);
+        else ok = false;
+      }
+    }
+    return ok ? 0.5 * total : __builtin_inf();
+  }
+  __device__ __forceinline__ void linearise(const double p[6], double acc[kRfSums]) const {
+    Rf4 u[4], w[2], dm[6];
+    rf_seed(p, u, w);
+    rf_plucker<Rf4>(u, w, dm);
+    for (int c = 0; c < kRfSums; ++c) acc[c] = 0.0;
+    if (lane < kRfTermWidth)
+      for (int k = lane; k < t.n; k += kRfTermWidth) {
+        const long long s = t.s0 + k;
+        rf_accumulate_terms<HM, Tx>(rf_load(dev.sup, dev.stride, s), rf_load_ext(tr.ext, dev.stride, s), grid(s), tr.cfg, dm,
+                                    dev.alpha, acc);
+      }
+    for (int c = 0; c < kRfSums; ++c) acc[c] = wave_sum(acc[c]);
+    if (f.n_smp == 0) return;
+    Rf4 d[3], m[3], mine[3];
+    rf_plucker_c<Rf4>(u, w, d, m);
+    for (int c = 0; c < 3; ++c) mine[c] = rf_const(0.0);
+    const RfFImg *imgs = ft.imgs + f.img0;
+    if (lane < f.n_img) rf_w2p<Rf4>(ft.views[imgs[lane].cam], d, m, mine);
+    for (int si = 0; si < f.n_smp; ++si) {
+      const RfFSample s = ft.smps[f.smp0 + si];
+      const RfFImg gr = imgs[s.ref];
+      const Rf4 cr[3] = {wave_get(mine[0], s.ref), wave_get(mine[1], s.ref), wave_get(mine[2], s.ref)};
+      Rf4 x, y, lx, ly;
+      const bool ok_ref = rf_feat_ref_xy<Rf4>(cr, s, gr, &x, &y, &lx, &ly);
+      RfFRef ref;
+      rf_feat_ref_lane<Tx>(gr, lx, ly, lane, &ref);
+      for (int ti = 0; ti < s.n_tgt; ++ti) {
+        const int tg = ft.tgts[s.tgt0 + ti];
+        const RfFImg gt = imgs[tg];
+        const Rf4 ct[3] = {wave_get(mine[0], tg), wave_get(mine[1], tg), wave_get(mine[2], tg)};
+        Rf4 tx, ty;
+        const bool ok_tgt = rf_feat_tgt_xy<Rf4>(ct, ft.pairs + 9 * (f.pair0 + (long long)s.ref * f.n_img + tg), x, y, gt, &tx, &ty);
+        double blk[kRfFeatSums];
+        for (int c = 0; c < kRfFeatSums; ++c) blk[c] = 0.0;
+        rf_feat_block_lane<Tx>(gt, tx, ty, ref, lane, blk);
+        for (int c = 0; c < kRfFeatSums; ++c) blk[c] = wave_sum(blk[c]);
+        if (ok_ref && ok_tgt) {  // a failed block adds nothing
+          const double rho1 = rf_rho1(s.weight, blk[kRfSums]);
+          for (int c = 0; c < kRfSums; ++c) acc[c] = acc[c] + rho1 * blk[c];
+        }
+      }
+    }
+  }
+};
+
+// every lane of a wave holds its track's state; the waves of a workgroup do not talk to each other
+template <bool HM, class Tx>
+__global__ void __launch_bounds__(kRfFeatBlock) k_refine_lm_feat(RfDev dev, RfDevTerms tr, RfDevFeat ft, RfOut *__restrict__ out) {
+  const long long ti = (long long)blockIdx.x * kRfFeatTracks + threadIdx.x / kRfFeatLanes;
+  const int lane = threadIdx.x % kRfFeatLanes;
+  if (ti >= dev.n_tracks) return;  // a whole wave leaves together
+  const RfTrack t = dev.tracks[ti];
+  const RfFTrack f = ft.ftracks[ti];
+  double p[6], F0, F1;
+  int it, code;
+  for (int c = 0; c < 6; ++c) p[c] = out[ti].p[c];
+  DevGroupFeat<HM, Tx> grp{dev, tr, ft, t, f, lane};
+  rf_lm_terms(grp, t.constant != 0, dev.max_iter, p, &F0, &F1, &it, &code);
+  if (lane == 0) {
+    for (int c = 0; c < 6; ++c) out[ti].p[c] = p[c];
+    out[ti].cost0 = F0;
+    out[ti].cost1 = F1;
+    out[ti].iters = it;
+    out[ti].code = code;
+  }
+}
+
 __global__ void __launch_bounds__(kRfBlock) k_refine_cut(RfDev dev, RfOut *__restrict__ out) {
   const long long ti = ((long long)blockIdx.x * kRfBlock + threadIdx.x) / kRfWidth;
   const int lane = threadIdx.x % kRfWidth;
@@ -238,6 +375,19 @@ void launch_refine_lm_terms(hipStream_t st, const RfDev &dev, const RfDevTerms &
     hipLaunchKernelGGL((k_refine_lm_terms<true, float>), grid, block, 0, st, dev, terms, out);
   else
     hipLaunchKernelGGL((k_refine_lm_terms<true, unsigned short>), grid, block, 0, st, dev, terms, out);
+}
+
+void launch_refine_lm_feat(hipStream_t st, const RfDev &dev, const RfDevTerms &terms, const RfDevFeat &feat, bool texel_f32,
+                           RfOut *out) {
+  if (dev.n_tracks <= 0) return;
+  const dim3 grid(grid_of(dev.n_tracks, kRfFeatTracks)), block(kRfFeatBlock);
+  if (!terms.cfg.use_heatmap) {
+    if (texel_f32) hipLaunchKernelGGL((k_refine_lm_feat<false, float>), grid, block, 0, st, dev, terms, feat, out);
+    else hipLaunchKernelGGL((k_refine_lm_feat<false, unsigned short>), grid, block, 0, st, dev, terms, feat, out);
+  } else {
+    if (texel_f32) hipLaunchKernelGGL((k_refine_lm_feat<true, float>), grid, block, 0, st, dev, terms, feat, out);
+    else hipLaunchKernelGGL((k_refine_lm_feat<true, unsigned short>), grid, block, 0, st, dev, terms, feat, out);
+  }
 }
 
 void launch_refine_cut(hipStream_t st, const RfDev &dev, RfOut *out) {

@@ -136,6 +136,188 @@ int make_terms_plan(const Plan &pl, const int32_t *img, const lt_refine_terms &t
   return 0;
 }
 
+// ---- the feature-consistency term ----
+// the tables of lt::RfDevFeat for a call's tracks; kept[n]: the samples ComputeFConsistencySamples keeps for track n,
+// with or without targets (the n_samples of the weight)
+struct FeatPlan {
+  std::vector<RfFTrack> ftracks;
+  std::vector<RfFImg> imgs;
+  std::vector<RfFView> views;
+  std::vector<RfFSample> smps;
+  std::vector<int> tgts;
+  std::vector<double> pairs;
+  std::vector<int> kept;
+  int type = LT_TEXEL_F16;
+};
+
+// a kept sample as upstream's tuple: reference image, sample line, targets (images of the track, ascending)
+struct FSample {
+  int ref;
+  double k[3];
+  std::vector<int> tgts;
+};
+
+int check_feature(const lt_refine_terms *t, const lt_refine_feature *f, std::string &msg) {
+  if (!t) { msg = "null terms"; return 1; }
+  if (!f) { msg = "null feature configuration"; return 1; }
+  if (!f->use_feature) { msg = "use_feature is off"; return 1; }
+  if (f->channels != kRfChannels) { msg = "channels must be 128"; return 1; }
+  if (f->n_samples_feature < 2 || f->n_samples_feature > 4096) { msg = "n_samples_feature outside [2, 4096]"; return 1; }
+  if (!std::isfinite(f->fconsis_multiplier)) { msg = "fconsis_multiplier is not finite"; return 1; }
+  if (f->texel_type != LT_TEXEL_F16 && f->texel_type != LT_TEXEL_F32) { msg = "unknown texel type"; return 1; }
+  if (!std::isfinite(t->sample_range_min) || !std::isfinite(t->sample_range_max)) { msg = "sample_range is not finite"; return 1; }
+  if (t->use_heatmap && t->texel_type != f->texel_type) {
+    msg = "the heatmaps' texel type is not the features'";
+    return 1;
+  }
+  if (t->use_geometric || t->use_vp || t->use_heatmap) return check_terms(t, msg);
+  return 0;
+}
+
+// ComputeFConsistencySamples (linetrack.cc:353-454) for one track: the supports in the caller's list order, ids the
+// track's sorted image ids, cams their cameras
+int feat_samples(const double *line6, int K, const int32_t *img, const double *l2d4, const std::vector<int> &ids,
+                 const std::vector<Cam> &cams, double rmin, double rmax, int n, std::vector<FSample> &out, std::string &msg) {
+  out.clear();
+  const size_t I = ids.size();
+  auto idx_of = [&](int id) { return (size_t)(std::lower_bound(ids.begin(), ids.end(), id) - ids.begin()); };
+  const d3 start = mk3(line6[0], line6[1], line6[2]), end = mk3(line6[3], line6[4], line6[5]);
+  const double nm1 = (double)(n - 1);
+  const d3 interval = mk3((end.x - start.x) / nm1, (end.y - start.y) / nm1, (end.z - start.z) / nm1);
+  std::vector<d2> ps(I), pe(I), proj(I);  // track.line.projection(view)
+  for (size_t i = 0; i < I; ++i) {
+    ps[i] = cam_project(cams[i], start);
+    pe[i] = cam_project(cams[i], end);
+  }
+  std::vector<int> supports, good, timg;
+  for (int pi = 0; pi < n; ++pi) {
+    const double fi = (double)pi;
+    const d3 point = mk3(start.x + fi * interval.x, start.y + fi * interval.y, start.z + fi * interval.z);
+    for (size_t i = 0; i < I; ++i) proj[i] = cam_project(cams[i], point);
+    supports.clear();
+    for (int k = 0; k < K; ++k) {
+      const d2 s = mk2(l2d4[4 * k], l2d4[4 * k + 1]), e = mk2(l2d4[4 * k + 2], l2d4[4 * k + 3]);
+      const double length = sqrt(sqn(sub(s, e)));
+      const d2 dir = unit(sub(e, s));
+      const double pr = dot(sub(proj[idx_of(img[k])], s), dir) / length;
+      if (pr >= rmin && pr <= rmax) supports.push_back(k);
+    }
+    if (supports.size() < 2) continue;
+    good.clear();
+    for (int k : supports) {  // PERPENDICULAR_ONEWAY of the support against the track's projection (line_dists.h:98-119)
+      const size_t i = idx_of(img[k]);
+      const d2 v2 = unit(sub(pe[i], ps[i]));
+      const d2 ds = sub(mk2(l2d4[4 * k], l2d4[4 * k + 1]), ps[i]), de = sub(mk2(l2d4[4 * k + 2], l2d4[4 * k + 3]), ps[i]);
+      const double a = dot(ds, v2), b = dot(de, v2);
+      const double d12s = sqrt(dmax(sqn(ds) - a * a, 0.0)), d12e = sqrt(dmax(sqn(de) - b * b, 0.0));
+      if (dmax(d12s, d12e) < 0.3) good.push_back(k);
+    }
+    if (good.empty()) continue;
+    double max_length = -1.0;
+    int max_id = -1;
+    for (int k : good) {
+      const double length = sqrt(sqn(sub(mk2(l2d4[4 * k], l2d4[4 * k + 1]), mk2(l2d4[4 * k + 2], l2d4[4 * k + 3]))));
+      if (length > max_length) { max_length = length; max_id = k; }
+    }
+    if (max_id < 0) { msg = "a support has no length"; return 1; }  // (a NaN length: upstream indexes image_id_list[-1])
+    FSample smp;
+    smp.ref = (int)idx_of(img[max_id]);
+    const d2 rs = mk2(l2d4[4 * max_id], l2d4[4 * max_id + 1]), re = mk2(l2d4[4 * max_id + 2], l2d4[4 * max_id + 3]);
+    const d2 rdir = unit(sub(re, rs));
+    const d2 perp = mk2(rdir.y, -rdir.x);
+    if (!(std::fabs(sqrt(sqn(perp)) - 1.0) < kEps)) {  // THROW_CHECK_LT(|direc.norm() - 1|, EPS) (infinite_line.cc:10)
+      msg = "a 2D support of zero length has no sample line";
+      return 1;
+    }
+    const d2 p = proj[(size_t)smp.ref];
+    const d3 coor = unit(mk3(perp.y, (-1.0) * perp.x, ((-1.0) * perp.y) * p.x + perp.x * p.y));  // InfiniteLine2d(p, direc)
+    smp.k[0] = coor.x; smp.k[1] = coor.y; smp.k[2] = coor.z;
+    timg.clear();
+    for (int k : supports) timg.push_back((int)idx_of(img[k]));
+    std::sort(timg.begin(), timg.end());
+    timg.erase(std::unique(timg.begin(), timg.end()), timg.end());
+    for (int i : timg)
+      if (i != smp.ref) smp.tgts.push_back(i);
+    out.push_back(std::move(smp));
+  }
+  return 0;
+}
+
+// the term's tables for the plan's tracks.  grids: one per (track, sorted image) in track order; all: where given, the
+// kept samples of every track (lt_fn_refine_eval_feature)
+int make_feat_plan(const Plan &pl, const std::unordered_map<int, int> &id2idx, int n_cams, const double *k4, const double *q4,
+                   const double *t3, const int64_t *off, const int32_t *img, const double *l2d4, const lt_refine_terms &t,
+                   const lt_refine_feature &f, int64_t n_grids, const lt_refine_grid *grids, bool device, FeatPlan &fp,
+                   std::string &msg, std::vector<std::vector<FSample>> *all = nullptr) {
+  const size_t T = pl.tracks.size();
+  if (n_grids < 0 || (n_grids > 0 && !grids)) { msg = "bad grid arrays"; return 1; }
+  fp.type = f.texel_type;
+  fp.views.resize((size_t)std::max(n_cams, 1));
+  for (int c = 0; c < n_cams; ++c) rf_fview_prep(k4 + 4 * (size_t)c, q4 + 4 * (size_t)c, t3 + 3 * (size_t)c, &fp.views[(size_t)c]);
+  fp.ftracks.resize(T);
+  fp.kept.assign(T, 0);
+  if (all) all->assign(T, {});
+  const size_t align = f.texel_type == LT_TEXEL_F32 ? 8 : 4;
+  std::vector<int> ids;
+  std::vector<Cam> cams;
+  std::vector<FSample> smps;
+  int64_t g = 0;
+  for (size_t n = 0; n < T; ++n) {
+    const long long a = off[n];
+    const int K = (int)(off[n + 1] - a);
+    ids.assign(img + a, img + a + K);
+    std::sort(ids.begin(), ids.end());
+    ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+    const int I = (int)ids.size();
+    if (I > kRfFeatMaxImages) {
+      msg = "track " + std::to_string(n) + " has more than " + std::to_string(kRfFeatMaxImages) + " images (not built)";
+      return 1;
+    }
+    if (g + I > n_grids) { msg = "fewer grids than images of the tracks"; return 1; }
+    RfFTrack ft{(long long)fp.imgs.size(), (long long)fp.smps.size(), (long long)(fp.pairs.size() / 9), I, 0};
+    cams.resize((size_t)I);
+    for (int i = 0; i < I; ++i, ++g) {
+      const lt_refine_grid &gr = grids[g];
+      const std::string who = "the grid of track " + std::to_string(n) + ", image " + std::to_string(ids[(size_t)i]);
+      if (!gr.data || gr.h < 1 || gr.w < 1) { msg = who + " is empty"; return 1; }
+      if (gr.on_device && !device) { msg = who + " is on the device (host path)"; return 1; }
+      if (reinterpret_cast<uintptr_t>(gr.data) % align) { msg = who + " is not aligned to two texels"; return 1; }
+      if (!all_finite(gr.R, 4) || !all_finite(gr.tvec, 2)) { msg = who + " has a non-finite transform"; return 1; }
+      const int cam = id2idx.at(ids[(size_t)i]);  // make_plan has checked the ids
+      fp.imgs.push_back(RfFImg{gr.data, gr.h, gr.w, {gr.R[0], gr.R[1], gr.R[2], gr.R[3]}, {gr.tvec[0], gr.tvec[1]}, cam, 0});
+      cam_build(k4 + 4 * (size_t)cam, q4 + 4 * (size_t)cam, t3 + 3 * (size_t)cam, &cams[(size_t)i]);
+    }
+    if (feat_samples(pl.line6.data() + 6 * n, K, img + a, l2d4 + 4 * a, ids, cams, t.sample_range_min, t.sample_range_max,
+                     f.n_samples_feature, smps, msg)) {
+      msg = "track " + std::to_string(n) + ": " + msg;
+      return 1;
+    }
+    fp.kept[n] = (int)smps.size();
+    for (const FSample &s : smps) {
+      if (s.tgts.empty()) continue;  // contributes nothing
+      RfFSample r;
+      r.k[0] = s.k[0]; r.k[1] = s.k[1]; r.k[2] = s.k[2];
+      r.weight = f.fconsis_multiplier / ((double)((double)smps.size() / 100.0) * (double)((double)s.tgts.size() / 5.0));  // refine.cc:394-396
+      r.tgt0 = (long long)fp.tgts.size();
+      r.ref = s.ref;
+      r.n_tgt = (int)s.tgts.size();
+      fp.tgts.insert(fp.tgts.end(), s.tgts.begin(), s.tgts.end());
+      fp.smps.push_back(r);
+      ++ft.n_smp;
+    }
+    fp.pairs.resize(fp.pairs.size() + 9 * (size_t)I * (size_t)I, 0.0);
+    for (int r = 0; r < I; ++r)
+      for (int c = 0; c < I; ++c)
+        if (r != c)
+          rf_fundamental(fp.views[(size_t)fp.imgs[(size_t)ft.img0 + (size_t)r].cam], fp.views[(size_t)fp.imgs[(size_t)ft.img0 + (size_t)c].cam],
+                         fp.pairs.data() + 9 * ((size_t)ft.pair0 + (size_t)r * (size_t)I + (size_t)c));
+    fp.ftracks[n] = ft;
+    if (all) (*all)[n] = smps;
+  }
+  if (g != n_grids) { msg = "more grids than images of the tracks"; return 1; }
+  return 0;
+}
+
 int check_config(const lt_refine_config *cfg, std::string &msg) {
   if (!cfg) { msg = "null configuration"; return 1; }
   if (!(cfg->geometric_alpha >= 0.0) || !(cfg->geometric_alpha <= 700.0)) { msg = "geometric_alpha outside [0, 700]"; return 1; }
@@ -314,6 +496,126 @@ void with_host_group(const double *tab, const double *ext, long long stride, con
   }
 }
 
+// the host twin of a wave of k_refine_lm_feat: the lanes are a loop, the tree is rf_tree64_host
+template <bool HM, class Tx>
+struct HostGroupFeat {
+  HostGroupTerms<HM, Tx> sup;  // the supports' blocks: lanes 0 .. kRfTermWidth - 1
+  const FeatPlan &fp;
+  const RfFTrack &f;
+  const RfFImg *imgs() const { return fp.imgs.data() + f.img0; }
+  const double *pair(int ref, int tg) const { return fp.pairs.data() + 9 * ((size_t)f.pair0 + (size_t)ref * (size_t)f.n_img + (size_t)tg); }
+  double support_cost(const double p[6]) const {
+    double dm[6];
+    rf_plucker<double>(p, p + 4, dm);
+    double part[kRfFeatLanes][1];
+    for (int l = 0; l < kRfFeatLanes; ++l) {
+      double s = 0.0;
+      if (l < kRfTermWidth)
+        for (int k = l; k < sup.t.n; k += kRfTermWidth)
+          s = s + rf_cost_terms<HM, Tx>(rf_load(sup.tab, sup.stride, sup.t.s0 + k), rf_load_ext(sup.ext, sup.stride, sup.t.s0 + k),
+                                        sup.grid(sup.t.s0 + k), sup.tp.cfg, dm, sup.alpha);
+      part[l][0] = s;
+    }
+    double out;
+    rf_tree64_host<1>(part, 1, &out);
+    return out;
+  }
+  double cost(const double p[6]) const {
+    double total = support_cost(p);
+    if (f.n_smp == 0) return 0.5 * total;
+    double d[3], m[3];
+    rf_plucker_c<double>(p, p + 4, d, m);
+    double c[kRfFeatMaxImages][3];
+    for (int i = 0; i < f.n_img; ++i) rf_w2p<double>(fp.views[(size_t)imgs()[i].cam], d, m, c[i]);
+    bool ok = true;
+    for (int si = 0; si < f.n_smp; ++si) {
+      const RfFSample &s = fp.smps[(size_t)f.smp0 + (size_t)si];
+      const RfFImg &gr = imgs()[s.ref];
+      double x, y, lx, ly, fref[kRfFeatLanes][2];
+      const bool ok_ref = rf_feat_ref_xy<double>(c[s.ref], s, gr, &x, &y, &lx, &ly);
+      for (int l = 0; l < kRfFeatLanes; ++l) rf_feat_value<Tx>(gr, ly, lx, l, fref[l]);
+      for (int ti = 0; ti < s.n_tgt; ++ti) {
+        const int tg = fp.tgts[(size_t)s.tgt0 + (size_t)ti];
+        const RfFImg &gt = imgs()[tg];
+        double tx, ty, part[kRfFeatLanes][1], sq;
+        const bool ok_tgt = rf_feat_tgt_xy<double>(c[tg], pair(s.ref, tg), x, y, gt, &tx, &ty);
+        for (int l = 0; l < kRfFeatLanes; ++l) part[l][0] = rf_feat_sq_lane<Tx>(gt, tx, ty, fref[l], l);
+        rf_tree64_host<1>(part, 1, &sq);
+        if (ok_ref && ok_tgt) total = total + rf_rho(s.weight, sq);
+        else ok = false;
+      }
+    }
+    return ok ? 0.5 * total : __builtin_inf();
+  }
+  // res: 128 residuals per block, failed: one flag per block, in block order (tests)
+  bool linearise_res(const double p[6], double acc[kRfSums], double *res, int32_t *failed) const {
+    Rf4 u[4], w[2], dm[6];
+    rf_seed(p, u, w);
+    rf_plucker<Rf4>(u, w, dm);
+    {
+      double part[kRfFeatLanes][kRfSums];
+      for (int l = 0; l < kRfFeatLanes; ++l) {
+        for (int c = 0; c < kRfSums; ++c) part[l][c] = 0.0;
+        if (l < kRfTermWidth)
+          for (int k = l; k < sup.t.n; k += kRfTermWidth)
+            rf_accumulate_terms<HM, Tx>(rf_load(sup.tab, sup.stride, sup.t.s0 + k), rf_load_ext(sup.ext, sup.stride, sup.t.s0 + k),
+                                        sup.grid(sup.t.s0 + k), sup.tp.cfg, dm, sup.alpha, part[l]);
+      }
+      rf_tree64_host<kRfSums>(part, kRfSums, acc);
+    }
+    if (f.n_smp == 0) return true;
+    Rf4 d[3], m[3];
+    rf_plucker_c<Rf4>(u, w, d, m);
+    Rf4 c[kRfFeatMaxImages][3];
+    for (int i = 0; i < f.n_img; ++i) rf_w2p<Rf4>(fp.views[(size_t)imgs()[i].cam], d, m, c[i]);
+    bool ok = true;
+    size_t b = 0;
+    for (int si = 0; si < f.n_smp; ++si) {
+      const RfFSample &s = fp.smps[(size_t)f.smp0 + (size_t)si];
+      const RfFImg &gr = imgs()[s.ref];
+      Rf4 x, y, lx, ly;
+      const bool ok_ref = rf_feat_ref_xy<Rf4>(c[s.ref], s, gr, &x, &y, &lx, &ly);
+      RfFRef ref[kRfFeatLanes];
+      for (int l = 0; l < kRfFeatLanes; ++l) rf_feat_ref_lane<Tx>(gr, lx, ly, l, &ref[l]);
+      for (int ti = 0; ti < s.n_tgt; ++ti, ++b) {
+        const int tg = fp.tgts[(size_t)s.tgt0 + (size_t)ti];
+        const RfFImg &gt = imgs()[tg];
+        Rf4 tx, ty;
+        const bool ok_tgt = rf_feat_tgt_xy<Rf4>(c[tg], pair(s.ref, tg), x, y, gt, &tx, &ty);
+        double part[kRfFeatLanes][kRfFeatSums], blk[kRfFeatSums];
+        for (int l = 0; l < kRfFeatLanes; ++l) {
+          for (int o = 0; o < kRfFeatSums; ++o) part[l][o] = 0.0;
+          rf_feat_block_lane<Tx>(gt, tx, ty, ref[l], l, part[l], res ? res + kRfChannels * b + 2 * (size_t)l : nullptr);
+        }
+        rf_tree64_host<kRfFeatSums>(part, kRfFeatSums, blk);
+        if (failed) failed[b] = (ok_ref && ok_tgt) ? 0 : 1;
+        if (ok_ref && ok_tgt) {
+          const double rho1 = rf_rho1(s.weight, blk[kRfSums]);
+          for (int o = 0; o < kRfSums; ++o) acc[o] = acc[o] + rho1 * blk[o];
+        } else {
+          ok = false;
+        }
+      }
+    }
+    return ok;
+  }
+  void linearise(const double p[6], double acc[kRfSums]) const { linearise_res(p, acc, nullptr, nullptr); }
+};
+
+// f(HostGroupFeat) for the instantiation the call selects, like launch_refine_lm_feat
+template <class F>
+void with_host_group_feat(const double *tab, const double *ext, long long stride, const RfTrack &t, double alpha,
+                          const TermsPlan &tp, const HmSet *hs, const FeatPlan &fp, const RfFTrack &ft, F &&f) {
+  const bool f32 = fp.type == LT_TEXEL_F32;
+  if (!tp.cfg.use_heatmap) {
+    if (f32) { HostGroupFeat<false, float> g{{tab, ext, stride, t, alpha, tp, hs}, fp, ft}; f(g); }
+    else { HostGroupFeat<false, unsigned short> g{{tab, ext, stride, t, alpha, tp, hs}, fp, ft}; f(g); }
+  } else {
+    if (f32) { HostGroupFeat<true, float> g{{tab, ext, stride, t, alpha, tp, hs}, fp, ft}; f(g); }
+    else { HostGroupFeat<true, unsigned short> g{{tab, ext, stride, t, alpha, tp, hs}, fp, ft}; f(g); }
+  }
+}
+
 // k_refine_cut on the host: the same rank rule
 void cut_host(const RfTrack &t, const double *l3d, int num_outliers, RfOut &o) {
   d3 dir, m;
@@ -343,7 +645,7 @@ void fill_support(const double *k4, const double *q4, const double *t3, const do
 
 // tp: the terms of the call, or null (then hs is not read)
 void run_host(const Plan &pl, const double *k, const double *q, const double *t, const lt_refine_config &cfg, int n_threads,
-              std::vector<RfOut> &out, const TermsPlan *tp = nullptr, const HmSet *hs = nullptr) {
+              std::vector<RfOut> &out, const TermsPlan *tp = nullptr, const HmSet *hs = nullptr, const FeatPlan *fp = nullptr) {
   const long long S = pl.n_sup, T = (long long)pl.tracks.size();
   const long long stride = std::max<long long>(S, 1);
   std::vector<double> tab((size_t)kRfFields * (size_t)stride), ext(tp ? (size_t)kRfExtFields * (size_t)stride : 0);
@@ -357,12 +659,16 @@ void run_host(const Plan &pl, const double *k, const double *q, const double *t,
                   ext.data() + i, stride);
   }
   out.resize((size_t)T);
-#pragma omp parallel for num_threads(nt) schedule(dynamic, 16)
+#pragma omp parallel for num_threads(nt) schedule(dynamic, fp ? 1 : 16)
   for (long long n = 0; n < T; ++n) {
     RfOut &o = out[(size_t)n];
     const RfTrack &tr = pl.tracks[(size_t)n];
     rf_minimal(pl.line6.data() + 6 * n, o.p);
-    if (tp) {
+    if (fp) {
+      with_host_group_feat(tab.data(), ext.data(), stride, tr, cfg.geometric_alpha, *tp, hs, *fp, fp->ftracks[(size_t)n], [&](auto &grp) {
+        rf_lm_terms(grp, tr.constant != 0, cfg.max_num_iterations, o.p, &o.cost0, &o.cost1, &o.iters, &o.code);
+      });
+    } else if (tp) {
       with_host_group(tab.data(), ext.data(), stride, tr, cfg.geometric_alpha, *tp, hs, [&](auto &grp) {
         rf_lm_terms(grp, tr.constant != 0, cfg.max_num_iterations, o.p, &o.cost0, &o.cost1, &o.iters, &o.code);
       });
@@ -384,10 +690,11 @@ void copy_out(const RfOut *o, long long T, double *params6, double *seg6, double
   }
 }
 
+#ifndef LT_REFINE_HOST_ONLY  // (tools/refine_feature_host_asan.cpp compiles the host twins alone: no context, no HIP runtime)
 // upload of the plan, the three kernels, download into ctx->rf.out; d_k / d_q / d_t: the cameras on the device
 // tp: the terms of the call, or null; with them k_refine_prep_terms runs too and k_refine_lm_terms replaces k_refine_lm
 int run_device(lt_ctx *ctx, const Plan &pl, const double *d_k, const double *d_q, const double *d_t,
-               const lt_refine_config &cfg, double t0, const TermsPlan *tp = nullptr) {
+               const lt_refine_config &cfg, double t0, const TermsPlan *tp = nullptr, const FeatPlan *fp = nullptr) {
   const long long S = pl.n_sup, T = (long long)pl.tracks.size();
   static_assert(sizeof(RfOut) == 15 * sizeof(double), "RfOut is 15 doubles");
   ctx->rf.out.assign(15 * (size_t)T, 0.0);
@@ -409,6 +716,14 @@ int run_device(lt_ctx *ctx, const Plan &pl, const double *d_k, const double *d_q
     if (int rc = upload_vec(ctx, ctx->rf.d_vp3, tp->vp3)) return rc;
     if (int rc = upload_vec(ctx, ctx->rf.d_sup_hm, tp->sup_hm)) return rc;
     ENSURE(ctx, ctx->rf.d_ext, 8 * (size_t)kRfExtFields * (size_t)stride);
+  }
+  if (fp) {  // (the grids already hold device addresses: upload_grids)
+    if (int rc = upload_vec(ctx, ctx->rf.d_f_tracks, fp->ftracks)) return rc;
+    if (int rc = upload_vec(ctx, ctx->rf.d_f_imgs, fp->imgs)) return rc;
+    if (int rc = upload_vec(ctx, ctx->rf.d_f_views, fp->views)) return rc;
+    if (int rc = upload_vec(ctx, ctx->rf.d_f_smps, fp->smps)) return rc;
+    if (int rc = upload_vec(ctx, ctx->rf.d_f_tgts, fp->tgts)) return rc;
+    if (int rc = upload_vec(ctx, ctx->rf.d_f_pairs, fp->pairs)) return rc;
   }
   if (int rc = stream_sync(ctx)) return rc;
   const double t1 = now_ms();
@@ -432,7 +747,13 @@ int run_device(lt_ctx *ctx, const Plan &pl, const double *d_k, const double *d_q
     launch_refine_prep_terms(st, d_k, d_q, ctx->rf.d_cam.as<int>(), ctx->rf.d_vp_flag.as<int>(), ctx->rf.d_vp3.as<double>(), S,
                              ctx->rf.d_ext.as<double>(), stride);
   if (int rc = ev.record(ctx, 0)) return rc;
-  if (tp) {
+  if (fp) {
+    const RfDevTerms terms{ctx->rf.d_ext.as<double>(), ctx->rf.d_sup_hm.as<int>(), ctx->rf.d_hm_tab.as<RfHm>(),
+                           ctx->rf.d_hm_tex.p, tp->cfg};
+    const RfDevFeat feat{ctx->rf.d_f_tracks.as<RfFTrack>(), ctx->rf.d_f_imgs.as<RfFImg>(), ctx->rf.d_f_views.as<RfFView>(),
+                         ctx->rf.d_f_smps.as<RfFSample>(), ctx->rf.d_f_tgts.as<int>(), ctx->rf.d_f_pairs.as<double>()};
+    launch_refine_lm_feat(st, dev, terms, feat, fp->type == LT_TEXEL_F32, d_out);
+  } else if (tp) {
     const RfDevTerms terms{ctx->rf.d_ext.as<double>(), ctx->rf.d_sup_hm.as<int>(), ctx->rf.d_hm_tab.as<RfHm>(),
                            ctx->rf.d_hm_tex.p, tp->cfg};
     launch_refine_lm_terms(st, dev, terms, ctx->rf.hm_type == LT_TEXEL_F32, d_out);
@@ -464,9 +785,11 @@ int upload_cameras(lt_ctx *ctx, int n_img, const double *kvec4, const double *qv
   }
   return LT_OK;
 }
+#endif  // LT_REFINE_HOST_ONLY
 
 }  // namespace
 
+#ifndef LT_REFINE_HOST_ONLY
 namespace lt_impl {
 
 // lt_refine_tracks (lt_tracks.cpp): the cameras of the context, resident since lt_init
@@ -485,6 +808,7 @@ int refine_with_ctx_cams(lt_ctx *ctx, int64_t T, const double *line6, const int6
 }
 
 }  // namespace lt_impl
+#endif  // LT_REFINE_HOST_ONLY
 
 extern "C" {
 
@@ -499,6 +823,7 @@ void lt_refine_config_default(lt_refine_config *cfg) {
   cfg->pad_ = 0;
 }
 
+#ifndef LT_REFINE_HOST_ONLY
 int lt_refine_arrays(lt_ctx *ctx, int n_img, const int32_t *img_ids, const double *kvec4, const double *qvec4,
                      const double *tvec3, int64_t n_tracks, const double *line6, const int64_t *off, const int32_t *img,
                      const double *line2d4, const double *line3d6, const lt_refine_config *cfg) {
@@ -515,6 +840,7 @@ int lt_refine_arrays(lt_ctx *ctx, int n_img, const int32_t *img_ids, const doubl
   if (int rc = upload_cameras(ctx, n_img, kvec4, qvec4, tvec3)) return rc;
   return run_device(ctx, pl, ctx->rf.d_k.as<double>(), ctx->rf.d_q.as<double>(), ctx->rf.d_t.as<double>(), *cfg, t0);
 }
+#endif  // LT_REFINE_HOST_ONLY
 
 void lt_refine_terms_default(lt_refine_terms *t) {
   if (!t) return;
@@ -530,6 +856,7 @@ void lt_refine_terms_default(lt_refine_terms *t) {
   t->pad_ = 0;
 }
 
+#ifndef LT_REFINE_HOST_ONLY
 int lt_refine_set_heatmaps(lt_ctx *ctx, int n, const int32_t *img_ids, const int32_t *h, const int32_t *w,
                            const void *const *data, int texel_type) {
   if (!ctx) return LT_ERR_ARGUMENT;
@@ -596,6 +923,126 @@ int lt_refine_arrays_terms(lt_ctx *ctx, int n_img, const int32_t *img_ids, const
   return run_device(ctx, pl, ctx->rf.d_k.as<double>(), ctx->rf.d_q.as<double>(), ctx->rf.d_t.as<double>(), *cfg, t0, &tp);
 }
 
+int lt_refine_set_feature_maps(lt_ctx *ctx, int n, const int32_t *img_ids, const int32_t *h, const int32_t *w,
+                               const void *const *data, int texel_type, int on_device) {
+  if (!ctx) return LT_ERR_ARGUMENT;
+  HmSet hs;  // the same checks as a heatmap's: distinct ids, positive sizes, a known texel type
+  std::string msg;
+  if (check_heatmaps(n, img_ids, h, w, data, texel_type, hs, msg))
+    return fail(ctx, LT_ERR_ARGUMENT, "lt_refine_set_feature_maps: " + msg);
+  const size_t px = texel_type == LT_TEXEL_F32 ? 4 : 2;
+  for (int i = 0; i < n; ++i)
+    if (reinterpret_cast<uintptr_t>(data[i]) % (2 * px))
+      return fail(ctx, LT_ERR_ARGUMENT, "lt_refine_set_feature_maps: a map is not aligned to two texels");
+  lt_refine_clear_feature_maps(ctx);  // a failure below leaves the context without feature maps
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::vector<const void *> ptr((size_t)n);
+  if (on_device) {
+    for (int i = 0; i < n; ++i) ptr[(size_t)i] = data[i];
+  } else {
+    ENSURE(ctx, ctx->rf.d_ft_tex, std::max<size_t>(px * kRfChannels * (size_t)hs.off.back(), 1));
+    for (int i = 0; i < n; ++i) {
+      char *dst = static_cast<char *>(ctx->rf.d_ft_tex.p) + px * kRfChannels * (size_t)hs.off[(size_t)i];
+      HIPCHK(ctx, hipMemcpyAsync(dst, data[i], px * kRfChannels * (size_t)h[i] * (size_t)w[i], hipMemcpyHostToDevice, ctx->stream));
+      ptr[(size_t)i] = dst;
+    }
+    if (int rc = stream_sync(ctx)) return rc;  // the caller's maps may go after the call
+  }
+  ctx->rf.ft_type = texel_type;
+  ctx->rf.ft_ids.assign(img_ids, img_ids + n);
+  ctx->rf.ft_h = hs.h;
+  ctx->rf.ft_w = hs.w;
+  ctx->rf.ft_ptr = ptr;
+  return LT_OK;
+}
+
+int lt_refine_clear_feature_maps(lt_ctx *ctx) {
+  if (!ctx) return LT_ERR_ARGUMENT;
+  ++ctx->rf.ft_generation;
+  ctx->rf.ft_ids.clear();
+  ctx->rf.ft_h.clear();
+  ctx->rf.ft_w.clear();
+  ctx->rf.ft_ptr.clear();
+  return LT_OK;
+}
+
+int64_t lt_refine_feature_maps_generation(lt_ctx *ctx) { return ctx ? (int64_t)ctx->rf.ft_generation : 0; }
+
+int lt_refine_arrays_feature(lt_ctx *ctx, int n_img, const int32_t *img_ids, const double *kvec4, const double *qvec4,
+                             const double *tvec3, int64_t n_tracks, const double *line6, const int64_t *off,
+                             const int32_t *img, const double *line2d4, const double *line3d6, const lt_refine_config *cfg,
+                             const lt_refine_terms *terms, const int32_t *vp_flag, const double *vp3,
+                             const int32_t *view_hw, const lt_refine_feature *feat, int64_t n_grids,
+                             const lt_refine_grid *grids) {
+  if (!ctx) return LT_ERR_ARGUMENT;
+  const std::string who = "lt_refine_arrays_feature";
+  const double t0 = now_ms();
+  std::string msg;
+  if (check_feature(terms, feat, msg)) return fail(ctx, LT_ERR_ARGUMENT, who + ": " + msg);
+  std::unordered_map<int, int> id2idx;
+  Plan pl;
+  TermsPlan tp;
+  FeatPlan fp;
+  HmSet hs;  // the context's heatmaps as the checks read them
+  hs.type = ctx->rf.hm_type;
+  hs.h = ctx->rf.hm_h;
+  hs.w = ctx->rf.hm_w;
+  for (size_t i = 0; i < ctx->rf.hm_ids.size(); ++i) hs.slot.emplace(ctx->rf.hm_ids[i], (int)i);
+  if (check_config(cfg, msg) || check_cams(n_img, img_ids, kvec4, qvec4, tvec3, id2idx, msg) ||
+      make_plan(id2idx, n_tracks, line6, off, img, line2d4, line3d6, *cfg, pl, msg) ||
+      make_terms_plan(pl, img, *terms, vp_flag, vp3, view_hw, &hs, tp, msg))
+    return fail(ctx, LT_ERR_ARGUMENT, who + ": " + msg);
+  std::vector<lt_refine_grid> maps;  // the map form: the context's maps with the identity transform
+  if (!grids) {
+    if (n_grids != 0) return fail(ctx, LT_ERR_ARGUMENT, who + ": n_grids without grids");
+    if (ctx->rf.ft_type != feat->texel_type && !ctx->rf.ft_ids.empty())
+      return fail(ctx, LT_ERR_ARGUMENT, who + ": the feature maps' texel type is not the configuration's");
+    std::unordered_map<int, size_t> slot;
+    for (size_t i = 0; i < ctx->rf.ft_ids.size(); ++i) slot.emplace(ctx->rf.ft_ids[i], i);
+    std::vector<int> ids;
+    for (int64_t n = 0; n < n_tracks; ++n) {
+      ids.assign(img + off[n], img + off[n + 1]);
+      std::sort(ids.begin(), ids.end());
+      ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+      for (int id : ids) {
+        auto it = slot.find(id);
+        if (it == slot.end())
+          return fail(ctx, LT_ERR_ARGUMENT, who + ": image " + std::to_string(id) + " supports a track and has no feature map");
+        const size_t sl = it->second;
+        const int cam = id2idx.at(id);
+        if (view_hw && view_hw[2 * cam] > 0 && view_hw[2 * cam + 1] > 0 &&
+            (view_hw[2 * cam] != ctx->rf.ft_h[sl] || view_hw[2 * cam + 1] != ctx->rf.ft_w[sl]))
+          return fail(ctx, LT_ERR_ARGUMENT, who + ": the feature map of image " + std::to_string(id) + " has not the size of its view");
+        maps.push_back(lt_refine_grid{ctx->rf.ft_ptr[sl], ctx->rf.ft_h[sl], ctx->rf.ft_w[sl], {1.0, 0.0, 0.0, 1.0}, {0.0, 0.0}, 1, 0});
+      }
+    }
+    grids = maps.data();
+    n_grids = (int64_t)maps.size();
+  }
+  if (make_feat_plan(pl, id2idx, n_img, kvec4, qvec4, tvec3, off, img, line2d4, *terms, *feat, n_grids, grids, true, fp, msg))
+    return fail(ctx, LT_ERR_ARGUMENT, who + ": " + msg);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  // the call's host patches into one packed buffer, every patch at a multiple of 256 bytes; device patches stay in place
+  const size_t px = feat->texel_type == LT_TEXEL_F32 ? 4 : 2;
+  size_t total = 0;
+  std::vector<size_t> at((size_t)n_grids, 0);
+  for (int64_t g = 0; g < n_grids; ++g)
+    if (!grids[g].on_device) {
+      at[(size_t)g] = total;
+      total += (px * kRfChannels * (size_t)grids[g].h * (size_t)grids[g].w + 255) / 256 * 256;
+    }
+  ENSURE(ctx, ctx->rf.d_f_tex, std::max<size_t>(total, 1));
+  for (int64_t g = 0; g < n_grids; ++g)
+    if (!grids[g].on_device) {
+      char *dst = static_cast<char *>(ctx->rf.d_f_tex.p) + at[(size_t)g];
+      HIPCHK(ctx, hipMemcpyAsync(dst, grids[g].data, px * kRfChannels * (size_t)grids[g].h * (size_t)grids[g].w,
+                                 hipMemcpyHostToDevice, ctx->stream));
+      fp.imgs[(size_t)g].tex = dst;
+    }
+  if (int rc = upload_cameras(ctx, n_img, kvec4, qvec4, tvec3)) return rc;
+  return run_device(ctx, pl, ctx->rf.d_k.as<double>(), ctx->rf.d_q.as<double>(), ctx->rf.d_t.as<double>(), *cfg, t0, &tp, &fp);
+}
+
 int64_t lt_refine_num(lt_ctx *ctx) { return ctx ? (int64_t)(ctx->rf.out.size() / 15) : 0; }
 
 int lt_refine_get(lt_ctx *ctx, double *params6, double *seg6, double *cost2, int32_t *iters, int32_t *codes) {
@@ -610,6 +1057,7 @@ int lt_refine_get_timers(lt_ctx *ctx, double out[4]) {
   for (int k = 0; k < 4; ++k) out[k] = ctx->rf.timers[k];
   return LT_OK;
 }
+#endif  // LT_REFINE_HOST_ONLY
 
 static thread_local std::string g_host_error;
 const char *lt_fn_refine_host_error(void) { return g_host_error.c_str(); }
@@ -663,6 +1111,121 @@ int lt_fn_refine_host_terms(int n_img, const int32_t *img_ids, const double *kve
   std::vector<RfOut> out;
   run_host(pl, kvec4, qvec4, tvec3, *cfg, n_threads, out, &tp, &hs);
   copy_out(out.data(), (long long)out.size(), params6, seg6, cost2, iters, codes);
+  return LT_OK;
+}
+
+void lt_refine_feature_default(lt_refine_feature *f) {
+  if (!f) return;
+  f->use_feature = 1;
+  f->n_samples_feature = 100;    // refinement_config.h:82-88
+  f->fconsis_multiplier = 1.0;
+  f->channels = kRfChannels;
+  f->texel_type = LT_TEXEL_F16;
+}
+
+int lt_fn_refine_host_feature(int n_img, const int32_t *img_ids, const double *kvec4, const double *qvec4, const double *tvec3,
+                              int64_t n_tracks, const double *line6, const int64_t *off, const int32_t *img,
+                              const double *line2d4, const double *line3d6, const lt_refine_config *cfg,
+                              const lt_refine_terms *terms, const int32_t *vp_flag, const double *vp3, const int32_t *view_hw,
+                              int n_hm, const int32_t *hm_ids, const int32_t *hm_h, const int32_t *hm_w,
+                              const void *const *hm_data, const lt_refine_feature *feat, int64_t n_grids,
+                              const lt_refine_grid *grids, int n_threads, double *params6, double *seg6, double *cost2,
+                              int32_t *iters, int32_t *codes) {
+  std::string msg;
+  std::unordered_map<int, int> id2idx;
+  Plan pl;
+  TermsPlan tp;
+  FeatPlan fp;
+  HmSet hs;
+  if (check_feature(terms, feat, msg) ||
+      (terms->use_heatmap && check_heatmaps(n_hm, hm_ids, hm_h, hm_w, hm_data, terms->texel_type, hs, msg)) ||
+      check_config(cfg, msg) || check_cams(n_img, img_ids, kvec4, qvec4, tvec3, id2idx, msg) ||
+      make_plan(id2idx, n_tracks, line6, off, img, line2d4, line3d6, *cfg, pl, msg) ||
+      make_terms_plan(pl, img, *terms, vp_flag, vp3, view_hw, &hs, tp, msg) ||
+      make_feat_plan(pl, id2idx, n_img, kvec4, qvec4, tvec3, off, img, line2d4, *terms, *feat, n_grids, grids, false, fp, msg)) {
+    g_host_error = "lt_fn_refine_host_feature: " + msg;
+    return LT_ERR_ARGUMENT;
+  }
+  g_host_error.clear();
+  std::vector<RfOut> out;
+  run_host(pl, kvec4, qvec4, tvec3, *cfg, n_threads, out, &tp, &hs, &fp);
+  copy_out(out.data(), (long long)out.size(), params6, seg6, cost2, iters, codes);
+  return LT_OK;
+}
+
+int lt_fn_refine_eval_feature(int n_img, const int32_t *img_ids, const double *kvec4, const double *qvec4, const double *tvec3,
+                              const double line6[6], int64_t K, const int32_t *img, const double *line2d4, double alpha,
+                              const lt_refine_terms *terms, const lt_refine_feature *feat, int64_t n_grids,
+                              const lt_refine_grid *grids, const double *params6, int64_t cap_samples, int64_t cap_blocks,
+                              int32_t *n_kept, int32_t *sample_ref, double *sample_line, int32_t *sample_ntgt,
+                              int32_t *targets, int32_t *n_blocks, double *residuals, int32_t *failed, double *cost,
+                              double g[4], double H[16]) {
+  std::string msg;
+  auto bad = [&](const std::string &m) {
+    g_host_error = "lt_fn_refine_eval_feature: " + m;
+    return LT_ERR_ARGUMENT;
+  };
+  if (K < 1 || K > (1 << 28) || !line6 || !(alpha >= 0.0) || !(alpha <= 700.0)) return bad("bad track arrays");
+  if (check_feature(terms, feat, msg)) return bad(msg);
+  if (terms->use_vp || terms->use_heatmap) return bad("the VP and heatmap terms are lt_fn_refine_eval_terms'");
+  lt_refine_config cfg;
+  lt_refine_config_default(&cfg);
+  cfg.geometric_alpha = alpha;
+  cfg.min_num_images = 0;
+  cfg.num_outliers_aggregator = 0;
+  const int64_t off[2] = {0, K};
+  const std::vector<double> l3d(6 * (size_t)K, 0.0);
+  std::unordered_map<int, int> id2idx;
+  Plan pl;
+  TermsPlan tp;
+  FeatPlan fp;
+  HmSet hs;
+  std::vector<std::vector<FSample>> all;
+  if (check_cams(n_img, img_ids, kvec4, qvec4, tvec3, id2idx, msg) ||
+      make_plan(id2idx, 1, line6, off, img, line2d4, l3d.data(), cfg, pl, msg) ||
+      make_terms_plan(pl, img, *terms, nullptr, nullptr, nullptr, &hs, tp, msg) ||
+      make_feat_plan(pl, id2idx, n_img, kvec4, qvec4, tvec3, off, img, line2d4, *terms, *feat, n_grids, grids, false, fp, msg, &all))
+    return bad(msg);
+  g_host_error.clear();
+  std::vector<int> ids(img, img + K);
+  std::sort(ids.begin(), ids.end());
+  ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+  const std::vector<FSample> &smps = all[0];
+  size_t nb = 0;
+  for (const FSample &s : smps) nb += s.tgts.size();
+  if ((int64_t)smps.size() > cap_samples || (int64_t)nb > cap_blocks) return bad("more samples or blocks than the outputs hold");
+  if (n_kept) *n_kept = (int32_t)smps.size();
+  if (n_blocks) *n_blocks = (int32_t)nb;
+  size_t ti = 0;
+  for (size_t i = 0; i < smps.size(); ++i) {
+    if (sample_ref) sample_ref[i] = ids[(size_t)smps[i].ref];
+    if (sample_line) std::copy(smps[i].k, smps[i].k + 3, sample_line + 3 * i);
+    if (sample_ntgt) sample_ntgt[i] = (int32_t)smps[i].tgts.size();
+    for (int tg : smps[i].tgts) {
+      if (targets) targets[ti] = ids[(size_t)tg];
+      ++ti;
+    }
+  }
+  double p[6];
+  if (params6) std::copy(params6, params6 + 6, p);
+  else rf_minimal(line6, p);
+  std::vector<double> tab((size_t)kRfFields * (size_t)K), ext((size_t)kRfExtFields * (size_t)K);
+  for (int64_t i = 0; i < K; ++i) {
+    const size_t cam = (size_t)pl.sup_cam[(size_t)i];
+    fill_support(kvec4 + 4 * cam, qvec4 + 4 * cam, tvec3 + 3 * cam, pl.l2d.data() + 4 * i, tab.data() + i, (long long)K);
+    rf_ext_prep(kvec4 + 4 * cam, qvec4 + 4 * cam, false, tp.vp3.data() + 3 * i, ext.data() + i, (long long)K);
+  }
+  with_host_group_feat(tab.data(), ext.data(), (long long)K, pl.tracks[0], alpha, tp, &hs, fp, fp.ftracks[0], [&](auto &grp) {
+    if (cost) *cost = grp.cost(p);
+    double acc[kRfSums];
+    grp.linearise_res(p, acc, residuals, failed);
+    if (H) {
+      int o = 0;
+      for (int i = 0; i < 4; ++i)
+        for (int j = i; j < 4; ++j, ++o) H[4 * i + j] = H[4 * j + i] = acc[o];
+    }
+    if (g) std::copy(acc + 10, acc + 14, g);
+  });
   return LT_OK;
 }
 

@@ -855,6 +855,305 @@ struct RfDevTerms {
   RfTermCfg cfg;
 };
 
+// ---- the feature-consistency term (limap.optimize.line_refinement with use_feature) ----
+// Restated in upstream's operation order down to the association of every sum (DESIGN §26 writes the order out; the
+// tests hold the residuals to a NumPy restatement bit for bit): paths relative to src/limap,
+//   optimize/line_refinement/pixel_cost_functions.h:198-400, refine.cc:363-543   FeatureConsisTgtFunctor and its blocks
+//   ceresbase/line_projection.h:136-213    GetEpipolarLineCoordinate, Ceres_GetIntersection2dFromInfiniteLine3d
+//   ceresbase/line_transforms.h:8-29, line_projection.h:14-80   MinimalPluckerToPlucker with Ceres' QuaternionToRotation
+//                                          (the product by the reciprocal of the squared norm), Line_WorldToPixel as the
+//                                          products R [m]x R^T - t (R d)^T + (R d) t^T and K [m']x K^T, every 3x3
+//                                          product summed left to right -- not the 3x6 matrix of rf_view_matrix
+//   features/featurepatch.h:53-123, featuremap.h:77-85   GlobalToLocal, Evaluate at (row = local y, col = local x)
+//   ceresbase/interpolation.h:526-579      the bilinear rule of rf_interp over 128 interleaved channels
+constexpr int kRfChannels = 128;
+constexpr int kRfFeatLanes = 64;                            // one wave64 per track; lane l owns channels 2 l and 2 l + 1
+constexpr int kRfFeatBlock = 256;                           // lanes per workgroup of k_refine_lm_feat
+constexpr int kRfFeatTracks = kRfFeatBlock / kRfFeatLanes;  // tracks per workgroup
+constexpr int kRfFeatSums = kRfSums + 1;                    // the sums of a block: kRfSums and the squared norm
+constexpr int kRfFeatMaxImages = kRfFeatLanes;              // lane i projects the line into image i of the track
+static_assert(kRfChannels == 2 * kRfFeatLanes, "two channels per lane");
+static_assert(kRfTermWidth <= kRfFeatLanes, "the supports go to the first kRfTermWidth lanes of the wave");
+
+// a camera as the term reads it: Ceres' rotation of CameraPose's normalised quaternion, row-major
+struct RfFView {
+  double R[9], t[3], k[4];
+};
+static_assert(sizeof(RfFView) == 128, "RfFView layout");
+// the grid of a (track, sorted image): h x w x 128 texels and local = R (xy - t); a map is the identity
+struct RfFImg {
+  const void *tex;
+  int h, w;
+  double R[4], t[2];
+  int cam, pad_;   // row of the views
+};
+static_assert(sizeof(RfFImg) == 72, "RfFImg layout");
+// a kept sample with at least one target: the sample line, the weight of its blocks, its targets [tgt0, tgt0 + n_tgt)
+struct RfFSample {
+  double k[3], weight;
+  long long tgt0;
+  int ref, n_tgt;  // ref and the targets: images of the track, 0 .. n_img - 1 in ascending id
+};
+static_assert(sizeof(RfFSample) == 48, "RfFSample layout");
+struct RfFTrack {
+  long long img0, smp0, pair0;  // first image, first sample, first fundamental matrix (pair0 + ref n_img + tgt)
+  int n_img, n_smp;
+};
+static_assert(sizeof(RfFTrack) == 32, "RfFTrack layout");
+// the term's tables on the device
+struct RfDevFeat {
+  const RfFTrack *ftracks;
+  const RfFImg *imgs;
+  const RfFView *views;
+  const RfFSample *smps;
+  const int *tgts;
+  const double *pairs;  // 9 doubles each, row-major
+};
+
+LT_HD Rf4 operator-(const Rf4 &a, double b) { return Rf4{a.v - b, {a.d[0], a.d[1], a.d[2], a.d[3]}}; }
+LT_HD double rf_inv(double a) { return 1.0 / a; }
+LT_HD Rf4 rf_inv(const Rf4 &a) {
+  const double q = 1.0 / a.v;
+  return Rf4{q, {-(q * a.d[0]) / a.v, -(q * a.d[1]) / a.v, -(q * a.d[2]) / a.v, -(q * a.d[3]) / a.v}};
+}
+
+LT_HD void rf_fview_prep(const double *k4, const double *q4, const double *t3, RfFView *v) {
+  double q[4];
+  const double n0 = sqrt((q4[0] * q4[0] + q4[2] * q4[2]) + (q4[1] * q4[1] + q4[3] * q4[3]));
+  for (int i = 0; i < 4; ++i) q[i] = n0 > 0.0 ? q4[i] / n0 : q4[i];
+  const double a = q[0], b = q[1], c = q[2], d = q[3];
+  const double aa = a * a, ab = a * b, ac = a * c, ad = a * d, bb = b * b, bc = b * c, bd = b * d, cc = c * c,
+               cd = c * d, dd = d * d;
+  const double R[9] = {((aa + bb) - cc) - dd, 2.0 * (bc - ad), 2.0 * (ac + bd), 2.0 * (ad + bc), ((aa - bb) + cc) - dd,
+                       2.0 * (cd - ab), 2.0 * (bd - ac), 2.0 * (ab + cd), ((aa - bb) - cc) + dd};
+  const double n = 1.0 / (((aa + bb) + cc) + dd);
+  for (int i = 0; i < 9; ++i) v->R[i] = R[i] * n;
+  for (int i = 0; i < 3; ++i) v->t[i] = t3[i];
+  for (int i = 0; i < 4; ++i) v->k[i] = k4[i];
+}
+
+// the fundamental matrix of GetEpipolarLineCoordinate (line_projection.h:150-191), constant per (reference, target):
+// relR = R_tgt R_ref^T, relT = t_tgt - relR t_ref, E = [relT]x relR, F = (Kinv_tgt^T E) Kinv_ref; every product sums its
+// three terms left to right, zero entries included
+LT_HD void rf_fundamental(const RfFView &ref, const RfFView &tgt, double F[9]) {
+  double Rrt[9], relR[9];
+  tr3(ref.R, Rrt);
+  mm(tgt.R, Rrt, relR);
+  const d3 rt = mv(relR, mk3(ref.t[0], ref.t[1], ref.t[2]));
+  const d3 relT = mk3(tgt.t[0] - rt.x, tgt.t[1] - rt.y, tgt.t[2] - rt.z);
+  const double sk[9] = {0.0, -relT.z, relT.y, relT.z, 0.0, -relT.x, -relT.y, relT.x, 0.0};
+  double E[9], Kitt[9], tmp[9];
+  mm(sk, relR, E);
+  const double Kir[9] = {1.0 / ref.k[0], 0.0, -ref.k[2] / ref.k[0], 0.0, 1.0 / ref.k[1], -ref.k[3] / ref.k[1], 0.0, 0.0, 1.0};
+  const double Kit[9] = {1.0 / tgt.k[0], 0.0, -tgt.k[2] / tgt.k[0], 0.0, 1.0 / tgt.k[1], -tgt.k[3] / tgt.k[1], 0.0, 0.0, 1.0};
+  tr3(Kit, Kitt);
+  mm(Kitt, E, tmp);
+  mm(tmp, Kir, F);
+}
+
+// MinimalPluckerToPlucker with Ceres' QuaternionToRotation as published: the scaled rotation times 1 / |u|^2
+template <class T>
+LT_HD void rf_plucker_c(const T u[4], const T w[2], T d[3], T m[3]) {
+  const T a = u[0], b = u[1], c = u[2], e = u[3];
+  const T aa = a * a, ab = a * b, ac = a * c, ae = a * e, bb = b * b, bc = b * c, be = b * e, cc = c * c, ce = c * e,
+          ee = e * e;
+  const T n = rf_inv(((aa + bb) + cc) + ee);
+  const T r0 = (((aa + bb) - cc) - ee) * n, r1 = ((bc - ae) * 2.0) * n;
+  const T r3 = ((ae + bc) * 2.0) * n, r4 = (((aa - bb) + cc) - ee) * n;
+  const T r6 = ((be - ac) * 2.0) * n, r7 = ((ab + ce) * 2.0) * n;
+  const T w1 = rf_abs(w[0]), w2 = rf_abs(w[1]);
+  const T bn = w2 / (w1 + kEps);
+  d[0] = r0; d[1] = r3; d[2] = r6;
+  m[0] = r1 * bn; m[1] = r4 * bn; m[2] = r7 * bn;
+}
+
+// Line_WorldToPixel (line_projection.h:14-80) by its matrix products, the zero entries of the skew matrices and of K
+// left out (they add an exact zero)
+template <class T>
+LT_HD void rf_w2p(const RfFView &v, const T d[3], const T m[3], T c[3]) {
+  const double *R = v.R;
+  T Rd[3], RS[3][3];
+  for (int i = 0; i < 3; ++i) {
+    const double r0 = R[3 * i], r1 = R[3 * i + 1], r2 = R[3 * i + 2];
+    Rd[i] = (d[0] * r0 + d[1] * r1) + d[2] * r2;
+    RS[i][0] = m[2] * r1 + (-m[1]) * r2;
+    RS[i][1] = (-m[2]) * r0 + m[0] * r2;
+    RS[i][2] = m[1] * r0 + (-m[0]) * r1;
+  }
+  // M(i, j) = ((R S R^T)(i, j) - t_i (R d)_j) + (R d)_i t_j at (2, 1), (0, 2), (1, 0)
+  const int ii[3] = {2, 0, 1}, jj[3] = {1, 2, 0};
+  T mt[3];
+  for (int e = 0; e < 3; ++e) {
+    const int i = ii[e], j = jj[e];
+    const T rmr = (RS[i][0] * R[3 * j] + RS[i][1] * R[3 * j + 1]) + RS[i][2] * R[3 * j + 2];
+    mt[e] = (rmr - Rd[j] * v.t[i]) + Rd[i] * v.t[j];
+  }
+  const double fx = v.k[0], fy = v.k[1], cx = v.k[2], cy = v.k[3];
+  const T c0 = mt[0] * fy;
+  const T c1 = mt[1] * fx;
+  const T c2 = (mt[2] * fy + (-mt[1]) * cy) * fx + ((-mt[0]) * fy) * cx;
+  const T cn = rf_sqrt(((c0 * c0 + c1 * c1) + c2 * c2) + kEps);
+  c[0] = c0 / cn; c[1] = c1 / cn; c[2] = c2 / cn;
+}
+
+// Ceres_IntersectLineCoordinates (line_transforms.h:55-72) of the projected line c with the line k, the rule of
+// rf_heat_residual; k is a constant (the sample line) or moves with the line (the epipolar line)
+template <class T, class K>
+LT_HD bool rf_intersect(const T c[3], const K k[3], T *x, T *y) {
+  T p0 = c[1] * k[2] - c[2] * k[1], p1 = c[2] * k[0] - c[0] * k[2], p2 = c[0] * k[1] - c[1] * k[0];
+  const T n = rf_sqrt((p0 * p0 + p1 * p1) + p2 * p2);
+  p0 = p0 / n; p1 = p1 / n; p2 = p2 / n;
+  if (!(rf_abs(rf_val(p2)) >= kEps)) {
+    rf_set(*x, 0.0);
+    rf_set(*y, 0.0);
+    return false;
+  }
+  *x = p0 / p2;
+  *y = p1 / p2;
+  return true;
+}
+
+// (F (x, y, 1)).normalized(): unchanged where the squared norm is not positive
+template <class T>
+LT_HD void rf_epiline(const double *F, const T &x, const T &y, T e[3]) {
+  for (int i = 0; i < 3; ++i) e[i] = (x * F[3 * i] + y * F[3 * i + 1]) + F[3 * i + 2];
+  const T z = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
+  if (rf_val(z) > 0.0) {
+    const T n = rf_sqrt(z);
+    e[0] = e[0] / n; e[1] = e[1] / n; e[2] = e[2] / n;
+  }
+}
+
+// FeaturePatch::GlobalToLocal (featurepatch.h:53-67)
+template <class T>
+LT_HD void rf_to_local(const RfFImg &g, const T &x, const T &y, T *lx, T *ly) {
+  const T ax = x - g.t[0], ay = y - g.t[1];
+  *lx = ax * g.R[0] + ay * g.R[1];
+  *ly = ax * g.R[2] + ay * g.R[3];
+}
+
+// the two channels of a lane at texel (r, c), clamped like Grid2D::GetValue: one 4-byte (binary16) or 8-byte (float) load
+LT_HD void rf_texel2(const unsigned short *tex, int h, int w, int r, int c, int lane, double out[2]) {
+  r = r < 0 ? 0 : (r > h - 1 ? h - 1 : r);
+  c = c < 0 ? 0 : (c > w - 1 ? w - 1 : c);
+  const unsigned short *p = tex + ((long long)r * w + c) * kRfChannels + 2 * lane;
+  unsigned int bits;
+  __builtin_memcpy(&bits, __builtin_assume_aligned(p, 4), 4);
+  out[0] = rf_widen((unsigned short)(bits & 0xffffu));
+  out[1] = rf_widen((unsigned short)(bits >> 16));
+}
+LT_HD void rf_texel2(const float *tex, int h, int w, int r, int c, int lane, double out[2]) {
+  r = r < 0 ? 0 : (r > h - 1 ? h - 1 : r);
+  c = c < 0 ? 0 : (c > w - 1 ? w - 1 : c);
+  const float *p = tex + ((long long)r * w + c) * kRfChannels + 2 * lane;
+  float f[2];
+  __builtin_memcpy(f, __builtin_assume_aligned(p, 8), 8);
+  out[0] = rf_widen(f[0]);
+  out[1] = rf_widen(f[1]);
+}
+// BiLinearInterpolator::Evaluate at (row, col) for the lane's two channels: the value from 4 texels, the Jet from 8
+template <class Tx>
+LT_HD void rf_feat_value(const RfFImg &g, double r, double c, int lane, double f[2]) {
+  int row, col;
+  double dy, dx, ll[2], lr[2], ul[2], ur[2];
+  const Tx *tex = static_cast<const Tx *>(g.tex);
+  rf_cell(r, c, g.h, g.w, &row, &col, &dy, &dx);
+  rf_texel2(tex, g.h, g.w, row, col, lane, ll);
+  rf_texel2(tex, g.h, g.w, row, col + 1, lane, lr);
+  rf_texel2(tex, g.h, g.w, row + 1, col, lane, ul);
+  rf_texel2(tex, g.h, g.w, row + 1, col + 1, lane, ur);
+  for (int ch = 0; ch < 2; ++ch) f[ch] = rf_bilinear(dx, dy, ll[ch], lr[ch], ul[ch], ur[ch]);
+}
+template <class Tx>
+LT_HD void rf_feat_jet(const RfFImg &g, double r, double c, int lane, double f[2], double dfdr[2], double dfdc[2]) {
+  int row, col;
+  double dy, dx, ll[2], lr[2], ul[2], ur[2], lrx[2], urx[2], uly[2], ury[2];
+  const Tx *tex = static_cast<const Tx *>(g.tex);
+  rf_cell(r, c, g.h, g.w, &row, &col, &dy, &dx);
+  rf_texel2(tex, g.h, g.w, row, col, lane, ll);
+  rf_texel2(tex, g.h, g.w, row, col + 1, lane, lr);
+  rf_texel2(tex, g.h, g.w, row + 1, col, lane, ul);
+  rf_texel2(tex, g.h, g.w, row + 1, col + 1, lane, ur);
+  rf_texel2(tex, g.h, g.w, row, col + 2, lane, lrx);
+  rf_texel2(tex, g.h, g.w, row + 1, col + 2, lane, urx);
+  rf_texel2(tex, g.h, g.w, row + 2, col, lane, uly);
+  rf_texel2(tex, g.h, g.w, row + 2, col + 1, lane, ury);
+  for (int ch = 0; ch < 2; ++ch) {
+    f[ch] = rf_bilinear(dx, dy, ll[ch], lr[ch], ul[ch], ur[ch]);
+    dfdr[ch] = rf_bilinear(dx, dy, ul[ch], ur[ch], uly[ch], ury[ch]) - f[ch];
+    dfdc[ch] = rf_bilinear(dx, dy, lr[ch], lrx[ch], ur[ch], urx[ch]) - f[ch];
+  }
+}
+
+// the wave-uniform geometry of a sample and of a block: local coordinates on the reference and on the target grid.
+// false: an intersection fails
+template <class T>
+LT_HD bool rf_feat_ref_xy(const T c_ref[3], const RfFSample &s, const RfFImg &g, T *x, T *y, T *lx, T *ly) {
+  const bool ok = rf_intersect<T, double>(c_ref, s.k, x, y);
+  rf_to_local<T>(g, *x, *y, lx, ly);
+  return ok;
+}
+template <class T>
+LT_HD bool rf_feat_tgt_xy(const T c_tgt[3], const double *F, const T &x, const T &y, const RfFImg &g, T *lx, T *ly) {
+  T e[3], xt, yt;
+  rf_epiline<T>(F, x, y, e);
+  const bool ok = rf_intersect<T, T>(c_tgt, e, &xt, &yt);
+  rf_to_local<T>(g, xt, yt, lx, ly);
+  return ok;
+}
+
+// a lane's two channels of the reference side of a sample: values and derivatives
+struct RfFRef {
+  double f[2], d[2][4];
+};
+template <class Tx>
+LT_HD void rf_feat_ref_lane(const RfFImg &g, const Rf4 &lx, const Rf4 &ly, int lane, RfFRef *o) {
+  double fr[2], fc[2];
+  rf_feat_jet<Tx>(g, ly.v, lx.v, lane, o->f, fr, fc);
+  for (int ch = 0; ch < 2; ++ch)
+    for (int i = 0; i < 4; ++i) o->d[ch][i] = fr[ch] * ly.d[i] + fc[ch] * lx.d[i];
+}
+// a lane's part of a block's sums (part starts at zero): channel 2 l, then 2 l + 1; the order of rf_accumulate, then
+// the squared norm.  res2 (host, tests): the lane's two residuals
+template <class Tx>
+LT_HD void rf_feat_block_lane(const RfFImg &g, const Rf4 &lx, const Rf4 &ly, const RfFRef &ref, int lane,
+                              double part[kRfFeatSums], double *res2 = nullptr) {
+  double f[2], fr[2], fc[2];
+  rf_feat_jet<Tx>(g, ly.v, lx.v, lane, f, fr, fc);
+  for (int ch = 0; ch < 2; ++ch) {
+    const double v = f[ch] - ref.f[ch];
+    double d[4];
+    for (int i = 0; i < 4; ++i) d[i] = (fr[ch] * ly.d[i] + fc[ch] * lx.d[i]) - ref.d[ch][i];
+    if (res2) res2[ch] = v;
+    int o = 0;
+    for (int i = 0; i < 4; ++i)
+      for (int j = i; j < 4; ++j, ++o) part[o] = part[o] + d[i] * d[j];
+    for (int i = 0; i < 4; ++i) part[10 + i] = part[10 + i] + d[i] * v;
+    part[kRfSums] = part[kRfSums] + v * v;
+  }
+}
+// a lane's part of a block's squared norm from the values alone
+template <class Tx>
+LT_HD double rf_feat_sq_lane(const RfFImg &g, double lx, double ly, const double fref[2], int lane) {
+  double f[2];
+  rf_feat_value<Tx>(g, ly, lx, lane, f);
+  const double v0 = f[0] - fref[0], v1 = f[1] - fref[1];
+  return (0.0 + v0 * v0) + v1 * v1;
+}
+
+// the fixed xor tree over the 64 lanes' parts of a block or of the supports (host twin of wave_sum)
+template <int C>
+inline void rf_tree64_host(double part[kRfFeatLanes][C], int n, double *out) {
+  for (int m = kRfFeatLanes / 2; m >= 1; m >>= 1) {
+    double nxt[kRfFeatLanes][C];
+    for (int l = 0; l < kRfFeatLanes; ++l)
+      for (int c = 0; c < n; ++c) nxt[l][c] = part[l][c] + part[l ^ m][c];
+    for (int l = 0; l < kRfFeatLanes; ++l)
+      for (int c = 0; c < n; ++c) part[l][c] = nxt[l][c];
+  }
+  for (int c = 0; c < n; ++c) out[c] = part[0][c];
+}
+
 void launch_refine_prep(hipStream_t st, const double *kvec, const double *qvec, const double *tvec, const int *sup_cam,
                         const double *l2d4, long long n_sup, double *sup_tab, long long stride, const double *line6,
                         long long n_tracks, RfOut *out);
@@ -864,5 +1163,9 @@ void launch_refine_prep_terms(hipStream_t st, const double *kvec, const double *
                               const int *vp_flag, const double *vp3, long long n_sup, double *ext, long long stride);
 // texel_f32: the texels are float, not binary16; only read with cfg.use_heatmap
 void launch_refine_lm_terms(hipStream_t st, const RfDev &dev, const RfDevTerms &terms, bool texel_f32, RfOut *out);
+// k_refine_lm_feat: the tracks' feature blocks besides the terms'; texel_f32: the type of the features (and of the
+// heatmaps, where cfg.use_heatmap)
+void launch_refine_lm_feat(hipStream_t st, const RfDev &dev, const RfDevTerms &terms, const RfDevFeat &feat, bool texel_f32,
+                           RfOut *out);
 
 }  // namespace lt

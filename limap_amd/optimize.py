@@ -5,23 +5,28 @@
     ba_engine = optimize.solve_line_bundle_adjustment(cfg_ba, imagecols, linetracks, max_num_iterations=200)
     linetracks_map = ba_engine.GetOutputLineTracks(num_outliers=cfg["refinement"]["num_outliers_aggregator"])
 
-and, per track, `solve_line_refinement` / `line_refinement` (optimize/line_refinement) with their geometric, VP and
-heatmap terms -- what limap.runners.refinement calls (cfgs/refinement/default.yaml):
+and, per track, `solve_line_refinement` / `line_refinement` (optimize/line_refinement) with their geometric, VP,
+heatmap and feature-consistency terms -- what limap.runners.refinement calls (cfgs/refinement/default.yaml):
 
     vpresults = vplib.get_vp_detector(cfg["vpdet"]).detect_vp_all_images(all_2d_lines, camviews)
-    tracks = optimize.line_refinement(cfg["refinement"], tracks, imagecols, heatmap_dir, vpresults=vpresults)
+    tracks = optimize.line_refinement(cfg["refinement"], tracks, imagecols, heatmap_dir, patch_dir, featuremap_dir,
+                                      vpresults=vpresults)
 
 With constant intrinsics and poses every track is its own 4-degree-of-freedom problem; all of them run in one launch of
 the HIP kernels of lt_kernels_refine.hip.  The heatmaps (`heatmap_{img_id}.npy` in heatmap_dir,
 or `heatmaps={img_id: array}`) are loaded once, rounded to `dtype` ("float16", upstream's default, or "float32") by
-numpy's astype, uploaded once and sampled by the kernel.  limap's cost, parameterisation, weights, residual order and
+numpy's astype, uploaded once and sampled by the kernel.  The feature term (use_feature) reads
+the line patches of limap_amd.features (`patch_dir` with track{t}/track{t}_img{i}.npy, or `patches={(t, img_id):
+PatchInfo}`, also those `extract_track_patches(..., device_out=True)` left on the device) or whole feature maps
+(`featuremap_dir` with feature_{img_id}.npy stored (C, H, W), or `featuremaps={img_id: (H, W, 128) array or GPU tensor}`);
+tracks with patches go to the device in groups of at most `patch_bytes` (FEATURE_PATCH_BYTES) of texels.  limap's cost, parameterisation, weights, residual order and
 segment cut are restated; **the minimiser is this project's deterministic Levenberg-Marquardt definition: refined lines
 are minimisers of upstream's cost, not the iterates of a particular Ceres run.**
 
 Not built, and rejected with a ValueError that names the key: constant_intrinsics=False, constant_pose=False, point
-tracks, use_feature (p_patches, p_features); use_vp and use_heatmap on the hybrid bundle adjustment, which has no such
-terms upstream either.  A track whose cost cannot be evaluated at its initial line (a heatmap sample line parallel to
-the projection) ends with TERMINATION 6 and keeps its line, re-cut.
+tracks, use_ref_descriptor, channels other than 128; use_vp, use_heatmap and use_feature on the hybrid bundle adjustment
+(the first two are no terms of it upstream either).  A track whose cost cannot be evaluated at its initial line (a
+sample line parallel to the projection) ends with TERMINATION 6 and keeps its line, re-cut.
 
 `host_threads=N` on the solve functions runs the documented host path (lt_fn_refine_host: the same inline functions in
 plain C++, bit-identical results) on N OpenMP threads instead of the device; it is a request, never a fallback -- without
@@ -36,20 +41,24 @@ from . import _capi
 from .base import Line3d, LineTrack
 
 __all__ = ["HybridBAConfig", "RefinementConfig", "HybridBAEngine", "RefinementEngine", "Heatmaps",
-           "solve_line_bundle_adjustment", "solve_line_refinement", "line_refinement", "TERMINATION"]
+           "solve_line_bundle_adjustment", "solve_line_refinement", "line_refinement", "TERMINATION", "FeatureMaps",
+           "FEATURE_PATCH_BYTES"]
 
 TERMINATION = {0: "max_num_iterations", 1: "radius", 2: "zero_gradient", 3: "pivot", 4: "model_decrease", 5: "constant",
                6: "evaluation_failed"}
+FEATURE_PATCH_BYTES = 512 << 20  # default budget of the feature term for the patch texels of one native call
 _TEXELS = {"float16": (np.float16, _capi.TEXEL_F16), "float32": (np.float32, _capi.TEXEL_F32)}
 
 
 class RefinementConfig:
-    """optimize/line_refinement/refinement_config.h:18-90 -- the keys the geometric, VP and heatmap terms read
-    (ASSIGN_PYDICT_ITEM: a present key overrides, unknown keys are ignored)."""
+    """optimize/line_refinement/refinement_config.h:18-90 -- the keys the geometric, VP, heatmap and feature terms
+    read (ASSIGN_PYDICT_ITEM: a present key overrides, unknown keys are ignored).  use_ref_descriptor=False and
+    ref_multiplier are accepted and not read."""
     _KEYS = dict(use_geometric=bool, min_num_images=int, num_outliers_aggregate=int, geometric_alpha=float,
                  print_summary=bool, vp_multiplier=float, sample_range_min=float, sample_range_max=float,
-                 n_samples_heatmap=int, heatmap_multiplier=float)
-    _UNSUPPORTED_TRUE = ("use_feature",)
+                 n_samples_heatmap=int, heatmap_multiplier=float, n_samples_feature=int, fconsis_multiplier=float,
+                 use_ref_descriptor=bool, ref_multiplier=float)
+    _UNSUPPORTED_TRUE = ("use_ref_descriptor",)
 
     def __init__(self, cfg=None):
         self.use_geometric, self.min_num_images, self.num_outliers_aggregate = True, 4, 2
@@ -60,9 +69,12 @@ class RefinementConfig:
         # not keys of upstream's C++ configuration: the python callers read them from the same dict
         self.num_outliers_aggregator = 2
         self.use_vp = self.use_heatmap = self.use_feature = False
-        self.dtype = "float16"  # the texels of the heatmaps (line_refinement.py:27: cfg["dtype"])
+        self.n_samples_feature, self.fconsis_multiplier = 100, 1.0
+        self.use_ref_descriptor, self.ref_multiplier = False, 5.0
+        self.channels = 128     # cfg["channels"] (line_refinement.py: the RefinementEngine's template argument)
+        self.dtype = "float16"  # the texels of the heatmaps and features (line_refinement.py:27: cfg["dtype"])
         self._assign(cfg, dict(self._KEYS, num_outliers_aggregator=int, use_vp=bool, use_heatmap=bool, use_feature=bool,
-                               dtype=str))
+                               dtype=str, channels=int))
 
     def _assign(self, cfg, keys):
         if cfg is None:
@@ -77,14 +89,26 @@ class RefinementConfig:
         for k in self._UNSUPPORTED_TRUE:
             if getattr(self, k):
                 raise ValueError(f"limap_amd.optimize: {k}=True is not built here")
-        if not (self.use_geometric or self.use_vp or self.use_heatmap):
+        if not (self.use_geometric or self.use_vp or self.use_heatmap or self.use_feature):
             raise ValueError("limap_amd.optimize: use_geometric=False leaves no residual")
-        if self.use_heatmap and self.dtype not in _TEXELS:
+        if (self.use_heatmap or self.use_feature) and self.dtype not in _TEXELS:
             raise ValueError(f"limap_amd.optimize: dtype={self.dtype!r} is not built (float16 or float32 texels)")
+        if self.use_feature and self.channels != 128:
+            raise ValueError(f"limap_amd.optimize: channels={self.channels} is not built (128, upstream's only instance)")
+
+    def _feature(self, dtype=None):
+        """lt_refine_feature, or None without the feature term"""
+        if not self.use_feature:
+            return None
+        f = _capi.LtRefineFeature()
+        _capi.load_library().lt_refine_feature_default(C.byref(f))
+        f.n_samples_feature, f.fconsis_multiplier = int(self.n_samples_feature), float(self.fconsis_multiplier)
+        f.channels, f.texel_type = int(self.channels), _TEXELS[dtype or self.dtype][1]
+        return f
 
     def _terms(self):
-        """lt_refine_terms, or None where neither the VP nor the heatmap term is on"""
-        if not (self.use_vp or self.use_heatmap):
+        """lt_refine_terms, or None where none of the VP, heatmap and feature terms is on"""
+        if not (self.use_vp or self.use_heatmap or self.use_feature):
             return None
         t = _capi.LtRefineTerms()
         _capi.load_library().lt_refine_terms_default(C.byref(t))
@@ -106,7 +130,8 @@ class RefinementConfig:
 
 class HybridBAConfig(RefinementConfig):
     """optimize/hybrid_bundle_adjustment/hybrid_bundle_adjustment_config.h:17-49"""
-    _UNSUPPORTED_TRUE = ("use_vp", "use_heatmap", "use_feature")  # no such terms in the hybrid bundle adjustment
+    # no VP or heatmap term in the hybrid bundle adjustment; its feature term is not built
+    _UNSUPPORTED_TRUE = ("use_vp", "use_heatmap", "use_feature", "use_ref_descriptor")
     _BA_KEYS = dict(constant_intrinsics=bool, constant_principal_point=bool, constant_pose=bool, constant_point=bool,
                     constant_line=bool, lw_point=float)
 
@@ -206,11 +231,87 @@ class Heatmaps:
             ctx._refine_heatmaps = (id(self), ctx.L.lt_refine_heatmaps_generation(ctx.h))
 
 
+def _is_torch(x):
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+def _texel_array(a, np_type, host, what):
+    """an (h, w, 128) array or tensor -> (what keeps the memory, address, h, w, on_device) in the texel type; a GPU
+    tensor stays on the device unless the host path was asked for"""
+    if _is_torch(a):
+        if a.is_cuda and not host:
+            import torch
+            a = a.to(getattr(torch, np.dtype(np_type).name)).contiguous()
+            if a.dim() != 3 or a.shape[2] != 128 or a.shape[0] < 1 or a.shape[1] < 1:
+                raise ValueError(f"limap_amd.optimize: {what} must be (h, w, 128), got shape {tuple(a.shape)}")
+            return a, a.data_ptr(), int(a.shape[0]), int(a.shape[1]), 1
+        a = a.detach().cpu().numpy()
+    a = np.ascontiguousarray(np.asarray(a).astype(np_type, copy=False))
+    if a.ndim != 3 or a.shape[2] != 128 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f"limap_amd.optimize: {what} must be (h, w, 128), got shape {a.shape}")
+    return a, a.ctypes.data, a.shape[0], a.shape[1], 0
+
+
+class FeatureMaps:
+    """The feature maps of a scene (the map form of the feature term): {img_id: (H, W, 128) array or GPU tensor},
+    rounded to the texel type by one astype like the heatmaps.  Host arrays are uploaded once per context, GPU tensors
+    are read in place."""
+
+    def __init__(self, featuremaps, dtype="float16", host=False):
+        if dtype not in _TEXELS:
+            raise ValueError(f"limap_amd.optimize: dtype={dtype!r} is not built (float16 or float32 texels)")
+        np_type, self.texel_type = _TEXELS[dtype]
+        self.ids = np.array(sorted(int(i) for i in featuremaps), np.int32)
+        ent = [_texel_array(featuremaps[int(i)], np_type, host, f"the feature map of image {i}") for i in self.ids]
+        dev = {e[4] for e in ent}
+        if len(dev) > 1:
+            raise ValueError("limap_amd.optimize: featuremaps mixes host arrays and GPU tensors")
+        self.on_device = int(bool(dev and dev.pop()))
+        self.keep = [e[0] for e in ent]
+        self.h = np.array([e[2] for e in ent], np.int32)
+        self.w = np.array([e[3] for e in ent], np.int32)
+        self.addr = {int(i): e[1] for i, e in zip(self.ids, ent)}
+        self.ptrs = (C.c_void_p * max(len(ent), 1))(*[e[1] for e in ent])
+
+    def grid(self, img_id):
+        """the identity grid of an image (host path)"""
+        k = int(np.searchsorted(self.ids, img_id))
+        if k >= len(self.ids) or self.ids[k] != img_id:
+            return None
+        return self.addr[int(img_id)], int(self.h[k]), int(self.w[k]), (1.0, 0.0, 0.0, 1.0), (0.0, 0.0), self.on_device
+
+    def upload(self, ctx):
+        """once per context, confirmed by the context's generation counter like Heatmaps.upload"""
+        gen = ctx.L.lt_refine_feature_maps_generation(ctx.h)
+        if getattr(ctx, "_refine_featuremaps", None) != (id(self), gen):
+            ctx._refine_featuremaps = None
+            if self.on_device:
+                import torch
+                torch.cuda.synchronize()  # the context's stream does not wait for torch's streams
+            p = _capi.ptr
+            ctx.chk(ctx.L.lt_refine_set_feature_maps(ctx.h, len(self.ids), p(self.ids, C.c_int32), p(self.h, C.c_int32),
+                                                     p(self.w, C.c_int32), self.ptrs, self.texel_type, self.on_device))
+            ctx._refine_featuremaps_owner = self
+            ctx._refine_featuremaps = (id(self), ctx.L.lt_refine_feature_maps_generation(ctx.h))
+
+
+def _grid_array(grids):
+    """[(address, h, w, R4, tvec2, on_device)] -> (lt_refine_grid array, count)"""
+    arr = (_capi.LtRefineGrid * max(len(grids), 1))()
+    for g, (addr, h, w, R, tv, dev) in zip(arr, grids):
+        g.data, g.h, g.w, g.on_device = addr, int(h), int(w), int(dev)
+        g.R[:] = [float(x) for x in R]
+        g.tvec[:] = [float(x) for x in tv]
+    return arr, len(grids)
+
+
 def refine_arrays(cams, tracks_csr, cfg_struct, host_threads=None, ctx=None, terms=None, vp=None, view_hw=None,
-                  heatmaps=None):
+                  heatmaps=None, feature=None, grids=None, featuremaps=None):
     """One call of lt_refine_arrays (device) or lt_fn_refine_host (host_threads given) -> dict of per-track results.
     terms (lt_refine_terms) selects the *_terms entry points: vp = (flag (M,), vp3 (M, 3)) per support in list order,
-    view_hw (n_img, 2) or None, heatmaps a Heatmaps."""
+    view_hw (n_img, 2) or None, heatmaps a Heatmaps.  feature (lt_refine_feature) selects the *_feature entry points:
+    grids = [(address, h, w, R, tvec, on_device)] per (track, sorted image), or None with featuremaps (a FeatureMaps),
+    which the device call reads from the context."""
     ids, k, q, t = cams
     line6, off, img, l2, l3 = tracks_csr
     T = len(off) - 1
@@ -229,12 +330,28 @@ def refine_arrays(cams, tracks_csr, cfg_struct, host_threads=None, ctx=None, ter
         targs = (C.byref(terms), p(flag, C.c_int32), p(vp3, C.c_double), None if hw is None else p(hw, C.c_int32))
         if terms.use_heatmap and heatmaps is None:
             raise ValueError("limap_amd.optimize: use_heatmap without heatmaps")
+    if feature is not None:
+        if terms is None:
+            raise ValueError("limap_amd.optimize: the feature term needs the terms")
+        if grids is None and featuremaps is None:
+            raise ValueError("limap_amd.optimize: use_feature without patches or feature maps")
+        if grids is None and host_threads is not None:  # the host twin takes a map as the identity grid
+            grids = []
+            for n in range(T):
+                for i in sorted(set(int(x) for x in img[off[n]:off[n + 1]])):
+                    g = featuremaps.grid(i)
+                    if g is None:
+                        raise ValueError(f"limap_amd.optimize: image {i} supports track {n} and has no feature map")
+                    grids.append(g)
+        garr, n_grids = _grid_array(grids) if grids is not None else (None, 0)
     if host_threads is not None:
+        hm = heatmaps.args() if terms is not None and terms.use_heatmap else (0, None, None, None, None)
         if terms is None:
             rc = L.lt_fn_refine_host(*args, int(host_threads), *outs)
-        else:
-            hm = heatmaps.args() if terms.use_heatmap else (0, None, None, None, None)
+        elif feature is None:
             rc = L.lt_fn_refine_host_terms(*args, *targs, *hm, int(host_threads), *outs)
+        else:
+            rc = L.lt_fn_refine_host_feature(*args, *targs, *hm, C.byref(feature), n_grids, garr, int(host_threads), *outs)
         if rc != 0:
             raise ValueError("limap_amd.optimize: " + L.lt_fn_refine_host_error().decode(errors="replace"))
     else:
@@ -244,7 +361,15 @@ def refine_arrays(cams, tracks_csr, cfg_struct, host_threads=None, ctx=None, ter
         else:
             if terms.use_heatmap:
                 heatmaps.upload(ctx)
-            ctx.chk(L.lt_refine_arrays_terms(ctx.h, *args, *targs))
+            if feature is None:
+                ctx.chk(L.lt_refine_arrays_terms(ctx.h, *args, *targs))
+            else:
+                if grids is None:
+                    featuremaps.upload(ctx)
+                elif any(g[5] for g in grids):
+                    import torch
+                    torch.cuda.synchronize()  # the context's stream does not wait for torch's streams
+                ctx.chk(L.lt_refine_arrays_feature(ctx.h, *args, *targs, C.byref(feature), n_grids, garr))
         ctx.chk(L.lt_refine_get(ctx.h, *outs))
         tm = np.zeros(4)
         ctx.chk(L.lt_refine_get_timers(ctx.h, p(tm, C.c_double)))
@@ -320,10 +445,7 @@ class RefinementEngine:
         return self._r
 
 
-def _refinement_cfg(cfg, kw):
-    for k in ("p_patches", "p_features"):
-        if kw.get(k) is not None:
-            raise ValueError(f"limap_amd.optimize: {k} is not built (use_feature)")
+def _refinement_cfg(cfg):
     rf = RefinementConfig(cfg) if isinstance(cfg, dict) or cfg is None else cfg
     rf._check()
     return rf
@@ -363,24 +485,74 @@ def _view_hw(ids, views):
     return np.array([[views[int(i)].h() or 0, views[int(i)].w() or 0] for i in ids], np.int32).reshape(-1, 2)
 
 
-def _refine(rf, tracks, views, vpresults, heatmaps, host_threads):
-    """all `tracks` in one native call; views, vpresults: {img_id: ...}; heatmaps: a Heatmaps"""
+def _patch_grids(patches, np_type, host, what):
+    """PatchInfos of one track's sorted images -> grid tuples, what keeps their memory, their texel bytes"""
+    grids, keep, nbytes = [], [], 0
+    for k, pt in enumerate(patches):
+        if not hasattr(pt, "array") or not hasattr(pt, "R") or not hasattr(pt, "tvec"):
+            raise ValueError(f"limap_amd.optimize: {what}[{k}] is not a features.PatchInfo")
+        a, addr, h, w, dev = _texel_array(pt.array, np_type, host, f"{what}[{k}].array")
+        keep.append(a)
+        grids.append((addr, h, w, np.asarray(pt.R, np.float64).reshape(4), np.asarray(pt.tvec, np.float64).reshape(2), dev))
+        nbytes += h * w * 128 * np.dtype(np_type).itemsize
+    return grids, keep, nbytes
+
+
+def _refine(rf, tracks, views, vpresults, heatmaps, host_threads, patches=None, featuremaps=None, dtype=None,
+            patch_bytes=FEATURE_PATCH_BYTES):
+    """all `tracks` in one native call -- with patches in as many as the byte budget asks for; views, vpresults:
+    {img_id: ...}; heatmaps: a Heatmaps; patches: per track the PatchInfos of its sorted images; featuremaps: a
+    FeatureMaps"""
     cams = _camera_arrays(views)
     terms = rf._terms()
-    vp = _vp_arrays(tracks, vpresults) if rf.use_vp else None
-    return refine_arrays(cams, _track_arrays(tracks), rf._struct(rf.num_outliers_aggregate), host_threads, terms=terms, vp=vp,
-                         view_hw=_view_hw(cams[0], views) if rf.use_heatmap else None, heatmaps=heatmaps)
+    cfg = rf._struct(rf.num_outliers_aggregate)
+    hw = _view_hw(cams[0], views) if rf.use_heatmap else None
+
+    def call(sub, **kw):
+        vp = _vp_arrays(sub, vpresults) if rf.use_vp else None
+        return refine_arrays(cams, _track_arrays(sub), cfg, host_threads, terms=terms, vp=vp, view_hw=hw, heatmaps=heatmaps, **kw)
+
+    if not rf.use_feature:
+        return call(tracks)
+    feature = rf._feature(dtype)
+    if patches is None:
+        return call(tracks, feature=feature, featuremaps=featuremaps)
+    # tracks in their order, a new native call where the next track's texels would pass the budget: every track is its
+    # own problem, so the grouping does not reach the results
+    np_type = _TEXELS[dtype or rf.dtype][0]
+    parts, group, grids, keep, used = [], [], [], [], 0
+    for n, t in enumerate(tracks):
+        g, k, nb = _patch_grids(patches[n], np_type, host_threads is not None, f"the patches of track {n}")
+        if group and used + nb > int(patch_bytes):
+            parts.append(call(group, feature=feature, grids=grids))
+            group, grids, keep, used = [], [], [], 0
+        group.append(t); grids += g; keep += k; used += nb
+    parts.append(call(group, feature=feature, grids=grids))
+    del keep
+    out = {k: np.concatenate([r[k] for r in parts]) for k in ("params", "segments", "cost", "iterations", "codes")}
+    out["timers"] = None if parts[0]["timers"] is None else {k: sum(r["timers"][k] for r in parts) for k in parts[0]["timers"]}
+    out["calls"] = len(parts)
+    return out
 
 
 def solve_line_refinement(cfg, track, p_camviews, p_vpresults=None, p_heatmaps=None, p_patches=None, p_features=None,
                           dtype=None, host_threads=None):
-    """optimize/line_refinement/solve.py:4-48: p_camviews, p_vpresults and p_heatmaps are the views, VPResults and
-    heatmaps of track.GetSortedImageIds(), in that order.  dtype: the texels ("float16" / "float32"; the
-    configuration's by default).  None below min_num_images."""
-    for name, lst in (("p_vpresults", p_vpresults), ("p_heatmaps", p_heatmaps)):
+    """optimize/line_refinement/solve.py:4-48: p_camviews, p_vpresults, p_heatmaps, p_patches (features.PatchInfo) and
+    p_features ((H, W, 128) arrays or GPU tensors) are the views, VPResults, heatmaps, patches and feature maps of
+    track.GetSortedImageIds(), in that order.  dtype: the texels ("float16" / "float32"; the configuration's by
+    default).  None below min_num_images."""
+    for name, lst in (("p_vpresults", p_vpresults), ("p_heatmaps", p_heatmaps), ("p_patches", p_patches),
+                      ("p_features", p_features)):
         if lst is not None and len(lst) != len(p_camviews):
             raise ValueError(f"limap_amd.optimize: {name} has {len(lst)} entries for {len(p_camviews)} views")
-    rf = _refinement_cfg(cfg, dict(p_patches=p_patches, p_features=p_features))
+    rf = _refinement_cfg(cfg)
+    if p_patches is not None and p_features is not None:
+        raise ValueError("limap_amd.optimize: p_patches and p_features are both given")
+    for name, lst in (("p_patches", p_patches), ("p_features", p_features)):
+        if lst is not None and not rf.use_feature:
+            raise ValueError(f"limap_amd.optimize: {name} is given and use_feature is off")
+    if rf.use_feature and p_patches is None and p_features is None:
+        raise ValueError("limap_amd.optimize: use_feature=True needs p_patches / p_features")
     if rf.use_vp and p_vpresults is None:
         raise ValueError("limap_amd.optimize: use_vp=True needs p_vpresults")
     if rf.use_heatmap and p_heatmaps is None:
@@ -391,18 +563,30 @@ def solve_line_refinement(cfg, track, p_camviews, p_vpresults=None, p_heatmaps=N
     if len(p_camviews) != len(ids):
         raise ValueError(f"{len(ids)} images support the track, {len(p_camviews)} views given")
     hm = Heatmaps(dict(zip(ids, p_heatmaps)), dtype or rf.dtype) if rf.use_heatmap else None
-    r = _refine(rf, [track], dict(zip(ids, p_camviews)), dict(zip(ids, p_vpresults)) if rf.use_vp else None, hm, host_threads)
+    fm = None
+    if rf.use_feature and p_features is not None:
+        fm = FeatureMaps(dict(zip(ids, p_features)), dtype or rf.dtype, host_threads is not None)
+    r = _refine(rf, [track], dict(zip(ids, p_camviews)), dict(zip(ids, p_vpresults)) if rf.use_vp else None, hm, host_threads,
+                patches=[list(p_patches)] if rf.use_feature and p_patches is not None else None, featuremaps=fm, dtype=dtype)
     return RefinementEngine(r)
 
 
 def line_refinement(cfg, tracks, imagecols, heatmap_dir=None, patch_dir=None, featuremap_dir=None, vpresults=None,
-                    n_visible_views=4, host_threads=None, heatmaps=None):
-    """optimize/line_refinement/line_refinement.py:15-136 with the geometric, VP and heatmap terms: the tracks seen in at
-    least n_visible_views images and min_num_images images are refined -- all of them in one call -- the others pass
-    through.  heatmap_dir holds heatmap_{img_id}.npy; heatmaps={img_id: array} gives them directly.  Every image is
-    loaded and uploaded once."""
+                    n_visible_views=4, host_threads=None, heatmaps=None, patches=None, featuremaps=None,
+                    patch_bytes=FEATURE_PATCH_BYTES):
+    """optimize/line_refinement/line_refinement.py:15-136: the tracks seen in at least n_visible_views images and
+    min_num_images images are refined, the others pass through.  heatmap_dir holds heatmap_{img_id}.npy;
+    heatmaps={img_id: array} gives them directly.  With use_feature, patch_dir holds track{t}/track{t}_img{i}.npy
+    (features.load_patch) and patches={(t, img_id): PatchInfo} gives them directly, t the track's index in `tracks`;
+    without patches, featuremap_dir holds feature_{img_id}.npy stored (C, H, W) and featuremaps={img_id: (H, W, 128)
+    array or GPU tensor} gives the maps directly.  Every image is loaded and uploaded once; tracks with patches run in
+    native calls of at most patch_bytes of texels each, which does not change a result."""
     import os
-    rf = _refinement_cfg(cfg, {})
+    rf = _refinement_cfg(cfg)
+    by_patch = patch_dir is not None or patches is not None
+    if rf.use_feature and not by_patch and featuremap_dir is None and featuremaps is None:
+        raise ValueError("limap_amd.optimize: use_feature=True needs patches / feature maps (patch_dir, patches, "
+                         "featuremap_dir or featuremaps)")
     if rf.use_vp and vpresults is None:
         raise ValueError("limap_amd.optimize: use_vp=True needs vpresults")
     if rf.use_heatmap and heatmap_dir is None and heatmaps is None:
@@ -411,13 +595,37 @@ def line_refinement(cfg, tracks, imagecols, heatmap_dir=None, patch_dir=None, fe
     out = list(tracks)
     if sel:
         views = {int(i): imagecols.camview(int(i)) for i in imagecols.get_img_ids()}
-        hm = None
+        hm = fm = plist = None
         if rf.use_heatmap:
             if heatmaps is None:
                 files = {i: os.path.join(heatmap_dir, f"heatmap_{i}.npy") for i in views}
                 heatmaps = {i: np.load(f) for i, f in files.items() if os.path.exists(f)}
             hm = Heatmaps(heatmaps, rf.dtype)
-        r = _refine(rf, [tracks[n] for n in sel], views, vpresults, hm, host_threads)
+        if rf.use_feature and by_patch:
+            from . import features
+            plist = []
+            for n in sel:
+                row = []
+                for i in tracks[n].GetSortedImageIds():
+                    pt = patches.get((n, int(i))) if patches is not None else None
+                    if pt is None and patch_dir is not None:
+                        fname = os.path.join(patch_dir, f"track{n}", f"track{n}_img{int(i)}.npy")
+                        pt = features.load_patch(fname, dtype=rf.dtype) if os.path.exists(fname) else None
+                    if pt is None:
+                        raise ValueError(f"limap_amd.optimize: no patch for track {n}, image {int(i)}")
+                    row.append(pt)
+                plist.append(row)
+        elif rf.use_feature:
+            if featuremaps is None:
+                files = {i: os.path.join(featuremap_dir, f"feature_{i}.npy") for i in views}
+                featuremaps = {i: np.load(f, allow_pickle=False).transpose(1, 2, 0) for i, f in files.items() if os.path.exists(f)}
+            for n in sel:
+                for i in tracks[n].GetSortedImageIds():
+                    if int(i) not in featuremaps:
+                        raise ValueError(f"limap_amd.optimize: no feature map for track {n}, image {int(i)}")
+            fm = FeatureMaps(featuremaps, rf.dtype, host_threads is not None)
+        r = _refine(rf, [tracks[n] for n in sel], views, vpresults, hm, host_threads, patches=plist, featuremaps=fm,
+                    patch_bytes=patch_bytes)
         for m, n in enumerate(sel):
             out[n] = _copy_track(tracks[n], Line3d(r["segments"][m, :3], r["segments"][m, 3:]))
     return out
