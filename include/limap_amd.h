@@ -1233,6 +1233,78 @@ int lt_fn_loc_score_host(const double kvec4[4], int64_t n_l3d, const double *lin
 /* CameraPose(R, T)'s quaternion: Eigen's Quaternion(Matrix3) of the row-major R9, (w, x, y, z) */
 int lt_fn_loc_qvec_from_R(const double R9[9], double qvec4[4]);
 
+/* ---- Bundle adjustment with free poses, points and lines: limap.optimize's
+ * solve_hybrid_bundle_adjustment / solve_point_bundle_adjustment, HybridBAEngine with constant intrinsics.  Every image
+ * that carries a residual block is a parameter (quaternion and translation), every point track (3 unknowns) and every
+ * line track (4, section 19's chart) unless its switch holds it constant.  limap's residuals, weights, losses, block
+ * order and segment cut are restated; the minimiser is this project's definition: one Levenberg-Marquardt loop over all
+ * unknowns with one radius, its linear step by a Schur complement over the images and a dense Cholesky factorisation in
+ * a fixed order.  The results are a stationary point of upstream's cost reached from the input, not the iterates of a
+ * Ceres run; upstream does not fix the gauge, so compare costs and reprojections, never parameters. ---- */
+#define LT_BA_MAX_IMAGES 128 /* images that carry residuals; above it LT_ERR_ARGUMENT before any launch */
+typedef struct lt_ba_config {
+  double geometric_alpha;          /* 10 */
+  double lw_point;                 /* 0.1; <= 0 adds no point block */
+  int32_t min_num_images;          /* 4: a line track seen in fewer images keeps its line and still constrains its cameras */
+  int32_t num_outliers_aggregator; /* 2: GetOutputLineTracks' cut */
+  int32_t max_num_iterations;      /* 100; an attempt counts whether accepted or not */
+  int32_t constant_intrinsics;     /* 1; 0 is LT_ERR_ARGUMENT (free intrinsics are not built) */
+  int32_t constant_principal_point; /* accepted, no effect with constant intrinsics */
+  int32_t constant_pose;           /* 0; 1: the tracks separate -- point tracks only (line tracks are lt_refine_arrays'), every
+                                      one its own 3-unknown problem under section 19's loop with its own radius */
+  int32_t constant_point, constant_line;
+  int32_t poll_interval;           /* attempts enqueued between two reads of the status record; 0: the default (8).
+                                      The result does not depend on it */
+  int32_t kernel_timers;           /* 1: HIP events around every kernel of every attempt (the interval becomes 1) */
+} lt_ba_config;
+void lt_ba_config_default(lt_ba_config *cfg);
+int lt_ba_max_images(void);   /* LT_BA_MAX_IMAGES */
+int lt_ba_poll_default(void);
+/* Cameras as lt_refine_arrays takes them.  Point track n: pt3[3 n ..] and its observations pt_off[n] .. pt_off[n + 1] of
+ * pt_img (image ids) / pt_xy2, in list order; tracks in ascending id.  Line tracks as lt_refine_arrays: line6, ln_off,
+ * ln_img, l2d4, l3d6.  LT_ERR_ARGUMENT before any launch: constant_intrinsics = 0, constant_pose = 1 with line tracks, an image id that is
+ * not in the collection, non-finite input, a track line of zero length, a line track without supports, a zero focal
+ * length or quaternion of an image with residuals, more than LT_BA_MAX_IMAGES images with residuals. */
+int lt_ba_arrays(lt_ctx *ctx, int n_img, const int32_t *img_ids, const double *kvec4, const double *qvec4,
+                 const double *tvec3, int64_t n_pt, const double *pt3, const int64_t *pt_off, const int32_t *pt_img,
+                 const double *pt_xy2, int64_t n_ln, const double *line6, const int64_t *ln_off, const int32_t *ln_img,
+                 const double *l2d4, const double *l3d6, const lt_ba_config *cfg);
+/* of the last lt_ba_arrays (any pointer may be NULL): the poses of all n_img images in input order (an image without a
+ * residual block keeps its input bit for bit, the others carry a unit quaternion), the points, the lines' minimal
+ * parameters (uvec, wvec) and segments, cost2 = the cost at the initial and at the final point, the iterations and
+ * the termination code of the solve: 0 max_num_iterations, 1 radius, 2 zero gradient, 6 the cost at the initial point
+ * is not finite, 7 no residual block (Solve() returns false); 6 and 7 change nothing.  With constant_pose = 1 the
+ * poses are the input's, cost2 sums the tracks' costs in ascending order, iters is the largest count and code the largest
+ * of the free tracks' section 19 codes (0-4, 6; 5 where every track is constant) */
+int lt_ba_get(lt_ctx *ctx, double *qvec4, double *tvec3, double *pt3, double *params6, double *seg6, double *cost2,
+              int32_t *iters, int32_t *code);
+/* host ms of [0] validation, tables and upload, [1] the loop, [2] download; [3] attempts enqueued; with kernel_timers the
+ * device ms of [4] k_ba_linearize [5] k_ba_blocks [6] k_ba_images [7] k_ba_damp [8] k_ba_schur [9] k_ba_chol
+ * [10] k_ba_backsub [11] k_ba_cost [12] k_ba_decide, summed over the attempts */
+int lt_ba_get_timers(lt_ctx *ctx, double out[16]);
+/* The same definition on the host, no context and no device: bit-identical results for every n_threads (0: default) */
+int lt_fn_ba_host(int n_img, const int32_t *img_ids, const double *kvec4, const double *qvec4, const double *tvec3,
+                  int64_t n_pt, const double *pt3, const int64_t *pt_off, const int32_t *pt_img, const double *pt_xy2,
+                  int64_t n_ln, const double *line6, const int64_t *ln_off, const int32_t *ln_img, const double *l2d4,
+                  const double *l3d6, const lt_ba_config *cfg, int n_threads, double *qvec4_out, double *tvec3_out,
+                  double *pt3_out, double *params6, double *seg6, double *cost2, int32_t *iters, int32_t *code);
+const char *lt_fn_ba_host_error(void);
+/* For tests: the problem at its initial point (params6_in, when given, replaces the lines' minimal parameters).
+ * dims4 = images with residuals, blocks, unknowns, structures; with every other output NULL only dims4 is written.
+ * The unknowns: (dq, dt) of the images with residuals in ascending id, then the free structures in order (3 / 4 each).
+ * blk_info3 per block: image row, structure, first unknown of the structure (-1: constant).  residuals: 2 per block;
+ * cost; g = sum rho' J^T r; H = sum rho' J^T J (dense, unknowns x unknowns); step: the Schur route's step at radius mu
+ * (NaN where a factorisation fails). */
+int lt_fn_ba_eval(int n_img, const int32_t *img_ids, const double *kvec4, const double *qvec4, const double *tvec3,
+                  int64_t n_pt, const double *pt3, const int64_t *pt_off, const int32_t *pt_img, const double *pt_xy2,
+                  int64_t n_ln, const double *line6, const int64_t *ln_off, const int32_t *ln_img, const double *l2d4,
+                  const double *l3d6, const lt_ba_config *cfg, const double *params6_in, int64_t *dims4, int32_t *blk_info3,
+                  double *residuals, double *cost, double *g, double *H, double mu, double *step);
+/* the defined factorisation alone: L (n x n by rows, zero above the diagonal) of S (its lower triangle is read),
+ * L_ij = (S_ij - sum_{k<j} L_ik L_jk) / L_jj with the sum in ascending k from S_ij, and, with rhs and x, the solution
+ * of S x = rhs by substitutions under the same rule.  LT_ERR_STATE: a pivot is not positive or not finite */
+int lt_fn_ba_cholesky(int64_t n, const double *S, const double *rhs, double *L, double *x);
+
 /* Counters of the last device run: [0] connections tested, [1] candidates, [2] ordered candidate
  * pairs swept by the scoring kernel (sum n_tris^2), [3] valid edges, [4] graph nodes,
  * [5] graph edges, [6] tracks, [7] nodes. */

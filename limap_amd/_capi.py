@@ -65,6 +65,8 @@ EXPORTED_SYMBOLS = [
     "lt_loc_config_default", "lt_loc_solve", "lt_loc_num", "lt_loc_get", "lt_loc_get_timers", "lt_fn_loc_host",
     "lt_fn_loc_host_error", "lt_fn_loc_eval", "lt_fn_loc_qvec_from_R",
     "lt_loc_score", "lt_loc_score_size", "lt_loc_score_get", "lt_loc_score_get_timers", "lt_fn_loc_score_host",
+    "lt_ba_config_default", "lt_ba_max_images", "lt_ba_poll_default", "lt_ba_arrays", "lt_ba_get", "lt_ba_get_timers",
+    "lt_fn_ba_host", "lt_fn_ba_host_error", "lt_fn_ba_eval", "lt_fn_ba_cholesky",
 ]
 
 
@@ -220,6 +222,15 @@ class LtLocConfig(C.Structure):
     _fields_ = [("cost_function", C.c_int32), ("weight_function", C.c_int32), ("loss", C.c_int32),
                 ("max_num_iterations", C.c_int32), ("loss_a", C.c_double), ("weight_line", C.c_double),
                 ("weight_point", C.c_double)]
+
+
+class LtBaConfig(C.Structure):
+    """lt_ba_config of include/limap_amd.h"""
+    _fields_ = [("geometric_alpha", C.c_double), ("lw_point", C.c_double), ("min_num_images", C.c_int32),
+                ("num_outliers_aggregator", C.c_int32), ("max_num_iterations", C.c_int32),
+                ("constant_intrinsics", C.c_int32), ("constant_principal_point", C.c_int32), ("constant_pose", C.c_int32),
+                ("constant_point", C.c_int32), ("constant_line", C.c_int32), ("poll_interval", C.c_int32),
+                ("kernel_timers", C.c_int32)]
 
 
 class LtLocScoreConfig(C.Structure):
@@ -558,6 +569,20 @@ def load_library():
     L.lt_loc_score_get.argtypes = [vp, dp, dp, i32p]
     L.lt_loc_score_get_timers.argtypes = [vp, dp]
     L.lt_fn_loc_score_host.argtypes = score_in + [C.c_int, dp, dp, i32p]
+    bcp = C.POINTER(LtBaConfig)
+    ba_in = [C.c_int, i32p, dp, dp, dp, C.c_int64, dp, i64p, i32p, dp, C.c_int64, dp, i64p, i32p, dp, dp, bcp]
+    L.lt_ba_config_default.argtypes = [bcp]
+    L.lt_ba_config_default.restype = None
+    L.lt_ba_max_images.argtypes = []
+    L.lt_ba_poll_default.argtypes = []
+    L.lt_ba_arrays.argtypes = [vp] + ba_in
+    L.lt_ba_get.argtypes = [vp, dp, dp, dp, dp, dp, dp, i32p, i32p]
+    L.lt_ba_get_timers.argtypes = [vp, dp]
+    L.lt_fn_ba_host.argtypes = ba_in + [C.c_int, dp, dp, dp, dp, dp, dp, i32p, i32p]
+    L.lt_fn_ba_host_error.argtypes = []
+    L.lt_fn_ba_host_error.restype = C.c_char_p
+    L.lt_fn_ba_eval.argtypes = ba_in + [dp, i64p, i32p, dp, dp, dp, dp, C.c_double, dp]
+    L.lt_fn_ba_cholesky.argtypes = [C.c_int64, dp, dp, dp, dp]
     _lib = L
     return L
 

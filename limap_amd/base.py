@@ -115,6 +115,28 @@ class LineTrack:
         self.__dict__.update(other.__dict__)
 
 
+class PointTrack:
+    """pointtrack.h:18-40: a 3D point with its observations (image ids, 2D point ids, 2D points)."""
+
+    def __init__(self, p=None, image_id_list=None, p2d_id_list=None, p2d_list=None):
+        if isinstance(p, dict):  # PointTrack(py::dict) (pointtrack.cc:30-35): a present key overrides
+            d, p = p, p.get("p")
+            image_id_list, p2d_id_list, p2d_list = d.get("image_id_list"), d.get("p2d_id_list"), d.get("p2d_list")
+        elif isinstance(p, PointTrack):
+            p, image_id_list, p2d_id_list, p2d_list = p.p, p.image_id_list, p.p2d_id_list, p.p2d_list
+        self.p = np.zeros(3) if p is None else np.asarray(p, float).reshape(3).copy()
+        self.image_id_list = [int(i) for i in (image_id_list if image_id_list is not None else [])]
+        self.p2d_id_list = [int(i) for i in (p2d_id_list if p2d_id_list is not None else [])]
+        self.p2d_list = [np.asarray(x, float).reshape(2).copy() for x in (p2d_list if p2d_list is not None else [])]
+
+    def count_images(self):  # pointtrack.h: image_id_list.size() (observations, not distinct images)
+        return len(self.image_id_list)
+
+    def as_dict(self):  # pointtrack.cc:21-28
+        return dict(p=self.p.copy(), image_id_list=list(self.image_id_list), p2d_id_list=list(self.p2d_id_list),
+                    p2d_list=[x.copy() for x in self.p2d_list])
+
+
 class CameraView:
     """camera_view.h:56-88 reduced to the undistorted pinhole the hot path requires
     (base_line_triangulator.cc:49)."""

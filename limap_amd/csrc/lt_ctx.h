@@ -281,6 +281,14 @@ struct LocState {  // point-line pose refinement (lt_loc.cpp): the result of the
   DevBuf d_stab, d_sq, d_st, d_table, d_scores, d_inl;
 };
 
+struct BaState {  // bundle adjustment with free poses (lt_ba.cpp): the result of the last lt_ba_arrays
+  double timers[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // lt_ba_get_timers
+  std::vector<double> q, t, pts, params, segs;  // per image, per point track, per line track
+  double cost[2] = {0, 0};
+  int iters = 0, code = 0;
+  DevBuf d_k, d_pose, d_sp, d_st, d_blk, d_idx, d_lin, d_sums, d_S, d_LT, d_vec, d_chunk, d_status;
+};
+
 struct SfmState {  // visual neighbours (lt_sfm.cpp): the result of the last lt_sfm_neighbors
   double timers[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // lt_sfm_get_timers
   std::vector<long long> nb_off;                // per image its neighbours (image indices)
@@ -557,6 +565,7 @@ struct lt_ctx {
   lt_host::VpState vp;
   lt_host::RefineState rf;
   lt_host::LocState lc;
+  lt_host::BaState ba;
   lt_host::SfmState sf;
   lt_host::UdState ud;
   lt_host::S2State s2;

@@ -23,10 +23,31 @@ tracks with patches go to the device in groups of at most `patch_bytes` (FEATURE
 segment cut are restated; **the minimiser is this project's deterministic Levenberg-Marquardt definition: refined lines
 are minimisers of upstream's cost, not the iterates of a particular Ceres run.**
 
-Not built, and rejected with a ValueError that names the key: constant_intrinsics=False, constant_pose=False, point
-tracks, use_ref_descriptor, channels other than 128; use_vp, use_heatmap and use_feature on the hybrid bundle adjustment
-(the first two are no terms of it upstream either).  A track whose cost cannot be evaluated at its initial line (a
-sample line parallel to the projection) ends with TERMINATION 6 and keeps its line, re-cut.
+The bundle adjustment with free poses and point tracks -- the call of
+runners/hypersim/refine_sfm.py --
+
+    cfg_ba = optimize.HybridBAConfig(cfg["refinement"]); cfg_ba.constant_intrinsics = True
+    ba_engine = optimize.solve_hybrid_bundle_adjustment(cfg_ba, imagecols, pointtracks, linetracks)
+    new_imagecols = ba_engine.GetOutputImagecols()
+
+is reached only through `solve_point_bundle_adjustment` and `solve_hybrid_bundle_adjustment`, which validate with a check
+of their own (HybridBAConfig._check_ba); line-only free-pose bundle adjustment is
+`solve_hybrid_bundle_adjustment(cfg, imagecols, {}, linetracks)`.  `solve_line_bundle_adjustment` and
+`HybridBAConfig._check()` keep rejecting constant_pose=False.  With constant_pose=True and line tracks only the two new
+entry points return what `solve_line_bundle_adjustment` returns, bit for bit (they delegate to it).  **Poses, points and
+lines are a stationary point of upstream's cost under upstream's parameterisation, weights and losses, reached from the
+input; they are not the iterates of a Ceres run.  Upstream does not fix the gauge, so compare costs and reprojections,
+never parameters.**  At most BA_MAX_IMAGES (LT_BA_MAX_IMAGES) images may carry residuals.
+
+With constant_pose=True the problem separates per track: the line tracks go through the line refinement above, every
+point track is its own 3-unknown problem under the same loop (its own radius; section 19's termination codes), so every
+point equals its own one-point solve.
+
+Not built, and rejected with a ValueError that names the key: constant_intrinsics=False, constant_pose=False and point
+tracks on solve_line_bundle_adjustment, use_ref_descriptor, channels other than 128; use_vp, use_heatmap and use_feature
+on the hybrid bundle adjustment (the first two are no terms of it upstream either).  A track whose cost cannot be
+evaluated at its initial line (a sample line parallel to the projection) ends with TERMINATION 6 and keeps its line,
+re-cut.
 
 `host_threads=N` on the solve functions runs the documented host path (lt_fn_refine_host: the same inline functions in
 plain C++, bit-identical results) on N OpenMP threads instead of the device; it is a request, never a fallback -- without
@@ -38,14 +59,15 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from .base import Line3d, LineTrack
+from .base import CameraView, ImageCollection, Line3d, LineTrack, PointTrack
 
 __all__ = ["HybridBAConfig", "RefinementConfig", "HybridBAEngine", "RefinementEngine", "Heatmaps",
            "solve_line_bundle_adjustment", "solve_line_refinement", "line_refinement", "TERMINATION", "FeatureMaps",
-           "FEATURE_PATCH_BYTES"]
+           "FEATURE_PATCH_BYTES", "solve_point_bundle_adjustment", "solve_hybrid_bundle_adjustment", "BA_MAX_IMAGES"]
 
 TERMINATION = {0: "max_num_iterations", 1: "radius", 2: "zero_gradient", 3: "pivot", 4: "model_decrease", 5: "constant",
-               6: "evaluation_failed"}
+               6: "evaluation_failed", 7: "no_residuals"}
+BA_MAX_IMAGES = 128  # LT_BA_MAX_IMAGES of include/limap_amd.h: images that may carry residuals in one bundle adjustment
 FEATURE_PATCH_BYTES = 512 << 20  # default budget of the feature term for the patch texels of one native call
 _TEXELS = {"float16": (np.float16, _capi.TEXEL_F16), "float32": (np.float32, _capi.TEXEL_F32)}
 
@@ -151,6 +173,24 @@ class HybridBAConfig(RefinementConfig):
             if not getattr(self, k):
                 raise ValueError(f"limap_amd.optimize: {k}=False is not built (cameras are constant: call "
                                  "set_constant_camera() or set the key)")
+
+    def _check_ba(self):
+        """the check of solve_point_bundle_adjustment / solve_hybrid_bundle_adjustment: poses may be free"""
+        super()._check()
+        if not self.constant_intrinsics:
+            raise ValueError("limap_amd.optimize: constant_intrinsics=False is not built (set cfg_ba.constant_intrinsics = "
+                             "True: the bundle adjustment holds the intrinsics constant)")
+
+    def _ba_struct(self, num_outliers, poll_interval=None, kernel_timers=False):
+        c = _capi.LtBaConfig()
+        _capi.load_library().lt_ba_config_default(C.byref(c))
+        c.geometric_alpha, c.lw_point = float(self.geometric_alpha), float(self.lw_point)
+        c.min_num_images, c.num_outliers_aggregator = int(self.min_num_images), int(num_outliers)
+        c.max_num_iterations = int(self.max_num_iterations)
+        c.constant_intrinsics, c.constant_principal_point = int(self.constant_intrinsics), int(self.constant_principal_point)
+        c.constant_pose, c.constant_point, c.constant_line = int(self.constant_pose), int(self.constant_point), int(self.constant_line)
+        c.poll_interval, c.kernel_timers = int(poll_interval or 0), int(bool(kernel_timers))
+        return c
 
 
 def _track_arrays(tracks):
@@ -384,21 +424,134 @@ def _copy_track(t, line):
     return n
 
 
-class HybridBAEngine:
-    """HybridBAEngine restricted to line tracks with constant cameras.  The solve runs once, with the configuration's
-    num_outliers_aggregator; GetOutputLineTracks with another num_outliers re-cuts the segments from the stored
-    parameters (cut_segment), it does not solve again."""
+def _point_arrays(tracks):
+    """[PointTrack] -> p (T, 3), offsets, image ids, 2D points"""
+    T = len(tracks)
+    off = np.zeros(T + 1, np.int64)
+    for n, t in enumerate(tracks):
+        if len(t.p2d_list) != len(t.image_id_list) or len(t.p2d_id_list) not in (0, len(t.image_id_list)):
+            raise ValueError(f"point track {n}: {len(t.image_id_list)} image ids, {len(t.p2d_id_list)} 2D point ids, "
+                             f"{len(t.p2d_list)} 2D points")
+        off[n + 1] = off[n] + len(t.image_id_list)
+    M = int(off[-1])
+    p3 = np.zeros((max(T, 1), 3)); img = np.zeros(max(M, 1), np.int32); xy = np.zeros((max(M, 1), 2))
+    for n, t in enumerate(tracks):
+        a, b = int(off[n]), int(off[n + 1])
+        p3[n] = np.asarray(t.p, float).reshape(3)
+        img[a:b] = t.image_id_list
+        if b > a:
+            xy[a:b] = np.asarray(t.p2d_list, float).reshape(-1, 2)
+    return p3, off, img, xy
 
-    def __init__(self, cfg, imagecols, linetracks, host_threads=None):
+
+def ba_arrays(cams, points_csr, lines_csr, cfg_struct, host_threads=None, ctx=None):
+    """One call of lt_ba_arrays (device) or lt_fn_ba_host (host_threads given) -> dict: qvec, tvec per image in the
+    order of `cams`, points, params (uvec, wvec) and segments per line track, cost (initial, final), iterations, code."""
+    ids, k, q, t = cams
+    p3, poff, pimg, pxy = points_csr
+    line6, loff, limg, l2, l3 = lines_csr
+    NP, NL, N = len(poff) - 1, len(loff) - 1, len(ids)
+    L = _capi.load_library()
+    p = _capi.ptr
+    qo = np.zeros((max(N, 1), 4)); to = np.zeros((max(N, 1), 3)); po = np.zeros((max(NP, 1), 3))
+    P = np.zeros((max(NL, 1), 6)); seg = np.zeros((max(NL, 1), 6)); cost = np.zeros(2)
+    it = np.zeros(1, np.int32); code = np.zeros(1, np.int32)
+    args = (N, p(ids, C.c_int32), p(k, C.c_double), p(q, C.c_double), p(t, C.c_double), NP, p(p3, C.c_double),
+            p(poff, C.c_int64), p(pimg, C.c_int32), p(pxy, C.c_double), NL, p(line6, C.c_double), p(loff, C.c_int64),
+            p(limg, C.c_int32), p(l2, C.c_double), p(l3, C.c_double), C.byref(cfg_struct))
+    outs = (p(qo, C.c_double), p(to, C.c_double), p(po, C.c_double), p(P, C.c_double), p(seg, C.c_double),
+            p(cost, C.c_double), p(it, C.c_int32), p(code, C.c_int32))
+    timers = None
+    if host_threads is not None:
+        if L.lt_fn_ba_host(*args, int(host_threads), *outs) != 0:
+            raise ValueError("limap_amd.optimize: " + L.lt_fn_ba_host_error().decode(errors="replace"))
+    else:
+        ctx = ctx if ctx is not None else _context()
+        ctx.chk(L.lt_ba_arrays(ctx.h, *args))
+        ctx.chk(L.lt_ba_get(ctx.h, *outs))
+        tm = np.zeros(16)
+        ctx.chk(L.lt_ba_get_timers(ctx.h, p(tm, C.c_double)))
+        names = ("linearize", "blocks", "images", "damp", "schur", "chol", "backsub", "cost", "decide")
+        timers = dict(prepare_ms=float(tm[0]), loop_ms=float(tm[1]), download_ms=float(tm[2]), attempts_enqueued=int(tm[3]),
+                      kernels_ms={"k_ba_" + n: float(tm[4 + i]) for i, n in enumerate(names)})
+    return dict(qvec=qo[:N], tvec=to[:N], points=po[:NP], params=P[:NL], segments=seg[:NL], cost=cost,
+                iterations=int(it[0]), code=int(code[0]), timers=timers)
+
+
+class HybridBAEngine:
+    """HybridBAEngine.  Built by solve_line_bundle_adjustment it is restricted to line tracks with constant cameras;
+    built by solve_point_bundle_adjustment / solve_hybrid_bundle_adjustment (`ba=True`) it takes point tracks too and
+    poses, points and lines are free unless the configuration holds them.  With constant poses
+    the tracks separate: the lines run through the line refinement, every point track through its own solve.  The solve
+    runs once, with the configuration's num_outliers_aggregator; GetOutputLineTracks with another num_outliers re-cuts
+    the segments from the stored parameters (cut_segment), it does not solve again."""
+
+    def __init__(self, cfg, imagecols, linetracks, host_threads=None, pointtracks=None, ba=False, poll_interval=None,
+                 kernel_timers=False):
         self.config, self.host_threads = cfg, host_threads
         self._tracks = dict(enumerate(linetracks)) if not isinstance(linetracks, dict) else dict(linetracks)
         self._keys = sorted(self._tracks)
+        pts = pointtracks if pointtracks is not None else {}
+        pts = dict(enumerate(pts)) if not isinstance(pts, dict) else dict(pts)
+        self._points = {k: (v if hasattr(v, "p2d_list") else PointTrack(v)) for k, v in pts.items()}
+        self._pkeys = sorted(self._points)
+        self._imagecols = imagecols
         self._cams = _camera_arrays({int(i): imagecols.camview(int(i)) for i in imagecols.get_img_ids()})
         self._csr = _track_arrays([self._tracks[k] for k in self._keys])
         self._n_out = int(cfg.num_outliers_aggregator)
-        c = cfg._struct(self._n_out, getattr(cfg, "constant_line", False))
-        self._res = refine_arrays(self._cams, self._csr, c, host_threads)
+        self._ba = None       # the result of lt_ba_arrays / lt_fn_ba_host, where one ran
+        self._moved = set()   # the images that were parameters of the problem
+        free = ba and not cfg.constant_pose
+        if free:
+            pcsr = _point_arrays([self._points[k] for k in self._pkeys])
+            c = cfg._ba_struct(self._n_out, poll_interval, kernel_timers)
+            self._ba = ba_arrays(self._cams, pcsr, self._csr, c, host_threads)
+            n = len(self._keys)
+            # the images that carry a residual block (SetUp's order of blocks does not matter for the set)
+            self._moved = {int(i) for i in self._csr[2][:int(self._csr[1][-1])]}
+            if cfg.lw_point > 0:
+                self._moved |= {int(i) for i in pcsr[2][:int(pcsr[1][-1])]}
+            # the per-track form of result(): one cost, iteration count and code per solve
+            self._res = dict(params=self._ba["params"], segments=self._ba["segments"],
+                             cost=np.tile(self._ba["cost"], (n, 1)), iterations=np.full(n, self._ba["iterations"], np.int32),
+                             codes=np.full(n, self._ba["code"], np.int32), timers=self._ba["timers"])
+        else:
+            if self._keys:
+                c = cfg._struct(self._n_out, getattr(cfg, "constant_line", False))
+                self._res = refine_arrays(self._cams, self._csr, c, host_threads)
+            else:
+                self._res = dict(params=np.zeros((0, 6)), segments=np.zeros((0, 6)), cost=np.zeros((0, 2)),
+                                 iterations=np.zeros(0, np.int32), codes=np.zeros(0, np.int32), timers=None)
+            if ba and self._pkeys:
+                none = (np.zeros((1, 6)), np.zeros(1, np.int64), np.zeros(1, np.int32), np.zeros((1, 4)), np.zeros((1, 6)))
+                self._ba = ba_arrays(self._cams, _point_arrays([self._points[k] for k in self._pkeys]), none,
+                                     cfg._ba_struct(self._n_out), host_threads)
         self._segs = {self._n_out: self._res["segments"]}
+
+    def GetOutputPoints(self):
+        """{track id: p}: the new points (the input's where no solve moved them)"""
+        if self._ba is None:
+            return {k: np.asarray(self._points[k].p, float).copy() for k in self._pkeys}
+        return {k: self._ba["points"][n].copy() for n, k in enumerate(self._pkeys)}
+
+    def GetOutputPointTracks(self):
+        pts = self.GetOutputPoints()
+        return {k: PointTrack(pts[k], self._points[k].image_id_list, self._points[k].p2d_id_list, self._points[k].p2d_list)
+                for k in self._pkeys}
+
+    def GetOutputImagecols(self):
+        """a copy of the collection with the new poses; an image that was no parameter of the problem (constant poses,
+        or no residual block) keeps its view"""
+        views = {}
+        for n, i in enumerate(self._cams[0]):
+            v = self._imagecols.camview(int(i))
+            if int(i) not in self._moved:
+                views[int(i)] = copy.copy(v)
+                continue
+            name = v.image_name() if hasattr(v, "image_name") else "none"
+            hw = (v.h(), v.w()) if hasattr(v, "h") and v.h() is not None else None
+            views[int(i)] = CameraView(self._cams[1][n], self._ba["qvec"][n], self._ba["tvec"][n], name, hw)
+        return ImageCollection(views)
 
     def _segments(self, num_outliers):
         if num_outliers not in self._segs:
@@ -408,9 +561,15 @@ class HybridBAEngine:
         return self._segs[num_outliers]
 
     def result(self, num_outliers=None):
-        """per-track arrays: params (uvec, wvec), segments, cost (initial, final), iterations, codes (TERMINATION)"""
+        """per-track arrays: params (uvec, wvec), segments, cost (initial, final), iterations, codes (TERMINATION).
+        After a free-pose solve also `cost_ba` (initial, final), `iterations_ba`, `code` of the one solve, and `qvec`,
+        `tvec` (images in ascending id), `points`"""
         n_out = self._n_out if num_outliers is None else int(num_outliers)
-        return dict(self._res, segments=self._segments(n_out))
+        r = dict(self._res, segments=self._segments(n_out))
+        if self._ba is not None:  # (with constant poses: of the separated point solves, DESIGN.md section 27)
+            r.update(cost_ba=self._ba["cost"], iterations_ba=self._ba["iterations"], code=self._ba["code"],
+                     qvec=self._ba["qvec"], tvec=self._ba["tvec"], points=self._ba["points"])
+        return r
 
     def GetOutputLineTracks(self, num_outliers=2):
         seg = self._segments(int(num_outliers))
@@ -431,6 +590,33 @@ def solve_line_bundle_adjustment(cfg, imagecols, linetracks, max_num_iterations=
     if len(linetracks) == 0:
         raise ValueError("limap_amd.optimize: no line tracks")
     return HybridBAEngine(ba, imagecols, linetracks, host_threads)
+
+
+def solve_hybrid_bundle_adjustment(cfg, imagecols, pointtracks, linetracks, max_num_iterations=100, host_threads=None,
+                                   poll_interval=None, kernel_timers=False):
+    """optimize/hybrid_bundle_adjustment/solve.py:42-51 with constant intrinsics: poses, points and lines are free unless
+    constant_pose / constant_point / constant_line say otherwise.  Lists or dicts of tracks, as the two Init*Tracks
+    overloads.  poll_interval: attempts enqueued between two reads of the device's status record (no effect on the
+    result).  With constant_pose=True the tracks separate: the lines are solved as solve_line_bundle_adjustment solves
+    them, bit for bit, and every point track by its own solve.  ValueError: constant_intrinsics=False; more than
+    BA_MAX_IMAGES images with residuals (LT_BA_MAX_IMAGES)."""
+    ba = HybridBAConfig(cfg) if isinstance(cfg, dict) or cfg is None else cfg
+    if not isinstance(ba, HybridBAConfig):
+        raise TypeError("cfg must be a dict or a HybridBAConfig")
+    ba._check_ba()
+    ba = copy.copy(ba)  # the caller's configuration is not changed
+    ba.max_num_iterations = int(max_num_iterations)
+    pointtracks = pointtracks if pointtracks is not None else {}
+    linetracks = linetracks if linetracks is not None else {}
+    return HybridBAEngine(ba, imagecols, linetracks, host_threads, pointtracks=pointtracks, ba=True,
+                          poll_interval=poll_interval, kernel_timers=kernel_timers)
+
+
+def solve_point_bundle_adjustment(cfg, imagecols, pointtracks, max_num_iterations=100, host_threads=None,
+                                  poll_interval=None, kernel_timers=False):
+    """optimize/hybrid_bundle_adjustment/solve.py:20-28"""
+    return solve_hybrid_bundle_adjustment(cfg, imagecols, pointtracks, {}, max_num_iterations, host_threads,
+                                          poll_interval, kernel_timers)
 
 
 class RefinementEngine:
