@@ -200,7 +200,7 @@ int make_plan(const Input &in, Plan &pl, std::string &msg) {
     if (k[0] == 0.0 || k[1] == 0.0) { msg = "image " + std::to_string(in.img_ids[r]) + ": a focal length is 0"; return 1; }
     if (q[0] == 0.0 && q[1] == 0.0 && q[2] == 0.0 && q[3] == 0.0) { msg = "image " + std::to_string(in.img_ids[r]) + ": zero quaternion"; return 1; }
     for (int x = 0; x < 4; ++x) pl.kvec[4 * (size_t)c + x] = k[x];
-    lc_normalise_q(q, pl.pose0.data() + 7 * (size_t)c);  // CameraPose's constructor (camera.h:94-95)
+    lm_normalise_q(q, pl.pose0.data() + 7 * (size_t)c);  // CameraPose's constructor (camera.h:94-95)
     for (int x = 0; x < 3; ++x) pl.pose0[7 * (size_t)c + 4 + x] = in.t[3 * r + x];
   }
   for (BaBlk &b : pl.blk) b.cam = row2cam[(size_t)b.cam];
@@ -341,7 +341,7 @@ void host_cost(const BaDev &d, int set, bool with_md, int nt) {
       part[l][1] = md;
     }
     double out[kLcSums];
-    lc_tree_host(part, 2, out);
+    lm_tree_host(part, 2, out);
     d.chunk[ch] = out[0];
     d.chunk[d.n_chunks + ch] = out[1];
   }
@@ -359,7 +359,7 @@ void host_totals(const BaDev &d, double *cost, double *md) {
     part[l][1] = m;
   }
   double out[kLcSums];
-  lc_tree_host(part, 2, out);
+  lm_tree_host(part, 2, out);
   *cost = out[0];
   *md = out[1];
 }
@@ -373,7 +373,7 @@ void host_linearise(const BaDev &d, int cur, int nt) {
     if (st.constant) continue;
     double part[kBaWidth][kRfSums], out[kRfSums];
     for (int l = 0; l < kBaWidth; ++l) ba_struct_part(d, st, l, part[l]);
-    rf_tree_host<kBaWidth>(part, kRfSums, out);
+    lm_tree_host(part, kRfSums, out);
     for (int c = 0; c < 10; ++c) d.V[(size_t)10 * s + c] = out[c];
     for (int c = 0; c < 4; ++c) d.bs[(size_t)4 * s + c] = out[10 + c];
     for (int q = st.p0; q < st.p0 + st.np; ++q) ba_pair_W(d, q);
@@ -382,7 +382,7 @@ void host_linearise(const BaDev &d, int cur, int nt) {
   for (int c = 0; c < d.C; ++c) {
     double part[kLcWidth][kLcSums], out[kLcSums];
     for (int l = 0; l < kBaWave; ++l) ba_cam_part(d, c, l, part[l]);
-    lc_tree_host(part, kLcSums, out);
+    lm_tree_host(part, kLcSums, out);
     for (int x = 0; x < 21; ++x) d.U[(size_t)21 * c + x] = out[x];
     for (int x = 0; x < 6; ++x) d.g[(size_t)6 * c + x] = out[21 + x];
   }
@@ -457,13 +457,13 @@ struct HostPointGroup {
   double cost(const double p[3]) const {
     double part[kBaWidth][kRfSums], out[kRfSums];
     for (int l = 0; l < kBaWidth; ++l) part[l][0] = ba_point_cost_part(d, st, l, p);
-    rf_tree_host<kBaWidth>(part, 1, out);
+    lm_tree_host(part, 1, out);
     return 0.5 * out[0];
   }
   void linearise(const double p[3], double acc[kRfSums]) const {
     double part[kBaWidth][kRfSums];
     for (int l = 0; l < kBaWidth; ++l) ba_point_lin_part(d, st, l, p, part[l]);
-    rf_tree_host<kBaWidth>(part, kRfSums, acc);
+    lm_tree_host(part, kRfSums, acc);
   }
 };
 

@@ -88,57 +88,15 @@ struct BaDev {
   BaStatus *status;
 };
 
-template <int N> LT_HD LcJ<N> rf_inv(const LcJ<N> &a) { return 1.0 / a; }
-typedef LcJ<4> Lc4;
-
-// ceres::QuaternionRotatePoint with every argument of one type (lc_rotate's order)
-template <class T>
-LT_HD void ba_rotate(const T q[4], const T p[3], T r[3]) {
-  const T scale = 1.0 / rf_sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-  const T a = scale * q[0], b = scale * q[1], c = scale * q[2], d = scale * q[3];
-  T uv0 = c * p[2] - d * p[1], uv1 = d * p[0] - b * p[2], uv2 = b * p[1] - c * p[0];
-  uv0 = uv0 + uv0; uv1 = uv1 + uv1; uv2 = uv2 + uv2;
-  r[0] = p[0] + a * uv0; r[1] = p[1] + a * uv1; r[2] = p[2] + a * uv2;
-  r[0] = r[0] + (c * uv2 - d * uv1);
-  r[1] = r[1] + (d * uv0 - b * uv2);
-  r[2] = r[2] + (b * uv1 - c * uv0);
-}
-
 // PointGeometricRefinementFunctor::operator() (cost_functions.h:65-78): WorldToPixel, then the difference
 template <class T>
 LT_HD void ba_point_res(const double k[4], const T q[4], const T t[3], const T X[3], const double o[4], T res[2]) {
   T r[3];
-  ba_rotate<T>(q, X, r);
+  lm_rotate<T, T>(q, X, r);
   const T p2 = r[2] + t[2];
   const T u = (r[0] + t[0]) / p2, v = (r[1] + t[1]) / p2;
   res[0] = (k[0] * u + k[2]) - o[0];
   res[1] = (k[1] * v + k[3]) - o[1];
-}
-
-// Line_WorldToPixel (line_projection.h:14-80) with R and t variables: rf_w2p's products
-template <class T>
-LT_HD void ba_w2p(const double k[4], const T R[9], const T t[3], const T d[3], const T m[3], T c[3]) {
-  T Rd[3], RS[3][3];
-  for (int i = 0; i < 3; ++i) {
-    const T r0 = R[3 * i], r1 = R[3 * i + 1], r2 = R[3 * i + 2];
-    Rd[i] = (d[0] * r0 + d[1] * r1) + d[2] * r2;
-    RS[i][0] = m[2] * r1 + (-m[1]) * r2;
-    RS[i][1] = (-m[2]) * r0 + m[0] * r2;
-    RS[i][2] = m[1] * r0 + (-m[0]) * r1;
-  }
-  const int ii[3] = {2, 0, 1}, jj[3] = {1, 2, 0};
-  T mt[3];
-  for (int e = 0; e < 3; ++e) {
-    const int i = ii[e], j = jj[e];
-    const T rmr = (RS[i][0] * R[3 * j] + RS[i][1] * R[3 * j + 1]) + RS[i][2] * R[3 * j + 2];
-    mt[e] = (rmr - Rd[j] * t[i]) + Rd[i] * t[j];
-  }
-  const double fx = k[0], fy = k[1], cx = k[2], cy = k[3];
-  const T c0 = mt[0] * fy;
-  const T c1 = mt[1] * fx;
-  const T c2 = (mt[2] * fy + (-mt[1]) * cy) * fx + ((-mt[0]) * fy) * cx;
-  const T cn = rf_sqrt(((c0 * c0 + c1 * c1) + c2 * c2) + kEps);
-  c[0] = c0 / cn; c[1] = c1 / cn; c[2] = c2 / cn;
 }
 
 // GeometricRefinementFunctor::operator() with the pose as a variable (line_refinement/cost_functions.h:129-178):
@@ -156,7 +114,7 @@ LT_HD void ba_line_res(const double k[4], const T q[4], const T t[3], const T u[
   const T R[9] = {(((aa + bb) - cc) - ee) * n, (2.0 * (bc - ae)) * n, (2.0 * (ac + be)) * n,
                   (2.0 * (ae + bc)) * n, (((aa - bb) + cc) - ee) * n, (2.0 * (ce - ab)) * n,
                   (2.0 * (be - ac)) * n, (2.0 * (ab + ce)) * n, (((aa - bb) - cc) + ee) * n};
-  ba_w2p<T>(k, R, t, d, m, c);
+  lm_w2p<T, T>(k, R, t, d, m, c);  // R and t carry derivatives
   const T c0 = c[0], c1 = c[1], c2 = c[2];
   const T dn = rf_sqrt((c0 * c0 + c1 * c1) + kEps);
   const T e0 = -(c1 / dn), e1 = c0 / dn;
@@ -191,23 +149,17 @@ LT_HD double ba_cost_term(const BaBlk &b, const double k[4], const double p[7], 
 template <int N>
 LT_HD void ba_pass(const BaBlk &b, const double k[4], const double p[7], const double s[6], double alpha, int which,
                    double r[2], double J[2][4]) {
-  typedef LcJ<N> T;
+  typedef Jet<N> T;
   T q[4], t[3], x[6], res[2];
   for (int i = 0; i < 4; ++i) q[i] = T(p[i]);
   for (int i = 0; i < 3; ++i) t[i] = T(p[4 + i]);
   for (int i = 0; i < 6; ++i) x[i] = T(s[i]);
-  if (which == 0) {  // lc_seed_q: (0, e_i) (x) q
-    q[0].d[0] = -p[1]; q[0].d[1] = -p[2]; q[0].d[2] = -p[3];
-    q[1].d[0] = p[0];  q[1].d[1] = p[3];  q[1].d[2] = -p[2];
-    q[2].d[0] = -p[3]; q[2].d[1] = p[0];  q[2].d[2] = p[1];
-    q[3].d[0] = p[2];  q[3].d[1] = -p[1]; q[3].d[2] = p[0];
+  if (which == 0) {
+    lm_seed_quat(p, q);
   } else if (which == 1) {
     for (int i = 0; i < 3; ++i) t[i].d[i] = 1.0;
-  } else if (b.kind) {  // rf_seed
-    x[0].d[0] = -s[1]; x[0].d[1] = -s[2]; x[0].d[2] = -s[3];
-    x[1].d[0] = s[0];  x[1].d[1] = s[3];  x[1].d[2] = -s[2];
-    x[2].d[0] = -s[3]; x[2].d[1] = s[0];  x[2].d[2] = s[1];
-    x[3].d[0] = s[2];  x[3].d[1] = -s[1]; x[3].d[2] = s[0];
+  } else if (b.kind) {  // rf_seed's directions
+    lm_seed_quat(s, x);
     x[4].d[N - 1] = -s[5];
     x[5].d[N - 1] = s[4];
   } else {
@@ -298,15 +250,7 @@ LT_HD void ba_cam_part(const BaDev &d, int c, int lane, double part[kLcSums]) {
   }
 }
 
-// the damped diagonal entry: h + D^2 / mu, D = clamp(sqrt h, 1e-6, 1e32)
-LT_HD double ba_damp(double h, double mu) {
-  double dg = sqrt(h);
-  dg = dg < kRfDMin ? kRfDMin : (dg > kRfDMax ? kRfDMax : dg);
-  return h + (dg * dg) / mu;
-}
-LT_HD bool ba_pivot_ok(double v) { return v > 0.0 && v < kMaxDist; }
-
-// k_ba_damp: V_s^{-1} of the damped block by its Cholesky factorisation (the recurrence of rf_step), column by column.
+// k_ba_damp: V_s^{-1} of the damped block by its Cholesky factorisation (the recurrence of lm_step), column by column.
 // false: a pivot is not positive or not finite
 LT_HD bool ba_item_vinv(const BaDev &d, int s, double mu) {
   const BaStruct st = d.st[s];
@@ -318,10 +262,10 @@ LT_HD bool ba_item_vinv(const BaDev &d, int s, double mu) {
     for (int j = i; j < 4; ++j, ++o) H[i][j] = H[j][i] = d.V[(size_t)10 * s + o];
   for (int i = 0; i < nd; ++i)
     for (int j = 0; j <= i; ++j) {
-      double sum = i == j ? ba_damp(H[i][i], mu) : H[i][j];
+      double sum = i == j ? lm_damp(H[i][i], mu) : H[i][j];
       for (int k = 0; k < j; ++k) sum = sum - L[i][k] * L[j][k];
       if (i == j) {
-        if (!ba_pivot_ok(sum)) return false;
+        if (!lm_pivot_ok(sum)) return false;
         L[i][i] = sqrt(sum);
       } else {
         L[i][j] = sum / L[j][j];
@@ -371,7 +315,7 @@ LT_HD void ba_item_schur(const BaDev &d, int i, int j, int e, double mu) {
     if (i == j) {
       const int x = a < b ? a : b, y = a < b ? b : a;
       u = d.U[(size_t)21 * i + (x * 6 - (x * (x - 1)) / 2) + (y - x)];
-      if (a == b) u = ba_damp(u, mu);
+      if (a == b) u = lm_damp(u, mu);
     }
     d.S[(size_t)(6 * i + a) * d.n + 6 * j + b] = u - acc;
   } else if (i == j) {
@@ -415,14 +359,14 @@ LT_HD void ba_item_backsub_struct(const BaDev &d, int cur, int s) {
   if (st.constant) {
     for (int c = 0; c < 6; ++c) out[c] = p[c];
   } else if (st.kind) {
-    rf_retract(p, dl, out);
+    RfChart::retract(p, dl, out);
   } else {
     for (int c = 0; c < 3; ++c) out[c] = p[c] + dl[c];
     for (int c = 3; c < 6; ++c) out[c] = 0.0;
   }
 }
 LT_HD void ba_item_backsub_cam(const BaDev &d, int cur, int c) {
-  lc_retract(ba_pose(d, cur, c), d.dc + 6 * c, d.pose + ((size_t)(1 - cur) * d.C + c) * 7);
+  LcChart::retract(ba_pose(d, cur, c), d.dc + 6 * c, d.pose + ((size_t)(1 - cur) * d.C + c) * 7);
 }
 
 // k_ba_cost: block bi's term of the cost at parameter set `set`; with md its term of the model decrease
@@ -498,7 +442,7 @@ inline bool ba_cholesky_host(int n, const double *S, const double *rhs, double *
       double sum = S[(size_t)i * n + j];
       for (int k = 0; k < j; ++k) sum = sum - LT[(size_t)k * n + i] * LT[(size_t)k * n + j];
       if (i == j) {
-        if (!ba_pivot_ok(sum)) return false;
+        if (!lm_pivot_ok(sum)) return false;
         LT[(size_t)j * n + j] = sqrt(sum);
       } else {
         LT[(size_t)j * n + i] = sum / LT[(size_t)j * n + j];
@@ -521,54 +465,28 @@ inline bool ba_cholesky_host(int n, const double *S, const double *rhs, double *
 // ---- constant poses (constant_pose = 1): the tracks separate.  The line side is §19's (lt_refine); every point track is
 // its own 3-unknown problem under §19's loop -- its own radius, §19's termination codes 0-6 -- with the additive chart.
 // G supplies cost(p) and linearise(p, acc) over the track's blocks as values every lane of its 16-lane group holds bit
-// for bit; acc is §19's 14 sums with the fourth direction zero, so rf_step's 4x4 factorisation solves the 3x3 system
-// (its fourth pivot is the clamp's 1e-12 / mu, its fourth step 0)
+// for bit; acc is §19's 14 sums with the fourth direction zero, so lm_step<4> solves the 3x3 system (its fourth pivot is
+// the clamp's 1e-12 / mu, its fourth step 0) and the fourth gradient sum never decides the zero-gradient test (§28)
 struct BaPtOut {
   double p[3], cost0, cost1;
   int iters, code;
 };
 static_assert(sizeof(BaPtOut) == 48, "BaPtOut layout");
 
+struct BaPointChart {
+  static constexpr int kParams = 3, kStep = 4;
+  static LT_HD void retract(const double p[3], const double dl[4], double out[3]) {
+    for (int c = 0; c < 3; ++c) out[c] = p[c] + dl[c];
+  }
+};
+// a constant track reports kRfConstant before a start that is not finite
 template <class G>
 LT_HD void ba_point_lm(G &grp, bool constant, int max_iter, double p[3], double *cost0, double *cost1, int *iters, int *code_out) {
-  double F = grp.cost(p);
+  const double F = grp.cost(p);
   *cost0 = F;
-  int it = 0, code = kRfMaxIter;
-  if (constant) {
-    code = kRfConstant;
-  } else if (!(F <= kMaxDist)) {
-    code = kRfEvalFailed;
-  } else {
-    double mu = kRfMu0, nu = 2.0, acc[kRfSums];
-    bool fresh = true;
-    for (; it < max_iter; ++it) {
-      if (fresh) {
-        grp.linearise(p, acc);
-        if (acc[10] == 0.0 && acc[11] == 0.0 && acc[12] == 0.0) { code = kRfZeroGrad; break; }
-        fresh = false;
-      }
-      double dl[4], md;
-      const int rc = rf_step(acc, mu, dl, &md);
-      if (rc) { code = rc; break; }
-      const double pn[3] = {p[0] + dl[0], p[1] + dl[1], p[2] + dl[2]};
-      const double Fn = grp.cost(pn);
-      const double ratio = (F - Fn) / md;
-      if (ratio > kRfMinRatio) {
-        for (int c = 0; c < 3; ++c) p[c] = pn[c];
-        F = Fn;
-        mu = rf_grow(mu, ratio);
-        nu = 2.0;
-        fresh = true;
-      } else {
-        mu = mu / nu;
-        nu = 2.0 * nu;
-        if (mu < kRfMuMin) { code = kRfRadius; ++it; break; }
-      }
-    }
-  }
-  *cost1 = F;
-  *iters = it;
-  *code_out = code;
+  if (constant) lm_skip(F, kRfConstant, cost1, iters, code_out);
+  else if (!(F <= kMaxDist)) lm_skip(F, kRfEvalFailed, cost1, iters, code_out);
+  else lm_loop<BaPointChart>(grp, F, max_iter, p, cost1, iters, code_out);
 }
 // lane `lane` of a point track's group: its blocks' terms of the cost, and of §19's sums at p
 LT_HD double ba_point_cost_part(const BaDev &d, const BaStruct &st, int lane, const double p[3]) {

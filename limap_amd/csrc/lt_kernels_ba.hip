@@ -27,12 +27,6 @@ namespace lt {
 
 namespace {
 
-__device__ __forceinline__ double wave_sum64(double v) {
-#pragma unroll
-  for (int m = kBaWave / 2; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, kBaWave);
-  return v;
-}
-
 __global__ void __launch_bounds__(256) k_ba_linearize(BaDev d) {
   const BaStatus *st = d.status;
   if (st->done || !st->fresh) return;
@@ -52,10 +46,7 @@ __global__ void __launch_bounds__(64) k_ba_blocks(BaDev d) {
   double part[kRfSums];
   ba_struct_part(d, rec, lane, part);
 #pragma unroll
-  for (int c = 0; c < kRfSums; ++c) {
-#pragma unroll
-    for (int m = kBaWidth / 2; m >= 1; m >>= 1) part[c] = part[c] + __shfl_xor(part[c], m, kBaWidth);
-  }
+  for (int c = 0; c < kRfSums; ++c) part[c] = lm_group_sum<kBaWidth>(part[c]);
   if (live && lane == 0) {
     for (int c = 0; c < 10; ++c) d.V[(size_t)10 * s + c] = part[c];
     for (int c = 0; c < 4; ++c) d.bs[(size_t)4 * s + c] = part[10 + c];
@@ -71,7 +62,7 @@ __global__ void __launch_bounds__(kBaWave) k_ba_images(BaDev d) {
   double part[kLcSums];
   ba_cam_part(d, c, threadIdx.x, part);
 #pragma unroll
-  for (int x = 0; x < kLcSums; ++x) part[x] = wave_sum64(part[x]);
+  for (int x = 0; x < kLcSums; ++x) part[x] = lm_group_sum<kBaWave>(part[x]);
   if (threadIdx.x == 0) {
     for (int x = 0; x < 21; ++x) d.U[(size_t)21 * c + x] = part[x];
     for (int x = 0; x < 6; ++x) d.g[(size_t)6 * c + x] = part[21 + x];
@@ -135,7 +126,7 @@ __global__ void __launch_bounds__(kBaCholThreads) k_ba_chol(BaDev d) {
       sum = s;
     }
     if (tid == 0) {
-      const bool ok = ba_pivot_ok(sum);
+      const bool ok = lm_pivot_ok(sum);
       sbad = ok ? 0 : 1;
       diag = ok ? sqrt(sum) : 1.0;
       if (ok) LT[(size_t)j * n + j] = diag;
@@ -204,8 +195,8 @@ __global__ void __launch_bounds__(kBaWave) k_ba_cost(BaDev d, int mode) {
     cost = cost + c;
     md = md + m;
   }
-  cost = wave_sum64(cost);
-  md = wave_sum64(md);
+  cost = lm_group_sum<kBaWave>(cost);
+  md = lm_group_sum<kBaWave>(md);
   if (threadIdx.x == 0) {
     d.chunk[blockIdx.x] = cost;
     d.chunk[d.n_chunks + blockIdx.x] = md;
@@ -220,8 +211,8 @@ __global__ void __launch_bounds__(kBaWave) k_ba_decide(BaDev d, int mode) {
     cost = cost + d.chunk[c];
     md = md + d.chunk[d.n_chunks + c];
   }
-  cost = wave_sum64(cost);
-  md = wave_sum64(md);
+  cost = lm_group_sum<kBaWave>(cost);
+  md = lm_group_sum<kBaWave>(md);
   if (mode) ba_decide_step(st, cost, md);
   else ba_decide_init(st, cost);
   if (threadIdx.x == 0) *d.status = st;
@@ -233,18 +224,12 @@ struct PointGroup {
   const BaStruct &st;
   int lane;
   __device__ __forceinline__ double cost(const double p[3]) const {
-    double v = ba_point_cost_part(d, st, lane, p);
-#pragma unroll
-    for (int m = kBaWidth / 2; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, kBaWidth);
-    return 0.5 * v;
+    return 0.5 * lm_group_sum<kBaWidth>(ba_point_cost_part(d, st, lane, p));
   }
   __device__ __forceinline__ void linearise(const double p[3], double acc[kRfSums]) const {
     ba_point_lin_part(d, st, lane, p, acc);
 #pragma unroll
-    for (int c = 0; c < kRfSums; ++c) {
-#pragma unroll
-      for (int m = kBaWidth / 2; m >= 1; m >>= 1) acc[c] = acc[c] + __shfl_xor(acc[c], m, kBaWidth);
-    }
+    for (int c = 0; c < kRfSums; ++c) acc[c] = lm_group_sum<kBaWidth>(acc[c]);
   }
 };
 

@@ -15,13 +15,6 @@ namespace lt {
 
 namespace {
 
-// the sum over the wave's lanes, the same bits in every lane (a + b == b + a)
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = kLcWidth / 2; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, kLcWidth);
-  return v;
-}
-
 struct DevGroup {
   const LcDev &dev;
   const LcProb &pr;
@@ -30,12 +23,12 @@ struct DevGroup {
   __device__ __forceinline__ double cost(const double p[7]) const {
     double part = 0.0;
     for (int i = lane; i < pr.n; i += kLcWidth) part = part + lc_cost_term(dev.cfg, k, p, lc_load(dev.tab, dev.stride, pr.b0 + i));
-    return 0.5 * wave_sum(part);
+    return 0.5 * lm_group_sum<kLcWidth>(part);
   }
   __device__ __forceinline__ void linearise(const double p[7], double acc[kLcSums]) const {
     for (int c = 0; c < kLcSums; ++c) acc[c] = 0.0;
     for (int i = lane; i < pr.n; i += kLcWidth) lc_accumulate(dev.cfg, k, p, lc_load(dev.tab, dev.stride, pr.b0 + i), acc);
-    for (int c = 0; c < kLcSums; ++c) acc[c] = wave_sum(acc[c]);
+    for (int c = 0; c < kLcSums; ++c) acc[c] = lm_group_sum<kLcWidth>(acc[c]);
   }
 };
 
@@ -81,7 +74,7 @@ __global__ void __launch_bounds__(kLcWidth) k_loc_score(LcScoreDev dev, double *
     }
   }
   if (dev.sc.want_msac) {
-    part = wave_sum(part);
+    part = lm_group_sum<kLcWidth>(part);
 #pragma unroll
     for (int m = kLcWidth / 2; m >= 1; m >>= 1) {
       in0 += __shfl_xor(in0, m, kLcWidth);

@@ -48,13 +48,6 @@ __global__ void __launch_bounds__(256) k_refine_prep(const double *__restrict__ 
   }
 }
 
-// the sum over the group's kRfWidth lanes, the same bits in every lane (a + b == b + a)
-__device__ __forceinline__ double group_sum(double v) {
-#pragma unroll
-  for (int m = kRfWidth / 2; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, kRfWidth);
-  return v;
-}
-
 // the reductions of rf_lm over the group's lanes: lane l takes supports l, l + kRfWidth, ... in ascending order
 struct DevGroup {
   const RfDev &dev;
@@ -65,7 +58,7 @@ struct DevGroup {
     rf_plucker<double>(p, p + 4, dm);
     double part = 0.0;
     for (int k = lane; k < t.n; k += kRfWidth) part = part + rf_cost_term(rf_load(dev.sup, dev.stride, t.s0 + k), dm, dev.alpha);
-    return 0.5 * group_sum(part);
+    return 0.5 * lm_group_sum<kRfWidth>(part);
   }
   __device__ __forceinline__ void linearise(const double p[6], double acc[kRfSums]) const {
     Rf4 u[4], w[2], dm[6];
@@ -73,7 +66,7 @@ struct DevGroup {
     rf_plucker<Rf4>(u, w, dm);
     for (int c = 0; c < kRfSums; ++c) acc[c] = 0.0;
     for (int k = lane; k < t.n; k += kRfWidth) rf_accumulate(rf_load(dev.sup, dev.stride, t.s0 + k), dm, dev.alpha, acc);
-    for (int c = 0; c < kRfSums; ++c) acc[c] = group_sum(acc[c]);
+    for (int c = 0; c < kRfSums; ++c) acc[c] = lm_group_sum<kRfWidth>(acc[c]);
   }
 };
 
@@ -108,12 +101,6 @@ __global__ void __launch_bounds__(256) k_refine_prep_terms(const double *__restr
   rf_ext_prep(kvec + 4 * (long long)cam, qvec + 4 * (long long)cam, vp_flag[i] != 0, vp3 + 3 * i, ext + i, stride);
 }
 
-__device__ __forceinline__ double group_sum_terms(double v) {
-#pragma unroll
-  for (int m = kRfTermWidth / 2; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, kRfTermWidth);
-  return v;
-}
-
 // DevGroup with the terms' blocks
 template <bool HM, class Tx>
 struct DevGroupTerms {
@@ -135,7 +122,7 @@ struct DevGroupTerms {
       part = part + rf_cost_terms<HM, Tx>(rf_load(dev.sup, dev.stride, s), rf_load_ext(tr.ext, dev.stride, s), grid(s),
                                           tr.cfg, dm, dev.alpha);
     }
-    return 0.5 * group_sum_terms(part);
+    return 0.5 * lm_group_sum<kRfTermWidth>(part);
   }
   __device__ __forceinline__ void linearise(const double p[6], double acc[kRfSums]) const {
     Rf4 u[4], w[2], dm[6];
@@ -147,7 +134,7 @@ struct DevGroupTerms {
       rf_accumulate_terms<HM, Tx>(rf_load(dev.sup, dev.stride, s), rf_load_ext(tr.ext, dev.stride, s), grid(s), tr.cfg, dm,
                                   dev.alpha, acc);
     }
-    for (int c = 0; c < kRfSums; ++c) acc[c] = group_sum_terms(acc[c]);
+    for (int c = 0; c < kRfSums; ++c) acc[c] = lm_group_sum<kRfTermWidth>(acc[c]);
   }
 };
 
@@ -171,15 +158,12 @@ __global__ void __launch_bounds__(kRfBlock) k_refine_lm_terms(RfDev dev, RfDevTe
   }
 }
 
-// the sum over the wave's 64 lanes by the xor tree 32, 16, .. 1, the same bits in every lane
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = kRfFeatLanes / 2; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, kRfFeatLanes);
-  return v;
-}
 __device__ __forceinline__ double wave_get(double v, int src) { return __shfl(v, src, kRfFeatLanes); }
 __device__ __forceinline__ Rf4 wave_get(const Rf4 &a, int src) {
-  return Rf4{wave_get(a.v, src), {wave_get(a.d[0], src), wave_get(a.d[1], src), wave_get(a.d[2], src), wave_get(a.d[3], src)}};
+  Rf4 r;
+  r.v = wave_get(a.v, src);
+  for (int i = 0; i < 4; ++i) r.d[i] = wave_get(a.d[i], src);
+  return r;
 }
 
 // a wave64 on one track with the feature term.  The supports' blocks go to the first kRfTermWidth lanes exactly as in
@@ -209,7 +193,7 @@ struct DevGroupFeat {
         part = part + rf_cost_terms<HM, Tx>(rf_load(dev.sup, dev.stride, s), rf_load_ext(tr.ext, dev.stride, s), grid(s),
                                             tr.cfg, dm, dev.alpha);
       }
-    double total = wave_sum(part);
+    double total = lm_group_sum<kRfFeatLanes>(part);
     if (f.n_smp == 0) return 0.5 * total;
     double d[3], m[3], mine[3] = {0.0, 0.0, 0.0};
     rf_plucker_c<double>(p, p + 4, d, m);
@@ -229,7 +213,7 @@ struct DevGroupFeat {
         const double ct[3] = {wave_get(mine[0], tg), wave_get(mine[1], tg), wave_get(mine[2], tg)};
         double tx, ty;
         const bool ok_tgt = rf_feat_tgt_xy<double>(ct, ft.pairs + 9 * (f.pair0 + (long long)s.ref * f.n_img + tg), x, y, gt, &tx, &ty);
-        const double sq = wave_sum(rf_feat_sq_lane<Tx>(gt, tx, ty, fref, lane));
+        const double sq = lm_group_sum<kRfFeatLanes>(rf_feat_sq_lane<Tx>(gt, tx, ty, fref, lane));
         if (ok_ref && ok_tgt) total = total + rf_rho(s.weight, sq);
         else ok = false;
       }
@@ -247,11 +231,11 @@ struct DevGroupFeat {
         rf_accumulate_terms<HM, Tx>(rf_load(dev.sup, dev.stride, s), rf_load_ext(tr.ext, dev.stride, s), grid(s), tr.cfg, dm,
                                     dev.alpha, acc);
       }
-    for (int c = 0; c < kRfSums; ++c) acc[c] = wave_sum(acc[c]);
+    for (int c = 0; c < kRfSums; ++c) acc[c] = lm_group_sum<kRfFeatLanes>(acc[c]);
     if (f.n_smp == 0) return;
     Rf4 d[3], m[3], mine[3];
     rf_plucker_c<Rf4>(u, w, d, m);
-    for (int c = 0; c < 3; ++c) mine[c] = rf_const(0.0);
+    for (int c = 0; c < 3; ++c) mine[c] = Rf4(0.0);
     const RfFImg *imgs = ft.imgs + f.img0;
     if (lane < f.n_img) rf_w2p<Rf4>(ft.views[imgs[lane].cam], d, m, mine);
     for (int si = 0; si < f.n_smp; ++si) {
@@ -271,7 +255,7 @@ struct DevGroupFeat {
         double blk[kRfFeatSums];
         for (int c = 0; c < kRfFeatSums; ++c) blk[c] = 0.0;
         rf_feat_block_lane<Tx>(gt, tx, ty, ref, lane, blk);
-        for (int c = 0; c < kRfFeatSums; ++c) blk[c] = wave_sum(blk[c]);
+        for (int c = 0; c < kRfFeatSums; ++c) blk[c] = lm_group_sum<kRfFeatLanes>(blk[c]);
         if (ok_ref && ok_tgt) {  // a failed block adds nothing
           const double rho1 = rf_rho1(s.weight, blk[kRfSums]);
           for (int c = 0; c < kRfSums; ++c) acc[c] = acc[c] + rho1 * blk[c];

@@ -92,7 +92,7 @@ int make_plan(int64_t P, const double *kvec4, const double *qvec4, const double 
     const double *q = qvec4 + 4 * n;
     if (q[0] == 0.0 && q[1] == 0.0 && q[2] == 0.0 && q[3] == 0.0) { msg = "problem " + std::to_string(n) + ": zero quaternion"; return 1; }
     LcOut &o = pl.init[(size_t)n];
-    lc_normalise_q(q, o.q);
+    lm_normalise_q(q, o.q);
     for (int c2 = 0; c2 < 3; ++c2) o.t[c2] = tvec3[3 * n + c2];
     o.cost0 = o.cost1 = 0.0;
     o.iters = 0;
@@ -168,7 +168,7 @@ struct HostGroup {
       part[l][0] = s;
     }
     double out[kLcSums];
-    lc_tree_host(part, 1, out);
+    lm_tree_host(part, 1, out);
     return 0.5 * out[0];
   }
   // res: 4 slots per block (tests)
@@ -179,7 +179,7 @@ struct HostGroup {
       for (int i = l; i < pr.n; i += kLcWidth)
         lc_accumulate(cfg, k, p, lc_load(tab, stride, pr.b0 + i), part[l], res ? res + 4 * (size_t)i : nullptr);
     }
-    lc_tree_host(part, kLcSums, acc);
+    lm_tree_host(part, kLcSums, acc);
   }
   void linearise(const double p[7], double acc[kLcSums]) const { linearise_res(p, acc, nullptr); }
 };
@@ -332,7 +332,7 @@ void score_host(const ScorePlan &pl, int n_threads, double *table, double *score
     }
     if (d.sc.want_msac) {
       double out[kLcSums];
-      lc_tree_host(part, 1, out);
+      lm_tree_host(part, 1, out);
       if (scores) scores[h] = out[0];
       if (inliers) { inliers[2 * h] = in[0]; inliers[2 * h + 1] = in[1]; }
     }

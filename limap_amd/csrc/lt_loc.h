@@ -30,6 +30,7 @@ namespace lt {
 constexpr int kLcWidth = 64;    // lanes per problem: one wave64 (the choice: DESIGN §25)
 constexpr int kLcFields = 12;   // doubles per residual block (SoA): s3d[3], e3d[3], s2d[2], e2d[2], loss weight, kind
 constexpr int kLcSums = 27;     // H upper triangle by rows (21), then g (6)
+static_assert(kLcSums == lm_sums(6), "the sums of six unknowns");
 constexpr double kLcEps8 = 1e-8;  // upstream's `+ 1e-8`
 constexpr double kLcAlpha = 10.0; // Ceres_Compute2DWeight's default, which every caller gets
 constexpr double kLcDblMin = 2.2250738585072014e-308;
@@ -62,57 +63,16 @@ struct LcOut {
 };
 static_assert(sizeof(LcOut) == 80, "LcOut layout");
 
-// ---- forward-mode scalar along N local directions.  A linearisation runs the chain twice with N = 3 -- the rotation's
-// directions with the translation a plain double, then the reverse -- so that no expression carries six derivatives ----
-template <int N>
-struct LcJ {
-  double v, d[N];
-  LcJ() = default;
-  LT_HD LcJ(double x) : v(x) {
-    for (int i = 0; i < N; ++i) d[i] = 0.0;
-  }
-};
-#define LC_J template <int N> LT_HD LcJ<N>
-LC_J operator+(const LcJ<N> &a, const LcJ<N> &b) { LcJ<N> r; r.v = a.v + b.v; for (int i = 0; i < N; ++i) r.d[i] = a.d[i] + b.d[i]; return r; }
-LC_J operator-(const LcJ<N> &a, const LcJ<N> &b) { LcJ<N> r; r.v = a.v - b.v; for (int i = 0; i < N; ++i) r.d[i] = a.d[i] - b.d[i]; return r; }
-LC_J operator-(const LcJ<N> &a) { LcJ<N> r; r.v = -a.v; for (int i = 0; i < N; ++i) r.d[i] = -a.d[i]; return r; }
-LC_J operator*(const LcJ<N> &a, const LcJ<N> &b) { LcJ<N> r; r.v = a.v * b.v; for (int i = 0; i < N; ++i) r.d[i] = a.v * b.d[i] + a.d[i] * b.v; return r; }
-LC_J operator/(const LcJ<N> &a, const LcJ<N> &b) { LcJ<N> r; r.v = a.v / b.v; for (int i = 0; i < N; ++i) r.d[i] = (a.d[i] - r.v * b.d[i]) / b.v; return r; }
-LC_J operator+(const LcJ<N> &a, double b) { LcJ<N> r = a; r.v = a.v + b; return r; }
-LC_J operator+(double b, const LcJ<N> &a) { LcJ<N> r = a; r.v = b + a.v; return r; }
-LC_J operator-(const LcJ<N> &a, double b) { LcJ<N> r = a; r.v = a.v - b; return r; }
-LC_J operator-(double b, const LcJ<N> &a) { LcJ<N> r; r.v = b - a.v; for (int i = 0; i < N; ++i) r.d[i] = -a.d[i]; return r; }
-LC_J operator*(const LcJ<N> &a, double b) { LcJ<N> r; r.v = a.v * b; for (int i = 0; i < N; ++i) r.d[i] = a.d[i] * b; return r; }
-LC_J operator*(double b, const LcJ<N> &a) { return a * b; }
-LC_J operator/(const LcJ<N> &a, double b) { LcJ<N> r; r.v = a.v / b; for (int i = 0; i < N; ++i) r.d[i] = a.d[i] / b; return r; }
-LC_J operator/(double a, const LcJ<N> &b) { LcJ<N> r; r.v = a / b.v; for (int i = 0; i < N; ++i) r.d[i] = (-(r.v * b.d[i])) / b.v; return r; }
-LC_J rf_sqrt(const LcJ<N> &a) { LcJ<N> r; r.v = sqrt(a.v); const double h = 0.5 / r.v; for (int i = 0; i < N; ++i) r.d[i] = a.d[i] * h; return r; }
-LC_J rf_abs(const LcJ<N> &a) { return a.v < 0.0 ? -a : a; }
-LC_J rf_exp(const LcJ<N> &a) { LcJ<N> r; r.v = lt_exp(a.v); for (int i = 0; i < N; ++i) r.d[i] = r.v * a.d[i]; return r; }
-#undef LC_J
-template <int N> LT_HD double rf_val(const LcJ<N> &a) { return a.v; }
-template <int N> LT_HD void rf_set(LcJ<N> &a, double v) { a = LcJ<N>(v); }
-typedef LcJ<3> Lc3;
+// the forward-mode scalar (lt_lm.h).  A linearisation runs the chain twice with three directions -- the rotation's with
+// the translation a plain double, then the reverse -- so that no expression carries six derivatives
+typedef Jet<3> Lc3;
 
 // ---- point_projection.h ----
-// ceres::QuaternionRotatePoint: normalises, then UnitQuaternionRotatePoint
-template <class TQ>
-LT_HD void lc_rotate(const TQ q[4], const double p[3], TQ r[3]) {
-  const TQ scale = 1.0 / rf_sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-  const TQ a = scale * q[0], b = scale * q[1], c = scale * q[2], d = scale * q[3];
-  TQ uv0 = c * p[2] - d * p[1], uv1 = d * p[0] - b * p[2], uv2 = b * p[1] - c * p[0];
-  uv0 = uv0 + uv0; uv1 = uv1 + uv1; uv2 = uv2 + uv2;
-  r[0] = p[0] + a * uv0; r[1] = p[1] + a * uv1; r[2] = p[2] + a * uv2;
-  r[0] = r[0] + (c * uv2 - d * uv1);
-  r[1] = r[1] + (d * uv0 - b * uv2);
-  r[2] = r[2] + (b * uv1 - c * uv0);
-}
-
 // WorldToPixel (:45-57)
 template <class TQ, class TT, class T>
 LT_HD void lc_world_to_pixel(const double k[4], const TQ q[4], const TT t[3], const double xyz[3], T xy[2]) {
   TQ r[3];
-  lc_rotate<TQ>(q, xyz, r);
+  lm_rotate<TQ, double>(q, xyz, r);
   const T p2 = r[2] + t[2];
   const T u = (r[0] + t[0]) / p2, v = (r[1] + t[1]) / p2;
   xy[0] = k[0] * u + k[2];
@@ -337,12 +297,6 @@ LT_HD void lc_loss(const LcCfg &cfg, double s, double *rho, double *rho1) {
 }
 
 // the pose as the minimiser carries it: p = (q w x y z, t)
-LT_HD void lc_seed_q(const double p[7], Lc3 q[4]) {
-  q[0].v = p[0]; q[0].d[0] = -p[1]; q[0].d[1] = -p[2]; q[0].d[2] = -p[3];
-  q[1].v = p[1]; q[1].d[0] = p[0];  q[1].d[1] = p[3];  q[1].d[2] = -p[2];
-  q[2].v = p[2]; q[2].d[0] = -p[3]; q[2].d[1] = p[0];  q[2].d[2] = p[1];
-  q[3].v = p[3]; q[3].d[0] = p[2];  q[3].d[1] = -p[1]; q[3].d[2] = p[0];
-}
 LT_HD void lc_seed_t(const double p[7], Lc3 t[3]) {
   for (int i = 0; i < 3; ++i) {
     t[i] = Lc3(p[4 + i]);
@@ -392,7 +346,7 @@ LT_HD void lc_accumulate(const LcCfg &cfg, const double k[4], const double p[7],
   {
     Lc3 q[4], rr[4];
     for (int i = 0; i < 4; ++i) rr[i] = Lc3(0.0);
-    lc_seed_q(p, q);
+    lm_seed_quat(p, q);
     n = lc_residual<Lc3, double, Lc3>(cfg, k, q, p + 4, b, rr);
     for (int i = 0; i < 4; ++i) {
       r[i] = rr[i].v;
@@ -414,128 +368,28 @@ LT_HD void lc_accumulate(const LcCfg &cfg, const double k[4], const double p[7],
   else lc_block_sums<4>(cfg, b.w, J, r, acc);
 }
 
-// the retraction: q+ = normalize((1, dq) (x) q), t+ = t + dt
-LT_HD void lc_retract(const double p[7], const double dl[6], double out[7]) {
-  const double q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
-  const double r0 = ((q0 - dl[0] * q1) - dl[1] * q2) - dl[2] * q3;
-  const double r1 = ((q1 + dl[0] * q0) + dl[1] * q3) - dl[2] * q2;
-  const double r2 = ((q2 - dl[0] * q3) + dl[1] * q0) + dl[2] * q1;
-  const double r3 = ((q3 + dl[0] * q2) - dl[1] * q1) + dl[2] * q0;
-  const double nu = sqrt(((r0 * r0 + r1 * r1) + r2 * r2) + r3 * r3);
-  out[0] = r0 / nu; out[1] = r1 / nu; out[2] = r2 / nu; out[3] = r3 / nu;
-  for (int i = 0; i < 3; ++i) out[4 + i] = p[4 + i] + dl[3 + i];
-}
+// the chart of a pose: q+ = normalize((1, dq) (x) q), t+ = t + dt
+struct LcChart {
+  static constexpr int kParams = 7, kStep = 6;
+  static LT_HD void retract(const double p[7], const double dl[6], double out[7]) {
+    lm_retract_quat(p, dl, out);
+    for (int i = 0; i < 3; ++i) out[4 + i] = p[4 + i] + dl[3 + i];
+  }
+};
 
-// rf_step with six unknowns: (H + D^2 / mu) dl = -g by a 6x6 Cholesky factorisation
-LT_HD int lc_step(const double acc[kLcSums], double mu, double dl[6], double *md) {
-  double H[6][6], L[6][6], y[6];
-  int o = 0;
-  for (int i = 0; i < 6; ++i)
-    for (int j = i; j < 6; ++j, ++o) H[i][j] = H[j][i] = acc[o];
-  const double *g = acc + 21;
-  for (int i = 0; i < 6; ++i) {
-    double dg = sqrt(H[i][i]);
-    dg = dg < kRfDMin ? kRfDMin : (dg > kRfDMax ? kRfDMax : dg);
-    for (int j = 0; j <= i; ++j) {
-      double sum = i == j ? H[i][i] + (dg * dg) / mu : H[i][j];
-      for (int k = 0; k < j; ++k) sum = sum - L[i][k] * L[j][k];
-      if (i == j) {
-        if (!(sum > 0.0) || !(sum < kMaxDist)) return kRfBadPivot;
-        L[i][i] = sqrt(sum);
-      } else {
-        L[i][j] = sum / L[j][j];
-      }
-    }
-  }
-  for (int i = 0; i < 6; ++i) {
-    double sum = -g[i];
-    for (int k = 0; k < i; ++k) sum = sum - L[i][k] * y[k];
-    y[i] = sum / L[i][i];
-  }
-  for (int i = 5; i >= 0; --i) {
-    double sum = y[i];
-    for (int k = i + 1; k < 6; ++k) sum = sum - L[k][i] * dl[k];
-    dl[i] = sum / L[i][i];
-  }
-  double gd = 0.0, dhd = 0.0;
-  for (int i = 0; i < 6; ++i) {
-    gd = gd + g[i] * dl[i];
-    double hd = 0.0;
-    for (int j = 0; j < 6; ++j) hd = hd + H[i][j] * dl[j];
-    dhd = dhd + dl[i] * hd;
-  }
-  *md = -(gd + 0.5 * dhd);
-  if (!(*md > 0.0) || !(*md < kMaxDist)) return kRfBadModel;
-  return 0;
-}
-
-// rf_lm with the pose as the unknown.  G supplies cost(p) and linearise(p, acc) as values every lane of the group holds
-// bit for bit, so every branch is uniform over the group.  A problem without blocks is not optimised; one whose cost at
-// the initial pose is not finite (a point in the camera's plane) ends with kRfEvalFailed; both keep the pose
+// lm_loop with the pose as the unknown.  A problem without blocks is not optimised and its cost is not evaluated; one
+// whose cost at the initial pose is not finite (a point in the camera's plane) ends with kRfEvalFailed; both keep the pose
 template <class G>
 LT_HD void lc_lm(G &grp, int n_blocks, int max_iter, double p[7], double *cost0, double *cost1, int *iters, int *code_out) {
   if (n_blocks <= 0) {
-    *cost0 = 0.0; *cost1 = 0.0; *iters = 0; *code_out = kLcNoResiduals;
+    *cost0 = 0.0;
+    lm_skip(0.0, kLcNoResiduals, cost1, iters, code_out);
     return;
   }
-  double F = grp.cost(p);
+  const double F = grp.cost(p);
   *cost0 = F;
-  if (!(F <= kMaxDist)) {
-    *cost1 = F; *iters = 0; *code_out = kRfEvalFailed;
-    return;
-  }
-  int it = 0, code = kRfMaxIter;
-  double mu = kRfMu0, nu = 2.0;
-  double acc[kLcSums];
-  bool fresh = true;
-  for (; it < max_iter; ++it) {
-    if (fresh) {
-      grp.linearise(p, acc);
-      bool zero = true;
-      for (int c = 0; c < 6; ++c) zero = zero && acc[21 + c] == 0.0;
-      if (zero) { code = kRfZeroGrad; break; }
-      fresh = false;
-    }
-    double dl[6], md;
-    const int rc = lc_step(acc, mu, dl, &md);
-    if (rc) { code = rc; break; }
-    double pn[7];
-    lc_retract(p, dl, pn);
-    const double Fn = grp.cost(pn);
-    const double ratio = (F - Fn) / md;
-    if (ratio > kRfMinRatio) {
-      for (int c = 0; c < 7; ++c) p[c] = pn[c];
-      F = Fn;
-      mu = rf_grow(mu, ratio);
-      nu = 2.0;
-      fresh = true;
-    } else {
-      mu = mu / nu;
-      nu = 2.0 * nu;
-      if (mu < kRfMuMin) { code = kRfRadius; ++it; break; }
-    }
-  }
-  *cost1 = F;
-  *iters = it;
-  *code_out = code;
-}
-
-// CameraPose's constructor normalises its quaternion once (camera.h:94-95), as rf_view_matrix does
-LT_HD void lc_normalise_q(const double q4[4], double q[4]) {
-  const double n0 = sqrt((q4[0] * q4[0] + q4[2] * q4[2]) + (q4[1] * q4[1] + q4[3] * q4[3]));
-  for (int i = 0; i < 4; ++i) q[i] = n0 > 0.0 ? q4[i] / n0 : q4[i];
-}
-
-// the fixed xor tree over kLcWidth partial sums (host twin of the shuffles of k_loc_lm)
-inline void lc_tree_host(double part[kLcWidth][kLcSums], int n_sums, double out[kLcSums]) {
-  for (int m = kLcWidth / 2; m >= 1; m >>= 1) {
-    double nxt[kLcWidth][kLcSums];
-    for (int l = 0; l < kLcWidth; ++l)
-      for (int c = 0; c < n_sums; ++c) nxt[l][c] = part[l][c] + part[l ^ m][c];
-    for (int l = 0; l < kLcWidth; ++l)
-      for (int c = 0; c < n_sums; ++c) part[l][c] = nxt[l][c];
-  }
-  for (int c = 0; c < n_sums; ++c) out[c] = part[0][c];
+  if (!(F <= kMaxDist)) lm_skip(F, kRfEvalFailed, cost1, iters, code_out);
+  else lm_loop<LcChart>(grp, F, max_iter, p, cost1, iters, code_out);
 }
 
 // ---- pose scoring: JointPoseEstimator::EvaluateModelOnPoint (estimators/absolute_pose/joint_pose_estimator.cc:176-251)
@@ -603,7 +457,7 @@ struct LcPose {
   bool nan;
 };
 LT_HD void lc_pose_build(const double k[4], const double q4[4], const double t3[3], LcPose *ps) {
-  lc_normalise_q(q4, ps->p);
+  lm_normalise_q(q4, ps->p);
   for (int i = 0; i < 3; ++i) ps->p[4 + i] = t3[i];
   const double qn = sqrt((ps->p[0] * ps->p[0] + ps->p[2] * ps->p[2]) + (ps->p[1] * ps->p[1] + ps->p[3] * ps->p[3]));
   const double tn = sqrt((t3[0] * t3[0] + t3[1] * t3[1]) + t3[2] * t3[2]);

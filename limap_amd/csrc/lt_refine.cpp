@@ -415,7 +415,7 @@ struct HostGroup {
       part[l][0] = s;
     }
     double out[kRfSums];
-    rf_tree_host<kRfWidth>(part, 1, out);
+    lm_tree_host(part, 1, out);
     return 0.5 * out[0];
   }
   void linearise(const double p[6], double acc[kRfSums]) const {
@@ -427,7 +427,7 @@ struct HostGroup {
       for (int c = 0; c < kRfSums; ++c) part[l][c] = 0.0;
       for (int k = l; k < t.n; k += kRfWidth) rf_accumulate(rf_load(tab, stride, t.s0 + k), dm, alpha, part[l]);
     }
-    rf_tree_host<kRfWidth>(part, kRfSums, acc);
+    lm_tree_host(part, kRfSums, acc);
   }
 };
 
@@ -457,7 +457,7 @@ struct HostGroupTerms {
       part[l][0] = s;
     }
     double out[kRfSums];
-    rf_tree_host<kRfTermWidth>(part, 1, out);
+    lm_tree_host(part, 1, out);
     return 0.5 * out[0];
   }
   // res: the residuals of every support, 3 + n_samples each (tests)
@@ -474,7 +474,7 @@ struct HostGroupTerms {
                                          tp.cfg, dm, alpha, part[l],
                                          res ? res + (size_t)k * (3 + (size_t)tp.cfg.n_samples) : nullptr) && ok;
     }
-    rf_tree_host<kRfTermWidth>(part, kRfSums, acc);
+    lm_tree_host(part, kRfSums, acc);
     return ok;
   }
   void linearise(const double p[6], double acc[kRfSums]) const { linearise_res(p, acc, nullptr); }
@@ -496,7 +496,7 @@ void with_host_group(const double *tab, const double *ext, long long stride, con
   }
 }
 
-// the host twin of a wave of k_refine_lm_feat: the lanes are a loop, the tree is rf_tree64_host
+// the host twin of a wave of k_refine_lm_feat: the lanes are a loop, the tree is lm_tree_host
 template <bool HM, class Tx>
 struct HostGroupFeat {
   HostGroupTerms<HM, Tx> sup;  // the supports' blocks: lanes 0 .. kRfTermWidth - 1
@@ -517,7 +517,7 @@ struct HostGroupFeat {
       part[l][0] = s;
     }
     double out;
-    rf_tree64_host<1>(part, 1, &out);
+    lm_tree_host(part, 1, &out);
     return out;
   }
   double cost(const double p[6]) const {
@@ -540,7 +540,7 @@ struct HostGroupFeat {
         double tx, ty, part[kRfFeatLanes][1], sq;
         const bool ok_tgt = rf_feat_tgt_xy<double>(c[tg], pair(s.ref, tg), x, y, gt, &tx, &ty);
         for (int l = 0; l < kRfFeatLanes; ++l) part[l][0] = rf_feat_sq_lane<Tx>(gt, tx, ty, fref[l], l);
-        rf_tree64_host<1>(part, 1, &sq);
+        lm_tree_host(part, 1, &sq);
         if (ok_ref && ok_tgt) total = total + rf_rho(s.weight, sq);
         else ok = false;
       }
@@ -561,7 +561,7 @@ struct HostGroupFeat {
             rf_accumulate_terms<HM, Tx>(rf_load(sup.tab, sup.stride, sup.t.s0 + k), rf_load_ext(sup.ext, sup.stride, sup.t.s0 + k),
                                         sup.grid(sup.t.s0 + k), sup.tp.cfg, dm, sup.alpha, part[l]);
       }
-      rf_tree64_host<kRfSums>(part, kRfSums, acc);
+      lm_tree_host(part, kRfSums, acc);
     }
     if (f.n_smp == 0) return true;
     Rf4 d[3], m[3];
@@ -587,7 +587,7 @@ struct HostGroupFeat {
           for (int o = 0; o < kRfFeatSums; ++o) part[l][o] = 0.0;
           rf_feat_block_lane<Tx>(gt, tx, ty, ref[l], l, part[l], res ? res + kRfChannels * b + 2 * (size_t)l : nullptr);
         }
-        rf_tree64_host<kRfFeatSums>(part, kRfFeatSums, blk);
+        lm_tree_host(part, kRfFeatSums, blk);
         if (failed) failed[b] = (ok_ref && ok_tgt) ? 0 : 1;
         if (ok_ref && ok_tgt) {
           const double rho1 = rf_rho1(s.weight, blk[kRfSums]);

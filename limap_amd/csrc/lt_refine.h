@@ -33,7 +33,7 @@
 // conversion is defined.  The minimiser is this project's own definition, not Ceres' iterates.
 #pragma once
 
-#include "lt_geom.h"
+#include "lt_lm.h"
 
 namespace lt {
 
@@ -41,24 +41,11 @@ constexpr int kRfWidth = 16;            // lanes of a wave64 that work on one tr
 constexpr int kRfBlock = 64;            // lanes per workgroup: one wave, four tracks
 constexpr int kRfFields = 23;           // doubles per support (SoA over the scene's supports): A[18], x1 y1 x2 y2, weight
 constexpr double kRfCauchyB = 0.0625;   // CauchyLoss(0.25): b = a^2 (refinement_config.h:21)
-constexpr double kRfMu0 = 1e4;          // initial trust-region radius (Ceres' default)
-constexpr double kRfMuMax = 1e16, kRfMuMin = 1e-32;
-constexpr double kRfMinRatio = 1e-3;    // min_relative_decrease
-constexpr double kRfDMin = 1e-6, kRfDMax = 1e32;  // min / max_lm_diagonal
 constexpr int kRfTermWidth = 16;        // lanes per track of k_refine_lm_terms and of its host twin (the choice: DESIGN §19)
 constexpr int kRfExtFields = 8;         // doubles per support of the terms' table: unit qvec[4], VP direction[3], VP flag
 constexpr double kRfHuberA = 0.001;     // HuberLoss(0.001) (refinement_config.h:23)
 
-// termination codes of a track (lt_refine_get)
-enum RfCode : int {
-  kRfMaxIter = 0,    // max_num_iterations reached
-  kRfRadius = 1,     // the radius fell below 1e-32
-  kRfZeroGrad = 2,   // g == 0
-  kRfBadPivot = 3,   // a Cholesky pivot is not positive or not finite
-  kRfBadModel = 4,   // the model decrease is not positive or not finite
-  kRfConstant = 5,   // constant_line, or fewer than min_num_images images: not optimised, segment re-cut
-  kRfEvalFailed = 6, // the cost at the initial point is not finite (a heatmap sample failed): not optimised, segment re-cut
-};
+// the termination codes of a track (lt_refine_get) are RfCode (lt_lm.h)
 
 // a track as the kernels see it: supports [s0, s0 + n) of the scene's supports (residual order), line, flags
 struct RfTrack {
@@ -141,48 +128,8 @@ LT_HD double lt_log(double y) {
   return ed * 6.93147180369123816490e-01 + (lf + ed * 1.90821492927058770002e-10);
 }
 
-// ---- forward-mode scalar: a value and its derivatives along the four local directions (du1, du2, du3, dw) ----
-struct Rf4 {
-  double v, d[4];
-};
-LT_HD Rf4 rf_const(double v) { return Rf4{v, {0.0, 0.0, 0.0, 0.0}}; }
-LT_HD double rf_val(double a) { return a; }
-LT_HD double rf_val(const Rf4 &a) { return a.v; }
-LT_HD Rf4 operator+(const Rf4 &a, const Rf4 &b) {
-  return Rf4{a.v + b.v, {a.d[0] + b.d[0], a.d[1] + b.d[1], a.d[2] + b.d[2], a.d[3] + b.d[3]}};
-}
-LT_HD Rf4 operator-(const Rf4 &a, const Rf4 &b) {
-  return Rf4{a.v - b.v, {a.d[0] - b.d[0], a.d[1] - b.d[1], a.d[2] - b.d[2], a.d[3] - b.d[3]}};
-}
-LT_HD Rf4 operator-(const Rf4 &a) { return Rf4{-a.v, {-a.d[0], -a.d[1], -a.d[2], -a.d[3]}}; }
-LT_HD Rf4 operator*(const Rf4 &a, const Rf4 &b) {
-  return Rf4{a.v * b.v,
-             {a.v * b.d[0] + a.d[0] * b.v, a.v * b.d[1] + a.d[1] * b.v, a.v * b.d[2] + a.d[2] * b.v,
-              a.v * b.d[3] + a.d[3] * b.v}};
-}
-LT_HD Rf4 operator/(const Rf4 &a, const Rf4 &b) {
-  const double q = a.v / b.v;
-  return Rf4{q, {(a.d[0] - q * b.d[0]) / b.v, (a.d[1] - q * b.d[1]) / b.v, (a.d[2] - q * b.d[2]) / b.v,
-                 (a.d[3] - q * b.d[3]) / b.v}};
-}
-LT_HD Rf4 operator+(const Rf4 &a, double b) { return Rf4{a.v + b, {a.d[0], a.d[1], a.d[2], a.d[3]}}; }
-LT_HD Rf4 operator*(const Rf4 &a, double b) { return Rf4{a.v * b, {a.d[0] * b, a.d[1] * b, a.d[2] * b, a.d[3] * b}}; }
-LT_HD Rf4 operator*(double b, const Rf4 &a) { return a * b; }
-LT_HD Rf4 operator-(double b, const Rf4 &a) { return Rf4{b - a.v, {-a.d[0], -a.d[1], -a.d[2], -a.d[3]}}; }
-LT_HD Rf4 rf_sqrt(const Rf4 &a) {
-  const double s = sqrt(a.v), h = 0.5 / s;
-  return Rf4{s, {a.d[0] * h, a.d[1] * h, a.d[2] * h, a.d[3] * h}};
-}
-LT_HD double rf_sqrt(double a) { return sqrt(a); }
-LT_HD Rf4 rf_abs(const Rf4 &a) { return a.v < 0.0 ? -a : a; }  // the Jet rule: +1 at 0
-LT_HD double rf_abs(double a) { return a < 0.0 ? -a : a; }
-LT_HD Rf4 rf_exp(const Rf4 &a) {
-  const double e = lt_exp(a.v);
-  return Rf4{e, {e * a.d[0], e * a.d[1], e * a.d[2], e * a.d[3]}};
-}
-LT_HD double rf_exp(double a) { return lt_exp(a); }
-LT_HD void rf_set(double &a, double v) { a = v; }
-LT_HD void rf_set(Rf4 &a, double v) { a = rf_const(v); }
+// the forward-mode scalar (lt_lm.h) along the four local directions (du1, du2, du3, dw)
+typedef Jet<4> Rf4;
 
 // MinimalPluckerToPlucker (line_transforms.h:8-29): dm = (d, m) from uvec (w, x, y, z) and wvec
 template <class T>
@@ -206,6 +153,7 @@ LT_HD void rf_plucker(const T u[4], const T w[2], T dm[6]) {
 // Ceres' QuaternionToRotation
 // A[f] goes to out[f * stride] (the SoA table directly: no private array of the lane)
 LT_HD void rf_view_matrix(const double *k4, const double *q4, const double *t3, double *out, long long stride) {
+  // lm_normalise_q's expressions, written out: through the call k_refine_prep needs 70 registers for 62 and loses a wave
   double q[4];
   const double n0 = sqrt((q4[0] * q4[0] + q4[2] * q4[2]) + (q4[1] * q4[1] + q4[3] * q4[3]));
 #pragma unroll
@@ -280,6 +228,7 @@ LT_HD double rf_rho1(double weight, double s) { return weight / (1.0 + s / kRfCa
 
 // the sums of a linearisation, in the order every reduction uses: H upper triangle (00 01 02 03 11 12 13 22 23 33), g
 constexpr int kRfSums = 14;
+static_assert(kRfSums == lm_sums(4), "the sums of four unknowns");
 LT_HD void rf_accumulate(const RfSup &s, const Rf4 dm[6], double alpha, double acc[kRfSums], double *r2 = nullptr) {
   Rf4 r[2];
   rf_residual<Rf4>(s, dm, alpha, r);
@@ -335,8 +284,7 @@ LT_HD RfExt rf_load_ext(const double *ext, long long stride, long long s) {
 // applies to its second argument (line_dists.h:42-50).  F[f] goes to out[f * stride]
 LT_HD void rf_ext_prep(const double *k4, const double *q4, bool has_vp, const double *vp3, double *out, long long stride) {
   double q[4];
-  const double n0 = sqrt((q4[0] * q4[0] + q4[2] * q4[2]) + (q4[1] * q4[1] + q4[3] * q4[3]));
-  for (int i = 0; i < 4; ++i) q[i] = n0 > 0.0 ? q4[i] / n0 : q4[i];
+  lm_normalise_q(q4, q);
   const double scale = 1.0 / sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
   for (int i = 0; i < 4; ++i) out[(long long)i * stride] = q[i] * scale;
   double d[3] = {0.0, 0.0, 0.0};
@@ -456,8 +404,10 @@ LT_HD Rf4 rf_interp(const RfGrid<Tx> &g, const Rf4 &r, const Rf4 &c) {
   const double f = rf_bilinear(dx, dy, ll, lr, ul, ur);
   const double dfdr = rf_bilinear(dx, dy, ul, ur, uly, ury) - f;
   const double dfdc = rf_bilinear(dx, dy, lr, lrx, ur, urx) - f;
-  return Rf4{f, {dfdr * r.d[0] + dfdc * c.d[0], dfdr * r.d[1] + dfdc * c.d[1], dfdr * r.d[2] + dfdc * c.d[2],
-                 dfdr * r.d[3] + dfdc * c.d[3]}};
+  Rf4 o;
+  o.v = f;
+  for (int i = 0; i < 4; ++i) o.d[i] = dfdr * r.d[i] + dfdc * c.d[i];
+  return o;
 }
 
 // one residual of a heatmap block (pixel_cost_functions.h:93-103): 1 - f at the intersection of the projected line c
@@ -561,124 +511,29 @@ LT_HD bool rf_accumulate_terms(const RfSup &s, const RfExt &e, const RfGrid<Tx> 
 
 // the point and its four local directions: u + du_i (0, e_i) (x) u, w + dw (-w1, w0)
 LT_HD void rf_seed(const double p[6], Rf4 u[4], Rf4 w[2]) {
-  u[0] = Rf4{p[0], {-p[1], -p[2], -p[3], 0.0}};
-  u[1] = Rf4{p[1], {p[0], p[3], -p[2], 0.0}};
-  u[2] = Rf4{p[2], {-p[3], p[0], p[1], 0.0}};
-  u[3] = Rf4{p[3], {p[2], -p[1], p[0], 0.0}};
-  w[0] = Rf4{p[4], {0.0, 0.0, 0.0, -p[5]}};
-  w[1] = Rf4{p[5], {0.0, 0.0, 0.0, p[4]}};
+  lm_seed_quat(p, u);
+  w[0] = Rf4(p[4]); w[0].d[3] = -p[5];
+  w[1] = Rf4(p[5]); w[1].d[3] = p[4];
 }
 
-// the retraction: u+ = normalize((1, du) (x) u), w+ = normalize(w + dw (-w1, w0))
-LT_HD void rf_retract(const double p[6], const double dl[4], double out[6]) {
-  const double q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
-  const double r0 = ((q0 - dl[0] * q1) - dl[1] * q2) - dl[2] * q3;
-  const double r1 = ((q1 + dl[0] * q0) + dl[1] * q3) - dl[2] * q2;
-  const double r2 = ((q2 - dl[0] * q3) + dl[1] * q0) + dl[2] * q1;
-  const double r3 = ((q3 + dl[0] * q2) - dl[1] * q1) + dl[2] * q0;
-  const double nu = sqrt(((r0 * r0 + r1 * r1) + r2 * r2) + r3 * r3);
-  out[0] = r0 / nu; out[1] = r1 / nu; out[2] = r2 / nu; out[3] = r3 / nu;
-  const double w0 = p[4] - dl[3] * p[5], w1 = p[5] + dl[3] * p[4];
-  const double nw = sqrt(w0 * w0 + w1 * w1);
-  out[4] = w0 / nw; out[5] = w1 / nw;
-}
+// the chart of a line: u+ = normalize((1, du) (x) u), w+ = normalize(w + dw (-w1, w0))
+struct RfChart {
+  static constexpr int kParams = 6, kStep = 4;
+  static LT_HD void retract(const double p[6], const double dl[4], double out[6]) {
+    lm_retract_quat(p, dl, out);
+    const double w0 = p[4] - dl[3] * p[5], w1 = p[5] + dl[3] * p[4];
+    const double nw = sqrt(w0 * w0 + w1 * w1);
+    out[4] = w0 / nw; out[5] = w1 / nw;
+  }
+};
 
-// the Levenberg-Marquardt step from the reduced sums: (H + D^2 / mu) dl = -g by a 4x4 Cholesky factorisation.
-// Returns 0, or the termination code; md = the model decrease -(g' dl + dl' H dl / 2)
-LT_HD int rf_step(const double acc[kRfSums], double mu, double dl[4], double *md) {
-  double H[4][4], L[4][4], g[4];
-  int o = 0;
-  for (int i = 0; i < 4; ++i)
-    for (int j = i; j < 4; ++j, ++o) H[i][j] = H[j][i] = acc[o];
-  for (int i = 0; i < 4; ++i) g[i] = acc[10 + i];
-  for (int i = 0; i < 4; ++i) {
-    double dg = sqrt(H[i][i]);
-    dg = dg < kRfDMin ? kRfDMin : (dg > kRfDMax ? kRfDMax : dg);
-    for (int j = 0; j <= i; ++j) {
-      double sum = i == j ? H[i][i] + (dg * dg) / mu : H[i][j];
-      for (int k = 0; k < j; ++k) sum = sum - L[i][k] * L[j][k];
-      if (i == j) {
-        if (!(sum > 0.0) || !(sum < kMaxDist)) return kRfBadPivot;
-        L[i][i] = sqrt(sum);
-      } else {
-        L[i][j] = sum / L[j][j];
-      }
-    }
-  }
-  double y[4];
-  for (int i = 0; i < 4; ++i) {
-    double sum = -g[i];
-    for (int k = 0; k < i; ++k) sum = sum - L[i][k] * y[k];
-    y[i] = sum / L[i][i];
-  }
-  for (int i = 3; i >= 0; --i) {
-    double sum = y[i];
-    for (int k = i + 1; k < 4; ++k) sum = sum - L[k][i] * dl[k];
-    dl[i] = sum / L[i][i];
-  }
-  double gd = 0.0, dhd = 0.0;
-  for (int i = 0; i < 4; ++i) {
-    gd = gd + g[i] * dl[i];
-    double hd = 0.0;
-    for (int j = 0; j < 4; ++j) hd = hd + H[i][j] * dl[j];
-    dhd = dhd + dl[i] * hd;
-  }
-  *md = -(gd + 0.5 * dhd);
-  if (!(*md > 0.0) || !(*md < kMaxDist)) return kRfBadModel;
-  return 0;
-}
-
-// the radius after an accepted step
-LT_HD double rf_grow(double mu, double ratio) {
-  const double t = 2.0 * ratio - 1.0;
-  double f = 1.0 - (t * t) * t;
-  f = f < 1.0 / 3.0 ? 1.0 / 3.0 : f;
-  const double m = mu / f;
-  return m < kRfMuMax ? m : kRfMuMax;
-}
-
-// the minimiser of one track.  G supplies the two reductions over the track's supports -- cost(p) and
-// linearise(p, acc) -- as values every lane of a group holds bit for bit (device: shuffles; host: rf_tree_host), so
-// every branch below is uniform over the group.  An iteration counts whether its step was accepted or not.
-// rf_lm_from: the loop after the first cost evaluation F (the cost at p)
+// the minimiser of one track: lm_loop over the line's chart.  G supplies the two reductions over the
+// track's supports, cost(p) and linearise(p, acc).  rf_lm_from: after the first cost evaluation F (the cost at p); a
+// constant track keeps its parameters.  rf_lm has no finiteness check of its own
 template <class G>
 LT_HD void rf_lm_from(G &grp, double F, bool constant, int max_iter, double p[6], double *cost1, int *iters, int *code_out) {
-  int it = 0, code = kRfMaxIter;
-  if (constant) {
-    code = kRfConstant;
-  } else {
-    double mu = kRfMu0, nu = 2.0;
-    double acc[kRfSums];
-    bool fresh = true;
-    for (; it < max_iter; ++it) {
-      if (fresh) {
-        grp.linearise(p, acc);
-        if (acc[10] == 0.0 && acc[11] == 0.0 && acc[12] == 0.0 && acc[13] == 0.0) { code = kRfZeroGrad; break; }
-        fresh = false;
-      }
-      double dl[4], md;
-      const int rc = rf_step(acc, mu, dl, &md);
-      if (rc) { code = rc; break; }
-      double pn[6];
-      rf_retract(p, dl, pn);
-      const double Fn = grp.cost(pn);
-      const double ratio = (F - Fn) / md;
-      if (ratio > kRfMinRatio) {
-        for (int c = 0; c < 6; ++c) p[c] = pn[c];
-        F = Fn;
-        mu = rf_grow(mu, ratio);
-        nu = 2.0;
-        fresh = true;
-      } else {
-        mu = mu / nu;
-        nu = 2.0 * nu;
-        if (mu < kRfMuMin) { code = kRfRadius; ++it; break; }
-      }
-    }
-  }
-  *cost1 = F;
-  *iters = it;
-  *code_out = code;
+  if (constant) lm_skip(F, kRfConstant, cost1, iters, code_out);
+  else lm_loop<RfChart>(grp, F, max_iter, p, cost1, iters, code_out);
 }
 template <class G>
 LT_HD void rf_lm(G &grp, bool constant, int max_iter, double p[6], double *cost0, double *cost1, int *iters, int *code_out) {
@@ -689,19 +544,14 @@ LT_HD void rf_lm(G &grp, bool constant, int max_iter, double p[6], double *cost0
 
 // rf_lm with the VP and heatmap terms: a cost evaluation in which a sample fails is +inf (non-finite texels make it
 // +inf or NaN), so the ratio test rejects the step and the radius shrinks; at the initial point the track ends with
-// kRfEvalFailed, its parameters unchanged, as Ceres' FAILURE leaves the line
+// kRfEvalFailed, its parameters unchanged, as Ceres' FAILURE leaves the line (a constant track reports kRfConstant first)
 template <class G>
 LT_HD void rf_lm_terms(G &grp, bool constant, int max_iter, double p[6], double *cost0, double *cost1, int *iters,
                        int *code_out) {
   const double F = grp.cost(p);
   *cost0 = F;
-  if (!(F <= kMaxDist)) {
-    *cost1 = F;
-    *iters = 0;
-    *code_out = constant ? kRfConstant : kRfEvalFailed;
-    return;
-  }
-  rf_lm_from(grp, F, constant, max_iter, p, cost1, iters, code_out);
+  if (!(F <= kMaxDist)) lm_skip(F, constant ? kRfConstant : kRfEvalFailed, cost1, iters, code_out);
+  else rf_lm_from(grp, F, constant, max_iter, p, cost1, iters, code_out);
 }
 
 LT_HD void rf_quat_from_matrix(const double m[3][3], double p[4]);
@@ -819,19 +669,6 @@ LT_HD void rf_rank_test(const double *l3d6, long long n, long long i, d3 pref, d
   *is_hi = first && lt <= hi && hi < lt + eq;
 }
 
-// the fixed xor tree over W partial sums (host twin of the shuffles of k_refine_lm and k_refine_lm_terms)
-template <int W>
-inline void rf_tree_host(double part[W][kRfSums], int n_sums, double out[kRfSums]) {
-  for (int m = W / 2; m >= 1; m >>= 1) {
-    double nxt[W][kRfSums];
-    for (int l = 0; l < W; ++l)
-      for (int c = 0; c < n_sums; ++c) nxt[l][c] = part[l][c] + part[l ^ m][c];
-    for (int l = 0; l < W; ++l)
-      for (int c = 0; c < n_sums; ++c) part[l][c] = nxt[l][c];
-  }
-  for (int c = 0; c < n_sums; ++c) out[c] = part[0][c];
-}
-
 static_assert(kRfBlock % kRfTermWidth == 0 && (kRfTermWidth & (kRfTermWidth - 1)) == 0, "a group is a power-of-two part of a wave");
 
 // the scene's tables on the device
@@ -910,17 +747,9 @@ struct RfDevFeat {
   const double *pairs;  // 9 doubles each, row-major
 };
 
-LT_HD Rf4 operator-(const Rf4 &a, double b) { return Rf4{a.v - b, {a.d[0], a.d[1], a.d[2], a.d[3]}}; }
-LT_HD double rf_inv(double a) { return 1.0 / a; }
-LT_HD Rf4 rf_inv(const Rf4 &a) {
-  const double q = 1.0 / a.v;
-  return Rf4{q, {-(q * a.d[0]) / a.v, -(q * a.d[1]) / a.v, -(q * a.d[2]) / a.v, -(q * a.d[3]) / a.v}};
-}
-
 LT_HD void rf_fview_prep(const double *k4, const double *q4, const double *t3, RfFView *v) {
   double q[4];
-  const double n0 = sqrt((q4[0] * q4[0] + q4[2] * q4[2]) + (q4[1] * q4[1] + q4[3] * q4[3]));
-  for (int i = 0; i < 4; ++i) q[i] = n0 > 0.0 ? q4[i] / n0 : q4[i];
+  lm_normalise_q(q4, q);
   const double a = q[0], b = q[1], c = q[2], d = q[3];
   const double aa = a * a, ab = a * b, ac = a * c, ad = a * d, bb = b * b, bc = b * c, bd = b * d, cc = c * c,
                cd = c * d, dd = d * d;
@@ -967,33 +796,10 @@ LT_HD void rf_plucker_c(const T u[4], const T w[2], T d[3], T m[3]) {
   m[0] = r1 * bn; m[1] = r4 * bn; m[2] = r7 * bn;
 }
 
-// Line_WorldToPixel (line_projection.h:14-80) by its matrix products, the zero entries of the skew matrices and of K
-// left out (they add an exact zero)
+// Line_WorldToPixel of a constant camera (lm_w2p, lt_lm.h)
 template <class T>
 LT_HD void rf_w2p(const RfFView &v, const T d[3], const T m[3], T c[3]) {
-  const double *R = v.R;
-  T Rd[3], RS[3][3];
-  for (int i = 0; i < 3; ++i) {
-    const double r0 = R[3 * i], r1 = R[3 * i + 1], r2 = R[3 * i + 2];
-    Rd[i] = (d[0] * r0 + d[1] * r1) + d[2] * r2;
-    RS[i][0] = m[2] * r1 + (-m[1]) * r2;
-    RS[i][1] = (-m[2]) * r0 + m[0] * r2;
-    RS[i][2] = m[1] * r0 + (-m[0]) * r1;
-  }
-  // M(i, j) = ((R S R^T)(i, j) - t_i (R d)_j) + (R d)_i t_j at (2, 1), (0, 2), (1, 0)
-  const int ii[3] = {2, 0, 1}, jj[3] = {1, 2, 0};
-  T mt[3];
-  for (int e = 0; e < 3; ++e) {
-    const int i = ii[e], j = jj[e];
-    const T rmr = (RS[i][0] * R[3 * j] + RS[i][1] * R[3 * j + 1]) + RS[i][2] * R[3 * j + 2];
-    mt[e] = (rmr - Rd[j] * v.t[i]) + Rd[i] * v.t[j];
-  }
-  const double fx = v.k[0], fy = v.k[1], cx = v.k[2], cy = v.k[3];
-  const T c0 = mt[0] * fy;
-  const T c1 = mt[1] * fx;
-  const T c2 = (mt[2] * fy + (-mt[1]) * cy) * fx + ((-mt[0]) * fy) * cx;
-  const T cn = rf_sqrt(((c0 * c0 + c1 * c1) + c2 * c2) + kEps);
-  c[0] = c0 / cn; c[1] = c1 / cn; c[2] = c2 / cn;
+  lm_w2p<T, double>(v.k, v.R, v.t, d, m, c);
 }
 
 // Ceres_IntersectLineCoordinates (line_transforms.h:55-72) of the projected line c with the line k, the rule of
@@ -1139,19 +945,6 @@ LT_HD double rf_feat_sq_lane(const RfFImg &g, double lx, double ly, const double
   rf_feat_value<Tx>(g, ly, lx, lane, f);
   const double v0 = f[0] - fref[0], v1 = f[1] - fref[1];
   return (0.0 + v0 * v0) + v1 * v1;
-}
-
-// the fixed xor tree over the 64 lanes' parts of a block or of the supports (host twin of wave_sum)
-template <int C>
-inline void rf_tree64_host(double part[kRfFeatLanes][C], int n, double *out) {
-  for (int m = kRfFeatLanes / 2; m >= 1; m >>= 1) {
-    double nxt[kRfFeatLanes][C];
-    for (int l = 0; l < kRfFeatLanes; ++l)
-      for (int c = 0; c < n; ++c) nxt[l][c] = part[l][c] + part[l ^ m][c];
-    for (int l = 0; l < kRfFeatLanes; ++l)
-      for (int c = 0; c < n; ++c) part[l][c] = nxt[l][c];
-  }
-  for (int c = 0; c < n; ++c) out[c] = part[0][c];
 }
 
 void launch_refine_prep(hipStream_t st, const double *kvec, const double *qvec, const double *tvec, const int *sup_cam,

@@ -226,7 +226,7 @@ class Packed:
 
     def chart(self, x0):
         """the minimiser's chart around the packed point x0: y = per image (dq, dt), per point dp, per line (du, dw) ->
-        the packed point the project's retractions reach (lc_retract, p + dp, section 19's rf_retract)"""
+        the packed point the project's retractions reach (the charts of lt_lm.h's loop: LcChart, p + dp, section 19's RfChart)"""
         pose0, pts0, lines0 = [a.copy() for a in self.split(np.asarray(x0, float))]
         n6, n3 = 6 * self.n_img, 3 * self.NP
 

@@ -110,6 +110,12 @@ def texel_maps(s, dtype="float16"):
     return {i: m.astype(dtype) for i, m in s["maps"].items()}
 
 
+def texel_digest(m):
+    """the SHA-256 of a map's texels (the goldens record it: they hold the maps' recipe, not the maps)"""
+    import hashlib
+    return hashlib.sha256(np.ascontiguousarray(m).tobytes()).hexdigest()
+
+
 def oracle_grids(s, n, form, src):
     """{img_id: (array, R, tvec)} of track n; src: patches_of(..) or texel_maps(..)"""
     if form == "patch":

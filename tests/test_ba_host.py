@@ -4,6 +4,8 @@ section 27) on the host, without a GPU: limap's own part through lt_fn_ba_eval a
 Cholesky recurrence against a straight loop), the minimiser through lt_fn_ba_host against scipy, upstream's switches,
 determinism and the Python surface on its host path."""
 import ctypes as C
+import glob
+import os
 
 import numpy as np
 import pytest
@@ -16,6 +18,8 @@ from limap_amd import _capi, optimize
 from limap_amd.base import CameraView, ImageCollection, Line2d, Line3d, LineTrack, PointTrack
 
 p = _capi.ptr
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ba")
+GOLDEN_IN = ("img_ids", "k", "q", "t", "p3", "poff", "pimg", "pxy", "line6", "loff", "limg", "l2d", "l3d")
 
 
 @pytest.fixture(scope="module")
@@ -256,6 +260,28 @@ def test_constant_pose_with_points_is_block_diagonal():
     # thread counts
     rc, o1 = bs.run_host(s, bs.cfg_of(constant_pose=1, max_num_iterations=30), 1)
     assert bs.same_bits(o, o1)
+
+
+# ---- goldens (tests/golden/make_ba_golden.py) ----
+def load_golden(path):
+    """-> the scene, the configuration's keywords, the recorded outputs"""
+    z = np.load(path)
+    s = {k: np.ascontiguousarray(z[k]) for k in GOLDEN_IN}
+    cfg = {k[4:]: z[k].item() for k in z.files if k.startswith("cfg_")}
+    return s, cfg, {k[4:]: z[k] for k in z.files if k.startswith("out_")}
+
+
+@pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(GOLDEN, "*.npz"))))
+def test_goldens_reproduce(path):
+    s, cfg, want = load_golden(path)
+    rc, o = bs.run_host(s, bs.cfg_of(**cfg), 4)
+    assert rc == 0 and set(o) == set(want)
+    for k in o:
+        assert np.array_equal(o[k], want[k]), (os.path.basename(path), k)
+
+
+def test_goldens_exist():
+    assert len(glob.glob(os.path.join(GOLDEN, "*.npz"))) >= 7
 
 
 def test_no_residuals_is_code_7(hybrid):

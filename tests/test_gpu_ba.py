@@ -1,11 +1,15 @@
 """-m gpu: the bundle adjustment with free poses on the device (lt_kernels_ba.hip) equals the host path (lt_fn_ba_host)
 bit for bit -- poses, points, line parameters, segments, both costs, iterations and code -- on the smallest shapes at
 which each kernel can go wrong.  Iteration caps of 30 or less."""
+import glob
+import os
+
 import numpy as np
 import pytest
 
 import ba_scenes as bs
 from limap_amd import _capi
+from test_ba_host import GOLDEN, load_golden
 
 pytestmark = pytest.mark.gpu
 
@@ -28,6 +32,16 @@ def both(ctx, s, what="", **kw):
     for k in h:
         assert np.array_equal(d[k].view(np.uint8), h[k].view(np.uint8)), (what, k, d[k], h[k])
     return d
+
+
+@pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(GOLDEN, "*.npz"))))
+def test_device_reproduces_the_goldens(ctx, path):
+    """against the recorded bytes, not against the twin"""
+    s, cfg, want = load_golden(path)
+    rc, d = bs.run_device(ctx, s, bs.cfg_of(**cfg))
+    assert rc == 0 and set(d) == set(want)
+    for k in d:
+        assert np.array_equal(d[k], want[k]), (os.path.basename(path), k)
 
 
 # degenerate-but-legal sizes

@@ -2,13 +2,16 @@
 for bit -- pose, both costs, iterations, termination codes -- over batch sizes, block counts around the wave width,
 every cost function, weight and loss; the engines equal the batch call; two runs and a permuted problem order give
 identical per-problem results."""
+import glob
+import os
+
 import numpy as np
 import pytest
 
 import loc_scenes as ls
 from limap_amd import _capi
 from limap_amd import hybrid_localization as hl
-from test_loc_host import ocfg, struct_of
+from test_loc_host import GOLDEN, load_golden, ocfg, struct_of
 
 pytestmark = pytest.mark.gpu
 KEYS = ("qvec", "tvec", "cost", "num_residuals", "iterations", "codes")
@@ -33,6 +36,13 @@ def sized(n_blocks, seed, lines_share=0.4):
     """a problem with exactly n_blocks residual blocks (one 2D segment per 3D line)"""
     nl = int(round(n_blocks * lines_share))
     return ls.make_problem(nl, n_blocks - nl, seed=seed, multi=0.0)
+
+
+@pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(GOLDEN, "*.npz"))))
+def test_device_reproduces_the_goldens(ctx, path):
+    """against the recorded bytes, not against the twin"""
+    csr, s, want = load_golden(path)
+    same(hl.loc_arrays(csr, s, ctx=ctx), want, os.path.basename(path))
 
 
 @pytest.mark.parametrize("n_prob", [1, 4, 5, 257])

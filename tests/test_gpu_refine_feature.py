@@ -2,13 +2,16 @@
 (lt_fn_refine_host_feature) bit for bit -- parameters, segments, both costs, iterations, termination codes -- for every
 combination with the other terms, both forms and texel types, at the edges of the tracks-per-workgroup count, for device
 inputs, the edge scenes of tests/test_refine_feature_host.py and the maps as context state."""
+import glob
 import itertools
+import os
 
 import numpy as np
 import pytest
 
 import refine_feature_scenes as fs
 from limap_amd import features, optimize
+from test_refine_feature_host import GOLDEN, load_golden, run_golden
 
 pytestmark = pytest.mark.gpu
 
@@ -34,6 +37,16 @@ def both(s, rf, form, src, **kw):
     d = fs.run(s, rf, form, src, **kw)
     fs.same_bits(h, d, (form, kw.get("tracks")))
     return h, d
+
+
+@pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(GOLDEN, "*.npz"))))
+def test_device_reproduces_the_goldens(gpu_lib, path):
+    """against the recorded bytes, not against the twin"""
+    z, maps, want = load_golden(path)
+    d = run_golden(z, maps)
+    for k in fs.RESULT_KEYS:
+        x, y = np.ascontiguousarray(d[k]), np.ascontiguousarray(want[k])
+        assert x.shape == y.shape and x.tobytes() == y.tobytes(), (os.path.basename(path), k)
 
 
 @pytest.mark.parametrize("geo,vp,hm", list(itertools.product([1, 0], [0, 1], [0, 1])))

@@ -1,7 +1,9 @@
 """The point-line pose refinement (limap_amd.hybrid_localization) on the host, without a GPU:
 limap's cost through lt_fn_loc_eval against the NumPy restatement (tests/loc_oracle.py) in longdouble, the minimiser
 through lt_fn_loc_host against scipy, and the Python surface on its host path."""
+import glob
 import itertools
+import os
 
 import numpy as np
 import pytest
@@ -15,6 +17,9 @@ WEIGHT_NAMES = {0: None, 1: "cosine", 3: "length", 4: "invlength"}
 COST_NAMES = ["MidpointDist2", "MidpointAngleDist", "PerpendicularDist2", "PerpendicularDist4", "3DLineLineDist2",
               "3DPlaneLineDist2"]
 LOSS_OBJ = {0: lambda a: hl.TrivialLoss(), 1: hl.HuberLoss, 2: hl.SoftLOneLoss, 3: hl.CauchyLoss}
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "loc")
+CSR_KEYS = ("P", "k", "q", "t", "line_off", "l3", "seg_off", "sg", "pt_off", "p3", "p2")  # hl._problem_arrays' tuple
+OUT_KEYS = ("qvec", "tvec", "cost", "num_residuals", "iterations", "codes")
 
 
 def struct_of(cfg):
@@ -330,6 +335,28 @@ def test_host_result_does_not_depend_on_threads_or_problem_order():
     for key in ("qvec", "tvec", "cost", "num_residuals", "iterations", "codes"):
         assert np.array_equal(a[key], b[key][::-1]), key
     assert a["codes"][-1] == 7
+
+
+# ---- goldens (tests/golden/make_loc_golden.py) ----
+def load_golden(path):
+    """-> the CSR tuple of hl.loc_arrays, the configuration struct, the recorded outputs"""
+    z = np.load(path)
+    csr = (int(z["in_P"]),) + tuple(np.ascontiguousarray(z["in_" + k]) for k in CSR_KEYS[1:])
+    s = struct_of({k[4:]: z[k].item() for k in z.files if k.startswith("cfg_")})
+    s.max_num_iterations = int(z["max_num_iterations"])
+    return csr, s, {k: z["out_" + k] for k in OUT_KEYS}
+
+
+@pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(GOLDEN, "*.npz"))))
+def test_goldens_reproduce(path):
+    csr, s, want = load_golden(path)
+    r = hl.loc_arrays(csr, s, 4)
+    for k in OUT_KEYS:
+        assert np.array_equal(r[k], want[k]), (os.path.basename(path), k)
+
+
+def test_goldens_exist():
+    assert len(glob.glob(os.path.join(GOLDEN, "*.npz"))) >= 7
 
 
 # ---- 3. pose scoring ----

@@ -1,6 +1,7 @@
 """The feature-consistency term of the line refinement on the host path: lt_fn_refine_eval_feature
 and lt_fn_refine_host_feature against the NumPy restatement of tests/refine_feature_oracle.py, the edges of the sample
 selection and of the sampling, and the Python surface.  No GPU."""
+import glob
 import os
 
 import numpy as np
@@ -16,6 +17,8 @@ from limap_amd import features, optimize
 # restatement alone stays inside it, which test_cost_agrees_with_the_longdouble_restatement asserts too.
 COST_DISTANCE = 3.1e-13
 COST_RTOL = 8 * COST_DISTANCE
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "refine_feature")
+GOLDEN_IN = ("img_ids", "k", "q", "t", "line6", "off", "img", "l2d", "l3d")
 
 
 @pytest.fixture(scope="module")
@@ -216,6 +219,53 @@ def test_failed_intersection_at_the_initial_line_is_code_6():
     r = fs.run(f, fs.refine_cfg(), "map", maps, host_threads=1)
     assert r["codes"][0] == 6 and r["iterations"][0] == 0 and np.all(np.isinf(r["cost"]))
     assert np.array_equal(r["params"][0], ro.minimal(f["line6"][0])), "the line is kept"
+
+
+# ---- goldens (tests/golden/make_refine_feature_golden.py) ----
+def golden_maps(z, dtype):
+    """the texel maps of a golden from their recipe: make_scene's arguments, or the zero maps of failing_scene"""
+    if "maps_seed" in z:
+        src = fs.make_scene(counts=tuple(int(c) for c in z["maps_counts"]), seed=int(z["maps_seed"]))["maps"]
+    else:
+        src = fs.failing_scene()["maps"]
+    return {i: m.astype(dtype) for i, m in src.items()}
+
+
+def run_golden(z, maps, host_threads=None):
+    """the solve of a golden's inputs on the host (host_threads) or on the device"""
+    s = {k: np.ascontiguousarray(z[k]) for k in GOLDEN_IN}
+    s["gt6"] = s["line6"]
+    cfg = {k[4:]: np.asarray(z[k]).item() for k in z if k.startswith("cfg_")}
+    rf = fs.refine_cfg(**cfg)
+    on_host = host_threads is not None
+    vp = (np.ascontiguousarray(z["vp_flag"]), np.ascontiguousarray(z["vp3"])) if "vp_flag" in z else None
+    heat = None
+    if rf.use_heatmap:  # some_heatmaps of the regenerated float64 maps: the texel type rounds them once
+        f64 = fs.make_scene(counts=tuple(int(c) for c in z["maps_counts"]), seed=int(z["maps_seed"]))
+        heat = optimize.Heatmaps(fs.some_heatmaps(f64), cfg["dtype"])
+    return fs.run(s, rf, "map", maps, host_threads=host_threads, vp=vp, heatmaps=heat) if on_host else \
+        fs.run(s, rf, "map", maps, vp=vp, heatmaps=heat)
+
+
+def load_golden(path):
+    """-> the file's arrays, the regenerated maps (their digests checked), the recorded outputs"""
+    z = dict(np.load(path))
+    maps = golden_maps(z, str(z["cfg_dtype"]))
+    got = [fs.texel_digest(maps[int(i)]) for i in z["img_ids"]]
+    assert got == list(z["maps_sha256"]), "the regenerated feature maps are not the recorded ones"
+    return z, maps, {k: z["out_" + k] for k in fs.RESULT_KEYS}
+
+
+@pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(GOLDEN, "*.npz"))))
+def test_goldens_reproduce(path):
+    z, maps, want = load_golden(path)
+    r = run_golden(z, maps, host_threads=4)
+    for k in fs.RESULT_KEYS:
+        assert np.array_equal(r[k], want[k]), (os.path.basename(path), k)
+
+
+def test_goldens_exist():
+    assert len(glob.glob(os.path.join(GOLDEN, "*.npz"))) >= 4
 
 
 # ---- 5. forms and texel types ----
