@@ -767,6 +767,11 @@ int lt_fn_refine_eval(int64_t K, const double *cam11, const double *line2d4, con
 int lt_fn_refine_explog(int which, int64_t n, const double *x, double *out);
 int lt_fn_refine_minimal(const double line6[6], double params6[6]);
 int lt_fn_refine_infinite(const double params6[6], double dm6[6]);
+/* For tests: the minimisers' damped step (lm_step of lt_lm.h) on the sums acc of a linearisation with n = 4 or 6
+ * unknowns (n (n + 1) / 2 entries of the upper triangle of H by rows, then g) at the radius mu.  Returns 0 with the step
+ * dl[n] and the model decrease *md, or the termination code 3 (bad pivot; dl and *md NaN) or 4 (bad model; dl and *md
+ * as computed); -1 on another n or a NULL pointer. */
+int lt_fn_lm_step(int n, const double *acc, double mu, double *dl, double *md);
 
 /* ---- the VP and the heatmap term of limap.optimize.line_refinement (runners/refinement.py with
  * cfgs/refinement/default.yaml; refine.cc:87-126,315-360).  Per support of a track, after its
@@ -1199,6 +1204,12 @@ const char *lt_fn_loc_host_error(void);
 int lt_fn_loc_eval(const double kvec4[4], const double qvec4[4], const double tvec3[3], int64_t n_lines,
                    const double *line3d6, const int64_t *seg_off, const double *seg4, int64_t n_points, const double *p3d3,
                    const double *p2d2, const lt_loc_config *cfg, double *residuals, double *cost, double g[6], double H[36]);
+/* For tests: lt_fn_loc_eval at the quaternion as given -- an iterate of the solve, which normalises its input once and
+ * then evaluates the retracted quaternions as they are -- not normalised once more. */
+int lt_fn_loc_eval_at(const double kvec4[4], const double qvec4[4], const double tvec3[3], int64_t n_lines,
+                      const double *line3d6, const int64_t *seg_off, const double *seg4, int64_t n_points,
+                      const double *p3d3, const double *p2d2, const lt_loc_config *cfg, double *residuals, double *cost,
+                      double g[6], double H[36]);
 /* Pose scoring: JointPoseEstimator::EvaluateModelOnPoint (estimators/absolute_pose/joint_pose_estimator.cc:176-251) for
  * n_poses hypotheses x N = n_pts + n_seg correspondences of one camera in one launch, the points first.  2D segment s
  * observes 3D line l3d_ids[s].  A cell is the squared norm of the correspondence's residuals (lines with ENoneWeight),
@@ -1300,6 +1311,29 @@ int lt_fn_ba_eval(int n_img, const int32_t *img_ids, const double *kvec4, const 
                   int64_t n_ln, const double *line6, const int64_t *ln_off, const int32_t *ln_img, const double *l2d4,
                   const double *l3d6, const lt_ba_config *cfg, const double *params6_in, int64_t *dims4, int32_t *blk_info3,
                   double *residuals, double *cost, double *g, double *H, double mu, double *step);
+/* For tests: point track `track` of a constant_pose = 1 problem at the point p3, as the separated solve sums it over
+ * the track's blocks: the cost, g[4] and H[16] of section 19's sums (the fourth direction is the literal zero). */
+int lt_fn_ba_point_eval(int n_img, const int32_t *img_ids, const double *kvec4, const double *qvec4, const double *tvec3,
+                        int64_t n_pt, const double *pt3, const int64_t *pt_off, const int32_t *pt_img, const double *pt_xy2,
+                        int64_t n_ln, const double *line6, const int64_t *ln_off, const int32_t *ln_img, const double *l2d4,
+                        const double *l3d6, const lt_ba_config *cfg, int64_t track, const double p3[3], double *cost,
+                        double g[4], double H[16]);
+/* For tests: the minimisers' loop (lm_loop of lt_lm.h over the additive point chart) from the point p3 with the cost F,
+ * its reductions read from a script: the k-th cost evaluation returns costs[k], the k-th linearisation the 14 sums
+ * acc14[14 k ..].  p3 becomes the final point; used2 (may be NULL; no other output may) = cost evaluations and
+ * linearisations consumed.  LT_ERR_STATE, with the outputs written, where the script is shorter than the solve. */
+int lt_fn_lm_loop_script(double F, int max_iter, int64_t n_costs, const double *costs, int64_t n_lin, const double *acc14,
+                         double p3[3], double *cost1, int32_t *iters, int32_t *code, int64_t used2[2]);
+/* For tests: the free-pose solve of lt_fn_ba_host (one thread) with what every attempt hands to its decision recorded.
+ * *total0: the sum of the blocks' cost terms at the initial point.  rec5[5 a ..] of attempt a (the first `cap` are
+ * written, *n_attempts counts all): the radius it ran with, 1 where a factorisation failed (-1: the attempt ended the
+ * solve by the zero gradient and no decision was taken), 1 where it linearised anew, the cost total and the total of the
+ * model-decrease terms.  cost2, iters, code (any may be NULL) as lt_fn_ba_host. */
+int lt_fn_ba_host_trace(int n_img, const int32_t *img_ids, const double *kvec4, const double *qvec4, const double *tvec3,
+                        int64_t n_pt, const double *pt3, const int64_t *pt_off, const int32_t *pt_img, const double *pt_xy2,
+                        int64_t n_ln, const double *line6, const int64_t *ln_off, const int32_t *ln_img, const double *l2d4,
+                        const double *l3d6, const lt_ba_config *cfg, int64_t cap, int64_t *n_attempts, double *total0,
+                        double *rec5, double *cost2, int32_t *iters, int32_t *code);
 /* the defined factorisation alone: L (n x n by rows, zero above the diagonal) of S (its lower triangle is read),
  * L_ij = (S_ij - sum_{k<j} L_ik L_jk) / L_jj with the sum in ascending k from S_ij, and, with rhs and x, the solution
  * of S x = rhs by substitutions under the same rule.  LT_ERR_STATE: a pivot is not positive or not finite */

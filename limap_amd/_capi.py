@@ -67,6 +67,8 @@ EXPORTED_SYMBOLS = [
     "lt_loc_score", "lt_loc_score_size", "lt_loc_score_get", "lt_loc_score_get_timers", "lt_fn_loc_score_host",
     "lt_ba_config_default", "lt_ba_max_images", "lt_ba_poll_default", "lt_ba_arrays", "lt_ba_get", "lt_ba_get_timers",
     "lt_fn_ba_host", "lt_fn_ba_host_error", "lt_fn_ba_eval", "lt_fn_ba_cholesky",
+    "lt_fn_lm_step", "lt_fn_loc_eval_at", "lt_fn_ba_point_eval", "lt_fn_lm_loop_script",
+    "lt_fn_ba_host_trace",
 ]
 
 
@@ -583,6 +585,11 @@ def load_library():
     L.lt_fn_ba_host_error.restype = C.c_char_p
     L.lt_fn_ba_eval.argtypes = ba_in + [dp, i64p, i32p, dp, dp, dp, dp, C.c_double, dp]
     L.lt_fn_ba_cholesky.argtypes = [C.c_int64, dp, dp, dp, dp]
+    L.lt_fn_lm_step.argtypes = [C.c_int, dp, C.c_double, dp, dp]
+    L.lt_fn_loc_eval_at.argtypes = L.lt_fn_loc_eval.argtypes
+    L.lt_fn_ba_point_eval.argtypes = ba_in + [C.c_int64, dp, dp, dp, dp]
+    L.lt_fn_ba_host_trace.argtypes = ba_in + [C.c_int64, i64p, dp, dp, dp, i32p, i32p]
+    L.lt_fn_lm_loop_script.argtypes = [C.c_double, C.c_int, C.c_int64, dp, C.c_int64, dp, dp, dp, i32p, i32p, i64p]
     _lib = L
     return L
 

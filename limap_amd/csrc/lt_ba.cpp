@@ -393,17 +393,20 @@ void host_schur_row(const BaDev &d, int i, double mu) {
     for (int e = 0; e < 42; ++e) ba_item_schur(d, i, j, e, mu);
 }
 
-void host_init(const BaDev &d, int nt) {
+void host_init(const BaDev &d, int nt, double *total0 = nullptr) {
   host_cost(d, 0, false, nt);
   double cost, md;
   host_totals(d, &cost, &md);
+  if (total0) *total0 = cost;
   ba_decide_init(*d.status, cost);
 }
 
-// one attempt: launch_ba_attempt on the host
-void host_attempt(const BaDev &d, int nt) {
+// one attempt: launch_ba_attempt on the host.  rec (tests): what the attempt hands to ba_decide_step -- the radius and
+// the fresh flag it ran with, whether a factorisation failed, the two totals; rec[1] = -1: it ended by the zero gradient
+void host_attempt(const BaDev &d, int nt, double *rec = nullptr) {
   BaStatus &st = *d.status;
   if (st.done) return;
+  if (rec) { rec[0] = st.mu; rec[1] = 0.0; rec[2] = st.fresh; rec[3] = rec[4] = 0.0; }
   if (st.fresh) host_linearise(d, st.cur, nt);
   {
     int bad = 0;
@@ -421,7 +424,11 @@ void host_attempt(const BaDev &d, int nt) {
         if (d.st[s].constant) continue;
         for (int l = 0; l < (d.st[s].kind ? 4 : 3); ++l) nz = nz || d.bs[(size_t)4 * s + l] != 0.0;
       }
-      if (!nz) { st.code = kRfZeroGrad; st.done = 1; return; }
+      if (!nz) {
+        st.code = kRfZeroGrad; st.done = 1;
+        if (rec) rec[1] = -1.0;
+        return;
+      }
     }
     if (!ba_cholesky_host(d.n, d.S, d.rhs, d.LT, d.dc)) st.bad = 1;
   }
@@ -435,6 +442,7 @@ void host_attempt(const BaDev &d, int nt) {
   }
   double cost, md;
   host_totals(d, &cost, &md);
+  if (rec) { rec[1] = st.bad; rec[3] = cost; rec[4] = md; }
   ba_decide_step(st, cost, md);
 }
 
@@ -886,6 +894,106 @@ int lt_fn_ba_eval(int n_img, const int32_t *img_ids, const double *kvec4, const 
           for (int l = 0; l < (pl.st[(size_t)s].kind ? 4 : 3); ++l) step[so[(size_t)s] + l] = d.ds[(size_t)4 * s + l];
     }
   }
+  return LT_OK;
+}
+
+int lt_fn_ba_point_eval(int n_img, const int32_t *img_ids, const double *kvec4, const double *qvec4, const double *tvec3,
+                        int64_t n_pt, const double *pt3, const int64_t *pt_off, const int32_t *pt_img, const double *pt_xy2,
+                        int64_t n_ln, const double *line6, const int64_t *ln_off, const int32_t *ln_img, const double *l2d4,
+                        const double *l3d6, const lt_ba_config *cfg, int64_t track, const double p3[3], double *cost,
+                        double g[4], double H[16]) {
+  const Input in = make_input(n_img, img_ids, kvec4, qvec4, tvec3, n_pt, pt3, pt_off, pt_img, pt_xy2, n_ln, line6, ln_off,
+                              ln_img, l2d4, l3d6, cfg);
+  std::string msg;
+  Plan pl;
+  if (make_plan(in, pl, msg)) {
+    g_host_error = "lt_fn_ba_point_eval: " + msg;
+    return LT_ERR_ARGUMENT;
+  }
+  g_host_error.clear();
+  if (!pl.constant_pose || !p3 || track < 0 || track >= pl.NP) {
+    g_host_error = "lt_fn_ba_point_eval: constant_pose=1, a point and a point track's index are needed";
+    return LT_ERR_ARGUMENT;
+  }
+  BaDev d;
+  bind_points(pl, d);
+  std::vector<double> pose = pl.pose0, sp = pl.sp0;
+  d.kvec = pl.kvec.data(); d.pose = pose.data(); d.sp = sp.data();
+  d.st = pl.st.data(); d.blk = pl.blk.data();
+  HostPointGroup grp{d, pl.st[(size_t)track]};
+  if (cost) *cost = grp.cost(p3);
+  double acc[kRfSums];
+  grp.linearise(p3, acc);
+  if (H) {
+    int o = 0;
+    for (int i = 0; i < 4; ++i)
+      for (int j = i; j < 4; ++j, ++o) H[4 * i + j] = H[4 * j + i] = acc[o];
+  }
+  if (g) std::copy(acc + 10, acc + 14, g);
+  return LT_OK;
+}
+
+// a group whose reductions are read from a script: the k-th cost, the k-th linearisation
+struct ScriptGroup {
+  const double *costs, *accs;
+  int64_t n_costs, n_lin, i_cost = 0, i_lin = 0;
+  bool short_of = false;
+  double cost(const double *) {
+    if (i_cost >= n_costs) { short_of = true; return std::nan(""); }
+    return costs[i_cost++];
+  }
+  void linearise(const double *, double acc[kRfSums]) {
+    if (i_lin >= n_lin) { short_of = true; std::fill(acc, acc + kRfSums, std::nan("")); return; }
+    std::copy(accs + kRfSums * i_lin, accs + kRfSums * (i_lin + 1), acc);
+    ++i_lin;
+  }
+};
+
+int lt_fn_lm_loop_script(double F, int max_iter, int64_t n_costs, const double *costs, int64_t n_lin, const double *acc14,
+                         double p3[3], double *cost1, int32_t *iters, int32_t *code, int64_t used2[2]) {
+  if (!p3 || !cost1 || !iters || !code || n_costs < 0 || n_lin < 0 || (n_costs > 0 && !costs) || (n_lin > 0 && !acc14))
+    return LT_ERR_ARGUMENT;
+  ScriptGroup grp{costs, acc14, n_costs, n_lin};
+  int it = 0, cd = 0;
+  lm_loop<BaPointChart>(grp, F, max_iter, p3, cost1, &it, &cd);
+  *iters = it;
+  *code = cd;
+  if (used2) { used2[0] = grp.i_cost; used2[1] = grp.i_lin; }
+  return grp.short_of ? LT_ERR_STATE : LT_OK;
+}
+
+int lt_fn_ba_host_trace(int n_img, const int32_t *img_ids, const double *kvec4, const double *qvec4, const double *tvec3,
+                        int64_t n_pt, const double *pt3, const int64_t *pt_off, const int32_t *pt_img, const double *pt_xy2,
+                        int64_t n_ln, const double *line6, const int64_t *ln_off, const int32_t *ln_img, const double *l2d4,
+                        const double *l3d6, const lt_ba_config *cfg, int64_t cap, int64_t *n_attempts, double *total0,
+                        double *rec5, double *cost2, int32_t *iters, int32_t *code) {
+  const Input in = make_input(n_img, img_ids, kvec4, qvec4, tvec3, n_pt, pt3, pt_off, pt_img, pt_xy2, n_ln, line6, ln_off,
+                              ln_img, l2d4, l3d6, cfg);
+  std::string msg;
+  Plan pl;
+  if (make_plan(in, pl, msg)) {
+    g_host_error = "lt_fn_ba_host_trace: " + msg;
+    return LT_ERR_ARGUMENT;
+  }
+  g_host_error.clear();
+  if (pl.constant_pose || pl.NB == 0 || cap < 0 || !n_attempts || !total0 || (cap > 0 && !rec5)) {
+    g_host_error = "lt_fn_ba_host_trace: free poses, a residual block and the outputs are needed";
+    return LT_ERR_ARGUMENT;
+  }
+  HostTables h;
+  host_tables(pl, h);
+  host_init(h.dev, 1, total0);
+  int64_t n = 0;
+  while (!h.status.done) {
+    double rec[5];
+    host_attempt(h.dev, 1, rec);
+    if (n < cap) std::copy(rec, rec + 5, rec5 + 5 * n);
+    ++n;
+  }
+  *n_attempts = n;
+  if (cost2) { cost2[0] = h.status.F0; cost2[1] = h.status.F; }
+  if (iters) *iters = h.status.iters;
+  if (code) *code = h.status.code;
   return LT_OK;
 }
 

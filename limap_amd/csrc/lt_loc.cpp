@@ -436,21 +436,25 @@ int lt_fn_loc_host(int64_t n_prob, const double *kvec4, const double *qvec4, con
   return LT_OK;
 }
 
-int lt_fn_loc_eval(const double kvec4[4], const double qvec4[4], const double tvec3[3], int64_t n_lines,
-                   const double *line3d6, const int64_t *seg_off, const double *seg4, int64_t n_points, const double *p3d3,
-                   const double *p2d2, const lt_loc_config *cfg, double *residuals, double *cost, double g[6], double H[36]) {
+// as_given: the pose as the caller holds it (an iterate of the solve), not normalised once more
+static int loc_eval(const char *who, bool as_given, const double kvec4[4], const double qvec4[4], const double tvec3[3],
+                    int64_t n_lines, const double *line3d6, const int64_t *seg_off, const double *seg4, int64_t n_points,
+                    const double *p3d3, const double *p2d2, const lt_loc_config *cfg, double *residuals, double *cost,
+                    double g[6], double H[36]) {
   std::string msg;
   Plan pl;
   const int64_t line_off[2] = {0, n_lines}, pt_off[2] = {0, n_points};
   if (n_lines < 0 || n_points < 0 ||
       make_plan(1, kvec4, qvec4, tvec3, line_off, line3d6, seg_off, seg4, pt_off, p3d3, p2d2, cfg, pl, msg)) {
-    g_host_error = "lt_fn_loc_eval: " + msg;
+    g_host_error = std::string(who) + ": " + msg;
     return LT_ERR_ARGUMENT;
   }
   g_host_error.clear();
   const LcProb &pr = pl.probs[0];
   const LcOut &o = pl.init[0];
-  const double p[7] = {o.q[0], o.q[1], o.q[2], o.q[3], o.t[0], o.t[1], o.t[2]};
+  double p[7] = {o.q[0], o.q[1], o.q[2], o.q[3], o.t[0], o.t[1], o.t[2]};
+  if (as_given)
+    for (int i = 0; i < 4; ++i) p[i] = qvec4[i];
   HostGroup grp{pl.cfg, pl.tab.data(), pl.stride, pr, pl.kvec.data()};
   if (residuals) std::fill(residuals, residuals + 4 * (size_t)pr.n, std::nan(""));
   if (cost) *cost = grp.cost(p);
@@ -463,6 +467,21 @@ int lt_fn_loc_eval(const double kvec4[4], const double qvec4[4], const double tv
   }
   if (g) std::copy(acc + 21, acc + 27, g);
   return LT_OK;
+}
+
+int lt_fn_loc_eval(const double kvec4[4], const double qvec4[4], const double tvec3[3], int64_t n_lines,
+                   const double *line3d6, const int64_t *seg_off, const double *seg4, int64_t n_points, const double *p3d3,
+                   const double *p2d2, const lt_loc_config *cfg, double *residuals, double *cost, double g[6], double H[36]) {
+  return loc_eval("lt_fn_loc_eval", false, kvec4, qvec4, tvec3, n_lines, line3d6, seg_off, seg4, n_points, p3d3, p2d2, cfg,
+                  residuals, cost, g, H);
+}
+
+int lt_fn_loc_eval_at(const double kvec4[4], const double qvec4[4], const double tvec3[3], int64_t n_lines,
+                      const double *line3d6, const int64_t *seg_off, const double *seg4, int64_t n_points,
+                      const double *p3d3, const double *p2d2, const lt_loc_config *cfg, double *residuals, double *cost,
+                      double g[6], double H[36]) {
+  return loc_eval("lt_fn_loc_eval_at", true, kvec4, qvec4, tvec3, n_lines, line3d6, seg_off, seg4, n_points, p3d3, p2d2,
+                  cfg, residuals, cost, g, H);
 }
 
 int lt_loc_score(lt_ctx *ctx, const double kvec4[4], int64_t n_l3d, const double *line3d6, int64_t n_seg,

@@ -1307,6 +1307,13 @@ int lt_fn_refine_eval(int64_t K, const double *cam11, const double *line2d4, con
   return LT_OK;
 }
 
+int lt_fn_lm_step(int n, const double *acc, double mu, double *dl, double *md) {
+  if ((n != 4 && n != 6) || !acc || !dl || !md) return -1;
+  for (int i = 0; i < n; ++i) dl[i] = std::nan("");
+  *md = std::nan("");
+  return n == 4 ? lm_step<4>(acc, mu, dl, md) : lm_step<6>(acc, mu, dl, md);
+}
+
 int lt_fn_refine_cut(int64_t K, const double *line3d6, const double params6[6], int num_outliers, double seg6[6]) {
   if (K < 1 || K > (1 << 28) || !line3d6 || !params6 || !seg6 || num_outliers < 0 || num_outliers > 2 * K - 1 ||
       !all_finite(line3d6, 6 * (size_t)K))
