@@ -1339,6 +1339,101 @@ int lt_fn_ba_host_trace(int n_img, const int32_t *img_ids, const double *kvec4, 
  * of S x = rhs by substitutions under the same rule.  LT_ERR_STATE: a pivot is not positive or not finite */
 int lt_fn_ba_cholesky(int64_t n, const double *S, const double *rhs, double *L, double *x);
 
+/* ---- Global point-line association: limap.optimize.global_pl_association's GlobalAssociator with
+ * constant cameras.  The unknowns are the point tracks (3 each), the line tracks (4, section 19's chart) and the
+ * vanishing points (2, the chart of DESIGN section 29), coupled by association edges: point-line (R2.1), VP-line (R2.2),
+ * VP-VP orthogonality (R2.3) and collinearity (R2.4).  limap's residuals, weights, losses and SetUp switches are
+ * restated; the minimiser is this project's definition: section 27's loop with its linear step by preconditioned
+ * conjugate gradients on the explicitly assembled block-sparse matrix.  The results are a stationary point of
+ * upstream's cost reached from the input, not the iterates of a Ceres run. ---- */
+typedef struct lt_assoc_config {
+  double geometric_alpha;            /* 10 */
+  double lw_point;                   /* 0.1; <= 0 adds no R1.1 block */
+  double lw_pointline_association;   /* 10; <= 0 adds no R2.1 block */
+  double lw_vpline_association;      /* 1; <= 0 adds no R2.2 block */
+  double lw_vp_orthogonality;        /* 1; <= 0 adds no R2.3 block */
+  double lw_vp_collinearity;         /* 0; <= 0 adds no R2.4 block */
+  double cg_eta;                     /* 0.1 (Ceres' eta): CG stops at sqrt(r.z) <= eta sqrt(r0.z0) */
+  int32_t cg_max_iterations;         /* 500 (Ceres' max_linear_solver_iterations) */
+  int32_t min_num_images;            /* 4: a line track seen in fewer images keeps its line */
+  int32_t max_num_iterations;        /* 100; an attempt counts whether accepted or not */
+  int32_t constant_intrinsics, constant_pose; /* 1, 1; 0 is LT_ERR_ARGUMENT (free cameras are not built here) */
+  int32_t constant_point, constant_line, constant_vp; /* 0 */
+  int32_t enable_pointline, enable_vpline; /* 1: Init2DBipartites_PointLine / _VPLine was called */
+  int32_t poll_interval;             /* batches enqueued between two reads of the status record; 0: the default (4) */
+  int32_t cg_batch;                  /* CG iterations enqueued per batch; 0: the default (4), at most 64.  The result
+                                        depends on neither */
+  int32_t kernel_timers;             /* 1: HIP events around every kernel (poll_interval becomes 1) */
+  int32_t pad_;
+} lt_assoc_config;
+void lt_assoc_config_default(lt_assoc_config *cfg);
+/* The problem.  Cameras, point tracks and line tracks as lt_ba_arrays takes them (no 3D supports: the segment cut is
+ * lt_fn_refine_cut's).  vp3: the vanishing points' directions.  Edges in the order upstream's maps give them:
+ * edge_kind 0 point-line (a = point track, b = line track; w = the count of supports within th_pixel), 1 VP-line
+ * (a = VP, b = line track; w = the count), 2 VP-VP orthogonality, 3 VP-VP collinearity (a < b VPs; w unused); a, b
+ * index the arrays.  The ScaledLoss weights (w lw, w 1e2 lw, 1e2 lw) and SetUp's switches are applied here. */
+typedef struct lt_assoc_input {
+  int32_t n_img, pad_;
+  const int32_t *img_ids;
+  const double *kvec4, *qvec4, *tvec3;
+  int64_t n_pt;
+  const double *pt3;
+  const int64_t *pt_off;
+  const int32_t *pt_img;
+  const double *pt_xy2;
+  int64_t n_ln;
+  const double *line6;
+  const int64_t *ln_off;
+  const int32_t *ln_img;
+  const double *l2d4;
+  int64_t n_vp;
+  const double *vp3;
+  int64_t n_edge;
+  const int32_t *edge_kind, *edge_a, *edge_b;
+  const double *edge_w;
+} lt_assoc_input;
+/* LT_ERR_ARGUMENT before any launch: constant_pose = 0 or constant_intrinsics = 0, non-finite input, an image id or an
+ * edge's index that is not in the collection, a vanishing point or a track line of zero length. */
+int lt_assoc_arrays(lt_ctx *ctx, const lt_assoc_input *in, const lt_assoc_config *cfg);
+/* of the last lt_assoc_arrays (any pointer may be NULL): the points, the lines' minimal parameters (uvec, wvec), the
+ * vanishing points (a free one is a unit vector, a constant one its input), cost2 = the cost at the initial and at the
+ * final point, the iterations, the CG iterations of all attempts, and the termination code: 0 max_num_iterations,
+ * 1 radius, 2 zero gradient, 6 the cost at the initial point is not finite, 7 no residual block; 6 and 7 change nothing */
+int lt_assoc_get(lt_ctx *ctx, double *pt3, double *params6, double *vp3, double *cost2, int32_t *iters, int64_t *cg_iters,
+                 int32_t *code);
+/* host ms of [0] validation, tables and upload, [1] the loop, [2] download; [3] batches enqueued; with kernel_timers the
+ * device ms of [4] k_as_linearize [5] k_as_diag [6] k_as_diag_vp [7] k_as_precond [8] k_as_cg_begin [9] k_as_matvec
+ * [10] k_as_alpha [11] k_as_update [12] k_as_beta [13] k_as_dir [14] k_as_backsub [15] k_as_cost [16] k_as_decide,
+ * summed over the batches */
+int lt_assoc_get_timers(lt_ctx *ctx, double out[20]);
+/* The same definition on the host, no context and no device: bit-identical results for every host_threads (0: default).
+ * For tests, with trace_cap > 0: rec6[6 a ..] of attempt a (the first trace_cap are written, *n_attempts counts all):
+ * the radius it ran with, 1 where the linear solve failed (-1: the attempt ended the solve by the zero gradient), 1
+ * where it linearised anew, the cost total, the total of the model-decrease terms, its CG iterations; *total0: the sum
+ * of the blocks' cost terms at the initial point (n_attempts, total0, rec6 may be NULL). */
+int lt_fn_assoc_host(const lt_assoc_input *in, const lt_assoc_config *cfg, int host_threads, double *pt3, double *params6,
+                     double *vp3, double *cost2, int32_t *iters, int64_t *cg_iters, int32_t *code, int64_t trace_cap,
+                     int64_t *n_attempts, double *total0, double *rec6);
+const char *lt_fn_assoc_host_error(void);
+/* For tests: the problem at the point sp6 (6 doubles per unknown -- point p[3], line uvec wvec, VP v[3] -- or NULL: the
+ * initial point).  dims8 = unknowns, points, lines, VPs, R1 blocks, edges, 0, 0; with every other output NULL only dims8
+ * is written.  unk_nd per unknown (0: constant); blk_unk per R1 block its unknown; edge_info3 per edge kind, a, b
+ * (unknowns) and edge_w its ScaledLoss weight; sp6_out the point; res_blk 2 per R1 block, res_edge 3 per edge; cost;
+ * g4 and diag16 per unknown (the 4 x 4 diagonal block, undamped); off16 per edge (rho' J_a^T J_b, 4 x 4 row-major). */
+int lt_fn_assoc_eval(const lt_assoc_input *in, const lt_assoc_config *cfg, const double *sp6, int64_t *dims8,
+                     int32_t *unk_nd, int32_t *blk_unk, int32_t *edge_info3, double *edge_w, double *sp6_out,
+                     double *res_blk, double *res_edge, double *cost, double *g4, double *diag16, double *off16);
+/* LineLinker2d(LineLinker2dConfig()).check_connection(l1, l2) on two segments (x1 y1 x2 y2): the default 2D linker of
+ * GlobalAssociator::test_linetrack_validity.  1 connected, 0 not.  No context, no device. */
+int lt_fn_assoc_link2d(const double l1[4], const double l2[4]);
+/* For tests: the linear solve alone.  n_unk unknowns of nd (0 .. 4) dimensions with their (damped) diagonal blocks
+ * diag16, n_edge off-diagonal blocks off16 between the unknowns edge_a, edge_b (rows a's, columns b's), the right-hand
+ * side rhs4: preconditioned CG from x = 0 in the defined orders.  x4 = the step; *iters; *end = 0 converged, 1 the cap,
+ * 2 p.Ap or r0.z0 not positive and finite, 3 a pivot of a diagonal block; rz2 (may be NULL) = r0.z0 and the last r.z */
+int lt_fn_assoc_pcg(int64_t n_unk, const int32_t *nd, const double *diag16, int64_t n_edge, const int32_t *edge_a,
+                    const int32_t *edge_b, const double *off16, const double *rhs4, double eta, int32_t cap, double *x4,
+                    int32_t *iters, int32_t *end, double *rz2);
+
 /* Counters of the last device run: [0] connections tested, [1] candidates, [2] ordered candidate
  * pairs swept by the scoring kernel (sum n_tris^2), [3] valid edges, [4] graph nodes,
  * [5] graph edges, [6] tracks, [7] nodes. */

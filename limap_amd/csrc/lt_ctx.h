@@ -289,6 +289,15 @@ struct BaState {  // bundle adjustment with free poses (lt_ba.cpp): the result o
   DevBuf d_k, d_pose, d_sp, d_st, d_blk, d_idx, d_lin, d_sums, d_S, d_LT, d_vec, d_chunk, d_status;
 };
 
+struct AsState {  // global point-line association (lt_assoc.cpp): the result of the last lt_assoc_arrays
+  double timers[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // lt_assoc_get_timers
+  std::vector<double> pts, params, vps;  // per point track, per line track, per vanishing point
+  double cost[2] = {0, 0};
+  int iters = 0, code = 0;
+  long long cg_iters = 0;
+  DevBuf d_cam, d_sp, d_unk, d_blk, d_edge, d_adj, d_lin, d_mat, d_vec, d_chunk, d_status;
+};
+
 struct SfmState {  // visual neighbours (lt_sfm.cpp): the result of the last lt_sfm_neighbors
   double timers[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // lt_sfm_get_timers
   std::vector<long long> nb_off;                // per image its neighbours (image indices)
@@ -566,6 +575,7 @@ struct lt_ctx {
   lt_host::RefineState rf;
   lt_host::LocState lc;
   lt_host::BaState ba;
+  lt_host::AsState as;
   lt_host::SfmState sf;
   lt_host::UdState ud;
   lt_host::S2State s2;

@@ -823,3 +823,7 @@ from . import hybrid_localization as _loc  # noqa: E402
 from .hybrid_localization import *  # noqa: E402,F401,F403
 
 __all__ += _loc.__all__
+
+# limap.optimize.global_pl_association: the joint optimisation of points, lines and vanishing points under soft
+# association constraints
+from . import global_pl_association as _assoc  # noqa: E402,F401  (it adds its names to this module, whichever loads first)

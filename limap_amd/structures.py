@@ -17,7 +17,8 @@ import numpy as np
 
 from . import _capi
 
-__all__ = ["Point2d", "Junction", "PL_Bipartite2dConfig", "PL_Bipartite2d", "compute_2d_bipartites",
+__all__ = ["VP2d", "VPLine_Bipartite2d", "VPLine_Bipartite3d", "PL_Bipartite3d", "GetAllBipartites_VPLine2d",
+           "Point2d", "Junction", "PL_Bipartite2dConfig", "PL_Bipartite2d", "compute_2d_bipartites",
            "compute_junctions", "lines2d_array", "timers"]
 
 _context = _capi.per_device_contexts()
@@ -174,7 +175,115 @@ def _junctions(lines_list, kps_list, cfg, device=0, candidates=False, sizes=Fals
     return (out, cands, sizes) if want_sizes else (out, cands)
 
 
-class PL_Bipartite2d:
+class _Graph:
+    """pl_bipartite_base.h: the bipartite graph over `points_` and `lines_` keyed by id, with the two adjacency maps.  The
+    node types, their insertion and their dict form are the subclasses'"""
+
+    def _check(self, cond, msg):
+        if not cond:
+            raise ValueError("Check failed: " + msg)
+
+    def _new_point_id(self):
+        return max(self.points_) + 1 if self.points_ else 0
+
+    def _new_line_id(self):
+        return max(self.lines_) + 1 if self.lines_ else 0
+
+    def add_edge(self, point_id, line_id):
+        self._check(self.exist_point(point_id), "exist_point(point_id)")
+        self._check(self.exist_line(line_id), "exist_line(line_id)")
+        self.np2l_[int(point_id)].add(int(line_id))
+        self.nl2p_[int(line_id)].add(int(point_id))
+
+    def delete_edge(self, point_id, line_id):
+        self._check(self.exist_point(point_id), "exist_point(point_id)")
+        self._check(self.exist_line(line_id), "exist_line(line_id)")
+        self.np2l_[int(point_id)].discard(int(line_id))
+        self.nl2p_[int(line_id)].discard(int(point_id))
+
+    def clear_edges(self):
+        for s in self.np2l_.values():
+            s.clear()
+        for s in self.nl2p_.values():
+            s.clear()
+
+    def delete_point(self, point_id):
+        self._check(self.exist_point(point_id), "exist_point(point_id)")
+        for line_id in self.np2l_.pop(int(point_id)):
+            self.nl2p_[line_id].discard(int(point_id))
+        del self.points_[int(point_id)]
+
+    def delete_line(self, line_id):
+        self._check(self.exist_line(line_id), "exist_line(line_id)")
+        for point_id in self.nl2p_.pop(int(line_id)):
+            self.np2l_[point_id].discard(int(line_id))
+        del self.lines_[int(line_id)]
+
+    def clear_points(self):
+        self.points_.clear()
+        self.clear_edges()
+        self.np2l_.clear()
+
+    def clear_lines(self):
+        self.lines_.clear()
+        self.clear_edges()
+        self.nl2p_.clear()
+
+    def reset(self):
+        self.points_.clear()
+        self.lines_.clear()
+        self.np2l_.clear()
+        self.nl2p_.clear()
+
+    def count_lines(self):
+        return len(self.lines_)
+
+    def count_points(self):
+        return len(self.points_)
+
+    def count_edges(self):
+        return sum(len(s) for s in self.nl2p_.values())
+
+    def exist_point(self, point_id):
+        return int(point_id) in self.points_
+
+    def exist_line(self, line_id):
+        return int(line_id) in self.lines_
+
+    def get_dict_points(self):
+        return {k: self.points_[k] for k in sorted(self.points_)}
+
+    def get_all_points(self):
+        return [self.points_[k] for k in sorted(self.points_)]
+
+    def get_point_ids(self):
+        return sorted(self.points_)
+
+    def get_line_ids(self):
+        return sorted(self.lines_)
+
+    def pdegree(self, point_id):
+        self._check(self.exist_point(point_id), "exist_point(point_id)")
+        return len(self.np2l_[int(point_id)])
+
+    def ldegree(self, line_id):
+        self._check(self.exist_line(line_id), "exist_line(line_id)")
+        return len(self.nl2p_[int(line_id)])
+
+    def neighbor_lines(self, point_id):
+        self._check(self.exist_point(point_id), "exist_point(point_id)")
+        return sorted(self.np2l_[int(point_id)])
+
+    def neighbor_points(self, line_id):
+        self._check(self.exist_line(line_id), "exist_line(line_id)")
+        return sorted(self.nl2p_[int(line_id)])
+
+    def point(self, point_id):
+        self._check(self.exist_point(point_id), "exist_point(point_id)")
+        return self.points_[int(point_id)]
+
+
+class PL_Bipartite2d(_Graph):
     """structures/pl_bipartite.h:35-60 over pl_bipartite_base.h: points, lines and their edges, keyed by id"""
 
     def __init__(self, cfg=None, device=0):
@@ -207,34 +316,6 @@ class PL_Bipartite2d:
                 "nl2p_": {k: set(self.nl2p_[k]) for k in sorted(self.nl2p_)}}
 
     # ---- insertion and deletion (pl_bipartite_base.cc:37-209) ---------------------------------------------------------
-    def _check(self, cond, msg):
-        if not cond:
-            raise ValueError("Check failed: " + msg)
-
-    def _new_point_id(self):
-        return max(self.points_) + 1 if self.points_ else 0
-
-    def _new_line_id(self):
-        return max(self.lines_) + 1 if self.lines_ else 0
-
-    def add_edge(self, point_id, line_id):
-        self._check(self.exist_point(point_id), "exist_point(point_id)")
-        self._check(self.exist_line(line_id), "exist_line(line_id)")
-        self.np2l_[int(point_id)].add(int(line_id))
-        self.nl2p_[int(line_id)].add(int(point_id))
-
-    def delete_edge(self, point_id, line_id):
-        self._check(self.exist_point(point_id), "exist_point(point_id)")
-        self._check(self.exist_line(line_id), "exist_line(line_id)")
-        self.np2l_[int(point_id)].discard(int(line_id))
-        self.nl2p_[int(line_id)].discard(int(point_id))
-
-    def clear_edges(self):
-        for s in self.np2l_.values():
-            s.clear()
-        for s in self.nl2p_.values():
-            s.clear()
-
     def add_point(self, p, point_id=-1, neighbors=()):
         point_id = int(point_id)
         if point_id == -1:
@@ -261,18 +342,6 @@ class PL_Bipartite2d:
             self.np2l_[int(point_id)].add(line_id)
         return line_id
 
-    def delete_point(self, point_id):
-        self._check(self.exist_point(point_id), "exist_point(point_id)")
-        for line_id in self.np2l_.pop(int(point_id)):
-            self.nl2p_[line_id].discard(int(point_id))
-        del self.points_[int(point_id)]
-
-    def delete_line(self, line_id):
-        self._check(self.exist_line(line_id), "exist_line(line_id)")
-        for point_id in self.nl2p_.pop(int(line_id)):
-            self.np2l_[point_id].discard(int(line_id))
-        del self.lines_[int(line_id)]
-
     def update_point(self, point_id, p):
         self._check(self.exist_point(point_id), "exist_point(point_id)")
         self.points_[int(point_id)] = p if isinstance(p, Point2d) else Point2d(p)
@@ -280,16 +349,6 @@ class PL_Bipartite2d:
     def update_line(self, line_id, line):
         self._check(self.exist_line(line_id), "exist_line(line_id)")
         self.lines_[int(line_id)] = lines2d_array([line]).reshape(2, 2)
-
-    def clear_points(self):
-        self.points_.clear()
-        self.clear_edges()
-        self.np2l_.clear()
-
-    def clear_lines(self):
-        self.lines_.clear()
-        self.clear_edges()
-        self.nl2p_.clear()
 
     def init_points(self, points, ids=None):
         ids = list(range(len(points))) if ids is None or len(ids) == 0 else list(ids)
@@ -306,65 +365,12 @@ class PL_Bipartite2d:
             self.lines_[i] = row.reshape(2, 2).copy()
             self.nl2p_[i] = set()
 
-    def reset(self):
-        self.points_.clear()
-        self.lines_.clear()
-        self.np2l_.clear()
-        self.nl2p_.clear()
-
     # ---- const operations (pl_bipartite_base.h:61-87) -------------------------------------------------------------------
-    def count_lines(self):
-        return len(self.lines_)
-
-    def count_points(self):
-        return len(self.points_)
-
-    def count_edges(self):
-        return sum(len(s) for s in self.nl2p_.values())
-
-    def exist_point(self, point_id):
-        return int(point_id) in self.points_
-
-    def exist_line(self, line_id):
-        return int(line_id) in self.lines_
-
-    def get_dict_points(self):
-        return {k: self.points_[k] for k in sorted(self.points_)}
-
     def get_dict_lines(self):
         return {k: self.line(k) for k in sorted(self.lines_)}
 
-    def get_all_points(self):
-        return [self.points_[k] for k in sorted(self.points_)]
-
     def get_all_lines(self):
         return [self.line(k) for k in sorted(self.lines_)]
-
-    def get_point_ids(self):
-        return sorted(self.points_)
-
-    def get_line_ids(self):
-        return sorted(self.lines_)
-
-    def pdegree(self, point_id):
-        self._check(self.exist_point(point_id), "exist_point(point_id)")
-        return len(self.np2l_[int(point_id)])
-
-    def ldegree(self, line_id):
-        self._check(self.exist_line(line_id), "exist_line(line_id)")
-        return len(self.nl2p_[int(line_id)])
-
-    def neighbor_lines(self, point_id):
-        self._check(self.exist_point(point_id), "exist_point(point_id)")
-        return sorted(self.np2l_[int(point_id)])
-
-    def neighbor_points(self, line_id):
-        self._check(self.exist_line(line_id), "exist_line(line_id)")
-        return sorted(self.nl2p_[int(line_id)])
-
-    def point(self, point_id):
-        self._check(self.exist_point(point_id), "exist_point(point_id)")
-        return self.points_[int(point_id)]
 
     def line(self, line_id):
         from .base import Line2d
@@ -472,3 +478,194 @@ def compute_junctions(all_2d_lines, all_keypoints, cfg=None, device=0):
         return {}
     res = _junctions(lines, kps, cfg, device)
     return {i: r[0] for i, r in zip(img_ids, res)}
+
+
+# ---- the containers of limap.runners.pointline_association (structures/vpline_bipartite.h, pl_bipartite.h:62-75): the
+# same graph over other node types.  Host containers: nothing here runs on the device ----
+class VP2d:
+    """vplib/vptrack.h:19: Feature2dWith3dIndex<V3D> -- a homogeneous 2D vanishing point and the id of its 3D track"""
+
+    def __init__(self, p=None, point3D_id=-1):
+        if isinstance(p, dict):
+            p, point3D_id = p.get("p"), p.get("point3D_id", -1)
+        elif isinstance(p, VP2d):
+            p, point3D_id = p.p, p.point3D_id
+        self.p = np.zeros(3) if p is None else np.array(p, np.float64).reshape(3)
+        self.point3D_id = int(point3D_id)
+
+    def as_dict(self):
+        return {"p": self.p.copy(), "point3D_id": self.point3D_id}
+
+
+class _Bipartite(_Graph):
+    """pl_bipartite_base.h over other node types: `_point(v)` / `_line(v)` build a node from an object or its dict"""
+
+    def __init__(self, d=None):
+        self.points_, self.lines_, self.np2l_, self.nl2p_ = {}, {}, {}, {}
+        if isinstance(d, _Bipartite):
+            d = d.as_dict()
+        if d is not None:
+            self._load(d)
+
+    def _load(self, d):
+        for key in ("points_", "lines_"):
+            if key not in d:
+                raise RuntimeError(f'Error! Key "{key}" does not exist!')
+        self.points_ = {int(k): self._point(v) for k, v in d["points_"].items()}
+        self.lines_ = {int(k): self._line(v) for k, v in d["lines_"].items()}
+        self.np2l_ = {int(k): {int(x) for x in v} for k, v in d.get("np2l_", {}).items()}
+        self.nl2p_ = {int(k): {int(x) for x in v} for k, v in d.get("nl2p_", {}).items()}
+        for k in self.points_:
+            self.np2l_.setdefault(k, set())
+        for k in self.lines_:
+            self.nl2p_.setdefault(k, set())
+
+    def as_dict(self):
+        return {"points_": {k: self.points_[k].as_dict() for k in sorted(self.points_)},
+                "lines_": {k: self._line_dict(self.lines_[k]) for k in sorted(self.lines_)},
+                "np2l_": {k: set(self.np2l_[k]) for k in sorted(self.np2l_)},
+                "nl2p_": {k: set(self.nl2p_[k]) for k in sorted(self.nl2p_)}}
+
+    def _line_dict(self, v):
+        return v.as_dict()
+
+    def add_point(self, p, point_id=-1, neighbors=()):
+        point_id = int(point_id)
+        if point_id == -1:
+            point_id = self._new_point_id()
+        self._check(not self.exist_point(point_id), "!exist_point(point_id)")
+        self.points_[point_id] = self._point(p)
+        self.np2l_[point_id] = set()
+        for line_id in neighbors:
+            self.add_edge(point_id, line_id)
+        return point_id
+
+    def add_line(self, line, line_id=-1, neighbors=()):
+        line_id = int(line_id)
+        if line_id == -1:
+            line_id = self._new_line_id()
+        self._check(not self.exist_line(line_id), "!exist_line(line_id)")
+        self.lines_[line_id] = self._line(line)
+        self.nl2p_[line_id] = set()
+        for point_id in neighbors:
+            self.add_edge(point_id, line_id)
+        return line_id
+
+    def update_point(self, point_id, p):
+        self._check(self.exist_point(point_id), "exist_point(point_id)")
+        self.points_[int(point_id)] = self._point(p)
+
+    def update_line(self, line_id, line):
+        self._check(self.exist_line(line_id), "exist_line(line_id)")
+        self.lines_[int(line_id)] = self._line(line)
+
+    def init_lines(self, lines, ids=None):
+        ids = list(range(len(lines))) if ids is None or len(ids) == 0 else [int(i) for i in ids]
+        self._check(len(ids) == len(lines), "lines.size() == ids.size()")
+        for ln, i in zip(lines, ids):
+            self.add_line(ln, i)
+
+    def line(self, line_id):
+        self._check(self.exist_line(line_id), "exist_line(line_id)")
+        return self.lines_[int(line_id)]
+
+    def get_dict_lines(self):
+        return {k: self.lines_[k] for k in sorted(self.lines_)}
+
+    def get_all_lines(self):
+        return [self.lines_[k] for k in sorted(self.lines_)]
+
+
+def _line2d(v):
+    from .base import Line2d
+    if isinstance(v, Line2d):
+        return Line2d(v.start, v.end)
+    a = np.array(v, np.float64).reshape(2, 2)
+    return Line2d(a[0], a[1])
+
+
+def _track(cls, v):
+    """a copy of a track object, or the track of its dict"""
+    if isinstance(v, dict):
+        if cls.__name__ == "LineTrack":
+            from .base import Line3d, Line2d
+            ln = v["line"]
+            ln = Line3d(ln["start"], ln["end"]) if isinstance(ln, dict) else Line3d(np.asarray(ln)[0], np.asarray(ln)[1])
+            t = cls(ln, v["image_id_list"], v["line_id_list"], [_line2d(x if not isinstance(x, dict) else
+                                                                         np.array([x["start"], x["end"]])) for x in v["line2d_list"]])
+            for k in ("node_id_list", "score_list"):
+                if k in v:
+                    setattr(t, k, list(v[k]))
+            if "line3d_list" in v:
+                t.line3d_list = [Line3d(x["start"], x["end"]) if isinstance(x, dict) else Line3d(np.asarray(x)[0], np.asarray(x)[1])
+                                 for x in v["line3d_list"]]
+            return t
+        if cls.__name__ == "PointTrack":
+            return cls(v["p"], v["image_id_list"], v["p2d_id_list"], v["p2d_list"])
+        return cls(v)
+    return v
+
+
+class VPLine_Bipartite2d(_Bipartite):
+    """structures/vpline_bipartite.h:20-27: VP2d nodes and Line2d nodes"""
+    _point = staticmethod(VP2d)
+    _line = staticmethod(_line2d)
+
+    def _line_dict(self, v):
+        return np.array([v.start, v.end])
+
+
+class PL_Bipartite3d(_Bipartite):
+    """structures/pl_bipartite.h:62-75: PointTrack nodes and LineTrack nodes"""
+
+    @staticmethod
+    def _point(v):
+        from .base import PointTrack
+        return _track(PointTrack, v)
+
+    @staticmethod
+    def _line(v):
+        from .base import LineTrack
+        return _track(LineTrack, v)
+
+    def get_point_cloud(self):
+        return [np.asarray(self.points_[k].p, float).copy() for k in sorted(self.points_)]
+
+    def get_line_cloud(self):
+        return [self.lines_[k].line for k in sorted(self.lines_)]
+
+
+class VPLine_Bipartite3d(_Bipartite):
+    """structures/vpline_bipartite.h:29-36: VPTrack nodes and LineTrack nodes"""
+
+    @staticmethod
+    def _point(v):
+        from .vplib import VPTrack
+        return VPTrack(v)
+
+    _line = staticmethod(PL_Bipartite3d._line)
+
+
+def GetAllBipartites_VPLine2d(all_2d_lines, vpresults, vptracks):
+    """vpline_bipartite.cc:97-158: per image the 2D lines, the 2D VPs that belong to a 3D track (VP2d with the track's
+    index) and an edge from every line with such a VP"""
+    if len(all_2d_lines) != len(vpresults):
+        raise ValueError("Check failed: all_2d_lines.size() == vpresults.size()")
+    m = {int(i): [-1] * r.count_vps() for i, r in vpresults.items()}
+    for track_id, t in enumerate(vptracks):
+        for img_id, vp2d_id in t.supports:
+            m[int(img_id)][int(vp2d_id)] = track_id
+    out = {}
+    for img_id in sorted(all_2d_lines):
+        bpt = VPLine_Bipartite2d()
+        lines = all_2d_lines[img_id]
+        bpt.init_lines([_line2d(x) for x in lines2d_array(lines).reshape(-1, 2, 2)])
+        res = vpresults[img_id]
+        for vp2d_id in range(res.count_vps()):
+            if m[int(img_id)][vp2d_id] >= 0:
+                bpt.add_point(VP2d(res.vps[vp2d_id], m[int(img_id)][vp2d_id]), vp2d_id)
+        for line_id in range(bpt.count_lines()):
+            if res.HasVP(line_id) and m[int(img_id)][res.GetVPLabel(line_id)] >= 0:
+                bpt.add_edge(res.GetVPLabel(line_id), line_id)
+        out[int(img_id)] = bpt
+    return out

@@ -23,7 +23,7 @@ import numpy as np
 from . import _capi
 from .structures import lines2d_array
 
-__all__ = ["VPResult", "BaseVPDetectorConfig", "BaseVPDetectorOptions", "DefaultVPDetectorOptions", "JLinkageConfig",
+__all__ = ["VPTrack", "MergeVPTracksByDirection", "GlobalVPTrackConstructorConfig", "GlobalVPTrackConstructor", "VPResult", "BaseVPDetectorConfig", "BaseVPDetectorOptions", "DefaultVPDetectorOptions", "JLinkageConfig",
            "JLinkage", "get_vp_detector", "detect_vps", "detect_vps_host", "timers"]
 
 _context = _capi.per_device_contexts()
@@ -256,3 +256,190 @@ def get_vp_detector(cfg_vp_detector, n_jobs=1):
     if method == "jlinkage":
         return JLinkage(cfg_vp_detector, options)
     raise NotImplementedError  # "progressivex" (a learned third party) and anything else
+
+
+# ---- 3D vanishing-point tracks (vplib/vptrack.h, global_vptrack_constructor.h): host containers and set-up of
+# limap.runners.pointline_association ----
+class VPTrack:
+    """vplib/vptrack.h:21-35: a 3D direction and its supports (image id, 2D VP id)"""
+
+    def __init__(self, direction=None, supports=None):
+        if isinstance(direction, VPTrack):
+            direction, supports = direction.direction, direction.supports
+        elif isinstance(direction, dict):
+            direction, supports = direction.get("direction"), direction.get("supports")
+        self.direction = np.zeros(3) if direction is None else np.array(direction, np.float64).reshape(3)
+        self.supports = [] if supports is None else [(int(a), int(b)) for a, b in supports]
+
+    def as_dict(self):
+        return {"direction": self.direction.copy(), "supports": list(self.supports)}
+
+    def length(self):
+        return len(self.supports)
+
+
+def _angle_deg(a, b):
+    c = min(abs(float(np.dot(a, b))), 1.0)
+    return float(np.degrees(np.arccos(c)))
+
+
+def MergeVPTracksByDirection(tracks, th_angle_merge=1.0):
+    """vptrack.cc:21-104: union-find over the pairs within th_angle_merge that share no image; the merged direction is
+    the length-weighted mean in input order, normalised; sorted by length (stable)"""
+    tracks = [VPTrack(t) for t in tracks]
+    n = len(tracks)
+    parent = [-1] * n
+    images = [set(i for i, _ in t.supports) for t in tracks]
+
+    def root(i):
+        while parent[i] != -1:
+            i = parent[i]
+        return i
+    for i in range(n - 1):
+        ri = root(i)  # read once per i, as upstream does
+        for j in range(i + 1, n):
+            rj = root(j)
+            if ri == rj:
+                continue
+            if _angle_deg(tracks[i].direction, tracks[j].direction) > th_angle_merge:
+                continue
+            if images[ri] & images[rj]:
+                continue
+            if len(images[ri]) < len(images[rj]):
+                parent[ri] = rj
+                images[rj] |= images[ri]
+                images[ri] = set()
+            else:
+                parent[rj] = ri
+                images[ri] |= images[rj]
+                images[rj] = set()
+    labels, k = [-1] * n, 0
+    for i in range(n):
+        if parent[i] == -1:
+            labels[i] = k
+            k += 1
+    for i in range(n):
+        if labels[i] == -1:
+            labels[i] = labels[root(i)]
+    out = [VPTrack() for _ in range(k)]
+    for i, t in enumerate(tracks):
+        o = out[labels[i]]
+        if not o.supports:
+            o.direction = t.direction.copy()
+        else:
+            o.direction = (o.direction * o.length() + t.direction * t.length()) / (o.length() + t.length())
+        o.supports += t.supports
+    for o in out:
+        o.direction = o.direction / np.linalg.norm(o.direction)
+    return sorted(out, key=lambda t: -t.length())
+
+
+class GlobalVPTrackConstructorConfig:
+    """global_vptrack_constructor.h:20-31"""
+
+    def __init__(self, d=None):
+        self.min_common_lines, self.th_angle_verify, self.min_track_length = 3, 10.0, 5
+        for k, typ in (("min_common_lines", int), ("th_angle_verify", float), ("min_track_length", int)):
+            if d and k in d and d[k] is not None:
+                setattr(self, k, typ(d[k]))
+
+
+def _direction_from_vp(view, vp):
+    """CameraView::get_direction_from_vp: R^T K^-1 vp, normalised"""
+    d = view.R().T @ np.linalg.solve(view.K(), np.asarray(vp, float))
+    return d / np.linalg.norm(d)
+
+
+def _track_labels(nodes, edges):
+    """ComputeTrackLabels (base/graph.cc:168-244): the edges (a, b, similarity) by descending (similarity, a, b); two
+    components join unless they share an image, the one with fewer images under the other; the roots are numbered in
+    node order"""
+    n = len(nodes)
+    parent = [-1] * n
+    imgs = [{nd[0]} for nd in nodes]
+
+    def root(i):
+        while parent[i] != -1:
+            i = parent[i]
+        return i
+    for a, b, _ in sorted(edges, key=lambda e: (e[2], e[0], e[1]), reverse=True):
+        ra, rb = root(a), root(b)
+        if ra == rb or imgs[ra] & imgs[rb]:
+            continue
+        if len(imgs[ra]) < len(imgs[rb]):
+            ra, rb = rb, ra
+        parent[rb] = ra
+        imgs[ra] |= imgs[rb]
+        imgs[rb] = set()
+    labels, k = [-1] * n, 0
+    for i in range(n):
+        if parent[i] == -1:
+            labels[i] = k
+            k += 1
+    return [labels[root(i)] for i in range(n)]
+
+
+class GlobalVPTrackConstructor:
+    """global_vptrack_constructor.h:33-51"""
+
+    def __init__(self, cfg=None):
+        self.config_ = cfg if isinstance(cfg, GlobalVPTrackConstructorConfig) else GlobalVPTrackConstructorConfig(cfg)
+        self.vpresults_ = {}
+
+    def Init(self, vpresults):
+        self.vpresults_ = {int(k): VPResult(v) for k, v in vpresults.items()}
+
+    def ClusterLineTracks(self, linetracks, imagecols):
+        """global_vptrack_constructor.cc:8-120"""
+        cfg, res = self.config_, self.vpresults_
+        counters = {}
+        for track in linetracks:
+            edges = set()
+            n = track.count_lines()
+            for i in range(n - 1):
+                i1, l1 = int(track.image_id_list[i]), int(track.line_id_list[i])
+                if not res[i1].HasVP(l1):
+                    continue
+                node1 = (i1, res[i1].GetVPLabel(l1))
+                d1 = _direction_from_vp(imagecols.camview(i1), res[i1].GetVP(l1))
+                for j in range(i + 1, n):
+                    i2, l2 = int(track.image_id_list[j]), int(track.line_id_list[j])
+                    if i1 == i2 or not res[i2].HasVP(l2):
+                        continue
+                    node2 = (i2, res[i2].GetVPLabel(l2))
+                    edge = (node1, node2) if i1 < i2 else (node2, node1)
+                    if edge in edges:
+                        continue
+                    d2 = _direction_from_vp(imagecols.camview(i2), res[i2].GetVP(l2))
+                    if _angle_deg(d1, d2) > cfg.th_angle_verify:
+                        continue
+                    edges.add(edge)
+            for e in edges:
+                counters[e] = counters.get(e, 0) + 1
+        nodes, index, gedges = [], {}, []
+        for e in sorted(counters):
+            if counters[e] < cfg.min_common_lines:
+                continue
+            ids = []
+            for nd in e:
+                if nd not in index:
+                    index[nd] = len(nodes)
+                    nodes.append(nd)
+                ids.append(index[nd])
+            gedges.append((ids[0], ids[1], counters[e]))
+        labels = _track_labels(nodes, gedges)
+        by_label = {}
+        for i, lb in enumerate(labels):
+            by_label.setdefault(lb, VPTrack()).supports.append(nodes[i])
+        out = []
+        for lb in sorted(by_label):
+            t = by_label[lb]
+            if t.length() < cfg.min_track_length:
+                continue
+            avg = np.zeros(3)
+            for img_id, vp_id in t.supports:
+                avg = avg + _direction_from_vp(imagecols.camview(img_id), res[img_id].GetVPbyCluster(vp_id))
+            avg = avg / float(t.length())
+            t.direction = avg / np.linalg.norm(avg)
+            out.append(t)
+        return sorted(out, key=lambda t: -t.length())
