@@ -6,13 +6,12 @@
 
 #include "lt_host.h"
 #include "lt_assoc.h"
+#include "lt_ingest.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <numeric>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include <omp.h>
@@ -71,15 +70,8 @@ int make_plan(const lt_assoc_input *inp, const lt_assoc_config *cfgp, Plan &pl, 
   if (!inp) { msg = "null input"; return 1; }
   const lt_assoc_input &in = *inp;
   const lt_assoc_config &cfg = *cfgp;
-  if (in.n_img < 0 || (in.n_img > 0 && (!in.img_ids || !in.kvec4 || !in.qvec4 || !in.tvec3))) { msg = "bad camera arrays"; return 1; }
-  if (!all_finite(in.kvec4, 4 * (long long)in.n_img) || !all_finite(in.qvec4, 4 * (long long)in.n_img) ||
-      !all_finite(in.tvec3, 3 * (long long)in.n_img)) {
-    msg = "non-finite camera";
-    return 1;
-  }
-  std::unordered_map<int, int> id2row;
-  for (int n = 0; n < in.n_img; ++n)
-    if (!id2row.emplace(in.img_ids[n], n).second) { msg = "image id " + std::to_string(in.img_ids[n]) + " appears twice"; return 1; }
+  IdRows id2row;
+  if (ingest_cams(in.n_img, in.img_ids, in.kvec4, in.qvec4, in.tvec3, id2row, msg)) return 1;
   if (in.n_pt < 0 || in.n_ln < 0 || in.n_vp < 0 || in.n_edge < 0) { msg = "bad counts"; return 1; }
   if (in.n_pt > 0) {
     msg = offsets_msg("point track", in.n_pt, in.pt_off);
@@ -118,7 +110,6 @@ int make_plan(const lt_assoc_input *inp, const lt_assoc_config *cfgp, Plan &pl, 
   pl.unk.assign((size_t)pl.NU, AsUnk{0, 0, 0, 0, 0, 0, {0, 0}});
   pl.sp0.assign(6 * (size_t)pl.NU, 0.0);
   const bool cpt = cfg.constant_point != 0, cln = cfg.constant_line != 0, cvp = cfg.constant_vp != 0;
-  std::vector<char> used((size_t)std::max(in.n_img, 1), 0);
   // R1.1 (global_associator.cc:182-187): only where the points are free; AddPointGeometricResiduals returns at once
   // without a weight
   const bool add_points = !cpt && cfg.lw_point > 0.0;
@@ -127,55 +118,26 @@ int make_plan(const lt_assoc_input *inp, const lt_assoc_config *cfgp, Plan &pl, 
     u.kind = kAsPoint;
     u.b0 = (int)pl.blk.size();
     for (int c = 0; c < 3; ++c) pl.sp0[6 * (size_t)n + c] = in.pt3[3 * n + c];
-    if (add_points)
-      for (long long i = in.pt_off[n]; i < in.pt_off[n + 1]; ++i) {
-        auto it = id2row.find(in.pt_img[i]);
-        if (it == id2row.end()) {
-          msg = "point track " + std::to_string(n) + ": image id " + std::to_string(in.pt_img[i]) + " is not in the collection";
-          return 1;
-        }
-        used[(size_t)it->second] = 1;
-        pl.blk.push_back(BaBlk{{in.pt_xy2[2 * i], in.pt_xy2[2 * i + 1], 0.0, 0.0}, cfg.lw_point, it->second, (int)n, 0, 0});
-      }
+    if (add_points && ingest_point_track(n, (int)n, in.pt_off, in.pt_img, in.pt_xy2, cfg.lw_point, id2row, pl.blk, msg)) return 1;
     u.nb = (int)pl.blk.size() - u.b0;
   }
   // R1.2 (:189-194): only where the lines are free; §19's order (sorted images, then list order) and weights
-  std::vector<int> order, ids;
+  SupportOrder so;
   std::vector<char> few((size_t)std::max(pl.NL, 1), 0);
   for (int64_t n = 0; n < in.n_ln; ++n) {
     const int ui = pl.NP + (int)n;
     AsUnk &u = pl.unk[(size_t)ui];
     u.kind = kAsLine;
     u.b0 = (int)pl.blk.size();
-    const double *l = in.line6 + 6 * n;
-    const double dx = l[0] - l[3], dy = l[1] - l[4], dz = l[2] - l[5];
-    if (!(std::sqrt((dx * dx + dy * dy) + dz * dz) > 0.0)) {
-      msg = "line track " + std::to_string(n) + ": the line has zero length";
-      return 1;
-    }
-    rf_minimal(l, pl.sp0.data() + 6 * (size_t)ui);
+    if (ingest_line_length("line track", n, in.line6 + 6 * n, msg)) return 1;
+    rf_minimal(in.line6 + 6 * n, pl.sp0.data() + 6 * (size_t)ui);
     const long long a = in.ln_off[n];
-    const int K = (int)(in.ln_off[n + 1] - a);
-    order.resize((size_t)K);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return in.ln_img[a + x] < in.ln_img[a + y]; });
-    ids.assign(in.ln_img + a, in.ln_img + a + K);
-    std::sort(ids.begin(), ids.end());
-    const int n_images = (int)(std::unique(ids.begin(), ids.end()) - ids.begin());
+    int n_images;
+    if (ingest_supports("line track", n, in.ln_img + a, (int)(in.ln_off[n + 1] - a), id2row, so, &n_images, msg, [&](int, int x, int row) {
+          if (!cln) pl.blk.push_back(line_blk(in.l2d4 + 4 * (a + x), row, ui));
+        }))
+      return 1;
     few[(size_t)n] = n_images < cfg.min_num_images;
-    for (int k = 0; k < K; ++k) {
-      const long long src = a + order[(size_t)k];
-      auto it = id2row.find(in.ln_img[src]);
-      if (it == id2row.end()) {
-        msg = "line track " + std::to_string(n) + ": image id " + std::to_string(in.ln_img[src]) + " is not in the collection";
-        return 1;
-      }
-      if (cln) continue;
-      used[(size_t)it->second] = 1;
-      const double *g = in.l2d4 + 4 * src;
-      const double ex = g[2] - g[0], ey = g[3] - g[1];
-      pl.blk.push_back(BaBlk{{g[0], g[1], g[2], g[3]}, std::sqrt(ex * ex + ey * ey) / 30.0, it->second, ui, 0, 1});
-    }
     u.nb = (int)pl.blk.size() - u.b0;
   }
   pl.NB = (int)pl.blk.size();
@@ -224,19 +186,15 @@ int make_plan(const lt_assoc_input *inp, const lt_assoc_config *cfgp, Plan &pl, 
       for (int c = 0; c < 3; ++c) v[c] = v[c] / nv;
     }
   }
-  // the cameras of the images that carry an R1 block
+  // every camera row; those of the images that carry an R1 block are checked
+  std::vector<char> used((size_t)std::max(in.n_img, 1), 0);
+  for (const BaBlk &b : pl.blk) used[(size_t)b.cam] = 1;
   pl.kvec.assign(4 * (size_t)std::max(in.n_img, 1), 0.0);
   pl.pose.assign(7 * (size_t)std::max(in.n_img, 1), 0.0);
-  for (int r = 0; r < in.n_img; ++r) {
-    const double *k = in.kvec4 + 4 * r, *q = in.qvec4 + 4 * r;
-    if (used[(size_t)r]) {
-      if (k[0] == 0.0 || k[1] == 0.0) { msg = "image " + std::to_string(in.img_ids[r]) + ": a focal length is 0"; return 1; }
-      if (q[0] == 0.0 && q[1] == 0.0 && q[2] == 0.0 && q[3] == 0.0) { msg = "image " + std::to_string(in.img_ids[r]) + ": zero quaternion"; return 1; }
-    }
-    for (int x = 0; x < 4; ++x) pl.kvec[4 * (size_t)r + x] = k[x];
-    lm_normalise_q(q, pl.pose.data() + 7 * (size_t)r);
-    for (int x = 0; x < 3; ++x) pl.pose[7 * (size_t)r + 4 + x] = in.tvec3[3 * r + x];
-  }
+  for (int r = 0; r < in.n_img; ++r)
+    if (ingest_cam_row(in.img_ids, in.kvec4, in.qvec4, in.tvec3, r, used[(size_t)r] != 0, pl.kvec.data() + 4 * (size_t)r,
+                       pl.pose.data() + 7 * (size_t)r, msg))
+      return 1;
   return 0;
 }
 
@@ -254,8 +212,8 @@ struct HostTables {
 void bind_plan(const Plan &pl, AsDev &d) {
   d = AsDev{};
   d.NU = pl.NU; d.NP = pl.NP; d.NL = pl.NL; d.NV = pl.NV; d.NB = pl.NB; d.NE = pl.NE;
-  d.n_chunks = std::max(1, (pl.NB + pl.NE + kAsChunk - 1) / kAsChunk);
-  d.n_uchunks = std::max(1, (pl.NU + kAsChunk - 1) / kAsChunk);
+  d.n_chunks = lm_chunks_of((long long)pl.NB + pl.NE);
+  d.n_uchunks = lm_chunks_of(pl.NU);
   d.alpha = pl.alpha;
 }
 AsStatus first_status(const Plan &pl) {
@@ -297,40 +255,12 @@ void host_tables(const Plan &pl, HostTables &h) {
 }
 
 // ---- the host twins of the kernels ----
-// the reduction of a wave64 per chunk of 256 items: lane stride, then the xor tree.  item(i, &a, &b) adds item i's terms
+// the chunked reduction over the solve's chunk table (lm_chunks_host, lm_totals_host)
 template <class F>
 void host_chunks(const AsDev &d, int n_items, int n_chunks, int stride, int nt, F item) {
-#pragma omp parallel for num_threads(nt) schedule(static)
-  for (int ch = 0; ch < n_chunks; ++ch) {
-    double part[kAsWave][2], out[2];
-    const int base = ch * kAsChunk;
-    for (int l = 0; l < kAsWave; ++l) {
-      double a = 0.0, b = 0.0;
-      for (int i = l; i < kAsChunk && base + i < n_items; i += kAsWave) item(base + i, &a, &b);
-      part[l][0] = a;
-      part[l][1] = b;
-    }
-    lm_tree_host(part, 2, out);
-    d.chunk[ch] = out[0];
-    if (stride) d.chunk[stride + ch] = out[1];
-  }
+  lm_chunks_host(d.chunk, n_items, n_chunks, stride, nt, item);
 }
-// as_totals
-void host_totals(const AsDev &d, int n, int stride, double *a, double *b) {
-  double part[kAsWave][2], out[2];
-  for (int l = 0; l < kAsWave; ++l) {
-    double x = 0.0, y = 0.0;
-    for (int c = l; c < n; c += kAsWave) {
-      x = x + d.chunk[c];
-      y = y + d.chunk[stride + c];
-    }
-    part[l][0] = x;
-    part[l][1] = y;
-  }
-  lm_tree_host(part, 2, out);
-  *a = out[0];
-  *b = out[1];
-}
+void host_totals(const AsDev &d, int n, int stride, double *a, double *b) { lm_totals_host(d.chunk, n, stride, a, b); }
 void host_cost(const AsDev &d, int set, bool with_md, int nt) {
   host_chunks(d, d.NB + d.NE, d.n_chunks, d.n_chunks, nt, [&](int i, double *a, double *b) {
     double c, m;
@@ -536,35 +466,30 @@ int run_device(lt_ctx *ctx, const Plan &pl, Result &res, double timers[20]) {
   // the loop: its decisions are made on the device; `poll` batches -- the head of an attempt, cg_batch CG iterations, the
   // tail of an attempt -- are enqueued back to back, then the status record (128 bytes) comes back.  A kernel returns at
   // once unless the record is in its phase, so the result depends neither on the interval nor on the batch
-  const int poll = pl.kernel_timers ? 1 : pl.poll, B = pl.cg_batch, n_ev = as_events(B) + 1;
-  std::vector<hipEvent_t> ev;
-  struct EvGuard {
-    std::vector<hipEvent_t> &v;
-    ~EvGuard() { for (hipEvent_t e : v) if (e) (void)hipEventDestroy(e); }
-  } guard{ev};
-  if (pl.kernel_timers) {
-    ev.assign((size_t)n_ev, nullptr);
-    for (hipEvent_t &e : ev) HIPCHK(ctx, hipEventCreate(&e));
-  }
+  const int B = pl.cg_batch;
+  EventList ev(pl.kernel_timers ? as_events(B) + 1 : 0);
+  if (int rc = ev.create(ctx)) return rc;
   launch_as_init(st, d);
   AsStatus status = AsStatus{};
   long long launched = 0;
-  for (;;) {
-    for (int k = 0; k < poll; ++k, ++launched) launch_as_attempt(st, d, B, pl.kernel_timers ? ev.data() : nullptr);
-    HIPCHK(ctx, hipMemcpyAsync(&status, as.d_status.p, sizeof(AsStatus), hipMemcpyDeviceToHost, st));
-    if (int rc = stream_sync(ctx)) return rc;
-    if (pl.kernel_timers)
-      for (int x = 0; x + 1 < n_ev; ++x) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, ev[(size_t)x], ev[(size_t)x + 1]) != hipSuccess) continue;
-        int slot;  // the kernel between the events x and x + 1
-        if (x < kAsHeadKernels) slot = x;
-        else if (x < kAsHeadKernels + kAsCgKernels * B) slot = kAsHeadKernels + (x - kAsHeadKernels) % kAsCgKernels;
-        else slot = kAsHeadKernels + kAsCgKernels + (x - kAsHeadKernels - kAsCgKernels * B);
-        timers[4 + slot] += ms;
-      }
-    if (status.lm.done) break;
-  }
+  if (int rc = run_polled(
+          ctx, pl.kernel_timers ? 1 : pl.poll, as.d_status.p, status,
+          [&]() {
+            launch_as_attempt(st, d, B, pl.kernel_timers ? ev.data() : nullptr);
+            ev.mark_all();
+          },
+          [](const AsStatus &s) { return s.lm.done != 0; },
+          [&]() {
+            for (int x = 0; x + 1 < ev.size(); ++x) {
+              int slot;  // the kernel between the events x and x + 1
+              if (x < kAsHeadKernels) slot = x;
+              else if (x < kAsHeadKernels + kAsCgKernels * B) slot = kAsHeadKernels + (x - kAsHeadKernels) % kAsCgKernels;
+              else slot = kAsHeadKernels + kAsCgKernels + (x - kAsHeadKernels - kAsCgKernels * B);
+              timers[4 + slot] += ev.ms(x, x + 1);
+            }
+          },
+          &launched))
+    return rc;
   const double t2 = now_ms();
   timers[1] = t2 - t1;
   timers[3] = (double)launched;
@@ -750,7 +675,7 @@ int lt_fn_assoc_pcg(int64_t n_unk, const int32_t *nd, const double *diag16, int6
   d.NU = (int)n_unk;
   d.NE = (int)n_edge;
   d.n_chunks = 1;
-  d.n_uchunks = std::max(1, (d.NU + kAsChunk - 1) / kAsChunk);
+  d.n_uchunks = lm_chunks_of(d.NU);
   host_solver_tables(h);
   // the given blocks, the entries outside an unknown's dimensions zero
   std::vector<double> E(16 * (size_t)std::max<int64_t>(n_edge, 1), 0.0);

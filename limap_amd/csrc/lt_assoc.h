@@ -21,9 +21,9 @@
 
 namespace lt {
 
-constexpr int kAsWave = 64;        // lanes per chunk of the reductions, per vanishing point of k_as_diag_vp
-constexpr int kAsWidth = 16;       // lanes per point or line of k_as_diag (§19's group)
-constexpr int kAsChunk = 256;      // residual blocks per chunk of the cost, unknowns per chunk of a dot product
+constexpr int kAsWave = kBaWave;   // lanes per chunk of the reductions, per vanishing point of k_as_diag_vp
+constexpr int kAsWidth = kBaWidth; // lanes per point or line of k_as_diag (§19's group)
+constexpr int kAsChunk = kBaChunk; // residual blocks per chunk of the cost, unknowns per chunk of a dot product
 constexpr int kAsLinFields = 11;   // doubles per R1 block of a linearisation (SoA): r[2], rho', J[2][4]
 constexpr int kAsELinFields = 28;  // per association edge: r[3], rho', J_a[3][4], J_b[3][4]
 constexpr int kAsPollDefault = 4;  // attempts enqueued between two reads of the status record
@@ -284,26 +284,21 @@ LT_HD void as_struct_part(const AsDev &d, const AsUnk &un, int lane, double part
   for (int c = 0; c < kRfSums; ++c) part[c] = 0.0;
   for (int i = lane; i < un.nb; i += kAsWidth) {
     const int b = un.b0 + i;
-    const double r0 = as_lin(d, 0, b), r1 = as_lin(d, 1, b), rho1 = as_lin(d, 2, b);
-    double j0[4], j1[4];
-    for (int c = 0; c < 4; ++c) { j0[c] = as_lin(d, 3 + c, b); j1[c] = as_lin(d, 7 + c, b); }
-    int o = 0;
-    for (int x = 0; x < 4; ++x)
-      for (int y = x; y < 4; ++y, ++o) part[o] = part[o] + rho1 * (j0[x] * j0[y] + j1[x] * j1[y]);
-    for (int x = 0; x < 4; ++x) part[10 + x] = part[10 + x] + rho1 * (j0[x] * r0 + j1[x] * r1);
+    const double r[2] = {as_lin(d, 0, b), as_lin(d, 1, b)}, rho1 = as_lin(d, 2, b);
+    double J[2][4];
+    for (int c = 0; c < 4; ++c) { J[0][c] = as_lin(d, 3 + c, b); J[1][c] = as_lin(d, 7 + c, b); }
+    lm_block_add<2, 4>(r, rho1, J, part);
   }
 }
 // entry i of the adjacency list added to the 14 sums acc: rho' J^T J (upper triangle by rows) and rho' J^T r of the
 // unknown's side of the edge
 LT_HD void as_adj_add(const AsDev &d, int i, double acc[kRfSums]) {
   const int e = d.adj[2 * i], f0 = d.adj[2 * i + 1] ? 16 : 4;
-  const double r0 = as_elin(d, 0, e), r1 = as_elin(d, 1, e), r2 = as_elin(d, 2, e), rho1 = as_elin(d, 3, e);
-  double j0[4], j1[4], j2[4];
-  for (int c = 0; c < 4; ++c) { j0[c] = as_elin(d, f0 + c, e); j1[c] = as_elin(d, f0 + 4 + c, e); j2[c] = as_elin(d, f0 + 8 + c, e); }
-  int o = 0;
-  for (int x = 0; x < 4; ++x)
-    for (int y = x; y < 4; ++y, ++o) acc[o] = acc[o] + rho1 * ((j0[x] * j0[y] + j1[x] * j1[y]) + j2[x] * j2[y]);
-  for (int x = 0; x < 4; ++x) acc[10 + x] = acc[10 + x] + rho1 * ((j0[x] * r0 + j1[x] * r1) + j2[x] * r2);
+  const double r[3] = {as_elin(d, 0, e), as_elin(d, 1, e), as_elin(d, 2, e)}, rho1 = as_elin(d, 3, e);
+  double J[3][4];
+  for (int c = 0; c < 4; ++c)
+    for (int m = 0; m < 3; ++m) J[m][c] = as_elin(d, f0 + 4 * m + c, e);
+  lm_block_add<3, 4>(r, rho1, J, acc);
 }
 // k_as_diag, after the tree: the reduced R1 sums, then the unknown's edges in ascending edge order
 LT_HD void as_item_diag_store(const AsDev &d, int u, double acc[kRfSums]) {
@@ -317,40 +312,12 @@ LT_HD void as_vp_part(const AsDev &d, const AsUnk &un, int lane, double part[kRf
   for (int i = un.a0 + lane; i < un.a0 + un.na; i += kAsWave) as_adj_add(d, i, part);
 }
 
-// k_as_precond: the damped diagonal block A_u and its inverse by the recurrence of lm_step, column by column.
+// k_as_precond: the inverse of the damped diagonal block A_u (lm_inverse4), zero outside the unknown's dimensions.
 // false: a pivot is not positive or not finite
 LT_HD bool as_item_minv(const AsDev &d, int u) {
-  const int nd = d.unk[u].nd;
-  const double *A = d.A + (size_t)16 * u;
   double *M = d.Minv + (size_t)16 * u;
   for (int c = 0; c < 16; ++c) M[c] = 0.0;
-  double L[4][4];
-  for (int i = 0; i < nd; ++i)
-    for (int j = 0; j <= i; ++j) {
-      double sum = A[4 * i + j];
-      for (int k = 0; k < j; ++k) sum = sum - L[i][k] * L[j][k];
-      if (i == j) {
-        if (!lm_pivot_ok(sum)) return false;
-        L[i][i] = sqrt(sum);
-      } else {
-        L[i][j] = sum / L[j][j];
-      }
-    }
-  for (int c = 0; c < nd; ++c) {
-    double y[4], x[4];
-    for (int i = 0; i < nd; ++i) {
-      double sum = i == c ? 1.0 : 0.0;
-      for (int k = 0; k < i; ++k) sum = sum - L[i][k] * y[k];
-      y[i] = sum / L[i][i];
-    }
-    for (int i = nd - 1; i >= 0; --i) {
-      double sum = y[i];
-      for (int k = i + 1; k < nd; ++k) sum = sum - L[k][i] * x[k];
-      x[i] = sum / L[i][i];
-    }
-    for (int i = 0; i < nd; ++i) M[4 * i + c] = x[i];
-  }
-  return true;
+  return lm_inverse4(d.A + (size_t)16 * u, d.unk[u].nd, M);
 }
 LT_HD void as_item_damp(const AsDev &d, int u, double mu) {
   const int nd = d.unk[u].nd;
@@ -533,8 +500,8 @@ LT_HD void as_item_cost(const AsDev &d, int set, int i, bool with_md, double *co
         for (int l = 0; l < 4; ++l) sum = sum + as_lin(d, 3 + 4 * m + l, i) * dl[l];
         jd[m] = sum;
       }
-      const double r0 = as_lin(d, 0, i), r1 = as_lin(d, 1, i);
-      *md = as_lin(d, 2, i) * ((jd[0] * r0 + jd[1] * r1) + 0.5 * (jd[0] * jd[0] + jd[1] * jd[1]));
+      const double r[2] = {as_lin(d, 0, i), as_lin(d, 1, i)};
+      *md = lm_model_term<2>(jd, r, as_lin(d, 2, i));
     }
     return;
   }
@@ -550,8 +517,8 @@ LT_HD void as_item_cost(const AsDev &d, int set, int i, bool with_md, double *co
       for (int l = 0; l < 4; ++l) sum = sum + as_elin(d, 16 + 4 * m + l, ei) * db[l];
       jd[m] = sum;
     }
-    const double r0 = as_elin(d, 0, ei), r1 = as_elin(d, 1, ei), r2 = as_elin(d, 2, ei);
-    *md = as_elin(d, 3, ei) * (((jd[0] * r0 + jd[1] * r1) + jd[2] * r2) + 0.5 * ((jd[0] * jd[0] + jd[1] * jd[1]) + jd[2] * jd[2]));
+    const double r[3] = {as_elin(d, 0, ei), as_elin(d, 1, ei), as_elin(d, 2, ei)};
+    *md = lm_model_term<3>(jd, r, as_elin(d, 3, ei));
   }
 }
 

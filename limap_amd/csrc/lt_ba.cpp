@@ -6,14 +6,13 @@
 
 #include "lt_host.h"
 #include "lt_ba.h"
+#include "lt_ingest.h"
 
 #include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstdint>
-#include <numeric>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include <omp.h>
@@ -68,15 +67,8 @@ int check_config(const lt_ba_config *c, std::string &msg) {
 int make_plan(const Input &in, Plan &pl, std::string &msg) {
   if (check_config(in.cfg, msg)) return 1;
   const lt_ba_config &cfg = *in.cfg;
-  if (in.n_img < 0 || (in.n_img > 0 && (!in.img_ids || !in.k || !in.q || !in.t))) { msg = "bad camera arrays"; return 1; }
-  if (!all_finite(in.k, 4 * (long long)in.n_img) || !all_finite(in.q, 4 * (long long)in.n_img) ||
-      !all_finite(in.t, 3 * (long long)in.n_img)) {
-    msg = "non-finite camera";
-    return 1;
-  }
-  std::unordered_map<int, int> id2row;
-  for (int n = 0; n < in.n_img; ++n)
-    if (!id2row.emplace(in.img_ids[n], n).second) { msg = "image id " + std::to_string(in.img_ids[n]) + " appears twice"; return 1; }
+  IdRows id2row;
+  if (ingest_cams(in.n_img, in.img_ids, in.k, in.q, in.t, id2row, msg)) return 1;
   if (in.n_pt < 0 || in.n_ln < 0) { msg = "bad track counts"; return 1; }
   pl.constant_pose = cfg.constant_pose != 0;
   if (pl.constant_pose && in.n_ln > 0) {
@@ -121,57 +113,25 @@ int make_plan(const Input &in, Plan &pl, std::string &msg) {
     BaStruct &s = pl.st[(size_t)n];
     s = BaStruct{(int)pl.blk.size(), 0, 0, 0, 0, 0, {0, 0}};
     for (int c = 0; c < 3; ++c) pl.sp0[6 * (size_t)n + c] = in.pt3[3 * n + c];
-    if (add_points)
-      for (long long i = in.pt_off[n]; i < in.pt_off[n + 1]; ++i) {
-        auto it = id2row.find(in.pt_img[i]);
-        if (it == id2row.end()) {  // imagecols_.camview(img_id): std::map::at
-          msg = "point track " + std::to_string(n) + ": image id " + std::to_string(in.pt_img[i]) + " is not in the collection";
-          return 1;
-        }
-        BaBlk b{{in.pt_xy[2 * i], in.pt_xy[2 * i + 1], 0.0, 0.0}, cfg.lw_point, it->second, (int)n, 0, 0};
-        pl.blk.push_back(b);
-      }
+    if (add_points && ingest_point_track(n, (int)n, in.pt_off, in.pt_img, in.pt_xy, cfg.lw_point, id2row, pl.blk, msg)) return 1;
     s.nb = (int)pl.blk.size() - s.b0;
     s.constant = (cfg.constant_point != 0 || s.nb == 0) ? 1 : 0;  // without a block the point is no parameter of the problem
   }
-  std::vector<int> order, ids;
+  SupportOrder so;
   for (int64_t n = 0; n < in.n_ln; ++n) {
     const int si = pl.NP + (int)n;
     BaStruct &s = pl.st[(size_t)si];
     s = BaStruct{(int)pl.blk.size(), 0, 0, 0, 1, 0, {0, 0}};
-    const double *l = in.line6 + 6 * n;
-    const double dx = l[0] - l[3], dy = l[1] - l[4], dz = l[2] - l[5];
-    if (!(std::sqrt((dx * dx + dy * dy) + dz * dz) > 0.0)) {  // CHECK_GT(line.length(), 0.0) (infinite_line.cc:68)
-      msg = "line track " + std::to_string(n) + ": the line has zero length";
-      return 1;
-    }
-    rf_minimal(l, pl.sp0.data() + 6 * (size_t)si);
+    if (ingest_line_length("line track", n, in.line6 + 6 * n, msg)) return 1;
+    rf_minimal(in.line6 + 6 * n, pl.sp0.data() + 6 * (size_t)si);
     const long long a = in.ln_off[n];
     const int K = (int)(in.ln_off[n + 1] - a);
     if (K <= 0) { msg = "line track " + std::to_string(n) + " has no supports"; return 1; }  // THROW_CHECK_GT(line3ds.size(), 0)
-    if (cfg.num_outliers_aggregator < 0 || cfg.num_outliers_aggregator > 2 * K - 1) {
-      msg = "num_outliers " + std::to_string(cfg.num_outliers_aggregator) + " leaves the " + std::to_string(2 * K) +
-            " values of line track " + std::to_string(n);
+    int n_images;
+    if (ingest_outliers("line track", n, cfg.num_outliers_aggregator, K, msg) ||
+        ingest_supports("line track", n, in.ln_img + a, K, id2row, so, &n_images, msg,
+                        [&](int, int x, int row) { pl.blk.push_back(line_blk(in.l2d4 + 4 * (a + x), row, si)); }))
       return 1;
-    }
-    order.resize((size_t)K);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return in.ln_img[a + x] < in.ln_img[a + y]; });
-    ids.assign(in.ln_img + a, in.ln_img + a + K);
-    std::sort(ids.begin(), ids.end());
-    const int n_images = (int)(std::unique(ids.begin(), ids.end()) - ids.begin());  // count_images()
-    for (int k = 0; k < K; ++k) {
-      const long long src = a + order[(size_t)k];
-      auto it = id2row.find(in.ln_img[src]);
-      if (it == id2row.end()) {
-        msg = "line track " + std::to_string(n) + ": image id " + std::to_string(in.ln_img[src]) + " is not in the collection";
-        return 1;
-      }
-      const double *g = in.l2d4 + 4 * src;
-      const double ex = g[2] - g[0], ey = g[3] - g[1];
-      BaBlk b{{g[0], g[1], g[2], g[3]}, std::sqrt(ex * ex + ey * ey) / 30.0, it->second, si, 0, 1};  // ComputeLineWeights
-      pl.blk.push_back(b);
-    }
     s.nb = K;
     s.constant = (cfg.constant_line != 0 || n_images < cfg.min_num_images) ? 1 : 0;
   }
@@ -196,12 +156,8 @@ int make_plan(const Input &in, Plan &pl, std::string &msg) {
   for (int c = 0; c < pl.C; ++c) {
     const int r = rows[(size_t)c];
     row2cam[(size_t)r] = c;
-    const double *k = in.k + 4 * r, *q = in.q + 4 * r;
-    if (k[0] == 0.0 || k[1] == 0.0) { msg = "image " + std::to_string(in.img_ids[r]) + ": a focal length is 0"; return 1; }
-    if (q[0] == 0.0 && q[1] == 0.0 && q[2] == 0.0 && q[3] == 0.0) { msg = "image " + std::to_string(in.img_ids[r]) + ": zero quaternion"; return 1; }
-    for (int x = 0; x < 4; ++x) pl.kvec[4 * (size_t)c + x] = k[x];
-    lm_normalise_q(q, pl.pose0.data() + 7 * (size_t)c);  // CameraPose's constructor (camera.h:94-95)
-    for (int x = 0; x < 3; ++x) pl.pose0[7 * (size_t)c + 4 + x] = in.t[3 * r + x];
+    if (ingest_cam_row(in.img_ids, in.k, in.q, in.t, r, true, pl.kvec.data() + 4 * (size_t)c, pl.pose0.data() + 7 * (size_t)c, msg))
+      return 1;
   }
   for (BaBlk &b : pl.blk) b.cam = row2cam[(size_t)b.cam];
   // the (track, image) pairs of every structure in ascending image order, and the blocks of each pair in residual order
@@ -282,7 +238,7 @@ struct HostTables {
 void bind_plan(const Plan &pl, BaDev &d) {
   d.C = pl.C; d.NS = pl.NS; d.NB = pl.NB; d.NPair = pl.NPair;
   d.n = 6 * pl.C;
-  d.n_chunks = std::max(1, (pl.NB + kBaChunk - 1) / kBaChunk);
+  d.n_chunks = lm_chunks_of(pl.NB);
   d.alpha = pl.alpha;
 }
 
@@ -323,46 +279,16 @@ void host_tables(const Plan &pl, HostTables &h) {
 }
 
 // ---- the host twins of the kernels ----
-// k_ba_cost: one "wave" per chunk
+// k_ba_cost; k_ba_decide's reduction of the chunks
 void host_cost(const BaDev &d, int set, bool with_md, int nt) {
-#pragma omp parallel for num_threads(nt) schedule(static)
-  for (int ch = 0; ch < d.n_chunks; ++ch) {
-    double part[kLcWidth][kLcSums];
-    const int base = ch * kBaChunk;
-    for (int l = 0; l < kBaWave; ++l) {
-      double cost = 0.0, md = 0.0;
-      for (int i = l; i < kBaChunk && base + i < d.NB; i += kBaWave) {
-        double c, m;
-        ba_item_cost(d, set, base + i, with_md, &c, &m);
-        cost = cost + c;
-        md = md + m;
-      }
-      part[l][0] = cost;
-      part[l][1] = md;
-    }
-    double out[kLcSums];
-    lm_tree_host(part, 2, out);
-    d.chunk[ch] = out[0];
-    d.chunk[d.n_chunks + ch] = out[1];
-  }
+  lm_chunks_host(d.chunk, d.NB, d.n_chunks, d.n_chunks, nt, [&](int i, double *a, double *b) {
+    double c, m;
+    ba_item_cost(d, set, i, with_md, &c, &m);
+    *a = *a + c;
+    *b = *b + m;
+  });
 }
-// k_ba_decide's reduction of the chunks
-void host_totals(const BaDev &d, double *cost, double *md) {
-  double part[kLcWidth][kLcSums];
-  for (int l = 0; l < kBaWave; ++l) {
-    double c = 0.0, m = 0.0;
-    for (int ch = l; ch < d.n_chunks; ch += kBaWave) {
-      c = c + d.chunk[ch];
-      m = m + d.chunk[d.n_chunks + ch];
-    }
-    part[l][0] = c;
-    part[l][1] = m;
-  }
-  double out[kLcSums];
-  lm_tree_host(part, 2, out);
-  *cost = out[0];
-  *md = out[1];
-}
+void host_totals(const BaDev &d, double *cost, double *md) { lm_totals_host(d.chunk, d.n_chunks, d.n_chunks, cost, md); }
 // k_ba_linearize, k_ba_blocks, k_ba_images
 void host_linearise(const BaDev &d, int cur, int nt) {
 #pragma omp parallel for num_threads(nt) schedule(static)
@@ -651,20 +577,20 @@ int run_device(lt_ctx *ctx, const Plan &pl, Result &res, double timers[16]) {
     if (int rc = ev.create(ctx)) return rc;
   launch_ba_init(st, d);
   BaStatus status = BaStatus{};
-  const int poll = pl.kernel_timers ? 1 : pl.poll;
   long long launched = 0;
-  for (;;) {
-    for (int k = 0; k < poll; ++k, ++launched) {
-      launch_ba_attempt(st, d, pl.kernel_timers ? ev.e : nullptr);
-      if (pl.kernel_timers)
-        for (int x = 0; x < 10; ++x) ev.recorded[x] = true;
-    }
-    HIPCHK(ctx, hipMemcpyAsync(&status, ba.d_status.p, sizeof(BaStatus), hipMemcpyDeviceToHost, st));
-    if (int rc = stream_sync(ctx)) return rc;
-    if (pl.kernel_timers)
-      for (int x = 0; x < 9; ++x) timers[4 + x] += ev.ms(x, x + 1);
-    if (status.done) break;
-  }
+  if (int rc = run_polled(
+          ctx, pl.kernel_timers ? 1 : pl.poll, ba.d_status.p, status,
+          [&]() {
+            launch_ba_attempt(st, d, pl.kernel_timers ? ev.data() : nullptr);
+            if (pl.kernel_timers) ev.mark_all();
+          },
+          [](const BaStatus &s) { return s.done != 0; },
+          [&]() {
+            if (pl.kernel_timers)
+              for (int x = 0; x < 9; ++x) timers[4 + x] += ev.ms(x, x + 1);
+          },
+          &launched))
+    return rc;
   const double t2 = now_ms();
   timers[1] = t2 - t1;
   timers[3] = (double)launched;

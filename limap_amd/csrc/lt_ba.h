@@ -31,8 +31,8 @@ namespace lt {
 
 constexpr int kBaMaxImages = 128;    // LT_BA_MAX_IMAGES: images that carry residuals (k_ba_chol keeps two vectors of 6 x 128 doubles in LDS)
 constexpr int kBaWidth = 16;         // lanes per structure track of k_ba_blocks (§19's group)
-constexpr int kBaWave = 64;          // lanes per image of k_ba_images, per chunk of k_ba_cost, of k_ba_decide
-constexpr int kBaChunk = 256;        // residual blocks per chunk of the cost reduction
+constexpr int kBaWave = kLmWave;     // lanes per image of k_ba_images, per chunk of k_ba_cost, of k_ba_decide
+constexpr int kBaChunk = kLmChunk;   // residual blocks per chunk of the cost reduction (lm_chunks_host, lm_chunk_sums)
 constexpr int kBaCholThreads = 1024; // lanes of the one workgroup of k_ba_chol
 static_assert(6 * kBaMaxImages <= kBaCholThreads, "k_ba_chol gives every row of S a lane of its own");
 constexpr int kBaLinFields = 23;     // doubles per block of a linearisation (SoA): r[2], rho', J_cam[2][6], J_struct[2][4]
@@ -212,13 +212,10 @@ LT_HD void ba_struct_part(const BaDev &d, const BaStruct &st, int lane, double p
   for (int c = 0; c < kRfSums; ++c) part[c] = 0.0;
   for (int i = lane; i < st.nb; i += kBaWidth) {
     const int b = st.b0 + i;
-    const double r0 = ba_lin(d, 0, b), r1 = ba_lin(d, 1, b), rho1 = ba_lin(d, 2, b);
-    double j0[4], j1[4];
-    for (int c = 0; c < 4; ++c) { j0[c] = ba_lin(d, 15 + c, b); j1[c] = ba_lin(d, 19 + c, b); }
-    int o = 0;
-    for (int x = 0; x < 4; ++x)
-      for (int y = x; y < 4; ++y, ++o) part[o] = part[o] + rho1 * (j0[x] * j0[y] + j1[x] * j1[y]);
-    for (int x = 0; x < 4; ++x) part[10 + x] = part[10 + x] + rho1 * (j0[x] * r0 + j1[x] * r1);
+    const double r[2] = {ba_lin(d, 0, b), ba_lin(d, 1, b)}, rho1 = ba_lin(d, 2, b);
+    double J[2][4];
+    for (int c = 0; c < 4; ++c) { J[0][c] = ba_lin(d, 15 + c, b); J[1][c] = ba_lin(d, 19 + c, b); }
+    lm_block_add<2, 4>(r, rho1, J, part);
   }
 }
 // W of pair p (6 x 4, row-major): its blocks in residual order, from 0.0
@@ -240,51 +237,24 @@ LT_HD void ba_cam_part(const BaDev &d, int c, int lane, double part[kLcSums]) {
   for (int x = 0; x < kLcSums; ++x) part[x] = 0.0;
   for (int i = d.cam_blk_off[c] + lane; i < d.cam_blk_off[c + 1]; i += kBaWave) {
     const int b = d.cam_blk[i];
-    const double r0 = ba_lin(d, 0, b), r1 = ba_lin(d, 1, b), rho1 = ba_lin(d, 2, b);
-    double j0[6], j1[6];
-    for (int x = 0; x < 6; ++x) { j0[x] = ba_lin(d, 3 + x, b); j1[x] = ba_lin(d, 9 + x, b); }
-    int o = 0;
-    for (int x = 0; x < 6; ++x)
-      for (int y = x; y < 6; ++y, ++o) part[o] = part[o] + rho1 * (j0[x] * j0[y] + j1[x] * j1[y]);
-    for (int x = 0; x < 6; ++x) part[21 + x] = part[21 + x] + rho1 * (j0[x] * r0 + j1[x] * r1);
+    const double r[2] = {ba_lin(d, 0, b), ba_lin(d, 1, b)}, rho1 = ba_lin(d, 2, b);
+    double J[2][6];
+    for (int x = 0; x < 6; ++x) { J[0][x] = ba_lin(d, 3 + x, b); J[1][x] = ba_lin(d, 9 + x, b); }
+    lm_block_add<2, 6>(r, rho1, J, part);
   }
 }
 
-// k_ba_damp: V_s^{-1} of the damped block by its Cholesky factorisation (the recurrence of lm_step), column by column.
-// false: a pivot is not positive or not finite
+// k_ba_damp: V_s^{-1} of the damped block (lm_inverse4).  false: a pivot is not positive or not finite
 LT_HD bool ba_item_vinv(const BaDev &d, int s, double mu) {
   const BaStruct st = d.st[s];
   if (st.constant) return true;
   const int nd = st.kind ? 4 : 3;
-  double H[4][4], L[4][4];
+  double H[16];  // the lower triangle of V_s, its diagonal damped
   int o = 0;
   for (int i = 0; i < 4; ++i)
-    for (int j = i; j < 4; ++j, ++o) H[i][j] = H[j][i] = d.V[(size_t)10 * s + o];
-  for (int i = 0; i < nd; ++i)
-    for (int j = 0; j <= i; ++j) {
-      double sum = i == j ? lm_damp(H[i][i], mu) : H[i][j];
-      for (int k = 0; k < j; ++k) sum = sum - L[i][k] * L[j][k];
-      if (i == j) {
-        if (!lm_pivot_ok(sum)) return false;
-        L[i][i] = sqrt(sum);
-      } else {
-        L[i][j] = sum / L[j][j];
-      }
-    }
-  for (int c = 0; c < nd; ++c) {
-    double y[4], x[4];
-    for (int i = 0; i < nd; ++i) {
-      double sum = i == c ? 1.0 : 0.0;
-      for (int k = 0; k < i; ++k) sum = sum - L[i][k] * y[k];
-      y[i] = sum / L[i][i];
-    }
-    for (int i = nd - 1; i >= 0; --i) {
-      double sum = y[i];
-      for (int k = i + 1; k < nd; ++k) sum = sum - L[k][i] * x[k];
-      x[i] = sum / L[i][i];
-    }
-    for (int i = 0; i < nd; ++i) d.Vinv[(size_t)16 * s + 4 * i + c] = x[i];
-  }
+    for (int j = i; j < 4; ++j, ++o) H[4 * j + i] = d.V[(size_t)10 * s + o];
+  for (int i = 0; i < nd; ++i) H[5 * i] = lm_damp(H[5 * i], mu);
+  if (!lm_inverse4(H, nd, d.Vinv + (size_t)16 * s)) return false;
   // Y = W_p V_s^{-1} (6 x 4; a point's fourth column is 0) of the structure's pairs
   for (int p = st.p0; p < st.p0 + st.np; ++p)
     for (int e = 0; e < 24; ++e) {
@@ -384,8 +354,8 @@ LT_HD void ba_item_cost(const BaDev &d, int set, int bi, bool with_md, double *c
       for (int l = 0; l < 4; ++l) sum = sum + ba_lin(d, 15 + 4 * m + l, bi) * dsv[l];
       jd[m] = sum;
     }
-    const double r0 = ba_lin(d, 0, bi), r1 = ba_lin(d, 1, bi);
-    *md = ba_lin(d, 2, bi) * ((jd[0] * r0 + jd[1] * r1) + 0.5 * (jd[0] * jd[0] + jd[1] * jd[1]));
+    const double r[2] = {ba_lin(d, 0, bi), ba_lin(d, 1, bi)};
+    *md = lm_model_term<2>(jd, r, ba_lin(d, 2, bi));
   }
 }
 
@@ -506,10 +476,7 @@ LT_HD void ba_point_lin_part(const BaDev &d, const BaStruct &st, int lane, const
     double r[2], J[2][4];
     ba_pass<3>(b, d.kvec + 4 * b.cam, ba_pose(d, 0, b.cam), sp, d.alpha, 2, r, J);
     const double rho1 = ba_rho1(b, r[0] * r[0] + r[1] * r[1]);
-    int o = 0;
-    for (int x = 0; x < 4; ++x)
-      for (int y = x; y < 4; ++y, ++o) part[o] = part[o] + rho1 * (J[0][x] * J[0][y] + J[1][x] * J[1][y]);
-    for (int x = 0; x < 4; ++x) part[10 + x] = part[10 + x] + rho1 * (J[0][x] * r[0] + J[1][x] * r[1]);
+    lm_block_add<2, 4>(r, rho1, J, part);
   }
 }
 

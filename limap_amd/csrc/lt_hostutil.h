@@ -1,7 +1,7 @@
 // lt_hostutil.h -- the host toolkit of the modules around the triangulation core (lt_merge, lt_fit, lt_eval, lt_bpt,
 // lt_match, lt_vp, lt_refine, lt_sfm, the remerge of lt_tracks): stream synchronisation, HIP event timing, transfers of host
-// vectors, input checks and the counted-output launch loop.  A new module uses these, it does not bring its own
-// (DESIGN §20).  Included from lt_host.h.
+// vectors, input checks, the counted-output launch loop and the polled loop of the coupled solves.  A new module uses
+// these, it does not bring its own.  Included from lt_host.h.
 #pragma once
 
 #include "lt_ctx.h"
@@ -20,33 +20,40 @@ inline int stream_sync(lt_ctx *ctx) {
   return LT_OK;
 }
 
-// N HIP events of one call, destroyed on every return path.  ms(a, b) is 0 unless both events were recorded (and the
-// stream has passed them: callers synchronise first).
-template <int N>
-struct Events {
-  hipEvent_t e[N] = {};
-  bool recorded[N] = {};
-  Events() = default;
-  Events(const Events &) = delete;
-  Events &operator=(const Events &) = delete;
-  ~Events() {
+// The HIP events of one call, destroyed on every return path; their count is chosen at run time (EventList) or fixed
+// (Events<N>).  ms(a, b) is 0 unless both events were recorded (and the stream has passed them: callers synchronise
+// first).  A launch wrapper that records the events itself takes data(); its caller then says mark_all().
+struct EventList {
+  std::vector<hipEvent_t> e;
+  std::vector<char> recorded;
+  explicit EventList(int n) : e((size_t)n, nullptr), recorded((size_t)n, 0) {}
+  EventList(const EventList &) = delete;
+  EventList &operator=(const EventList &) = delete;
+  ~EventList() {
     for (hipEvent_t x : e)
       if (x) (void)hipEventDestroy(x);
   }
+  int size() const { return (int)e.size(); }
+  hipEvent_t *data() { return e.data(); }
   int create(lt_ctx *ctx) {
     for (hipEvent_t &x : e) HIPCHK(ctx, hipEventCreate(&x));
     return LT_OK;
   }
   int record(lt_ctx *ctx, int k) {
-    HIPCHK(ctx, hipEventRecord(e[k], ctx->stream));
-    recorded[k] = true;
+    HIPCHK(ctx, hipEventRecord(e[(size_t)k], ctx->stream));
+    recorded[(size_t)k] = 1;
     return LT_OK;
   }
+  void mark_all() { recorded.assign(recorded.size(), 1); }
   double ms(int a, int b) const {
     float v = 0.f;
-    if (!recorded[a] || !recorded[b] || hipEventElapsedTime(&v, e[a], e[b]) != hipSuccess) return 0.0;
+    if (!recorded[(size_t)a] || !recorded[(size_t)b] || hipEventElapsedTime(&v, e[(size_t)a], e[(size_t)b]) != hipSuccess) return 0.0;
     return v;
   }
+};
+template <int N>
+struct Events : EventList {
+  Events() : EventList(N) {}
 };
 
 template <class T>
@@ -121,6 +128,23 @@ int run_counted(lt_ctx *ctx, DevBuf &buf, size_t head, size_t item, unsigned lon
     capacity = n;
   }
   return fail(ctx, LT_ERR_STATE, "k_track_connect: the edge count kept growing between launches");
+}
+
+// The polled device loop of a solve whose decisions are made on the device: `poll` times launch() -- one attempt or
+// batch, whose kernels return at once when the solve has ended, so the result does not depend on the interval -- then
+// the status record comes back in one copy and the stream is synchronised; after() follows every synchronisation (the
+// callers add their event times there), and the loop ends when done(status).  *launched counts the calls of launch().
+// Nothing is allocated and nothing but the one copy is enqueued here.
+template <class Status, class Launch, class Done, class After>
+int run_polled(lt_ctx *ctx, int poll, const void *d_status, Status &status, Launch launch, Done done, After after,
+               long long *launched) {
+  for (*launched = 0;;) {
+    for (int k = 0; k < poll; ++k, ++*launched) launch();
+    HIPCHK(ctx, hipMemcpyAsync(&status, d_status, sizeof(Status), hipMemcpyDeviceToHost, ctx->stream));
+    if (int rc = stream_sync(ctx)) return rc;
+    after();
+    if (done(status)) return LT_OK;
+  }
 }
 
 }  // namespace lt_impl

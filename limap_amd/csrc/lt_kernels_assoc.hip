@@ -95,22 +95,11 @@ __global__ void __launch_bounds__(kAsWave) k_as_precond(AsDev d) {
   }
 }
 
-// the totals of the first n chunks: lane stride, then the xor tree
-__device__ __forceinline__ void as_totals(const AsDev &d, int n, int stride, double *a, double *b) {
-  double x = 0.0, y = 0.0;
-  for (int c = threadIdx.x; c < n; c += kAsWave) {
-    x = x + d.chunk[c];
-    y = y + d.chunk[stride + c];
-  }
-  *a = lm_group_sum<kAsWave>(x);
-  *b = lm_group_sum<kAsWave>(y);
-}
-
 __global__ void __launch_bounds__(kAsWave) k_as_cg_begin(AsDev d) {
   AsStatus st = *d.status;
   if (st.lm.done || st.phase != kAsHead) return;
   double rz, flag;
-  as_totals(d, d.n_uchunks, d.n_uchunks, &rz, &flag);
+  lm_totals(d.chunk, d.n_uchunks, d.n_uchunks, &rz, &flag);
   as_decide_begin(st, rz, flag != 0.0);
   if (threadIdx.x == 0) *d.status = st;
 }
@@ -129,7 +118,7 @@ __global__ void __launch_bounds__(kAsWave) k_as_alpha(AsDev d) {
   AsStatus st = *d.status;
   if (st.lm.done || st.phase != kAsCg) return;
   double pap, unused;
-  as_totals(d, d.n_uchunks, 0, &pap, &unused);
+  lm_totals(d.chunk, d.n_uchunks, 0, &pap, &unused);
   as_decide_alpha(st, pap);
   if (threadIdx.x == 0) *d.status = st;
 }
@@ -149,7 +138,7 @@ __global__ void __launch_bounds__(kAsWave) k_as_beta(AsDev d) {
   AsStatus st = *d.status;
   if (st.lm.done || st.phase != kAsCg) return;
   double rz, unused;
-  as_totals(d, d.n_uchunks, 0, &rz, &unused);
+  lm_totals(d.chunk, d.n_uchunks, 0, &rz, &unused);
   as_decide_beta(st, rz);
   if (threadIdx.x == 0) *d.status = st;
 }
@@ -176,16 +165,13 @@ __global__ void __launch_bounds__(kAsWave) k_as_cost(AsDev d, int mode) {
     if (!as_in_phase(st, kAsTail) || st->lm.bad) return;
     set = 1 - st->lm.cur;
   }
-  const int base = blockIdx.x * kAsChunk, nt = d.NB + d.NE;
-  double cost = 0.0, md = 0.0;
-  for (int i = threadIdx.x; i < kAsChunk && base + i < nt; i += kAsWave) {
+  double cost, md;
+  lm_chunk_sums(d.NB + d.NE, [&](int i, double *a, double *b) {
     double c, m;
-    as_item_cost(d, set, base + i, mode != 0, &c, &m);
-    cost = cost + c;
-    md = md + m;
-  }
-  cost = lm_group_sum<kAsWave>(cost);
-  md = lm_group_sum<kAsWave>(md);
+    as_item_cost(d, set, i, mode != 0, &c, &m);
+    *a = *a + c;
+    *b = *b + m;
+  }, &cost, &md);
   if (threadIdx.x == 0) {
     d.chunk[blockIdx.x] = cost;
     d.chunk[d.n_chunks + blockIdx.x] = md;
@@ -196,14 +182,12 @@ __global__ void __launch_bounds__(kAsWave) k_as_decide(AsDev d, int mode) {
   AsStatus st = *d.status;
   if (mode && (st.lm.done || st.phase != kAsTail)) return;
   double cost, md;
-  as_totals(d, d.n_chunks, d.n_chunks, &cost, &md);
+  lm_totals(d.chunk, d.n_chunks, d.n_chunks, &cost, &md);
   if (mode) ba_decide_step(st.lm, cost, md);
   else ba_decide_init(st.lm, cost);
   st.phase = kAsHead;
   if (threadIdx.x == 0) *d.status = st;
 }
-
-inline unsigned blocks_of(long long n, int per) { return (unsigned)((n + per - 1) / per > 0 ? (n + per - 1) / per : 1); }
 
 }  // namespace
 
@@ -217,11 +201,11 @@ void launch_as_attempt(hipStream_t s, const AsDev &d, int cg_batch, hipEvent_t *
   auto mark = [&]() {
     if (ev) (void)hipEventRecord(ev[e++], s);
   };
-  const dim3 wave(kAsWave), uch((unsigned)d.n_uchunks), per_u(blocks_of(d.NU, 256));
+  const dim3 wave(kAsWave), uch((unsigned)d.n_uchunks), per_u(lm_blocks_of(d.NU, 256));
   mark();
-  hipLaunchKernelGGL(k_as_linearize, dim3(blocks_of((long long)d.NB + d.NE, 256)), dim3(256), 0, s, d);
+  hipLaunchKernelGGL(k_as_linearize, dim3(lm_blocks_of((long long)d.NB + d.NE, 256)), dim3(256), 0, s, d);
   mark();
-  hipLaunchKernelGGL(k_as_diag, dim3(blocks_of((long long)d.NP + d.NL, 64 / kAsWidth)), dim3(64), 0, s, d);
+  hipLaunchKernelGGL(k_as_diag, dim3(lm_blocks_of((long long)d.NP + d.NL, 64 / kAsWidth)), dim3(64), 0, s, d);
   mark();
   if (d.NV > 0) hipLaunchKernelGGL(k_as_diag_vp, dim3((unsigned)d.NV), wave, 0, s, d);
   mark();

@@ -187,16 +187,13 @@ __global__ void __launch_bounds__(kBaWave) k_ba_cost(BaDev d, int mode) {
     if (st->done || st->bad) return;
     set = 1 - st->cur;
   }
-  const int base = blockIdx.x * kBaChunk;
-  double cost = 0.0, md = 0.0;
-  for (int i = threadIdx.x; i < kBaChunk && base + i < d.NB; i += kBaWave) {
+  double cost, md;
+  lm_chunk_sums(d.NB, [&](int i, double *a, double *b) {
     double c, m;
-    ba_item_cost(d, set, base + i, mode != 0, &c, &m);
-    cost = cost + c;
-    md = md + m;
-  }
-  cost = lm_group_sum<kBaWave>(cost);
-  md = lm_group_sum<kBaWave>(md);
+    ba_item_cost(d, set, i, mode != 0, &c, &m);
+    *a = *a + c;
+    *b = *b + m;
+  }, &cost, &md);
   if (threadIdx.x == 0) {
     d.chunk[blockIdx.x] = cost;
     d.chunk[d.n_chunks + blockIdx.x] = md;
@@ -206,13 +203,8 @@ __global__ void __launch_bounds__(kBaWave) k_ba_cost(BaDev d, int mode) {
 __global__ void __launch_bounds__(kBaWave) k_ba_decide(BaDev d, int mode) {
   BaStatus st = *d.status;
   if (mode && st.done) return;
-  double cost = 0.0, md = 0.0;
-  for (int c = threadIdx.x; c < d.n_chunks; c += kBaWave) {
-    cost = cost + d.chunk[c];
-    md = md + d.chunk[d.n_chunks + c];
-  }
-  cost = lm_group_sum<kBaWave>(cost);
-  md = lm_group_sum<kBaWave>(md);
+  double cost, md;
+  lm_totals(d.chunk, d.n_chunks, d.n_chunks, &cost, &md);
   if (mode) ba_decide_step(st, cost, md);
   else ba_decide_init(st, cost);
   if (threadIdx.x == 0) *d.status = st;
@@ -256,8 +248,6 @@ __global__ void __launch_bounds__(64) k_ba_point_lm(BaDev d, int max_iter, BaPtO
   }
 }
 
-inline unsigned blocks_of(long long n, int per) { return (unsigned)((n + per - 1) / per > 0 ? (n + per - 1) / per : 1); }
-
 }  // namespace
 
 void launch_ba_init(hipStream_t s, const BaDev &d) {
@@ -271,19 +261,19 @@ void launch_ba_attempt(hipStream_t s, const BaDev &d, hipEvent_t *ev) {
     if (ev) (void)hipEventRecord(ev[e++], s);
   };
   mark();
-  hipLaunchKernelGGL(k_ba_linearize, dim3(blocks_of(d.NB, 256)), dim3(256), 0, s, d);
+  hipLaunchKernelGGL(k_ba_linearize, dim3(lm_blocks_of(d.NB, 256)), dim3(256), 0, s, d);
   mark();
-  hipLaunchKernelGGL(k_ba_blocks, dim3(blocks_of(d.NS, 64 / kBaWidth)), dim3(64), 0, s, d);
+  hipLaunchKernelGGL(k_ba_blocks, dim3(lm_blocks_of(d.NS, 64 / kBaWidth)), dim3(64), 0, s, d);
   mark();
   hipLaunchKernelGGL(k_ba_images, dim3((unsigned)d.C), dim3(kBaWave), 0, s, d);
   mark();
-  hipLaunchKernelGGL(k_ba_damp, dim3(blocks_of(d.NS, 256)), dim3(256), 0, s, d);
+  hipLaunchKernelGGL(k_ba_damp, dim3(lm_blocks_of(d.NS, 256)), dim3(256), 0, s, d);
   mark();
   hipLaunchKernelGGL(k_ba_schur, dim3((unsigned)d.C, (unsigned)d.C), dim3(kBaWave), 0, s, d);
   mark();
   hipLaunchKernelGGL(k_ba_chol, dim3(1), dim3(kBaCholThreads), 0, s, d);
   mark();
-  hipLaunchKernelGGL(k_ba_backsub, dim3(blocks_of((long long)d.NS + d.C, 256)), dim3(256), 0, s, d);
+  hipLaunchKernelGGL(k_ba_backsub, dim3(lm_blocks_of((long long)d.NS + d.C, 256)), dim3(256), 0, s, d);
   mark();
   hipLaunchKernelGGL(k_ba_cost, dim3((unsigned)d.n_chunks), dim3(kBaWave), 0, s, d, 1);
   mark();
@@ -293,7 +283,7 @@ void launch_ba_attempt(hipStream_t s, const BaDev &d, hipEvent_t *ev) {
 
 void launch_ba_points(hipStream_t s, const BaDev &d, int max_iter, BaPtOut *out) {
   if (d.NS <= 0) return;
-  hipLaunchKernelGGL(k_ba_point_lm, dim3(blocks_of(d.NS, 64 / kBaWidth)), dim3(64), 0, s, d, max_iter, out);
+  hipLaunchKernelGGL(k_ba_point_lm, dim3(lm_blocks_of(d.NS, 64 / kBaWidth)), dim3(64), 0, s, d, max_iter, out);
 }
 
 }  // namespace lt

@@ -1,6 +1,7 @@
-// lt_lm.h -- the numerical core the minimisers of lt_refine.h, lt_loc.h and lt_ba.h share: the forward-mode
-// scalar, the damped step, the trust-region loop over a chart, the xor trees of the reductions, and the rotation, the
-// line projection and the quaternion normalisation more than one of them evaluates.  Every definition here is a
+// lt_lm.h -- the numerical core the minimisers of lt_refine.h, lt_loc.h, lt_ba.h and lt_assoc.h share: the
+// forward-mode scalar, the damped step, the trust-region loop over a chart, the xor trees of the reductions, the chunked
+// reduction and the block pieces of the coupled solves, and the rotation, the line projection and the quaternion
+// normalisation more than one of them evaluates.  Every definition here is a
 // bit-exactness contract -- the device equals its host twin bit for bit, and both equal the NumPy restatements of the
 // tests -- so each exists once: a new minimiser uses these, it does not bring its own.  Both sides compile them with
 // -ffp-contract=off.
@@ -230,6 +231,131 @@ __device__ __forceinline__ double lm_group_sum(double v) {
   return v;
 }
 #endif
+
+// ---- the chunked reduction of the coupled solves: two sums over any number of items in an order no
+// grid decides.  A wave64 owns a chunk of 256 items -- lane stride, then the xor tree -- and writes chunk[ch] and
+// chunk[stride + ch]; one wave then reduces the chunk results the same way.  item(i, &a, &b) adds item i's terms to the
+// lane's two sums.  With stride 0 there is one sum: the second is not stored, and its total repeats the first ----
+constexpr int kLmWave = 64, kLmChunk = 256;
+constexpr int lm_chunks_of(long long n) { return n > 0 ? (int)((n + kLmChunk - 1) / kLmChunk) : 1; }
+
+template <class F>
+inline void lm_chunks_host(double *chunk, int n_items, int n_chunks, int stride, int nt, F item) {
+#pragma omp parallel for num_threads(nt) schedule(static)
+  for (int ch = 0; ch < n_chunks; ++ch) {
+    double part[kLmWave][2], out[2];
+    const int base = ch * kLmChunk;
+    for (int l = 0; l < kLmWave; ++l) {
+      part[l][0] = part[l][1] = 0.0;
+      for (int i = l; i < kLmChunk && base + i < n_items; i += kLmWave) item(base + i, &part[l][0], &part[l][1]);
+    }
+    lm_tree_host(part, 2, out);
+    chunk[ch] = out[0];
+    if (stride) chunk[stride + ch] = out[1];
+  }
+}
+// the totals of the first n chunks
+inline void lm_totals_host(const double *chunk, int n, int stride, double *a, double *b) {
+  double part[kLmWave][2], out[2];
+  for (int l = 0; l < kLmWave; ++l) {
+    part[l][0] = part[l][1] = 0.0;
+    for (int c = l; c < n; c += kLmWave) {
+      part[l][0] = part[l][0] + chunk[c];
+      part[l][1] = part[l][1] + chunk[stride + c];
+    }
+  }
+  lm_tree_host(part, 2, out);
+  *a = out[0];
+  *b = out[1];
+}
+#ifdef __HIPCC__
+// device: the chunk of workgroup blockIdx.x, one wave64; every lane returns both sums
+template <class F>
+__device__ __forceinline__ void lm_chunk_sums(int n_items, F item, double *a, double *b) {
+  const int base = blockIdx.x * kLmChunk;
+  double x = 0.0, y = 0.0;
+  for (int i = threadIdx.x; i < kLmChunk && base + i < n_items; i += kLmWave) item(base + i, &x, &y);
+  *a = lm_group_sum<kLmWave>(x);
+  *b = lm_group_sum<kLmWave>(y);
+}
+// device: the totals of the first n chunks by one wave64
+__device__ __forceinline__ void lm_totals(const double *chunk, int n, int stride, double *a, double *b) {
+  double x = 0.0, y = 0.0;
+  for (int c = threadIdx.x; c < n; c += kLmWave) {
+    x = x + chunk[c];
+    y = y + chunk[stride + c];
+  }
+  *a = lm_group_sum<kLmWave>(x);
+  *b = lm_group_sum<kLmWave>(y);
+}
+// the workgroups a launch needs for n items, `per` each: one at least
+inline unsigned lm_blocks_of(long long n, int per) { return (unsigned)((n + per - 1) / per > 0 ? (n + per - 1) / per : 1); }
+#endif
+
+// ---- the pieces of a coupled linearisation ----
+// one residual block added to the sums of NC unknowns: rho' J^T J (upper triangle by rows), then rho' J^T r, the
+// products of the NR residuals paired as (j0 j0 + j1 j1) [+ j2 j2]
+template <int NR, int NC>
+LT_HD void lm_block_add(const double r[NR], double rho1, const double J[NR][NC], double acc[lm_sums(NC)]) {
+  static_assert(NR == 2 || NR == 3, "two or three residuals");
+  int o = 0;
+  for (int x = 0; x < NC; ++x)
+    for (int y = x; y < NC; ++y, ++o) {
+      double s = J[0][x] * J[0][y] + J[1][x] * J[1][y];
+      if (NR == 3) s = s + J[NR - 1][x] * J[NR - 1][y];
+      acc[o] = acc[o] + rho1 * s;
+    }
+  for (int x = 0; x < NC; ++x, ++o) {
+    double s = J[0][x] * r[0] + J[1][x] * r[1];
+    if (NR == 3) s = s + J[NR - 1][x] * r[NR - 1];
+    acc[o] = acc[o] + rho1 * s;
+  }
+}
+
+// a block's term of the model decrease, rho' ((J d) . r + |J d|^2 / 2), from jd = J d
+template <int NR>
+LT_HD double lm_model_term(const double jd[NR], const double r[NR], double rho1) {
+  static_assert(NR == 2 || NR == 3, "two or three residuals");
+  double jr = jd[0] * r[0] + jd[1] * r[1], jj = jd[0] * jd[0] + jd[1] * jd[1];
+  if (NR == 3) {
+    jr = jr + jd[NR - 1] * r[NR - 1];
+    jj = jj + jd[NR - 1] * jd[NR - 1];
+  }
+  return rho1 * (jr + 0.5 * jj);
+}
+
+// the inverse of a symmetric positive block with nd <= 4 unknowns by the Cholesky recurrence of lm_step, column by
+// column.  A and M are 4 x 4 by rows; the lower triangle of A's leading nd x nd part is read, the leading nd x nd part
+// of M is written.  false: a pivot is not positive or not finite (M is then as it was)
+LT_HD bool lm_inverse4(const double *A, int nd, double *M) {
+  double L[4][4];
+  for (int i = 0; i < nd; ++i)
+    for (int j = 0; j <= i; ++j) {
+      double sum = A[4 * i + j];
+      for (int k = 0; k < j; ++k) sum = sum - L[i][k] * L[j][k];
+      if (i == j) {
+        if (!lm_pivot_ok(sum)) return false;
+        L[i][i] = sqrt(sum);
+      } else {
+        L[i][j] = sum / L[j][j];
+      }
+    }
+  for (int c = 0; c < nd; ++c) {
+    double y[4], x[4];
+    for (int i = 0; i < nd; ++i) {
+      double sum = i == c ? 1.0 : 0.0;
+      for (int k = 0; k < i; ++k) sum = sum - L[i][k] * y[k];
+      y[i] = sum / L[i][i];
+    }
+    for (int i = nd - 1; i >= 0; --i) {
+      double sum = y[i];
+      for (int k = i + 1; k < nd; ++k) sum = sum - L[k][i] * x[k];
+      x[i] = sum / L[i][i];
+    }
+    for (int i = 0; i < nd; ++i) M[4 * i + c] = x[i];
+  }
+  return true;
+}
 
 // ---- geometry more than one minimiser evaluates ----
 // CameraPose's constructor normalises its quaternion once (camera.h:94-95)

@@ -8,6 +8,7 @@
 
 #include "lt_host.h"
 #include "lt_refine.h"
+#include "lt_ingest.h"
 
 #include <algorithm>
 #include <climits>
@@ -325,18 +326,6 @@ int check_config(const lt_refine_config *cfg, std::string &msg) {
   return 0;
 }
 
-int check_cams(int n_img, const int32_t *ids, const double *k, const double *q, const double *t,
-               std::unordered_map<int, int> &id2idx, std::string &msg) {
-  if (n_img < 0 || (n_img > 0 && (!ids || !k || !q || !t))) { msg = "bad camera arrays"; return 1; }
-  if (!all_finite(k, 4 * (size_t)n_img) || !all_finite(q, 4 * (size_t)n_img) || !all_finite(t, 3 * (size_t)n_img)) {
-    msg = "non-finite camera";
-    return 1;
-  }
-  for (int n = 0; n < n_img; ++n)
-    if (!id2idx.emplace(ids[n], n).second) { msg = "image id " + std::to_string(ids[n]) + " appears twice"; return 1; }
-  return 0;
-}
-
 // the checks upstream makes (or fails without) and the tables of the kernels
 int make_plan(const std::unordered_map<int, int> &id2idx, int64_t T, const double *line6, const int64_t *off,
               const int32_t *img, const double *l2d4, const double *l3d6, const lt_refine_config &cfg, Plan &pl,
@@ -361,39 +350,18 @@ int make_plan(const std::unordered_map<int, int> &id2idx, int64_t T, const doubl
   pl.src.resize((size_t)S);
   pl.l3d.assign(l3d6, l3d6 + 6 * (size_t)S);
   pl.line6.assign(line6, line6 + 6 * (size_t)T);
-  std::vector<int> order, ids;
+  SupportOrder so;
   for (int64_t n = 0; n < T; ++n) {
-    const double *l = line6 + 6 * n;
-    const double dx = l[0] - l[3], dy = l[1] - l[4], dz = l[2] - l[5];
-    if (!(std::sqrt((dx * dx + dy * dy) + dz * dz) > 0.0)) {  // CHECK_GT(line.length(), 0.0) (infinite_line.cc:68)
-      msg = "track " + std::to_string(n) + ": the line has zero length";
-      return 1;
-    }
     const long long a = off[n];
     const int K = (int)(off[n + 1] - a);
-    // values[num_outliers] and values[2 K - 1 - num_outliers] (infinite_line.cc:284-285)
-    if (cfg.num_outliers_aggregator < 0 || cfg.num_outliers_aggregator > 2 * K - 1) {
-      msg = "num_outliers " + std::to_string(cfg.num_outliers_aggregator) + " leaves the " + std::to_string(2 * K) +
-            " values of track " + std::to_string(n);
+    int n_images;
+    if (ingest_line_length("track", n, line6 + 6 * n, msg) || ingest_outliers("track", n, cfg.num_outliers_aggregator, K, msg) ||
+        ingest_supports("track", n, img + a, K, id2idx, so, &n_images, msg, [&](int k, int x, int row) {
+          pl.sup_cam[(size_t)(a + k)] = row;
+          pl.src[(size_t)(a + k)] = a + x;
+          for (int c = 0; c < 4; ++c) pl.l2d[4 * (size_t)(a + k) + c] = l2d4[4 * (a + x) + c];
+        }))
       return 1;
-    }
-    order.resize((size_t)K);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return img[a + x] < img[a + y]; });
-    ids.assign(img + a, img + a + K);
-    std::sort(ids.begin(), ids.end());
-    const int n_images = (int)(std::unique(ids.begin(), ids.end()) - ids.begin());  // count_images()
-    for (int k = 0; k < K; ++k) {
-      const long long src = a + order[(size_t)k];
-      auto it = id2idx.find(img[src]);
-      if (it == id2idx.end()) {  // imagecols_.camview(img_id): std::map::at
-        msg = "track " + std::to_string(n) + ": image id " + std::to_string(img[src]) + " is not in the collection";
-        return 1;
-      }
-      pl.sup_cam[(size_t)(a + k)] = it->second;
-      pl.src[(size_t)(a + k)] = src;
-      for (int c = 0; c < 4; ++c) pl.l2d[4 * (size_t)(a + k) + c] = l2d4[4 * src + c];
-    }
     pl.tracks[(size_t)n] = RfTrack{a, K, (cfg.constant_line != 0 || n_images < cfg.min_num_images) ? 1 : 0};
   }
   return 0;
@@ -833,7 +801,7 @@ int lt_refine_arrays(lt_ctx *ctx, int n_img, const int32_t *img_ids, const doubl
   std::string msg;
   std::unordered_map<int, int> id2idx;
   Plan pl;
-  if (check_config(cfg, msg) || check_cams(n_img, img_ids, kvec4, qvec4, tvec3, id2idx, msg) ||
+  if (check_config(cfg, msg) || ingest_cams(n_img, img_ids, kvec4, qvec4, tvec3, id2idx, msg) ||
       make_plan(id2idx, n_tracks, line6, off, img, line2d4, line3d6, *cfg, pl, msg))
     return fail(ctx, LT_ERR_ARGUMENT, who + ": " + msg);
   HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -914,7 +882,7 @@ int lt_refine_arrays_terms(lt_ctx *ctx, int n_img, const int32_t *img_ids, const
   hs.h = ctx->rf.hm_h;
   hs.w = ctx->rf.hm_w;
   for (size_t i = 0; i < ctx->rf.hm_ids.size(); ++i) hs.slot.emplace(ctx->rf.hm_ids[i], (int)i);
-  if (check_config(cfg, msg) || check_cams(n_img, img_ids, kvec4, qvec4, tvec3, id2idx, msg) ||
+  if (check_config(cfg, msg) || ingest_cams(n_img, img_ids, kvec4, qvec4, tvec3, id2idx, msg) ||
       make_plan(id2idx, n_tracks, line6, off, img, line2d4, line3d6, *cfg, pl, msg) ||
       make_terms_plan(pl, img, *terms, vp_flag, vp3, view_hw, &hs, tp, msg))
     return fail(ctx, LT_ERR_ARGUMENT, who + ": " + msg);
@@ -988,7 +956,7 @@ int lt_refine_arrays_feature(lt_ctx *ctx, int n_img, const int32_t *img_ids, con
   hs.h = ctx->rf.hm_h;
   hs.w = ctx->rf.hm_w;
   for (size_t i = 0; i < ctx->rf.hm_ids.size(); ++i) hs.slot.emplace(ctx->rf.hm_ids[i], (int)i);
-  if (check_config(cfg, msg) || check_cams(n_img, img_ids, kvec4, qvec4, tvec3, id2idx, msg) ||
+  if (check_config(cfg, msg) || ingest_cams(n_img, img_ids, kvec4, qvec4, tvec3, id2idx, msg) ||
       make_plan(id2idx, n_tracks, line6, off, img, line2d4, line3d6, *cfg, pl, msg) ||
       make_terms_plan(pl, img, *terms, vp_flag, vp3, view_hw, &hs, tp, msg))
     return fail(ctx, LT_ERR_ARGUMENT, who + ": " + msg);
@@ -1069,7 +1037,7 @@ int lt_fn_refine_host(int n_img, const int32_t *img_ids, const double *kvec4, co
   std::string msg;
   std::unordered_map<int, int> id2idx;
   Plan pl;
-  if (check_config(cfg, msg) || check_cams(n_img, img_ids, kvec4, qvec4, tvec3, id2idx, msg) ||
+  if (check_config(cfg, msg) || ingest_cams(n_img, img_ids, kvec4, qvec4, tvec3, id2idx, msg) ||
       make_plan(id2idx, n_tracks, line6, off, img, line2d4, line3d6, *cfg, pl, msg)) {
     g_host_error = "lt_fn_refine_host: " + msg;
     return LT_ERR_ARGUMENT;
@@ -1101,7 +1069,7 @@ int lt_fn_refine_host_terms(int n_img, const int32_t *img_ids, const double *kve
   TermsPlan tp;
   HmSet hs;
   if ((terms->use_heatmap && check_heatmaps(n_hm, hm_ids, hm_h, hm_w, hm_data, terms->texel_type, hs, msg)) ||
-      check_config(cfg, msg) || check_cams(n_img, img_ids, kvec4, qvec4, tvec3, id2idx, msg) ||
+      check_config(cfg, msg) || ingest_cams(n_img, img_ids, kvec4, qvec4, tvec3, id2idx, msg) ||
       make_plan(id2idx, n_tracks, line6, off, img, line2d4, line3d6, *cfg, pl, msg) ||
       make_terms_plan(pl, img, *terms, vp_flag, vp3, view_hw, &hs, tp, msg)) {
     g_host_error = "lt_fn_refine_host_terms: " + msg;
@@ -1139,7 +1107,7 @@ int lt_fn_refine_host_feature(int n_img, const int32_t *img_ids, const double *k
   HmSet hs;
   if (check_feature(terms, feat, msg) ||
       (terms->use_heatmap && check_heatmaps(n_hm, hm_ids, hm_h, hm_w, hm_data, terms->texel_type, hs, msg)) ||
-      check_config(cfg, msg) || check_cams(n_img, img_ids, kvec4, qvec4, tvec3, id2idx, msg) ||
+      check_config(cfg, msg) || ingest_cams(n_img, img_ids, kvec4, qvec4, tvec3, id2idx, msg) ||
       make_plan(id2idx, n_tracks, line6, off, img, line2d4, line3d6, *cfg, pl, msg) ||
       make_terms_plan(pl, img, *terms, vp_flag, vp3, view_hw, &hs, tp, msg) ||
       make_feat_plan(pl, id2idx, n_img, kvec4, qvec4, tvec3, off, img, line2d4, *terms, *feat, n_grids, grids, false, fp, msg)) {
@@ -1181,7 +1149,7 @@ int lt_fn_refine_eval_feature(int n_img, const int32_t *img_ids, const double *k
   FeatPlan fp;
   HmSet hs;
   std::vector<std::vector<FSample>> all;
-  if (check_cams(n_img, img_ids, kvec4, qvec4, tvec3, id2idx, msg) ||
+  if (ingest_cams(n_img, img_ids, kvec4, qvec4, tvec3, id2idx, msg) ||
       make_plan(id2idx, 1, line6, off, img, line2d4, l3d.data(), cfg, pl, msg) ||
       make_terms_plan(pl, img, *terms, nullptr, nullptr, nullptr, &hs, tp, msg) ||
       make_feat_plan(pl, id2idx, n_img, kvec4, qvec4, tvec3, off, img, line2d4, *terms, *feat, n_grids, grids, false, fp, msg, &all))

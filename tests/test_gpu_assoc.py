@@ -2,6 +2,7 @@
 (lt_fn_assoc_host) bit for bit -- points, line parameters, vanishing points, both costs, iterations, CG iteration totals
 and the code -- on the smallest shapes at which each kernel can go wrong.  Iteration caps of 30 or
 less."""
+import ctypes as C
 import glob
 import os
 
@@ -139,10 +140,22 @@ def test_repeated_runs_and_batch_sizes(ctx):
     s = sc.structured_scene(n_cams=4, seed=7)
     base = both(ctx, s, max_num_iterations=20, cg_eta=1e-6)
     assert base["cg_iterations"][0] > 2 * base["iterations"][0]  # more than one batch of two CG iterations per attempt
+    # the CG iterations of every attempt (host twin): with kernel_timers the record is read after every batch, and an
+    # attempt of n iterations takes max(1, ceil(n / cg_batch)) batches
+    _, _, tr = sc.run_host(s, sc.cfg_of(max_num_iterations=20, cg_eta=1e-6), 1, trace=64)
+    cg = tr["rec"][:, 5].astype(np.int64)
+    assert len(cg) == base["iterations"][0]
+    # kernel_timers at cg_batch 1 and 64: 14 and 329 events, the smallest and the largest count of the event holder
     for kw in (dict(), dict(poll_interval=1, cg_batch=1), dict(poll_interval=3, cg_batch=2), dict(poll_interval=7, cg_batch=64),
-               dict(kernel_timers=1)):
+               dict(kernel_timers=1), dict(kernel_timers=1, cg_batch=1), dict(kernel_timers=1, cg_batch=64)):
         rc, d = sc.run_device(ctx, s, sc.cfg_of(max_num_iterations=20, cg_eta=1e-6, **kw))
         assert rc == 0 and sc.same_bits(d, base), kw
+        if kw.get("kernel_timers"):
+            tm = np.zeros(20)
+            ctx.chk(ctx.L.lt_assoc_get_timers(ctx.h, _capi.ptr(tm, C.c_double)))
+            batch = kw.get("cg_batch", 4)  # kAsCgBatchDefault
+            assert np.isfinite(tm[4:17]).all() and (tm[4:17] >= 0.0).all(), (kw, tm)
+            assert tm[3] == np.maximum(1, -(-cg // batch)).sum(), (kw, tm[3], cg)
 
 
 def test_python_surface_on_the_device(ctx):
