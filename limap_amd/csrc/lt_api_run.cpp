@@ -3,6 +3,8 @@
 // its completion (finish_run) and the read-back of the per-node results (lt_download).
 #include "lt_host.h"
 
+#include <functional>
+
 using namespace lt;
 using namespace lt_impl;
 
@@ -393,6 +395,12 @@ int lt_run_device_async(lt_ctx *ctx) {
                      n_status, ln_job ? ctx->d_blk_surv.as<unsigned>() : nullptr);
 
   bool node_rec_valid = false;  // k_node_prefix of this run wrote the per-node scoring records (d_node_rec)
+  // Line-slot form: k_node_prefix also writes every candidate's scoring record and the placement launch lists the tiles
+  // (its second role), so k_cand_meta does not run and nothing writes cand_node.  That launch needs the scoring stage's
+  // buffers: it is enqueued where those are known, right in front of launch_score3 (place_args).
+  bool meta_fused = false;
+  std::function<void(const lt::PlaceLists *, hipEvent_t)> place_args;
+  static const bool ev_markers = getenv("LT_EV_MARKERS") != nullptr;  // plain event records instead of stop events (launch_score3)
   long long C_known = -1;  // candidate count once it is known on the host
   long long C_bound = 0;   // what sizes the compact arrays: the count, or an upper bound while it stays on the device
   int ev_gen_end = 3, ev_place_end = 4;  // events that close the generation / placement stage (see finish_run)
@@ -521,18 +529,6 @@ int lt_run_device_async(lt_ctx *ctx) {
     if (fast) {
       // rows of every block are sorted by line id: sort-free placement
       ENSURE(ctx, ctx->d_node_rec, 16 * (size_t)std::max<long long>(G, 1));
-      launch_node_prefix(st, G, ctx->d_node_img.as<int>(), ctx->d_seg_off.as<long long>(),
-                         ctx->d_nb_off.as<long long>(), ctx->d_blk_line_base.as<long long>(),
-                         ctx->d_cnt_bl.as<unsigned>(), ctx->d_base_bl.as<unsigned>(), ctx->d_ntris_u.as<unsigned>(),
-                         ctx->d_tri_off.as<long long>(), ctx->d_scan_status.as<unsigned long long>(),
-                         ctx->d_err.as<int>(), ctx->d_node_rec.p);  // tri_off = exclusive scan of the counts, in the same kernel
-      node_rec_valid = true;
-      ctx->cnt_bl_clean = true;
-      // Nothing below needs the candidate count on the host (the kernels read tri_off[G]; the grids of
-      // k_place / k_score3 do not depend on it) except the SIZE of the compact arrays.  While the trivial
-      // bound -- one candidate per staging slot -- fits kCountFreeBytes, the arrays get that size and the
-      // whole run is enqueued without a host round trip (the count then arrives with the error flag);
-      // otherwise (or with LT_TEST_SYNC_COUNT) one 8-byte copy + stream sync fetches the exact count.
       const long long bound = P;
       // (288 GB of HBM: a sixth of it may go to bound-sized arrays before a run pays a host round trip for its count --
       // at 2e8 match rows the bound costs 20 GB, and the round trip kept lt_run_device_async from returning before the
@@ -543,9 +539,28 @@ int lt_run_device_async(lt_ctx *ctx) {
       const bool perm_bound = !test_switch("LT_TEST_PLACE_COPY");
       const long long per_cand = (perm_bound ? 4 : (long long)(sizeof(CRec) + 8)) + 8 + 4 + 4 + (long long)cand_meta_bytes() +
                                  (long long)score_split_entry_bytes() * 256 / 64;
+      const bool count_free = !extras && ctx->h_pinned && bound * per_cand <= kCountFreeBytes && !test_switch("LT_TEST_SYNC_COUNT");
+      // the records are written before the count can reach the host: only where the bound sizes the arrays
+      // (LT_TEST_SEPARATE_CAND_META: k_cand_meta behind the placement here too, for comparison)
+      meta_fused = ln && count_free && perm_bound && ctx->n_blk > 0 && ctx->max_rows > 0 && bound > 0 &&
+                   !test_switch("LT_TEST_SEPARATE_CAND_META") && ctx->d_cand_meta.ensure(cand_meta_bytes() * (size_t)bound);
+      if (!meta_fused) (void)hipGetLastError();
+      launch_node_prefix(st, G, ctx->d_node_img.as<int>(), ctx->d_seg_off.as<long long>(),
+                         ctx->d_nb_off.as<long long>(), ctx->d_blk_line_base.as<long long>(),
+                         ctx->d_cnt_bl.as<unsigned>(), ctx->d_base_bl.as<unsigned>(), ctx->d_ntris_u.as<unsigned>(),
+                         ctx->d_tri_off.as<long long>(), ctx->d_scan_status.as<unsigned long long>(),
+                         ctx->d_err.as<int>(), ctx->d_node_rec.p,
+                         meta_fused ? ctx->d_cand_meta.p : nullptr);  // tri_off = exclusive scan of the counts, in the same kernel
+      node_rec_valid = true;
+      ctx->cnt_bl_clean = true;
+      // Nothing below needs the candidate count on the host (the kernels read tri_off[G]; the grids of
+      // k_place / k_score3 do not depend on it) except the SIZE of the compact arrays.  While the trivial
+      // bound -- one candidate per staging slot -- fits kCountFreeBytes, the arrays get that size and the
+      // whole run is enqueued without a host round trip (the count then arrives with the error flag);
+      // otherwise (or with LT_TEST_SYNC_COUNT) one 8-byte copy + stream sync fetches the exact count.
       if (extras) {
         C_known = staged_total;  // the counting run of stage B already brought the count to the host
-      } else if (ctx->h_pinned && bound * per_cand <= kCountFreeBytes && !test_switch("LT_TEST_SYNC_COUNT")) {
+      } else if (count_free) {
         C_known = -1;
         C_bound = bound;
       } else {
@@ -594,13 +609,16 @@ int lt_run_device_async(lt_ctx *ctx) {
     ENSURE(ctx, ctx->d_score, 8 * Cn); ENSURE(ctx, ctx->d_edge_flag, 4 * Cn); ENSURE(ctx, ctx->d_cand_node, 4 * Cn);
     ctx->cand_cap = (long long)Cn;
     if (fast) {
+      place_args = [=](const lt::PlaceLists *lists, hipEvent_t ev_stop) {
       launch_place(st, ctx->n_blk, ctx->max_rows, ctx->d_m_off.as<long long>(), ctx->d_blk_img.as<int>(),
                    ctx->d_seg_off.as<long long>(), ctx->d_blk_line_base.as<long long>(),
                    ctx->d_base_bl.as<unsigned>(), ctx->d_wave_count.as<unsigned>(), ctx->d_tri_off.as<long long>(),
                    ctx->d_st_c.as<CRec>(), ctx->d_st_l.as<double>(), ctx->d_st_key.as<unsigned>(),
-                   ctx->d_cand.as<CRec>(), ctx->d_lite.as<double>(), ctx->d_cand_node.as<unsigned>(), group_base,
+                   ctx->d_cand.as<CRec>(), ctx->d_lite.as<double>(), lists ? nullptr : ctx->d_cand_node.as<unsigned>(), group_base,
                    perm_mode ? ctx->d_place_perm.as<unsigned>() : nullptr, ctx->d_blk_surv.as<unsigned>(),
-                   ctx->d_blk_rnd0.as<unsigned>(), ln ? ctx->d_round_count.as<unsigned>() : nullptr);
+                   ctx->d_blk_rnd0.as<unsigned>(), ln ? ctx->d_round_count.as<unsigned>() : nullptr, lists, ev_stop);
+      };
+      if (!meta_fused) place_args(nullptr, nullptr);
     } else {
       ENSURE(ctx, ctx->d_keys, 4 * Cn); ENSURE(ctx, ctx->d_rows, 4 * Cn);
       ENSURE(ctx, ctx->d_skeys, 4 * Cn); ENSURE(ctx, ctx->d_srows, 4 * Cn);
@@ -621,8 +639,9 @@ int lt_run_device_async(lt_ctx *ctx) {
                      ctx->d_cand_node.as<unsigned>());
     }
     // ... and the one in front of k_score3 ends the placement stage (it then includes k_cand_meta)
+    // (line-slot form: either one rides on the placement launch as its stop event, below)
     if (fine_score && C_bound > 0) ev_place_end = 11;
-    else if (sampled) HIPCHK(ctx, hipEventRecord(ev[4], st));
+    else if (sampled && !meta_fused) HIPCHK(ctx, hipEventRecord(ev[4], st));
     if (gen_event_pending) ev_gen_end = ev_place_end;
   } else if (ctx->job_mode == 2) {
     ctx->perm_mode = false;
@@ -855,6 +874,27 @@ int lt_run_device_async(lt_ctx *ctx) {
       ENSURE(ctx, ctx->d_pc_cnt, 128 * (size_t)score3_tile_buckets());
       ENSURE(ctx, ctx->d_pc_list, 8 * (size_t)tile_cap * (size_t)score3_tile_buckets());
     }
+    // the one-kernel form k_score_q (default; LT_SCORE_TWO_KERNELS=1 or device flag 8 once: sweep kernel + k_dense8;
+    // its pair entries carry the neighbour word in 26 bits; 2 = LT_TEST_Q_LOSE_TILE, a tile is never published)
+    // (+ 4 = LT_TEST_DENSE_TABLES: k_dense8's per-tile tables in the exhaustive mode too, instead of k_dense_rows;
+    //  + 8 = LT_TEST_DENSE_FEW_ROWS: k_dense_rows with a table of 64 rows)
+    const int one_kernel = ((ctx->score_two_kernels || test_switch("LT_SCORE_TWO_KERNELS") || ctx->n_img >= (1 << 18))
+                                ? 0 : (test_switch("LT_TEST_Q_LOSE_TILE") ? 2 : 1)) |
+                           (test_switch("LT_TEST_DENSE_TABLES") ? 4 : 0) | (test_switch("LT_TEST_DENSE_FEW_ROWS") ? 8 : 0);
+    unsigned *const bucket_cnt = tile_classes ? (unsigned *)(ctx->d_scan_status.as<unsigned long long>() + n_status_scan) : nullptr;
+    if (meta_fused) {
+      const bool q_form = score3_q_form(one_kernel, split, score_f32, ctx->perm_mode && !staged_sorted, score_sorted, tile_classes,
+                                        pair_classes);
+      const lt::PlaceLists lists = {ctx->d_cand_meta.p, G, C_bound, ctx->d_tile_order.as<unsigned>(), bucket_cnt,
+                                    tile_classes ? ctx->d_tile_list.as<unsigned>() : nullptr,
+                                    pair_classes ? ctx->d_pc_cnt.as<unsigned>() : nullptr, q_form ? ctx->d_pc_list.p : nullptr,
+                                    tile_cap, tile_cap};
+      // the launch in front of the scoring kernel: its completion starts the scoring stage's timer (ev[11]) or, on a sampled
+      // run without that, ends the placement stage (ev[4])
+      const hipEvent_t ev_pl = ev_place_end == 11 ? ev[11] : (sampled ? ev[4] : nullptr);
+      place_args(&lists, ev_markers ? nullptr : ev_pl);
+      if (ev_markers && ev_pl == ev[4] && sampled) HIPCHK(ctx, hipEventRecord(ev[4], st));
+    }
     launch_score3(st, C_bound, G, ctx->d_tri_off.as<long long>(), ctx->d_cand_node.as<unsigned>(), ctx->d_cand_meta.p,
                   ctx->perm_mode ? ctx->d_st_c.as<CRec>() : ctx->d_cand.as<CRec>(), ctx->d_node_img.as<int>(),
                   ctx->d_nb_off.as<long long>(), ctx->d_blk_order.as<int>(), ctx->d_cams.as<Cam>(),
@@ -863,22 +903,14 @@ int lt_run_device_async(lt_ctx *ctx) {
                   (ctx->perm_mode && !staged_sorted) ? ctx->d_place_perm.as<unsigned>()
                                                      : (score_sorted ? ctx->d_perm.as<unsigned>() : nullptr),
                   score_sorted ? ctx->d_rng.p : nullptr, ctx->perm_mode && !staged_sorted,
-                  tile_classes ? (unsigned *)(ctx->d_scan_status.as<unsigned long long>() + n_status_scan) : nullptr,
-                  tile_classes ? ctx->d_tile_list.as<unsigned>() : nullptr, tile_cap,
+                  bucket_cnt, tile_classes ? ctx->d_tile_list.as<unsigned>() : nullptr, tile_cap,
                   staged_sorted ? ctx->d_place_perm.as<unsigned>() : nullptr,
                   staged_sorted ? ctx->d_ex_rec.as<unsigned>() : nullptr,
                   staged_sorted ? ctx->d_ex_z.as<float>() : nullptr, ctx->d_err.as<int>(),
                   split ? ctx->d_sp_slots.p : nullptr, sp_slot_cap, ctx->d_sp_cnt.as<unsigned>(),
                   ctx->d_sp_ovf.as<unsigned>(), ctx->d_sp_pairs.p, ctx->d_sp_desc.p, sp_chunks, sampled ? ev[5] : nullptr,
                   node_rec_valid ? ctx->d_node_rec.p : nullptr, pair_classes ? ctx->d_pc_cnt.as<unsigned>() : nullptr,
-                  pair_classes ? ctx->d_pc_list.p : nullptr, tile_cap,
-                  // the one-kernel form k_score_q (default; LT_SCORE_TWO_KERNELS=1 or device flag 8 once: sweep kernel + k_dense8;
-                  // its pair entries carry the neighbour word in 26 bits; 2 = LT_TEST_Q_LOSE_TILE, a tile is never published)
-                  // (+ 4 = LT_TEST_DENSE_TABLES: k_dense8's per-tile tables in the exhaustive mode too, instead of k_dense_rows;
-                  //  + 8 = LT_TEST_DENSE_FEW_ROWS: k_dense_rows with a table of 64 rows)
-                  (((ctx->score_two_kernels || test_switch("LT_SCORE_TWO_KERNELS") || ctx->n_img >= (1 << 18))
-                        ? 0 : (test_switch("LT_TEST_Q_LOSE_TILE") ? 2 : 1)) |
-                   (test_switch("LT_TEST_DENSE_TABLES") ? 4 : 0) | (test_switch("LT_TEST_DENSE_FEW_ROWS") ? 8 : 0)));
+                  pair_classes ? ctx->d_pc_list.p : nullptr, tile_cap, one_kernel, meta_fused);
     if (C_bound <= 0 && sampled) HIPCHK(ctx, hipEventRecord(ev[5], st));  // nothing to score: no kernel carries the event
   }
   ENSURE(ctx, ctx->d_best_idx, 8 * (size_t)std::max<long long>(G, 1));
@@ -902,6 +934,9 @@ int lt_run_device_async(lt_ctx *ctx) {
   HIPCHK(ctx, hipGetLastError());
   // the device error flag, the candidate count and the pair statistic ride on the stream into this set's
   // pinned slots; finish_run reads them behind the end marker
+  // (The marker bound to k_select as its stop event instead of recorded behind it was measured: the stream's idle time per
+  // step goes from 5.8 to 4.5-4.8 us and k_select from 11.6 to 12.5-13.0 -- the release to the host moves into the kernel's
+  // own completion --, the step is the same within 0.3 us.  The record stays.)
   hipEvent_t ev_end = nullptr;
   if (hp) {
     // hp[0] candidate count, hp[1] error flag, hp[2] pair statistic: one record, WRITTEN BY k_select straight into this

@@ -67,6 +67,61 @@ static __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_wave_barrier();
 }
 
+// Per-candidate record for the scoring kernel: where its node's candidates start, how many there
+// are, and the neighbour table of its image -- so that the scoring prologue is ONE load level
+// instead of the chain cand_node -> tri_off / node_img -> nb_off.  Written by k_cand_meta (lt_kernels_score.hip) or,
+// in the line-slot form of matched mode, by k_node_prefix for the candidates of its own nodes (lt_kernels_v2.hip).
+struct CandMeta {
+  unsigned off_lo, off_hi;  // tri_off[node] (64-bit split)
+  unsigned n;               // candidates of the node
+  unsigned nb;              // (nb_off[img] << 8) | number of neighbours  (nb_off < 2^24)
+};
+static_assert(sizeof(CandMeta) == 16, "CandMeta is stored and loaded as one uint4");
+constexpr int kTileQueues = 8;  // one draw counter per XCD (workgroups are dealt round-robin to the XCDs)
+constexpr int kTileBuckets = 32;
+__device__ __forceinline__ int tile_bucket(unsigned cost_sum_n) {  // mean node size over the 64 lanes, 2 per class
+  const unsigned b = cost_sum_n >> 7;
+  return (int)(b < (unsigned)(kTileBuckets - 1) ? b : (unsigned)(kTileBuckets - 1));
+}
+// What the scoring stage expects to find reset when it starts; i / stride: the calling thread's index among the threads
+// that share the work (at least 256 of them) and their number, C: the exact candidate count.
+static __device__ __forceinline__ void score_stage_resets(long long i, long long stride, long long C, unsigned *__restrict__ draw,
+                                                          unsigned *__restrict__ pc_cnt, uint2 *__restrict__ fifo,
+                                                          unsigned fifo_cap) {
+  if (pc_cnt && i < kTileQueues * kTileBuckets) pc_cnt[i * 32] = 0;  // the sweep's pair-count lists
+  if (i < 2 * kTileQueues + 1) draw[i * 32] = 0;  // 128 bytes apart; behind the draw queues: the split form's overflow-chunk counter and k_dense8's eight claim counters
+  if (fifo) {
+    // k_score_q: behind those the XCD seen by each queue's first workgroup (none yet) and the queues' sweep-claim counters;
+    // the FIFOs of finished tiles (queue q: fifo[q * fifo_cap ...], one entry per tile of the queue) start empty
+    if (i >= 2 * kTileQueues + 1 && i < 3 * kTileQueues + 1) draw[i * 32] = 0xFFFFFFFFu;
+    if (i >= 3 * kTileQueues + 1 && i < 4 * kTileQueues + 1) draw[i * 32] = 0;
+    const long long per = ((C + 63) / 64 + kTileQueues - 1) / kTileQueues;
+    for (long long j = i; j < per * kTileQueues; j += stride)
+      fifo[(size_t)(j / per) * fifo_cap + (size_t)(j % per)] = make_uint2(0xFFFFFFFFu, 0u);
+  }
+}
+// One wave lists its tile (64 consecutive candidates from position `base`, lane = candidate) by cost class.  n: the size
+// of the lane's node (0 beyond the last candidate), w_lo / w_hi: first and end position of that node.  All 64 lanes.
+static __device__ __forceinline__ void tile_list_append(long long base, long long C, unsigned n, unsigned w_lo, unsigned w_hi,
+                                                        unsigned *__restrict__ bucket_cnt, unsigned *__restrict__ bucket_list,
+                                                        unsigned bucket_cap) {
+  unsigned sum = n;
+  for (int d = 32; d >= 1; d >>= 1) sum += (unsigned)__shfl_xor((int)sum, d);
+  // the tile's window (natural order): from the node of its first candidate to the end of the node of its last one
+  const int last = (int)((C - base) < 64 ? (C - base) : 64) - 1;  // base < C
+  const unsigned t_hi = (unsigned)__builtin_amdgcn_readlane((int)w_hi, last);
+  if (lane_id() == 0) {
+    // one list per (draw queue, class): 128 counters -- a single counter per class would serialise thousands
+    // of device-scope atomics on one address (~15 ns each).  An entry is 16 bytes: the tile and its window bounds,
+    // so that k_score3 knows what to stage from the draw alone.
+    const unsigned tile = (unsigned)(base >> 6);
+    const int qb = (int)(tile & (kTileQueues - 1)) * kTileBuckets + tile_bucket(sum);
+    const unsigned idx = atomicAdd(&bucket_cnt[qb * 32], 1u);  // counters 128 bytes apart: one L2 line each
+    if (idx < bucket_cap)
+      reinterpret_cast<uint4 *>(bucket_list)[(size_t)qb * bucket_cap + idx] = uint4{tile, w_lo, t_hi, 0u};
+  }
+}
+
 
 struct GenOut {
   CRec r;      // nb_slot / ng_line are filled in by the caller

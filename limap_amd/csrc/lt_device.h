@@ -80,6 +80,16 @@ void launch_select(hipStream_t st, long long G, const long long *tri_off, const 
                    const double *cand_unc, Cand *best_c, double *best_score, int *best_src2, int *n_tris,
                    bool wide, const int *err_flag, const unsigned long long *pair_counter, long long *result3,
                    const unsigned *perm);
+
+// What the list role of the k_place_rounds launch (launch_place, lt_kernels_v2.hip) needs of the scoring stage's buffers
+struct PlaceLists {
+  const void *meta;   // CandMeta per candidate, as k_node_prefix wrote them
+  long long G;
+  long long C_bound;  // the candidate count or an upper bound of it
+  unsigned *draw, *bucket_cnt, *bucket_list, *pc_cnt;
+  void *fifo;         // k_score_q's FIFOs of finished tiles (nullptr: another scoring form)
+  unsigned bucket_cap, fifo_cap;
+};
 void launch_edge_fill(hipStream_t st, long long G, const long long *tri_off, const unsigned *edge_flag,
                       const long long *edge_off, const CRec *cand, int *edges2, const unsigned *perm);
 

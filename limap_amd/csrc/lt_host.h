@@ -56,13 +56,14 @@ size_t seg_point_bytes();
 void launch_node_prefix(hipStream_t st, long long G, const int *node_img, const long long *seg_off,
                         const long long *nb_off, const long long *blk_line_base, unsigned *cnt_bl,
                         unsigned *base_bl, unsigned *n_tris, long long *tri_off, unsigned long long *status,
-                        int *err_flag, void *node_rec);
+                        int *err_flag, void *node_rec, void *cand_meta);
 void launch_expand_rows(hipStream_t st, int n_blk, const void *desc, const unsigned *stream, const unsigned *ovf, unsigned *rows);
 void launch_place(hipStream_t st, int n_blk, long long max_rows, const long long *m_off, const int *blk_img,
                   const long long *seg_off, const long long *blk_line_base, const unsigned *base_bl,
                   const unsigned *wave_count, const long long *tri_off, const CRec *st_r, const double *st_unc,
                   const unsigned *st_key, CRec *cand, double *cand_unc, unsigned *cand_node, const long long *group_base,
-                  unsigned *perm, const unsigned *blk_surv, const unsigned *blk_rnd0, const unsigned *round_count);
+                  unsigned *perm, const unsigned *blk_surv, const unsigned *blk_rnd0, const unsigned *round_count,
+                  const PlaceLists *lists, hipEvent_t ev_stop);
 void launch_pack_keys(hipStream_t st, int n_blk, long long max_rows, const long long *m_off,
                       const unsigned *wave_count, const long long *wave_pos, const unsigned *st_key,
                       unsigned *keys_c, unsigned *src_c, const long long *group_base);
@@ -81,7 +82,9 @@ void launch_score3(hipStream_t st, long long C, long long G, const long long *tr
                    unsigned *bucket_list, unsigned bucket_cap, const unsigned *place, unsigned *rec, const float *st_z,
                    int *err_flag, void *sp_slots, int sp_slot_cap, unsigned *sp_cnt, unsigned *sp_ovf, void *sp_pairs,
                    void *sp_desc, long long sp_chunks, hipEvent_t ev_after, const void *node_rec, unsigned *pc_cnt,
-                   void *pc_list, unsigned pc_cap, int one_kernel);
+                   void *pc_list, unsigned pc_cap, int one_kernel, bool meta_done);
+bool score3_q_form(int one_kernel, bool split, bool f32, bool perm_is_placement, bool ranges, bool tile_classes,
+                   bool pair_lists);
 size_t score_split_chunk_bytes();
 size_t score_split_entry_bytes();
 long long score_split_chunks(long long C);

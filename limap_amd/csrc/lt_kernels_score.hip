@@ -43,15 +43,7 @@ __device__ unsigned long long g_trace[4 * 4 * 65536];
 
 static inline unsigned nblk2(long long n, int bs) { return (unsigned)((n + bs - 1) / bs); }
 
-// Per-candidate record for the scoring kernel: where its node's candidates start, how many there
-// are, and the neighbour table of its image -- so that the scoring prologue is ONE load level
-// instead of the chain cand_node -> tri_off / node_img -> nb_off.
-struct CandMeta {
-  unsigned off_lo, off_hi;  // tri_off[node] (64-bit split)
-  unsigned n;               // candidates of the node
-  unsigned nb;              // (nb_off[img] << 8) | number of neighbours  (nb_off < 2^24)
-};
-
+// (CandMeta, the per-candidate prologue record, and the cost classes of the tiles: lt_devfn.h)
 // Also resets the tile draw counters of the persistent k_score3 that follows, and lists the tiles (64 consecutive
 // candidates = what one wave of this kernel handles per iteration) by COST CLASS: a tile's time in k_score3 grows
 // with the sizes of the nodes it touches (correlation 0.62 with the sum over its lanes of the node size), and a
@@ -59,12 +51,6 @@ struct CandMeta {
 // 138 -> 127 us with the tiles in descending cost order.  No sort: per draw queue kTileBuckets lists filled through
 // one counter each (zeroed by k_build_pairs), drawn from the most expensive class down; the order inside a class
 // is arbitrary.
-constexpr int kTileQueues = 8;  // one draw counter per XCD (workgroups are dealt round-robin to the XCDs)
-constexpr int kTileBuckets = 32;
-__device__ __forceinline__ int tile_bucket(unsigned cost_sum_n) {  // mean node size over the 64 lanes, 2 per class
-  const unsigned b = cost_sum_n >> 7;
-  return (int)(b < (unsigned)(kTileBuckets - 1) ? b : (unsigned)(kTileBuckets - 1));
-}
 __global__ void __launch_bounds__(256)
 k_cand_meta(long long G, const unsigned *__restrict__ cand_node, const long long *__restrict__ tri_off,
             const int *__restrict__ node_img, const long long *__restrict__ nb_off, CandMeta *__restrict__ meta,
@@ -75,17 +61,7 @@ k_cand_meta(long long G, const unsigned *__restrict__ cand_node, const long long
   const long long C = tri_off[G];
   const long long stride = (long long)gridDim.x * blockDim.x;
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (pc_cnt && i < kTileQueues * kTileBuckets) pc_cnt[i * 32] = 0;  // the sweep's pair-count lists
-  if (i < 2 * kTileQueues + 1) draw[i * 32] = 0;  // 128 bytes apart; behind the draw queues: the split form's overflow-chunk counter and k_dense8's eight claim counters
-  if (fifo) {
-    // k_score_q: behind those the XCD seen by each queue's first workgroup (none yet) and the queues' sweep-claim counters;
-    // the FIFOs of finished tiles (queue q: fifo[q * fifo_cap ...], one entry per tile of the queue) start empty
-    if (i >= 2 * kTileQueues + 1 && i < 3 * kTileQueues + 1) draw[i * 32] = 0xFFFFFFFFu;
-    if (i >= 3 * kTileQueues + 1 && i < 4 * kTileQueues + 1) draw[i * 32] = 0;
-    const long long per = ((C + 63) / 64 + kTileQueues - 1) / kTileQueues;
-    for (long long j = i; j < per * kTileQueues; j += stride)
-      fifo[(size_t)(j / per) * fifo_cap + (size_t)(j % per)] = make_uint2(0xFFFFFFFFu, 0u);
-  }
+  score_stage_resets(i, stride, C, draw, pc_cnt, fifo, fifo_cap);
   const long long C_up = (C + 63) & ~63ll;  // whole waves take part in the tile's reduction
   for (; i < C_up; i += stride) {
     unsigned n = 0, w_lo = 0, w_hi = 0;
@@ -108,24 +84,7 @@ k_cand_meta(long long G, const unsigned *__restrict__ cand_node, const long long
       n = m.n;
       w_lo = m.off_lo; w_hi = m.off_lo + m.n;
     }
-    if (bucket_cnt) {
-      unsigned sum = n;
-      for (int d = 32; d >= 1; d >>= 1) sum += (unsigned)__shfl_xor((int)sum, d);
-      // the tile's window (natural order): from the node of its first candidate to the end of the node of its last one
-      const long long base = i - lane_id();  // < C: the loop runs over whole waves up to C rounded up
-      const int last = (int)((C - base) < 64 ? (C - base) : 64) - 1;
-      const unsigned t_hi = (unsigned)__builtin_amdgcn_readlane((int)w_hi, last);
-      if (lane_id() == 0) {
-        // one list per (draw queue, class): 128 counters -- a single counter per class would serialise thousands
-        // of device-scope atomics on one address (~15 ns each).  An entry is 16 bytes: the tile and its window bounds,
-        // so that k_score3 knows what to stage from the draw alone.
-        const unsigned tile = (unsigned)(i >> 6);
-        const int qb = (int)(tile & (kTileQueues - 1)) * kTileBuckets + tile_bucket(sum);
-        const unsigned idx = atomicAdd(&bucket_cnt[qb * 32], 1u);  // counters 128 bytes apart: one L2 line each
-        if (idx < bucket_cap)
-          reinterpret_cast<uint4 *>(bucket_list)[(size_t)qb * bucket_cap + idx] = uint4{tile, w_lo, t_hi, 0u};
-      }
-    }
+    if (bucket_cnt) tile_list_append(i - lane_id(), C, n, w_lo, w_hi, bucket_cnt, bucket_list, bucket_cap);  // (whole waves up to C rounded up)
   }
 }
 
@@ -2187,6 +2146,12 @@ int score3_tile_buckets() { return kTileBuckets * kTileQueues; }  // counters (1
 // (A two-kernel form -- light sweep writing per-tile pair lists, then a dense evaluation kernel -- was
 // measured: the sweep alone takes 53 us, but the evaluation does not get cheaper and the two phases no
 // longer overlap across waves: 165+ us against 150 us fused.)
+// whether launch_score3 scores with the one persistent kernel k_score_q (one_kernel: its low two bits): the single-precision
+// sweep over the placement permutation, without sweep ranges, cost-class lists and the pair store present
+bool score3_q_form(int one_kernel, bool split, bool f32, bool perm_is_placement, bool ranges, bool tile_classes,
+                   bool pair_lists) {
+  return (one_kernel & 3) != 0 && split && f32 && perm_is_placement && !ranges && tile_classes && pair_lists;
+}
 void launch_score3(hipStream_t st, long long C, long long G, const long long *tri_off, const unsigned *cand_node,
                    void *meta, const CRec *cand, const int *node_img, const long long *nb_off,
                    const int *blk_order, const Cam *cams, double *score, unsigned long long *pair_counter,
@@ -2195,7 +2160,9 @@ void launch_score3(hipStream_t st, long long C, long long G, const long long *tr
                    unsigned *bucket_list, unsigned bucket_cap, const unsigned *place, unsigned *rec, const float *st_z,
                    int *err_flag, void *sp_slots, int sp_slot_cap, unsigned *sp_cnt, unsigned *sp_ovf, void *sp_pairs,
                    void *sp_desc, long long sp_chunks, hipEvent_t ev_after, const void *node_rec, unsigned *pc_cnt,
-                   void *pc_list, unsigned pc_cap, int one_kernel) {
+                   void *pc_list, unsigned pc_cap, int one_kernel, bool meta_done) {
+  // meta_done: the records in `meta`, the class lists and the stage's resets are already on the stream (k_node_prefix and
+  // the k_place_rounds launch, which then also carries ev_before): no k_cand_meta, cand_node is not read
   // ev_before / ev_after: bound as the STOP events of k_cand_meta and of the stage's last kernel (hipExtLaunchKernelGGL:
   // the kernel's own completion signal carries the timestamp) -- a hipEventRecord between two kernels is a barrier packet
   // that opens a ~5.5 us gap in the stream (LT_EV_MARKERS=1: the plain records, for comparison)
@@ -2209,8 +2176,8 @@ void launch_score3(hipStream_t st, long long C, long long G, const long long *tr
   const bool dense_tables = (one_kernel & 4) != 0;  // LT_TEST_DENSE_TABLES: k_dense8 instead of k_dense_rows (exhaustive mode)
   const bool few_rows = (one_kernel & 8) != 0;      // LT_TEST_DENSE_FEW_ROWS: a table of 64 rows (units worked off in groups of tiles)
   one_kernel &= 3;
-  const bool q_form = one_kernel != 0 && sp_slots != nullptr && f32 && perm != nullptr && perm_is_placement && rng == nullptr &&
-                      bucket_cnt != nullptr && pc_list != nullptr;
+  const bool q_form = score3_q_form(one_kernel, sp_slots != nullptr, f32, perm != nullptr && perm_is_placement, rng != nullptr,
+                                    bucket_cnt != nullptr, pc_list != nullptr);
   static int n_cu = 0;
   if (n_cu == 0) {
     int dev = 0;
@@ -2221,11 +2188,12 @@ void launch_score3(hipStream_t st, long long C, long long G, const long long *tr
   // C: the candidate count or an upper bound of it (the kernels read the exact count from tri_off[G])
   const long long n_tiles = (C + 63) / 64;
   static const bool ev_markers = getenv("LT_EV_MARKERS") != nullptr;
-  hipExtLaunchKernelGGL(k_cand_meta, dim3((unsigned)std::min<long long>(nblk2(C, 256), 16ll * n_cu)), dim3(256), 0, st,
-                        nullptr, ev_markers ? nullptr : ev_before, 0, G, cand_node, tri_off, node_img, nb_off,
-                        reinterpret_cast<CandMeta *>(meta), draw, bucket_cnt, bucket_list, bucket_cap,
-                        reinterpret_cast<const uint4 *>(node_rec), pc_cnt,
-                        q_form ? reinterpret_cast<uint2 *>(pc_list) : nullptr, pc_cap);
+  if (!meta_done)
+    hipExtLaunchKernelGGL(k_cand_meta, dim3((unsigned)std::min<long long>(nblk2(C, 256), 16ll * n_cu)), dim3(256), 0, st,
+                          nullptr, ev_markers ? nullptr : ev_before, 0, G, cand_node, tri_off, node_img, nb_off,
+                          reinterpret_cast<CandMeta *>(meta), draw, bucket_cnt, bucket_list, bucket_cap,
+                          reinterpret_cast<const uint4 *>(node_rec), pc_cnt,
+                          q_form ? reinterpret_cast<uint2 *>(pc_list) : nullptr, pc_cap);
   hipEvent_t ev_stop = ev_markers ? nullptr : ev_after;
   Score3Args a;
   a.G = G; a.tri_off = tri_off; a.meta = reinterpret_cast<const CandMeta *>(meta); a.cand = cand;

@@ -18,10 +18,13 @@
 //       match-row order -- base_line_triangulator.cc:71-103): per-(block, line) counts -> per-node
 //       prefix over the neighbour blocks -> final position of every candidate.
 //   k_pack_keys + radix sort + k_permute (generic rows): stable sort of the candidates by node.
-// The scoring stage (k_cand_meta, k_score3, ...) lives in lt_kernels_score.hip.
+// The scoring stage (k_cand_meta, k_score3, ...) lives in lt_kernels_score.hip; in the line-slot form k_node_prefix writes
+// the per-candidate scoring records and the k_place_rounds launch lists the tiles, and k_cand_meta does not run.
 // Compiled with -ffp-contract=off (see lt_geom.h).
 
 #include "lt_devfn.h"
+
+#include <hip/hip_ext.h>
 
 #include <algorithm>
 
@@ -1094,18 +1097,58 @@ k_tri_rounds(GenArgs a, GenCfg cfg, const Cam *__restrict__ cams_r, const PairRe
 #ifndef LT_PLACE_WG_PER_CU
 #define LT_PLACE_WG_PER_CU 8
 #endif
+// Second role of the k_place_rounds launch: what k_cand_meta does besides copying records, from the records k_node_prefix
+// has already written per candidate.  One tile (64 consecutive candidates) per wave and iteration; the two roles share
+// no data, so the list workgroups run beside the placement instead of behind it.
+struct TileLists {
+  const uint4 *meta;  // CandMeta per candidate
+  long long G;
+  unsigned *draw, *bucket_cnt, *bucket_list, *pc_cnt;
+  uint2 *fifo;
+  unsigned bucket_cap, fifo_cap;
+  int n_wg;    // list workgroups in the grid (0: placement only)
+  int period;  // the last of every `period` workgroups is a list workgroup until there are n_wg (0: the first n_wg are)
+};
+static __device__ __forceinline__ void tile_lists_role(const TileLists &tl, const long long *__restrict__ tri_off, int wg) {
+  const long long C = tri_off[tl.G];
+  const long long stride = (long long)tl.n_wg * 256;
+  score_stage_resets((long long)wg * 256 + threadIdx.x, stride, C, tl.draw, tl.pc_cnt, tl.fifo, tl.fifo_cap);
+  if (!tl.bucket_cnt) return;
+  for (long long base = (long long)wg * 256 + (threadIdx.x & ~63u); base < C; base += stride) {
+    unsigned n = 0, w_lo = 0, w_hi = 0;
+    if (base + lane_id() < C) {
+      const uint4 m = tl.meta[base + lane_id()];
+      n = m.z;
+      w_lo = m.x; w_hi = m.x + m.z;
+    }
+    tile_list_append(base, C, n, w_lo, w_hi, tl.bucket_cnt, tl.bucket_list, tl.bucket_cap);
+  }
+}
 // Placement for the round lists of k_tri_rounds: as k_place, one wave per round; a (block, line) run that begins in an
-// earlier round of the block is followed back through the previous rounds' lists.
+// earlier round of the block is followed back through the previous rounds' lists.  cand_node == nullptr: the permutation
+// only (nothing reads the node of a candidate when the scoring records come from k_node_prefix).
 __global__ void __launch_bounds__(256)
 k_place_rounds(const long long *__restrict__ m_off, const int *__restrict__ blk_img, const long long *__restrict__ seg_off,
                const long long *__restrict__ blk_line_base, const unsigned *__restrict__ base_bl,
                const long long *__restrict__ tri_off, const CRec *__restrict__ st_r, const double *__restrict__ st_unc,
                const unsigned *__restrict__ st_key, CRec *__restrict__ cand, double *__restrict__ cand_unc,
                unsigned *__restrict__ cand_node, unsigned *__restrict__ perm, const unsigned *__restrict__ blk_surv,
-               const unsigned *__restrict__ blk_rnd0, const unsigned *__restrict__ round_count, int n_blk) {
+               const unsigned *__restrict__ blk_rnd0, const unsigned *__restrict__ round_count, int n_blk,
+               const TileLists tl) {
   const int wave = threadIdx.x >> 6;
   const int lane = lane_id();
-  for (int b = (int)blockIdx.x; b < n_blk; b += (int)gridDim.x) {  // persistent, as k_tri_rounds
+  int b0 = (int)blockIdx.x;
+  if (tl.n_wg > 0) {  // (workgroup-uniform)
+    const int q = tl.period ? b0 / tl.period : b0;
+    const bool lists = q < tl.n_wg && (tl.period == 0 || b0 % tl.period == tl.period - 1);
+    if (lists) {
+      tile_lists_role(tl, tri_off, q);
+      return;
+    }
+    b0 -= q < tl.n_wg ? q : tl.n_wg;  // list workgroups in front of this one
+  }
+  const int n_place = (int)gridDim.x - tl.n_wg;
+  for (int b = b0; b < n_blk; b += n_place) {  // persistent, as k_tri_rounds
   const int x = (wave + b) & 3;
   const int n_rounds = (int)((blk_surv[b] + 63u) >> 6);
   if (x >= n_rounds) continue;
@@ -1154,7 +1197,7 @@ k_place_rounds(const long long *__restrict__ m_off, const int *__restrict__ blk_
       const unsigned rank = (unsigned)(lane - my_head) + (my_head == 0 ? carry : 0u);
       const long long pos = tri_off[key] + base_bl[lbase + (long long)(key - g1)] + rank;
       pos32 = (unsigned)pos;  // candidate positions fit 32 bits (cand_node / tri counts are 32-bit)
-      cand_node[pos] = key;
+      if (cand_node) cand_node[pos] = key;
       if (perm) perm[pos] = (unsigned)(s0 + lane);
     }
     if (perm) continue;
@@ -1187,7 +1230,7 @@ k_node_prefix(long long G, const int *__restrict__ node_img, const long long *__
               const long long *__restrict__ nb_off, const long long *__restrict__ blk_line_base,
               unsigned *__restrict__ cnt_bl, unsigned *__restrict__ base_bl, unsigned *__restrict__ n_tris,
               long long *__restrict__ tri_off, unsigned long long *__restrict__ status, int *__restrict__ err_flag,
-              uint4 *__restrict__ node_rec) {
+              uint4 *__restrict__ node_rec, uint4 *__restrict__ cand_meta) {
   __shared__ unsigned s_tile;
   __shared__ long long s_wave[4];
   __shared__ long long s_prefix;
@@ -1278,7 +1321,20 @@ k_node_prefix(long long G, const int *__restrict__ node_img, const long long *__
   }
   // the scoring prologue record of the node's candidates (CandMeta, lt_kernels_score.hip), 16 bytes per node: k_cand_meta
   // then copies it with one gather per candidate instead of five (tri_off twice, node_img, nb_off twice)
-  if (node_rec && g < G) node_rec[g] = uint4{(unsigned)(off & 0xFFFFFFFFll), (unsigned)(off >> 32), run, nbv};
+  const uint4 rec = uint4{(unsigned)(off & 0xFFFFFFFFll), (unsigned)(off >> 32), run, nbv};
+  if (node_rec && g < G) node_rec[g] = rec;
+  // ... or is that copy already (cand_meta != nullptr): the record depends on nothing but the node, and the node's
+  // candidates are the positions [off, off + run).  Adjacent threads write adjacent ranges; the node g == G and the
+  // ones beyond it have run == 0.  (Measured on the bench scene against an expansion through LDS -- one coalesced
+  // 16-byte store per position, the node found by a search over the workgroup's 256 offsets: the same within 0.4 us;
+  // the kernel's 3.7 us over the form without the records are the 9.3 MB they take, whoever writes them.)
+  if (cand_meta) {
+    // (a native vector: the struct assignment compiles to two 8-byte stores per record, 19.5 instead of 15.6 us)
+    using u32x4 = unsigned __attribute__((ext_vector_type(4)));
+    const u32x4 r4 = {rec.x, rec.y, rec.z, rec.w};
+    u32x4 *dst = reinterpret_cast<u32x4 *>(cand_meta) + off;
+    for (unsigned j = 0; j < run; ++j) dst[j] = r4;
+  }
 }
 
 // Fast path: move every staged candidate to its final, reference-ordered position
@@ -1573,15 +1629,20 @@ void launch_gen_split(hipStream_t st, int n_blk, long long max_rows, const GenCf
 void launch_node_prefix(hipStream_t st, long long G, const int *node_img, const long long *seg_off,
                         const long long *nb_off, const long long *blk_line_base, unsigned *cnt_bl,
                         unsigned *base_bl, unsigned *n_tris, long long *tri_off, unsigned long long *status,
-                        int *err_flag, void *node_rec) {
+                        int *err_flag, void *node_rec, void *cand_meta) {
+  // cand_meta: room for every candidate's scoring record (CandMeta), or nullptr where k_cand_meta writes them
   hipLaunchKernelGGL(k_node_prefix, dim3(nblk2(G + 1, 256)), dim3(256), 0, st, G, node_img, seg_off, nb_off,
-                     blk_line_base, cnt_bl, base_bl, n_tris, tri_off, status, err_flag, reinterpret_cast<uint4 *>(node_rec));
+                     blk_line_base, cnt_bl, base_bl, n_tris, tri_off, status, err_flag, reinterpret_cast<uint4 *>(node_rec),
+                     reinterpret_cast<uint4 *>(cand_meta));
 }
 void launch_place(hipStream_t st, int n_blk, long long max_rows, const long long *m_off, const int *blk_img,
                   const long long *seg_off, const long long *blk_line_base, const unsigned *base_bl,
                   const unsigned *wave_count, const long long *tri_off, const CRec *st_r, const double *st_unc,
                   const unsigned *st_key, CRec *cand, double *cand_unc, unsigned *cand_node, const long long *group_base,
-                  unsigned *perm, const unsigned *blk_surv, const unsigned *blk_rnd0, const unsigned *round_count) {
+                  unsigned *perm, const unsigned *blk_surv, const unsigned *blk_rnd0, const unsigned *round_count,
+                  const PlaceLists *lists, hipEvent_t ev_stop) {
+  // lists (line-slot form only): the launch also lists the tiles by cost class and resets the scoring stage's counters
+  // (the caller then skips k_cand_meta and passes cand_node == nullptr); ev_stop: bound as the launch's stop event
   if (n_blk <= 0 || max_rows <= 0) return;
   if (round_count) {  // the line-slot form: candidate lists per round of 64 survivors
     static int n_cu = 0;
@@ -1591,9 +1652,27 @@ void launch_place(hipStream_t st, int n_blk, long long max_rows, const long long
           hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)
         n_cu = 256;
     }
-    hipLaunchKernelGGL(k_place_rounds, dim3((unsigned)std::min<long long>(n_blk, (long long)n_cu * LT_PLACE_WG_PER_CU)), dim3(256), 0, st, m_off,
-                       blk_img, seg_off, blk_line_base, base_bl, tri_off, st_r, st_unc, st_key, cand, cand_unc, cand_node, perm,
-                       blk_surv, blk_rnd0, round_count, n_blk);
+    const long long slots = (long long)n_cu * LT_PLACE_WG_PER_CU;  // what is resident at once
+    TileLists tl = {};
+    long long n_place = std::min<long long>(n_blk, slots);
+    if (lists) {
+      tl.meta = reinterpret_cast<const uint4 *>(lists->meta);
+      tl.G = lists->G;
+      tl.draw = lists->draw; tl.bucket_cnt = lists->bucket_cnt; tl.bucket_list = lists->bucket_list; tl.pc_cnt = lists->pc_cnt;
+      tl.fifo = reinterpret_cast<uint2 *>(lists->fifo);
+      tl.bucket_cap = lists->bucket_cap; tl.fifo_cap = lists->fifo_cap;
+      // one list workgroup per CU at the most (four tiles per pass), out of the placement's share of the slots, so that
+      // both roles are resident from the start; dealt out as every fifth workgroup (an odd period: the workgroups go
+      // round-robin to the eight XCDs, and the list role should not land on two of them) while the placement has
+      // four workgroups for each, in front otherwise
+      const long long want = std::max<long long>(1, std::min<long long>((lists->C_bound + 255) / 256, n_cu));
+      n_place = std::min<long long>(n_blk, slots - want);
+      tl.n_wg = (int)want;
+      tl.period = n_place >= 4 * want ? 5 : 0;
+    }
+    hipExtLaunchKernelGGL(k_place_rounds, dim3((unsigned)(n_place + tl.n_wg)), dim3(256), 0, st, nullptr, ev_stop, 0, m_off,
+                          blk_img, seg_off, blk_line_base, base_bl, tri_off, st_r, st_unc, st_key, cand, cand_unc, cand_node, perm,
+                          blk_surv, blk_rnd0, round_count, n_blk, tl);
     return;
   }
   const int n_groups = gen_groups(max_rows);
