@@ -1244,6 +1244,95 @@ int lt_fn_loc_score_host(const double kvec4[4], int64_t n_l3d, const double *lin
 /* CameraPose(R, T)'s quaternion: Eigen's Quaternion(Matrix3) of the row-major R9, (w, x, y, z) */
 int lt_fn_loc_qvec_from_R(const double R9[9], double qvec4[4]);
 
+/* ---- Minimal absolute-pose solvers from points and lines: the solvers
+ * JointPoseEstimator::MinimalSolver calls (p3p, p2p1ll, p1p2ll, p3ll) as one problem with one core.  A sample of kind k
+ * is 3 - k points (unit bearing x, world point X) and k lines (unit image-line normal l, a point C and the unit direction
+ * V of the 3D line), built as joint_pose_estimator.cc:80-110 builds them.  The arithmetic is this project's definition
+ * (PoseLib's is not restated): poses are solutions of the sample's six constraints with positive point depths, at most 8,
+ * in ascending order of z / w of the quaternion, which is normalised with w > 0.  A degenerate sample returns fewer
+ * poses, or none; no pose holds a NaN. ---- */
+#define LT_EST_P3P 0
+#define LT_EST_P2P1LL 1
+#define LT_EST_P1P2LL 2
+#define LT_EST_P3LL 3
+#define LT_EST_MAX_SOLUTIONS 8
+/* n samples of one kind on the device, one lane per sample.  xs, Xs: n x (3 - kind) x 3; ls, Cs, Vs: n x kind x 3 (an
+ * array of a kind without such data may be NULL).  Non-finite input is LT_ERR_ARGUMENT. */
+int lt_est_minimal(lt_ctx *ctx, int kind, int64_t n, const double *xs, const double *Xs, const double *ls, const double *Cs,
+                   const double *Vs);
+int64_t lt_est_minimal_num(lt_ctx *ctx);
+/* of the last lt_est_minimal (any pointer may be NULL): poses[n][8][7] (qvec w x y z, tvec; rows past the count are 0),
+ * counts[n] */
+int lt_est_minimal_get(lt_ctx *ctx, double *poses56, int32_t *counts);
+/* host ms of [0] validation, table and upload, [1] the kernel, [2] download; device ms (HIP events) of [3] k_est_minimal */
+int lt_est_minimal_get_timers(lt_ctx *ctx, double out[4]);
+/* The same inline functions in plain C++: bit-identical results; OpenMP over n_threads threads (0: the default).
+ * Errors through lt_fn_est_host_error. */
+int lt_fn_est_minimal_host(int kind, int64_t n, const double *xs, const double *Xs, const double *ls, const double *Cs,
+                           const double *Vs, int n_threads, double *poses56, int32_t *counts);
+const char *lt_fn_est_host_error(void);
+
+/* ---- The hybrid LO-MSAC around these solvers: PointLineAbsolutePoseHybridRansac::EstimateModel
+ * (estimators/absolute_pose/pl_absolute_pose_hybrid_ransac.h:63-249) for Q independent queries in one set of launches.
+ * limap's control flow, score, thresholds, weights, cheirality tests and refinements (section 25) are restated; the
+ * minimal solvers, the sampler, the shuffles and NumRequiredIterations are this project's seedable definition, which the
+ * device and the host twin compute bit-identically.  The loop advances in rounds of round_size iterations whose solver
+ * types are drawn under the probabilities frozen at the round's start; everything else is upstream's sequential
+ * semantics, replayed in iteration order on the device.  Poses are those of a hybrid LO-MSAC, not the iterates of a
+ * RansacLib run. ---- */
+typedef struct lt_est_config {
+  double squared_inlier_thresholds[2]; /* 1, 1: points, lines */
+  double data_type_weights[2];         /* 1, 1 */
+  double success_probability;          /* 0.9999 */
+  double threshold_multiplier;         /* sqrt(2) */
+  double cheirality_min_depth;         /* 0 */
+  double cheirality_overlap_pixels;    /* 10 */
+  uint64_t random_seed;                /* 0 */
+  uint32_t min_num_iterations;         /* 100 */
+  uint32_t max_num_iterations;         /* 10000 */
+  uint32_t max_num_iterations_per_solver; /* 10000 */
+  uint32_t lo_starting_iterations;     /* 50 */
+  int32_t num_lo_steps;                /* 10 */
+  int32_t num_lsq_iterations;          /* 4 */
+  int32_t min_sample_multiplicator;    /* 7 */
+  int32_t non_min_sample_multiplier;   /* 3 */
+  int32_t final_least_squares;         /* 0 */
+  int32_t round_size;                  /* 64: iterations per round; 1 is upstream's control flow exactly */
+  int32_t solver_flags[4];             /* 1 1 1 1: p3p, p2p1ll, p1p2ll, p3ll */
+  int32_t poll_interval;               /* 4: rounds enqueued between two looks at the count of finished queries */
+  lt_loc_config loc;                   /* LeastSquares: cost function, weight, loss, block weights, iteration cap */
+} lt_est_config;
+void lt_est_config_default(lt_est_config *cfg);
+#define LT_EST_TRACE_DOUBLES 12
+/* Q queries as CSR: per query its camera and input pose (returned where no solver can run), points [pt_off[q],
+ * pt_off[q + 1]), 3D lines [l3d_off[q], ..) and 2D segments [seg_off[q], ..) with l3d_ids[s] the index of the segment's
+ * 3D line within its query.  trace_cap > 0 keeps up to that many records of the loop's decisions per query. */
+int lt_est_solve(lt_ctx *ctx, int64_t n_query, const double *kvec4, const double *qvec4, const double *tvec3,
+                 const int64_t *pt_off, const double *p3d3, const double *p2d2, const int64_t *l3d_off, const double *line3d6,
+                 const int64_t *seg_off, const int32_t *l3d_ids, const double *seg4, const lt_est_config *cfg,
+                 int64_t trace_cap);
+/* of the last lt_est_solve (any pointer may be NULL): pose7[Q][7] (qvec, tvec); dstats3[Q][3] = best_model_score and
+ * the two inlier ratios; istats12[Q][12] = num_iterations_total, num_iterations_per_solver[4], best_num_inliers,
+ * best_solver_type, number_lo_iterations, inlier counts (points, lines), VerifyData (1: the loop ran), trace records;
+ * inliers[pt_off[Q] + seg_off[Q]]: at pt_off[q] + seg_off[q] the query's inlier points, then its inlier segments, as
+ * indices within their type; trace[Q][trace_cap][12] */
+int lt_est_get(lt_ctx *ctx, double *pose7, double *dstats3, int32_t *istats12, int32_t *inliers, double *trace);
+/* host ms of [0] validation, tables and upload, [1] the rounds, [2] download; [3] rounds enqueued; device ms (HIP
+ * events, summed over the polls) of [4] all rounds */
+int lt_est_get_timers(lt_ctx *ctx, double out[8]);
+/* The same definition in plain C++ from the same inline functions: bit-identical results; OpenMP over the queries */
+int lt_fn_est_host(int64_t n_query, const double *kvec4, const double *qvec4, const double *tvec3, const int64_t *pt_off,
+                   const double *p3d3, const double *p2d2, const int64_t *l3d_off, const double *line3d6,
+                   const int64_t *seg_off, const int32_t *l3d_ids, const double *seg4, const lt_est_config *cfg,
+                   int64_t trace_cap, int host_threads, double *pose7, double *dstats3, int32_t *istats12, int32_t *inliers,
+                   double *trace);
+/* the definition's arithmetic, for tests: NumRequiredIterations, the logarithm, the frozen solver probabilities
+ * (prob4 from ratios2, iterations per solver and priors) and the priors of a query's data counts */
+uint32_t lt_fn_est_num_required(const double ratios2[2], double success_probability, int solver, uint32_t min_it, uint32_t max_it);
+double lt_fn_est_log(double x);
+int lt_fn_est_probabilities(const double ratios2[2], const uint32_t its4[4], const int32_t flags4[4], int32_t n_pts,
+                            int32_t n_lines, uint32_t min_it, double prior4[4], double prob4[4]);
+
 /* ---- Bundle adjustment with free poses, points and lines: limap.optimize's
  * solve_hybrid_bundle_adjustment / solve_point_bundle_adjustment, HybridBAEngine with constant intrinsics.  Every image
  * that carries a residual block is a parameter (quaternion and translation), every point track (3 unknowns) and every

@@ -298,6 +298,19 @@ struct AsState {  // global point-line association (lt_assoc.cpp): the result of
   DevBuf d_cam, d_sp, d_unk, d_blk, d_edge, d_adj, d_lin, d_mat, d_vec, d_chunk, d_status;
 };
 
+struct EsState {  // minimal pose solvers (lt_est.cpp): the result of the last lt_est_minimal
+  double timers[4] = {0, 0, 0, 0};  // lt_est_minimal_get_timers
+  std::vector<double> poses;        // 8 x 7 doubles per sample
+  std::vector<int> counts;          // poses per sample
+  DevBuf d_tab, d_poses, d_counts;
+  // the hybrid loop: the result of the last lt_est_solve
+  double loop_timers[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // lt_est_get_timers
+  long long n_query = 0, n_corr = 0, trace_cap = 0;
+  std::vector<double> pose, dstats, trace;  // 7, 3, trace_cap x 12 per query
+  std::vector<int> istats, inliers;         // 12 per query; per correspondence
+  DevBuf d_qs, d_st, d_ltab, d_ids, d_r2, d_lists, d_blk, d_ints, d_rposes, d_rscores, d_rints, d_trace, d_done;
+};
+
 struct SfmState {  // visual neighbours (lt_sfm.cpp): the result of the last lt_sfm_neighbors
   double timers[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // lt_sfm_get_timers
   std::vector<long long> nb_off;                // per image its neighbours (image indices)
@@ -576,6 +589,7 @@ struct lt_ctx {
   lt_host::LocState lc;
   lt_host::BaState ba;
   lt_host::AsState as;
+  lt_host::EsState es;
   lt_host::SfmState sf;
   lt_host::UdState ud;
   lt_host::S2State s2;

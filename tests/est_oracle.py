@@ -1,0 +1,239 @@
+"""Independent NumPy restatement of the minimal-solver core of limap_amd.estimators: the same
+formulation -- constraints n^T M(q) Y + sigma n^T t' = 0, translation eliminated by the left null space of the normals,
+three quadrics in the chart w = 1, the octic in z -- with other tools: numpy.linalg.svd for the null spaces, numpy.roots
+for the octic, numpy.linalg.pinv for the translation, and no polish.  Nothing here is shared with the library."""
+import numpy as np
+
+KINDS = ("p3p", "p2p1ll", "p1p2ll", "p3ll")
+N_POINTS = {"p3p": 3, "p2p1ll": 2, "p1p2ll": 1, "p3ll": 0}
+
+# monomials of q = (w, x, y, z): w2 wx wy wz x2 xy xz y2 yz z2
+
+
+def monomials(q):
+    w, x, y, z = q
+    return np.array([w * w, w * x, w * y, w * z, x * x, x * y, x * z, y * y, y * z, z * z])
+
+
+def quad_row(n, Y):
+    """coefficients of n^T M(q) Y on the monomials, M(q) = |q|^2 R(q)"""
+    d = n * Y
+    return np.array([d[0] + d[1] + d[2],
+                     2 * (n[2] * Y[1] - n[1] * Y[2]), 2 * (n[0] * Y[2] - n[2] * Y[0]), 2 * (n[1] * Y[0] - n[0] * Y[1]),
+                     d[0] - d[1] - d[2], 2 * (n[0] * Y[1] + n[1] * Y[0]), 2 * (n[0] * Y[2] + n[2] * Y[0]),
+                     -d[0] + d[1] - d[2], 2 * (n[1] * Y[2] + n[2] * Y[1]), -d[0] - d[1] + d[2]])
+
+
+def rotation(q):
+    w, x, y, z = np.asarray(q, float) / np.linalg.norm(q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def constraint_rows(xs, Xs, ls, Cs, Vs):
+    """(n, Y, sigma) of the six constraints: per point two with sigma 1, per line one with sigma 1 and one with 0"""
+    rows = []
+    for x, X in zip(xs, Xs):
+        _, _, vt = np.linalg.svd(np.asarray(x, float).reshape(1, 3))
+        rows.append((vt[1], np.asarray(X, float), 1.0))
+        rows.append((vt[2], np.asarray(X, float), 1.0))
+    for l, Cp, V in zip(ls, Cs, Vs):
+        rows.append((np.asarray(l, float), np.asarray(Cp, float), 1.0))
+        rows.append((np.asarray(l, float), np.asarray(V, float), 0.0))
+    return rows
+
+
+def residuals(q, t, xs, Xs, ls, Cs, Vs):
+    """the six constraints at (q, t), each normalised to the sine of an angle: n^T (R Y + sigma t) / |R Y + sigma t|"""
+    R = rotation(q)
+    out = []
+    for n, Y, s in constraint_rows(xs, Xs, ls, Cs, Vs):
+        v = R @ Y + s * np.asarray(t, float)
+        out.append(float(n @ v) / np.linalg.norm(v))
+    return np.array(out)
+
+
+def _pmul(a, b):
+    return np.polynomial.polynomial.polymul(a, b)
+
+
+def _padd(*ps):
+    n = max(len(p) for p in ps)
+    return sum(np.pad(np.asarray(p, float), (0, n - len(p))) for p in ps)
+
+
+def solve_minimal(xs, Xs, ls, Cs, Vs, imag_tol=1e-8):
+    """-> list of (qvec, tvec): the poses with positive point depths"""
+    rows = constraint_rows(xs, Xs, ls, Cs, Vs)
+    r1 = [(n, Y) for n, Y, s in rows if s == 1.0]
+    r0 = [(n, Y) for n, Y, s in rows if s == 0.0]
+    N = np.array([n for n, _ in r1])
+    A1 = np.array([quad_row(n, Y) for n, Y in r1])
+    m = len(r1)
+    eqs = []
+    if m > 3:
+        U, _, _ = np.linalg.svd(N)
+        eqs.extend((U[:, 3:].T @ A1))
+    eqs.extend(quad_row(n, Y) for n, Y in r0)
+    E = np.array(eqs)
+    assert E.shape == (3, 10)
+    G = E[:, [4, 5, 7]]
+    if np.linalg.cond(G) > 1e12:
+        return []
+    S = -np.linalg.solve(G, E[:, [6, 1, 8, 2, 9, 3, 0]])  # d e f g h i j per unknown x2, xy, y2
+    # P[k] = (px, py, pc): polynomials in z, ascending
+    P = [([S[k, 1], S[k, 0]], [S[k, 3], S[k, 2]], [S[k, 6], S[k, 5], S[k, 4]]) for k in range(3)]
+    (P1x, P1y, P1c), (P2x, P2y, P2c), (P3x, P3y, P3c) = P
+
+    def subst(a, b, c, lx, ly, lc):
+        """a x2 + b xy + c y2 + lx x + ly y + lc reduced to [x, y, 1]"""
+        return (_padd(_pmul(a, P1x), _pmul(b, P2x), _pmul(c, P3x), lx),
+                _padd(_pmul(a, P1y), _pmul(b, P2y), _pmul(c, P3y), ly),
+                _padd(_pmul(a, P1c), _pmul(b, P2c), _pmul(c, P3c), lc))
+
+    neg = lambda p: -np.asarray(p, float)  # noqa: E731
+    I1 = subst(P2x, _padd(P2y, neg(P1x)), neg(P1y), P2c, neg(P1c), [0.0])
+    I2 = subst(neg(P3x), _padd(P2x, neg(P3y)), P2y, neg(P3c), P2c, [0.0])
+    I3 = subst(_padd(_pmul(P1x, P3x), neg(_pmul(P2x, P2x))),
+               _padd(_pmul(P1x, P3y), _pmul(P1y, P3x), -2.0 * _pmul(P2x, P2y)),
+               _padd(_pmul(P1y, P3y), neg(_pmul(P2y, P2y))),
+               _padd(_pmul(P1x, P3c), _pmul(P1c, P3x), -2.0 * _pmul(P2x, P2c)),
+               _padd(_pmul(P1y, P3c), _pmul(P1c, P3y), -2.0 * _pmul(P2y, P2c)),
+               _padd(_pmul(P1c, P3c), neg(_pmul(P2c, P2c))))
+    Mz = [I1, I2, I3]
+
+    def minor(i, j, k, l):
+        return _padd(_pmul(Mz[i][k], Mz[j][l]), neg(_pmul(Mz[i][l], Mz[j][k])))
+
+    det = _padd(_pmul(Mz[0][0], minor(1, 2, 1, 2)), neg(_pmul(Mz[0][1], minor(1, 2, 0, 2))),
+                _pmul(Mz[0][2], minor(1, 2, 0, 1)))
+    det = np.pad(det, (0, max(0, 9 - len(det))))[:9]
+    if not np.all(np.isfinite(det)) or np.max(np.abs(det)) == 0.0:
+        return []
+    roots = np.roots(det[::-1])
+    pinvN = np.linalg.pinv(N)
+    out = []
+    for r in roots:
+        if abs(r.imag) > imag_tol * max(1.0, abs(r.real)):
+            continue
+        z = float(r.real)
+        Mn = np.array([[np.polynomial.polynomial.polyval(z, Mz[i][j]) for j in range(3)] for i in range(3)])
+        Mn = Mn / np.maximum(np.abs(Mn).max(axis=1, keepdims=True), 1e-300)
+        _, _, vt = np.linalg.svd(Mn)
+        v = vt[2]
+        if abs(v[2]) < 1e-12:
+            continue
+        q = np.array([1.0, v[0] / v[2], v[1] / v[2], z])
+        tp = -pinvN @ (A1 @ monomials(q))
+        n2 = float(q @ q)
+        t = tp / n2
+        q = q / np.sqrt(n2)
+        R = rotation(q)
+        if all(float(np.asarray(x, float) @ (R @ np.asarray(X, float) + t)) > 0.0 for x, X in zip(xs, Xs)):
+            out.append((q, t))
+    return out
+
+
+def pose_error(q, t, R_true, t_true):
+    """|R - R*|_F + |t - t*|"""
+    return float(np.linalg.norm(rotation(q) - R_true) + np.linalg.norm(np.asarray(t, float) - t_true))
+
+
+# ---- the hybrid loop's arithmetic, restated with Python integers and math.log ----
+import math
+
+MASK = (1 << 64) - 1
+GOLD = 0x9E3779B97F4A7C15
+LO_KEY = 0x80000000
+SIZES = [(3, 0), (2, 1), (1, 2), (0, 3)]  # min_sample_sizes: points, lines
+
+
+def fmix(z):
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & MASK
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & MASK
+    return z ^ (z >> 31)
+
+
+class Rng:
+    """SplitMix64's finaliser keyed by (seed, query, iteration, stream); draw c = fmix(key + c GOLD) >> 32, c = 1, 2, ..."""
+
+    def __init__(self, seed, query, iteration, stream):
+        k = fmix((seed + GOLD) & MASK)
+        for v in (query, iteration, stream):
+            k = fmix(k ^ ((v + GOLD) & MASK))
+        self.k, self.c = k, 0
+
+    def draw(self):
+        self.c += 1
+        return fmix((self.k + self.c * GOLD) & MASK) >> 32
+
+    def uniform(self, n):
+        thr = ((1 << 32) - n) % n
+        while True:
+            u = self.draw()
+            if u >= thr:
+                return u % n
+
+    def unit(self):
+        return (self.draw() + 0.5) / 4294967296.0
+
+
+def comb(n, m):
+    return math.comb(n, m) if n >= m else 0
+
+
+def priors(flags, n_pts, n_lines):
+    """solver_probabilities and VerifyData"""
+    return [float(comb(n_pts, a) * comb(n_lines, b)) if f and a <= n_pts and b <= n_lines else 0.0
+            for f, (a, b) in zip(flags, SIZES)]
+
+
+def probabilities(ratios, its, prior, min_it):
+    """SelectMinimalSolver's probabilities (Eq. 1), the all-zero inlier ratios included"""
+    if ratios[0] + ratios[1] == 0.0:
+        return list(prior)
+    out = []
+    for i, (a, b) in enumerate(SIZES):
+        n = float(its[i]) - (1.0 if its[i] > 0 else 0.0)
+        p = ratios[0] ** a * ratios[1] ** b
+        out.append(p * prior[i] if n < min_it else p * (1.0 - p) ** n * prior[i])
+    return out
+
+
+def select(prob, prior, u):
+    kprob, cur, last = u * sum(prob), 0.0, -1
+    for i in range(4):
+        if prior[i] == 0.0:
+            continue
+        last = i
+        cur += prob[i]
+        if kprob <= cur:
+            return i
+    return last
+
+
+def num_required(ratios, success, solver, min_it, max_it):
+    """NumRequiredIterations: p = prod ratio^size; ceil(log(1 - success) / log(1 - p) + 0.5) within [min, max]"""
+    a, b = SIZES[solver]
+    p = ratios[0] ** a * ratios[1] ** b
+    if p <= 0.0:
+        return max_it, 1.0
+    if p >= 1.0:
+        return min_it, 1.0
+    den = math.log1p(-p)
+    if den >= 0.0:
+        return max_it, 1.0
+    v = math.log(1.0 - success) / den + 0.5
+    frac = abs(v - round(v))  # how far from the integer where one rounding error moves the ceiling
+    return max(min_it, min(max_it, int(math.ceil(v)))) if v < max_it else max_it, frac
+
+
+def lo_sizes(n_base, non_min_mult):
+    """the non-minimal sample size of a local optimisation: max(6, min(3 multiplier, |inliers| / 2)), at most |inliers|"""
+    return min(max(6, min(3 * non_min_mult, n_base // 2)), n_base)
+
+
+def lo_thresholds(thr2, mult, num_lsq):
+    """the relaxed squared threshold and its decrement per least-squares iteration"""
+    return thr2 * mult, (mult - 1.0) * thr2 / (num_lsq - 1)

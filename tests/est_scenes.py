@@ -1,0 +1,178 @@
+"""Samples for the minimal solvers of limap_amd.estimators: planted poses with one minimal sample of a kind, built as
+JointPoseEstimator::MinimalSolver builds its inputs, and the degenerate samples a RANSAC meets."""
+import numpy as np
+
+import est_oracle as eo
+
+FIELDS = ("xs", "Xs", "ls", "Cs", "Vs")
+
+
+def random_rotation(rng):
+    return eo.rotation(rng.normal(size=4))
+
+
+def _arr(v):
+    return np.array(v, float).reshape(-1, 3)
+
+
+def _unit(v):
+    v = np.asarray(v, float)
+    return v / np.linalg.norm(v)
+
+
+def _cam_point(rng):
+    return np.array([rng.uniform(-1, 1), rng.uniform(-1, 1), 1.0]) * rng.uniform(2, 6)
+
+
+def _point(R, t, pc):
+    """bearing and world point of the camera-frame point pc"""
+    return _unit(pc), R.T @ (pc - t)
+
+
+def _line(R, t, a, b, shift=0.0):
+    """normal, point and direction of the line through the camera-frame points a, b; C moved along the line by shift"""
+    A, B = R.T @ (a - t), R.T @ (b - t)
+    V = _unit(B - A)
+    return _unit(np.cross(_unit(a), _unit(b))), A + shift * V, V
+
+
+def planted_sample(rng, kind, R=None, t=None):
+    """random rotation, t ~ N(0, I); points and line endpoints in the camera frame with x, y in [-1, 1] and depth in
+    [2, 6]; C moved along the line"""
+    npts = eo.N_POINTS[kind]
+    R = random_rotation(rng) if R is None else R
+    t = rng.normal(size=3) if t is None else t
+    pts = [_point(R, t, _cam_point(rng)) for _ in range(npts)]
+    lines = [_line(R, t, _cam_point(rng), _cam_point(rng), rng.uniform(-2, 2)) for _ in range(3 - npts)]
+    return dict(kind=kind, R=R, t=t, xs=_arr([p[0] for p in pts]), Xs=_arr([p[1] for p in pts]),
+                ls=_arr([l[0] for l in lines]), Cs=_arr([l[1] for l in lines]), Vs=_arr([l[2] for l in lines]))
+
+
+def planted_batch(kind, n, seed):
+    rng = np.random.default_rng(seed)
+    return [planted_sample(rng, kind) for _ in range(n)]
+
+
+def stack(samples):
+    """the five arrays of minimal_solver for samples of one kind"""
+    return tuple(np.array([s[k] for s in samples], float).reshape(len(samples), -1, 3) for k in FIELDS)
+
+
+def degenerate_samples(seed=11):
+    """name -> sample: what must return without a crash and without a NaN pose"""
+    rng = np.random.default_rng(seed)
+    out = {}
+    R, t = random_rotation(rng), rng.normal(size=3)
+    # three collinear world points
+    a, b = _cam_point(rng), _cam_point(rng)
+    pts = [_point(R, t, a + s * (b - a)) for s in (0.0, 0.4, 1.0)]
+    out["collinear_points"] = dict(kind="p3p", xs=_arr([p[0] for p in pts]), Xs=_arr([p[1] for p in pts]), ls=_arr([]),
+                                   Cs=_arr([]), Vs=_arr([]))
+    # two identical correspondences
+    s = planted_sample(rng, "p3p")
+    s["xs"][1], s["Xs"][1] = s["xs"][0], s["Xs"][0]
+    out["identical_points"] = s
+    s = planted_sample(rng, "p3ll")
+    for k in ("ls", "Cs", "Vs"):
+        s[k][2] = s[k][0]
+    out["identical_lines"] = s
+    s = planted_sample(rng, "p2p1ll")
+    s["xs"][1], s["Xs"][1] = s["xs"][0], s["Xs"][0]
+    out["identical_points_and_a_line"] = s
+    # three parallel 3D lines
+    d = np.array([0.3, -0.2, 0.1])
+    lines = []
+    for _ in range(3):
+        a = _cam_point(rng)
+        lines.append(_line(R, t, a, a + d))
+    out["parallel_lines"] = dict(kind="p3ll", xs=_arr([]), Xs=_arr([]), ls=_arr([l[0] for l in lines]),
+                                 Cs=_arr([l[1] for l in lines]), Vs=_arr([l[2] for l in lines]))
+    # a line through the camera centre: its image is a point, any normal orthogonal to its direction serves
+    s = planted_sample(rng, "p1p2ll")
+    centre = -s["R"].T @ s["t"]
+    V = _unit(rng.normal(size=3))
+    s["Cs"][0], s["Vs"][0] = centre + 1.5 * V, V
+    s["ls"][0] = _unit(np.cross(s["R"] @ V, rng.normal(size=3)))
+    out["line_through_centre"] = s
+    # a rotation by 180 degrees (w = 0), outside the chart
+    for kind in eo.KINDS:
+        axis = _unit(rng.normal(size=3))
+        out["half_turn_" + kind] = planted_sample(rng, kind, R=eo.rotation(np.concatenate([[0.0], axis])))
+    # the bearings negated: the planted pose fails the depth test, the mirrored configuration's poses pass it
+    s = planted_sample(rng, "p3p")
+    s["xs"] = -s["xs"]
+    out["negated_bearings"] = s
+    # zero vectors
+    s = planted_sample(rng, "p2p1ll")
+    s["xs"][0] = 0.0
+    out["zero_bearing"] = s
+    s = planted_sample(rng, "p3ll")
+    s["ls"][1] = 0.0
+    s["Vs"][2] = 0.0
+    out["zero_normal_and_direction"] = s
+    s = planted_sample(rng, "p3p")
+    s["Xs"][:] = 0.0
+    out["all_points_at_origin"] = s
+    return out
+
+
+# ---- planted scenes for the hybrid loop ----
+KVEC = np.array([600.0, 590.0, 400.0, 300.0])
+
+
+def _pix(pc):
+    return np.array([KVEC[0] * pc[0] / pc[2] + KVEC[2], KVEC[1] * pc[1] / pc[2] + KVEC[3]])
+
+
+def planted_scene(n_pts=40, n_segs=30, n_l3d=20, outliers=0.4, noise=0.5, seed=0):
+    """A planted pose with n_pts point matches and n_segs line matches on n_l3d 3D lines; the first `outliers` share of
+    each type is wrong (the 2D side drawn anew), the rest carries `noise` pixels; a segment spans its 3D line.  -> dict with the runner's arguments,
+    the ground truth (R, t, qvec) and the planted inlier masks."""
+    rng = np.random.default_rng(seed)
+    q = rng.normal(size=4)
+    q = q / np.linalg.norm(q) * (1 if q[0] > 0 else -1)
+    R, t = eo.rotation(q), rng.normal(size=3)
+
+    def cam():
+        return np.array([rng.uniform(-1.2, 1.2), rng.uniform(-0.9, 0.9), 1.0]) * rng.uniform(2, 6)
+
+    n_out_p, n_out_l = int(round(outliers * n_pts)), int(round(outliers * n_segs))
+    p3ds, p2ds = [], []
+    for i in range(n_pts):
+        pc = cam()
+        p3ds.append(R.T @ (pc - t))
+        p2ds.append(_pix(cam()) if i < n_out_p else _pix(pc) + rng.normal(0, noise, 2))
+    ends = []
+    while len(ends) < n_l3d:  # lines whose image is at least 60 pixels long
+        a = cam()
+        b = a + rng.normal(0, 0.8, 3)
+        b[2] = max(b[2], 1.5)
+        if np.linalg.norm(_pix(a) - _pix(b)) >= 60.0:
+            ends.append((a, b))
+    l3ds = [np.concatenate([R.T @ (a - t), R.T @ (b - t)]).reshape(2, 3) for a, b in ends]
+    l3d_ids, l2ds = [], []
+    for i in range(n_segs):
+        j = i % n_l3d if n_l3d else 0
+        a, b = ends[j]
+        l3d_ids.append(j)
+        if i < n_out_l:
+            l2ds.append(np.concatenate([_pix(cam()), _pix(cam())]).reshape(2, 2))
+        else:
+            l2ds.append(np.concatenate([_pix(a) + rng.normal(0, noise, 2), _pix(b) + rng.normal(0, noise, 2)]).reshape(2, 2))
+    arr = lambda v, *sh: np.array(v, float).reshape(-1, *sh)  # noqa: E731
+    return dict(l3ds=arr(l3ds, 2, 3), l3d_ids=np.array(l3d_ids, int), l2ds=arr(l2ds, 2, 2), p3ds=arr(p3ds, 3), p2ds=arr(p2ds, 2),
+                camera=KVEC.copy(), R=R, t=t, qvec=q, inlier_points=np.arange(n_pts) >= n_out_p,
+                inlier_lines=np.arange(n_segs) >= n_out_l)
+
+
+def loc_cfg(method="hybrid", thres=10.0, flags=(True, True, True, True), final_least_squares=True, cost="PerpendicularDist",
+            min_num_iterations=100, **ransac):
+    """cfgs/localization/default.yaml's `localization` block as a dict"""
+    return dict(ransac=dict(method=method, thres=thres, thres_point=thres, thres_line=thres, weight_point=1.0, weight_line=1.0,
+                            final_least_squares=final_least_squares, min_num_iterations=min_num_iterations,
+                            solver_flags=list(flags), **ransac),
+                optimize=dict(loss_func="TrivialLoss", loss_func_args=[]), line_cost_func=cost, line_weight=1.0)
+
+
+def query_of(sc):
+    return {k: sc[k] for k in ("l3ds", "l3d_ids", "l2ds", "p3ds", "p2ds", "camera")}

@@ -1,0 +1,152 @@
+"""-m gpu: the minimal pose solvers on the device (k_est_minimal of lt_kernels_est.hip) equal the host twin
+(lt_fn_est_minimal_host) bit for bit -- every pose, every count -- at batch sizes around the block width, on the
+degenerate samples, and from run to run; the hybrid loop (lt_est_solve: k_est_draw, k_est_score, k_est_replay) equals
+lt_fn_est_host bit for bit on poses, scores, inlier lists, every statistic and the trace."""
+import numpy as np
+import pytest
+
+import est_oracle as eo
+import est_scenes as es
+from limap_amd import _capi
+from limap_amd import estimators as est
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def ctx(gpu_lib):
+    return _capi.Context()
+
+
+def both(ctx, kind, arrays):
+    return est.minimal_solver(kind, *arrays, ctx=ctx), est.minimal_solver(kind, *arrays, host_threads=8)
+
+
+def same(dev, host, what):
+    assert np.array_equal(dev[1], host[1]), (what, "counts", np.flatnonzero(dev[1] != host[1])[:5])
+    assert dev[0].tobytes() == host[0].tobytes(), (what, "poses", np.flatnonzero((dev[0] != host[0]).any(axis=(1, 2)))[:5])
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 257])
+@pytest.mark.parametrize("kind", eo.KINDS)
+def test_device_equals_the_twin(ctx, kind, n):
+    arrays = es.stack(es.planted_batch(kind, n, 1000 + n))
+    dev, host = both(ctx, kind, arrays)
+    same(dev, host, (kind, n))
+    assert dev[1].sum() >= n  # the planted poses are there: the kernel did run
+
+
+def test_device_finds_the_planted_poses(ctx):
+    for kind in eo.KINDS:
+        S = es.planted_batch(kind, 64, 77)
+        poses, counts = est.minimal_solver(kind, *es.stack(S), ctx=ctx)
+        err = [min([eo.pose_error(poses[i, j, :4], poses[i, j, 4:], s["R"], s["t"]) for j in range(counts[i])], default=np.inf)
+               for i, s in enumerate(S)]
+        assert np.mean(np.array(err) < 1e-6) >= 0.95, kind
+
+
+def test_degenerate_samples_on_the_device(ctx):
+    D = es.degenerate_samples()
+    for kind in eo.KINDS:
+        group = [D[k] for k in sorted(D) if D[k]["kind"] == kind]
+        # the degenerate samples between healthy ones: a lane that returns early does not disturb its wave
+        batch = es.planted_batch(kind, 3, 5) + group + es.planted_batch(kind, 70, 6)
+        dev, host = both(ctx, kind, es.stack(batch))
+        same(dev, host, kind)
+        assert np.isfinite(dev[0]).all()
+
+
+def test_repeated_runs_and_an_empty_batch(ctx):
+    arrays = es.stack(es.planted_batch("p3ll", 130, 9))
+    a = est.minimal_solver("p3ll", *arrays, ctx=ctx)
+    est.minimal_solver("p3p", *es.stack(es.planted_batch("p3p", 5, 1)), ctx=ctx)  # another call in between
+    b = est.minimal_solver("p3ll", *arrays, ctx=ctx)
+    same(a, b, "repeat")
+    p, c, tm = est.minimal_solver("p3p", np.zeros((0, 3, 3)), np.zeros((0, 3, 3)), ctx=ctx, return_timers=True)
+    assert p.shape == (0, 8, 7) and c.shape == (0,) and tm["solve_device_ms"] == 0.0
+    with pytest.raises(ValueError, match="non-finite"):
+        est.minimal_solver("p3p", np.full((1, 3, 3), np.nan), np.zeros((1, 3, 3)), ctx=ctx)
+
+
+# ======== the hybrid loop: lt_est_solve against lt_fn_est_host ========
+LOOP_KEYS = ("qvec", "tvec", "dstats", "istats", "inliers", "trace")
+
+
+def loop_both(ctx, scenes, cfg=None, seed=3, trace_cap=300, **fields):
+    csr = est._query_arrays([es.query_of(s) for s in scenes])
+    st = est._hybrid_options(cfg or es.loc_cfg(), None, seed)._struct()
+    for k, v in fields.items():
+        setattr(st, k, v)
+    return est.hybrid_arrays(csr, st, ctx=ctx, trace_cap=trace_cap), est.hybrid_arrays(csr, st, host_threads=8, trace_cap=trace_cap)
+
+
+def loop_same(dev, host, what):
+    for k in LOOP_KEYS:  # poses, scores and ratios, every statistic, the inlier lists, the trace
+        assert dev[k].tobytes() == host[k].tobytes(), (what, k)
+
+
+def sized(n, seed):
+    return es.planted_scene(n_pts=n - n // 3, n_segs=n // 3, n_l3d=max(n // 4, 1), seed=seed)
+
+
+@pytest.mark.parametrize("round_size", [1, 64, 100])
+def test_loop_round_sizes(ctx, round_size):
+    dev, host = loop_both(ctx, [es.planted_scene(seed=1)], round_size=round_size)
+    loop_same(dev, host, round_size)
+    assert dev["stats"][0].ran and dev["stats"][0].number_lo_iterations >= 1
+
+
+@pytest.mark.parametrize("n", [3, 63, 64, 65, 130])
+def test_loop_correspondence_counts_around_the_wave(ctx, n):
+    kw = dict(max_num_iterations=300) if n == 3 else {}
+    dev, host = loop_both(ctx, [sized(n, n)], **kw)
+    loop_same(dev, host, n)
+
+
+@pytest.mark.parametrize("n_query", [1, 3, 65])
+def test_loop_batches_of_unequal_queries_with_one_rejected(ctx, n_query):
+    scenes = [es.planted_scene(n_pts=8 + i % 7, n_segs=6 + i % 5, n_l3d=5, seed=100 + i) for i in range(n_query)]
+    if n_query > 1:
+        scenes[1] = es.planted_scene(n_pts=1, n_segs=1, n_l3d=1, seed=9)  # VerifyData rejects it beside ones that run
+    dev, host = loop_both(ctx, scenes)
+    loop_same(dev, host, n_query)
+    ran = [s.ran for s in dev["stats"]]
+    assert ran == [not (n_query > 1 and i == 1) for i in range(n_query)]
+    assert dev["timers"]["rounds"] >= 1
+
+
+def test_loop_ends_at_the_cap_inside_a_round_and_at_max_iterations(ctx):
+    dev, host = loop_both(ctx, [es.planted_scene(seed=1)], cfg=es.loc_cfg(min_num_iterations=10), max_num_iterations_per_solver=37)
+    loop_same(dev, host, "cap")
+    s = dev["stats"][0]
+    its = [r for r in dev["trace"][0] if r[0] == 0 and r[3] + r[10] > 0]  # the iteration records; the last one breaks
+    assert 37 in s.num_iterations_per_solver and s.num_iterations_total % 64 != 63 and int(its[-1][5]) & 8
+    assert int(its[-1][1]) == s.num_iterations_total  # the breaking iteration does not count
+    dev, host = loop_both(ctx, [es.planted_scene(outliers=0.9, seed=4)], max_num_iterations=150)
+    loop_same(dev, host, "max")
+    assert dev["stats"][0].num_iterations_total == 150
+
+
+def test_loop_lo_samples_of_6_and_of_more_than_64(ctx):
+    dev, host = loop_both(ctx, [es.planted_scene(n_pts=8, n_segs=6, n_l3d=5, outliers=0.2, seed=6)])
+    loop_same(dev, host, "lo 6")
+    assert 6 in [int(r[5]) for r in dev["trace"][0] if r[0] == 1]
+    dev, host = loop_both(ctx, [es.planted_scene(n_pts=200, n_segs=100, n_l3d=60, outliers=0.2, seed=5)],
+                          non_min_sample_multiplier=30, min_sample_multiplicator=30)
+    loop_same(dev, host, "lo > 64")
+    assert max(int(r[5]) for r in dev["trace"][0] if r[0] == 1) > 64
+
+
+def test_loop_repeated_runs_and_the_public_call(ctx):
+    scenes = [es.planted_scene(seed=2), sized(65, 3)]
+    a, _ = loop_both(ctx, scenes)
+    loop_both(ctx, [es.planted_scene(n_pts=200, n_segs=100, n_l3d=60, seed=5)])  # a larger call in between: other buffers
+    b, host = loop_both(ctx, scenes)
+    loop_same(a, b, "repeat")
+    loop_same(b, host, "repeat against the twin")
+    sc, cfg = scenes[0], es.loc_cfg()
+    pose, stats = est.pl_estimate_absolute_pose(cfg, sc["l3ds"], sc["l3d_ids"], sc["l2ds"], sc["p3ds"], sc["p2ds"], sc["camera"])
+    hpose, hstats = est.pl_estimate_absolute_pose(cfg, sc["l3ds"], sc["l3d_ids"], sc["l2ds"], sc["p3ds"], sc["p2ds"], sc["camera"],
+                                                  host=True)
+    assert pose.qvec.tobytes() == hpose.qvec.tobytes() and stats.inlier_indices == hstats.inlier_indices
+    assert eo.pose_error(pose.qvec, pose.tvec, sc["R"], sc["t"]) < 0.05
