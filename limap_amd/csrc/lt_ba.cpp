@@ -385,22 +385,6 @@ void run_host(const Plan &pl, int n_threads, Result &res) {
 }
 
 // ---- constant poses: every point track its own problem (k_ba_point_lm) ----
-struct HostPointGroup {
-  const BaDev &d;
-  const BaStruct &st;
-  double cost(const double p[3]) const {
-    double part[kBaWidth][kRfSums], out[kRfSums];
-    for (int l = 0; l < kBaWidth; ++l) part[l][0] = ba_point_cost_part(d, st, l, p);
-    lm_tree_host(part, 1, out);
-    return 0.5 * out[0];
-  }
-  void linearise(const double p[3], double acc[kRfSums]) const {
-    double part[kBaWidth][kRfSums];
-    for (int l = 0; l < kBaWidth; ++l) ba_point_lin_part(d, st, l, p, part[l]);
-    lm_tree_host(part, kRfSums, acc);
-  }
-};
-
 void bind_points(const Plan &pl, BaDev &d) {
   d = BaDev{};
   bind_plan(pl, d);
@@ -418,7 +402,7 @@ void run_points_host(const Plan &pl, int n_threads, std::vector<BaPtOut> &out) {
   for (int s = 0; s < pl.NS; ++s) {
     BaPtOut &o = out[(size_t)s];
     for (int c = 0; c < 3; ++c) o.p[c] = pl.sp0[6 * (size_t)s + c];
-    HostPointGroup grp{d, pl.st[(size_t)s]};
+    BaPointGroup<LmHostLanes<kBaWidth>> grp{{}, d, pl.st[(size_t)s]};
     ba_point_lm(grp, pl.st[(size_t)s].constant != 0, pl.max_iter, o.p, &o.cost0, &o.cost1, &o.iters, &o.code);
   }
 }
@@ -846,7 +830,7 @@ int lt_fn_ba_point_eval(int n_img, const int32_t *img_ids, const double *kvec4, 
   std::vector<double> pose = pl.pose0, sp = pl.sp0;
   d.kvec = pl.kvec.data(); d.pose = pose.data(); d.sp = sp.data();
   d.st = pl.st.data(); d.blk = pl.blk.data();
-  HostPointGroup grp{d, pl.st[(size_t)track]};
+  BaPointGroup<LmHostLanes<kBaWidth>> grp{{}, d, pl.st[(size_t)track]};
   if (cost) *cost = grp.cost(p3);
   double acc[kRfSums];
   grp.linearise(p3, acc);

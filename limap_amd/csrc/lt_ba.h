@@ -479,6 +479,22 @@ LT_HD void ba_point_lin_part(const BaDev &d, const BaStruct &st, int lane, const
     lm_block_add<2, 4>(r, rho1, J, part);
   }
 }
+// the group of a point track over the lanes.  The host twin runs it over LmHostLanes; k_ba_point_lm keeps a device
+// group of its own over the same two parts
+template <class Lanes>
+struct BaPointGroup {
+  Lanes lanes;
+  const BaDev &d;
+  const BaStruct &st;
+  LT_HD double cost(const double p[3]) const {
+    double s;
+    lanes.template sum<1>(1, [&](int l, double *a) { a[0] = ba_point_cost_part(d, st, l, p); }, &s);
+    return 0.5 * s;
+  }
+  LT_HD void linearise(const double p[3], double acc[kRfSums]) const {
+    lanes.template sum<kRfSums>(kRfSums, [&](int l, double *a) { ba_point_lin_part(d, st, l, p, a); }, acc);
+  }
+};
 
 // the launches of lt_kernels_ba.hip; every kernel reads the status record and returns at once when the solve has ended
 void launch_ba_init(hipStream_t st, const BaDev &dev);     // the cost at the initial point, then k_ba_decide's first call

@@ -108,16 +108,7 @@ int make_loop_plan(int64_t Q, const double *kvec4, const double *qvec4, const do
   }
   const lt_loc_config &lc = c->loc;
   if (lc.cost_function == kLcMidpointAngle3) { msg = "E2DMidpointAngleDist3 is not compatible with scoring (upstream throws)"; return 1; }
-  if (lc.cost_function < kLcMidpoint2 || lc.cost_function > kLcPlaneLine2) { msg = "unknown line cost function"; return 1; }
-  if (lc.weight_function == kLcLine3dpp) { msg = "ELine3dppWeight is not built (it needs an arccosine)"; return 1; }
-  if (lc.weight_function < kLcNone || lc.weight_function > kLcInvLength) { msg = "unknown line weight function"; return 1; }
-  if (lc.loss < kLcTrivial || lc.loss > kLcCauchy) { msg = "unknown loss function"; return 1; }
-  if (lc.loss != kLcTrivial && !(lc.loss_a > 0.0 && std::isfinite(lc.loss_a))) { msg = "the loss parameter must be > 0"; return 1; }
-  if (lc.max_num_iterations < 0 || !std::isfinite(lc.weight_line) || !std::isfinite(lc.weight_point) || lc.weight_line < 0.0 ||
-      lc.weight_point < 0.0) {
-    msg = "bad refinement configuration";
-    return 1;
-  }
+  if (lc_check_config(&lc, pl.opt.lsq, msg)) return 1;
   for (int i = 0; i < 2; ++i)
     if (!(c->squared_inlier_thresholds[i] >= 0.0) || !std::isfinite(c->squared_inlier_thresholds[i]) || !std::isfinite(c->data_type_weights[i])) {
       msg = "non-finite or negative threshold or weight";
@@ -157,11 +148,6 @@ int make_loop_plan(int64_t Q, const double *kvec4, const double *qvec4, const do
   o.solver_flags = 0;
   for (int i = 0; i < 4; ++i) o.solver_flags |= (c->solver_flags[i] ? 1 : 0) << i;
   o.trace_cap = (int)trace_cap;
-  o.lsq.cost = lc.cost_function; o.lsq.weight = lc.weight_function; o.lsq.loss = lc.loss;
-  o.lsq.points_3d_dist = (lc.cost_function == kLcLineLine2 || lc.cost_function == kLcPlaneLine2) ? 1 : 0;
-  o.lsq.loss_a = lc.loss == kLcTrivial ? 1.0 : lc.loss_a;
-  o.lsq.max_iter = lc.max_num_iterations;
-  o.lsq.pad_ = 0;
   pl.poll = c->poll_interval > 0 ? c->poll_interval : 4;
   pl.Q = Q;
   pl.N = N;
@@ -187,22 +173,15 @@ int make_loop_plan(int64_t Q, const double *kvec4, const double *qvec4, const do
     const long long n_l3d = l3d_off[q + 1] - l3d_off[q];
     for (long long a = 0; a < qr.n_pts; ++a) {
       const long long i = qr.c0 + a, src = pt_off[q] + a;
-      for (int f = 0; f < 3; ++f) tab[(long long)f * st + i] = p3d3[3 * src + f];
-      tab[6 * st + i] = p2d2[2 * src];
-      tab[7 * st + i] = p2d2[2 * src + 1];
+      lc_score_fill_point(tab, st, i, p3d3 + 3 * src, p2d2 + 2 * src);
       pl.ids[(size_t)i] = -1;
     }
     for (long long a = 0; a < qr.n_lines; ++a) {
       const long long i = qr.c0 + qr.n_pts + a, src = seg_off[q] + a, id = l3d_ids[src];
-      if (id < 0 || id >= n_l3d) { msg = "query " + std::to_string(q) + ": l3d_id " + std::to_string(id) + " is outside its " + std::to_string(n_l3d) + " 3D lines"; return 1; }
-      const double *l3 = line3d6 + 6 * (l3d_off[q] + id);
-      const double dx = l3[3] - l3[0], dy = l3[4] - l3[1], dz = l3[5] - l3[2];
-      if (!(std::sqrt((dx * dx + dy * dy) + dz * dz) > 0.0)) { msg = "query " + std::to_string(q) + ": 3D line " + std::to_string(id) + " has zero length"; return 1; }
-      double dm[6];
-      lc_item_prep(l3, dm, dm + 3);
-      for (int f = 0; f < 6; ++f) tab[(long long)f * st + i] = l3[f];
-      for (int f = 0; f < 4; ++f) tab[(long long)(6 + f) * st + i] = seg4[4 * src + f];
-      for (int f = 0; f < 6; ++f) tab[(long long)(10 + f) * st + i] = dm[f];
+      if (lc_score_fill_line(tab, st, i, n_l3d, line3d6 + 6 * l3d_off[q], id, seg4 + 4 * src, nullptr, nullptr, msg)) {
+        msg = "query " + std::to_string(q) + ": " + msg;
+        return 1;
+      }
       pl.ids[(size_t)i] = (int)id;
     }
     eh_init(o, qr, pl.st[(size_t)q]);
@@ -212,64 +191,7 @@ int make_loop_plan(int64_t Q, const double *kvec4, const double *qvec4, const do
 }
 
 // the host twin's wave
-struct HostLm {
-  const LcCfg &cfg;
-  const double *blk;
-  long long stride, b0;
-  int n;
-  const double *k;
-  double cost(const double p[7]) const {
-    double part[kLcWidth][kLcSums];
-    for (int l = 0; l < kLcWidth; ++l) {
-      double s = 0.0;
-      for (int i = l; i < n; i += kLcWidth) s = s + lc_cost_term(cfg, k, p, lc_load(blk, stride, b0 + i));
-      part[l][0] = s;
-    }
-    double out[kLcSums];
-    lm_tree_host(part, 1, out);
-    return 0.5 * out[0];
-  }
-  void linearise(const double p[7], double acc[kLcSums]) const {
-    double part[kLcWidth][kLcSums];
-    for (int l = 0; l < kLcWidth; ++l) {
-      for (int c = 0; c < kLcSums; ++c) part[l][c] = 0.0;
-      for (int i = l; i < n; i += kLcWidth) lc_accumulate(cfg, k, p, lc_load(blk, stride, b0 + i), part[l]);
-    }
-    lm_tree_host(part, kLcSums, acc);
-  }
-};
-
-struct HostWave {
-  const EhDev &d;
-  const EhQuery &qr;
-  LcScoreCfg sc;
-  bool lead() const { return true; }
-  void sync() const {}
-  double score_impl(const double m[7], bool store) const {
-    LcPose ps;
-    lc_pose_build(qr.k, m, m + 4, &ps);
-    const int N = qr.n_pts + qr.n_lines;
-    double part[kLcWidth][kLcSums];
-    for (int l = 0; l < kLcWidth; ++l) part[l][0] = 0.0;
-    for (int i = 0; i < N; ++i) {
-      const bool is_point = i < qr.n_pts;
-      const double r2 = lc_score_cell(sc, qr.k, ps, lc_load_item(d.tab, d.stride, qr.c0 + i, is_point));
-      if (store) d.r2[qr.c0 + i] = r2;
-      double &p = part[i % kLcWidth][0];
-      p = p + lc_msac_term(sc, is_point ? 0 : 1, r2);
-    }
-    double out[kLcSums];
-    lm_tree_host(part, 1, out);
-    return out[0];
-  }
-  double score(const double m[7]) const { return score_impl(m, true); }
-  void lm(const LcCfg &cfg, int n_blocks, double p[7], int *code) const {
-    HostLm grp{cfg, d.blk, d.stride, qr.c0, n_blocks, qr.k};
-    double F0, F1;
-    int it;
-    lc_lm(grp, n_blocks, cfg.max_iter, p, &F0, &F1, &it, code);
-  }
-};
+typedef EhWave<LmHostLanes<kLcWidth>> HostWave;
 
 struct LoopResult {
   std::vector<EhState> st;
@@ -300,7 +222,7 @@ void run_loop_host(const LoopPlan &pl, int n_threads, LoopResult &res) {
 #pragma omp parallel for num_threads(nt) schedule(dynamic, 1)
   for (long long q = 0; q < Q; ++q) {
     const EhQuery &qr = d.qs[q];
-    HostWave g{d, qr, eh_score_cfg(d.opt, qr)};
+    HostWave g{{}, d, qr, eh_score_cfg(d.opt, qr)};
     while (!d.st[q].done) {
       for (int slot = 0; slot < R; ++slot) eh_draw_solve(d, q, slot);
       for (int slot = 0; slot < R; ++slot) {

@@ -202,6 +202,31 @@ LT_HD LcScoreCfg eh_score_cfg(const EhOpt &o, const EhQuery &qr) {
   return sc;
 }
 
+// the group G of the replay: what a wave does together, over the lanes (LmWaveLanes in the kernels, LmHostLanes in the
+// host twin)
+template <class Lanes>
+struct EhWave {
+  Lanes lanes;
+  const EhDev &d;
+  const EhQuery &qr;
+  LcScoreCfg sc;
+  LT_HD bool lead() const { return lanes.lead(); }
+  LT_HD void sync() const { lanes.sync(); }
+  LT_HD double score_impl(const double m[7], bool store) const {
+    const double sum = lc_msac_sum(lanes, sc, qr.k, m, m + 4, d.tab, d.stride, qr.c0, qr.n_pts, qr.n_lines,
+                                   [&](int i, bool, double r2) { if (store) d.r2[qr.c0 + i] = r2; });
+    if (store) lanes.sync();
+    return sum;
+  }
+  LT_HD double score(const double m[7]) const { return score_impl(m, true); }
+  LT_HD void lm(const LcCfg &cfg, int n_blocks, double p[7], int *code) const {
+    LcGroup<Lanes> grp{lanes, cfg, d.blk, d.stride, qr.c0, n_blocks, qr.k};
+    double F0, F1;
+    int it;
+    lc_lm(grp, n_blocks, cfg.max_iter, p, &F0, &F1, &it, code);
+  }
+};
+
 // ---- step 1: one iteration slot of a round ----
 ES_HD void eh_draw_solve(const EhDev &d, long long q, int slot) {
   const EhState &s = d.st[q];

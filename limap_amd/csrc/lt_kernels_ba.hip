@@ -210,7 +210,9 @@ __global__ void __launch_bounds__(kBaWave) k_ba_decide(BaDev d, int mode) {
   if (threadIdx.x == 0) *d.status = st;
 }
 
-// constant poses: the whole loop of a point track by its 16-lane group (§19's k_refine_lm with three unknowns)
+// constant poses: the whole loop of a point track by its 16-lane group (§19's k_refine_lm with three unknowns).  The
+// group is the kernel's own; its host twin is BaPointGroup over LmHostLanes.  With BaPointGroup over the wave's lanes
+// the kernel keeps its registers and is 10 % slower
 struct PointGroup {
   const BaDev &d;
   const BaStruct &st;

@@ -29,56 +29,7 @@ __global__ void __launch_bounds__(kEsBlock) k_est_minimal(EsDev dev, double *__r
   counts[i] = n;
 }
 
-// what a wave does together in the replay
-struct EhLm {
-  const LcCfg &cfg;
-  const double *blk;
-  long long stride, b0;
-  int n;
-  const double *k;
-  int lane;
-  __device__ __forceinline__ double cost(const double p[7]) const {
-    double part = 0.0;
-    for (int i = lane; i < n; i += kLcWidth) part = part + lc_cost_term(cfg, k, p, lc_load(blk, stride, b0 + i));
-    return 0.5 * lm_group_sum<kLcWidth>(part);
-  }
-  __device__ __forceinline__ void linearise(const double p[7], double acc[kLcSums]) const {
-    for (int c = 0; c < kLcSums; ++c) acc[c] = 0.0;
-    for (int i = lane; i < n; i += kLcWidth) lc_accumulate(cfg, k, p, lc_load(blk, stride, b0 + i), acc);
-    for (int c = 0; c < kLcSums; ++c) acc[c] = lm_group_sum<kLcWidth>(acc[c]);
-  }
-};
-
-struct EhWave {
-  const EhDev &d;
-  const EhQuery &qr;
-  LcScoreCfg sc;
-  int lane;
-  __device__ __forceinline__ bool lead() const { return lane == 0; }
-  __device__ __forceinline__ void sync() const { __syncthreads(); }
-  __device__ __forceinline__ double score_impl(const double m[7], bool store) const {
-    LcPose ps;
-    lc_pose_build(qr.k, m, m + 4, &ps);
-    const int N = qr.n_pts + qr.n_lines;
-    double part = 0.0;
-    for (int i = lane; i < N; i += kLcWidth) {
-      const bool is_point = i < qr.n_pts;
-      const double r2 = lc_score_cell(sc, qr.k, ps, lc_load_item(d.tab, d.stride, qr.c0 + i, is_point));
-      if (store) d.r2[qr.c0 + i] = r2;
-      part = part + lc_msac_term(sc, is_point ? 0 : 1, r2);
-    }
-    part = lm_group_sum<kLcWidth>(part);
-    if (store) __syncthreads();
-    return part;
-  }
-  __device__ __forceinline__ double score(const double m[7]) const { return score_impl(m, true); }
-  __device__ __forceinline__ void lm(const LcCfg &cfg, int n_blocks, double p[7], int *code) const {
-    EhLm grp{cfg, d.blk, d.stride, qr.c0, n_blocks, qr.k, lane};
-    double F0, F1;
-    int it;
-    lc_lm(grp, n_blocks, cfg.max_iter, p, &F0, &F1, &it, code);
-  }
-};
+typedef EhWave<LmWaveLanes<kLcWidth>> DevWave;
 
 __global__ void __launch_bounds__(kEsBlock) k_est_draw(EhDev d) {
   const long long idx = (long long)blockIdx.x * kEsBlock + threadIdx.x;
@@ -92,7 +43,7 @@ __global__ void __launch_bounds__(kLcWidth) k_est_score(EhDev d) {
   const int m = (int)(idx % kEsMaxSol);
   if (q >= d.n_queries || m >= d.r_counts[ri]) return;
   const EhQuery &qr = d.qs[q];
-  const EhWave g{d, qr, eh_score_cfg(d.opt, qr), (int)threadIdx.x};
+  const DevWave g{{(int)threadIdx.x}, d, qr, eh_score_cfg(d.opt, qr)};
   const double sc = g.score_impl(d.r_poses + (ri * kEsMaxSol + m) * kEsPoseDoubles, false);
   if (threadIdx.x == 0) d.r_scores[ri * kEsMaxSol + m] = sc;
 }
@@ -103,7 +54,7 @@ __global__ void __launch_bounds__(kLcWidth) k_est_replay(EhDev d) {
   EhState s = d.st[q];
   if (s.done) return;
   const EhQuery &qr = d.qs[q];
-  EhWave g{d, qr, eh_score_cfg(d.opt, qr), (int)threadIdx.x};
+  DevWave g{{(int)threadIdx.x}, d, qr, eh_score_cfg(d.opt, qr)};
   eh_replay(g, d, q, s);
   if (threadIdx.x == 0) {
     d.st[q] = s;

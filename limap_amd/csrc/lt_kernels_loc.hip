@@ -15,6 +15,8 @@ namespace lt {
 
 namespace {
 
+// k_loc_lm's own group; its host twin is LcGroup over LmHostLanes.  With LcGroup over the wave's lanes the kernel keeps
+// its registers and scratch and is 1.5 - 3 % slower
 struct DevGroup {
   const LcDev &dev;
   const LcProb &pr;
@@ -57,24 +59,15 @@ __global__ void __launch_bounds__(kLcWidth) k_loc_score(LcScoreDev dev, double *
                                                        double *__restrict__ scores, int *__restrict__ inliers) {
   const long long h = blockIdx.x;
   if (h >= dev.n_poses) return;
-  const int lane = threadIdx.x, np = dev.sc.n_points;
-  const long long N = (long long)np + dev.sc.n_lines;
-  LcPose ps;
-  lc_pose_build(dev.k, dev.qvec + 4 * h, dev.tvec + 3 * h, &ps);
-  double part = 0.0;
+  const int lane = threadIdx.x;
+  const long long N = (long long)dev.sc.n_points + dev.sc.n_lines;
   int in0 = 0, in1 = 0;
-  for (long long i = lane; i < N; i += kLcWidth) {
-    const bool is_point = i < np;
-    const double r2 = lc_score_cell(dev.sc, dev.k, ps, lc_load_item(dev.tab, dev.stride, i, is_point));
+  const double part = lc_msac_sum(LmWaveLanes<kLcWidth>{lane}, dev.sc, dev.k, dev.qvec + 4 * h, dev.tvec + 3 * h, dev.tab,
+                                  dev.stride, 0, dev.sc.n_points, dev.sc.n_lines, [&](int i, bool is_point, double r2) {
     table[h * N + i] = r2;
-    if (dev.sc.want_msac) {
-      const int type = is_point ? 0 : 1;
-      part = part + lc_msac_term(dev.sc, type, r2);
-      if (r2 < dev.sc.thr2[type]) (is_point ? in0 : in1) += 1;
-    }
-  }
+    if (dev.sc.want_msac && r2 < dev.sc.thr2[is_point ? 0 : 1]) (is_point ? in0 : in1) += 1;
+  });
   if (dev.sc.want_msac) {
-    part = lm_group_sum<kLcWidth>(part);
 #pragma unroll
     for (int m = kLcWidth / 2; m >= 1; m >>= 1) {
       in0 += __shfl_xor(in0, m, kLcWidth);

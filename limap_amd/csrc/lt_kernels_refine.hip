@@ -48,28 +48,6 @@ __global__ void __launch_bounds__(256) k_refine_prep(const double *__restrict__ 
   }
 }
 
-// the reductions of rf_lm over the group's lanes: lane l takes supports l, l + kRfWidth, ... in ascending order
-struct DevGroup {
-  const RfDev &dev;
-  const RfTrack &t;
-  int lane;
-  __device__ __forceinline__ double cost(const double p[6]) const {
-    double dm[6];
-    rf_plucker<double>(p, p + 4, dm);
-    double part = 0.0;
-    for (int k = lane; k < t.n; k += kRfWidth) part = part + rf_cost_term(rf_load(dev.sup, dev.stride, t.s0 + k), dm, dev.alpha);
-    return 0.5 * lm_group_sum<kRfWidth>(part);
-  }
-  __device__ __forceinline__ void linearise(const double p[6], double acc[kRfSums]) const {
-    Rf4 u[4], w[2], dm[6];
-    rf_seed(p, u, w);
-    rf_plucker<Rf4>(u, w, dm);
-    for (int c = 0; c < kRfSums; ++c) acc[c] = 0.0;
-    for (int k = lane; k < t.n; k += kRfWidth) rf_accumulate(rf_load(dev.sup, dev.stride, t.s0 + k), dm, dev.alpha, acc);
-    for (int c = 0; c < kRfSums; ++c) acc[c] = lm_group_sum<kRfWidth>(acc[c]);
-  }
-};
-
 // a group whose track ends leaves rf_lm's loop while the other groups of its wave go on; the wave retires with its
 // last track
 __global__ void __launch_bounds__(kRfBlock) k_refine_lm(RfDev dev, RfOut *__restrict__ out) {
@@ -80,7 +58,7 @@ __global__ void __launch_bounds__(kRfBlock) k_refine_lm(RfDev dev, RfOut *__rest
   double p[6], F0, F1;
   int it, code;
   for (int c = 0; c < 6; ++c) p[c] = out[ti].p[c];
-  DevGroup grp{dev, t, lane};
+  RfGroup<LmWaveLanes<kRfWidth>> grp{{lane}, dev.sup, dev.stride, t, dev.alpha};
   rf_lm(grp, t.constant != 0, dev.max_iter, p, &F0, &F1, &it, &code);
   if (lane == 0) {
     for (int c = 0; c < 6; ++c) out[ti].p[c] = p[c];
@@ -101,7 +79,9 @@ __global__ void __launch_bounds__(256) k_refine_prep_terms(const double *__restr
   rf_ext_prep(kvec + 4 * (long long)cam, qvec + 4 * (long long)cam, vp_flag[i] != 0, vp3 + 3 * i, ext + i, stride);
 }
 
-// DevGroup with the terms' blocks
+// the device group of k_refine_lm_terms; its host twin is RfGroupTerms over LmHostLanes.  It is written out here, as is
+// the supports' half of DevGroupFeat below: with RfGroupTerms over the wave's lanes in either of the two,
+// k_refine_lm_feat<true, unsigned short> gains scratch and spilled registers
 template <bool HM, class Tx>
 struct DevGroupTerms {
   const RfDev &dev;

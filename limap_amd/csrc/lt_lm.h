@@ -232,6 +232,57 @@ __device__ __forceinline__ double lm_group_sum(double v) {
 }
 #endif
 
+// ---- the lanes of a group: what a minimiser's group is written over, once for the wave and its host twin.
+//   sum<C>(n, part, out)          part(l, acc) adds lane l's terms to its acc[C], zeroed before; the first n sums are
+//                                 reduced by the xor tree into out (C doubles), which every lane then holds
+//   over<C>(n_items, n, item, out)  the same with item(i, acc) for the lane's items i = l, l + W, ... in ascending order;
+//                                 over<C, S>: the items go to the first S lanes (i = l, l + S, ...), the others add zeros
+//   lead(), sync()                the lane that writes what the group shares, and the barrier around such writes
+// Host: the lanes are a loop ----
+template <int W>
+struct LmHostLanes {
+  bool lead() const { return true; }
+  void sync() const {}
+  template <int C, class F>
+  void sum(int n, F part, double *out) const {
+    double acc[W][C];
+    for (int l = 0; l < W; ++l) {
+      for (int c = 0; c < C; ++c) acc[l][c] = 0.0;
+      part(l, acc[l]);
+    }
+    lm_tree_host(acc, n, out);
+  }
+  template <int C, int S = W, class I, class F>
+  void over(I n_items, int n, F item, double *out) const {
+    sum<C>(n, [&](int l, double *acc) {
+      if (S == W || l < S)
+        for (I i = l; i < n_items; i += S) item(i, acc);
+    }, out);
+  }
+};
+#ifdef __HIPCC__
+// device: a lane of the wave
+template <int W>
+struct LmWaveLanes {
+  int lane;
+  __device__ __forceinline__ bool lead() const { return lane == 0; }
+  __device__ __forceinline__ void sync() const { __syncthreads(); }
+  template <int C, class F>
+  __device__ __forceinline__ void sum(int n, F part, double *out) const {
+    for (int c = 0; c < C; ++c) out[c] = 0.0;
+    part(lane, out);
+    for (int c = 0; c < n; ++c) out[c] = lm_group_sum<W>(out[c]);
+  }
+  template <int C, int S = W, class I, class F>
+  __device__ __forceinline__ void over(I n_items, int n, F item, double *out) const {
+    sum<C>(n, [&](int l, double *acc) {
+      if (S == W || l < S)
+        for (I i = l; i < n_items; i += S) item(i, acc);
+    }, out);
+  }
+};
+#endif
+
 // ---- the chunked reduction of the coupled solves: two sums over any number of items in an order no
 // grid decides.  A wave64 owns a chunk of 256 items -- lane stride, then the xor tree -- and writes chunk[ch] and
 // chunk[stride + ch]; one wave then reduces the chunk results the same way.  item(i, &a, &b) adds item i's terms to the

@@ -30,35 +30,12 @@ struct Plan {
   LcCfg cfg;
 };
 
-int check_config(const lt_loc_config *c, LcCfg &cfg, std::string &msg) {
-  if (!c) { msg = "null configuration"; return 1; }
-  if (c->cost_function < kLcMidpoint2 || c->cost_function > kLcPlaneLine2) { msg = "unknown line cost function"; return 1; }
-  if (c->weight_function == kLcLine3dpp) { msg = "ELine3dppWeight is not built (it needs an arccosine)"; return 1; }
-  if (c->weight_function < kLcNone || c->weight_function > kLcInvLength) { msg = "unknown line weight function"; return 1; }
-  if (c->loss < kLcTrivial || c->loss > kLcCauchy) { msg = "unknown loss function"; return 1; }
-  if (c->loss != kLcTrivial && !(c->loss_a > 0.0 && std::isfinite(c->loss_a))) { msg = "the loss parameter must be > 0"; return 1; }
-  if (c->max_num_iterations < 0) { msg = "max_num_iterations is negative"; return 1; }
-  if (!std::isfinite(c->weight_line) || !std::isfinite(c->weight_point) || c->weight_line < 0.0 || c->weight_point < 0.0) {
-    msg = "weight_line and weight_point must be finite and >= 0";  // ScaledLoss with a negative scale is no loss
-    return 1;
-  }
-  cfg.cost = c->cost_function;
-  cfg.weight = c->weight_function;
-  cfg.loss = c->loss;
-  // hybrid_localization.h:36-40
-  cfg.points_3d_dist = (c->cost_function == kLcLineLine2 || c->cost_function == kLcPlaneLine2) ? 1 : 0;
-  cfg.loss_a = c->loss == kLcTrivial ? 1.0 : c->loss_a;
-  cfg.max_iter = c->max_num_iterations;
-  cfg.pad_ = 0;
-  return 0;
-}
-
 // the checks and the block table.  Blocks of a problem: its 3D lines in order, each with its 2D segments in order
 // (ScaledLoss weight weight_line * length / sum_lengths), then its points (weight_point)
 int make_plan(int64_t P, const double *kvec4, const double *qvec4, const double *tvec3, const int64_t *line_off,
               const double *line3d6, const int64_t *seg_off, const double *seg4, const int64_t *pt_off, const double *p3d3,
               const double *p2d2, const lt_loc_config *c, Plan &pl, std::string &msg) {
-  if (check_config(c, pl.cfg, msg)) return 1;
+  if (lc_check_config(c, pl.cfg, msg)) return 1;
   if (P < 0 || (P > 0 && (!kvec4 || !qvec4 || !tvec3))) { msg = "bad problem arrays"; return 1; }
   msg = offsets_msg("line", P, line_off);
   if (!msg.empty()) return 1;
@@ -154,35 +131,7 @@ int make_plan(int64_t P, const double *kvec4, const double *qvec4, const double 
 }
 
 // the host twin of the wave of k_loc_lm
-struct HostGroup {
-  const LcCfg &cfg;
-  const double *tab;
-  long long stride;
-  const LcProb &pr;
-  const double *k;
-  double cost(const double p[7]) const {
-    double part[kLcWidth][kLcSums];
-    for (int l = 0; l < kLcWidth; ++l) {
-      double s = 0.0;
-      for (int i = l; i < pr.n; i += kLcWidth) s = s + lc_cost_term(cfg, k, p, lc_load(tab, stride, pr.b0 + i));
-      part[l][0] = s;
-    }
-    double out[kLcSums];
-    lm_tree_host(part, 1, out);
-    return 0.5 * out[0];
-  }
-  // res: 4 slots per block (tests)
-  void linearise_res(const double p[7], double acc[kLcSums], double *res) const {
-    double part[kLcWidth][kLcSums];
-    for (int l = 0; l < kLcWidth; ++l) {
-      for (int c = 0; c < kLcSums; ++c) part[l][c] = 0.0;
-      for (int i = l; i < pr.n; i += kLcWidth)
-        lc_accumulate(cfg, k, p, lc_load(tab, stride, pr.b0 + i), part[l], res ? res + 4 * (size_t)i : nullptr);
-    }
-    lm_tree_host(part, kLcSums, acc);
-  }
-  void linearise(const double p[7], double acc[kLcSums]) const { linearise_res(p, acc, nullptr); }
-};
+typedef LcGroup<LmHostLanes<kLcWidth>> HostGroup;
 
 void run_host(const Plan &pl, int n_threads, std::vector<LcOut> &out) {
   const long long P = (long long)pl.probs.size();
@@ -191,9 +140,10 @@ void run_host(const Plan &pl, int n_threads, std::vector<LcOut> &out) {
 #pragma omp parallel for num_threads(nt) schedule(dynamic, 4)
   for (long long n = 0; n < P; ++n) {
     LcOut &o = out[(size_t)n];
-    HostGroup grp{pl.cfg, pl.tab.data(), pl.stride, pl.probs[(size_t)n], pl.kvec.data() + 4 * n};
+    const LcProb &pr = pl.probs[(size_t)n];
+    HostGroup grp{{}, pl.cfg, pl.tab.data(), pl.stride, pr.b0, pr.n, pl.kvec.data() + 4 * n};
     double p[7] = {o.q[0], o.q[1], o.q[2], o.q[3], o.t[0], o.t[1], o.t[2]};
-    lc_lm(grp, pl.probs[(size_t)n].n, pl.cfg.max_iter, p, &o.cost0, &o.cost1, &o.iters, &o.code);
+    lc_lm(grp, pr.n, pl.cfg.max_iter, p, &o.cost0, &o.cost1, &o.iters, &o.code);
     for (int c = 0; c < 4; ++c) o.q[c] = p[c];
     for (int c = 0; c < 3; ++c) o.t[c] = p[4 + c];
   }
@@ -257,30 +207,11 @@ int make_score_plan(const double *kvec4, int64_t n_l3d, const double *line3d6, i
   pl.tab.assign((size_t)kLcScoreFields * (size_t)pl.stride, 0.0);
   const long long st = pl.stride;
   double *tab = pl.tab.data();
-  for (long long i = 0; i < n_pts; ++i) {
-    for (int k = 0; k < 3; ++k) tab[(long long)k * st + i] = p3d3[3 * i + k];
-    tab[6 * st + i] = p2d2[2 * i];
-    tab[7 * st + i] = p2d2[2 * i + 1];
-  }
-  std::vector<double> dm(6 * (size_t)std::max<int64_t>(n_l3d, 1));
+  for (long long i = 0; i < n_pts; ++i) lc_score_fill_point(tab, st, i, p3d3 + 3 * i, p2d2 + 2 * i);
+  std::vector<double> dm(6 * (size_t)std::max<int64_t>(n_l3d, 1));  // the pose-independent part of a 3D line, once
   std::vector<char> have((size_t)std::max<int64_t>(n_l3d, 1), 0);
-  for (long long s2 = 0; s2 < n_seg; ++s2) {
-    const long long id = l3d_ids[s2], i = n_pts + s2;
-    if (id < 0 || id >= n_l3d) { msg = "l3d_id " + std::to_string(id) + " is outside the " + std::to_string(n_l3d) + " 3D lines"; return 1; }
-    const double *l3 = line3d6 + 6 * id;
-    if (!have[(size_t)id]) {  // the pose-independent part of a 3D line, once
-      const double dx = l3[3] - l3[0], dy = l3[4] - l3[1], dz = l3[5] - l3[2];
-      if (!(std::sqrt((dx * dx + dy * dy) + dz * dz) > 0.0)) {  // CHECK_GT(line.length(), 0.0) (infinite_line.cc:68)
-        msg = "3D line " + std::to_string(id) + " has zero length";
-        return 1;
-      }
-      lc_item_prep(l3, dm.data() + 6 * id, dm.data() + 6 * id + 3);
-      have[(size_t)id] = 1;
-    }
-    for (int k = 0; k < 6; ++k) tab[(long long)k * st + i] = l3[k];
-    for (int k = 0; k < 4; ++k) tab[(long long)(6 + k) * st + i] = seg4[4 * s2 + k];
-    for (int k = 0; k < 6; ++k) tab[(long long)(10 + k) * st + i] = dm[6 * (size_t)id + k];
-  }
+  for (long long s2 = 0; s2 < n_seg; ++s2)
+    if (lc_score_fill_line(tab, st, n_pts + s2, n_l3d, line3d6, l3d_ids[s2], seg4 + 4 * s2, dm.data(), have.data(), msg)) return 1;
   pl.q.assign(qvec4, qvec4 + 4 * (size_t)n_poses);
   pl.t.assign(tvec3, tvec3 + 3 * (size_t)n_poses);
   LcScoreDev &d = pl.dev;
@@ -290,13 +221,7 @@ int make_score_plan(const double *kvec4, int64_t n_l3d, const double *line3d6, i
   d.tvec = pl.t.data();
   d.n_poses = n_poses;
   for (int k = 0; k < 4; ++k) d.k[k] = kvec4[k];
-  d.sc.cfg.cost = c->cost_function;
-  d.sc.cfg.weight = kLcNone;
-  d.sc.cfg.loss = kLcTrivial;
-  d.sc.cfg.points_3d_dist = (c->cost_function == kLcLineLine2 || c->cost_function == kLcPlaneLine2) ? 1 : 0;
-  d.sc.cfg.loss_a = 1.0;
-  d.sc.cfg.max_iter = 0;
-  d.sc.cfg.pad_ = 0;
+  d.sc.cfg = lc_cfg_of(c->cost_function, kLcNone, kLcTrivial, 1.0, 0);
   d.sc.min_depth = c->cheirality_min_depth;
   d.sc.overlap = c->cheirality_overlap_pixels;
   for (int i = 0; i < 2; ++i) { d.sc.thr2[i] = c->squared_thresholds[i]; d.sc.w[i] = c->weights[i]; }
@@ -311,29 +236,17 @@ int make_score_plan(const double *kvec4, int64_t n_l3d, const double *line3d6, i
 void score_host(const ScorePlan &pl, int n_threads, double *table, double *scores, int32_t *inliers) {
   const LcScoreDev &d = pl.dev;
   const int nt = n_threads > 0 ? n_threads : omp_get_max_threads();
-  const long long N = pl.N, np = d.sc.n_points;
+  const long long N = pl.N;
 #pragma omp parallel for num_threads(nt) schedule(dynamic, 8)
   for (long long h = 0; h < pl.H; ++h) {
-    LcPose ps;
-    lc_pose_build(d.k, d.qvec + 4 * h, d.tvec + 3 * h, &ps);
-    double part[kLcWidth][kLcSums];
     int in[2] = {0, 0};
-    for (int l = 0; l < kLcWidth; ++l) part[l][0] = 0.0;
-    for (long long i = 0; i < N; ++i) {
-      const bool is_point = i < np;
-      const double r2 = lc_score_cell(d.sc, d.k, ps, lc_load_item(d.tab, d.stride, i, is_point));
+    const double sum = lc_msac_sum(LmHostLanes<kLcWidth>{}, d.sc, d.k, d.qvec + 4 * h, d.tvec + 3 * h, d.tab, d.stride, 0,
+                                   d.sc.n_points, d.sc.n_lines, [&](int i, bool is_point, double r2) {
       if (table) table[h * N + i] = r2;
-      if (d.sc.want_msac) {
-        const int type = is_point ? 0 : 1;
-        double &p = part[i % kLcWidth][0];  // lane i % 64 meets its correspondences in ascending order
-        p = p + lc_msac_term(d.sc, type, r2);
-        if (r2 < d.sc.thr2[type]) in[type] += 1;
-      }
-    }
+      if (d.sc.want_msac && r2 < d.sc.thr2[is_point ? 0 : 1]) in[is_point ? 0 : 1] += 1;
+    });
     if (d.sc.want_msac) {
-      double out[kLcSums];
-      lm_tree_host(part, 1, out);
-      if (scores) scores[h] = out[0];
+      if (scores) scores[h] = sum;
       if (inliers) { inliers[2 * h] = in[0]; inliers[2 * h + 1] = in[1]; }
     }
   }
@@ -455,7 +368,7 @@ static int loc_eval(const char *who, bool as_given, const double kvec4[4], const
   double p[7] = {o.q[0], o.q[1], o.q[2], o.q[3], o.t[0], o.t[1], o.t[2]};
   if (as_given)
     for (int i = 0; i < 4; ++i) p[i] = qvec4[i];
-  HostGroup grp{pl.cfg, pl.tab.data(), pl.stride, pr, pl.kvec.data()};
+  HostGroup grp{{}, pl.cfg, pl.tab.data(), pl.stride, pr.b0, pr.n, pl.kvec.data()};
   if (residuals) std::fill(residuals, residuals + 4 * (size_t)pr.n, std::nan(""));
   if (cost) *cost = grp.cost(p);
   double acc[kLcSums];

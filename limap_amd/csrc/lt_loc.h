@@ -392,6 +392,30 @@ LT_HD void lc_lm(G &grp, int n_blocks, int max_iter, double p[7], double *cost0,
   else lm_loop<LcChart>(grp, F, max_iter, p, cost1, iters, code_out);
 }
 
+// the group of a pose: blocks [b0, b0 + n) of a kLcFields table over the lanes (LmWaveLanes in the kernels, LmHostLanes
+// in their host twins)
+template <class Lanes>
+struct LcGroup {
+  Lanes lanes;
+  const LcCfg &cfg;
+  const double *tab;
+  long long stride, b0;
+  int n;
+  const double *k;
+  LT_HD double cost(const double p[7]) const {
+    double s;
+    lanes.template over<1>(n, 1, [&](int i, double *a) { a[0] = a[0] + lc_cost_term(cfg, k, p, lc_load(tab, stride, b0 + i)); }, &s);
+    return 0.5 * s;
+  }
+  // res: 4 slots per block (tests)
+  LT_HD void linearise_res(const double p[7], double acc[kLcSums], double *res) const {
+    lanes.template over<kLcSums>(n, kLcSums, [&](int i, double *a) {
+      lc_accumulate(cfg, k, p, lc_load(tab, stride, b0 + i), a, res ? res + 4 * (size_t)i : nullptr);
+    }, acc);
+  }
+  LT_HD void linearise(const double p[7], double acc[kLcSums]) const { linearise_res(p, acc, nullptr); }
+};
+
 // ---- pose scoring: JointPoseEstimator::EvaluateModelOnPoint (estimators/absolute_pose/joint_pose_estimator.cc:176-251)
 // for H poses x N correspondences, points first.  CameraView's members are lt_geom.h's (cam_build, cam_depth,
 // cam_project, cam_ray); base/infinite_line.cc:55-71,151-163 and base/linebase.cc:20-27,93-98 are restated here ----
@@ -495,6 +519,23 @@ LT_HD double lc_score_cell(const LcScoreCfg &sc, const double k[4], const LcPose
 LT_HD double lc_msac_term(const LcScoreCfg &sc, int type, double r2) {
   return (r2 < sc.thr2[type] ? r2 : sc.thr2[type]) * sc.w[type];  // std::min(r2, thr2)
 }
+// ScoreModel of the pose (q4, t3) against correspondences [c0, c0 + n_pts + n_lines) of a kLcScoreFields table, the
+// points first: the MSAC sum over the lanes, which every lane returns (0.0 where the call does not want it).
+// each(i, is_point, r2) sees correspondence c0 + i's squared error first: the callers' stores and inlier counts
+template <class Lanes, class Each>
+LT_HD double lc_msac_sum(const Lanes &lanes, const LcScoreCfg &sc, const double k[4], const double q4[4], const double t3[3],
+                         const double *tab, long long stride, long long c0, int n_pts, int n_lines, Each each) {
+  LcPose ps;
+  lc_pose_build(k, q4, t3, &ps);
+  double sum;
+  lanes.template over<1>(n_pts + n_lines, 1, [&](int i, double *a) {
+    const bool is_point = i < n_pts;
+    const double r2 = lc_score_cell(sc, k, ps, lc_load_item(tab, stride, c0 + i, is_point));
+    each(i, is_point, r2);
+    if (sc.want_msac) a[0] = a[0] + lc_msac_term(sc, is_point ? 0 : 1, r2);
+  }, &sum);
+  return sum;
+}
 
 struct LcScoreDev {
   const double *tab;  // kLcScoreFields x stride
@@ -520,4 +561,67 @@ struct LcDev {
 // out[i].q, out[i].t hold the initial poses (q normalised on the host) and receive the results
 void launch_loc_lm(hipStream_t st, const LcDev &dev, LcOut *out);
 
+// hybrid_localization.h:36-40: points_3d_dist follows the 3D cost functions; a trivial loss has no parameter
+LT_HD LcCfg lc_cfg_of(int cost, int weight, int loss, double loss_a, int max_iter) {
+  return LcCfg{cost, weight, loss, (cost == kLcLineLine2 || cost == kLcPlaneLine2) ? 1 : 0, loss == kLcTrivial ? 1.0 : loss_a, max_iter, 0};
+}
+
 }  // namespace lt
+
+#ifndef __HIPCC__
+// ---- the host's checks and table rows, shared by lt_loc.cpp and lt_est.cpp ----
+#include "../../include/limap_amd.h"
+
+#include <cmath>
+#include <string>
+
+namespace lt {
+
+// a refinement configuration; 1 with msg: an argument error
+inline int lc_check_config(const lt_loc_config *c, LcCfg &cfg, std::string &msg) {
+  if (!c) { msg = "null configuration"; return 1; }
+  if (c->cost_function < kLcMidpoint2 || c->cost_function > kLcPlaneLine2) { msg = "unknown line cost function"; return 1; }
+  if (c->weight_function == kLcLine3dpp) { msg = "ELine3dppWeight is not built (it needs an arccosine)"; return 1; }
+  if (c->weight_function < kLcNone || c->weight_function > kLcInvLength) { msg = "unknown line weight function"; return 1; }
+  if (c->loss < kLcTrivial || c->loss > kLcCauchy) { msg = "unknown loss function"; return 1; }
+  if (c->loss != kLcTrivial && !(c->loss_a > 0.0 && std::isfinite(c->loss_a))) { msg = "the loss parameter must be > 0"; return 1; }
+  if (c->max_num_iterations < 0) { msg = "max_num_iterations is negative"; return 1; }
+  if (!std::isfinite(c->weight_line) || !std::isfinite(c->weight_point) || c->weight_line < 0.0 || c->weight_point < 0.0) {
+    msg = "weight_line and weight_point must be finite and >= 0";  // ScaledLoss with a negative scale is no loss
+    return 1;
+  }
+  cfg = lc_cfg_of(c->cost_function, c->weight_function, c->loss, c->loss_a, c->max_num_iterations);
+  return 0;
+}
+
+// row i of a kLcScoreFields table (zeroed by the caller) for a point correspondence
+inline void lc_score_fill_point(double *tab, long long st, long long i, const double p3d[3], const double p2d[2]) {
+  for (int k = 0; k < 3; ++k) tab[(long long)k * st + i] = p3d[k];
+  tab[6 * st + i] = p2d[0];
+  tab[7 * st + i] = p2d[1];
+}
+// ... and for the 2D segment seg of 3D line id of the n_l3d lines at line3d6.  dm, have: the pose-independent part of
+// every 3D line (6 doubles) and whether it is there yet, where the caller keeps it; null: prepared per segment
+inline int lc_score_fill_line(double *tab, long long st, long long i, long long n_l3d, const double *line3d6, long long id,
+                              const double seg[4], double *dm, char *have, std::string &msg) {
+  if (id < 0 || id >= n_l3d) { msg = "l3d_id " + std::to_string(id) + " is outside the " + std::to_string(n_l3d) + " 3D lines"; return 1; }
+  const double *l3 = line3d6 + 6 * id;
+  double own[6];
+  double *pre = dm ? dm + 6 * id : own;
+  if (!have || !have[id]) {
+    const double dx = l3[3] - l3[0], dy = l3[4] - l3[1], dz = l3[5] - l3[2];
+    if (!(std::sqrt((dx * dx + dy * dy) + dz * dz) > 0.0)) {  // CHECK_GT(line.length(), 0.0) (infinite_line.cc:68)
+      msg = "3D line " + std::to_string(id) + " has zero length";
+      return 1;
+    }
+    lc_item_prep(l3, pre, pre + 3);
+    if (have) have[id] = 1;
+  }
+  for (int k = 0; k < 6; ++k) tab[(long long)k * st + i] = l3[k];
+  for (int k = 0; k < 4; ++k) tab[(long long)(6 + k) * st + i] = seg[k];
+  for (int k = 0; k < 6; ++k) tab[(long long)(10 + k) * st + i] = pre[k];
+  return 0;
+}
+
+}  // namespace lt
+#endif

@@ -367,129 +367,50 @@ int make_plan(const std::unordered_map<int, int> &id2idx, int64_t T, const doubl
   return 0;
 }
 
-// ---- the host twin of a group of kRfWidth lanes ----
-struct HostGroup {
-  const double *tab;
-  long long stride;
-  const RfTrack &t;
-  double alpha;
-  double cost(const double p[6]) const {
-    double dm[6];
-    rf_plucker<double>(p, p + 4, dm);
-    double part[kRfWidth][kRfSums];
-    for (int l = 0; l < kRfWidth; ++l) {
-      double s = 0.0;
-      for (int k = l; k < t.n; k += kRfWidth) s = s + rf_cost_term(rf_load(tab, stride, t.s0 + k), dm, alpha);
-      part[l][0] = s;
-    }
-    double out[kRfSums];
-    lm_tree_host(part, 1, out);
-    return 0.5 * out[0];
-  }
-  void linearise(const double p[6], double acc[kRfSums]) const {
-    Rf4 u[4], w[2], dm[6];
-    rf_seed(p, u, w);
-    rf_plucker<Rf4>(u, w, dm);
-    double part[kRfWidth][kRfSums];
-    for (int l = 0; l < kRfWidth; ++l) {
-      for (int c = 0; c < kRfSums; ++c) part[l][c] = 0.0;
-      for (int k = l; k < t.n; k += kRfWidth) rf_accumulate(rf_load(tab, stride, t.s0 + k), dm, alpha, part[l]);
-    }
-    lm_tree_host(part, kRfSums, acc);
-  }
-};
+// ---- the host twins of the groups of k_refine_lm and k_refine_lm_terms (W lanes): the lanes are a loop ----
+typedef RfGroup<LmHostLanes<kRfWidth>> HostGroup;
 
-// the host twin of a group of k_refine_lm_terms
-template <bool HM, class Tx>
-struct HostGroupTerms {
-  const double *tab, *ext;
-  long long stride;
-  const RfTrack &t;
-  double alpha;
+// where a support's heatmap comes from on the host: the caller's images
+struct HostGrids {
   const TermsPlan &tp;
   const HmSet *hs;
+  template <class Tx>
   RfGrid<Tx> grid(long long s) const {
-    if (!HM) return RfGrid<Tx>{nullptr, 1, 1};
     const size_t sl = (size_t)tp.sup_hm[(size_t)s];
     return RfGrid<Tx>{static_cast<const Tx *>(hs->data[sl]), hs->h[sl], hs->w[sl]};
   }
-  double cost(const double p[6]) const {
-    double dm[6];
-    rf_plucker<double>(p, p + 4, dm);
-    double part[kRfTermWidth][kRfSums];
-    for (int l = 0; l < kRfTermWidth; ++l) {
-      double s = 0.0;
-      for (int k = l; k < t.n; k += kRfTermWidth)
-        s = s + rf_cost_terms<HM, Tx>(rf_load(tab, stride, t.s0 + k), rf_load_ext(ext, stride, t.s0 + k), grid(t.s0 + k),
-                                      tp.cfg, dm, alpha);
-      part[l][0] = s;
-    }
-    double out[kRfSums];
-    lm_tree_host(part, 1, out);
-    return 0.5 * out[0];
-  }
-  // res: the residuals of every support, 3 + n_samples each (tests)
-  bool linearise_res(const double p[6], double acc[kRfSums], double *res) const {
-    Rf4 u[4], w[2], dm[6];
-    rf_seed(p, u, w);
-    rf_plucker<Rf4>(u, w, dm);
-    double part[kRfTermWidth][kRfSums];
-    bool ok = true;
-    for (int l = 0; l < kRfTermWidth; ++l) {
-      for (int c = 0; c < kRfSums; ++c) part[l][c] = 0.0;
-      for (int k = l; k < t.n; k += kRfTermWidth)
-        ok = rf_accumulate_terms<HM, Tx>(rf_load(tab, stride, t.s0 + k), rf_load_ext(ext, stride, t.s0 + k), grid(t.s0 + k),
-                                         tp.cfg, dm, alpha, part[l],
-                                         res ? res + (size_t)k * (3 + (size_t)tp.cfg.n_samples) : nullptr) && ok;
-    }
-    lm_tree_host(part, kRfSums, acc);
-    return ok;
-  }
-  void linearise(const double p[6], double acc[kRfSums]) const { linearise_res(p, acc, nullptr); }
 };
+template <int W, bool HM, class Tx>
+using HostGroupTerms = RfGroupTerms<LmHostLanes<W>, HM, Tx, HostGrids>;
 
 // f(HostGroupTerms) for the instantiation the terms select, like launch_refine_lm_terms
 template <class F>
 void with_host_group(const double *tab, const double *ext, long long stride, const RfTrack &t, double alpha,
                      const TermsPlan &tp, const HmSet *hs, F &&f) {
+  const HostGrids gr{tp, hs};
   if (!tp.cfg.use_heatmap) {
-    HostGroupTerms<false, float> g{tab, ext, stride, t, alpha, tp, hs};
+    HostGroupTerms<kRfTermWidth, false, float> g{{}, tab, ext, stride, t, alpha, tp.cfg, gr};
     f(g);
   } else if (hs->type == LT_TEXEL_F32) {
-    HostGroupTerms<true, float> g{tab, ext, stride, t, alpha, tp, hs};
+    HostGroupTerms<kRfTermWidth, true, float> g{{}, tab, ext, stride, t, alpha, tp.cfg, gr};
     f(g);
   } else {
-    HostGroupTerms<true, unsigned short> g{tab, ext, stride, t, alpha, tp, hs};
+    HostGroupTerms<kRfTermWidth, true, unsigned short> g{{}, tab, ext, stride, t, alpha, tp.cfg, gr};
     f(g);
   }
 }
 
-// the host twin of a wave of k_refine_lm_feat: the lanes are a loop, the tree is lm_tree_host
+// the host twin of a wave of k_refine_lm_feat: the supports' half is RfGroupTerms over the wave's lanes; in the feature
+// blocks' half the lanes are a loop, the tree is lm_tree_host
 template <bool HM, class Tx>
 struct HostGroupFeat {
-  HostGroupTerms<HM, Tx> sup;  // the supports' blocks: lanes 0 .. kRfTermWidth - 1
+  HostGroupTerms<kRfFeatLanes, HM, Tx> sup;  // the supports' blocks: lanes 0 .. kRfTermWidth - 1 of the wave
   const FeatPlan &fp;
   const RfFTrack &f;
   const RfFImg *imgs() const { return fp.imgs.data() + f.img0; }
   const double *pair(int ref, int tg) const { return fp.pairs.data() + 9 * ((size_t)f.pair0 + (size_t)ref * (size_t)f.n_img + (size_t)tg); }
-  double support_cost(const double p[6]) const {
-    double dm[6];
-    rf_plucker<double>(p, p + 4, dm);
-    double part[kRfFeatLanes][1];
-    for (int l = 0; l < kRfFeatLanes; ++l) {
-      double s = 0.0;
-      if (l < kRfTermWidth)
-        for (int k = l; k < sup.t.n; k += kRfTermWidth)
-          s = s + rf_cost_terms<HM, Tx>(rf_load(sup.tab, sup.stride, sup.t.s0 + k), rf_load_ext(sup.ext, sup.stride, sup.t.s0 + k),
-                                        sup.grid(sup.t.s0 + k), sup.tp.cfg, dm, sup.alpha);
-      part[l][0] = s;
-    }
-    double out;
-    lm_tree_host(part, 1, &out);
-    return out;
-  }
   double cost(const double p[6]) const {
-    double total = support_cost(p);
+    double total = sup.cost_sum(p);
     if (f.n_smp == 0) return 0.5 * total;
     double d[3], m[3];
     rf_plucker_c<double>(p, p + 4, d, m);
@@ -520,17 +441,7 @@ struct HostGroupFeat {
     Rf4 u[4], w[2], dm[6];
     rf_seed(p, u, w);
     rf_plucker<Rf4>(u, w, dm);
-    {
-      double part[kRfFeatLanes][kRfSums];
-      for (int l = 0; l < kRfFeatLanes; ++l) {
-        for (int c = 0; c < kRfSums; ++c) part[l][c] = 0.0;
-        if (l < kRfTermWidth)
-          for (int k = l; k < sup.t.n; k += kRfTermWidth)
-            rf_accumulate_terms<HM, Tx>(rf_load(sup.tab, sup.stride, sup.t.s0 + k), rf_load_ext(sup.ext, sup.stride, sup.t.s0 + k),
-                                        sup.grid(sup.t.s0 + k), sup.tp.cfg, dm, sup.alpha, part[l]);
-      }
-      lm_tree_host(part, kRfSums, acc);
-    }
+    sup.lin_sums(dm, acc, nullptr);
     if (f.n_smp == 0) return true;
     Rf4 d[3], m[3];
     rf_plucker_c<Rf4>(u, w, d, m);
@@ -575,12 +486,13 @@ template <class F>
 void with_host_group_feat(const double *tab, const double *ext, long long stride, const RfTrack &t, double alpha,
                           const TermsPlan &tp, const HmSet *hs, const FeatPlan &fp, const RfFTrack &ft, F &&f) {
   const bool f32 = fp.type == LT_TEXEL_F32;
+  const HostGrids gr{tp, hs};
   if (!tp.cfg.use_heatmap) {
-    if (f32) { HostGroupFeat<false, float> g{{tab, ext, stride, t, alpha, tp, hs}, fp, ft}; f(g); }
-    else { HostGroupFeat<false, unsigned short> g{{tab, ext, stride, t, alpha, tp, hs}, fp, ft}; f(g); }
+    if (f32) { HostGroupFeat<false, float> g{{{}, tab, ext, stride, t, alpha, tp.cfg, gr}, fp, ft}; f(g); }
+    else { HostGroupFeat<false, unsigned short> g{{{}, tab, ext, stride, t, alpha, tp.cfg, gr}, fp, ft}; f(g); }
   } else {
-    if (f32) { HostGroupFeat<true, float> g{{tab, ext, stride, t, alpha, tp, hs}, fp, ft}; f(g); }
-    else { HostGroupFeat<true, unsigned short> g{{tab, ext, stride, t, alpha, tp, hs}, fp, ft}; f(g); }
+    if (f32) { HostGroupFeat<true, float> g{{{}, tab, ext, stride, t, alpha, tp.cfg, gr}, fp, ft}; f(g); }
+    else { HostGroupFeat<true, unsigned short> g{{{}, tab, ext, stride, t, alpha, tp.cfg, gr}, fp, ft}; f(g); }
   }
 }
 
@@ -641,7 +553,7 @@ void run_host(const Plan &pl, const double *k, const double *q, const double *t,
         rf_lm_terms(grp, tr.constant != 0, cfg.max_num_iterations, o.p, &o.cost0, &o.cost1, &o.iters, &o.code);
       });
     } else {
-      HostGroup grp{tab.data(), stride, tr, cfg.geometric_alpha};
+      HostGroup grp{{}, tab.data(), stride, tr, cfg.geometric_alpha};
       rf_lm(grp, tr.constant != 0, cfg.max_num_iterations, o.p, &o.cost0, &o.cost1, &o.iters, &o.code);
     }
     cut_host(tr, pl.l3d.data(), cfg.num_outliers_aggregator, o);
@@ -1255,7 +1167,7 @@ int lt_fn_refine_eval(int64_t K, const double *cam11, const double *line2d4, con
     tab[22 * K + i] = std::sqrt(dx * dx + dy * dy) / 30.0;
   }
   const RfTrack tr{0, (int)K, 0};
-  HostGroup grp{tab.data(), (long long)K, tr, alpha};
+  HostGroup grp{{}, tab.data(), (long long)K, tr, alpha};
   if (cost) *cost = grp.cost(params6);
   double acc[kRfSums];
   grp.linearise(params6, acc);

@@ -692,6 +692,73 @@ struct RfDevTerms {
   RfTermCfg cfg;
 };
 
+// ---- the groups of rf_lm and rf_lm_terms over the lanes (LmWaveLanes in the kernels, LmHostLanes in the host twins) ----
+// the supports of a track, lane l taking supports l, l + kRfWidth, ...
+template <class Lanes>
+struct RfGroup {
+  Lanes lanes;
+  const double *sup;  // kRfFields x stride
+  long long stride;
+  const RfTrack &t;
+  double alpha;
+  LT_HD double cost(const double p[6]) const {
+    double dm[6], s;
+    rf_plucker<double>(p, p + 4, dm);
+    lanes.template over<1>(t.n, 1, [&](int k, double *a) { a[0] = a[0] + rf_cost_term(rf_load(sup, stride, t.s0 + k), dm, alpha); }, &s);
+    return 0.5 * s;
+  }
+  LT_HD void linearise(const double p[6], double acc[kRfSums]) const {
+    Rf4 u[4], w[2], dm[6];
+    rf_seed(p, u, w);
+    rf_plucker<Rf4>(u, w, dm);
+    lanes.template over<kRfSums>(t.n, kRfSums, [&](int k, double *a) { rf_accumulate(rf_load(sup, stride, t.s0 + k), dm, alpha, a); }, acc);
+  }
+};
+
+// RfGroup with the terms' blocks.  The supports go to the first kRfTermWidth lanes, however many the group has: the
+// lanes past them add zeros to the tree, so the wave of k_refine_lm_feat gets k_refine_lm_terms' bits for them.
+// Grids: where a support's heatmap comes from, grid<Tx>(s).  The host twins of k_refine_lm_terms and k_refine_lm_feat
+// are this group; the two kernels keep device groups of their own
+template <class Lanes, bool HM, class Tx, class Grids>
+struct RfGroupTerms {
+  Lanes lanes;
+  const double *sup, *ext;  // kRfFields, kRfExtFields x stride
+  long long stride;
+  const RfTrack &t;
+  double alpha;
+  const RfTermCfg &cfg;
+  const Grids &grids;
+  LT_HD RfGrid<Tx> grid(long long s) const { return HM ? grids.template grid<Tx>(s) : RfGrid<Tx>{nullptr, 1, 1}; }
+  // the sum of the supports' costs, and of their blocks at dm (res: the residuals of every support, 3 + n_samples
+  // each; false where a heatmap sample of the lane's supports fails: tests, on the host)
+  LT_HD double cost_sum(const double p[6]) const {
+    double dm[6], total;
+    rf_plucker<double>(p, p + 4, dm);
+    lanes.template over<1, kRfTermWidth>(t.n, 1, [&](int k, double *a) {
+      const long long s = t.s0 + k;
+      a[0] = a[0] + rf_cost_terms<HM, Tx>(rf_load(sup, stride, s), rf_load_ext(ext, stride, s), grid(s), cfg, dm, alpha);
+    }, &total);
+    return total;
+  }
+  LT_HD bool lin_sums(const Rf4 dm[6], double acc[kRfSums], double *res) const {
+    bool ok = true;
+    lanes.template over<kRfSums, kRfTermWidth>(t.n, kRfSums, [&](int k, double *a) {
+      const long long s = t.s0 + k;
+      ok = rf_accumulate_terms<HM, Tx>(rf_load(sup, stride, s), rf_load_ext(ext, stride, s), grid(s), cfg, dm, alpha, a,
+                                       res ? res + (size_t)k * (3 + (size_t)cfg.n_samples) : nullptr) && ok;
+    }, acc);
+    return ok;
+  }
+  LT_HD double cost(const double p[6]) const { return 0.5 * cost_sum(p); }
+  LT_HD bool linearise_res(const double p[6], double acc[kRfSums], double *res) const {
+    Rf4 u[4], w[2], dm[6];
+    rf_seed(p, u, w);
+    rf_plucker<Rf4>(u, w, dm);
+    return lin_sums(dm, acc, res);
+  }
+  LT_HD void linearise(const double p[6], double acc[kRfSums]) const { linearise_res(p, acc, nullptr); }
+};
+
 // ---- the feature-consistency term (limap.optimize.line_refinement with use_feature) ----
 // Restated in upstream's operation order down to the association of every sum (DESIGN §26 writes the order out; the
 // tests hold the residuals to a NumPy restatement bit for bit): paths relative to src/limap,
