@@ -7,6 +7,7 @@
 #include "lt_host.h"
 #include "lt_assoc.h"
 #include "lt_ingest.h"
+#include "lt_twin.h"
 
 #include <algorithm>
 #include <cmath>
@@ -419,9 +420,9 @@ void copy_out(const Outputs &o, double *pt3, double *params6, double *vp3, doubl
   if (code) *code = o.code;
 }
 
-static thread_local std::string g_host_error;
+static thread_local HostError g_host_error;
 
-#ifndef LT_ASSOC_HOST_ONLY  // (tools/assoc_host_asan.cpp compiles the host twin alone: no context, no HIP runtime)
+#ifndef LT_HOST_ONLY  // (tools/assoc_host_asan.cpp compiles the host twin alone: no context, no HIP runtime)
 int run_device(lt_ctx *ctx, const Plan &pl, Result &res, double timers[20]) {
   lt_host::AsState &as = ctx->as;
   const double t0 = now_ms();
@@ -500,7 +501,7 @@ int run_device(lt_ctx *ctx, const Plan &pl, Result &res, double timers[20]) {
   timers[2] = now_ms() - t2;
   return LT_OK;
 }
-#endif  // LT_ASSOC_HOST_ONLY
+#endif  // LT_HOST_ONLY
 
 }  // namespace
 
@@ -525,7 +526,7 @@ void lt_assoc_config_default(lt_assoc_config *cfg) {
   cfg->enable_vpline = 1;
 }
 
-#ifndef LT_ASSOC_HOST_ONLY
+#ifndef LT_HOST_ONLY
 int lt_assoc_arrays(lt_ctx *ctx, const lt_assoc_input *in, const lt_assoc_config *cfg) {
   if (!ctx) return LT_ERR_ARGUMENT;
   std::string msg;
@@ -558,7 +559,7 @@ int lt_assoc_get_timers(lt_ctx *ctx, double out[20]) {
   for (int k = 0; k < 20; ++k) out[k] = ctx->as.timers[k];
   return LT_OK;
 }
-#endif  // LT_ASSOC_HOST_ONLY
+#endif  // LT_HOST_ONLY
 
 const char *lt_fn_assoc_host_error(void) { return g_host_error.c_str(); }
 
@@ -567,11 +568,7 @@ int lt_fn_assoc_host(const lt_assoc_input *in, const lt_assoc_config *cfg, int h
                      int64_t *n_attempts, double *total0, double *rec6) {
   std::string msg;
   Plan pl;
-  if (make_plan(in, cfg, pl, msg)) {
-    g_host_error = "lt_fn_assoc_host: " + msg;
-    return LT_ERR_ARGUMENT;
-  }
-  g_host_error.clear();
+  if (int rc = g_host_error.check("lt_fn_assoc_host", make_plan(in, cfg, pl, msg), msg)) return rc;
   Result res;
   if (n_attempts) *n_attempts = 0;
   if (total0) *total0 = 0.0;
@@ -588,11 +585,7 @@ int lt_fn_assoc_eval(const lt_assoc_input *in, const lt_assoc_config *cfg, const
                      double *res_blk, double *res_edge, double *cost, double *g4, double *diag16, double *off16) {
   std::string msg;
   Plan pl;
-  if (make_plan(in, cfg, pl, msg)) {
-    g_host_error = "lt_fn_assoc_eval: " + msg;
-    return LT_ERR_ARGUMENT;
-  }
-  g_host_error.clear();
+  if (int rc = g_host_error.check("lt_fn_assoc_eval", make_plan(in, cfg, pl, msg), msg)) return rc;
   if (dims8) {
     const int64_t v[8] = {pl.NU, pl.NP, pl.NL, pl.NV, pl.NB, pl.NE, 0, 0};
     std::copy(v, v + 8, dims8);
@@ -600,7 +593,7 @@ int lt_fn_assoc_eval(const lt_assoc_input *in, const lt_assoc_config *cfg, const
   if (!unk_nd && !blk_unk && !edge_info3 && !edge_w && !sp6_out && !res_blk && !res_edge && !cost && !g4 && !diag16 && !off16)
     return LT_OK;
   if (sp6) {
-    if (!all_finite(sp6, 6 * (long long)pl.NU)) { g_host_error = "lt_fn_assoc_eval: non-finite point"; return LT_ERR_ARGUMENT; }
+    if (!all_finite(sp6, 6 * (long long)pl.NU)) return g_host_error.refuse("lt_fn_assoc_eval", "non-finite point");
     std::copy(sp6, sp6 + 6 * (size_t)pl.NU, pl.sp0.begin());
   }
   HostTables h;

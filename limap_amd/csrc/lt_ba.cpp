@@ -7,6 +7,7 @@
 #include "lt_host.h"
 #include "lt_ba.h"
 #include "lt_ingest.h"
+#include "lt_twin.h"
 
 #include <algorithm>
 #include <climits>
@@ -495,9 +496,9 @@ void copy_out(const Outputs &o, double *qvec4, double *tvec3, double *pt3, doubl
   if (code) *code = o.code;
 }
 
-static thread_local std::string g_host_error;
+static thread_local HostError g_host_error;
 
-#ifndef LT_BA_HOST_ONLY  // (tools/ba_host_asan.cpp compiles the host twin alone: no context, no HIP runtime)
+#ifndef LT_HOST_ONLY  // (tools/ba_host_asan.cpp compiles the host twin alone: no context, no HIP runtime)
 int run_device(lt_ctx *ctx, const Plan &pl, Result &res, double timers[16]) {
   lt_host::BaState &ba = ctx->ba;
   const double t0 = now_ms();
@@ -586,9 +587,7 @@ int run_device(lt_ctx *ctx, const Plan &pl, Result &res, double timers[16]) {
   timers[2] = now_ms() - t2;
   return LT_OK;
 }
-#endif  // LT_BA_HOST_ONLY
 
-#ifndef LT_BA_HOST_ONLY
 int run_points_device(lt_ctx *ctx, const Plan &pl, std::vector<BaPtOut> &out, double timers[16]) {
   lt_host::BaState &ba = ctx->ba;
   const double t0 = now_ms();
@@ -615,7 +614,7 @@ int run_points_device(lt_ctx *ctx, const Plan &pl, std::vector<BaPtOut> &out, do
   timers[2] = now_ms() - t2;
   return LT_OK;
 }
-#endif  // LT_BA_HOST_ONLY
+#endif  // LT_HOST_ONLY
 
 Input make_input(int n_img, const int32_t *img_ids, const double *kvec4, const double *qvec4, const double *tvec3,
                  int64_t n_pt, const double *pt3, const int64_t *pt_off, const int32_t *pt_img, const double *pt_xy2,
@@ -647,7 +646,7 @@ void lt_ba_config_default(lt_ba_config *cfg) {
 int lt_ba_max_images(void) { return kBaMaxImages; }
 int lt_ba_poll_default(void) { return kBaPollDefault; }
 
-#ifndef LT_BA_HOST_ONLY
+#ifndef LT_HOST_ONLY
 int lt_ba_arrays(lt_ctx *ctx, int n_img, const int32_t *img_ids, const double *kvec4, const double *qvec4,
                  const double *tvec3, int64_t n_pt, const double *pt3, const int64_t *pt_off, const int32_t *pt_img,
                  const double *pt_xy2, int64_t n_ln, const double *line6, const int64_t *ln_off, const int32_t *ln_img,
@@ -692,7 +691,7 @@ int lt_ba_get_timers(lt_ctx *ctx, double out[16]) {
   for (int k = 0; k < 16; ++k) out[k] = ctx->ba.timers[k];
   return LT_OK;
 }
-#endif  // LT_BA_HOST_ONLY
+#endif  // LT_HOST_ONLY
 
 const char *lt_fn_ba_host_error(void) { return g_host_error.c_str(); }
 
@@ -705,11 +704,7 @@ int lt_fn_ba_host(int n_img, const int32_t *img_ids, const double *kvec4, const 
                               ln_img, l2d4, l3d6, cfg);
   std::string msg;
   Plan pl;
-  if (make_plan(in, pl, msg)) {
-    g_host_error = "lt_fn_ba_host: " + msg;
-    return LT_ERR_ARGUMENT;
-  }
-  g_host_error.clear();
+  if (int rc = g_host_error.check("lt_fn_ba_host", make_plan(in, pl, msg), msg)) return rc;
   Result res;
   if (pl.NB == 0) {
     no_residuals(pl, res);
@@ -735,12 +730,8 @@ int lt_fn_ba_eval(int n_img, const int32_t *img_ids, const double *kvec4, const 
                               ln_img, l2d4, l3d6, cfg);
   std::string msg;
   Plan pl;
-  if (make_plan(in, pl, msg)) {
-    g_host_error = "lt_fn_ba_eval: " + msg;
-    return LT_ERR_ARGUMENT;
-  }
-  g_host_error.clear();
-  if (pl.constant_pose) { g_host_error = "lt_fn_ba_eval: constant_pose=1 has no joint system"; return LT_ERR_ARGUMENT; }
+  if (int rc = g_host_error.check("lt_fn_ba_eval", make_plan(in, pl, msg), msg)) return rc;
+  if (pl.constant_pose) return g_host_error.refuse("lt_fn_ba_eval", "constant_pose=1 has no joint system");
   const int NL = pl.NS - pl.NP;
   if (params6_in)  // the lines' minimal parameters as given (the edge fixtures), not those of their segments
     std::copy(params6_in, params6_in + 6 * (size_t)NL, pl.sp0.begin() + 6 * (size_t)pl.NP);
@@ -751,7 +742,7 @@ int lt_fn_ba_eval(int n_img, const int32_t *img_ids, const double *kvec4, const 
     if (!pl.st[(size_t)s].constant) { so[(size_t)s] = nu; nu += pl.st[(size_t)s].kind ? 4 : 3; }
   if (dims4) { dims4[0] = pl.C; dims4[1] = pl.NB; dims4[2] = nu; dims4[3] = pl.NS; }
   if (!residuals && !cost && !g && !H && !step && !blk_info3) return LT_OK;
-  if (pl.NB == 0) { g_host_error = "lt_fn_ba_eval: no residual blocks"; return LT_ERR_ARGUMENT; }
+  if (pl.NB == 0) return g_host_error.refuse("lt_fn_ba_eval", "no residual blocks");
   HostTables h;
   host_tables(pl, h);
   const BaDev &d = h.dev;
@@ -816,15 +807,9 @@ int lt_fn_ba_point_eval(int n_img, const int32_t *img_ids, const double *kvec4, 
                               ln_img, l2d4, l3d6, cfg);
   std::string msg;
   Plan pl;
-  if (make_plan(in, pl, msg)) {
-    g_host_error = "lt_fn_ba_point_eval: " + msg;
-    return LT_ERR_ARGUMENT;
-  }
-  g_host_error.clear();
-  if (!pl.constant_pose || !p3 || track < 0 || track >= pl.NP) {
-    g_host_error = "lt_fn_ba_point_eval: constant_pose=1, a point and a point track's index are needed";
-    return LT_ERR_ARGUMENT;
-  }
+  if (int rc = g_host_error.check("lt_fn_ba_point_eval", make_plan(in, pl, msg), msg)) return rc;
+  if (!pl.constant_pose || !p3 || track < 0 || track >= pl.NP)
+    return g_host_error.refuse("lt_fn_ba_point_eval", "constant_pose=1, a point and a point track's index are needed");
   BaDev d;
   bind_points(pl, d);
   std::vector<double> pose = pl.pose0, sp = pl.sp0;
@@ -834,12 +819,7 @@ int lt_fn_ba_point_eval(int n_img, const int32_t *img_ids, const double *kvec4, 
   if (cost) *cost = grp.cost(p3);
   double acc[kRfSums];
   grp.linearise(p3, acc);
-  if (H) {
-    int o = 0;
-    for (int i = 0; i < 4; ++i)
-      for (int j = i; j < 4; ++j, ++o) H[4 * i + j] = H[4 * j + i] = acc[o];
-  }
-  if (g) std::copy(acc + 10, acc + 14, g);
+  sums_to_gH<4>(acc, g, H);
   return LT_OK;
 }
 
@@ -881,15 +861,9 @@ int lt_fn_ba_host_trace(int n_img, const int32_t *img_ids, const double *kvec4, 
                               ln_img, l2d4, l3d6, cfg);
   std::string msg;
   Plan pl;
-  if (make_plan(in, pl, msg)) {
-    g_host_error = "lt_fn_ba_host_trace: " + msg;
-    return LT_ERR_ARGUMENT;
-  }
-  g_host_error.clear();
-  if (pl.constant_pose || pl.NB == 0 || cap < 0 || !n_attempts || !total0 || (cap > 0 && !rec5)) {
-    g_host_error = "lt_fn_ba_host_trace: free poses, a residual block and the outputs are needed";
-    return LT_ERR_ARGUMENT;
-  }
+  if (int rc = g_host_error.check("lt_fn_ba_host_trace", make_plan(in, pl, msg), msg)) return rc;
+  if (pl.constant_pose || pl.NB == 0 || cap < 0 || !n_attempts || !total0 || (cap > 0 && !rec5))
+    return g_host_error.refuse("lt_fn_ba_host_trace", "free poses, a residual block and the outputs are needed");
   HostTables h;
   host_tables(pl, h);
   host_init(h.dev, 1, total0);

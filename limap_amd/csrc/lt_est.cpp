@@ -5,6 +5,7 @@
 
 #include "lt_host.h"
 #include "lt_est_loop.h"
+#include "lt_twin.h"
 
 #include <algorithm>
 #include <climits>
@@ -75,7 +76,7 @@ void run_host(const Plan &pl, int n_threads, double *poses, int32_t *counts) {
   }
 }
 
-thread_local std::string g_host_error;
+thread_local HostError g_host_error;
 
 // ---- the hybrid loop ----
 struct LoopPlan {
@@ -260,7 +261,7 @@ void copy_loop_out(const LoopPlan &pl, const EhState *st, const int *inl, const 
 
 extern "C" {
 
-#ifndef LT_EST_HOST_ONLY
+#ifndef LT_HOST_ONLY
 int lt_est_minimal(lt_ctx *ctx, int kind, int64_t n, const double *xs, const double *Xs, const double *ls, const double *Cs,
                    const double *Vs) {
   if (!ctx) return LT_ERR_ARGUMENT;
@@ -313,7 +314,7 @@ int lt_est_minimal_get_timers(lt_ctx *ctx, double out[4]) {
   for (int k = 0; k < 4; ++k) out[k] = ctx->es.timers[k];
   return LT_OK;
 }
-#endif  // LT_EST_HOST_ONLY
+#endif  // LT_HOST_ONLY
 
 const char *lt_fn_est_host_error(void) { return g_host_error.c_str(); }
 
@@ -347,7 +348,7 @@ void lt_est_config_default(lt_est_config *c) {
   c->loc.weight_point = 1.0;
 }
 
-#ifndef LT_EST_HOST_ONLY
+#ifndef LT_HOST_ONLY
 int lt_est_solve(lt_ctx *ctx, int64_t n_query, const double *kvec4, const double *qvec4, const double *tvec3,
                  const int64_t *pt_off, const double *p3d3, const double *p2d2, const int64_t *l3d_off, const double *line3d6,
                  const int64_t *seg_off, const int32_t *l3d_ids, const double *seg4, const lt_est_config *cfg,
@@ -447,7 +448,7 @@ int lt_est_get_timers(lt_ctx *ctx, double out[8]) {
   for (int k = 0; k < 8; ++k) out[k] = ctx->es.loop_timers[k];
   return LT_OK;
 }
-#endif  // LT_EST_HOST_ONLY
+#endif  // LT_HOST_ONLY
 
 int lt_fn_est_host(int64_t n_query, const double *kvec4, const double *qvec4, const double *tvec3, const int64_t *pt_off,
                    const double *p3d3, const double *p2d2, const int64_t *l3d_off, const double *line3d6,
@@ -456,12 +457,9 @@ int lt_fn_est_host(int64_t n_query, const double *kvec4, const double *qvec4, co
                    double *trace) {
   std::string msg;
   LoopPlan pl;
-  if (make_loop_plan(n_query, kvec4, qvec4, tvec3, pt_off, p3d3, p2d2, l3d_off, line3d6, seg_off, l3d_ids, seg4, cfg, trace_cap,
-                     pl, msg)) {
-    g_host_error = "lt_fn_est_host: " + msg;
-    return LT_ERR_ARGUMENT;
-  }
-  g_host_error.clear();
+  const bool bad = make_loop_plan(n_query, kvec4, qvec4, tvec3, pt_off, p3d3, p2d2, l3d_off, line3d6, seg_off, l3d_ids, seg4, cfg,
+                                  trace_cap, pl, msg);
+  if (int rc = g_host_error.check("lt_fn_est_host", bad, msg)) return rc;
   LoopResult res;
   run_loop_host(pl, host_threads, res);
   copy_loop_out(pl, res.st.data(), res.inl.data(), res.trace.data(), pose7, dstats3, istats12, inliers, trace);
@@ -494,11 +492,7 @@ int lt_fn_est_minimal_host(int kind, int64_t n, const double *xs, const double *
                            const double *Vs, int n_threads, double *poses56, int32_t *counts) {
   std::string msg;
   Plan pl;
-  if (make_plan(kind, n, xs, Xs, ls, Cs, Vs, pl, msg)) {
-    g_host_error = "lt_fn_est_minimal_host: " + msg;
-    return LT_ERR_ARGUMENT;
-  }
-  g_host_error.clear();
+  if (int rc = g_host_error.check("lt_fn_est_minimal_host", make_plan(kind, n, xs, Xs, ls, Cs, Vs, pl, msg), msg)) return rc;
   run_host(pl, n_threads, poses56, counts);
   return LT_OK;
 }

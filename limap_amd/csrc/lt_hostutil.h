@@ -1,7 +1,8 @@
 // lt_hostutil.h -- the host toolkit of the modules around the triangulation core (lt_merge, lt_fit, lt_eval, lt_bpt,
 // lt_match, lt_vp, lt_refine, lt_sfm, the remerge of lt_tracks): stream synchronisation, HIP event timing, transfers of host
 // vectors, input checks, the counted-output launch loop and the polled loop of the coupled solves.  A new module uses
-// these, it does not bring its own.  Included from lt_host.h.
+// these, it does not bring its own.  Included from lt_host.h.  What a host twin's entry points share without
+// a context or the HIP runtime (the error slot, the unpacking of the packed sums) is lt_twin.h.
 #pragma once
 
 #include "lt_ctx.h"

@@ -6,6 +6,7 @@
 
 #include "lt_host.h"
 #include "lt_loc.h"
+#include "lt_twin.h"
 
 #include <algorithm>
 #include <climits>
@@ -167,7 +168,7 @@ std::vector<int> residual_counts(const Plan &pl) {
   return r;
 }
 
-static thread_local std::string g_host_error;
+static thread_local HostError g_host_error;
 
 // ---- pose scoring ----
 struct ScorePlan {
@@ -337,11 +338,8 @@ int lt_fn_loc_host(int64_t n_prob, const double *kvec4, const double *qvec4, con
                    double *tvec3_out, double *cost2, int32_t *num_res, int32_t *iters, int32_t *codes) {
   std::string msg;
   Plan pl;
-  if (make_plan(n_prob, kvec4, qvec4, tvec3, line_off, line3d6, seg_off, seg4, pt_off, p3d3, p2d2, cfg, pl, msg)) {
-    g_host_error = "lt_fn_loc_host: " + msg;
-    return LT_ERR_ARGUMENT;
-  }
-  g_host_error.clear();
+  const bool bad = make_plan(n_prob, kvec4, qvec4, tvec3, line_off, line3d6, seg_off, seg4, pt_off, p3d3, p2d2, cfg, pl, msg);
+  if (int rc = g_host_error.check("lt_fn_loc_host", bad, msg)) return rc;
   std::vector<LcOut> out;
   run_host(pl, n_threads, out);
   const std::vector<int> nr = residual_counts(pl);
@@ -357,12 +355,9 @@ static int loc_eval(const char *who, bool as_given, const double kvec4[4], const
   std::string msg;
   Plan pl;
   const int64_t line_off[2] = {0, n_lines}, pt_off[2] = {0, n_points};
-  if (n_lines < 0 || n_points < 0 ||
-      make_plan(1, kvec4, qvec4, tvec3, line_off, line3d6, seg_off, seg4, pt_off, p3d3, p2d2, cfg, pl, msg)) {
-    g_host_error = std::string(who) + ": " + msg;
-    return LT_ERR_ARGUMENT;
-  }
-  g_host_error.clear();
+  const bool bad = n_lines < 0 || n_points < 0 ||
+                   make_plan(1, kvec4, qvec4, tvec3, line_off, line3d6, seg_off, seg4, pt_off, p3d3, p2d2, cfg, pl, msg);
+  if (int rc = g_host_error.check(who, bad, msg)) return rc;
   const LcProb &pr = pl.probs[0];
   const LcOut &o = pl.init[0];
   double p[7] = {o.q[0], o.q[1], o.q[2], o.q[3], o.t[0], o.t[1], o.t[2]};
@@ -373,12 +368,7 @@ static int loc_eval(const char *who, bool as_given, const double kvec4[4], const
   if (cost) *cost = grp.cost(p);
   double acc[kLcSums];
   grp.linearise_res(p, acc, residuals);
-  if (H) {
-    int o2 = 0;
-    for (int i = 0; i < 6; ++i)
-      for (int j = i; j < 6; ++j, ++o2) H[6 * i + j] = H[6 * j + i] = acc[o2];
-  }
-  if (g) std::copy(acc + 21, acc + 27, g);
+  sums_to_gH<6>(acc, g, H);
   return LT_OK;
 }
 
@@ -479,11 +469,8 @@ int lt_fn_loc_score_host(const double kvec4[4], int64_t n_l3d, const double *lin
                          double *table, double *scores, int32_t *inliers2) {
   std::string msg;
   ScorePlan pl;
-  if (make_score_plan(kvec4, n_l3d, line3d6, n_seg, l3d_ids, seg4, n_pts, p3d3, p2d2, n_poses, qvec4, tvec3, cfg, pl, msg)) {
-    g_host_error = "lt_fn_loc_score_host: " + msg;
-    return LT_ERR_ARGUMENT;
-  }
-  g_host_error.clear();
+  const bool bad = make_score_plan(kvec4, n_l3d, line3d6, n_seg, l3d_ids, seg4, n_pts, p3d3, p2d2, n_poses, qvec4, tvec3, cfg, pl, msg);
+  if (int rc = g_host_error.check("lt_fn_loc_score_host", bad, msg)) return rc;
   score_host(pl, n_threads, table, scores, inliers2);
   return LT_OK;
 }

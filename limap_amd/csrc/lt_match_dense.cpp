@@ -149,7 +149,7 @@ void host_dists(const float *lines1, long long n1, const int32_t *shape1, const 
 
 extern "C" {
 
-#ifndef LT_DENSE_HOST_ONLY  // (the sanitizer program of tools/dense_host_asan.cpp compiles the host restatement alone)
+#ifndef LT_HOST_ONLY  // (the sanitizer program of tools/dense_host_asan.cpp compiles the host restatement alone)
 int lt_match_dense_pairs(lt_ctx *ctx, int n_img, const int64_t *line_off, const float *lines, const int32_t *shapes,
                          int64_t n_pairs, const int32_t *pair_img, const float *const *warp, const float *const *cert,
                          const int32_t *dims, const lt_match_dense_config *cfg, int64_t *n_rows) {
@@ -359,7 +359,7 @@ int lt_match_dense_get_dirs(lt_ctx *ctx, float *d12, float *o12, float *d21, flo
   return LT_OK;
 }
 
-#endif  // LT_DENSE_HOST_ONLY
+#endif  // LT_HOST_ONLY
 
 int lt_fn_match_dense_dists_host(const float *lines1, int64_t n1, const int32_t *shape1, const float *lines2, int64_t n2,
                                  const int32_t *shape2, const float *warp12, const float *cert12, const int32_t *dims12,

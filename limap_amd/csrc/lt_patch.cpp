@@ -3,15 +3,16 @@
 // (lt_kernels_patch.hip); lt_fn_patch_extract_host is the host path from the same inline expressions of lt_patch.h
 // under OpenMP, lt_fn_patch_geometry the patches' geometry alone and lt_fn_patch_ranges GetLine2DRange over CSR arrays
 // of tracks and supports.  Every argument is checked before any work.  The sanitizer program of
-// tools/patch_host_asan.cpp compiles this file with LT_PATCH_HOST_ONLY: the host-only entry points, no context, no
+// tools/patch_host_asan.cpp compiles this file with LT_HOST_ONLY: the host-only entry points, no context, no
 // HIP runtime.
 
-#ifndef LT_PATCH_HOST_ONLY
+#ifndef LT_HOST_ONLY
 #include "lt_host.h"
 #else
 #include "../../include/limap_amd.h"
 #endif
 #include "lt_patch.h"
+#include "lt_twin.h"
 
 #include <climits>
 #include <cmath>
@@ -26,7 +27,7 @@ using namespace lt;
 
 namespace {
 
-thread_local std::string t_err;
+thread_local lt_impl::HostError t_err;
 
 struct PtPlan {
   std::vector<PtGeom> geom;
@@ -173,7 +174,7 @@ int lt_fn_patch_geometry(const lt_patch_config *cfg, int64_t c, int64_t n, const
                          double *tvec2, int32_t *h, int64_t *off) {
   t_err.clear();
   PtPlan plan;
-  if (make_plan(cfg, c, n, lines4, plan, t_err)) return LT_ERR_ARGUMENT;
+  if (make_plan(cfg, c, n, lines4, plan, t_err.text)) return LT_ERR_ARGUMENT;
   copy_geometry(plan, R4, tvec2, h, off);
   return LT_OK;
 }
@@ -182,10 +183,10 @@ int lt_fn_patch_extract_host(const lt_patch_config *cfg, const lt_feature_map *m
                              int32_t out_dtype, void *out, int n_threads) {
   t_err.clear();
   PtPlan plan;
-  if (check_map(map, t_err) || make_plan(cfg, map->c, n, lines4, plan, t_err)) return LT_ERR_ARGUMENT;
-  if (!known_dtype(out_dtype)) { t_err = "unknown output dtype " + std::to_string(out_dtype); return LT_ERR_ARGUMENT; }
-  if (map->on_device) { t_err = "lt_fn_patch_extract_host: device feature map"; return LT_ERR_ARGUMENT; }
-  if (n > 0 && !out) { t_err = "null output"; return LT_ERR_ARGUMENT; }
+  if (check_map(map, t_err.text) || make_plan(cfg, map->c, n, lines4, plan, t_err.text)) return LT_ERR_ARGUMENT;
+  if (!known_dtype(out_dtype)) { t_err.text = "unknown output dtype " + std::to_string(out_dtype); return LT_ERR_ARGUMENT; }
+  if (map->on_device) { t_err.text = "lt_fn_patch_extract_host: device feature map"; return LT_ERR_ARGUMENT; }
+  if (n > 0 && !out) { t_err.text = "null output"; return LT_ERR_ARGUMENT; }
   std::vector<PtPatch> patches;
   std::vector<PtBlock> blocks;
   make_blocks(plan, 0, n, map->c, 1, patches, blocks);
@@ -207,29 +208,29 @@ int lt_fn_patch_ranges(int64_t n_tracks, const double *line6, const int64_t *sup
                        const double *sup_seg4, int64_t n_pairs, const int32_t *pair_track, const int32_t *pair_img,
                        const double *pair_cam11, double *range4, int32_t *status) {
   t_err.clear();
-  if (n_tracks < 0 || n_pairs < 0) { t_err = "negative count"; return LT_ERR_ARGUMENT; }
-  if (n_tracks > 0 && (!line6 || !sup_off)) { t_err = "null track arrays"; return LT_ERR_ARGUMENT; }
+  if (n_tracks < 0 || n_pairs < 0) { t_err.text = "negative count"; return LT_ERR_ARGUMENT; }
+  if (n_tracks > 0 && (!line6 || !sup_off)) { t_err.text = "null track arrays"; return LT_ERR_ARGUMENT; }
   if (n_pairs > 0 && (!pair_track || !pair_img || !pair_cam11 || !range4 || !status)) {
-    t_err = "null pair arrays";
+    t_err.text = "null pair arrays";
     return LT_ERR_ARGUMENT;
   }
   if (n_tracks > 0) {
-    if (sup_off[0] != 0) { t_err = "support offsets must start at 0"; return LT_ERR_ARGUMENT; }
+    if (sup_off[0] != 0) { t_err.text = "support offsets must start at 0"; return LT_ERR_ARGUMENT; }
     for (int64_t t = 0; t < n_tracks; ++t)
-      if (sup_off[t + 1] < sup_off[t]) { t_err = "support offsets decrease"; return LT_ERR_ARGUMENT; }
-    if (sup_off[n_tracks] > 0 && (!sup_img || !sup_seg4)) { t_err = "null support arrays"; return LT_ERR_ARGUMENT; }
+      if (sup_off[t + 1] < sup_off[t]) { t_err.text = "support offsets decrease"; return LT_ERR_ARGUMENT; }
+    if (sup_off[n_tracks] > 0 && (!sup_img || !sup_seg4)) { t_err.text = "null support arrays"; return LT_ERR_ARGUMENT; }
     for (int64_t k = 0; k < 6 * n_tracks; ++k)
-      if (!std::isfinite(line6[k])) { t_err = "track " + std::to_string(k / 6) + ": non-finite 3D line"; return LT_ERR_ARGUMENT; }
+      if (!std::isfinite(line6[k])) { t_err.text = "track " + std::to_string(k / 6) + ": non-finite 3D line"; return LT_ERR_ARGUMENT; }
     for (int64_t k = 0; k < 4 * sup_off[n_tracks]; ++k)
-      if (!std::isfinite(sup_seg4[k])) { t_err = "support " + std::to_string(k / 4) + ": non-finite 2D line"; return LT_ERR_ARGUMENT; }
+      if (!std::isfinite(sup_seg4[k])) { t_err.text = "support " + std::to_string(k / 4) + ": non-finite 2D line"; return LT_ERR_ARGUMENT; }
   }
   for (int64_t i = 0; i < n_pairs; ++i) {
     if (pair_track[i] < 0 || pair_track[i] >= n_tracks) {
-      t_err = "pair " + std::to_string(i) + ": track index outside the table";
+      t_err.text = "pair " + std::to_string(i) + ": track index outside the table";
       return LT_ERR_ARGUMENT;
     }
     for (int k = 0; k < 11; ++k)
-      if (!std::isfinite(pair_cam11[11 * i + k])) { t_err = "pair " + std::to_string(i) + ": non-finite camera"; return LT_ERR_ARGUMENT; }
+      if (!std::isfinite(pair_cam11[11 * i + k])) { t_err.text = "pair " + std::to_string(i) + ": non-finite camera"; return LT_ERR_ARGUMENT; }
   }
 #pragma omp parallel for schedule(static)
   for (int64_t i = 0; i < n_pairs; ++i) {
@@ -243,7 +244,7 @@ int lt_fn_patch_ranges(int64_t n_tracks, const double *line6, const int64_t *sup
   return LT_OK;
 }
 
-#ifndef LT_PATCH_HOST_ONLY
+#ifndef LT_HOST_ONLY
 
 using namespace lt_impl;
 
@@ -417,6 +418,6 @@ int lt_patch_copy_yardstick(lt_ctx *ctx, int64_t bytes, double *ms) {
   return LT_OK;
 }
 
-#endif  // LT_PATCH_HOST_ONLY
+#endif  // LT_HOST_ONLY
 
 }  // extern "C"

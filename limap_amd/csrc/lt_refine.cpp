@@ -9,6 +9,7 @@
 #include "lt_host.h"
 #include "lt_refine.h"
 #include "lt_ingest.h"
+#include "lt_twin.h"
 
 #include <algorithm>
 #include <climits>
@@ -570,7 +571,7 @@ void copy_out(const RfOut *o, long long T, double *params6, double *seg6, double
   }
 }
 
-#ifndef LT_REFINE_HOST_ONLY  // (tools/refine_feature_host_asan.cpp compiles the host twins alone: no context, no HIP runtime)
+#ifndef LT_HOST_ONLY  // (tools/refine_feature_host_asan.cpp compiles the host twins alone: no context, no HIP runtime)
 // upload of the plan, the three kernels, download into ctx->rf.out; d_k / d_q / d_t: the cameras on the device
 // tp: the terms of the call, or null; with them k_refine_prep_terms runs too and k_refine_lm_terms replaces k_refine_lm
 int run_device(lt_ctx *ctx, const Plan &pl, const double *d_k, const double *d_q, const double *d_t,
@@ -665,11 +666,11 @@ int upload_cameras(lt_ctx *ctx, int n_img, const double *kvec4, const double *qv
   }
   return LT_OK;
 }
-#endif  // LT_REFINE_HOST_ONLY
+#endif  // LT_HOST_ONLY
 
 }  // namespace
 
-#ifndef LT_REFINE_HOST_ONLY
+#ifndef LT_HOST_ONLY
 namespace lt_impl {
 
 // lt_refine_tracks (lt_tracks.cpp): the cameras of the context, resident since lt_init
@@ -688,7 +689,7 @@ int refine_with_ctx_cams(lt_ctx *ctx, int64_t T, const double *line6, const int6
 }
 
 }  // namespace lt_impl
-#endif  // LT_REFINE_HOST_ONLY
+#endif  // LT_HOST_ONLY
 
 extern "C" {
 
@@ -703,7 +704,7 @@ void lt_refine_config_default(lt_refine_config *cfg) {
   cfg->pad_ = 0;
 }
 
-#ifndef LT_REFINE_HOST_ONLY
+#ifndef LT_HOST_ONLY
 int lt_refine_arrays(lt_ctx *ctx, int n_img, const int32_t *img_ids, const double *kvec4, const double *qvec4,
                      const double *tvec3, int64_t n_tracks, const double *line6, const int64_t *off, const int32_t *img,
                      const double *line2d4, const double *line3d6, const lt_refine_config *cfg) {
@@ -720,7 +721,7 @@ int lt_refine_arrays(lt_ctx *ctx, int n_img, const int32_t *img_ids, const doubl
   if (int rc = upload_cameras(ctx, n_img, kvec4, qvec4, tvec3)) return rc;
   return run_device(ctx, pl, ctx->rf.d_k.as<double>(), ctx->rf.d_q.as<double>(), ctx->rf.d_t.as<double>(), *cfg, t0);
 }
-#endif  // LT_REFINE_HOST_ONLY
+#endif  // LT_HOST_ONLY
 
 void lt_refine_terms_default(lt_refine_terms *t) {
   if (!t) return;
@@ -736,7 +737,7 @@ void lt_refine_terms_default(lt_refine_terms *t) {
   t->pad_ = 0;
 }
 
-#ifndef LT_REFINE_HOST_ONLY
+#ifndef LT_HOST_ONLY
 int lt_refine_set_heatmaps(lt_ctx *ctx, int n, const int32_t *img_ids, const int32_t *h, const int32_t *w,
                            const void *const *data, int texel_type) {
   if (!ctx) return LT_ERR_ARGUMENT;
@@ -937,9 +938,9 @@ int lt_refine_get_timers(lt_ctx *ctx, double out[4]) {
   for (int k = 0; k < 4; ++k) out[k] = ctx->rf.timers[k];
   return LT_OK;
 }
-#endif  // LT_REFINE_HOST_ONLY
+#endif  // LT_HOST_ONLY
 
-static thread_local std::string g_host_error;
+static thread_local HostError g_host_error;
 const char *lt_fn_refine_host_error(void) { return g_host_error.c_str(); }
 
 int lt_fn_refine_host(int n_img, const int32_t *img_ids, const double *kvec4, const double *qvec4, const double *tvec3,
@@ -949,12 +950,9 @@ int lt_fn_refine_host(int n_img, const int32_t *img_ids, const double *kvec4, co
   std::string msg;
   std::unordered_map<int, int> id2idx;
   Plan pl;
-  if (check_config(cfg, msg) || ingest_cams(n_img, img_ids, kvec4, qvec4, tvec3, id2idx, msg) ||
-      make_plan(id2idx, n_tracks, line6, off, img, line2d4, line3d6, *cfg, pl, msg)) {
-    g_host_error = "lt_fn_refine_host: " + msg;
-    return LT_ERR_ARGUMENT;
-  }
-  g_host_error.clear();
+  const bool bad = check_config(cfg, msg) || ingest_cams(n_img, img_ids, kvec4, qvec4, tvec3, id2idx, msg) ||
+                   make_plan(id2idx, n_tracks, line6, off, img, line2d4, line3d6, *cfg, pl, msg);
+  if (int rc = g_host_error.check("lt_fn_refine_host", bad, msg)) return rc;
   std::vector<RfOut> out;
   run_host(pl, kvec4, qvec4, tvec3, *cfg, n_threads, out);
   copy_out(out.data(), (long long)out.size(), params6, seg6, cost2, iters, codes);
@@ -969,10 +967,7 @@ int lt_fn_refine_host_terms(int n_img, const int32_t *img_ids, const double *kve
                             const void *const *hm_data, int n_threads, double *params6, double *seg6, double *cost2,
                             int32_t *iters, int32_t *codes) {
   std::string msg;
-  if (check_terms(terms, msg)) {
-    g_host_error = "lt_fn_refine_host_terms: " + msg;
-    return LT_ERR_ARGUMENT;
-  }
+  if (check_terms(terms, msg)) return g_host_error.refuse("lt_fn_refine_host_terms", msg);
   if (!terms->use_vp && !terms->use_heatmap)
     return lt_fn_refine_host(n_img, img_ids, kvec4, qvec4, tvec3, n_tracks, line6, off, img, line2d4, line3d6, cfg,
                              n_threads, params6, seg6, cost2, iters, codes);
@@ -980,14 +975,11 @@ int lt_fn_refine_host_terms(int n_img, const int32_t *img_ids, const double *kve
   Plan pl;
   TermsPlan tp;
   HmSet hs;
-  if ((terms->use_heatmap && check_heatmaps(n_hm, hm_ids, hm_h, hm_w, hm_data, terms->texel_type, hs, msg)) ||
-      check_config(cfg, msg) || ingest_cams(n_img, img_ids, kvec4, qvec4, tvec3, id2idx, msg) ||
-      make_plan(id2idx, n_tracks, line6, off, img, line2d4, line3d6, *cfg, pl, msg) ||
-      make_terms_plan(pl, img, *terms, vp_flag, vp3, view_hw, &hs, tp, msg)) {
-    g_host_error = "lt_fn_refine_host_terms: " + msg;
-    return LT_ERR_ARGUMENT;
-  }
-  g_host_error.clear();
+  const bool bad = (terms->use_heatmap && check_heatmaps(n_hm, hm_ids, hm_h, hm_w, hm_data, terms->texel_type, hs, msg)) ||
+                   check_config(cfg, msg) || ingest_cams(n_img, img_ids, kvec4, qvec4, tvec3, id2idx, msg) ||
+                   make_plan(id2idx, n_tracks, line6, off, img, line2d4, line3d6, *cfg, pl, msg) ||
+                   make_terms_plan(pl, img, *terms, vp_flag, vp3, view_hw, &hs, tp, msg);
+  if (int rc = g_host_error.check("lt_fn_refine_host_terms", bad, msg)) return rc;
   std::vector<RfOut> out;
   run_host(pl, kvec4, qvec4, tvec3, *cfg, n_threads, out, &tp, &hs);
   copy_out(out.data(), (long long)out.size(), params6, seg6, cost2, iters, codes);
@@ -1017,16 +1009,14 @@ int lt_fn_refine_host_feature(int n_img, const int32_t *img_ids, const double *k
   TermsPlan tp;
   FeatPlan fp;
   HmSet hs;
-  if (check_feature(terms, feat, msg) ||
+  const bool bad =
+      check_feature(terms, feat, msg) ||
       (terms->use_heatmap && check_heatmaps(n_hm, hm_ids, hm_h, hm_w, hm_data, terms->texel_type, hs, msg)) ||
       check_config(cfg, msg) || ingest_cams(n_img, img_ids, kvec4, qvec4, tvec3, id2idx, msg) ||
       make_plan(id2idx, n_tracks, line6, off, img, line2d4, line3d6, *cfg, pl, msg) ||
       make_terms_plan(pl, img, *terms, vp_flag, vp3, view_hw, &hs, tp, msg) ||
-      make_feat_plan(pl, id2idx, n_img, kvec4, qvec4, tvec3, off, img, line2d4, *terms, *feat, n_grids, grids, false, fp, msg)) {
-    g_host_error = "lt_fn_refine_host_feature: " + msg;
-    return LT_ERR_ARGUMENT;
-  }
-  g_host_error.clear();
+      make_feat_plan(pl, id2idx, n_img, kvec4, qvec4, tvec3, off, img, line2d4, *terms, *feat, n_grids, grids, false, fp, msg);
+  if (int rc = g_host_error.check("lt_fn_refine_host_feature", bad, msg)) return rc;
   std::vector<RfOut> out;
   run_host(pl, kvec4, qvec4, tvec3, *cfg, n_threads, out, &tp, &hs, &fp);
   copy_out(out.data(), (long long)out.size(), params6, seg6, cost2, iters, codes);
@@ -1041,10 +1031,7 @@ int lt_fn_refine_eval_feature(int n_img, const int32_t *img_ids, const double *k
                               int32_t *targets, int32_t *n_blocks, double *residuals, int32_t *failed, double *cost,
                               double g[4], double H[16]) {
   std::string msg;
-  auto bad = [&](const std::string &m) {
-    g_host_error = "lt_fn_refine_eval_feature: " + m;
-    return LT_ERR_ARGUMENT;
-  };
+  auto bad = [&](const std::string &m) { return g_host_error.refuse("lt_fn_refine_eval_feature", m); };
   if (K < 1 || K > (1 << 28) || !line6 || !(alpha >= 0.0) || !(alpha <= 700.0)) return bad("bad track arrays");
   if (check_feature(terms, feat, msg)) return bad(msg);
   if (terms->use_vp || terms->use_heatmap) return bad("the VP and heatmap terms are lt_fn_refine_eval_terms'");
@@ -1099,12 +1086,7 @@ int lt_fn_refine_eval_feature(int n_img, const int32_t *img_ids, const double *k
     if (cost) *cost = grp.cost(p);
     double acc[kRfSums];
     grp.linearise_res(p, acc, residuals, failed);
-    if (H) {
-      int o = 0;
-      for (int i = 0; i < 4; ++i)
-        for (int j = i; j < 4; ++j, ++o) H[4 * i + j] = H[4 * j + i] = acc[o];
-    }
-    if (g) std::copy(acc + 10, acc + 14, g);
+    sums_to_gH<4>(acc, g, H);
   });
   return LT_OK;
 }
@@ -1145,12 +1127,7 @@ int lt_fn_refine_eval_terms(int64_t K, const double *cam11, const double *line2d
     double acc[kRfSums];
     const bool ok = grp.linearise_res(params6, acc, residuals);
     if (failed) *failed = ok ? 0 : 1;
-    if (H) {
-      int o = 0;
-      for (int i = 0; i < 4; ++i)
-        for (int j = i; j < 4; ++j, ++o) H[4 * i + j] = H[4 * j + i] = acc[o];
-    }
-    if (g) std::copy(acc + 10, acc + 14, g);
+    sums_to_gH<4>(acc, g, H);
   });
   return LT_OK;
 }
@@ -1171,12 +1148,7 @@ int lt_fn_refine_eval(int64_t K, const double *cam11, const double *line2d4, con
   if (cost) *cost = grp.cost(params6);
   double acc[kRfSums];
   grp.linearise(params6, acc);
-  if (H) {
-    int o = 0;
-    for (int i = 0; i < 4; ++i)
-      for (int j = i; j < 4; ++j, ++o) H[4 * i + j] = H[4 * j + i] = acc[o];
-  }
-  if (g) std::copy(acc + 10, acc + 14, g);
+  sums_to_gH<4>(acc, g, H);
   if (residuals) {
     Rf4 u[4], w[2], dm[6];
     rf_seed(params6, u, w);

@@ -5,6 +5,7 @@
 
 #include "lt_hostutil.h"
 #include "lt_sfm_host.h"
+#include "lt_twin.h"
 
 #include <algorithm>
 #include <climits>
@@ -78,7 +79,7 @@ struct HostResult {
   std::vector<long long> nb_off{0};
   std::vector<int> nb;
   std::vector<SfmPair> pairs;
-  std::string err;
+  HostError err;
 };
 thread_local HostResult t_host;
 
@@ -143,7 +144,7 @@ int lt_fn_sfm_neighbors_host(int n_img, const float *R9, const float *T3, int64_
   out.nb.clear();
   out.pairs.clear();
   SfmPrep m;
-  if (sfm_prepare(n_img, R9, T3, n_pts, xyz, track_off, track_img, kind, num_images, min_triangulation_angle, m, out.err))
+  if (sfm_prepare(n_img, R9, T3, n_pts, xyz, track_off, track_img, kind, num_images, min_triangulation_angle, m, out.err.text))
     return LT_ERR_ARGUMENT;
   const int nt = n_threads > 0 ? n_threads : omp_get_max_threads();
   host_neighbors(m, xyz, track_off, track_img, kind, (long long)num_images, sfm_gate_of(min_triangulation_angle), nt, out);
@@ -164,7 +165,7 @@ const char *lt_fn_sfm_host_error(void) { return t_host.err.c_str(); }
 
 int lt_fn_sfm_ranges(int64_t n_pts, const float *xyz, double range_lo, double range_hi, double k_stretch, double lo[3],
                      double hi[3]) {
-  std::string &err = t_host.err;
+  std::string &err = t_host.err.text;
   err.clear();
   if (!lo || !hi) { err = "lt_fn_sfm_ranges: null output"; return LT_ERR_ARGUMENT; }
   if (n_pts <= 0 || !xyz) { err = "lt_fn_sfm_ranges: the model has no points"; return LT_ERR_ARGUMENT; }

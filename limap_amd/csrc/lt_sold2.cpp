@@ -6,6 +6,7 @@
 // lt_fn_sold2_descinfo_host) and the getters.
 
 #include "lt_host.h"
+#include "lt_twin.h"
 
 #include <algorithm>
 #include <cmath>
@@ -22,7 +23,7 @@ using lt_host::S2Result;
 
 namespace {
 
-thread_local std::string t_err;
+thread_local HostError t_err;
 thread_local S2Result t_res;
 
 struct Prep {
@@ -242,8 +243,8 @@ S2Seg host_refine_segment(const Prep &pr, const S2Img &m, int img, long long p) 
 
 int host_detect(const lt_sold2_config *c, int n_img, const lt_sold2_image *imgs, int n_threads) {
   Prep pr;
-  t_err = prepare(c, n_img, imgs, true, pr);
-  if (!t_err.empty()) return LT_ERR_ARGUMENT;
+  t_err.text = prepare(c, n_img, imgs, true, pr);
+  if (!t_err.text.empty()) return LT_ERR_ARGUMENT;
   const int saved = omp_get_max_threads();
   if (n_threads > 0) omp_set_num_threads(n_threads);
   S2Result &res = t_res;
@@ -294,7 +295,7 @@ const S2Result *result_of(lt_ctx *ctx) { return ctx ? &ctx->s2.res : &t_res; }
 int bad_image(lt_ctx *ctx, const char *who) {
   const std::string msg = std::string(who) + ": no such image in the last detection";
   if (ctx) return fail(ctx, LT_ERR_ARGUMENT, msg);
-  t_err = msg;
+  t_err.text = msg;
   return LT_ERR_ARGUMENT;
 }
 
@@ -341,14 +342,14 @@ const char *lt_fn_sold2_host_error(void) { return t_err.c_str(); }
 int lt_fn_sold2_samples_host(const lt_sold2_config *cfg, const lt_sold2_image *img, int64_t n_pairs, const int32_t *pairs2,
                              float *pos, float *values) {
   Prep pr;
-  t_err = prepare(cfg, 1, img, true, pr);
-  if (t_err.empty() && (n_pairs < 0 || (n_pairs > 0 && (!pairs2 || !pos || !values)))) t_err = "line2d: null pairs or outputs";
-  if (!t_err.empty()) return LT_ERR_ARGUMENT;
+  t_err.text = prepare(cfg, 1, img, true, pr);
+  if (t_err.text.empty() && (n_pairs < 0 || (n_pairs > 0 && (!pairs2 || !pos || !values)))) t_err.text = "line2d: null pairs or outputs";
+  if (!t_err.text.empty()) return LT_ERR_ARGUMENT;
   const S2Cfg &k = pr.cfg;
   const S2Img &m = pr.imgs[0];
   for (int64_t p = 0; p < n_pairs; ++p)
     if (pairs2[2 * p] < 0 || pairs2[2 * p] >= m.n || pairs2[2 * p + 1] < 0 || pairs2[2 * p + 1] >= m.n) {
-      t_err = "line2d: a pair names no junction";
+      t_err.text = "line2d: a pair names no junction";
       return LT_ERR_ARGUMENT;
     }
   const S2HeatGlobal heat{m.heat, m.heat_stride};
@@ -371,9 +372,9 @@ int lt_fn_sold2_samples_host(const lt_sold2_config *cfg, const lt_sold2_image *i
 
 int lt_fn_sold2_block_scales_host(const lt_sold2_config *cfg, const lt_sold2_image *img, float *scales, int32_t *bounds4) {
   Prep pr;
-  t_err = prepare(cfg, 1, img, true, pr);
-  if (t_err.empty() && (!pr.refine_heat || !scales || !bounds4)) t_err = "line2d: heatmap refinement is off or an output is null";
-  if (!t_err.empty()) return LT_ERR_ARGUMENT;
+  t_err.text = prepare(cfg, 1, img, true, pr);
+  if (t_err.text.empty() && (!pr.refine_heat || !scales || !bounds4)) t_err.text = "line2d: heatmap refinement is off or an output is null";
+  if (!t_err.text.empty()) return LT_ERR_ARGUMENT;
   const S2Img &m = pr.imgs[0];
   std::vector<float> vals;
   for (int b = 0; b < m.nb * m.nb; ++b) scales[b] = host_block_scale(pr.cfg, m, b / m.nb, b % m.nb, vals);
@@ -560,8 +561,8 @@ int lt_sold2_get_kernel_ms(lt_ctx *ctx, double out[8]) {
 }
 
 int lt_fn_sold2_descinfo_host(int n_img, const lt_sold2_desc_image *imgs, int n_threads) {
-  t_err = check_desc(n_img, imgs, true);
-  if (!t_err.empty()) return LT_ERR_ARGUMENT;
+  t_err.text = check_desc(n_img, imgs, true);
+  if (!t_err.text.empty()) return LT_ERR_ARGUMENT;
   const int saved = omp_get_max_threads();
   if (n_threads > 0) omp_set_num_threads(n_threads);
   for (int i = 0; i < n_img; ++i) {

@@ -6,6 +6,7 @@
 
 #include "lt_hostutil.h"
 #include "lt_undist_host.h"
+#include "lt_twin.h"
 
 #include <climits>
 #include <cmath>
@@ -112,7 +113,7 @@ int ud_check_points(int n_cam, int64_t n, const double *xy, const int32_t *cam_s
 
 namespace {
 
-thread_local std::string t_err;
+thread_local HostError t_err;
 
 template <int C>
 void host_row(const UdCam &cs, const UdCam &ct, const lt_undist_image &m, int y) {
@@ -136,9 +137,9 @@ int lt_fn_undist_warp_host(int n_cam, const lt_undist_camera *cams, int n_img, c
   t_err.clear();
   std::vector<UdCam> table;
   UdBatch batch;
-  if (ud_prepare_cams(n_cam, cams, table, t_err) || ud_prepare_images(table, n_img, imgs, batch, t_err))
+  if (ud_prepare_cams(n_cam, cams, table, t_err.text) || ud_prepare_images(table, n_img, imgs, batch, t_err.text))
     return LT_ERR_ARGUMENT;
-  if (batch.on_device) { t_err = "lt_fn_undist_warp_host: device images"; return LT_ERR_ARGUMENT; }
+  if (batch.on_device) { t_err.text = "lt_fn_undist_warp_host: device images"; return LT_ERR_ARGUMENT; }
   const int nt = n_threads > 0 ? n_threads : omp_get_max_threads();
   for (int i = 0; i < n_img; ++i) {
     const lt_undist_image &m = imgs[i];
@@ -158,7 +159,7 @@ int lt_fn_undist_points_host(int n_cam, const lt_undist_camera *cams, int64_t n,
                              int32_t *iters, int n_threads) {
   t_err.clear();
   std::vector<UdCam> table;
-  if (ud_prepare_cams(n_cam, cams, table, t_err) || ud_check_points(n_cam, n, xy, cam_src, cam_dst, out_xy, status, iters, t_err))
+  if (ud_prepare_cams(n_cam, cams, table, t_err.text) || ud_check_points(n_cam, n, xy, cam_src, cam_dst, out_xy, status, iters, t_err.text))
     return LT_ERR_ARGUMENT;
   const int nt = n_threads > 0 ? n_threads : omp_get_max_threads();
 #pragma omp parallel for num_threads(nt) schedule(static)
@@ -174,12 +175,12 @@ int lt_fn_undist_points_host(int n_cam, const lt_undist_camera *cams, int64_t n,
 int lt_fn_undist_scale(int32_t w, int32_t h, double cx, double cy, const double ext[8], double blank_pixels,
                        double min_scale, double max_scale, double out[4]) {
   t_err.clear();
-  if (!ext || !out || w < 1 || h < 1) { t_err = "lt_fn_undist_scale: bad arguments"; return LT_ERR_ARGUMENT; }
-  if (!(blank_pixels >= 0.0 && blank_pixels <= 1.0)) { t_err = "Check failed: blank_pixels in [0, 1]"; return LT_ERR_ARGUMENT; }
-  if (!(min_scale > 0.0)) { t_err = "Check failed: min_scale > 0"; return LT_ERR_ARGUMENT; }
-  if (!(min_scale <= max_scale) || !std::isfinite(max_scale)) { t_err = "Check failed: min_scale <= max_scale"; return LT_ERR_ARGUMENT; }
+  if (!ext || !out || w < 1 || h < 1) { t_err.text = "lt_fn_undist_scale: bad arguments"; return LT_ERR_ARGUMENT; }
+  if (!(blank_pixels >= 0.0 && blank_pixels <= 1.0)) { t_err.text = "Check failed: blank_pixels in [0, 1]"; return LT_ERR_ARGUMENT; }
+  if (!(min_scale > 0.0)) { t_err.text = "Check failed: min_scale > 0"; return LT_ERR_ARGUMENT; }
+  if (!(min_scale <= max_scale) || !std::isfinite(max_scale)) { t_err.text = "Check failed: min_scale <= max_scale"; return LT_ERR_ARGUMENT; }
   if (!all_finite(ext, 8) || !std::isfinite(cx) || !std::isfinite(cy)) {
-    t_err = "lt_fn_undist_scale: non-finite border";
+    t_err.text = "lt_fn_undist_scale: non-finite border";
     return LT_ERR_ARGUMENT;
   }
   const double dims[2] = {(double)w, (double)h}, c[2] = {cx, cy};
@@ -190,11 +191,11 @@ int lt_fn_undist_scale(int32_t w, int32_t h, double cx, double cy, const double 
     const double smin = lo_b < lo_a ? lo_b : lo_a;  // std::min(lo_a, lo_b)
     const double smax = hi_a < hi_b ? hi_b : hi_a;  // std::max(hi_a, hi_b)
     double s = 1.0 / (smin * blank_pixels + smax * (1.0 - blank_pixels));
-    if (s != s) { t_err = "lt_fn_undist_scale: the border gives no scale"; return LT_ERR_ARGUMENT; }
+    if (s != s) { t_err.text = "lt_fn_undist_scale: the border gives no scale"; return LT_ERR_ARGUMENT; }
     s = s < min_scale ? min_scale : (max_scale < s ? max_scale : s);  // std::clamp
     double n = s * dims[a];
     if (!(n >= 1.0)) n = 1.0;
-    if (n > (double)kUdMaxDim) { t_err = "lt_fn_undist_scale: the undistorted image is too large"; return LT_ERR_ARGUMENT; }
+    if (n > (double)kUdMaxDim) { t_err.text = "lt_fn_undist_scale: the undistorted image is too large"; return LT_ERR_ARGUMENT; }
     const double size = (double)(long long)n;  // size_t(max(1.0, scale * size))
     out[a] = size;
     out[2 + a] = c[a] * (size / dims[a]);

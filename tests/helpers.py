@@ -106,6 +106,17 @@ def small_scene(seed=0, n_views=16, n_segs=120, n_neighbors=8, **kw):
 
 
 import contextlib
+import os
+import subprocess
+
+
+def run_host_asan(target, program):
+    """`make -C limap_amd/csrc <target>`: builds tools/<program>.cpp with its unit under AddressSanitizer and UBSan (a
+    program of its own: no device, nothing loaded into Python) and runs it; exit status 0 and the success line"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    res = subprocess.run(["make", "-C", os.path.join(root, "limap_amd", "csrc"), target], stdout=subprocess.PIPE,
+                         stderr=subprocess.STDOUT, text=True)
+    assert res.returncode == 0 and f"{program}: all checks passed" in res.stdout.splitlines(), res.stdout[-2000:]
 
 
 @contextlib.contextmanager

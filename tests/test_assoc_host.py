@@ -630,3 +630,9 @@ def test_goldens_reproduce(path):
 
 def test_goldens_exist():
     assert len(glob.glob(os.path.join(GOLDEN, "*.npz"))) >= 4
+
+
+def test_sanitizer_program_of_the_host_twin():
+    """tools/assoc_host_asan.cpp + lt_assoc.cpp (host-only) under AddressSanitizer and UBSan, a program of its own"""
+    from helpers import run_host_asan
+    run_host_asan("assoc_asan", "assoc_host_asan")

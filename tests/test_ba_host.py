@@ -424,3 +424,9 @@ def test_constant_pose_line_tracks_delegate_bit_for_bit(hybrid):
     free = optimize.HybridBAConfig(dict(constant_intrinsics=True))
     with pytest.raises(ValueError, match="constant_pose"):
         optimize.solve_line_bundle_adjustment(free, imagecols, lines, host_threads=1)
+
+
+def test_sanitizer_program_of_the_host_twin():
+    """tools/ba_host_asan.cpp + lt_ba.cpp (host-only) under AddressSanitizer and UBSan, a program of its own"""
+    from helpers import run_host_asan
+    run_host_asan("ba_asan", "ba_host_asan")

@@ -209,12 +209,8 @@ def test_the_package_exposes_the_module():
 
 def test_sanitizer_program_of_the_host_twin():
     """tools/est_host_asan.cpp + lt_est.cpp (host-only) under AddressSanitizer and UBSan, a program of its own"""
-    import os
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    res = subprocess.run(["make", "-C", os.path.join(root, "limap_amd", "csrc"), "est_asan"], stdout=subprocess.PIPE,
-                         stderr=subprocess.STDOUT, text=True)
-    assert res.returncode == 0 and "est_host_asan: ok" in res.stdout, res.stdout[-2000:]
+    from helpers import run_host_asan
+    run_host_asan("est_asan", "est_host_asan")
 
 
 # ======== the hybrid loop (host twin lt_fn_est_host) ========

@@ -6,7 +6,6 @@ import ctypes as C
 import glob
 import importlib.util
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -179,7 +178,5 @@ def test_python_surface(tmp_path):
 
 def test_sanitizer_program_of_the_host_restatement():
     """tools/dense_host_asan.cpp + lt_match_dense.cpp under AddressSanitizer and UBSan, a program of its own"""
-    root = os.path.dirname(HERE)
-    res = subprocess.run(["make", "-C", os.path.join(root, "limap_amd", "csrc"), "dense_asan"], stdout=subprocess.PIPE,
-                         stderr=subprocess.STDOUT, text=True)
-    assert res.returncode == 0 and "all checks passed" in res.stdout, res.stdout[-2000:]
+    from helpers import run_host_asan
+    run_host_asan("dense_asan", "dense_host_asan")

@@ -349,8 +349,5 @@ def test_argument_errors(gpu_lib):
 
 def test_sanitizer_program_of_the_host_path():
     """tools/patch_host_asan.cpp + lt_patch.cpp (host-only) under AddressSanitizer and UBSan, a program of its own"""
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    res = subprocess.run(["make", "-C", os.path.join(root, "limap_amd", "csrc"), "patch_asan"], stdout=subprocess.PIPE,
-                         stderr=subprocess.STDOUT, text=True)
-    assert res.returncode == 0 and "all checks passed" in res.stdout, res.stdout[-2000:]
+    from helpers import run_host_asan
+    run_host_asan("patch_asan", "patch_host_asan")

@@ -355,3 +355,9 @@ def test_python_surface(scene, sources, tmp_path):
         np.save(os.path.join(fdir, f"feature_{i}.npy"), np.ascontiguousarray(m.transpose(2, 0, 1)))
     assert np.array_equal(_lines(optimize.line_refinement(dict(CFG), tracks, ic, patch_dir=pdir, host_threads=2)), _lines(by_p))
     assert np.array_equal(_lines(optimize.line_refinement(dict(CFG), tracks, ic, featuremap_dir=fdir, host_threads=2)), _lines(by_m))
+
+
+def test_sanitizer_program_of_the_host_twin():
+    """tools/refine_feature_host_asan.cpp + lt_refine.cpp (host-only) under AddressSanitizer and UBSan, a program of its own"""
+    from helpers import run_host_asan
+    run_host_asan("refine_feature_asan", "refine_feature_host_asan")

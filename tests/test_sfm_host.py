@@ -94,11 +94,8 @@ def test_non_finite_projection_centre_is_refused(gpu_lib):
 
 def test_sanitizer_program_of_the_host_unit():
     """tools/sfm_host_asan.cpp + lt_sfm_host.cpp under AddressSanitizer and UBSan, a program of its own"""
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    res = subprocess.run(["make", "-C", os.path.join(root, "limap_amd", "csrc"), "sfm_asan"], stdout=subprocess.PIPE,
-                         stderr=subprocess.STDOUT, text=True)
-    assert res.returncode == 0 and "all checks passed" in res.stdout, res.stdout[-2000:]
+    from helpers import run_host_asan
+    run_host_asan("sfm_asan", "sfm_host_asan")
 
 
 def test_percentile_picks_round_half_away_from_zero(gpu_lib):

@@ -299,8 +299,5 @@ def test_errors_before_any_work(gpu_lib):
 
 def test_sanitizer_program_of_the_host_unit():
     """tools/undist_host_asan.cpp + lt_undist_host.cpp under AddressSanitizer and UBSan, a program of its own"""
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    res = subprocess.run(["make", "-C", os.path.join(root, "limap_amd", "csrc"), "undist_asan"], stdout=subprocess.PIPE,
-                         stderr=subprocess.STDOUT, text=True)
-    assert res.returncode == 0 and "all checks passed" in res.stdout, res.stdout[-2000:]
+    from helpers import run_host_asan
+    run_host_asan("undist_asan", "undist_host_asan")

@@ -1,12 +1,12 @@
 // assoc_host_asan.cpp -- the host twin of the global point-line association (lt_fn_assoc_host, lt_fn_assoc_eval,
 // lt_fn_assoc_pcg, lt_fn_assoc_link2d of lt_assoc.cpp) under AddressSanitizer and UBSan, as a program of its own:
-// lt_assoc.cpp is compiled into it with LT_ASSOC_HOST_ONLY and the sanitizers; nothing is loaded into Python and no device
+// lt_assoc.cpp is compiled into it with LT_HOST_ONLY and the sanitizers; nothing is loaded into Python and no device
 // is touched.  `make -C limap_amd/csrc assoc_asan` builds and runs it.
 // The cases: a scene of 4 cameras with points on lines along three orthogonal directions, three vanishing points and
 // every edge kind; every switch; the traced solve; the zero-gradient end and the no-residual end; the refusals; the
 // evaluation with all of its outputs; the linear solve at 1, 255, 256 and 257 unknowns, a breakdown and a bad pivot.
 // Every array is exactly as long as the call may read or write.
-#include "../include/limap_amd.h"
+#include "host_asan.h"
 
 #include <cmath>
 #include <cstdint>
@@ -16,25 +16,11 @@
 
 namespace {
 
-int failures = 0;
-#define EXPECT(cond)                                                  \
-  do {                                                                \
-    if (!(cond)) {                                                    \
-      std::printf("FAILED line %d: %s\n", __LINE__, #cond);           \
-      ++failures;                                                     \
-    }                                                                 \
-  } while (0)
+bool has(const char *what) { return host_asan::has(lt_fn_assoc_host_error, what); }
 
-bool has(const char *what) { return std::string(lt_fn_assoc_host_error()).find(what) != std::string::npos; }
-
-double jitter(unsigned &state) {
-  state = state * 1664525u + 1013904223u;
-  return (double)(state >> 8) / 8388608.0 - 1.0;
-}
-
-struct Scene {
-  std::vector<int32_t> ids, pimg, limg, ek, ea, eb;
-  std::vector<double> k, q, t, p3, pxy, line6, l2d, vp, ew;
+struct Scene : Cameras {
+  std::vector<int32_t> pimg, limg, ek, ea, eb;
+  std::vector<double> p3, pxy, line6, l2d, vp, ew;
   std::vector<int64_t> poff{0}, loff{0};
   lt_assoc_input input() const {
     lt_assoc_input in{};
@@ -52,28 +38,10 @@ struct Scene {
   }
 };
 
-// cameras in a row looking down +z, slightly turned about y
-void project(const Scene &s, int c, const double X[3], double xy[2]) {
-  const double w = s.q[4 * c], y = s.q[4 * c + 2], n = w * w + y * y;
-  const double r00 = (w * w - y * y) / n, r02 = 2 * w * y / n, r20 = -r02, r22 = r00;
-  const double x = r00 * X[0] + r02 * X[2] + s.t[3 * c], yy = X[1] + s.t[3 * c + 1], z = r20 * X[0] + r22 * X[2] + s.t[3 * c + 2];
-  xy[0] = s.k[4 * c] * x / z + s.k[4 * c + 2];
-  xy[1] = s.k[4 * c + 1] * yy / z + s.k[4 * c + 3];
-}
-
 Scene make(int n_cams, int lines_per_dir, unsigned seed) {
   Scene s;
   unsigned st = seed;
-  for (int c = 0; c < n_cams; ++c) {
-    s.ids.push_back(5 + 3 * c);
-    const double kk[4] = {600, 590, 400, 300};
-    s.k.insert(s.k.end(), kk, kk + 4);
-    const double a = 0.05 * (c - 0.5 * n_cams);
-    const double qq[4] = {std::cos(a), 0.0, std::sin(a), 0.0};
-    s.q.insert(s.q.end(), qq, qq + 4);
-    const double tt[3] = {0.8 * (c - 0.5 * n_cams), 0.1 * c, 5.0};
-    s.t.insert(s.t.end(), tt, tt + 3);
-  }
+  camera_row(s, n_cams);
   int n_lines = 0, n_points = 0;
   for (int dir = 0; dir < 3; ++dir)
     for (int l = 0; l < lines_per_dir; ++l, ++n_lines) {
@@ -81,8 +49,6 @@ Scene make(int n_cams, int lines_per_dir, unsigned seed) {
       b[dir] += 1.2;
       for (int c = 0; c < n_cams; ++c) {
         double xa[2], xb[2];
-        project(s, c, a, xa);
-        project(s, c, b, xb);
         s.limg.push_back(s.ids[(size_t)((c + n_lines) % n_cams)]);
         project(s, (c + n_lines) % n_cams, a, xa);
         project(s, (c + n_lines) % n_cams, b, xb);
@@ -241,6 +207,5 @@ int main() {
   pcg_case(12, false, true);
   const double l1[4] = {0, 0, 100, 0}, l2[4] = {10, 1, 90, 2}, l3[4] = {10, 40, 90, 41};
   EXPECT(lt_fn_assoc_link2d(l1, l2) == 1 && lt_fn_assoc_link2d(l1, l3) == 0);
-  std::printf(failures ? "assoc_host_asan: %d FAILED\n" : "assoc_host_asan: ok\n", failures);
-  return failures ? 1 : 0;
+  return finish("assoc_host_asan");
 }

@@ -1,13 +1,13 @@
 // ba_host_asan.cpp -- the host twin of the bundle adjustment with free poses (lt_fn_ba_host, lt_fn_ba_eval,
 // lt_fn_ba_cholesky of lt_ba.cpp) under AddressSanitizer and UBSan, as a program of its own: lt_ba.cpp is compiled into
-// it with LT_BA_HOST_ONLY and the sanitizers; nothing is loaded into Python and no device is touched.
+// it with LT_HOST_ONLY and the sanitizers; nothing is loaded into Python and no device is touched.
 // `make -C limap_amd/csrc ba_asan` builds and runs it.
 // The cases follow tests/test_ba_host.py: a hybrid scene of 4 cameras, 24 points and 6 lines; tracks with 1, 15, 16, 17
 // and 33 observations (an image then observes a track more than once); an image without observations in the middle of
 // the ids; every switch; constant poses (the separated point solves); termination codes 6 and 7; every refusal; the
 // evaluation with its dense H and the Schur step;
 // the Cholesky recurrence at sizes 1, 6, 7, 64, 65 and 258.  Every array is exactly as long as the call may read.
-#include "../include/limap_amd.h"
+#include "host_asan.h"
 
 #include <cmath>
 #include <cstdint>
@@ -17,52 +17,18 @@
 
 namespace {
 
-int failures = 0;
-#define EXPECT(cond)                                                  \
-  do {                                                                \
-    if (!(cond)) {                                                    \
-      std::printf("FAILED line %d: %s\n", __LINE__, #cond);           \
-      ++failures;                                                     \
-    }                                                                 \
-  } while (0)
+bool has(const char *what) { return host_asan::has(lt_fn_ba_host_error, what); }
 
-bool has(const char *what) { return std::string(lt_fn_ba_host_error()).find(what) != std::string::npos; }
-
-// a deterministic stand-in for noise in [-1, 1)
-double jitter(unsigned &state) {
-  state = state * 1664525u + 1013904223u;
-  return (double)(state >> 8) / 8388608.0 - 1.0;
-}
-
-struct Scene {
-  std::vector<int32_t> ids, pimg, limg;
-  std::vector<double> k, q, t, p3, pxy, line6, l2d, l3d;
+struct Scene : Cameras {
+  std::vector<int32_t> pimg, limg;
+  std::vector<double> p3, pxy, line6, l2d, l3d;
   std::vector<int64_t> poff{0}, loff{0};
 };
-
-// cameras in a row looking down +z from z = -5, slightly turned; structure around the origin
-void project(const Scene &s, int c, const double X[3], double xy[2]) {
-  // the turn is small: the rotation of the unit quaternion (w, 0, y, 0)
-  const double w = s.q[4 * c], y = s.q[4 * c + 2], n = w * w + y * y;
-  const double r00 = (w * w - y * y) / n, r02 = 2 * w * y / n, r20 = -r02, r22 = r00;
-  const double x = r00 * X[0] + r02 * X[2] + s.t[3 * c], yy = X[1] + s.t[3 * c + 1], z = r20 * X[0] + r22 * X[2] + s.t[3 * c + 2];
-  xy[0] = s.k[4 * c] * x / z + s.k[4 * c + 2];
-  xy[1] = s.k[4 * c + 1] * yy / z + s.k[4 * c + 3];
-}
 
 Scene make(int n_cams, int n_points, int n_lines, const std::vector<int> &pobs, const std::vector<int> &lobs, unsigned seed) {
   Scene s;
   unsigned st = seed;
-  for (int c = 0; c < n_cams; ++c) {
-    s.ids.push_back(5 + 3 * c);
-    const double kk[4] = {600, 590, 400, 300};
-    s.k.insert(s.k.end(), kk, kk + 4);
-    const double a = 0.05 * (c - 0.5 * n_cams);
-    const double qq[4] = {std::cos(a), 0.0, std::sin(a), 0.0};
-    s.q.insert(s.q.end(), qq, qq + 4);
-    const double tt[3] = {0.8 * (c - 0.5 * n_cams), 0.1 * c, 5.0};
-    s.t.insert(s.t.end(), tt, tt + 3);
-  }
+  camera_row(s, n_cams);
   for (int n = 0; n < n_points; ++n) {
     double X[3] = {jitter(st), jitter(st), jitter(st)};
     const int cnt = n < (int)pobs.size() ? pobs[(size_t)n] : n_cams;
@@ -233,6 +199,5 @@ int main() {
     S[0] = -1.0;
     EXPECT(lt_fn_ba_cholesky(n, S.data(), rhs.data(), L.data(), x.data()) != 0);
   }
-  if (failures == 0) std::printf("all checks passed\n");
-  return failures == 0 ? 0 : 1;
+  return finish("ba_host_asan");
 }

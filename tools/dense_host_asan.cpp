@@ -1,12 +1,12 @@
 // dense_host_asan.cpp -- the host restatement of the dense-warp line matcher (lt_fn_match_dense_pair_host,
 // lt_fn_match_dense_dists_host of lt_match_dense.cpp) under AddressSanitizer and UBSan, as a program of its own: the
-// file is compiled into it with the sanitizers and without its device entry (LT_DENSE_HOST_ONLY); nothing is loaded into
+// file is compiled into it with the sanitizers and without its device entry (LT_HOST_ONLY); nothing is loaded into
 // Python and no device is touched.  `make -C limap_amd/csrc dense_asan` builds and runs it on two fixtures of
 // tests/golden/match_dense (asan_*.bin: raw arrays written by make_match_dense_golden.py -- lines that leave the
 // maps, maps whose aspect differs from the images', certainty holes, zero-length lines) and on the degenerate shapes:
 // no lines on either side, 1 x 1 maps, NaN and infinity in a warp, every refusal.  Buffers are exactly as large as the
 // sizes say: an overrun of one element is the sanitizer's to find.
-#include "../include/limap_amd.h"
+#include "host_asan.h"
 
 #include <cmath>
 #include <cstdint>
@@ -15,15 +15,6 @@
 #include <vector>
 
 namespace {
-
-int failures = 0;
-#define EXPECT(cond)                                                  \
-  do {                                                                \
-    if (!(cond)) {                                                    \
-      std::printf("FAILED line %d: %s\n", __LINE__, #cond);           \
-      ++failures;                                                     \
-    }                                                                 \
-  } while (0)
 
 struct Pair {
   std::vector<float> l1, l2, w12, c12, w21, c21;
@@ -166,6 +157,5 @@ int main(int argc, char **argv) {
     p.cfg.pixel_th = 10.0f;
     EXPECT(run(p).rc == 0);
   }
-  if (failures == 0) std::printf("all checks passed\n");
-  return failures == 0 ? 0 : 1;
+  return finish("dense_host_asan");
 }

@@ -1,12 +1,12 @@
 // est_host_asan.cpp -- the host twin of the minimal pose solvers (lt_fn_est_minimal_host of lt_est.cpp) under
-// AddressSanitizer and UBSan, as a program of its own: lt_est.cpp is compiled into it with LT_EST_HOST_ONLY and the
+// AddressSanitizer and UBSan, as a program of its own: lt_est.cpp is compiled into it with LT_HOST_ONLY and the
 // sanitizers; nothing is loaded into Python and no device is touched.  `make -C limap_amd/csrc est_asan` builds and runs it.
 // The cases: planted poses of every kind at 1, 63, 64, 65 and 257 samples with the planted pose looked for among the
 // results; 1 against 4 threads; the degenerate samples (identical correspondences, collinear points, parallel lines,
 // zero vectors, a half turn); the refusals; the hybrid loop (lt_fn_est_host) on planted queries of unequal size with one
 // that VerifyData rejects, with the trace, at round sizes 1, 64 and 100, 1 against 3 threads, and its refusals.  Every
 // array is exactly as long as the call may read or write.
-#include "../include/limap_amd.h"
+#include "host_asan.h"
 
 #include <cmath>
 #include <cstdint>
@@ -16,16 +16,7 @@
 
 namespace {
 
-int failures = 0;
-#define EXPECT(cond)                                                  \
-  do {                                                                \
-    if (!(cond)) {                                                    \
-      std::printf("FAILED line %d: %s\n", __LINE__, #cond);           \
-      ++failures;                                                     \
-    }                                                                 \
-  } while (0)
-
-bool has(const char *what) { return std::string(lt_fn_est_host_error()).find(what) != std::string::npos; }
+bool has(const char *what) { return host_asan::has(lt_fn_est_host_error, what); }
 
 double uniform(unsigned &state) {  // [0, 1)
   state = state * 1664525u + 1013904223u;
@@ -247,6 +238,5 @@ int main() {
     EXPECT(lt_fn_est_host(3, k.data(), q.data(), t.data(), po.data(), p3.data(), p2.data(), lo.data(), l3.data(), so.data(), ids.data(),
                           sg.data(), &cfg, 0, 1, nullptr, nullptr, nullptr, nullptr, nullptr) == LT_ERR_ARGUMENT && has("l3d_id"));
   }
-  std::printf(failures ? "est_host_asan: %d FAILED\n" : "est_host_asan: ok\n", failures);
-  return failures ? 1 : 0;
+  return finish("est_host_asan");
 }

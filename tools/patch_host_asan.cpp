@@ -1,12 +1,12 @@
 // patch_host_asan.cpp -- the host path of limap_amd.features (lt_fn_patch_extract_host, lt_fn_patch_geometry,
 // lt_fn_patch_ranges of lt_patch.cpp) under AddressSanitizer and UBSan, as a program of its own: lt_patch.cpp is
-// compiled into it with LT_PATCH_HOST_ONLY and the sanitizers; nothing is loaded into Python and no device is touched.
+// compiled into it with LT_HOST_ONLY and the sanitizers; nothing is loaded into Python and no device is touched.
 // `make -C limap_amd/csrc patch_asan` builds and runs it (tests/test_patch_host.py does that).
 // The cases are the degenerate ones of the tests: a 1x1 map, one row, one column, every input and output type, channel
 // counts 1, 3 and 8, a (C, H, W) map read through its strides, patches that hang over every edge or lie outside the
 // image, a zero-length line, range_perp 0, no lines, the narrowing's edge values, tracks without supports, and every
 // refusal.  Buffers are exactly as large as the sizes say: an overrun of one element is the sanitizer's to find.
-#include "../include/limap_amd.h"
+#include "host_asan.h"
 
 #include <cmath>
 #include <cstdint>
@@ -17,18 +17,9 @@
 
 namespace {
 
-int failures = 0;
-#define EXPECT(cond)                                                  \
-  do {                                                                \
-    if (!(cond)) {                                                    \
-      std::printf("FAILED line %d: %s\n", __LINE__, #cond);           \
-      ++failures;                                                     \
-    }                                                                 \
-  } while (0)
-
 int esize(int dtype) { return dtype == LT_PATCH_F16 ? 2 : (dtype == LT_PATCH_F32 ? 4 : 8); }
 
-bool has(const char *what) { return std::string(lt_fn_patch_host_error()).find(what) != std::string::npos; }
+bool has(const char *what) { return host_asan::has(lt_fn_patch_host_error, what); }
 
 const std::vector<double> kLines = {
     2.0, 3.0, 6.0, 3.0,      // horizontal
@@ -176,6 +167,5 @@ int main() {
     fm.on_device = 0;
     EXPECT(lt_fn_patch_extract_host(&def, &fm, 1, line, LT_PATCH_F64, out, 1) == 0 && has(""));
   }
-  if (failures == 0) std::printf("all checks passed\n");
-  return failures == 0 ? 0 : 1;
+  return finish("patch_host_asan");
 }

@@ -1,13 +1,13 @@
 // refine_feature_host_asan.cpp -- the host twin of the feature-consistency term (lt_fn_refine_host_feature,
 // lt_fn_refine_eval_feature and the sample builder of lt_refine.cpp) under AddressSanitizer and UBSan, as a program of
-// its own: lt_refine.cpp is compiled into it with LT_REFINE_HOST_ONLY and the sanitizers; nothing is loaded into Python
+// its own: lt_refine.cpp is compiled into it with LT_HOST_ONLY and the sanitizers; nothing is loaded into Python
 // and no device is touched.  `make -C limap_amd/csrc refine_feature_asan` builds and runs it.
 // The cases are the edge scenes of tests/test_refine_feature_host.py on four unrotated cameras beside a line along x: grids
 // of 1x1, 3x4 and 6x40 texels that the intersections leave on every side (the clamp), both texel types, a rotated
 // transform, supports beside the projection by just under and just over 0.3 px, points with one support, all supports
 // of a point in one image, a sample line parallel to the projection (termination code 6), and every refusal.  The texel
 // buffers are exactly h * w * 128 texels: a read past a grid is the sanitizer's to find.
-#include "../include/limap_amd.h"
+#include "host_asan.h"
 
 #include <cmath>
 #include <cstdint>
@@ -18,16 +18,7 @@
 
 namespace {
 
-int failures = 0;
-#define EXPECT(cond)                                                  \
-  do {                                                                \
-    if (!(cond)) {                                                    \
-      std::printf("FAILED line %d: %s\n", __LINE__, #cond);           \
-      ++failures;                                                     \
-    }                                                                 \
-  } while (0)
-
-bool has(const char *what) { return std::string(lt_fn_refine_host_error()).find(what) != std::string::npos; }
+bool has(const char *what) { return host_asan::has(lt_fn_refine_host_error, what); }
 
 const int32_t kIds[4] = {3, 5, 6, 9};
 const double kK[16] = {64, 64, 32, 24, 64, 64, 32, 24, 64, 64, 32, 24, 64, 64, 32, 24};
@@ -73,7 +64,7 @@ void grid(Scene &s, int h, int w, int type, bool rotated) {
   s.grids.push_back(g);
 }
 
-void finish(Scene &s) {
+void bind_grids(Scene &s) {
   for (size_t k = 0; k < s.grids.size(); ++k) s.grids[k].data = s.tex[k].data();
 }
 
@@ -130,7 +121,7 @@ Scene plain(int type, double dy, int h, int w, bool rotated) {
     support(s, c, 0.0, 1.0, dy);
     grid(s, h, w, type, rotated);
   }
-  finish(s);
+  bind_grids(s);
   return s;
 }
 
@@ -163,7 +154,7 @@ int main() {
     support(s, 1, 0.35, 0.62, 0.0);
     for (int c = 1; c < 4; ++c) support(s, c, 0.65, 1.0, 0.0);
     for (int c = 0; c < 4; ++c) grid(s, 3, 4, LT_TEXEL_F16, false);
-    finish(s);
+    bind_grids(s);
     EXPECT(eval(s, LT_TEXEL_F16, 12, &nk, &nb, &failed) == 0 && nk > 0 && nk < 12 && nb > 0 && nb < 2 * nk);
     EXPECT(run(s, LT_TEXEL_F16, 12, 2, &o) == 0);
   }
@@ -178,7 +169,7 @@ int main() {
       s.l3d.insert(s.l3d.end(), kLine, kLine + 6);
       grid(s, 3, 4, LT_TEXEL_F16, false);
     }
-    finish(s);
+    bind_grids(s);
     EXPECT(eval(s, LT_TEXEL_F16, 8, &nk, &nb, &failed) == 0 && nk == 1 && nb == 3 && failed[0] && failed[1] && failed[2]);
     EXPECT(run(s, LT_TEXEL_F16, 8, 1, &o) == 0 && o.code == 6 && o.it == 0 && std::isinf(o.cost[0]));
   }
@@ -209,6 +200,5 @@ int main() {
     lt_refine_feature_default(&feat);
     EXPECT(feat.use_feature == 1 && feat.n_samples_feature == 100 && feat.fconsis_multiplier == 1.0 && feat.channels == 128);
   }
-  if (failures == 0) std::printf("all checks passed\n");
-  return failures == 0 ? 0 : 1;
+  return finish("refine_feature_host_asan");
 }

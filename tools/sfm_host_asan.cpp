@@ -4,7 +4,7 @@
 // and runs it (tests/test_sfm_host.py does that).
 // The cases are the degenerate ones: no images, no points, tracks of length 0 and 1, repeated images, skipped slots
 // only, one image, a bad index, non-finite input, every undefined range.
-#include "../include/limap_amd.h"
+#include "host_asan.h"
 
 #include <cmath>
 #include <cstdint>
@@ -16,15 +16,6 @@
 #include <limits>
 
 namespace {
-
-int failures = 0;
-#define EXPECT(cond)                                                  \
-  do {                                                                \
-    if (!(cond)) {                                                    \
-      std::printf("FAILED line %d: %s\n", __LINE__, #cond);           \
-      ++failures;                                                     \
-    }                                                                 \
-  } while (0)
 
 struct Out {
   int rc;
@@ -122,6 +113,5 @@ int main() {
   EXPECT(lt_fn_sfm_ranges(20, pts.data(), 0.05, 1e30, 1.25, lo, hi) == LT_ERR_ARGUMENT);
   pts[7] = std::nanf("");
   EXPECT(lt_fn_sfm_ranges(20, pts.data(), 0.05, 0.95, 1.25, lo, hi) == LT_ERR_ARGUMENT);
-  std::printf(failures ? "sfm_host_asan: %d check(s) FAILED\n" : "sfm_host_asan: all checks passed\n", failures);
-  return failures ? 1 : 0;
+  return finish("sfm_host_asan");
 }

@@ -7,7 +7,7 @@
 // infinity and NaN, a target larger and one smaller than its source, no points, the singular Jacobian, the 100
 // iterations, and every refusal.  Buffers are exactly as large as the sizes say: an overrun of one byte is the
 // sanitizer's to find.
-#include "../include/limap_amd.h"
+#include "host_asan.h"
 
 #include <cmath>
 #include <cstdint>
@@ -17,15 +17,6 @@
 #include <vector>
 
 namespace {
-
-int failures = 0;
-#define EXPECT(cond)                                                  \
-  do {                                                                \
-    if (!(cond)) {                                                    \
-      std::printf("FAILED line %d: %s\n", __LINE__, #cond);           \
-      ++failures;                                                     \
-    }                                                                 \
-  } while (0)
 
 lt_undist_camera cam(int model, std::vector<double> p) {
   lt_undist_camera c;
@@ -82,7 +73,7 @@ Pts points(const lt_undist_camera &src, const lt_undist_camera &dst, const std::
   return p;
 }
 
-bool has(const char *what) { return std::string(lt_fn_undist_host_error()).find(what) != std::string::npos; }
+bool has(const char *what) { return host_asan::has(lt_fn_undist_host_error, what); }
 
 }  // namespace
 
@@ -186,6 +177,5 @@ int main() {
     const double nan_ext[8] = {NAN, 0, 0, 0, 0, 0, 0, 0};
     EXPECT(lt_fn_undist_scale(40, 30, 20.0, 15.0, nan_ext, 0.0, 0.2, 2.0, out) != 0 && has("non-finite"));
   }
-  if (failures == 0) std::printf("all checks passed\n");
-  return failures == 0 ? 0 : 1;
+  return finish("undist_host_asan");
 }
