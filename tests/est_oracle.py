@@ -229,6 +229,85 @@ def num_required(ratios, success, solver, min_it, max_it):
     return max(min_it, min(max_it, int(math.ceil(v)))) if v < max_it else max_it, frac
 
 
+def sample_picks(rng, count, n):
+    """eh_draw_solve's draw without replacement: the j-th draw is uniform(n - j), shifted past the ascending list of
+    what is taken"""
+    picks = []
+    for j in range(count):
+        v = rng.uniform(n - j)
+        for s in sorted(picks):
+            if v >= s:
+                v += 1
+        picks.append(v)
+    return picks
+
+
+def _bearing(u, v, kvec):
+    b0, b1 = (float(u) - kvec[2]) / kvec[0], (float(v) - kvec[3]) / kvec[1]
+    n0 = math.sqrt((b0 * b0 + b1 * b1) + 1.0)
+    return [b0 / n0, b1 / n0, 1.0 / n0]
+
+
+def loop_sample(scene, kvec, solver, picks_p, picks_l):
+    """The minimal sample of an iteration as eh_draw_solve builds it, in its operation order with float64 scalars
+    -> xs, Xs (3 - solver rows), ls, Cs, Vs (solver rows)"""
+    kvec = [float(k) for k in kvec]
+    xs = [_bearing(*scene["p2ds"][i], kvec) for i in picks_p]
+    Xs = [[float(c) for c in scene["p3ds"][i]] for i in picks_p]
+    ls, Cs, Vs = [], [], []
+    for i in picks_l:
+        seg = np.asarray(scene["l2ds"][i], float).reshape(4)
+        l3 = np.asarray(scene["l3ds"][int(scene["l3d_ids"][i])], float).reshape(6)
+        e0, e1 = _bearing(seg[0], seg[1], kvec), _bearing(seg[2], seg[3], kvec)
+        c0, c1, c2 = e0[1] * e1[2] - e0[2] * e1[1], e0[2] * e1[0] - e0[0] * e1[2], e0[0] * e1[1] - e0[1] * e1[0]
+        n0 = math.sqrt((c0 * c0 + c1 * c1) + c2 * c2)
+        ls.append([c0 / n0, c1 / n0, c2 / n0] if n0 > 0.0 else [0.0, 0.0, 0.0])  # a segment of zero length: no pose
+        Cs.append([float(c) for c in l3[:3]])
+        x, y, z = float(l3[3]) - float(l3[0]), float(l3[4]) - float(l3[1]), float(l3[5]) - float(l3[2])
+        n = math.sqrt((x * x + y * y) + z * z)  # unit() of lt_geom.h
+        Vs.append([x / n, y / n, z / n])
+    arr = lambda v: np.array(v, float).reshape(-1, 3)  # noqa: E731
+    return arr(xs), arr(Xs), arr(ls), arr(Cs), arr(Vs)
+
+
+def normalise_q(q):
+    """lm_normalise_q: CameraPose's constructor, the squares summed as (w2 + y2) + (x2 + z2)"""
+    q = [float(c) for c in q]
+    n0 = math.sqrt((q[0] * q[0] + q[2] * q[2]) + (q[1] * q[1] + q[3] * q[3]))
+    return np.array([c / n0 if n0 > 0.0 else c for c in q])
+
+
+def pose_round_trip(q, t):
+    """What eh_refine does to a refined pose: lm_normalise_q, es_rotation, rf_quat_from_matrix (Eigen's
+    Quaternion(Matrix3)), in the functions' operation order -> (qvec, tvec)"""
+    w, x, y, z = normalise_q(q)
+    m = [[1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y)],
+         [2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x)],
+         [2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y)]]
+    tr = (m[0][0] + m[1][1]) + m[2][2]
+    o = [0.0] * 4  # x, y, z, w
+    if tr > 0.0:
+        s = math.sqrt(tr + 1.0)
+        o[3] = 0.5 * s
+        s = 0.5 / s
+        o[0], o[1], o[2] = (m[2][1] - m[1][2]) * s, (m[0][2] - m[2][0]) * s, (m[1][0] - m[0][1]) * s
+    else:
+        i = 0
+        if m[1][1] > m[0][0]:
+            i = 1
+        if m[2][2] > m[i][i]:
+            i = 2
+        j = (i + 1) % 3
+        k = (j + 1) % 3
+        s = math.sqrt(((m[i][i] - m[j][j]) - m[k][k]) + 1.0)
+        o[i] = 0.5 * s
+        s = 0.5 / s
+        o[3] = (m[k][j] - m[j][k]) * s
+        o[j] = (m[j][i] + m[i][j]) * s
+        o[k] = (m[k][i] + m[i][k]) * s
+    return np.array([o[3], o[0], o[1], o[2]]), np.array(t, float)
+
+
 def lo_sizes(n_base, non_min_mult):
     """the non-minimal sample size of a local optimisation: max(6, min(3 multiplier, |inliers| / 2)), at most |inliers|"""
     return min(max(6, min(3 * non_min_mult, n_base // 2)), n_base)

@@ -175,4 +175,121 @@ def loc_cfg(method="hybrid", thres=10.0, flags=(True, True, True, True), final_l
 
 
 def query_of(sc):
-    return {k: sc[k] for k in ("l3ds", "l3d_ids", "l2ds", "p3ds", "p2ds", "camera")}
+    return {k: sc[k] for k in ("l3ds", "l3d_ids", "l2ds", "p3ds", "p2ds", "camera", "campose") if k in sc}
+
+
+# ---- the configuration matrix of the hybrid loop: one list for the twin (test_est_host.py) and the device (test_gpu_est.py) ----
+class _Pose:
+    def __init__(self, qvec, tvec):
+        self.qvec, self.tvec = np.array(qvec, float), np.array(tvec, float)
+
+
+START = ([0.9, 0.1, -0.2, 0.3], [0.5, -1.0, 2.0])  # a non-identity input pose, not normalised
+LOSS_PAIRS = [(0, 0), (1, 1), (3, 2), (4, 3)]  # (weight_function, loss): none / trivial, cosine / Huber, length / SoftLOne, inverse length / Cauchy
+LOOP_COSTS = [("MidpointDist2", 10.0), ("PerpendicularDist2", 10.0), ("PerpendicularDist4", 10.0), ("3DLineLineDist2", 0.1),
+              ("3DPlaneLineDist2", 0.1)]
+ZERO_SEGMENT = 11  # the segment of zero length in the case of that name
+
+
+def _with_pose(sc):
+    return dict(sc, campose=_Pose(*START))
+
+
+def _ransac(cfg, **kw):
+    return dict(cfg, ransac=dict(cfg["ransac"], **kw))
+
+
+def loop_cases():
+    """The cases of the loop: dicts with name, scenes, cfg, seed, trace_cap, fields (lt_est_config members), loc (members
+    of its loc block) and show, the property that keeps the case from passing vacuously (case_property)."""
+    out = []
+
+    def add(name, scenes, show, cfg=None, trace_cap=400, loc=None, **fields):
+        out.append(dict(name=name, scenes=scenes, show=show, cfg=cfg or loc_cfg(), seed=3, trace_cap=trace_cap, loc=loc or {},
+                        fields=fields))
+
+    for cost, thres in LOOP_COSTS:
+        for weight, loss in LOSS_PAIRS:
+            add(f"{cost}-w{weight}-l{loss}", [planted_scene(seed=2)], "lo", cfg=loc_cfg(cost=cost, thres=thres),
+                loc=dict(weight_function=weight, loss=loss, loss_a=0.05 if cost.startswith("3D") else 1.5, weight_line=0.7,
+                         weight_point=1.3))
+    for s, kind in enumerate(eo.KINDS):
+        add("only-" + kind, [planted_scene(seed=1)], ("only_solver", s), cfg=loc_cfg(flags=[i == s for i in range(4)]))
+    add("points-only", [planted_scene(n_pts=40, n_segs=0, n_l3d=0, seed=11)], ("empty_type", 1))
+    add("lines-only", [planted_scene(n_pts=0, n_segs=30, n_l3d=20, seed=12)], ("empty_type", 0))
+    add("three-points", [planted_scene(n_pts=3, n_segs=0, n_l3d=0, outliers=0, seed=13)], "all_skipped")
+    add("three-lines", [planted_scene(n_pts=0, n_segs=3, n_l3d=3, outliers=0, seed=14)], "all_skipped")
+    add("no-pose", [_with_pose(planted_scene(n_pts=0, n_segs=3, n_l3d=1, outliers=0, seed=15))], "no_pose", max_num_iterations=150)
+    add("all-wrong", [planted_scene(n_pts=12, n_segs=8, n_l3d=8, outliers=1.0, seed=16)], "ran", max_num_iterations=200)
+    sc = planted_scene(n_pts=0, n_segs=12, n_l3d=12, seed=17)
+    sc["l2ds"][ZERO_SEGMENT, 1] = sc["l2ds"][ZERO_SEGMENT, 0]
+    add("zero-segment", [sc], "zero_segment", cfg=loc_cfg(flags=(False, False, False, True)))
+    add("groups-of-three", [planted_scene(n_pts=10, n_segs=30, n_l3d=10, seed=18)], "lo")
+    add("short-run", [planted_scene(seed=3)], "lo_after", cfg=loc_cfg(min_num_iterations=5), max_num_iterations=30)
+    add("no-final-lsq", [planted_scene(seed=1)], "no_final", cfg=loc_cfg(final_least_squares=False))
+    add("no-lo-steps", [planted_scene(seed=1)], "lo", num_lo_steps=0)
+    add("unequal-thresholds", [planted_scene(seed=1)], "lo", cfg=_ransac(loc_cfg(), thres_point=4.0, thres_line=12.0, weight_line=2.0))
+    add("trace-cap-7", [planted_scene(seed=1), planted_scene(n_pts=20, n_segs=12, n_l3d=8, seed=21)], "trace_cap", trace_cap=7)
+    add("all-rejected", [_with_pose(planted_scene(n_pts=1, n_segs=1, n_l3d=1, seed=9)),
+                         _with_pose(planted_scene(n_pts=2, n_segs=0, n_l3d=0, seed=10))], ("rejected", (0, 1)))
+    add("poll-1", [planted_scene(seed=1)], "lo", poll_interval=1)
+    add("poll-9", [planted_scene(seed=1)], "lo", poll_interval=9)
+    add("campose", [_with_pose(planted_scene(n_pts=1, n_segs=1, n_l3d=1, seed=9)), _with_pose(planted_scene(n_pts=20, n_segs=12, n_l3d=8, seed=22))],
+        ("rejected", (0,)))
+    return out
+
+
+def case_property(case, res):
+    """what a case is there for, on the result dict of estimators.hybrid_arrays (twin or device); -> a line for the log"""
+    show = case["show"]
+    key, arg = show if isinstance(show, tuple) else (show, None)
+    Q = len(case["scenes"])
+    ist, dst = res["istats"], res["dstats"]
+    assert np.isfinite(res["qvec"]).all() and np.isfinite(res["tvec"]).all() and np.isfinite(dst).all(), case["name"]
+    rec = []
+    if case["trace_cap"] >= 400:
+        assert (ist[:, 11] <= case["trace_cap"]).all(), (case["name"], "the trace buffer is too short for this case")
+        rec = [res["trace"][q][:ist[q][11]] for q in range(Q)]
+    its = [t[t[:, 0] == 0] for t in rec]
+    los = [t[t[:, 0] == 1] for t in rec]
+    fin = [t[t[:, 0] == 2] for t in rec]
+    ran = [bool(ist[q][10]) for q in range(Q)]
+    if key != "rejected":
+        assert all(ran), case["name"]
+    if key == "lo":
+        assert len(los[0]) >= 1 and ist[0][7] == len(los[0])
+    elif key == "only_solver":
+        assert [int(ist[0][1 + s]) for s in range(4) if s != arg] == [0, 0, 0] and ist[0][1 + arg] > 0
+    elif key == "empty_type":
+        assert dst[0][1 + arg] == 0.0 and dst[0][2 - arg] > 0.0 and ist[0][8 + arg] == 0
+    elif key == "all_skipped":
+        steps = case["fields"].get("num_lo_steps", 10)
+        assert len(los[0]) >= 1 and all(int(r[5]) == 3 and int(r[11]) == steps for r in los[0])
+    elif key == "no_pose":
+        assert ist[0][5] == 0 and ist[0][7] == 0 and len(los[0]) == 0 and not its[0][:, 3].any()
+        assert ist[0][0] == case["fields"]["max_num_iterations"]
+        assert np.array_equal(res["qvec"][0], eo.normalise_q(START[0])) and np.array_equal(res["tvec"][0], START[1])
+    elif key == "zero_segment":
+        seen = 0
+        for r in its[0]:  # a sample with the segment of zero length has no pose
+            rng = eo.Rng(case["seed"], 0, int(r[1]), 0)
+            rng.unit()
+            if ZERO_SEGMENT in eo.sample_picks(rng, 3, len(case["scenes"][0]["l2ds"])):
+                seen += 1
+                assert r[3] == 0
+        assert seen >= 1
+    elif key == "lo_after":
+        t = rec[0]
+        assert len(los[0]) == 1 and t[-2, 0] == 1 and t[-3, 0] == 0 and ist[0][0] == case["fields"]["max_num_iterations"]
+    elif key == "no_final":
+        assert fin[0][0][2] == 0.0 and fin[0][0][3] == 0.0
+    elif key == "trace_cap":
+        assert (ist[:, 11] > case["trace_cap"]).all()
+    elif key == "rejected":
+        for q in range(Q):
+            assert ran[q] == (q not in arg)
+            if q in arg:
+                assert not ist[q][:6].any() and ist[q][6] == -1 and not ist[q][7:].any()  # no iteration, no solver, no record
+                assert np.array_equal(res["qvec"][q], eo.normalise_q(START[0])) and np.array_equal(res["tvec"][q], START[1])
+    return (f"{case['name']}: iterations {ist[:, 0].tolist()}, LOs {ist[:, 7].tolist()}, "
+            f"skipped LO steps {[int(l[:, 11].sum()) for l in los]}, inliers {ist[:, 5].tolist()}")

@@ -1,6 +1,8 @@
 """The minimal pose solvers (limap_amd.estimators) on the host, without a GPU: the host twin
 (lt_fn_est_minimal_host) on planted poses and against the NumPy restatement of tests/est_oracle.py, the degenerate
-samples, determinism, and the Python surface."""
+samples, determinism, and the Python surface; the hybrid loop's twin (lt_fn_est_host): its decisions replayed, its
+numbers replayed bit for bit (every iteration record's models and score, the statistics of the returned pose, the final
+least squares through the public refinement), and the device's configuration matrix on the twin first."""
 import numpy as np
 import pytest
 
@@ -221,11 +223,14 @@ from limap_amd import _capi
 THR2 = 100.0
 
 
-def run_twin(scenes, cfg=None, seed=1, trace_cap=400, threads=4, **fields):
-    """the twin on scenes (est_scenes.planted_scene) -> hybrid_arrays' dict; fields: lt_est_config members to set"""
+def run_twin(scenes, cfg=None, seed=1, trace_cap=400, threads=4, loc=None, **fields):
+    """the twin on scenes (est_scenes.planted_scene) -> hybrid_arrays' dict; fields: lt_est_config members to set, loc:
+    members of its loc block"""
     st = est._hybrid_options(cfg or es.loc_cfg(), None, seed)._struct()
     for k, v in fields.items():
         setattr(st, k, v)
+    for k, v in (loc or {}).items():
+        setattr(st.loc, k, v)
     return est.hybrid_arrays(est._query_arrays([es.query_of(s) for s in scenes]), st, host_threads=threads, trace_cap=trace_cap), st
 
 
@@ -527,3 +532,166 @@ def test_the_runners_call_with_the_default_localization_block():
     assert pose2.tvec.tobytes() == final_pose.tvec.tobytes() and st2.inlier_indices == ransac_stats.inlier_indices
     opts.random = True
     assert opts._struct().random_seed != opts._struct().random_seed
+
+
+# ---- 9. the twin's numbers: every record's values, the statistics, the final least squares ----
+def numeric_cases():
+    d = es.planted_scene
+    return {
+        "default": dict(scenes=[d(seed=1)], cfg=es.loc_cfg()),
+        "3DLineLineDist2": dict(scenes=[d(seed=2)], cfg=es.loc_cfg(cost="3DLineLineDist2", thres=0.1)),
+        "lines-only": dict(scenes=[d(n_pts=0, n_segs=30, n_l3d=20, seed=12)], cfg=es.loc_cfg()),
+        "round-size-1": dict(scenes=[d(seed=3)], cfg=es.loc_cfg(final_least_squares=False), fields=dict(round_size=1)),
+        "two-queries": dict(scenes=[d(n_pts=20, n_segs=12, n_l3d=8, seed=20), d(n_pts=25, n_segs=16, n_l3d=8, seed=21)], cfg=es.loc_cfg()),
+        "points-only": dict(scenes=[d(n_pts=40, n_segs=0, n_l3d=0, seed=11)], cfg=es.loc_cfg()),
+        # three pixels of noise: squared errors on both sides of each threshold, so the two cannot be exchanged unseen
+        "unequal-thresholds": dict(scenes=[d(noise=3.0, seed=1)], cfg=es._ransac(es.loc_cfg(), thres_point=4.0, thres_line=12.0, weight_line=2.0)),
+        "groups-of-three": dict(scenes=[d(n_pts=50, n_segs=45, n_l3d=15, seed=5)], cfg=es.loc_cfg()),
+    }
+
+
+REPLAYED = ["default", "3DLineLineDist2", "lines-only", "round-size-1", "two-queries"]
+_NUMERIC = {}
+
+
+def numeric(name, **over):
+    """a numeric case with the twin's result and the configuration it ran under, computed once"""
+    key = (name, tuple(sorted(over.items())))
+    if key not in _NUMERIC:
+        case = numeric_cases()[name]
+        cfg = dict(case["cfg"], ransac=dict(case["cfg"]["ransac"], **over))
+        res, st = run_twin(case["scenes"], cfg=cfg, trace_cap=600, **case.get("fields", {}))
+        assert (res["istats"][:, 11] <= 600).all()
+        _NUMERIC[key] = (dict(case, cfg=cfg), res, st)
+    return _NUMERIC[key]
+
+
+def score_at(sc, cfg, st, poses):
+    """hl.score_poses on the host under the estimator's thresholds, weights and cheirality bounds"""
+    return hl.score_poses(cfg["line_cost_func"], sc["l3ds"], sc["l3d_ids"], sc["l2ds"], sc["p3ds"], sc["p2ds"], sc["camera"],
+                          np.asarray(poses, float).reshape(-1, 7), cheirality_min_depth=st.cheirality_min_depth,
+                          cheirality_overlap_pixels=st.cheirality_overlap_pixels, thresholds=tuple(st.squared_inlier_thresholds),
+                          weights=tuple(st.data_type_weights), host=True)
+
+
+@pytest.mark.parametrize("name", REPLAYED)
+def test_every_iteration_record_replays_numerically(name):
+    """The values of the trace, not only its decisions: the restated draws (est_oracle.sample_picks) and sample
+    (est_oracle.loop_sample) of every iteration record, solved by the twin's minimal solver and scored by the host
+    scoring, give the record's number of models and its best local score, with == on the doubles."""
+    case, res, st = numeric(name)
+    for q, sc in enumerate(case["scenes"]):
+        tr = res["trace"][q][:res["istats"][q][11]]
+        it_rec = tr[tr[:, 0] == 0]
+        n_pts, n_lines = len(sc["p3ds"]), len(sc["l2ds"])
+        by_solver = {s: [] for s in range(4)}
+        for n, r in enumerate(it_rec):
+            solver = int(r[2])
+            rng = eo.Rng(st.random_seed, q, int(r[1]), 0)
+            rng.unit()  # the solver's draw
+            pp = eo.sample_picks(rng, 3 - solver, n_pts)
+            pl = eo.sample_picks(rng, solver, n_lines)
+            assert len(set(pp)) == len(pp) and len(set(pl)) == len(pl), (name, n)
+            assert all(0 <= i < n_pts for i in pp) and all(0 <= i < n_lines for i in pl), (name, n)
+            by_solver[solver].append((n, eo.loop_sample(sc, sc["camera"], solver, pp, pl)))
+        counts = np.zeros(len(it_rec), int)
+        best = np.full(len(it_rec), np.inf)
+        for solver, items in by_solver.items():
+            if not items:
+                continue
+            arrays = [np.array([s[k] for _, s in items]) if items[0][1][k].size else None for k in range(5)]
+            poses, cnt = est.minimal_solver(solver, *arrays, host=True)
+            flat = [(n, poses[i, j]) for i, (n, _) in enumerate(items) for j in range(int(cnt[i]))]
+            for i, (n, _) in enumerate(items):
+                counts[n] = cnt[i]
+            if flat:
+                scores = score_at(sc, case["cfg"], st, np.array([p for _, p in flat]))["scores"]
+                for (n, _), s in zip(flat, scores):
+                    best[n] = min(best[n], float(s))
+        has = counts > 0
+        bad = np.flatnonzero(counts != it_rec[:, 3].astype(int))
+        assert not len(bad), (name, q, "n_models", bad[:5])
+        bad = np.flatnonzero(best[has] != it_rec[has, 4])
+        assert not len(bad), (name, q, "best_local", bad[:5], best[has][bad[:5]], it_rec[has, 4][bad[:5]])
+        print(f"{name}, query {q}: {len(it_rec)} iteration records checked, {int(has.sum())} with poses")
+        assert has.sum() >= 10
+
+
+@pytest.mark.parametrize("name", sorted(numeric_cases()))
+def test_the_returned_statistics_belong_to_the_returned_pose(name):
+    case, res, st = numeric(name)
+    thr2 = tuple(st.squared_inlier_thresholds)
+    for q, sc in enumerate(case["scenes"]):
+        s = res["stats"][q]
+        r = score_at(sc, case["cfg"], st, np.concatenate([res["qvec"][q], res["tvec"][q]]))
+        n_pts, n_lines = len(sc["p3ds"]), len(sc["l2ds"])
+        inl = [np.flatnonzero(r["residuals"][0][:n_pts] < thr2[0]).tolist(), np.flatnonzero(r["residuals"][0][n_pts:] < thr2[1]).tolist()]
+        assert r["scores"][0] == s.best_model_score, (name, q)
+        assert inl == s.inlier_indices, (name, q)
+        assert s.inlier_ratios == [len(inl[0]) / n_pts if n_pts else 0.0, len(inl[1]) / n_lines if n_lines else 0.0], (name, q)
+        assert s.best_num_inliers == len(inl[0]) + len(inl[1]) > 0, (name, q)
+        assert r["inliers"][0].tolist() == [len(inl[0]), len(inl[1])]
+
+
+@pytest.mark.parametrize("name", ["default", "3DLineLineDist2", "groups-of-three"])
+def test_the_final_least_squares_is_the_public_refinement_of_the_inliers(name):
+    """final_least_squares_: pose A and its inliers from a run without it, refined by solve_jointloc_batch over exactly
+    those inliers and passed through eh_refine's round trip (est_oracle.pose_round_trip), is bit for bit the pose the
+    final record of the run with it implies: its score is the record's, and where the record says applied it is the
+    returned pose.  Bit equality held on all three scenes; the fallback of 2^-50 on qvec was not needed."""
+    case, on, st = numeric(name, final_least_squares=True)
+    _, off, _ = numeric(name, final_least_squares=False)
+    sc, cfg = case["scenes"][0], case["cfg"]
+    A, inl_p, inl_l = (off["qvec"][0], off["tvec"][0]), *off["stats"][0].inlier_indices
+    lc = est._hybrid_options(cfg, None, 1).lineloc_config
+    out = hl.solve_jointloc_batch(cfg["line_cost_func"], dict(weight_line=lc.weight_line, weight_point=lc.weight_point,
+                                                              loss_function=lc.loss_function),
+                                  [dict(l3ds=sc["l3ds"], l3d_ids=sc["l3d_ids"][inl_l], l2ds=sc["l2ds"][inl_l], p3ds=sc["p3ds"][inl_p],
+                                        p2ds=sc["p2ds"][inl_p], K=sc["camera"], qvec=A[0], tvec=A[1])], host=True)
+    usable = int(out["codes"][0]) <= 2  # IsSolutionUsable; else the pose is kept
+    want = eo.pose_round_trip(out["qvec"][0], out["tvec"][0]) if usable else A
+    tr = on["trace"][0][:on["istats"][0][11]]
+    fin = tr[tr[:, 0] == 2][0]
+    assert fin[2] == 1.0 and usable
+    assert score_at(sc, cfg, st, np.concatenate(want))["scores"][0] == fin[4], name
+    got = (on["qvec"][0], on["tvec"][0])
+    print(f"{name}: applied {fin[3]}, refined score {fin[4]!r}, score without {off['dstats'][0][0]!r}, code {out['codes'][0]}")
+    for a, b in zip(got, want if fin[3] == 1.0 else A):
+        assert a.tobytes() == np.asarray(b, float).tobytes(), (name, a, b)
+
+
+# ---- 10. the device's configuration matrix on the twin first ----
+LOOP_CASES = es.loop_cases()
+
+
+@pytest.mark.parametrize("case", LOOP_CASES, ids=[c["name"] for c in LOOP_CASES])
+def test_the_twin_runs_the_device_matrix(case):
+    """every case of tests/test_gpu_est.py's matrix on the twin: finite poses, the decisions replay, and the property
+    the case is there for -- the device is never the first to run an input"""
+    how = dict(cfg=case["cfg"], seed=case["seed"], loc=case["loc"], **case["fields"])
+    full, st = twin_with_sizes(case["scenes"], trace_cap=max(400, case["trace_cap"]), **how)
+    assert (full["istats"][:, 11] <= 400).all()
+    for q in range(len(case["scenes"])):
+        if full["istats"][q][10]:
+            replay(full, st, q)
+    res = full if case["trace_cap"] >= 400 else run_twin(case["scenes"], trace_cap=case["trace_cap"], **how)[0]
+    print(es.case_property(case, res))
+    if res is not full:  # a short trace buffer holds the first records, and nothing else changes
+        cap = case["trace_cap"]
+        for k in ("qvec", "tvec", "dstats", "istats", "inliers"):
+            assert res[k].tobytes() == full[k].tobytes(), k
+        for q in range(len(case["scenes"])):
+            assert res["trace"][q].tobytes() == full["trace"][q][:cap].tobytes()
+
+
+def test_the_matrix_reaches_the_refinement_configuration():
+    """the weight, the loss and the block weights of a case arrive in the refinements: the four (weight, loss) pairs of
+    a cost end at four different poses, and the struct holds what the case set"""
+    for cost, _ in es.LOOP_COSTS:
+        poses = set()
+        for case in (c for c in LOOP_CASES if c["name"].startswith(cost + "-w")):
+            res, st = run_twin(case["scenes"], cfg=case["cfg"], seed=case["seed"], loc=case["loc"], **case["fields"])
+            assert all(getattr(st.loc, k) == v for k, v in case["loc"].items()), case["name"]
+            assert st.loc.cost_function == hl.get_lineloc_cost_func(cost)
+            poses.add(res["qvec"][0].tobytes() + res["tvec"][0].tobytes())
+        assert len(poses) == len(es.LOSS_PAIRS), cost

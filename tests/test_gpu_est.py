@@ -1,7 +1,9 @@
 """-m gpu: the minimal pose solvers on the device (k_est_minimal of lt_kernels_est.hip) equal the host twin
 (lt_fn_est_minimal_host) bit for bit -- every pose, every count -- at batch sizes around the block width, on the
 degenerate samples, and from run to run; the hybrid loop (lt_est_solve: k_est_draw, k_est_score, k_est_replay) equals
-lt_fn_est_host bit for bit on poses, scores, inlier lists, every statistic and the trace."""
+lt_fn_est_host bit for bit on poses, scores, inlier lists, every statistic and the trace, at the
+defaults and over the configuration matrix of est_scenes.loop_cases(): every cost, weight and loss of the refinement on
+the shared lane group, and every path of the loop."""
 import numpy as np
 import pytest
 
@@ -72,11 +74,13 @@ def test_repeated_runs_and_an_empty_batch(ctx):
 LOOP_KEYS = ("qvec", "tvec", "dstats", "istats", "inliers", "trace")
 
 
-def loop_both(ctx, scenes, cfg=None, seed=3, trace_cap=300, **fields):
+def loop_both(ctx, scenes, cfg=None, seed=3, trace_cap=300, loc=None, **fields):
     csr = est._query_arrays([es.query_of(s) for s in scenes])
     st = est._hybrid_options(cfg or es.loc_cfg(), None, seed)._struct()
     for k, v in fields.items():
         setattr(st, k, v)
+    for k, v in (loc or {}).items():  # members of the refinement's block: cost_function, weight_function, loss, ...
+        setattr(st.loc, k, v)
     return est.hybrid_arrays(csr, st, ctx=ctx, trace_cap=trace_cap), est.hybrid_arrays(csr, st, host_threads=8, trace_cap=trace_cap)
 
 
@@ -150,3 +154,57 @@ def test_loop_repeated_runs_and_the_public_call(ctx):
                                                   host=True)
     assert pose.qvec.tobytes() == hpose.qvec.tobytes() and stats.inlier_indices == hstats.inlier_indices
     assert eo.pose_error(pose.qvec, pose.tvec, sc["R"], sc["t"]) < 0.05
+
+
+# ---- the configuration matrix (est_scenes.loop_cases; the twin runs it in test_est_host.py) ----
+LOOP_CASES = es.loop_cases()
+
+
+def case_both(ctx, case, **over):
+    how = dict(cfg=case["cfg"], seed=case["seed"], trace_cap=case["trace_cap"], loc=case["loc"], **case["fields"])
+    how.update(over)
+    return loop_both(ctx, case["scenes"], **how)
+
+
+@pytest.mark.parametrize("case", LOOP_CASES, ids=[c["name"] for c in LOOP_CASES])
+def test_loop_configuration_matrix(ctx, case):
+    """every cost, weight and loss on the shared lane group, and every path of the loop, on the device: all outputs and
+    the trace equal the twin's bits, and the case shows what it is there for"""
+    dev, host = case_both(ctx, case)
+    loop_same(dev, host, case["name"])
+    print(es.case_property(case, dev))
+    if case["name"] == "all-rejected":  # no query runs: no round is enqueued
+        assert dev["timers"]["rounds"] == 0
+    else:
+        assert dev["timers"]["rounds"] >= 1
+
+
+def test_loop_trace_buffers_shorter_than_the_records(ctx):
+    case = next(c for c in LOOP_CASES if c["name"] == "trace-cap-7")
+    short, _ = case_both(ctx, case)
+    _, full = case_both(ctx, case, trace_cap=400)
+    assert (short["istats"][:, 11] > 7).all() and short["trace"].shape == (2, 7, est.TRACE_DOUBLES)
+    for q in range(2):  # the first 7 records of each query, in its own region
+        assert short["trace"][q].tobytes() == full["trace"][q][:7].tobytes(), q
+        assert short["trace"][q][:, 0].tolist() == [0.0] * 7 and short["trace"][q][:, 1].tolist() == list(range(7))
+    assert short["trace"][0].tobytes() != short["trace"][1].tobytes()
+    for k in LOOP_KEYS[:-1]:
+        assert short[k].tobytes() == full[k].tobytes(), k
+    # no trace at all, through hybrid_arrays directly
+    csr = est._query_arrays([es.query_of(s) for s in case["scenes"]])
+    st = est._hybrid_options(case["cfg"], None, case["seed"])._struct()
+    none = est.hybrid_arrays(csr, st, ctx=ctx, trace_cap=0)
+    assert none["trace"] is None and not none["istats"][:, 11].any()
+    for k in ("qvec", "tvec", "dstats", "inliers"):
+        assert none[k].tobytes() == full[k].tobytes(), k
+    assert none["istats"][:, :11].tobytes() == full["istats"][:, :11].tobytes()
+
+
+def test_loop_poll_intervals_give_identical_bits(ctx):
+    """how many rounds the host enqueues between two looks at the count of finished queries changes no bit on the device"""
+    base = loop_both(ctx, [es.planted_scene(seed=1)], trace_cap=400)[0]  # poll_interval 4; 225 iterations: four rounds of 64
+    assert base["stats"][0].num_iterations_total > 192 and base["timers"]["rounds"] % 4 == 0
+    for n in (1, 9):
+        dev, _ = case_both(ctx, next(c for c in LOOP_CASES if c["name"] == f"poll-{n}"))
+        loop_same(dev, base, f"poll_interval {n}")
+        assert dev["timers"]["rounds"] % n == 0 and dev["timers"]["rounds"] >= 4  # whole polls, and at least the four rounds

@@ -4,8 +4,9 @@
 // The cases: planted poses of every kind at 1, 63, 64, 65 and 257 samples with the planted pose looked for among the
 // results; 1 against 4 threads; the degenerate samples (identical correspondences, collinear points, parallel lines,
 // zero vectors, a half turn); the refusals; the hybrid loop (lt_fn_est_host) on planted queries of unequal size with one
-// that VerifyData rejects, with the trace, at round sizes 1, 64 and 100, 1 against 3 threads, and its refusals.  Every
-// array is exactly as long as the call may read or write.
+// that VerifyData rejects, with the trace, at round sizes 1, 64 and 100, 1 against 3 threads, a points-only, a lines-only
+// and a three-point query (in one batch and alone), E3DLineLineDist2 with the Cauchy loss, and its refusals.  Every
+// array is exactly as long as the call may read or write; a call without data of a kind passes null for it.
 #include "host_asan.h"
 
 #include <cmath>
@@ -123,6 +124,60 @@ bool all_finite(const std::vector<double> &v) {
   return true;
 }
 
+// planted queries of the hybrid loop in CSR form: every third point match and every fourth segment's start are wrong,
+// two segments per 3D line; every array is exactly as long as its offsets say
+struct Queries {
+  std::vector<double> k, q, t, p3, p2, l3, sg;
+  std::vector<int64_t> po{0}, lo{0}, so{0};
+  std::vector<int32_t> ids;
+  int64_t n() const { return (int64_t)po.size() - 1; }
+  int64_t N() const { return po.back() + so.back(); }
+};
+Queries make_queries(const std::vector<int> &n_pts, const std::vector<int> &n_seg, unsigned seed) {
+  Queries Q;
+  unsigned st = seed;
+  for (size_t qi = 0; qi < n_pts.size(); ++qi) {
+    const Pose P = random_pose(st, false);
+    const double kk[4] = {600, 590, 400, 300}, qq[4] = {1, 0, 0, 0}, tt[3] = {0, 0, 0};
+    Q.k.insert(Q.k.end(), kk, kk + 4); Q.q.insert(Q.q.end(), qq, qq + 4); Q.t.insert(Q.t.end(), tt, tt + 3);
+    auto pix = [&](V3 c, double *o) { o[0] = kk[0] * c.v[0] / c.v[2] + kk[2]; o[1] = kk[1] * c.v[1] / c.v[2] + kk[3]; };
+    for (int i = 0; i < n_pts[qi]; ++i) {
+      const V3 c = cam_point(st), w = to_world(P, c);
+      double o[2];
+      pix(i % 3 == 0 && n_pts[qi] != 3 ? cam_point(st) : c, o);  // every third match is wrong, but for a query of exactly three
+      Q.p3.insert(Q.p3.end(), w.v, w.v + 3); Q.p2.insert(Q.p2.end(), o, o + 2);
+    }
+    const int n_l3 = (n_seg[qi] + 1) / 2;  // two segments per 3D line
+    std::vector<V3> ea, eb;
+    for (int i = 0; i < n_l3; ++i) {
+      V3 a = cam_point(st), b = cam_point(st);
+      ea.push_back(a); eb.push_back(b);
+      const V3 A = to_world(P, a), B = to_world(P, b);
+      Q.l3.insert(Q.l3.end(), A.v, A.v + 3); Q.l3.insert(Q.l3.end(), B.v, B.v + 3);
+    }
+    for (int i = 0; i < n_seg[qi]; ++i) {
+      double o[4];
+      pix(i % 4 == 0 ? cam_point(st) : ea[(size_t)(i % n_l3)], o);
+      pix(eb[(size_t)(i % n_l3)], o + 2);
+      Q.sg.insert(Q.sg.end(), o, o + 4);
+      Q.ids.push_back(i % n_l3);
+    }
+    Q.po.push_back((int64_t)Q.p3.size() / 3); Q.lo.push_back((int64_t)Q.l3.size() / 6); Q.so.push_back((int64_t)Q.sg.size() / 4);
+  }
+  return Q;
+}
+// lt_fn_est_host on Q with exact-size outputs; an array without data is a null pointer
+int run_loop(const Queries &Q, const lt_est_config &cfg, int64_t cap, int threads, std::vector<double> &pose, std::vector<double> &ds,
+             std::vector<int32_t> &is, std::vector<int32_t> &inl, std::vector<double> &tr) {
+  const size_t n = (size_t)Q.n();
+  pose.assign(7 * n, -1.0); ds.assign(3 * n, -1.0); is.assign(12 * n, -1);
+  inl.assign((size_t)Q.N(), -1); tr.assign(n * (size_t)cap * LT_EST_TRACE_DOUBLES, -1.0);
+  auto dp = [](const std::vector<double> &v) { return v.empty() ? nullptr : v.data(); };
+  return lt_fn_est_host(Q.n(), Q.k.data(), Q.q.data(), Q.t.data(), Q.po.data(), dp(Q.p3), dp(Q.p2), Q.lo.data(), dp(Q.l3), Q.so.data(),
+                        Q.ids.empty() ? nullptr : Q.ids.data(), dp(Q.sg), &cfg, cap, threads, pose.data(), ds.data(), is.data(),
+                        inl.empty() ? nullptr : inl.data(), tr.empty() ? nullptr : tr.data());
+}
+
 }  // namespace
 
 int main() {
@@ -176,39 +231,10 @@ int main() {
   }
   // the hybrid loop
   {
-    const int n_pts[3] = {14, 1, 30}, n_seg[3] = {9, 1, 40};
-    std::vector<double> k, q, t, p3, p2, l3, sg;
-    std::vector<int64_t> po{0}, lo{0}, so{0};
-    std::vector<int32_t> ids;
-    unsigned st = 99u;
-    for (int qi = 0; qi < 3; ++qi) {
-      const Pose P = random_pose(st, false);
-      const double kk[4] = {600, 590, 400, 300}, qq[4] = {1, 0, 0, 0}, tt[3] = {0, 0, 0};
-      k.insert(k.end(), kk, kk + 4); q.insert(q.end(), qq, qq + 4); t.insert(t.end(), tt, tt + 3);
-      auto pix = [&](V3 c, double *o) { o[0] = kk[0] * c.v[0] / c.v[2] + kk[2]; o[1] = kk[1] * c.v[1] / c.v[2] + kk[3]; };
-      for (int i = 0; i < n_pts[qi]; ++i) {
-        const V3 c = cam_point(st), w = to_world(P, c);
-        double o[2];
-        pix(i % 3 == 0 ? cam_point(st) : c, o);  // every third match is wrong
-        p3.insert(p3.end(), w.v, w.v + 3); p2.insert(p2.end(), o, o + 2);
-      }
-      const int n_l3 = (n_seg[qi] + 1) / 2;  // two segments per 3D line
-      std::vector<V3> ea, eb;
-      for (int i = 0; i < n_l3; ++i) {
-        V3 a = cam_point(st), b = cam_point(st);
-        ea.push_back(a); eb.push_back(b);
-        const V3 A = to_world(P, a), B = to_world(P, b);
-        l3.insert(l3.end(), A.v, A.v + 3); l3.insert(l3.end(), B.v, B.v + 3);
-      }
-      for (int i = 0; i < n_seg[qi]; ++i) {
-        double o[4];
-        pix(i % 4 == 0 ? cam_point(st) : ea[(size_t)(i % n_l3)], o);
-        pix(eb[(size_t)(i % n_l3)], o + 2);
-        sg.insert(sg.end(), o, o + 4);
-        ids.push_back(i % n_l3);
-      }
-      po.push_back((int64_t)p3.size() / 3); lo.push_back((int64_t)l3.size() / 6); so.push_back((int64_t)sg.size() / 4);
-    }
+    const Queries QS = make_queries({14, 1, 30}, {9, 1, 40}, 99u);
+    const std::vector<double> &k = QS.k, &q = QS.q, &t = QS.t, &p3 = QS.p3, &p2 = QS.p2, &l3 = QS.l3, &sg = QS.sg;
+    const std::vector<int64_t> &po = QS.po, &lo = QS.lo, &so = QS.so;
+    std::vector<int32_t> ids = QS.ids;
     lt_est_config cfg;
     lt_est_config_default(&cfg);
     EXPECT(cfg.round_size == 64 && cfg.lo_starting_iterations == 50 && cfg.num_lsq_iterations == 4);
@@ -230,6 +256,31 @@ int main() {
       }
     EXPECT(lt_fn_est_host(3, k.data(), q.data(), t.data(), po.data(), p3.data(), p2.data(), lo.data(), l3.data(), so.data(), ids.data(),
                           sg.data(), &cfg, 0, 2, nullptr, nullptr, nullptr, nullptr, nullptr) == LT_OK);
+    // a points-only, a lines-only and a three-point query in one batch: empty types, null arrays where a call has no
+    // data of a kind, local optimisations whose every step is skipped
+    {
+      cfg.round_size = 64;
+      std::vector<double> pose, ds, tr;
+      std::vector<int32_t> is, inl;
+      const Queries M = make_queries({24, 0, 3}, {0, 22, 0}, 7u);
+      EXPECT(run_loop(M, cfg, cap, 2, pose, ds, is, inl, tr) == LT_OK && all_finite(pose) && all_finite(ds));
+      for (int qi = 0; qi < 3; ++qi) EXPECT(is[(size_t)(12 * qi + 10)] == 1 && is[(size_t)(12 * qi)] >= 99);
+      EXPECT(ds[2] == 0.0 && ds[1] > 0.0 && is[9] == 0 && is[8] >= 8);                 // points only: no line ratio
+      EXPECT(ds[3 + 1] == 0.0 && ds[3 + 2] > 0.0 && is[12 + 8] == 0 && is[12 + 9] >= 8);  // lines only
+      EXPECT(is[24 + 5] == 3 && is[24 + 7] >= 1 && is[24 + 2] + is[24 + 3] + is[24 + 4] == 0);  // three points: p3p alone
+      for (int only : {0, 1}) {  // each of the two alone: the other type's arrays are null
+        const Queries S = only == 0 ? make_queries({24}, {0}, 8u) : make_queries({0}, {22}, 9u);
+        EXPECT(run_loop(S, cfg, cap, 1, pose, ds, is, inl, tr) == LT_OK && all_finite(pose) && is[10] == 1 && is[5] >= 8);
+      }
+      // a 3D cost with a robust loss in the refinements
+      lt_est_config c3 = cfg;
+      c3.loc.cost_function = 4;  // E3DLineLineDist2
+      c3.loc.loss = 3;           // CauchyLoss
+      c3.loc.loss_a = 0.05;
+      c3.squared_inlier_thresholds[0] = c3.squared_inlier_thresholds[1] = 0.01;
+      EXPECT(run_loop(QS, c3, cap, 2, pose, ds, is, inl, tr) == LT_OK && all_finite(pose) && is[10] == 1 && is[24 + 10] == 1);
+      EXPECT(is[7] >= 1 && is[24 + 7] >= 1 && is[5] >= 8 && is[24 + 5] >= 30);
+    }
     cfg.round_size = 0;
     EXPECT(lt_fn_est_host(3, k.data(), q.data(), t.data(), po.data(), p3.data(), p2.data(), lo.data(), l3.data(), so.data(), ids.data(),
                           sg.data(), &cfg, 0, 1, nullptr, nullptr, nullptr, nullptr, nullptr) == LT_ERR_ARGUMENT && has("round_size"));
