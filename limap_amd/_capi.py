@@ -1013,6 +1013,12 @@ class Context:
         self.chk(self.L.lt_get_timer_sums(self.h, ptr(out, C.c_double), C.byref(n), 1 if reset else 0))
         return dict(zip(self._TIMER_KEYS, out.tolist())), int(n.value)
 
+    def module_timers(self, getter, n):
+        """the n timer slots of a module's last call, from its `lt_*_get_timers` entry point named by `getter`"""
+        out = np.zeros(n)
+        self.chk(getattr(self.L, getter)(self.h, ptr(out, C.c_double)))
+        return out
+
     # --- free functions ---
     def fn_normal_direction(self, seg, cam):
         out = np.zeros(3)

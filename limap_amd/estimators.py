@@ -27,7 +27,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _capi
+from . import _capi, _native
 from . import hybrid_localization as _hl
 
 __all__ = ["SOLVER_KINDS", "minimal_solver", "minimal_inputs", "pl_estimate_absolute_pose", "pl_estimate_absolute_pose_batch",
@@ -86,17 +86,16 @@ def minimal_solver(kind, xs=None, Xs=None, ls=None, Cs=None, Vs=None, host=False
     p = _capi.ptr
     args = (k, n) + tuple(p(a, C.c_double) if a is not None and len(a) else None for a in arrs)
     outs = (p(poses, C.c_double), p(counts, C.c_int32))
-    ht = host_threads if host_threads is not None else (0 if host else None)
+    ht = _native.host_threads(host, host_threads)
     timers = None
     if ht is not None:
         if L.lt_fn_est_minimal_host(*args, int(ht), *outs) != 0:
-            raise ValueError("limap_amd.estimators: " + L.lt_fn_est_host_error().decode(errors="replace"))
+            _native.raise_host_error(L, "lt_fn_est_host_error", "limap_amd.estimators: ")
     else:
         ctx = ctx if ctx is not None else _context()
         ctx.chk(L.lt_est_minimal(ctx.h, *args))
         ctx.chk(L.lt_est_minimal_get(ctx.h, *outs))
-        tm = np.zeros(4)
-        ctx.chk(L.lt_est_minimal_get_timers(ctx.h, p(tm, C.c_double)))
+        tm = ctx.module_timers("lt_est_minimal_get_timers", 4)
         timers = dict(prepare_ms=float(tm[0]), kernel_ms=float(tm[1]), download_ms=float(tm[2]), solve_device_ms=float(tm[3]))
     if return_timers:
         return poses[:n], counts[:n], timers
@@ -250,13 +249,12 @@ def hybrid_arrays(csr, cfg_struct, host_threads=None, ctx=None, trace_cap=0):
     timers = None
     if host_threads is not None:
         if L.lt_fn_est_host(*args, int(host_threads), *outs) != 0:
-            raise ValueError("limap_amd.estimators: " + L.lt_fn_est_host_error().decode(errors="replace"))
+            _native.raise_host_error(L, "lt_fn_est_host_error", "limap_amd.estimators: ")
     else:
         ctx = ctx if ctx is not None else _context()
         ctx.chk(L.lt_est_solve(ctx.h, *args))
         ctx.chk(L.lt_est_get(ctx.h, *outs))
-        tm = np.zeros(8)
-        ctx.chk(L.lt_est_get_timers(ctx.h, p(tm)))
+        tm = ctx.module_timers("lt_est_get_timers", 8)
         timers = dict(prepare_ms=float(tm[0]), rounds_ms=float(tm[1]), download_ms=float(tm[2]), rounds=int(tm[3]),
                       rounds_device_ms=float(tm[4]))
     stats = []
@@ -268,16 +266,13 @@ def hybrid_arrays(csr, cfg_struct, host_threads=None, ctx=None, trace_cap=0):
                 trace=trace[:Q] if trace_cap else None, timers=timers)
 
 
-def _ht(host, host_threads):
-    return host_threads if host_threads is not None else (0 if host else None)
-
-
 def EstimateAbsolutePose_PointLine_Hybrid(l3ds, l3d_ids, l2ds, p3ds, p2ds, cam, options, campose=None, host=False,
                                           host_threads=None, trace_cap=0):
     """hybrid_pose_estimator.cc:14-42 -> (CameraPose, HybridRansacStatistics).  `campose` comes back where VerifyData
     finds no solver that can run (fewer than three correspondences, or every feasible solver switched off)."""
     res = hybrid_arrays(_query_arrays([dict(l3ds=l3ds, l3d_ids=l3d_ids, l2ds=l2ds, p3ds=p3ds, p2ds=p2ds, camera=cam,
-                                            campose=campose)]), options._struct(), _ht(host, host_threads), trace_cap=trace_cap)
+                                            campose=campose)]), options._struct(),
+                        _native.host_threads(host, host_threads), trace_cap=trace_cap)
     return _hl.CameraPose(res["qvec"][0], res["tvec"][0]), res["stats"][0]
 
 
@@ -346,6 +341,6 @@ def pl_estimate_absolute_pose_batch(cfg, queries, jointloc_cfg=None, host=False,
     set of launches -> list of (CameraPose, HybridRansacStatistics).  The draws of a query are keyed by its index."""
     if _method(cfg) is None:
         raise ValueError("limap_amd.estimators: the batch call is the hybrid estimator's (ransac.method: \"hybrid\")")
-    res = hybrid_arrays(_query_arrays(queries), _hybrid_options(cfg, jointloc_cfg, seed)._struct(), _ht(host, host_threads),
-                        trace_cap=trace_cap)
+    res = hybrid_arrays(_query_arrays(queries), _hybrid_options(cfg, jointloc_cfg, seed)._struct(),
+                        _native.host_threads(host, host_threads), trace_cap=trace_cap)
     return [(_hl.CameraPose(res["qvec"][n], res["tvec"][n]), res["stats"][n]) for n in range(len(queries))]

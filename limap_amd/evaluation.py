@@ -21,7 +21,7 @@ import struct
 
 import numpy as np
 
-from . import _capi
+from . import _capi, _native
 from .base import Line3d
 
 __all__ = ["PointCloudEvaluator", "RefLineEvaluator", "MeshEvaluator", "report_error_to_GT", "report_pc_recall_for_GT",
@@ -108,10 +108,7 @@ class _SampledEvaluator:
             pass
 
     def timers(self):
-        out = np.zeros(4)
-        ctx = self._ctx()
-        ctx.chk(ctx.L.lt_eval_get_timers(ctx.h, _p(out)))
-        return out
+        return self._ctx().module_timers("lt_eval_get_timers", 4)
 
     def ComputeDistPoints(self, points, chunk=None):
         """ComputeDistPoint for each row of an (M, 3) array"""
@@ -192,11 +189,8 @@ class PointCloudEvaluator(_SampledEvaluator):
         self._torch = None
         if points is None:
             raise ValueError("PointCloudEvaluator: an empty point cloud cannot be evaluated against")
-        try:
+        if _native.is_torch(points):
             import torch
-        except ImportError:  # pragma: no cover
-            torch = None
-        if torch is not None and isinstance(points, torch.Tensor):
             if points.dim() != 2 or points.shape[1] != 3 or points.dtype not in (torch.float32, torch.float64):
                 raise ValueError("PointCloudEvaluator: a tensor must be (N, 3) float32 or float64")
             if not points.is_contiguous():
@@ -205,12 +199,13 @@ class PointCloudEvaluator(_SampledEvaluator):
                 raise ValueError("PointCloudEvaluator: empty point cloud")
             if not bool(torch.isfinite(points).all()):
                 raise ValueError("PointCloudEvaluator: non-finite point coordinate")
-            if points.is_cuda:
+            # a GPU tensor is read in place, and the evaluator runs on the tensor's device: no device to refuse
+            if _native.check_device(points, host=False, device=None, who="PointCloudEvaluator", what="the tensor"):
                 self.device = points.device.index or 0
                 self._torch = points
                 self.points = None
             else:
-                self.points = points.detach().numpy().astype(np.float64).reshape(-1, 3)
+                self.points = _native.to_host(points).astype(np.float64).reshape(-1, 3)
         else:
             if isinstance(points, (list, tuple)):
                 arr = np.stack([np.asarray(p, np.float64).reshape(3) for p in points], 0) if len(points) else \
@@ -233,16 +228,12 @@ class PointCloudEvaluator(_SampledEvaluator):
         self._free()
         out = C.c_void_p()
         pp = None if perm is None else np.ascontiguousarray(perm, np.uint32)
-        if self._torch is not None:
-            import torch
-            t = self._torch
-            with torch.cuda.device(self.device):
-                torch.cuda.current_stream().synchronize()
-            ctx.chk(ctx.L.lt_pcd_build(ctx.h, C.c_void_p(t.data_ptr()), t.shape[0], 1 if t.dtype == torch.float64 else 0,
-                                       1, None if pp is None else pp.ctypes.data, C.byref(out)))
-        else:
-            ctx.chk(ctx.L.lt_pcd_build(ctx.h, self.points.ctypes.data, self.points.shape[0], 1, 0,
-                                       None if pp is None else pp.ctypes.data, C.byref(out)))
+        t = self._torch
+        src, is_f64 = (self.points, 1) if t is None else (t, int(str(t.dtype) == "torch.float64"))
+        if t is not None:
+            _native.wait_for_torch(self.device)
+        ctx.chk(ctx.L.lt_pcd_build(ctx.h, C.c_void_p(_native.address(src)), src.shape[0], is_f64, int(t is not None),
+                                   None if pp is None else pp.ctypes.data, C.byref(out)))
         self._handle = out
 
     def _index(self):

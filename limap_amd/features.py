@@ -20,7 +20,7 @@ import os
 
 import numpy as np
 
-from . import _capi
+from . import _capi, _native
 from . import base as _base
 
 __all__ = ["LinePatchExtractorOptions", "PatchInfo", "PatchInfo_f16", "PatchInfo_f32", "PatchInfo_f64",
@@ -81,41 +81,17 @@ def _dtype_code(dtype):
     return name, _DTYPES[name]
 
 
-def _is_torch(x):
-    return type(x).__module__.split(".")[0] == "torch"
-
-
 def _feature_map(feature, host, device):
-    """-> (lt_feature_map, (H, W, C), what keeps the memory alive, on_device)"""
-    on_device = 0
-    if _is_torch(feature):
-        import torch
-        names = {torch.float16: "float16", torch.float32: "float32", torch.float64: "float64"}
-        if feature.dtype not in names:
-            raise ValueError(f"features: a feature map must be float16, float32 or float64, got {feature.dtype}")
-        if feature.dim() != 3:
-            raise ValueError(f"features: a feature map must be (H, W, C), got shape {tuple(feature.shape)}")
-        if feature.is_cuda and not host:
-            if feature.device.index != device:
-                raise ValueError(f"features: the tensor lives on {feature.device}, the call runs on device {device}")
-            shape, strides, ptr, code = tuple(feature.shape), feature.stride(), feature.data_ptr(), _DTYPES[names[feature.dtype]]
-            on_device = 1
-        else:
-            feature = feature.detach().cpu().numpy()
-    if not on_device:
-        feature = np.asarray(feature)
-        if feature.dtype.name not in _DTYPES:
-            raise ValueError(f"features: a feature map must be float16, float32 or float64, got {feature.dtype}")
-        if feature.ndim != 3:
-            raise ValueError(f"features: a feature map must be (H, W, C), got shape {feature.shape}")
-        if any(s % feature.itemsize for s in feature.strides) or not feature.flags.aligned:
-            feature = np.ascontiguousarray(feature)
-        shape, strides = feature.shape, tuple(s // feature.itemsize for s in feature.strides)
-        ptr, code = feature.ctypes.data, _DTYPES[feature.dtype.name]
-    if min(shape) < 1:
-        raise ValueError(f"features: a feature map must have H, W, C >= 1, got shape {tuple(shape)}")
-    fm = _capi.LtFeatureMap(ptr, shape[0], shape[1], shape[2], strides[0], strides[1], strides[2], code, on_device)
-    return fm, tuple(int(s) for s in shape), feature, on_device
+    """-> (lt_feature_map, (H, W, C), what keeps the memory alive, on_device); any strides are read in place"""
+    f = _native.operand(feature, host=host, device=device, who="features", what="the tensor")
+    if f.dtype not in _DTYPES:
+        raise ValueError("features: a feature map must be float16, float32 or float64, got "
+                         f"{getattr(feature, 'dtype', f.dtype)}")
+    if f.ndim != 3:
+        raise ValueError(f"features: a feature map must be (H, W, C), got shape {f.shape}")
+    if min(f.shape) < 1:
+        raise ValueError(f"features: a feature map must have H, W, C >= 1, got shape {f.shape}")
+    return _capi.LtFeatureMap(f.address, *f.shape, *f.strides, _DTYPES[f.dtype], f.on_device), f.shape, f.keep, f.on_device
 
 
 def _lines4(line2ds):
@@ -125,10 +101,6 @@ def _lines4(line2ds):
     rows = [np.concatenate([np.asarray(l.start, np.float64).reshape(2), np.asarray(l.end, np.float64).reshape(2)])
             if hasattr(l, "start") else np.asarray(l, np.float64).reshape(4) for l in line2ds]
     return _capi.f64(rows).reshape(-1, 4)
-
-
-def _raise_host(L):
-    raise ValueError("features: " + L.lt_fn_patch_host_error().decode(errors="replace"))
 
 
 def _extract(options, line2ds, feature, host=False, dtype=None, device_out=False, device=0, max_chunk_bytes=0,
@@ -148,26 +120,23 @@ def _extract(options, line2ds, feature, host=False, dtype=None, device_out=False
     off = np.zeros(n + 1, np.int64)
     lp = _p(lines if n else np.zeros((1, 4)))
     if L.lt_fn_patch_geometry(C.byref(cfg), Cc, n, lp, _p(R), _p(tv), _p(hs, C.c_int32), _p(off, C.c_int64)) != 0:
-        _raise_host(L)
+        _native.raise_host_error(L, "lt_fn_patch_host_error", "features: ")
     total, pw = int(off[n]), cfg.range_perp + 1
     if host:
         flat = np.empty(max(total, 1), np.dtype(name))
         if L.lt_fn_patch_extract_host(C.byref(cfg), C.byref(fm), n, lp, code, flat.ctypes.data, int(n_threads)) != 0:
-            _raise_host(L)
+            _native.raise_host_error(L, "lt_fn_patch_host_error", "features: ")
     else:
         ctx = _context(device)
         if device_out:
             import torch
             flat = torch.empty(max(total, 8), dtype=getattr(torch, name), device=f"cuda:{device}")
-            out_ptr = flat.data_ptr()
         else:
             flat = np.empty(max(total, 1), np.dtype(name))
-            out_ptr = flat.ctypes.data
         if on_device or device_out:
-            import torch
-            torch.cuda.synchronize(device)  # the context's stream does not wait for torch's streams
-        ctx.chk(ctx.L.lt_patch_extract(ctx.h, C.byref(cfg), C.byref(fm), n, lp, code, out_ptr, 1 if device_out else 0,
-                                       int(max_chunk_bytes)))
+            _native.wait_for_torch(device)
+        ctx.chk(ctx.L.lt_patch_extract(ctx.h, C.byref(cfg), C.byref(fm), n, lp, code, _native.address(flat),
+                                       1 if device_out else 0, int(max_chunk_bytes)))
     del keep  # (held the map's memory until the call had returned)
     return [PatchInfo(flat[int(off[i]):int(off[i + 1])].reshape(int(hs[i]), pw, Cc), R[i].reshape(2, 2).copy(),
                       tv[i].copy(), (H, W)) for i in range(n)]
@@ -233,7 +202,7 @@ def ranges_from_arrays(line6, sup_off, sup_img, sup_seg4, pair_track, pair_img, 
     L = _capi.load_library()
     if L.lt_fn_patch_ranges(T, _p(line6), _p(sup_off, C.c_int64), _p(sup_img, C.c_int32), _p(sup_seg), n,
                             _p(pt, C.c_int32), _p(pi, C.c_int32), _p(cams), _p(out), _p(status, C.c_int32)) != 0:
-        _raise_host(L)
+        _native.raise_host_error(L, "lt_fn_patch_host_error", "features: ")
     return out[:n], status[:n]
 
 
@@ -291,9 +260,7 @@ def extract_line_patches(cfg, track, p_camviews, p_features, **kw):
 
 def write_patch(fname, patch, dtype="float16"):
     """extract_line_patches.py:5-15: np.savez with the keys array, R, tvec, img_hw"""
-    array = patch.array
-    if _is_torch(array):
-        array = array.detach().cpu().numpy()
+    array = _native.to_host(patch.array)
     if dtype == "float16":
         array = array.astype(np.float16)
     elif dtype == "float32":
@@ -371,7 +338,4 @@ def _patch_name(output_dir, track_id, img_id):
 
 def timers(device=0):
     """lt_patch_get_timers of the last device call as a dict (TIMER_KEYS)"""
-    out = np.zeros(8)
-    ctx = _context(device)
-    ctx.chk(ctx.L.lt_patch_get_timers(ctx.h, _p(out)))
-    return dict(zip(TIMER_KEYS, out.tolist()))
+    return dict(zip(TIMER_KEYS, _context(device).module_timers("lt_patch_get_timers", 8).tolist()))

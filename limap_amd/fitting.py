@@ -17,7 +17,7 @@ import math
 
 import numpy as np
 
-from . import _capi
+from . import _capi, _native
 from .base import Line3d
 
 STATUS_OK, STATUS_TOO_FEW_POINTS, STATUS_LOW_INLIER_RATIO, STATUS_SCAN_OUT_OF_RANGE = 0, 1, 2, 3
@@ -146,53 +146,23 @@ def estimate_seg3d(points, ransac_th=0.75, min_percentage_inliers=0.6):
 
 
 # ---- depth maps -----------------------------------------------------------------------------------------------------
-def _is_torch(x):
-    return type(x).__module__.split(".")[0] == "torch"
-
-
 def _map_of(depth, device=0):
     """(LtDepthMap, keep-alive) of a NumPy array or a torch tensor; integer maps become float64 (exact), like NumPy's
-    promotion in the reference; float16 is refused.  A GPU tensor must live on `device`, the context's device; it is
-    read in place on the context's stream, so the caller orders that read after torch's work (_sync_torch)."""
-    if _is_torch(depth):
-        import torch
-        if depth.dim() != 2:
-            raise ValueError(f"fitting: a depth map must be 2-D, got shape {tuple(depth.shape)}")
-        if depth.dtype == torch.float16 or depth.dtype == torch.bfloat16:
-            raise ValueError("fitting: float16 depth maps are not supported")
-        if depth.is_cuda and depth.device.index != device:
-            raise ValueError(f"fitting: a depth map on {depth.device} for a fit on cuda:{device}")
-        if depth.dtype not in (torch.float32, torch.float64):
-            depth = depth.to(torch.float64)
-        if depth.stride(1) != 1 or depth.stride(0) < depth.shape[1]:
-            depth = depth.contiguous()
-        on_dev = 1 if depth.is_cuda else 0
-        if not on_dev:
-            return _map_of(depth.numpy())
-        dm = _capi.LtDepthMap(C.c_void_p(depth.data_ptr()), depth.shape[0], depth.shape[1], depth.stride(0),
-                              0 if depth.dtype == torch.float32 else 1, 1)
-        return dm, depth
-    a = np.asarray(depth)
-    if a.ndim != 2:
-        raise ValueError(f"fitting: a depth map must be 2-D, got shape {a.shape}")
-    if a.dtype == np.float16:
+    promotion in the reference; float16 is refused.  A GPU tensor is read in place (_native.operand)."""
+    d = _native.operand(depth, host=False, device=device, who="fitting", what="a depth map")
+    if d.ndim != 2:
+        raise ValueError(f"fitting: a depth map must be 2-D, got shape {d.shape}")
+    if d.dtype in ("float16", "bfloat16"):
         raise ValueError("fitting: float16 depth maps are not supported")
-    if a.dtype not in (np.float32, np.float64):
-        if a.dtype.kind not in "iub":
-            raise ValueError(f"fitting: unsupported depth dtype {a.dtype}")
-        a = a.astype(np.float64)
-    if a.strides[1] != a.itemsize or a.strides[0] % a.itemsize:
-        a = np.ascontiguousarray(a)
-    dm = _capi.LtDepthMap(C.c_void_p(a.ctypes.data), a.shape[0], a.shape[1], a.strides[0] // a.itemsize,
-                          0 if a.dtype == np.float32 else 1, 0)
-    return dm, a
-
-
-def _sync_torch(device):
-    """the context's stream does not wait for torch's streams: a map a network has just written, and the conversions of
-    _map_of, must be finished before lt_fit_segs reads them"""
-    import torch
-    torch.cuda.synchronize(device)
+    if d.dtype not in ("float32", "float64"):
+        if not d.dtype.startswith(("int", "uint", "bool")):
+            raise ValueError(f"fitting: unsupported depth dtype {d.dtype}")
+        d = d.astype("float64")
+    if d.strides[1] != 1 or d.strides[0] < d.shape[1]:
+        d = d.contiguous()
+    dm = _capi.LtDepthMap(C.c_void_p(d.address), d.shape[0], d.shape[1], d.strides[0],
+                          0 if d.dtype == "float32" else 1, d.on_device)
+    return dm, d.keep
 
 
 def _shape_of(depth):
@@ -263,7 +233,6 @@ def _fit_chunks(ids, cams, seg_off, allsegs, map_of, nbytes_of, launch, max_chun
     G = int(seg_off[-1])
     seg = np.zeros((max(G, 1), 6)); status = np.zeros(max(G, 1), np.int32); stats = np.zeros((max(G, 1), 5), np.int32)
     timers = dict(device_ms=0.0, upload_ms=0.0, host_ms=0.0, attempts=0, chunks=0)
-    p = _capi.ptr
     ctx = None
     n = 0
     carry = None  # the map that did not fit into the last chunk: it opens the next one (a reader is not read twice)
@@ -286,11 +255,10 @@ def _fit_chunks(ids, cams, seg_off, allsegs, map_of, nbytes_of, launch, max_chun
             ctx = _capi.Context(device=device)
             ctx.init(ids, *cams, seg_off, allsegs)
         if on_dev:
-            _sync_torch(device)
+            _native.wait_for_torch(device)
         g0 = int(seg_off[n])
         launch(ctx, n, maps, seg[g0:], status[g0:], stats[g0:])
-        tm = np.zeros(4)
-        ctx.chk(ctx.L.lt_fit_get_timers(ctx.h, p(tm, C.c_double)))
+        tm = ctx.module_timers("lt_fit_get_timers", 4)
         timers["device_ms"] += tm[0]; timers["upload_ms"] += tm[1]; timers["host_ms"] += tm[2]
         timers["attempts"] = max(timers["attempts"], int(tm[3])); timers["chunks"] += 1
         del keep
@@ -355,36 +323,19 @@ def estimate_seg3d_from_depth(seg2d, depth, camview, ransac_th=0.75, min_percent
 def _scan_of(p3ds, img_hw, device=0):
     """(LtScanMap, keep-alive) of an (H, W, 3) NumPy array or torch tensor (a reader's read_p3ds()), img_hw the camera's
     (h, w).  float32 and float64 only (the reference's grid_sample takes float64; float32 is widened exactly); any
-    non-negative strides are read in place.  A GPU tensor must live on `device` (see _map_of)."""
-    if _is_torch(p3ds):
-        import torch
-        if p3ds.dim() != 3 or p3ds.shape[2] != 3:
-            raise ValueError(f"fitting: a scan must be (H, W, 3), got shape {tuple(p3ds.shape)}")
-        if p3ds.dtype not in (torch.float32, torch.float64):
-            raise ValueError(f"fitting: scans must be float32 or float64, got {p3ds.dtype}")
-        if p3ds.is_cuda and p3ds.device.index != device:
-            raise ValueError(f"fitting: a scan on {p3ds.device} for a fit on cuda:{device}")
-        if not p3ds.is_cuda:
-            return _scan_of(p3ds.numpy(), img_hw, device)
-        if p3ds.shape[0] < 2 or p3ds.shape[1] < 2:
-            raise ValueError(f"fitting: a scan needs at least 2 x 2 pixels, got shape {tuple(p3ds.shape)}")
-        st = p3ds.stride()
-        sm = _capi.LtScanMap(C.c_void_p(p3ds.data_ptr()), p3ds.shape[0], p3ds.shape[1], st[0], st[1], st[2],
-                             img_hw[0], img_hw[1], 0 if p3ds.dtype == torch.float32 else 1, 1)
-        return sm, p3ds
-    a = np.asarray(p3ds)
-    if a.ndim != 3 or a.shape[2] != 3:
-        raise ValueError(f"fitting: a scan must be (H, W, 3), got shape {a.shape}")
-    if a.dtype not in (np.float32, np.float64):
-        raise ValueError(f"fitting: scans must be float32 or float64, got {a.dtype}")
-    if a.shape[0] < 2 or a.shape[1] < 2:
-        raise ValueError(f"fitting: a scan needs at least 2 x 2 pixels, got shape {a.shape}")
-    if any(s < 0 or s % a.itemsize for s in a.strides):
-        a = np.ascontiguousarray(a)
-    rs, ps, cs = (s // a.itemsize for s in a.strides)
-    sm = _capi.LtScanMap(C.c_void_p(a.ctypes.data), a.shape[0], a.shape[1], rs, ps, cs, img_hw[0], img_hw[1],
-                         0 if a.dtype == np.float32 else 1, 0)
-    return sm, a
+    non-negative strides are read in place, a GPU tensor where it lies (_native.operand)."""
+    s = _native.operand(p3ds, host=False, device=device, who="fitting", what="a scan")
+    if s.ndim != 3 or s.shape[2] != 3:
+        raise ValueError(f"fitting: a scan must be (H, W, 3), got shape {s.shape}")
+    if s.dtype not in ("float32", "float64"):
+        raise ValueError(f"fitting: scans must be float32 or float64, got {getattr(p3ds, 'dtype', s.dtype)}")
+    if s.shape[0] < 2 or s.shape[1] < 2:
+        raise ValueError(f"fitting: a scan needs at least 2 x 2 pixels, got shape {s.shape}")
+    if any(v < 0 for v in s.strides):
+        s = s.contiguous()
+    sm = _capi.LtScanMap(C.c_void_p(s.address), s.shape[0], s.shape[1], *s.strides, img_hw[0], img_hw[1],
+                         0 if s.dtype == "float32" else 1, s.on_device)
+    return sm, s.keep
 
 
 def _scan_nbytes(sm):

@@ -26,7 +26,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _capi
+from . import _capi, _native
 from .base import Line3d, PointTrack
 from .structures import PL_Bipartite3d, VPLine_Bipartite3d
 from .vplib import VPTrack
@@ -119,13 +119,12 @@ def assoc_arrays(cams, points_csr, lines_csr, vps, edges, cfg_struct, host_threa
     timers = None
     if host_threads is not None:
         if L.lt_fn_assoc_host(C.byref(a), C.byref(cfg_struct), int(host_threads), *outs, 0, None, None, None) != 0:
-            raise ValueError("limap_amd.optimize: " + L.lt_fn_assoc_host_error().decode(errors="replace"))
+            _native.raise_host_error(L, "lt_fn_assoc_host_error", "limap_amd.optimize: ")
     else:
         ctx = ctx if ctx is not None else _context()
         ctx.chk(L.lt_assoc_arrays(ctx.h, C.byref(a), C.byref(cfg_struct)))  # (a refusal raises ValueError)
         ctx.chk(L.lt_assoc_get(ctx.h, *outs))
-        tm = np.zeros(20)
-        ctx.chk(L.lt_assoc_get_timers(ctx.h, p(tm)))
+        tm = ctx.module_timers("lt_assoc_get_timers", 20)
         timers = dict(prepare_ms=float(tm[0]), loop_ms=float(tm[1]), download_ms=float(tm[2]), batches_enqueued=int(tm[3]),
                       kernels_ms={"k_as_" + n: float(tm[4 + i]) for i, n in enumerate(_KERNELS)})
     return dict(points=po[:NP], params=P[:NL], vps=vo[:NV], cost=cost, iterations=int(it[0]), cg_iterations=int(cg[0]),

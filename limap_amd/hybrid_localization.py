@@ -22,7 +22,7 @@ from collections import defaultdict
 
 import numpy as np
 
-from . import _capi
+from . import _capi, _native
 
 __all__ = ["LineLocConfig", "TrivialLoss", "HuberLoss", "SoftLOneLoss", "CauchyLoss", "LineLocCostFunction",
            "LineLocCostFunctionWeight", "get_lineloc_cost_func", "get_lineloc_weight_func", "get_line_pairs",
@@ -267,13 +267,12 @@ def loc_arrays(csr, cfg_struct, host_threads=None, ctx=None):
     timers = None
     if host_threads is not None:
         if L.lt_fn_loc_host(*args, int(host_threads), *outs) != 0:
-            raise ValueError("limap_amd.optimize: " + L.lt_fn_loc_host_error().decode(errors="replace"))
+            _native.raise_host_error(L, "lt_fn_loc_host_error", "limap_amd.optimize: ")
     else:
         ctx = ctx if ctx is not None else _context()
         ctx.chk(L.lt_loc_solve(ctx.h, *args))
         ctx.chk(L.lt_loc_get(ctx.h, *outs))
-        tm = np.zeros(4)
-        ctx.chk(L.lt_loc_get_timers(ctx.h, p(tm, C.c_double)))
+        tm = ctx.module_timers("lt_loc_get_timers", 4)
         timers = dict(prepare_ms=float(tm[0]), kernel_ms=float(tm[1]), download_ms=float(tm[2]), lm_device_ms=float(tm[3]))
     return dict(qvec=Q[:P], tvec=T[:P], cost=cost[:P], num_residuals=nres[:P], iterations=it[:P], codes=code[:P],
                 timers=timers)
@@ -290,12 +289,8 @@ def loc_eval(cfg_struct, problem):
                           p(seg_off, C.c_int64), p(sg, C.c_double), int(pt_off[-1]), p(p3, C.c_double), p(p2, C.c_double),
                           C.byref(cfg_struct), p(res, C.c_double), p(cost, C.c_double), p(g, C.c_double), p(H, C.c_double))
     if rc != 0:
-        raise ValueError("limap_amd.optimize: " + L.lt_fn_loc_host_error().decode(errors="replace"))
+        _native.raise_host_error(L, "lt_fn_loc_host_error", "limap_amd.optimize: ")
     return res[:nb], float(cost[0]), g, H
-
-
-def _host_threads(host, host_threads):
-    return host_threads if host_threads is not None else (0 if host else None)
 
 
 class LineLocEngine:
@@ -304,7 +299,7 @@ class LineLocEngine:
 
     def __init__(self, cfg=None, host=False, host_threads=None):
         self.config = cfg if isinstance(cfg, LineLocConfig) else LineLocConfig(cfg)
-        self._ht = _host_threads(host, host_threads)
+        self._ht = _native.host_threads(host, host_threads)
         self._problem = self._result = None
 
     def _pose(self, K, R, T):
@@ -433,7 +428,7 @@ def solve_jointloc_batch(line_cost_func, cfg, problems, line_weight_func=None, h
         q = pr["qvec"] if "qvec" in pr else _qvec_from_R(pr["R"])
         plist.append(dict(l3ds=l3ds, l2ds=l2ds, p3ds=pr.get("p3ds", []), p2ds=pr.get("p2ds", []), kvec=_kvec(pr["K"]),
                           qvec=np.asarray(q, float).reshape(4), tvec=np.asarray(pr.get("tvec", pr.get("T")), float).reshape(3)))
-    return loc_arrays(_problem_arrays(plist), c._struct(), _host_threads(host, host_threads))
+    return loc_arrays(_problem_arrays(plist), c._struct(), _native.host_threads(host, host_threads))
 
 
 def _pose_arrays(poses):
@@ -486,17 +481,16 @@ def score_poses(line_cost_func, l3ds, l3d_ids, l2ds, p3ds, p2ds, K, poses, cheir
             p(p3, C.c_double), p(p2, C.c_double), H, p(q, C.c_double), p(t, C.c_double), C.byref(c))
     msac = thresholds is not None
     outs = (p(table, C.c_double), p(scores, C.c_double) if msac else None, p(inl, C.c_int32) if msac else None)
-    ht = _host_threads(host, host_threads)
+    ht = _native.host_threads(host, host_threads)
     timers = None
     if ht is not None:
         if L.lt_fn_loc_score_host(*args, int(ht), *outs) != 0:
-            raise ValueError("limap_amd.optimize: " + L.lt_fn_loc_host_error().decode(errors="replace"))
+            _native.raise_host_error(L, "lt_fn_loc_host_error", "limap_amd.optimize: ")
     else:
         ctx = ctx if ctx is not None else _context()
         ctx.chk(L.lt_loc_score(ctx.h, *args))
         ctx.chk(L.lt_loc_score_get(ctx.h, *outs))
-        tm = np.zeros(4)
-        ctx.chk(L.lt_loc_score_get_timers(ctx.h, p(tm, C.c_double)))
+        tm = ctx.module_timers("lt_loc_score_get_timers", 4)
         timers = dict(prepare_ms=float(tm[0]), kernel_ms=float(tm[1]), download_ms=float(tm[2]), score_device_ms=float(tm[3]))
     table = table.reshape(-1)[:H * N].reshape(H, N)
     return dict(residuals=table, scores=scores[:H] if msac else None, inliers=inl[:H] if msac else None, timers=timers)

@@ -18,7 +18,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _capi
+from . import _capi, _native
 
 __all__ = ["LineSegmentDetectionModule", "detect_scene", "line_map_to_segments", "sold2segstosegs", "segstosold2segs",
            "compute_descinfo", "compute_descinfo_scene", "sample_line_points", "kernel_ms", "SHIPPED_CFG"]
@@ -33,10 +33,6 @@ SHIPPED_CFG = {
     "heatmap_refine_cfg": {"mode": "local", "ratio": 0.2, "valid_thresh": 0.001, "num_blocks": 20, "overlap_ratio": 0.5},
     "use_junction_refinement": True, "junction_refine_cfg": {"num_perturbs": 9, "perturb_interval": 0.25},
 }
-
-
-def _is_torch(x):
-    return type(x).__module__.split(".")[0] == "torch"
 
 
 def linspace_sampler(n):
@@ -148,9 +144,9 @@ class LineSegmentDetectionModule:
         if self.use_junction_refinement:
             line_map, junc = st["line_map_refined"], st["junctions_refined"]
         else:
-            line_map, junc = st["line_map"], np.asarray(_host_array(junctions), np.float32).reshape(-1, 2)
+            line_map, junc = st["line_map"], np.asarray(_native.to_host(junctions), np.float32).reshape(-1, 2)
         out = (line_map, junc, st["heatmap"])
-        if _is_torch(heatmap):
+        if _native.is_torch(heatmap):
             import torch
             out = tuple(torch.from_numpy(np.ascontiguousarray(o)).to(heatmap.device) for o in out)
         return out
@@ -162,33 +158,24 @@ def _as_module(module_or_cfg):
     return LineSegmentDetectionModule(**dict(module_or_cfg))
 
 
-def _host_array(x):
-    if _is_torch(x):
-        return x.detach().cpu().numpy()
-    return np.asarray(x)
-
-
-def _prepare_image(junctions, heatmap, use_device, device):
-    """-> (junctions, heatmap, heat stride in floats, on_device) with both inputs of one kind and FP32"""
+def _prepare_image(junctions, heatmap, host, device):
+    """-> the Operands (junctions (n, 2), heatmap) of one image, both FP32, contiguous and in one place: the heatmap's,
+    to which the junctions are brought"""
     jshape, hshape = tuple(junctions.shape), tuple(heatmap.shape)
     empty = len(jshape) in (1, 2) and jshape[0] == 0  # np.zeros(0) and np.zeros((0, 2)) both mean "no junction"
     if not empty and (len(jshape) != 2 or jshape[1] != 2):
         raise ValueError(f"line2d: junctions must be (n, 2), got shape {jshape}")
     if len(hshape) != 2:
         raise ValueError(f"line2d: a heatmap must be 2-D (H, W), got shape {hshape}")
-    if use_device:
+    hm = _native.operand(heatmap, host=host, device=device, who="line2d", what="the heatmap")
+    hm = hm.astype("float32").contiguous()
+    if hm.on_device:
         import torch
-        if heatmap.device.index != device:
-            raise ValueError(f"line2d: the heatmap lives on {heatmap.device}, the call runs on device {device}")
-        hm = heatmap.to(torch.float32)
-        if hm.stride(1) != 1 or hm.stride(0) < hm.shape[1]:
-            hm = hm.contiguous()
-        jn = junctions if _is_torch(junctions) else torch.as_tensor(np.asarray(junctions))
-        jn = jn.to(device=hm.device, dtype=torch.float32).reshape(-1, 2).contiguous()
-        return jn, hm, hm.stride(0), 1
-    hm = np.ascontiguousarray(_host_array(heatmap), np.float32)
-    jn = np.ascontiguousarray(_host_array(junctions), np.float32).reshape(-1, 2)
-    return jn, hm, hm.shape[1], 0
+        jn = junctions if _native.is_torch(junctions) else torch.as_tensor(np.asarray(junctions))
+        jn = jn.to(device=hm.keep.device, dtype=torch.float32).reshape(-1, 2).contiguous()
+    else:
+        jn = np.ascontiguousarray(_native.to_host(junctions), np.float32).reshape(-1, 2)
+    return _native.Operand(jn, hm.on_device), hm
 
 
 def unique_rows(points):
@@ -214,8 +201,8 @@ def segments_to_line_map(junctions, segments):
 def line_map_to_segments(junctions, line_map):
     """line_detector.py:line_map_to_segments: (N, 2, 2) float64 segments in the reference's emission order.  A segment
     refined to a single point sits on the diagonal of the line map and is emitted as the reference emits it."""
-    junctions = np.asarray(_host_array(junctions))
-    tmp = np.array(_host_array(line_map), copy=True)
+    junctions = _native.to_host(junctions)
+    tmp = np.array(_native.to_host(line_map), copy=True)
     out = []
     for idx in range(junctions.shape[0]):
         if tmp[idx, :].sum() == 0:
@@ -255,19 +242,20 @@ def detect_scene(module_or_cfg, junctions_list, heatmaps, device=0, host=False, 
         raise ValueError("line2d: one heatmap per junction array")
     n_img = len(heatmaps)
     cfg, keep = module._config()
-    use_device = (not host) and n_img > 0 and all(_is_torch(h) and h.is_cuda for h in heatmaps)
+    # (a list: every heatmap meets the device rule, whatever the others are)
+    use_device = n_img > 0 and all([_native.check_device(h, host=host, device=device, who="line2d", what="the heatmap")
+                                    for h in heatmaps])
     arr = (_capi.LtSold2Image * max(n_img, 1))()
     recs = []
     for k in range(n_img):
-        jn, hm, stride, on_dev = _prepare_image(junctions_list[k], heatmaps[k], use_device, device)
+        jn, hm = _prepare_image(junctions_list[k], heatmaps[k], not use_device, device)
         recs.append((jn, hm))
         a = arr[k]
-        a.junctions = jn.data_ptr() if on_dev else jn.ctypes.data
-        a.heatmap = hm.data_ptr() if on_dev else hm.ctypes.data
-        a.heat_stride, a.n_junc, a.H, a.W, a.on_device = stride, jn.shape[0], hm.shape[0], hm.shape[1], on_dev
+        a.junctions, a.heatmap, a.heat_stride, a.n_junc = jn.address, hm.address, hm.shape[1], jn.shape[0]
+        a.H, a.W, a.on_device = *hm.shape, hm.on_device
         for name, masks in (("cand_in", cand_in), ("det_in", det_in)):
             if masks is not None and masks[k] is not None:
-                m = np.ascontiguousarray(np.asarray(_host_array(masks[k])) != 0, np.uint8)
+                m = np.ascontiguousarray(_native.to_host(masks[k]) != 0, np.uint8)
                 if m.shape != (jn.shape[0], jn.shape[0]):
                     raise ValueError(f"line2d: {name} must be (n, n)")
                 keep.append(m)
@@ -277,14 +265,13 @@ def detect_scene(module_or_cfg, junctions_list, heatmaps, device=0, host=False, 
 
         def chk(rc):
             if rc != 0:
-                raise ValueError(L.lt_fn_sold2_host_error().decode(errors="replace"))
+                _native.raise_host_error(L, "lt_fn_sold2_host_error")
         chk(L.lt_fn_sold2_detect_host(C.byref(cfg), n_img, arr, int(n_threads)))
     else:
         ctx = _context(device)
         L, h, chk = ctx.L, ctx.h, ctx.chk
         if use_device:
-            import torch
-            torch.cuda.synchronize(device)  # the context's stream does not wait for torch's
+            _native.wait_for_torch(device)
         chk(L.lt_sold2_detect_scene(h, C.byref(cfg), n_img, arr))
     counts = np.zeros(max(n_img, 1), np.int64)
     chk(L.lt_sold2_get_counts(h, _capi.ptr(counts, C.c_int64)))
@@ -321,9 +308,9 @@ def detect_scene(module_or_cfg, junctions_list, heatmaps, device=0, host=False, 
 
 def _one_image(module, junctions, heatmap):
     cfg, keep = module._config()
-    jn, hm, stride, _ = _prepare_image(junctions, heatmap, False, 0)
+    jn, hm = _prepare_image(junctions, heatmap, True, 0)
     img = _capi.LtSold2Image()
-    img.junctions, img.heatmap, img.heat_stride = jn.ctypes.data, hm.ctypes.data, stride
+    img.junctions, img.heatmap, img.heat_stride = jn.address, hm.address, hm.shape[1]
     img.n_junc, img.H, img.W = jn.shape[0], hm.shape[0], hm.shape[1]
     return cfg, img, keep + [jn, hm]
 
@@ -339,7 +326,7 @@ def samples_host(module_or_cfg, junctions, heatmap, pairs):
     L = _capi.load_library()
     if L.lt_fn_sold2_samples_host(C.byref(cfg), C.byref(img), P, _capi.ptr(pairs, C.c_int32), _capi.ptr(pos, C.c_float),
                                   _capi.ptr(val, C.c_float)) != 0:
-        raise ValueError(L.lt_fn_sold2_host_error().decode(errors="replace"))
+        _native.raise_host_error(L, "lt_fn_sold2_host_error")
     return pos[:P], val[:P]
 
 
@@ -354,23 +341,20 @@ def block_scales_host(module_or_cfg, heatmap):
     L = _capi.load_library()
     if L.lt_fn_sold2_block_scales_host(C.byref(cfg), C.byref(img), _capi.ptr(scales, C.c_float),
                                        _capi.ptr(bounds, C.c_int32)) != 0:
-        raise ValueError(L.lt_fn_sold2_host_error().decode(errors="replace"))
+        _native.raise_host_error(L, "lt_fn_sold2_host_error")
     return scales, bounds
 
 
 def kernel_ms(device=0):
     """lt_sold2_get_kernel_ms of the last device detection: device ms per kernel, all kernels, the whole call"""
-    ctx = _context(device)
-    out = np.zeros(8)
-    ctx.chk(ctx.L.lt_sold2_get_kernel_ms(ctx.h, _capi.ptr(out)))
-    return dict(zip(KERNEL_MS_KEYS, out.tolist()))
+    return dict(zip(KERNEL_MS_KEYS, _context(device).module_timers("lt_sold2_get_kernel_ms", 8).tolist()))
 
 
 # ---- compute_descriptors of WunschLineMatcher ----
 def sample_line_points(line_seg, num_samples=5, min_dist_pts=8):
     """line_matching.py:sample_line_points: 2 .. num_samples points at least min_dist_pts apart along every segment,
     padded with zeros -> (points (N, num_samples, 2) float64, valid (N, num_samples) bool)"""
-    line_seg = np.asarray(_host_array(line_seg), np.float64).reshape(-1, 2, 2)
+    line_seg = np.asarray(_native.to_host(line_seg), np.float64).reshape(-1, 2, 2)
     num_lines = len(line_seg)
     line_lengths = np.linalg.norm(line_seg[:, 0] - line_seg[:, 1], axis=1)
     num_samples_lst = np.clip(line_lengths // min_dist_pts, 2, num_samples)
@@ -416,34 +400,28 @@ def compute_descinfo_scene(segs_list, descriptors, num_samples=5, min_dist_pts=8
         pts, valid = sample_line_points(segs, num_samples, min_dist_pts)
         pts = np.ascontiguousarray(pts.reshape(-1, 2), np.float32)
         _, ch, hd, wd = (int(v) for v in desc.shape)
-        on_dev = int((not host) and _is_torch(desc) and desc.is_cuda)
-        if on_dev:
+        cl = _native.operand(desc, host=host, device=device, who="line2d", what="the descriptor").astype("float32")
+        cl = cl.map(lambda d: d[0].swapaxes(0, 1).swapaxes(1, 2)).contiguous()  # (C, H, W) -> (H, W, C)
+        if cl.on_device:
             import torch
-            if desc.device.index != device:
-                raise ValueError(f"line2d: the descriptor lives on {desc.device}, the call runs on device {device}")
-            cl = desc[0].to(torch.float32).permute(1, 2, 0).contiguous()
             out = torch.empty((ch, pts.shape[0]), dtype=torch.float32, device=desc.device)
-            mp, op = cl.data_ptr(), out.data_ptr()
         else:
-            cl = np.ascontiguousarray(np.asarray(_host_array(desc), np.float32)[0].transpose(1, 2, 0))
             out = np.zeros((ch, pts.shape[0]), np.float32)
-            mp, op = cl.ctypes.data, out.ctypes.data
         keep += [pts, cl]
         a = arr[len(rows)]
-        a.map, a.points, a.out, a.n_points = mp, pts.ctypes.data, op, pts.shape[0]
-        a.Hd, a.Wd, a.C, a.grid_size, a.on_device = hd, wd, ch, int(grid_size), on_dev
+        a.map, a.points, a.out, a.n_points = cl.address, pts.ctypes.data, _native.address(out), pts.shape[0]
+        a.Hd, a.Wd, a.C, a.grid_size, a.on_device = hd, wd, ch, int(grid_size), cl.on_device
         rows.append(k)
         outs.append(out)
         valids.append(valid)
     if host:
         L = _capi.load_library()
         if L.lt_fn_sold2_descinfo_host(len(rows), arr, int(n_threads)) != 0:
-            raise ValueError(L.lt_fn_sold2_host_error().decode(errors="replace"))
+            _native.raise_host_error(L, "lt_fn_sold2_host_error")
     else:
         ctx = _context(device)
         if any(arr[j].on_device for j in range(len(rows))):
-            import torch
-            torch.cuda.synchronize(device)
+            _native.wait_for_torch(device)
         ms = C.c_double(0.0)
         ctx.chk(ctx.L.lt_sold2_descinfo_scene(ctx.h, len(rows), arr, C.byref(ms)))
         compute_descinfo_scene.last_ms = ms.value

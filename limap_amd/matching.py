@@ -30,7 +30,7 @@ from typing import NamedTuple
 
 import numpy as np
 
-from . import _capi
+from . import _capi, _native
 from . import io as limapio
 
 __all__ = ["BaseMatcherOptions", "DefaultMatcherOptions", "BaseMatcher", "L2D2Matcher", "NNEndpointsMatcher",
@@ -62,28 +62,23 @@ def _kind(kind):
     return int(kind)
 
 
-def _is_torch(a):
-    return type(a).__module__.split(".")[0] == "torch"
+def _rows(d, rule, empty, transpose):
+    """a descriptor array as contiguous float32 rows, NumPy or a torch GPU tensor where the input is one: 2-D (`rule`
+    is the refusal's text; without elements it takes the shape `empty`), transposed where the rows are its columns.
+    The device rule waits for the call's device (_gather)"""
+    d = _native.operand(d, host=False, device=None, who="matching", what="a descriptor array").astype("float32")
+    if d.ndim != 2:
+        if all(d.shape):
+            raise ValueError(f"matching: {rule}, got shape {d.shape}")
+        d = d.map(lambda k: k.reshape(empty))
+    return (d.map(lambda k: k.T) if transpose else d).contiguous().keep
 
 
 def _rows_of(descinfo, kind):
-    """the descriptor rows of one image, (rows, dim) float32: NumPy array, or torch tensor where the input is one.
-    Endpoints: limap keeps (dim, 2 M); the native layout is one row per endpoint."""
+    """the descriptor rows of one image, (rows, dim).  Endpoints: limap keeps (dim, 2 M); the native layout is one row
+    per endpoint."""
     d = descinfo[_KEY[kind]] if isinstance(descinfo, dict) else descinfo
-    if _is_torch(d):
-        import torch
-        d = d.to(torch.float32)
-        if d.dim() != 2:
-            d = d.reshape(0, 0) if d.numel() == 0 else d
-        if d.dim() != 2:
-            raise ValueError(f"matching: descriptors must be 2-D, got shape {tuple(d.shape)}")
-        return (d.t() if kind == 1 else d).contiguous()
-    a = np.asarray(d, np.float32)
-    if a.ndim != 2:
-        if a.size:
-            raise ValueError(f"matching: descriptors must be 2-D, got shape {a.shape}")
-        a = a.reshape(0, 0)
-    return np.ascontiguousarray(a.T if kind == 1 else a)
+    return _rows(d, "descriptors must be 2-D", (0, 0), kind == 1)
 
 
 def _width(parts):
@@ -102,10 +97,7 @@ def _sold2_parts(descinfo, num_samples):
         return np.zeros((0, 8), np.float32), np.zeros((0, S), np.uint8)
     if isinstance(descinfo, dict) or len(descinfo) != 2:
         raise ValueError("matching: a sold2 descinfo is the pair [desc (dim, S N), valid (N, S)]")
-    d, v = descinfo[0], descinfo[1]
-    if _is_torch(v):
-        v = v.cpu().numpy()
-    v = np.asarray(v)
+    d, v = descinfo[0], _native.to_host(descinfo[1])
     if v.ndim == 3 and v.shape[0] == 1:
         v = v[0]
     if v.size == 0:
@@ -113,19 +105,7 @@ def _sold2_parts(descinfo, num_samples):
     if v.ndim != 2 or v.shape[1] != S:
         raise ValueError(f"matching: valid must be (N, num_samples = {S}), got shape {v.shape}")
     v = np.ascontiguousarray(v != 0, np.uint8)
-    if _is_torch(d):
-        import torch
-        d = d.to(torch.float32)
-        if d.dim() != 2:
-            raise ValueError(f"matching: desc must be 2-D (dim, S N), got shape {tuple(d.shape)}")
-        rows = d.t().contiguous()
-    else:
-        d = np.asarray(d, np.float32)
-        if d.ndim != 2:
-            if d.size:
-                raise ValueError(f"matching: desc must be 2-D (dim, S N), got shape {d.shape}")
-            d = d.reshape(8, 0)
-        rows = np.ascontiguousarray(d.T)
+    rows = _rows(d, "desc must be 2-D (dim, S N)", (8, 0), True)
     if rows.shape[0] != S * v.shape[0]:
         raise ValueError(f"matching: desc has {rows.shape[0]} columns, valid {v.shape[0]} rows: not num_samples = {S} "
                          "columns per line")
@@ -133,18 +113,15 @@ def _sold2_parts(descinfo, num_samples):
 
 
 def _gather(parts, dim, device):
-    """one array for the native call from the per-image rows: (keep-alive, pointer, on_device)"""
-    if parts and all(_is_torch(p) for p in parts):
+    """one array for the native call from the per-image rows: (keep-alive, pointer, on_device).  On the device where
+    every image with rows brought a GPU tensor (an image without rows does not decide), else all on the host"""
+    live = [_native.operand(p, host=False, device=device, who="matching", what="a descriptor array") for p in parts]
+    live = [p for p in live if p.shape[0] > 0]
+    if live and all(p.on_device for p in live):
         import torch
-        live = [p for p in parts if p.shape[0] > 0]
-        if live and all(p.is_cuda for p in live):
-            if any(p.device.index != device for p in live):
-                raise ValueError(f"matching: descriptors on another device than cuda:{device}")
-            keep = torch.cat(live, 0).contiguous()
-            torch.cuda.synchronize(device)  # the context's stream does not wait for torch's streams
-            return keep, C.c_void_p(keep.data_ptr()), 1
-    parts = [p.cpu().numpy() if _is_torch(p) else p for p in parts]
-    live = [p.reshape(-1, dim) for p in parts if p.shape[0] > 0]
+        keep = torch.cat([p.keep for p in live], 0).contiguous()
+        return keep, C.c_void_p(_native.address(keep)), 1
+    live = [_native.to_host(p.keep).reshape(-1, dim) for p in live]
     keep = np.ascontiguousarray(np.concatenate(live, 0), np.float32) if live else np.zeros((1, dim), np.float32)
     return keep, C.c_void_p(keep.ctypes.data), 0
 
@@ -169,11 +146,13 @@ def _match_flat(parts, pair_off, pair_nb, kind, topk, device=0, want_scores=Fals
                 top_k_candidates=10):
     """the native call: parts = descriptor rows per image (all NumPy or all torch); returns row_off, rows, scores.
     kind SOLD2 is lt_match_wunsch_scene: parts = point-descriptor rows per image, valids = (N, S) uint8 per image"""
-    ctx = _context(device)
     dim = _width(parts)
     desc_off = np.zeros(len(parts) + 1, np.int64)
     desc_off[1:] = np.cumsum([p.shape[0] for p in parts])
     keep, dptr, on_dev = _gather(parts, dim, device)
+    ctx = _context(device)
+    if on_dev:
+        _native.wait_for_torch(device)
     pair_off, pair_nb = _capi.i64(pair_off), _capi.i32(pair_nb)
     pairs = (_capi.ptr(pair_off, C.c_int64), _capi.ptr(pair_nb if len(pair_nb) else _capi.i32([0]), C.c_int32))
     n_rows = C.c_int64(0)
@@ -198,17 +177,13 @@ def _match_flat(parts, pair_off, pair_nb, kind, topk, device=0, want_scores=Fals
 
 def kernel_ms(device=0):
     """lt_match_wunsch_get_kernel_ms of the last sold2 call: device ms of the line-score kernel and of the NW kernel"""
-    out = np.zeros(2)
-    ctx = _context(device)
-    ctx.chk(ctx.L.lt_match_wunsch_get_kernel_ms(ctx.h, out.ctypes.data_as(C.POINTER(C.c_double))))
-    return out
+    return _context(device).module_timers("lt_match_wunsch_get_kernel_ms", 2)
 
 
 def _host_pair_args(descinfo1, descinfo2, num_samples):
     a, va = _sold2_parts(descinfo1, num_samples)
     b, vb = _sold2_parts(descinfo2, num_samples)
-    a = a.cpu().numpy() if _is_torch(a) else a
-    b = b.cpu().numpy() if _is_torch(b) else b
+    a, b = _native.to_host(a), _native.to_host(b)
     dim = _width([a, b])
     a = np.ascontiguousarray(a.reshape(-1, dim), np.float32)
     b = np.ascontiguousarray(b.reshape(-1, dim), np.float32)
@@ -249,10 +224,7 @@ def wunsch_nw_host(block):
 
 def timers(device=0):
     """lt_match_get_timers of the last native call: host ms of validation + upload, kernels, download, row bookkeeping"""
-    out = np.zeros(4)
-    ctx = _context(device)
-    ctx.chk(ctx.L.lt_match_get_timers(ctx.h, out.ctypes.data_as(C.POINTER(C.c_double))))
-    return out
+    return _context(device).module_timers("lt_match_get_timers", 4)
 
 
 def match_scene(descinfos, neighbors, kind="l2d2", topk=10, device=0, return_scores=False, num_samples=5,
@@ -315,11 +287,7 @@ def match_pair_host(desc1, desc2, kind="l2d2", topk=10, return_scores=False, num
             raise ValueError(f"lt_fn_match_wunsch_pair_host: rejected (code {rc})")
         rows, scores = rows[:n.value].copy(), scores[:n.value].copy()
         return (rows, scores) if return_scores else rows
-    a, b = _rows_of(desc1, kind), _rows_of(desc2, kind)
-    if _is_torch(a):
-        a = a.cpu().numpy()
-    if _is_torch(b):
-        b = b.cpu().numpy()
+    a, b = _native.to_host(_rows_of(desc1, kind)), _native.to_host(_rows_of(desc2, kind))
     dim = _width([a, b])
     a = np.ascontiguousarray(a.reshape(-1, dim), np.float32)
     b = np.ascontiguousarray(b.reshape(-1, dim), np.float32)
@@ -515,7 +483,7 @@ DefaultDenseLineMatcherOptions = BaseDenseLineMatcherOptions()
 
 
 def _stack_xy(x, y):
-    if _is_torch(x):
+    if _native.is_torch(x):
         import torch
         return torch.stack([x, y], -1)
     return np.stack([x, y], axis=-1)
@@ -575,10 +543,7 @@ class DenseNaiveExtractor:
 
 def _dense_image(descinfo):
     """lines (N, 4) float32 and (h, w) of a dense descinfo"""
-    lines = descinfo["lines"]
-    if _is_torch(lines):
-        lines = lines.detach().cpu().numpy()
-    lines = np.asarray(lines)
+    lines = _native.to_host(descinfo["lines"])
     if lines.size == 0:
         lines = np.zeros((0, 4), np.float32)
     if lines.shape[1:] not in ((2, 2), (4,)):
@@ -591,22 +556,14 @@ def _dense_maps(quad, device):
     """(warp_12, cert_12, warp_21, cert_21) -> the four arrays as float32, contiguous; all torch GPU tensors or all NumPy"""
     if len(quad) != 4:
         raise ValueError("matching: a pair's warps are (warp_12, cert_12, warp_21, cert_21)")
-    if all(_is_torch(a) and a.is_cuda for a in quad):
-        import torch
-        if any(a.device.index != device for a in quad):
-            raise ValueError(f"matching: warps on another device than cuda:{device}")
-        out = [a.detach().to(torch.float32).contiguous() for a in quad]
-    else:
-        out = [np.ascontiguousarray(a.detach().cpu().numpy() if _is_torch(a) else a, np.float32) for a in quad]
+    out = [_native.operand(a, host=False, device=device, who="matching", what="a warp") for a in quad]
+    if not all(a.on_device for a in out):
+        out = [_native.operand(a, host=True, device=device, who="matching", what="a warp") for a in quad]
+    out = [a.astype("float32").contiguous() for a in out]
     for w, c in ((out[0], out[1]), (out[2], out[3])):
-        if len(w.shape) != 3 or w.shape[2] != 2 or len(c.shape) != 2:
-            raise ValueError(f"matching: a warp must be (H, W, 2) and its certainty (H, W), got {tuple(w.shape)} and "
-                             f"{tuple(c.shape)}")
-    return out
-
-
-def _dense_ptr(a):
-    return a.data_ptr() if _is_torch(a) else a.ctypes.data
+        if w.ndim != 3 or w.shape[2] != 2 or c.ndim != 2:
+            raise ValueError(f"matching: a warp must be (H, W, 2) and its certainty (H, W), got {w.shape} and {c.shape}")
+    return [a.keep for a in out]
 
 
 def _dense_dims(maps):
@@ -629,19 +586,19 @@ def _match_dense_flat(images, pairs, maps, opts, sample_thresh, device=0, want_s
     if lines.shape[0] == 0:
         lines = np.zeros((1, 4), np.float32)
     shapes = _capi.i32(np.array([im[1] for im in images], np.int64).reshape(-1))
-    on_dev = bool(maps) and all(_is_torch(a) for q in maps for a in q)
+    on_dev = bool(maps) and all([_native.check_device(a, host=False, device=device, who="matching", what="a warp")
+                                 for q in maps for a in q])
     if not on_dev:
-        maps = [[a.cpu().numpy() if _is_torch(a) else a for a in q] for q in maps]
+        maps = [[_native.to_host(a) for a in q] for q in maps]
     n = len(pairs)
     warp_p, cert_p = (C.c_void_p * max(2 * n, 1))(), (C.c_void_p * max(2 * n, 1))()
     dims = np.zeros(max(8 * n, 1), np.int32)
     for q, m in enumerate(maps):
-        warp_p[2 * q], cert_p[2 * q], warp_p[2 * q + 1], cert_p[2 * q + 1] = (_dense_ptr(a) for a in m)
+        warp_p[2 * q], cert_p[2 * q], warp_p[2 * q + 1], cert_p[2 * q + 1] = (_native.address(a) for a in m)
         dims[8 * q:8 * q + 8] = _dense_dims(m)
     pair_img = _capi.i32(np.array(pairs, np.int64).reshape(-1)) if n else _capi.i32([0])
     if on_dev:
-        import torch
-        torch.cuda.synchronize(device)  # the context's stream does not wait for torch's streams
+        _native.wait_for_torch(device)
     cfg = _dense_cfg(opts, sample_thresh, 1 if on_dev else 0, 1 if want_scores else 0, 1 if want_dirs else 0)
     n_rows = C.c_int64(0)
     ctx.chk(ctx.L.lt_match_dense_pairs(ctx.h, len(images), _capi.ptr(line_off, C.c_int64),
@@ -668,16 +625,13 @@ def _match_dense_flat(images, pairs, maps, opts, sample_thresh, device=0, want_s
 
 def dense_kernel_ms(device=0):
     """lt_match_dense_get_kernel_ms of the last dense call: device ms of k_dense_warp, k_dense_pairs, k_dense_select"""
-    out = np.zeros(3)
-    ctx = _context(device)
-    ctx.chk(ctx.L.lt_match_dense_get_kernel_ms(ctx.h, out.ctypes.data_as(C.POINTER(C.c_double))))
-    return out
+    return _context(device).module_timers("lt_match_dense_get_kernel_ms", 3)
 
 
 def _dense_host_args(descinfo1, descinfo2, warps, dense_options, sample_thresh):
     l1, s1 = _dense_image(descinfo1)
     l2, s2 = _dense_image(descinfo2)
-    m = [np.ascontiguousarray(a.detach().cpu().numpy() if _is_torch(a) else a, np.float32) for a in warps]
+    m = [np.ascontiguousarray(_native.to_host(a), np.float32) for a in warps]
     if len(m) != 4 or m[0].ndim != 3 or m[0].shape[2] != 2 or m[2].ndim != 3 or m[2].shape[2] != 2 or m[1].ndim != 2 \
             or m[3].ndim != 2:
         raise ValueError("matching: a pair's warps are (warp_12 (H, W, 2), cert_12 (H, W), warp_21, cert_21)")
@@ -764,10 +718,10 @@ def match_scene_dense(descinfos, neighbors, warps, dense_options=DefaultDenseLin
     for i, j in todo:
         m = _dense_maps(_warps_of(warps, descinfos, i, j), device)
         nbytes = 4 * sum(int(np.prod(a.shape)) for a in m)
-        if batch and (used + nbytes > warp_bytes or _is_torch(m[0]) != kind):
+        if batch and (used + nbytes > warp_bytes or _native.is_torch(m[0]) != kind):
             flush(batch, maps)
             batch, maps, used = [], [], 0
-        kind = _is_torch(m[0])
+        kind = _native.is_torch(m[0])
         batch.append((i, j))
         maps.append(m)
         used += nbytes
@@ -815,7 +769,7 @@ class DenseLineMatcher(BaseMatcher):
     def compute_distance_one_direction(self, descinfo1, descinfo2, warp_1to2, cert_1to2):
         """(weighted_dists, overlap), both (N1, N2) float32, of the restated definition, from the device"""
         back_w, back_c = np.zeros((1, 1, 2), np.float32), np.zeros((1, 1), np.float32)
-        if _is_torch(warp_1to2) and warp_1to2.is_cuda:
+        if _native.check_device(warp_1to2, host=False, device=self.device, who="matching", what="a warp"):
             import torch
             back_w, back_c = (torch.from_numpy(a).to(warp_1to2.device) for a in (back_w, back_c))
         maps = _dense_maps((warp_1to2, cert_1to2, back_w, back_c), self.device)

@@ -13,7 +13,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _capi
+from . import _capi, _native
 from .base import Line2d, Line3d, LineTrack
 
 
@@ -192,8 +192,7 @@ class TrackSet:
                                          float(var2d), C.byref(out)))
         ts = cls(ctx, out.value)
         ts.graph = MergeGraph.from_ctx(ctx)
-        tm = np.zeros(4)
-        ctx.chk(ctx.L.lt_merge_get_timers(ctx.h, p(tm, C.c_double)))
+        tm = ctx.module_timers("lt_merge_get_timers", 4)
         ts.merge_timers = dict(device_ms=float(tm[0]), host_ms=float(tm[1]), attempts=int(tm[2]), edges=int(tm[3]))
         return ts
 

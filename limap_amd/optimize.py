@@ -58,7 +58,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _capi
+from . import _capi, _native
 from .base import CameraView, ImageCollection, Line3d, LineTrack, PointTrack
 
 __all__ = ["HybridBAConfig", "RefinementConfig", "HybridBAEngine", "RefinementEngine", "Heatmaps",
@@ -271,25 +271,21 @@ class Heatmaps:
             ctx._refine_heatmaps = (id(self), ctx.L.lt_refine_heatmaps_generation(ctx.h))
 
 
-def _is_torch(x):
-    return type(x).__module__.split(".")[0] == "torch"
-
-
 def _texel_array(a, np_type, host, what):
-    """an (h, w, 128) array or tensor -> (what keeps the memory, address, h, w, on_device) in the texel type; a GPU
-    tensor stays on the device unless the host path was asked for"""
-    if _is_torch(a):
-        if a.is_cuda and not host:
-            import torch
-            a = a.to(getattr(torch, np.dtype(np_type).name)).contiguous()
-            if a.dim() != 3 or a.shape[2] != 128 or a.shape[0] < 1 or a.shape[1] < 1:
-                raise ValueError(f"limap_amd.optimize: {what} must be (h, w, 128), got shape {tuple(a.shape)}")
-            return a, a.data_ptr(), int(a.shape[0]), int(a.shape[1]), 1
-        a = a.detach().cpu().numpy()
-    a = np.ascontiguousarray(np.asarray(a).astype(np_type, copy=False))
-    if a.ndim != 3 or a.shape[2] != 128 or a.shape[0] < 1 or a.shape[1] < 1:
-        raise ValueError(f"limap_amd.optimize: {what} must be (h, w, 128), got shape {a.shape}")
-    return a, a.ctypes.data, a.shape[0], a.shape[1], 0
+    """an (h, w, 128) array or tensor -> its contiguous Operand in the texel type; a GPU tensor stays on the device
+    unless the host path was asked for.  The context is not known yet: _on_context applies the device rule"""
+    t = _native.operand(a, host=host, device=None, who="limap_amd.optimize", what=what)
+    t = t.astype(np.dtype(np_type).name).contiguous()
+    if t.ndim != 3 or t.shape[2] != 128 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError(f"limap_amd.optimize: {what} must be (h, w, 128), got shape {t.shape}")
+    return t
+
+
+def _on_context(ctx, arrays, what):
+    """the device rule for what _texel_array kept, against the context the call runs on, and the stream rule"""
+    for a in arrays:
+        _native.check_device(a, host=False, device=ctx.device, who="limap_amd.optimize", what=what)
+    _native.wait_for_torch(ctx.device)
 
 
 class FeatureMaps:
@@ -303,15 +299,15 @@ class FeatureMaps:
         np_type, self.texel_type = _TEXELS[dtype]
         self.ids = np.array(sorted(int(i) for i in featuremaps), np.int32)
         ent = [_texel_array(featuremaps[int(i)], np_type, host, f"the feature map of image {i}") for i in self.ids]
-        dev = {e[4] for e in ent}
+        dev = {e.on_device for e in ent}
         if len(dev) > 1:
             raise ValueError("limap_amd.optimize: featuremaps mixes host arrays and GPU tensors")
         self.on_device = int(bool(dev and dev.pop()))
-        self.keep = [e[0] for e in ent]
-        self.h = np.array([e[2] for e in ent], np.int32)
-        self.w = np.array([e[3] for e in ent], np.int32)
-        self.addr = {int(i): e[1] for i, e in zip(self.ids, ent)}
-        self.ptrs = (C.c_void_p * max(len(ent), 1))(*[e[1] for e in ent])
+        self.keep = [e.keep for e in ent]
+        self.h = np.array([e.shape[0] for e in ent], np.int32)
+        self.w = np.array([e.shape[1] for e in ent], np.int32)
+        self.addr = {int(i): e.address for i, e in zip(self.ids, ent)}
+        self.ptrs = (C.c_void_p * max(len(ent), 1))(*self.addr.values())
 
     def grid(self, img_id):
         """the identity grid of an image (host path)"""
@@ -326,8 +322,7 @@ class FeatureMaps:
         if getattr(ctx, "_refine_featuremaps", None) != (id(self), gen):
             ctx._refine_featuremaps = None
             if self.on_device:
-                import torch
-                torch.cuda.synchronize()  # the context's stream does not wait for torch's streams
+                _on_context(ctx, self.keep, "a feature map")
             p = _capi.ptr
             ctx.chk(ctx.L.lt_refine_set_feature_maps(ctx.h, len(self.ids), p(self.ids, C.c_int32), p(self.h, C.c_int32),
                                                      p(self.w, C.c_int32), self.ptrs, self.texel_type, self.on_device))
@@ -336,10 +331,12 @@ class FeatureMaps:
 
 
 def _grid_array(grids):
-    """[(address, h, w, R4, tvec2, on_device)] -> (lt_refine_grid array, count)"""
+    """[(texels, h, w, R4, tvec2, on_device)] -> (lt_refine_grid array, count); texels: the array or tensor that holds
+    them, or their address"""
     arr = (_capi.LtRefineGrid * max(len(grids), 1))()
-    for g, (addr, h, w, R, tv, dev) in zip(arr, grids):
-        g.data, g.h, g.w, g.on_device = addr, int(h), int(w), int(dev)
+    for g, (texels, h, w, R, tv, dev) in zip(arr, grids):
+        g.data = int(texels) if isinstance(texels, (int, np.integer)) else _native.address(texels)
+        g.h, g.w, g.on_device = int(h), int(w), int(dev)
         g.R[:] = [float(x) for x in R]
         g.tvec[:] = [float(x) for x in tv]
     return arr, len(grids)
@@ -350,8 +347,9 @@ def refine_arrays(cams, tracks_csr, cfg_struct, host_threads=None, ctx=None, ter
     """One call of lt_refine_arrays (device) or lt_fn_refine_host (host_threads given) -> dict of per-track results.
     terms (lt_refine_terms) selects the *_terms entry points: vp = (flag (M,), vp3 (M, 3)) per support in list order,
     view_hw (n_img, 2) or None, heatmaps a Heatmaps.  feature (lt_refine_feature) selects the *_feature entry points:
-    grids = [(address, h, w, R, tvec, on_device)] per (track, sorted image), or None with featuremaps (a FeatureMaps),
-    which the device call reads from the context."""
+    grids = [(texels, h, w, R, tvec, on_device)] per (track, sorted image) -- texels the array or tensor itself, which
+    the device rule is then applied to, or a bare address, which it cannot see -- or None with featuremaps (a
+    FeatureMaps), which the device call reads from the context."""
     ids, k, q, t = cams
     line6, off, img, l2, l3 = tracks_csr
     T = len(off) - 1
@@ -393,7 +391,7 @@ def refine_arrays(cams, tracks_csr, cfg_struct, host_threads=None, ctx=None, ter
         else:
             rc = L.lt_fn_refine_host_feature(*args, *targs, *hm, C.byref(feature), n_grids, garr, int(host_threads), *outs)
         if rc != 0:
-            raise ValueError("limap_amd.optimize: " + L.lt_fn_refine_host_error().decode(errors="replace"))
+            _native.raise_host_error(L, "lt_fn_refine_host_error", "limap_amd.optimize: ")
     else:
         ctx = ctx if ctx is not None else _context()
         if terms is None:
@@ -407,12 +405,10 @@ def refine_arrays(cams, tracks_csr, cfg_struct, host_threads=None, ctx=None, ter
                 if grids is None:
                     featuremaps.upload(ctx)
                 elif any(g[5] for g in grids):
-                    import torch
-                    torch.cuda.synchronize()  # the context's stream does not wait for torch's streams
+                    _on_context(ctx, [g[0] for g in grids], "a patch")
                 ctx.chk(L.lt_refine_arrays_feature(ctx.h, *args, *targs, C.byref(feature), n_grids, garr))
         ctx.chk(L.lt_refine_get(ctx.h, *outs))
-        tm = np.zeros(4)
-        ctx.chk(L.lt_refine_get_timers(ctx.h, p(tm, C.c_double)))
+        tm = ctx.module_timers("lt_refine_get_timers", 4)
         timers = dict(prepare_ms=float(tm[0]), kernels_ms=float(tm[1]), download_ms=float(tm[2]), lm_device_ms=float(tm[3]))
     return dict(params=P[:T], segments=seg[:T], cost=cost[:T], iterations=it[:T], codes=code[:T], timers=timers)
 
@@ -464,13 +460,12 @@ def ba_arrays(cams, points_csr, lines_csr, cfg_struct, host_threads=None, ctx=No
     timers = None
     if host_threads is not None:
         if L.lt_fn_ba_host(*args, int(host_threads), *outs) != 0:
-            raise ValueError("limap_amd.optimize: " + L.lt_fn_ba_host_error().decode(errors="replace"))
+            _native.raise_host_error(L, "lt_fn_ba_host_error", "limap_amd.optimize: ")
     else:
         ctx = ctx if ctx is not None else _context()
         ctx.chk(L.lt_ba_arrays(ctx.h, *args))
         ctx.chk(L.lt_ba_get(ctx.h, *outs))
-        tm = np.zeros(16)
-        ctx.chk(L.lt_ba_get_timers(ctx.h, p(tm, C.c_double)))
+        tm = ctx.module_timers("lt_ba_get_timers", 16)
         names = ("linearize", "blocks", "images", "damp", "schur", "chol", "backsub", "cost", "decide")
         timers = dict(prepare_ms=float(tm[0]), loop_ms=float(tm[1]), download_ms=float(tm[2]), attempts_enqueued=int(tm[3]),
                       kernels_ms={"k_ba_" + n: float(tm[4 + i]) for i, n in enumerate(names)})
@@ -672,16 +667,16 @@ def _view_hw(ids, views):
 
 
 def _patch_grids(patches, np_type, host, what):
-    """PatchInfos of one track's sorted images -> grid tuples, what keeps their memory, their texel bytes"""
-    grids, keep, nbytes = [], [], 0
+    """PatchInfos of one track's sorted images -> grid tuples (which hold the texels' memory), their texel bytes"""
+    grids, nbytes = [], 0
     for k, pt in enumerate(patches):
         if not hasattr(pt, "array") or not hasattr(pt, "R") or not hasattr(pt, "tvec"):
             raise ValueError(f"limap_amd.optimize: {what}[{k}] is not a features.PatchInfo")
-        a, addr, h, w, dev = _texel_array(pt.array, np_type, host, f"{what}[{k}].array")
-        keep.append(a)
-        grids.append((addr, h, w, np.asarray(pt.R, np.float64).reshape(4), np.asarray(pt.tvec, np.float64).reshape(2), dev))
-        nbytes += h * w * 128 * np.dtype(np_type).itemsize
-    return grids, keep, nbytes
+        a = _texel_array(pt.array, np_type, host, f"{what}[{k}].array")
+        grids.append((a.keep, *a.shape[:2], np.asarray(pt.R, np.float64).reshape(4),
+                      np.asarray(pt.tvec, np.float64).reshape(2), a.on_device))
+        nbytes += a.shape[0] * a.shape[1] * 128 * np.dtype(np_type).itemsize
+    return grids, nbytes
 
 
 def _refine(rf, tracks, views, vpresults, heatmaps, host_threads, patches=None, featuremaps=None, dtype=None,
@@ -706,15 +701,14 @@ def _refine(rf, tracks, views, vpresults, heatmaps, host_threads, patches=None, 
     # tracks in their order, a new native call where the next track's texels would pass the budget: every track is its
     # own problem, so the grouping does not reach the results
     np_type = _TEXELS[dtype or rf.dtype][0]
-    parts, group, grids, keep, used = [], [], [], [], 0
+    parts, group, grids, used = [], [], [], 0
     for n, t in enumerate(tracks):
-        g, k, nb = _patch_grids(patches[n], np_type, host_threads is not None, f"the patches of track {n}")
+        g, nb = _patch_grids(patches[n], np_type, host_threads is not None, f"the patches of track {n}")
         if group and used + nb > int(patch_bytes):
             parts.append(call(group, feature=feature, grids=grids))
-            group, grids, keep, used = [], [], [], 0
-        group.append(t); grids += g; keep += k; used += nb
+            group, grids, used = [], [], 0
+        group.append(t); grids += g; used += nb
     parts.append(call(group, feature=feature, grids=grids))
-    del keep
     out = {k: np.concatenate([r[k] for r in parts]) for k in ("params", "segments", "cost", "iterations", "codes")}
     out["timers"] = None if parts[0]["timers"] is None else {k: sum(r["timers"][k] for r in parts) for k in parts[0]["timers"]}
     out["calls"] = len(parts)

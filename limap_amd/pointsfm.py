@@ -17,7 +17,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _capi
+from . import _capi, _native
 
 __all__ = ["SfmImage", "SfmModel", "compute_neighbors", "compute_metainfos", "timers"]
 
@@ -209,7 +209,7 @@ class SfmModel:
         x = xyz if xyz.shape[0] else np.zeros((1, 3), np.float32)
         if L.lt_fn_sfm_ranges(xyz.shape[0], _p(x, C.c_float), float(range_robust[0]), float(range_robust[1]),
                               float(k_stretch), _p(lo), _p(hi)) != 0:
-            raise ValueError(L.lt_fn_sfm_host_error().decode(errors="replace"))
+            _native.raise_host_error(L, "lt_fn_sfm_host_error")
         return lo, hi
 
 
@@ -232,7 +232,4 @@ def compute_metainfos(cfg, model, n_neighbors=20, host=False, device=0):
 def timers(device=0):
     """lt_sfm_get_timers of the last device call: host ms of setup + upload, the device stage, download; device ms of
     k_sfm_pairs, the key sort, k_sfm_segments, partner lists + selection; launches of k_sfm_segments"""
-    out = np.zeros(8)
-    ctx = _context(device)
-    ctx.chk(ctx.L.lt_sfm_get_timers(ctx.h, _p(out)))
-    return out
+    return _context(device).module_timers("lt_sfm_get_timers", 8)

@@ -15,7 +15,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _capi
+from . import _capi, _native
 
 __all__ = ["VP2d", "VPLine_Bipartite2d", "VPLine_Bipartite3d", "PL_Bipartite3d", "GetAllBipartites_VPLine2d",
            "Point2d", "Junction", "PL_Bipartite2dConfig", "PL_Bipartite2d", "compute_2d_bipartites",
@@ -27,10 +27,7 @@ _p = _capi.ptr
 
 def timers(device=0):
     """lt_bpt_get_timers of the last native call: host ms of upload, kernels, sorts, download + host replay"""
-    out = np.zeros(4)
-    ctx = _context(device)
-    ctx.chk(ctx.L.lt_bpt_get_timers(ctx.h, _p(out)))
-    return out
+    return _context(device).module_timers("lt_bpt_get_timers", 4)
 
 
 class Point2d:
@@ -114,19 +111,11 @@ def _points2(p, what="points"):
     return q
 
 
-def _csr(parts, width):
-    off = np.zeros(len(parts) + 1, np.int64)
-    for k, a in enumerate(parts):
-        off[k + 1] = off[k] + a.shape[0]
-    flat = np.ascontiguousarray(np.concatenate(parts, 0), np.float64) if off[-1] else np.zeros((1, width))
-    return off, flat
-
-
 def _associate(lines_list, points_list, cfg, device=0):
     """per image the (edge_off, edge_line) CSR of its points: one native call for the batch"""
     ctx = _context(device)
-    loff, lflat = _csr(lines_list, 4)
-    poff, pflat = _csr(points_list, 2)
+    loff, lflat = _native.csr(lines_list, 4)
+    poff, pflat = _native.csr(points_list, 2)
     st = cfg._struct()
     n_edges = C.c_int64(0)
     ctx.chk(ctx.L.lt_bpt_associate(ctx.h, len(lines_list), _p(loff, C.c_int64), _p(lflat), _p(poff, C.c_int64),
@@ -146,8 +135,8 @@ def _junctions(lines_list, kps_list, cfg, device=0, candidates=False, sizes=Fals
     per-image candidate lists; sizes: also lt_bpt_junctions' sizes[4] (junctions, line indices, candidates, close
     pairs of the whole call)"""
     ctx = _context(device)
-    loff, lflat = _csr(lines_list, 4)
-    koff, kflat = _csr(kps_list, 2)
+    loff, lflat = _native.csr(lines_list, 4)
+    koff, kflat = _native.csr(kps_list, 2)
     st = cfg._struct()
     want_sizes, sizes = sizes, np.zeros(4, np.int64)
     n = len(lines_list)

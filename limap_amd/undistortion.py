@@ -18,7 +18,7 @@ import os
 
 import numpy as np
 
-from . import _capi
+from . import _capi, _native
 
 __all__ = ["Camera", "undistort_camera", "undistort_image_camera", "undistort_images", "undistort_points",
            "undistort_points_scene", "timers"]
@@ -141,11 +141,6 @@ def _cam_table(cams):
     return tab
 
 
-def _host_chk(L, rc):
-    if rc != 0:
-        raise ValueError(L.lt_fn_undist_host_error().decode(errors="replace"))
-
-
 def _points_raw(cams, xy, src_idx, dst_idx, host=False, device=0, n_threads=0):
     """-> (out (N, 2), status (N,), iters (N,)): point i through CamFromImg of cams[src_idx[i]] and ImgFromCam of
     cams[dst_idx[i]]"""
@@ -159,35 +154,19 @@ def _points_raw(cams, xy, src_idx, dst_idx, host=False, device=0, n_threads=0):
             _p(iters, C.c_int32))
     if host:
         L = _capi.load_library()
-        _host_chk(L, L.lt_fn_undist_points_host(*args, int(n_threads)))
+        if L.lt_fn_undist_points_host(*args, int(n_threads)) != 0:
+            _native.raise_host_error(L, "lt_fn_undist_host_error")
     else:
         ctx = _context(device)
         ctx.chk(ctx.L.lt_undist_points(ctx.h, *args))
     return out[:n], status[:n], iters[:n]
 
 
-def _is_torch(x):
-    return type(x).__module__.split(".")[0] == "torch"
-
-
-def _sync_torch(device):
-    """the context's stream does not wait for torch's streams: a tensor torch has just written must be finished before
-    the warp reads it, and the outputs allocated before it writes them"""
-    import torch
-    torch.cuda.synchronize(device)
-
-
 def _check_image(img):
-    """-> (h, w, channels) of a uint8 image (H, W) or (H, W, C)"""
-    if _is_torch(img):
-        import torch
-        if img.dtype != torch.uint8:
-            raise ValueError(f"undistortion: an image must be uint8, got {img.dtype}")
-        shape = tuple(img.shape)
-    else:
-        if img.dtype != np.uint8:
-            raise ValueError(f"undistortion: an image must be uint8, got {img.dtype}")
-        shape = img.shape
+    """-> (h, w, channels) of a uint8 image (H, W) or (H, W, C), an array or a tensor"""
+    if str(img.dtype).split(".")[-1] != "uint8":
+        raise ValueError(f"undistortion: an image must be uint8, got {img.dtype}")
+    shape = tuple(img.shape)
     if len(shape) not in (2, 3) or shape[0] < 1 or shape[1] < 1:
         raise ValueError(f"undistortion: an image must be (H, W) or (H, W, C) with H, W >= 1, got shape {shape}")
     ch = 1 if len(shape) == 2 else shape[2]
@@ -197,18 +176,10 @@ def _check_image(img):
 
 
 def _rows(img, ch):
-    """an image whose pixels are ch contiguous bytes and whose rows are a stride apart: (the image, row stride)"""
-    if _is_torch(img):
-        st = img.stride()
-        ok = st[1] == ch and (img.dim() == 2 or st[2] == 1) and st[0] >= img.shape[1] * ch
-        if not ok:
-            img = img.contiguous()
-        return img, img.stride(0)
+    """the Operand of an image whose pixels are ch contiguous bytes and whose rows are a stride apart"""
     st = img.strides
     ok = st[1] == ch and (img.ndim == 2 or st[2] == 1) and st[0] >= img.shape[1] * ch
-    if not ok:
-        img = np.ascontiguousarray(img)
-    return img, img.strides[0]
+    return img if ok else img.contiguous()
 
 
 def _warp_batch(items, host=False, device=0, max_chunk_bytes=1 << 30, n_threads=0):
@@ -223,24 +194,16 @@ def _warp_batch(items, host=False, device=0, max_chunk_bytes=1 << 30, n_threads=
             raise RuntimeError(_SIZE_MSG)
         if ct.h() < 1 or ct.w() < 1:
             raise ValueError("undistortion: image size below 1")
-        back = None
-        if _is_torch(img):
-            if img.is_cuda and not host:
-                if img.device.index != device:
-                    raise ValueError(f"undistortion: the tensor lives on {img.device}, the call runs on device {device}")
-                import torch
-                src, stride = _rows(img, ch)
-                out = torch.empty((ct.h(), ct.w()) + tuple(img.shape[2:]), dtype=torch.uint8, device=img.device)
-                recs.append((k, src, stride, out, out.stride(0), 1, cs, ct, ch))
-                outs[k] = out
-                on_gpu.append(k)
-                continue
-            back = img.device
-            img = img.detach().cpu().numpy()
-        src, stride = _rows(img, ch)
-        out = np.zeros((ct.h(), ct.w()) + img.shape[2:], np.uint8)
-        recs.append((k, src, stride, out, out.strides[0], 0, cs, ct, ch))
-        outs[k] = (out, back)
+        src = _rows(_native.operand(img, host=host, device=device, who="undistortion", what="the tensor"), ch)
+        if src.on_device:
+            import torch
+            out = torch.empty((ct.h(), ct.w()) + src.shape[2:], dtype=torch.uint8, device=img.device)
+            outs[k] = out
+            on_gpu.append(k)
+        else:
+            out = np.zeros((ct.h(), ct.w()) + src.shape[2:], np.uint8)
+            outs[k] = (out, img.device if _native.is_torch(img) else None)
+        recs.append((k, src, src.strides[0], out, ct.w() * ch, src.on_device, cs, ct, ch))
     for kind in (0, 1):
         group = [r for r in recs if r[5] == kind]
         n = 0
@@ -262,18 +225,18 @@ def _warp_batch(items, host=False, device=0, max_chunk_bytes=1 << 30, n_threads=
                         rows[c.key()] = len(tab_cams)
                         tab_cams.append(c)
                 a = arr[j]
-                a.src = src.data_ptr() if dev else src.ctypes.data
-                a.dst = out.data_ptr() if dev else out.ctypes.data
+                a.src, a.dst = src.address, _native.address(out)
                 a.src_stride, a.dst_stride = sst, ost
                 a.src_w, a.src_h, a.dst_w, a.dst_h = cs.w(), cs.h(), ct.w(), ct.h()
                 a.channels, a.src_cam, a.dst_cam, a.on_device = ch, rows[cs.key()], rows[ct.key()], dev
             tab = _cam_table(tab_cams)
             if host:
                 L = _capi.load_library()
-                _host_chk(L, L.lt_fn_undist_warp_host(len(tab_cams), tab, m - n, arr, int(n_threads)))
+                if L.lt_fn_undist_warp_host(len(tab_cams), tab, m - n, arr, int(n_threads)) != 0:
+                    _native.raise_host_error(L, "lt_fn_undist_host_error")
             else:
                 if kind:
-                    _sync_torch(device)
+                    _native.wait_for_torch(device)
                 ctx = _context(device)
                 ctx.chk(ctx.L.lt_undist_warp(ctx.h, len(tab_cams), tab, m - n, arr))
             stats["warp_calls"] += 1
@@ -322,7 +285,7 @@ def undistort_camera(camera, host=False, device=0, blank_pixels=0.0, min_scale=0
     L = _capi.load_library()
     fx, fy, cx, cy = target.params
     if L.lt_fn_undist_scale(w, h, cx, cy, _p(ext), blank_pixels, min_scale, max_scale, _p(res)) != 0:
-        raise ValueError(f"undistortion: camera {camera.camera_id}: " + L.lt_fn_undist_host_error().decode(errors="replace"))
+        _native.raise_host_error(L, "lt_fn_undist_host_error", f"undistortion: camera {camera.camera_id}: ")
     return Camera("PINHOLE", [fx, fy, res[2], res[3]], camera.camera_id, (int(res[1]), int(res[0])))
 
 
@@ -351,8 +314,7 @@ def _read(path):
 
 
 def _write(path, img):
-    if _is_torch(img):
-        img = img.detach().cpu().numpy()
+    img = _native.to_host(img)
     _pil().fromarray(img[:, :, 0] if img.ndim == 3 and img.shape[2] == 1 else img).save(path)
 
 
@@ -394,12 +356,13 @@ def undistort_images(cameras, images, output_dir=None, host=False, device=0, max
             raise ValueError(f"undistortion: image {i} has no camera")
         loaded[i] = _read(images[i]) if _is_path(images[i]) else images[i]
         _check_image(loaded[i])
+        _native.check_device(loaded[i], host=host, device=device, who="undistortion", what="the tensor")
     cache, cams_out, imgs_out, items, item_ids, plans = {}, {}, {}, [], [], {}
     for i in ids:
         cam = cameras[i]
         if cam.IsUndistorted():
             cams_out[i] = _as_upstream_returns(cam)
-            imgs_out[i] = loaded[i].clone() if _is_torch(loaded[i]) else np.array(loaded[i])
+            imgs_out[i] = loaded[i].clone() if _native.is_torch(loaded[i]) else np.array(loaded[i])
             continue
         src, target, rotated = _plan(cam, loaded[i], cache, host, device)
         plans[i] = (target, rotated)
@@ -469,7 +432,4 @@ def undistort_points_scene(points_by_image, dist_cameras, undist_cameras, host=F
 def timers(device=0):
     """lt_undist_get_timers of the last device call: host ms of validation + upload, device ms of the kernel, host ms
     of the download; its work units (runs of 4 target pixels) or points"""
-    out = np.zeros(4)
-    ctx = _context(device)
-    ctx.chk(ctx.L.lt_undist_get_timers(ctx.h, _p(out)))
-    return out
+    return _context(device).module_timers("lt_undist_get_timers", 4)

@@ -20,7 +20,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _capi
+from . import _capi, _native
 from .structures import lines2d_array
 
 __all__ = ["VPTrack", "MergeVPTracksByDirection", "GlobalVPTrackConstructorConfig", "GlobalVPTrackConstructor", "VPResult", "BaseVPDetectorConfig", "BaseVPDetectorOptions", "DefaultVPDetectorOptions", "JLinkageConfig",
@@ -115,14 +115,6 @@ def _cfg(cfg):
     return cfg if isinstance(cfg, BaseVPDetectorConfig) else BaseVPDetectorConfig(cfg)
 
 
-def _csr(parts):
-    off = np.zeros(len(parts) + 1, np.int64)
-    for k, a in enumerate(parts):
-        off[k + 1] = off[k] + a.shape[0]
-    flat = np.ascontiguousarray(np.concatenate(parts, 0), np.float64) if off[-1] else np.zeros((1, 4))
-    return off, flat
-
-
 def _split(off, labels, vp_off, vps, clusters, want_clusters):
     out = []
     for m in range(len(off) - 1):
@@ -136,7 +128,7 @@ def _detect(lines_list, cfg, device=0, clusters=False):
     if not lines_list:
         return []
     ctx = _context(device)
-    off, flat = _csr(lines_list)
+    off, flat = _native.csr(lines_list, 4)
     st = cfg._struct()
     n_vps = C.c_int64(0)
     ctx.chk(ctx.L.lt_vp_detect(ctx.h, len(lines_list), _p(off, C.c_int64), _p(flat), C.byref(st), C.byref(n_vps)))
@@ -152,7 +144,7 @@ def _detect_host(lines_list, cfg, n_threads=0, clusters=False):
     if not lines_list:
         return []
     L = _capi.load_library()
-    off, flat = _csr(lines_list)
+    off, flat = _native.csr(lines_list, 4)
     st = cfg._struct()
     cap = int(sum(a.shape[0] // 3 for a in lines_list)) + 1
     labels = np.zeros(max(int(off[-1]), 1), np.int32)
@@ -205,10 +197,7 @@ def detect_vps_host(all_2d_lines, cfg=None, n_threads=0):
 def timers(device=0):
     """lt_vp_get_timers of the last device call: host ms of upload + length filter, kernels, download, host tail; device
     ms of the preference kernel and of the clustering kernel"""
-    out = np.zeros(6)
-    ctx = _context(device)
-    ctx.chk(ctx.L.lt_vp_get_timers(ctx.h, _p(out)))
-    return out
+    return _context(device).module_timers("lt_vp_get_timers", 6)
 
 
 class BaseVPDetector:
