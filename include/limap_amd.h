@@ -1333,6 +1333,65 @@ double lt_fn_est_log(double x);
 int lt_fn_est_probabilities(const double ratios2[2], const uint32_t its4[4], const int32_t flags4[4], int32_t n_pts,
                             int32_t n_lines, uint32_t min_it, double prior4[4], double prob4[4]);
 
+/* ---- 2D-3D line matching for localization: optimize/hybrid_localization/functions.py as
+ * runners/hybrid_localization.py:277-340 runs it, for Q queries in one set of launches.  A pair (query line i, database
+ * line j) of a task (query q, retrieved database image d) survives if compute_epipolar_IoU(l_i, view_q, l_j, view_d) >
+ * IoU_threshold (strict: a NaN fails) and db_track[j] != -1.  mode 0 (all_pairs, the "epipolar" matcher) tests every
+ * (i, j) of every task; mode 1 (listed) takes the pairs per task from pairs2 and applies only the track lookup; mode 2
+ * (listed_filtered, epipolar_filter) puts the listed pairs through the IoU test too.  Rows come in upstream's order:
+ * query lines in the order of their first survivor (task position, then i * n_d + j or the position in the list), a
+ * line's rows in that order too, duplicates kept.  filter 1 Perpendicular, 2 Midpoint, 3 Midpoint_Perpendicular is
+ * reprojection_filter_matches_2to3: at most one (line, best track) per line, the strict minimum of the loss over the
+ * line's distinct tracks in ascending id order. ---- */
+typedef struct lt_l23_config {
+  int32_t mode;         /* 0 */
+  int32_t filter;       /* 0: none */
+  double IoU_threshold; /* 0.2 (cfgs/localization/default.yaml) */
+  double dist_thres;    /* 10 (the function's default; the runner passes 2) */
+  double sine_thres;    /* 0.4 */
+  double angle_scale;   /* 1 */
+} lt_l23_config;
+void lt_l23_config_default(lt_l23_config *cfg);
+/* The scene as flat arrays.  Database images: db_cam11[n_db][11] (kvec, qvec, tvec), their segments [db_seg_off[d],
+ * db_seg_off[d + 1]) of db_seg4 and db_track (the track of each segment, -1: none).  Queries: q_cam11 (the coarse pose),
+ * q_seg_off, q_seg4.  Tasks: query q owns [task_off[q], task_off[q + 1]) of task_db, the database image rows in
+ * retrieval order (a row may repeat, a query may have none).  Listed modes: task t owns [pair_off[t], pair_off[t + 1])
+ * of pairs2 (query line, database line); NULL in mode 0.  track6[n_tracks][6]: start and end of every track's line
+ * (read only with a filter).  Refused with LT_ERR_ARGUMENT and the offending index: offsets that do not ascend,
+ * non-finite cameras, segments or tracks, an image row or a line index out of range, a track id >= n_tracks or < -1,
+ * any count above 2^31 - 1, more than 2^31 - 1 (task, query line) units or rows in one call. */
+typedef struct lt_l23_input {
+  int64_t n_db;
+  const double *db_cam11;
+  const int64_t *db_seg_off;
+  const double *db_seg4;
+  const int32_t *db_track;
+  int64_t n_query;
+  const double *q_cam11;
+  const int64_t *q_seg_off;
+  const double *q_seg4;
+  const int64_t *task_off;
+  const int32_t *task_db;
+  const int64_t *pair_off;
+  const int32_t *pairs2;
+  int64_t n_tracks;
+  const double *track6;
+} lt_l23_input;
+int lt_l23_match(lt_ctx *ctx, const lt_l23_input *in, const lt_l23_config *cfg);
+/* rows of the last lt_l23_match */
+int64_t lt_l23_num(lt_ctx *ctx);
+/* of the last lt_l23_match (any pointer may be NULL): q_off[Q + 1], rows2[rows][2] = (query line, track id),
+ * loss[rows] = the winning loss (with a filter; zeros without) */
+int lt_l23_get(lt_ctx *ctx, int64_t *q_off, int32_t *rows2, double *loss);
+/* host ms of [0] validation and upload, [1] the launches, [2] download; device ms (HIP events) of [3] the records,
+ * [4] the count pass or the listed pairs' flags, [5] the scan, [6] the fill, [7] the filter and its compaction */
+int lt_l23_get_timers(lt_ctx *ctx, double out[8]);
+/* The same definition in plain C++ from the same inline functions: bit-identical results; OpenMP over queries and
+ * lines.  The result stays with the calling thread: *n_rows says how many rows lt_fn_l23_host_get then copies. */
+int lt_fn_l23_host(const lt_l23_input *in, const lt_l23_config *cfg, int host_threads, int64_t *n_rows);
+int lt_fn_l23_host_get(int64_t *q_off, int32_t *rows2, double *loss);
+const char *lt_fn_l23_host_error(void);
+
 /* ---- Bundle adjustment with free poses, points and lines: limap.optimize's
  * solve_hybrid_bundle_adjustment / solve_point_bundle_adjustment, HybridBAEngine with constant intrinsics.  Every image
  * that carries a residual block is a parameter (quaternion and translation), every point track (3 unknowns) and every

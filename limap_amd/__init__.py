@@ -8,7 +8,7 @@ and a HIP device must be visible; there is no CPU fallback.
 """
 from . import base, synthetic  # noqa: F401
 
-__all__ = ["base", "synthetic", "triangulation", "evaluation", "structures", "vplib", "optimize", "estimators", "pointsfm", "undistortion", "line2d", "build", "warmup"]
+__all__ = ["base", "synthetic", "triangulation", "evaluation", "structures", "vplib", "optimize", "estimators", "localization", "pointsfm", "undistortion", "line2d", "build", "warmup"]
 
 
 def warmup(n_views=100, n_segs=500, n_neighbors=20, topk=10, device=None):
@@ -49,7 +49,7 @@ def warmup(n_views=100, n_segs=500, n_neighbors=20, topk=10, device=None):
 
 
 def __getattr__(name):  # lazy: importing the package must not require the GPU library
-    if name in ("triangulation", "build", "_capi", "dist", "io", "evaluation", "structures", "vplib", "optimize", "estimators", "pointsfm", "undistortion", "line2d"):
+    if name in ("triangulation", "build", "_capi", "dist", "io", "evaluation", "structures", "vplib", "optimize", "estimators", "localization", "pointsfm", "undistortion", "line2d"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

@@ -242,6 +242,16 @@ def get_all_lines_2d(all_2d_segs):
             for i, segs in all_2d_segs.items()}
 
 
+def get_invert_idmap_from_linetracks(all_lines_2d, linetracks):
+    """base/functions.py:48-70: dict img_id -> per 2D line the index of its track, -1 where it has none.  Tracks are
+    entered in order, so a line that two tracks name keeps the later one."""
+    idmap = {img_id: [-1] * len(lines) for img_id, lines in all_lines_2d.items()}
+    for track_id, track in enumerate(linetracks):
+        for img_id, line_id in zip(track.image_id_list, track.line_id_list):
+            idmap[img_id][line_id] = track_id
+    return idmap
+
+
 class LineLinker3d:
     """base/line_linker.h:168-185 as far as the path needs it: a holder of the 3D linker configuration (dict of
     cfg["triangulation"]["remerging"]["linker3d"]); `limap_amd.merging.remerge` reads the fields."""

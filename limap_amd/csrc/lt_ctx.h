@@ -311,6 +311,17 @@ struct EsState {  // minimal pose solvers (lt_est.cpp): the result of the last l
   DevBuf d_qs, d_st, d_ltab, d_ids, d_r2, d_lists, d_blk, d_ints, d_rposes, d_rscores, d_rints, d_trace, d_done;
 };
 
+struct L23State {  // 2D-3D line matching (lt_l23.cpp): the result of the last lt_l23_match
+  double timers[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // lt_l23_get_timers
+  std::vector<long long> q_off;                 // per query its rows
+  std::vector<int> rows;                        // (query line, track id) per row
+  std::vector<double> loss;                     // with a filter: the winning loss per row
+  DevBuf d_db_cam11, d_q_cam11, d_db_seg4, d_q_seg4, d_track6, d_db_seg_off, d_q_seg_off, d_task_off, d_unit_off, d_pair_off,
+      d_task_db, d_task_q, d_db_track, d_pairs, d_db_cam, d_q_cam, d_db_rec, d_task_F, d_count, d_unit_pos, d_first, d_tot,
+      d_kl_line, d_kl_start, d_kl_cnt, d_q_total, d_q_row0, d_rows, d_keep, d_win_track, d_win_loss, d_out_rows, d_out_loss,
+      d_out_cnt;
+};
+
 struct SfmState {  // visual neighbours (lt_sfm.cpp): the result of the last lt_sfm_neighbors
   double timers[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // lt_sfm_get_timers
   std::vector<long long> nb_off;                // per image its neighbours (image indices)
@@ -590,6 +601,7 @@ struct lt_ctx {
   lt_host::BaState ba;
   lt_host::AsState as;
   lt_host::EsState es;
+  lt_host::L23State l23;
   lt_host::SfmState sf;
   lt_host::UdState ud;
   lt_host::S2State s2;

@@ -171,28 +171,6 @@ static __device__ __forceinline__ bool sensitivity_gt(const GenCfg &cfg, const C
   return 90 - acos(cv) * 180.0 / kPi > cfg.sens_th;
 }
 
-// compute_epipolar_IoU (functions.cc:76-98) with the fundamental matrix hoisted per image pair
-static __device__ __forceinline__ double epipolar_iou(const Seg &s1, const Seg &s2, const double *F) {
-  L2 l2{mk2(s2.x1, s2.y1), mk2(s2.x2, s2.y2)};
-  double ln2 = len(l2);
-  d3 lc2 = mk3(s2.lc[0], s2.lc[1], s2.lc[2]);
-  d3 eps = unit(mv(F, mk3(s1.x1, s1.y1, 1.0)));
-  d3 hs = cross(lc2, eps);
-  double zs = hs.z + kEps;
-  d2 cs = d2{hs.x / zs, hs.y / zs};
-  d3 epe = unit(mv(F, mk3(s1.x2, s1.y2, 1.0)));
-  d3 he = cross(lc2, epe);
-  double ze = he.z + kEps;
-  d2 ce = d2{he.x / ze, he.y / ze};
-  d2 dv = dir(l2);
-  double c1v = dot(sub(cs, l2.s), dv) / ln2;
-  double c2v = dot(sub(ce, l2.s), dv) / ln2;
-  if (c1v > c2v) {
-    double t = c1v; c1v = c2v; c2v = t;
-  }
-  return (dmin(c2v, 1.0) - dmax(c1v, 0.0)) / (dmax(c2v, 1.0) - dmin(c1v, 0.0));
-}
-
 // line_triangulation (functions.cc:194-233): x = (A^-1 B)[0], A = [c1 | -c2s | -c2e]
 static __device__ __forceinline__ bool tri_line(const Cam &c1, const Cam &c2, const Seg &s1, const Seg &s2,
                                                 const double *Bv, d3 *ps_o, d3 *pe_o, double *z_start,

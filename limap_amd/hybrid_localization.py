@@ -29,6 +29,20 @@ __all__ = ["LineLocConfig", "TrivialLoss", "HuberLoss", "SoftLOneLoss", "CauchyL
            "LineLocEngine", "JointLocEngine", "solve_lineloc_merged", "solve_jointloc_merged", "solve_jointloc",
            "solve_lineloc", "solve_jointloc_batch", "score_poses", "pl_estimate_absolute_pose", "CameraPose", "LOC_TERMINATION"]
 
+# optimize/hybrid_localization/functions.py lives in this package upstream: the 2D-3D matching of limap_amd.localization
+# is re-exported from here, on first use (that module imports this one)
+_FUNCTIONS = ("match_line_2to2_epipolarIoU", "filter_line_2to2_epipolarIoU", "match_line_2to3", "midpoint_dist",
+              "midpoint_perpendicular_dist", "perpendicular_dist", "get_reprojection_dist_func",
+              "reprojection_filter_matches_2to3")
+__all__ += list(_FUNCTIONS)
+
+
+def __getattr__(name):
+    if name in _FUNCTIONS:
+        from . import localization
+        return getattr(localization, name)
+    raise AttributeError(name)
+
 LOC_TERMINATION = {0: "max_num_iterations", 1: "radius", 2: "zero_gradient", 3: "pivot", 4: "model_decrease",
                    6: "evaluation_failed", 7: "no_residuals"}
 
